@@ -24,6 +24,8 @@ same with a first batch of 8 sentences), `fp32` repeats a few steps with the par
 934-frame chunk: 32 Euler steps of the DiT + BigVGAN), `cold_prompt` the reference-audio front-end (WAV -> HuBERT -> codes,
 spectrogram) that precedes a first utterance.
 `cpu_baseline` = the oracle (CPU restatement, kind "port") on a bounded sample of the same workload on this box's host cores.
+`--dump-outputs DIR` writes the audio the last timed step returned as DIR/audio.npy (float32; seeded inputs, so two builds can
+be compared output for output).
 """
 from __future__ import annotations
 
@@ -288,6 +290,25 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_MAX_BYTES = 64_000_000 - 4096          # all .npy files together, headers included
+
+
+def dump_outputs(out_dir: str, audio: np.ndarray) -> dict:
+    """--dump-outputs: what the timed path returned in its last step -- the job's int16 audio, every fragment in submission
+    order -- as DIR/audio.npy in float32 (exact for int16).  Larger than the budget (weak scaling over many GPUs, or
+    --total-utterances): a fixed, seeded, sorted sample of positions, their values in audio.npy and the positions
+    themselves in audio_index.npy (float64, exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    a = np.asarray(audio).reshape(-1)
+    if a.size * 4 <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "audio.npy"), a.astype(np.float32))
+        return {"audio": int(a.size)}
+    idx = np.unique(np.random.default_rng(0).integers(0, a.size, size=DUMP_MAX_BYTES // 12))   # 4 B value + 8 B position
+    np.save(os.path.join(out_dir, "audio.npy"), a[idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "audio_index.npy"), idx.astype(np.float64))
+    return {"audio": int(idx.size), "audio_index": int(idx.size), "sampled_from": int(a.size)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -302,7 +323,11 @@ def main():
                     help="BASELINE configs[2]: utterances per step over the whole job, in batches of --batch (0 = --batch per GPU)")
     ap.add_argument("--no-extras", action="store_true", help="skip the fp32 / v3 / cold-prompt sub-records")
     ap.add_argument("--pyprofile", action="store_true", help="cProfile one extra step (host-side hot spots)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the audio the last timed step returned (rank 0) as DIR/<name>.npy, float32, <= 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -400,6 +425,8 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     elapsed = float(tmax.item())
     audio_s = float(tot_tokens.item()) * 0.04            # 25 Hz semantic tokens (TTS.py:349)
+    if rank == 0 and args.dump_outputs:
+        log(f"outputs of the last timed step -> {args.dump_outputs}: {dump_outputs(args.dump_outputs, out)}")
 
     if rank == 0:
         # --- stage breakdown of the last step (reference prints the same four numbers, TTS.py:1320)

@@ -13,7 +13,8 @@
   tests/golden/mel_v3.npz / mel_v4.npz  the reference's `mel_spectrogram_torch` (module/mel_processing.py:93-143) with the v3 /
                               v4 `mel_fn` parameters (TTS_infer_pack/TTS.py:67-92) on seeded waveforms; librosa is not
                               installed, so the module's `librosa_mel_fn` is oracle/mel_filterbank.mel here (the filterbank
-                              matrix itself is "parity unpinned", the STFT / magnitude / matmul / log-clamp around it is pinned)
+                              matrix itself is "parity unpinned", the STFT / magnitude / matmul / log-clamp around it is pinned);
+                              `mel` in fp32, `mel_f64` the same on the float64 waveform (gen_mel)
   tests/golden/sv_eres2net.npz  the reference's Kaldi fbank (eres2net/kaldi.py, pure torch) and ERes2NetV2(baseWidth=24, scale=4,
                               expansion=4).forward3 (eres2net/ERes2NetV2.py) -- what SV.compute_embedding3 (sv.py:24-32) runs --
                               on gsv.synthetic.make_eres2net_state_dict weights and a seeded 3 s waveform at 16 kHz
@@ -37,6 +38,26 @@ SPEC_CASES = {"spec_32k_half_s": (16000, 0), "spec_32k_ragged": (22001, 1), "spe
 BERT_TEXT = "你好，我是小明。今天天气不错，我们一起去公园散步吧！"
 SV_N = 48000             # 3 s at 16 kHz -> 298 fbank frames
 HUBERT_N = 20800          # 1.3 s at 16 kHz -> 64 frames
+
+
+def gen_mel():
+    """mel_v3 / mel_v4: `mel` in fp32 (what the product computes in), `mel_f64` the same function on the float64 waveform (the
+    module casts its basis and window to the input dtype).  Near the log clamp fp32 is only good to ~1e-5, so the oracle is
+    compared against `mel_f64`, where another CPU's FFT / GEMM kernels change nothing at that scale."""
+    ref_import.setup()
+    import module.mel_processing as mp
+    from oracle import mel_filterbank
+    mp.librosa_mel_fn = mel_filterbank.mel
+    for name, kw, n, seed in (("mel_v3", dict(n_fft=1024, win_size=1024, hop_size=256, num_mels=100, sampling_rate=24000, fmin=0,
+                                             fmax=None, center=False), 36000, 3),
+                              ("mel_v4", dict(n_fft=1280, win_size=1280, hop_size=320, num_mels=100, sampling_rate=32000, fmin=0,
+                                             fmax=None, center=False), 41003, 4)):
+        y = S.make_waveform(n, seed, sr=kw["sampling_rate"]).unsqueeze(0)
+        m = mp.mel_spectrogram_torch(y, **kw)
+        m64 = mp.mel_spectrogram_torch(y.double(), **kw)
+        np.savez_compressed(os.path.join(GOLD, name + ".npz"), mel=m.numpy().astype(np.float32),
+                            mel_f64=m64.numpy().astype(np.float64))
+        print(name, tuple(m.shape), float(m.min()), float(m.max()), "fp32 vs fp64", float((m.double() - m64).abs().max()))
 
 
 def main():
@@ -78,17 +99,7 @@ def main():
         spec = spectrogram_torch(y, 2048, 32000, 640, 2048, center=False)
         np.savez_compressed(os.path.join(GOLD, name + ".npz"), spec=spec.numpy().astype(np.float32))
         print(name, tuple(spec.shape), float(spec.max()))
-    import module.mel_processing as mp
-    from oracle import mel_filterbank
-    mp.librosa_mel_fn = mel_filterbank.mel
-    for name, kw, n, seed in (("mel_v3", dict(n_fft=1024, win_size=1024, hop_size=256, num_mels=100, sampling_rate=24000, fmin=0,
-                                             fmax=None, center=False), 36000, 3),
-                              ("mel_v4", dict(n_fft=1280, win_size=1280, hop_size=320, num_mels=100, sampling_rate=32000, fmin=0,
-                                             fmax=None, center=False), 41003, 4)):
-        y = S.make_waveform(n, seed, sr=kw["sampling_rate"]).unsqueeze(0)
-        m = mp.mel_spectrogram_torch(y, **kw)
-        np.savez_compressed(os.path.join(GOLD, name + ".npz"), mel=m.numpy().astype(np.float32))
-        print(name, tuple(m.shape), float(m.min()), float(m.max()))
+    gen_mel()
     sys.path.insert(0, os.path.join(ref_import.REF_ROOT, "GPT_SoVITS", "eres2net"))
     import kaldi as Kaldi
     from ERes2NetV2 import ERes2NetV2

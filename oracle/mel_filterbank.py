@@ -47,12 +47,13 @@ def mel(sr: int, n_fft: int, n_mels: int = 128, fmin: float = 0.0, fmax=None) ->
 
 def mel_spectrogram(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center=False):
     """reference module/mel_processing.py:93-143 on the CPU: reflect padding (n_fft - hop) / 2, torch.stft with a periodic Hann
-    window, sqrt(re^2 + im^2 + 1e-8), filterbank matmul, log(clamp(min=1e-5)).  y [1, n] fp32 -> [1, num_mels, frames]."""
+    window, sqrt(re^2 + im^2 + 1e-8), filterbank matmul, log(clamp(min=1e-5)).  y [1, n] fp32 -> [1, num_mels, frames]; basis and
+    window take y's dtype, as in the reference (float64 y: the whole chain in float64)."""
     import torch
-    basis = torch.from_numpy(mel(sampling_rate, n_fft, num_mels, fmin, fmax))
+    basis = torch.from_numpy(mel(sampling_rate, n_fft, num_mels, fmin, fmax)).to(y.dtype)
     p = int((n_fft - hop_size) / 2)
     y = torch.nn.functional.pad(y.unsqueeze(1), (p, p), mode="reflect").squeeze(1)
-    spec = torch.stft(y, n_fft, hop_length=hop_size, win_length=win_size, window=torch.hann_window(win_size), center=center,
+    spec = torch.stft(y, n_fft, hop_length=hop_size, win_length=win_size, window=torch.hann_window(win_size).to(y.dtype), center=center,
                       pad_mode="reflect", normalized=False, onesided=True, return_complex=True)
     spec = torch.sqrt(spec.real.pow(2) + spec.imag.pow(2) + 1e-8)
     return torch.log(torch.clamp(torch.matmul(basis, spec), min=1e-5))

@@ -167,6 +167,8 @@ struct ConvArgs {
   int vt_col0 = 0, vt_ld = 0;
   const float* rope_cs = nullptr;            // [T][rope_half][2] cos, sin
   int rope_half = 0, rope_q0 = 0, rope_k0 = 0;
+  int z_res = 0;                             // batched launch (Z > 1) whose residual has its own slice stride rz: takes the LDS GEMM
+                                             // path (bwe.hip; other batched launches with a residual keep the generic kernel)
 };
 int launch_conv_gemm(int dtype, const ConvArgs& a, hipStream_t s);
 // split-K-in-workgroup streaming GEMM for under-filled grids (gemm_sk.hip): 0 = launched, 1 = not eligible, <0 = error

@@ -584,7 +584,7 @@ template <typename T> static int try_launch_gemm(const ConvArgs& a, hipStream_t 
   }
   if (a.taps != 1 || a.stride != 1 || a.ups_u > 0 || a.accumulate || a.pad != 0) return 1;
   if (a.T_virt < 512 || a.Cout < 96 || a.Cin % (2 * G) != 0 || a.Cin < BK) return 1;
-  if (a.Z > 1 && ((a.xz % G) || (a.wz % G) || a.res)) return 1;      // batched: head slices must stay 16-byte aligned
+  if (a.Z > 1 && ((a.xz % G) || (a.wz % G) || (a.res && (!a.z_res || a.rz % G)))) return 1;   // batched: head slices must stay 16-byte aligned
   if (a.res && a.res_f32) return 1;
   if (a.ldx % G != 0 || a.ldw % G != 0 || ((uintptr_t)a.x % 16) || ((uintptr_t)a.w % 16)) return 1;
   size_t lds = (size_t)2 * (128 + 128) * (BK + G) * sizeof(T);           // 73.7 KB; epilogue tile 33.8 KB fits inside

@@ -97,13 +97,15 @@ struct PostTable {
   int len[32];
 };
 
-template <typename T>
-__global__ __launch_bounds__(1024) void postprocess_kernel(PostTable tab, int gap, short* __restrict__ out) {
+// O = short: the int16 PCM; O = float: the same fragments as fp32 before the x32768 / int16 step (what the reference's
+// super-sampling path concatenates and feeds to AP_BWE, TTS.py:1397-1417)
+template <typename T, typename O = short>
+__global__ __launch_bounds__(1024) void postprocess_kernel(PostTable tab, int gap, O* __restrict__ out) {
   __shared__ float red[16];
   __shared__ int red_nan[16];
   const T* __restrict__ x = (const T*)tab.src[blockIdx.x];
   const int n = tab.len[blockIdx.x];
-  short* __restrict__ o = out + tab.dst[blockIdx.x];
+  O* __restrict__ o = out + tab.dst[blockIdx.x];
   float peak = 0.f;
   int nan = 0;
   for (int i = threadIdx.x; i < n; i += 1024) {
@@ -123,10 +125,14 @@ __global__ __launch_bounds__(1024) void postprocess_kernel(PostTable tab, int ga
   for (int i = threadIdx.x; i < n; i += 1024) {
     T v = x[i];
     if (divide) v = (T)((float)v / (float)denom);
-    const T m = (T)((float)v * 32768.f);
-    o[i] = (short)(int)(float)m;
+    if constexpr (std::is_same<O, float>::value) {
+      o[i] = (float)v;
+    } else {
+      const T m = (T)((float)v * 32768.f);
+      o[i] = (short)(int)(float)m;
+    }
   }
-  for (int i = threadIdx.x; i < gap; i += 1024) o[n + i] = 0;
+  for (int i = threadIdx.x; i < gap; i += 1024) o[n + i] = (O)0;
 }
 
 }  // namespace gsv
@@ -183,9 +189,10 @@ extern "C" int gsv_sola(float* frags, const int* lens, int n, int overlap, float
 }
 
 
-extern "C" int gsv_postprocess(const void* const* frags, const int* lens, int n, int dtype, int gap, int16_t* out,
-                               gsv_stream_t stream) {
-  using namespace gsv;
+namespace gsv {
+
+template <typename O>
+static int postprocess_t(const void* const* frags, const int* lens, int n, int dtype, int gap, O* out, gsv_stream_t stream) {
   GSV_REQUIRE(n >= 0 && gap >= 0 && (dtype == GSV_F16 || dtype == GSV_F32), "postprocess: bad argument");
   if (n == 0) return GSV_OK;
   GSV_REQUIRE(frags && lens && out, "postprocess: null pointer");
@@ -201,9 +208,21 @@ extern "C" int gsv_postprocess(const void* const* frags, const int* lens, int n,
       tab.dst[i] = off;
       off += (long long)lens[base + i] + gap;
     }
-    if (dtype == GSV_F16) hipLaunchKernelGGL(postprocess_kernel<_Float16>, dim3(m), dim3(1024), 0, s, tab, gap, (short*)out);
-    else hipLaunchKernelGGL(postprocess_kernel<float>, dim3(m), dim3(1024), 0, s, tab, gap, (short*)out);
+    if (dtype == GSV_F16) hipLaunchKernelGGL((postprocess_kernel<_Float16, O>), dim3(m), dim3(1024), 0, s, tab, gap, out);
+    else hipLaunchKernelGGL((postprocess_kernel<float, O>), dim3(m), dim3(1024), 0, s, tab, gap, out);
     GSV_HIP(hipGetLastError());
   }
   return GSV_OK;
+}
+
+}  // namespace gsv
+
+extern "C" int gsv_postprocess(const void* const* frags, const int* lens, int n, int dtype, int gap, int16_t* out,
+                               gsv_stream_t stream) {
+  return gsv::postprocess_t<short>(frags, lens, n, dtype, gap, (short*)out, stream);
+}
+
+extern "C" int gsv_postprocess_f32(const void* const* frags, const int* lens, int n, int dtype, int gap, float* out,
+                                   gsv_stream_t stream) {
+  return gsv::postprocess_t<float>(frags, lens, n, dtype, gap, out, stream);
 }

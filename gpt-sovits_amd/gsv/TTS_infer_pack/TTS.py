@@ -204,6 +204,9 @@ class TTS:
         self._t2s_state = None
         self._vits_state = None
         self.vocoder = None
+        self.sr_model = None                 # AP_BWE super-sampling (reference TTS.py:662-670), loaded on first use
+        self.sr_model_not_exist = False
+        self._sr_source = None
         self.cnhuhbert_model = None
         self.sv_model = None
         self.bert_model = None
@@ -304,6 +307,23 @@ class TTS:
             if cfg and k in cfg:
                 self.vocoder_configs[k] = cfg[k]
 
+    def init_sr_model(self, checkpoint_file: Optional[str] = None, state: Optional[dict] = None, config: Optional[dict] = None):
+        """reference TTS.py:662-670: the AP_BWE 24k -> 48k super-sampling model behind `super_sampling` (v3).  Loads once;
+        `checkpoint_file` defaults to the reference's tools/AP_BWE_main/24kto48k/g_24kto48k.zip (relative to the working
+        directory, with config.json beside it); `state` = {"generator": state_dict} plus `config` replace the file for tests.
+        The engine dtype follows configs.is_half like every other engine here (the reference keeps this model in fp32).
+        A missing checkpoint raises FileNotFoundError naming the path (the reference prints a message and fails later)."""
+        if self.sr_model is not None and checkpoint_file is None and state is None:
+            return
+        from ..tools.audio_sr import AP_BWE, DEFAULT_CHECKPOINT
+        if state is None and checkpoint_file is None and self._sr_source is not None:
+            checkpoint_file, state, config = self._sr_source
+        if state is None:
+            checkpoint_file = checkpoint_file or DEFAULT_CHECKPOINT
+        self.sr_model = AP_BWE(self.configs.device, checkpoint_file=checkpoint_file, state=state, config=config, dtype=self.precision)
+        self._sr_source = (checkpoint_file, state, config)
+        self.sr_model_not_exist = False
+
     # ---- prompt cache (replaces set_ref_audio's HuBERT/STFT front-end, TTS.py:737-819) ---------
     def set_prompt_cache(self, prompt_semantic: torch.Tensor, refer_spec: Sequence[torch.Tensor],
                          phones: Optional[List[int]] = None, bert_features: Optional[torch.Tensor] = None,
@@ -358,6 +378,8 @@ class TTS:
             self.init_vits_weights(self.configs.vits_weights_path, state=self._vits_state)
         if getattr(self, "_hubert_state", None) is not None:
             self.init_cnhuhbert_weights(state_dict=self._hubert_state)
+        if self.sr_model is not None:               # reference TTS.py:734-735 moves it; here it follows the dtype as well
+            self.sr_model.to(self.configs.device, self.precision)
         if getattr(self, "_bert_state", None) is not None:
             self.init_bert_weights(state_dict=self._bert_state[0], vocab=self._bert_state[1])
         for k in ("prompt_semantic",):
@@ -562,9 +584,10 @@ class TTS:
                           speed_factor: float = 1.0, split_bucket: bool = True, fragment_interval: float = 0.3,
                           super_sampling: bool = False) -> Tuple[int, np.ndarray]:
         """TTS.py:1377-1429: per fragment divide by its peak if the peak exceeds 1, append
-        int(sr*interval) zeros, restore order, concatenate, scale by 32768 and truncate to int16."""
-        if super_sampling:
-            raise NotImplementedError("audio super-sampling (v3 only) is out of scope")
+        int(sr*interval) zeros, restore order, concatenate, scale by 32768 and truncate to int16.
+
+        super_sampling (TTS.py:1407-1417): the same concatenation as fp32 (gsv_postprocess_f32), AP_BWE to 48 kHz, then the
+        peak rule and int16 step of gsv_postprocess on that one fragment without a gap; returns 48000."""
         import ctypes as C
         from .. import _lib
         dev = torch.device(self.configs.device)
@@ -577,13 +600,26 @@ class TTS:
         self.last_fragment_lengths = [n + gap for n in lens]                                   # used by gsv.sharding
         # one launch (`gsv_postprocess`, csrc/sola.hip): peak, division, gaps, order and the int16 conversion -- the
         # reference loops over fragments on the host with a sync each (TTS.py:1391-1396); only int16 crosses PCIe
+        code = _lib.GSV_F16 if self.precision == torch.float16 else _lib.GSV_F32
         with torch.cuda.device(dev):
-            pcm = torch.empty(sum(lens) + gap * len(lens), dtype=torch.int16, device=dev)
             ptrs = (C.c_void_p * max(len(flat), 1))(*[f.data_ptr() for f in flat])
             arr = (C.c_int * max(len(flat), 1))(*lens)
             st = torch.cuda.current_stream(dev)
-            _lib.check(_lib.lib().gsv_postprocess(ptrs, arr, len(flat), _lib.GSV_F16 if self.precision == torch.float16 else
-                                                  _lib.GSV_F32, gap, pcm.data_ptr(), C.c_void_p(st.cuda_stream)), "gsv_postprocess")
+            if super_sampling:
+                self.init_sr_model()
+                wav = torch.empty(sum(lens) + gap * len(lens), dtype=torch.float32, device=dev)
+                _lib.check(_lib.lib().gsv_postprocess_f32(ptrs, arr, len(flat), code, gap, wav.data_ptr(), C.c_void_p(st.cuda_stream)),
+                           "gsv_postprocess_f32")
+                hr = self.sr_model.forward_device(wav, sr)
+                sr = self.sr_model.config["hr_sampling_rate"]
+                pcm = torch.empty(int(hr.shape[0]), dtype=torch.int16, device=dev)
+                one_p, one_n = (C.c_void_p * 1)(hr.data_ptr()), (C.c_int * 1)(int(hr.shape[0]))
+                _lib.check(_lib.lib().gsv_postprocess(one_p, one_n, 1, _lib.GSV_F32, 0, pcm.data_ptr(), C.c_void_p(st.cuda_stream)),
+                           "gsv_postprocess")
+                return sr, self._to_host(pcm)
+            pcm = torch.empty(sum(lens) + gap * len(lens), dtype=torch.int16, device=dev)
+            _lib.check(_lib.lib().gsv_postprocess(ptrs, arr, len(flat), code, gap, pcm.data_ptr(), C.c_void_p(st.cuda_stream)),
+                       "gsv_postprocess")
         return sr, self._to_host(pcm)
 
     def _to_host(self, t: torch.Tensor) -> np.ndarray:
@@ -740,10 +776,10 @@ class TTS:
             split_bucket = False
         elif getattr(self.configs, "use_vocoder", False) and parallel_infer:
             split_bucket = False           # v3 / v4 parallel runs are never bucketed (reference TTS.py:1060-1062)
-        if inputs.get("super_sampling", False):
-            # reference TTS.py:1040, 1408-1419: AP_BWE super-sampling, a separate model that is out of scope (DESIGN.md
-            # section 7) -- refused, never silently ignored
-            raise NotImplementedError("super_sampling (AP_BWE audio super-resolution) is not part of this engine")
+        # reference TTS.py:1040, 1328, 1349: AP_BWE super-sampling applies to the v3 vocoder output only; v1 / v2 / v2Pro / v4
+        # ignore the key
+        super_sampling = bool(inputs.get("super_sampling", False)) and getattr(self.configs, "use_vocoder", False) and \
+            self.configs.version == "v3"
         try:
             if self.t2s_model is None or self.vits_model is None:
                 raise RuntimeError("init_t2s_weights / init_vits_weights first")
@@ -896,7 +932,7 @@ class TTS:
                 t5 = time.perf_counter()
                 t_45 += t5 - t4
                 if return_fragment:
-                    yield self.audio_postprocess([frags], sr, None, speed_factor, False, fragment_interval)
+                    yield self.audio_postprocess([frags], sr, None, speed_factor, False, fragment_interval, super_sampling)
                 else:
                     audio.append(frags)
                 if self.stop_flag:
@@ -908,7 +944,8 @@ class TTS:
                     yield 16000, np.zeros(16000, dtype=np.int16)
                     return
                 t6 = time.perf_counter()
-                result = self.audio_postprocess(audio, sr, batch_index_list, speed_factor, split_bucket, fragment_interval)
+                result = self.audio_postprocess(audio, sr, batch_index_list, speed_factor, split_bucket, fragment_interval,
+                                                super_sampling)
                 self.last_postprocess_s = time.perf_counter() - t6
                 yield result
         except Exception as e:

@@ -41,6 +41,10 @@ class DitConfig(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("dim", "depth", "heads", "dim_head", "ff_mult", "mel_dim", "text_dim", "conv_layers")]
 
 
+class BweConfig(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n_fft", "hop_size", "win_size", "channels", "layers", "hr_sampling_rate")]
+
+
 class ConvDesc(C.Structure):
     _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("y", C.c_void_p), ("res", C.c_void_p),
                 ("T_in", C.c_int), ("T_out", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int), ("taps", C.c_int),
@@ -102,6 +106,15 @@ _SIGS = {
                                     C.c_float, C.c_uint64, C.c_void_p, C.c_void_p]),
     "gsv_sola": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "gsv_postprocess": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "gsv_postprocess_f32": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                      C.c_void_p]),
+    "gsv_bwe_create": (C.c_int, [C.POINTER(BweConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "gsv_bwe_destroy": (None, [C.c_void_p]),
+    "gsv_bwe_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
+    "gsv_bwe_finalize": (C.c_int, [C.c_void_p]),
+    "gsv_bwe_out_len": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "gsv_bwe_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "gsv_bwe_debug_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
     "gsv_aa_act_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "gsv_op_flash_attn64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -21,10 +21,26 @@ ACT_LOGCLAMP = 10      # csrc/common.h: log(max(u, 1e-5))
 _basis: Dict[Tuple, torch.Tensor] = {}
 
 
-def _dft_basis(n_fft: int, win_size: int, device) -> torch.Tensor:
+def _dft_basis(n_fft: int, win_size: int, device, inverse: bool = False) -> torch.Tensor:
     """[2 * bins][n_fft] fp32: rows 0..bins-1 = w[n] cos(2 pi k n / N), rows bins.. = -w[n] sin(2 pi k n / N); torch.stft pads a
-    shorter window to n_fft centred (mel_processing.py passes win_size == n_fft for every reference config)."""
-    key = (n_fft, win_size, str(device))
+    shorter window to n_fft centred (mel_processing.py passes win_size == n_fft for every reference config).
+
+    inverse=True: [n_fft][2 * bins], the windowed one-sided inverse of torch.istft before its overlap-add -- column k (re) =
+    c_k w[n] cos(2 pi k n / N) / N, column bins + k (im) = -c_k w[n] sin(2 pi k n / N) / N with c_k = 2 except c_0 = c_{N/2} = 1,
+    and zero imaginary columns at DC and Nyquist (irfft ignores those parts)."""
+    key = (n_fft, win_size, str(device), inverse)
+    if inverse and key not in _basis:
+        bins = n_fft // 2 + 1
+        n = torch.arange(n_fft, dtype=torch.float64).unsqueeze(1)
+        k = torch.arange(bins, dtype=torch.float64)
+        w = _dft_basis(n_fft, win_size, "cpu")[0].double().unsqueeze(1)       # row 0 = the centred window
+        ang = 2.0 * math.pi * ((k.long() * n.long()) % n_fft).double() / n_fft
+        ck = torch.full((bins,), 2.0, dtype=torch.float64)
+        ck[0] = ck[-1] = 1.0
+        im = -torch.sin(ang) * ck * w / n_fft
+        im[:, 0] = 0.0
+        im[:, -1] = 0.0
+        _basis[key] = torch.cat([torch.cos(ang) * ck * w / n_fft, im], 1).float().to(device).contiguous()
     if key not in _basis:
         bins = n_fft // 2 + 1
         n = torch.arange(n_fft, dtype=torch.float64)

@@ -669,3 +669,85 @@ def make_bert_state_dict(seed: int = 0, layers: int = 24, hidden: int = 1024, ff
         sd[p + "output.LayerNorm.weight"] = 1.0 + hash_symmetric(p + "ln2.w", (hidden,), 0.1, seed)
         sd[p + "output.LayerNorm.bias"] = _b(p + "ln2.b", hidden, 0.1, seed)
     return sd
+
+
+# --------------------------------------------------------------------------
+# AP-BWE super-sampling model (reference tools/AP_BWE_main/models/model.py:76-147)
+# --------------------------------------------------------------------------
+# The 24k -> 48k release's config.json is not in the reference tree; these are the values it is believed to hold
+# (unverified: every engine reads them from the config.json beside the checkpoint at run time).
+BWE_24K_48K_CONFIG = {"n_fft": 1024, "hop_size": 80, "win_size": 320, "ConvNeXt_channels": 512, "ConvNeXt_layers": 8,
+                      "hr_sampling_rate": 48000}
+
+
+def small_bwe_config():
+    return {"n_fft": 256, "hop_size": 32, "win_size": 128, "ConvNeXt_channels": 64, "ConvNeXt_layers": 2, "hr_sampling_rate": 48000}
+
+
+def make_bwe_state_dict(cfg: dict, seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
+    """APNet_BWE_Model state dict (the "generator" entry of the checkpoint), keys and shapes as the reference registers them.
+    Hash weights with the reference's init statistics: Conv1d / Linear weights of std 0.02 (model.py:112-115), gamma =
+    1 / ConvNeXt_layers (:82); the three post Linears are created after that init (:109-111) and get PyTorch's default
+    bound 1 / sqrt(fan_in).  Biases and norm affines are small non-trivial values so that loading them is exercised."""
+    C, L, bins = cfg["ConvNeXt_channels"], cfg["ConvNeXt_layers"], cfg["n_fft"] // 2 + 1
+    u02 = 0.02 * math.sqrt(3.0)                 # uniform of std 0.02
+    sd = OrderedDict()
+
+    def vec(name, n, amp, base=0.0):
+        t = hash_symmetric("bwe." + name, (n,), amp, seed)
+        sd[name] = t + base if base else t
+
+    for br in ("mag", "pha"):
+        sd[f"conv_pre_{br}.weight"] = hash_symmetric(f"bwe.conv_pre_{br}.weight", (C, bins, 7), u02, seed)
+        vec(f"conv_pre_{br}.bias", C, 0.02)
+        vec(f"norm_pre_{br}.weight", C, 0.1, 1.0)
+        vec(f"norm_pre_{br}.bias", C, 0.05)
+    for br in ("mag", "pha"):
+        for i in range(L):
+            p = f"convnext_{br}.{i}."
+            sd[p + "dwconv.weight"] = hash_symmetric("bwe." + p + "dwconv.weight", (C, 1, 7), u02, seed)
+            vec(p + "dwconv.bias", C, 0.02)
+            vec(p + "norm.weight", C, 0.1, 1.0)
+            vec(p + "norm.bias", C, 0.05)
+            sd[p + "pwconv1.weight"] = hash_symmetric("bwe." + p + "pwconv1.weight", (3 * C, C), u02, seed)
+            vec(p + "pwconv1.bias", 3 * C, 0.02)
+            sd[p + "pwconv2.weight"] = hash_symmetric("bwe." + p + "pwconv2.weight", (C, 3 * C), u02, seed)
+            vec(p + "pwconv2.bias", C, 0.02)
+            vec(p + "gamma", C, 0.2 / L, 1.0 / L)
+    for br in ("mag", "pha"):
+        vec(f"norm_post_{br}.weight", C, 0.1, 1.0)
+        vec(f"norm_post_{br}.bias", C, 0.05)
+    bound = 1.0 / math.sqrt(C)
+    for nm in ("linear_post_mag", "linear_post_pha_r", "linear_post_pha_i"):
+        sd[nm + ".weight"] = hash_symmetric("bwe." + nm + ".weight", (bins, C), bound, seed)
+        vec(nm + ".bias", bins, bound)
+    return sd
+
+
+def make_bwe_input(name: str, n: int, seed: int = 1, amp: float = 0.6, lead: int = 300, tail: int = 300, gap=None) -> torch.Tensor:
+    """[1, n] test waveform for the AP-BWE engine: hash noise with `lead` / `tail` exact zeros (so that the first and last STFT
+    frames are all-zero: a reflect-padded frame of a non-zero signal is symmetric about its centre, its spectrum is real up to
+    rounding, and the phase of a bin with a negative real part is then +pi or -pi by the sign of that rounding -- a coin toss
+    between any two FFTs), and an optional all-zero stretch gap = (start, stop)"""
+    x = hash_symmetric(name, (n,), amp, seed)
+    x[:lead] = 0.0
+    if tail:
+        x[n - tail:] = 0.0
+    if gap is not None:
+        x[gap[0]:gap[1]] = 0.0
+    return x.view(1, -1)
+
+
+def make_bwe_fragments(dtype=torch.float32):
+    """the post-processing input of the super-sampling glue test: three batches of ragged fragments, some above 1 in
+    magnitude (peak-normalised), one silent; every fragment starts with exact zeros (see make_bwe_input)"""
+    batch_index_list = [[4, 0, 6], [2, 5], [1, 3]]
+    audio, k = [], 0
+    for idxs in batch_index_list:
+        row = []
+        for _ in idxs:
+            amp = [0.4, 1.7, 0.0, 0.99, 2.5, 1.0, 0.05][k % 7]
+            row.append((make_bwe_input(f"bwe_frag{k}", 600 + 137 * k, 2, 1.0, lead=300, tail=0)[0] * amp).to(dtype))
+            k += 1
+        audio.append(row)
+    return audio, batch_index_list

@@ -9,6 +9,8 @@
  *                   sampling AR/models/utils.py:140-199
  *   gsv_vits_*   <- SynthesizerTrn.decode / extract_latent, module/models.py:961-1010
  *                   (called from TTS_infer_pack/TTS.py:1271, 818; inference_webui.py:920)
+ *   gsv_bwe_*    <- tools/audio_sr.py::AP_BWE.__call__ (AP-BWE 24k -> 48k super-sampling, called from
+ *                   TTS_infer_pack/TTS.py:1407-1417 when super_sampling is requested for v3)
  *   gsv_aa_act_forward <- anti_alias_activation_cuda.forward, the reference's only native
  *                   FFI: BigVGAN/alias_free_activation/cuda/anti_alias_activation.cpp:19-22,
  *                   anti_alias_activation_cuda.cu:212-246
@@ -251,6 +253,41 @@ int gsv_sola(float* frags, const int* lens, int n, int overlap, float* out, int*
  * lens [host] n sample counts, out [dev] int16 with capacity sum(lens) + n * gap.  Asynchronous on `stream`.
  * ------------------------------------------------------------------------------------- */
 int gsv_postprocess(const void* const* frags, const int* lens, int n, int dtype, int gap, int16_t* out, gsv_stream_t stream);
+/* the same fragments, peak rule, gaps and order, written as fp32 without the x32768 / int16 step (out capacity as above): the
+ * float concatenation the reference's super-sampling path feeds to AP_BWE (TTS.py:1397-1417) */
+int gsv_postprocess_f32(const void* const* frags, const int* lens, int n, int dtype, int gap, float* out, gsv_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * AP-BWE audio super-resolution (tools/audio_sr.py::AP_BWE.__call__): torchaudio resample to hr_sampling_rate
+ * (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99; restated from its published definition, parity unpinned against the
+ * package itself), amp_pha_stft (AP_BWE_main/datasets1/dataset.py:9-27), APNet_BWE_Model.forward
+ * (AP_BWE_main/models/model.py:76-147), amp_pha_istft (dataset.py:30-37).  Every shape value comes from the checkpoint's
+ * config.json.  Tensor names = the reference state-dict keys (the "generator" dict), plus the two DFT bases the caller builds
+ * (gsv/module/mel_processing.py::_dft_basis): "dft.forward" fp32 [n_fft/2+1 re rows | n_fft/2+1 im rows][n_fft] (periodic Hann
+ * of win_size centred in n_fft) and "dft.inverse" fp32 [n_fft][n_fft/2+1 re | n_fft/2+1 im columns] (irfft / n_fft times the
+ * window; the imaginary parts of the DC and Nyquist bins ignored).
+ * ------------------------------------------------------------------------------------- */
+typedef struct gsv_bwe gsv_bwe_t;
+
+typedef struct {
+  int n_fft, hop_size, win_size;    /* 1024, 80, 320 (assumed 24k -> 48k release) */
+  int channels, layers;             /* ConvNeXt_channels 512, ConvNeXt_layers 8 */
+  int hr_sampling_rate;             /* 48000 */
+} gsv_bwe_config;
+
+int gsv_bwe_create(const gsv_bwe_config* cfg, int dtype, gsv_bwe_t** out);
+void gsv_bwe_destroy(gsv_bwe_t* h);
+int gsv_bwe_load_tensor(gsv_bwe_t* h, const char* name, const float* data, int64_t numel);
+int gsv_bwe_finalize(gsv_bwe_t* h);
+/* output samples of a forward over n input samples at orig_sr: hop * floor(n_new / hop), n_new = ceil(n * hr / orig_sr)
+ * (torch.istft with center=True and no length); -1 when the input is too short to reflect-pad by n_fft / 2 */
+int gsv_bwe_out_len(gsv_bwe_t* h, int n, int orig_sr);
+/* wav [dev] [n] of dtype (GSV_F16 / GSV_F32) at orig_sr -> out [dev] fp32 [gsv_bwe_out_len(h, n, orig_sr)] at hr_sampling_rate.
+ * The workspace grows on demand; GSV_ERR_ARG when the resampled input has n_fft / 2 samples or fewer. */
+int gsv_bwe_forward(gsv_bwe_t* h, const void* wav, int n, int dtype, int orig_sr, float* out, gsv_stream_t stream);
+/* test hook: a stage of the last forward into out [dev] fp32: "resampled" [n_new], "log_amp", "pha", "mag_wb", "pha_wb"
+ * channels-first [n_fft/2+1][frames] (the reference's [1, bins, T] tensors); element count via *numel */
+int gsv_bwe_debug_tensor(gsv_bwe_t* h, const char* name, float* out, int64_t cap, int64_t* numel, gsv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * BigVGAN anti-aliased snake activation (v3 vocoder), the reference's one native kernel.

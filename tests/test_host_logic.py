@@ -341,3 +341,28 @@ def test_tts_config_dict_yaml_and_defaults(tmp_path):
                                         "cnhuhbert_base_path"}
     with pytest.raises(NotImplementedError):
         TTS_Config({"version": "v9"})
+
+
+def test_localisation_check_finds_one_bad_window():
+    """tests/_parity.py::check_localised (used by the bench-shape GPU tests): fp16-size noise spread evenly passes; 1 % extra
+    error confined to ONE window of 2048 samples fails, although the global relative RMS (0.16 %) stays far inside a 5 %
+    bar; so does an error large enough in one window, whatever the others do."""
+    from _parity import check_localised, rel_rms, window_rel_rms
+    rng = np.random.default_rng(0)
+    ref = rng.standard_normal((1, 1, 64 * 2048 + 700))                    # a ragged last window, as at the bench's lengths
+    out = ref + 1e-3 * rng.uniform(-1, 1, ref.shape) * np.sqrt(3)        # relative rms 1e-3 everywhere
+    assert len(window_rel_rms(out, ref, 2048)) == 65
+    worst, med, _, n = check_localised(out, ref, 2048, 0.05, 4.0, "uniform noise")
+    assert n == 65 and worst / med < 1.5
+    bad = out.copy()
+    bad[..., 17 * 2048:18 * 2048] += 1e-2 * ref[..., 17 * 2048:18 * 2048]
+    assert rel_rms(bad, ref) < 0.002
+    with pytest.raises(AssertionError, match="window 17"):
+        check_localised(bad, ref, 2048, 0.05, 4.0, "one bad window")
+    tail = out.copy()
+    tail[..., -700:] += 0.2 * ref[..., -700:]                            # only the short last window is broken
+    with pytest.raises(AssertionError, match="window 64"):
+        check_localised(tail, ref, 2048, 0.05, 4.0, "bad tail")
+    mel = rng.standard_normal((1, 100, 466))
+    with pytest.raises(AssertionError, match="window 3"):
+        check_localised(mel + np.where(np.arange(466) // 32 == 3, 0.02, 1e-3) * mel, mel, 32, 0.03, 4.0, "mel")

@@ -70,10 +70,21 @@ def _noise_fn(call, shape):
     return S.hash_normal(f"v3_cfm_noise{call}", shape, 1)
 
 
-@pytest.mark.parametrize("version", ["v3", "v4"])
-def test_using_vocoder_synthesis_matches_oracle_chain(version):
-    """one fragment, mel generated in 3 chunks each prompted by the previous tail; fp32: waveform max-abs <= 5e-3."""
-    tts, t2s, vits, voc = _build(version)
+def _check_fp16_wave(wav, ref, label):
+    """the fp16 vocoder bar against the fp32 oracle chain: max-abs <= 3e-2, relative RMS <= 5 %"""
+    assert torch.isfinite(wav).all()
+    err = (wav - ref).abs().max().item()
+    rel = ((wav - ref).double().pow(2).mean().sqrt() / ref.double().pow(2).mean().sqrt()).item()
+    print(f"[parity] fp16 {label} vs the oracle chain: max-abs error {err:.2e}, relative rms {rel * 100:.2f} %")
+    assert err <= 3e-2 and rel <= 0.05
+
+
+@pytest.mark.parametrize("version,is_half", [("v3", False), ("v4", False), ("v3", True), ("v4", True)],
+                         ids=["v3", "v4", "v3-fp16", "v4-fp16"])
+def test_using_vocoder_synthesis_matches_oracle_chain(version, is_half):
+    """one fragment, mel generated in 3 chunks each prompted by the previous tail; fp32: waveform max-abs <= 5e-3; fp16
+    engines (the production dtype, fp16 mel hand-off between the chunks and to the vocoder): the fp16 vocoder bar."""
+    tts, t2s, vits, voc = _build(version, is_half)
     refer, psem, pph, ref_mel = _prompt(tts)
     sem = torch.from_numpy(S.hash_ints("v3_sem", 19, 1024, 4)).view(1, 1, -1)
     ph = torch.from_numpy(S.hash_ints("v3_ph", 11, 732, 4)).view(1, -1)
@@ -83,12 +94,25 @@ def test_using_vocoder_synthesis_matches_oracle_chain(version):
     ref = tts_v3_oracle.using_vocoder_synthesis(de, cfm, vo, vc, psem, pph, refer, ref_mel, sem, ph, 1.0, 3)
     assert wav.shape == ref.shape
     assert wav.shape[0] == (int(2 * 19 * 1.875) if version == "v3" else 2 * 19 * 2) * vc["upsample_rate"]
-    assert (wav - ref).abs().max() <= 5e-3
+    if is_half:
+        _check_fp16_wave(wav, ref, f"{version} single fragment")
+    else:
+        assert (wav - ref).abs().max() <= 5e-3
 
 
 def test_batched_infer_with_sola_matches_oracle_chain():
     """three fragments -> overlapping chunks -> ONE batched CFM call -> vocoder -> SOLA -> split (TTS.py:1496-1609)."""
-    tts, t2s, vits, voc = _build("v3")
+    _batched_chain(is_half=False)
+
+
+def test_batched_infer_with_sola_fp16_matches_oracle_chain():
+    """the same chain with fp16 engines (SOLA over fp16 fragments): same fragment lengths (= same SOLA offsets) as the
+    oracle chain, samples within the fp16 vocoder bar."""
+    _batched_chain(is_half=True)
+
+
+def _batched_chain(is_half):
+    tts, t2s, vits, voc = _build("v3", is_half)
     refer, psem, pph, ref_mel = _prompt(tts)
     sems = [torch.from_numpy(S.hash_ints(f"v3_bsem{i}", n, 1024, 6)) for i, n in enumerate([9, 14, 6])]
     phs = [torch.from_numpy(S.hash_ints(f"v3_bph{i}", n, 732, 6)) for i, n in enumerate([7, 9, 5])]
@@ -101,9 +125,12 @@ def test_batched_infer_with_sola_matches_oracle_chain():
     assert len(out) == len(ref) == 3
     for a, b in zip(out, ref):
         assert a.shape == b.shape
-        if b.numel():
+        if b.numel() and not is_half:
             assert (a.float().cpu() - b).abs().max() <= 5e-3
     assert sum(int(b.numel()) for b in ref) > 0
+    if is_half:
+        assert all(a.dtype == torch.float16 for a in out)
+        _check_fp16_wave(torch.cat([a.float().cpu() for a in out]), torch.cat(ref), "v3 batched chunks + SOLA")
 
 
 @pytest.mark.parametrize("n,length,ov", [(2, 9000, 3072), (4, 700, 96), (1, 50, 8)])

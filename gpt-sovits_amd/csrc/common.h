@@ -170,6 +170,22 @@ struct ConvArgs {
   int z_res = 0;                             // batched launch (Z > 1) whose residual has its own slice stride rz: takes the LDS GEMM
                                              // path (bwe.hip; other batched launches with a residual keep the generic kernel)
 };
+// Route record (gsv_debug_last_conv_route): every launch site of launch_conv_gemm / launch_conv_pair stores which kernel
+// instantiation it launched, as one 64-bit code of byte fields (include/gsv.h has the layout).  A plain store on the host:
+// no formatting, allocation or synchronisation on the launch path.
+enum { ROUTE_GEMM_SK = 1, ROUTE_GEMM_T64 = 2, ROUTE_CONV_WIDE = 3, ROUTE_GEMM_LDS = 4, ROUTE_CONV_LDS = 5, ROUTE_CONV_NARROW = 6,
+       ROUTE_CONV_GEMM = 7, ROUTE_CONV_PAIR = 8 };
+enum { ROUTE_RES = 1, ROUTE_ACCU = 2, ROUTE_ALLW = 4, ROUTE_WNT = 8 };
+constexpr unsigned long long route_code(int family, int dtype, int p0 = 0, int p1 = 0, int p2 = 0, int p3 = 0, int p4 = 0, int flags = 0) {
+  return (unsigned long long)(family & 255) | (unsigned long long)(dtype & 255) << 8 | (unsigned long long)(p0 & 255) << 16 |
+         (unsigned long long)(p1 & 255) << 24 | (unsigned long long)(p2 & 255) << 32 | (unsigned long long)(p3 & 255) << 40 |
+         (unsigned long long)(p4 & 255) << 48 | (unsigned long long)(flags & 255) << 56;
+}
+constexpr int route_flags(bool res, bool accu, bool allw = false, bool wnt = false) {
+  return (res ? ROUTE_RES : 0) | (accu ? ROUTE_ACCU : 0) | (allw ? ROUTE_ALLW : 0) | (wnt ? ROUTE_WNT : 0);
+}
+void set_conv_route(unsigned long long code);
+
 int launch_conv_gemm(int dtype, const ConvArgs& a, hipStream_t s);
 // split-K-in-workgroup streaming GEMM for under-filled grids (gemm_sk.hip): 0 = launched, 1 = not eligible, <0 = error
 int launch_gemm_sk(int dtype, const ConvArgs& a, hipStream_t s);

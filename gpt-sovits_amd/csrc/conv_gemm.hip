@@ -191,21 +191,26 @@ template <typename T> static int launch_t(const ConvArgs& a, hipStream_t s) {
   GSV_REQUIRE(a.T_virt > 0 && a.Cout > 0 && a.Z > 0, "conv_gemm: empty problem");
   if (a.Cout <= 32) {
     dim3 grid(cdiv(a.T_virt, 512), cdiv(a.Cout, 32), a.Z);
+    set_conv_route(route_code(ROUTE_CONV_GEMM, DT<T>::id, 1, 4, 1, 4));
     hipLaunchKernelGGL((conv_gemm_kernel<T, 1, 4, 1, 4>), grid, dim3(256), 0, s, a);
   } else if (a.Cout <= 64 && (long long)cdiv(a.T_virt, 256) * a.Z < 192) {
     // under-filled grid (e.g. the DiT's grouped position conv: 16 groups x 4 time tiles): 64 x 64 tiles instead
     dim3 grid(cdiv(a.T_virt, 64), cdiv(a.Cout, 64), a.Z);
+    set_conv_route(route_code(ROUTE_CONV_GEMM, DT<T>::id, 1, 1, 2, 2));
     hipLaunchKernelGGL((conv_gemm_kernel<T, 1, 1, 2, 2>), grid, dim3(256), 0, s, a);
   } else if (a.Cout <= 64) {
     dim3 grid(cdiv(a.T_virt, 256), cdiv(a.Cout, 64), a.Z);
+    set_conv_route(route_code(ROUTE_CONV_GEMM, DT<T>::id, 2, 2, 1, 4));
     hipLaunchKernelGGL((conv_gemm_kernel<T, 2, 2, 1, 4>), grid, dim3(256), 0, s, a);
   } else if ((long long)cdiv(a.T_virt, 128) * cdiv(a.Cout, 128) * a.Z < small_tiles_below()) {
     // a handful of 128 x 128 tiles (single-utterance enc_p / flow convs: 200 frames x 384 channels = 6 workgroups, each
     // a serial chain over taps x Cin): 64 x 64 tiles put four times as many CUs on the same chain length
     dim3 grid(cdiv(a.T_virt, 64), cdiv(a.Cout, 64), a.Z);
+    set_conv_route(route_code(ROUTE_CONV_GEMM, DT<T>::id, 1, 1, 2, 2));
     hipLaunchKernelGGL((conv_gemm_kernel<T, 1, 1, 2, 2>), grid, dim3(256), 0, s, a);
   } else {
     dim3 grid(cdiv(a.T_virt, 128), cdiv(a.Cout, 128), a.Z);
+    set_conv_route(route_code(ROUTE_CONV_GEMM, DT<T>::id, 2, 2, 2, 2));
     hipLaunchKernelGGL((conv_gemm_kernel<T, 2, 2, 2, 2>), grid, dim3(256), 0, s, a);
   }
   GSV_HIP(hipGetLastError());
@@ -214,6 +219,7 @@ template <typename T> static int launch_t(const ConvArgs& a, hipStream_t s) {
 
 int launch_conv_gemm(int dtype, const ConvArgs& a_in, hipStream_t s) {
   ConvArgs a = a_in;
+  set_conv_route(0);
   if (a.T_virt == 0) a.T_virt = a.T_out;
   if (a.ups_u > 0 && a.ups_cout == 0) { set_error("conv_gemm: ups_cout missing"); return GSV_ERR_ARG; }
   static const bool no_lds = getenv("GSV_NO_CONV_LDS") != nullptr;   // A/B switch for profiling

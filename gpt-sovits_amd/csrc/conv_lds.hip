@@ -610,6 +610,7 @@ template <typename T> static int try_launch_gemm(const ConvArgs& a, hipStream_t 
     auto kern = gemm_lds_kernel<T, R, NTW, W>;                                                                             \
     static bool set = false;                                                                                               \
     if (!set) { GSV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set = true; } \
+    set_conv_route(route_code(ROUTE_GEMM_LDS, DT<T>::id, W, b.xcd_order, 0, 0, 0, route_flags(R, false, false, NTW)));      \
     hipLaunchKernelGGL(kern, grid, dim3(W * 64), lds, s, b);                                                               \
   } while (0)
   if (a.res) { if (w8) GSV_GEMM_LAUNCH(true, false, 8); else GSV_GEMM_LAUNCH(true, false, 4); }
@@ -635,6 +636,7 @@ static int launch_inst2(const ConvArgs& a, int rows_win, int lo, hipStream_t s) 
   }
   if (lds > 160 * 1024) { set_error("conv_lds: window needs %zu B of LDS", lds); return GSV_ERR_ARG; }
   dim3 grid(cdiv(a.T_virt, TT), cdiv(a.Cout, CT), 1);
+  set_conv_route(route_code(ROUTE_CONV_LDS, DT<T>::id, TM, TN, WM, WN, CC, route_flags(RES, ACCU, ALLW)));
   hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), lds, s, a, rows_win, lo);
   GSV_HIP(hipGetLastError());
   return GSV_OK;
@@ -854,6 +856,7 @@ static int launch_narrow(const ConvArgs& a, int rows_win, hipStream_t s) {
     auto kern = conv_narrow_f16_kernel<CC, TM, TN, WN, R, A>;                                                                         \
     static bool set = false;                                                                                               \
     if (!set) { GSV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set = true; } \
+    set_conv_route(route_code(ROUTE_CONV_NARROW, GSV_F16, CC, TM, TN, WN, 0, route_flags(R, A)));                          \
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WN), lds, s, ap, rows_win, ntiles);                                         \
   } while (0)
   if (res && acc) GSV_NARROW(true, true);

@@ -230,6 +230,7 @@ int launch_pair(const ConvPairArgs& a, hipStream_t s) {
     auto kern = conv_pair_f16_kernel<CC, TAPS, A>;                                                                         \
     static bool set = false;                                                                                               \
     if (!set) { GSV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set = true; } \
+    set_conv_route(route_code(ROUTE_CONV_PAIR, GSV_F16, CC, TAPS, 0, 0, 0, route_flags(false, A)));                        \
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a, ntiles);                                                    \
   } while (0)
   if (a.accumulate) GSV_PAIR(true);
@@ -246,7 +247,8 @@ int launch_pair_taps(const ConvPairArgs& a, hipStream_t s) {
     case 5: return launch_pair<CC, 5>(a, s);
     case 7: return launch_pair<CC, 7>(a, s);
     case 9: return launch_pair<CC, 9>(a, s);
-    default: return launch_pair<CC, 11>(a, s);
+    case 11: return launch_pair<CC, 11>(a, s);
+    default: set_error("conv_pair: no kernel for taps=%d", a.taps); return GSV_ERR_ARG;
   }
 }
 
@@ -254,11 +256,13 @@ int launch_pair_taps(const ConvPairArgs& a, hipStream_t s) {
 
 bool conv_pair_eligible(int dtype, int C, int taps, int dil, int T) {
   static const bool off = getenv("GSV_NO_CONV_PAIR") != nullptr;       // A/B switch: two launches per pair
-  return !off && dtype == GSV_F16 && (C == 16 || C == 32) && (taps & 1) && taps <= 11 && dil >= 1 && ((taps - 1) / 2) * dil <= 25 &&
-         T >= 256;
+  // taps: exactly the instantiated kernels (launch_pair_taps); any other count would read tap slabs past w1 / w2
+  const bool inst = taps == 3 || taps == 5 || taps == 7 || taps == 9 || taps == 11;
+  return !off && dtype == GSV_F16 && (C == 16 || C == 32) && inst && dil >= 1 && ((taps - 1) / 2) * dil <= 25 && T >= 256;
 }
 
 int launch_conv_pair(const ConvPairArgs& a, hipStream_t s) {
+  set_conv_route(0);
   GSV_REQUIRE(a.x && a.y && a.w1 && a.w2 && a.b1 && a.b2, "conv_pair: null operand");
   GSV_REQUIRE(conv_pair_eligible(GSV_F16, a.C, a.taps, a.dil, a.T) || getenv("GSV_NO_CONV_PAIR"), "conv_pair: shape C=%d taps=%d dil=%d T=%d not supported",
               a.C, a.taps, a.dil, a.T);

@@ -246,6 +246,7 @@ int launch_conv_wide(int dtype, const ConvArgs& a, hipStream_t s) {
     auto kern = conv_wide_f16_kernel<R, A, W>;                                                                             \
     static bool set = false;                                                                                               \
     if (!set) { GSV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set = true; } \
+    set_conv_route(route_code(ROUTE_CONV_WIDE, GSV_F16, W, 0, 0, 0, 0, route_flags(R, A)));                                 \
     hipLaunchKernelGGL(kern, dim3(grid), dim3(W * 64), lds, s, b, rows_win, ntiles);                                       \
   } while (0)
 #define GSV_WIDE(R, A) do { if (nw == 8) GSV_WIDE_NW(R, A, 8); else GSV_WIDE_NW(R, A, 4); } while (0)

@@ -303,6 +303,7 @@ int launch_gemm_sk(int dtype, const ConvArgs& a, hipStream_t s) {
       attr64 = true;
     }
     dim3 grid64(cdiv(a.T_virt, 64), cdiv(a.Cout, 64));
+    set_conv_route(route_code(ROUTE_GEMM_T64, GSV_F16, slab / 16, 0, 0, 0, 0, route_flags(false, false, false, a.w_nt != 0)));
     if (slab == 128) {
       if (a.w_nt) hipLaunchKernelGGL((gemm_t64_f16_kernel<true, 128>), grid64, dim3(256), 65536, s, a);
       else hipLaunchKernelGGL((gemm_t64_f16_kernel<false, 128>), grid64, dim3(256), 65536, s, a);
@@ -320,6 +321,7 @@ int launch_gemm_sk(int dtype, const ConvArgs& a, hipStream_t s) {
     attr = true;
   }
   dim3 grid(cdiv(a.T_virt, 64), cdiv(a.Cout, 64));
+  set_conv_route(route_code(ROUTE_GEMM_SK, GSV_F16));
   hipLaunchKernelGGL(gemm_sk_f16_kernel, grid, dim3(256), lds, s, a);
   GSV_HIP(hipGetLastError());
   return 0;

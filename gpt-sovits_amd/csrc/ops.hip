@@ -12,6 +12,9 @@ void set_error(const char* fmt, ...) {
 }
 const char* get_error() { return g_err; }
 
+static thread_local unsigned long long g_conv_route = 0;
+void set_conv_route(unsigned long long code) { g_conv_route = code; }
+
 template <typename T> __global__ void convert_kernel(const float* __restrict__ s, T* __restrict__ d, long long n) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long stride = (long long)gridDim.x * blockDim.x;
@@ -213,6 +216,11 @@ __global__ void cnorm_apply_kernel(const T* __restrict__ x, int Tn, int C, int s
 extern "C" {
 const char* gsv_last_error(void) { return gsv::get_error(); }
 int gsv_abi_version(void) { return 1; }
+uint64_t gsv_debug_last_conv_route(int reset) {
+  const uint64_t code = gsv::g_conv_route;
+  if (reset) gsv::g_conv_route = 0;
+  return code;
+}
 int gsv_init(int device) {
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
@@ -259,7 +267,9 @@ int gsv_op_conv1d(const gsv_conv_desc* d, int dtype, gsv_stream_t stream) {
   a.stride = d->stride; a.dil = d->dil; a.pad = d->pad;
   a.ldx = d->Cin; a.ldw = d->taps * d->Cin;
   a.pre_act = d->pre_act; a.pre_slope = d->pre_slope; a.post_act = d->post_act; a.scale = d->scale;
-  a.accumulate = d->accumulate; a.out_f32 = d->out_f32; a.res_f32 = d->out_f32;
+  a.accumulate = d->accumulate; a.out_f32 = d->out_f32;
+  a.res_f32 = d->res_dtype == 0 ? d->out_f32 : d->res_dtype == 1;
+  a.y_col0 = d->y_col0; a.w_nt = d->w_nt; a.z_res = d->z_res;
   if (d->ups_u > 0) {
     // transposed conv restated as a polyphase conv: Cout = u * real_cout virtual channels
     a.ups_u = d->ups_u; a.ups_pad = d->ups_pad; a.ups_cout = d->Cout / d->ups_u;
@@ -302,7 +312,7 @@ int gsv_op_magnitude(const float* re_im, int T, int bins, float eps, int frame_l
 
 int gsv_op_conv_pair(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y, int T, int C, int taps,
                      int dil, float scale, int accumulate, gsv_stream_t stream) {
-  GSV_REQUIRE(gsv::conv_pair_eligible(GSV_F16, C, taps, dil, T), "op_conv_pair: C must be 16 or 32, taps odd <= 11, (taps - 1) / 2 * dil <= 25, T >= 256");
+  GSV_REQUIRE(gsv::conv_pair_eligible(GSV_F16, C, taps, dil, T), "op_conv_pair: C must be 16 or 32, taps 3, 5, 7, 9 or 11, (taps - 1) / 2 * dil <= 25, T >= 256");
   gsv::ConvPairArgs a;
   a.x = (const _Float16*)x; a.w1 = (const _Float16*)w1; a.b1 = b1; a.w2 = (const _Float16*)w2; a.b2 = b2; a.y = (_Float16*)y;
   a.T = T; a.C = C; a.taps = taps; a.dil = dil; a.ldx = C; a.ldy = C; a.scale = scale; a.accumulate = accumulate;

@@ -53,7 +53,10 @@ class ConvDesc(C.Structure):
                 ("out_f32", C.c_int), ("ups_u", C.c_int), ("ups_pad", C.c_int),
                 ("Z", C.c_int), ("xz", C.c_longlong), ("wz", C.c_longlong), ("yz", C.c_longlong),
                 ("ldx", C.c_int), ("ldw", C.c_int), ("ldy", C.c_int), ("gate", C.c_void_p), ("bz", C.c_int),
-                ("rz", C.c_longlong), ("ldr", C.c_int)]
+                ("rz", C.c_longlong), ("ldr", C.c_int),
+                # optional, 0 = default: residual dtype (0 follows out_f32, 1 fp32, 2 engine dtype), slice column offset in y,
+                # non-temporal weights, batched residual slices (include/gsv.h)
+                ("res_dtype", C.c_int), ("y_col0", C.c_int), ("w_nt", C.c_int), ("z_res", C.c_int)]
 
 
 _SIGS = {
@@ -121,6 +124,7 @@ _SIGS = {
     "gsv_op_flash_rel96": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
     "gsv_op_conv1d": (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_void_p]),
+    "gsv_debug_last_conv_route": (C.c_uint64, [C.c_int]),
     "gsv_op_frame": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "gsv_op_magnitude": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "gsv_op_conv_pair": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,

@@ -310,6 +310,10 @@ typedef struct {
   const float* gate;   /* optional per-output-channel gate: y = ((W x + b) * gate + res) * scale */
   int bz;              /* grouped convs (Z > 1): element stride of bias between slices (0 = one bias shared by all) */
   long long rz; int ldr; /* residual: element stride between slices (0 = yz) and leading dim (0 = ldy) */
+  int res_dtype;       /* residual dtype: 0 = follows out_f32, 1 = fp32, 2 = the engine dtype (out_f32 with an fp16 residual) */
+  int y_col0;          /* column offset of the written slice inside each y row (ldy must cover it) */
+  int w_nt;            /* weights loaded non-temporal (GEMM paths) */
+  int z_res;           /* batched launch (Z > 1) with a residual of its own slice stride rz: may take the LDS GEMM path */
 } gsv_conv_desc;
 /* fused softmax attention of the DiT blocks alone (fp16, head dim 64): qkv [dev] f16 [T][3*heads*64] (q | k | v column
  * blocks), vt_scratch [dev] heads*64*ceil32(T) halfs, out [dev] f16 [T][heads*64] */
@@ -326,6 +330,13 @@ int gsv_op_decode_attn(const void* q, const void* kc, const void* vc, const int3
                        int smax, int dtype, void* out, gsv_stream_t stream);
 /* channels-last conv1d: x [T_in][Cin], w [Cout][taps*Cin] (tap-major, cin fastest), y [T_out][Cout] */
 int gsv_op_conv1d(const gsv_conv_desc* d, int dtype, gsv_stream_t stream);
+/* test hook: which kernel instantiation the last gsv_op_conv1d / gsv_op_conv_pair / engine conv launch on this thread ran
+ * (0 = none since the last reset).  Byte fields, low to high: family, dtype (GSV_F32 / GSV_F16), five template parameters p0..p4,
+ * flags (1 RES, 2 ACCU, 4 ALLW, 8 WNT).  Families and their parameters:
+ *   1 gemm_sk_f16 | 2 gemm_t64_f16 p0 = SLAB / 16 | 3 conv_wide_f16 p0 = waves | 4 gemm_lds p0 = waves, p1 = xcd_order
+ *   5 conv_lds p0..p4 = TM, TN, WM, WN, CC | 6 conv_narrow_f16 p0..p3 = CC, TM, TN, WN | 7 conv_gemm (generic) p0..p3 = TM, TN, WM, WN
+ *   8 conv_pair_f16 p0 = C, p1 = taps.  reset != 0 clears the record after reading it. */
+uint64_t gsv_debug_last_conv_route(int reset);
 /* y = LN(x (+res)) over the last dim C; all buffers of `dtype`, gamma/beta fp32 */
 int gsv_op_layernorm(const void* x, const void* res, const float* gamma, const float* beta, void* y, int rows,
                      int C, float eps, int dtype, gsv_stream_t stream);

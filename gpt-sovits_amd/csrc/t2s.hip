@@ -32,17 +32,18 @@ typedef float f4v __attribute__((ext_vector_type(4)));
 
 // x[row] = E_text[id] + bert_proj(bert)[row] + alpha_t * pe[pos]     (H2; t2s_model.py:612-617)
 // or       E_audio[tok] + alpha_a * pe[pos]                            (t2s_model.py:636-640)
-// rows are packed per utterance: [x_0 .. x_{X-1}, y_0 .. y_{P-1}]
+// rows are packed per utterance: [x_0 .. x_{X-1}, y_0 .. y_{P_b-1}]; row b's prompt is prompts[poff[b] .. + P_b)
 template <typename T>
 __global__ void embed_prefill_kernel(const int* __restrict__ phones, const int* __restrict__ prompts,
                                      const int* __restrict__ row_off, const int* __restrict__ ph_off,
                                      const int* __restrict__ x_len, const float* __restrict__ e_text,
                                      const float* __restrict__ e_audio, const float* __restrict__ bertp,  // [sumX][d] or null
                                      const float* __restrict__ bert_bias, const float* __restrict__ pe, float alpha_t,
-                                     float alpha_a, int P, int d, T* __restrict__ x) {
+                                     float alpha_a, const int* __restrict__ plen, const int* __restrict__ poff, int d,
+                                     T* __restrict__ x) {
   const int b = blockIdx.y;
   const int i = blockIdx.x;  // position within the row's sequence
-  const int X = x_len[b];
+  const int X = x_len[b], P = plen[b];
   if (i >= X + P) return;
   T* out = x + (long long)(row_off[b] + i) * d;
   if (i < X) {
@@ -54,7 +55,7 @@ __global__ void embed_prefill_kernel(const int* __restrict__ phones, const int* 
       out[c] = (T)(v + alpha_t * pe[(long long)i * d + c]);
     }
   } else {
-    const int tok = prompts[b * P + (i - X)];
+    const int tok = prompts[poff[b] + (i - X)];
     const float* e = e_audio + (long long)tok * d;
     for (int c = threadIdx.x; c < d; c += blockDim.x) out[c] = (T)(e[c] + alpha_a * pe[(long long)(i - X) * d + c]);
   }
@@ -63,9 +64,9 @@ __global__ void embed_prefill_kernel(const int* __restrict__ phones, const int* 
 // scatter the prefill K/V (columns d..3d of qkv) into the head-major cache
 template <typename T>
 __global__ void kv_scatter_kernel(const T* __restrict__ qkv, const int* __restrict__ row_off, const int* __restrict__ x_len,
-                                  int P, int d, int H, int smax, T* __restrict__ kc, T* __restrict__ vc) {
+                                  const int* __restrict__ plen, int d, int H, int smax, T* __restrict__ kc, T* __restrict__ vc) {
   const int b = blockIdx.y, i = blockIdx.x;
-  if (i >= x_len[b] + P) return;
+  if (i >= x_len[b] + plen[b]) return;
   const int hd = d / H;
   const T* src = qkv + (long long)(row_off[b] + i) * 3 * d;
   for (int c = threadIdx.x; c < d; c += blockDim.x) {
@@ -80,10 +81,10 @@ __global__ void kv_scatter_kernel(const T* __restrict__ qkv, const int* __restri
 // Mask (t2s_model.py:655-683): text rows see the text keys; audio rows see all text + causal audio.
 template <typename T, int HD>
 __global__ void prefill_attn_kernel(const T* __restrict__ qkv, const T* __restrict__ kc, const T* __restrict__ vc,
-                                    const int* __restrict__ row_off, const int* __restrict__ x_len, int P, int d, int H,
-                                    int smax, T* __restrict__ out) {
+                                    const int* __restrict__ row_off, const int* __restrict__ x_len, const int* __restrict__ plen,
+                                    int d, int H, int smax, T* __restrict__ out) {
   const int b = blockIdx.z, h = blockIdx.y;
-  const int X = x_len[b], S = X + P;
+  const int X = x_len[b], S = X + plen[b];
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int q0 = blockIdx.x * blockDim.x;
   if (q0 >= S) return;
@@ -132,11 +133,11 @@ __global__ void prefill_attn_kernel(const T* __restrict__ qkv, const T* __restri
 // Mask (t2s_model.py:655-683): text queries see the text keys; audio queries see all text + causal audio.
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void prefill_vt_kernel(const _Float16* __restrict__ qkv, const int* __restrict__ row_off,
-                                                         const int* __restrict__ x_len, int P, int d, int H, int spad,
-                                                         _Float16* __restrict__ vt) {
+                                                         const int* __restrict__ x_len, const int* __restrict__ plen, int d,
+                                                         int H, int spad, _Float16* __restrict__ vt) {
   __shared__ _Float16 tile[32][34];
   const int b = blockIdx.z, h = blockIdx.y, j0 = blockIdx.x * 32;
-  const int S = x_len[b] + P;
+  const int S = x_len[b] + plen[b];
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   for (int i = ty; i < 32; i += 8) {
     const int j = j0 + i;
@@ -149,12 +150,12 @@ __global__ __launch_bounds__(256) void prefill_vt_kernel(const _Float16* __restr
 // The same V^T tiles plus the head-major K/V cache rows of those 32 positions: one launch per layer instead of
 // kv_scatter_kernel + prefill_vt_kernel (a 32 x 32 tile of one head is 2 KB contiguous in either cache).
 __global__ __launch_bounds__(256) void prefill_kvt_kernel(const _Float16* __restrict__ qkv, const int* __restrict__ row_off,
-                                                          const int* __restrict__ x_len, int P, int d, int H, int smax, int spad,
-                                                          _Float16* __restrict__ kc, _Float16* __restrict__ vc,
-                                                          _Float16* __restrict__ vt) {
+                                                          const int* __restrict__ x_len, const int* __restrict__ plen, int d,
+                                                          int H, int smax, int spad, _Float16* __restrict__ kc,
+                                                          _Float16* __restrict__ vc, _Float16* __restrict__ vt) {
   __shared__ _Float16 tile[32][34];
   const int b = blockIdx.z, h = blockIdx.y, j0 = blockIdx.x * 32;
-  const int S = x_len[b] + P;
+  const int S = x_len[b] + plen[b];
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   for (int i = ty; i < 32; i += 8) {
     const int j = j0 + i;
@@ -175,13 +176,13 @@ __global__ __launch_bounds__(256) void prefill_kvt_kernel(const _Float16* __rest
 template <int QT>
 __global__ __launch_bounds__(256) void prefill_flash32_f16_kernel(const _Float16* __restrict__ qkv, const _Float16* __restrict__ kc,
                                                                    const _Float16* __restrict__ vt, const int* __restrict__ row_off,
-                                                                   const int* __restrict__ x_len, int P, int d, int H, int smax,
-                                                                   int spad, _Float16* __restrict__ out) {
+                                                                   const int* __restrict__ x_len, const int* __restrict__ plen, int d,
+                                                                   int H, int smax, int spad, _Float16* __restrict__ out) {
   constexpr int BQ = 16 * QT, LDO = 36;
   __shared__ float Os[4][BQ][LDO];
   __shared__ float Ms[4][BQ], Ls[4][BQ];
   const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * BQ;
-  const int X = x_len[b], S = X + P;
+  const int X = x_len[b], S = X + plen[b];
   if (q0 >= S) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = lane & 15, g = lane >> 4;
@@ -286,10 +287,17 @@ __global__ __launch_bounds__(256) void prefill_flash32_f16_kernel(const _Float16
 
 // gather each row's last prefill position of the fp32 pre-LN2 stream into the decode buffer
 __global__ void gather_last_kernel(const float* __restrict__ y2, const int* __restrict__ row_off,
-                                   const int* __restrict__ x_len, int P, int d, float* __restrict__ ybuf) {
+                                   const int* __restrict__ x_len, const int* __restrict__ plen, int d, float* __restrict__ ybuf) {
   const int b = blockIdx.x;
-  const float* src = y2 + (long long)(row_off[b] + x_len[b] + P - 1) * d;
+  const float* src = y2 + (long long)(row_off[b] + x_len[b] + plen[b] - 1) * d;
   for (int c = threadIdx.x; c < d; c += blockDim.x) ybuf[(long long)b * d + c] = src[c];
+}
+
+// each row's prompt into the head of its token history (the repetition penalty's window): ytok[b][0 .. P_b)
+__global__ void prompt_copy_kernel(const int* __restrict__ prompts, const int* __restrict__ plen, const int* __restrict__ poff,
+                                   int ycap, int* __restrict__ ytok) {
+  const int b = blockIdx.x, P = plen[b];
+  for (int t = threadIdx.x; t < P; t += blockDim.x) ytok[(long long)b * ycap + t] = prompts[poff[b] + t];
 }
 
 // ---------------------------------------------------------------------------------------
@@ -916,14 +924,15 @@ __global__ __launch_bounds__(64) void sample_step_kernel(const float* __restrict
   const int step = step_ctr[b];
   if (!active[b]) return;
   const int Veff = (step < sp.eos_mask_steps) ? V - 1 : V;
-  const int prev_len = sp.P + step;
+  const int P = sp.plen[b];
+  const int prev_len = P + step;
   int* yrow = ytok + (long long)b * ycap;
   const float* nrow = nullptr;
   if (sp.noise)
     nrow = sp.noise + ((long long)step * sp.noise_rows + (sp.noise_rows > 1 ? b : 0)) * V;
   int smp, amx;
   sample_row<NPL>(logits + (long long)b * V, V, Veff, yrow, prev_len, sp.top_k, sp.top_p, sp.temperature,
-                  sp.rep_penalty, nrow, sp.seed, b, step, seen, &smp, &amx);
+                  sp.rep_penalty, nrow, sp.rng_seed[b], sp.rng_row[b], step, seen, &smp, &amx);
   if (sp.dump)
     for (int v = lane; v < V; v += 64) sp.dump[((long long)step * gridDim.x + b) * V + v] = logits[(long long)b * V + v];
   if (sp.drawn && lane == 0) { int* dr = sp.drawn + ((long long)step * gridDim.x + b) * 2; dr[0] = smp; dr[1] = amx; }
@@ -945,7 +954,7 @@ __global__ __launch_bounds__(64) void sample_step_kernel(const float* __restrict
   if (!(fin || early)) {
     const int tok = min(max(smp, 0), V - 1);
     const float* e = e_audio + (long long)tok * d;
-    const float* p = pe + (long long)(sp.P + step) * d;
+    const float* p = pe + (long long)(P + step) * d;
     for (int c = lane; c < d; c += 64) ybuf[(long long)b * d + c] = e[c] + alpha_a * p[c];
   }
 }
@@ -994,6 +1003,10 @@ struct gsv_t2s {
   int *d_x_len = nullptr, *d_row_off = nullptr, *d_ph_off = nullptr, *d_kv_len = nullptr, *d_active = nullptr,
       *d_step = nullptr, *d_n_active = nullptr, *d_ytok = nullptr;
   int ycap = 0;
+  int* d_plen = nullptr;    // [2][max_batch]: prompt length P_b | offset of row b's prompt in the packed prompt buffer
+  unsigned long long* d_rng_seed = nullptr; int* d_rng_row = nullptr;   // [max_batch] counter-RNG keys of the rows
+  std::vector<unsigned long long> rng_seed_up; std::vector<int> rng_row_up;   // what the device arrays hold (skip re-uploads)
+  std::vector<unsigned long long> rng_seed_next; std::vector<int> rng_row_next;   // gsv_t2s_set_row_rng: NEXT decode only
   int* h_pinned = nullptr;
   StepParams* d_sp = nullptr;
   // decode buffers
@@ -1006,7 +1019,7 @@ struct gsv_t2s {
   float *pf_y = nullptr, *pf_bert = nullptr;
   void* pf_bert_t = nullptr;
   // current batch
-  int B = 0, P = 0;
+  int B = 0, P = 0;         // P: the longest row's prompt (uniform prefill: every row's)
   int max_kv0 = 0;          // longest row's cached positions after prefill (host copy: bounds the decode budget)
   // persistent decode engine (t2s_mega.hip): fp16, v1/v2 shape, B <= 128; the launch-per-phase step stays as the
   // fp32 / other-shape path and behind GSV_T2S_NO_MEGA=1 for A/B
@@ -1239,6 +1252,9 @@ int gsv_t2s_finalize(gsv_t2s_t* h) {
   h->d_active = h->d_kv_len + B; h->d_step = h->d_kv_len + 2 * B; h->d_n_active = h->d_kv_len + 3 * B;
   h->ycap = h->max_seq + 8;
   GSV_RC(dev_alloc(h, (void**)&h->d_ytok, B * h->ycap * 4));
+  GSV_RC(dev_alloc(h, (void**)&h->d_plen, 2 * B * 4));
+  GSV_RC(dev_alloc(h, (void**)&h->d_rng_seed, B * 8));
+  GSV_RC(dev_alloc(h, (void**)&h->d_rng_row, B * 4));
   GSV_RC(dev_alloc(h, (void**)&h->d_sp, sizeof(StepParams)));
   GSV_HIP(hipHostMalloc((void**)&h->h_pinned, 64));
   GSV_RC(dev_alloc(h, (void**)&h->ybuf, B * d * 4));
@@ -1395,37 +1411,42 @@ static int grow_prefill(gsv_t2s* h, size_t rows, size_t xrows) {
   return GSV_OK;
 }
 
-extern "C" {
-
-int gsv_t2s_prefill(gsv_t2s_t* h, const int32_t* phones, const int32_t* phone_lens, int B, const float* bert,
-                    const int32_t* prompts, int P, gsv_stream_t stream) {
-  GSV_REQUIRE(h && h->finalized, "t2s_prefill: handle not finalized");
-  GSV_REQUIRE(phones && phone_lens && (prompts || P == 0), "t2s_prefill: null argument");
-  GSV_REQUIRE(B >= 1 && B <= h->max_batch, "t2s_prefill: batch %d exceeds max_batch %d", B, h->max_batch);
-  GSV_REQUIRE(P >= 0, "t2s_prefill: negative prompt length %d", P);   // P == 0: prompt-free decode (t2s_model.py:849-856)
-  hipStream_t s = (hipStream_t)stream;
+// Prefill of B rows with prompts of P_b = plen[b] tokens, packed back to back in `prompts` (device) from poff[b] on.
+// The uniform entry (every P_b = P, poff[b] = b P) and the ragged one share this body: the kernels read P_b per row either
+// way, so a uniform batch computes exactly what it computed when P was a kernel argument.
+static int t2s_prefill_rows(gsv_t2s* h, const int32_t* phones, const int32_t* phone_lens, int B, const float* bert,
+                            const int32_t* prompts, const int* plen, const int* poff, hipStream_t s) {
   const auto& c = h->cfg;
   const int d = c.dim, H = c.n_head;
-  std::vector<int> row_off(B), ph_off(B), kvl(B), ones(B, 1), zeros(B, 0);
-  int M = 0, SX = 0, maxS = 0;
+  std::vector<int> row_off(B), ph_off(B), kvl(B);
+  int M = 0, SX = 0, maxS = 0, maxP = 0;
   for (int b = 0; b < B; ++b) {
     GSV_REQUIRE(phone_lens[b] >= 1, "t2s_prefill: empty phoneme sequence in row %d", b);
     row_off[b] = M; ph_off[b] = SX;
+    const int P = plen[b];
     const int S = phone_lens[b] + P;
     GSV_REQUIRE(S + 2 <= h->max_seq, "t2s_prefill: row %d needs %d positions, max_seq is %d", b, S + 2, h->max_seq);
-    GSV_REQUIRE(phone_lens[b] <= h->pe_rows && P <= h->pe_rows, "t2s_prefill: sequence exceeds the position table");
+    GSV_REQUIRE(phone_lens[b] <= h->pe_rows, "t2s_prefill: sequence exceeds the position table");
+    GSV_REQUIRE(P <= h->pe_rows, "t2s_prefill: row %d's prompt of %d tokens exceeds the position table (%d rows)", b, P, h->pe_rows);
+    GSV_REQUIRE(P + 1 <= h->ycap, "t2s_prefill: row %d's prompt of %d tokens exceeds the token history (%d)", b, P, h->ycap);
     kvl[b] = S; M += S; SX += phone_lens[b];
     maxS = S > maxS ? S : maxS;
+    maxP = P > maxP ? P : maxP;
   }
   GSV_RC(grow_prefill(h, M, SX));
   if (h->dtype == GSV_F16) {
     const size_t need_vt = (size_t)B * H * 32 * ((maxS + 31) / 32 * 32) * 2;
     if (need_vt > h->pf_vt_cap) { GSV_RC(dev_alloc(h, &h->pf_vt, need_vt + need_vt / 4)); h->pf_vt_cap = need_vt + need_vt / 4; }
   }
-  h->B = B; h->P = P; h->max_kv0 = maxS;
+  h->B = B; h->P = maxP; h->max_kv0 = maxS;
   GSV_HIP(hipMemcpyAsync(h->d_x_len, phone_lens, B * 4, hipMemcpyHostToDevice, s));
   GSV_HIP(hipMemcpyAsync(h->d_row_off, row_off.data(), B * 4, hipMemcpyHostToDevice, s));
   GSV_HIP(hipMemcpyAsync(h->d_ph_off, ph_off.data(), B * 4, hipMemcpyHostToDevice, s));
+  const int* d_plen = h->d_plen;
+  const int* d_poff = h->d_plen + h->max_batch;
+  std::vector<int> pl(2 * (size_t)h->max_batch, 0);
+  for (int b = 0; b < B; ++b) { pl[b] = plen[b]; pl[h->max_batch + b] = poff[b]; }
+  GSV_HIP(hipMemcpyAsync(h->d_plen, pl.data(), pl.size() * 4, hipMemcpyHostToDevice, s));
   {
     // row state [kv_len | active | step | n_active] is one block: one upload
     const size_t mb = (size_t)h->max_batch;
@@ -1435,8 +1456,10 @@ int gsv_t2s_prefill(gsv_t2s_t* h, const int32_t* phones, const int32_t* phone_le
     GSV_HIP(hipMemcpyAsync(h->d_kv_len, st.data(), st.size() * 4, hipMemcpyHostToDevice, s));
     GSV_HIP(hipStreamSynchronize(s));
   }
-  if (P > 0)
-    GSV_HIP(hipMemcpy2DAsync(h->d_ytok, (size_t)h->ycap * 4, prompts, (size_t)P * 4, (size_t)P * 4, B, hipMemcpyDeviceToDevice, s));
+  if (maxP > 0) {
+    hipLaunchKernelGGL(prompt_copy_kernel, dim3(B), dim3(64), 0, s, prompts, d_plen, d_poff, h->ycap, h->d_ytok);
+    GSV_HIP(hipGetLastError());
+  }
   GSV_HIP(hipStreamSynchronize(s));  // host vectors above go out of scope
 
   const float* bertp = nullptr;
@@ -1450,7 +1473,8 @@ int gsv_t2s_prefill(gsv_t2s_t* h, const int32_t* phones, const int32_t* phone_le
   }
 #define GSV_EMBED(T)                                                                                              \
   hipLaunchKernelGGL(embed_prefill_kernel<T>, dim3(maxS, B), dim3(128), 0, s, phones, prompts, h->d_row_off, h->d_ph_off, \
-                     h->d_x_len, h->e_text, h->e_audio, bertp, h->bert_b, h->pe, h->alpha_t, h->alpha_a, P, d, (T*)h->pf_x)
+                     h->d_x_len, h->e_text, h->e_audio, bertp, h->bert_b, h->pe, h->alpha_t, h->alpha_a, d_plen, d_poff, d, \
+                     (T*)h->pf_x)
   if (h->dtype == GSV_F16) GSV_EMBED(_Float16); else GSV_EMBED(float);
 #undef GSV_EMBED
   GSV_HIP(hipGetLastError());
@@ -1467,29 +1491,29 @@ int gsv_t2s_prefill(gsv_t2s_t* h, const int32_t* phones, const int32_t* phone_le
       const bool fused_kvt = d / H == 32 && !scalar_pf && !split_scatter;
       if (!fused_kvt)
         hipLaunchKernelGGL(kv_scatter_kernel<_Float16>, dim3(maxS, B), dim3(128), 0, s, (const _Float16*)h->pf_qkv,
-                           h->d_row_off, h->d_x_len, P, d, H, h->max_seq, (_Float16*)kv_ptr(h, li, 0), (_Float16*)kv_ptr(h, li, 1));
+                           h->d_row_off, h->d_x_len, d_plen, d, H, h->max_seq, (_Float16*)kv_ptr(h, li, 0), (_Float16*)kv_ptr(h, li, 1));
       if (d / H == 32 && !scalar_pf) {
         const int spad = (maxS + 31) / 32 * 32;
         if (fused_kvt)
           hipLaunchKernelGGL(prefill_kvt_kernel, dim3(spad / 32, H, B), dim3(256), 0, s, (const _Float16*)h->pf_qkv, h->d_row_off,
-                             h->d_x_len, P, d, H, h->max_seq, spad, (_Float16*)kv_ptr(h, li, 0), (_Float16*)kv_ptr(h, li, 1),
+                             h->d_x_len, d_plen, d, H, h->max_seq, spad, (_Float16*)kv_ptr(h, li, 0), (_Float16*)kv_ptr(h, li, 1),
                              (_Float16*)h->pf_vt);
         else
         hipLaunchKernelGGL(prefill_vt_kernel, dim3(spad / 32, H, B), dim3(256), 0, s, (const _Float16*)h->pf_qkv, h->d_row_off,
-                           h->d_x_len, P, d, H, spad, (_Float16*)h->pf_vt);
+                           h->d_x_len, d_plen, d, H, spad, (_Float16*)h->pf_vt);
         hipLaunchKernelGGL(prefill_flash32_f16_kernel<4>, dim3(cdiv(maxS, 64), H, B), dim3(256), 0, s, (const _Float16*)h->pf_qkv,
-                           (const _Float16*)kv_ptr(h, li, 0), (const _Float16*)h->pf_vt, h->d_row_off, h->d_x_len, P, d, H,
+                           (const _Float16*)kv_ptr(h, li, 0), (const _Float16*)h->pf_vt, h->d_row_off, h->d_x_len, d_plen, d, H,
                            h->max_seq, spad, (_Float16*)h->pf_attn);
       } else
       hipLaunchKernelGGL((prefill_attn_kernel<_Float16, 32>), dim3(cdiv(maxS, 64), H, B), dim3(64), 0, s,
                          (const _Float16*)h->pf_qkv, (const _Float16*)kv_ptr(h, li, 0), (const _Float16*)kv_ptr(h, li, 1),
-                         h->d_row_off, h->d_x_len, P, d, H, h->max_seq, (_Float16*)h->pf_attn);
+                         h->d_row_off, h->d_x_len, d_plen, d, H, h->max_seq, (_Float16*)h->pf_attn);
     } else {
       hipLaunchKernelGGL(kv_scatter_kernel<float>, dim3(maxS, B), dim3(128), 0, s, (const float*)h->pf_qkv, h->d_row_off,
-                         h->d_x_len, P, d, H, h->max_seq, (float*)kv_ptr(h, li, 0), (float*)kv_ptr(h, li, 1));
+                         h->d_x_len, d_plen, d, H, h->max_seq, (float*)kv_ptr(h, li, 0), (float*)kv_ptr(h, li, 1));
       hipLaunchKernelGGL((prefill_attn_kernel<float, 32>), dim3(cdiv(maxS, 64), H, B), dim3(64), 0, s,
                          (const float*)h->pf_qkv, (const float*)kv_ptr(h, li, 0), (const float*)kv_ptr(h, li, 1),
-                         h->d_row_off, h->d_x_len, P, d, H, h->max_seq, (float*)h->pf_attn);
+                         h->d_row_off, h->d_x_len, d_plen, d, H, h->max_seq, (float*)h->pf_attn);
     }
     GSV_HIP(hipGetLastError());
     // y1 = attn Wo^T + bo + x  (fp32) ; x1 = LN1(y1)
@@ -1510,8 +1534,44 @@ int gsv_t2s_prefill(gsv_t2s_t* h, const int32_t* phones, const int32_t* phone_le
     if (li + 1 < c.n_layer)
       GSV_RC(launch_layernorm(h->dtype, h->pf_y, 1, nullptr, 0, L.n2w, L.n2b, h->pf_x, 0, M, d, 1e-5f, s));
   }
-  hipLaunchKernelGGL(gather_last_kernel, dim3(B), dim3(128), 0, s, h->pf_y, h->d_row_off, h->d_x_len, P, d, h->ybuf);
+  hipLaunchKernelGGL(gather_last_kernel, dim3(B), dim3(128), 0, s, h->pf_y, h->d_row_off, h->d_x_len, d_plen, d, h->ybuf);
   GSV_HIP(hipGetLastError());
+  return GSV_OK;
+}
+
+extern "C" {
+
+int gsv_t2s_prefill(gsv_t2s_t* h, const int32_t* phones, const int32_t* phone_lens, int B, const float* bert,
+                    const int32_t* prompts, int P, gsv_stream_t stream) {
+  GSV_REQUIRE(h && h->finalized, "t2s_prefill: handle not finalized");
+  GSV_REQUIRE(phones && phone_lens && (prompts || P == 0), "t2s_prefill: null argument");
+  GSV_REQUIRE(B >= 1 && B <= h->max_batch, "t2s_prefill: batch %d exceeds max_batch %d", B, h->max_batch);
+  GSV_REQUIRE(P >= 0, "t2s_prefill: negative prompt length %d", P);   // P == 0: prompt-free decode (t2s_model.py:849-856)
+  std::vector<int> plen(B, P), poff(B);
+  for (int b = 0; b < B; ++b) poff[b] = b * P;
+  return t2s_prefill_rows(h, phones, phone_lens, B, bert, prompts, plen.data(), poff.data(), (hipStream_t)stream);
+}
+
+int gsv_t2s_prefill_ragged(gsv_t2s_t* h, const int32_t* phones, const int32_t* phone_lens, int B, const float* bert,
+                           const int32_t* prompts_packed, const int32_t* prompt_lens, gsv_stream_t stream) {
+  GSV_REQUIRE(h && h->finalized, "t2s_prefill_ragged: handle not finalized");
+  GSV_REQUIRE(phones && phone_lens && prompts_packed && prompt_lens, "t2s_prefill_ragged: null argument");
+  GSV_REQUIRE(B >= 1 && B <= h->max_batch, "t2s_prefill_ragged: batch %d exceeds max_batch %d", B, h->max_batch);
+  std::vector<int> poff(B);
+  int o = 0;
+  for (int b = 0; b < B; ++b) {
+    // prompt-free rows keep the uniform entry (P = 0 there also masks EOS for 11 steps: t2s_model.py:849-856)
+    GSV_REQUIRE(prompt_lens[b] >= 1, "t2s_prefill_ragged: row %d has prompt length %d (must be >= 1)", b, prompt_lens[b]);
+    poff[b] = o; o += prompt_lens[b];
+  }
+  return t2s_prefill_rows(h, phones, phone_lens, B, bert, prompts_packed, prompt_lens, poff.data(), (hipStream_t)stream);
+}
+
+int gsv_t2s_set_row_rng(gsv_t2s_t* h, const uint64_t* seeds, const int32_t* rows, int B) {
+  GSV_REQUIRE(h && h->finalized, "t2s_set_row_rng: handle not finalized");
+  GSV_REQUIRE(seeds && rows && B >= 1 && B <= h->max_batch, "t2s_set_row_rng: bad argument (B = %d)", B);
+  h->rng_seed_next.assign(seeds, seeds + B);
+  h->rng_row_next.assign(rows, rows + B);
   return GSV_OK;
 }
 
@@ -1526,14 +1586,30 @@ int gsv_t2s_decode(gsv_t2s_t* h, const gsv_sampling_params* sp, const float* noi
   p.top_k = sp->top_k; p.top_p = sp->top_p; p.temperature = sp->temperature; p.rep_penalty = sp->repetition_penalty;
   p.early_stop_num = sp->early_stop_num; p.eos_mask_steps = sp->eos_mask_steps; p.max_steps = sp->max_steps;
   p.noise_rows = noise ? noise_rows : 0; p.seed = sp->seed; p.noise = noise; p.out_tokens = out_tokens; p.out_len = out_len;
-  p.P = h->P;
+  p.plen = h->d_plen; p.rng_seed = h->d_rng_seed; p.rng_row = h->d_rng_row;
   p.force = h->dbg_force; p.dump = h->dbg_dump; p.drawn = h->dbg_drawn;
   h->dbg_force = nullptr; h->dbg_dump = nullptr; h->dbg_drawn = nullptr;
+  // counter-RNG keys of the rows: gsv_t2s_set_row_rng's for this call, else (seed, b) -- the draws of a batch without keys
+  const bool keyed = !h->rng_seed_next.empty();
+  const int nkeys = (int)h->rng_seed_next.size();
+  std::vector<unsigned long long> seeds(h->B);
+  std::vector<int> rows(h->B);
+  for (int b = 0; b < h->B && (!keyed || nkeys == h->B); ++b) {
+    seeds[b] = keyed ? h->rng_seed_next[b] : (unsigned long long)sp->seed;
+    rows[b] = keyed ? h->rng_row_next[b] : b;
+  }
+  h->rng_seed_next.clear(); h->rng_row_next.clear();
+  GSV_REQUIRE(!keyed || nkeys == h->B, "t2s_decode: gsv_t2s_set_row_rng gave %d keys for a batch of %d rows", nkeys, h->B);
   GSV_HIP(hipMemcpyAsync(h->d_sp, &p, sizeof(p), hipMemcpyHostToDevice, s));
+  if (seeds != h->rng_seed_up || rows != h->rng_row_up) {
+    GSV_HIP(hipMemcpyAsync(h->d_rng_seed, seeds.data(), (size_t)h->B * 8, hipMemcpyHostToDevice, s));
+    GSV_HIP(hipMemcpyAsync(h->d_rng_row, rows.data(), (size_t)h->B * 4, hipMemcpyHostToDevice, s));
+    h->rng_seed_up = seeds; h->rng_row_up = rows;
+  }
   GSV_HIP(hipStreamSynchronize(s));
   // budget: step 0 samples from the prefill's last position, every later step appends one K/V position, so the
-  // longest row ends at max_kv0 + budget - 1 cached positions; the sampling tail reads pe[P + step] and writes
-  // token history [P + step].  A request that does not fit is refused here: the kernels clamp out-of-range
+  // longest row ends at max_kv0 + budget - 1 cached positions; the sampling tail of row b reads pe[P_b + step] and writes
+  // token history [P_b + step] (h->P is the longest prompt).  A request that does not fit is refused here: the kernels clamp out-of-range
   // appends, which would otherwise yield silently wrong tokens with rc 0.
   int budget = sp->max_steps;
   if (sp->early_stop_num >= 0 && sp->early_stop_num + 1 < budget) budget = sp->early_stop_num + 1;
@@ -1542,6 +1618,7 @@ int gsv_t2s_decode(gsv_t2s_t* h, const gsv_sampling_params* sp, const float* noi
               "or create the engine with a larger max_seq", h->max_kv0, budget, h->max_seq);
   GSV_REQUIRE(h->P + budget <= h->pe_rows, "t2s_decode: prompt %d + %d steps exceed the position table (%d rows)", h->P, budget,
               h->pe_rows);
+  GSV_REQUIRE(h->P + budget <= h->ycap, "t2s_decode: prompt %d + %d steps exceed the token history (%d)", h->P, budget, h->ycap);
   // step 0: logits of the last prefill position, sample, emit first embedding
   GSV_RC(launch_tail(h, s));
   int steps = 1;
@@ -1560,8 +1637,9 @@ int gsv_t2s_decode(gsv_t2s_t* h, const gsv_sampling_params* sp, const float* noi
       GSV_HIP(hipMemsetAsync(m.hop, 0, m.hop_bytes, s));      // no tag survives a call (epochs are unique per launch as well: ep_base)
       GSV_HIP(hipMemsetAsync(m.err, 0, 64, s));
       // the row state as step 0 left it: if the launch ends in a hand-off timeout the batch is re-run from here on the
-      // launch-per-phase path (the engine only appends K/V behind kv_len and token history behind P + step: restoring the
-      // counters makes both invisible again; ybuf, the first step's input, is read-only for the engine)
+      // launch-per-phase path (the engine only appends K/V behind kv_len and token history behind P_b + step: restoring the
+      // counters makes both invisible again; ybuf, the first step's input, is read-only for the engine; P_b and the RNG keys
+      // are read-only during a decode call)
       const size_t mb = (size_t)h->max_batch;
       GSV_HIP(hipMemcpyAsync(m.snap, h->d_kv_len, (3 * mb + 4) * 4, hipMemcpyDeviceToDevice, s));
       GSV_HIP(hipMemcpyAsync(m.snap + 3 * mb + 4, out_len, h->B * 4, hipMemcpyDeviceToDevice, s));
@@ -1790,8 +1868,9 @@ int gsv_t2s_debug_set_state(gsv_t2s_t* h, int B, int kv_len) {
   // arena holds); used by tools/attn_sweep.py to time the decode-attention kernel at other (B, S) points
   GSV_REQUIRE(h && h->finalized, "t2s_debug_set_state: handle not finalized");
   GSV_REQUIRE(B >= 1 && B <= h->max_batch && kv_len >= 1 && kv_len + 2 <= h->max_seq, "t2s_debug_set_state: out of range");
-  std::vector<int> kv(B, kv_len), zero(B, 0);
+  std::vector<int> kv(B, kv_len), zero(B, 0), plen(B, h->P);
   GSV_HIP(hipMemcpy(h->d_kv_len, kv.data(), B * 4, hipMemcpyHostToDevice));
+  GSV_HIP(hipMemcpy(h->d_plen, plen.data(), B * 4, hipMemcpyHostToDevice));   // every row: the last prefill's longest prompt
   GSV_HIP(hipMemcpy(h->d_active, zero.data(), B * 4, hipMemcpyHostToDevice));
   GSV_HIP(hipMemset(h->ybuf, 0, (size_t)B * h->cfg.dim * 4));
   GSV_HIP(hipMemset(h->kv, 0, (size_t)h->cfg.n_layer * 2 * h->kv_layer_stride * esz(h)));

@@ -99,7 +99,8 @@ constexpr int L_ATT = L_QKV + 2 * 3 * 32 * 2;                 // float [8] m + [
 constexpr int L_STAGE = L_ATT + 32 + 8 * 4 * 36 * 4;          // 4 x 1 KB: per-wave transposition buffers of the publishers
 constexpr int L_ST = L_STAGE + 4 * 1024;                      // int: active[QMAX * RMAX], kvlen[..], step[..], abort, -, barrier counter, flag
 constexpr int ST_N = QMAX * RMAX;                             // rows of a group
-constexpr int L_SEEN = L_ST + (3 * ST_N + 16) * 4;            // bytes [VPAD]
+constexpr int L_SR = L_ST + (3 * ST_N + 16) * 4;              // int: prompt length P_b[ST_N], RNG key seed lo[..], seed hi[..], row[..]
+constexpr int L_SEEN = L_SR + 4 * ST_N * 4;                   // bytes [VPAD]
 constexpr int L_KV = (L_SEEN + VPAD + 63) & ~63;              // [2 rows][K|V][KV_CAP][64 B]
 constexpr int L_TOTAL = L_KV + 2 * 2 * KV_CAP * 64;
 static_assert(L_TOTAL <= 160 * 1024, "LDS budget");
@@ -182,6 +183,11 @@ __device__ __forceinline__ lds_int* st_kvlen(const Ctx& c) { return (lds_int*)(u
 __device__ __forceinline__ lds_int* st_step(const Ctx& c) { return (lds_int*)(unsigned)L_ST + 2 * ST_N + RMAX * c.qd; }
 __device__ __forceinline__ lds_vint* st_abort(const Ctx&) { return (lds_vint*)(unsigned)L_ST + 3 * ST_N; }
 __device__ __forceinline__ lds_int* st_cbar(const Ctx&) { return (lds_int*)(unsigned)L_ST + 3 * ST_N + 2; }
+// the samplers' per-row constants of a call (read once at kernel start): P_b and the counter-RNG key (seed_b, row_b)
+__device__ __forceinline__ lds_int* st_plen(const Ctx& c) { return (lds_int*)(unsigned)L_SR + RMAX * c.qd; }
+__device__ __forceinline__ lds_int* st_seed_lo(const Ctx& c) { return (lds_int*)(unsigned)L_SR + ST_N + RMAX * c.qd; }
+__device__ __forceinline__ lds_int* st_seed_hi(const Ctx& c) { return (lds_int*)(unsigned)L_SR + 2 * ST_N + RMAX * c.qd; }
+__device__ __forceinline__ lds_int* st_krow(const Ctx& c) { return (lds_int*)(unsigned)L_SR + 3 * ST_N + RMAX * c.qd; }
 
 // Barrier among the 4 compute waves only (an s_barrier would also wait for the comm waves, which are busy issuing the next
 // layer's K/V loads during P1): an arrival counter in LDS; LDS operations of a wave complete in order, so the add is behind
@@ -711,7 +717,8 @@ __device__ __forceinline__ void kv_stage_store(const Ctx& q, int qd, int extra, 
       const float* nrow = nullptr; \
       if (sp.noise) nrow = sp.noise + ((size_t)step * sp.noise_rows + (sp.noise_rows > 1 ? b : 0)) * V; \
       int smp, amx; \
-      sample_core<17>(x, Veff, sp.top_k, sp.top_p, sp.temperature, nrow, sp.seed, b, step, &smp, &amx); \
+      const unsigned long long seed_b = ((unsigned long long)(unsigned)st_seed_hi(q)[r] << 32) | (unsigned)st_seed_lo(q)[r]; \
+      sample_core<17>(x, Veff, sp.top_k, sp.top_p, sp.temperature, nrow, seed_b, st_krow(q)[r], step, &smp, &amx); \
       if (sp.dump) { \
   _Pragma("unroll") \
         for (int i = 0; i < 17; ++i) { \
@@ -723,7 +730,8 @@ __device__ __forceinline__ void kv_stage_store(const Ctx& q, int qd, int extra, 
       if (sp.force) { smp = sp.force[(size_t)b * sp.max_steps + step]; amx = smp; } \
       const bool fin = smp == EOS || amx == EOS; \
       const bool early = (sp.early_stop_num != -1 && (step + 1) > sp.early_stop_num) || step >= sp.max_steps - 1; \
-      const int prev_len = sp.P + step; \
+      const int P_b = st_plen(q)[r]; \
+      const int prev_len = P_b + step; \
       if (q.lane == 0) { \
         if (prev_len < a.ycap) a.ytok[(size_t)b * a.ycap + prev_len] = smp; \
         if (smp >= 0 && smp < VPAD) seen[smp] = 1; \
@@ -741,7 +749,7 @@ __device__ __forceinline__ void kv_stage_store(const Ctx& q, int qd, int extra, 
         now_active = 1; \
         const int tok = min(max(smp, 0), V - 1); \
         const float* e = a.e_audio + (size_t)tok * D; \
-        const float* p = a.pe + (size_t)(sp.P + step) * D; \
+        const float* p = a.pe + (size_t)(P_b + step) * D; \
   _Pragma("unroll") \
         for (int k = 0; k < 8; ++k) x0[k] = e[k * 64 + q.lane] + a.alpha_a * p[k * 64 + q.lane]; \
       } \
@@ -1747,12 +1755,17 @@ __global__ __launch_bounds__(MG_THREADS, 1) void t2s_mega_kernel(MegaArgs a) {
     ((int*)(smem + L_ST))[tid] = a.active[b];
     ((int*)(smem + L_ST))[ST_N + tid] = a.kv_len[b];
     ((int*)(smem + L_ST))[2 * ST_N + tid] = a.step_ctr[b];
+    const unsigned long long seed_b = sp.rng_seed[b];
+    ((int*)(smem + L_SR))[tid] = sp.plen[b];
+    ((int*)(smem + L_SR))[ST_N + tid] = (int)(unsigned)seed_b;
+    ((int*)(smem + L_SR))[2 * ST_N + tid] = (int)(unsigned)(seed_b >> 32);
+    ((int*)(smem + L_SR))[3 * ST_N + tid] = sp.rng_row[b];
   }
   if (c.member < Rtot && c.wave == 0) {
     unsigned char* seen = smem + L_SEEN;
     for (int v = lane; v < VPAD; v += 64) seen[v] = 0;
     const int b = c.group + MG_GROUPS * c.member;
-    const int prev_len = sp.P + a.step_ctr[b];
+    const int prev_len = sp.plen[b] + a.step_ctr[b];
     const int* yrow = a.ytok + (size_t)b * a.ycap;
     __builtin_amdgcn_s_waitcnt(0);
     for (int t = lane; t < prev_len; t += 64) {

@@ -21,7 +21,10 @@ struct StepParams {
   const float* noise;      // [max_steps][noise_rows][V] or null
   int* out_tokens;         // [B][max_steps]
   int* out_len;            // [B]
-  int P;                   // prompt length (position offset of generated tokens)
+  // per-row state of the batch, device arrays [B] (t2s.hip: filled by the prefill / in front of every decode)
+  const int* plen;         // prompt length P_b: position offset of row b's generated tokens and its history length
+  const unsigned long long* rng_seed;   // counter-RNG key (rng_seed[b], rng_row[b]) of row b; (seed, b) unless
+  const int* rng_row;                   // gsv_t2s_set_row_rng gave one
   // parity hooks (gsv_t2s_set_debug; null in production): teacher forcing and a per-step dump of the raw logits
   const int* force;        // [B][max_steps]: the token taken at step s of row b instead of the sampled one
   float* dump;             // [max_steps][B][V]: logits of every executed step, before the repetition penalty

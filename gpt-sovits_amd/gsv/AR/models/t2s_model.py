@@ -105,18 +105,34 @@ class Text2SemanticDecoder:
     # ---- engine call ---------------------------------------------------------------
     def _run(self, x: Sequence[torch.Tensor], prompts: torch.Tensor, bert: Sequence[torch.Tensor], top_k, top_p,
              early_stop_num, temperature, repetition_penalty, eos_mask_steps, noise=None, seed=0,
-             max_steps: int = 1500, force_tokens=None, dump_logits=False):
+             max_steps: int = 1500, force_tokens=None, dump_logits=False, rng_keys=None):
+        """prompts: [B, P] (one prompt length for the batch; P = 0 or None: prompt-free) or a list of B 1-D prompts of
+        lengths P_b >= 1 (ragged: gsv_t2s_prefill_ragged).  rng_keys: optional [(seed_b, row_b)] per row, the counter-RNG
+        key that replaces (seed, b) (gsv_t2s_set_row_rng)."""
         if not self._loaded:
             raise RuntimeError("load_state_dict() first")
         B = len(x)
         dev = self.device
         if prompts is None:                  # prompt-free (reference t2s_model.py:849-856): empty audio prefix
             prompts = torch.zeros(B, 0, dtype=torch.int64)
+        ragged = isinstance(prompts, (list, tuple))
+        if ragged:
+            if len(prompts) != B:
+                raise ValueError(f"{len(prompts)} prompts for {B} rows")
+            plens = [int(p_.reshape(-1).shape[0]) for p_ in prompts]
+            if min(plens) < 1:
+                raise ValueError("ragged prompts must each hold at least one token (prompt-free rows: prompts=None)")
+        if rng_keys is not None and len(rng_keys) != B:
+            raise ValueError(f"{len(rng_keys)} RNG keys for {B} rows")
         l = _lib.lib()
         with torch.cuda.device(dev):
             lens = [int(t.shape[-1]) for t in x]
-            P = int(prompts.shape[1])
-            need = max(lens) + P + 2
+            if ragged:
+                P = max(plens)
+                need = max(n_ + p_ for n_, p_ in zip(lens, plens)) + 2
+            else:
+                P = int(prompts.shape[1])
+                need = max(lens) + P + 2
             wanted = max_steps if early_stop_num in (-1, None) else min(max_steps, int(early_stop_num) + 1)
             budget = min(wanted, self.max_seq - need)
             if budget < 1:
@@ -143,7 +159,10 @@ class Text2SemanticDecoder:
                     allb = torch.cat(cols, 0).contiguous()
                     if bool(torch.any(allb)):            # one host sync for the whole batch
                         bert_dev = allb
-            pr = prompts.to(dev, torch.int32).contiguous()
+            if ragged:
+                pr = torch.cat([p_.reshape(-1) for p_ in prompts]).to(dev, torch.int32).contiguous()
+            else:
+                pr = prompts.to(dev, torch.int32).contiguous()
             out_tokens = torch.zeros(B, budget, dtype=torch.int32, device=dev)
             out_len = torch.full((B,), -1, dtype=torch.int32, device=dev)
             noise_dev, noise_rows = None, 0
@@ -160,10 +179,22 @@ class Text2SemanticDecoder:
             if early_stop_num not in (-1, None) and budget < int(early_stop_num) + 1:
                 sp.early_stop_num = -1   # the arena bound (max_steps) ends generation first
             s = C.c_void_p(self.stream.cuda_stream)
-            _lib.check(l.gsv_t2s_prefill(self._h, phones.data_ptr(), C.cast(lens_h, C.c_void_p), B,
-                                         bert_dev.data_ptr() if bert_dev is not None else None,
-                                         pr.data_ptr() if P > 0 else None, P, s),
-                       "gsv_t2s_prefill")
+            if ragged:
+                plens_h = (C.c_int32 * B)(*plens)
+                _lib.check(l.gsv_t2s_prefill_ragged(self._h, phones.data_ptr(), C.cast(lens_h, C.c_void_p), B,
+                                                    bert_dev.data_ptr() if bert_dev is not None else None,
+                                                    pr.data_ptr(), C.cast(plens_h, C.c_void_p), s),
+                           "gsv_t2s_prefill_ragged")
+            else:
+                _lib.check(l.gsv_t2s_prefill(self._h, phones.data_ptr(), C.cast(lens_h, C.c_void_p), B,
+                                             bert_dev.data_ptr() if bert_dev is not None else None,
+                                             pr.data_ptr() if P > 0 else None, P, s),
+                           "gsv_t2s_prefill")
+            if rng_keys is not None:
+                seeds_h = (C.c_uint64 * B)(*[int(k[0]) & 0xFFFFFFFFFFFFFFFF for k in rng_keys])
+                rows_h = (C.c_int32 * B)(*[int(k[1]) for k in rng_keys])
+                _lib.check(l.gsv_t2s_set_row_rng(self._h, C.cast(seeds_h, C.c_void_p), C.cast(rows_h, C.c_void_p), B),
+                           "gsv_t2s_set_row_rng")
             steps = C.c_int(0)
             dump = None
             if force_tokens is not None or dump_logits:
@@ -190,7 +221,13 @@ class Text2SemanticDecoder:
             torch.cuda.current_stream(dev).wait_stream(self.stream)
             idx = out_len.cpu().tolist()
             self.last_steps = steps.value
-            y_all = torch.cat([pr, out_tokens], dim=1).long()       # one concat for the batch; rows are sliced as views
+            if ragged:
+                y_all = None
+                offs = np.concatenate([[0], np.cumsum(plens)]).tolist()
+                gen_all = out_tokens.long()
+                pr_all = pr.long()
+            else:
+                y_all = torch.cat([pr, out_tokens], dim=1).long()       # one concat for the batch; rows are sliced as views
             y_list = []
             self.last_truncated = [b for b in range(B) if idx[b] < 0] if arena_bound else []
             if self.last_truncated:
@@ -202,7 +239,10 @@ class Text2SemanticDecoder:
             for b in range(B):
                 n = idx[b] if idx[b] >= 0 else steps.value - 1
                 idx[b] = n
-                y_list.append(y_all[b, :P + n])
+                if ragged:
+                    y_list.append(torch.cat([pr_all[offs[b]:offs[b + 1]], gen_all[b, :n]]))
+                else:
+                    y_list.append(y_all[b, :P + n])
         return y_list, idx
 
     # ---- reference entry points -----------------------------------------------------
@@ -212,7 +252,15 @@ class Text2SemanticDecoder:
                                 early_stop_num: int = -1, temperature: float = 1.0,
                                 repetition_penalty: float = 1.35, **kwargs):
         """reference t2s_model.py:583-779: returns (y_list, idx_list); y_list[i] = prompt + generated
-        tokens (finishing token dropped), idx_list[i] = number of generated tokens."""
+        tokens (finishing token dropped), idx_list[i] = number of generated tokens.
+
+        `prompts` is the reference's [B, P] tensor, or a list of B 1-D prompts of different lengths (one reference voice
+        per row, every length >= 1).  kwarg `rng_keys=[(seed, row), ...]`: row i draws with the counter-RNG key
+        (seed, row) instead of (seed kwarg, its row in the launch), so it samples the same tokens whichever batch it
+        is decoded in."""
+        rng_keys = kwargs.get("rng_keys")
+        if rng_keys is not None and len(rng_keys) != len(x):
+            raise ValueError(f"{len(rng_keys)} RNG keys for {len(x)} rows")
         if prompts is None:
             return self.infer_panel_naive_batched(x, x_lens, prompts, bert_feature, top_k=top_k, top_p=top_p,
                                                   early_stop_num=early_stop_num, temperature=temperature, **kwargs)
@@ -229,7 +277,8 @@ class Text2SemanticDecoder:
                              repetition_penalty, eos_mask_steps=1, noise=nz, seed=kwargs.get("seed", 0),
                              max_steps=kwargs.get("max_steps", 1500),
                              force_tokens=None if kwargs.get("force_tokens") is None else kwargs["force_tokens"][lo:hi],
-                             dump_logits=kwargs.get("dump_logits", False))
+                             dump_logits=kwargs.get("dump_logits", False),
+                             rng_keys=None if rng_keys is None else list(rng_keys[lo:hi]))
             ys[lo:hi] = y
             idxs[lo:hi] = i
         return ys, idxs

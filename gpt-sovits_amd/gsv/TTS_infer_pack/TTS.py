@@ -15,6 +15,8 @@ language splitter, BERT engine for zh).  Pre-tokenised `segments` and `set_promp
 """
 from __future__ import annotations
 
+import collections
+import contextlib
 import math
 import os
 import random
@@ -750,6 +752,308 @@ class TTS:
                                            C.c_void_p(st.cuda_stream)), "gsv_sola")
         return out[:n_out.value].to(dt)
 
+    def _prepare_prompt(self, inputs: dict) -> None:
+        """run()'s reference-audio / prompt-text handling (reference TTS.py:1078-1120): brings self.prompt_cache up to date
+        with the request's ref_audio_path, aux_ref_audio_paths and prompt_text / prompt_lang."""
+        ref_audio_path = inputs.get("ref_audio_path")
+        prompt_text, prompt_lang = inputs.get("prompt_text"), inputs.get("prompt_lang", "")
+        if ref_audio_path in [None, ""] and inputs.get("segments") is None and "text" in inputs and (
+                self.prompt_cache["prompt_semantic"] is None or self.prompt_cache["refer_spec"] in [None, []]):
+            raise ValueError("ref_audio_path cannot be empty, when the reference audio is not set using set_ref_audio()")
+        if ref_audio_path not in [None, ""] and ref_audio_path != self.prompt_cache["ref_audio_path"]:
+            if not os.path.exists(ref_audio_path):
+                raise ValueError(f"{ref_audio_path} not exists")
+            self.set_ref_audio(ref_audio_path)
+        # auxiliary references for multi-speaker tone fusion (reference TTS.py:1098-1113): their spectrograms (and, v2Pro,
+        # speaker embeddings) follow the main one; the style vector is the mean over all of them (models.py:971-985)
+        aux = inputs.get("aux_ref_audio_paths") or []
+        cached = self.prompt_cache.get("aux_ref_audio_paths") or []
+        if "aux_ref_audio_paths" in inputs and not (len(set(aux) & set(cached)) == len(aux) == len(cached)):
+            if self.prompt_cache["refer_spec"] in [None, []]:
+                raise ValueError("aux_ref_audio_paths need a main reference audio first (ref_audio_path / set_ref_audio)")
+            self.prompt_cache["aux_ref_audio_paths"] = list(aux)
+            self.prompt_cache["refer_spec"] = [self.prompt_cache["refer_spec"][0]]
+            if self.prompt_cache.get("sv_emb"):
+                self.prompt_cache["sv_emb"] = [self.prompt_cache["sv_emb"][0]]
+            for path in aux:
+                if path in [None, ""]:
+                    continue
+                if not os.path.exists(path):
+                    print("音频文件不存在，跳过：", path)
+                    continue
+                spec_audio = self._get_ref_spec(path)
+                self.prompt_cache["refer_spec"].append(spec_audio)
+                if spec_audio[1] is not None:
+                    self.prompt_cache["sv_emb"].append(self.sv_model.compute_embedding3(spec_audio[1]))
+            self.vits_model.invalidate_refer()
+        if prompt_text not in [None, ""]:
+            from .text_segmentation_method import splits
+            if prompt_lang not in self.configs.languages:
+                raise ValueError(f"prompt_lang {prompt_lang!r} is not one of {self.configs.languages}")
+            prompt_text = prompt_text.strip("\n")
+            if prompt_text[-1] not in splits:
+                prompt_text += "。" if prompt_lang != "en" else "."
+            if self.prompt_cache["prompt_text"] != prompt_text:
+                phones, bert_features, norm_text = self.text_preprocessor.segment_and_extract_feature_for_text(
+                    prompt_text, prompt_lang, self.configs.version)
+                self.prompt_cache.update(prompt_text=prompt_text, prompt_lang=prompt_lang, phones=phones,
+                                         bert_features=bert_features, norm_text=norm_text)
+        elif "prompt_text" in inputs and self.configs.use_vocoder:
+            raise NO_PROMPT_ERROR("prompt_text cannot be empty when using SoVITS_V3")
+        if not self.prompt_cache["refer_spec"] or (self.prompt_cache["prompt_semantic"] is None
+                                                   and self.prompt_cache["phones"] is not None):
+            raise NO_PROMPT_ERROR("set_prompt_cache() first (reference: ref_audio_path is required)")
+
+    def _segments(self, inputs: dict) -> list:
+        """run()'s text front-end (reference TTS.py:1018-1024, 1100-1135): the request's segments"""
+        segments = inputs.get("segments")
+        if segments is None:
+            # reference TTS.py:1018-1024, 1100-1135: raw text through the TextPreprocessor (G2P back-ends are plug-ins,
+            # gsv.text.cleaner.register_g2p); a `text_frontend` callable replaces it wholesale
+            text, text_lang = inputs.get("text", ""), inputs.get("text_lang", "")
+            method = inputs.get("text_split_method", "cut0")
+            if self.text_frontend is not None:
+                segments = self.text_frontend(text, text_lang, method)
+            else:
+                if text_lang not in self.configs.languages:
+                    raise ValueError(f"text_lang {text_lang!r} is not one of {self.configs.languages}")
+                segments = self.text_preprocessor.preprocess(text, text_lang, method, self.configs.version)
+        return segments
+
+    def _synthesize_batch(self, item: dict, pred: List[torch.Tensor], pred_list: List[torch.Tensor], idx_list: List[int],
+                          seed_b: int, bi: int, actual_seed: int, speed_factor: float, parallel_infer: bool, sample_steps: int,
+                          refer: List[torch.Tensor], sv_kw: dict, up: int) -> List[torch.Tensor]:
+        """run()'s post-AR stage of one to_batch batch `bi` (reference TTS.py:1259-1299): the fragments of its sentences from
+        the generated tokens `pred`, with the voice of self.prompt_cache (v3/v4) / `refer` + `sv_kw` (v1/v2/v2Pro)"""
+        frags: List[torch.Tensor] = []
+        if self.configs.use_vocoder:
+            # TTS.py:1283-1299
+            dev_ph = [ph.to(self.configs.device) for ph in item["phones"]]
+            if parallel_infer:
+                frags = self.using_vocoder_synthesis_batched_infer(idx_list, pred_list, dev_ph, speed=speed_factor,
+                                                                   sample_steps=sample_steps, seed=seed_b)
+            else:
+                for k, idx in enumerate(idx_list):
+                    frags.append(self.using_vocoder_synthesis(pred_list[k][-idx:].view(1, 1, -1), dev_ph[k].view(1, -1),
+                                                              speed=speed_factor, sample_steps=sample_steps,
+                                                              seed=actual_seed + bi * 4096 + k))
+        elif speed_factor == 1.0:
+            # one decode over the batch folded into the time axis (TTS.py:1259-1282)
+            ends = np.cumsum([0] + [int(p.shape[0]) * 2 * up for p in pred])
+            keep = [k for k, p in enumerate(pred) if p.shape[0] > 0]
+            if keep:
+                all_pred = torch.cat([pred[k] for k in keep]).view(1, 1, -1)
+                all_ph = torch.cat([item["phones"][k] for k in keep]).view(1, -1)
+                wav = self.vits_model.decode(all_pred, all_ph, refer, speed=speed_factor,
+                                             seed=seed_b, **sv_kw)[0, 0]
+            else:
+                wav = torch.zeros(0, dtype=self.precision, device=self.configs.device)
+            o = 0
+            for k, p in enumerate(pred):
+                nsm = int(p.shape[0]) * 2 * up
+                frags.append(wav[o:o + nsm])
+                o += nsm
+        else:
+            for k, p in enumerate(pred):
+                frags.append(self.vits_model.decode(p.view(1, 1, -1), item["phones"][k].view(1, -1), refer,
+                                                    speed=speed_factor, seed=seed_b, **sv_kw)[0, 0])
+        return frags
+
+    # ---- several voices in one AR decode -----------------------------------------------------------
+    _VOICE_KEYS = ("prompt_semantic", "refer_spec", "phones", "bert_features", "norm_text", "ref_mel", "sv_emb", "raw_audio",
+                   "raw_sr", "ref_audio_path", "aux_ref_audio_paths", "prompt_text", "prompt_lang")
+
+    @contextlib.contextmanager
+    def _with_prompt_cache(self, cache: dict):
+        """self.prompt_cache is `cache` inside the block and the caller's dict again after it; the SoVITS engine's cached
+        reference terms (ge) are dropped on the way in and out, so no voice ever reuses another's style vector"""
+        saved = self.prompt_cache
+        self.prompt_cache = cache
+        if self.vits_model is not None:
+            self.vits_model.invalidate_refer()
+        try:
+            yield cache
+        finally:
+            self.prompt_cache = saved
+            if self.vits_model is not None:
+                self.vits_model.invalidate_refer()
+
+    def _empty_prompt_cache(self) -> dict:
+        return {"ref_audio_path": None, "prompt_semantic": None, "refer_spec": [], "prompt_text": None, "prompt_lang": None,
+                "phones": None, "bert_features": None, "norm_text": None, "aux_ref_audio_paths": [], "ref_mel": None,
+                "sv_emb": None}
+
+    def make_voice(self, prompt_semantic: Optional[torch.Tensor] = None, refer_spec: Optional[Sequence[torch.Tensor]] = None,
+                   phones: Optional[List[int]] = None, bert_features: Optional[torch.Tensor] = None, norm_text: str = "",
+                   ref_mel: Optional[torch.Tensor] = None, sv_emb: Optional[Sequence[torch.Tensor]] = None, *,
+                   ref_audio_path: Optional[str] = None, prompt_text: Optional[str] = None, prompt_lang: str = "",
+                   aux_ref_audio_paths: Optional[Sequence[str]] = None) -> dict:
+        """A reference voice for run_batch: a snapshot of what set_prompt_cache (components: same arguments) or
+        set_ref_audio + prompt text + aux_ref_audio_paths (keyword `ref_audio_path`, ...) store.  Voices made from audio are
+        kept in a small LRU keyed by (ref_audio_path, prompt_text, prompt_lang, aux_ref_audio_paths).  self.prompt_cache is
+        not changed."""
+        if ref_audio_path is None:
+            if prompt_semantic is None and phones is not None:
+                raise NO_PROMPT_ERROR("a voice with prompt phones needs its prompt_semantic")
+            with self._with_prompt_cache(self._empty_prompt_cache()) as pc:
+                self.set_prompt_cache(prompt_semantic, refer_spec or [], phones=phones, bert_features=bert_features,
+                                      norm_text=norm_text, ref_mel=ref_mel, sv_emb=sv_emb)
+            return {k: pc.get(k) for k in self._VOICE_KEYS}
+        key = (ref_audio_path, prompt_text, prompt_lang, tuple(aux_ref_audio_paths or ()))
+        lru = self.__dict__.setdefault("_voice_lru", collections.OrderedDict())
+        if key in lru:
+            lru.move_to_end(key)
+            return lru[key]
+        req = {"ref_audio_path": ref_audio_path, "prompt_text": prompt_text, "prompt_lang": prompt_lang}
+        if aux_ref_audio_paths is not None:
+            req["aux_ref_audio_paths"] = list(aux_ref_audio_paths)
+        with self._with_prompt_cache(self._empty_prompt_cache()) as pc:
+            self._prepare_prompt(req)
+        voice = {k: pc.get(k) for k in self._VOICE_KEYS}
+        lru[key] = voice
+        while len(lru) > self.voice_cache_size:
+            lru.popitem(last=False)
+        return voice
+
+    voice_cache_size = 8
+
+    def _request_voice(self, req: dict) -> dict:
+        if req.get("voice") is not None:
+            return req["voice"]
+        if req.get("ref_audio_path") not in [None, ""]:
+            return self.make_voice(ref_audio_path=req["ref_audio_path"], prompt_text=req.get("prompt_text"),
+                                   prompt_lang=req.get("prompt_lang", ""), aux_ref_audio_paths=req.get("aux_ref_audio_paths"))
+        if not self.prompt_cache["refer_spec"]:
+            raise NO_PROMPT_ERROR("run_batch: a request without `voice` or `ref_audio_path` needs set_prompt_cache() first")
+        return {k: self.prompt_cache.get(k) for k in self._VOICE_KEYS}
+
+    @staticmethod
+    def _request_options(req: dict) -> dict:
+        """run()'s per-request options, resolved exactly as run() resolves them"""
+        o = dict(top_k=req.get("top_k", 5), top_p=req.get("top_p", 1), temperature=req.get("temperature", 1),
+                 batch_size=req.get("batch_size", 1), batch_threshold=req.get("batch_threshold", 0.75),
+                 speed_factor=req.get("speed_factor", 1.0), split_bucket=req.get("split_bucket", True),
+                 fragment_interval=req.get("fragment_interval", 0.3), parallel_infer=req.get("parallel_infer", True),
+                 repetition_penalty=req.get("repetition_penalty", 1.35), sample_steps=req.get("sample_steps", 32))
+        seed = req.get("seed", -1)
+        o["seed"] = -1 if seed in ["", None] else seed
+        if o["fragment_interval"] < 0.01:
+            o["fragment_interval"] = 0.01
+        return o
+
+    def plan_batch(self, plans: List[dict]) -> List[List[dict]]:
+        """The AR launches of run_batch.  `plans[r]` = {"data": request r's to_batch batches, "no_prompt", "actual_seed",
+        "opts"}.  Sentence j of batch bi of request r draws with the counter-RNG key (actual_seed_r + bi, j mod max_batch)
+        -- the key it has in run(r) (the naive / prompt-free loop decodes every sentence alone: row 0).  Sentences are
+        grouped by what is per launch (sampling parameters, parallel_infer, prompt-free, the decode budget run() gives them),
+        sorted by length inside a group and cut into launches of at most max_batch rows.  Returns the launches: lists of
+        {"r", "bi", "j", "len", "key"}."""
+        mb, max_seq = self.t2s_model.max_batch, self.t2s_model.max_seq
+        groups: Dict[tuple, List[dict]] = {}
+        for r, pl in enumerate(plans):
+            o = pl["opts"]
+            naive = pl["no_prompt"] or not o["parallel_infer"]
+            P = 0 if pl["no_prompt"] else int(pl["P"])
+            hz_max = self.configs.hz * (self.configs.max_sec if self.configs.max_sec is not None else 54)
+            wanted = min(1500, int(hz_max) + 1)
+            for bi, item in enumerate(pl["data"]):
+                lens = [int(t.shape[-1]) for t in item["all_phones"]]
+                for j, n in enumerate(lens):
+                    # run() decodes this sentence in a launch of `lens` (naive: alone); the K/V arena bounds its budget there
+                    need = (n if naive else max(lens[j - j % mb:j - j % mb + mb])) + P + 2
+                    budget = min(wanted, max_seq - need)
+                    g = (o["top_k"], o["top_p"], o["temperature"], o["repetition_penalty"], bool(o["parallel_infer"]),
+                         bool(pl["no_prompt"]), budget)
+                    groups.setdefault(g, []).append(dict(r=r, bi=bi, j=j, len=n + P, group=g,
+                                                         key=(pl["actual_seed"] + bi, 0 if naive else j % mb)))
+        launches = []
+        for g in groups:
+            rows = sorted(groups[g], key=lambda e: e["len"])
+            launches += [rows[i:i + mb] for i in range(0, len(rows), mb)]
+        return launches
+
+    @torch.no_grad()
+    def run_batch(self, requests: List[dict]) -> List[Tuple[int, np.ndarray]]:
+        """Several requests, each with its own reference voice, through shared AR decodes.  Each request dict takes the
+        keys run() accepts plus an optional "voice" (make_voice); without one it uses its ref_audio_path / prompt_text
+        (through make_voice's LRU) or the current prompt cache.  Returns one (sr, int16 audio) per request, in order: what
+        run(request) alone returns.  self.prompt_cache is not changed.  return_fragment is not supported."""
+        if self.t2s_model is None or self.vits_model is None:
+            raise RuntimeError("init_t2s_weights / init_vits_weights first")
+        self.stop_flag = False
+        plans = []
+        for req in requests:
+            if req.get("return_fragment", False):
+                raise ValueError("run_batch returns whole utterances: return_fragment=True is not supported")
+            o = self._request_options(req)
+            voice = self._request_voice(req)
+            if o["speed_factor"] != 1.0:
+                o["split_bucket"] = False
+            elif getattr(self.configs, "use_vocoder", False) and o["parallel_infer"]:
+                o["split_bucket"] = False
+            actual_seed = set_seed(o["seed"])
+            segments = self._segments(req)
+            no_prompt = voice["phones"] is None
+            if no_prompt and self.configs.use_vocoder:
+                raise NO_PROMPT_ERROR("v3/v4 need the prompt text (phones) of the reference audio")
+            prompt_data = None if no_prompt else {"phones": voice["phones"], "bert_features": voice["bert_features"]}
+            data, index = ([], []) if len(segments) == 0 else self.to_batch(
+                segments, prompt_data=prompt_data, batch_size=o["batch_size"], threshold=o["batch_threshold"],
+                split_bucket=o["split_bucket"], device=torch.device("cpu"), precision=self.precision)
+            plans.append(dict(voice=voice, opts=o, actual_seed=actual_seed, data=data, index=index, no_prompt=no_prompt,
+                              P=0 if no_prompt else int(voice["prompt_semantic"].numel()),
+                              super_sampling=bool(req.get("super_sampling", False)) and
+                              getattr(self.configs, "use_vocoder", False) and self.configs.version == "v3"))
+        # ---- AR: every sentence of every request, in shared launches
+        preds = [[[None] * len(item["all_phones"]) for item in pl["data"]] for pl in plans]
+        idxs = [[[None] * len(item["all_phones"]) for item in pl["data"]] for pl in plans]
+        max_sec = self.configs.max_sec if self.configs.max_sec is not None else 54
+        for rows in self.plan_batch(plans):
+            o = plans[rows[0]["r"]]["opts"]
+            no_prompt = rows[0]["group"][5]
+            naive = no_prompt or not o["parallel_infer"]
+            items = [plans[e["r"]]["data"][e["bi"]] for e in rows]
+            x = [it["all_phones"][e["j"]] for it, e in zip(items, rows)]
+            bert = [it["all_bert_features"][e["j"]] for it, e in zip(items, rows)]
+            prompts = None if no_prompt else [plans[e["r"]]["voice"]["prompt_semantic"].view(-1) for e in rows]
+            y, idx = self.t2s_model._run(x, prompts, bert, o["top_k"], o["top_p"], self.configs.hz * max_sec, o["temperature"],
+                                         o["repetition_penalty"], eos_mask_steps=11 if naive else 1,
+                                         max_steps=rows[0]["group"][6], rng_keys=[e["key"] for e in rows])
+            for e, y_, i_ in zip(rows, y, idx):
+                preds[e["r"]][e["bi"]][e["j"]] = y_
+                idxs[e["r"]][e["bi"]][e["j"]] = 0 if no_prompt else i_
+        torch.cuda.current_stream(self.configs.device).synchronize()
+        # ---- post-AR: each request with its own voice, as run() does it
+        up = math.prod(self.vits_model.upsample_rates)
+        sr = self.configs.sampling_rate if not self.configs.use_vocoder else self.vocoder_configs["sr"]
+        if self.configs.use_vocoder and self.vocoder is None:
+            raise RuntimeError("init_vocoder() first")
+        results = []
+        for r, pl in enumerate(plans):
+            o = pl["opts"]
+            if not pl["data"]:
+                results.append((16000, np.zeros(16000, dtype=np.int16)))
+                continue
+            voice = dict(pl["voice"])
+            with self._with_prompt_cache(voice):
+                refer = [spec.to(device=self.configs.device) for spec, _ in voice["refer_spec"]]
+                sv_kw = {"sv_emb": voice["sv_emb"]} if getattr(self.vits_model, "is_v2pro", False) else {}
+                audio = []
+                for bi, item in enumerate(pl["data"]):
+                    pred_list, idx_list = preds[r][bi], idxs[r][bi]
+                    if pl["no_prompt"]:
+                        pred = list(pred_list)
+                        idx_list = [int(p_.shape[0]) for p_ in pred]
+                    else:
+                        pred = [p_[-i:] if i > 0 else p_[:0] for p_, i in zip(pred_list, idx_list)]
+                    audio.append(self._synthesize_batch(item, pred, pred_list, idx_list, pl["actual_seed"] + bi, bi,
+                                                        pl["actual_seed"], o["speed_factor"], o["parallel_infer"],
+                                                        o["sample_steps"], refer, sv_kw, up))
+                torch.cuda.current_stream(self.configs.device).synchronize()
+                results.append(self.audio_postprocess(audio, sr, pl["index"], o["speed_factor"], o["split_bucket"],
+                                                      o["fragment_interval"], pl["super_sampling"]))
+        return results
+
     # ---- the pipeline (reference TTS.py:984-1365) ---------------------------------------------
     @torch.no_grad()
     def run(self, inputs: dict) -> Generator[Tuple[int, np.ndarray], None, None]:
@@ -784,67 +1088,9 @@ class TTS:
             if self.t2s_model is None or self.vits_model is None:
                 raise RuntimeError("init_t2s_weights / init_vits_weights first")
             # ---- reference audio and prompt text (reference TTS.py:1078-1120)
-            ref_audio_path = inputs.get("ref_audio_path")
-            prompt_text, prompt_lang = inputs.get("prompt_text"), inputs.get("prompt_lang", "")
-            if ref_audio_path in [None, ""] and inputs.get("segments") is None and "text" in inputs and (
-                    self.prompt_cache["prompt_semantic"] is None or self.prompt_cache["refer_spec"] in [None, []]):
-                raise ValueError("ref_audio_path cannot be empty, when the reference audio is not set using set_ref_audio()")
-            if ref_audio_path not in [None, ""] and ref_audio_path != self.prompt_cache["ref_audio_path"]:
-                if not os.path.exists(ref_audio_path):
-                    raise ValueError(f"{ref_audio_path} not exists")
-                self.set_ref_audio(ref_audio_path)
-            # auxiliary references for multi-speaker tone fusion (reference TTS.py:1098-1113): their spectrograms (and, v2Pro,
-            # speaker embeddings) follow the main one; the style vector is the mean over all of them (models.py:971-985)
-            aux = inputs.get("aux_ref_audio_paths") or []
-            cached = self.prompt_cache.get("aux_ref_audio_paths") or []
-            if "aux_ref_audio_paths" in inputs and not (len(set(aux) & set(cached)) == len(aux) == len(cached)):
-                if self.prompt_cache["refer_spec"] in [None, []]:
-                    raise ValueError("aux_ref_audio_paths need a main reference audio first (ref_audio_path / set_ref_audio)")
-                self.prompt_cache["aux_ref_audio_paths"] = list(aux)
-                self.prompt_cache["refer_spec"] = [self.prompt_cache["refer_spec"][0]]
-                if self.prompt_cache.get("sv_emb"):
-                    self.prompt_cache["sv_emb"] = [self.prompt_cache["sv_emb"][0]]
-                for path in aux:
-                    if path in [None, ""]:
-                        continue
-                    if not os.path.exists(path):
-                        print("音频文件不存在，跳过：", path)
-                        continue
-                    spec_audio = self._get_ref_spec(path)
-                    self.prompt_cache["refer_spec"].append(spec_audio)
-                    if spec_audio[1] is not None:
-                        self.prompt_cache["sv_emb"].append(self.sv_model.compute_embedding3(spec_audio[1]))
-                self.vits_model.invalidate_refer()
-            if prompt_text not in [None, ""]:
-                from .text_segmentation_method import splits
-                if prompt_lang not in self.configs.languages:
-                    raise ValueError(f"prompt_lang {prompt_lang!r} is not one of {self.configs.languages}")
-                prompt_text = prompt_text.strip("\n")
-                if prompt_text[-1] not in splits:
-                    prompt_text += "。" if prompt_lang != "en" else "."
-                if self.prompt_cache["prompt_text"] != prompt_text:
-                    phones, bert_features, norm_text = self.text_preprocessor.segment_and_extract_feature_for_text(
-                        prompt_text, prompt_lang, self.configs.version)
-                    self.prompt_cache.update(prompt_text=prompt_text, prompt_lang=prompt_lang, phones=phones,
-                                             bert_features=bert_features, norm_text=norm_text)
-            elif "prompt_text" in inputs and self.configs.use_vocoder:
-                raise NO_PROMPT_ERROR("prompt_text cannot be empty when using SoVITS_V3")
-            if not self.prompt_cache["refer_spec"] or (self.prompt_cache["prompt_semantic"] is None
-                                                       and self.prompt_cache["phones"] is not None):
-                raise NO_PROMPT_ERROR("set_prompt_cache() first (reference: ref_audio_path is required)")
+            self._prepare_prompt(inputs)
             t0 = time.perf_counter()
-            segments = inputs.get("segments")
-            if segments is None:
-                # reference TTS.py:1018-1024, 1100-1135: raw text through the TextPreprocessor (G2P back-ends are plug-ins,
-                # gsv.text.cleaner.register_g2p); a `text_frontend` callable replaces it wholesale
-                text, text_lang = inputs.get("text", ""), inputs.get("text_lang", "")
-                method = inputs.get("text_split_method", "cut0")
-                if self.text_frontend is not None:
-                    segments = self.text_frontend(text, text_lang, method)
-                else:
-                    if text_lang not in self.configs.languages:
-                        raise ValueError(f"text_lang {text_lang!r} is not one of {self.configs.languages}")
-                    segments = self.text_preprocessor.preprocess(text, text_lang, method, self.configs.version)
+            segments = self._segments(inputs)
             if len(segments) == 0:
                 yield 16000, np.zeros(16000, dtype=np.int16)
                 return
@@ -893,39 +1139,8 @@ class TTS:
                 else:
                     pred = [p[-i:] if i > 0 else p[:0] for p, i in zip(pred_list, idx_list)]
                 self.last_generated_tokens += int(sum(idx_list))
-                frags: List[torch.Tensor] = []
-                if self.configs.use_vocoder:
-                    # TTS.py:1283-1299
-                    sample_steps = inputs.get("sample_steps", 32)
-                    dev_ph = [ph.to(self.configs.device) for ph in item["phones"]]
-                    if parallel_infer:
-                        frags = self.using_vocoder_synthesis_batched_infer(idx_list, pred_list, dev_ph, speed=speed_factor,
-                                                                           sample_steps=sample_steps, seed=actual_seed + bi)
-                    else:
-                        for k, idx in enumerate(idx_list):
-                            frags.append(self.using_vocoder_synthesis(pred_list[k][-idx:].view(1, 1, -1), dev_ph[k].view(1, -1),
-                                                                      speed=speed_factor, sample_steps=sample_steps,
-                                                                      seed=actual_seed + bi * 4096 + k))
-                elif speed_factor == 1.0:
-                    # one decode over the batch folded into the time axis (TTS.py:1259-1282)
-                    ends = np.cumsum([0] + [int(p.shape[0]) * 2 * up for p in pred])
-                    keep = [k for k, p in enumerate(pred) if p.shape[0] > 0]
-                    if keep:
-                        all_pred = torch.cat([pred[k] for k in keep]).view(1, 1, -1)
-                        all_ph = torch.cat([item["phones"][k] for k in keep]).view(1, -1)
-                        wav = self.vits_model.decode(all_pred, all_ph, refer, speed=speed_factor,
-                                                     seed=actual_seed + bi, **sv_kw)[0, 0]
-                    else:
-                        wav = torch.zeros(0, dtype=self.precision, device=self.configs.device)
-                    o = 0
-                    for k, p in enumerate(pred):
-                        nsm = int(p.shape[0]) * 2 * up
-                        frags.append(wav[o:o + nsm])
-                        o += nsm
-                else:
-                    for k, p in enumerate(pred):
-                        frags.append(self.vits_model.decode(p.view(1, 1, -1), item["phones"][k].view(1, -1), refer,
-                                                            speed=speed_factor, seed=actual_seed + bi, **sv_kw)[0, 0])
+                frags = self._synthesize_batch(item, pred, pred_list, idx_list, actual_seed + bi, bi, actual_seed, speed_factor,
+                                               parallel_infer, inputs.get("sample_steps", 32), refer, sv_kw, up)
                 # stream-level wait only: the engine calls above already synchronised their own streams, and a DEVICE-wide
                 # synchronize intermittently stalls 20-30 ms on this ROCm build
                 torch.cuda.current_stream(self.configs.device).synchronize()

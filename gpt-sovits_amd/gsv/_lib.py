@@ -69,6 +69,9 @@ _SIGS = {
     "gsv_t2s_finalize": (C.c_int, [C.c_void_p]),
     "gsv_t2s_prefill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                   C.c_void_p]),
+    "gsv_t2s_prefill_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "gsv_t2s_set_row_rng": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "gsv_t2s_decode": (C.c_int, [C.c_void_p, C.POINTER(SamplingParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                  C.POINTER(C.c_int), C.c_void_p]),
     "gsv_t2s_decode_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int)]),

@@ -85,6 +85,17 @@ int gsv_t2s_finalize(gsv_t2s_t* h);
  * starts empty at position 0).  Leaves the KV cache and per-row state ready for gsv_t2s_decode. */
 int gsv_t2s_prefill(gsv_t2s_t* h, const int32_t* phones, const int32_t* phone_lens, int B,
                     const float* bert, const int32_t* prompts, int P, gsv_stream_t stream);
+/* Prefill of a batch whose rows carry prompts of different lengths (one reference voice per row): prompts_packed [dev]
+ * int32, row b's P_b = prompt_lens[b] [host] tokens back to back in row order; every P_b >= 1 (prompt-free rows keep
+ * gsv_t2s_prefill with P = 0).  Row b needs phone_lens[b] + P_b + 2 <= max_seq; its generated tokens sit at audio
+ * positions P_b, P_b + 1, ... and its repetition history is its own prompt plus what it generated.  With every P_b equal
+ * this computes exactly what gsv_t2s_prefill computes. */
+int gsv_t2s_prefill_ragged(gsv_t2s_t* h, const int32_t* phones, const int32_t* phone_lens, int B, const float* bert,
+                           const int32_t* prompts_packed, const int32_t* prompt_lens, gsv_stream_t stream);
+/* Counter-RNG keys for the NEXT gsv_t2s_decode call only (like gsv_t2s_set_debug): row b draws with the key
+ * (seeds[b], rows[b]) [host] instead of (sp->seed, b), so a row draws the same tokens wherever it sits in a batch.
+ * B must equal the batch of that call.  Without it the keys are (sp->seed, b). */
+int gsv_t2s_set_row_rng(gsv_t2s_t* h, const uint64_t* seeds, const int32_t* rows, int B);
 
 /* Decode loop (H4+H5).  noise [dev] fp32 Exp(1) draws [max_steps][noise_rows][vocab] or NULL
  * (noise_rows is 1 = shared by all rows, or B).  out_tokens [dev] int32 [B][max_steps]: generated

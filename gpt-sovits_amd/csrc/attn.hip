@@ -227,7 +227,7 @@ template <int QT>
 __global__ __launch_bounds__(256) void flash_rel96_f16_kernel(const _Float16* __restrict__ q, int ldq, const _Float16* __restrict__ k,
                                                               int ldk, const _Float16* __restrict__ vt, int ldv, int T, float scale,
                                                               const float* __restrict__ rel_k, const float* __restrict__ rel_v,
-                                                              _Float16* __restrict__ out, int ldo) {
+                                                              _Float16* __restrict__ out, int ldo, const int* __restrict__ kr) {
   constexpr int D = 96, KS = 3, DT = 6, W = 4, NB = 9, LDO = 100, BQ = 16 * QT;
   extern __shared__ float smem[];
   float* Os = smem;                                  // [4][BQ][LDO]
@@ -275,7 +275,17 @@ __global__ __launch_bounds__(256) void flash_rel96_f16_kernel(const _Float16* __
 #pragma unroll
     for (int d = 0; d < DT; ++d) o[t][d] = (f4){0.f, 0.f, 0.f, 0.f};
   }
-  const int nchunks = (T + 31) >> 5, lastc = nchunks - 1;
+  // segmented decode (kr != null): query row i sees keys [kr[2i], kr[2i+1]) only.  The host builds non-decreasing ranges, so the
+  // workgroup's keys are [lo of its first row, hi of its last row) and the chunks outside it are skipped, not masked.
+  int klo[QT], khi[QT];
+#pragma unroll
+  for (int t = 0; t < QT; ++t) {
+    const int qi = min(q0 + 16 * t + r, T - 1);
+    klo[t] = kr ? kr[2 * qi] : 0;
+    khi[t] = kr ? kr[2 * qi + 1] : T;
+  }
+  const int c0 = kr ? kr[2 * q0] >> 5 : 0;
+  const int nchunks = kr ? (kr[2 * min(q0 + BQ - 1, T - 1) + 1] + 31) >> 5 : (T + 31) >> 5, lastc = nchunks - 1;
   struct KV { h8 ka[KS], kb[KS]; h8 v[DT]; };
   auto fetch = [&](KV& f, int c) {
     const int key0 = c << 5;
@@ -296,8 +306,9 @@ __global__ __launch_bounds__(256) void flash_rel96_f16_kernel(const _Float16* __
       float p[8];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        p[i] = (valid && key0 + 8 * g + i < T) ? sa[i] * scale : -INFINITY;
-        p[4 + i] = (valid && key0 + 8 * g + 4 + i < T) ? sb[i] * scale : -INFINITY;
+        const int ja = key0 + 8 * g + i, jb = ja + 4;
+        p[i] = (valid && ja >= klo[t] && ja < khi[t]) ? sa[i] * scale : -INFINITY;
+        p[4 + i] = (valid && jb >= klo[t] && jb < khi[t]) ? sb[i] * scale : -INFINITY;
       }
       const int qt0 = q0 + 16 * t;
       if (valid && key0 + 31 >= qt0 - W && key0 <= qt0 + 15 + W) {      // wave-uniform: this chunk touches the diagonal band
@@ -306,7 +317,7 @@ __global__ __launch_bounds__(256) void flash_rel96_f16_kernel(const _Float16* __
         for (int i = 0; i < 8; ++i) {
           const int j = key0 + 8 * g + i;
           const int rp = j - qi + W;
-          if (rp >= 0 && rp < NB && j < T && qi < T) {
+          if (rp >= 0 && rp < NB && j >= klo[t] && j < khi[t] && qi < T) {
             p[i] += Bias[(16 * t + r) * NB + rp];
             Sb[(16 * t + r) * NB + rp] = p[i];
           }
@@ -317,11 +328,12 @@ __global__ __launch_bounds__(256) void flash_rel96_f16_kernel(const _Float16* __
       for (int i = 0; i < 8; ++i) mx = fmaxf(mx, p[i]);
       mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
       mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      const float mnew = fmaxf(m[t], mx);
-      const float alpha = __expf(m[t] - mnew);
+      // a segmented row may meet a chunk with none of its keys before any of them: keep exp(-inf - -inf) out of m / l / o
+      const float mnew = fmaxf(m[t], mx), msafe = mnew == -INFINITY ? 0.f : mnew;
+      const float alpha = __expf(m[t] - msafe);
       float ps = 0.f;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) { p[i] = __expf(p[i] - mnew); ps += p[i]; }
+      for (int i = 0; i < 8; ++i) { p[i] = __expf(p[i] - msafe); ps += p[i]; }
       ps += __shfl_xor(ps, 16, 64);
       ps += __shfl_xor(ps, 32, 64);
       l[t] = l[t] * alpha + ps;
@@ -335,8 +347,8 @@ __global__ __launch_bounds__(256) void flash_rel96_f16_kernel(const _Float16* __
     }
   };
   KV fA, fB;
-  fetch(fA, min(wave, lastc));
-  for (int c = wave; c < nchunks; c += 8) {
+  fetch(fA, min(c0 + wave, lastc));
+  for (int c = c0 + wave; c < nchunks; c += 8) {
     fetch(fB, min(c + 4, lastc));
     GSV_PIN();
     process(fA, c, true);
@@ -379,7 +391,7 @@ __global__ __launch_bounds__(256) void flash_rel96_f16_kernel(const _Float16* __
 
 // self-attention with relative positions (window 4), fp16, head dim 96; vt_buf: heads * 96 * ceil32(T) halfs of scratch
 int launch_flash_rel96_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldvv, void* vt_buf, int T, int heads,
-                           float scale, const float* rel_k, const float* rel_v, void* out, int ldo, hipStream_t s) {
+                           float scale, const float* rel_k, const float* rel_v, void* out, int ldo, hipStream_t s, const int* kr) {
   GSV_REQUIRE(T >= 1 && heads >= 1 && rel_k && rel_v, "flash_rel96: bad argument");
   GSV_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldo % 4 == 0 && ((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)out % 8) == 0 &&
               ((uintptr_t)rel_v % 16) == 0, "flash_rel96: operands must be 16-byte aligned with leading dims multiple of 8");
@@ -393,7 +405,7 @@ int launch_flash_rel96_f16(const void* q, int ldq, const void* k, int ldk, const
     attr = true;
   }
   hipLaunchKernelGGL(flash_rel96_f16_kernel<QT>, dim3(cdiv(T, 16 * QT), heads), dim3(256), lds, s, (const _Float16*)q, ldq,
-                     (const _Float16*)k, ldk, (const _Float16*)vt_buf, ldv, T, scale, rel_k, rel_v, (_Float16*)out, ldo);
+                     (const _Float16*)k, ldk, (const _Float16*)vt_buf, ldv, T, scale, rel_k, rel_v, (_Float16*)out, ldo, kr);
   GSV_HIP(hipGetLastError());
   return GSV_OK;
 }

@@ -169,6 +169,12 @@ struct ConvArgs {
   int rope_half = 0, rope_q0 = 0, rope_k0 = 0;
   int z_res = 0;                             // batched launch (Z > 1) whose residual has its own slice stride rz: takes the LDS GEMM
                                              // path (bwe.hip; other batched launches with a residual keep the generic kernel)
+  // segmented decode (vits.hip gsv_vits_decode_segments): one int32 per OUTPUT row, the row's segment or -1 for a gap row.
+  // A gap row is stored as 0 whatever the conv computes (bias, residual, accumulate included).  launch_conv_gemm applies it
+  // in a row pass after the conv kernel (launch_seg_rows), so a masked launch takes the same instantiation and records the
+  // same route as an unmasked one, and the conv kernels never read it: their code and registers are the unmasked ones.
+  // Null = unmasked.  (One 8-byte field: three of them regrouped the kernel arguments and cost gemm_lds a 64-byte spill.)
+  const int* row_seg = nullptr;
 };
 // Route record (gsv_debug_last_conv_route): every launch site of launch_conv_gemm / launch_conv_pair stores which kernel
 // instantiation it launched, as one 64-bit code of byte fields (include/gsv.h has the layout).  A plain store on the host:
@@ -185,6 +191,10 @@ constexpr int route_flags(bool res, bool accu, bool allw = false, bool wnt = fal
   return (res ? ROUTE_RES : 0) | (accu ? ROUTE_ACCU : 0) | (allw ? ROUTE_ALLW : 0) | (wnt ? ROUTE_WNT : 0);
 }
 void set_conv_route(unsigned long long code);
+// the row pass of a segmented launch (ConvArgs::row_seg): gap rows of y [rows][ldy] (columns col0 .. col0 + C) to 0, and with a
+// per-segment bias table tab [n][ldb], segment rows + tab[row_seg[t]] (the per-segment voice biases of gsv_vits_decode_segments)
+int launch_seg_rows(int dtype, int out_f32, void* y, int ldy, int col0, int C, int rows, const int* row_seg, const float* tab, int ldb,
+                    hipStream_t s);
 
 int launch_conv_gemm(int dtype, const ConvArgs& a, hipStream_t s);
 // split-K-in-workgroup streaming GEMM for under-filled grids (gemm_sk.hip): 0 = launched, 1 = not eligible, <0 = error
@@ -217,11 +227,13 @@ int launch_flash_attn64_f16(const void* q, int ldq, const void* k, int ldk, cons
 
 // enc_p self-attention with window-4 relative positions, fp16, head dim 96 (attn.hip)
 int launch_flash_rel96_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* vt_buf, int T, int heads,
-                           float scale, const float* rel_k, const float* rel_v, void* out, int ldo, hipStream_t s);
+                           float scale, const float* rel_k, const float* rel_v, void* out, int ldo, hipStream_t s,
+                           const int* kr = nullptr);   // kr: per-query key range [kr[2i], kr[2i+1]), non-decreasing (block-diagonal)
 
 // elementwise / small ops (ops.hip)
 int launch_layernorm(int dtype, const void* x, int x_f32, const void* res, int res_f32, const float* gamma,
-                     const float* beta, void* y, int y_f32, int rows, int C, float eps, hipStream_t s);
+                     const float* beta, void* y, int y_f32, int rows, int C, float eps, hipStream_t s,
+                     const int* row_seg = nullptr);   // row_seg: gap rows (-1) are stored as 0 (ConvArgs::row_seg)
 int launch_convert(const float* src, void* dst, int dtype, long long n, hipStream_t s);
 
 }  // namespace gsv

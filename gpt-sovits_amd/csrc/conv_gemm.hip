@@ -217,7 +217,43 @@ template <typename T> static int launch_t(const ConvArgs& a, hipStream_t s) {
   return GSV_OK;
 }
 
-int launch_conv_gemm(int dtype, const ConvArgs& a_in, hipStream_t s) {
+// segmented decode (ConvArgs::row_seg), the row pass after a conv: 32 lanes per output row; a gap row is stored as 0, a segment
+// row adds its segment's bias row when there is a table, and any other row is left as the conv stored it
+template <typename T>
+__global__ __launch_bounds__(256) void seg_rows_kernel(void* __restrict__ y, int ldy, int col0, int C, int rows, const int* __restrict__ row_seg,
+                                                       const float* __restrict__ tab, int ldb) {
+  const int t = blockIdx.x * 8 + (threadIdx.x >> 5), lane = threadIdx.x & 31;
+  if (t >= rows) return;
+  const int sg = row_seg[t];
+  if (sg >= 0 && !tab) return;
+  T* p = (T*)y + (long long)t * ldy + col0;
+  if (sg < 0) { for (int c = lane; c < C; c += 32) p[c] = (T)0.f; return; }
+  const float* b = tab + (long long)sg * ldb;
+  for (int c = lane; c < C; c += 32) p[c] = (T)(to_f(p[c]) + b[c]);
+}
+
+int launch_seg_rows(int dtype, int out_f32, void* y, int ldy, int col0, int C, int rows, const int* row_seg, const float* tab, int ldb,
+                    hipStream_t s) {
+  if (!row_seg || rows <= 0) return GSV_OK;
+  if (out_f32 || dtype == GSV_F32)
+    hipLaunchKernelGGL(seg_rows_kernel<float>, dim3(cdiv(rows, 8)), dim3(256), 0, s, y, ldy, col0, C, rows, row_seg, tab, ldb);
+  else
+    hipLaunchKernelGGL(seg_rows_kernel<_Float16>, dim3(cdiv(rows, 8)), dim3(256), 0, s, y, ldy, col0, C, rows, row_seg, tab, ldb);
+  GSV_HIP(hipGetLastError());
+  return GSV_OK;
+}
+
+static int launch_conv_gemm_kernel(int dtype, const ConvArgs& a_in, hipStream_t s);
+
+int launch_conv_gemm(int dtype, const ConvArgs& a, hipStream_t s) {
+  if (!a.row_seg) return launch_conv_gemm_kernel(dtype, a, s);
+  GSV_REQUIRE(a.Z == 1 && !a.vt_out && !a.rope_cs, "conv_gemm: a segment mask needs a plain (Z = 1) launch");
+  GSV_RC(launch_conv_gemm_kernel(dtype, a, s));      // records the conv's route; the row pass records none
+  const int C = a.ups_u > 0 ? a.ups_cout : a.Cout;
+  return launch_seg_rows(dtype, a.out_f32, a.y, a.ldy ? a.ldy : C, a.y_col0, C, a.T_out, a.row_seg, nullptr, 0, s);
+}
+
+static int launch_conv_gemm_kernel(int dtype, const ConvArgs& a_in, hipStream_t s) {
   ConvArgs a = a_in;
   set_conv_route(0);
   if (a.T_virt == 0) a.T_virt = a.T_out;

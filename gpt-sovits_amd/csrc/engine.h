@@ -51,6 +51,17 @@ struct gsv_vits {
   float* ge = nullptr;         // fp32 [gin]
   void* ge_t = nullptr;        // T [gin]
   float* mo_bias_eff = nullptr;
+  // voice slots of the segmented decode (gsv_vits_store_voice): [GSV_VITS_MAX_VOICES][voice_len] fp32, one row per slot holding
+  // mo_bias_eff | conv_pre_bias_eff | the 16 WN in_bias_eff vectors (offsets voice_off_*)
+  float* voices = nullptr;
+  int voice_len = 0, voice_off_pre = 0, voice_off_in = 0;
+  std::vector<char> voice_ok;
+  std::vector<int> seg_host;                    // host image of the last segmented decode's maps (alive until its copy is done:
+  std::vector<unsigned long long> seed_host;    // seg_ev, recorded after the upload)
+  hipEvent_t seg_ev = nullptr;
+  hipStream_t ref_stream = nullptr;             // stream of the last set_refer (store_voice copies on it, then records ev[3])
+  const void* dbg_last_in = nullptr;            // input of the last generator stage (intact after a decode) for the debug hook
+  int dbg_last_T = 0, dbg_last_C = 0;
   // workspace
   std::map<std::string, Buf> bufs;
   // last decode bookkeeping
@@ -72,6 +83,7 @@ struct ConvOpt {
   // DiT QKV projection: rotary embedding + transposed V from the GEMM's epilogue (ConvArgs::vt_out ...)
   void* vt_out = nullptr; int vt_col0 = 0, vt_ld = 0;
   const float* rope_cs = nullptr; int rope_half = 0, rope_q0 = 0, rope_k0 = 0;
+  const int* row_seg = nullptr;   // segmented decode: gap rows of the output stored as 0 (ConvArgs::row_seg)
 };
 
 #define GSV_DISPATCH(h, call_f16, call_f32) \
@@ -95,7 +107,8 @@ int make_vec(gsv_vits* h, const std::string& name, size_t n, float** out);
 int need(gsv_vits* h, const char* name, size_t bytes, void** out);
 int conv(gsv_vits* h, hipStream_t s, const Conv& c, const void* x, int ldx, int T_in, void* y, int T_out, const ConvOpt& o);
 int attention(gsv_vits* h, hipStream_t s, const void* q, int ldq, int qcol0, const void* kv, int ldkv, int kcol0, int vcol0,
-              int Tq, int Tk, int nh, int kc, float scale, const float* rel_k, const float* rel_v, void* out, int ldo);
+              int Tq, int Tk, int nh, int kc, float scale, const float* rel_k, const float* rel_v, void* out, int ldo,
+              const int* kr = nullptr);   // kr: per-query key range [kr[2i], kr[2i+1]) (segmented decode)
 void free_ctx(gsv_vits* h);
 
 }  // namespace gsveng

@@ -34,10 +34,15 @@ int launch_convert(const float* src, void* dst, int dtype, long long n, hipStrea
 // One wave per row.  y = LN(x + res) * gamma + beta, statistics in fp32 (two-pass).
 template <typename TX, typename TR, typename TY>
 __global__ void layernorm_kernel(const TX* __restrict__ x, const TR* __restrict__ res, const float* __restrict__ gamma,
-                                 const float* __restrict__ beta, TY* __restrict__ y, int rows, int C, float eps) {
+                                 const float* __restrict__ beta, TY* __restrict__ y, int rows, int C, float eps,
+                                 const int* __restrict__ row_seg) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (row >= rows) return;
+  if (row_seg && row_seg[row] < 0) {           // segmented decode: a gap row is stored as 0 (ConvArgs::row_seg)
+    for (int c = lane; c < C; c += 64) y[(long long)row * C + c] = (TY)0.f;
+    return;
+  }
   const TX* xr = x + (long long)row * C;
   const TR* rr = res ? res + (long long)row * C : nullptr;
   if (C <= 512) {
@@ -84,24 +89,24 @@ __global__ void layernorm_kernel(const TX* __restrict__ x, const TR* __restrict_
 
 template <typename TX, typename TR, typename TY>
 static int ln_launch(const void* x, const void* res, const float* g, const float* b, void* y, int rows, int C, float eps,
-                     hipStream_t s) {
+                     hipStream_t s, const int* row_seg) {
   hipLaunchKernelGGL((layernorm_kernel<TX, TR, TY>), dim3(cdiv(rows, 4)), dim3(256), 0, s, (const TX*)x, (const TR*)res,
-                     g, b, (TY*)y, rows, C, eps);
+                     g, b, (TY*)y, rows, C, eps, row_seg);
   GSV_HIP(hipGetLastError());
   return GSV_OK;
 }
 
 int launch_layernorm(int dtype, const void* x, int x_f32, const void* res, int res_f32, const float* gamma,
-                     const float* beta, void* y, int y_f32, int rows, int C, float eps, hipStream_t s) {
+                     const float* beta, void* y, int y_f32, int rows, int C, float eps, hipStream_t s, const int* row_seg) {
   if (rows <= 0) return GSV_OK;
   const bool h = dtype == GSV_F16;
   const bool xf = x_f32 || !h, rf = res_f32 || !h, yf = y_f32 || !h;
-  if (xf && rf && yf) return ln_launch<float, float, float>(x, res, gamma, beta, y, rows, C, eps, s);
-  if (xf && rf && !yf) return ln_launch<float, float, _Float16>(x, res, gamma, beta, y, rows, C, eps, s);
-  if (xf && !rf && !yf) return ln_launch<float, _Float16, _Float16>(x, res, gamma, beta, y, rows, C, eps, s);
-  if (!xf && !rf && !yf) return ln_launch<_Float16, _Float16, _Float16>(x, res, gamma, beta, y, rows, C, eps, s);
-  if (!xf && !rf && yf) return ln_launch<_Float16, _Float16, float>(x, res, gamma, beta, y, rows, C, eps, s);
-  if (!xf && rf && !yf) return ln_launch<_Float16, float, _Float16>(x, res, gamma, beta, y, rows, C, eps, s);
+  if (xf && rf && yf) return ln_launch<float, float, float>(x, res, gamma, beta, y, rows, C, eps, s, row_seg);
+  if (xf && rf && !yf) return ln_launch<float, float, _Float16>(x, res, gamma, beta, y, rows, C, eps, s, row_seg);
+  if (xf && !rf && !yf) return ln_launch<float, _Float16, _Float16>(x, res, gamma, beta, y, rows, C, eps, s, row_seg);
+  if (!xf && !rf && !yf) return ln_launch<_Float16, _Float16, _Float16>(x, res, gamma, beta, y, rows, C, eps, s, row_seg);
+  if (!xf && !rf && yf) return ln_launch<_Float16, _Float16, float>(x, res, gamma, beta, y, rows, C, eps, s, row_seg);
+  if (!xf && rf && !yf) return ln_launch<_Float16, float, _Float16>(x, res, gamma, beta, y, rows, C, eps, s, row_seg);
   set_error("layernorm: unsupported dtype combination");
   return GSV_ERR_ARG;
 }

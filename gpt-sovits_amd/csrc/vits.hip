@@ -27,6 +27,41 @@ __global__ void gather_rows_kernel(const int* __restrict__ idx, const float* __r
   for (int c = threadIdx.x; c < C; c += blockDim.x) dst[c] = (T)src[c];
 }
 
+// segmented decode: out[row][c] = table[ids[src[row]]][c], or 0 for a gap row (src[row] < 0)
+template <typename T>
+__global__ void gather_seg_kernel(const int* __restrict__ ids, const int* __restrict__ src, const float* __restrict__ table, int C,
+                                  int rows, T* __restrict__ out) {
+  const int row = blockIdx.x;
+  if (row >= rows) return;
+  const int i = src[row];
+  T* dst = out + (long long)row * C;
+  if (i < 0) { for (int c = threadIdx.x; c < C; c += blockDim.x) dst[c] = (T)0.f; return; }
+  const float* sp = table + (long long)ids[i] * C;
+  for (int c = threadIdx.x; c < C; c += blockDim.x) dst[c] = (T)sp[c];
+}
+
+// segment map of an upsampled resolution: every boundary (segment start, length, gap) scales by the same factor `up`
+__global__ void expand_seg_kernel(const int* __restrict__ seg, int up, long long n, int* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = seg[i / up];
+}
+
+// per-segment bias table: out[s][:] = slots[slot_of[s]][:]
+__global__ void gather_voice_kernel(const float* __restrict__ slots, const int* __restrict__ slot_of, int vs, float* __restrict__ out) {
+  const int sg = blockIdx.x;
+  const float* src = slots + (long long)slot_of[sg] * vs;
+  for (int i = threadIdx.x; i < vs; i += blockDim.x) out[(long long)sg * vs + i] = src[i];
+}
+
+// drop the gaps from the padded waveform: segment s's samples move left by s gaps of `gap` samples
+__global__ void compact_wav_kernel(const float* __restrict__ src, const int* __restrict__ seg_f, int up, long long gap, long long n,
+                                   float* __restrict__ wav) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const int sg = seg_f[t / up];
+  if (sg >= 0) wav[t - sg * gap] = src[t];
+}
+
 // fp32 channels-first [C_total][T] -> T channels-last [T][C] (first C channels)
 template <typename T>
 __global__ void cf_to_cl_kernel(const float* __restrict__ src, int Tn, int C, T* __restrict__ dst, int ldd = 0) {
@@ -137,10 +172,17 @@ template <typename T>
 __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restrict__ scores, int Tq, int Tk, int ldp,
                                                            T* __restrict__ P, const T* __restrict__ q, int ldq, int kc,
                                                            const float* __restrict__ rel_k, int w, float qscale,
-                                                           float* __restrict__ band) {
+                                                           float* __restrict__ band, const int* __restrict__ kr) {
   const int i = blockIdx.x, z = blockIdx.y;
   const float* srow = scores + ((long long)z * Tq + i) * Tk;
   T* prow = P + ((long long)z * Tq + i) * ldp;
+  // segmented decode (kr != null): row i sees keys [kr[2i], kr[2i+1]) only; an empty range gives a zero row
+  const int klo = kr ? kr[2 * i] : 0, khi = kr ? kr[2 * i + 1] : Tk;
+  if (khi <= klo) {
+    for (int j = threadIdx.x; j < ldp; j += 256) prow[j] = (T)0.f;
+    if (w > 0 && threadIdx.x < 2 * w + 1) band[((long long)z * Tq + i) * (2 * w + 1) + threadIdx.x] = 0.f;
+    return;
+  }
   __shared__ float s_bias[16];
   __shared__ float s_red[8];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -162,6 +204,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
   for (int j = tid; j < Tk; j += 256) {
     float v = srow[j];
     if (w > 0) { int r = j - i + w; if (r >= 0 && r <= 2 * w) v += s_bias[r]; }
+    if (j < klo || j >= khi) v = -INFINITY;
     if (cached) s_row[j] = v;
     m = fmaxf(m, v);
   }
@@ -176,6 +219,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
     else {
       v = srow[j];
       if (w > 0) { int r = j - i + w; if (r >= 0 && r <= 2 * w) v += s_bias[r]; }
+      if (j < klo || j >= khi) v = -INFINITY;
     }
     const float e = expf(v - m);
     if (cached) s_row[j] = e;
@@ -195,7 +239,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
       else {
         float v = srow[j];
         if (inband) v += s_bias[r];
-        p = expf(v - m) * inv;
+        p = (j < klo || j >= khi) ? 0.f : expf(v - m) * inv;
       }
       if (inband) band[((long long)z * Tq + i) * (2 * w + 1) + r] = p;
     }
@@ -203,7 +247,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
   }
   if (w > 0 && tid < 2 * w + 1) {
     int j = i + tid - w;
-    if (j < 0 || j >= Tk) band[((long long)z * Tq + i) * (2 * w + 1) + tid] = 0.f;
+    if (j < 0 || j >= Tk || j < klo || j >= khi) band[((long long)z * Tq + i) * (2 * w + 1) + tid] = 0.f;
   }
 }
 
@@ -258,21 +302,34 @@ __device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
 }
 
 // z_p[t][c] = m + noise * exp(logs) * scale   (models.py:1000); noise fp32 channels-first or counter RNG
+// segmented decode (seg != null): a gap row is 0; segment s draws with its own seeds[s] and segment-local element index, and
+// reads explicit noise [C][Fn] (segments packed without gaps) at column noff[s] + local frame -- each segment's noise is the
+// one its own gsv_vits_decode would draw
 template <typename T>
 __global__ void zp_kernel(const float* __restrict__ stats, int F, int C, const float* __restrict__ noise, float scale,
-                          unsigned long long seed, T* __restrict__ z) {
+                          unsigned long long seed, T* __restrict__ z, const int* __restrict__ seg, const int* __restrict__ start,
+                          const int* __restrict__ noff, const unsigned long long* __restrict__ seeds, int Fn) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)F * C) return;
   int t = (int)(i / C), c = (int)(i - (long long)t * C);
   float m = stats[(long long)t * 2 * C + c], ls = stats[(long long)t * 2 * C + C + c];
+  int tn = t, ldn = F;
+  if (seg) {
+    const int sg = seg[t];
+    if (sg < 0) { z[i] = (T)0.f; return; }
+    const int tl = t - start[sg];
+    seed = seeds[sg];
+    tn = noff[sg] + tl; ldn = Fn;
+    i = (long long)tl * C + c;
+  }
   float n;
-  if (noise) n = noise[(long long)c * F + t];
+  if (noise) n = noise[(long long)c * ldn + tn];
   else {
     unsigned long long h1 = mix64(seed ^ mix64((unsigned long long)i * 2 + 1)), h2 = mix64(seed ^ mix64((unsigned long long)i * 2 + 2));
     float u1 = ((float)(h1 >> 40) + 1.0f) * (1.0f / 16777217.0f), u2 = (float)(h2 >> 40) * (1.0f / 16777216.0f);
     n = sqrtf(-2.f * logf(u1)) * cosf(6.28318530718f * u2);
   }
-  z[i] = (T)(m + n * expf(ls) * scale);
+  z[(long long)t * C + c] = (T)(m + n * expf(ls) * scale);
 }
 
 // out[c] (+)= mean_t x[t][c] * wgt
@@ -525,6 +582,7 @@ int conv(gsv_vits* h, hipStream_t s, const Conv& c, const void* x, int ldx, int 
   a.y_col0 = o.y_col0;
   a.vt_out = o.vt_out; a.vt_col0 = o.vt_col0; a.vt_ld = o.vt_ld;
   a.rope_cs = o.rope_cs; a.rope_half = o.rope_half; a.rope_q0 = o.rope_q0; a.rope_k0 = o.rope_k0;
+  a.row_seg = o.row_seg;
   return launch_conv_gemm(h->dtype, a, s);
 }
 
@@ -532,14 +590,14 @@ int conv(gsv_vits* h, hipStream_t s, const Conv& c, const void* x, int ldx, int 
 // materialised multi-head attention: q [Tq][ldq] cols qcol0.., k/v [Tk][ldkv] cols kcol0/vcol0..
 // -> out [Tq][ldo] (heads concatenated).  rel_k/rel_v non-null: window-4 relative positions.
 int attention(gsv_vits* h, hipStream_t s, const void* q, int ldq, int qcol0, const void* kv, int ldkv, int kcol0, int vcol0,
-              int Tq, int Tk, int nh, int kc, float scale, const float* rel_k, const float* rel_v, void* out, int ldo) {
+              int Tq, int Tk, int nh, int kc, float scale, const float* rel_k, const float* rel_v, void* out, int ldo, const int* kr) {
   const size_t es = esz(h);
   static const bool no_flash = getenv("GSV_MATERIALIZED_ENC_ATTN") != nullptr;    // A/B switch
   if (!no_flash && h->dtype == GSV_F16 && kc == 96 && rel_k && rel_v && Tq == Tk && q == kv && ldq == ldkv) {
     void* vtb;
     GSV_RC(need(h, "att_vt96", (size_t)nh * 96 * ((Tk + 31) / 32 * 32) * 2, &vtb));
     return launch_flash_rel96_f16((const _Float16*)q + qcol0, ldq, (const _Float16*)kv + kcol0, ldkv, (const _Float16*)kv + vcol0, ldkv,
-                                  vtb, Tq, nh, scale, rel_k, rel_v, out, ldo, s);
+                                  vtb, Tq, nh, scale, rel_k, rel_v, out, ldo, s, kr);
   }
   const int G = h->dtype == GSV_F16 ? 8 : 4;
   const int ldp = (Tk + G - 1) / G * G;
@@ -557,9 +615,9 @@ int attention(gsv_vits* h, hipStream_t s, const void* q, int ldq, int qcol0, con
   const int w = rel_k ? 4 : 0;
   GSV_DISPATCH(h,
     hipLaunchKernelGGL(softmax_rows_kernel<_Float16>, dim3(Tq, nh), dim3(256), Tk <= 12288 ? (size_t)Tk * 4 : 0, s, (const float*)scores, Tq, Tk, ldp, (_Float16*)P,
-                       (const _Float16*)q + qcol0, ldq, kc, rel_k, w, scale, (float*)band),
+                       (const _Float16*)q + qcol0, ldq, kc, rel_k, w, scale, (float*)band, kr),
     hipLaunchKernelGGL(softmax_rows_kernel<float>, dim3(Tq, nh), dim3(256), Tk <= 12288 ? (size_t)Tk * 4 : 0, s, (const float*)scores, Tq, Tk, ldp, (float*)P,
-                       (const float*)q + qcol0, ldq, kc, rel_k, w, scale, (float*)band));
+                       (const float*)q + qcol0, ldq, kc, rel_k, w, scale, (float*)band, kr));
   GSV_DISPATCH(h,
     hipLaunchKernelGGL(transpose_v_kernel<_Float16>, dim3(cdiv(ldp, 32), cdiv(kc, 32), nh), dim3(256), 0, s, (const _Float16*)kv, ldkv,
                        vcol0, kc, Tk, ldp, (_Float16*)Vt),
@@ -581,7 +639,9 @@ int attention(gsv_vits* h, hipStream_t s, const void* q, int ldq, int qcol0, con
 }
 
 // attentions.Encoder.forward (attentions.py:64-84) on x [Tn][H] in place
-int run_encoder(gsv_vits* h, hipStream_t s, std::vector<AttnLayerW>& layers, void* x, int Tn) {
+// segmented decode: row_seg masks the gap rows of what the FFN convs read, kr makes the self-attention block-diagonal
+int run_encoder(gsv_vits* h, hipStream_t s, std::vector<AttnLayerW>& layers, void* x, int Tn, const int* row_seg = nullptr,
+                const int* kr = nullptr) {
   const auto& c = h->cfg;
   const int H = c.hidden_channels, FC = c.filter_channels, kc = H / c.n_heads;
   const size_t es = esz(h);
@@ -593,13 +653,13 @@ int run_encoder(gsv_vits* h, hipStream_t s, std::vector<AttnLayerW>& layers, voi
   for (auto& L : layers) {
     ConvOpt o;
     GSV_RC(conv(h, s, L.qkv, x, H, Tn, qkv, Tn, o));
-    GSV_RC(attention(h, s, qkv, 3 * H, 0, qkv, 3 * H, H, 2 * H, Tn, Tn, c.n_heads, kc, 1.f / sqrtf((float)kc), L.rel_k, L.rel_v, ao, H));
+    GSV_RC(attention(h, s, qkv, 3 * H, 0, qkv, 3 * H, H, 2 * H, Tn, Tn, c.n_heads, kc, 1.f / sqrtf((float)kc), L.rel_k, L.rel_v, ao, H, kr));
     GSV_RC(conv(h, s, L.o, ao, H, Tn, y, Tn, o));
-    GSV_RC(launch_layernorm(h->dtype, x, 0, y, 0, L.g1, L.b1, x, 0, Tn, H, 1e-5f, s));
-    ConvOpt o1; o1.post_act = ACT_RELU;
+    GSV_RC(launch_layernorm(h->dtype, x, 0, y, 0, L.g1, L.b1, x, 0, Tn, H, 1e-5f, s, row_seg));
+    ConvOpt o1; o1.post_act = ACT_RELU; o1.row_seg = row_seg;
     GSV_RC(conv(h, s, L.f1, x, H, Tn, ff, Tn, o1));
     GSV_RC(conv(h, s, L.f2, ff, FC, Tn, y, Tn, o));
-    GSV_RC(launch_layernorm(h->dtype, x, 0, y, 0, L.g2, L.b2, x, 0, Tn, H, 1e-5f, s));
+    GSV_RC(launch_layernorm(h->dtype, x, 0, y, 0, L.g2, L.b2, x, 0, Tn, H, 1e-5f, s, row_seg));
   }
   return GSV_OK;
 }
@@ -616,31 +676,108 @@ using namespace gsveng;
 
 namespace gsveng {
 
+// ---------------------------------------------------------------------------------------
+// segmented decode (gsv_vits_decode_segments): n independent sequences back to back on one time axis, G zero "gap" rows
+// between neighbours at the frame rate (G * prod(rates[:i]) after upsampling stage i) and G between their phones
+// ---------------------------------------------------------------------------------------
+// one-sided input reach of a conv with `taps` taps at dilation `dil` ("same" padding)
+static int reach(int taps, int dil) { return (taps - 1) / 2 * dil; }
+// the gap, in frames: at every resolution it covers the reach of each conv reading that resolution, so a conv of a segment row
+// reads zeros (its isolated zero padding) wherever it would reach past the segment's edge, and never the neighbour's rows
+int seg_gap(const gsv_vits_config& c) {
+  auto need_at = [](int r, long long cum) { return (int)((r + cum - 1) / cum); };
+  int g = 1;
+  g = std::max(g, reach(c.kernel_size, 1));      // encoder FFN convs (frame and text axes)
+  g = std::max(g, reach(5, 1));                  // flow WN in_layers (kernel 5, dilation rate 1)
+  g = std::max(g, reach(7, 1));                  // generator conv_pre
+  long long cum = 1;
+  for (int i = 0; i < c.n_ups; ++i) {
+    // ups[i] reads resolution `cum`: transposed conv, kernel k, stride u, padding (k - u) / 2; output row t reads input rows
+    // (t + p - j) / u, j < k: ceil((k - 1 - p) / u) to the left of a segment, floor((u - 1 + p) / u) to its right
+    const int u = c.up_rates[i], k = c.up_kernels[i], p = (k - u) / 2;
+    g = std::max(g, need_at(std::max((k - 1 - p + u - 1) / u, (u - 1 + p) / u), cum));
+    cum *= u;
+    for (int j = 0; j < c.n_resblocks; ++j)        // ResBlock1 convs1 (dilated) and convs2 (dilation 1); a conv_pair counts as both
+      for (int d = 0; d < 3; ++d) g = std::max(g, need_at(reach(c.rb_kernels[j], c.rb_dilations[j][d]), cum));
+  }
+  g = std::max(g, need_at(reach(7, 1), cum));    // conv_post
+  return g;
+}
+
+struct SegLayout {
+  int n = 0, G = 0, F = 0, L = 0, Fn = 0;        // frames / phones with gaps; Fn = frames without gaps
+  std::vector<int> f0, l0, c0, p0, fn0;          // per segment: first frame / phone row, first packed code / phone, packed frame
+};
+
+int seg_layout(const gsv_vits_config& c, int n, const int* code_lens, const int* phone_lens, SegLayout* o) {
+  GSV_REQUIRE(n >= 1 && n <= 4096 && code_lens && phone_lens, "vits segments: bad segment count %d", n);
+  o->n = n; o->G = seg_gap(c);
+  o->f0.resize(n); o->l0.resize(n); o->c0.resize(n); o->p0.resize(n); o->fn0.resize(n);
+  long long f = 0, l = 0, cc = 0, pp = 0;
+  for (int i = 0; i < n; ++i) {
+    GSV_REQUIRE(code_lens[i] >= 1 && phone_lens[i] >= 1, "vits segments: segment %d is empty (%d codes, %d phones)", i, code_lens[i],
+                phone_lens[i]);
+    if (i) { f += o->G; l += o->G; }
+    o->f0[i] = (int)f; o->l0[i] = (int)l; o->c0[i] = (int)cc; o->p0[i] = (int)pp; o->fn0[i] = (int)(2 * cc);
+    f += 2LL * code_lens[i]; l += phone_lens[i]; cc += code_lens[i]; pp += phone_lens[i];
+    GSV_REQUIRE(f < (1LL << 24) && l < (1LL << 24), "vits segments: too long");
+  }
+  o->F = (int)f; o->L = (int)l; o->Fn = (int)(2 * cc);
+  return GSV_OK;
+}
+
+// device side of one segmented decode
+struct SegRun {
+  const SegLayout* lay = nullptr;
+  const int *seg_f = nullptr, *seg_l = nullptr;          // segment id per frame row / phone row, -1 = gap
+  const int *kr_f = nullptr, *kr_l = nullptr, *kr_x = nullptr;   // key ranges: frame and text self-attention, MRTE (phones)
+  const int *src_code = nullptr, *src_phone = nullptr;   // packed code / phone index per row, -1 = gap
+  const int *start = nullptr, *noff = nullptr;           // per segment: first frame row, first packed noise column
+  const unsigned long long* seeds = nullptr;
+  std::vector<int*> seg_up;                              // segment id per row after each upsampling stage
+  const float* bias = nullptr;                           // per-segment voice rows [n][voice_len]
+};
+
 // quantizer.decode + nearest x2 (H8) and TextEncoder.forward up to (and including) the speed interpolation (H10, reference
 // module/models.py:199-231): returns the hidden sequence y [F][hidden] (what `enc_p` returns as its first value)
+// sr != null: segmented (speed 1), T / L are ignored for the padded totals of sr->lay
 int run_enc_p(gsv_vits* h, hipStream_t s, const int32_t* codes, int T, const int32_t* phones, int L, double speed, void** y_out,
-              int* F_out) {
+              int* F_out, const SegRun* sr = nullptr) {
   const auto& c = h->cfg;
   const size_t es = esz(h);
   const int H = c.hidden_channels, SSL = c.ssl_dim, MH = 512;
-  const int F0 = 2 * T;
-  const int F = (speed == 1.0) ? F0 : (int)((double)F0 / speed) + 1;   // frames after the speed interpolation
+  if (sr) L = sr->lay->L;
+  const int F0 = sr ? sr->lay->F : 2 * T;
+  const int F = (speed == 1.0 || sr) ? F0 : (int)((double)F0 / speed) + 1;   // frames after the speed interpolation
   // ---- H8: codebook gather + nearest x2
   void *q768, *y, *tx;
   GSV_RC(need(h, "q768", (size_t)F0 * SSL * es, &q768));
   GSV_RC(need(h, "enc_x", (size_t)F0 * H * es, &y));
   GSV_RC(need(h, "enc_tx", (size_t)L * H * es, &tx));
+  if (sr) {
+    GSV_DISPATCH(h,
+      hipLaunchKernelGGL(gather_seg_kernel<_Float16>, dim3(F0), dim3(128), 0, s, codes, sr->src_code, h->codebook, SSL, F0, (_Float16*)q768),
+      hipLaunchKernelGGL(gather_seg_kernel<float>, dim3(F0), dim3(128), 0, s, codes, sr->src_code, h->codebook, SSL, F0, (float*)q768));
+  } else {
   GSV_DISPATCH(h,
     hipLaunchKernelGGL(gather_rows_kernel<_Float16>, dim3(F0), dim3(128), 0, s, codes, h->codebook, SSL, 2, T, (_Float16*)q768),
     hipLaunchKernelGGL(gather_rows_kernel<float>, dim3(F0), dim3(128), 0, s, codes, h->codebook, SSL, 2, T, (float*)q768));
+  }
   // ---- H10: enc_p
+  const int *seg_f = sr ? sr->seg_f : nullptr, *kr_f = sr ? sr->kr_f : nullptr;
   ConvOpt o;
   GSV_RC(conv(h, s, h->ssl_proj_enc, q768, SSL, F0, y, F0, o));
-  GSV_RC(run_encoder(h, s, h->enc_ssl, y, F0));
+  GSV_RC(run_encoder(h, s, h->enc_ssl, y, F0, seg_f, kr_f));
+  if (sr) {
+    GSV_DISPATCH(h,
+      hipLaunchKernelGGL(gather_seg_kernel<_Float16>, dim3(L), dim3(128), 0, s, phones, sr->src_phone, h->text_emb, H, L, (_Float16*)tx),
+      hipLaunchKernelGGL(gather_seg_kernel<float>, dim3(L), dim3(128), 0, s, phones, sr->src_phone, h->text_emb, H, L, (float*)tx));
+  } else {
   GSV_DISPATCH(h,
     hipLaunchKernelGGL(gather_rows_kernel<_Float16>, dim3(L), dim3(128), 0, s, phones, h->text_emb, H, 1, L, (_Float16*)tx),
     hipLaunchKernelGGL(gather_rows_kernel<float>, dim3(L), dim3(128), 0, s, phones, h->text_emb, H, 1, L, (float*)tx));
-  GSV_RC(run_encoder(h, s, h->enc_text, tx, L));
+  }
+  GSV_RC(run_encoder(h, s, h->enc_text, tx, L, sr ? sr->seg_l : nullptr, sr ? sr->kr_l : nullptr));
   {  // MRTE (mrte_model.py:25-44)
     void *s512, *t512, *q512, *kv512, *o512, *x512;
     GSV_RC(need(h, "m_s", (size_t)F0 * MH * es, &s512));
@@ -653,12 +790,16 @@ int run_enc_p(gsv_vits* h, hipStream_t s, const int32_t* codes, int T, const int
     GSV_RC(conv(h, s, h->text_pre, tx, H, L, t512, L, o));
     GSV_RC(conv(h, s, h->mq, s512, MH, F0, q512, F0, o));
     GSV_RC(conv(h, s, h->mkv, t512, MH, L, kv512, L, o));
-    GSV_RC(attention(h, s, q512, MH, 0, kv512, 2 * MH, 0, MH, F0, L, 4, MH / 4, 1.f / sqrtf((float)(MH / 4)), nullptr, nullptr, o512, MH));
+    GSV_RC(attention(h, s, q512, MH, 0, kv512, 2 * MH, 0, MH, F0, L, 4, MH / 4, 1.f / sqrtf((float)(MH / 4)), nullptr, nullptr, o512, MH,
+                     sr ? sr->kr_x : nullptr));
     ConvOpt om; om.res = s512; om.ldr = MH; om.bias_override = h->mo_bias_eff;
+    if (sr) om.bias_override = sr->bias;                  // one segment: its voice row
+    if (seg_f) om.no_bias = true;                         // several: each segment's voice row in the row pass below
     GSV_RC(conv(h, s, h->mo, o512, MH, F0, x512, F0, om));
+    if (seg_f) GSV_RC(launch_seg_rows(h->dtype, 0, x512, MH, 0, MH, F0, seg_f, sr->bias, h->voice_len, s));
     GSV_RC(conv(h, s, h->c_post, x512, MH, F0, y, F0, o));
   }
-  GSV_RC(run_encoder(h, s, h->enc2, y, F0));
+  GSV_RC(run_encoder(h, s, h->enc2, y, F0, seg_f, kr_f));
   if (F != F0) {
     void* yi;
     GSV_RC(need(h, "enc_x_speed", (size_t)F * H * es, &yi));
@@ -697,6 +838,7 @@ void gsv_vits_destroy(gsv_vits_t* h) {
   for (void* p : h->allocs) (void)hipFree(p);
   for (auto& b : h->bufs) if (b.second.p) (void)hipFree(b.second.p);
   for (auto e : h->ev) if (e) (void)hipEventDestroy(e);
+  if (h->seg_ev) (void)hipEventDestroy(h->seg_ev);
   delete h;
 }
 
@@ -845,6 +987,7 @@ static int set_refer_impl(gsv_vits_t* h, const float* const* specs, const int* f
   GSV_REQUIRE(specs && frames && n_refs >= 1, "vits_set_refer: no reference spectrogram");
   GSV_REQUIRE(bins >= h->cfg.ref_bins, "vits_set_refer: spectrogram has %d bins, need >= %d", bins, h->cfg.ref_bins);
   hipStream_t s = (hipStream_t)stream;
+  h->ref_stream = s;
   const auto& c = h->cfg;
   const size_t es = esz(h);
   const int RB = c.ref_bins, RH = 128, GIN = c.gin_channels;
@@ -926,21 +1069,17 @@ static int set_refer_impl(gsv_vits_t* h, const float* const* specs, const int* f
   return GSV_OK;
 }
 
-int gsv_vits_decode(gsv_vits_t* h, const int32_t* codes, int T, const int32_t* phones, int L, const float* noise,
-                    float noise_scale, double speed, uint64_t seed, float* wav, gsv_stream_t stream) {
-  GSV_REQUIRE(h && h->finalized, "vits_decode: handle not finalized");
-  GSV_REQUIRE(h->has_ref, "vits_decode: call gsv_vits_set_refer first");
-  GSV_REQUIRE(codes && phones && wav && T >= 1 && L >= 1, "vits_decode: empty input (T=%d, L=%d)", T, L);
-  hipStream_t s = (hipStream_t)stream;
+}  // extern "C"
+
+namespace gsveng {
+// proj -> z_p -> flow reverse -> generator on the enc_p output y [F][hidden]; sr != null: segmented (gap rows masked, per-segment
+// voice biases and noise keys, the gaps dropped from the waveform)
+static int decode_tail(gsv_vits* h, hipStream_t s, void* y, int F, const float* noise, float noise_scale, uint64_t seed, float* wav,
+                       const SegRun* sr) {
   const auto& c = h->cfg;
   const size_t es = esz(h);
   const int H = c.hidden_channels, IC = c.inter_channels;
-  GSV_REQUIRE(speed > 0.0, "vits_decode: speed must be positive");
-  GSV_REQUIRE(c.flavor == 0, "vits_decode: this handle is a v3/v4 model (use gsv_vits_decode_encp + gsv_cfm_inference + a vocoder)");
-  GSV_HIP(hipEventRecord(h->ev[0], s));
-  void* y = nullptr;
-  int F = 0;
-  GSV_RC(run_enc_p(h, s, codes, T, phones, L, speed, &y, &F));
+  const int* seg_f = sr ? sr->seg_f : nullptr;
   ConvOpt o;
   float* stats;
   GSV_RC(need(h, "stats", (size_t)F * 2 * IC * 4, (void**)&stats));
@@ -954,8 +1093,10 @@ int gsv_vits_decode(gsv_vits_t* h, const int32_t* codes, int T, const int32_t* p
   GSV_RC(need(h, "wn_acts", (size_t)F * H * es, &acts));
   GSV_RC(need(h, "wn_out", (size_t)F * H * es, &wout));
   GSV_DISPATCH(h,
-    hipLaunchKernelGGL(zp_kernel<_Float16>, dim3(nblk((long long)F * IC)), dim3(256), 0, s, stats, F, IC, noise, noise_scale, (unsigned long long)seed, (_Float16*)z),
-    hipLaunchKernelGGL(zp_kernel<float>, dim3(nblk((long long)F * IC)), dim3(256), 0, s, stats, F, IC, noise, noise_scale, (unsigned long long)seed, (float*)z));
+    hipLaunchKernelGGL(zp_kernel<_Float16>, dim3(nblk((long long)F * IC)), dim3(256), 0, s, stats, F, IC, noise, noise_scale, (unsigned long long)seed, (_Float16*)z,
+                       seg_f, sr ? sr->start : nullptr, sr ? sr->noff : nullptr, sr ? sr->seeds : nullptr, sr ? sr->lay->Fn : 0),
+    hipLaunchKernelGGL(zp_kernel<float>, dim3(nblk((long long)F * IC)), dim3(256), 0, s, stats, F, IC, noise, noise_scale, (unsigned long long)seed, (float*)z,
+                       seg_f, sr ? sr->start : nullptr, sr ? sr->noff : nullptr, sr ? sr->seeds : nullptr, sr ? sr->lay->Fn : 0));
   const int half = IC / 2;
   for (int fi = 3; fi >= 0; --fi) {
     FlowW& f = h->flows[fi];
@@ -963,15 +1104,20 @@ int gsv_vits_decode(gsv_vits_t* h, const int32_t* codes, int T, const int32_t* p
       hipLaunchKernelGGL(flip_channels_kernel<_Float16>, dim3(nblk((long long)F * IC)), dim3(256), 0, s, (const _Float16*)z, (long long)F * IC, IC, (_Float16*)zf),
       hipLaunchKernelGGL(flip_channels_kernel<float>, dim3(nblk((long long)F * IC)), dim3(256), 0, s, (const float*)z, (long long)F * IC, IC, (float*)zf));
     std::swap(z, zf);
-    GSV_RC(conv(h, s, f.pre, z, IC, F, hb, F, o));   // x0 = channels [0, half)
+    ConvOpt om; om.row_seg = seg_f;                  // what the WN in_layers (kernel 5) read: gap rows stay 0
+    GSV_RC(conv(h, s, f.pre, z, IC, F, hb, F, om));  // x0 = channels [0, half)
     for (int li = 0; li < 4; ++li) {
       ConvOpt oi; oi.bias_override = f.wn.in_bias_eff[li];
+      const float* vrow = sr ? sr->bias + h->voice_off_in + (size_t)(fi * 4 + li) * 2 * H : nullptr;
+      if (sr) oi.bias_override = vrow;
+      if (seg_f) oi.no_bias = true;                   // each segment's voice row in the row pass (xin feeds only the gate)
       GSV_RC(conv(h, s, f.wn.in[li], hb, H, F, xin, F, oi));
+      if (seg_f) GSV_RC(launch_seg_rows(h->dtype, 0, xin, 2 * H, 0, 2 * H, F, seg_f, vrow, h->voice_len, s));
       GSV_DISPATCH(h,
         hipLaunchKernelGGL(gate_kernel<_Float16>, dim3(nblk((long long)F * H)), dim3(256), 0, s, (const _Float16*)xin, (long long)F * H, H, (_Float16*)acts),
         hipLaunchKernelGGL(gate_kernel<float>, dim3(nblk((long long)F * H)), dim3(256), 0, s, (const float*)xin, (long long)F * H, H, (float*)acts));
       if (li < 3) {
-        ConvOpt ores; ores.cout = H; ores.w_row0 = 0; ores.accumulate = 1;        // h += rs[:H]
+        ConvOpt ores; ores.cout = H; ores.w_row0 = 0; ores.accumulate = 1; ores.row_seg = seg_f;   // h += rs[:H]
         GSV_RC(conv(h, s, f.wn.res[li], acts, H, F, hb, F, ores));
         ConvOpt osk; osk.cout = H; osk.w_row0 = H; osk.accumulate = li > 0;       // out (+)= rs[H:]
         GSV_RC(conv(h, s, f.wn.res[li], acts, H, F, wout, F, osk));
@@ -980,7 +1126,7 @@ int gsv_vits_decode(gsv_vits_t* h, const int32_t* codes, int T, const int32_t* p
         GSV_RC(conv(h, s, f.wn.res[li], acts, H, F, wout, F, osk));
       }
     }
-    ConvOpt op; op.scale = -1.f; op.accumulate = 1; op.ldy = IC; op.y_col0 = half;  // x1 -= post(h)
+    ConvOpt op; op.scale = -1.f; op.accumulate = 1; op.ldy = IC; op.y_col0 = half; op.row_seg = seg_f;  // x1 -= post(h)
     GSV_RC(conv(h, s, f.post, wout, H, F, z, F, op));
   }
   h->lastF = F;
@@ -1001,19 +1147,28 @@ int gsv_vits_decode(gsv_vits_t* h, const int32_t* codes, int T, const int32_t* p
   const char* gnames[5] = {"g0", "g1", "g2", "g3", "g4"};
   for (int i = 0; i < 5; ++i) GSV_RC(need(h, gnames[i], maxel * es, &gb[i]));
   void* cur = gb[3];
-  { ConvOpt op; op.bias_override = h->conv_pre_bias_eff; GSV_RC(conv(h, s, h->conv_pre, z, IC, F, cur, F, op)); }
+  { ConvOpt op; op.bias_override = h->conv_pre_bias_eff;
+    const float* vrow = sr ? sr->bias + h->voice_off_pre : nullptr;
+    if (sr) op.bias_override = vrow;
+    if (seg_f) op.no_bias = true;
+    GSV_RC(conv(h, s, h->conv_pre, z, IC, F, cur, F, op));
+    if (seg_f) GSV_RC(launch_seg_rows(h->dtype, 0, cur, c.upsample_initial_channel, 0, c.upsample_initial_channel, F, seg_f, vrow,
+                                      h->voice_len, s)); }
   int Tn = F, ch = c.upsample_initial_channel;
   for (int i = 0; i < c.n_ups; ++i) {
     const int Tout = Tn * c.up_rates[i];
     ch >>= 1;
     void* xup = gb[0]; void* xt = gb[1]; void* R = gb[2]; void* xs = (cur == gb[3]) ? gb[4] : gb[3];
-    { ConvOpt ou; ou.pre_act = ACT_LRELU; ou.pre_slope = 0.1f; GSV_RC(conv(h, s, h->ups[i], cur, ch * 2, Tn, xup, Tout, ou)); }
+    const int* seg_o = seg_f ? sr->seg_up[i] : nullptr;   // gap rows of this stage's outputs
+    h->dbg_last_in = cur; h->dbg_last_T = Tn; h->dbg_last_C = 2 * ch;
+    { ConvOpt ou; ou.pre_act = ACT_LRELU; ou.pre_slope = 0.1f; ou.row_seg = seg_o; GSV_RC(conv(h, s, h->ups[i], cur, ch * 2, Tn, xup, Tout, ou)); }
     for (int j = 0; j < c.n_resblocks; ++j) {
       const void* xr = xup;
       for (int k = 0; k < 3; ++k) {
         const Conv& c1 = h->rb1[(i * c.n_resblocks + j) * 3 + k];
         const Conv& c2 = h->rb2[(i * c.n_resblocks + j) * 3 + k];
-        if (c1.b && c2.b && c1.taps == c2.taps && conv_pair_eligible(h->dtype, ch, c1.taps, c.rb_dilations[j][k], Tout)) {
+        // (segmented: the two convs with their row passes; the fused pair's intermediate never leaves the CU)
+        if (!seg_o && c1.b && c2.b && c1.taps == c2.taps && conv_pair_eligible(h->dtype, ch, c1.taps, c.rb_dilations[j][k], Tout)) {
           // narrow stages: the pair in one kernel, the intermediate tensor never leaves the CU (conv_pair.hip)
           ConvPairArgs pa;
           pa.x = (const _Float16*)xr; pa.w1 = (const _Float16*)c1.w; pa.b1 = c1.b; pa.w2 = (const _Float16*)c2.w; pa.b2 = c2.b;
@@ -1026,9 +1181,9 @@ int gsv_vits_decode(gsv_vits_t* h, const int32_t* codes, int T, const int32_t* p
           if (k < 2) { if (pa.y == (_Float16*)xt) { std::swap(xt, R); } xr = R; }
           continue;
         }
-        ConvOpt o1; o1.pre_act = ACT_LRELU; o1.pre_slope = 0.1f; o1.dil = c.rb_dilations[j][k];
+        ConvOpt o1; o1.pre_act = ACT_LRELU; o1.pre_slope = 0.1f; o1.dil = c.rb_dilations[j][k]; o1.row_seg = seg_o;
         GSV_RC(conv(h, s, c1, xr, ch, Tout, xt, Tout, o1));
-        ConvOpt o2; o2.pre_act = ACT_LRELU; o2.pre_slope = 0.1f; o2.res = xr; o2.ldr = ch;
+        ConvOpt o2; o2.pre_act = ACT_LRELU; o2.pre_slope = 0.1f; o2.res = xr; o2.ldr = ch; o2.row_seg = seg_o;
         if (k < 2) {
           GSV_RC(conv(h, s, c2, xt, ch, Tout, R, Tout, o2));
           xr = R;
@@ -1040,10 +1195,163 @@ int gsv_vits_decode(gsv_vits_t* h, const int32_t* codes, int T, const int32_t* p
     }
     cur = xs; Tn = Tout;
   }
+  float* wout_p = wav;                 // segmented: the padded waveform, then the gaps are dropped into wav
+  if (seg_f) GSV_RC(need(h, "wav_pad", (size_t)Tn * 4, (void**)&wout_p));
   { ConvOpt op; op.pre_act = ACT_LRELU; op.pre_slope = 0.01f; op.post_act = ACT_TANH; op.out_f32 = 1;
-    GSV_RC(conv(h, s, h->conv_post, cur, ch, Tn, wav, Tn, op)); }
+    GSV_RC(conv(h, s, h->conv_post, cur, ch, Tn, wout_p, Tn, op)); }
+  if (seg_f) {
+    const int up = Tn / F;
+    hipLaunchKernelGGL(compact_wav_kernel, dim3(nblk(Tn)), dim3(256), 0, s, (const float*)wout_p, seg_f, up, (long long)sr->lay->G * up,
+                       (long long)Tn, wav);
+    GSV_HIP(hipGetLastError());
+  }
   GSV_HIP(hipEventRecord(h->ev[2], s));
   return GSV_OK;
+}
+}  // namespace gsveng
+
+extern "C" {
+
+int gsv_vits_decode(gsv_vits_t* h, const int32_t* codes, int T, const int32_t* phones, int L, const float* noise,
+                    float noise_scale, double speed, uint64_t seed, float* wav, gsv_stream_t stream) {
+  GSV_REQUIRE(h && h->finalized, "vits_decode: handle not finalized");
+  GSV_REQUIRE(h->has_ref, "vits_decode: call gsv_vits_set_refer first");
+  GSV_REQUIRE(codes && phones && wav && T >= 1 && L >= 1, "vits_decode: empty input (T=%d, L=%d)", T, L);
+  hipStream_t s = (hipStream_t)stream;
+  GSV_REQUIRE(speed > 0.0, "vits_decode: speed must be positive");
+  GSV_REQUIRE(h->cfg.flavor == 0, "vits_decode: this handle is a v3/v4 model (use gsv_vits_decode_encp + gsv_cfm_inference + a vocoder)");
+  GSV_HIP(hipEventRecord(h->ev[0], s));
+  void* y = nullptr;
+  int F = 0;
+  GSV_RC(run_enc_p(h, s, codes, T, phones, L, speed, &y, &F));
+  return decode_tail(h, s, y, F, noise, noise_scale, seed, wav, nullptr);
+}
+
+int gsv_vits_segment_gap(const gsv_vits_config* cfg) {
+  if (!cfg || cfg->n_ups < 1 || cfg->n_ups > 8 || cfg->n_resblocks < 1 || cfg->n_resblocks > 4) return -1;
+  return seg_gap(*cfg);
+}
+
+int gsv_vits_segment_map(const gsv_vits_config* cfg, int n, const int* code_lens, const int* phone_lens, int level, int32_t* seg,
+                         int64_t cap, int64_t* rows) {
+  GSV_REQUIRE(cfg && rows && cfg->n_ups >= 1 && cfg->n_ups <= 8, "vits_segment_map: bad argument");
+  GSV_REQUIRE(level >= -1 && level <= cfg->n_ups, "vits_segment_map: level %d outside [-1, %d]", level, cfg->n_ups);
+  SegLayout lay;
+  GSV_RC(seg_layout(*cfg, n, code_lens, phone_lens, &lay));
+  long long up = 1;
+  for (int i = 0; i < level; ++i) up *= cfg->up_rates[i];
+  const long long nr = level < 0 ? lay.L : (long long)lay.F * up;
+  *rows = nr;
+  if (!seg) return GSV_OK;
+  GSV_REQUIRE(cap >= nr, "vits_segment_map: buffer holds %lld rows, need %lld", (long long)cap, nr);
+  for (long long t = 0; t < nr; ++t) seg[t] = -1;
+  for (int i = 0; i < n; ++i) {
+    const long long a = level < 0 ? lay.l0[i] : lay.f0[i] * up, len = level < 0 ? phone_lens[i] : 2LL * code_lens[i] * up;
+    for (long long t = a; t < a + len; ++t) seg[t] = i;
+  }
+  return GSV_OK;
+}
+
+int gsv_vits_store_voice(gsv_vits_t* h, int slot) {
+  GSV_REQUIRE(h && h->finalized, "vits_store_voice: handle not finalized");
+  GSV_REQUIRE(h->cfg.flavor == 0, "vits_store_voice: voice slots serve the v1/v2 segmented decode only");
+  GSV_REQUIRE(h->has_ref, "vits_store_voice: call gsv_vits_set_refer first");
+  GSV_REQUIRE(slot >= 0 && slot < GSV_VITS_MAX_VOICES, "vits_store_voice: slot %d outside [0, %d)", slot, GSV_VITS_MAX_VOICES);
+  const auto& c = h->cfg;
+  const int H2 = 2 * c.hidden_channels, UIC = c.upsample_initial_channel;
+  if (!h->voices) {
+    h->voice_off_pre = 512;
+    h->voice_off_in = (512 + UIC + 3) / 4 * 4;
+    h->voice_len = h->voice_off_in + 16 * H2;
+    GSV_RC(dalloc(h, (void**)&h->voices, (size_t)GSV_VITS_MAX_VOICES * h->voice_len * 4));
+    h->voice_ok.assign(GSV_VITS_MAX_VOICES, 0);
+  }
+  // stream-ordered after the set_refer that wrote the conditioning; decode_segments waits for ev[3]
+  hipStream_t s = h->ref_stream;
+  float* row = h->voices + (size_t)slot * h->voice_len;
+  GSV_HIP(hipMemcpyAsync(row, h->mo_bias_eff, 512 * 4, hipMemcpyDeviceToDevice, s));
+  GSV_HIP(hipMemcpyAsync(row + h->voice_off_pre, h->conv_pre_bias_eff, (size_t)UIC * 4, hipMemcpyDeviceToDevice, s));
+  for (int fi = 0; fi < 4; ++fi)
+    for (int li = 0; li < 4; ++li)
+      GSV_HIP(hipMemcpyAsync(row + h->voice_off_in + (size_t)(fi * 4 + li) * H2, h->flows[fi].wn.in_bias_eff[li], (size_t)H2 * 4,
+                             hipMemcpyDeviceToDevice, s));
+  GSV_HIP(hipEventRecord(h->ev[3], s));
+  h->voice_ok[slot] = 1;
+  return GSV_OK;
+}
+
+int gsv_vits_decode_segments(gsv_vits_t* h, int n, const int32_t* codes, const int* code_lens, const int32_t* phones,
+                             const int* phone_lens, const int* voice_slots, const uint64_t* seeds, const float* noise, float noise_scale,
+                             float* wav, gsv_stream_t stream) {
+  GSV_REQUIRE(h, "vits_decode_segments: null handle");
+  GSV_REQUIRE(h->cfg.flavor == 0, "vits_decode_segments: this handle is a v3/v4 model (segmented decode covers v1/v2 only)");
+  GSV_REQUIRE(h->finalized, "vits_decode_segments: handle not finalized");
+  GSV_REQUIRE(codes && phones && wav && code_lens && phone_lens && voice_slots && seeds && n >= 1, "vits_decode_segments: null argument");
+  for (int i = 0; i < n; ++i)
+    GSV_REQUIRE(voice_slots[i] >= 0 && voice_slots[i] < GSV_VITS_MAX_VOICES && h->voice_ok.size() && h->voice_ok[voice_slots[i]],
+                "vits_decode_segments: segment %d names voice slot %d, which holds no voice (gsv_vits_store_voice)", i, voice_slots[i]);
+  SegLayout lay;
+  GSV_RC(seg_layout(h->cfg, n, code_lens, phone_lens, &lay));
+  hipStream_t s = (hipStream_t)stream;
+  const int F = lay.F, L = lay.L;
+  // host image of every map, one upload: seg_f | seg_l | kr_f | kr_l | kr_x | src_code | src_phone | start | noff | slot
+  if (!h->seg_ev) GSV_HIP(hipEventCreateWithFlags(&h->seg_ev, hipEventDisableTiming));
+  GSV_HIP(hipEventSynchronize(h->seg_ev));   // the previous call's upload (any stream) is done before its host image is rewritten
+  GSV_HIP(hipStreamWaitEvent(s, h->ev[3], 0));   // the voice slots are stored
+  std::vector<int>& m = h->seg_host;
+  const size_t o_sf = 0, o_sl = o_sf + F, o_kf = o_sl + L, o_kl = o_kf + 2 * (size_t)F, o_kx = o_kl + 2 * (size_t)L,
+               o_sc = o_kx + 2 * (size_t)F, o_sp = o_sc + F, o_st = o_sp + L, o_no = o_st + n, o_vs = o_no + n, total = o_vs + n;
+  m.assign(total, -1);
+  for (int t = 0; t < F; ++t) { m[o_kf + 2 * t] = t; m[o_kf + 2 * t + 1] = t + 1; m[o_kx + 2 * t] = 0; m[o_kx + 2 * t + 1] = 0; }
+  for (int t = 0; t < L; ++t) { m[o_kl + 2 * t] = t; m[o_kl + 2 * t + 1] = t + 1; }
+  for (int i = 0; i < n; ++i) {
+    const int f0 = lay.f0[i], nf = 2 * code_lens[i], l0 = lay.l0[i], nl = phone_lens[i];
+    for (int t = f0; t < f0 + nf; ++t) {
+      m[o_sf + t] = i;
+      m[o_kf + 2 * t] = f0; m[o_kf + 2 * t + 1] = f0 + nf;
+      m[o_kx + 2 * t] = l0; m[o_kx + 2 * t + 1] = l0 + nl;
+      m[o_sc + t] = lay.c0[i] + (t - f0) / 2;          // nearest x2 of the codes
+    }
+    for (int t = l0; t < l0 + nl; ++t) {
+      m[o_sl + t] = i;
+      m[o_kl + 2 * t] = l0; m[o_kl + 2 * t + 1] = l0 + nl;
+      m[o_sp + t] = lay.p0[i] + (t - l0);
+    }
+    m[o_st + i] = f0; m[o_no + i] = lay.fn0[i]; m[o_vs + i] = voice_slots[i];
+  }
+  h->seed_host.assign(seeds, seeds + n);
+  int* dm;
+  unsigned long long* dseed;
+  float* vb;
+  GSV_RC(need(h, "seg_maps", total * 4, (void**)&dm));
+  GSV_RC(need(h, "seg_seeds", (size_t)n * 8, (void**)&dseed));
+  GSV_RC(need(h, "seg_voices", (size_t)n * h->voice_len * 4, (void**)&vb));
+  GSV_HIP(hipMemcpyAsync(dm, m.data(), total * 4, hipMemcpyHostToDevice, s));
+  GSV_HIP(hipMemcpyAsync(dseed, h->seed_host.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+  GSV_HIP(hipEventRecord(h->seg_ev, s));
+  hipLaunchKernelGGL(gather_voice_kernel, dim3(n), dim3(256), 0, s, (const float*)h->voices, (const int*)(dm + o_vs), h->voice_len, vb);
+  SegRun sr;
+  sr.lay = &lay;
+  sr.seg_f = dm + o_sf; sr.seg_l = dm + o_sl; sr.kr_f = dm + o_kf; sr.kr_l = dm + o_kl; sr.kr_x = dm + o_kx;
+  sr.src_code = dm + o_sc; sr.src_phone = dm + o_sp; sr.start = dm + o_st; sr.noff = dm + o_no; sr.seeds = dseed; sr.bias = vb;
+  if (n == 1) {     // one segment is laid out exactly as gsv_vits_decode: no gaps, nothing to mask, its voice row as the bias
+    sr.seg_f = sr.seg_l = sr.kr_f = sr.kr_l = sr.kr_x = nullptr;
+  }
+  long long up = 1;
+  for (int i = 0; i < h->cfg.n_ups && n > 1; ++i) {
+    up *= h->cfg.up_rates[i];
+    const std::string nm = "seg_up" + std::to_string(i);
+    int* su;
+    GSV_RC(need(h, nm.c_str(), (size_t)F * up * 4, (void**)&su));
+    hipLaunchKernelGGL(expand_seg_kernel, dim3(nblk((long long)F * up)), dim3(256), 0, s, (const int*)sr.seg_f, (int)up, (long long)F * up, su);
+    sr.seg_up.push_back(su);
+  }
+  GSV_HIP(hipGetLastError());
+  GSV_HIP(hipEventRecord(h->ev[0], s));
+  void* y = nullptr;
+  int Fy = 0;
+  GSV_RC(run_enc_p(h, s, codes, 0, phones, L, 1.0, &y, &Fy, &sr));
+  return decode_tail(h, s, y, F, noise, noise_scale, seeds[0], wav, &sr);
 }
 
 int gsv_vits_encp_frames(gsv_vits_t* h, int T, double speed) {
@@ -1172,6 +1480,16 @@ int gsv_vits_debug_tensor(gsv_vits_t* h, const char* name, float* out, int64_t c
     return GSV_OK;
   }
   GSV_REQUIRE(F > 0, "vits_debug_tensor: no decode yet");
+  if (n == "gen_last_in") {        // input of the last generator stage, [C][T] (segmented decode: its gap rows are 0)
+    const long long ne = (long long)h->dbg_last_T * h->dbg_last_C;
+    GSV_REQUIRE(h->dbg_last_in && cap >= ne, "vits_debug_tensor: buffer too small");
+    *numel = ne;
+    GSV_DISPATCH(h,
+      hipLaunchKernelGGL(cl_to_cf_kernel<_Float16>, dim3(nblk(ne)), dim3(256), 0, s, (const _Float16*)h->dbg_last_in, h->dbg_last_T, h->dbg_last_C, 0, h->dbg_last_C, out),
+      hipLaunchKernelGGL(cl_to_cf_kernel<float>, dim3(nblk(ne)), dim3(256), 0, s, (const float*)h->dbg_last_in, h->dbg_last_T, h->dbg_last_C, 0, h->dbg_last_C, out));
+    GSV_HIP(hipGetLastError());
+    return GSV_OK;
+  }
   GSV_REQUIRE(cap >= (int64_t)F * IC, "vits_debug_tensor: buffer too small");
   *numel = (int64_t)F * IC;
   if (n == "m_p" || n == "logs_p") {
@@ -1183,7 +1501,7 @@ int gsv_vits_debug_tensor(gsv_vits_t* h, const char* name, float* out, int64_t c
       hipLaunchKernelGGL(cl_to_cf_kernel<_Float16>, dim3(nblk((long long)F * IC)), dim3(256), 0, s, (const _Float16*)z, F, IC, 0, IC, out),
       hipLaunchKernelGGL(cl_to_cf_kernel<float>, dim3(nblk((long long)F * IC)), dim3(256), 0, s, (const float*)z, F, IC, 0, IC, out));
   } else {
-    set_error("vits_debug_tensor: unknown tensor '%s' (ge, m_p, logs_p, z)", name);
+    set_error("vits_debug_tensor: unknown tensor '%s' (ge, m_p, logs_p, z, gen_last_in)", name);
     return GSV_ERR_ARG;
   }
   GSV_HIP(hipGetLastError());

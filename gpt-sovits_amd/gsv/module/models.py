@@ -171,6 +171,56 @@ class SynthesizerTrn:
         return wav.to(self.dtype).view(1, 1, -1)
 
     @torch.no_grad()
+    def decode_segments(self, codes_list, text_list, voices, seeds, noise_scale: float = 0.5,
+                        noise: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+        """Segmented decode (speed 1): segment s = (codes_list[s] [1,1,T_s], text_list[s] [1,L_s], voices[s], seeds[s]) in one
+        pass of enc_p, flow and generator (gsv_vits_decode_segments).  A voice is (refer, sv_emb) as taken by `decode`
+        (sv_emb None except for v2Pro / v2ProPlus); distinct voices are stored into slots once per call.  `noise`
+        (optional) holds one [inter, 2T_s] draw per segment.  Returns one waveform [1, 1, 2T_s * prod(upsample_rates)] per
+        segment, what `decode(codes_list[s], text_list[s], *voices[s], noise_scale, seed=seeds[s])` returns."""
+        if not self._loaded:
+            raise RuntimeError("load_state_dict() first")
+        n = len(codes_list)
+        if n == 0 or not (len(text_list) == len(voices) == len(seeds) == n):
+            raise ValueError("decode_segments: codes_list, text_list, voices and seeds must have the same non-zero length")
+        if noise is not None and len(noise) != n:
+            raise ValueError("decode_segments: one noise tensor per segment")
+        T = [int(c.shape[-1]) for c in codes_list]
+        L = [int(t.shape[-1]) for t in text_list]
+        up = math.prod(self.upsample_rates)
+        with torch.cuda.device(self.device):
+            slot_of, slots = {}, []
+            for refer, sv_emb in voices:
+                refs = list(refer) if isinstance(refer, (list, tuple)) else [refer]
+                svl = [] if sv_emb is None else (list(sv_emb) if isinstance(sv_emb, (list, tuple)) else [sv_emb])
+                key = tuple(id(r) for r in refs + svl)
+                if key not in slot_of:
+                    if len(slot_of) >= _lib.VITS_MAX_VOICES:
+                        raise ValueError(f"decode_segments: more than {_lib.VITS_MAX_VOICES} distinct voices in one call")
+                    self._set_refer(refer, sv_emb)
+                    _lib.check(_lib.lib().gsv_vits_store_voice(self._h, len(slot_of)), "gsv_vits_store_voice")
+                    slot_of[key] = len(slot_of)
+                slots.append(slot_of[key])
+            cd = torch.cat([c.reshape(-1) for c in codes_list]).to(self.device, torch.int32).contiguous()
+            tx = torch.cat([t.reshape(-1) for t in text_list]).to(self.device, torch.int32).contiguous()
+            nz = None
+            if noise is not None:
+                nz = torch.cat([z.reshape(self.inter_channels, 2 * t).to(self.device, torch.float32) for z, t in zip(noise, T)],
+                               dim=1).contiguous()
+            wav = torch.empty(2 * sum(T) * up, dtype=torch.float32, device=self.device)
+            cl, pl = (C.c_int * n)(*T), (C.c_int * n)(*L)
+            vs = (C.c_int * n)(*slots)
+            sd = (C.c_uint64 * n)(*[int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds])
+            self.stream.wait_stream(torch.cuda.current_stream(self.device))
+            _lib.check(_lib.lib().gsv_vits_decode_segments(self._h, n, cd.data_ptr(), cl, tx.data_ptr(), pl, vs, sd,
+                                                           nz.data_ptr() if nz is not None else None, float(noise_scale),
+                                                           wav.data_ptr(), C.c_void_p(self.stream.cuda_stream)),
+                       "gsv_vits_decode_segments")
+            self.stream.synchronize()
+        out = wav.to(self.dtype)
+        return [p.view(1, 1, -1) for p in torch.split(out, [2 * t * up for t in T])]
+
+    @torch.no_grad()
     def extract_latent(self, x: torch.Tensor) -> torch.Tensor:
         """reference models.py:1007-1010: HuBERT features [1, 768, T50] -> codes [1, 1, T50 // 2] (int64)."""
         if not self._loaded:

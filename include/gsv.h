@@ -176,7 +176,7 @@ int gsv_vits_decode(gsv_vits_t* h, const int32_t* codes, int T, const int32_t* p
                     float noise_scale, double speed, uint64_t seed, float* wav, gsv_stream_t stream);
 /* ssl [dev] fp32 [ssl_dim][T50] channels-first -> codes [dev] int32 [T50/2] */
 int gsv_vits_extract_latent(gsv_vits_t* h, const float* ssl, int T50, int32_t* codes, gsv_stream_t stream);
-/* test hook: copy a named intermediate of the last decode ("ge","m_p","logs_p","z","stage0".."stage4")
+/* test hook: copy a named intermediate of the last decode ("ge","m_p","logs_p","z", "gen_last_in" = the last generator stage's input)
  * into out [dev] fp32 in channels-first [C][T] order; returns element count via *numel. */
 int gsv_vits_debug_tensor(gsv_vits_t* h, const char* name, float* out, int64_t cap, int64_t* numel,
                           gsv_stream_t stream);
@@ -191,6 +191,26 @@ int gsv_vits_decode_encp(gsv_vits_t* h, const int32_t* codes, int T, const int32
  * ge = mean_r ge_r; the MRTE receives ge_to512(ge). */
 int gsv_vits_set_refer_sv(gsv_vits_t* h, const float* const* specs, const int* frames, int bins, const float* const* sv_embs,
                           int n_refs, gsv_stream_t stream);
+/* Segmented decode (v1 / v2 / v2Pro / v2ProPlus, speed 1): n independent sequences, each with its own voice and seed, in one
+ * pass of enc_p, flow and generator.  The library lays the segments back to back with G zero "gap" frames between them
+ * (G = gsv_vits_segment_gap(cfg), G * prod(up_rates[:i]) rows after upsampling stage i, G rows between phone runs); every
+ * tensor a conv reads keeps its gap rows at 0 and attention is block-diagonal, so segment s yields what gsv_vits_decode of
+ * segment s alone yields.
+ * gsv_vits_store_voice copies the conditioning of the last gsv_vits_set_refer / _set_refer_sv into voice slot `slot`
+ * (0 <= slot < GSV_VITS_MAX_VOICES).  gsv_vits_decode_segments: codes [dev] int32 [sum code_lens], phones [dev] int32
+ * [sum phone_lens], both packed without gaps; code_lens / phone_lens / voice_slots / seeds [host] [n]; noise [dev] fp32
+ * [inter][sum 2 code_lens] or NULL (segment s draws the counter RNG keyed by seeds[s]); wav [dev] fp32, segment s's
+ * 2 * code_lens[s] * prod(up_rates) samples back to back. */
+#define GSV_VITS_MAX_VOICES 128
+int gsv_vits_store_voice(gsv_vits_t* h, int slot);
+int gsv_vits_decode_segments(gsv_vits_t* h, int n, const int32_t* codes, const int* code_lens, const int32_t* phones,
+                             const int* phone_lens, const int* voice_slots, const uint64_t* seeds, const float* noise,
+                             float noise_scale, float* wav, gsv_stream_t stream);
+/* host-only planning helpers (no device needed): the gap G in frames, and the segment id (-1 = gap) of every row at `level`
+ * (-1 = phones, 0 = frames, i = after upsampling stage i); *rows = row count (seg may be NULL to query it). */
+int gsv_vits_segment_gap(const gsv_vits_config* cfg);
+int gsv_vits_segment_map(const gsv_vits_config* cfg, int n, const int* code_lens, const int* phone_lens, int level, int32_t* seg,
+                         int64_t cap, int64_t* rows);
 /* per-kernel timing hooks for bench.py: device ms of the last decode's generator section */
 int gsv_vits_last_timing(gsv_vits_t* h, float* total_ms, float* generator_ms);
 

@@ -181,7 +181,7 @@ struct ConvArgs {
 // no formatting, allocation or synchronisation on the launch path.
 enum { ROUTE_GEMM_SK = 1, ROUTE_GEMM_T64 = 2, ROUTE_CONV_WIDE = 3, ROUTE_GEMM_LDS = 4, ROUTE_CONV_LDS = 5, ROUTE_CONV_NARROW = 6,
        ROUTE_CONV_GEMM = 7, ROUTE_CONV_PAIR = 8 };
-enum { ROUTE_RES = 1, ROUTE_ACCU = 2, ROUTE_ALLW = 4, ROUTE_WNT = 8 };
+enum { ROUTE_RES = 1, ROUTE_ACCU = 2, ROUTE_ALLW = 4, ROUTE_WNT = 8, ROUTE_SEG = 16 };
 constexpr unsigned long long route_code(int family, int dtype, int p0 = 0, int p1 = 0, int p2 = 0, int p3 = 0, int p4 = 0, int flags = 0) {
   return (unsigned long long)(family & 255) | (unsigned long long)(dtype & 255) << 8 | (unsigned long long)(p0 & 255) << 16 |
          (unsigned long long)(p1 & 255) << 24 | (unsigned long long)(p2 & 255) << 32 | (unsigned long long)(p3 & 255) << 40 |
@@ -218,6 +218,9 @@ struct ConvPairArgs {
 };
 bool conv_pair_eligible(int dtype, int C, int taps, int dil, int T);
 int launch_conv_pair(const ConvPairArgs& a, hipStream_t s);
+// the pair of a segmented decode: row_seg [T] int32, -1 = gap row (ConvArgs::row_seg).  Gap rows of the intermediate and of y are
+// 0, as after convs1 -> row pass -> convs2 -> row pass.  row_seg travels beside ConvPairArgs, whose layout the unmasked kernels keep.
+int launch_conv_pair_seg(const ConvPairArgs& a, const int* row_seg, hipStream_t s);
 
 // fused attention, fp16, head dim 64 (attn.hip); vt_buf: heads * 64 * ceil32(T) halfs of scratch
 // rope_cs != null: rotate the first 2*rope_half channels of q and k in place first (cos|sin table [T][rope_half][2])

@@ -13,6 +13,7 @@
 // Every rounding point of the two-launch path is kept (fp16 intermediate, fp16 lrelu, same tap / k order of the MFMAs): the
 // result is bit-identical to it, except that with scale != 1 AND accumulate the compiler contracts the last two operations of
 // the two epilogues differently (one fp16 ulp on ~0.02 % of the elements; tests/test_ops_gpu.py::test_conv_pair_matches_two_launches).
+// SEG = true is the same pair inside a segmented decode (gsv_op_conv_pair_seg; gap rows of the intermediate and of y are 0).
 #include <stdlib.h>
 
 #include <algorithm>
@@ -34,9 +35,13 @@ __device__ __forceinline__ T4 lrelu4(T4 v, float s) { T4 t = v * (_Float16)s; re
 constexpr int ROWS_Y = 288;      // intermediate rows per tile (9 x 32 >= 256 + 2 * 5)
 constexpr int ROWS_X = 338;      // window rows at most (288 + 2 * 5 * 5)
 
+// SEG = the pair of a segmented decode (gsv_vits_decode_segments): row_seg holds one int32 per row, -1 = gap row.  An intermediate
+// gap row goes into the LDS image as 0 and an output gap row is stored as 0, which is what the row passes after convs1 and convs2
+// do on the two-launch path.  Everything SEG adds sits under `if constexpr (SEG)` and row_seg is a trailing kernel argument that
+// the unmasked instantiations never read (ConvPairArgs keeps its layout): they keep the registers and scratch they had without it.
 // second launch bound = waves per SIMD the register allocation must leave room for: 2 workgroups per CU at C = 32, 3 at C = 16
-template <int CC, int TAPS, bool ACCU>
-__global__ __launch_bounds__(256, CC == 32 ? 2 : 3) void conv_pair_f16_kernel(ConvPairArgs a, int ntiles) {
+template <int CC, int TAPS, bool ACCU, bool SEG>
+__global__ __launch_bounds__(256, CC == 32 ? 2 : 3) void conv_pair_f16_kernel(ConvPairArgs a, int ntiles, const int* __restrict__ row_seg) {
   constexpr int G = 8, KC = 16, CT = 32, WN = 4, TN = 2, NT = 256;
   constexpr int LDX = CC + G, VPR = CC / G;
   constexpr int XB = (ROWS_X * VPR + NT - 1) / NT;
@@ -121,6 +126,8 @@ __global__ __launch_bounds__(256, CC == 32 ? 2 : 3) void conv_pair_f16_kernel(Co
     F nxt[XB];
     load_window(min(tile + (int)gridDim.x, ntiles - 1), nxt);
     T4 rv[NP * NI], yv[ACCU ? NP * NI : 1];
+    constexpr int NS1 = (ROWS_Y / 32 + WN - 1) / WN;
+    int so[SEG ? NP * NI : 1], s1[SEG ? NS1 : 1];
 #pragma unroll
     for (int q = 0; q < NP * NI; ++q) {
       const int pass = q / NI, e = q - pass * NI;
@@ -128,9 +135,14 @@ __global__ __launch_bounds__(256, CC == 32 ? 2 : 3) void conv_pair_f16_kernel(Co
       const int cc = min(ec, CC - 4);
       rv[q] = *(const T4*)(x + (long long)t * a.ldx + cc);
       if (ACCU) yv[q] = *(const T4*)(a.y + (long long)t * a.ldy + cc);
+      if constexpr (SEG) so[q] = row_seg[t];
+    }
+    if constexpr (SEG) {               // the intermediate rows of this lane's column tiles (wn, wn + 4, wn + 8)
+#pragma unroll
+      for (int i = 0; i < NS1; ++i) s1[i] = row_seg[min(max(t0 - h2 + (wn + i * WN) * 32 + r, 0), a.T - 1)];
     }
     // ---- convs1 (dilation d) over the 288 intermediate rows: column tiles wn, wn + 4 and, wave 0, tile 8
-    for (int n1 = wn; n1 < ROWS_Y / 32; n1 += WN) {
+    for (int n1 = wn, i1 = 0; n1 < ROWS_Y / 32; n1 += WN, ++i1) {
       f16v acc;
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[i] = 0.f;
@@ -145,7 +157,8 @@ __global__ __launch_bounds__(256, CC == 32 ? 2 : 3) void conv_pair_f16_kernel(Co
         }
       }
       const int row = n1 * 32 + r, t = t0 - h2 + row;
-      const bool inside = t >= 0 && t < a.T;             // convs2 pads its input with zeros, not with convs1 of padding
+      bool inside = t >= 0 && t < a.T;                   // convs2 pads its input with zeros, not with convs1 of padding
+      if constexpr (SEG) inside = inside && (i1 == 0 ? s1[0] : i1 == 1 ? s1[1] : s1[2]) >= 0;   // nor with convs1 of a gap row
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int c0 = 8 * g + 4 * h;
@@ -203,8 +216,17 @@ __global__ __launch_bounds__(256, CC == 32 ? 2 : 3) void conv_pair_f16_kernel(Co
         for (int j = 0; j < 4; ++j) {
           float u = av[j] + ebias[j];
           u += (float)rv[q][j];
-          u *= a.scale;
-          if (ACCU) u += (float)yv[q][j];
+          if constexpr (SEG && ACCU) {
+            // the unmasked kernel rounds `* scale + y` once to fp32 (v_pk_fma_f32) and then to fp16.  Next to the select the
+            // compiler turns half of the lanes into v_fma_mixlo_f16, which rounds once, to fp16: 1 ulp apart on ~0.01 % of the
+            // elements.  A map without gaps must give the unmasked pair's bits, so the fp32 value is pinned before the select.
+            u = __builtin_fmaf(u, a.scale, (float)yv[q][j]);
+            asm volatile("" : "+v"(u));
+          } else {
+            u *= a.scale;
+            if (ACCU) u += (float)yv[q][j];
+          }
+          if constexpr (SEG) u = so[q] < 0 ? 0.f : u;
           v[j] = u;
         }
         T* yp = a.y + (long long)t * a.ldy + ec;
@@ -219,7 +241,7 @@ __global__ __launch_bounds__(256, CC == 32 ? 2 : 3) void conv_pair_f16_kernel(Co
 }
 
 template <int CC, int TAPS>
-int launch_pair(const ConvPairArgs& a, hipStream_t s) {
+int launch_pair(const ConvPairArgs& a, const int* row_seg, hipStream_t s) {
   const int ntiles = cdiv(a.T, 256);
   const size_t lds = ((size_t)ROWS_X + ROWS_Y + (size_t)TAPS * 32) * (CC + 8) * 2;
   static const int cap = getenv("GSV_PAIR_PER_CU") ? std::max(1, atoi(getenv("GSV_PAIR_PER_CU"))) : 3;
@@ -227,27 +249,37 @@ int launch_pair(const ConvPairArgs& a, hipStream_t s) {
   const int grid = std::min(ntiles, 256 * per_cu);
 #define GSV_PAIR(A)                                                                                                        \
   do {                                                                                                                     \
-    auto kern = conv_pair_f16_kernel<CC, TAPS, A>;                                                                         \
+    auto kern = conv_pair_f16_kernel<CC, TAPS, A, false>;                                                                  \
     static bool set = false;                                                                                               \
     if (!set) { GSV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set = true; } \
     set_conv_route(route_code(ROUTE_CONV_PAIR, GSV_F16, CC, TAPS, 0, 0, 0, route_flags(false, A)));                        \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a, ntiles);                                                    \
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a, ntiles, (const int*)nullptr);                               \
   } while (0)
-  if (a.accumulate) GSV_PAIR(true);
+#define GSV_PAIR_SEG(A)                                                                                                    \
+  do {                                                                                                                     \
+    auto kern = conv_pair_f16_kernel<CC, TAPS, A, true>;                                                                   \
+    static bool set = false;                                                                                               \
+    if (!set) { GSV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set = true; } \
+    set_conv_route(route_code(ROUTE_CONV_PAIR, GSV_F16, CC, TAPS, 0, 0, 0, route_flags(false, A) | ROUTE_SEG));            \
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a, ntiles, row_seg);                                           \
+  } while (0)
+  if (row_seg) { if (a.accumulate) GSV_PAIR_SEG(true); else GSV_PAIR_SEG(false); }
+  else if (a.accumulate) GSV_PAIR(true);
   else GSV_PAIR(false);
+#undef GSV_PAIR_SEG
 #undef GSV_PAIR
   GSV_HIP(hipGetLastError());
   return GSV_OK;
 }
 
 template <int CC>
-int launch_pair_taps(const ConvPairArgs& a, hipStream_t s) {
+int launch_pair_taps(const ConvPairArgs& a, const int* row_seg, hipStream_t s) {
   switch (a.taps) {
-    case 3: return launch_pair<CC, 3>(a, s);
-    case 5: return launch_pair<CC, 5>(a, s);
-    case 7: return launch_pair<CC, 7>(a, s);
-    case 9: return launch_pair<CC, 9>(a, s);
-    case 11: return launch_pair<CC, 11>(a, s);
+    case 3: return launch_pair<CC, 3>(a, row_seg, s);
+    case 5: return launch_pair<CC, 5>(a, row_seg, s);
+    case 7: return launch_pair<CC, 7>(a, row_seg, s);
+    case 9: return launch_pair<CC, 9>(a, row_seg, s);
+    case 11: return launch_pair<CC, 11>(a, row_seg, s);
     default: set_error("conv_pair: no kernel for taps=%d", a.taps); return GSV_ERR_ARG;
   }
 }
@@ -261,14 +293,26 @@ bool conv_pair_eligible(int dtype, int C, int taps, int dil, int T) {
   return !off && dtype == GSV_F16 && (C == 16 || C == 32) && inst && dil >= 1 && ((taps - 1) / 2) * dil <= 25 && T >= 256;
 }
 
-int launch_conv_pair(const ConvPairArgs& a, hipStream_t s) {
-  set_conv_route(0);
+namespace {
+int launch_conv_pair_any(const ConvPairArgs& a, const int* row_seg, hipStream_t s) {
   GSV_REQUIRE(a.x && a.y && a.w1 && a.w2 && a.b1 && a.b2, "conv_pair: null operand");
   GSV_REQUIRE(conv_pair_eligible(GSV_F16, a.C, a.taps, a.dil, a.T) || getenv("GSV_NO_CONV_PAIR"), "conv_pair: shape C=%d taps=%d dil=%d T=%d not supported",
               a.C, a.taps, a.dil, a.T);
   GSV_REQUIRE(a.ldx % 8 == 0 && a.ldy % 4 == 0 && ((uintptr_t)a.x % 16) == 0 && ((uintptr_t)a.w1 % 16) == 0 && ((uintptr_t)a.w2 % 16) == 0,
               "conv_pair: operands must be 16-byte aligned");
-  return a.C == 16 ? launch_pair_taps<16>(a, s) : launch_pair_taps<32>(a, s);
+  return a.C == 16 ? launch_pair_taps<16>(a, row_seg, s) : launch_pair_taps<32>(a, row_seg, s);
+}
+}  // namespace
+
+int launch_conv_pair(const ConvPairArgs& a, hipStream_t s) {
+  set_conv_route(0);
+  return launch_conv_pair_any(a, nullptr, s);
+}
+
+int launch_conv_pair_seg(const ConvPairArgs& a, const int* row_seg, hipStream_t s) {
+  set_conv_route(0);
+  GSV_REQUIRE(row_seg, "conv_pair_seg: row_seg is null (the unmasked pair is launch_conv_pair)");
+  return launch_conv_pair_any(a, row_seg, s);
 }
 
 }  // namespace gsv

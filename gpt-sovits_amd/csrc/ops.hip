@@ -13,7 +13,11 @@ void set_error(const char* fmt, ...) {
 const char* get_error() { return g_err; }
 
 static thread_local unsigned long long g_conv_route = 0;
-void set_conv_route(unsigned long long code) { g_conv_route = code; }
+static thread_local unsigned long long g_pair_route = 0;   // the last fused-pair launch, kept aside: a decode ends in conv_post
+void set_conv_route(unsigned long long code) {
+  g_conv_route = code;
+  if ((code & 255) == ROUTE_CONV_PAIR) g_pair_route = code;
+}
 
 template <typename T> __global__ void convert_kernel(const float* __restrict__ s, T* __restrict__ d, long long n) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -226,6 +230,12 @@ uint64_t gsv_debug_last_conv_route(int reset) {
   if (reset) gsv::g_conv_route = 0;
   return code;
 }
+
+uint64_t gsv_debug_last_pair_route(int reset) {
+  const uint64_t r = gsv::g_pair_route;
+  if (reset) gsv::g_pair_route = 0;
+  return r;
+}
 int gsv_init(int device) {
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
@@ -322,6 +332,16 @@ int gsv_op_conv_pair(const void* x, const void* w1, const float* b1, const void*
   a.x = (const _Float16*)x; a.w1 = (const _Float16*)w1; a.b1 = b1; a.w2 = (const _Float16*)w2; a.b2 = b2; a.y = (_Float16*)y;
   a.T = T; a.C = C; a.taps = taps; a.dil = dil; a.ldx = C; a.ldy = C; a.scale = scale; a.accumulate = accumulate;
   return gsv::launch_conv_pair(a, (hipStream_t)stream);
+}
+
+int gsv_op_conv_pair_seg(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y, int T, int C, int taps,
+                         int dil, float scale, int accumulate, const int32_t* row_seg, gsv_stream_t stream) {
+  GSV_REQUIRE(row_seg, "op_conv_pair_seg: row_seg is null (gsv_op_conv_pair is the unmasked pair)");
+  GSV_REQUIRE(gsv::conv_pair_eligible(GSV_F16, C, taps, dil, T), "op_conv_pair_seg: C must be 16 or 32, taps 3, 5, 7, 9 or 11, (taps - 1) / 2 * dil <= 25, T >= 256");
+  gsv::ConvPairArgs a;
+  a.x = (const _Float16*)x; a.w1 = (const _Float16*)w1; a.b1 = b1; a.w2 = (const _Float16*)w2; a.b2 = b2; a.y = (_Float16*)y;
+  a.T = T; a.C = C; a.taps = taps; a.dil = dil; a.ldx = C; a.ldy = C; a.scale = scale; a.accumulate = accumulate;
+  return gsv::launch_conv_pair_seg(a, row_seg, (hipStream_t)stream);
 }
 
 int gsv_op_aff_mix(const float* x, const float* y, const float* t, long long n, float* out, gsv_stream_t stream) {

@@ -1167,8 +1167,10 @@ static int decode_tail(gsv_vits* h, hipStream_t s, void* y, int F, const float* 
       for (int k = 0; k < 3; ++k) {
         const Conv& c1 = h->rb1[(i * c.n_resblocks + j) * 3 + k];
         const Conv& c2 = h->rb2[(i * c.n_resblocks + j) * 3 + k];
-        // (segmented: the two convs with their row passes; the fused pair's intermediate never leaves the CU)
-        if (!seg_o && c1.b && c2.b && c1.taps == c2.taps && conv_pair_eligible(h->dtype, ch, c1.taps, c.rb_dilations[j][k], Tout)) {
+        // segmented: the masked pair zeroes the gap rows of its LDS intermediate and of its output itself (conv_pair.hip, SEG);
+        // GSV_NO_SEG_PAIR=1 is the A/B switch back to the two convs with their row passes
+        static const bool no_seg_pair = getenv("GSV_NO_SEG_PAIR") != nullptr;
+        if (!(seg_o && no_seg_pair) && c1.b && c2.b && c1.taps == c2.taps && conv_pair_eligible(h->dtype, ch, c1.taps, c.rb_dilations[j][k], Tout)) {
           // narrow stages: the pair in one kernel, the intermediate tensor never leaves the CU (conv_pair.hip)
           ConvPairArgs pa;
           pa.x = (const _Float16*)xr; pa.w1 = (const _Float16*)c1.w; pa.b1 = c1.b; pa.w2 = (const _Float16*)c2.w; pa.b2 = c2.b;
@@ -1177,7 +1179,8 @@ static int decode_tail(gsv_vits* h, hipStream_t s, void* y, int F, const float* 
           else { pa.y = (_Float16*)xs; pa.scale = 1.f / (float)c.n_resblocks; pa.accumulate = j > 0; }
           // the pair reads x as window AND residual: it must not be overwritten in place
           if ((const void*)pa.y == xr) { pa.y = (_Float16*)xt; }
-          GSV_RC(launch_conv_pair(pa, s));
+          if (seg_o) { GSV_RC(launch_conv_pair_seg(pa, seg_o, s)); }
+          else { GSV_RC(launch_conv_pair(pa, s)); }
           if (k < 2) { if (pa.y == (_Float16*)xt) { std::swap(xt, R); } xr = R; }
           continue;
         }

@@ -972,12 +972,52 @@ class TTS:
             launches += [rows[i:i + mb] for i in range(0, len(rows), mb)]
         return launches
 
+    sovits_max_frames = 25600     # frames (gaps included) of one shared SoVITS pass: the largest fold this engine has run
+
+    @staticmethod
+    def _voice_key(voice: dict) -> tuple:
+        """what makes two requests' SoVITS voices the same one: the stored spectrogram list and speaker embeddings themselves"""
+        return (id(voice.get("refer_spec")), id(voice.get("sv_emb")))
+
+    def plan_sovits(self, plans: List[dict]) -> List[List[Tuple[int, int]]]:
+        """The waveform launches of run_batch(shared_sovits=True).  `plans[r]` = {"voice", "opts", "folds"}; folds[bi] is
+        the number of kept semantic tokens of to_batch batch bi, which run() decodes as one time-folded sequence with seed
+        actual_seed + bi.  A fold is one segment of SynthesizerTrn.decode_segments.  Shared: v1 / v2 / v2Pro / v2ProPlus
+        folds at speed 1 with at least one token; the others are left to _synthesize_batch.  A launch holds at most
+        VITS_MAX_VOICES distinct voices and at most sovits_max_frames frames, gaps included (n folds of T_s tokens take
+        sum(2 T_s) + (n - 1) * segment_gap() frames); a fold larger than that gets a launch of its own.  Returns the
+        launches, lists of (r, bi) in (r, bi) order."""
+        from .. import _lib
+        if getattr(self.configs, "use_vocoder", False):
+            return []
+        gap = self.vits_model.segment_gap()
+        launches, cur, frames, voices = [], [], 0, set()
+        for r, pl in enumerate(plans):
+            if pl["opts"]["speed_factor"] != 1.0:
+                continue
+            key = self._voice_key(pl["voice"])
+            for bi, tokens in enumerate(pl["folds"]):
+                if tokens <= 0:
+                    continue
+                need = 2 * int(tokens)
+                if cur and (frames + gap + need > self.sovits_max_frames or len(voices | {key}) > _lib.VITS_MAX_VOICES):
+                    launches.append(cur)
+                    cur, frames, voices = [], 0, set()
+                frames += need + (gap if cur else 0)
+                cur.append((r, bi))
+                voices.add(key)
+        if cur:
+            launches.append(cur)
+        return launches
+
     @torch.no_grad()
-    def run_batch(self, requests: List[dict]) -> List[Tuple[int, np.ndarray]]:
+    def run_batch(self, requests: List[dict], shared_sovits: bool = False) -> List[Tuple[int, np.ndarray]]:
         """Several requests, each with its own reference voice, through shared AR decodes.  Each request dict takes the
         keys run() accepts plus an optional "voice" (make_voice); without one it uses its ref_audio_path / prompt_text
         (through make_voice's LRU) or the current prompt cache.  Returns one (sr, int16 audio) per request, in order: what
-        run(request) alone returns.  self.prompt_cache is not changed.  return_fragment is not supported."""
+        run(request) alone returns.  self.prompt_cache is not changed.  return_fragment is not supported.
+        shared_sovits=True: the waveform stage of v1 / v2 / v2Pro / v2ProPlus requests at speed 1 runs as shared segmented
+        passes over all voices (plan_sovits, SynthesizerTrn.decode_segments) instead of one decode per to_batch batch."""
         if self.t2s_model is None or self.vits_model is None:
             raise RuntimeError("init_t2s_weights / init_vits_weights first")
         self.stop_flag = False
@@ -1028,6 +1068,40 @@ class TTS:
         sr = self.configs.sampling_rate if not self.configs.use_vocoder else self.vocoder_configs["sr"]
         if self.configs.use_vocoder and self.vocoder is None:
             raise RuntimeError("init_vocoder() first")
+
+        def kept(r, bi):
+            """the generated tokens of batch bi of request r without their prompts, and run()'s idx_list"""
+            pred_list, idx_list = preds[r][bi], idxs[r][bi]
+            if plans[r]["no_prompt"]:
+                pred = list(pred_list)
+                return pred, [int(p_.shape[0]) for p_ in pred]
+            return [p_[-i:] if i > 0 else p_[:0] for p_, i in zip(pred_list, idx_list)], idx_list
+
+        # ---- shared SoVITS passes: every fold (request r, to_batch batch bi) is one segment with r's voice
+        shared: Dict[Tuple[int, int], List[torch.Tensor]] = {}
+        if shared_sovits and not self.configs.use_vocoder:
+            for r, pl in enumerate(plans):
+                pl["folds"] = [sum(int(p_.shape[0]) for p_ in kept(r, bi)[0]) for bi in range(len(pl["data"]))]
+            dev_voice: Dict[tuple, tuple] = {}          # one device refer list per distinct voice: one voice slot
+            for launch in self.plan_sovits(plans):
+                codes, phones, voices, seeds, cuts = [], [], [], [], []
+                for r, bi in launch:
+                    pl = plans[r]
+                    pred = kept(r, bi)[0]
+                    keep = [k for k, p_ in enumerate(pred) if p_.shape[0] > 0]
+                    codes.append(torch.cat([pred[k] for k in keep]).view(1, 1, -1))
+                    phones.append(torch.cat([pl["data"][bi]["phones"][k] for k in keep]).view(1, -1))
+                    vk = self._voice_key(pl["voice"])
+                    if vk not in dev_voice:
+                        dev_voice[vk] = ([spec.to(device=self.configs.device) for spec, _ in pl["voice"]["refer_spec"]],
+                                         pl["voice"]["sv_emb"] if getattr(self.vits_model, "is_v2pro", False) else None)
+                    voices.append(dev_voice[vk])
+                    seeds.append(pl["actual_seed"] + bi)
+                    cuts.append([int(p_.shape[0]) * 2 * up for p_ in pred])
+                wavs = self.vits_model.decode_segments(codes, phones, voices, seeds)
+                for (r, bi), wav, cut in zip(launch, wavs, cuts):
+                    shared[(r, bi)] = list(torch.split(wav[0, 0], cut))
+            self.vits_model.invalidate_refer()          # the engine's cached reference terms are the last slot's voice
         results = []
         for r, pl in enumerate(plans):
             o = pl["opts"]
@@ -1040,12 +1114,11 @@ class TTS:
                 sv_kw = {"sv_emb": voice["sv_emb"]} if getattr(self.vits_model, "is_v2pro", False) else {}
                 audio = []
                 for bi, item in enumerate(pl["data"]):
-                    pred_list, idx_list = preds[r][bi], idxs[r][bi]
-                    if pl["no_prompt"]:
-                        pred = list(pred_list)
-                        idx_list = [int(p_.shape[0]) for p_ in pred]
-                    else:
-                        pred = [p_[-i:] if i > 0 else p_[:0] for p_, i in zip(pred_list, idx_list)]
+                    if (r, bi) in shared:
+                        audio.append(shared[(r, bi)])
+                        continue
+                    pred_list = preds[r][bi]
+                    pred, idx_list = kept(r, bi)
                     audio.append(self._synthesize_batch(item, pred, pred_list, idx_list, pl["actual_seed"] + bi, bi,
                                                         pl["actual_seed"], o["speed_factor"], o["parallel_infer"],
                                                         o["sample_steps"], refer, sv_kw, up))

@@ -67,9 +67,11 @@ class SynthesizerTrn:
             _lib.check(_lib.lib().gsv_vits_create(C.byref(cfg), _lib.dtype_code(dtype), C.byref(h)), "gsv_vits_create")
             self._h = h
             self.stream = torch.cuda.Stream(device=self.device)
+        self._cfg = cfg
         self._loaded = False
         self._ref_key = None
         self._ref_hold = None
+        self.decode_segments_calls = 0      # test / bench hook: segmented passes run so far
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -170,6 +172,11 @@ class SynthesizerTrn:
             self.stream.synchronize()
         return wav.to(self.dtype).view(1, 1, -1)
 
+    def segment_gap(self) -> int:
+        """Zero frames decode_segments lays between neighbouring segments (gsv_vits_segment_gap): n segments of T_s codes
+        take sum(2 T_s) + (n - 1) * segment_gap() frames"""
+        return int(_lib.lib().gsv_vits_segment_gap(C.byref(self._cfg)))
+
     @torch.no_grad()
     def decode_segments(self, codes_list, text_list, voices, seeds, noise_scale: float = 0.5,
                         noise: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
@@ -188,6 +195,7 @@ class SynthesizerTrn:
         T = [int(c.shape[-1]) for c in codes_list]
         L = [int(t.shape[-1]) for t in text_list]
         up = math.prod(self.upsample_rates)
+        self.decode_segments_calls += 1
         with torch.cuda.device(self.device):
             slot_of, slots = {}, []
             for refer, sv_emb in voices:

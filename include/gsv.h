@@ -363,11 +363,15 @@ int gsv_op_decode_attn(const void* q, const void* kc, const void* vc, const int3
 int gsv_op_conv1d(const gsv_conv_desc* d, int dtype, gsv_stream_t stream);
 /* test hook: which kernel instantiation the last gsv_op_conv1d / gsv_op_conv_pair / engine conv launch on this thread ran
  * (0 = none since the last reset).  Byte fields, low to high: family, dtype (GSV_F32 / GSV_F16), five template parameters p0..p4,
- * flags (1 RES, 2 ACCU, 4 ALLW, 8 WNT).  Families and their parameters:
+ * flags (1 RES, 2 ACCU, 4 ALLW, 8 WNT, 16 SEG).  Families and their parameters:
  *   1 gemm_sk_f16 | 2 gemm_t64_f16 p0 = SLAB / 16 | 3 conv_wide_f16 p0 = waves | 4 gemm_lds p0 = waves, p1 = xcd_order
  *   5 conv_lds p0..p4 = TM, TN, WM, WN, CC | 6 conv_narrow_f16 p0..p3 = CC, TM, TN, WN | 7 conv_gemm (generic) p0..p3 = TM, TN, WM, WN
- *   8 conv_pair_f16 p0 = C, p1 = taps.  reset != 0 clears the record after reading it. */
+ *   8 conv_pair_f16 p0 = C, p1 = taps; flag SEG = the masked pair of a segmented decode (gsv_op_conv_pair_seg).
+ * reset != 0 clears the record after reading it. */
 uint64_t gsv_debug_last_conv_route(int reset);
+/* the same record for the last family-8 launch (gsv_op_conv_pair / gsv_op_conv_pair_seg / a fused pair inside an engine decode)
+ * since the last reset.  A decode's last launch is conv_post, so its pairs are read here. */
+uint64_t gsv_debug_last_pair_route(int reset);
 /* y = LN(x (+res)) over the last dim C; all buffers of `dtype`, gamma/beta fp32 */
 int gsv_op_layernorm(const void* x, const void* res, const float* gamma, const float* beta, void* y, int rows,
                      int C, float eps, int dtype, gsv_stream_t stream);
@@ -389,6 +393,12 @@ int gsv_op_magnitude(const float* re_im, int T, int bins, float eps, int frame_l
  * tap-major, convs1 dilated by `dil`, convs2 dilation 1; b1 / b2 [dev] fp32 [C].  Same rounding points as two gsv_op_conv1d launches. */
 int gsv_op_conv_pair(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y, int T, int C, int taps,
                      int dil, float scale, int accumulate, gsv_stream_t stream);
+/* the same pair inside a segmented decode (gsv_vits_decode_segments): row_seg [dev] int32 [T], the row's segment or -1 for a gap
+ * row.  Gap rows of the intermediate are 0 to convs2 and gap rows of y are stored as 0 whatever bias, residual, scale or accumulate
+ * give: bit-identical to convs1 -> zero the gap rows -> convs2 -> zero the gap rows.  x must hold 0 in its gap rows.
+ * row_seg == NULL is GSV_ERR_ARG. */
+int gsv_op_conv_pair_seg(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y, int T, int C, int taps,
+                         int dil, float scale, int accumulate, const int32_t* row_seg, gsv_stream_t stream);
 int gsv_op_aff_mix(const float* x, const float* y, const float* t, long long n, float* out, gsv_stream_t stream);
 int gsv_op_time_mean(const float* x, int T, int ld, float* out, gsv_stream_t stream);
 int gsv_op_channel_norm(const void* x, int T, int C, const float* gamma, const float* beta, float eps, int act, float* scratch,

@@ -1,9 +1,11 @@
 """Multi-voice throughput: N requests, each with its own reference voice (prompt length, spectrogram), one 4 s sentence
 each, fp16 synthetic v2 weights.  TTS.run_batch (one shared AR decode) against N sequential TTS.run calls (one voice per
 call, the only way before run_batch).  Prints one JSON line: audio-s/s of both, the speed-up, and the persistent engine's
-fallback count (gsv_t2s_engine_stats), which must stay 0.
+fallback count (gsv_t2s_engine_stats), which must stay 0.  --shared-sovits also times run_batch(shared_sovits=True) (one
+segmented SoVITS pass for all voices) in the same process and reports its SoVITS device time.  Every mode lists the wall
+time of each iteration, so the gain can be read against the spread.
 
-    python tools/multivoice_bench.py [--requests 32] [--tokens 100] [--iters 3]
+    python tools/multivoice_bench.py [--requests 32] [--tokens 100] [--iters 3] [--shared-sovits]
 """
 import argparse
 import json
@@ -24,6 +26,7 @@ def main():
     ap.add_argument("--requests", type=int, default=32)
     ap.add_argument("--tokens", type=int, default=100, help="AR tokens per request (25 tokens = 1 s)")
     ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--shared-sovits", action="store_true", help="also time run_batch(shared_sovits=True)")
     a = ap.parse_args()
     from bench import build_tts, make_segments
     from gsv import synthetic as S
@@ -45,18 +48,23 @@ def main():
     params = dict(top_k=15, top_p=1.0, temperature=1.0, repetition_penalty=1.35, fragment_interval=0.01, seed=7)
     reqs = [dict(params, segments=[segs[i]], voice=voices[i]) for i in range(N)]
 
+    times = {}
+
     def audio_s(outs):
         return sum(int(w.shape[0]) for _sr, w in outs) / 32000.0
 
     def timed(fn):
-        best = None
-        for _ in range(a.iters + 1):                   # first pass: warm-up (graphs, workspaces)
+        best, each = None, []
+        for it in range(a.iters + 1):                  # first pass: warm-up (graphs, workspaces)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             outs = fn()
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             best = dt if best is None else min(best, dt)
+            if it > 0:
+                each.append(round(dt, 4))
+        times[fn] = each
         return outs, best
 
     def sequential():
@@ -68,14 +76,31 @@ def main():
             outs += list(tts.run({k: x for k, x in r.items() if k != "voice"}))
         return outs
 
+    def batch():
+        return tts.run_batch(reqs)
+
+    def batch_shared():
+        return tts.run_batch(reqs, shared_sovits=True)
+
     so, st = timed(sequential)
-    bo, bt = timed(lambda: tts.run_batch(reqs))
+    bo, bt = timed(batch)
     _avail, fallbacks, _err = tts.t2s_model.engine_stats()
     same = sum(int(x[1].shape == y[1].shape and (x[1] == y[1]).all()) for x, y in zip(so, bo))
     res = {"requests": N, "tokens_per_request": TOK,
            "sequential_audio_s_per_s": round(audio_s(so) / st, 1), "run_batch_audio_s_per_s": round(audio_s(bo) / bt, 1),
            "speedup": round(st / bt, 2), "sequential_s": round(st, 4), "run_batch_s": round(bt, 4),
            "outputs_identical": f"{same}/{N}", "engine_fallbacks": fallbacks, "decode_mode": tts.t2s_model.decode_info()[0]}
+    res["sequential_iters_s"], res["run_batch_iters_s"] = times[sequential], times[batch]
+    if a.shared_sovits:
+        n0 = tts.vits_model.decode_segments_calls
+        ho, ht = timed(batch_shared)
+        dev_ms, gen_ms = tts.vits_model.last_timing()      # of the last pass of the last iteration
+        res.update({"shared_audio_s_per_s": round(audio_s(ho) / ht, 1), "shared_s": round(ht, 4), "shared_iters_s": times[batch_shared],
+                    "shared_speedup_over_run_batch": round(bt / ht, 2),
+                    "shared_passes_per_call": (tts.vits_model.decode_segments_calls - n0) // (a.iters + 1),
+                    "shared_sovits_device_ms": round(dev_ms, 2), "shared_sovits_generator_ms": round(gen_ms, 2),
+                    "shared_equal_lengths": f"{sum(int(x[1].shape == y[1].shape) for x, y in zip(bo, ho))}/{N}",
+                    "engine_fallbacks": tts.t2s_model.engine_stats()[1]})
     print(json.dumps(res))
 
 

@@ -1,5 +1,6 @@
-// Engine context shared by the SoVITS decoder (vits.hip), the vocoders and the flow-matching DiT (cfm.hip):
-// weight staging / upload, workspace arena, and the conv / attention launch helpers.
+// Engine context shared by the SoVITS decoder (vits.hip), the generator and vocoders (generator.hip), the flow-matching DiT
+// (cfm.hip) and the AP-BWE super-sampler (bwe.hip): weight staging / upload, workspace arena, and the conv / attention /
+// generator launch helpers.
 #pragma once
 #include <math.h>
 #include <map>
@@ -16,8 +17,21 @@ struct Conv {
 };
 
 struct AttnLayerW { Conv qkv, o; float *rel_k = nullptr, *rel_v = nullptr; float *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr; Conv f1, f2; };
-struct WNW { Conv in[4], res[4], skip[4]; float* in_bias_eff[4] = {nullptr, nullptr, nullptr, nullptr}; Conv cond; };
+// modules.WN: per layer in_layers (kernel 5) and res_skip_layers (1x1); in_bias_eff = in_layers bias + cond_layer(ge) (fp32 [2H])
+struct WNW { std::vector<Conv> in, res; std::vector<float*> in_bias_eff; Conv cond; };
 struct FlowW { Conv pre, post; WNW wn; };
+
+// HiFi-GAN / BigVGAN upsampling stages (everything between conv_pre and conv_post) with the shape they need
+struct VocAct { float *alpha = nullptr, *beta = nullptr; };
+struct GenW {
+  int uic = 0, n_ups = 0, n_resblocks = 0;     // uic = upsample_initial_channel, halved by every stage
+  int up_rates[8], up_kernels[8], rb_kernels[4], rb_dilations[4][3];
+  std::vector<Conv> ups, rb1, rb2;             // rb1 / rb2 = convs1 / convs2, [stage][block][3]
+  // BigVGAN only (empty / null for HiFi-GAN): anti-aliased snake parameters [stage][block][6] + activation_post, the two FIRs
+  std::vector<VocAct> acts;
+  int snake_logscale = 0;
+  float *up12 = nullptr, *dn12 = nullptr;
+};
 
 struct Buf { void* p = nullptr; size_t cap = 0; };
 
@@ -36,12 +50,10 @@ struct gsv_vits {
   FlowW flows[4];
   Conv conv_pre, conv_post, cond;
   float* conv_pre_bias_eff = nullptr;
-  std::vector<Conv> ups;
-  std::vector<Conv> rb1, rb2;  // [stage][j][c]
+  GenW gen;
   // v3 / v4: bridge + wns1 (Encoder with an 8-layer WN)
-  Conv bridge, w1_pre, w1_proj, w1_cond;
-  std::vector<Conv> w1_in, w1_res;
-  std::vector<float*> w1_in_bias_eff;
+  Conv bridge, w1_pre, w1_proj;
+  WNW w1;
   // v2Pro: speaker-verification conditioning
   Conv sv_emb, ge_to512;
   float *prelu_w = nullptr, *ge_ref = nullptr, *sv_proj = nullptr, *ge512 = nullptr;
@@ -86,8 +98,21 @@ struct ConvOpt {
   const int* row_seg = nullptr;   // segmented decode: gap rows of the output stored as 0 (ConvArgs::row_seg)
 };
 
-#define GSV_DISPATCH(h, call_f16, call_f32) \
-  do { if ((h)->dtype == GSV_F16) { call_f16; } else { call_f32; } } while (0)
+// Host code that launches typed kernels is a template on the element type T; an entry point picks T from the handle once:
+//   return GSV_WITH_T(h, decode<T>(h, ...));
+#define GSV_WITH_T(h, call)                                              \
+  [&]() -> int {                                                         \
+    if ((h)->dtype == GSV_F16) { using T = _Float16; return call; }      \
+    using T = float;                                                     \
+    return call;                                                         \
+  }()
+
+// every kernel launch of the engine files: the launch and its error check, the argument list written once
+#define GSV_LAUNCH(kern, grid, block, shmem, s, ...)                    \
+  do {                                                                   \
+    hipLaunchKernelGGL(kern, grid, block, shmem, s, __VA_ARGS__);        \
+    GSV_HIP(hipGetLastError());                                          \
+  } while (0)
 
 namespace gsveng {
 
@@ -110,5 +135,23 @@ int attention(gsv_vits* h, hipStream_t s, const void* q, int ldq, int qcol0, con
               int Tq, int Tk, int nh, int kc, float scale, const float* rel_k, const float* rel_v, void* out, int ldo,
               const int* kr = nullptr);   // kr: per-query key range [kr[2i], kr[2i+1]) (segmented decode)
 void free_ctx(gsv_vits* h);
+// fp32 channels-first [C][Tn] -> engine dtype channels-last [Tn][ldd] (first C columns; ldd = 0: C)
+int cf_to_cl(gsv_vits* h, hipStream_t s, const float* src, int Tn, int C, void* dst, int ldd = 0);
+
+// generator.hip
+// copies the generator's shape out of either config struct (gsv_vits_config, gsv_vocoder_config: same field names)
+template <class Cfg>
+void gen_shape(const Cfg& c, GenW* g) {
+  g->uic = c.upsample_initial_channel; g->n_ups = c.n_ups; g->n_resblocks = c.n_resblocks;
+  for (int i = 0; i < 8; ++i) { g->up_rates[i] = c.up_rates[i]; g->up_kernels[i] = c.up_kernels[i]; }
+  for (int j = 0; j < 4; ++j) { g->rb_kernels[j] = c.rb_kernels[j]; for (int d = 0; d < 3; ++d) g->rb_dilations[j][d] = c.rb_dilations[j][d]; }
+}
+// ups / resblocks (BigVGAN: + activations and FIRs) named `prefix`ups.N, `prefix`resblocks.N; g's shape is already set
+int load_generator(gsv_vits* h, const std::string& prefix, bool bigvgan, GenW* g);
+// the 5 (BigVGAN: 6) ping-pong workspaces `name`0.. of a generator fed with F frames
+int gen_buffers(gsv_vits* h, const GenW& g, const char* name, int F, void** gb);
+// all upsampling stages on *cur = gb[3] ([*Tn][g.uic], the conv_pre output) -> *cur [*Tn][g.uic >> g.n_ups], one of gb[3], gb[4].
+// seg_up != null (segmented decode): per-stage row maps, gap rows of every stage output are 0
+int run_generator_stages(gsv_vits* h, hipStream_t s, const GenW& g, void* const* gb, void** cur, int* Tn, int* const* seg_up = nullptr);
 
 }  // namespace gsveng

@@ -1,4 +1,6 @@
-// SoVITS v2 waveform decoder engine (H6-H12) for gfx950.
+// SoVITS engine (H6-H12) for gfx950: the v1/v2 waveform decoder (gsv_vits_decode, gsv_vits_decode_segments), the v3/v4
+// semantic path up to the CFM features (gsv_vits_decode_encp), the reference encoder and extract_latent.  The generator's
+// upsampling stages and the vocoders of the v3/v4 path are in generator.hip.
 //
 // Every activation is channels-last [time][channel] in the engine dtype, so every conv /
 // 1x1 / Linear / attention product is one call of the MFMA implicit-GEMM kernel
@@ -7,8 +9,12 @@
 // passes), transposed convs as polyphase convs with a scatter epilogue, weight-norm folded
 // once at load (the reference re-materialises it every forward), speaker-conditioning
 // terms (cond(ge), WN cond_layer(ge)) folded into biases once per reference audio.
-// A single sequence is decoded per call (as in the reference, TTS.py:1266-1273 folds the
-// batch into the time axis), so all x_mask terms are identically one and are dropped.
+// gsv_vits_decode takes a single sequence (the reference, TTS.py:1266-1273, folds the batch into
+// the time axis), so its x_mask terms are identically one and are dropped.  The two paths that do
+// mask say so where they do: the segmented decode (several sequences on one time axis, the gap
+// rows between them kept at zero by row maps) and wns1 of decode_encp (frames >= Lm zeroed).
+// Host functions that launch typed kernels are templates on the element type T, picked once per
+// entry point (GSV_WITH_T); every launch is written once (GSV_LAUNCH).
 #include "engine.h"
 
 namespace gsv {
@@ -77,63 +83,6 @@ __global__ void cf_to_cl_kernel(const float* __restrict__ src, int Tn, int C, T*
   for (int i = ty; i < 32; i += 8) {
     int t = t0 + i, c = c0 + tx;
     if (t < Tn && c < C) dst[(long long)t * ldd + c] = (T)tile[tx][i];
-  }
-}
-
-// Anti-aliased snake / snakebeta on channels-last activations [T][C] (BigVGAN Activation1d,
-// alias_free_activation/torch/act.py:25-30): 2x zero-stuffed 12-tap up-FIR -> x + sin^2(a x)/(b+1e-9)
-// -> 12-tap stride-2 down-FIR, replicate padding as in aa.hip.  A workgroup owns 64 time steps x 64
-// channels: rows are read/written 128 B wide (lane = channel), the 2x-rate intermediate lives in LDS.
-template <typename T>
-__global__ __launch_bounds__(256) void aa_act_cl_kernel(const T* __restrict__ x, T* __restrict__ y, int Tn, int C, int ld,
-                                                        const float* __restrict__ alpha, const float* __restrict__ beta,
-                                                        int logscale, const float* __restrict__ up12,
-                                                        const float* __restrict__ dn12) {
-  constexpr int TT = 64, CW = 64;
-  __shared__ float xs[TT + 16][CW];
-  __shared__ float as[2 * TT + 16][CW];
-  __shared__ float uf[12], df[12];
-  const int t0 = blockIdx.x * TT, c0 = blockIdx.y * CW;
-  const int cl = threadIdx.x & 63, tq = threadIdx.x >> 6;
-  const int c = c0 + cl;
-  const bool cok = c < C;
-  if (threadIdx.x < 12) { uf[threadIdx.x] = up12[threadIdx.x]; df[threadIdx.x] = dn12[threadIdx.x]; }
-  float a = 1.f, ib = 1.f;
-  if (cok) {
-    a = logscale ? expf(alpha[c]) : alpha[c];
-    ib = 1.f / ((logscale ? expf(beta[c]) : beta[c]) + 1e-9f);
-  }
-  for (int i = tq; i < TT + 16; i += 4) {
-    const int t = min(max(t0 - 8 + i, 0), Tn - 1);
-    xs[i][cl] = cok ? to_f(x[(long long)t * ld + c]) : 0.f;
-  }
-  __syncthreads();
-  const int n0 = 2 * t0 - 8;
-  for (int k = tq; k < 2 * TT + 16; k += 4) {
-    const int n = min(max(n0 + k, 0), 2 * Tn - 1);
-    const int ilo = (n + 5) >> 1;
-    float acc = 0.f;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      const int i = ilo + j;
-      const int f = n + 15 - 2 * i;
-      if (f >= 0 && f < 12) {
-        const int xo = min(max(i - 5, 0), Tn - 1);
-        acc += xs[xo - (t0 - 8)][cl] * uf[f];
-      }
-    }
-    const float u = 2.f * acc;
-    const float sn = sinf(u * a);
-    as[k][cl] = u + ib * sn * sn;
-  }
-  __syncthreads();
-  for (int i = tq; i < TT; i += 4) {
-    const int t = t0 + i;
-    if (t >= Tn || !cok) continue;
-    float acc = 0.f;
-#pragma unroll
-    for (int f = 0; f < 12; ++f) acc += df[f] * as[2 * i + f + 3][cl];
-    y[(long long)t * ld + c] = (T)acc;
   }
 }
 
@@ -476,6 +425,23 @@ int make_conv(gsv_vits* h, const std::string& name, int cout, int cin, int k, bo
   return GSV_OK;
 }
 
+// Conv1d weight [cout][cin][k] with the input channels zero-padded to cin_pad
+int make_conv_padded(gsv_vits* h, const std::string& name, int cout, int cin, int cin_pad, int k, bool bias, Conv* c) {
+  std::vector<float> w, b;
+  if (!fetch(h, name + ".weight", (size_t)cout * cin * k, cout, w)) return GSV_ERR_ARG;
+  std::vector<float> p((size_t)cout * k * cin_pad, 0.f);
+  for (int o = 0; o < cout; ++o)
+    for (int i = 0; i < cin; ++i)
+      for (int j = 0; j < k; ++j) p[((size_t)o * k + j) * cin_pad + i] = w[((size_t)o * cin + i) * k + j];
+  GSV_RC(up_t(h, p, &c->w));
+  if (bias) {
+    if (!fetch(h, name + ".bias", cout, cout, b)) return GSV_ERR_ARG;
+    GSV_RC(up_f32(h, b.data(), b.size(), &c->b));
+  }
+  c->cin = cin_pad; c->cout = cout; c->taps = k;
+  return GSV_OK;
+}
+
 // several 1x1 convs / Linears stacked along the output dim
 int make_stacked(gsv_vits* h, const std::vector<std::string>& names, int cout_each, int cin, Conv* c) {
   std::vector<float> W, B;
@@ -542,6 +508,17 @@ int make_encoder(gsv_vits* h, const std::string& prefix, int n_layers, std::vect
   return GSV_OK;
 }
 
+// modules.WN(hidden H, kernel 5, dilation rate 1, NL layers, gin GIN) under `prefix`; the last layer has no residual half
+static int make_wn(gsv_vits* h, const std::string& prefix, int NL, int H, int GIN, WNW* w) {
+  w->in.resize(NL); w->res.resize(NL); w->in_bias_eff.resize(NL);
+  for (int li = 0; li < NL; ++li) {
+    GSV_RC(make_conv(h, prefix + ".in_layers." + std::to_string(li), 2 * H, H, 5, true, &w->in[li]));
+    GSV_RC(make_conv(h, prefix + ".res_skip_layers." + std::to_string(li), li < NL - 1 ? 2 * H : H, H, 1, true, &w->res[li]));
+    GSV_RC(dalloc(h, (void**)&w->in_bias_eff[li], (size_t)2 * H * 4));
+  }
+  return make_conv(h, prefix + ".cond_layer", 2 * H * NL, GIN, 1, true, &w->cond);
+}
+
 int need(gsv_vits* h, const char* name, size_t bytes, void** out) {
   Buf& b = h->bufs[name];
   if (b.cap < bytes) {
@@ -587,19 +564,13 @@ int conv(gsv_vits* h, hipStream_t s, const Conv& c, const void* x, int ldx, int 
 }
 
 
-// materialised multi-head attention: q [Tq][ldq] cols qcol0.., k/v [Tk][ldkv] cols kcol0/vcol0..
-// -> out [Tq][ldo] (heads concatenated).  rel_k/rel_v non-null: window-4 relative positions.
-int attention(gsv_vits* h, hipStream_t s, const void* q, int ldq, int qcol0, const void* kv, int ldkv, int kcol0, int vcol0,
-              int Tq, int Tk, int nh, int kc, float scale, const float* rel_k, const float* rel_v, void* out, int ldo, const int* kr) {
-  const size_t es = esz(h);
-  static const bool no_flash = getenv("GSV_MATERIALIZED_ENC_ATTN") != nullptr;    // A/B switch
-  if (!no_flash && h->dtype == GSV_F16 && kc == 96 && rel_k && rel_v && Tq == Tk && q == kv && ldq == ldkv) {
-    void* vtb;
-    GSV_RC(need(h, "att_vt96", (size_t)nh * 96 * ((Tk + 31) / 32 * 32) * 2, &vtb));
-    return launch_flash_rel96_f16((const _Float16*)q + qcol0, ldq, (const _Float16*)kv + kcol0, ldkv, (const _Float16*)kv + vcol0, ldkv,
-                                  vtb, Tq, nh, scale, rel_k, rel_v, out, ldo, s, kr);
-  }
-  const int G = h->dtype == GSV_F16 ? 8 : 4;
+// materialised multi-head attention: scores GEMM -> row softmax -> P V GEMM (-> relative-value term)
+template <typename T>
+static int attention_mat(gsv_vits* h, hipStream_t s, const void* q, int ldq, int qcol0, const void* kv, int ldkv, int kcol0, int vcol0,
+                         int Tq, int Tk, int nh, int kc, float scale, const float* rel_k, const float* rel_v, void* out, int ldo,
+                         const int* kr) {
+  const size_t es = sizeof(T);
+  const int G = es == 2 ? 8 : 4;
   const int ldp = (Tk + G - 1) / G * G;
   void *scores, *P, *Vt, *band;
   GSV_RC(need(h, "att_scores", (size_t)nh * Tq * Tk * 4, &scores));
@@ -613,29 +584,41 @@ int attention(gsv_vits* h, hipStream_t s, const void* q, int ldq, int qcol0, con
   a.Z = nh; a.xz = kc; a.wz = kc; a.yz = (long long)Tq * Tk;
   GSV_RC(launch_conv_gemm(h->dtype, a, s));
   const int w = rel_k ? 4 : 0;
-  GSV_DISPATCH(h,
-    hipLaunchKernelGGL(softmax_rows_kernel<_Float16>, dim3(Tq, nh), dim3(256), Tk <= 12288 ? (size_t)Tk * 4 : 0, s, (const float*)scores, Tq, Tk, ldp, (_Float16*)P,
-                       (const _Float16*)q + qcol0, ldq, kc, rel_k, w, scale, (float*)band, kr),
-    hipLaunchKernelGGL(softmax_rows_kernel<float>, dim3(Tq, nh), dim3(256), Tk <= 12288 ? (size_t)Tk * 4 : 0, s, (const float*)scores, Tq, Tk, ldp, (float*)P,
-                       (const float*)q + qcol0, ldq, kc, rel_k, w, scale, (float*)band, kr));
-  GSV_DISPATCH(h,
-    hipLaunchKernelGGL(transpose_v_kernel<_Float16>, dim3(cdiv(ldp, 32), cdiv(kc, 32), nh), dim3(256), 0, s, (const _Float16*)kv, ldkv,
-                       vcol0, kc, Tk, ldp, (_Float16*)Vt),
-    hipLaunchKernelGGL(transpose_v_kernel<float>, dim3(cdiv(ldp, 32), cdiv(kc, 32), nh), dim3(256), 0, s, (const float*)kv, ldkv, vcol0,
-                       kc, Tk, ldp, (float*)Vt));
+  GSV_LAUNCH(softmax_rows_kernel<T>, dim3(Tq, nh), dim3(256), Tk <= 12288 ? (size_t)Tk * 4 : 0, s, (const float*)scores, Tq, Tk, ldp, (T*)P,
+             (const T*)q + qcol0, ldq, kc, rel_k, w, scale, (float*)band, kr);
+  GSV_LAUNCH(transpose_v_kernel<T>, dim3(cdiv(ldp, 32), cdiv(kc, 32), nh), dim3(256), 0, s, (const T*)kv, ldkv, vcol0, kc, Tk, ldp, (T*)Vt);
   ConvArgs b;
   b.x = P; b.w = Vt; b.y = out;
   b.T_in = Tq; b.T_out = Tq; b.T_virt = Tq; b.Cin = ldp; b.Cout = kc; b.taps = 1;
   b.ldx = ldp; b.ldw = ldp; b.ldy = ldo;
   b.Z = nh; b.xz = (long long)Tq * ldp; b.wz = (long long)kc * ldp; b.yz = kc;
   GSV_RC(launch_conv_gemm(h->dtype, b, s));
-  if (rel_v) {
-    GSV_DISPATCH(h,
-      hipLaunchKernelGGL(relv_add_kernel<_Float16>, dim3(Tq), dim3(256), 0, s, (const float*)band, rel_v, Tq, kc, nh, 4, (_Float16*)out, ldo),
-      hipLaunchKernelGGL(relv_add_kernel<float>, dim3(Tq), dim3(256), 0, s, (const float*)band, rel_v, Tq, kc, nh, 4, (float*)out, ldo));
-  }
-  GSV_HIP(hipGetLastError());
+  if (rel_v) GSV_LAUNCH(relv_add_kernel<T>, dim3(Tq), dim3(256), 0, s, (const float*)band, rel_v, Tq, kc, nh, 4, (T*)out, ldo);
   return GSV_OK;
+}
+
+// multi-head attention: q [Tq][ldq] cols qcol0.., k/v [Tk][ldkv] cols kcol0/vcol0.. -> out [Tq][ldo] (heads concatenated).
+// rel_k/rel_v non-null: window-4 relative positions.  Called with the handle's runtime dtype (also from cfm.hip and bwe.hip):
+// the fused fp16 kernel where it applies, else the materialised path in the handle's element type.
+int attention(gsv_vits* h, hipStream_t s, const void* q, int ldq, int qcol0, const void* kv, int ldkv, int kcol0, int vcol0,
+              int Tq, int Tk, int nh, int kc, float scale, const float* rel_k, const float* rel_v, void* out, int ldo, const int* kr) {
+  static const bool no_flash = getenv("GSV_MATERIALIZED_ENC_ATTN") != nullptr;    // A/B switch
+  if (!no_flash && h->dtype == GSV_F16 && kc == 96 && rel_k && rel_v && Tq == Tk && q == kv && ldq == ldkv) {
+    void* vtb;
+    GSV_RC(need(h, "att_vt96", (size_t)nh * 96 * ((Tk + 31) / 32 * 32) * 2, &vtb));
+    return launch_flash_rel96_f16((const _Float16*)q + qcol0, ldq, (const _Float16*)kv + kcol0, ldkv, (const _Float16*)kv + vcol0, ldkv,
+                                  vtb, Tq, nh, scale, rel_k, rel_v, out, ldo, s, kr);
+  }
+  return GSV_WITH_T(h, attention_mat<T>(h, s, q, ldq, qcol0, kv, ldkv, kcol0, vcol0, Tq, Tk, nh, kc, scale, rel_k, rel_v, out, ldo, kr));
+}
+
+template <typename T>
+static int cf_to_cl_t(hipStream_t s, const float* src, int Tn, int C, void* dst, int ldd = 0) {
+  GSV_LAUNCH(cf_to_cl_kernel<T>, dim3(cdiv(Tn, 32), cdiv(C, 32)), dim3(256), 0, s, src, Tn, C, (T*)dst, ldd);
+  return GSV_OK;
+}
+int cf_to_cl(gsv_vits* h, hipStream_t s, const float* src, int Tn, int C, void* dst, int ldd) {
+  return GSV_WITH_T(h, cf_to_cl_t<T>(s, src, Tn, C, dst, ldd));
 }
 
 // attentions.Encoder.forward (attentions.py:64-84) on x [Tn][H] in place
@@ -738,45 +721,46 @@ struct SegRun {
   const float* bias = nullptr;                           // per-segment voice rows [n][voice_len]
 };
 
+// A conv whose bias carries the speaker conditioning, x [F][c.cin] -> y [F][c.cout].  Plain decode: the handle's folded bias.
+// Segmented decode: the vector at `voff` of a voice row -- one segment takes its row as the bias; with several, the conv runs
+// without bias and a row pass over y adds each segment's own row and zeroes the gap rows (so y must feed nothing in between).
+static int conv_voice(gsv_vits* h, hipStream_t s, const Conv& c, const void* x, int F, void* y, ConvOpt o, const float* handle_bias,
+                      const SegRun* sr, size_t voff) {
+  const float* vrow = sr ? sr->bias + voff : nullptr;
+  const int* seg_f = sr ? sr->seg_f : nullptr;
+  o.bias_override = sr ? vrow : handle_bias;
+  o.no_bias = seg_f != nullptr;
+  GSV_RC(conv(h, s, c, x, c.cin, F, y, F, o));
+  if (seg_f) GSV_RC(launch_seg_rows(h->dtype, 0, y, c.cout, 0, c.cout, F, seg_f, vrow, h->voice_len, s));
+  return GSV_OK;
+}
+
 // quantizer.decode + nearest x2 (H8) and TextEncoder.forward up to (and including) the speed interpolation (H10, reference
 // module/models.py:199-231): returns the hidden sequence y [F][hidden] (what `enc_p` returns as its first value)
-// sr != null: segmented (speed 1), T / L are ignored for the padded totals of sr->lay
-int run_enc_p(gsv_vits* h, hipStream_t s, const int32_t* codes, int T, const int32_t* phones, int L, double speed, void** y_out,
+// sr != null: segmented (speed 1), Tc / L are ignored for the padded totals of sr->lay
+template <typename T>
+int run_enc_p(gsv_vits* h, hipStream_t s, const int32_t* codes, int Tc, const int32_t* phones, int L, double speed, void** y_out,
               int* F_out, const SegRun* sr = nullptr) {
   const auto& c = h->cfg;
   const size_t es = esz(h);
   const int H = c.hidden_channels, SSL = c.ssl_dim, MH = 512;
   if (sr) L = sr->lay->L;
-  const int F0 = sr ? sr->lay->F : 2 * T;
+  const int F0 = sr ? sr->lay->F : 2 * Tc;
   const int F = (speed == 1.0 || sr) ? F0 : (int)((double)F0 / speed) + 1;   // frames after the speed interpolation
   // ---- H8: codebook gather + nearest x2
   void *q768, *y, *tx;
   GSV_RC(need(h, "q768", (size_t)F0 * SSL * es, &q768));
   GSV_RC(need(h, "enc_x", (size_t)F0 * H * es, &y));
   GSV_RC(need(h, "enc_tx", (size_t)L * H * es, &tx));
-  if (sr) {
-    GSV_DISPATCH(h,
-      hipLaunchKernelGGL(gather_seg_kernel<_Float16>, dim3(F0), dim3(128), 0, s, codes, sr->src_code, h->codebook, SSL, F0, (_Float16*)q768),
-      hipLaunchKernelGGL(gather_seg_kernel<float>, dim3(F0), dim3(128), 0, s, codes, sr->src_code, h->codebook, SSL, F0, (float*)q768));
-  } else {
-  GSV_DISPATCH(h,
-    hipLaunchKernelGGL(gather_rows_kernel<_Float16>, dim3(F0), dim3(128), 0, s, codes, h->codebook, SSL, 2, T, (_Float16*)q768),
-    hipLaunchKernelGGL(gather_rows_kernel<float>, dim3(F0), dim3(128), 0, s, codes, h->codebook, SSL, 2, T, (float*)q768));
-  }
+  if (sr) GSV_LAUNCH(gather_seg_kernel<T>, dim3(F0), dim3(128), 0, s, codes, sr->src_code, h->codebook, SSL, F0, (T*)q768);
+  else GSV_LAUNCH(gather_rows_kernel<T>, dim3(F0), dim3(128), 0, s, codes, h->codebook, SSL, 2, Tc, (T*)q768);
   // ---- H10: enc_p
   const int *seg_f = sr ? sr->seg_f : nullptr, *kr_f = sr ? sr->kr_f : nullptr;
   ConvOpt o;
   GSV_RC(conv(h, s, h->ssl_proj_enc, q768, SSL, F0, y, F0, o));
   GSV_RC(run_encoder(h, s, h->enc_ssl, y, F0, seg_f, kr_f));
-  if (sr) {
-    GSV_DISPATCH(h,
-      hipLaunchKernelGGL(gather_seg_kernel<_Float16>, dim3(L), dim3(128), 0, s, phones, sr->src_phone, h->text_emb, H, L, (_Float16*)tx),
-      hipLaunchKernelGGL(gather_seg_kernel<float>, dim3(L), dim3(128), 0, s, phones, sr->src_phone, h->text_emb, H, L, (float*)tx));
-  } else {
-  GSV_DISPATCH(h,
-    hipLaunchKernelGGL(gather_rows_kernel<_Float16>, dim3(L), dim3(128), 0, s, phones, h->text_emb, H, 1, L, (_Float16*)tx),
-    hipLaunchKernelGGL(gather_rows_kernel<float>, dim3(L), dim3(128), 0, s, phones, h->text_emb, H, 1, L, (float*)tx));
-  }
+  if (sr) GSV_LAUNCH(gather_seg_kernel<T>, dim3(L), dim3(128), 0, s, phones, sr->src_phone, h->text_emb, H, L, (T*)tx);
+  else GSV_LAUNCH(gather_rows_kernel<T>, dim3(L), dim3(128), 0, s, phones, h->text_emb, H, 1, L, (T*)tx);
   GSV_RC(run_encoder(h, s, h->enc_text, tx, L, sr ? sr->seg_l : nullptr, sr ? sr->kr_l : nullptr));
   {  // MRTE (mrte_model.py:25-44)
     void *s512, *t512, *q512, *kv512, *o512, *x512;
@@ -792,24 +776,102 @@ int run_enc_p(gsv_vits* h, hipStream_t s, const int32_t* codes, int T, const int
     GSV_RC(conv(h, s, h->mkv, t512, MH, L, kv512, L, o));
     GSV_RC(attention(h, s, q512, MH, 0, kv512, 2 * MH, 0, MH, F0, L, 4, MH / 4, 1.f / sqrtf((float)(MH / 4)), nullptr, nullptr, o512, MH,
                      sr ? sr->kr_x : nullptr));
-    ConvOpt om; om.res = s512; om.ldr = MH; om.bias_override = h->mo_bias_eff;
-    if (sr) om.bias_override = sr->bias;                  // one segment: its voice row
-    if (seg_f) om.no_bias = true;                         // several: each segment's voice row in the row pass below
-    GSV_RC(conv(h, s, h->mo, o512, MH, F0, x512, F0, om));
-    if (seg_f) GSV_RC(launch_seg_rows(h->dtype, 0, x512, MH, 0, MH, F0, seg_f, sr->bias, h->voice_len, s));
+    ConvOpt om; om.res = s512; om.ldr = MH;
+    GSV_RC(conv_voice(h, s, h->mo, o512, F0, x512, om, h->mo_bias_eff, sr, 0));
     GSV_RC(conv(h, s, h->c_post, x512, MH, F0, y, F0, o));
   }
   GSV_RC(run_encoder(h, s, h->enc2, y, F0, seg_f, kr_f));
   if (F != F0) {
     void* yi;
     GSV_RC(need(h, "enc_x_speed", (size_t)F * H * es, &yi));
-    GSV_DISPATCH(h,
-      hipLaunchKernelGGL(interp_linear_kernel<_Float16>, dim3(F), dim3(64), 0, s, (const _Float16*)y, F0, F, H, (_Float16*)yi),
-      hipLaunchKernelGGL(interp_linear_kernel<float>, dim3(F), dim3(64), 0, s, (const float*)y, F0, F, H, (float*)yi));
+    GSV_LAUNCH(interp_linear_kernel<T>, dim3(F), dim3(64), 0, s, (const T*)y, F0, F, H, (T*)yi);
     y = yi;
   }
   *y_out = y;
   *F_out = F;
+  return GSV_OK;
+}
+
+// in_bias_eff[li] = in_layers[li].bias + cond_layer(ge)[li]: the WN's conditioning term is constant per reference audio
+static int fold_wn_cond(gsv_vits* h, hipStream_t s, WNW& w, float* tmp) {
+  ConvOpt o; o.out_f32 = 1;
+  GSV_RC(conv(h, s, w.cond, h->ge_t, w.cond.cin, 1, tmp, 1, o));
+  for (size_t li = 0; li < w.in.size(); ++li) {
+    const int n = w.in[li].cout;
+    GSV_LAUNCH(vec_add_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, tmp + li * n, w.in[li].b, w.in_bias_eff[li], n);
+  }
+  return GSV_OK;
+}
+
+// ref_enc (modules.MelStyleEncoder) over every reference -> ge, then everything ge conditions folded into biases
+template <typename T>
+static int set_refer_impl(gsv_vits* h, const float* const* specs, const int* frames, int bins, const float* const* sv_embs, int n_refs,
+                          gsv_stream_t stream) {
+  GSV_REQUIRE(h && h->finalized, "vits_set_refer: handle not finalized");
+  GSV_REQUIRE(specs && frames && n_refs >= 1, "vits_set_refer: no reference spectrogram");
+  GSV_REQUIRE(bins >= h->cfg.ref_bins, "vits_set_refer: spectrogram has %d bins, need >= %d", bins, h->cfg.ref_bins);
+  hipStream_t s = (hipStream_t)stream;
+  h->ref_stream = s;
+  const auto& c = h->cfg;
+  const size_t es = esz(h);
+  const int RB = c.ref_bins, RH = 128, GIN = c.gin_channels;
+  for (int r = 0; r < n_refs; ++r) {
+    const int Tr = frames[r];
+    GSV_REQUIRE(Tr >= 1 && specs[r], "vits_set_refer: empty reference %d", r);
+    void *x0, *a, *b, *y2, *qkv, *ao;
+    GSV_RC(need(h, "ref_x0", (size_t)Tr * RB * es, &x0));
+    GSV_RC(need(h, "ref_a", (size_t)Tr * RH * es, &a));
+    GSV_RC(need(h, "ref_b", (size_t)Tr * RH * es, &b));
+    GSV_RC(need(h, "ref_y2", (size_t)Tr * 2 * RH * es, &y2));
+    GSV_RC(need(h, "ref_qkv", (size_t)Tr * 3 * RH * es, &qkv));
+    GSV_RC(need(h, "ref_ao", (size_t)Tr * GIN * es, &ao));
+    GSV_RC(cf_to_cl_t<T>(s, specs[r], Tr, RB, x0));
+    ConvOpt om; om.post_act = ACT_MISH;
+    GSV_RC(conv(h, s, h->r_sp0, x0, RB, Tr, a, Tr, om));
+    GSV_RC(conv(h, s, h->r_sp3, a, RH, Tr, b, Tr, om));
+    ConvOpt o;
+    for (int t = 0; t < 2; ++t) {
+      GSV_RC(conv(h, s, t == 0 ? h->r_t0 : h->r_t1, b, RH, Tr, y2, Tr, o));
+      GSV_LAUNCH(glu_res_kernel<T>, dim3(nblk((long long)Tr * RH)), dim3(256), 0, s, (const T*)y2, (long long)Tr * RH, RH, (T*)b);
+    }
+    GSV_RC(conv(h, s, h->r_qkv, b, RH, Tr, qkv, Tr, o));
+    // 2 heads x 64, temperature sqrt(d_model) (modules.py:610)
+    GSV_RC(attention(h, s, qkv, 3 * RH, 0, qkv, 3 * RH, RH, 2 * RH, Tr, Tr, 2, RH / 2, 1.f / sqrtf((float)RH), nullptr, nullptr, a, RH));
+    ConvOpt orr; orr.res = b; orr.ldr = RH;
+    GSV_RC(conv(h, s, h->r_fc, a, RH, Tr, y2, Tr, orr));          // fc(attn) + residual -> y2 [Tr][RH]
+    GSV_RC(conv(h, s, h->r_out, y2, RH, Tr, ao, Tr, o));            // [Tr][GIN]
+    if (!sv_embs) {
+      GSV_LAUNCH(mean_time_kernel<T>, dim3(cdiv(GIN, 64)), dim3(64), 0, s, (const T*)ao, Tr, GIN, 1.f / n_refs, r > 0, h->ge);
+    } else {
+      GSV_LAUNCH(mean_time_kernel<T>, dim3(cdiv(GIN, 64)), dim3(64), 0, s, (const T*)ao, Tr, GIN, 1.f, 0, h->ge_ref);
+      GSV_RC(launch_convert(sv_embs[r], h->sv_t, h->dtype, 20480, s));
+      ConvOpt osv; osv.out_f32 = 1;
+      GSV_RC(conv(h, s, h->sv_emb, h->sv_t, 20480, 1, h->sv_proj, 1, osv));
+      GSV_LAUNCH(sv_prelu_acc_kernel, dim3(cdiv(GIN, 256)), dim3(256), 0, s, (const float*)h->ge_ref, (const float*)h->sv_proj,
+                 (const float*)h->prelu_w, 1.f / n_refs, r > 0, GIN, h->ge);
+    }
+  }
+  GSV_RC(launch_convert(h->ge, h->ge_t, h->dtype, GIN, s));
+  // fold conditioning into biases: conv_pre + cond(ge); MRTE conv_o bias + ge; WN in_layers + cond_layer(ge)
+  float* tmp;
+  GSV_RC(need(h, "cond_tmp", (size_t)2048 * 4 * 4, (void**)&tmp));
+  {
+    ConvOpt o; o.out_f32 = 1;
+    if (c.v2pro) {     // the MRTE adds ge_to512(ge) (models.py:997)
+      GSV_RC(conv(h, s, h->ge_to512, h->ge_t, GIN, 1, h->ge512, 1, o));
+      GSV_LAUNCH(vec_add_kernel, dim3(cdiv(512, 256)), dim3(256), 0, s, h->ge512, h->mo.b, h->mo_bias_eff, 512);
+    } else {
+      GSV_LAUNCH(vec_add_kernel, dim3(cdiv(GIN, 256)), dim3(256), 0, s, h->ge, h->mo.b, h->mo_bias_eff, GIN);
+    }
+    if (c.flavor != 0) {
+      GSV_RC(fold_wn_cond(h, s, h->w1, tmp));
+    } else {
+      GSV_RC(conv(h, s, h->cond, h->ge_t, GIN, 1, tmp, 1, o));
+      GSV_LAUNCH(vec_add_kernel, dim3(cdiv(h->conv_pre.cout, 256)), dim3(256), 0, s, tmp, h->conv_pre.b, h->conv_pre_bias_eff, h->conv_pre.cout);
+      for (int fi = 0; fi < 4; ++fi) GSV_RC(fold_wn_cond(h, s, h->flows[fi].wn, tmp));
+    }
+  }
+  h->has_ref = true;
   return GSV_OK;
 }
 
@@ -835,8 +897,7 @@ int gsv_vits_create(const gsv_vits_config* cfg, int dtype, gsv_vits_t** out) {
 
 void gsv_vits_destroy(gsv_vits_t* h) {
   if (!h) return;
-  for (void* p : h->allocs) (void)hipFree(p);
-  for (auto& b : h->bufs) if (b.second.p) (void)hipFree(b.second.p);
+  free_ctx(h);
   for (auto e : h->ev) if (e) (void)hipEventDestroy(e);
   if (h->seg_ev) (void)hipEventDestroy(h->seg_ev);
   delete h;
@@ -884,44 +945,22 @@ int gsv_vits_finalize(gsv_vits_t* h) {
     GSV_RC(make_conv(h, "ssl_proj", SSL, SSL, 2, true, &h->top_ssl_proj));
   }
   if (c.flavor == 0) {
-  // flow
-  for (int fi = 0; fi < 4; ++fi) {
-    FlowW& f = h->flows[fi];
-    const std::string p = "flow.flows." + std::to_string(2 * fi);
-    GSV_RC(make_conv(h, p + ".pre", H, IC / 2, 1, true, &f.pre));
-    GSV_RC(make_conv(h, p + ".post", IC / 2, H, 1, true, &f.post));
-    for (int li = 0; li < 4; ++li) {
-      GSV_RC(make_conv(h, p + ".enc.in_layers." + std::to_string(li), 2 * H, H, 5, true, &f.wn.in[li]));
-      const int rs = li < 3 ? 2 * H : H;
-      GSV_RC(make_conv(h, p + ".enc.res_skip_layers." + std::to_string(li), rs, H, 1, true, &f.wn.res[li]));
-      GSV_RC(dalloc(h, (void**)&f.wn.in_bias_eff[li], (size_t)2 * H * 4));
+    // flow
+    for (int fi = 0; fi < 4; ++fi) {
+      FlowW& f = h->flows[fi];
+      const std::string p = "flow.flows." + std::to_string(2 * fi);
+      GSV_RC(make_conv(h, p + ".pre", H, IC / 2, 1, true, &f.pre));
+      GSV_RC(make_conv(h, p + ".post", IC / 2, H, 1, true, &f.post));
+      GSV_RC(make_wn(h, p + ".enc", 4, H, GIN, &f.wn));
     }
-    GSV_RC(make_conv(h, p + ".enc.cond_layer", 2 * H * 4, GIN, 1, true, &f.wn.cond));
-  }
-  // generator
-  const int UIC = c.upsample_initial_channel;
-  GSV_RC(make_conv(h, "dec.conv_pre", UIC, IC, 7, true, &h->conv_pre));
-  GSV_RC(make_conv(h, "dec.cond", UIC, GIN, 1, true, &h->cond));
-  GSV_RC(dalloc(h, (void**)&h->conv_pre_bias_eff, (size_t)UIC * 4));
-  h->ups.resize(c.n_ups);
-  int ch = UIC;
-  for (int i = 0; i < c.n_ups; ++i) {
-    const int cin = UIC >> i, cout = UIC >> (i + 1);
-    GSV_REQUIRE(cout % 8 == 0, "vits: generator channel count %d must be a multiple of 8", cout);
-    GSV_RC(make_ups(h, "dec.ups." + std::to_string(i), cin, cout, c.up_kernels[i], c.up_rates[i], &h->ups[i]));
-    ch = cout;
-    for (int j = 0; j < c.n_resblocks; ++j) {
-      const std::string r = "dec.resblocks." + std::to_string(i * c.n_resblocks + j);
-      for (int k = 0; k < 3; ++k) {
-        Conv c1, c2;
-        GSV_RC(make_conv(h, r + ".convs1." + std::to_string(k), ch, ch, c.rb_kernels[j], true, &c1));
-        GSV_RC(make_conv(h, r + ".convs2." + std::to_string(k), ch, ch, c.rb_kernels[j], true, &c2));
-        h->rb1.push_back(c1);
-        h->rb2.push_back(c2);
-      }
-    }
-  }
-  GSV_RC(make_conv(h, "dec.conv_post", 1, ch, 7, false, &h->conv_post));
+    // generator
+    const int UIC = c.upsample_initial_channel;
+    GSV_RC(make_conv(h, "dec.conv_pre", UIC, IC, 7, true, &h->conv_pre));
+    GSV_RC(make_conv(h, "dec.cond", UIC, GIN, 1, true, &h->cond));
+    GSV_RC(dalloc(h, (void**)&h->conv_pre_bias_eff, (size_t)UIC * 4));
+    gen_shape(c, &h->gen);
+    GSV_RC(load_generator(h, "dec.", false, &h->gen));
+    GSV_RC(make_conv(h, "dec.conv_post", 1, UIC >> c.n_ups, 7, false, &h->conv_post));
   } else {
     // v3 / v4 (SynthesizerTrnV3, module/models.py:1203-1206): bridge + wns1 = Encoder(512, 512, 512, 5, 1, 8, gin)
     const int W = 512, NL = 8;
@@ -929,13 +968,7 @@ int gsv_vits_finalize(gsv_vits_t* h) {
     GSV_RC(make_conv(h, "bridge.0", W, IC, 1, true, &h->bridge));
     GSV_RC(make_conv(h, "wns1.pre", W, W, 1, true, &h->w1_pre));
     GSV_RC(make_conv(h, "wns1.proj", W, W, 1, true, &h->w1_proj));
-    GSV_RC(make_conv(h, "wns1.enc.cond_layer", 2 * W * NL, GIN, 1, true, &h->w1_cond));
-    h->w1_in.resize(NL); h->w1_res.resize(NL); h->w1_in_bias_eff.resize(NL);
-    for (int li = 0; li < NL; ++li) {
-      GSV_RC(make_conv(h, "wns1.enc.in_layers." + std::to_string(li), 2 * W, W, 5, true, &h->w1_in[li]));
-      GSV_RC(make_conv(h, "wns1.enc.res_skip_layers." + std::to_string(li), li < NL - 1 ? 2 * W : W, W, 1, true, &h->w1_res[li]));
-      GSV_RC(dalloc(h, (void**)&h->w1_in_bias_eff[li], (size_t)2 * W * 4));
-    }
+    GSV_RC(make_wn(h, "wns1.enc", NL, W, GIN, &h->w1));
   }
   // ref_enc
   const int RH = 128;
@@ -964,13 +997,10 @@ int gsv_vits_finalize(gsv_vits_t* h) {
   return GSV_OK;
 }
 
-static int set_refer_impl(gsv_vits_t* h, const float* const* specs, const int* frames, int bins, const float* const* sv_embs, int n_refs,
-                          gsv_stream_t stream);
-
 int gsv_vits_set_refer(gsv_vits_t* h, const float* const* specs, const int* frames, int bins, int n_refs, gsv_stream_t stream) {
   GSV_REQUIRE(h && h->finalized, "vits_set_refer: handle not finalized");
   GSV_REQUIRE(!h->cfg.v2pro, "vits_set_refer: a v2Pro model needs gsv_vits_set_refer_sv (one sv embedding per reference)");
-  return set_refer_impl(h, specs, frames, bins, nullptr, n_refs, stream);
+  return GSV_WITH_T(h, set_refer_impl<T>(h, specs, frames, bins, nullptr, n_refs, stream));
 }
 
 int gsv_vits_set_refer_sv(gsv_vits_t* h, const float* const* specs, const int* frames, int bins, const float* const* sv_embs,
@@ -978,109 +1008,50 @@ int gsv_vits_set_refer_sv(gsv_vits_t* h, const float* const* specs, const int* f
   GSV_REQUIRE(h && h->finalized, "vits_set_refer_sv: handle not finalized");
   GSV_REQUIRE(h->cfg.v2pro && sv_embs, "vits_set_refer_sv: not a v2Pro model, or no sv embeddings");
   for (int r = 0; r < n_refs; ++r) GSV_REQUIRE(sv_embs[r], "vits_set_refer_sv: missing sv embedding %d", r);
-  return set_refer_impl(h, specs, frames, bins, sv_embs, n_refs, stream);
-}
-
-static int set_refer_impl(gsv_vits_t* h, const float* const* specs, const int* frames, int bins, const float* const* sv_embs, int n_refs,
-                          gsv_stream_t stream) {
-  GSV_REQUIRE(h && h->finalized, "vits_set_refer: handle not finalized");
-  GSV_REQUIRE(specs && frames && n_refs >= 1, "vits_set_refer: no reference spectrogram");
-  GSV_REQUIRE(bins >= h->cfg.ref_bins, "vits_set_refer: spectrogram has %d bins, need >= %d", bins, h->cfg.ref_bins);
-  hipStream_t s = (hipStream_t)stream;
-  h->ref_stream = s;
-  const auto& c = h->cfg;
-  const size_t es = esz(h);
-  const int RB = c.ref_bins, RH = 128, GIN = c.gin_channels;
-  for (int r = 0; r < n_refs; ++r) {
-    const int Tr = frames[r];
-    GSV_REQUIRE(Tr >= 1 && specs[r], "vits_set_refer: empty reference %d", r);
-    void *x0, *a, *b, *y2, *qkv, *ao;
-    GSV_RC(need(h, "ref_x0", (size_t)Tr * RB * es, &x0));
-    GSV_RC(need(h, "ref_a", (size_t)Tr * RH * es, &a));
-    GSV_RC(need(h, "ref_b", (size_t)Tr * RH * es, &b));
-    GSV_RC(need(h, "ref_y2", (size_t)Tr * 2 * RH * es, &y2));
-    GSV_RC(need(h, "ref_qkv", (size_t)Tr * 3 * RH * es, &qkv));
-    GSV_RC(need(h, "ref_ao", (size_t)Tr * GIN * es, &ao));
-    GSV_DISPATCH(h,
-      hipLaunchKernelGGL(cf_to_cl_kernel<_Float16>, dim3(cdiv(Tr, 32), cdiv(RB, 32)), dim3(256), 0, s, specs[r], Tr, RB, (_Float16*)x0),
-      hipLaunchKernelGGL(cf_to_cl_kernel<float>, dim3(cdiv(Tr, 32), cdiv(RB, 32)), dim3(256), 0, s, specs[r], Tr, RB, (float*)x0));
-    ConvOpt om; om.post_act = ACT_MISH;
-    GSV_RC(conv(h, s, h->r_sp0, x0, RB, Tr, a, Tr, om));
-    GSV_RC(conv(h, s, h->r_sp3, a, RH, Tr, b, Tr, om));
-    ConvOpt o;
-    for (int t = 0; t < 2; ++t) {
-      GSV_RC(conv(h, s, t == 0 ? h->r_t0 : h->r_t1, b, RH, Tr, y2, Tr, o));
-      GSV_DISPATCH(h,
-        hipLaunchKernelGGL(glu_res_kernel<_Float16>, dim3(nblk((long long)Tr * RH)), dim3(256), 0, s, (const _Float16*)y2, (long long)Tr * RH, RH, (_Float16*)b),
-        hipLaunchKernelGGL(glu_res_kernel<float>, dim3(nblk((long long)Tr * RH)), dim3(256), 0, s, (const float*)y2, (long long)Tr * RH, RH, (float*)b));
-    }
-    GSV_RC(conv(h, s, h->r_qkv, b, RH, Tr, qkv, Tr, o));
-    // 2 heads x 64, temperature sqrt(d_model) (modules.py:610)
-    GSV_RC(attention(h, s, qkv, 3 * RH, 0, qkv, 3 * RH, RH, 2 * RH, Tr, Tr, 2, RH / 2, 1.f / sqrtf((float)RH), nullptr, nullptr, a, RH));
-    ConvOpt orr; orr.res = b; orr.ldr = RH;
-    GSV_RC(conv(h, s, h->r_fc, a, RH, Tr, y2, Tr, orr));          // fc(attn) + residual -> y2 [Tr][RH]
-    GSV_RC(conv(h, s, h->r_out, y2, RH, Tr, ao, Tr, o));            // [Tr][GIN]
-    if (!sv_embs) {
-      GSV_DISPATCH(h,
-        hipLaunchKernelGGL(mean_time_kernel<_Float16>, dim3(cdiv(GIN, 64)), dim3(64), 0, s, (const _Float16*)ao, Tr, GIN, 1.f / n_refs, r > 0, h->ge),
-        hipLaunchKernelGGL(mean_time_kernel<float>, dim3(cdiv(GIN, 64)), dim3(64), 0, s, (const float*)ao, Tr, GIN, 1.f / n_refs, r > 0, h->ge));
-    } else {
-      GSV_DISPATCH(h,
-        hipLaunchKernelGGL(mean_time_kernel<_Float16>, dim3(cdiv(GIN, 64)), dim3(64), 0, s, (const _Float16*)ao, Tr, GIN, 1.f, 0, h->ge_ref),
-        hipLaunchKernelGGL(mean_time_kernel<float>, dim3(cdiv(GIN, 64)), dim3(64), 0, s, (const float*)ao, Tr, GIN, 1.f, 0, h->ge_ref));
-      GSV_RC(launch_convert(sv_embs[r], h->sv_t, h->dtype, 20480, s));
-      ConvOpt osv; osv.out_f32 = 1;
-      GSV_RC(conv(h, s, h->sv_emb, h->sv_t, 20480, 1, h->sv_proj, 1, osv));
-      hipLaunchKernelGGL(sv_prelu_acc_kernel, dim3(cdiv(GIN, 256)), dim3(256), 0, s, (const float*)h->ge_ref, (const float*)h->sv_proj,
-                         (const float*)h->prelu_w, 1.f / n_refs, r > 0, GIN, h->ge);
-    }
-  }
-  GSV_RC(launch_convert(h->ge, h->ge_t, h->dtype, GIN, s));
-  // fold conditioning into biases: conv_pre + cond(ge); MRTE conv_o bias + ge; WN in_layers + cond_layer(ge)
-  float* tmp;
-  GSV_RC(need(h, "cond_tmp", (size_t)2048 * 4 * 4, (void**)&tmp));
-  {
-    ConvOpt o; o.out_f32 = 1;
-    if (c.v2pro) {     // the MRTE adds ge_to512(ge) (models.py:997)
-      GSV_RC(conv(h, s, h->ge_to512, h->ge_t, GIN, 1, h->ge512, 1, o));
-      hipLaunchKernelGGL(vec_add_kernel, dim3(cdiv(512, 256)), dim3(256), 0, s, h->ge512, h->mo.b, h->mo_bias_eff, 512);
-    } else {
-      hipLaunchKernelGGL(vec_add_kernel, dim3(cdiv(GIN, 256)), dim3(256), 0, s, h->ge, h->mo.b, h->mo_bias_eff, GIN);
-    }
-    if (c.flavor != 0) {
-      GSV_RC(conv(h, s, h->w1_cond, h->ge_t, GIN, 1, tmp, 1, o));
-      const int n = 2 * 512;
-      for (size_t li = 0; li < h->w1_in.size(); ++li)
-        hipLaunchKernelGGL(vec_add_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, tmp + li * n, h->w1_in[li].b, h->w1_in_bias_eff[li], n);
-    } else {
-    GSV_RC(conv(h, s, h->cond, h->ge_t, GIN, 1, tmp, 1, o));
-    hipLaunchKernelGGL(vec_add_kernel, dim3(cdiv(h->conv_pre.cout, 256)), dim3(256), 0, s, tmp, h->conv_pre.b, h->conv_pre_bias_eff, h->conv_pre.cout);
-    for (int fi = 0; fi < 4; ++fi) {
-      WNW& w = h->flows[fi].wn;
-      GSV_RC(conv(h, s, w.cond, h->ge_t, GIN, 1, tmp, 1, o));
-      const int n = 2 * c.hidden_channels;
-      for (int li = 0; li < 4; ++li)
-        hipLaunchKernelGGL(vec_add_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, tmp + li * n, w.in[li].b, w.in_bias_eff[li], n);
-    }
-    }
-  }
-  GSV_HIP(hipGetLastError());
-  h->has_ref = true;
-  return GSV_OK;
+  return GSV_WITH_T(h, set_refer_impl<T>(h, specs, frames, bins, sv_embs, n_refs, stream));
 }
 
 }  // extern "C"
 
 namespace gsveng {
-// proj -> z_p -> flow reverse -> generator on the enc_p output y [F][hidden]; sr != null: segmented (gap rows masked, per-segment
-// voice biases and noise keys, the gaps dropped from the waveform)
-static int decode_tail(gsv_vits* h, hipStream_t s, void* y, int F, const float* noise, float noise_scale, uint64_t seed, float* wav,
-                       const SegRun* sr) {
+// modules.WN.forward (modules.py:  in -> gate -> res/skip) on hb [F][H]: hb accumulates the residual halves, wout [F][H] the skip
+// halves; xin [F][2H] and acts [F][H] are scratch.  The two ways rows are masked, and where the in-layer bias comes from:
+//   sr != null (segmented flow): voice-row biases at voff + li * 2H (conv_voice), sr->seg_f keeps the gap rows of hb zero;
+//   Lm < F (wns1, models.py:1252-1258): rows >= Lm of hb are zeroed after each residual add.
+template <typename T>
+static int run_wn(gsv_vits* h, hipStream_t s, const WNW& w, int F, void* hb, void* xin, void* acts, void* wout, const SegRun* sr,
+                  size_t voff, int Lm) {
+  const int NL = (int)w.in.size(), H = w.in[0].cin;
+  const int* seg_f = sr ? sr->seg_f : nullptr;
+  for (int li = 0; li < NL; ++li) {
+    GSV_RC(conv_voice(h, s, w.in[li], hb, F, xin, ConvOpt(), w.in_bias_eff[li], sr, voff + (size_t)li * 2 * H));   // xin feeds only the gate
+    GSV_LAUNCH(gate_kernel<T>, dim3(nblk((long long)F * H)), dim3(256), 0, s, (const T*)xin, (long long)F * H, H, (T*)acts);
+    if (li < NL - 1) {
+      ConvOpt ores; ores.cout = H; ores.w_row0 = 0; ores.accumulate = 1; ores.row_seg = seg_f;   // h += rs[:H]
+      GSV_RC(conv(h, s, w.res[li], acts, H, F, hb, F, ores));
+      if (Lm < F) GSV_HIP(hipMemsetAsync((T*)hb + (size_t)Lm * H, 0, (size_t)(F - Lm) * H * sizeof(T), s));
+      ConvOpt osk; osk.cout = H; osk.w_row0 = H; osk.accumulate = li > 0;       // out (+)= rs[H:]
+      GSV_RC(conv(h, s, w.res[li], acts, H, F, wout, F, osk));
+    } else {
+      ConvOpt osk; osk.accumulate = li > 0;
+      GSV_RC(conv(h, s, w.res[li], acts, H, F, wout, F, osk));
+    }
+  }
+  return GSV_OK;
+}
+
+// the v1/v2 decode: enc_p -> proj -> z_p -> flow reverse -> generator; sr != null: segmented (gap rows masked, per-segment voice
+// biases and noise keys, the gaps dropped from the waveform)
+template <typename T>
+static int decode_wav(gsv_vits* h, hipStream_t s, const int32_t* codes, int Tc, const int32_t* phones, int L, double speed,
+                      const float* noise, float noise_scale, uint64_t seed, float* wav, const SegRun* sr) {
   const auto& c = h->cfg;
-  const size_t es = esz(h);
+  void* y = nullptr;
+  int F = 0;
+  GSV_RC(run_enc_p<T>(h, s, codes, Tc, phones, L, speed, &y, &F, sr));
+  const size_t es = sizeof(T);
   const int H = c.hidden_channels, IC = c.inter_channels;
   const int* seg_f = sr ? sr->seg_f : nullptr;
-  ConvOpt o;
   float* stats;
   GSV_RC(need(h, "stats", (size_t)F * 2 * IC * 4, (void**)&stats));
   { ConvOpt of; of.out_f32 = 1; GSV_RC(conv(h, s, h->proj, y, H, F, stats, F, of)); }
@@ -1092,40 +1063,16 @@ static int decode_tail(gsv_vits* h, hipStream_t s, void* y, int F, const float* 
   GSV_RC(need(h, "wn_xin", (size_t)F * 2 * H * es, &xin));
   GSV_RC(need(h, "wn_acts", (size_t)F * H * es, &acts));
   GSV_RC(need(h, "wn_out", (size_t)F * H * es, &wout));
-  GSV_DISPATCH(h,
-    hipLaunchKernelGGL(zp_kernel<_Float16>, dim3(nblk((long long)F * IC)), dim3(256), 0, s, stats, F, IC, noise, noise_scale, (unsigned long long)seed, (_Float16*)z,
-                       seg_f, sr ? sr->start : nullptr, sr ? sr->noff : nullptr, sr ? sr->seeds : nullptr, sr ? sr->lay->Fn : 0),
-    hipLaunchKernelGGL(zp_kernel<float>, dim3(nblk((long long)F * IC)), dim3(256), 0, s, stats, F, IC, noise, noise_scale, (unsigned long long)seed, (float*)z,
-                       seg_f, sr ? sr->start : nullptr, sr ? sr->noff : nullptr, sr ? sr->seeds : nullptr, sr ? sr->lay->Fn : 0));
+  GSV_LAUNCH(zp_kernel<T>, dim3(nblk((long long)F * IC)), dim3(256), 0, s, stats, F, IC, noise, noise_scale, (unsigned long long)seed, (T*)z,
+             seg_f, sr ? sr->start : nullptr, sr ? sr->noff : nullptr, sr ? sr->seeds : nullptr, sr ? sr->lay->Fn : 0);
   const int half = IC / 2;
   for (int fi = 3; fi >= 0; --fi) {
     FlowW& f = h->flows[fi];
-    GSV_DISPATCH(h,
-      hipLaunchKernelGGL(flip_channels_kernel<_Float16>, dim3(nblk((long long)F * IC)), dim3(256), 0, s, (const _Float16*)z, (long long)F * IC, IC, (_Float16*)zf),
-      hipLaunchKernelGGL(flip_channels_kernel<float>, dim3(nblk((long long)F * IC)), dim3(256), 0, s, (const float*)z, (long long)F * IC, IC, (float*)zf));
+    GSV_LAUNCH(flip_channels_kernel<T>, dim3(nblk((long long)F * IC)), dim3(256), 0, s, (const T*)z, (long long)F * IC, IC, (T*)zf);
     std::swap(z, zf);
     ConvOpt om; om.row_seg = seg_f;                  // what the WN in_layers (kernel 5) read: gap rows stay 0
     GSV_RC(conv(h, s, f.pre, z, IC, F, hb, F, om));  // x0 = channels [0, half)
-    for (int li = 0; li < 4; ++li) {
-      ConvOpt oi; oi.bias_override = f.wn.in_bias_eff[li];
-      const float* vrow = sr ? sr->bias + h->voice_off_in + (size_t)(fi * 4 + li) * 2 * H : nullptr;
-      if (sr) oi.bias_override = vrow;
-      if (seg_f) oi.no_bias = true;                   // each segment's voice row in the row pass (xin feeds only the gate)
-      GSV_RC(conv(h, s, f.wn.in[li], hb, H, F, xin, F, oi));
-      if (seg_f) GSV_RC(launch_seg_rows(h->dtype, 0, xin, 2 * H, 0, 2 * H, F, seg_f, vrow, h->voice_len, s));
-      GSV_DISPATCH(h,
-        hipLaunchKernelGGL(gate_kernel<_Float16>, dim3(nblk((long long)F * H)), dim3(256), 0, s, (const _Float16*)xin, (long long)F * H, H, (_Float16*)acts),
-        hipLaunchKernelGGL(gate_kernel<float>, dim3(nblk((long long)F * H)), dim3(256), 0, s, (const float*)xin, (long long)F * H, H, (float*)acts));
-      if (li < 3) {
-        ConvOpt ores; ores.cout = H; ores.w_row0 = 0; ores.accumulate = 1; ores.row_seg = seg_f;   // h += rs[:H]
-        GSV_RC(conv(h, s, f.wn.res[li], acts, H, F, hb, F, ores));
-        ConvOpt osk; osk.cout = H; osk.w_row0 = H; osk.accumulate = li > 0;       // out (+)= rs[H:]
-        GSV_RC(conv(h, s, f.wn.res[li], acts, H, F, wout, F, osk));
-      } else {
-        ConvOpt osk; osk.accumulate = 1;
-        GSV_RC(conv(h, s, f.wn.res[li], acts, H, F, wout, F, osk));
-      }
-    }
+    GSV_RC(run_wn<T>(h, s, f.wn, F, hb, xin, acts, wout, sr, h->voice_off_in + (size_t)fi * 4 * 2 * H, F));
     ConvOpt op; op.scale = -1.f; op.accumulate = 1; op.ldy = IC; op.y_col0 = half; op.row_seg = seg_f;  // x1 -= post(h)
     GSV_RC(conv(h, s, f.post, wout, H, F, z, F, op));
   }
@@ -1138,96 +1085,110 @@ static int decode_tail(gsv_vits* h, hipStream_t s, void* y, int F, const float* 
   }
   GSV_HIP(hipEventRecord(h->ev[1], s));
   // ---- H12: generator
-  size_t maxel = (size_t)F * c.upsample_initial_channel;
-  {
-    long long Tn = F; int ch = c.upsample_initial_channel;
-    for (int i = 0; i < c.n_ups; ++i) { Tn *= c.up_rates[i]; ch >>= 1; maxel = std::max(maxel, (size_t)Tn * ch); }
-  }
   void* gb[5];
-  const char* gnames[5] = {"g0", "g1", "g2", "g3", "g4"};
-  for (int i = 0; i < 5; ++i) GSV_RC(need(h, gnames[i], maxel * es, &gb[i]));
+  GSV_RC(gen_buffers(h, h->gen, "g", F, gb));
   void* cur = gb[3];
-  { ConvOpt op; op.bias_override = h->conv_pre_bias_eff;
-    const float* vrow = sr ? sr->bias + h->voice_off_pre : nullptr;
-    if (sr) op.bias_override = vrow;
-    if (seg_f) op.no_bias = true;
-    GSV_RC(conv(h, s, h->conv_pre, z, IC, F, cur, F, op));
-    if (seg_f) GSV_RC(launch_seg_rows(h->dtype, 0, cur, c.upsample_initial_channel, 0, c.upsample_initial_channel, F, seg_f, vrow,
-                                      h->voice_len, s)); }
-  int Tn = F, ch = c.upsample_initial_channel;
-  for (int i = 0; i < c.n_ups; ++i) {
-    const int Tout = Tn * c.up_rates[i];
-    ch >>= 1;
-    void* xup = gb[0]; void* xt = gb[1]; void* R = gb[2]; void* xs = (cur == gb[3]) ? gb[4] : gb[3];
-    const int* seg_o = seg_f ? sr->seg_up[i] : nullptr;   // gap rows of this stage's outputs
-    h->dbg_last_in = cur; h->dbg_last_T = Tn; h->dbg_last_C = 2 * ch;
-    { ConvOpt ou; ou.pre_act = ACT_LRELU; ou.pre_slope = 0.1f; ou.row_seg = seg_o; GSV_RC(conv(h, s, h->ups[i], cur, ch * 2, Tn, xup, Tout, ou)); }
-    for (int j = 0; j < c.n_resblocks; ++j) {
-      const void* xr = xup;
-      for (int k = 0; k < 3; ++k) {
-        const Conv& c1 = h->rb1[(i * c.n_resblocks + j) * 3 + k];
-        const Conv& c2 = h->rb2[(i * c.n_resblocks + j) * 3 + k];
-        // segmented: the masked pair zeroes the gap rows of its LDS intermediate and of its output itself (conv_pair.hip, SEG);
-        // GSV_NO_SEG_PAIR=1 is the A/B switch back to the two convs with their row passes
-        static const bool no_seg_pair = getenv("GSV_NO_SEG_PAIR") != nullptr;
-        if (!(seg_o && no_seg_pair) && c1.b && c2.b && c1.taps == c2.taps && conv_pair_eligible(h->dtype, ch, c1.taps, c.rb_dilations[j][k], Tout)) {
-          // narrow stages: the pair in one kernel, the intermediate tensor never leaves the CU (conv_pair.hip)
-          ConvPairArgs pa;
-          pa.x = (const _Float16*)xr; pa.w1 = (const _Float16*)c1.w; pa.b1 = c1.b; pa.w2 = (const _Float16*)c2.w; pa.b2 = c2.b;
-          pa.T = Tout; pa.C = ch; pa.taps = c1.taps; pa.dil = c.rb_dilations[j][k]; pa.ldx = ch; pa.ldy = ch;
-          if (k < 2) { pa.y = (_Float16*)R; }
-          else { pa.y = (_Float16*)xs; pa.scale = 1.f / (float)c.n_resblocks; pa.accumulate = j > 0; }
-          // the pair reads x as window AND residual: it must not be overwritten in place
-          if ((const void*)pa.y == xr) { pa.y = (_Float16*)xt; }
-          if (seg_o) { GSV_RC(launch_conv_pair_seg(pa, seg_o, s)); }
-          else { GSV_RC(launch_conv_pair(pa, s)); }
-          if (k < 2) { if (pa.y == (_Float16*)xt) { std::swap(xt, R); } xr = R; }
-          continue;
-        }
-        ConvOpt o1; o1.pre_act = ACT_LRELU; o1.pre_slope = 0.1f; o1.dil = c.rb_dilations[j][k]; o1.row_seg = seg_o;
-        GSV_RC(conv(h, s, c1, xr, ch, Tout, xt, Tout, o1));
-        ConvOpt o2; o2.pre_act = ACT_LRELU; o2.pre_slope = 0.1f; o2.res = xr; o2.ldr = ch; o2.row_seg = seg_o;
-        if (k < 2) {
-          GSV_RC(conv(h, s, c2, xt, ch, Tout, R, Tout, o2));
-          xr = R;
-        } else {
-          o2.scale = 1.f / (float)c.n_resblocks; o2.accumulate = j > 0;
-          GSV_RC(conv(h, s, c2, xt, ch, Tout, xs, Tout, o2));
-        }
-      }
-    }
-    cur = xs; Tn = Tout;
-  }
+  GSV_RC(conv_voice(h, s, h->conv_pre, z, F, cur, ConvOpt(), h->conv_pre_bias_eff, sr, h->voice_off_pre));
+  int Tn = F;
+  GSV_RC(run_generator_stages(h, s, h->gen, gb, &cur, &Tn, seg_f ? sr->seg_up.data() : nullptr));
   float* wout_p = wav;                 // segmented: the padded waveform, then the gaps are dropped into wav
   if (seg_f) GSV_RC(need(h, "wav_pad", (size_t)Tn * 4, (void**)&wout_p));
   { ConvOpt op; op.pre_act = ACT_LRELU; op.pre_slope = 0.01f; op.post_act = ACT_TANH; op.out_f32 = 1;
-    GSV_RC(conv(h, s, h->conv_post, cur, ch, Tn, wout_p, Tn, op)); }
+    GSV_RC(conv(h, s, h->conv_post, cur, h->conv_post.cin, Tn, wout_p, Tn, op)); }
   if (seg_f) {
     const int up = Tn / F;
-    hipLaunchKernelGGL(compact_wav_kernel, dim3(nblk(Tn)), dim3(256), 0, s, (const float*)wout_p, seg_f, up, (long long)sr->lay->G * up,
-                       (long long)Tn, wav);
-    GSV_HIP(hipGetLastError());
+    GSV_LAUNCH(compact_wav_kernel, dim3(nblk(Tn)), dim3(256), 0, s, (const float*)wout_p, seg_f, up, (long long)sr->lay->G * up,
+               (long long)Tn, wav);
   }
   GSV_HIP(hipEventRecord(h->ev[2], s));
+  return GSV_OK;
+}
+
+// the v3/v4 semantic path (SynthesizerTrnV3.decode_encp, module/models.py:1234-1262): enc_p -> bridge -> nearest upsampling ->
+// wns1 -> fea [512][F] fp32 channels-first
+template <typename T>
+static int decode_encp(gsv_vits* h, hipStream_t s, const int32_t* codes, int Tc, const int32_t* phones, int L, double speed, float* fea) {
+  const auto& c = h->cfg;
+  const size_t es = sizeof(T);
+  const int H = c.hidden_channels, W = 512;
+  void* y = nullptr;
+  int Fs = 0;
+  GSV_RC(run_enc_p<T>(h, s, codes, Tc, phones, L, speed, &y, &Fs));
+  const double sf = c.flavor == 1 ? 1.875 : 2.0;
+  const int F = (int)floor((double)Fs * sf);
+  // wns1's mask length (models.py:1252-1258): frames >= Lm are zeroed at every masked point of Encoder / WN
+  const double per = c.flavor == 1 ? 3.875 : 4.0;
+  const int sizee = (speed == 1.0) ? (int)((double)Tc * per) : (int)((double)Tc * per / speed) + 1;
+  const int Lm = std::min(sizee, F);
+  void *br, *up, *hb, *xin, *acts, *wout, *st;
+  GSV_RC(need(h, "e_br", (size_t)Fs * W * es, &br));
+  GSV_RC(need(h, "e_up", (size_t)F * W * es, &up));
+  GSV_RC(need(h, "e_h", (size_t)F * W * es, &hb));
+  GSV_RC(need(h, "e_xin", (size_t)F * 2 * W * es, &xin));
+  GSV_RC(need(h, "e_acts", (size_t)F * W * es, &acts));
+  GSV_RC(need(h, "e_out", (size_t)F * W * es, &wout));
+  GSV_RC(need(h, "e_st", (size_t)F * W * es, &st));
+  auto mask_tail = [&](void* p) -> int {
+    if (Lm < F) GSV_HIP(hipMemsetAsync((char*)p + (size_t)Lm * W * es, 0, (size_t)(F - Lm) * W * es, s));
+    return GSV_OK;
+  };
+  { ConvOpt ob; ob.post_act = ACT_LRELU01; GSV_RC(conv(h, s, h->bridge, y, H, Fs, br, Fs, ob)); }   // bridge: 1x1 + LeakyReLU(0.01)
+  GSV_LAUNCH(interp_nearest_kernel<T>, dim3(F), dim3(128), 0, s, (const T*)br, Fs, F, W, (float)(1.0 / sf), (T*)up);
+  ConvOpt o;
+  GSV_RC(conv(h, s, h->w1_pre, up, W, F, hb, F, o));
+  GSV_RC(mask_tail(hb));
+  GSV_RC(run_wn<T>(h, s, h->w1, F, hb, xin, acts, wout, nullptr, 0, Lm));
+  GSV_RC(mask_tail(wout));
+  GSV_RC(conv(h, s, h->w1_proj, wout, W, F, st, F, o));
+  GSV_RC(mask_tail(st));
+  GSV_LAUNCH(cl_to_cf_kernel<T>, dim3(nblk((long long)F * W)), dim3(256), 0, s, (const T*)st, F, W, 0, W, fea);
+  return GSV_OK;
+}
+
+// gsv_vits_extract_latent: top-level ssl_proj (kernel 2, stride 2) -> nearest codeword of the first quantizer layer
+template <typename T>
+static int extract_latent(gsv_vits* h, hipStream_t s, const float* ssl, int T50, int32_t* codes) {
+  const auto& c = h->cfg;
+  const int SSL = c.ssl_dim, T25 = (T50 - 2) / 2 + 1;
+  void* x; float *p, *dots;
+  GSV_RC(need(h, "xl_x", (size_t)T50 * SSL * sizeof(T), &x));
+  GSV_RC(need(h, "xl_p", (size_t)T25 * SSL * 4, (void**)&p));
+  GSV_RC(need(h, "xl_d", (size_t)T25 * c.n_bins * 4, (void**)&dots));
+  GSV_RC(cf_to_cl_t<T>(s, ssl, T50, SSL, x));
+  ConvOpt o; o.stride = 2; o.pad = 0; o.out_f32 = 1;
+  GSV_RC(conv(h, s, h->top_ssl_proj, x, SSL, T50, p, T25, o));
+  // x . E^T in the engine dtype operands (fp32 engine: exact-f32 MFMA)
+  void* pt;
+  GSV_RC(need(h, "xl_pt", (size_t)T25 * SSL * sizeof(T), &pt));
+  GSV_RC(launch_convert(p, pt, h->dtype, (long long)T25 * SSL, s));
+  ConvArgs a;
+  a.x = pt; a.w = h->codebook_t; a.y = dots; a.out_f32 = 1;
+  a.T_in = T25; a.T_out = T25; a.T_virt = T25; a.Cin = SSL; a.Cout = c.n_bins; a.ldx = SSL; a.ldw = SSL; a.ldy = c.n_bins;
+  GSV_RC(launch_conv_gemm(h->dtype, a, s));
+  GSV_LAUNCH(argmax_code_kernel, dim3(T25), dim3(64), 0, s, dots, p, h->code_ee, SSL, c.n_bins, codes);
+  return GSV_OK;
+}
+
+// gsv_vits_debug_tensor: T channels-last [Tn][ld] -> out fp32 channels-first [C][Tn]
+template <typename T>
+static int debug_cl_to_cf(hipStream_t s, const void* src, int Tn, int C, float* out) {
+  GSV_LAUNCH(cl_to_cf_kernel<T>, dim3(nblk((long long)Tn * C)), dim3(256), 0, s, (const T*)src, Tn, C, 0, C, out);
   return GSV_OK;
 }
 }  // namespace gsveng
 
 extern "C" {
 
-int gsv_vits_decode(gsv_vits_t* h, const int32_t* codes, int T, const int32_t* phones, int L, const float* noise,
+int gsv_vits_decode(gsv_vits_t* h, const int32_t* codes, int Tc, const int32_t* phones, int L, const float* noise,
                     float noise_scale, double speed, uint64_t seed, float* wav, gsv_stream_t stream) {
   GSV_REQUIRE(h && h->finalized, "vits_decode: handle not finalized");
   GSV_REQUIRE(h->has_ref, "vits_decode: call gsv_vits_set_refer first");
-  GSV_REQUIRE(codes && phones && wav && T >= 1 && L >= 1, "vits_decode: empty input (T=%d, L=%d)", T, L);
+  GSV_REQUIRE(codes && phones && wav && Tc >= 1 && L >= 1, "vits_decode: empty input (T=%d, L=%d)", Tc, L);
   hipStream_t s = (hipStream_t)stream;
   GSV_REQUIRE(speed > 0.0, "vits_decode: speed must be positive");
   GSV_REQUIRE(h->cfg.flavor == 0, "vits_decode: this handle is a v3/v4 model (use gsv_vits_decode_encp + gsv_cfm_inference + a vocoder)");
   GSV_HIP(hipEventRecord(h->ev[0], s));
-  void* y = nullptr;
-  int F = 0;
-  GSV_RC(run_enc_p(h, s, codes, T, phones, L, speed, &y, &F));
-  return decode_tail(h, s, y, F, noise, noise_scale, seed, wav, nullptr);
+  return GSV_WITH_T(h, decode_wav<T>(h, s, codes, Tc, phones, L, speed, noise, noise_scale, seed, wav, nullptr));
 }
 
 int gsv_vits_segment_gap(const gsv_vits_config* cfg) {
@@ -1332,7 +1293,7 @@ int gsv_vits_decode_segments(gsv_vits_t* h, int n, const int32_t* codes, const i
   GSV_HIP(hipMemcpyAsync(dm, m.data(), total * 4, hipMemcpyHostToDevice, s));
   GSV_HIP(hipMemcpyAsync(dseed, h->seed_host.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
   GSV_HIP(hipEventRecord(h->seg_ev, s));
-  hipLaunchKernelGGL(gather_voice_kernel, dim3(n), dim3(256), 0, s, (const float*)h->voices, (const int*)(dm + o_vs), h->voice_len, vb);
+  GSV_LAUNCH(gather_voice_kernel, dim3(n), dim3(256), 0, s, (const float*)h->voices, (const int*)(dm + o_vs), h->voice_len, vb);
   SegRun sr;
   sr.lay = &lay;
   sr.seg_f = dm + o_sf; sr.seg_l = dm + o_sl; sr.kr_f = dm + o_kf; sr.kr_l = dm + o_kl; sr.kr_x = dm + o_kx;
@@ -1346,15 +1307,11 @@ int gsv_vits_decode_segments(gsv_vits_t* h, int n, const int32_t* codes, const i
     const std::string nm = "seg_up" + std::to_string(i);
     int* su;
     GSV_RC(need(h, nm.c_str(), (size_t)F * up * 4, (void**)&su));
-    hipLaunchKernelGGL(expand_seg_kernel, dim3(nblk((long long)F * up)), dim3(256), 0, s, (const int*)sr.seg_f, (int)up, (long long)F * up, su);
+    GSV_LAUNCH(expand_seg_kernel, dim3(nblk((long long)F * up)), dim3(256), 0, s, (const int*)sr.seg_f, (int)up, (long long)F * up, su);
     sr.seg_up.push_back(su);
   }
-  GSV_HIP(hipGetLastError());
   GSV_HIP(hipEventRecord(h->ev[0], s));
-  void* y = nullptr;
-  int Fy = 0;
-  GSV_RC(run_enc_p(h, s, codes, 0, phones, L, 1.0, &y, &Fy, &sr));
-  return decode_tail(h, s, y, F, noise, noise_scale, seeds[0], wav, &sr);
+  return GSV_WITH_T(h, decode_wav<T>(h, s, codes, 0, phones, L, 1.0, noise, noise_scale, seeds[0], wav, &sr));
 }
 
 int gsv_vits_encp_frames(gsv_vits_t* h, int T, double speed) {
@@ -1365,70 +1322,14 @@ int gsv_vits_encp_frames(gsv_vits_t* h, int T, double speed) {
   return (int)floor((double)Fs * sf);
 }
 
-int gsv_vits_decode_encp(gsv_vits_t* h, const int32_t* codes, int T, const int32_t* phones, int L, double speed, float* fea,
+int gsv_vits_decode_encp(gsv_vits_t* h, const int32_t* codes, int Tc, const int32_t* phones, int L, double speed, float* fea,
                          gsv_stream_t stream) {
   GSV_REQUIRE(h && h->finalized, "vits_decode_encp: handle not finalized");
   GSV_REQUIRE(h->cfg.flavor != 0, "vits_decode_encp: this handle is a v1/v2 model (use gsv_vits_decode)");
   GSV_REQUIRE(h->has_ref, "vits_decode_encp: call gsv_vits_set_refer first");
-  GSV_REQUIRE(codes && phones && fea && T >= 1 && L >= 1, "vits_decode_encp: empty input (T=%d, L=%d)", T, L);
+  GSV_REQUIRE(codes && phones && fea && Tc >= 1 && L >= 1, "vits_decode_encp: empty input (T=%d, L=%d)", Tc, L);
   GSV_REQUIRE(speed > 0.0, "vits_decode_encp: speed must be positive");
-  hipStream_t s = (hipStream_t)stream;
-  const auto& c = h->cfg;
-  const size_t es = esz(h);
-  const int H = c.hidden_channels, W = 512, NL = (int)h->w1_in.size();
-  void* y = nullptr;
-  int Fs = 0;
-  GSV_RC(run_enc_p(h, s, codes, T, phones, L, speed, &y, &Fs));
-  const double sf = c.flavor == 1 ? 1.875 : 2.0;
-  const int F = (int)floor((double)Fs * sf);
-  // wns1's mask length (models.py:1252-1258): frames >= Lm are zeroed at every masked point of Encoder / WN
-  const double per = c.flavor == 1 ? 3.875 : 4.0;
-  const int sizee = (speed == 1.0) ? (int)((double)T * per) : (int)((double)T * per / speed) + 1;
-  const int Lm = std::min(sizee, F);
-  void *br, *up, *hb, *xin, *acts, *wout, *st;
-  GSV_RC(need(h, "e_br", (size_t)Fs * W * es, &br));
-  GSV_RC(need(h, "e_up", (size_t)F * W * es, &up));
-  GSV_RC(need(h, "e_h", (size_t)F * W * es, &hb));
-  GSV_RC(need(h, "e_xin", (size_t)F * 2 * W * es, &xin));
-  GSV_RC(need(h, "e_acts", (size_t)F * W * es, &acts));
-  GSV_RC(need(h, "e_out", (size_t)F * W * es, &wout));
-  GSV_RC(need(h, "e_st", (size_t)F * W * es, &st));
-  auto mask_tail = [&](void* p) -> int {
-    if (Lm < F) GSV_HIP(hipMemsetAsync((char*)p + (size_t)Lm * W * es, 0, (size_t)(F - Lm) * W * es, s));
-    return GSV_OK;
-  };
-  { ConvOpt ob; ob.post_act = ACT_LRELU01; GSV_RC(conv(h, s, h->bridge, y, H, Fs, br, Fs, ob)); }   // bridge: 1x1 + LeakyReLU(0.01)
-  GSV_DISPATCH(h,
-    hipLaunchKernelGGL(interp_nearest_kernel<_Float16>, dim3(F), dim3(128), 0, s, (const _Float16*)br, Fs, F, W, (float)(1.0 / sf), (_Float16*)up),
-    hipLaunchKernelGGL(interp_nearest_kernel<float>, dim3(F), dim3(128), 0, s, (const float*)br, Fs, F, W, (float)(1.0 / sf), (float*)up));
-  ConvOpt o;
-  GSV_RC(conv(h, s, h->w1_pre, up, W, F, hb, F, o));
-  GSV_RC(mask_tail(hb));
-  for (int li = 0; li < NL; ++li) {                        // modules.WN.forward (modules.py:  in -> gate -> res/skip)
-    ConvOpt oi; oi.bias_override = h->w1_in_bias_eff[li];
-    GSV_RC(conv(h, s, h->w1_in[li], hb, W, F, xin, F, oi));
-    GSV_DISPATCH(h,
-      hipLaunchKernelGGL(gate_kernel<_Float16>, dim3(nblk((long long)F * W)), dim3(256), 0, s, (const _Float16*)xin, (long long)F * W, W, (_Float16*)acts),
-      hipLaunchKernelGGL(gate_kernel<float>, dim3(nblk((long long)F * W)), dim3(256), 0, s, (const float*)xin, (long long)F * W, W, (float*)acts));
-    if (li < NL - 1) {
-      ConvOpt ores; ores.cout = W; ores.w_row0 = 0; ores.accumulate = 1;
-      GSV_RC(conv(h, s, h->w1_res[li], acts, W, F, hb, F, ores));
-      GSV_RC(mask_tail(hb));
-      ConvOpt osk; osk.cout = W; osk.w_row0 = W; osk.accumulate = li > 0;
-      GSV_RC(conv(h, s, h->w1_res[li], acts, W, F, wout, F, osk));
-    } else {
-      ConvOpt osk; osk.accumulate = NL > 1;
-      GSV_RC(conv(h, s, h->w1_res[li], acts, W, F, wout, F, osk));
-    }
-  }
-  GSV_RC(mask_tail(wout));
-  GSV_RC(conv(h, s, h->w1_proj, wout, W, F, st, F, o));
-  GSV_RC(mask_tail(st));
-  GSV_DISPATCH(h,
-    hipLaunchKernelGGL(cl_to_cf_kernel<_Float16>, dim3(nblk((long long)F * W)), dim3(256), 0, s, (const _Float16*)st, F, W, 0, W, fea),
-    hipLaunchKernelGGL(cl_to_cf_kernel<float>, dim3(nblk((long long)F * W)), dim3(256), 0, s, (const float*)st, F, W, 0, W, fea));
-  GSV_HIP(hipGetLastError());
-  return GSV_OK;
+  return GSV_WITH_T(h, decode_encp<T>(h, (hipStream_t)stream, codes, Tc, phones, L, speed, fea));
 }
 
 int gsv_vits_last_timing(gsv_vits_t* h, float* total_ms, float* generator_ms) {
@@ -1445,29 +1346,7 @@ int gsv_vits_last_timing(gsv_vits_t* h, float* total_ms, float* generator_ms) {
 int gsv_vits_extract_latent(gsv_vits_t* h, const float* ssl, int T50, int32_t* codes, gsv_stream_t stream) {
   GSV_REQUIRE(h && h->finalized && ssl && codes, "vits_extract_latent: bad argument");
   GSV_REQUIRE(T50 >= 2, "vits_extract_latent: need at least 2 ssl frames (got %d)", T50);
-  hipStream_t s = (hipStream_t)stream;
-  const auto& c = h->cfg;
-  const int SSL = c.ssl_dim, T25 = (T50 - 2) / 2 + 1;
-  void* x; float *p, *dots;
-  GSV_RC(need(h, "xl_x", (size_t)T50 * SSL * esz(h), &x));
-  GSV_RC(need(h, "xl_p", (size_t)T25 * SSL * 4, (void**)&p));
-  GSV_RC(need(h, "xl_d", (size_t)T25 * c.n_bins * 4, (void**)&dots));
-  GSV_DISPATCH(h,
-    hipLaunchKernelGGL(cf_to_cl_kernel<_Float16>, dim3(cdiv(T50, 32), cdiv(SSL, 32)), dim3(256), 0, s, ssl, T50, SSL, (_Float16*)x),
-    hipLaunchKernelGGL(cf_to_cl_kernel<float>, dim3(cdiv(T50, 32), cdiv(SSL, 32)), dim3(256), 0, s, ssl, T50, SSL, (float*)x));
-  ConvOpt o; o.stride = 2; o.pad = 0; o.out_f32 = 1;
-  GSV_RC(conv(h, s, h->top_ssl_proj, x, SSL, T50, p, T25, o));
-  // x . E^T in the engine dtype operands (fp32 engine: exact-f32 MFMA)
-  void* pt;
-  GSV_RC(need(h, "xl_pt", (size_t)T25 * SSL * esz(h), &pt));
-  GSV_RC(launch_convert(p, pt, h->dtype, (long long)T25 * SSL, s));
-  ConvArgs a;
-  a.x = pt; a.w = h->codebook_t; a.y = dots; a.out_f32 = 1;
-  a.T_in = T25; a.T_out = T25; a.T_virt = T25; a.Cin = SSL; a.Cout = c.n_bins; a.ldx = SSL; a.ldw = SSL; a.ldy = c.n_bins;
-  GSV_RC(launch_conv_gemm(h->dtype, a, s));
-  hipLaunchKernelGGL(argmax_code_kernel, dim3(T25), dim3(64), 0, s, dots, p, h->code_ee, SSL, c.n_bins, codes);
-  GSV_HIP(hipGetLastError());
-  return GSV_OK;
+  return GSV_WITH_T(h, extract_latent<T>(h, (hipStream_t)stream, ssl, T50, codes));
 }
 
 int gsv_vits_debug_tensor(gsv_vits_t* h, const char* name, float* out, int64_t cap, int64_t* numel, gsv_stream_t stream) {
@@ -1487,264 +1366,18 @@ int gsv_vits_debug_tensor(gsv_vits_t* h, const char* name, float* out, int64_t c
     const long long ne = (long long)h->dbg_last_T * h->dbg_last_C;
     GSV_REQUIRE(h->dbg_last_in && cap >= ne, "vits_debug_tensor: buffer too small");
     *numel = ne;
-    GSV_DISPATCH(h,
-      hipLaunchKernelGGL(cl_to_cf_kernel<_Float16>, dim3(nblk(ne)), dim3(256), 0, s, (const _Float16*)h->dbg_last_in, h->dbg_last_T, h->dbg_last_C, 0, h->dbg_last_C, out),
-      hipLaunchKernelGGL(cl_to_cf_kernel<float>, dim3(nblk(ne)), dim3(256), 0, s, (const float*)h->dbg_last_in, h->dbg_last_T, h->dbg_last_C, 0, h->dbg_last_C, out));
-    GSV_HIP(hipGetLastError());
-    return GSV_OK;
+    return GSV_WITH_T(h, debug_cl_to_cf<T>(s, h->dbg_last_in, h->dbg_last_T, h->dbg_last_C, out));
   }
   GSV_REQUIRE(cap >= (int64_t)F * IC, "vits_debug_tensor: buffer too small");
   *numel = (int64_t)F * IC;
   if (n == "m_p" || n == "logs_p") {
     const float* st = (const float*)h->bufs["stats"].p;
-    hipLaunchKernelGGL(cl_to_cf_kernel<float>, dim3(nblk((long long)F * IC)), dim3(256), 0, s, st, F, 2 * IC, n == "m_p" ? 0 : IC, IC, out);
-  } else if (n == "z") {
-    const void* z = h->bufs["z_keep"].p;
-    GSV_DISPATCH(h,
-      hipLaunchKernelGGL(cl_to_cf_kernel<_Float16>, dim3(nblk((long long)F * IC)), dim3(256), 0, s, (const _Float16*)z, F, IC, 0, IC, out),
-      hipLaunchKernelGGL(cl_to_cf_kernel<float>, dim3(nblk((long long)F * IC)), dim3(256), 0, s, (const float*)z, F, IC, 0, IC, out));
-  } else {
-    set_error("vits_debug_tensor: unknown tensor '%s' (ge, m_p, logs_p, z, gen_last_in)", name);
-    return GSV_ERR_ARG;
-  }
-  GSV_HIP(hipGetLastError());
-  return GSV_OK;
-}
-
-}  // extern "C"
-
-// =======================================================================================
-// Vocoders of the v3/v4 path: v4 = the HiFi-GAN `Generator` used as a mel vocoder (H16, reference
-// TTS_infer_pack/TTS.py:631-648, module/models.py:407-471), v3 = BigVGAN-v2 (H15, reference
-// BigVGAN/bigvgan.py:226-355 with AMPBlock1 :31-131 and anti-aliased SnakeBeta).  Same conv kernels
-// and channels-last layout as the v2 generator above; mel channels are zero-padded to a multiple of 8.
-// =======================================================================================
-struct VocAct { float *alpha = nullptr, *beta = nullptr; };
-
-struct gsv_vocoder {
-  gsv_vits ctx;               // reused as the allocation / staging / workspace context of the helpers above
-  gsv_vocoder_config cfg;
-  int cin_pad = 0;
-  Conv conv_pre, conv_post;
-  std::vector<Conv> ups, rb1, rb2;
-  std::vector<VocAct> acts;   // BigVGAN: [stage][block][6] + final
-  float *up12 = nullptr, *dn12 = nullptr;
-  bool finalized = false;
-};
-
-namespace gsveng {
-
-// Conv1d weight [cout][cin][k] with the input channels zero-padded to cin_pad
-int make_conv_padded(gsv_vits* h, const std::string& name, int cout, int cin, int cin_pad, int k, bool bias, Conv* c) {
-  std::vector<float> w, b;
-  if (!fetch(h, name + ".weight", (size_t)cout * cin * k, cout, w)) return GSV_ERR_ARG;
-  std::vector<float> p((size_t)cout * k * cin_pad, 0.f);
-  for (int o = 0; o < cout; ++o)
-    for (int i = 0; i < cin; ++i)
-      for (int j = 0; j < k; ++j) p[((size_t)o * k + j) * cin_pad + i] = w[((size_t)o * cin + i) * k + j];
-  GSV_RC(up_t(h, p, &c->w));
-  if (bias) {
-    if (!fetch(h, name + ".bias", cout, cout, b)) return GSV_ERR_ARG;
-    GSV_RC(up_f32(h, b.data(), b.size(), &c->b));
-  }
-  c->cin = cin_pad; c->cout = cout; c->taps = k;
-  return GSV_OK;
-}
-
-// Kaiser-windowed sinc low-pass of BigVGAN's Activation1d (filter.py:30-60), cutoff 0.25, half-width 0.3, 12 taps
-void kaiser_sinc12(float* out) {
-  const int K = 12, half = 6;
-  const double cutoff = 0.25, hw = 0.3;
-  const double A = 2.285 * (half - 1) * M_PI * 4 * hw + 7.95;
-  const double beta = A > 50.0 ? 0.1102 * (A - 8.7) : (A >= 21.0 ? 0.5842 * pow(A - 21.0, 0.4) + 0.07886 * (A - 21.0) : 0.0);
-  auto i0 = [](double x) { double s = 1.0, t = 1.0; for (int k = 1; k < 60; ++k) { t *= (x / (2.0 * k)) * (x / (2.0 * k)); s += t; } return s; };
-  double f[12], sum = 0.0;
-  for (int n = 0; n < K; ++n) {
-    const double r = 2.0 * n / (K - 1) - 1.0;
-    const double win = i0(beta * sqrt(1.0 - r * r)) / i0(beta);
-    const double t = (n - half) + 0.5;
-    const double xx = 2 * cutoff * t;
-    const double sinc = xx == 0.0 ? 1.0 : sin(M_PI * xx) / (M_PI * xx);
-    f[n] = 2 * cutoff * win * sinc;
-    sum += f[n];
-  }
-  for (int n = 0; n < K; ++n) out[n] = (float)(f[n] / sum);
-}
-
-int voc_act(gsv_vocoder* v, hipStream_t s, const VocAct& a, const void* x, void* y, int Tn, int C) {
-  gsv_vits* h = &v->ctx;
-  dim3 grid(cdiv(Tn, 64), cdiv(C, 64));
-  GSV_DISPATCH(h,
-    hipLaunchKernelGGL(aa_act_cl_kernel<_Float16>, grid, dim3(256), 0, s, (const _Float16*)x, (_Float16*)y, Tn, C, C, a.alpha, a.beta,
-                       v->cfg.snake_logscale, v->up12, v->dn12),
-    hipLaunchKernelGGL(aa_act_cl_kernel<float>, grid, dim3(256), 0, s, (const float*)x, (float*)y, Tn, C, C, a.alpha, a.beta,
-                       v->cfg.snake_logscale, v->up12, v->dn12));
-  GSV_HIP(hipGetLastError());
-  return GSV_OK;
-}
-
-}  // namespace gsveng
-
-extern "C" {
-
-int gsv_vocoder_create(const gsv_vocoder_config* cfg, int dtype, gsv_vocoder_t** out) {
-  GSV_REQUIRE(cfg && out, "vocoder_create: null argument");
-  GSV_REQUIRE(dtype == GSV_F16 || dtype == GSV_F32, "vocoder_create: bad dtype");
-  GSV_REQUIRE(cfg->n_ups >= 1 && cfg->n_ups <= 8 && cfg->n_resblocks >= 1 && cfg->n_resblocks <= 4, "vocoder_create: bad shape");
-  GSV_REQUIRE(cfg->kind == 0 || cfg->kind == 1, "vocoder_create: kind must be 0 (HiFi-GAN) or 1 (BigVGAN)");
-  GSV_REQUIRE((cfg->upsample_initial_channel >> cfg->n_ups) % 8 == 0, "vocoder_create: final channel count must be a multiple of 8");
-  int n = 0;
-  GSV_HIP(hipGetDeviceCount(&n));
-  gsv_vocoder* v = new gsv_vocoder();
-  v->cfg = *cfg;
-  v->ctx.dtype = dtype;
-  v->cin_pad = (cfg->in_channels + 7) / 8 * 8;
-  *out = v;
-  return GSV_OK;
-}
-
-void gsv_vocoder_destroy(gsv_vocoder_t* v) {
-  if (!v) return;
-  for (void* p : v->ctx.allocs) (void)hipFree(p);
-  for (auto& b : v->ctx.bufs) if (b.second.p) (void)hipFree(b.second.p);
-  delete v;
-}
-
-int gsv_vocoder_load_tensor(gsv_vocoder_t* v, const char* name, const float* data, int64_t numel) {
-  GSV_REQUIRE(v && name && data && numel > 0, "vocoder_load_tensor: bad argument");
-  GSV_REQUIRE(!v->finalized, "vocoder_load_tensor: handle already finalized");
-  v->ctx.staged[name].assign(data, data + numel);
-  return GSV_OK;
-}
-
-int gsv_vocoder_finalize(gsv_vocoder_t* v) {
-  GSV_REQUIRE(v && !v->finalized, "vocoder_finalize: bad handle");
-  gsv_vits* h = &v->ctx;
-  const auto& c = v->cfg;
-  const int UIC = c.upsample_initial_channel;
-  const bool big = c.kind == 1;
-  GSV_RC(make_conv_padded(h, "conv_pre", UIC, c.in_channels, v->cin_pad, 7, true, &v->conv_pre));
-  v->ups.resize(c.n_ups);
-  int ch = UIC;
-  auto load_act = [&](const std::string& prefix, int C, VocAct* a) -> int {
-    GSV_RC(make_vec(h, prefix + ".alpha", C, &a->alpha));
-    if (h->staged.count(prefix + ".beta")) { GSV_RC(make_vec(h, prefix + ".beta", C, &a->beta)); }
-    else a->beta = a->alpha;   // Snake: one parameter for both (activation1d.py:58-61)
+    GSV_LAUNCH(cl_to_cf_kernel<float>, dim3(nblk((long long)F * IC)), dim3(256), 0, s, st, F, 2 * IC, n == "m_p" ? 0 : IC, IC, out);
     return GSV_OK;
-  };
-  for (int i = 0; i < c.n_ups; ++i) {
-    const int cin = UIC >> i, cout = UIC >> (i + 1);
-    const std::string un = big ? "ups." + std::to_string(i) + ".0" : "ups." + std::to_string(i);
-    GSV_RC(make_ups(h, un, cin, cout, c.up_kernels[i], c.up_rates[i], &v->ups[i]));
-    ch = cout;
-    for (int j = 0; j < c.n_resblocks; ++j) {
-      const std::string r = "resblocks." + std::to_string(i * c.n_resblocks + j);
-      for (int k = 0; k < 3; ++k) {
-        Conv c1, c2;
-        GSV_RC(make_conv(h, r + ".convs1." + std::to_string(k), ch, ch, c.rb_kernels[j], true, &c1));
-        GSV_RC(make_conv(h, r + ".convs2." + std::to_string(k), ch, ch, c.rb_kernels[j], true, &c2));
-        v->rb1.push_back(c1);
-        v->rb2.push_back(c2);
-      }
-      if (big)
-        for (int k = 0; k < 6; ++k) {
-          VocAct a;
-          GSV_RC(load_act(r + ".activations." + std::to_string(k) + ".act", ch, &a));
-          v->acts.push_back(a);
-        }
-    }
   }
-  if (big) {
-    VocAct a;
-    GSV_RC(load_act("activation_post.act", ch, &a));
-    v->acts.push_back(a);
-    float f[12];
-    kaiser_sinc12(f);
-    GSV_RC(up_f32(h, f, 12, &v->up12));
-    GSV_RC(up_f32(h, f, 12, &v->dn12));
-  }
-  GSV_RC(make_conv(h, "conv_post", 1, ch, 7, c.bias_at_final != 0, &v->conv_post));
-  h->staged.clear();
-  h->finalized = true;
-  v->finalized = true;
-  return GSV_OK;
-}
-
-int gsv_vocoder_forward(gsv_vocoder_t* v, const float* mel, int F, float* wav, gsv_stream_t stream) {
-  GSV_REQUIRE(v && v->finalized, "vocoder_forward: handle not finalized");
-  GSV_REQUIRE(mel && wav && F >= 1, "vocoder_forward: empty input");
-  hipStream_t s = (hipStream_t)stream;
-  gsv_vits* h = &v->ctx;
-  const auto& c = v->cfg;
-  const size_t es = esz(h);
-  const bool big = c.kind == 1;
-  const int UIC = c.upsample_initial_channel;
-  size_t maxel = (size_t)F * UIC;
-  {
-    long long Tn = F; int ch = UIC;
-    for (int i = 0; i < c.n_ups; ++i) { Tn *= c.up_rates[i]; ch >>= 1; maxel = std::max(maxel, (size_t)Tn * ch); }
-  }
-  void* xin;
-  GSV_RC(need(h, "voc_in", (size_t)F * v->cin_pad * es, &xin));
-  GSV_HIP(hipMemsetAsync(xin, 0, (size_t)F * v->cin_pad * es, s));
-  GSV_DISPATCH(h,
-    hipLaunchKernelGGL(cf_to_cl_kernel<_Float16>, dim3(cdiv(F, 32), cdiv(c.in_channels, 32)), dim3(256), 0, s, mel, F, c.in_channels, (_Float16*)xin, v->cin_pad),
-    hipLaunchKernelGGL(cf_to_cl_kernel<float>, dim3(cdiv(F, 32), cdiv(c.in_channels, 32)), dim3(256), 0, s, mel, F, c.in_channels, (float*)xin, v->cin_pad));
-  void* gb[6];
-  const char* gnames[6] = {"v0", "v1", "v2", "v3", "v4", "v5"};
-  for (int i = 0; i < 6; ++i) GSV_RC(need(h, gnames[i], maxel * es, &gb[i]));
-  void* cur = gb[3];
-  { ConvOpt o; GSV_RC(conv(h, s, v->conv_pre, xin, v->cin_pad, F, cur, F, o)); }
-  int Tn = F, ch = UIC, ai = 0;
-  for (int i = 0; i < c.n_ups; ++i) {
-    const int Tout = Tn * c.up_rates[i];
-    ch >>= 1;
-    void* xup = gb[0]; void* xt = gb[1]; void* R = gb[2]; void* xa = gb[5]; void* xs = (cur == gb[3]) ? gb[4] : gb[3];
-    { ConvOpt ou; if (!big) { ou.pre_act = ACT_LRELU; ou.pre_slope = 0.1f; }
-      GSV_RC(conv(h, s, v->ups[i], cur, ch * 2, Tn, xup, Tout, ou)); }
-    for (int j = 0; j < c.n_resblocks; ++j) {
-      const void* xr = xup;
-      for (int k = 0; k < 3; ++k) {
-        const Conv& c1 = v->rb1[(i * c.n_resblocks + j) * 3 + k];
-        const Conv& c2 = v->rb2[(i * c.n_resblocks + j) * 3 + k];
-        if (!big && c1.b && c2.b && c1.taps == c2.taps && conv_pair_eligible(h->dtype, ch, c1.taps, c.rb_dilations[j][k], Tout)) {
-          ConvPairArgs pa;                                // narrow stages of the v4 HiFi-GAN vocoder: same fused pair as gsv_vits_decode
-          pa.x = (const _Float16*)xr; pa.w1 = (const _Float16*)c1.w; pa.b1 = c1.b; pa.w2 = (const _Float16*)c2.w; pa.b2 = c2.b;
-          pa.T = Tout; pa.C = ch; pa.taps = c1.taps; pa.dil = c.rb_dilations[j][k]; pa.ldx = ch; pa.ldy = ch;
-          if (k < 2) { pa.y = (_Float16*)R; }
-          else { pa.y = (_Float16*)xs; pa.scale = 1.f / (float)c.n_resblocks; pa.accumulate = j > 0; }
-          if ((const void*)pa.y == xr) { pa.y = (_Float16*)xt; }
-          GSV_RC(launch_conv_pair(pa, s));
-          if (k < 2) { if (pa.y == (_Float16*)xt) { std::swap(xt, R); } xr = R; }
-          continue;
-        }
-        ConvOpt o1; o1.dil = c.rb_dilations[j][k];
-        ConvOpt o2; o2.res = xr; o2.ldr = ch;
-        const void* in1 = xr;
-        if (big) { GSV_RC(voc_act(v, s, v->acts[ai + 2 * k], xr, xa, Tout, ch)); in1 = xa; }
-        else { o1.pre_act = ACT_LRELU; o1.pre_slope = 0.1f; o2.pre_act = ACT_LRELU; o2.pre_slope = 0.1f; }
-        GSV_RC(conv(h, s, c1, in1, ch, Tout, xt, Tout, o1));
-        const void* in2 = xt;
-        if (big) { GSV_RC(voc_act(v, s, v->acts[ai + 2 * k + 1], xt, xa, Tout, ch)); in2 = xa; }
-        if (k < 2) {
-          GSV_RC(conv(h, s, c2, in2, ch, Tout, R, Tout, o2));
-          xr = R;
-        } else {
-          o2.scale = 1.f / (float)c.n_resblocks; o2.accumulate = j > 0;
-          GSV_RC(conv(h, s, c2, in2, ch, Tout, xs, Tout, o2));
-        }
-      }
-      if (big) ai += 6;
-    }
-    cur = xs; Tn = Tout;
-  }
-  ConvOpt op; op.out_f32 = 1;
-  const void* pin = cur;
-  if (big) { GSV_RC(voc_act(v, s, v->acts[ai], cur, gb[5], Tn, ch)); pin = gb[5]; }
-  else { op.pre_act = ACT_LRELU; op.pre_slope = 0.01f; }
-  op.post_act = c.tanh_at_final ? ACT_TANH : ACT_CLAMP1;
-  GSV_RC(conv(h, s, v->conv_post, pin, ch, Tn, wav, Tn, op));
-  return GSV_OK;
+  if (n == "z") return GSV_WITH_T(h, debug_cl_to_cf<T>(s, h->bufs["z_keep"].p, F, IC, out));
+  set_error("vits_debug_tensor: unknown tensor '%s' (ge, m_p, logs_p, z, gen_last_in)", name);
+  return GSV_ERR_ARG;
 }
 
 }  // extern "C"

@@ -44,6 +44,24 @@ void set_error(const char* fmt, ...);
     if (_rc) return _rc;     \
   } while (0)
 
+// Host code that launches typed kernels is a template on the element type T; an entry point picks T once, from its handle or
+// from a dtype argument:
+//   return GSV_WITH_T(h, decode<T>(h, ...));
+#define GSV_WITH_DTYPE(dt, call)                                         \
+  [&]() -> int {                                                         \
+    if ((dt) == GSV_F16) { using T = _Float16; return call; }            \
+    using T = float;                                                     \
+    return call;                                                         \
+  }()
+#define GSV_WITH_T(h, call) GSV_WITH_DTYPE((h)->dtype, call)
+
+// every kernel launch of the engine files: the launch and its error check, the argument list written once
+#define GSV_LAUNCH(kern, grid, block, shmem, s, ...)                    \
+  do {                                                                   \
+    hipLaunchKernelGGL(kern, grid, block, shmem, s, __VA_ARGS__);        \
+    GSV_HIP(hipGetLastError());                                          \
+  } while (0)
+
 template <typename T> struct DT;
 template <> struct DT<float> { static constexpr int id = GSV_F32; static constexpr int G = 4; };
 template <> struct DT<_Float16> { static constexpr int id = GSV_F16; static constexpr int G = 8; };

@@ -98,22 +98,6 @@ struct ConvOpt {
   const int* row_seg = nullptr;   // segmented decode: gap rows of the output stored as 0 (ConvArgs::row_seg)
 };
 
-// Host code that launches typed kernels is a template on the element type T; an entry point picks T from the handle once:
-//   return GSV_WITH_T(h, decode<T>(h, ...));
-#define GSV_WITH_T(h, call)                                              \
-  [&]() -> int {                                                         \
-    if ((h)->dtype == GSV_F16) { using T = _Float16; return call; }      \
-    using T = float;                                                     \
-    return call;                                                         \
-  }()
-
-// every kernel launch of the engine files: the launch and its error check, the argument list written once
-#define GSV_LAUNCH(kern, grid, block, shmem, s, ...)                    \
-  do {                                                                   \
-    hipLaunchKernelGGL(kern, grid, block, shmem, s, __VA_ARGS__);        \
-    GSV_HIP(hipGetLastError());                                          \
-  } while (0)
-
 namespace gsveng {
 
 inline int nblk(long long n, int b = 256) { return (int)((n + b - 1) / b); }

@@ -1,26 +1,27 @@
-// AR semantic-token decoder engine (H1-H5) for gfx950.
+// AR semantic-token decoder engine (H1-H5) for gfx950: load / finalize, decode, and the debug / timing hooks.  The engine
+// state (gsv_t2s) is in t2s_engine.h, the prefill in t2s_prefill.hip, the persistent decode engine in t2s_mega.hip.
 //
 // State lives in HBM behind an opaque handle: weights in the engine dtype, a head-major KV
 // arena [layer][k|v][row][head][pos][head_dim] (so one (row, head) stream is contiguous and a
 // wave reads it as 1 KiB wave-instructions), per-row lengths/flags, and the token history.
 // The reference re-concatenates the cache every step (t2s_model.py:186-187) and
 // index_selects finished rows away on the host (:727-745); here rows are appended in place and
-// finished rows are flagged on the device, so a decode step has no host synchronisation and
-// is replayed as one hipGraph.
+// finished rows are flagged on the device, so a decode step has no host synchronisation.
 //
-// Decode step = per layer 5 kernels (QKV+append, attention, out-proj, FFN1, FFN2), LayerNorm
-// fused into the consumer's prologue, split-K across the waves of a workgroup with an LDS
-// combine (no global partials), then logits + a one-wave-per-row sampling kernel.
+// gsv_t2s_decode samples step 0 from the prefill's last position and then has two ways through the remaining steps:
+//  * the persistent engine (fp16, v1/v2 shape, B <= 128): ONE launch of t2s_mega.hip's kernel runs every step; a hand-off
+//    timeout restores the row state and the batch continues on the other path;
+//  * the launch-per-phase step (fp32, other shapes, gsv_t2s_set_mega(0), GSV_T2S_NO_MEGA=1, fallback): per layer 4 GEMM
+//    launches (QKV+append, out-proj, FFN1, FFN2) and one attention launch, LayerNorm fused into the consumer's prologue,
+//    split-K across the waves of a workgroup with an LDS combine (no global partials), then logits + a one-wave-per-row
+//    sampling kernel; the step is captured once per batch size and replayed as one hipGraph.
 #include <math.h>
 #include <stdlib.h>
 #include <algorithm>
-#include <map>
 #include <string>
 #include <vector>
 
-#include "common.h"
-#include "t2s_sample.h"
-#include "t2s_mega.h"
+#include "t2s_engine.h"
 
 namespace gsv {
 
@@ -30,276 +31,6 @@ typedef float f4v __attribute__((ext_vector_type(4)));
 // kernels
 // =======================================================================================
 
-// x[row] = E_text[id] + bert_proj(bert)[row] + alpha_t * pe[pos]     (H2; t2s_model.py:612-617)
-// or       E_audio[tok] + alpha_a * pe[pos]                            (t2s_model.py:636-640)
-// rows are packed per utterance: [x_0 .. x_{X-1}, y_0 .. y_{P_b-1}]; row b's prompt is prompts[poff[b] .. + P_b)
-template <typename T>
-__global__ void embed_prefill_kernel(const int* __restrict__ phones, const int* __restrict__ prompts,
-                                     const int* __restrict__ row_off, const int* __restrict__ ph_off,
-                                     const int* __restrict__ x_len, const float* __restrict__ e_text,
-                                     const float* __restrict__ e_audio, const float* __restrict__ bertp,  // [sumX][d] or null
-                                     const float* __restrict__ bert_bias, const float* __restrict__ pe, float alpha_t,
-                                     float alpha_a, const int* __restrict__ plen, const int* __restrict__ poff, int d,
-                                     T* __restrict__ x) {
-  const int b = blockIdx.y;
-  const int i = blockIdx.x;  // position within the row's sequence
-  const int X = x_len[b], P = plen[b];
-  if (i >= X + P) return;
-  T* out = x + (long long)(row_off[b] + i) * d;
-  if (i < X) {
-    const int id = phones[ph_off[b] + i];
-    const float* e = e_text + (long long)id * d;
-    const float* bp = bertp ? bertp + (long long)(ph_off[b] + i) * d : nullptr;
-    for (int c = threadIdx.x; c < d; c += blockDim.x) {
-      float v = e[c] + (bp ? bp[c] : bert_bias[c]);
-      out[c] = (T)(v + alpha_t * pe[(long long)i * d + c]);
-    }
-  } else {
-    const int tok = prompts[poff[b] + (i - X)];
-    const float* e = e_audio + (long long)tok * d;
-    for (int c = threadIdx.x; c < d; c += blockDim.x) out[c] = (T)(e[c] + alpha_a * pe[(long long)(i - X) * d + c]);
-  }
-}
-
-// scatter the prefill K/V (columns d..3d of qkv) into the head-major cache
-template <typename T>
-__global__ void kv_scatter_kernel(const T* __restrict__ qkv, const int* __restrict__ row_off, const int* __restrict__ x_len,
-                                  const int* __restrict__ plen, int d, int H, int smax, T* __restrict__ kc, T* __restrict__ vc) {
-  const int b = blockIdx.y, i = blockIdx.x;
-  if (i >= x_len[b] + plen[b]) return;
-  const int hd = d / H;
-  const T* src = qkv + (long long)(row_off[b] + i) * 3 * d;
-  for (int c = threadIdx.x; c < d; c += blockDim.x) {
-    const int h = c / hd, e = c - h * hd;
-    const long long o = (((long long)b * H + h) * smax + i) * hd + e;
-    kc[o] = src[d + c];
-    vc[o] = src[2 * d + c];
-  }
-}
-
-// Prefill attention (H3): one thread per query, keys streamed with a block-uniform address.
-// Mask (t2s_model.py:655-683): text rows see the text keys; audio rows see all text + causal audio.
-template <typename T, int HD>
-__global__ void prefill_attn_kernel(const T* __restrict__ qkv, const T* __restrict__ kc, const T* __restrict__ vc,
-                                    const int* __restrict__ row_off, const int* __restrict__ x_len, const int* __restrict__ plen,
-                                    int d, int H, int smax, T* __restrict__ out) {
-  const int b = blockIdx.z, h = blockIdx.y;
-  const int X = x_len[b], S = X + plen[b];
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int q0 = blockIdx.x * blockDim.x;
-  if (q0 >= S) return;
-  const bool valid = i < S;
-  const int nk = valid ? (i < X ? X : i + 1) : 0;
-  // block-uniform upper bound of the key loop
-  const int qlast = min(q0 + (int)blockDim.x, S) - 1;
-  const int nk_max = (qlast < X) ? X : qlast + 1;
-  float q[HD], acc[HD];
-  const T* qp = qkv + (long long)(row_off[b] + (valid ? i : 0)) * 3 * d + h * HD;
-  const float scale = rsqrtf((float)HD);
-#pragma unroll
-  for (int e = 0; e < HD; ++e) { q[e] = to_f(qp[e]) * scale; acc[e] = 0.f; }
-  float m = -INFINITY, l = 0.f;
-  const T* kb = kc + ((long long)b * H + h) * smax * HD;
-  const T* vb = vc + ((long long)b * H + h) * smax * HD;
-  for (int j = 0; j < nk_max; ++j) {
-    const T* kr = kb + (long long)j * HD;
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < HD; ++e) s += q[e] * to_f(kr[e]);
-    if (j < nk) {
-      const float mn = fmaxf(m, s);
-      const float corr = expf(m - mn);
-      const float p = expf(s - mn);
-      const T* vr = vb + (long long)j * HD;
-      l = l * corr + p;
-#pragma unroll
-      for (int e = 0; e < HD; ++e) acc[e] = acc[e] * corr + p * to_f(vr[e]);
-      m = mn;
-    }
-  }
-  if (valid) {
-    T* o = out + (long long)(row_off[b] + i) * d + h * HD;
-    const float inv = 1.f / l;
-#pragma unroll
-    for (int e = 0; e < HD; ++e) o[e] = (T)(acc[e] * inv);
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// Prefill attention on MFMA (fp16, head dim 32), same construction as the DiT kernel (attn.hip): transposed scores
-// S^T = K Q^T (one 16x16x32 MFMA per 16 keys x 16 queries: k = head dim), the probabilities a lane holds are the B
-// operand of O^T = V^T P^T, keys dealt in 32-key chunks to the 4 waves with online softmax, LDS combine.  K comes
-// straight from the head-major cache (a 16-key fragment is 1 KB contiguous), V^T from a per-prefill scratch.
-// Mask (t2s_model.py:655-683): text queries see the text keys; audio queries see all text + causal audio.
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void prefill_vt_kernel(const _Float16* __restrict__ qkv, const int* __restrict__ row_off,
-                                                         const int* __restrict__ x_len, const int* __restrict__ plen, int d,
-                                                         int H, int spad, _Float16* __restrict__ vt) {
-  __shared__ _Float16 tile[32][34];
-  const int b = blockIdx.z, h = blockIdx.y, j0 = blockIdx.x * 32;
-  const int S = x_len[b] + plen[b];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (int i = ty; i < 32; i += 8) {
-    const int j = j0 + i;
-    tile[i][tx] = j < S ? qkv[(long long)(row_off[b] + j) * 3 * d + 2 * d + h * 32 + tx] : (_Float16)0.f;
-  }
-  __syncthreads();
-  for (int i = ty; i < 32; i += 8) vt[(((long long)b * H + h) * 32 + i) * spad + j0 + tx] = tile[tx][i];
-}
-
-// The same V^T tiles plus the head-major K/V cache rows of those 32 positions: one launch per layer instead of
-// kv_scatter_kernel + prefill_vt_kernel (a 32 x 32 tile of one head is 2 KB contiguous in either cache).
-__global__ __launch_bounds__(256) void prefill_kvt_kernel(const _Float16* __restrict__ qkv, const int* __restrict__ row_off,
-                                                          const int* __restrict__ x_len, const int* __restrict__ plen, int d,
-                                                          int H, int smax, int spad, _Float16* __restrict__ kc,
-                                                          _Float16* __restrict__ vc, _Float16* __restrict__ vt) {
-  __shared__ _Float16 tile[32][34];
-  const int b = blockIdx.z, h = blockIdx.y, j0 = blockIdx.x * 32;
-  const int S = x_len[b] + plen[b];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (int i = ty; i < 32; i += 8) {
-    const int j = j0 + i;
-    _Float16 v = (_Float16)0.f;
-    if (j < S) {
-      const _Float16* src = qkv + (long long)(row_off[b] + j) * 3 * d + h * 32 + tx;
-      const long long o = (((long long)b * H + h) * smax + j) * 32 + tx;
-      v = src[2 * d];
-      kc[o] = src[d];
-      vc[o] = v;
-    }
-    tile[i][tx] = v;
-  }
-  __syncthreads();
-  for (int i = ty; i < 32; i += 8) vt[(((long long)b * H + h) * 32 + i) * spad + j0 + tx] = tile[tx][i];
-}
-
-template <int QT>
-__global__ __launch_bounds__(256) void prefill_flash32_f16_kernel(const _Float16* __restrict__ qkv, const _Float16* __restrict__ kc,
-                                                                   const _Float16* __restrict__ vt, const int* __restrict__ row_off,
-                                                                   const int* __restrict__ x_len, const int* __restrict__ plen, int d,
-                                                                   int H, int smax, int spad, _Float16* __restrict__ out) {
-  constexpr int BQ = 16 * QT, LDO = 36;
-  __shared__ float Os[4][BQ][LDO];
-  __shared__ float Ms[4][BQ], Ls[4][BQ];
-  const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * BQ;
-  const int X = x_len[b], S = X + plen[b];
-  if (q0 >= S) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int r = lane & 15, g = lane >> 4;
-  const float scale = rsqrtf(32.f);
-  h8 qf[QT];
-#pragma unroll
-  for (int t = 0; t < QT; ++t)
-    qf[t] = *(const h8*)(qkv + (long long)(row_off[b] + min(q0 + 16 * t + r, S - 1)) * 3 * d + h * 32 + g * 8);
-  const _Float16* kb = kc + ((long long)b * H + h) * smax * 32 + g * 8;
-  const _Float16* vb = vt + (((long long)b * H + h) * 32 + r) * spad + 8 * g;
-  const int kra = 8 * (r >> 2) + (r & 3);           // permuted K rows: the lane's 8 scores are 8 consecutive keys (attn.hip)
-  f4 o[QT][2];
-  float m[QT], l[QT];
-#pragma unroll
-  for (int t = 0; t < QT; ++t) { m[t] = -INFINITY; l[t] = 0.f; o[t][0] = (f4){0.f, 0.f, 0.f, 0.f}; o[t][1] = o[t][0]; }
-  const int qlast = min(q0 + BQ, S) - 1;
-  const int nk = qlast < X ? X : qlast + 1;          // workgroup-uniform bound of the key range
-  const int nchunks = (nk + 31) >> 5, lastc = nchunks - 1;
-  struct KV { h8 ka, kb2; h8 v[2]; };
-  auto fetch = [&](KV& f, int c) {
-    const int key0 = c << 5;
-    f.ka = *(const h8*)(kb + (long long)min(key0 + kra, S - 1) * 32);
-    f.kb2 = *(const h8*)(kb + (long long)min(key0 + kra + 4, S - 1) * 32);
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt) f.v[dt] = *(const h8*)(vb + (long long)(dt * 16) * spad + key0);
-  };
-  auto process = [&](const KV& f, int c, bool valid) {
-    const int key0 = c << 5;
-#pragma unroll
-    for (int t = 0; t < QT; ++t) {
-      const int qi = q0 + 16 * t + r;
-      const int lim = qi < X ? X : qi + 1;           // keys [0, lim) are visible to query qi
-      f4 sa = (f4){0.f, 0.f, 0.f, 0.f}, sb = sa;
-      sa = __builtin_amdgcn_mfma_f32_16x16x32_f16(f.ka, qf[t], sa, 0, 0, 0);
-      sb = __builtin_amdgcn_mfma_f32_16x16x32_f16(f.kb2, qf[t], sb, 0, 0, 0);
-      float p[8];
-      float mx = -INFINITY;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        p[i] = (valid && key0 + 8 * g + i < lim) ? sa[i] * scale : -INFINITY;
-        p[4 + i] = (valid && key0 + 8 * g + 4 + i < lim) ? sb[i] * scale : -INFINITY;
-        mx = fmaxf(mx, fmaxf(p[i], p[4 + i]));
-      }
-      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      const float mnew = fmaxf(m[t], mx);
-      const float ms = mnew == -INFINITY ? 0.f : mnew;   // a causal query may see none of this wave's keys yet
-      const float alpha = __expf(m[t] - ms);
-      float ps = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) { p[i] = __expf(p[i] - ms); ps += p[i]; }
-      ps += __shfl_xor(ps, 16, 64);
-      ps += __shfl_xor(ps, 32, 64);
-      l[t] = l[t] * alpha + ps;
-      m[t] = mnew;
-      const h8 pf = (h8){(_Float16)p[0], (_Float16)p[1], (_Float16)p[2], (_Float16)p[3], (_Float16)p[4], (_Float16)p[5], (_Float16)p[6], (_Float16)p[7]};
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        o[t][dt] *= alpha;
-        o[t][dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f.v[dt], pf, o[t][dt], 0, 0, 0);
-      }
-    }
-  };
-#define GSV_PIN2() do { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-  KV fA, fB;
-  fetch(fA, min(wave, lastc));
-  for (int c = wave; c < nchunks; c += 8) {
-    fetch(fB, min(c + 4, lastc));
-    GSV_PIN2();
-    process(fA, c, true);
-    GSV_PIN2();
-    fetch(fA, min(c + 8, lastc));
-    GSV_PIN2();
-    process(fB, c + 4, c + 4 < nchunks);
-    GSV_PIN2();
-  }
-#undef GSV_PIN2
-#pragma unroll
-  for (int t = 0; t < QT; ++t) {
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt) *(f4*)&Os[wave][16 * t + r][dt * 16 + 4 * g] = o[t][dt];
-    if (g == 0) { Ms[wave][16 * t + r] = m[t]; Ls[wave][16 * t + r] = l[t]; }
-  }
-  __syncthreads();
-  for (int it = threadIdx.x; it < BQ * 8; it += 256) {
-    const int qq = it >> 3, d4 = (it & 7) * 4;
-    if (q0 + qq >= S) continue;
-    const float mt = fmaxf(fmaxf(Ms[0][qq], Ms[1][qq]), fmaxf(Ms[2][qq], Ms[3][qq]));   // finite: key 0 is visible to every query
-    float den = 0.f;
-    f4 acc = (f4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const float e = __expf(Ms[w][qq] - mt);
-      den += e * Ls[w][qq];
-      acc += *(const f4*)&Os[w][qq][d4] * e;
-    }
-    const float inv = 1.f / den;
-    *(h4*)(out + (long long)(row_off[b] + q0 + qq) * d + h * 32 + d4) =
-        (h4){(_Float16)(acc[0] * inv), (_Float16)(acc[1] * inv), (_Float16)(acc[2] * inv), (_Float16)(acc[3] * inv)};
-  }
-}
-
-// gather each row's last prefill position of the fp32 pre-LN2 stream into the decode buffer
-__global__ void gather_last_kernel(const float* __restrict__ y2, const int* __restrict__ row_off,
-                                   const int* __restrict__ x_len, const int* __restrict__ plen, int d, float* __restrict__ ybuf) {
-  const int b = blockIdx.x;
-  const float* src = y2 + (long long)(row_off[b] + x_len[b] + plen[b] - 1) * d;
-  for (int c = threadIdx.x; c < d; c += blockDim.x) ybuf[(long long)b * d + c] = src[c];
-}
-
-// each row's prompt into the head of its token history (the repetition penalty's window): ytok[b][0 .. P_b)
-__global__ void prompt_copy_kernel(const int* __restrict__ prompts, const int* __restrict__ plen, const int* __restrict__ poff,
-                                   int ycap, int* __restrict__ ytok) {
-  const int b = blockIdx.x, P = plen[b];
-  for (int t = threadIdx.x; t < P; t += blockDim.x) ytok[(long long)b * ycap + t] = prompts[poff[b] + t];
-}
-
 // ---------------------------------------------------------------------------------------
 // Decode-step skinny GEMM:  Y[b][n] = sum_k X[b][k] W[n][k]   for b < B (B <= 16*CB)
 // Workgroup = one 16-row tile of W (n0..n0+15), NW waves each owning K/NW of the contraction,
@@ -307,26 +38,27 @@ __global__ void prompt_copy_kernel(const int* __restrict__ prompts, const int* _
 // ---------------------------------------------------------------------------------------
 enum { EPI_QKV = 0, EPI_RESID = 1, EPI_RELU = 2, EPI_LOGITS = 3 };
 
-struct DecGemmArgs {
+struct DecGemmArgs {   // a kernel argument: trivially copyable, every field zero unless set
   // X source (exactly one of yin / xin)
-  const float* yin;     // fp32 pre-LN stream [B][K] -> LN(gamma,beta) (or plain convert if gamma==null) -> LDS
-  const float* gamma;
-  const float* beta;
-  float* xres_out;      // if non-null, workgroup 0 writes the normalised fp32 rows here [B][K]
-  const void* xin;      // T activations [B][K] read straight from HBM/L2
-  const void* w;        // T [N][K]
-  const float* bias;    // [N] or null
-  int B, K, N;
-  int epi;
+  const float* yin = nullptr;     // fp32 pre-LN stream [B][K] -> LN(gamma,beta) (or plain convert if gamma==null) -> LDS
+  const float* gamma = nullptr;
+  const float* beta = nullptr;
+  float* xres_out = nullptr;      // if non-null, workgroup 0 writes the normalised fp32 rows here [B][K]
+  const void* xin = nullptr;      // T activations [B][K] read straight from HBM/L2
+  const void* w = nullptr;        // T [N][K]
+  const float* bias = nullptr;    // [N] or null
+  int B = 0, K = 0, N = 0;
+  int epi = 0;
   // epilogue targets
-  void* out_t;          // EPI_RELU: T [B][N]; EPI_QKV: q buffer T [B][d]
-  float* out_f;         // EPI_RESID / EPI_LOGITS: fp32 [B][N]
-  const float* xres;    // EPI_RESID: fp32 residual [B][N]
-  void* kc; void* vc;   // EPI_QKV: cache bases for this layer
-  const int* kv_len;    // EPI_QKV
-  const int* active;
-  int d, H, smax;
+  void* out_t = nullptr;          // EPI_RELU: T [B][N]; EPI_QKV: q buffer T [B][d]
+  float* out_f = nullptr;         // EPI_RESID / EPI_LOGITS: fp32 [B][N]
+  const float* xres = nullptr;    // EPI_RESID: fp32 residual [B][N]
+  void* kc = nullptr; void* vc = nullptr;   // EPI_QKV: cache bases for this layer
+  const int* kv_len = nullptr;    // EPI_QKV
+  const int* active = nullptr;
+  int d = 0, H = 0, smax = 0;
 };
+static_assert(std::is_trivially_copyable<DecGemmArgs>::value, "DecGemmArgs is passed to kernels by value");
 
 template <typename T> struct Frag16;
 template <> struct Frag16<_Float16> { typedef h8 type; static constexpr int KS = 32; };
@@ -671,244 +403,6 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const T* __restrict__ 
 #undef KVLOAD
 }
 
-// ---------------------------------------------------------------------------------------
-// Fused decode kernel A = LayerNorm prologue + QKV projection of ONE head + in-place KV append +
-// attention over the cached keys, for RPG = 2 batch rows per workgroup (grid = heads x rows/2 = 256
-// workgroups at B = 32: one per CU).  It replaces the separate QKV and attention launches: the
-// K/V stream of the (row, head) pairs is requested at kernel entry (speculatively, before kv_len is
-// known) so the HBM latency of the cache overlaps the weight fetch, the LayerNorm and the MFMAs.
-//   waves 0,1 -> row 0, waves 2,3 -> row 1 for the attention; all 4 waves split K for the projection.
-// ---------------------------------------------------------------------------------------
-struct QkvAttnArgs {
-  const float* yin; const float* gamma; const float* beta; float* xres_out;
-  const void* w; const float* bias;           // [3d][K] and [3d]
-  void* kc; void* vc; const int* kv_len; const int* active;
-  void* out;                                  // T [B][d]
-  int B, d, H, smax;
-};
-
-template <typename T, int HD, int KD>
-__global__ __launch_bounds__(256) void dec_qkv_attn_kernel(QkvAttnArgs a) {
-  typedef typename Frag16<T>::type F;
-  constexpr int G = DT<T>::G;
-  constexpr int KS = Frag16<T>::KS;
-  constexpr int RPG = 2;
-  constexpr int LPK = HD / G, KPI = 64 / LPK;
-  constexpr int EPL = KD / 64;                 // LayerNorm elements per lane
-  constexpr int LDXS = KD + G;
-  constexpr int NKS_ALL = KD / KS;             // k-steps of the projection
-  constexpr int NKS_W = NKS_ALL / 4;           // per wave
-  constexpr int KCH = NKS_W > 4 ? 4 : NKS_W;   // k-steps in flight per wave
-  static_assert(NKS_ALL % 4 == 0 && NKS_W % KCH == 0, "K split");
-  __shared__ __attribute__((aligned(16))) T xs[(RPG + 1) * LDXS];
-  __shared__ __attribute__((aligned(16))) float red[4 * 6 * 64 * 4];
-  __shared__ float qkv_s[RPG][3 * HD];
-  __shared__ float s_m[4];
-  __shared__ float s_acc[4][HD + 1];
-
-  const int h = blockIdx.x, rg = blockIdx.y;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int d = a.d, H = a.H, smax = a.smax;
-  const int part = lane % LPK, slot = lane / LPK;
-  const int arow = wave >> 1, half = wave & 1;          // attention: row of this wave, key-group parity
-  const int b_att = rg * RPG + arow;
-  const bool row_ok = b_att < a.B;
-  const int bsafe = row_ok ? b_att : 0;
-  const T* kb = (const T*)a.kc + ((long long)bsafe * H + h) * smax * HD;
-  const T* vb = (const T*)a.vc + ((long long)bsafe * H + h) * smax * HD;
-
-  // ---- (1) speculative K/V groups of this wave: group g = half + 2*i holds keys [g*KPI, (g+1)*KPI)
-  constexpr int SPEC = 4, NEXT = 6;
-  F ksp[SPEC], vsp[SPEC];
-#pragma unroll
-  for (int i = 0; i < SPEC; ++i) {
-    const int j = (half + 2 * i) * KPI + slot;
-    if (j < smax) { ksp[i] = *(const F*)(kb + (long long)j * HD + part * G); vsp[i] = *(const F*)(vb + (long long)j * HD + part * G); }
-    else {
-#pragma unroll
-      for (int e = 0; e < G; ++e) { ksp[i][e] = 0; vsp[i][e] = 0; }
-    }
-  }
-  const int act = row_ok ? a.active[bsafe] : 0;
-  const int nold = row_ok ? min(a.kv_len[bsafe], smax - 1) : 0;   // cached keys; the new key goes to position nold
-
-  // ---- (2) LayerNorm prologue: wave w < RPG normalises row w (fp32, two-pass), writes T copy to LDS
-  if (wave < RPG) {
-    const int b = rg * RPG + wave;
-    float v[EPL];
-    const bool live = b < a.B;
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) v[i] = live ? a.yin[(long long)b * KD + lane + 64 * i] : 0.f;
-    if (a.gamma) {
-      float sum = 0.f;
-#pragma unroll
-      for (int i = 0; i < EPL; ++i) sum += v[i];
-      const float mean = wave_sum(sum) / (float)KD;
-      float q2 = 0.f;
-#pragma unroll
-      for (int i = 0; i < EPL; ++i) { float dl = v[i] - mean; q2 += dl * dl; }
-      const float rstd = rsqrtf(wave_sum(q2) / (float)KD + 1e-5f);
-#pragma unroll
-      for (int i = 0; i < EPL; ++i) v[i] = live ? (v[i] - mean) * rstd * a.gamma[lane + 64 * i] + a.beta[lane + 64 * i] : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) {
-      xs[wave * LDXS + lane + 64 * i] = (T)v[i];
-      if (a.xres_out && h == 0 && live) a.xres_out[(long long)b * KD + lane + 64 * i] = v[i];
-    }
-  } else if (wave == RPG) {
-    for (int c = lane; c < LDXS; c += 64) xs[RPG * LDXS + c] = (T)0.f;     // zero row for the unused MFMA columns
-  }
-
-  // ---- (3) second K/V batch now that kv_len is known (same round trip as the speculative one)
-  F kn[NEXT], vn[NEXT];
-#pragma unroll
-  for (int i = 0; i < NEXT; ++i) {
-    const int j = (half + 2 * (SPEC + i)) * KPI + slot;
-    if (j < nold) { kn[i] = *(const F*)(kb + (long long)j * HD + part * G); vn[i] = *(const F*)(vb + (long long)j * HD + part * G); }
-    else {
-#pragma unroll
-      for (int e = 0; e < G; ++e) { kn[i][e] = 0; vn[i][e] = 0; }
-    }
-  }
-
-  // ---- (4) QKV projection of head h: 6 tiles of 16 weight rows (q|k|v x 2), K split over the 4 waves
-  f4v acc[6];
-#pragma unroll
-  for (int j = 0; j < 6; ++j) acc[j] = (f4v){0.f, 0.f, 0.f, 0.f};
-  const int rowl = lane & 15, kg = lane >> 4;
-  const T* wbase = (const T*)a.w;
-  __syncthreads();                                                           // xs ready
-  for (int kc0 = 0; kc0 < NKS_W; kc0 += KCH) {
-    F af[KCH][6];
-#pragma unroll
-    for (int i = 0; i < KCH; ++i) {
-      const int k = (wave * NKS_W + kc0 + i) * KS + G * kg;
-#pragma unroll
-      for (int j = 0; j < 6; ++j) {
-        const int wrow = (j >> 1) * d + h * HD + (j & 1) * 16 + rowl;          // q rows, k rows, v rows of head h
-        af[i][j] = *(const F*)(wbase + (long long)wrow * KD + k);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < KCH; ++i) {
-      const int k = (wave * NKS_W + kc0 + i) * KS + G * kg;
-      const F bf = *(const F*)(xs + (rowl < RPG ? rowl : RPG) * LDXS + k);
-#pragma unroll
-      for (int j = 0; j < 6; ++j) mma16(acc[j], af[i][j], bf);
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 6; ++j) *(f4v*)(red + ((wave * 6 + j) * 64 + lane) * 4) = acc[j];
-  __syncthreads();
-  if (tid < RPG * 3 * HD) {
-    const int r = tid / (3 * HD), nl = tid - r * (3 * HD);     // nl: 0..31 q, 32..63 k, 64..95 v
-    const int j = nl >> 4, rr = nl & 15;
-    const int ln = (rr >> 2) * 16 + r, i = rr & 3;             // D layout: col = batch row, row = 4*(ln>>4)+i
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) v += red[((w * 6 + j) * 64 + ln) * 4 + i];
-    const int which = nl / HD, e = nl - which * HD;
-    v += a.bias[which * d + h * HD + e];
-    qkv_s[r][nl] = v;
-    const int b = rg * RPG + r;
-    if (which > 0 && b < a.B && a.active[b]) {                  // append the new key / value row in place
-      const int pos = min(a.kv_len[b], smax - 1);
-      T* base = (T*)(which == 1 ? a.kc : a.vc);
-      base[(((long long)b * H + h) * smax + pos) * HD + e] = (T)v;
-    }
-  }
-  __syncthreads();
-
-  // ---- (5) attention of (b_att, h): this wave's key groups + (half == 0) the new key from LDS
-  float qf[G];
-  {
-    const float scale = rsqrtf((float)HD);
-#pragma unroll
-    for (int i = 0; i < G; ++i) qf[i] = to_f((T)qkv_s[arow][part * G + i]) * scale;
-  }
-  float m = -INFINITY, l = 0.f, oacc[G];
-#pragma unroll
-  for (int i = 0; i < G; ++i) oacc[i] = 0.f;
-  auto consume = [&](const float* kf, const float* vf, bool ok) {
-    float sc = 0.f;
-#pragma unroll
-    for (int i = 0; i < G; ++i) sc += qf[i] * kf[i];
-#pragma unroll
-    for (int o = 1; o < LPK; o <<= 1) sc += __shfl_xor(sc, o, 64);
-    if (ok) {
-      const float mn = fmaxf(m, sc);
-      const float corr = __expf(m - mn);
-      const float p = __expf(sc - mn);
-      l = l * corr + p;
-#pragma unroll
-      for (int i = 0; i < G; ++i) oacc[i] = oacc[i] * corr + p * vf[i];
-      m = mn;
-    }
-  };
-  auto consume_frag = [&](const F& kv, const F& vv, bool ok) {
-    float kf[G], vf[G];
-#pragma unroll
-    for (int i = 0; i < G; ++i) { kf[i] = to_f(kv[i]); vf[i] = to_f(vv[i]); }
-    consume(kf, vf, ok);
-  };
-  const bool live_row = row_ok && act;
-#pragma unroll
-  for (int i = 0; i < SPEC; ++i) consume_frag(ksp[i], vsp[i], live_row && (half + 2 * i) * KPI + slot < nold);
-#pragma unroll
-  for (int i = 0; i < NEXT; ++i) consume_frag(kn[i], vn[i], live_row && (half + 2 * (SPEC + i)) * KPI + slot < nold);
-  if (live_row) {
-    for (int j0 = (half + 2 * (SPEC + NEXT)) * KPI; j0 < nold; j0 += 2 * KPI) {
-      const int j = j0 + slot;
-      const bool ok = j < nold;
-      F kv, vv;
-      if (ok) { kv = *(const F*)(kb + (long long)j * HD + part * G); vv = *(const F*)(vb + (long long)j * HD + part * G); }
-      else {
-#pragma unroll
-        for (int e = 0; e < G; ++e) { kv[e] = 0; vv[e] = 0; }
-      }
-      consume_frag(kv, vv, ok);
-    }
-  }
-  {
-    // the key/value just produced (position nold), rounded to the cache dtype exactly as a later step reads it
-    float kf[G], vf[G];
-#pragma unroll
-    for (int i = 0; i < G; ++i) { kf[i] = to_f((T)qkv_s[arow][HD + part * G + i]); vf[i] = to_f((T)qkv_s[arow][2 * HD + part * G + i]); }
-    consume(kf, vf, live_row && half == 0 && slot == 0);
-  }
-  // combine the two waves of the row (and all key slots)
-  float wm = wave_max(m);
-  if (lane == 0) s_m[wave] = wm;
-  __syncthreads();
-  const float M = fmaxf(s_m[arow * 2], s_m[arow * 2 + 1]);
-  const float f = (m == -INFINITY) ? 0.f : __expf(m - M);
-  l *= f;
-#pragma unroll
-  for (int i = 0; i < G; ++i) oacc[i] *= f;
-#pragma unroll
-  for (int o = LPK; o < 64; o <<= 1) {
-    l += __shfl_xor(l, o, 64);
-#pragma unroll
-    for (int i = 0; i < G; ++i) oacc[i] += __shfl_xor(oacc[i], o, 64);
-  }
-  if (lane < LPK) {
-#pragma unroll
-    for (int i = 0; i < G; ++i) s_acc[wave][lane * G + i] = oacc[i];
-    if (lane == 0) s_acc[wave][HD] = l;
-  }
-  __syncthreads();
-  if (tid < RPG * HD) {
-    const int r = tid / HD, e = tid - r * HD;
-    const int b = rg * RPG + r;
-    if (b < a.B && a.active[b]) {
-      const float L = s_acc[2 * r][HD] + s_acc[2 * r + 1][HD];
-      const float v = s_acc[2 * r][e] + s_acc[2 * r + 1][e];
-      ((T*)a.out)[(long long)b * d + h * HD + e] = (T)(v / L);
-    }
-  }
-}
-
 // step tail: sample every row, update row state, emit the next step's input embedding
 // (t2s_model.py:714-769).  grid = B, block = 64.
 template <int NPL>
@@ -980,67 +474,7 @@ __global__ __launch_bounds__(64) void sample_only_kernel(const float* __restrict
 // =======================================================================================
 using namespace gsv;
 
-struct LayerW {
-  void *qkv_w = nullptr, *out_w = nullptr, *w1 = nullptr, *w2 = nullptr;
-  float *qkv_b = nullptr, *out_b = nullptr, *b1 = nullptr, *b2 = nullptr;
-  float *n1w = nullptr, *n1b = nullptr, *n2w = nullptr, *n2b = nullptr;
-};
-
-struct gsv_t2s {
-  gsv_t2s_config cfg;
-  int dtype, max_batch, max_seq;
-  bool finalized = false;
-  std::map<std::string, std::vector<float>> staged;
-  std::vector<LayerW> layers;
-  void* bert_w = nullptr; float* bert_b = nullptr;
-  float *e_text = nullptr, *e_audio = nullptr, *pe = nullptr;
-  void* pred_w = nullptr;
-  float alpha_t = 1.f, alpha_a = 1.f;
-  int pe_rows = 0;
-  // KV arena
-  void* kv = nullptr; size_t kv_layer_stride = 0;  // elements per (layer, k|v)
-  // row state
-  int *d_x_len = nullptr, *d_row_off = nullptr, *d_ph_off = nullptr, *d_kv_len = nullptr, *d_active = nullptr,
-      *d_step = nullptr, *d_n_active = nullptr, *d_ytok = nullptr;
-  int ycap = 0;
-  int* d_plen = nullptr;    // [2][max_batch]: prompt length P_b | offset of row b's prompt in the packed prompt buffer
-  unsigned long long* d_rng_seed = nullptr; int* d_rng_row = nullptr;   // [max_batch] counter-RNG keys of the rows
-  std::vector<unsigned long long> rng_seed_up; std::vector<int> rng_row_up;   // what the device arrays hold (skip re-uploads)
-  std::vector<unsigned long long> rng_seed_next; std::vector<int> rng_row_next;   // gsv_t2s_set_row_rng: NEXT decode only
-  int* h_pinned = nullptr;
-  StepParams* d_sp = nullptr;
-  // decode buffers
-  float *ybuf = nullptr, *xres = nullptr, *logits = nullptr;
-  void *qbuf = nullptr, *abuf = nullptr, *hbuf = nullptr;
-  // prefill workspace (grown on demand)
-  size_t pf_rows = 0;
-  void *pf_x = nullptr, *pf_qkv = nullptr, *pf_attn = nullptr, *pf_h = nullptr;
-  void* pf_vt = nullptr; size_t pf_vt_cap = 0;   // V^T scratch of the MFMA prefill attention: [B][H][32][ceil32(maxS)] halfs
-  float *pf_y = nullptr, *pf_bert = nullptr;
-  void* pf_bert_t = nullptr;
-  // current batch
-  int B = 0, P = 0;         // P: the longest row's prompt (uniform prefill: every row's)
-  int max_kv0 = 0;          // longest row's cached positions after prefill (host copy: bounds the decode budget)
-  // persistent decode engine (t2s_mega.hip): fp16, v1/v2 shape, B <= 128; the launch-per-phase step stays as the
-  // fp32 / other-shape path and behind GSV_T2S_NO_MEGA=1 for A/B
-  MegaState mega;
-  hipEvent_t mega_ev[2] = {nullptr, nullptr};
-  float last_decode_ms = 0.f; int last_decode_steps = 0; int last_decode_mode = 0;
-  bool mega_on = true;      // gsv_t2s_set_mega (A/B inside one process); GSV_T2S_NO_MEGA=1 never builds the engine
-  const int* dbg_force = nullptr; float* dbg_dump = nullptr; int* dbg_drawn = nullptr; int dbg_stall = 0;   // gsv_t2s_set_debug / gsv_t2s_debug_stall: apply to the NEXT decode call only
-  std::map<int, hipGraphExec_t> graphs;
-  std::vector<void*> allocs;
-};
-
 namespace {
-
-size_t esz(const gsv_t2s* h) { return dt_size(h->dtype); }
-
-int dev_alloc(gsv_t2s* h, void** p, size_t bytes) {
-  GSV_HIP(hipMalloc(p, bytes ? bytes : 16));
-  h->allocs.push_back(*p);
-  return GSV_OK;
-}
 
 int upload_f32(gsv_t2s* h, const std::vector<float>& v, float** out) {
   int rc = dev_alloc(h, (void**)out, v.size() * 4);
@@ -1076,8 +510,7 @@ int launch_dec_gemm_inst(const DecGemmArgs& a, hipStream_t s) {
   if (KV4 > 0) lds = std::max(lds, (size_t)CB * 16 * (a.K + G) * sizeof(T));
   auto kern = dec_gemm_kernel<T, CB, NW, KSL, KV4>;
   if (lds > 64 * 1024) GSV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3(cdiv(a.N, 16), cdiv(a.B, CB * 16)), dim3(NW * 64), lds, s, a);
-  GSV_HIP(hipGetLastError());
+  GSV_LAUNCH(kern, dim3(cdiv(a.N, 16), cdiv(a.B, CB * 16)), dim3(NW * 64), lds, s, a);
   return GSV_OK;
 }
 
@@ -1121,7 +554,351 @@ int launch_dec_gemm(const DecGemmArgs& a, bool lnpro, hipStream_t s) {
   return GSV_ERR_ARG;
 }
 
-int sample_npl(int V) { return V <= 128 ? 2 : (V <= 1088 ? 17 : 32); }
+// one wave samples a row with its logits in registers, NPL per lane (64 * NPL >= V): the instantiation for a vocabulary,
+// shared by sample_step_kernel and sample_only_kernel
+template <typename F>
+int with_npl(int V, F&& f) {
+  if (V <= 128) return f(std::integral_constant<int, 2>{});
+  if (V <= 1088) return f(std::integral_constant<int, 17>{});
+  return f(std::integral_constant<int, 32>{});
+}
+
+// The two X-operand forms of the decode GEMMs.  LayerNorm prologue: X = LN(ybuf) with gamma / beta (null: plain convert),
+// the normalised fp32 rows also go to xres, the residual of the layer's next EPI_RESID; the caller adds the epilogue targets.
+DecGemmArgs ln_gemm(const gsv_t2s* h, const float* gamma, const float* beta, const void* w, const float* bias, int N, int epi) {
+  DecGemmArgs a;
+  a.yin = h->ybuf; a.gamma = gamma; a.beta = beta; a.xres_out = h->xres;
+  a.w = w; a.bias = bias; a.B = h->B; a.K = h->cfg.dim; a.N = N; a.epi = epi;
+  return a;
+}
+// Plain form: ybuf = xin W^T + bias + xres, xin [B][K] in the engine dtype
+DecGemmArgs resid_gemm(const gsv_t2s* h, const void* xin, const void* w, const float* bias, int K) {
+  DecGemmArgs a;
+  a.xin = xin; a.w = w; a.bias = bias; a.B = h->B; a.K = K; a.N = h->cfg.dim; a.epi = EPI_RESID;
+  a.out_f = h->ybuf; a.xres = h->xres;
+  return a;
+}
+
+template <typename T>
+int launch_decode_attn(const void* q, const void* kc, const void* vc, const int* kv_len, const int* active, int B, int H, int smax,
+                       void* out, hipStream_t s) {
+  GSV_LAUNCH((decode_attn_kernel<T, 32>), dim3(H, B), dim3(256), 0, s, (const T*)q, (const T*)kc, (const T*)vc, kv_len, active,
+             H, smax, (T*)out);
+  return GSV_OK;
+}
+
+// the layers of one decode step; only_attn: the attention launches alone (gsv_t2s_time_step)
+template <typename T>
+int launch_decode_layers(gsv_t2s* h, hipStream_t s, bool only_attn) {
+  const auto& c = h->cfg;
+  const int d = c.dim, H = c.n_head;
+  for (int li = 0; li < c.n_layer; ++li) {
+    const LayerW& L = h->layers[li];
+    if (!only_attn) {
+      // the previous layer's LN2 is this GEMM's prologue (layer 0: ybuf is the embedding, converted as it is)
+      const LayerW* prev = li > 0 ? &h->layers[li - 1] : nullptr;
+      DecGemmArgs a = ln_gemm(h, prev ? prev->n2w : nullptr, prev ? prev->n2b : nullptr, L.qkv_w, L.qkv_b, 3 * d, EPI_QKV);
+      a.out_t = h->qbuf; a.kc = kv_ptr(h, li, 0); a.vc = kv_ptr(h, li, 1); a.kv_len = h->d_kv_len; a.active = h->d_active;
+      a.d = d; a.H = H; a.smax = h->max_seq;
+      GSV_RC(launch_dec_gemm<T>(a, true, s));
+    }
+    GSV_RC(launch_decode_attn<T>(h->qbuf, kv_ptr(h, li, 0), kv_ptr(h, li, 1), h->d_kv_len, h->d_active, h->B, H, h->max_seq,
+                                 h->abuf, s));
+    if (only_attn) continue;
+    GSV_RC(launch_dec_gemm<T>(resid_gemm(h, h->abuf, L.out_w, L.out_b, d), false, s));
+    DecGemmArgs f1 = ln_gemm(h, L.n1w, L.n1b, L.w1, L.b1, c.ffn_dim, EPI_RELU);
+    f1.out_t = h->hbuf;
+    GSV_RC(launch_dec_gemm<T>(f1, true, s));
+    GSV_RC(launch_dec_gemm<T>(resid_gemm(h, h->hbuf, L.w2, L.b2, c.ffn_dim), false, s));
+  }
+  return GSV_OK;
+}
+
+// logits (LN2 prologue of the last layer) + sampling/state update
+template <typename T>
+int launch_tail(gsv_t2s* h, hipStream_t s) {
+  const auto& c = h->cfg;
+  const LayerW& L = h->layers[c.n_layer - 1];
+  DecGemmArgs a = ln_gemm(h, L.n2w, L.n2b, h->pred_w, nullptr, c.vocab, EPI_LOGITS);
+  a.xres_out = nullptr;   // no residual follows the last LayerNorm
+  a.out_f = h->logits;
+  GSV_RC(launch_dec_gemm<T>(a, true, s));
+  const int V = c.vocab, EOS = c.vocab - 1;
+  return with_npl(V, [&](auto npl) -> int {
+    GSV_LAUNCH(sample_step_kernel<decltype(npl)::value>, dim3(h->B), dim3(64), (size_t)((V + 15) & ~15), s, h->logits, V, EOS,
+               h->d_sp, h->d_ytok, h->ycap, h->d_kv_len, h->d_active, h->d_step, h->d_n_active, h->e_audio, h->pe, h->alpha_a,
+               c.dim, h->ybuf);
+    return GSV_OK;
+  });
+}
+
+template <typename T>
+int launch_step(gsv_t2s* h, hipStream_t s) {
+  GSV_RC(launch_decode_layers<T>(h, s, false));
+  return launch_tail<T>(h, s);
+}
+
+// ---- gsv_t2s_decode in the order it runs: decode_begin, step 0 (launch_tail), then run_mega and / or run_steps ----
+
+// Uploads the call's sampling parameters and the rows' counter-RNG keys and checks that the request fits the arena, the
+// position table and the token history.  Returns the step budget (>= 1) or an error code (< 0).
+int decode_begin(gsv_t2s* h, const gsv_sampling_params* sp, const float* noise, int noise_rows, int32_t* out_tokens,
+                 int32_t* out_len, hipStream_t s) {
+  StepParams p;
+  p.top_k = sp->top_k; p.top_p = sp->top_p; p.temperature = sp->temperature; p.rep_penalty = sp->repetition_penalty;
+  p.early_stop_num = sp->early_stop_num; p.eos_mask_steps = sp->eos_mask_steps; p.max_steps = sp->max_steps;
+  p.noise_rows = noise ? noise_rows : 0; p.seed = sp->seed; p.noise = noise; p.out_tokens = out_tokens; p.out_len = out_len;
+  p.plen = h->d_plen; p.rng_seed = h->d_rng_seed; p.rng_row = h->d_rng_row;
+  p.force = h->dbg_force; p.dump = h->dbg_dump; p.drawn = h->dbg_drawn;
+  h->dbg_force = nullptr; h->dbg_dump = nullptr; h->dbg_drawn = nullptr;
+  // counter-RNG keys of the rows: gsv_t2s_set_row_rng's for this call, else (seed, b) -- the draws of a batch without keys
+  const bool keyed = !h->rng_seed_next.empty();
+  const int nkeys = (int)h->rng_seed_next.size();
+  std::vector<unsigned long long> seeds(h->B);
+  std::vector<int> rows(h->B);
+  for (int b = 0; b < h->B && (!keyed || nkeys == h->B); ++b) {
+    seeds[b] = keyed ? h->rng_seed_next[b] : (unsigned long long)sp->seed;
+    rows[b] = keyed ? h->rng_row_next[b] : b;
+  }
+  h->rng_seed_next.clear(); h->rng_row_next.clear();
+  GSV_REQUIRE(!keyed || nkeys == h->B, "t2s_decode: gsv_t2s_set_row_rng gave %d keys for a batch of %d rows", nkeys, h->B);
+  GSV_HIP(hipMemcpyAsync(h->d_sp, &p, sizeof(p), hipMemcpyHostToDevice, s));
+  if (seeds != h->rng_seed_up || rows != h->rng_row_up) {
+    GSV_HIP(hipMemcpyAsync(h->d_rng_seed, seeds.data(), (size_t)h->B * 8, hipMemcpyHostToDevice, s));
+    GSV_HIP(hipMemcpyAsync(h->d_rng_row, rows.data(), (size_t)h->B * 4, hipMemcpyHostToDevice, s));
+    h->rng_seed_up = seeds; h->rng_row_up = rows;
+  }
+  GSV_HIP(hipStreamSynchronize(s));
+  // budget: step 0 samples from the prefill's last position, every later step appends one K/V position, so the
+  // longest row ends at max_kv0 + budget - 1 cached positions; the sampling tail of row b reads pe[P_b + step] and writes
+  // token history [P_b + step] (h->P is the longest prompt).  A request that does not fit is refused here: the kernels clamp out-of-range
+  // appends, which would otherwise yield silently wrong tokens with rc 0.
+  int budget = sp->max_steps;
+  if (sp->early_stop_num >= 0 && sp->early_stop_num + 1 < budget) budget = sp->early_stop_num + 1;
+  GSV_REQUIRE(h->max_kv0 + budget <= h->max_seq,
+              "t2s_decode: %d cached positions + %d steps exceed the K/V arena (max_seq %d); lower max_steps / early_stop_num "
+              "or create the engine with a larger max_seq", h->max_kv0, budget, h->max_seq);
+  GSV_REQUIRE(h->P + budget <= h->pe_rows, "t2s_decode: prompt %d + %d steps exceed the position table (%d rows)", h->P, budget,
+              h->pe_rows);
+  GSV_REQUIRE(h->P + budget <= h->ycap, "t2s_decode: prompt %d + %d steps exceed the token history (%d)", h->P, budget, h->ycap);
+  return budget;
+}
+
+int env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
+
+// arguments of the persistent-engine launch that runs steps 1 .. budget - 1; its knobs are read once per process
+MegaArgs mega_args(gsv_t2s* h, int budget) {
+  static const bool map_local = getenv("GSV_MEGA_GROUP_XCD") != nullptr;
+  static const int map_mode = env_int("GSV_MEGA_MAP", 2);   // 2: roles by the XCD a workgroup runs on, 1: by blockIdx % 8
+  // bits 0-3: hops A-D poll ONE hint line before the full pass (hop B, 2 KB per row, is faster polled in full: 288 -> 284 us
+  // per step); bit 4: sweep2 keeps two polls in flight (measured 3 % slower, left off); bit 7: every member polls ANOTHER
+  // publisher's line instead of all 32 polling the row's last line (297 -> 288 us); bits 8-12: 16ths of the lines that may
+  // still be missing when sweep2's full passes start (logits hop)
+  static const int hint_mask = env_int("GSV_MEGA_HINT", 13 | (1 << 7) | (2 << 8));
+  MegaState& m = h->mega;
+  MegaArgs a;
+  memset(&a, 0, sizeof(a));
+  a.wpack = (const h8*)m.wpack; a.lpack = (const h8*)m.lpack; a.fpack = m.fpack;
+  a.kv = (_Float16*)h->kv; a.kv_layer_stride = h->kv_layer_stride; a.smax = h->max_seq;
+  a.kv_len = h->d_kv_len; a.active = h->d_active; a.step_ctr = h->d_step; a.n_active = h->d_n_active;
+  a.ytok = h->d_ytok; a.ycap = h->ycap; a.sp = h->d_sp; a.e_audio = h->e_audio; a.pe = h->pe; a.alpha_a = h->alpha_a;
+  a.ybuf = h->ybuf; a.logits_out = h->logits; a.hop = m.hop; a.err = m.err; a.B = h->B; a.L = h->cfg.n_layer; a.V = h->cfg.vocab;
+  a.nsteps = budget - 1; a.map_shared = map_local ? 0 : map_mode;
+  a.hint_mask = hint_mask;
+  a.ring = m.ring;
+  m.launch_gen = (m.launch_gen + 1) & 2047;
+  a.ep_base = m.launch_gen << 20;                       // 1500 steps x 98 hops < 2^20
+  a.test_stall = h->dbg_stall; h->dbg_stall = 0;        // tests only (gsv_t2s_debug_stall): this launch loses one publish
+  return a;
+}
+
+// Measurement runs: GSV_MEGA_PROF=<file> dumps in-kernel shader-clock stamps of one (step, layer) for every wave.
+// mega_prof_arm puts the stamp buffer into the launch arguments, mega_prof_dump copies it back, writes the file and frees it.
+constexpr size_t MEGA_PROF_N = (size_t)256 * 8 * 32;
+
+int mega_prof_arm(MegaArgs& a, int budget, hipStream_t s) {
+  if (!getenv("GSV_MEGA_PROF") || budget <= 8) return GSV_OK;
+  GSV_HIP(hipMalloc((void**)&a.prof, MEGA_PROF_N * 8));
+  GSV_HIP(hipMemsetAsync(a.prof, 0, MEGA_PROF_N * 8, s));
+  a.prof_step = env_int("GSV_MEGA_PROF_STEP", 5);
+  a.prof_layer = env_int("GSV_MEGA_PROF_LAYER", 7);
+  a.prof_quad = env_int("GSV_MEGA_PROF_QUAD", 0);
+  return GSV_OK;
+}
+
+int mega_prof_dump(const MegaArgs& a, float decode_ms) {
+  std::vector<unsigned long long> hp(MEGA_PROF_N);
+  GSV_HIP(hipMemcpy(hp.data(), a.prof, MEGA_PROF_N * 8, hipMemcpyDeviceToHost));
+  (void)hipFree(a.prof);
+  if (FILE* f = fopen(getenv("GSV_MEGA_PROF"), "w")) {
+    fprintf(f, "# decode %.3f ms for %d steps; stamps of step %d layer %d: wg wave stamp0 then deltas to stamp0\n", decode_ms,
+            a.nsteps, a.prof_step, a.prof_layer);
+    for (int wg = 0; wg < 256; ++wg)
+      for (int w = 0; w < 8; ++w) {
+        const unsigned long long* p = &hp[((size_t)wg * 8 + w) * 32];
+        if (!p[0]) continue;
+        fprintf(f, "%d %d %llu", wg, w, p[0]);
+        for (int i = 1; i < 24; ++i) fprintf(f, " %lld", p[i] ? (long long)(p[i] - p[0]) : -1ll);
+        fprintf(f, "\n");
+      }
+    fclose(f);
+  }
+  return GSV_OK;
+}
+
+// Steps 1 .. budget - 1 on the persistent engine.  MEGA_DONE: every row is finished; MEGA_FELL_BACK: the engine cannot run on
+// this device, or a hand-off timed out and the row state is again what step 0 left -- the caller continues on the launch
+// path; < 0: error.
+enum { MEGA_DONE = 0, MEGA_FELL_BACK = 1 };
+
+int run_mega(gsv_t2s* h, int budget, int32_t* out_len, hipStream_t s) {
+  MegaState& m = h->mega;
+  if (m.census < 0) {
+    // once per handle: are the engine's 256 workgroups co-resident on this device?  If not, a hand-off could wait
+    // for a workgroup that never starts: the launch-per-phase step is used instead (gsv_t2s_decode_info reports it)
+    const int rc = mega_census(s, m.err, m.h_err);
+    if (rc < 0) return rc;
+    m.census = rc;
+  }
+  if (m.census != 1) return MEGA_FELL_BACK;
+  GSV_HIP(hipMemsetAsync(m.hop, 0, m.hop_bytes, s));      // no tag survives a call (epochs are unique per launch as well: ep_base)
+  GSV_HIP(hipMemsetAsync(m.err, 0, 64, s));
+  // the row state as step 0 left it: if the launch ends in a hand-off timeout the batch is re-run from here on the
+  // launch-per-phase path (the engine only appends K/V behind kv_len and token history behind P_b + step: restoring the
+  // counters makes both invisible again; ybuf, the first step's input, is read-only for the engine; P_b and the RNG keys
+  // are read-only during a decode call)
+  const size_t mb = (size_t)h->max_batch;
+  GSV_HIP(hipMemcpyAsync(m.snap, h->d_kv_len, (3 * mb + 4) * 4, hipMemcpyDeviceToDevice, s));
+  GSV_HIP(hipMemcpyAsync(m.snap + 3 * mb + 4, out_len, h->B * 4, hipMemcpyDeviceToDevice, s));
+  MegaArgs a = mega_args(h, budget);
+  GSV_RC(mega_prof_arm(a, budget, s));
+  GSV_HIP(hipEventRecord(h->mega_ev[0], s));
+  GSV_RC(launch_t2s_mega(a, s));
+  GSV_HIP(hipEventRecord(h->mega_ev[1], s));
+  GSV_HIP(hipMemcpyAsync(m.h_err, m.err, 16, hipMemcpyDeviceToHost, s));
+  GSV_HIP(hipMemcpyAsync(h->h_pinned, h->d_step, 4, hipMemcpyDeviceToHost, s));
+  GSV_HIP(hipStreamSynchronize(s));
+  if (m.h_err[0] != 0u) {
+    // A hand-off timed out (a member was not running: another kernel held its CU, or a fault).  The request is not
+    // failed: the row state is restored to what step 0 left and THIS batch is re-run by the caller on the launch-per-phase
+    // path.  A transient cause (a foreign kernel held a CU) is given another chance: census again at the next call; three
+    // strikes disable the engine for the handle (census = 0, gsv_t2s_engine_stats reports it).
+    // GSV_MEGA_STRICT=1 restores the old behaviour (GSV_ERR_STATE) for tests of the error path.
+    set_error("t2s_decode: persistent engine hand-off timed out (epoch %u, workgroup %u, hop code 0x%x); the handle now uses "
+              "the launch-per-phase step (GSV_T2S_NO_MEGA=1 selects it from the start)", m.h_err[1], m.h_err[2], m.h_err[3]);
+    m.fallbacks += 1;
+    m.census = m.fallbacks >= 3 ? 0 : -1;
+    m.last_err[0] = m.h_err[1]; m.last_err[1] = m.h_err[2]; m.last_err[2] = m.h_err[3];
+    if (a.prof) (void)hipFree(a.prof);
+    if (getenv("GSV_MEGA_STRICT")) return GSV_ERR_STATE;
+    GSV_HIP(hipMemcpyAsync(h->d_kv_len, m.snap, (3 * mb + 4) * 4, hipMemcpyDeviceToDevice, s));
+    GSV_HIP(hipMemcpyAsync(out_len, m.snap + 3 * mb + 4, h->B * 4, hipMemcpyDeviceToDevice, s));
+    return MEGA_FELL_BACK;
+  }
+  (void)hipEventElapsedTime(&h->last_decode_ms, h->mega_ev[0], h->mega_ev[1]);
+  if (a.prof) GSV_RC(mega_prof_dump(a, h->last_decode_ms));
+  // every row ends by the budget's last step (early == step >= max_steps - 1); row 0's step counter tells how
+  // far the longest-running group got only for its own group, so report the budget like the launch loop does
+  h->last_decode_mode = 1; h->last_decode_steps = budget - 1;
+  return MEGA_DONE;
+}
+
+// Steps 1 .. budget - 1 one launch-per-phase step at a time: captured once per batch size and replayed; n_active is polled
+// every 8 steps so a batch whose rows have all finished stops early.  Returns the steps run, step 0 included, in *steps_run.
+template <typename T>
+int run_steps(gsv_t2s* h, int budget, int* steps_run, hipStream_t s) {
+  hipGraphExec_t exec = nullptr;
+  auto it = h->graphs.find(h->B);
+  if (it != h->graphs.end()) exec = it->second;
+  else if (s != nullptr && !getenv("GSV_T2S_NO_GRAPH") && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+    hipGraph_t graph;
+    int rc = launch_step<T>(h, s);
+    hipError_t e = hipStreamEndCapture(s, &graph);
+    if (rc) return rc;
+    GSV_HIP(e);
+    GSV_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+    (void)hipGraphDestroy(graph);
+    h->graphs[h->B] = exec;
+  } else {
+    (void)hipGetLastError();  // legacy default stream cannot capture: eager launches instead
+  }
+  const int check_every = 8;
+  int steps = 1;
+  while (steps < budget) {
+    if (exec) GSV_HIP(hipGraphLaunch(exec, s));
+    else GSV_RC(launch_step<T>(h, s));
+    ++steps;
+    if (steps % check_every == 0 || steps == budget) {
+      GSV_HIP(hipMemcpyAsync(h->h_pinned, h->d_n_active, 4, hipMemcpyDeviceToHost, s));
+      GSV_HIP(hipStreamSynchronize(s));
+      if (h->h_pinned[0] <= 0) break;
+    }
+  }
+  GSV_HIP(hipStreamSynchronize(s));
+  if (steps_run) *steps_run = steps;
+  return GSV_OK;
+}
+
+template <typename T>
+int decode(gsv_t2s* h, const gsv_sampling_params* sp, const float* noise, int noise_rows, int32_t* out_tokens, int32_t* out_len,
+           int* steps_run, hipStream_t s) {
+  const int budget = decode_begin(h, sp, noise, noise_rows, out_tokens, out_len, s);
+  if (budget < 0) return budget;
+  GSV_RC(launch_tail<T>(h, s));   // step 0: logits of the last prefill position, sample, emit the first embedding
+  h->last_decode_mode = 0; h->last_decode_ms = 0.f; h->last_decode_steps = 0;
+  if (h->mega.ready && h->mega_on && h->B <= MEGA_MAX_B && budget > 1) {
+    const int r = run_mega(h, budget, out_len, s);
+    if (r < 0) return r;
+    if (r == MEGA_DONE) {
+      if (steps_run) *steps_run = budget;
+      return GSV_OK;
+    }
+  }
+  return run_steps<T>(h, budget, steps_run, s);
+}
+
+// gsv_t2s_time_step: in-situ timing of the launch-per-phase step at the current cache state.  (a) The full per-layer kernel
+// sequence (QKV+append, attention, out-proj, FFN1, FFN2) is launched eagerly on the stream, 2 warm-up passes and then
+// `iters` passes between one event pair.  Rows are forced active for the measurement (finished rows skip attention) and
+// restored afterwards; no row state advances because the sampling tail is not launched.
+template <typename T>
+int time_step(gsv_t2s* h, int iters, float* step_ms, float* attn_ms, hipStream_t s) {
+  const int L = h->cfg.n_layer, B = h->B;
+  std::vector<int> saved(B), ones(B, 1);
+  GSV_HIP(hipMemcpy(saved.data(), h->d_active, B * 4, hipMemcpyDeviceToHost));
+  GSV_HIP(hipMemcpy(h->d_active, ones.data(), B * 4, hipMemcpyHostToDevice));
+  hipEvent_t ev[4];
+  for (auto& e : ev) GSV_HIP(hipEventCreate(&e));
+  int rc = GSV_OK;
+  for (int w = 0; w < 2 && !rc; ++w) rc = launch_decode_layers<T>(h, s, false);
+  GSV_HIP(hipEventRecord(ev[2], s));
+  for (int i = 0; i < iters && !rc; ++i) rc = launch_decode_layers<T>(h, s, false);
+  GSV_HIP(hipEventRecord(ev[3], s));
+  GSV_HIP(hipStreamSynchronize(s));
+  // (b) the attention kernel alone: iters x L launches back to back between ONE event pair (an event pair
+  // per launch adds ~3 us of its own); the L layers' arenas are distinct memory (L x bytes > Infinity Cache
+  // at the benchmark shape), so every launch streams its K/V from HBM like it does inside a step
+  float attn_total = 0.f;
+  if (!rc) {
+    GSV_HIP(hipEventRecord(ev[0], s));
+    for (int i = 0; i < iters && !rc; ++i) rc = launch_decode_layers<T>(h, s, true);
+    GSV_HIP(hipEventRecord(ev[1], s));
+    GSV_HIP(hipStreamSynchronize(s));
+    if (!rc) GSV_HIP(hipEventElapsedTime(&attn_total, ev[0], ev[1]));
+  }
+  GSV_HIP(hipMemcpy(h->d_active, saved.data(), B * 4, hipMemcpyHostToDevice));
+  if (!rc) {
+    if (attn_ms) *attn_ms = attn_total / (float)(iters * L);
+    float ms = 0.f;
+    GSV_HIP(hipEventElapsedTime(&ms, ev[2], ev[3]));
+    if (step_ms) *step_ms = ms / iters;
+  }
+  for (auto& e : ev) (void)hipEventDestroy(e);
+  return rc;
+}
 
 }  // namespace
 
@@ -1134,9 +911,9 @@ int gsv_t2s_create(const gsv_t2s_config* cfg, int dtype, int max_batch, int max_
               "t2s_create: dim must be 64/128/256/512/1024 with ffn_dim = 4*dim (got %d, %d)", cfg->dim, cfg->ffn_dim);
   GSV_REQUIRE(cfg->dim / cfg->n_head == 32, "t2s_create: head_dim must be 32 (got %d)", cfg->dim / cfg->n_head);
   GSV_REQUIRE(cfg->vocab <= 2048, "t2s_create: vocab %d > 2048", cfg->vocab);
-  GSV_REQUIRE(max_batch >= 1 && max_batch <= (dtype == GSV_F16 ? 128 : 64), "t2s_create: max_batch %d out of range", max_batch);
-  int n = 0;
-  GSV_HIP(hipGetDeviceCount(&n));
+  GSV_REQUIRE(max_batch >= 1 && max_batch <= (dtype == GSV_F32 ? 64 : 128), "t2s_create: max_batch %d out of range", max_batch);
+  int n_dev = 0;
+  GSV_HIP(hipGetDeviceCount(&n_dev));   // no usable device: refused here, not at the first upload
   gsv_t2s* h = new gsv_t2s();
   h->cfg = *cfg;
   h->dtype = dtype;
@@ -1268,305 +1045,6 @@ int gsv_t2s_finalize(gsv_t2s_t* h) {
   return GSV_OK;
 }
 
-}  // extern "C"
-
-static void* kv_ptr(gsv_t2s* h, int layer, int which) {
-  return (char*)h->kv + ((size_t)(layer * 2 + which) * h->kv_layer_stride) * esz(h);
-}
-
-// logits (LN2 prologue of the last layer) + sampling/state update
-static int launch_tail(gsv_t2s* h, hipStream_t s) {
-  const auto& c = h->cfg;
-  DecGemmArgs a;
-  memset(&a, 0, sizeof(a));
-  const LayerW& L = h->layers[c.n_layer - 1];
-  a.yin = h->ybuf; a.gamma = L.n2w; a.beta = L.n2b; a.w = h->pred_w; a.bias = nullptr;
-  a.B = h->B; a.K = c.dim; a.N = c.vocab; a.epi = EPI_LOGITS; a.out_f = h->logits;
-  int rc = h->dtype == GSV_F16 ? launch_dec_gemm<_Float16>(a, true, s) : launch_dec_gemm<float>(a, true, s);
-  if (rc) return rc;
-  const int V = c.vocab, EOS = c.vocab - 1;
-  const int npl = sample_npl(V);
-#define GSV_SAMPLE(N)                                                                                          \
-  hipLaunchKernelGGL(sample_step_kernel<N>, dim3(h->B), dim3(64), (size_t)((V + 15) & ~15), s, h->logits, V, EOS, h->d_sp, \
-                     h->d_ytok, h->ycap, h->d_kv_len, h->d_active, h->d_step, h->d_n_active, h->e_audio, h->pe,  \
-                     h->alpha_a, c.dim, h->ybuf)
-  if (npl == 2) GSV_SAMPLE(2);
-  else if (npl == 17) GSV_SAMPLE(17);
-  else GSV_SAMPLE(32);
-#undef GSV_SAMPLE
-  GSV_HIP(hipGetLastError());
-  return GSV_OK;
-}
-
-template <typename T, int KD>
-static bool launch_qkv_attn_kd(const QkvAttnArgs& q, hipStream_t s) {
-  if constexpr ((KD / Frag16<T>::KS) % 4 == 0) {
-    hipLaunchKernelGGL((dec_qkv_attn_kernel<T, 32, KD>), dim3(q.H, cdiv(q.B, 2)), dim3(256), 0, s, q);
-    return true;
-  } else {
-    return false;   // contraction too short to split over 4 waves: the caller uses the unfused kernels
-  }
-}
-
-template <typename T>
-static bool launch_qkv_attn(const QkvAttnArgs& q, hipStream_t s) {
-  switch (q.d) {
-    case 64: return launch_qkv_attn_kd<T, 64>(q, s);
-    case 128: return launch_qkv_attn_kd<T, 128>(q, s);
-    case 256: return launch_qkv_attn_kd<T, 256>(q, s);
-    case 512: return launch_qkv_attn_kd<T, 512>(q, s);
-    case 1024: return launch_qkv_attn_kd<T, 1024>(q, s);
-    default: return false;
-  }
-}
-
-template <typename T>
-static int launch_decode_layers(gsv_t2s* h, hipStream_t s, int only_attn, hipEvent_t* attn_ev = nullptr) {
-  const auto& c = h->cfg;
-  const int d = c.dim, H = c.n_head;
-  for (int li = 0; li < c.n_layer; ++li) {
-    const LayerW& L = h->layers[li];
-    // The fused LN+QKV+append+attention kernel is OPT-IN: measured on MI355X at B=32 it is slower than the
-    // two separate launches (153.3 vs 148.1 ms per bench step): one workgroup per CU has to pull 96 KB of
-    // weights plus 72 KB of K/V through a single CU's memory path and runs LN -> MFMA -> reduce -> softmax
-    // as one serial chain, whereas the split kernels spread the same bytes over 96 + 512 workgroups.
-    static const bool use_fuse = getenv("GSV_FUSED_QKV_ATTN") != nullptr;
-    bool fused = false;
-    if (!only_attn && use_fuse) {
-      QkvAttnArgs q;
-      memset(&q, 0, sizeof(q));
-      q.yin = h->ybuf;
-      if (li > 0) { q.gamma = h->layers[li - 1].n2w; q.beta = h->layers[li - 1].n2b; }
-      q.xres_out = h->xres; q.w = L.qkv_w; q.bias = L.qkv_b;
-      q.kc = kv_ptr(h, li, 0); q.vc = kv_ptr(h, li, 1); q.kv_len = h->d_kv_len; q.active = h->d_active;
-      q.out = h->abuf; q.B = h->B; q.d = d; q.H = H; q.smax = h->max_seq;
-      fused = launch_qkv_attn<T>(q, s);
-    }
-    if (fused) {
-    } else {
-    if (!only_attn) {
-      DecGemmArgs a;
-      memset(&a, 0, sizeof(a));
-      a.yin = h->ybuf;
-      if (li > 0) { a.gamma = h->layers[li - 1].n2w; a.beta = h->layers[li - 1].n2b; }
-      a.xres_out = h->xres;
-      a.w = L.qkv_w; a.bias = L.qkv_b; a.B = h->B; a.K = d; a.N = 3 * d; a.epi = EPI_QKV;
-      a.out_t = h->qbuf; a.kc = kv_ptr(h, li, 0); a.vc = kv_ptr(h, li, 1); a.kv_len = h->d_kv_len; a.active = h->d_active;
-      a.d = d; a.H = H; a.smax = h->max_seq;
-      GSV_RC(launch_dec_gemm<T>(a, true, s));
-    }
-    if (attn_ev) GSV_HIP(hipEventRecord(attn_ev[2 * li], s));
-    hipLaunchKernelGGL((decode_attn_kernel<T, 32>), dim3(H, h->B), dim3(256), 0, s, (const T*)h->qbuf,
-                       (const T*)kv_ptr(h, li, 0), (const T*)kv_ptr(h, li, 1), h->d_kv_len, h->d_active, H, h->max_seq,
-                       (T*)h->abuf);
-    if (attn_ev) GSV_HIP(hipEventRecord(attn_ev[2 * li + 1], s));
-    }
-    if (only_attn) continue;
-    {
-      DecGemmArgs a;
-      memset(&a, 0, sizeof(a));
-      a.xin = h->abuf; a.w = L.out_w; a.bias = L.out_b; a.B = h->B; a.K = d; a.N = d; a.epi = EPI_RESID;
-      a.out_f = h->ybuf; a.xres = h->xres;
-      GSV_RC(launch_dec_gemm<T>(a, false, s));
-    }
-    {
-      DecGemmArgs a;
-      memset(&a, 0, sizeof(a));
-      a.yin = h->ybuf; a.gamma = L.n1w; a.beta = L.n1b; a.xres_out = h->xres;
-      a.w = L.w1; a.bias = L.b1; a.B = h->B; a.K = d; a.N = c.ffn_dim; a.epi = EPI_RELU; a.out_t = h->hbuf;
-      GSV_RC(launch_dec_gemm<T>(a, true, s));
-    }
-    {
-      DecGemmArgs a;
-      memset(&a, 0, sizeof(a));
-      a.xin = h->hbuf; a.w = L.w2; a.bias = L.b2; a.B = h->B; a.K = c.ffn_dim; a.N = d; a.epi = EPI_RESID;
-      a.out_f = h->ybuf; a.xres = h->xres;
-      GSV_RC(launch_dec_gemm<T>(a, false, s));
-    }
-  }
-  GSV_HIP(hipGetLastError());
-  return GSV_OK;
-}
-
-static int launch_step(gsv_t2s* h, hipStream_t s) {
-  int rc = h->dtype == GSV_F16 ? launch_decode_layers<_Float16>(h, s, 0) : launch_decode_layers<float>(h, s, 0);
-  if (rc) return rc;
-  return launch_tail(h, s);
-}
-
-static int grow_prefill(gsv_t2s* h, size_t rows, size_t xrows) {
-  if (rows <= h->pf_rows) return GSV_OK;
-  const size_t d = h->cfg.dim, ff = h->cfg.ffn_dim, es = esz(h);
-  rows = (rows + 255) & ~(size_t)255;
-  // old buffers stay registered in allocs and are released at destroy; growth is rare
-  GSV_RC(dev_alloc(h, &h->pf_x, rows * d * es));
-  GSV_RC(dev_alloc(h, &h->pf_qkv, rows * 3 * d * es));
-  GSV_RC(dev_alloc(h, &h->pf_attn, rows * d * es));
-  GSV_RC(dev_alloc(h, &h->pf_h, rows * ff * es));
-  GSV_RC(dev_alloc(h, (void**)&h->pf_y, rows * d * 4));
-  GSV_RC(dev_alloc(h, (void**)&h->pf_bert, rows * d * 4));
-  GSV_RC(dev_alloc(h, &h->pf_bert_t, rows * (size_t)h->cfg.bert_dim * es));
-  h->pf_rows = rows;
-  (void)xrows;
-  return GSV_OK;
-}
-
-// Prefill of B rows with prompts of P_b = plen[b] tokens, packed back to back in `prompts` (device) from poff[b] on.
-// The uniform entry (every P_b = P, poff[b] = b P) and the ragged one share this body: the kernels read P_b per row either
-// way, so a uniform batch computes exactly what it computed when P was a kernel argument.
-static int t2s_prefill_rows(gsv_t2s* h, const int32_t* phones, const int32_t* phone_lens, int B, const float* bert,
-                            const int32_t* prompts, const int* plen, const int* poff, hipStream_t s) {
-  const auto& c = h->cfg;
-  const int d = c.dim, H = c.n_head;
-  std::vector<int> row_off(B), ph_off(B), kvl(B);
-  int M = 0, SX = 0, maxS = 0, maxP = 0;
-  for (int b = 0; b < B; ++b) {
-    GSV_REQUIRE(phone_lens[b] >= 1, "t2s_prefill: empty phoneme sequence in row %d", b);
-    row_off[b] = M; ph_off[b] = SX;
-    const int P = plen[b];
-    const int S = phone_lens[b] + P;
-    GSV_REQUIRE(S + 2 <= h->max_seq, "t2s_prefill: row %d needs %d positions, max_seq is %d", b, S + 2, h->max_seq);
-    GSV_REQUIRE(phone_lens[b] <= h->pe_rows, "t2s_prefill: sequence exceeds the position table");
-    GSV_REQUIRE(P <= h->pe_rows, "t2s_prefill: row %d's prompt of %d tokens exceeds the position table (%d rows)", b, P, h->pe_rows);
-    GSV_REQUIRE(P + 1 <= h->ycap, "t2s_prefill: row %d's prompt of %d tokens exceeds the token history (%d)", b, P, h->ycap);
-    kvl[b] = S; M += S; SX += phone_lens[b];
-    maxS = S > maxS ? S : maxS;
-    maxP = P > maxP ? P : maxP;
-  }
-  GSV_RC(grow_prefill(h, M, SX));
-  if (h->dtype == GSV_F16) {
-    const size_t need_vt = (size_t)B * H * 32 * ((maxS + 31) / 32 * 32) * 2;
-    if (need_vt > h->pf_vt_cap) { GSV_RC(dev_alloc(h, &h->pf_vt, need_vt + need_vt / 4)); h->pf_vt_cap = need_vt + need_vt / 4; }
-  }
-  h->B = B; h->P = maxP; h->max_kv0 = maxS;
-  GSV_HIP(hipMemcpyAsync(h->d_x_len, phone_lens, B * 4, hipMemcpyHostToDevice, s));
-  GSV_HIP(hipMemcpyAsync(h->d_row_off, row_off.data(), B * 4, hipMemcpyHostToDevice, s));
-  GSV_HIP(hipMemcpyAsync(h->d_ph_off, ph_off.data(), B * 4, hipMemcpyHostToDevice, s));
-  const int* d_plen = h->d_plen;
-  const int* d_poff = h->d_plen + h->max_batch;
-  std::vector<int> pl(2 * (size_t)h->max_batch, 0);
-  for (int b = 0; b < B; ++b) { pl[b] = plen[b]; pl[h->max_batch + b] = poff[b]; }
-  GSV_HIP(hipMemcpyAsync(h->d_plen, pl.data(), pl.size() * 4, hipMemcpyHostToDevice, s));
-  {
-    // row state [kv_len | active | step | n_active] is one block: one upload
-    const size_t mb = (size_t)h->max_batch;
-    std::vector<int> st(3 * mb + 4, 0);
-    for (int b = 0; b < B; ++b) { st[b] = kvl[b]; st[mb + b] = 1; }
-    st[3 * mb] = B;
-    GSV_HIP(hipMemcpyAsync(h->d_kv_len, st.data(), st.size() * 4, hipMemcpyHostToDevice, s));
-    GSV_HIP(hipStreamSynchronize(s));
-  }
-  if (maxP > 0) {
-    hipLaunchKernelGGL(prompt_copy_kernel, dim3(B), dim3(64), 0, s, prompts, d_plen, d_poff, h->ycap, h->d_ytok);
-    GSV_HIP(hipGetLastError());
-  }
-  GSV_HIP(hipStreamSynchronize(s));  // host vectors above go out of scope
-
-  const float* bertp = nullptr;
-  if (bert) {
-    GSV_RC(launch_convert(bert, h->pf_bert_t, h->dtype, (long long)SX * c.bert_dim, s));
-    ConvArgs g;
-    g.x = h->pf_bert_t; g.w = h->bert_w; g.bias = h->bert_b; g.y = h->pf_bert; g.out_f32 = 1;
-    g.T_in = SX; g.T_out = SX; g.T_virt = SX; g.Cin = c.bert_dim; g.Cout = d; g.ldx = c.bert_dim; g.ldw = c.bert_dim; g.ldy = d;
-    GSV_RC(launch_conv_gemm(h->dtype, g, s));
-    bertp = h->pf_bert;
-  }
-#define GSV_EMBED(T)                                                                                              \
-  hipLaunchKernelGGL(embed_prefill_kernel<T>, dim3(maxS, B), dim3(128), 0, s, phones, prompts, h->d_row_off, h->d_ph_off, \
-                     h->d_x_len, h->e_text, h->e_audio, bertp, h->bert_b, h->pe, h->alpha_t, h->alpha_a, d_plen, d_poff, d, \
-                     (T*)h->pf_x)
-  if (h->dtype == GSV_F16) GSV_EMBED(_Float16); else GSV_EMBED(float);
-#undef GSV_EMBED
-  GSV_HIP(hipGetLastError());
-
-  static const bool scalar_pf = getenv("GSV_SCALAR_PREFILL_ATTN") != nullptr;   // A/B switch: thread-per-query VALU kernel
-  static const bool split_scatter = getenv("GSV_PREFILL_SPLIT_SCATTER") != nullptr;   // A/B switch: K/V scatter and V^T as two launches
-  for (int li = 0; li < c.n_layer; ++li) {
-    const LayerW& L = h->layers[li];
-    ConvArgs g;
-    g.x = h->pf_x; g.w = L.qkv_w; g.bias = L.qkv_b; g.y = h->pf_qkv;
-    g.T_in = M; g.T_out = M; g.T_virt = M; g.Cin = d; g.Cout = 3 * d; g.ldx = d; g.ldw = d; g.ldy = 3 * d;
-    GSV_RC(launch_conv_gemm(h->dtype, g, s));
-    if (h->dtype == GSV_F16) {
-      const bool fused_kvt = d / H == 32 && !scalar_pf && !split_scatter;
-      if (!fused_kvt)
-        hipLaunchKernelGGL(kv_scatter_kernel<_Float16>, dim3(maxS, B), dim3(128), 0, s, (const _Float16*)h->pf_qkv,
-                           h->d_row_off, h->d_x_len, d_plen, d, H, h->max_seq, (_Float16*)kv_ptr(h, li, 0), (_Float16*)kv_ptr(h, li, 1));
-      if (d / H == 32 && !scalar_pf) {
-        const int spad = (maxS + 31) / 32 * 32;
-        if (fused_kvt)
-          hipLaunchKernelGGL(prefill_kvt_kernel, dim3(spad / 32, H, B), dim3(256), 0, s, (const _Float16*)h->pf_qkv, h->d_row_off,
-                             h->d_x_len, d_plen, d, H, h->max_seq, spad, (_Float16*)kv_ptr(h, li, 0), (_Float16*)kv_ptr(h, li, 1),
-                             (_Float16*)h->pf_vt);
-        else
-        hipLaunchKernelGGL(prefill_vt_kernel, dim3(spad / 32, H, B), dim3(256), 0, s, (const _Float16*)h->pf_qkv, h->d_row_off,
-                           h->d_x_len, d_plen, d, H, spad, (_Float16*)h->pf_vt);
-        hipLaunchKernelGGL(prefill_flash32_f16_kernel<4>, dim3(cdiv(maxS, 64), H, B), dim3(256), 0, s, (const _Float16*)h->pf_qkv,
-                           (const _Float16*)kv_ptr(h, li, 0), (const _Float16*)h->pf_vt, h->d_row_off, h->d_x_len, d_plen, d, H,
-                           h->max_seq, spad, (_Float16*)h->pf_attn);
-      } else
-      hipLaunchKernelGGL((prefill_attn_kernel<_Float16, 32>), dim3(cdiv(maxS, 64), H, B), dim3(64), 0, s,
-                         (const _Float16*)h->pf_qkv, (const _Float16*)kv_ptr(h, li, 0), (const _Float16*)kv_ptr(h, li, 1),
-                         h->d_row_off, h->d_x_len, d_plen, d, H, h->max_seq, (_Float16*)h->pf_attn);
-    } else {
-      hipLaunchKernelGGL(kv_scatter_kernel<float>, dim3(maxS, B), dim3(128), 0, s, (const float*)h->pf_qkv, h->d_row_off,
-                         h->d_x_len, d_plen, d, H, h->max_seq, (float*)kv_ptr(h, li, 0), (float*)kv_ptr(h, li, 1));
-      hipLaunchKernelGGL((prefill_attn_kernel<float, 32>), dim3(cdiv(maxS, 64), H, B), dim3(64), 0, s,
-                         (const float*)h->pf_qkv, (const float*)kv_ptr(h, li, 0), (const float*)kv_ptr(h, li, 1),
-                         h->d_row_off, h->d_x_len, d_plen, d, H, h->max_seq, (float*)h->pf_attn);
-    }
-    GSV_HIP(hipGetLastError());
-    // y1 = attn Wo^T + bo + x  (fp32) ; x1 = LN1(y1)
-    ConvArgs o;
-    o.x = h->pf_attn; o.w = L.out_w; o.bias = L.out_b; o.y = h->pf_y; o.out_f32 = 1; o.res = h->pf_x; o.res_f32 = 0;
-    o.T_in = M; o.T_out = M; o.T_virt = M; o.Cin = d; o.Cout = d; o.ldx = d; o.ldw = d; o.ldy = d; o.ldr = d;
-    GSV_RC(launch_conv_gemm(h->dtype, o, s));
-    GSV_RC(launch_layernorm(h->dtype, h->pf_y, 1, nullptr, 0, L.n1w, L.n1b, h->pf_x, 0, M, d, 1e-5f, s));
-    ConvArgs f1;
-    f1.x = h->pf_x; f1.w = L.w1; f1.bias = L.b1; f1.y = h->pf_h; f1.post_act = ACT_RELU;
-    f1.T_in = M; f1.T_out = M; f1.T_virt = M; f1.Cin = d; f1.Cout = c.ffn_dim; f1.ldx = d; f1.ldw = d; f1.ldy = c.ffn_dim;
-    GSV_RC(launch_conv_gemm(h->dtype, f1, s));
-    ConvArgs f2;
-    f2.x = h->pf_h; f2.w = L.w2; f2.bias = L.b2; f2.y = h->pf_y; f2.out_f32 = 1; f2.res = h->pf_x; f2.res_f32 = 0;
-    f2.T_in = M; f2.T_out = M; f2.T_virt = M; f2.Cin = c.ffn_dim; f2.Cout = d; f2.ldx = c.ffn_dim; f2.ldw = c.ffn_dim;
-    f2.ldy = d; f2.ldr = d;
-    GSV_RC(launch_conv_gemm(h->dtype, f2, s));
-    if (li + 1 < c.n_layer)
-      GSV_RC(launch_layernorm(h->dtype, h->pf_y, 1, nullptr, 0, L.n2w, L.n2b, h->pf_x, 0, M, d, 1e-5f, s));
-  }
-  hipLaunchKernelGGL(gather_last_kernel, dim3(B), dim3(128), 0, s, h->pf_y, h->d_row_off, h->d_x_len, d_plen, d, h->ybuf);
-  GSV_HIP(hipGetLastError());
-  return GSV_OK;
-}
-
-extern "C" {
-
-int gsv_t2s_prefill(gsv_t2s_t* h, const int32_t* phones, const int32_t* phone_lens, int B, const float* bert,
-                    const int32_t* prompts, int P, gsv_stream_t stream) {
-  GSV_REQUIRE(h && h->finalized, "t2s_prefill: handle not finalized");
-  GSV_REQUIRE(phones && phone_lens && (prompts || P == 0), "t2s_prefill: null argument");
-  GSV_REQUIRE(B >= 1 && B <= h->max_batch, "t2s_prefill: batch %d exceeds max_batch %d", B, h->max_batch);
-  GSV_REQUIRE(P >= 0, "t2s_prefill: negative prompt length %d", P);   // P == 0: prompt-free decode (t2s_model.py:849-856)
-  std::vector<int> plen(B, P), poff(B);
-  for (int b = 0; b < B; ++b) poff[b] = b * P;
-  return t2s_prefill_rows(h, phones, phone_lens, B, bert, prompts, plen.data(), poff.data(), (hipStream_t)stream);
-}
-
-int gsv_t2s_prefill_ragged(gsv_t2s_t* h, const int32_t* phones, const int32_t* phone_lens, int B, const float* bert,
-                           const int32_t* prompts_packed, const int32_t* prompt_lens, gsv_stream_t stream) {
-  GSV_REQUIRE(h && h->finalized, "t2s_prefill_ragged: handle not finalized");
-  GSV_REQUIRE(phones && phone_lens && prompts_packed && prompt_lens, "t2s_prefill_ragged: null argument");
-  GSV_REQUIRE(B >= 1 && B <= h->max_batch, "t2s_prefill_ragged: batch %d exceeds max_batch %d", B, h->max_batch);
-  std::vector<int> poff(B);
-  int o = 0;
-  for (int b = 0; b < B; ++b) {
-    // prompt-free rows keep the uniform entry (P = 0 there also masks EOS for 11 steps: t2s_model.py:849-856)
-    GSV_REQUIRE(prompt_lens[b] >= 1, "t2s_prefill_ragged: row %d has prompt length %d (must be >= 1)", b, prompt_lens[b]);
-    poff[b] = o; o += prompt_lens[b];
-  }
-  return t2s_prefill_rows(h, phones, phone_lens, B, bert, prompts_packed, prompt_lens, poff.data(), (hipStream_t)stream);
-}
-
 int gsv_t2s_set_row_rng(gsv_t2s_t* h, const uint64_t* seeds, const int32_t* rows, int B) {
   GSV_REQUIRE(h && h->finalized, "t2s_set_row_rng: handle not finalized");
   GSV_REQUIRE(seeds && rows && B >= 1 && B <= h->max_batch, "t2s_set_row_rng: bad argument (B = %d)", B);
@@ -1581,183 +1059,7 @@ int gsv_t2s_decode(gsv_t2s_t* h, const gsv_sampling_params* sp, const float* noi
   GSV_REQUIRE(sp && out_tokens && out_len, "t2s_decode: null argument");
   GSV_REQUIRE(sp->max_steps >= 1, "t2s_decode: max_steps must be >= 1");
   GSV_REQUIRE(noise == nullptr || noise_rows == 1 || noise_rows == h->B, "t2s_decode: noise_rows must be 1 or B");
-  hipStream_t s = (hipStream_t)stream;
-  StepParams p;
-  p.top_k = sp->top_k; p.top_p = sp->top_p; p.temperature = sp->temperature; p.rep_penalty = sp->repetition_penalty;
-  p.early_stop_num = sp->early_stop_num; p.eos_mask_steps = sp->eos_mask_steps; p.max_steps = sp->max_steps;
-  p.noise_rows = noise ? noise_rows : 0; p.seed = sp->seed; p.noise = noise; p.out_tokens = out_tokens; p.out_len = out_len;
-  p.plen = h->d_plen; p.rng_seed = h->d_rng_seed; p.rng_row = h->d_rng_row;
-  p.force = h->dbg_force; p.dump = h->dbg_dump; p.drawn = h->dbg_drawn;
-  h->dbg_force = nullptr; h->dbg_dump = nullptr; h->dbg_drawn = nullptr;
-  // counter-RNG keys of the rows: gsv_t2s_set_row_rng's for this call, else (seed, b) -- the draws of a batch without keys
-  const bool keyed = !h->rng_seed_next.empty();
-  const int nkeys = (int)h->rng_seed_next.size();
-  std::vector<unsigned long long> seeds(h->B);
-  std::vector<int> rows(h->B);
-  for (int b = 0; b < h->B && (!keyed || nkeys == h->B); ++b) {
-    seeds[b] = keyed ? h->rng_seed_next[b] : (unsigned long long)sp->seed;
-    rows[b] = keyed ? h->rng_row_next[b] : b;
-  }
-  h->rng_seed_next.clear(); h->rng_row_next.clear();
-  GSV_REQUIRE(!keyed || nkeys == h->B, "t2s_decode: gsv_t2s_set_row_rng gave %d keys for a batch of %d rows", nkeys, h->B);
-  GSV_HIP(hipMemcpyAsync(h->d_sp, &p, sizeof(p), hipMemcpyHostToDevice, s));
-  if (seeds != h->rng_seed_up || rows != h->rng_row_up) {
-    GSV_HIP(hipMemcpyAsync(h->d_rng_seed, seeds.data(), (size_t)h->B * 8, hipMemcpyHostToDevice, s));
-    GSV_HIP(hipMemcpyAsync(h->d_rng_row, rows.data(), (size_t)h->B * 4, hipMemcpyHostToDevice, s));
-    h->rng_seed_up = seeds; h->rng_row_up = rows;
-  }
-  GSV_HIP(hipStreamSynchronize(s));
-  // budget: step 0 samples from the prefill's last position, every later step appends one K/V position, so the
-  // longest row ends at max_kv0 + budget - 1 cached positions; the sampling tail of row b reads pe[P_b + step] and writes
-  // token history [P_b + step] (h->P is the longest prompt).  A request that does not fit is refused here: the kernels clamp out-of-range
-  // appends, which would otherwise yield silently wrong tokens with rc 0.
-  int budget = sp->max_steps;
-  if (sp->early_stop_num >= 0 && sp->early_stop_num + 1 < budget) budget = sp->early_stop_num + 1;
-  GSV_REQUIRE(h->max_kv0 + budget <= h->max_seq,
-              "t2s_decode: %d cached positions + %d steps exceed the K/V arena (max_seq %d); lower max_steps / early_stop_num "
-              "or create the engine with a larger max_seq", h->max_kv0, budget, h->max_seq);
-  GSV_REQUIRE(h->P + budget <= h->pe_rows, "t2s_decode: prompt %d + %d steps exceed the position table (%d rows)", h->P, budget,
-              h->pe_rows);
-  GSV_REQUIRE(h->P + budget <= h->ycap, "t2s_decode: prompt %d + %d steps exceed the token history (%d)", h->P, budget, h->ycap);
-  // step 0: logits of the last prefill position, sample, emit first embedding
-  GSV_RC(launch_tail(h, s));
-  int steps = 1;
-  h->last_decode_mode = 0; h->last_decode_ms = 0.f; h->last_decode_steps = 0;
-  if (h->mega.ready && h->mega_on && h->B <= MEGA_MAX_B && budget > 1) {
-    MegaState& m = h->mega;
-    if (m.census < 0) {
-      // once per handle: are the engine's 256 workgroups co-resident on this device?  If not, a hand-off could wait
-      // for a workgroup that never starts: the launch-per-phase step is used instead (gsv_t2s_decode_info reports it)
-      const int rc = mega_census(s, m.err, m.h_err);
-      if (rc < 0) return rc;
-      m.census = rc;
-    }
-    if (m.census == 1) {
-      static const bool map_local = getenv("GSV_MEGA_GROUP_XCD") != nullptr;
-      GSV_HIP(hipMemsetAsync(m.hop, 0, m.hop_bytes, s));      // no tag survives a call (epochs are unique per launch as well: ep_base)
-      GSV_HIP(hipMemsetAsync(m.err, 0, 64, s));
-      // the row state as step 0 left it: if the launch ends in a hand-off timeout the batch is re-run from here on the
-      // launch-per-phase path (the engine only appends K/V behind kv_len and token history behind P_b + step: restoring the
-      // counters makes both invisible again; ybuf, the first step's input, is read-only for the engine; P_b and the RNG keys
-      // are read-only during a decode call)
-      const size_t mb = (size_t)h->max_batch;
-      GSV_HIP(hipMemcpyAsync(m.snap, h->d_kv_len, (3 * mb + 4) * 4, hipMemcpyDeviceToDevice, s));
-      GSV_HIP(hipMemcpyAsync(m.snap + 3 * mb + 4, out_len, h->B * 4, hipMemcpyDeviceToDevice, s));
-      MegaArgs a;
-      memset(&a, 0, sizeof(a));
-      a.wpack = (const h8*)m.wpack; a.lpack = (const h8*)m.lpack; a.fpack = m.fpack;
-      a.kv = (_Float16*)h->kv; a.kv_layer_stride = h->kv_layer_stride; a.smax = h->max_seq;
-      a.kv_len = h->d_kv_len; a.active = h->d_active; a.step_ctr = h->d_step; a.n_active = h->d_n_active;
-      a.ytok = h->d_ytok; a.ycap = h->ycap; a.sp = h->d_sp; a.e_audio = h->e_audio; a.pe = h->pe; a.alpha_a = h->alpha_a;
-      a.ybuf = h->ybuf; a.logits_out = h->logits; a.hop = m.hop; a.err = m.err; a.B = h->B; a.L = h->cfg.n_layer; a.V = h->cfg.vocab;
-      static const int map_mode = getenv("GSV_MEGA_MAP") ? atoi(getenv("GSV_MEGA_MAP")) : 2;   // 2: roles by the XCD a workgroup runs on, 1: by blockIdx % 8
-      a.nsteps = budget - 1; a.map_shared = map_local ? 0 : map_mode;
-      // bits 0-3: hops (A, B, C, D) that poll one granule per line first; bits 8-12: 16ths of the lines that may still be
-      // missing when the full passes start
-      // bits 0-3: hops A-D poll ONE hint line before the full pass (hop B, 2 KB per row, is faster polled in full: 288 -> 284 us
-      // per step); bit 7: every member polls ANOTHER publisher's line instead of all 32 polling the row's last line (297 -> 288
-      // us); bits 8-12: miss threshold of sweep2's per-line hints (logits hop).  Measured and left off: bit 4 (sweep2: two polls
-      // in flight, 3 % slower), bit 5 (payload through L2, needs GSV_MEGA_RING > 1: no gain).  Tried in sweep_wide and removed
-      // again: several hint lines per row, polls in flight, one polling wave per workgroup, a slower pace, a wait before the
-      // first poll (+1 to +9 %, profiles/r03_ab_hint_spread.txt) -- the knobs themselves cost 2 % in scalar registers
-      static const int hint_mask = getenv("GSV_MEGA_HINT") ? atoi(getenv("GSV_MEGA_HINT")) : (13 | (1 << 7) | (2 << 8));
-      a.hint_mask = hint_mask;
-      a.ring = m.ring;
-      m.launch_gen = (m.launch_gen + 1) & 2047;
-      a.ep_base = m.launch_gen << 20;                       // 1500 steps x 98 hops < 2^20
-      a.test_stall = h->dbg_stall; h->dbg_stall = 0;        // tests only (gsv_t2s_debug_stall): this launch loses one publish
-      // measurement runs: GSV_MEGA_PROF=<file> dumps in-kernel shader-clock stamps of one (step, layer) for every wave
-      const char* prof_path = getenv("GSV_MEGA_PROF");
-      unsigned long long* d_prof = nullptr;
-      const size_t prof_n = (size_t)256 * 8 * 32;
-      if (prof_path && budget > 8) {
-        GSV_HIP(hipMalloc((void**)&d_prof, prof_n * 8));
-        GSV_HIP(hipMemsetAsync(d_prof, 0, prof_n * 8, s));
-        a.prof = d_prof; a.prof_step = getenv("GSV_MEGA_PROF_STEP") ? atoi(getenv("GSV_MEGA_PROF_STEP")) : 5;
-        a.prof_layer = getenv("GSV_MEGA_PROF_LAYER") ? atoi(getenv("GSV_MEGA_PROF_LAYER")) : 7;
-        a.prof_quad = getenv("GSV_MEGA_PROF_QUAD") ? atoi(getenv("GSV_MEGA_PROF_QUAD")) : 0;
-      }
-      GSV_HIP(hipEventRecord(h->mega_ev[0], s));
-      GSV_RC(launch_t2s_mega(a, s));
-      GSV_HIP(hipEventRecord(h->mega_ev[1], s));
-      GSV_HIP(hipMemcpyAsync(m.h_err, m.err, 16, hipMemcpyDeviceToHost, s));
-      GSV_HIP(hipMemcpyAsync(h->h_pinned, h->d_step, 4, hipMemcpyDeviceToHost, s));
-      GSV_HIP(hipStreamSynchronize(s));
-      bool engine_ok = true;
-      if (m.h_err[0] != 0u) {
-        // A hand-off timed out (a member was not running: another kernel held its CU, or a fault).  The request is not
-        // failed: the row state is restored to what step 0 left, the handle stops using the engine (census = 0: later calls
-        // take the launch-per-phase step, gsv_t2s_engine_stats reports it) and THIS batch is re-run below on that path.
-        // GSV_MEGA_STRICT=1 restores the old behaviour (GSV_ERR_STATE) for tests of the error path.
-        set_error("t2s_decode: persistent engine hand-off timed out (epoch %u, workgroup %u, hop code 0x%x); the handle now uses "
-                  "the launch-per-phase step (GSV_T2S_NO_MEGA=1 selects it from the start)", m.h_err[1], m.h_err[2], m.h_err[3]);
-        m.fallbacks += 1;
-        m.census = m.fallbacks >= 3 ? 0 : -1;     // a transient cause (a foreign kernel held a CU): census again at the next call; three strikes disable the engine
-        m.last_err[0] = m.h_err[1]; m.last_err[1] = m.h_err[2]; m.last_err[2] = m.h_err[3];
-        if (d_prof) (void)hipFree(d_prof);
-        if (getenv("GSV_MEGA_STRICT")) return GSV_ERR_STATE;
-        GSV_HIP(hipMemcpyAsync(h->d_kv_len, m.snap, (3 * mb + 4) * 4, hipMemcpyDeviceToDevice, s));
-        GSV_HIP(hipMemcpyAsync(out_len, m.snap + 3 * mb + 4, h->B * 4, hipMemcpyDeviceToDevice, s));
-        engine_ok = false;
-      }
-      if (engine_ok) {
-      (void)hipEventElapsedTime(&h->last_decode_ms, h->mega_ev[0], h->mega_ev[1]);
-      if (d_prof) {
-        std::vector<unsigned long long> hp(prof_n);
-        GSV_HIP(hipMemcpy(hp.data(), d_prof, prof_n * 8, hipMemcpyDeviceToHost));
-        (void)hipFree(d_prof);
-        if (FILE* f = fopen(prof_path, "w")) {
-          fprintf(f, "# decode %.3f ms for %d steps; stamps of step %d layer %d: wg wave stamp0 then deltas to stamp0\n",
-                  h->last_decode_ms, budget - 1, a.prof_step, a.prof_layer);
-          for (int wg = 0; wg < 256; ++wg)
-            for (int w = 0; w < 8; ++w) {
-              const unsigned long long* p = &hp[((size_t)wg * 8 + w) * 32];
-              if (!p[0]) continue;
-              fprintf(f, "%d %d %llu", wg, w, p[0]);
-              for (int i = 1; i < 24; ++i) fprintf(f, " %lld", p[i] ? (long long)(p[i] - p[0]) : -1ll);
-              fprintf(f, "\n");
-            }
-          fclose(f);
-        }
-      }
-      // every row ends by the budget's last step (early == step >= max_steps - 1); row 0's step counter tells how
-      // far the longest-running group got only for its own group, so report the budget like the launch loop does
-      h->last_decode_mode = 1; h->last_decode_steps = budget - 1;
-      if (steps_run) *steps_run = budget;
-      return GSV_OK;
-      }   // engine_ok
-    }
-  }
-  // steps >= 1 : captured once per batch size, replayed
-  hipGraphExec_t exec = nullptr;
-  auto it = h->graphs.find(h->B);
-  if (it != h->graphs.end()) exec = it->second;
-  else if (s != nullptr && !getenv("GSV_T2S_NO_GRAPH") && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-    hipGraph_t graph;
-    int rc = launch_step(h, s);
-    hipError_t e = hipStreamEndCapture(s, &graph);
-    if (rc) return rc;
-    GSV_HIP(e);
-    GSV_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(graph);
-    h->graphs[h->B] = exec;
-  } else {
-    (void)hipGetLastError();  // legacy default stream cannot capture: eager launches instead
-  }
-  const int check_every = 8;
-  while (steps < budget) {
-    if (exec) GSV_HIP(hipGraphLaunch(exec, s));
-    else GSV_RC(launch_step(h, s));
-    ++steps;
-    if (steps % check_every == 0 || steps == budget) {
-      GSV_HIP(hipMemcpyAsync(h->h_pinned, h->d_n_active, 4, hipMemcpyDeviceToHost, s));
-      GSV_HIP(hipStreamSynchronize(s));
-      if (h->h_pinned[0] <= 0) break;
-    }
-  }
-  GSV_HIP(hipStreamSynchronize(s));
-  if (steps_run) *steps_run = steps;
-  return GSV_OK;
+  return GSV_WITH_T(h, decode<T>(h, sp, noise, noise_rows, out_tokens, out_len, steps_run, (hipStream_t)stream));
 }
 
 int gsv_t2s_set_mega(gsv_t2s_t* h, int on) {
@@ -1818,49 +1120,8 @@ int64_t gsv_t2s_step_bytes(gsv_t2s_t* h, int64_t* attn_bytes) {
 }
 
 int gsv_t2s_time_step(gsv_t2s_t* h, int iters, float* step_ms, float* attn_ms, gsv_stream_t stream) {
-  // In-situ timing of the decode step at the current cache state: the full per-layer kernel
-  // sequence (QKV+append, attention, out-proj, FFN1, FFN2) is launched eagerly on `stream` with a
-  // HIP event pair around every decode-attention launch, so each attention launch runs behind its
-  // producer and in front of its consumer exactly as in the replayed graph.  Rows are forced
-  // active for the measurement (finished rows skip attention) and restored afterwards; no row
-  // state advances because the sampling tail is not launched.
   GSV_REQUIRE(h && h->finalized && h->B > 0 && iters > 0, "t2s_time_step: bad state");
-  hipStream_t s = (hipStream_t)stream;
-  const int L = h->cfg.n_layer, B = h->B;
-  std::vector<int> saved(B), ones(B, 1);
-  GSV_HIP(hipMemcpy(saved.data(), h->d_active, B * 4, hipMemcpyDeviceToHost));
-  GSV_HIP(hipMemcpy(h->d_active, ones.data(), B * 4, hipMemcpyHostToDevice));
-  std::vector<hipEvent_t> ev((size_t)iters * 2 * L + 2);
-  for (auto& e : ev) GSV_HIP(hipEventCreate(&e));
-  int rc = GSV_OK;
-  for (int w = 0; w < 2 && !rc; ++w)
-    rc = h->dtype == GSV_F16 ? launch_decode_layers<_Float16>(h, s, 0) : launch_decode_layers<float>(h, s, 0);
-  GSV_HIP(hipEventRecord(ev[(size_t)iters * 2 * L], s));
-  for (int i = 0; i < iters && !rc; ++i)
-    rc = h->dtype == GSV_F16 ? launch_decode_layers<_Float16>(h, s, 0) : launch_decode_layers<float>(h, s, 0);
-  GSV_HIP(hipEventRecord(ev[(size_t)iters * 2 * L + 1], s));
-  GSV_HIP(hipStreamSynchronize(s));
-  // (b) the attention kernel alone: iters x L launches back to back between ONE event pair (an event pair
-  // per launch adds ~3 us of its own); the L layers' arenas are distinct memory (L x bytes > Infinity Cache
-  // at the benchmark shape), so every launch streams its K/V from HBM like it does inside a step
-  float attn_total = 0.f;
-  if (!rc) {
-    GSV_HIP(hipEventRecord(ev[0], s));
-    for (int i = 0; i < iters && !rc; ++i)
-      rc = h->dtype == GSV_F16 ? launch_decode_layers<_Float16>(h, s, 1) : launch_decode_layers<float>(h, s, 1);
-    GSV_HIP(hipEventRecord(ev[1], s));
-    GSV_HIP(hipStreamSynchronize(s));
-    if (!rc) GSV_HIP(hipEventElapsedTime(&attn_total, ev[0], ev[1]));
-  }
-  GSV_HIP(hipMemcpy(h->d_active, saved.data(), B * 4, hipMemcpyHostToDevice));
-  if (!rc) {
-    if (attn_ms) *attn_ms = attn_total / (float)(iters * L);
-    float ms = 0.f;
-    GSV_HIP(hipEventElapsedTime(&ms, ev[(size_t)iters * 2 * L], ev[(size_t)iters * 2 * L + 1]));
-    if (step_ms) *step_ms = ms / iters;
-  }
-  for (auto& e : ev) (void)hipEventDestroy(e);
-  return rc;
+  return GSV_WITH_T(h, time_step<T>(h, iters, step_ms, attn_ms, (hipStream_t)stream));
 }
 
 int gsv_t2s_debug_set_state(gsv_t2s_t* h, int B, int kv_len) {
@@ -1883,15 +1144,7 @@ int gsv_op_decode_attn(const void* q, const void* kc, const void* vc, const int3
   GSV_REQUIRE(q && kc && vc && kv_len && active && out, "op_decode_attn: null pointer");
   GSV_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && smax >= 1, "op_decode_attn: bad shape B=%d H=%d smax=%d", B, H, smax);
   GSV_REQUIRE(dtype == GSV_F16 || dtype == GSV_F32, "op_decode_attn: bad dtype %d", dtype);
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == GSV_F16)
-    hipLaunchKernelGGL((decode_attn_kernel<_Float16, 32>), dim3(H, B), dim3(256), 0, s, (const _Float16*)q, (const _Float16*)kc,
-                       (const _Float16*)vc, kv_len, active, H, smax, (_Float16*)out);
-  else
-    hipLaunchKernelGGL((decode_attn_kernel<float, 32>), dim3(H, B), dim3(256), 0, s, (const float*)q, (const float*)kc,
-                       (const float*)vc, kv_len, active, H, smax, (float*)out);
-  GSV_HIP(hipGetLastError());
-  return GSV_OK;
+  return GSV_WITH_DTYPE(dtype, launch_decode_attn<T>(q, kc, vc, kv_len, active, B, H, smax, out, (hipStream_t)stream));
 }
 
 int gsv_op_sample(const float* logits, int B, int vocab, int vocab_eff, const int32_t* prev, int prev_len,
@@ -1900,18 +1153,13 @@ int gsv_op_sample(const float* logits, int B, int vocab, int vocab_eff, const in
   GSV_REQUIRE(logits && sp && sampled && argmax_tok && B > 0, "op_sample: null argument");
   GSV_REQUIRE(vocab <= 2048 && vocab_eff <= vocab, "op_sample: vocab too large");
   hipStream_t s = (hipStream_t)stream;
-  const int npl = sample_npl(vocab);
   const size_t lds = (size_t)((vocab + 15) & ~15);
-#define GSV_SO(N)                                                                                                   \
-  hipLaunchKernelGGL(sample_only_kernel<N>, dim3(B), dim3(64), lds, s, logits, vocab, vocab_eff, prev, prev_len, sp->top_k, \
-                     sp->top_p, sp->temperature, sp->repetition_penalty, noise, (unsigned long long)sp->seed, step, sampled, \
-                     argmax_tok)
-  if (npl == 2) GSV_SO(2);
-  else if (npl == 17) GSV_SO(17);
-  else GSV_SO(32);
-#undef GSV_SO
-  GSV_HIP(hipGetLastError());
-  return GSV_OK;
+  return with_npl(vocab, [&](auto npl) -> int {
+    GSV_LAUNCH(sample_only_kernel<decltype(npl)::value>, dim3(B), dim3(64), lds, s, logits, vocab, vocab_eff, prev, prev_len,
+               sp->top_k, sp->top_p, sp->temperature, sp->repetition_penalty, noise, (unsigned long long)sp->seed, step, sampled,
+               argmax_tok);
+    return GSV_OK;
+  });
 }
 
 }  // extern "C"

@@ -3,7 +3,7 @@
 //
 // Layout: one utterance at a time, every activation channels-last [frame][channel] in the engine dtype,
 // the Euler state x and the velocity in fp32.  Every Linear / conv is one call of the MFMA GEMM / implicit-GEMM
-// kernels (conv_lds.hip / conv_gemm.hip); the grouped position conv is a Z=16 batched implicit GEMM.
+// kernels (gemm_lds.hip / conv_lds.hip / conv_gemm.hip); the grouped position conv is a Z=16 batched implicit GEMM.
 // Everything that depends only on the step index is hoisted out of the Euler loop: the time embeddings of all
 // n steps are computed at once and pushed through every block's AdaLN-Zero modulation Linear as ONE [n][dim] x
 // [dim][6 dim] GEMM per block (the reference re-reads those 22 x 6 dim x dim weights as a GEMV every step);

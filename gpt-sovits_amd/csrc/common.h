@@ -214,13 +214,8 @@ void set_conv_route(unsigned long long code);
 int launch_seg_rows(int dtype, int out_f32, void* y, int ldy, int col0, int C, int rows, const int* row_seg, const float* tab, int ldb,
                     hipStream_t s);
 
+// picks the kernel for the shape (conv_gemm.hip; the kernels it chooses from are declared in conv_launch.h)
 int launch_conv_gemm(int dtype, const ConvArgs& a, hipStream_t s);
-// split-K-in-workgroup streaming GEMM for under-filled grids (gemm_sk.hip): 0 = launched, 1 = not eligible, <0 = error
-int launch_gemm_sk(int dtype, const ConvArgs& a, hipStream_t s);
-// LDS-staged variant for stride-1 convs (conv_lds.hip): 0 = launched, 1 = not eligible, <0 = error
-int launch_conv_lds(int dtype, const ConvArgs& a, hipStream_t s);
-// persistent 128-channel tile convolution (conv_wide.hip): 1 = not eligible, 0 = launched, < 0 error
-int launch_conv_wide(int dtype, const ConvArgs& a, hipStream_t s);
 
 // fused ResBlock pair of the generator's narrow stages (conv_pair.hip): y = (convs2(lrelu(convs1(lrelu(x)))) + x) * scale [+ y]
 struct ConvPairArgs {

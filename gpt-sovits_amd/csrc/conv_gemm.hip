@@ -11,11 +11,7 @@
 // into the channels-last output.  fp16 uses v_mfma_f32_32x32x16_f16 (fp32 accumulate);
 // fp32 uses the exact-f32 v_mfma_f32_32x32x2_f32 with a permuted k order so that both
 // operands are still fetched as 16-byte contiguous chunks.
-#include <stdlib.h>
-
-#include <stdio.h>
-
-#include "common.h"
+#include "conv_launch.h"
 
 namespace gsv {
 
@@ -177,9 +173,9 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(ConvArgs a) {
   }
 }
 
-static long long small_tiles_below() {
-  static const long long v = getenv("GSV_CONV_GEMM_SMALL_TILES") ? atoll(getenv("GSV_CONV_GEMM_SMALL_TILES")) : 64;   // A/B switch (0 = off)
-  return v;
+template <typename T, int TM, int TN, int WM, int WN> static int launch_direct(const ConvArgs& a, hipStream_t s) {
+  const dim3 grid(cdiv(a.T_virt, WN * TN * 32), cdiv(a.Cout, WM * TM * 32), a.Z);
+  return launch_routed<conv_gemm_kernel<T, TM, TN, WM, WN>, 0>(route_code(ROUTE_CONV_GEMM, DT<T>::id, TM, TN, WM, WN), grid, dim3(WM * WN * 64), 0, s, a);
 }
 
 template <typename T> static int launch_t(const ConvArgs& a, hipStream_t s) {
@@ -189,32 +185,17 @@ template <typename T> static int launch_t(const ConvArgs& a, hipStream_t s) {
   GSV_REQUIRE(a.ldw >= a.taps * a.Cin, "conv_gemm: ldw too small");
   GSV_REQUIRE(((uintptr_t)a.x % 16) == 0 && ((uintptr_t)a.w % 16) == 0, "conv_gemm: x/w must be 16-byte aligned");
   GSV_REQUIRE(a.T_virt > 0 && a.Cout > 0 && a.Z > 0, "conv_gemm: empty problem");
-  if (a.Cout <= 32) {
-    dim3 grid(cdiv(a.T_virt, 512), cdiv(a.Cout, 32), a.Z);
-    set_conv_route(route_code(ROUTE_CONV_GEMM, DT<T>::id, 1, 4, 1, 4));
-    hipLaunchKernelGGL((conv_gemm_kernel<T, 1, 4, 1, 4>), grid, dim3(256), 0, s, a);
-  } else if (a.Cout <= 64 && (long long)cdiv(a.T_virt, 256) * a.Z < 192) {
+  // workgroup tile (channels x time steps): 32 x 512, 64 x 256 or 128 x 128 by Cout, and 64 x 64 where those leave the chip idle
+  if (a.Cout <= 32) return launch_direct<T, 1, 4, 1, 4>(a, s);
+  if (a.Cout <= 64) {
     // under-filled grid (e.g. the DiT's grouped position conv: 16 groups x 4 time tiles): 64 x 64 tiles instead
-    dim3 grid(cdiv(a.T_virt, 64), cdiv(a.Cout, 64), a.Z);
-    set_conv_route(route_code(ROUTE_CONV_GEMM, DT<T>::id, 1, 1, 2, 2));
-    hipLaunchKernelGGL((conv_gemm_kernel<T, 1, 1, 2, 2>), grid, dim3(256), 0, s, a);
-  } else if (a.Cout <= 64) {
-    dim3 grid(cdiv(a.T_virt, 256), cdiv(a.Cout, 64), a.Z);
-    set_conv_route(route_code(ROUTE_CONV_GEMM, DT<T>::id, 2, 2, 1, 4));
-    hipLaunchKernelGGL((conv_gemm_kernel<T, 2, 2, 1, 4>), grid, dim3(256), 0, s, a);
-  } else if ((long long)cdiv(a.T_virt, 128) * cdiv(a.Cout, 128) * a.Z < small_tiles_below()) {
-    // a handful of 128 x 128 tiles (single-utterance enc_p / flow convs: 200 frames x 384 channels = 6 workgroups, each
-    // a serial chain over taps x Cin): 64 x 64 tiles put four times as many CUs on the same chain length
-    dim3 grid(cdiv(a.T_virt, 64), cdiv(a.Cout, 64), a.Z);
-    set_conv_route(route_code(ROUTE_CONV_GEMM, DT<T>::id, 1, 1, 2, 2));
-    hipLaunchKernelGGL((conv_gemm_kernel<T, 1, 1, 2, 2>), grid, dim3(256), 0, s, a);
-  } else {
-    dim3 grid(cdiv(a.T_virt, 128), cdiv(a.Cout, 128), a.Z);
-    set_conv_route(route_code(ROUTE_CONV_GEMM, DT<T>::id, 2, 2, 2, 2));
-    hipLaunchKernelGGL((conv_gemm_kernel<T, 2, 2, 2, 2>), grid, dim3(256), 0, s, a);
+    if ((long long)cdiv(a.T_virt, 256) * a.Z < 192) return launch_direct<T, 1, 1, 2, 2>(a, s);
+    return launch_direct<T, 2, 2, 1, 4>(a, s);
   }
-  GSV_HIP(hipGetLastError());
-  return GSV_OK;
+  // a handful of 128 x 128 tiles (single-utterance enc_p / flow convs: 200 frames x 384 channels = 6 workgroups, each
+  // a serial chain over taps x Cin): 64 x 64 tiles put four times as many CUs on the same chain length
+  if ((long long)cdiv(a.T_virt, 128) * cdiv(a.Cout, 128) * a.Z < conv_switches().gemm_small_tiles) return launch_direct<T, 1, 1, 2, 2>(a, s);
+  return launch_direct<T, 2, 2, 2, 2>(a, s);
 }
 
 // segmented decode (ConvArgs::row_seg), the row pass after a conv: 32 lanes per output row; a gap row is stored as 0, a segment
@@ -236,10 +217,9 @@ int launch_seg_rows(int dtype, int out_f32, void* y, int ldy, int col0, int C, i
                     hipStream_t s) {
   if (!row_seg || rows <= 0) return GSV_OK;
   if (out_f32 || dtype == GSV_F32)
-    hipLaunchKernelGGL(seg_rows_kernel<float>, dim3(cdiv(rows, 8)), dim3(256), 0, s, y, ldy, col0, C, rows, row_seg, tab, ldb);
+    GSV_LAUNCH(seg_rows_kernel<float>, dim3(cdiv(rows, 8)), dim3(256), 0, s, y, ldy, col0, C, rows, row_seg, tab, ldb);
   else
-    hipLaunchKernelGGL(seg_rows_kernel<_Float16>, dim3(cdiv(rows, 8)), dim3(256), 0, s, y, ldy, col0, C, rows, row_seg, tab, ldb);
-  GSV_HIP(hipGetLastError());
+    GSV_LAUNCH(seg_rows_kernel<_Float16>, dim3(cdiv(rows, 8)), dim3(256), 0, s, y, ldy, col0, C, rows, row_seg, tab, ldb);
   return GSV_OK;
 }
 
@@ -258,20 +238,20 @@ static int launch_conv_gemm_kernel(int dtype, const ConvArgs& a_in, hipStream_t 
   set_conv_route(0);
   if (a.T_virt == 0) a.T_virt = a.T_out;
   if (a.ups_u > 0 && a.ups_cout == 0) { set_error("conv_gemm: ups_cout missing"); return GSV_ERR_ARG; }
-  static const bool no_lds = getenv("GSV_NO_CONV_LDS") != nullptr;   // A/B switch for profiling
-  {
-    const int rc = launch_gemm_sk(dtype, a, s);
-    if (rc <= 0) return rc;
+  const ConvSwitches& sw = conv_switches();
+  const bool fused_qkv = a.vt_out || a.rope_cs;      // the rotary / V^T epilogue exists in gemm_lds_kernel only
+  // gemm_sk -> conv_wide -> gemm_lds -> conv_narrow -> conv_lds -> conv_gemm: the first kernel that is eligible takes the launch
+  int rc = launch_gemm_sk(dtype, a, s);
+  if (rc <= 0) return rc;
+  if (sw.no_conv_lds && fused_qkv) { set_error("conv_gemm: fused QKV epilogue needs the LDS GEMM path"); return GSV_ERR_ARG; }
+  if (!sw.no_conv_lds) {
+    if ((rc = launch_conv_wide(dtype, a, s)) <= 0) return rc;
+    if ((rc = launch_gemm_lds(dtype, a, s)) <= 0) return rc;
+    if (fused_qkv) { set_error("gemm: the fused rotary / V^T epilogue exists in gemm_lds_kernel only (shape not eligible)"); return GSV_ERR_ARG; }
+    if ((rc = launch_conv_narrow(dtype, a, s)) <= 0) return rc;
+    if ((rc = launch_conv_lds(dtype, a, s)) <= 0) return rc;
   }
-  if (no_lds && (a.vt_out || a.rope_cs)) { set_error("conv_gemm: fused QKV epilogue needs the LDS GEMM path"); return GSV_ERR_ARG; }
-  if (!no_lds) {
-    int rc = launch_conv_wide(dtype, a, s);
-    if (rc <= 0) return rc;
-    rc = launch_conv_lds(dtype, a, s);
-    if (rc <= 0) return rc;
-  }
-  static const bool trace = getenv("GSV_TRACE_CONV_GEMM") != nullptr;      // which shapes take the direct-from-global fallback
-  if (trace)
+  if (sw.trace_conv_gemm)                            // which shapes take the direct-from-global kernel
     fprintf(stderr, "[conv_gemm fallback] T_in %d T_virt %d Cin %d Cout %d taps %d stride %d dil %d Z %d res %d res_f32 %d acc %d out_f32 %d gate %d ups %d\n",
             a.T_in, a.T_virt, a.Cin, a.Cout, a.taps, a.stride, a.dil, a.Z, a.res != nullptr, a.res_f32, a.accumulate, a.out_f32,
             a.gate != nullptr, a.ups_u);

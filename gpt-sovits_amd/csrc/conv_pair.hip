@@ -5,7 +5,7 @@
 // convs1 has dilation d, convs2 dilation 1, both k taps, C -> C channels with C = 16 or 32 (the last two generator stages at
 // 2 M / 4.1 M samples: 131 MB per tensor).  As two launches a pair moves 5 tensors through HBM (x in, t out | t in, x as
 // residual, y out); fused it moves 2 (x once -- the residual rows come out of L2, where the window load left them -- and y).
-// Construction = conv_narrow_f16_kernel (conv_lds.hip) twice inside one persistent 256-step tile:
+// Construction = conv_narrow_f16_kernel (conv_narrow.hip) twice inside one persistent 256-step tile:
 //   convs1's weights in registers (A-fragments, loaded once per wave), convs2's in LDS
 //   window  x[t0 - h2 - h1, t0 - h2 + 288 + h1) -> LDS (lrelu while staging), prefetched one tile ahead in registers
 //   convs1 over 288 rows (9 MFMA column tiles dealt to the 4 waves) -> + bias -> fp16 -> lrelu -> zero outside [0, T)  -> LDS
@@ -14,11 +14,7 @@
 // result is bit-identical to it, except that with scale != 1 AND accumulate the compiler contracts the last two operations of
 // the two epilogues differently (one fp16 ulp on ~0.02 % of the elements; tests/test_ops_gpu.py::test_conv_pair_matches_two_launches).
 // SEG = true is the same pair inside a segmented decode (gsv_op_conv_pair_seg; gap rows of the intermediate and of y are 0).
-#include <stdlib.h>
-
-#include <algorithm>
-
-#include "common.h"
+#include "conv_launch.h"
 
 namespace gsv {
 
@@ -244,32 +240,13 @@ template <int CC, int TAPS>
 int launch_pair(const ConvPairArgs& a, const int* row_seg, hipStream_t s) {
   const int ntiles = cdiv(a.T, 256);
   const size_t lds = ((size_t)ROWS_X + ROWS_Y + (size_t)TAPS * 32) * (CC + 8) * 2;
-  static const int cap = getenv("GSV_PAIR_PER_CU") ? std::max(1, atoi(getenv("GSV_PAIR_PER_CU"))) : 3;
-  const int per_cu = std::max(1, std::min(cap, (int)((156 * 1024) / lds)));
+  const int per_cu = std::max(1, std::min(conv_switches().pair_per_cu, (int)((156 * 1024) / lds)));
   const int grid = std::min(ntiles, 256 * per_cu);
-#define GSV_PAIR(A)                                                                                                        \
-  do {                                                                                                                     \
-    auto kern = conv_pair_f16_kernel<CC, TAPS, A, false>;                                                                  \
-    static bool set = false;                                                                                               \
-    if (!set) { GSV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set = true; } \
-    set_conv_route(route_code(ROUTE_CONV_PAIR, GSV_F16, CC, TAPS, 0, 0, 0, route_flags(false, A)));                        \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a, ntiles, (const int*)nullptr);                               \
-  } while (0)
-#define GSV_PAIR_SEG(A)                                                                                                    \
-  do {                                                                                                                     \
-    auto kern = conv_pair_f16_kernel<CC, TAPS, A, true>;                                                                   \
-    static bool set = false;                                                                                               \
-    if (!set) { GSV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set = true; } \
-    set_conv_route(route_code(ROUTE_CONV_PAIR, GSV_F16, CC, TAPS, 0, 0, 0, route_flags(false, A) | ROUTE_SEG));            \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a, ntiles, row_seg);                                           \
-  } while (0)
-  if (row_seg) { if (a.accumulate) GSV_PAIR_SEG(true); else GSV_PAIR_SEG(false); }
-  else if (a.accumulate) GSV_PAIR(true);
-  else GSV_PAIR(false);
-#undef GSV_PAIR_SEG
-#undef GSV_PAIR
-  GSV_HIP(hipGetLastError());
-  return GSV_OK;
+  return with_flags([&](auto A, auto SEG) {
+    return launch_routed<conv_pair_f16_kernel<CC, TAPS, A.value, SEG.value>, LDS_CAP>(
+        route_code(ROUTE_CONV_PAIR, GSV_F16, CC, TAPS, 0, 0, 0, route_flags(false, A.value) | (SEG.value ? ROUTE_SEG : 0)), dim3(grid), dim3(256), lds, s,
+        a, ntiles, row_seg);
+  }, a.accumulate != 0, row_seg != nullptr);
 }
 
 template <int CC>
@@ -287,16 +264,15 @@ int launch_pair_taps(const ConvPairArgs& a, const int* row_seg, hipStream_t s) {
 }  // namespace
 
 bool conv_pair_eligible(int dtype, int C, int taps, int dil, int T) {
-  static const bool off = getenv("GSV_NO_CONV_PAIR") != nullptr;       // A/B switch: two launches per pair
   // taps: exactly the instantiated kernels (launch_pair_taps); any other count would read tap slabs past w1 / w2
   const bool inst = taps == 3 || taps == 5 || taps == 7 || taps == 9 || taps == 11;
-  return !off && dtype == GSV_F16 && (C == 16 || C == 32) && inst && dil >= 1 && ((taps - 1) / 2) * dil <= 25 && T >= 256;
+  return !conv_switches().no_conv_pair && dtype == GSV_F16 && (C == 16 || C == 32) && inst && dil >= 1 && ((taps - 1) / 2) * dil <= 25 && T >= 256;
 }
 
 namespace {
 int launch_conv_pair_any(const ConvPairArgs& a, const int* row_seg, hipStream_t s) {
   GSV_REQUIRE(a.x && a.y && a.w1 && a.w2 && a.b1 && a.b2, "conv_pair: null operand");
-  GSV_REQUIRE(conv_pair_eligible(GSV_F16, a.C, a.taps, a.dil, a.T) || getenv("GSV_NO_CONV_PAIR"), "conv_pair: shape C=%d taps=%d dil=%d T=%d not supported",
+  GSV_REQUIRE(conv_pair_eligible(GSV_F16, a.C, a.taps, a.dil, a.T) || conv_switches().no_conv_pair, "conv_pair: shape C=%d taps=%d dil=%d T=%d not supported",
               a.C, a.taps, a.dil, a.T);
   GSV_REQUIRE(a.ldx % 8 == 0 && a.ldy % 4 == 0 && ((uintptr_t)a.x % 16) == 0 && ((uintptr_t)a.w1 % 16) == 0 && ((uintptr_t)a.w2 % 16) == 0,
               "conv_pair: operands must be 16-byte aligned");

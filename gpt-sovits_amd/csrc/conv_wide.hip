@@ -9,13 +9,7 @@
 // conv_narrow_f16_kernel): the NEXT tile's window is requested into registers before the current tile's tap loop and written to
 // LDS after its epilogue, and the residual rows of a pass are requested one pass ahead.  Arithmetic, MFMA order and epilogue formula are those of conv_lds_kernel<half, 2, 4, 2, 2, 128>:
 // results are bit-identical (tests/test_ops_gpu.py::test_wide_persistent_conv_matches_tile_kernel).
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <algorithm>
-#include <type_traits>
-
-#include "common.h"
+#include "conv_launch.h"
 
 namespace gsv {
 
@@ -221,50 +215,28 @@ __global__ __launch_bounds__(NW * 64) void conv_wide_f16_kernel(ConvArgs a, int 
 
 // returns 1 if the problem is not eligible (the caller goes on to the tile kernel), 0 on success, < 0 on error
 int launch_conv_wide(int dtype, const ConvArgs& a, hipStream_t s) {
-  static const bool off = getenv("GSV_NO_CONV_WIDE") != nullptr;          // A/B switch: one tile per workgroup (conv_lds_kernel)
-  if (off || dtype != GSV_F16) return 1;
+  const ConvSwitches& sw = conv_switches();
+  if (sw.no_conv_wide || dtype != GSV_F16) return 1;
   if (a.Cin != 128 || a.Cout != 128 || a.Z != 1 || a.stride != 1 || a.ups_u > 0 || a.dil < 1 || a.gate || a.taps < 2) return 1;
   if (a.out_f32 || a.res_f32 || a.y_col0 != 0 || a.T_virt < 16384 || a.T_out != a.T_virt || a.T_in < 1) return 1;
-  if (a.ldx % 8 != 0 || a.ldw % 8 != 0 || a.ldy % 4 != 0 || (a.res && a.ldr % 4 != 0) || ((uintptr_t)a.x % 16) || ((uintptr_t)a.w % 16)) return 1;
+  if (!operands_aligned<8>(a) || a.ldy % 4 != 0 || (a.res && a.ldr % 4 != 0)) return 1;
   const int span = (a.taps - 1) * a.dil;
   if (span > 50 || a.pad < 0 || a.pad > span) return 1;
   const int rows_win = 256 + span;
   const int ntiles = cdiv(a.T_virt, 256);
   const size_t lds = ((size_t)306 + 2 * 128) * 136 * 2;
   const int grid = std::min(ntiles, 256);
+  static TileStamps stamps;
   ConvArgs b = a;
-  static unsigned long long* d_prof = nullptr;
-  static int prof_calls = 0;
-  if (getenv("GSV_WIDE_PROF") && !d_prof) { (void)hipMalloc((void**)&d_prof, 64 * 8); (void)hipMemset(d_prof, 0, 64 * 8); }
-  b.prof = d_prof;
-  const bool res = a.res != nullptr, acc = a.accumulate != 0;
+  b.prof = stamps.buffer(sw.wide_prof);
   // 8 waves (round 3): 246 -> 222 us at 7 taps, 309 -> 291 us at 11 taps (tools/conv_probe.py), generator 10.87 -> 10.37 ms per bench
   // step in 2 of 2 alternating pairs, 0 / 10 spilled VGPRs instead of 0 / 22-58; GSV_WIDE_WAVES=4 restores round 2's geometry
-  static const int nw = getenv("GSV_WIDE_WAVES") ? atoi(getenv("GSV_WIDE_WAVES")) : 8;
-#define GSV_WIDE_NW(R, A, W)                                                                                               \
-  do {                                                                                                                     \
-    auto kern = conv_wide_f16_kernel<R, A, W>;                                                                             \
-    static bool set = false;                                                                                               \
-    if (!set) { GSV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set = true; } \
-    set_conv_route(route_code(ROUTE_CONV_WIDE, GSV_F16, W, 0, 0, 0, 0, route_flags(R, A)));                                 \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(W * 64), lds, s, b, rows_win, ntiles);                                       \
-  } while (0)
-#define GSV_WIDE(R, A) do { if (nw == 8) GSV_WIDE_NW(R, A, 8); else GSV_WIDE_NW(R, A, 4); } while (0)
-  if (res && acc) GSV_WIDE(true, true);
-  else if (res) GSV_WIDE(true, false);
-  else if (acc) GSV_WIDE(false, true);
-  else GSV_WIDE(false, false);
-#undef GSV_WIDE
-#undef GSV_WIDE_NW
-  GSV_HIP(hipGetLastError());
-  if (d_prof && ++prof_calls == 3) {
-    (void)hipStreamSynchronize(s);
-    unsigned long long hp[64];
-    (void)hipMemcpy(hp, d_prof, sizeof(hp), hipMemcpyDeviceToHost);
-    fprintf(stderr, "[wide prof] taps %d:", a.taps);
-    for (int i = 1; i < 24 && hp[i]; ++i) fprintf(stderr, " %.2f", (double)(hp[i] - hp[0]) / 100.0);
-    fprintf(stderr, "\n");
-  }
+  GSV_RC(with_flags([&](auto R, auto A, auto W8) {
+    constexpr int NW = W8.value ? 8 : 4;
+    return launch_routed<conv_wide_f16_kernel<R.value, A.value, NW>, LDS_CAP>(
+        route_code(ROUTE_CONV_WIDE, GSV_F16, NW, 0, 0, 0, 0, route_flags(R.value, A.value)), dim3(grid), dim3(NW * 64), lds, s, b, rows_win, ntiles);
+  }, a.res != nullptr, a.accumulate != 0, sw.wide_waves == 8));
+  stamps.report(s, 24, "[wide prof] taps %d:", a.taps);
   return GSV_OK;
 }
 

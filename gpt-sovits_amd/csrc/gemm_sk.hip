@@ -1,7 +1,7 @@
 // "Skinny" fp16 GEMM for gfx950: y[t][co] = epilogue(sum_k w[co][k] * x[t][k]) when the output has too few 128 x 128
 // tiles to fill 256 CUs (the DiT's Linear layers at T ~ 1000 frames: 64-192 tiles; prefill / encoder 1x1 layers).
 //
-// There the LDS-tiled kernel (conv_lds.hip) is latency-bound, not MFMA-bound: one workgroup per CU walks 16-32
+// There the LDS-tiled kernel (gemm_lds.hip) is latency-bound, not MFMA-bound: one workgroup per CU walks 16-32
 // dependent global -> LDS -> barrier -> MFMA steps of ~2 us each.  This kernel is cut the other way:
 //   * 64 x 64 output tile per workgroup (4x as many workgroups), and the K range dealt in 64-wide chunks to the
 //     workgroup's 4 waves (in-workgroup split-K): each wave streams its chunks straight from global memory into MFMA
@@ -12,7 +12,7 @@
 //     of a row cover one 128-byte line;
 //   * the 4 partial tiles are summed through LDS in a fixed order (deterministic), then bias / gate / residual /
 //     activation are applied and whole channels-last row segments (128 B per 4 threads) are stored.
-#include "common.h"
+#include "conv_launch.h"
 
 // order fence for the software pipelines: the empty asm stops IR-level sinking / hoisting of the loads across it, the
 // sched_barrier stops the machine scheduler
@@ -276,11 +276,11 @@ __global__ __launch_bounds__(256) void gemm_t64_f16_kernel(ConvArgs a) {
 
 // 0 = launched, 1 = not eligible, < 0 error
 int launch_gemm_sk(int dtype, const ConvArgs& a, hipStream_t s) {
-  static const bool off = getenv("GSV_NO_GEMM_SK") != nullptr;     // A/B switch for profiling
-  if (off || dtype != GSV_F16 || a.vt_out || a.rope_cs) return 1;     // fused QKV epilogues live in gemm_lds_kernel
+  const ConvSwitches& sw = conv_switches();
+  if (sw.no_gemm_sk || dtype != GSV_F16 || a.vt_out || a.rope_cs) return 1;     // fused QKV epilogues live in gemm_lds_kernel
   if (a.taps != 1 || a.stride != 1 || a.ups_u > 0 || a.accumulate || a.pad != 0 || a.Z != 1 || a.pre_act != ACT_NONE) return 1;
   if (a.Cin % 64 != 0 || a.Cin < 256 || a.Cout < 64) return 1;
-  if (a.ldx % 8 != 0 || a.ldw % 8 != 0 || ((uintptr_t)a.x % 16) || ((uintptr_t)a.w % 16)) return 1;
+  if (!operands_aligned<8>(a)) return 1;
   if (a.T_in < a.T_virt) return 1;
   // only where the 128 x 128 LDS-tiled kernel cannot fill the chip
   // and only for skinny M: at M = 5760 (AR prefill) the 128 x 128 kernel wins even at 0.7 workgroups per CU
@@ -288,43 +288,18 @@ int launch_gemm_sk(int dtype, const ConvArgs& a, hipStream_t s) {
   const long long tiles128 = (long long)cdiv(a.T_virt, 128) * cdiv(a.Cout, 128);
   // measured in the DiT step (tools/cfm_bench.py, GSV_SK_MAX_TILES): 384 -> 3.16, 160 -> 3.02, 100 -> 3.31 ms per step, i.e. the
   // QKV projection (192 tiles) is better off on the 128 x 128 kernel, FF1 (128 tiles) and the N = 1024 layers are not
-  static const int max_tiles = getenv("GSV_SK_MAX_TILES") ? atoi(getenv("GSV_SK_MAX_TILES")) : 160;
-  if (tiles128 >= max_tiles || a.T_virt > 2048) return 1;
-  static const bool t64 = !(getenv("GSV_GEMM_T64") && getenv("GSV_GEMM_T64")[0] == '0');   // A/B switch
-  if (t64 && a.Cin % 512 == 0) {
+  if (tiles128 >= sw.sk_max_tiles || a.T_virt > 2048) return 1;
+  const dim3 grid(cdiv(a.T_virt, 64), cdiv(a.Cout, 64));
+  if (sw.gemm_t64 && a.Cin % 512 == 0) {
     // 128-half stages (two workgroups per CU) by default; GSV_T64_SLAB=256 restores round 2's single resident workgroup
-    static const int slab = getenv("GSV_T64_SLAB") ? atoi(getenv("GSV_T64_SLAB")) : 128;
-    static bool attr64 = false;
-    if (!attr64) {
-      GSV_HIP(hipFuncSetAttribute((const void*)gemm_t64_f16_kernel<false, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
-      GSV_HIP(hipFuncSetAttribute((const void*)gemm_t64_f16_kernel<true, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
-      GSV_HIP(hipFuncSetAttribute((const void*)gemm_t64_f16_kernel<false, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
-      GSV_HIP(hipFuncSetAttribute((const void*)gemm_t64_f16_kernel<true, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
-      attr64 = true;
-    }
-    dim3 grid64(cdiv(a.T_virt, 64), cdiv(a.Cout, 64));
-    set_conv_route(route_code(ROUTE_GEMM_T64, GSV_F16, slab / 16, 0, 0, 0, 0, route_flags(false, false, false, a.w_nt != 0)));
-    if (slab == 128) {
-      if (a.w_nt) hipLaunchKernelGGL((gemm_t64_f16_kernel<true, 128>), grid64, dim3(256), 65536, s, a);
-      else hipLaunchKernelGGL((gemm_t64_f16_kernel<false, 128>), grid64, dim3(256), 65536, s, a);
-    } else {
-      if (a.w_nt) hipLaunchKernelGGL((gemm_t64_f16_kernel<true, 256>), grid64, dim3(256), 131072, s, a);
-      else hipLaunchKernelGGL((gemm_t64_f16_kernel<false, 256>), grid64, dim3(256), 131072, s, a);
-    }
-    GSV_HIP(hipGetLastError());
-    return 0;
+    return with_flags([&](auto WNT, auto S128) {
+      constexpr int SLAB = S128.value ? 128 : 256, LDS = 2 * 2 * 64 * SLAB * 2;   // two buffers of two 64-row operands of SLAB halfs
+      return launch_routed<gemm_t64_f16_kernel<WNT.value, SLAB>, LDS>(
+          route_code(ROUTE_GEMM_T64, GSV_F16, sw.t64_slab / 16, 0, 0, 0, 0, route_flags(false, false, false, WNT.value)), grid, dim3(256), LDS, s, a);
+    }, a.w_nt != 0, sw.t64_slab == 128);
   }
-  static bool attr = false;
-  const size_t lds = (size_t)4 * 64 * 68 * 4;
-  if (!attr) {
-    GSV_HIP(hipFuncSetAttribute((const void*)gemm_sk_f16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr = true;
-  }
-  dim3 grid(cdiv(a.T_virt, 64), cdiv(a.Cout, 64));
-  set_conv_route(route_code(ROUTE_GEMM_SK, GSV_F16));
-  hipLaunchKernelGGL(gemm_sk_f16_kernel, grid, dim3(256), lds, s, a);
-  GSV_HIP(hipGetLastError());
-  return 0;
+  constexpr int LDS = 4 * 64 * 68 * 4;              // the four waves' partial tiles
+  return launch_routed<gemm_sk_f16_kernel, LDS>(route_code(ROUTE_GEMM_SK, GSV_F16), grid, dim3(256), LDS, s, a);
 }
 
 }  // namespace gsv

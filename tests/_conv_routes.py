@@ -57,8 +57,9 @@ SK = "gemm_sk_f16"
 MODES = ((0, 0), (1, 0), (0, 1), (1, 1))     # (RES, ACCU)
 
 # Every instantiation the default dispatcher can launch (gemm_lds without its run-time xcd_order), read from the launchers:
-# gemm_sk.hip launch_gemm_sk, conv_wide.hip launch_conv_wide, conv_lds.hip try_launch_gemm / try_launch / launch_narrow,
-# conv_gemm.hip launch_t, conv_pair.hip launch_pair_taps.  Not here, reached only through A/B switches: gemm_t64 with
+# gemm_sk.hip launch_gemm_sk, conv_wide.hip launch_conv_wide, gemm_lds.hip launch_gemm_lds, conv_narrow.hip launch_conv_narrow,
+# conv_lds.hip launch_conv_lds, conv_gemm.hip launch_t, conv_pair.hip launch_pair_taps.  Not here, reached only through A/B
+# switches (csrc/conv_launch.h ConvSwitches): gemm_t64 with
 # SLAB 256 (GSV_T64_SLAB), conv_wide with 4 waves (GSV_WIDE_WAVES), the 4-wave fp16 conv_lds tiles (GSV_CONV_HALF_WAVES,
 # GSV_CONV_TILE_WAVES); gemm_lds<f16,...,W4> IS default-reachable (grids of more than 256 tiles, Cin < 128).
 REACHABLE = sorted(
@@ -138,7 +139,7 @@ def _cases():
         C("t64_prefill_out32_res16", t64(0), "T2S prefill: fp32 output, fp16 residual", Cin=512, Cout=512, T=300, taps=1,
           pre=NONE, res=True, out_f32=True, res_dtype=2),
     ]
-    # ---------------- conv_lds.hip try_launch_gemm: 1 x 1, T_virt >= 512, Cout >= 96, Cin >= BK
+    # ---------------- gemm_lds.hip launch_gemm_lds: 1 x 1, T_virt >= 512, Cout >= 96, Cin >= BK
     L += [
         C("glds_prefill_out32_res16", glds("f16", 1, 0, 8, 2), "T2S prefill beyond 2048 tokens: fp32 out, fp16 residual",
           Cin=512, Cout=512, T=2100, taps=1, pre=NONE, res=True, out_f32=True, res_dtype=2),

@@ -1,5 +1,5 @@
 """Times one Linear-shaped launch of gsv_op_conv1d (taps = 1) with HIP events over back-to-back launches; used to probe
-the GEMM kernels (GSV_SK_MODE / GSV_NO_GEMM_SK select variants).  Not part of the product."""
+the GEMM kernels (GSV_NO_GEMM_SK and the other switches of csrc/conv_launch.h select variants).  Not part of the product."""
 import ctypes as C
 import json
 import os
@@ -34,7 +34,7 @@ def main():
         torch.cuda.synchronize()
         us = e0.elapsed_time(e1) * 1e3 / n
         print(json.dumps({"T": T, "K": K, "N": N, "us": round(us, 2), "tflops": round(2 * T * K * N / us / 1e6, 1),
-                          "mode": os.environ.get("GSV_SK_MODE", "0"), "sk": "GSV_NO_GEMM_SK" not in os.environ}))
+                          "sk": "GSV_NO_GEMM_SK" not in os.environ}))
 
 
 if __name__ == "__main__":

@@ -29,10 +29,15 @@ __device__ __forceinline__ f4 mma16(h8 a, h8 b, f4 c) { return __builtin_amdgcn_
 // Vt[head][d][key] = V[key][head*64 + d], keys zero padded to ldv (a multiple of 32).  The extra grid plane z == heads
 // applies the DiT's rotary embedding in place to the first 2*rope_half channels of q and k (x_transformers'
 // apply_rotary_pos_emb on the un-split projections, modules.py:420-427): same launch, one kernel less per block.
+// Several utterances (rows of a batch) in one launch: blockIdx.z = row * planes + plane, planes = heads (+ 1 with rotary);
+// row b's q / k / v start xz elements after row b-1's and its V^T buffer vtz elements after.
 __global__ __launch_bounds__(256) void vt_kernel(const _Float16* __restrict__ v, int ld, int T, int ldv, _Float16* __restrict__ vt,
                                                  int heads, _Float16* __restrict__ q, int ldq, _Float16* __restrict__ k, int ldk,
-                                                 const float* __restrict__ rope_cs, int rope_half) {
-  if ((int)blockIdx.z == heads) {
+                                                 const float* __restrict__ rope_cs, int rope_half, int planes, long long xz,
+                                                 long long vtz) {
+  const int row = blockIdx.z / planes, plane = blockIdx.z - row * planes;
+  v += row * xz; q += row * xz; k += row * xz; vt += row * vtz;
+  if (plane == heads) {
     const int n = T * rope_half * 2;
     const int stride = gridDim.x * gridDim.y * 256;
     for (int i = (blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x; i < n; i += stride) {
@@ -48,7 +53,7 @@ __global__ __launch_bounds__(256) void vt_kernel(const _Float16* __restrict__ v,
     return;
   }
   __shared__ _Float16 tile[32][34];
-  const int head = blockIdx.z, j0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  const int head = plane, j0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   for (int i = ty; i < 32; i += 8) {
     const int j = j0 + i;
@@ -64,18 +69,25 @@ __global__ __launch_bounds__(256) void vt_kernel(const _Float16* __restrict__ v,
 // QT = 16-query tiles per workgroup.  Every K / V^T fragment a wave loads feeds QT score tiles and QT output tiles:
 // fragment-shaped global loads cost ~120 clocks of the CU's texture-address path each (measured),
 // and with QT = 1 those loads, not MFMA or latency, set the kernel's time.
+// Several utterances in one launch: gridDim.y = rows * heads.  Row b's q / k start xz elements after row b-1's, its V^T vtz
+// and its output oz elements after.
 template <int QT>
 __global__ __launch_bounds__(256) void flash_attn64_f16_kernel(const _Float16* __restrict__ q, int ldq, const _Float16* __restrict__ k,
                                                                int ldk, const _Float16* __restrict__ vt, int ldv, int T, float scale,
-                                                               _Float16* __restrict__ out, int ldo) {
+                                                               _Float16* __restrict__ out, int ldo, int heads, long long xz,
+                                                               long long vtz, long long oz) {
   constexpr int LDO = 68, BQ = 16 * QT;
   extern __shared__ float smem[];
   float* Os = smem;                                  // [4][BQ][LDO]
   float* Ms = smem + 4 * BQ * LDO;                   // [4][BQ]
   float* Ls = Ms + 4 * BQ;                           // [4][BQ]
-  // heads are dealt to XCDs in contiguous runs (2 heads per XCD at 16 heads): a head's K / V^T stay in one L2
+  // (row, head) pairs are dealt to XCDs in contiguous runs (2 heads per XCD at 16 heads and one row, 2 * rows with more):
+  // all query tiles of a pair run on one XCD, so its K / V^T stay in one L2.  The pair is the slow index of the virtual id,
+  // so an XCD works through its pairs one after the other and holds only the few in flight.
   const int vid = xcd_virtual_id(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
-  const int head = vid / gridDim.x, q0 = (vid % gridDim.x) * BQ;
+  const int pair = vid / gridDim.x, q0 = (vid % gridDim.x) * BQ;
+  const int row = pair / heads, head = pair - row * heads;
+  q += row * xz; k += row * xz; vt += row * vtz; out += row * oz;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = lane & 15, g = lane >> 4;
   h8 qf0[QT], qf1[QT];
@@ -187,15 +199,15 @@ __global__ __launch_bounds__(256) void flash_attn64_f16_kernel(const _Float16* _
 
 template <int QT>
 static int launch_flash_qt(const void* q, int ldq, const void* k, int ldk, const void* vt_buf, int ldv, int T, int heads, float scale,
-                           void* out, int ldo, hipStream_t s) {
+                           void* out, int ldo, hipStream_t s, int rows, long long xz, long long vtz, long long oz) {
   const size_t lds = ((size_t)4 * 16 * QT * 68 + 8 * 16 * QT) * 4;
   static bool attr = false;
   if (!attr) {
     GSV_HIP(hipFuncSetAttribute((const void*)flash_attn64_f16_kernel<QT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = true;
   }
-  hipLaunchKernelGGL(flash_attn64_f16_kernel<QT>, dim3(cdiv(T, 16 * QT), heads), dim3(256), lds, s, (const _Float16*)q, ldq,
-                     (const _Float16*)k, ldk, (const _Float16*)vt_buf, ldv, T, scale, (_Float16*)out, ldo);
+  hipLaunchKernelGGL(flash_attn64_f16_kernel<QT>, dim3(cdiv(T, 16 * QT), rows * heads), dim3(256), lds, s, (const _Float16*)q, ldq,
+                     (const _Float16*)k, ldk, (const _Float16*)vt_buf, ldv, T, scale, (_Float16*)out, ldo, heads, xz, vtz, oz);
   GSV_HIP(hipGetLastError());
   return GSV_OK;
 }
@@ -410,22 +422,35 @@ int launch_flash_rel96_f16(const void* q, int ldq, const void* k, int ldk, const
   return GSV_OK;
 }
 
-// q / k: [T][ld] with head h at columns h*64..; v likewise; vt_buf: heads * 64 * ceil32(T) halfs of scratch
-int launch_flash_attn64_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldvv, void* vt_buf, int T, int heads,
-                            float scale, void* out, int ldo, hipStream_t s, const float* rope_cs, int rope_half, bool vt_ready) {
-  GSV_REQUIRE(T >= 1 && heads >= 1, "flash_attn: empty problem");
+// `rows` utterances of T frames in two launches.  q / k: [T][ld] with head h at columns h*64..; v likewise; row b of q, k and v
+// starts xz elements after row b-1, of out oz elements after; vt_buf: rows * vtz halfs of scratch, vtz >= heads * 64 * ceil32(T)
+int launch_flash_attn64_f16_rows(const void* q, int ldq, const void* k, int ldk, const void* v, int ldvv, void* vt_buf, int T, int heads,
+                                 float scale, void* out, int ldo, hipStream_t s, const float* rope_cs, int rope_half, bool vt_ready,
+                                 int rows, long long xz, long long vtz, long long oz) {
+  GSV_REQUIRE(T >= 1 && heads >= 1 && rows >= 1, "flash_attn: empty problem");
   GSV_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldo % 4 == 0 && ((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)out % 8) == 0,
               "flash_attn: operands must be 16-byte aligned with leading dims multiple of 8");
   const int ldv = (T + 31) / 32 * 32;
+  const int planes = heads + (rope_cs ? 1 : 0);
+  GSV_REQUIRE(rows == 1 || (xz % 8 == 0 && vtz % 8 == 0 && oz % 4 == 0 && vtz >= (long long)heads * 64 * ldv),
+              "flash_attn: row strides must keep every row 16-byte aligned and its V^T buffer apart");
+  GSV_REQUIRE((long long)rows * planes <= 65535 && (long long)rows * heads <= 65535, "flash_attn: %d rows x %d heads exceed the grid", rows, heads);
   if (!vt_ready)
-    hipLaunchKernelGGL(vt_kernel, dim3(ldv / 32, 2, heads + (rope_cs ? 1 : 0)), dim3(256), 0, s, (const _Float16*)v, ldvv, T, ldv,
-                       (_Float16*)vt_buf, heads, (_Float16*)const_cast<void*>(q), ldq, (_Float16*)const_cast<void*>(k), ldk, rope_cs, rope_half);
+    hipLaunchKernelGGL(vt_kernel, dim3(ldv / 32, 2, rows * planes), dim3(256), 0, s, (const _Float16*)v, ldvv, T, ldv, (_Float16*)vt_buf,
+                       heads, (_Float16*)const_cast<void*>(q), ldq, (_Float16*)const_cast<void*>(k), ldk, rope_cs, rope_half, planes, xz,
+                       vtz);
   static const int qt_env = getenv("GSV_FLASH_QT") ? atoi(getenv("GSV_FLASH_QT")) : 0;     // A/B switch
-  // more query tiles per workgroup = fewer K / V fragment loads per query, but fewer workgroups: keep >= ~1 per CU
+  // more query tiles per workgroup = fewer K / V fragment loads per query, but fewer workgroups: keep >= ~1 per CU.  Chosen
+  // from ONE row's size whatever `rows` is, so that a row computes the same bits alone and in a batch.
   int qt = qt_env ? qt_env : ((long long)cdiv(T, 64) * heads >= 200 ? 4 : ((long long)cdiv(T, 32) * heads >= 200 ? 2 : 1));
-  if (qt >= 4) return launch_flash_qt<4>(q, ldq, k, ldk, vt_buf, ldv, T, heads, scale, out, ldo, s);
-  if (qt >= 2) return launch_flash_qt<2>(q, ldq, k, ldk, vt_buf, ldv, T, heads, scale, out, ldo, s);
-  return launch_flash_qt<1>(q, ldq, k, ldk, vt_buf, ldv, T, heads, scale, out, ldo, s);
+  if (qt >= 4) return launch_flash_qt<4>(q, ldq, k, ldk, vt_buf, ldv, T, heads, scale, out, ldo, s, rows, xz, vtz, oz);
+  if (qt >= 2) return launch_flash_qt<2>(q, ldq, k, ldk, vt_buf, ldv, T, heads, scale, out, ldo, s, rows, xz, vtz, oz);
+  return launch_flash_qt<1>(q, ldq, k, ldk, vt_buf, ldv, T, heads, scale, out, ldo, s, rows, xz, vtz, oz);
+}
+
+int launch_flash_attn64_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldvv, void* vt_buf, int T, int heads,
+                            float scale, void* out, int ldo, hipStream_t s, const float* rope_cs, int rope_half, bool vt_ready) {
+  return launch_flash_attn64_f16_rows(q, ldq, k, ldk, v, ldvv, vt_buf, T, heads, scale, out, ldo, s, rope_cs, rope_half, vt_ready, 1, 0, 0, 0);
 }
 
 }  // namespace gsv

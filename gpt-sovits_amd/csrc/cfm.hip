@@ -46,13 +46,17 @@ __global__ void cfm_cast_rows_kernel(const float* __restrict__ src, int lds, int
   dst[(long long)r * ldd + col0 + c] = (T)src[(long long)r * lds + c];
 }
 
+// The kernels that look along time take the utterance (row of the batch) as blockIdx.y: one launch over all rows, every row
+// an independent [Tn][C] slab, back to back.
+//
 // te0[t][c] = mu[t][c] + table[min(t, 4095)][c]   (TextEmbedding.forward, dit.py:50-72)
 template <typename T>
 __global__ void cfm_text_pos_kernel(const float* __restrict__ mu, const float* __restrict__ table, int Tn, int C, T* __restrict__ out) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)Tn * C) return;
   int t = (int)(i / C), c = (int)(i - (long long)t * C);
-  out[i] = (T)(mu[i] + table[(long long)min(t, 4095) * C + c]);
+  const long long o = (long long)blockIdx.y * Tn * C + i;
+  out[o] = (T)(mu[o] + table[(long long)min(t, 4095) * C + c]);
 }
 
 // depthwise conv, 7 taps, zero padding 3 (ConvNeXtV2Block.dwconv, modules.py:250)
@@ -62,6 +66,8 @@ __global__ void cfm_dwconv7_kernel(const T* __restrict__ x, const float* __restr
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)Tn * C) return;
   int t = (int)(i / C), c = (int)(i - (long long)t * C);
+  x += (long long)blockIdx.y * Tn * C;
+  y += (long long)blockIdx.y * Tn * C;
   float acc = b[c];
 #pragma unroll
   for (int j = 0; j < 7; ++j) {
@@ -71,11 +77,13 @@ __global__ void cfm_dwconv7_kernel(const T* __restrict__ x, const float* __restr
   y[i] = (T)acc;
 }
 
-// GRN (modules.py:225-236): gx[c] = ||y[:, c]||_2 over time
+// GRN (modules.py:225-236): gx[row][c] = ||y[row][:, c]||_2 over the row's own frames
 template <typename T>
 __global__ void cfm_grn_norm_kernel(const T* __restrict__ y, int Tn, int C, float* __restrict__ gx) {
   __shared__ float red[4][64];
   const int c = blockIdx.x * 64 + (threadIdx.x & 63), part = threadIdx.x >> 6;
+  y += (long long)blockIdx.y * Tn * C;
+  gx += (long long)blockIdx.y * C;
   float s = 0.f;
   if (c < C)
     for (int t = part; t < Tn; t += 4) { float v = to_f(y[(long long)t * C + c]); s += v * v; }
@@ -89,6 +97,8 @@ template <typename T>
 __global__ void cfm_grn_apply_kernel(T* __restrict__ y, const float* __restrict__ gx, const float* __restrict__ gamma,
                                      const float* __restrict__ beta, int Tn, int C) {
   __shared__ float wsum[4];
+  y += (long long)blockIdx.y * Tn * C;
+  gx += (long long)blockIdx.y * C;
   float s = 0.f;
   for (int c = threadIdx.x; c < C; c += 256) s += gx[c];
   s = wave_sum(s);
@@ -178,14 +188,36 @@ __device__ __forceinline__ unsigned long long cfm_mix64(unsigned long long z) {
   return z ^ (z >> 31);
 }
 
-// x0[t][c] = temperature * noise (given channels-first [C][Tn], or a counter-based normal draw), zero on the prompt rows
-__global__ void cfm_init_x_kernel(const float* __restrict__ noise, unsigned long long seed, float temperature, int Tn, int Tp, int C,
+// what differs between the utterances of one call: the prompt mel (channels-first [C][Tp], device) and its length, and the key
+// of the noise draw.  A small device array, one entry per utterance, read by the four kernels below.
+struct CfmRow {
+  const float* prompt;
+  unsigned long long seed;
+  int Tp, pad_;
+};
+
+// the table reaches the device as kernel arguments, up to CFM_ROW_CHUNK entries per launch: the runtime copies arguments at
+// launch, so the host vector may go away at once and the host never waits for the stream
+constexpr int CFM_ROW_CHUNK = 64;
+struct CfmRowChunk { CfmRow r[CFM_ROW_CHUNK]; };
+
+__global__ void cfm_rows_fill_kernel(CfmRowChunk ch, int n, CfmRow* __restrict__ rw) {
+  const int b = threadIdx.x;
+  if (b < n) rw[b] = ch.r[b];
+}
+
+// x0[t][c] = temperature * noise (given channels-first [B][C][Tn], or a counter-based normal draw), zero on the prompt frames
+__global__ void cfm_init_x_kernel(const float* __restrict__ noise, const CfmRow* __restrict__ rw, float temperature, int Tn, int C,
                                   float* __restrict__ x) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)Tn * C) return;
   int t = (int)(i / C), c = (int)(i - (long long)t * C);
+  const int b = blockIdx.y;
+  const unsigned long long seed = rw[b].seed;
+  const int Tp = rw[b].Tp;
+  x += (long long)b * Tn * C;
   float n;
-  if (noise) n = noise[(long long)c * Tn + t];
+  if (noise) n = noise[((long long)b * C + c) * Tn + t];
   else {
     unsigned long long h1 = cfm_mix64(seed ^ cfm_mix64((unsigned long long)i * 2 + 1)), h2 = cfm_mix64(seed ^ cfm_mix64((unsigned long long)i * 2 + 2));
     float u1 = ((float)(h1 >> 40) + 1.f) * (1.f / 16777217.f), u2 = (float)(h2 >> 40) * (1.f / 16777216.f);
@@ -194,15 +226,16 @@ __global__ void cfm_init_x_kernel(const float* __restrict__ noise, unsigned long
   x[i] = t < Tp ? 0.f : n * temperature;
 }
 
-// Euler update x += d * v (rows >= Tp; prompt rows stay 0, models.py:1083-1084) and refresh the x columns of the DiT input;
-// rows = batch * Tn, the prompt region restarts per utterance
+// Euler update x += d * v (frames >= Tp; prompt frames stay 0, models.py:1083-1084) and refresh the x columns of the DiT input;
+// rows = batch * Tn, the prompt region restarts per utterance with that utterance's own length
 template <typename T>
-__global__ void cfm_euler_kernel(float* __restrict__ x, const float* __restrict__ v, float d, int rows, int Tn, int Tp, int C,
-                                 T* __restrict__ xin, int ldin) {
+__global__ void cfm_euler_kernel(float* __restrict__ x, const float* __restrict__ v, float d, int rows, int Tn,
+                                 const CfmRow* __restrict__ rw, int C, T* __restrict__ xin, int ldin) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)rows * C) return;
   int row = (int)(i / C), c = (int)(i - (long long)row * C);
-  const int t = row % Tn;
+  const int b = row / Tn, t = row - b * Tn;
+  const int Tp = rw[b].Tp;
   float u = t < Tp ? 0.f : x[i] + (v ? d * v[i] : 0.f);
   x[i] = u;
   xin[(long long)row * ldin + c] = (T)u;
@@ -210,12 +243,14 @@ __global__ void cfm_euler_kernel(float* __restrict__ x, const float* __restrict_
 
 // prompt mel (channels-first [C][Tp]) -> the cond columns of the DiT input, zero after the prompt; also zeroes the pad columns
 template <typename T>
-__global__ void cfm_cond_kernel(const float* __restrict__ prompt, int Tn, int Tp, int C, T* __restrict__ xin, int ldin, int col0,
-                                int pad0) {
+__global__ void cfm_cond_kernel(const CfmRow* __restrict__ rw, int Tn, int C, T* __restrict__ xin, int ldin, int col0, int pad0) {
   const int W = C + (ldin - pad0);
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)Tn * W) return;
   int t = (int)(i / W), c = (int)(i - (long long)t * W);
+  const float* prompt = rw[blockIdx.y].prompt;
+  const int Tp = rw[blockIdx.y].Tp;
+  xin += (long long)blockIdx.y * Tn * ldin;
   if (c < C) xin[(long long)t * ldin + col0 + c] = (T)(t < Tp ? prompt[(long long)c * Tp + t] : 0.f);
   else xin[(long long)t * ldin + pad0 + (c - C)] = (T)0.f;
 }
@@ -228,12 +263,13 @@ __global__ void cfm_copy_cols_kernel(const T* __restrict__ src, int lds, int row
   dst[(long long)r * ldd + col0 + c] = src[(long long)r * lds + c];
 }
 
-// channels-last fp32 [Tn][C] -> channels-first [C][Tn]
-__global__ void cfm_out_kernel(const float* __restrict__ x, int Tn, int C, float* __restrict__ out) {
+// channels-last fp32 [Tn][C] -> channels-first [C][Tn]; the prompt frames are written as the zeros they are held at
+__global__ void cfm_out_kernel(const float* __restrict__ x, const CfmRow* __restrict__ rw, int Tn, int C, float* __restrict__ out) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)Tn * C) return;
   int c = (int)(i / Tn), t = (int)(i - (long long)c * Tn);
-  out[i] = x[(long long)t * C + c];
+  const long long o = (long long)blockIdx.y * Tn * C;
+  out[o + i] = t < rw[blockIdx.y].Tp ? 0.f : x[o + (long long)t * C + c];
 }
 
 }  // namespace gsv
@@ -256,6 +292,13 @@ struct gsv_cfm {
 #define CFM_LAUNCH(kern, n, ...)                                                                         \
   do {                                                                                                   \
     hipLaunchKernelGGL(kern, dim3(nblk((long long)(n))), dim3(256), 0, s, __VA_ARGS__);                 \
+    GSV_HIP(hipGetLastError());                                                                          \
+  } while (0)
+
+// the same over B utterances: blockIdx.y = utterance
+#define CFM_LAUNCH_ROWS(kern, n, B, ...)                                                                 \
+  do {                                                                                                   \
+    hipLaunchKernelGGL(kern, dim3(nblk((long long)(n)), (B)), dim3(256), 0, s, __VA_ARGS__);            \
     GSV_HIP(hipGetLastError());                                                                          \
   } while (0)
 
@@ -302,26 +345,37 @@ int cfm_modulations(gsv_cfm* c, hipStream_t s, int N, float** mods_out) {
   return GSV_OK;
 }
 
-// B utterances of Tn frames: mu [B][Tn][text_dim] fp32, prompt [B][mel][Tp] fp32, noise [B][mel][Tn] fp32 or null -> out
-// [B][mel][Tn] fp32.  All row-wise work (Linear layers, AdaLN, rotary, Euler) runs over the B * Tn rows at once -- the
-// batched caller (TTS.py:1576-1579) hands over 4-8 chunks, which is what fills the chip and reads the 370 MB of weights
-// once per step instead of once per chunk; only the ops that look along time (depthwise / position convs, GRN, attention)
-// are issued per utterance.
+// B utterances of Tn frames: mu [B][Tn][text_dim] fp32, noise [B][mel][Tn] fp32 or null -> out [B][mel][Tn] fp32; `host_rows`
+// holds every utterance's own prompt ([mel][Tp_b] fp32, device), prompt length and noise key.  All row-wise work (Linear
+// layers, AdaLN, rotary, Euler) runs over the B * Tn rows at once, which is what fills the chip and reads the 370 MB of
+// weights once per step instead of once per chunk.  The ops that look along time (depthwise convs, GRN, fused attention)
+// take the utterance as a grid dimension: one launch for all of them.  Only the two grouped position convs and the
+// materialised attention (the parity path) are issued per utterance.
 template <typename T>
-int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* mu, const float* prompt, int B, int Tn, int Tp, int N,
-                    const float* noise, float temperature, unsigned long long seed, float* out) {
+int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* mu, const std::vector<CfmRow>& host_rows, int Tn, int N,
+                    const float* noise, float temperature, float* out) {
   gsv_vits* h = &c->ctx;
   const auto& g = c->cfg;
   const int D = g.dim, td = g.text_dim, md = g.mel_dim, inner = g.heads * g.dim_head, FF = D * g.ff_mult, ldin = c->ldin;
   const int half = g.dim_head / 2;
   const size_t es = sizeof(T);
+  const int B = (int)host_rows.size();
   const int R = B * Tn;
+  CfmRow* rw;
+  GSV_RC(need(h, "cfm_rows", (size_t)B * sizeof(CfmRow), (void**)&rw));
+  for (int b0 = 0; b0 < B; b0 += CFM_ROW_CHUNK) {
+    const int n = std::min(CFM_ROW_CHUNK, B - b0);
+    CfmRowChunk ch{};
+    std::copy_n(host_rows.begin() + b0, n, ch.r);
+    hipLaunchKernelGGL(cfm_rows_fill_kernel, dim3(1), dim3(CFM_ROW_CHUNK), 0, s, ch, n, rw + b0);
+    GSV_HIP(hipGetLastError());
+  }
   float *x, *v, *cs, *gx;
   void *xin, *ta, *tb, *tw, *hb, *c1, *nrm, *qkv, *ao, *ff;
   GSV_RC(need(h, "cfm_x", (size_t)R * md * 4, (void**)&x));
   GSV_RC(need(h, "cfm_v", (size_t)R * md * 4, (void**)&v));
   GSV_RC(need(h, "cfm_cs", (size_t)Tn * half * 2 * 4, (void**)&cs));
-  GSV_RC(need(h, "cfm_gx", (size_t)2 * td * 4, (void**)&gx));
+  GSV_RC(need(h, "cfm_gx", (size_t)B * 2 * td * 4, (void**)&gx));
   GSV_RC(need(h, "cfm_xin", (size_t)R * ldin * es, &xin));
   GSV_RC(need(h, "cfm_ta", (size_t)R * td * es, &ta));
   GSV_RC(need(h, "cfm_tb", (size_t)R * td * es, &tb));
@@ -335,38 +389,30 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
   auto rows = [&](void* p, int b, int width) { return (void*)((char*)p + (size_t)b * Tn * width * es); };
 
   // ---- per-utterance constants: text embedding (dit.py:50-72), cond columns, rotary table
-  for (int b = 0; b < B; ++b)
-    CFM_LAUNCH(cfm_text_pos_kernel<T>, (long long)Tn * td, mu + (size_t)b * Tn * td, c->pos_table, Tn, td, (T*)rows(ta, b, td));
+  CFM_LAUNCH_ROWS(cfm_text_pos_kernel<T>, (long long)Tn * td, B, mu, c->pos_table, Tn, td, (T*)ta);
   for (auto& blk : c->text) {
-    for (int b = 0; b < B; ++b)
-      CFM_LAUNCH(cfm_dwconv7_kernel<T>, (long long)Tn * td, (const T*)rows(ta, b, td), blk.dw, blk.db, Tn, td, (T*)rows(tb, b, td));
+    CFM_LAUNCH_ROWS(cfm_dwconv7_kernel<T>, (long long)Tn * td, B, (const T*)ta, blk.dw, blk.db, Tn, td, (T*)tb);
     GSV_RC(launch_layernorm(h->dtype, tb, 0, nullptr, 0, blk.ng, blk.nb, tb, 0, R, td, 1e-6f, s));
     ConvOpt og; og.post_act = ACT_GELU;
     GSV_RC(conv(h, s, blk.pw1, tb, td, R, tw, R, og));
-    for (int b = 0; b < B; ++b) {                      // GRN statistics are per utterance (norm over its own frames)
-      T* twb = (T*)rows(tw, b, 2 * td);
-      hipLaunchKernelGGL(cfm_grn_norm_kernel<T>, dim3(cdiv(2 * td, 64)), dim3(256), 0, s, (const T*)twb, Tn, 2 * td, gx);
-      hipLaunchKernelGGL(cfm_grn_apply_kernel<T>, dim3(std::min(1024, nblk((long long)Tn * 2 * td))), dim3(256), 0, s, twb, gx, blk.gg,
-                         blk.gb, Tn, 2 * td);
-    }
+    // GRN statistics are per utterance (norm over its own frames): gx [B][2 td]
+    hipLaunchKernelGGL(cfm_grn_norm_kernel<T>, dim3(cdiv(2 * td, 64), B), dim3(256), 0, s, (const T*)tw, Tn, 2 * td, gx);
+    hipLaunchKernelGGL(cfm_grn_apply_kernel<T>, dim3(std::min(1024, nblk((long long)Tn * 2 * td)), B), dim3(256), 0, s, (T*)tw, gx,
+                       blk.gg, blk.gb, Tn, 2 * td);
     GSV_HIP(hipGetLastError());
     ConvOpt orr; orr.res = ta;
     GSV_RC(conv(h, s, blk.pw2, tw, 2 * td, R, ta, R, orr));
   }
   {
     const int W = md + (ldin - (2 * md + td));
-    for (int b = 0; b < B; ++b)
-      CFM_LAUNCH(cfm_cond_kernel<T>, (long long)Tn * W, prompt ? prompt + (size_t)b * md * Tp : nullptr, Tn, Tp, md,
-                 (T*)rows(xin, b, ldin), ldin, md, 2 * md + td);
+    CFM_LAUNCH_ROWS(cfm_cond_kernel<T>, (long long)Tn * W, B, rw, Tn, md, (T*)xin, ldin, md, 2 * md + td);
     hipLaunchKernelGGL((cfm_copy_cols_kernel<T>), dim3(nblk((long long)R * td)), dim3(256), 0, s, (const T*)ta, td, R, td, (T*)xin,
                        ldin, 2 * md);
     GSV_HIP(hipGetLastError());
   }
   CFM_LAUNCH(cfm_rope_table_kernel, Tn * half, Tn, half, cs);
-  for (int b = 0; b < B; ++b)
-    CFM_LAUNCH(cfm_init_x_kernel, (long long)Tn * md, noise ? noise + (size_t)b * md * Tn : nullptr,
-               seed + 0x9E3779B97F4A7C15ull * (unsigned long long)b, temperature, Tn, Tp, md, x + (size_t)b * Tn * md);
-  CFM_LAUNCH(cfm_euler_kernel<T>, (long long)R * md, x, (const float*)nullptr, 0.f, R, Tn, Tp, md, (T*)xin, ldin);
+  CFM_LAUNCH_ROWS(cfm_init_x_kernel, (long long)Tn * md, B, noise, rw, temperature, Tn, md, x);
+  CFM_LAUNCH(cfm_euler_kernel<T>, (long long)R * md, x, (const float*)nullptr, 0.f, R, Tn, rw, md, (T*)xin, ldin);
 
   const float d = (float)(1.0 / N);
   const float att_scale = 1.f / sqrtf((float)g.dim_head);
@@ -378,7 +424,8 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
   static const int resident_mb = getenv("GSV_CFM_RESIDENT_MB") ? atoi(getenv("GSV_CFM_RESIDENT_MB")) : 150;   // scan: 1000 -> 3.03, 200 -> 2.95, 150 -> 2.94, 60 -> 2.97, 0 -> 2.99 ms per step
   const int resident = per_block ? (int)std::min<size_t>((size_t)g.depth, (size_t)resident_mb * 1024 * 1024 / per_block) : g.depth;
   void* vtb = nullptr;
-  if (flash) GSV_RC(need(h, "cfm_vt", (size_t)g.heads * 64 * ((Tn + 31) / 32 * 32) * 2, &vtb));
+  const long long vtz = (long long)g.heads * 64 * ((Tn + 31) / 32 * 32);   // one V^T buffer per utterance
+  if (flash) GSV_RC(need(h, "cfm_vt", (size_t)B * vtz * 2, &vtb));
   for (int step = 0; step < N; ++step) {
     // ---- InputEmbedding (dit.py:75-84): proj(cat(x, cond, text)) then + ConvPositionEmbedding
     ConvOpt o;
@@ -415,12 +462,13 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
         GSV_RC(conv(h, s, blk.qkv, nrm, D, R, qkv, R, oq));
       }
       if (!flash) CFM_LAUNCH(cfm_rope_kernel<T>, R * half * 2, (T*)qkv, 3 * inner, inner, R, Tn, half, cs);   // else inside the V^T launch
-      for (int b = 0; b < B; ++b) {
-        const T* qb = (const T*)rows(qkv, b, 3 * inner);
-        if (flash) {
-          GSV_RC(launch_flash_attn64_f16(qb, 3 * inner, (const _Float16*)qb + inner, 3 * inner, (const _Float16*)qb + 2 * inner, 3 * inner,
-                                         vtb, Tn, g.heads, att_scale, rows(ao, b, inner), inner, s, cs, half, fuse_qkv));
-        } else {
+      if (flash) {   // every utterance in the same two launches (V^T + rotary, attention): the row is a grid dimension
+        const _Float16* qb = (const _Float16*)qkv;
+        GSV_RC(launch_flash_attn64_f16_rows(qb, 3 * inner, qb + inner, 3 * inner, qb + 2 * inner, 3 * inner, vtb, Tn, g.heads, att_scale,
+                                            ao, inner, s, cs, half, fuse_qkv, B, (long long)Tn * 3 * inner, vtz, (long long)Tn * inner));
+      } else {
+        for (int b = 0; b < B; ++b) {
+          const T* qb = (const T*)rows(qkv, b, 3 * inner);
           GSV_RC(attention(h, s, qb, 3 * inner, 0, qb, 3 * inner, inner, 2 * inner, Tn, Tn, g.heads, g.dim_head, att_scale, nullptr,
                            nullptr, rows(ao, b, inner), inner));
         }
@@ -438,10 +486,21 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
     GSV_RC(launch_ln_mod<T>(hb, mf, mf + D, R, D, nrm, s));
     ConvOpt ov; ov.out_f32 = 1;
     GSV_RC(conv(h, s, c->proj_out, nrm, D, R, v, R, ov));
-    CFM_LAUNCH(cfm_euler_kernel<T>, (long long)R * md, x, (const float*)v, d, R, Tn, Tp, md, (T*)xin, ldin);
+    CFM_LAUNCH(cfm_euler_kernel<T>, (long long)R * md, x, (const float*)v, d, R, Tn, rw, md, (T*)xin, ldin);
   }
-  for (int b = 0; b < B; ++b) CFM_LAUNCH(cfm_out_kernel, (long long)Tn * md, x + (size_t)b * Tn * md, Tn, md, out + (size_t)b * md * Tn);
+  CFM_LAUNCH_ROWS(cfm_out_kernel, (long long)Tn * md, B, x, rw, Tn, md, out);
   return GSV_OK;
+}
+
+int cfm_run(gsv_cfm* c, hipStream_t s, const float* mu, const std::vector<CfmRow>& rows, int T, int N, const float* noise,
+            float temperature, float* out) {
+  float* mods = nullptr;
+  if (c->ctx.dtype == GSV_F16) {
+    GSV_RC(cfm_modulations<_Float16>(c, s, N, &mods));
+    return cfm_infer_batch<_Float16>(c, s, mods, mu, rows, T, N, noise, temperature, out);
+  }
+  GSV_RC(cfm_modulations<float>(c, s, N, &mods));
+  return cfm_infer_batch<float>(c, s, mods, mu, rows, T, N, noise, temperature, out);
 }
 
 }  // namespace
@@ -543,14 +602,25 @@ int gsv_cfm_inference(gsv_cfm_t* c, const float* mu, const float* prompt, int B,
   GSV_REQUIRE(c && c->finalized, "cfm_inference: handle not finalized");
   GSV_REQUIRE(mu && out && B > 0 && T > 0 && n_steps > 0 && n_steps <= 1024, "cfm_inference: bad argument");
   GSV_REQUIRE(Tp >= 0 && Tp <= T && (Tp == 0 || prompt), "cfm_inference: prompt length %d does not fit %d frames", Tp, T);
-  hipStream_t s = (hipStream_t)stream;
-  const auto& g = c->cfg;
-  float* mods = nullptr;
-  if (c->ctx.dtype == GSV_F16) GSV_RC(cfm_modulations<_Float16>(c, s, n_steps, &mods));
-  else GSV_RC(cfm_modulations<float>(c, s, n_steps, &mods));
-  if (c->ctx.dtype == GSV_F16) GSV_RC(cfm_infer_batch<_Float16>(c, s, mods, mu, prompt, B, T, Tp, n_steps, noise, temperature, seed, out));
-  else GSV_RC(cfm_infer_batch<float>(c, s, mods, mu, prompt, B, T, Tp, n_steps, noise, temperature, seed, out));
-  return GSV_OK;
+  std::vector<CfmRow> rows(B);
+  for (int b = 0; b < B; ++b)
+    rows[b] = CfmRow{Tp ? prompt + (size_t)b * c->cfg.mel_dim * Tp : nullptr, seed + 0x9E3779B97F4A7C15ull * (unsigned long long)b, Tp, 0};
+  return cfm_run(c, (hipStream_t)stream, mu, rows, T, n_steps, noise, temperature, out);
+}
+
+int gsv_cfm_inference_rows(gsv_cfm_t* c, const float* mu, const float* const* prompts, const int* Tp, int B, int T, int n_steps,
+                           const float* noise, const uint64_t* seeds, float temperature, float* out, gsv_stream_t stream) {
+  GSV_REQUIRE(c && c->finalized, "cfm_inference_rows: handle not finalized");
+  GSV_REQUIRE(mu && out && Tp && B > 0 && T > 0 && n_steps > 0 && n_steps <= 1024, "cfm_inference_rows: bad argument");
+  GSV_REQUIRE(B <= 65535, "cfm_inference_rows: %d rows exceed the grid's 65535", B);
+  GSV_REQUIRE(noise || seeds, "cfm_inference_rows: neither noise nor seeds given");
+  std::vector<CfmRow> rows(B);
+  for (int b = 0; b < B; ++b) {
+    GSV_REQUIRE(Tp[b] >= 0 && Tp[b] <= T && (Tp[b] == 0 || (prompts && prompts[b])),
+                "cfm_inference_rows: row %d: prompt length %d does not fit %d frames, or its prompt is null", b, Tp[b], T);
+    rows[b] = CfmRow{Tp[b] ? prompts[b] : nullptr, seeds ? (unsigned long long)seeds[b] : 0ull, Tp[b], 0};
+  }
+  return cfm_run(c, (hipStream_t)stream, mu, rows, T, n_steps, noise, temperature, out);
 }
 
 }  // extern "C"

@@ -240,6 +240,11 @@ int launch_conv_pair_seg(const ConvPairArgs& a, const int* row_seg, hipStream_t 
 int launch_flash_attn64_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* vt_buf, int T, int heads,
                             float scale, void* out, int ldo, hipStream_t s, const float* rope_cs = nullptr, int rope_half = 0,
                             bool vt_ready = false);   // vt_ready: V^T (and the rotary embedding) already produced by the QKV GEMM's epilogue
+// the same over `rows` utterances of T frames in the same two launches: row b's q / k / v start xz elements after row b-1's,
+// its output oz elements after, its V^T scratch vtz halfs after (vtz >= heads * 64 * ceil32(T))
+int launch_flash_attn64_f16_rows(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* vt_buf, int T, int heads,
+                                 float scale, void* out, int ldo, hipStream_t s, const float* rope_cs, int rope_half, bool vt_ready,
+                                 int rows, long long xz, long long vtz, long long oz);
 
 // enc_p self-attention with window-4 relative positions, fp16, head dim 96 (attn.hip)
 int launch_flash_rel96_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* vt_buf, int T, int heads,

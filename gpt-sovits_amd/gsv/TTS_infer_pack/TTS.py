@@ -692,34 +692,53 @@ class TTS:
                                               seed: int = 0, noise_fn: Optional[Callable] = None) -> List[torch.Tensor]:
         """TTS.py:1496-1609: all fragments of a batch concatenated, cut into overlapping chunks that go through ONE
         batched cfm.inference, vocoded as one sequence, re-joined with SOLA and split back per fragment."""
-        spec, fea_ref, ge, mel2, T_min = self._prompt_features()
+        prompt = self._prompt_features()
+        fea, lens, pad_len = self._fold_chunks(prompt, idx_list, semantic_tokens_list, batch_phones, speed)
+        mel2 = prompt[3]
+        nz = noise_fn(0, (fea.shape[0], 100, fea.shape[1])) if noise_fn else None
+        pred = self.vits_model.cfm.inference(fea, None, mel2, sample_steps, inference_cfg_rate=0, noise=nz, seed=seed)
+        return self._fold_audio(pred[:, :, mel2.shape[2]:], lens, pad_len)
+
+    @staticmethod
+    def _chunk_cuts(frames: int, chunk_len: int, ov: int) -> List[Tuple[int, int]]:
+        """TTS.py:1553-1570 as arithmetic: the [start, stop) cuts of a fold of `frames` feature frames after `ov` frames of
+        left padding, every cut starting `ov` before the previous one's end; the last one is padded to chunk_len"""
+        cuts, pos, total = [], 0, frames + ov
+        while True:
+            if pos != 0:
+                pos -= ov
+            if pos >= total:
+                return cuts
+            cuts.append((pos, min(pos + chunk_len, total)))
+            pos += chunk_len
+
+    def _fold_chunks(self, prompt: tuple, idx_list: List[int], semantic_tokens_list: List[torch.Tensor],
+                     batch_phones: List[torch.Tensor], speed: float) -> Tuple[torch.Tensor, List[int], int]:
+        """the CFM input rows of one fold with the voice of `prompt` (= _prompt_features()): [chunks, T_chunk, 512], every
+        row the voice's fea_ref followed by one chunk; the sentences' frame counts; the padding of the last chunk"""
+        spec, fea_ref, ge, mel2, T_min = prompt
         vc = self.vocoder_configs
-        chunk_len = vc["T_chunk"] - T_min
-        ov, up = vc["overlapped_len"], vc["upsample_rate"]
+        chunk_len, ov = vc["T_chunk"] - T_min, vc["overlapped_len"]
         feats, lens = [], []
         for i, idx in enumerate(idx_list):
             f, _ = self.vits_model.decode_encp(semantic_tokens_list[i][-idx:].view(1, 1, -1), batch_phones[i].view(1, -1), spec, ge, speed)
             feats.append(f)
             lens.append(int(f.shape[2]))
         padded = F.pad(torch.cat(feats, 2), (ov, 0))
-        chunks, pos, pad_len = [], 0, 0
-        while True:
-            if pos != 0:
-                pos -= ov
-            chunk = padded[:, :, pos:pos + chunk_len]
-            pos += chunk_len
-            if chunk.shape[-1] == 0:
-                break
+        chunks, pad_len = [], 0
+        for a, b in self._chunk_cuts(sum(lens), chunk_len, ov):
+            chunk = padded[:, :, a:b]
             pad_len = chunk_len - chunk.shape[2]
             if pad_len:
                 chunk = F.pad(chunk, (0, pad_len))
             chunks.append(chunk)
         chunks = torch.cat(chunks, 0)
-        bs = chunks.shape[0]
-        fea = torch.cat([fea_ref.repeat(bs, 1, 1), chunks], 2).transpose(2, 1)
-        nz = noise_fn(0, (bs, 100, fea.shape[1])) if noise_fn else None
-        pred = self.vits_model.cfm.inference(fea, None, mel2, sample_steps, inference_cfg_rate=0, noise=nz, seed=seed)
-        pred = pred[:, :, -chunk_len:]
+        return torch.cat([fea_ref.repeat(chunks.shape[0], 1, 1), chunks], 2).transpose(2, 1), lens, pad_len
+
+    def _fold_audio(self, pred: torch.Tensor, lens: List[int], pad_len: int) -> List[torch.Tensor]:
+        """the generated frames [chunks, 100, chunk_len] of one fold -> its sentences' waveforms (TTS.py:1581-1609)"""
+        vc = self.vocoder_configs
+        ov, up, chunk_len = vc["overlapped_len"], vc["upsample_rate"], pred.shape[2]
         pred = pred.permute(1, 0, 2).contiguous().view(pred.shape[1], -1).unsqueeze(0)
         audio = self.vocoder(denorm_spec(pred))[0][0]
         pieces, p = [], 0
@@ -975,9 +994,12 @@ class TTS:
     sovits_max_frames = 25600     # frames (gaps included) of one shared SoVITS pass: the largest fold this engine has run
 
     @staticmethod
-    def _voice_key(voice: dict) -> tuple:
-        """what makes two requests' SoVITS voices the same one: the stored spectrogram list and speaker embeddings themselves"""
-        return (id(voice.get("refer_spec")), id(voice.get("sv_emb")))
+    def _voice_key(voice: dict, fields: Tuple[str, ...] = ("refer_spec", "sv_emb")) -> tuple:
+        """what makes two requests' voices the same one for a shared stage: the stored objects the stage reads, themselves.
+        The SoVITS pass reads the spectrogram list and the speaker embeddings; the flow-matching pass _CFM_VOICE_FIELDS."""
+        return tuple(id(voice.get(f)) for f in fields)
+
+    _CFM_VOICE_FIELDS = ("refer_spec", "prompt_semantic", "phones", "ref_mel", "raw_audio")   # what _prompt_features reads
 
     def plan_sovits(self, plans: List[dict]) -> List[List[Tuple[int, int]]]:
         """The waveform launches of run_batch(shared_sovits=True).  `plans[r]` = {"voice", "opts", "folds"}; folds[bi] is
@@ -1010,14 +1032,44 @@ class TTS:
             launches.append(cur)
         return launches
 
+    cfm_max_rows = 32             # rows (chunks of T_chunk frames) of one shared flow-matching pass: where the measured cost per
+                                  # row stops falling, about 0.7 GB of workspace at T_chunk = 934
+
+    def plan_cfm(self, plans: List[dict]) -> List[List[Tuple[int, int, int]]]:
+        """The flow-matching passes of run_batch(shared_cfm=True).  `plans[r]` = {"opts", "T_min", "cfm_folds"}: T_min is the
+        prompt length _prompt_features() gives request r's voice, cfm_folds[bi] the feature frames decode_encp makes of the
+        sentences of to_batch batch bi (0 when nothing was generated).  Shared: v3 / v4 folds of parallel_infer requests with
+        at least one frame, at any speed.  A fold is cut into rows as using_vocoder_synthesis_batched_infer cuts it
+        (_chunk_cuts with the voice's chunk_len = T_chunk - T_min); every row is T_chunk frames whatever its voice.  Folds
+        are grouped by sample_steps, and a group's rows fill passes of at most cfm_max_rows rows in (r, bi, k) order, so a
+        fold may span two passes.  Returns the passes, lists of (r, bi, k)."""
+        if not getattr(self.configs, "use_vocoder", False):
+            return []
+        vc = self.vocoder_configs
+        groups: Dict[int, List[Tuple[int, int, int]]] = {}
+        for r, pl in enumerate(plans):
+            o = pl["opts"]
+            if not o["parallel_infer"]:
+                continue
+            for bi, frames in enumerate(pl["cfm_folds"]):
+                if frames <= 0:
+                    continue
+                n = len(self._chunk_cuts(int(frames), vc["T_chunk"] - int(pl["T_min"]), vc["overlapped_len"]))
+                groups.setdefault(int(o["sample_steps"]), []).extend((r, bi, k) for k in range(n))
+        cap = max(1, int(self.cfm_max_rows))
+        return [rows[i:i + cap] for rows in groups.values() for i in range(0, len(rows), cap)]
+
     @torch.no_grad()
-    def run_batch(self, requests: List[dict], shared_sovits: bool = False) -> List[Tuple[int, np.ndarray]]:
+    def run_batch(self, requests: List[dict], shared_sovits: bool = False, shared_cfm: bool = False) -> List[Tuple[int, np.ndarray]]:
         """Several requests, each with its own reference voice, through shared AR decodes.  Each request dict takes the
         keys run() accepts plus an optional "voice" (make_voice); without one it uses its ref_audio_path / prompt_text
         (through make_voice's LRU) or the current prompt cache.  Returns one (sr, int16 audio) per request, in order: what
         run(request) alone returns.  self.prompt_cache is not changed.  return_fragment is not supported.
         shared_sovits=True: the waveform stage of v1 / v2 / v2Pro / v2ProPlus requests at speed 1 runs as shared segmented
-        passes over all voices (plan_sovits, SynthesizerTrn.decode_segments) instead of one decode per to_batch batch."""
+        passes over all voices (plan_sovits, SynthesizerTrn.decode_segments) instead of one decode per to_batch batch.
+        shared_cfm=True: the flow-matching stage of v3 / v4 parallel_infer requests runs as shared passes over all voices'
+        chunks (plan_cfm, CFM.inference_rows), every row with its own voice's prompt mel and the noise key run() gives it;
+        vocoder and SOLA stay per fold.  Neither keyword changes anything for the other model family."""
         if self.t2s_model is None or self.vits_model is None:
             raise RuntimeError("init_t2s_weights / init_vits_weights first")
         self.stop_flag = False
@@ -1102,6 +1154,40 @@ class TTS:
                 for (r, bi), wav, cut in zip(launch, wavs, cuts):
                     shared[(r, bi)] = list(torch.split(wav[0, 0], cut))
             self.vits_model.invalidate_refer()          # the engine's cached reference terms are the last slot's voice
+        # ---- shared flow-matching passes: every chunk of every fold is one row with its voice's prompt
+        if shared_cfm and self.configs.use_vocoder:
+            dev = self.configs.device
+            prompts: Dict[tuple, tuple] = {}            # _prompt_features() per distinct voice
+            fold_in: Dict[Tuple[int, int], tuple] = {}  # (rows [chunks, T_chunk, 512], lens, pad_len)
+            for r, pl in enumerate(plans):
+                pl["cfm_folds"], pl["T_min"] = [0] * len(pl["data"]), 0
+                if not pl["opts"]["parallel_infer"] or not pl["data"]:
+                    continue
+                with self._with_prompt_cache(dict(pl["voice"])):
+                    vk = pl["cfm_voice"] = self._voice_key(pl["voice"], self._CFM_VOICE_FIELDS)
+                    if vk not in prompts:
+                        prompts[vk] = self._prompt_features()
+                    prompt = prompts[vk]
+                    pl["T_min"] = prompt[4]
+                    for bi, item in enumerate(pl["data"]):
+                        idx_list = kept(r, bi)[1]
+                        if sum(int(i) for i in idx_list) <= 0:
+                            continue
+                        fold_in[(r, bi)] = self._fold_chunks(prompt, idx_list, preds[r][bi], [ph.to(dev) for ph in item["phones"]],
+                                                             pl["opts"]["speed_factor"])
+                        pl["cfm_folds"][bi] = sum(fold_in[(r, bi)][1])
+            fold_out: Dict[Tuple[int, int], list] = {}
+            for rows in self.plan_cfm(plans):
+                mu = torch.cat([fold_in[(r, bi)][0][k:k + 1] for r, bi, k in rows], 0)
+                mels = [prompts[plans[r]["cfm_voice"]][3] for r, _, _ in rows]
+                seeds = [(plans[r]["actual_seed"] + bi + 0x9E3779B97F4A7C15 * k) & 0xFFFFFFFFFFFFFFFF for r, bi, k in rows]
+                pred = self.vits_model.cfm.inference_rows(mu, mels, plans[rows[0][0]]["opts"]["sample_steps"], seeds=seeds)
+                for n, (r, bi, k) in enumerate(rows):
+                    fold_out.setdefault((r, bi), []).append(pred[n:n + 1, :, mels[n].shape[2]:])
+            for (r, bi), got in fold_out.items():        # a fold is finished when all its rows are back
+                fea, lens, pad_len = fold_in[(r, bi)]
+                assert len(got) == fea.shape[0]
+                shared[(r, bi)] = self._fold_audio(torch.cat(got, 0), lens, pad_len)
         results = []
         for r, pl in enumerate(plans):
             o = pl["opts"]

@@ -389,3 +389,43 @@ class CFM:
                                                     out.data_ptr(), C.c_void_p(dit.stream.cuda_stream)), "gsv_cfm_inference")
             dit.stream.synchronize()
         return out.to(mu.dtype if mu.dtype in (torch.float16, torch.float32) else torch.float32)
+
+    @torch.no_grad()
+    def inference_rows(self, mu, prompts, n_timesteps, temperature=1.0, noise=None, seeds=None):
+        """`inference` for B rows that each have their own prompt (`gsv_cfm_inference_rows`): mu [B, T, text_dim]; prompts a
+        list of B tensors [1, in_channels, Tp_b], 0 <= Tp_b <= T -> [B, in_channels, T], row b's first Tp_b frames zero.
+        `seeds` (B ints) are the rows' own noise keys, taken as they are: row b of `inference(seed=s)` is seeds[b] =
+        s + 0x9E3779B97F4A7C15 * b here.  `noise` [B, in_channels, T] pins the draw instead."""
+        dit = self.estimator
+        if not dit._loaded:
+            raise RuntimeError("DiT.load_state_dict() first")
+        if mu.dim() != 3 or mu.shape[2] != dit.text_dim or mu.shape[1] < 1:
+            raise ValueError(f"expected mu of shape [B, T>=1, {dit.text_dim}], got {tuple(mu.shape)}")
+        B, T = int(mu.shape[0]), int(mu.shape[1])
+        if B < 1 or len(prompts) != B:
+            raise ValueError(f"expected {B} >= 1 prompts, one per row of mu, got {len(prompts)}")
+        for b, p in enumerate(prompts):
+            if p.dim() != 3 or p.shape[0] != 1 or p.shape[1] != self.in_channels or p.shape[2] > T:
+                raise ValueError(f"expected prompt {b} of shape [1, {self.in_channels}, Tp<={T}], got {tuple(p.shape)}")
+        if noise is None and seeds is None:
+            raise ValueError("inference_rows needs `noise` or `seeds`")
+        if noise is not None and tuple(noise.shape) != (B, self.in_channels, T):
+            raise ValueError(f"noise must have shape {(B, self.in_channels, T)}")
+        if seeds is not None and len(seeds) != B:
+            raise ValueError(f"expected {B} seeds, got {len(seeds)}")
+        dev = dit.device
+        with torch.cuda.device(dev):
+            m = mu.to(dev, torch.float32).contiguous()
+            ps = [p.to(dev, torch.float32).contiguous() for p in prompts]
+            nz = noise.to(dev, torch.float32).contiguous() if noise is not None else None
+            out = torch.empty(B, self.in_channels, T, dtype=torch.float32, device=dev)
+            ptrs = (C.c_void_p * B)(*[p.data_ptr() if p.shape[2] else None for p in ps])
+            tps = (C.c_int * B)(*[int(p.shape[2]) for p in ps])
+            sd = (C.c_uint64 * B)(*[int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds]) if seeds is not None else None
+            dit.stream.wait_stream(torch.cuda.current_stream(dev))
+            _lib.check(_lib.lib().gsv_cfm_inference_rows(dit._h, m.data_ptr(), ptrs, tps, B, T, int(n_timesteps),
+                                                         nz.data_ptr() if nz is not None else None, sd, float(temperature),
+                                                         out.data_ptr(), C.c_void_p(dit.stream.cuda_stream)),
+                       "gsv_cfm_inference_rows")
+            dit.stream.synchronize()
+        return out.to(mu.dtype if mu.dtype in (torch.float16, torch.float32) else torch.float32)

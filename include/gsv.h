@@ -268,6 +268,14 @@ int gsv_cfm_finalize(gsv_cfm_t* h);
  * reference).  n_steps Euler steps with d = 1/n_steps. */
 int gsv_cfm_inference(gsv_cfm_t* h, const float* mu, const float* prompt, int B, int T, int Tp, int n_steps,
                       const float* noise, float temperature, uint64_t seed, float* out, gsv_stream_t stream);
+/* The same over B rows that each have their own prompt: prompts [host] B device pointers, row b's fp32 [mel_dim][Tp[b]]
+ * (may be NULL where Tp[b] == 0), Tp [host] B lengths, 0 <= Tp[b] <= T; seeds [host] B noise keys, used where noise is NULL
+ * (one of the two must be given).  Row b draws what gsv_cfm_inference draws for a row whose seed + 0x9E3779B97F4A7C15 * b
+ * equals seeds[b]: no offset is added here.  out [dev] fp32 [B][mel_dim][T], row b's first Tp[b] frames zero.  A bad
+ * argument returns an error before anything is launched. */
+int gsv_cfm_inference_rows(gsv_cfm_t* h, const float* mu, const float* const* prompts, const int* Tp, int B, int T,
+                           int n_steps, const float* noise, const uint64_t* seeds, float temperature, float* out,
+                           gsv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * SOLA stitching of the chunked v3/v4 vocoder output (H17, TTS.sola_algorithm, TTS_infer_pack/TTS.py:1611-1637).

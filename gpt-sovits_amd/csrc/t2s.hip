@@ -725,7 +725,6 @@ int mega_prof_arm(MegaArgs& a, int budget, hipStream_t s) {
   GSV_HIP(hipMemsetAsync(a.prof, 0, MEGA_PROF_N * 8, s));
   a.prof_step = env_int("GSV_MEGA_PROF_STEP", 5);
   a.prof_layer = env_int("GSV_MEGA_PROF_LAYER", 7);
-  a.prof_quad = env_int("GSV_MEGA_PROF_QUAD", 0);
   return GSV_OK;
 }
 

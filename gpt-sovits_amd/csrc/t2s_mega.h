@@ -37,7 +37,7 @@ struct MegaArgs {
   unsigned long long* hop; unsigned* err;
   int B, L, V, nsteps;
   unsigned long long* prof;       // optional [256 workgroups][8 waves][32] s_memtime stamps of one (step, layer); null = off
-  int prof_step, prof_layer, prof_quad;
+  int prof_step, prof_layer;      // single-quad launches only: the pipelined kernel (B > 32) carries no stamps
   int hint_mask;                  // hops that poll a hint line before the full pass: bit 0 A, 1 B, 2 C, 3 D; bit 4: two polls in flight (sweep2); bit 7: spread hint lines; bits 8-12: miss threshold (sweep2)
   int map_shared;                 // 1: workgroups reading the same weight slice share an XCD (default), 0: group = XCD
   int ring;                       // hop buffer sets used round-robin over (step, layer); > 1 enables L2-shared payload reads

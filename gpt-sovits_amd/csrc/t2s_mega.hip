@@ -29,16 +29,13 @@
 //     t2s_sample.h), which also emits the next input embedding: the step's tail is two more hops.
 //   * (round 3) more than 32 rows: a group serves up to four QUADS of rows, phase by phase one after the other with the weight
 //     slices it already holds; the comm waves sweep quad i + 1 into a second copy of the operand image while the compute
-//     waves work on quad i (comm_role_pipe / compute_role_pipe, MODE 2).  The step is latency-bound, so rows are added in
+//     waves work on quad i (comm_role_pipe / compute_role_pipe).  The step is latency-bound, so rows are added in
 //     time, not in tile width: 128 rows cost 0.79 ms per step against 4 x 0.30.
+//   * the arithmetic of a phase (sweep + LayerNorm, reduce, publish, ...) is written once, as a "phase body" shared by the
+//     single-quad and the pipelined roles; the four role functions are the two synchronisation skeletons.
 //   * weight slices are loaded with the DEFAULT cache policy (the 8 same-slice workgroups of an XCD share one L2 fill), K/V
 //     non-temporal (read once per step; keeps the weights in the Infinity Cache).
 #include <math.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <type_traits>
-
 #include "t2s_mega.h"
 
 namespace gsv {
@@ -89,7 +86,7 @@ constexpr int HOP_GROUP_ALL = QMAX * HOP_GROUP;    // a group's buffers: quad af
 
 // LDS carve (bytes); everything dynamic so the base stays 16-byte aligned
 constexpr int L_XRES = 0;                                     // fp32 [RMAX][512]   LayerNorm output (residual operand); one quad per group
-constexpr int L_RS = 0;                                       // f4 [2][QMAX][64]   the same 8 KB in multi-quad launches: residual operands kept per quad
+constexpr int L_RS = 0;                                       // f4 [2][QMAX][64]   the same 8 KB in pipelined launches: residual operands parked per quad (rs_at)
 constexpr int L_XS = L_XRES + RMAX * 512 * 4;                 // half [2][RMAX][XS_LD] LayerNorm output (MFMA operand); second copy: pipelined quads
 constexpr int L_AT = L_XS + 2 * RMAX * XS_LD * 2;             // half [2][RMAX][XS_LD] attention output of all heads
 constexpr int L_HS = L_AT + 2 * RMAX * XS_LD * 2;             // half [2][RMAX][HS_LD] FFN hidden
@@ -385,12 +382,12 @@ __device__ __forceinline__ bool sweep_wide(const Ctx& c, gu64* g, unsigned epoch
 }
 
 // LayerNorm of one row delivered by sweep_wide<4>: lane m holds elements j * 128 + 2 m + {0, 1}; gm / bt in the same order;
-// gamma == null: identity (layer 0's input is the embedding itself)
-__device__ __forceinline__ void ln_row_wide(const Ctx& c, int row, const u4v (&v)[4], const float* gm, const float* bt) {
-  float x[8];
+// norm == false: identity (layer 0's input is the embedding itself).  The row goes to XS copy `copy` as the MFMA operand;
+// what becomes of the fp32 values x (the residual operand) is the caller's: ln_row_wide, ln_row_pipe.
+__device__ __forceinline__ void ln_core(const Ctx& c, int row, int copy, const u4v (&v)[4], bool norm, const float (&gm)[8], const float (&bt)[8], float (&x)[8]) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) { x[2 * j] = __uint_as_float(v[j][0]); x[2 * j + 1] = __uint_as_float(v[j][2]); }
-  if (gm) {
+  if (norm) {
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) s += x[k];
@@ -402,13 +399,34 @@ __device__ __forceinline__ void ln_row_wide(const Ctx& c, int row, const u4v (&v
 #pragma unroll
     for (int k = 0; k < 8; ++k) x[k] = (x[k] - mean) * rstd * gm[k] + bt[k];
   }
-  float* xr = (float*)(c.smem + L_XRES) + row * D + 2 * c.lane;
-  _Float16* xs = (_Float16*)(c.smem + L_XS) + row * XS_LD + 2 * c.lane;
+  _Float16* xs = (_Float16*)(c.smem + L_XS) + (copy * RMAX + row) * XS_LD + 2 * c.lane;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    *(f2*)(xr + j * 128) = (f2){x[2 * j], x[2 * j + 1]};
-    *(h2*)(xs + j * 128) = (h2){(_Float16)x[2 * j], (_Float16)x[2 * j + 1]};
-  }
+  for (int j = 0; j < 4; ++j) *(h2*)(xs + j * 128) = (h2){(_Float16)x[2 * j], (_Float16)x[2 * j + 1]};
+}
+
+// single quad: XS copy 0, and the whole fp32 row -> XRES (the reducing waves read their residual columns from it)
+__device__ __forceinline__ void ln_row_wide(const Ctx& c, int row, const u4v (&v)[4], bool norm, const float (&gm)[8], const float (&bt)[8]) {
+  float x[8];
+  ln_core(c, row, 0, v, norm, gm, bt, x);
+  float* xr = (float*)(c.smem + L_XRES) + row * D + 2 * c.lane;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) *(f2*)(xr + j * 128) = (f2){x[2 * j], x[2 * j + 1]};
+}
+
+// pipelined quads: XS copy `buf`; XRES would be overwritten by the next quad's LayerNorm before the phase that needs it comes
+// round, so only the member's 16 residual columns of the row are kept, parked per quad in rs[which][qd] (which = 0: operand of
+// the out-projection, 1: of FFN2; f4 per lane of the reducing wave, 1 KB per quad)
+__device__ __forceinline__ f4* rs_at(unsigned char* smem, int which, int qd, int lane) { return (f4*)(smem + L_RS) + (which * QMAX + qd) * 64 + lane; }
+__device__ __forceinline__ void ln_row_pipe(const Ctx& c, int row, int buf, int which, const u4v (&v)[4], bool norm, const float (&gm)[8], const float (&bt)[8]) {
+  float x[8];
+  ln_core(c, row, buf, v, norm, gm, bt, x);
+  // columns [16 member, +16) of this row: chunk j = member / 8, lanes 8 (member % 8) .. + 7, two elements each; the reducing
+  // wave's lane r + 16 g holds columns 4 g .. 4 g + 3 of row r
+  const int jm = c.member >> 3, m0 = 8 * (c.member & 7), dm = c.lane - m0;
+  const float e0 = jm == 0 ? x[0] : jm == 1 ? x[2] : jm == 2 ? x[4] : x[6];
+  const float e1 = jm == 0 ? x[1] : jm == 1 ? x[3] : jm == 2 ? x[5] : x[7];
+  if (dm >= 0 && dm < 8)
+    *(f2*)((float*)rs_at(c.smem, which, c.qd, row + 16 * (dm >> 1)) + 2 * (dm & 1)) = (f2){e0, e1};
 }
 
 // compute waves: NT tiles x 4 k-steps of this wave's 128-wide K chunk `kc` against the activation image `act`
@@ -762,272 +780,368 @@ __device__ __forceinline__ void kv_stage_store(const Ctx& q, int qd, int extra, 
     } \
 } while (0)
 
-// MULTI = false: the group has ONE quad (B <= 32), the quad loops below run once with qd = 0 and fold away.
-// MULTI = true (32 < B <= 128): a group serves up to QMAX quads.  Every phase of a layer is run for quad 0, 1, ... in turn with
-// the weights the compute waves already hold; each quad has its own hop buffers, so while a member works on quad q the other
-// members' publishes of quad q + 1 are already on their way: the hop latency that a single quad waits out four times per layer
-// is overlapped with the other quads' compute, and the weights are still streamed once per layer.
-template <bool MULTI, bool PROF>
+// ---------------------------------------------------------------------------------------------------------------
+// Phase bodies.  Each is written ONCE and used by the single-quad roles (comm_role / compute_role) and by the pipelined
+// ones (comm_role_pipe / compute_role_pipe).  What differs between the two is a parameter: the copy of the operand image,
+// the residual operand (read from XRES by the single quad, parked per quad by the pipelined LayerNorm), the hop buffers of
+// the quad.  The roles below hold only the synchronisation skeleton: barriers, weight requests, hop epochs.
+// Form: the bodies take their few scalars and pointers BY VALUE (the sampler as a function taking the context by
+// reference cost > 1000 spilled VGPRs, see MG_RUN_SAMPLER) and weight arrays as array references, like gemm_chunk.
+// ---------------------------------------------------------------------------------------------------------------
+// copy `copy` (0 | 1) of the operand images; the single quad uses copy 0 only
+__device__ __forceinline__ _Float16* xs_img(unsigned char* smem, int copy) { return (_Float16*)(smem + L_XS) + copy * RMAX * XS_LD; }
+__device__ __forceinline__ _Float16* at_img(unsigned char* smem, int copy) { return (_Float16*)(smem + L_AT) + copy * RMAX * XS_LD; }
+__device__ __forceinline__ _Float16* hs_img(unsigned char* smem, int copy) { return (_Float16*)(smem + L_HS) + copy * RMAX * HS_LD; }
+
+// this wave's packed weight slices: P1 by head; out-projection | FFN1 | FFN2 by member (`off` in KiB-instructions); logits
+__device__ __forceinline__ const h8* p1_src(const MegaArgs& a, const Ctx& q, int layer) {
+  return a.wpack + ((size_t)layer * LAYER_HALFS + ((size_t)q.head * 4 + q.cw) * WI_P1 * 512) / 8 + q.lane;
+}
+__device__ __forceinline__ const h8* pm_src(const MegaArgs& a, const Ctx& q, int layer, int off) {
+  return a.wpack + ((size_t)layer * LAYER_HALFS + P1_HALFS + (((size_t)q.member * 4 + q.cw) * (WI_P2 + WI_P3 + WI_P4) + off) * 512) / 8 + q.lane;
+}
+__device__ __forceinline__ const h8* lg_src(const MegaArgs& a, const Ctx& q) {
+  return a.lpack + (((size_t)q.member * 4 + q.cw) * WI_LG * 512) / 8 + q.lane;
+}
+
+// ---- comm waves ----
+// One row of hop A, hop C or the tail's hop A' (at `g`) -> LayerNorm -> XS copy `copy`.  ya != null: the call's first
+// step reads its input embedding from there instead of sweeping (s == 0 && l == 0).  The single quad keeps the fp32 row in
+// XRES; PIPE parks the member's residual columns in rs[which] of the current quad.
+template <bool PIPE>
+__device__ __forceinline__ void sweep_ln(const Ctx& q, int ra, gu64* g, unsigned ep, unsigned code, bool hint, const float* ya,
+                                         int copy, int which, bool norm, const float (&gm)[8], const float (&bt)[8]) {
+  if (ra >= q.R) return;
+  u4v qa[4];
+  bool ok = true;
+  if (ya) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { const f2 y2 = *(const f2*)(ya + 2 * q.lane + j * 128); qa[j] = (u4v){__float_as_uint(y2[0]), 0u, __float_as_uint(y2[1]), 0u}; }
+  } else {
+    ok = sweep_wide<4>(q, g + ra * 512, ep, qa, code, hint);
+  }
+  if (!ok) return;
+  if constexpr (PIPE) ln_row_pipe(q, ra, copy, which, qa, norm, gm, bt);
+  else ln_row_wide(q, ra, qa, norm, gm, bt);
+}
+
+// One row of hop B (NQ = 2: attention output) or hop D (NQ = 8: FFN hidden) at `g` -> the row of the AT / HS copy `img`
+template <int NQ>
+__device__ __forceinline__ void sweep_img(const Ctx& q, int ra, gu64* g, unsigned ep, unsigned code, bool hint, _Float16* img, int ld) {
+  if (ra >= q.R) return;
+  u4v v[NQ];
+  if (sweep_wide<NQ>(q, g + ra * NQ * 128, ep, v, code, hint)) {
+    unsigned* d = (unsigned*)img + ra * (ld / 2) + 2 * q.lane;
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) *(u2v*)(d + j * 128) = (u2v){v[j][0], v[j][2]};
+  }
+}
+
+// Row state published by the samplers with the embedding: {active} per row.  ALL quads' rows, in front of the step's first
+// barrier, so that every later slot of the step (K/V prefetch, exit test) sees the step's state.  One wave.
+__device__ __forceinline__ void sweep_row_state(const Ctx& q, int nq, int s, unsigned ep) {
+  for (int q2 = 0; q2 < nq; ++q2) {
+    Ctx t = q;
+    set_quad(t, q2);
+    unsigned sv[1];
+    if (sweep<1>(t, hop_slot(t, s, 0) + HOP_ST, t.R, ep, sv, 2u) && t.lane < t.R) {
+      const int was = st_active(t)[t.lane], now = (int)(sv[0] & 1u);
+      if (was) { st_step(t)[t.lane] += 1; if (now) st_kvlen(t)[t.lane] += 1; }
+      st_active(t)[t.lane] = now;
+    }
+  }
+}
+
+// LayerNorm parameters of a layer, loaded in P1's poll-free stretch (a load issued right before a sweep would sit in front
+// of its polls: a wave's memory operations return in order): norm1 for hop C, norm2 for the next hop A / the tail
+__device__ __forceinline__ void ln_params_load(const float* lp, int lane, float (&gC)[8], float (&bC)[8], float (&gA)[8], float (&bA)[8]) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int el = (k >> 1) * 128 + 2 * lane + (k & 1);      // the element sweep_wide<4> delivers in slot k
+    gC[k] = lp[FP_N1W + el]; bC[k] = lp[FP_N1B + el];
+    gA[k] = lp[FP_N2W + el]; bA[k] = lp[FP_N2B + el];
+  }
+}
+
+// ---- compute waves ----
+// lane j < 24 of every wave reduces 4 values of q | k | v of the wave's OWN attention row (qkv_reduce): their bias
+__device__ __forceinline__ f4 qkv_bias(const float* lp, int lane, int head) {
+  const int rj_which = (lane >> 3) % 3, rj_e = 4 * (lane & 7);
+  return lane < 24 ? *(const f4*)(lp + FP_QKVB + rj_which * D + head * HD + rj_e) : (f4){0.f, 0.f, 0.f, 0.f};
+}
+// split-K reduce of q, k, v (+ bias) by the wave that consumes them: each attention wave sums the 96 values of ITS row
+// (both waves of a row do, and write identical bytes), so that no barrier stands between the reduce and the attention
+// -- the workgroup-wide reduce + compute-only barrier here were 0.7 us of every layer (stamps 4-7).  Same summation
+// order as before: ((w0 + w1) + w2) + w3 + bias.
+__device__ __forceinline__ void qkv_reduce(unsigned char* smem, int lane, int cw, int half, int R, f4 p1_bias) {
+  const int rj_which = (lane >> 3) % 3, rj_e = 4 * (lane & 7);
+  const f4* red = (const f4*)(smem + L_RED);
+  _Float16* qkv_s = (_Float16*)(smem + L_QKV);
+  const int ro = cw / 2, r = 2 * ro + half;
+  if (lane < 24 && r < R) {
+    const int tile = rj_which * 2 + (rj_e >> 4), ln = r + 16 * ((rj_e & 15) >> 2);
+    const f4 v0 = red[red_idx(0 * 6 + tile, ln)], v1 = red[red_idx(1 * 6 + tile, ln)], v2 = red[red_idx(2 * 6 + tile, ln)],
+             v3 = red[red_idx(3 * 6 + tile, ln)];
+    f4 v = v0;
+    v += v1; v += v2; v += v3;
+    v += p1_bias;
+    *(h4*)(qkv_s + (ro * 3 + rj_which) * HD + rj_e) = (h4){(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};    // the arena append of k, v follows (arena_append)
+  }
+  asm volatile("" ::: "memory");                      // the attention's reads of qkv_s stay behind the writes (same wave: in order)
+}
+
+// one wave combines the partials of the 2 attention waves of each own row (lane = ro * 32 + e) and publishes hop B
+__device__ __forceinline__ void attn_combine_publish(unsigned char* smem, int lane, int head, int half, int R, gu64* hop_b, unsigned ep) {
+  const float* s_m = (const float*)(smem + L_ATT);
+  const float* s_acc = s_m + 8;
+  const int ro = lane >> 5, e = lane & 31, r = 2 * ro + half;
+  float M = -INFINITY;
+#pragma unroll
+  for (int w = 0; w < 2; ++w) M = fmaxf(M, s_m[2 * ro + w]);
+  float o = 0.f;
+  if (M != -INFINITY) {
+    float Lsum = 0.f, num = 0.f;
+#pragma unroll
+    for (int w = 0; w < 2; ++w) {
+      const float mw = s_m[2 * ro + w];
+      const float ew = mw == -INFINITY ? 0.f : __expf(mw - M);
+      const float* pa = s_acc + (2 * ro + w) * 4 * 36;
+      Lsum += ((pa[32] + pa[36 + 32]) + (pa[72 + 32] + pa[108 + 32])) * ew;
+      num += ((pa[e] + pa[36 + e]) + (pa[72 + e] + pa[108 + e])) * ew;
+    }
+    o = num / Lsum;
+  }
+  const float o2 = dpp_f<DPP_QUAD_XOR1>(o);            // lane ^ 1
+  // 16 granules (one 128-B line) per own row, written by one wave instruction
+  if (r < R && !(e & 1)) gstore(hop_b + r * 256 + (head * HD + e) / 2, ep, pack_h2(o, o2));
+}
+
+// K/V arena append of this step's k, v of the own rows (rows 2 ro + half of the quad whose state and first batch row are
+// given), from the LDS copy the attention used; lanes 0..31 of one wave
+__device__ __forceinline__ void arena_append(const MegaArgs& a, unsigned char* smem, int lane, int l, int head, int half, int R,
+                                             int b0, const lds_int* active, const lds_int* kvlen) {
+  const int ro = lane >> 4, which = (lane >> 3) & 1, e = 4 * (lane & 7), r = 2 * ro + half;
+  if (r < R && active[r]) {
+    const int pos = kvlen[r];
+    if (pos < a.smax)
+      *(h4*)(a.kv + ((size_t)(l * 2 + which)) * a.kv_layer_stride + ((size_t)(b0 + MG_GROUPS * r) * NH + head) * (size_t)a.smax * HD +
+             (size_t)pos * HD + e) = *(const h4*)((const _Float16*)(smem + L_QKV) + (ro * 3 + 1 + which) * HD + e);
+  }
+}
+
+// test hook (gsv_t2s_debug_stall, tests only): that member of group 0 skips ONE publish of hop C, so that the group's
+// bounded waits must end the launch with an error instead of hanging
+__device__ __forceinline__ bool stall_hook(const MegaArgs& a, int member, int group, int s, int l, int qd) {
+  return a.test_stall && member == a.test_stall - 1 && group == 0 && s == 2 && l == 3 && qd == 0;
+}
+
+// One wave: split-K reduce of the member's 16 columns + bias + residual `xr` (the lane's f4 of the LayerNorm output the
+// GEMM's input came from) -> fp32 row segment published at `dst` (+ row * 512): the out-projection's y1 to hop C, FFN2's
+// y2 to hop A of the next layer (hop A' of the logits after the last).  skip: stall_hook.
+__device__ __forceinline__ void reduce_residual_publish(unsigned char* smem, int lane, int member, int R, f4 bias, f4 xr, gu64* dst,
+                                                        unsigned ep, bool skip) {
+  const f4* red = (const f4*)(smem + L_RED);
+  const int r = lane & 15;
+  if (r < R) {
+    const f4 v0 = red[red_idx(0, lane)], v1 = red[red_idx(1, lane)], v2 = red[red_idx(2, lane)], v3 = red[red_idx(3, lane)];
+    f4 v = v0;
+    v += v1; v += v2; v += v3;
+    v += bias;
+    v += xr;
+    *(f4*)((float*)(smem + L_STAGE) + r * 16 + 4 * (lane >> 4)) = v;
+  }
+  // transposed through LDS (same wave): lane = row * 16 + column, so each row's 16 granules = one 128-B line
+  // written whole by ONE store instruction (scattered 8-B write-through stores made every hop 2-3x slower)
+  if (lane < R * 16 && !skip)
+    gstore(dst + (lane >> 4) * 512 + 16 * member + (lane & 15), ep, __float_as_uint(((const float*)(smem + L_STAGE))[lane]));
+}
+
+// FFN1: every wave publishes its own tile (+ bias, ReLU) to hop D: 16 columns = 8 half-pair granules = 64 contiguous bytes
+// per row, the rows of the quad by one store instruction (transposed through the wave's own LDS patch: lane = row * 8 + granule)
+__device__ __forceinline__ void ffn1_publish(unsigned char* smem, int lane, int cw, int member, int R, f4 v, f4 bias, gu64* hop_d, unsigned ep) {
+  const int r = lane & 15;
+  unsigned* stage = (unsigned*)(smem + L_STAGE) + cw * 64;
+  v += bias;
+  if (r < R) {
+    const int w0 = r * 8 + 2 * (lane >> 4);
+    stage[w0] = pack_h2(fmaxf(v[0], 0.f), fmaxf(v[1], 0.f));
+    stage[w0 + 1] = pack_h2(fmaxf(v[2], 0.f), fmaxf(v[3], 0.f));
+  }
+  if (lane < R * 8) gstore(hop_d + (lane >> 3) * 1024 + 32 * member + 8 * cw + (lane & 7), ep, stage[lane]);
+}
+
+// FFN2 over K = 2048: each wave chains its 4 chunks of 128 of the hidden image `hs` into ONE accumulator (the MFMA forwards
+// a dependent accumulator without a stall): one partial per wave like the other phases, instead of 16 per workgroup through
+// LDS.  The operand reads of chunk cc + 1 are in flight under the MFMAs of chunk cc (two register sets of 4 fragments; same
+// MFMA order, bit-identical): 295.8 -> 292.6 us per step over 4 pairs (3 of 4), profiles/r03_ab_ffn2_operand_prefetch.txt
+__device__ __forceinline__ void ffn2_chunks(const h8 (&w)[WI_P4], const _Float16* hs, unsigned char* smem, int lane, int cw) {
+  const int rowl = lane & 15, kg = lane >> 4;
+  f4* red = (f4*)(smem + L_RED);
+  f4 acc = (f4){0.f, 0.f, 0.f, 0.f};
+  const _Float16* bp0 = hs + (rowl & (RMAX - 1)) * HS_LD + (4 * cw) * 128 + 8 * kg;
+  h8 bA[4], bB[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) bA[ks] = *(const h8*)(bp0 + 32 * ks);
+#pragma unroll
+  for (int cc = 0; cc < 4; cc += 2) {
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) bB[ks] = *(const h8*)(bp0 + (cc + 1) * 128 + 32 * ks);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[cc * 4 + ks], bA[ks], acc, 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    if (cc + 2 < 4) {
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) bA[ks] = *(const h8*)(bp0 + (cc + 2) * 128 + 32 * ks);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[(cc + 1) * 4 + ks], bB[ks], acc, 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  if (rowl < RMAX) red[red_idx(cw, lane)] = acc;
+}
+
+// logits: wave t < 3 reduces and publishes tile t of the member (tiles member, member + 32, and tile 64 on member 0) to hop E
+__device__ __forceinline__ void logits_publish(unsigned char* smem, int lane, int t, int member, int R, int V, gu64* hop_e, unsigned ep) {
+  const f4* red = (const f4*)(smem + L_RED);
+  const int r = lane & 15;
+  const int tile = t == 0 ? member : (t == 1 ? member + 32 : 64);
+  float* stage = (float*)(smem + L_STAGE) + t * 256;
+  if (r < R) {
+    f4 v = red[red_idx(0 * 3 + t, lane)];
+    v += red[red_idx(1 * 3 + t, lane)]; v += red[red_idx(2 * 3 + t, lane)]; v += red[red_idx(3 * 3 + t, lane)];
+    *(f4*)(stage + r * 16 + 4 * (lane >> 4)) = v;
+  }
+  if (lane < R * 16 && (t < 2 || member == 0) && 16 * tile + (lane & 15) < V)
+    gstore(hop_e + (lane >> 4) * VPAD + 16 * tile + (lane & 15), ep, __float_as_uint(stage[lane]));
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// One quad per group (B <= 32).  Every phase waits out its hop: the comm waves sweep it into the operand image, B1, the
+// compute waves multiply, B2, reduce and publish.
+// ---------------------------------------------------------------------------------------------------------------
+template <bool PROF>
 __device__ __forceinline__ void comm_role(const MegaArgs& a, const Ctx& c0, const StepParams& sp) {
   Ctx q = c0;
   unsigned char* smem = c0.smem;
-  const int Rtot = c0.Rtot;
-  const int nq = MULTI ? (Rtot + RMAX - 1) / RMAX : 1;
-  const int V = a.V, EOS = a.V - 1;
-  const bool sampler = c0.member < Rtot && c0.cw == 0;   // wave 0 of member m samples the group's local row m (quad m / 4, row m % 4)
+  const bool sampler = c0.member < c0.Rtot && c0.cw == 0;   // wave 0 of member m samples the group's local row m
   const int EPS = 4 * a.L + 2;                       // hops per step
   unsigned char* seen = smem + L_SEEN;
   KvStage kvs;
   set_quad(q, 0);
   kv_stage_load(a, q, 0, 0, 0, kvs);
-  kv_stage_store(q, 0, 0, kvs);                      // layer 0's image of quad 0 (the attention waves read it after B1 + two compute barriers)
-  // LayerNorm parameters of the current layer, loaded in P1's poll-free stretch (a load issued right before a sweep would sit
-  // in front of its polls: a wave's memory operations return in order): norm1 for hop C, norm2 for the next hop A / the tail
-  float gC[8], bC[8], gA[8], bA[8];
+  kv_stage_store(q, 0, 0, kvs);                      // layer 0's image (the attention waves read it after B1 + two compute barriers)
+  float gC[8], bC[8], gA[8], bA[8];                  // see ln_params_load
 #pragma unroll
   for (int k = 0; k < 8; ++k) gC[k] = bC[k] = gA[k] = bA[k] = 0.f;
-  const int ra = c0.cw;                              // this wave's row of every quad
+  const int ra = c0.cw;                              // this wave's row
   for (int s = 0; s < a.nsteps; ++s) {
     const unsigned ep0 = a.ep_base + (unsigned)s * (unsigned)EPS;  // epoch of hop i of this step = ep0 + i + 1
     for (int l = 0; l < a.L; ++l) {
       const int ab_l = *st_abort(q);       // the abort test of this layer: read here, acted on behind the first barrier
       const float* lp = a.fpack + (size_t)l * FP_LAYER;
-      // ================= P1 of every quad: hop A -> LayerNorm; the compute waves run QKV, append and attention
-      for (int qd = 0; qd < nq; ++qd) {
-        relaunder(q);
-        set_quad(q, qd);
-        const int R = q.R;
-        q.hop = hop_slot(q, s, l);
-        q.prof_on = PROF && s == a.prof_step && l == a.prof_layer && qd == a.prof_quad;
-        MG_STAMP(q, 0);
-        // ---- hop A: y of the previous layer (or the step's input embedding) -> LayerNorm -> XS / XRES
-        {
-          const unsigned ep = ep0 + 4 * l + 1;
-          if (ra < R) {
-            u4v qa[4];
-            const bool has_ln = l > 0;                       // layer 0's input is the embedding itself
-            bool ok = true;
-            if (s == 0 && l == 0) {
-              const float* ya = a.ybuf + (size_t)batch_row(q, ra) * D + 2 * q.lane;
-#pragma unroll
-              for (int j = 0; j < 4; ++j) { const f2 y2 = *(const f2*)(ya + j * 128); qa[j] = (u4v){__float_as_uint(y2[0]), 0u, __float_as_uint(y2[1]), 0u}; }
-            } else {
-              ok = sweep_wide<4>(q, q.hop + HOP_A + ra * 512, ep, qa, 1u, a.hint_mask & 1);
-            }
-            if (ok) ln_row_wide(q, ra, qa, has_ln ? gA : nullptr, bA);
-          }
-          if (l == 0 && s > 0 && qd == 0 && q.cw == 0) {
-            // row state published by the samplers with the embedding: {active} per row; ALL quads' rows here, in front of
-            // quad 0's first barrier, so that every later slot of the step (K/V prefetch, exit test) sees the step's state
-            for (int q2 = 0; q2 < nq; ++q2) {
-              Ctx t = q;
-              set_quad(t, q2);
-              unsigned sv[1];
-              if (sweep<1>(t, hop_slot(t, s, l) + HOP_ST, t.R, ep, sv, 2u) && t.lane < t.R) {
-                const int was = st_active(t)[t.lane], now = (int)(sv[0] & 1u);
-                if (was) { st_step(t)[t.lane] += 1; if (now) st_kvlen(t)[t.lane] += 1; }
-                st_active(t)[t.lane] = now;
-              }
-            }
-          }
-        }
-        MG_STAMP(q, 1);
-        MG_BAR_AL(q);                                                       // B1
-        if (l == 0 && s > 0 && qd == 0 && group_done(q)) return;           // every row of the group has finished
-        MG_STAMP(q, 2);
-        // K/V of the NEXT slot's quad: the next quad of this layer, else quad 0 of the next layer (across the step boundary the
-        // rows hold one more position: appended at this step's layer 0); the compute waves run the QKV GEMM, the reduce and
-        // the attention meanwhile, synchronised among themselves
-        const bool kv_same = qd + 1 < nq;
-        const int kv_nq = kv_same ? qd + 1 : 0;
-        const int kv_nl = kv_same ? l : (l + 1 < a.L ? l + 1 : 0), kv_extra = (kv_same || l + 1 < a.L) ? 0 : 1;
-        const bool kv_more = kv_same || l + 1 < a.L || s + 1 < a.nsteps;
-        if (kv_more) kv_stage_load(a, q, kv_nl, kv_nq, kv_extra, kvs);
-        if (qd + 1 == nq) {       // after the LAST quad's hop A: every quad's LayerNorm above still needed the previous layer's norm2
-#pragma unroll
-          for (int k = 0; k < 8; ++k) {
-            const int el = (k >> 1) * 128 + 2 * q.lane + (k & 1);      // the element sweep_wide<4> delivers in slot k
-            gC[k] = lp[FP_N1W + el]; bC[k] = lp[FP_N1B + el];
-            gA[k] = lp[FP_N2W + el]; bA[k] = lp[FP_N2B + el];
-          }
-        }
-        MG_STAMP(q, 4);
-        MG_BAR();                                                          // B4: the attention is done, the K/V image is free
-        MG_STAMP(q, 5);
-        relaunder(q);
-        if (kv_more) kv_stage_store(q, kv_nq, kv_extra, kvs);
-      }
-      // ================= P2 of every quad: hop B (attention output of all heads) -> AT
-      for (int qd = 0; qd < nq; ++qd) {
-        relaunder(q);
-        set_quad(q, qd);
-        q.hop = hop_slot(q, s, l);
-        q.prof_on = PROF && s == a.prof_step && l == a.prof_layer && qd == a.prof_quad;
-        if (ra < q.R) {
-          u4v qb[2];
-          if (sweep_wide<2>(q, q.hop + HOP_B + ra * 256, ep0 + 4 * l + 2, qb, 3u, a.hint_mask & 2)) {
-            unsigned* at = (unsigned*)(smem + L_AT) + ra * (XS_LD / 2) + 2 * q.lane;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) *(u2v*)(at + j * 128) = (u2v){qb[j][0], qb[j][2]};
-          }
-        }
-        MG_STAMP(q, 6);
-        MG_BAR();                                                           // B1
-        MG_STAMP(q, 7);
-        MG_BAR();                                                          // B2
-        MG_STAMP(q, 8);
-      }
-      // ================= P3 of every quad: hop C (y1) -> LayerNorm1 -> XS / XRES
-      for (int qd = 0; qd < nq; ++qd) {
-        relaunder(q);
-        set_quad(q, qd);
-        q.hop = hop_slot(q, s, l);
-        q.prof_on = PROF && s == a.prof_step && l == a.prof_layer && qd == a.prof_quad;
-        if (ra < q.R) {
-          u4v qc[4];
-          if (sweep_wide<4>(q, q.hop + HOP_C + ra * 512, ep0 + 4 * l + 3, qc, 4u, a.hint_mask & 4)) ln_row_wide(q, ra, qc, gC, bC);
-        }
-        MG_STAMP(q, 9);
-        MG_BAR();                                                           // B1
-        MG_STAMP(q, 10);
-        if (MULTI) MG_BAR();                                               // B2 (sequential quads only: see compute_role)
-        MG_STAMP(q, 11);
-      }
-      // ================= P4 of every quad: hop D (FFN hidden) -> HS
-      for (int qd = 0; qd < nq; ++qd) {
-        relaunder(q);
-        set_quad(q, qd);
-        q.hop = hop_slot(q, s, l);
-        q.prof_on = PROF && s == a.prof_step && l == a.prof_layer && qd == a.prof_quad;
-        if (ra < q.R) {
-          u4v qd8[8];
-          if (sweep_wide<8>(q, q.hop + HOP_D + ra * 1024, ep0 + 4 * l + 4, qd8, 5u, a.hint_mask & 8)) {
-            unsigned* hs = (unsigned*)(smem + L_HS) + ra * (HS_LD / 2) + 2 * q.lane;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) *(u2v*)(hs + j * 128) = (u2v){qd8[j][0], qd8[j][2]};
-          }
-        }
-        MG_STAMP(q, 12);
-        MG_BAR();                                                           // B1
-        MG_STAMP(q, 13);
-        MG_BAR();                                                          // B2
-        MG_STAMP(q, 14);
-      }
-    }
-    // ---- tail: hop A' -> LayerNorm2 of the last layer -> XS, logits by the compute waves; quad after quad
-    const unsigned epA = ep0 + 4 * a.L + 1, epE = ep0 + 4 * a.L + 2;
-    for (int qd = 0; qd < nq; ++qd) {
+      q.prof_on = PROF && s == a.prof_step && l == a.prof_layer;
+      // ================= P1: hop A (y of the previous layer, or the step's input embedding) -> LayerNorm -> XS / XRES;
+      // the compute waves run QKV and the attention
       relaunder(q);
-      set_quad(q, qd);
-      q.hop = hop_slot(q, s, a.L);
-      q.prof_on = false;
-      if (ra < q.R) {
-        u4v qa[4];
-        if (sweep_wide<4>(q, q.hop + HOP_A + ra * 512, epA, qa, 6u, a.hint_mask & 1)) ln_row_wide(q, ra, qa, gA, bA);   // norm2 of the last layer
-      }
-      MG_BAR();                                                             // B1
-      MG_BAR();                                                            // B2
+      q.hop = hop_slot(q, s, l);
+      MG_STAMP(q, 0);
+      sweep_ln<false>(q, ra, q.hop + HOP_A, ep0 + 4 * l + 1, 1u, a.hint_mask & 1,
+                      s == 0 && l == 0 ? a.ybuf + (size_t)batch_row(q, ra) * D : nullptr, 0, 0, l > 0, gA, bA);   // layer 0's input is the embedding itself
+      if (l == 0 && s > 0 && q.cw == 0) sweep_row_state(q, 1, s, ep0 + 1);
+      MG_STAMP(q, 1);
+      MG_BAR_AL(q);                                                       // B1
+      if (l == 0 && s > 0 && group_done(q)) return;                       // every row of the group has finished
+      MG_STAMP(q, 2);
+      // K/V of the NEXT layer (across the step boundary the rows hold one more position: appended at this step's layer 0);
+      // the compute waves run the QKV GEMM, the reduce and the attention meanwhile, synchronised among themselves
+      const int kv_nl = l + 1 < a.L ? l + 1 : 0, kv_extra = l + 1 < a.L ? 0 : 1;
+      const bool kv_more = l + 1 < a.L || s + 1 < a.nsteps;
+      if (kv_more) kv_stage_load(a, q, kv_nl, 0, kv_extra, kvs);
+      ln_params_load(lp, q.lane, gC, bC, gA, bA);    // after hop A: its LayerNorm above still needed the previous layer's norm2
+      MG_STAMP(q, 4);
+      MG_BAR();                                                          // B4: the attention is done, the K/V image is free
+      MG_STAMP(q, 5);
+      relaunder(q);
+      if (kv_more) kv_stage_store(q, 0, kv_extra, kvs);
+      // ================= P2: hop B (attention output of all heads) -> AT
+      relaunder(q);
+      q.hop = hop_slot(q, s, l);
+      sweep_img<2>(q, ra, q.hop + HOP_B, ep0 + 4 * l + 2, 3u, a.hint_mask & 2, at_img(smem, 0), XS_LD);
+      MG_STAMP(q, 6);
+      MG_BAR();                                                           // B1
+      MG_STAMP(q, 7);
+      MG_BAR();                                                          // B2
+      MG_STAMP(q, 8);
+      // ================= P3: hop C (y1) -> LayerNorm1 -> XS / XRES
+      relaunder(q);
+      q.hop = hop_slot(q, s, l);
+      sweep_ln<false>(q, ra, q.hop + HOP_C, ep0 + 4 * l + 3, 4u, a.hint_mask & 4, nullptr, 0, 1, true, gC, bC);
+      MG_STAMP(q, 9);
+      MG_BAR();                                                           // B1 (no B2: see compute_role)
+      MG_STAMP(q, 10);
+      MG_STAMP(q, 11);
+      // ================= P4: hop D (FFN hidden) -> HS
+      relaunder(q);
+      q.hop = hop_slot(q, s, l);
+      sweep_img<8>(q, ra, q.hop + HOP_D, ep0 + 4 * l + 4, 5u, a.hint_mask & 8, hs_img(smem, 0), HS_LD);
+      MG_STAMP(q, 12);
+      MG_BAR();                                                           // B1
+      MG_STAMP(q, 13);
+      MG_BAR();                                                          // B2
+      MG_STAMP(q, 14);
     }
-    // ---- sampling (see run_sampler)
+    // ---- tail: hop A' -> LayerNorm2 of the last layer -> XS, logits by the compute waves
+    relaunder(q);
+    q.hop = hop_slot(q, s, a.L);
+    q.prof_on = false;
+    sweep_ln<false>(q, ra, q.hop + HOP_A, ep0 + 4 * a.L + 1, 6u, a.hint_mask & 1, nullptr, 0, 0, true, gA, bA);
+    MG_BAR();                                                             // B1
+    MG_BAR();                                                            // B2
     if (sampler) MG_RUN_SAMPLER();
   }
 }
 
-template <bool MULTI, bool PROF>
+template <bool PROF>
 __device__ __forceinline__ void compute_role(const MegaArgs& a, const Ctx& c0) {
   Ctx q = c0;
   unsigned char* smem = c0.smem;
-  const int Rtot = c0.Rtot;
-  const int nq = MULTI ? (Rtot + RMAX - 1) / RMAX : 1;
   const int V = a.V;
   const int EPS = 4 * a.L + 2;
-  // own rows of this member (attention): rows 2*ro + half of the current quad, ro = 0, 1
-  auto kv_row_base = [&](int layer, int which, int r) -> const _Float16* {
-    const int b = batch_row(q, r);
-    return a.kv + ((size_t)(layer * 2 + which)) * a.kv_layer_stride + ((size_t)b * NH + q.head) * (size_t)a.smax * HD;
-  };
-  const h8* wp = a.wpack;
-  auto p1_src = [&](int layer) { return wp + ((size_t)layer * LAYER_HALFS + ((size_t)q.head * 4 + q.cw) * WI_P1 * 512) / 8 + q.lane; };
-  auto pm_src = [&](int layer, int off) {
-    return wp + ((size_t)layer * LAYER_HALFS + P1_HALFS + (((size_t)q.member * 4 + q.cw) * (WI_P2 + WI_P3 + WI_P4) + off) * 512) / 8 + q.lane;
-  };
-  // residual operands of the out-projection (LN(y) of hop A) and of FFN2 (LN1(y1) of hop C) for the reducing wave's lanes.
-  // One quad: read from XRES when needed.  Several quads: XRES is overwritten by the next quad's LayerNorm before the phase
-  // that needs it comes round, so the member's 16 columns of every row are parked per quad (f4 per lane, 1 KB per quad).
-  auto rs_slot = [&](int which, int qd) { return (f4*)(smem + L_HS + RMAX * HS_LD * 2) + (which * QMAX + qd) * 64 + q.lane; };   // (the second HS copy: unused by these roles)
-  // K/V arena append of this step's k, v (own rows), from the LDS copy the attention used
-  auto arena_append = [&](int l) {
-    const int ro = q.lane >> 4, which = (q.lane >> 3) & 1, e = 4 * (q.lane & 7), r = 2 * ro + q.half;
-    if (r < q.R && st_active(q)[r]) {
-      const int pos = st_kvlen(q)[r];
-      if (pos < a.smax)
-        *(h4*)(const_cast<_Float16*>(kv_row_base(l, which, r)) + (size_t)pos * HD + e) =
-            *(const h4*)((const _Float16*)(smem + L_QKV) + (ro * 3 + 1 + which) * HD + e);
-    }
-  };
   // P1's slice is held as two halves (tiles q0 q1 k0 | k1 v0 v1): the second half is requested one phase later than the
   // first, so that FFN2's slice + the whole next P1 slice are never live together (160 + operands would spill)
   h8 wA0[WI_P1 / 2], wA1[WI_P1 / 2], wB[WI_P2], wC[WI_P3], wD[WI_P4];       // the logits slice reuses wA0
   int cgen = 0;                                       // compute_barrier generation
   // Weight slices are requested right AFTER a hop has landed (B1), never right after a publish: a load issued behind a
   // publish sits in the CU's in-order memory pipeline in front of the sweep waves' polls of the next hop.
-  wload(wA0, p1_src(0));
-  wload(wA1, p1_src(0) + (size_t)(WI_P1 / 2) * 64);
+  wload(wA0, p1_src(a, q, 0));
+  wload(wA1, p1_src(a, q, 0) + (size_t)(WI_P1 / 2) * 64);
 
   for (int s = 0; s < a.nsteps; ++s) {
     const unsigned ep0 = a.ep_base + (unsigned)s * (unsigned)EPS;
     for (int l = 0; l < a.L; ++l) {
       const int ab_l = *st_abort(q);       // the abort test of this layer: read here, acted on behind the first barrier
       const float* lp = a.fpack + (size_t)l * FP_LAYER;
+      q.prof_on = PROF && s == a.prof_step && l == a.prof_layer;
       // ================= P1: q,k,v of head `head` for the own rows, attention (K/V append: see P2)
-      // (the next phase's weight slice is requested in EVERY quad's slot, not only the first: a request under a run-time
-      // `if (qd == 0)` inside the quad loop is a CONDITIONAL definition of the register array, which keeps the array's
-      // previous contents alive around the whole loop -- every slice live everywhere, ~100 spilled VGPRs.  The repeated
-      // requests hit L2 and rewrite the registers with the same bytes; no slot reads the array it requests)
-      for (int qd = 0; qd < nq; ++qd) {
-        const bool first = qd == 0;
+      {
         relaunder(q);
-        set_quad(q, qd);
-        const int R = q.R;
         q.hop = hop_slot(q, s, l);
-        q.prof_on = PROF && s == a.prof_step && l == a.prof_layer && first;
         MG_STAMP(q, 0);
-        // lane j < 24 of every wave reduces 4 values of q | k | v of the wave's OWN attention row (see after B2)
-        const int rj_which = (q.lane >> 3) % 3, rj_e = 4 * (q.lane & 7);
-        const f4 p1_bias = q.lane < 24 ? *(const f4*)(lp + FP_QKVB + rj_which * D + q.head * HD + rj_e) : (f4){0.f, 0.f, 0.f, 0.f};
+        const f4 p1_bias = qkv_bias(lp, q.lane, q.head);
         MG_STAMP(q, 1);
         MG_BAR_AL(q);                                                       // B1: XS / XRES hold LN(y)
-        if (first && l == 0 && s > 0 && group_done(q)) return;
+        if (l == 0 && s > 0 && group_done(q)) return;
         MG_STAMP(q, 2);
-        wload(wB, pm_src(l, 0));                                           // every quad's slot (see the note above the loop)
-        gemm_chunk<3>(q, wA0, (const _Float16*)(smem + L_XS), XS_LD, q.cw, q.cw * 6);
-        gemm_chunk<3>(q, wA1, (const _Float16*)(smem + L_XS), XS_LD, q.cw, q.cw * 6 + 3);
-        if (MULTI && q.cw == 0 && (q.lane & 15) < R)                       // the out-projection's residual operand of this quad
-          *rs_slot(0, qd) = *(const f4*)((const float*)(smem + L_XRES) + (q.lane & 15) * D + 16 * q.member + 4 * (q.lane >> 4));
+        wload(wB, pm_src(a, q, l, 0));
+        gemm_chunk<3>(q, wA0, xs_img(smem, 0), XS_LD, q.cw, q.cw * 6);
+        gemm_chunk<3>(q, wA1, xs_img(smem, 0), XS_LD, q.cw, q.cw * 6 + 3);
         MG_STAMP(q, 3);
         if (compute_barrier(q, cgen)) return;                              // B2 (compute waves only)
         MG_STAMP(q, 4);
-        {
-          // split-K reduce of q, k, v (+ bias) by the wave that consumes them: each attention wave sums the 96 values of ITS row
-          // (both waves of a row do, and write identical bytes), so that no barrier stands between the reduce and the attention
-          // -- the workgroup-wide reduce + compute-only barrier here were 0.7 us of every layer (stamps 4-7).  Same summation
-          // order as before: ((w0 + w1) + w2) + w3 + bias.
-          const f4* red = (const f4*)(smem + L_RED);
-          _Float16* qkv_s = (_Float16*)(smem + L_QKV);
-          const int ro = q.cw / 2, r = 2 * ro + q.half;
-          if (q.lane < 24 && r < R) {
-            const int tile = rj_which * 2 + (rj_e >> 4), ln = r + 16 * ((rj_e & 15) >> 2);
-            const f4 v0 = red[red_idx(0 * 6 + tile, ln)], v1 = red[red_idx(1 * 6 + tile, ln)], v2 = red[red_idx(2 * 6 + tile, ln)],
-                     v3 = red[red_idx(3 * 6 + tile, ln)];
-            f4 v = v0;
-            v += v1; v += v2; v += v3;
-            v += p1_bias;
-            const h4 ov = (h4){(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-            *(h4*)(qkv_s + (ro * 3 + rj_which) * HD + rj_e) = ov;    // the arena append of k, v follows (see arena_append)
-          }
-          asm volatile("" ::: "memory");                      // the attention's reads of qkv_s stay behind the writes (same wave: in order)
-          MG_STAMP(q, 5);
-        }
+        qkv_reduce(smem, q.lane, q.cw, q.half, q.R, p1_bias);
+        MG_STAMP(q, 5);
         MG_STAMP(q, 6);
         MG_STAMP(q, 7);
         attention_part<2>(a, q, l, q.cw);
@@ -1037,314 +1151,124 @@ __device__ __forceinline__ void compute_role(const MegaArgs& a, const Ctx& c0) {
         // state is read once per call (it was 3.5 us, and a compute-only barrier stood here so that the publish did not wait)
         MG_BAR();                                                           // B4
         MG_STAMP(q, 9);
-        if (q.cw == 0) {
-          // combine the 2 waves of each own row; lane = ro * 32 + e
-          const float* s_m = (const float*)(smem + L_ATT);
-          const float* s_acc = s_m + 8;
-          const int ro = q.lane >> 5, e = q.lane & 31, r = 2 * ro + q.half;
-          float M = -INFINITY;
-#pragma unroll
-          for (int w = 0; w < 2; ++w) M = fmaxf(M, s_m[2 * ro + w]);
-          float o = 0.f;
-          if (M != -INFINITY) {
-            float Lsum = 0.f, num = 0.f;
-#pragma unroll
-            for (int w = 0; w < 2; ++w) {
-              const float mw = s_m[2 * ro + w];
-              const float ew = mw == -INFINITY ? 0.f : __expf(mw - M);
-              const float* pa = s_acc + (2 * ro + w) * 4 * 36;
-              Lsum += ((pa[32] + pa[36 + 32]) + (pa[72 + 32] + pa[108 + 32])) * ew;
-              num += ((pa[e] + pa[36 + e]) + (pa[72 + e] + pa[108 + e])) * ew;
-            }
-            o = num / Lsum;
-          }
-          const float o2 = dpp_f<DPP_QUAD_XOR1>(o);            // lane ^ 1
-          // 16 granules (one 128-B line) per own row, written by one wave instruction
-          if (r < R && !(e & 1)) gstore(q.hop + HOP_B + r * 256 + (q.head * HD + e) / 2, ep0 + 4 * l + 2, pack_h2(o, o2));
-        }
-        // several quads: the next quad's reduce overwrites the q/k/v copy before P2 comes round, so the arena append happens
-        // here (the comm waves' K/V burst of the next slot was issued a whole attention ago and has drained)
-        if (MULTI && q.cw == 1 && q.lane < 32) arena_append(l);
+        if (q.cw == 0) attn_combine_publish(smem, q.lane, q.head, q.half, q.R, q.hop + HOP_B, ep0 + 4 * l + 2);
         MG_STAMP(q, 10);
       }
       // ================= P2: out-projection columns [16 member, +16) + bias + residual -> y1
-      for (int qd = 0; qd < nq; ++qd) {
-        const bool first = qd == 0;
+      {
         relaunder(q);
-        set_quad(q, qd);
-        const int R = q.R;
         q.hop = hop_slot(q, s, l);
-        q.prof_on = PROF && s == a.prof_step && l == a.prof_layer && first;
         const f4 p_bias = *(const f4*)(lp + FP_OUTB + 16 * q.member + 4 * (q.lane >> 4));
         MG_STAMP(q, 11);
         MG_BAR();                                                           // B1: AT holds the attention output
         MG_STAMP(q, 12);
-        wload(wC, pm_src(l, WI_P2));
-        gemm_chunk<1>(q, wB, (const _Float16*)(smem + L_AT), XS_LD, q.cw, q.cw);
+        wload(wC, pm_src(a, q, l, WI_P2));
+        gemm_chunk<1>(q, wB, at_img(smem, 0), XS_LD, q.cw, q.cw);
         MG_STAMP(q, 13);
         MG_BAR();                                                          // B2
         MG_STAMP(q, 14);
-        if (q.cw == 0) {
-          const f4* red = (const f4*)(smem + L_RED);
-          const int r = q.lane & 15, n0 = 16 * q.member + 4 * (q.lane >> 4);
-          if (r < R) {
-            const f4 v0 = red[red_idx(0, q.lane)], v1 = red[red_idx(1, q.lane)], v2 = red[red_idx(2, q.lane)], v3 = red[red_idx(3, q.lane)];
-            const f4 xr = MULTI ? *rs_slot(0, qd) : *(const f4*)((const float*)(smem + L_XRES) + r * D + n0);
-            f4 v = v0;
-            v += v1; v += v2; v += v3;
-            v += p_bias;
-            v += xr;
-            *(f4*)((float*)(smem + L_STAGE) + r * 16 + 4 * (q.lane >> 4)) = v;
-          }
-          // transposed through LDS (same wave): lane = row * 16 + column, so each row's 16 granules = one 128-B line
-          // written whole by ONE store instruction (scattered 8-B write-through stores made every hop 2-3x slower)
-          // test hook (gsv_t2s_debug_stall, tests only): that member of group 0 skips ONE publish, so that the group's
-          // bounded waits must end the launch with an error instead of hanging
-          const bool stall = a.test_stall && q.member == a.test_stall - 1 && q.group == 0 && s == 2 && l == 3 && qd == 0;
-          if (q.lane < R * 16 && !stall)
-            gstore(q.hop + HOP_C + (q.lane >> 4) * 512 + 16 * q.member + (q.lane & 15), ep0 + 4 * l + 3,
-                   __float_as_uint(((const float*)(smem + L_STAGE))[q.lane]));
-        }
-        if (!MULTI && q.cw == 1 && q.lane < 32) {   // wave 1 is idle while wave 0 publishes
-          // K/V arena append: not in P1 where k, v are produced -- there the store has to queue behind the comm waves' K/V
-          // burst of the next layer in the CU's memory pipeline (1.3 us of blocked issue in the stamps); nothing reads the
-          // arena row before the next step's staging
-          arena_append(l);
-        }
+        if (q.cw == 0)
+          reduce_residual_publish(smem, q.lane, q.member, q.R, p_bias,
+                                  *(const f4*)((const float*)(smem + L_XRES) + (q.lane & 15) * D + 16 * q.member + 4 * (q.lane >> 4)),
+                                  q.hop + HOP_C, ep0 + 4 * l + 3, stall_hook(a, q.member, q.group, s, l, 0));
+        // wave 1 is idle while wave 0 publishes.  K/V arena append: not in P1 where k, v are produced -- there the store has
+        // to queue behind the comm waves' K/V burst of the next layer in the CU's memory pipeline (1.3 us of blocked issue in
+        // the stamps); nothing reads the arena row before the next step's staging
+        if (q.cw == 1 && q.lane < 32) arena_append(a, smem, q.lane, l, q.head, q.half, q.R, batch_row(q, 0), st_active(q), st_kvlen(q));
       }
       // ================= P3: FFN1 columns [64 member, +64), ReLU -> h
-      for (int qd = 0; qd < nq; ++qd) {
-        const bool first = qd == 0;
+      {
         relaunder(q);
-        set_quad(q, qd);
-        const int R = q.R;
         q.hop = hop_slot(q, s, l);
-        q.prof_on = PROF && s == a.prof_step && l == a.prof_layer && first;
         const f4 p_bias = *(const f4*)(lp + FP_B1 + 64 * q.member + 16 * q.cw + 4 * (q.lane >> 4));       // tile cw of the member's four
         MG_STAMP(q, 15);
         MG_BAR();                                                           // B1: XS / XRES hold LN1(y1)
         MG_STAMP(q, 16);
-        wload(wD, pm_src(l, WI_P2 + WI_P3));
-        f4 v = gemm_tile_k512(q, wC, (const _Float16*)(smem + L_XS), XS_LD);
-        if (MULTI && q.cw == 2 && (q.lane & 15) < R)                       // FFN2's residual operand of this quad
-          *rs_slot(1, qd) = *(const f4*)((const float*)(smem + L_XRES) + (q.lane & 15) * D + 16 * q.member + 4 * (q.lane >> 4));
+        wload(wD, pm_src(a, q, l, WI_P2 + WI_P3));
+        const f4 v = gemm_tile_k512(q, wC, xs_img(smem, 0), XS_LD);
         MG_STAMP(q, 17);
-        // sequential quads: the comm waves overwrite XS with the next quad's rows right after this barrier.  One quad: none
-        // needed -- the next writer of XS is hop A of the next layer, two workgroup barriers away
-        if (MULTI) MG_BAR();                                               // B2
+        // no B2: the next writer of XS is hop A of the next layer, two workgroup barriers away
         MG_STAMP(q, 18);
-        {
-          // every wave publishes its own tile: 16 columns = 8 half-pair granules = 64 contiguous bytes per row, the rows of
-          // the quad by one store instruction (transposed through the wave's own LDS patch: lane = row * 8 + granule)
-          const int r = q.lane & 15;
-          unsigned* stage = (unsigned*)(smem + L_STAGE) + q.cw * 64;
-          v += p_bias;
-          if (r < R) {
-            const int w0 = r * 8 + 2 * (q.lane >> 4);
-            stage[w0] = pack_h2(fmaxf(v[0], 0.f), fmaxf(v[1], 0.f));
-            stage[w0 + 1] = pack_h2(fmaxf(v[2], 0.f), fmaxf(v[3], 0.f));
-          }
-          if (q.lane < R * 8)
-            gstore(q.hop + HOP_D + (q.lane >> 3) * 1024 + 32 * q.member + 8 * q.cw + (q.lane & 7), ep0 + 4 * l + 4, stage[q.lane]);
-        }
+        ffn1_publish(smem, q.lane, q.cw, q.member, q.R, v, p_bias, q.hop + HOP_D, ep0 + 4 * l + 4);
       }
-      // ================= P4: FFN2 columns [16 member, +16) over K = 2048 (each wave chains its 4 chunks of 128, 4 partials) -> y2
-      for (int qd = 0; qd < nq; ++qd) {
+      // ================= P4: FFN2 columns [16 member, +16) over K = 2048 -> y2
+      {
         relaunder(q);
-        set_quad(q, qd);
-        const int R = q.R;
         q.hop = hop_slot(q, s, l);
-        q.prof_on = PROF && s == a.prof_step && l == a.prof_layer && qd == a.prof_quad;
         const f4 p_bias = *(const f4*)(lp + FP_B2 + 16 * q.member + 4 * (q.lane >> 4));
         MG_STAMP(q, 19);
         MG_BAR();                                                           // B1: HS holds the FFN hidden
         MG_STAMP(q, 20);
-        if (l + 1 < a.L) wload(wA0, p1_src(l + 1));                        // P1 has finished with wA0 for every quad
-        else wload(wA0, a.lpack + (((size_t)q.member * 4 + q.cw) * WI_LG * 512) / 8 + q.lane);
-        {
-          const int rowl = q.lane & 15, kg = q.lane >> 4;
-          f4* red = (f4*)(smem + L_RED);
-          // one accumulator over the wave's four 128-wide chunks (the MFMA forwards a dependent accumulator without a stall):
-          // ONE partial per wave like the other phases, instead of 16 per workgroup through LDS
-          f4 acc = (f4){0.f, 0.f, 0.f, 0.f};
-          // the operand reads of chunk cc + 1 are in flight under the MFMAs of chunk cc (two register sets of 4 fragments; same
-          // MFMA order, bit-identical): 295.8 -> 292.6 us per step over 4 pairs (3 of 4), profiles/r03_ab_ffn2_operand_prefetch.txt
-          const _Float16* bp0 = (const _Float16*)(smem + L_HS) + (rowl & (RMAX - 1)) * HS_LD + (4 * q.cw) * 128 + 8 * kg;
-          h8 bA[4], bB[4];
-#pragma unroll
-          for (int ks = 0; ks < 4; ++ks) bA[ks] = *(const h8*)(bp0 + 32 * ks);
-#pragma unroll
-          for (int cc = 0; cc < 4; cc += 2) {
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) bB[ks] = *(const h8*)(bp0 + (cc + 1) * 128 + 32 * ks);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wD[cc * 4 + ks], bA[ks], acc, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (cc + 2 < 4) {
-#pragma unroll
-              for (int ks = 0; ks < 4; ++ks) bA[ks] = *(const h8*)(bp0 + (cc + 2) * 128 + 32 * ks);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wD[(cc + 1) * 4 + ks], bB[ks], acc, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-          if (rowl < RMAX) red[red_idx(q.cw, q.lane)] = acc;
-        }
-        // second half of the next P1 slice: this quad's FFN2 is done, and the request is still in front of the publish
-        wload(wA1, p1_src(l + 1 < a.L ? l + 1 : 0) + (size_t)(WI_P1 / 2) * 64);
+        if (l + 1 < a.L) wload(wA0, p1_src(a, q, l + 1));                  // P1 has finished with wA0
+        else wload(wA0, lg_src(a, q));
+        ffn2_chunks(wD, hs_img(smem, 0), smem, q.lane, q.cw);
+        // second half of the next P1 slice: FFN2 is done, and the request is still in front of the publish
+        wload(wA1, p1_src(a, q, l + 1 < a.L ? l + 1 : 0) + (size_t)(WI_P1 / 2) * 64);
         MG_STAMP(q, 21);
         MG_BAR();                                                          // B2
         MG_STAMP(q, 22);
-        if (q.cw == 0) {
-          const f4* red = (const f4*)(smem + L_RED);
-          const int r = q.lane & 15, n0 = 16 * q.member + 4 * (q.lane >> 4);
-          if (r < R) {
-            const f4 v0 = red[red_idx(0, q.lane)], v1 = red[red_idx(1, q.lane)], v2 = red[red_idx(2, q.lane)], v3 = red[red_idx(3, q.lane)];
-            const f4 xr = MULTI ? *rs_slot(1, qd) : *(const f4*)((const float*)(smem + L_XRES) + r * D + n0);
-            f4 v = v0;
-            v += v1; v += v2; v += v3;
-            v += p_bias;
-            v += xr;
-            // y2 feeds hop A of the next layer, or hop A' (the logits' LayerNorm) after the last layer
-            *(f4*)((float*)(smem + L_STAGE) + r * 16 + 4 * (q.lane >> 4)) = v;
-          }
-          const unsigned ep = l + 1 < a.L ? ep0 + 4 * (l + 1) + 1 : ep0 + 4 * a.L + 1;
-          if (q.lane < R * 16)
-            gstore(hop_slot(q, s, l + 1) + HOP_A + (q.lane >> 4) * 512 + 16 * q.member + (q.lane & 15), ep,
-                   __float_as_uint(((const float*)(smem + L_STAGE))[q.lane]));
-        }
+        if (q.cw == 0)                     // y2 feeds hop A of the next layer, or hop A' (the logits' LayerNorm) after the last layer
+          reduce_residual_publish(smem, q.lane, q.member, q.R, p_bias,
+                                  *(const f4*)((const float*)(smem + L_XRES) + (q.lane & 15) * D + 16 * q.member + 4 * (q.lane >> 4)),
+                                  hop_slot(q, s, l + 1) + HOP_A, ep0 + 4 * (l + 1) + 1, false);
         MG_STAMP(q, 23);
       }
     }
-    // ================= tail: logits split over the members (tiles member, member + 32, and tile 64 on member 0)
-    const unsigned epE = ep0 + 4 * a.L + 2;
-    for (int qd = 0; qd < nq; ++qd) {
-      relaunder(q);
-      set_quad(q, qd);
-      const int R = q.R;
-      q.hop = hop_slot(q, s, a.L);
-      q.prof_on = false;
-      MG_BAR();                                                             // B1: XS holds LN2(y) of the last layer
-      gemm_chunk<3>(q, wA0, (const _Float16*)(smem + L_XS), XS_LD, q.cw, q.cw * 3);
-      if (!MULTI) wload(wA0, p1_src(0));                                   // next step's layer 0 (two hops away; wA1 is there already)
-      MG_BAR();                                                            // B2
-      if (q.cw < 3) {
-        const f4* red = (const f4*)(smem + L_RED);
-        const int t = q.cw, r = q.lane & 15;
-        const int tile = t == 0 ? q.member : (t == 1 ? q.member + 32 : 64);
-        float* stage = (float*)(smem + L_STAGE) + q.cw * 256;
-        if (r < R) {
-          f4 v = red[red_idx(0 * 3 + t, q.lane)];
-          v += red[red_idx(1 * 3 + t, q.lane)]; v += red[red_idx(2 * 3 + t, q.lane)]; v += red[red_idx(3 * 3 + t, q.lane)];
-          *(f4*)(stage + r * 16 + 4 * (q.lane >> 4)) = v;
-        }
-        if (q.lane < R * 16 && (t < 2 || q.member == 0) && 16 * tile + (q.lane & 15) < V)
-          gstore(q.hop + HOP_E + (q.lane >> 4) * VPAD + 16 * tile + (q.lane & 15), epE, __float_as_uint(stage[q.lane]));
-      }
-    }
-    // several quads: the logits slice is read by every quad's slot, the next step's first slice follows the last one
-    if (MULTI) wload(wA0, p1_src(0));
+    // ================= tail: logits split over the members
+    relaunder(q);
+    q.hop = hop_slot(q, s, a.L);
+    q.prof_on = false;
+    MG_BAR();                                                             // B1: XS holds LN2(y) of the last layer
+    gemm_chunk<3>(q, wA0, xs_img(smem, 0), XS_LD, q.cw, q.cw * 3);
+    wload(wA0, p1_src(a, q, 0));                                         // next step's layer 0 (two hops away; wA1 is there already)
+    MG_BAR();                                                            // B2
+    if (q.cw < 3) logits_publish(smem, q.lane, q.cw, q.member, q.R, V, q.hop + HOP_E, ep0 + 4 * a.L + 2);
   }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Pipelined quads (32 < B <= 128).  The sequential-quad roles above (MULTI = true) wait out every quad's sweep round trip
-// (~1.1 us even when the data arrived long ago) in front of its GEMM: a GEMM-phase slot costs 1.8-2.7 us, a layer 44 us
-// for four quads (in-kernel stamps, gpurun_out r3_prof128_*).  Here the comm waves sweep quad i + 1's hop into the SECOND
-// copy of the operand image while the compute waves multiply, reduce and publish quad i -- one workgroup barrier per slot:
+// Pipelined quads (32 < B <= 128): a group serves up to QMAX quads of rows, phase by phase one after the other with the
+// weight slices it already holds.  Run like the single quad, every quad would wait out its sweep round trip (~1.1 us even
+// when the data arrived long ago) in front of its GEMM: a GEMM-phase slot cost 1.8-2.7 us, a layer 44 us for four quads
+// (in-kernel stamps of the removed sequential-quad mode).  Here the comm waves sweep quad i + 1's hop into the
+// SECOND copy of the operand image while the compute waves multiply, reduce and publish quad i -- one workgroup barrier
+// per slot:
 //     comm:    sweep(0) | B | sweep(1)              | B | sweep(2)              | B | ...
 //     compute:          | B | gemm(0) cb reduce(0)  | B | gemm(1) cb reduce(1)  | B | ...
 // and P1 (QKV + attention) keeps two barriers per slot: B_a (the previous quad's attention has released the K/V image,
 // LN(hop A) of this quad is in its XS copy) and B_b (the image of this quad is stored; the QKV partials are parked).
 // The member's 16 residual columns of every row are parked per quad by the LayerNorm itself (no XRES image).
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ f4* rs_at(unsigned char* smem, int which, int qd, int lane) { return (f4*)(smem + L_RS) + (which * QMAX + qd) * 64 + lane; }
-
-// LayerNorm of one row delivered by sweep_wide<4> -> XS copy `buf` (MFMA operand) + the member's residual columns -> rs[which][qd]
-__device__ __forceinline__ void ln_row_pipe(const Ctx& c, int row, int buf, int which, const u4v (&v)[4], const float* gm, const float* bt) {
-  float x[8];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { x[2 * j] = __uint_as_float(v[j][0]); x[2 * j + 1] = __uint_as_float(v[j][2]); }
-  if (gm) {
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s += x[k];
-    const float mean = wave_sum_dpp(s) * (1.f / D);
-    float qq = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { const float dl = x[k] - mean; qq += dl * dl; }
-    const float rstd = rsqrtf(wave_sum_dpp(qq) * (1.f / D) + 1e-5f);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) x[k] = (x[k] - mean) * rstd * gm[k] + bt[k];
-  }
-  _Float16* xs = (_Float16*)(c.smem + L_XS) + (buf * RMAX + row) * XS_LD + 2 * c.lane;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) *(h2*)(xs + j * 128) = (h2){(_Float16)x[2 * j], (_Float16)x[2 * j + 1]};
-  // columns [16 member, +16) of this row: chunk j = member / 8, lanes 8 (member % 8) .. + 7, two elements each; the reducing
-  // wave's lane r + 16 g holds columns 4 g .. 4 g + 3 of row r
-  const int jm = c.member >> 3, m0 = 8 * (c.member & 7), dm = c.lane - m0;
-  const float e0 = jm == 0 ? x[0] : jm == 1 ? x[2] : jm == 2 ? x[4] : x[6];
-  const float e1 = jm == 0 ? x[1] : jm == 1 ? x[3] : jm == 2 ? x[5] : x[7];
-  if (dm >= 0 && dm < 8)
-    *(f2*)((float*)rs_at(c.smem, which, c.qd, row + 16 * (dm >> 1)) + 2 * (dm & 1)) = (f2){e0, e1};
-}
-
 __device__ __forceinline__ void comm_role_pipe(const MegaArgs& a, const Ctx& c0, const StepParams& sp) {
   Ctx q = c0;
   unsigned char* smem = c0.smem;
   const int Rtot = c0.Rtot;
   const int nq = (Rtot + RMAX - 1) / RMAX;
-  const bool sampler = c0.member < Rtot && c0.cw == 0;
+  const bool sampler = c0.member < Rtot && c0.cw == 0;   // wave 0 of member m samples the group's local row m (quad m / 4, row m % 4)
   const int EPS = 4 * a.L + 2;
   unsigned char* seen = smem + L_SEEN;
   KvStage kvs;
   set_quad(q, 0);
   kv_stage_load(a, q, 0, 0, 0, kvs);                 // image of (layer 0, quad 0): stored by the first P1 slot like every other
-  float gC[8], bC[8], gA[8], bA[8];
+  float gC[8], bC[8], gA[8], bA[8];                  // see ln_params_load
 #pragma unroll
   for (int k = 0; k < 8; ++k) gC[k] = bC[k] = gA[k] = bA[k] = 0.f;
   const int ra = c0.cw;                              // this wave's row of every quad
   for (int s = 0; s < a.nsteps; ++s) {
     const unsigned ep0 = a.ep_base + (unsigned)s * (unsigned)EPS;
+    // a sweep's preamble: quad qd becomes the current one (its rows, state entries and hop buffers)
+    auto enter = [&](int qd, int l) { relaunder(q); set_quad(q, qd); q.hop = hop_slot(q, s, l); };
     for (int l = 0; l < a.L; ++l) {
       const int ab_l = *st_abort(q);       // the abort test of this layer: read here, acted on behind the first barrier
       const float* lp = a.fpack + (size_t)l * FP_LAYER;
-      // hop A of quad qd -> LayerNorm -> XS copy qd & 1 (+ the residual columns of the out-projection)
+      // ================= P1: hop A of quad qd -> LayerNorm -> XS copy qd & 1 (+ the residual columns of the out-projection)
       auto sweep_a = [&](int qd) {
-        relaunder(q);
-        set_quad(q, qd);
-        q.hop = hop_slot(q, s, l);
-        if (ra < q.R) {
-          u4v qa[4];
-          bool ok = true;
-          if (s == 0 && l == 0) {
-            const float* ya = a.ybuf + (size_t)batch_row(q, ra) * D + 2 * q.lane;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { const f2 y2 = *(const f2*)(ya + j * 128); qa[j] = (u4v){__float_as_uint(y2[0]), 0u, __float_as_uint(y2[1]), 0u}; }
-          } else {
-            ok = sweep_wide<4>(q, q.hop + HOP_A + ra * 512, ep0 + 4 * l + 1, qa, 1u, a.hint_mask & 1);
-          }
-          if (ok) ln_row_pipe(q, ra, qd & 1, 0, qa, l > 0 ? gA : nullptr, bA);
-        }
+        enter(qd, l);
+        sweep_ln<true>(q, ra, q.hop + HOP_A, ep0 + 4 * l + 1, 1u, a.hint_mask & 1,
+                       s == 0 && l == 0 ? a.ybuf + (size_t)batch_row(q, ra) * D : nullptr, qd & 1, 0, l > 0, gA, bA);
       };
-      // ================= P1
-      q.prof_on = false;
       sweep_a(0);
-      if (l == 0 && s > 0 && q.cw == 0) {
-        // row state published by the samplers with the embedding, every quad's rows (see comm_role)
-        for (int q2 = 0; q2 < nq; ++q2) {
-          Ctx t = q;
-          set_quad(t, q2);
-          unsigned sv[1];
-          if (sweep<1>(t, hop_slot(t, s, l) + HOP_ST, t.R, ep0 + 1, sv, 2u) && t.lane < t.R) {
-            const int was = st_active(t)[t.lane], now = (int)(sv[0] & 1u);
-            if (was) { st_step(t)[t.lane] += 1; if (now) st_kvlen(t)[t.lane] += 1; }
-            st_active(t)[t.lane] = now;
-          }
-        }
-      }
+      if (l == 0 && s > 0 && q.cw == 0) sweep_row_state(q, nq, s, ep0 + 1);
       for (int qd = 0; qd < nq; ++qd) {
         MG_BAR_AL(q);                                                       // B_a
         if (l == 0 && s > 0 && qd == 0 && group_done(q)) return;
@@ -1354,34 +1278,19 @@ __device__ __forceinline__ void comm_role_pipe(const MegaArgs& a, const Ctx& c0,
         // advanced state with extra = 0 -- the same positions
         kv_stage_store(q, qd, 0, kvs);
         MG_BAR();                                                           // B_b
-        // the NEXT slot's image (the compute waves run the reduce and the attention meanwhile)
+        // the NEXT slot's image: the next quad of this layer, else quad 0 of the next layer (across the step boundary the rows
+        // hold one more position: appended at this step's layer 0); the compute waves run the reduce and the attention meanwhile
         const bool kv_same = qd + 1 < nq;
         const int kv_nq = kv_same ? qd + 1 : 0;
         const int kv_nl = kv_same ? l : (l + 1 < a.L ? l + 1 : 0), kv_extra = (kv_same || l + 1 < a.L) ? 0 : 1;
         if (kv_same || l + 1 < a.L || s + 1 < a.nsteps) kv_stage_load(a, q, kv_nl, kv_nq, kv_extra, kvs);
         if (kv_same) sweep_a(qd + 1);
-        else {
-#pragma unroll
-          for (int k = 0; k < 8; ++k) {
-            const int el = (k >> 1) * 128 + 2 * q.lane + (k & 1);
-            gC[k] = lp[FP_N1W + el]; bC[k] = lp[FP_N1B + el];
-            gA[k] = lp[FP_N2W + el]; bA[k] = lp[FP_N2B + el];
-          }
-        }
+        else ln_params_load(lp, q.lane, gC, bC, gA, bA);    // after the LAST quad's hop A: every quad's LayerNorm still needed the previous layer's norm2
       }
       // ================= P2: hop B -> AT copies
       auto sweep_b = [&](int qd) {
-        relaunder(q);
-        set_quad(q, qd);
-        q.hop = hop_slot(q, s, l);
-        if (ra < q.R) {
-          u4v qb[2];
-          if (sweep_wide<2>(q, q.hop + HOP_B + ra * 256, ep0 + 4 * l + 2, qb, 3u, a.hint_mask & 2)) {
-            unsigned* at = (unsigned*)(smem + L_AT) + ((qd & 1) * RMAX + ra) * (XS_LD / 2) + 2 * q.lane;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) *(u2v*)(at + j * 128) = (u2v){qb[j][0], qb[j][2]};
-          }
-        }
+        enter(qd, l);
+        sweep_img<2>(q, ra, q.hop + HOP_B, ep0 + 4 * l + 2, 3u, a.hint_mask & 2, at_img(smem, qd & 1), XS_LD);
       };
       sweep_b(0);
       for (int qd = 0; qd < nq; ++qd) {
@@ -1390,13 +1299,8 @@ __device__ __forceinline__ void comm_role_pipe(const MegaArgs& a, const Ctx& c0,
       }
       // ================= P3: hop C -> LayerNorm1 -> XS copies (+ the residual columns of FFN2)
       auto sweep_c = [&](int qd) {
-        relaunder(q);
-        set_quad(q, qd);
-        q.hop = hop_slot(q, s, l);
-        if (ra < q.R) {
-          u4v qc[4];
-          if (sweep_wide<4>(q, q.hop + HOP_C + ra * 512, ep0 + 4 * l + 3, qc, 4u, a.hint_mask & 4)) ln_row_pipe(q, ra, qd & 1, 1, qc, gC, bC);
-        }
+        enter(qd, l);
+        sweep_ln<true>(q, ra, q.hop + HOP_C, ep0 + 4 * l + 3, 4u, a.hint_mask & 4, nullptr, qd & 1, 1, true, gC, bC);
       };
       sweep_c(0);                       // no barrier between the phases: this sweep overlaps the last out-projection slot
       for (int qd = 0; qd < nq; ++qd) {
@@ -1405,17 +1309,8 @@ __device__ __forceinline__ void comm_role_pipe(const MegaArgs& a, const Ctx& c0,
       }
       // ================= P4: hop D -> HS copies
       auto sweep_d = [&](int qd) {
-        relaunder(q);
-        set_quad(q, qd);
-        q.hop = hop_slot(q, s, l);
-        if (ra < q.R) {
-          u4v qd8[8];
-          if (sweep_wide<8>(q, q.hop + HOP_D + ra * 1024, ep0 + 4 * l + 4, qd8, 5u, a.hint_mask & 8)) {
-            unsigned* hs = (unsigned*)(smem + L_HS) + ((qd & 1) * RMAX + ra) * (HS_LD / 2) + 2 * q.lane;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) *(u2v*)(hs + j * 128) = (u2v){qd8[j][0], qd8[j][2]};
-          }
-        }
+        enter(qd, l);
+        sweep_img<8>(q, ra, q.hop + HOP_D, ep0 + 4 * l + 4, 5u, a.hint_mask & 8, hs_img(smem, qd & 1), HS_LD);
       };
       sweep_d(0);
       for (int qd = 0; qd < nq; ++qd) {
@@ -1425,13 +1320,8 @@ __device__ __forceinline__ void comm_role_pipe(const MegaArgs& a, const Ctx& c0,
     }
     // ---- tail: hop A' -> LayerNorm2 of the last layer -> XS copies; logits by the compute waves
     auto sweep_t = [&](int qd) {
-      relaunder(q);
-      set_quad(q, qd);
-      q.hop = hop_slot(q, s, a.L);
-      if (ra < q.R) {
-        u4v qa[4];
-        if (sweep_wide<4>(q, q.hop + HOP_A + ra * 512, ep0 + 4 * a.L + 1, qa, 6u, a.hint_mask & 1)) ln_row_pipe(q, ra, qd & 1, 0, qa, gA, bA);
-      }
+      enter(qd, a.L);
+      sweep_ln<true>(q, ra, q.hop + HOP_A, ep0 + 4 * a.L + 1, 6u, a.hint_mask & 1, nullptr, qd & 1, 0, true, gA, bA);
     };
     sweep_t(0);
     for (int qd = 0; qd < nq; ++qd) {
@@ -1446,257 +1336,111 @@ __device__ __forceinline__ void comm_role_pipe(const MegaArgs& a, const Ctx& c0,
 __device__ __forceinline__ void compute_role_pipe(const MegaArgs& a, const Ctx& c0) {
   Ctx q = c0;
   unsigned char* smem = c0.smem;
-  const int Rtot = c0.Rtot;
-  const int nq = (Rtot + RMAX - 1) / RMAX;
+  const int nq = (c0.Rtot + RMAX - 1) / RMAX;
   const int V = a.V;
   const int EPS = 4 * a.L + 2;
-  auto kv_row_base = [&](int layer, int which, int r) -> const _Float16* {
-    const int b = batch_row(q, r);
-    return a.kv + ((size_t)(layer * 2 + which)) * a.kv_layer_stride + ((size_t)b * NH + q.head) * (size_t)a.smax * HD;
-  };
-  const h8* wp = a.wpack;
-  auto p1_src = [&](int layer) { return wp + ((size_t)layer * LAYER_HALFS + ((size_t)q.head * 4 + q.cw) * WI_P1 * 512) / 8 + q.lane; };
-  auto pm_src = [&](int layer, int off) {
-    return wp + ((size_t)layer * LAYER_HALFS + P1_HALFS + (((size_t)q.member * 4 + q.cw) * (WI_P2 + WI_P3 + WI_P4) + off) * 512) / 8 + q.lane;
-  };
-  h8 wA0[WI_P1 / 2], wA1[WI_P1 / 2], wB[WI_P2], wC[WI_P3], wD[WI_P4];
+  h8 wA0[WI_P1 / 2], wA1[WI_P1 / 2], wB[WI_P2], wC[WI_P3], wD[WI_P4];       // as in compute_role
   int cgen = 0;
-  wload(wA0, p1_src(0));
-  wload(wA1, p1_src(0) + (size_t)(WI_P1 / 2) * 64);
+  wload(wA0, p1_src(a, q, 0));
+  wload(wA1, p1_src(a, q, 0) + (size_t)(WI_P1 / 2) * 64);
   for (int s = 0; s < a.nsteps; ++s) {
     const unsigned ep0 = a.ep_base + (unsigned)s * (unsigned)EPS;
+    // a slot's preamble: quad qd becomes the current one (its rows, state entries and hop buffers)
+    auto enter = [&](int qd, int l) { relaunder(q); set_quad(q, qd); q.hop = hop_slot(q, s, l); };
     for (int l = 0; l < a.L; ++l) {
       const int ab_l = *st_abort(q);       // the abort test of this layer: read here, acted on behind the first barrier
       const float* lp = a.fpack + (size_t)l * FP_LAYER;
       // ================= P1.  The first slot's barrier and the next phase's weight request stand in FRONT of the quad loop: a
       // request inside the loop is either conditional (`if (qd == 0)`: a conditional definition keeps the register array's old
-      // contents alive around the whole loop, ~100 spilled VGPRs) or repeated per quad -- and the weight loads are
-      // non-temporal, so the repeats miss L2 and every quad streamed the layer's slice again from the memory side: 6 GB per
-      // step at B = 128, no faster than the sequential quads (1.07 ms per step both)
+      // contents alive around the whole loop, ~100 spilled VGPRs) or repeated per quad -- and with non-temporal weight loads
+      // the repeats missed L2 and every quad streamed the layer's slice again from the memory side: 6 GB per step at
+      // B = 128, 1.07 ms per step
       MG_BAR_AL(q);                                                         // B_a of quad 0
       if (l == 0 && s > 0 && group_done(q)) return;
       relaunder(q);
-      wload(wB, pm_src(l, 0));
+      wload(wB, pm_src(a, q, l, 0));
       for (int qd = 0; qd < nq; ++qd) {
         if (qd > 0) {
           MG_BAR();                                                         // B_a: XS copy qd & 1 holds LN(y); the image is free
         }
-        relaunder(q);
-        set_quad(q, qd);
-        const int R = q.R;
-        q.hop = hop_slot(q, s, l);
-        q.prof_on = false;
-        const int rj_which = (q.lane >> 3) % 3, rj_e = 4 * (q.lane & 7);
-        const f4 p1_bias = q.lane < 24 ? *(const f4*)(lp + FP_QKVB + rj_which * D + q.head * HD + rj_e) : (f4){0.f, 0.f, 0.f, 0.f};
-        const _Float16* xs = (const _Float16*)(smem + L_XS) + (qd & 1) * RMAX * XS_LD;
-        gemm_chunk<3>(q, wA0, xs, XS_LD, q.cw, q.cw * 6);
-        gemm_chunk<3>(q, wA1, xs, XS_LD, q.cw, q.cw * 6 + 3);
+        enter(qd, l);
+        const f4 p1_bias = qkv_bias(lp, q.lane, q.head);
+        gemm_chunk<3>(q, wA0, xs_img(smem, qd & 1), XS_LD, q.cw, q.cw * 6);
+        gemm_chunk<3>(q, wA1, xs_img(smem, qd & 1), XS_LD, q.cw, q.cw * 6 + 3);
         MG_BAR();                                                           // B_b: partials parked, this quad's K/V image stored
-        {
-          const f4* red = (const f4*)(smem + L_RED);
-          _Float16* qkv_s = (_Float16*)(smem + L_QKV);
-          const int ro = q.cw / 2, r = 2 * ro + q.half;
-          if (q.lane < 24 && r < R) {
-            const int tile = rj_which * 2 + (rj_e >> 4), ln = r + 16 * ((rj_e & 15) >> 2);
-            const f4 v0 = red[red_idx(0 * 6 + tile, ln)], v1 = red[red_idx(1 * 6 + tile, ln)], v2 = red[red_idx(2 * 6 + tile, ln)],
-                     v3 = red[red_idx(3 * 6 + tile, ln)];
-            f4 v = v0;
-            v += v1; v += v2; v += v3;
-            v += p1_bias;
-            *(h4*)(qkv_s + (ro * 3 + rj_which) * HD + rj_e) = (h4){(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-          }
-          asm volatile("" ::: "memory");
-        }
+        qkv_reduce(smem, q.lane, q.cw, q.half, q.R, p1_bias);
         attention_part<2>(a, q, l, q.cw);
-        if (compute_barrier(q, cgen)) return;                                          // the partials of a row's two waves meet (compute waves only)
-        if (q.cw == 0) {
-          const float* s_m = (const float*)(smem + L_ATT);
-          const float* s_acc = s_m + 8;
-          const int ro = q.lane >> 5, e = q.lane & 31, r = 2 * ro + q.half;
-          float M = -INFINITY;
-#pragma unroll
-          for (int w = 0; w < 2; ++w) M = fmaxf(M, s_m[2 * ro + w]);
-          float o = 0.f;
-          if (M != -INFINITY) {
-            float Lsum = 0.f, num = 0.f;
-#pragma unroll
-            for (int w = 0; w < 2; ++w) {
-              const float mw = s_m[2 * ro + w];
-              const float ew = mw == -INFINITY ? 0.f : __expf(mw - M);
-              const float* pa = s_acc + (2 * ro + w) * 4 * 36;
-              Lsum += ((pa[32] + pa[36 + 32]) + (pa[72 + 32] + pa[108 + 32])) * ew;
-              num += ((pa[e] + pa[36 + e]) + (pa[72 + e] + pa[108 + e])) * ew;
-            }
-            o = num / Lsum;
-          }
-          const float o2 = dpp_f<DPP_QUAD_XOR1>(o);
-          if (r < R && !(e & 1)) gstore(q.hop + HOP_B + r * 256 + (q.head * HD + e) / 2, ep0 + 4 * l + 2, pack_h2(o, o2));
-        }
-        if (q.cw == 1 && q.lane < 32) {                                    // K/V arena append of this step's k, v (see compute_role)
-          const int ro = q.lane >> 4, which = (q.lane >> 3) & 1, e = 4 * (q.lane & 7), r = 2 * ro + q.half;
-          if (r < R && st_active(q)[r]) {
-            const int pos = st_kvlen(q)[r];
-            if (pos < a.smax)
-              *(h4*)(const_cast<_Float16*>(kv_row_base(l, which, r)) + (size_t)pos * HD + e) =
-                  *(const h4*)((const _Float16*)(smem + L_QKV) + (ro * 3 + 1 + which) * HD + e);
-          }
-        }
+        if (compute_barrier(q, cgen)) return;                              // the partials of a row's two waves meet (compute waves only)
+        if (q.cw == 0) attn_combine_publish(smem, q.lane, q.head, q.half, q.R, q.hop + HOP_B, ep0 + 4 * l + 2);
+        // the next quad's reduce overwrites the q/k/v copy before P2 comes round, so the arena append happens here (the
+        // comm waves' K/V burst of the next slot was issued a whole attention ago and has drained)
+        if (q.cw == 1 && q.lane < 32) arena_append(a, smem, q.lane, l, q.head, q.half, q.R, batch_row(q, 0), st_active(q), st_kvlen(q));
       }
       // ================= P2: out-projection
       MG_BAR();                                                             // AT copy 0 holds quad 0's attention output
       relaunder(q);
-      wload(wC, pm_src(l, WI_P2));
+      wload(wC, pm_src(a, q, l, WI_P2));
       for (int qd = 0; qd < nq; ++qd) {
         if (qd > 0) {
           MG_BAR();                                                         // AT copy qd & 1 holds the attention output
         }
-        relaunder(q);
-        set_quad(q, qd);
-        const int R = q.R;
-        q.hop = hop_slot(q, s, l);
+        enter(qd, l);
         const f4 p_bias = *(const f4*)(lp + FP_OUTB + 16 * q.member + 4 * (q.lane >> 4));
-        gemm_chunk<1>(q, wB, (const _Float16*)(smem + L_AT) + (qd & 1) * RMAX * XS_LD, XS_LD, q.cw, q.cw);
+        gemm_chunk<1>(q, wB, at_img(smem, qd & 1), XS_LD, q.cw, q.cw);
         if (compute_barrier(q, cgen)) return;
-        if (q.cw == 0) {
-          const f4* red = (const f4*)(smem + L_RED);
-          const int r = q.lane & 15;
-          if (r < R) {
-            const f4 v0 = red[red_idx(0, q.lane)], v1 = red[red_idx(1, q.lane)], v2 = red[red_idx(2, q.lane)], v3 = red[red_idx(3, q.lane)];
-            f4 v = v0;
-            v += v1; v += v2; v += v3;
-            v += p_bias;
-            v += *rs_at(smem, 0, qd, q.lane);
-            *(f4*)((float*)(smem + L_STAGE) + r * 16 + 4 * (q.lane >> 4)) = v;
-          }
-          const bool stall = a.test_stall && q.member == a.test_stall - 1 && q.group == 0 && s == 2 && l == 3 && qd == 0;
-          if (q.lane < R * 16 && !stall)
-            gstore(q.hop + HOP_C + (q.lane >> 4) * 512 + 16 * q.member + (q.lane & 15), ep0 + 4 * l + 3,
-                   __float_as_uint(((const float*)(smem + L_STAGE))[q.lane]));
-        }
+        if (q.cw == 0)
+          reduce_residual_publish(smem, q.lane, q.member, q.R, p_bias, *rs_at(smem, 0, qd, q.lane), q.hop + HOP_C, ep0 + 4 * l + 3,
+                                  stall_hook(a, q.member, q.group, s, l, qd));
       }
       // ================= P3: FFN1 + ReLU
       MG_BAR();                                                             // XS copy 0 holds LN1(y1) of quad 0
       relaunder(q);
-      wload(wD, pm_src(l, WI_P2 + WI_P3));
+      wload(wD, pm_src(a, q, l, WI_P2 + WI_P3));
       for (int qd = 0; qd < nq; ++qd) {
         if (qd > 0) {
           MG_BAR();                                                         // XS copy qd & 1 holds LN1(y1)
         }
-        relaunder(q);
-        set_quad(q, qd);
-        const int R = q.R;
-        q.hop = hop_slot(q, s, l);
+        enter(qd, l);
         const f4 p_bias = *(const f4*)(lp + FP_B1 + 64 * q.member + 16 * q.cw + 4 * (q.lane >> 4));
-        f4 v = gemm_tile_k512(q, wC, (const _Float16*)(smem + L_XS) + (qd & 1) * RMAX * XS_LD, XS_LD);
-        {
-          // tile cw of the member's four, published by the wave that computed it (see compute_role)
-          const int r = q.lane & 15;
-          unsigned* stage = (unsigned*)(smem + L_STAGE) + q.cw * 64;
-          v += p_bias;
-          if (r < R) {
-            const int w0 = r * 8 + 2 * (q.lane >> 4);
-            stage[w0] = pack_h2(fmaxf(v[0], 0.f), fmaxf(v[1], 0.f));
-            stage[w0 + 1] = pack_h2(fmaxf(v[2], 0.f), fmaxf(v[3], 0.f));
-          }
-          if (q.lane < R * 8)
-            gstore(q.hop + HOP_D + (q.lane >> 3) * 1024 + 32 * q.member + 8 * q.cw + (q.lane & 7), ep0 + 4 * l + 4, stage[q.lane]);
-        }
+        const f4 v = gemm_tile_k512(q, wC, xs_img(smem, qd & 1), XS_LD);
+        ffn1_publish(smem, q.lane, q.cw, q.member, q.R, v, p_bias, q.hop + HOP_D, ep0 + 4 * l + 4);
       }
       // ================= P4: FFN2
       MG_BAR();                                                             // HS copy 0 holds quad 0's FFN hidden
       relaunder(q);
-      if (l + 1 < a.L) wload(wA0, p1_src(l + 1));                          // P1 has finished with both halves for every quad
-      else wload(wA0, a.lpack + (((size_t)q.member * 4 + q.cw) * WI_LG * 512) / 8 + q.lane);
-      wload(wA1, p1_src(l + 1 < a.L ? l + 1 : 0) + (size_t)(WI_P1 / 2) * 64);
+      if (l + 1 < a.L) wload(wA0, p1_src(a, q, l + 1));                    // P1 has finished with both halves for every quad
+      else wload(wA0, lg_src(a, q));
+      wload(wA1, p1_src(a, q, l + 1 < a.L ? l + 1 : 0) + (size_t)(WI_P1 / 2) * 64);
       for (int qd = 0; qd < nq; ++qd) {
         if (qd > 0) {
           MG_BAR();                                                         // HS copy qd & 1 holds the FFN hidden
         }
-        relaunder(q);
-        set_quad(q, qd);
-        const int R = q.R;
-        q.hop = hop_slot(q, s, l);
+        enter(qd, l);
         const f4 p_bias = *(const f4*)(lp + FP_B2 + 16 * q.member + 4 * (q.lane >> 4));
-        {
-          const int rowl = q.lane & 15, kg = q.lane >> 4;
-          f4* red = (f4*)(smem + L_RED);
-          f4 acc = (f4){0.f, 0.f, 0.f, 0.f};
-          const _Float16* bp0 = (const _Float16*)(smem + L_HS) + ((qd & 1) * RMAX + (rowl & (RMAX - 1))) * HS_LD + (4 * q.cw) * 128 + 8 * kg;
-          h8 bA[4], bB[4];                                   // chunk cc + 1's operands in flight under chunk cc's MFMAs (see compute_role)
-#pragma unroll
-          for (int ks = 0; ks < 4; ++ks) bA[ks] = *(const h8*)(bp0 + 32 * ks);
-#pragma unroll
-          for (int cc = 0; cc < 4; cc += 2) {
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) bB[ks] = *(const h8*)(bp0 + (cc + 1) * 128 + 32 * ks);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wD[cc * 4 + ks], bA[ks], acc, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (cc + 2 < 4) {
-#pragma unroll
-              for (int ks = 0; ks < 4; ++ks) bA[ks] = *(const h8*)(bp0 + (cc + 2) * 128 + 32 * ks);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wD[(cc + 1) * 4 + ks], bB[ks], acc, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-          if (rowl < RMAX) red[red_idx(q.cw, q.lane)] = acc;
-        }
+        ffn2_chunks(wD, hs_img(smem, qd & 1), smem, q.lane, q.cw);
         if (compute_barrier(q, cgen)) return;
-        if (q.cw == 0) {
-          const f4* red = (const f4*)(smem + L_RED);
-          const int r = q.lane & 15;
-          if (r < R) {
-            const f4 v0 = red[red_idx(0, q.lane)], v1 = red[red_idx(1, q.lane)], v2 = red[red_idx(2, q.lane)], v3 = red[red_idx(3, q.lane)];
-            f4 v = v0;
-            v += v1; v += v2; v += v3;
-            v += p_bias;
-            v += *rs_at(smem, 1, qd, q.lane);
-            *(f4*)((float*)(smem + L_STAGE) + r * 16 + 4 * (q.lane >> 4)) = v;
-          }
-          const unsigned ep = l + 1 < a.L ? ep0 + 4 * (l + 1) + 1 : ep0 + 4 * a.L + 1;
-          if (q.lane < R * 16)
-            gstore(hop_slot(q, s, l + 1) + HOP_A + (q.lane >> 4) * 512 + 16 * q.member + (q.lane & 15), ep,
-                   __float_as_uint(((const float*)(smem + L_STAGE))[q.lane]));
-        }
+        if (q.cw == 0)                     // y2 feeds hop A of the next layer, or hop A' (the logits' LayerNorm) after the last layer
+          reduce_residual_publish(smem, q.lane, q.member, q.R, p_bias, *rs_at(smem, 1, qd, q.lane), hop_slot(q, s, l + 1) + HOP_A,
+                                  ep0 + 4 * (l + 1) + 1, false);
       }
     }
     // ================= tail: logits
-    const unsigned epE = ep0 + 4 * a.L + 2;
     for (int qd = 0; qd < nq; ++qd) {
-      relaunder(q);
-      set_quad(q, qd);
-      const int R = q.R;
-      q.hop = hop_slot(q, s, a.L);
+      enter(qd, a.L);
       MG_BAR();                                                             // XS copy qd & 1 holds LN2(y) of the last layer
-      gemm_chunk<3>(q, wA0, (const _Float16*)(smem + L_XS) + (qd & 1) * RMAX * XS_LD, XS_LD, q.cw, q.cw * 3);
+      gemm_chunk<3>(q, wA0, xs_img(smem, qd & 1), XS_LD, q.cw, q.cw * 3);
       if (compute_barrier(q, cgen)) return;
-      if (q.cw < 3) {
-        const f4* red = (const f4*)(smem + L_RED);
-        const int t = q.cw, r = q.lane & 15;
-        const int tile = t == 0 ? q.member : (t == 1 ? q.member + 32 : 64);
-        float* stage = (float*)(smem + L_STAGE) + q.cw * 256;
-        if (r < R) {
-          f4 v = red[red_idx(0 * 3 + t, q.lane)];
-          v += red[red_idx(1 * 3 + t, q.lane)]; v += red[red_idx(2 * 3 + t, q.lane)]; v += red[red_idx(3 * 3 + t, q.lane)];
-          *(f4*)(stage + r * 16 + 4 * (q.lane >> 4)) = v;
-        }
-        if (q.lane < R * 16 && (t < 2 || q.member == 0) && 16 * tile + (q.lane & 15) < V)
-          gstore(q.hop + HOP_E + (q.lane >> 4) * VPAD + 16 * tile + (q.lane & 15), epE, __float_as_uint(stage[q.lane]));
-      }
+      if (q.cw < 3) logits_publish(smem, q.lane, q.cw, q.member, q.R, V, q.hop + HOP_E, ep0 + 4 * a.L + 2);
     }
     MG_BAR();                                                               // end of the step's GEMMs
-    wload(wA0, p1_src(0));                                                 // the next step's first slice follows the logits slice's last reader
+    wload(wA0, p1_src(a, q, 0));                                           // the next step's first slice follows the logits slice's last reader
   }
 }
 
-// MODE 0: one quad per group (B <= 32); 1: several quads, one after the other in every phase (kept for A/B: GSV_MEGA_QUADS=seq);
-// 2: several quads, pipelined (default for 32 < B <= 128)
+// PIPE = false: one quad per group (B <= 32); true: several quads, pipelined (32 < B <= 128)
 // PROF: the in-kernel stamps (tools/mega_prof.py) are compiled in only for measurement launches -- as run-time tests they
-// cost ~100 scalar instructions per layer and wave
-template <int MODE, bool PROF>
+// cost ~100 scalar instructions per layer and wave.  Only the single-quad roles carry stamps.
+template <bool PIPE, bool PROF>
 __global__ __launch_bounds__(MG_THREADS, 1) void t2s_mega_kernel(MegaArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   Ctx c;
@@ -1775,12 +1519,12 @@ __global__ __launch_bounds__(MG_THREADS, 1) void t2s_mega_kernel(MegaArgs a) {
   }
   __syncthreads();
   if (group_done(c)) return;
-  if constexpr (MODE == 2) {
+  if constexpr (PIPE) {
     if (c.comm) comm_role_pipe(a, c, sp);
     else compute_role_pipe(a, c);
   } else {
-    if (c.comm) comm_role<MODE == 1, PROF>(a, c, sp);
-    else compute_role<MODE == 1, PROF>(a, c);
+    if (c.comm) comm_role<PROF>(a, c, sp);
+    else compute_role<PROF>(a, c);
   }
 }
 
@@ -1861,20 +1605,17 @@ int mega_census(hipStream_t s, unsigned* d_scratch, unsigned* h_pinned) {
 int launch_t2s_mega(const MegaArgs& a, hipStream_t s) {
   // every launch: the attribute belongs to the (function, device) pair, and TTS.set_device may have moved the handle's owner
   // to another GPU of the process since the last launch (mega_census does the same)
-  static const bool seq_quads = getenv("GSV_MEGA_QUADS") && !strcmp(getenv("GSV_MEGA_QUADS"), "seq");
-#define GSV_MEGA_LAUNCH(MODE, PROF)                                                                                              \
+#define GSV_MEGA_LAUNCH(PIPE, PROF)                                                                                              \
   do {                                                                                                                          \
-    GSV_HIP(hipFuncSetAttribute((const void*)t2s_mega_kernel<MODE, PROF>, hipFuncAttributeMaxDynamicSharedMemorySize, L_TOTAL)); \
-    hipLaunchKernelGGL((t2s_mega_kernel<MODE, PROF>), dim3(MG_NWG), dim3(MG_THREADS), L_TOTAL, s, a);                            \
+    GSV_HIP(hipFuncSetAttribute((const void*)t2s_mega_kernel<PIPE, PROF>, hipFuncAttributeMaxDynamicSharedMemorySize, L_TOTAL)); \
+    hipLaunchKernelGGL((t2s_mega_kernel<PIPE, PROF>), dim3(MG_NWG), dim3(MG_THREADS), L_TOTAL, s, a);                            \
   } while (0)
-  const bool prof = a.prof != nullptr;                // measurement launches (tools/mega_prof.py): stamps compiled in
-  if (a.B > RMAX * MG_GROUPS && seq_quads) {          // more than one quad per group, one after the other (A/B)
-    if (prof) GSV_MEGA_LAUNCH(1, true); else GSV_MEGA_LAUNCH(1, false);
-  } else if (a.B > RMAX * MG_GROUPS) {                // pipelined quads (no stamps)
-    GSV_MEGA_LAUNCH(2, false);
-  } else {
-    if (prof) GSV_MEGA_LAUNCH(0, true); else GSV_MEGA_LAUNCH(0, false);
-  }
+  // Three kernels.  More than one quad per group (B > 32): pipelined quads, which carry no stamps -- a profiling request
+  // (a.prof, tools/mega_prof.py) at B > 32 runs this kernel all the same and its stamp buffer stays zero.  One quad: stamps
+  // compiled in for measurement launches only.
+  if (a.B > RMAX * MG_GROUPS) GSV_MEGA_LAUNCH(true, false);
+  else if (a.prof != nullptr) GSV_MEGA_LAUNCH(false, true);
+  else GSV_MEGA_LAUNCH(false, false);
 #undef GSV_MEGA_LAUNCH
   GSV_HIP(hipGetLastError());
   return GSV_OK;

@@ -361,3 +361,28 @@ def test_multi_quad_ragged_eos_and_teacher_forced_logits():
         worst = max(worst, float(np.abs(La[:n + 1, r] - Lb[:n + 1, r]).max()))
     print(f"[mega] B=77 (quads) teacher-forced logits vs launch path over every executed step: max-abs {worst:.3e}")
     assert worst <= 4e-2
+
+
+def test_pipelined_and_single_quad_kernels_give_the_same_logits_per_row(v2_engine_128, v2_engine):
+    """The pipelined kernel (B = 40: five rows per group, a full quad and a quad of one row) and the single-quad kernel
+    (the same first 32 rows alone) run the same phase bodies (csrc/t2s_mega.hip) on a row, so teacher-forced on the same
+    tokens they must give the same logits for rows 0..31 at every step, bit for bit.  Measured before the bodies were shared: already bit-equal (max-abs 0 over 11 dumped steps), so exact equality
+    is asserted."""
+    B, steps = 40, 10
+    xs, berts, prompts = _batch(B)
+    g = torch.Generator().manual_seed(B)
+    tok = torch.randint(0, 1024, (B, steps + 1), generator=g, dtype=torch.int32)
+    kw = dict(top_k=1, top_p=1.0, temperature=1.0, early_stop_num=steps, repetition_penalty=1.35, dump_logits=True)
+    big, small = v2_engine_128, v2_engine
+    big.set_mega(True)
+    _, ia = big.infer_panel_batch_infer(xs, None, prompts, berts, force_tokens=tok, **kw)
+    assert big.decode_info()[0] == 1 and ia == [steps] * B
+    La = big.last_logits_dump.cpu().numpy()[:, :32]
+    small.set_mega(True)
+    _, ib = small.infer_panel_batch_infer(xs[:32], None, prompts[:32], berts[:32], force_tokens=tok[:32], **kw)
+    assert small.decode_info()[0] == 1 and ib == [steps] * 32
+    Lb = small.last_logits_dump.cpu().numpy()
+    assert La.shape == Lb.shape and La.shape[0] >= steps and np.isfinite(Lb).all() and np.abs(Lb[1:]).max() > 1.0
+    err = float(np.abs(La - Lb).max())
+    print(f"[mega] rows 0..31 of B=40 (pipelined) vs B=32 (single quad), {La.shape[0]} teacher-forced steps: max-abs {err:.3e}")
+    assert np.array_equal(La, Lb)

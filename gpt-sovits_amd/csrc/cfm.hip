@@ -10,6 +10,8 @@
 // the text embedding (ConvNeXt-V2 stack), the rotary table and the prompt / text columns of the input
 // concatenation are built once per utterance (the reference caches the first two the same way, models.py:1046-1062).
 // Gate * (W a + b) + residual is the GEMM epilogue (ConvArgs::gate), GELU / Mish too.
+#include <cmath>
+
 #include "engine.h"
 
 using namespace gsv;
@@ -49,14 +51,17 @@ __global__ void cfm_cast_rows_kernel(const float* __restrict__ src, int lds, int
 // The kernels that look along time take the utterance (row of the batch) as blockIdx.y: one launch over all rows, every row
 // an independent [Tn][C] slab, back to back.
 //
-// te0[t][c] = mu[t][c] + table[min(t, 4095)][c]   (TextEmbedding.forward, dit.py:50-72)
+// te0[t][c] = mu[t][c] + table[min(t, 4095)][c]   (TextEmbedding.forward, dit.py:50-72).  Rows from `mu_rows` on have no
+// text: zeros before the table (drop_text, dit.py:44-48) -- the null text row of a guided pass.
 template <typename T>
-__global__ void cfm_text_pos_kernel(const float* __restrict__ mu, const float* __restrict__ table, int Tn, int C, T* __restrict__ out) {
+__global__ void cfm_text_pos_kernel(const float* __restrict__ mu, int mu_rows, const float* __restrict__ table, int Tn, int C,
+                                    T* __restrict__ out) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)Tn * C) return;
   int t = (int)(i / C), c = (int)(i - (long long)t * C);
   const long long o = (long long)blockIdx.y * Tn * C + i;
-  out[o] = (T)(mu[o] + table[(long long)min(t, 4095) * C + c]);
+  const float tab = table[(long long)min(t, 4095) * C + c];
+  out[o] = (T)((int)blockIdx.y < mu_rows ? mu[o] + tab : tab);
 }
 
 // depthwise conv, 7 taps, zero padding 3 (ConvNeXtV2Block.dwconv, modules.py:250)
@@ -189,7 +194,8 @@ __device__ __forceinline__ unsigned long long cfm_mix64(unsigned long long z) {
 }
 
 // what differs between the utterances of one call: the prompt mel (channels-first [C][Tp], device) and its length, and the key
-// of the noise draw.  A small device array, one entry per utterance, read by the four kernels below.
+// of the noise draw.  A small device array, one entry per utterance, read by the kernels below.  A guided pass appends one
+// entry per unconditioned twin: prompt null (its cond columns are zeros whatever Tp says), Tp the conditioned row's.
 struct CfmRow {
   const float* prompt;
   unsigned long long seed;
@@ -241,6 +247,32 @@ __global__ void cfm_euler_kernel(float* __restrict__ x, const float* __restrict_
   xin[(long long)row * ldin + c] = (T)u;
 }
 
+// The Euler update of a guided pass (models.py:1063-1084): v holds the conditioned estimate of request b in DiT row b and the
+// unconditioned one in its twin, row B + b (rows = B * Tn frames of requests, so the twin of frame i is frame rows + i).
+// x += d * (v_pos + (v_pos - v_neg) * rate) in fp32, prompt frames held at 0, and the refreshed x goes into the x columns of
+// BOTH rows: the two estimates of the next step see the same state.
+template <typename T>
+__global__ void cfm_euler_cfg_kernel(float* __restrict__ x, const float* __restrict__ v, float d, float rate, int rows, int Tn,
+                                     const CfmRow* __restrict__ rw, int C, T* __restrict__ xin, int ldin) {
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long n = (long long)rows * C;
+  if (i >= n) return;
+  int row = (int)(i / C), c = (int)(i - (long long)row * C);
+  const int b = row / Tn, t = row - b * Tn;
+  const int Tp = rw[b].Tp;
+  float u = 0.f;
+  if (t >= Tp) {
+    u = x[i];
+    if (v) {
+      const float vp = v[i], vn = v[n + i];
+      u += d * (vp + (vp - vn) * rate);
+    }
+  }
+  x[i] = u;
+  xin[(long long)row * ldin + c] = (T)u;
+  xin[((long long)rows + row) * ldin + c] = (T)u;
+}
+
 // prompt mel (channels-first [C][Tp]) -> the cond columns of the DiT input, zero after the prompt; also zeroes the pad columns
 template <typename T>
 __global__ void cfm_cond_kernel(const CfmRow* __restrict__ rw, int Tn, int C, T* __restrict__ xin, int ldin, int col0, int pad0) {
@@ -251,7 +283,7 @@ __global__ void cfm_cond_kernel(const CfmRow* __restrict__ rw, int Tn, int C, T*
   const float* prompt = rw[blockIdx.y].prompt;
   const int Tp = rw[blockIdx.y].Tp;
   xin += (long long)blockIdx.y * Tn * ldin;
-  if (c < C) xin[(long long)t * ldin + col0 + c] = (T)(t < Tp ? prompt[(long long)c * Tp + t] : 0.f);
+  if (c < C) xin[(long long)t * ldin + col0 + c] = (T)(prompt && t < Tp ? prompt[(long long)c * Tp + t] : 0.f);
   else xin[(long long)t * ldin + pad0 + (c - C)] = (T)0.f;
 }
 
@@ -261,6 +293,15 @@ __global__ void cfm_copy_cols_kernel(const T* __restrict__ src, int lds, int row
   if (i >= (long long)rows * C) return;
   int r = (int)(i / C), c = (int)(i - (long long)r * C);
   dst[(long long)r * ldd + col0 + c] = src[(long long)r * lds + c];
+}
+
+// one [Tn][C] slab into columns [col0, col0 + C) of every row blockIdx.y of dst (the null text embedding into all twins)
+template <typename T>
+__global__ void cfm_bcast_cols_kernel(const T* __restrict__ src, int Tn, int C, T* __restrict__ dst, int ldd, int col0) {
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)Tn * C) return;
+  int t = (int)(i / C), c = (int)(i - (long long)t * C);
+  dst[((long long)blockIdx.y * Tn + t) * ldd + col0 + c] = src[i];
 }
 
 // channels-last fp32 [Tn][C] -> channels-first [C][Tn]; the prompt frames are written as the zeros they are held at
@@ -351,31 +392,48 @@ int cfm_modulations(gsv_cfm* c, hipStream_t s, int N, float** mods_out) {
 // weights once per step instead of once per chunk.  The ops that look along time (depthwise convs, GRN, fused attention)
 // take the utterance as a grid dimension: one launch for all of them.  Only the two grouped position convs and the
 // materialised attention (the parity path) are issued per utterance.
+//
+// Classifier-free guidance (cfg_rate > CFM_CFG_THRESHOLD, models.py:1063-1081): the DiT runs over 2 B rows.  Rows [0, B) are
+// the requests as above; row B + b is request b's unconditioned twin -- the same x columns, zero cond columns, and the null
+// text embedding (the text stack run on ONE extra row of zero text, then copied into every twin: it depends on Tn alone).
+// The Euler state, the noise draw and the output stay B rows; cfm_euler_cfg_kernel combines the two estimates.  Unguided,
+// DB == B and every launch below is the one it was.
+constexpr float CFM_CFG_THRESHOLD = 1e-5f;
+
 template <typename T>
 int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* mu, const std::vector<CfmRow>& host_rows, int Tn, int N,
-                    const float* noise, float temperature, float* out) {
+                    const float* noise, float temperature, float cfg_rate, float* out) {
   gsv_vits* h = &c->ctx;
   const auto& g = c->cfg;
   const int D = g.dim, td = g.text_dim, md = g.mel_dim, inner = g.heads * g.dim_head, FF = D * g.ff_mult, ldin = c->ldin;
   const int half = g.dim_head / 2;
   const size_t es = sizeof(T);
-  const int B = (int)host_rows.size();
-  const int R = B * Tn;
+  const bool guided = cfg_rate > CFM_CFG_THRESHOLD;
+  const int B = (int)host_rows.size();        // requests: rows of x, noise and out
+  const int DB = guided ? 2 * B : B;          // rows the DiT sees
+  const int TB = guided ? B + 1 : B;          // rows of the text stack: the requests, then the null text row
+  const int RX = B * Tn, R = DB * Tn, RT = TB * Tn;
+  std::vector<CfmRow> with_twins;             // guided only: the requests' entries, then one per twin
+  if (guided) {
+    with_twins = host_rows;
+    for (int b = 0; b < B; ++b) with_twins.push_back(CfmRow{nullptr, 0ull, host_rows[b].Tp, 0});
+  }
+  const std::vector<CfmRow>& table = guided ? with_twins : host_rows;
   CfmRow* rw;
-  GSV_RC(need(h, "cfm_rows", (size_t)B * sizeof(CfmRow), (void**)&rw));
-  for (int b0 = 0; b0 < B; b0 += CFM_ROW_CHUNK) {
-    const int n = std::min(CFM_ROW_CHUNK, B - b0);
+  GSV_RC(need(h, "cfm_rows", (size_t)DB * sizeof(CfmRow), (void**)&rw));
+  for (int b0 = 0; b0 < DB; b0 += CFM_ROW_CHUNK) {
+    const int n = std::min(CFM_ROW_CHUNK, DB - b0);
     CfmRowChunk ch{};
-    std::copy_n(host_rows.begin() + b0, n, ch.r);
+    std::copy_n(table.begin() + b0, n, ch.r);
     hipLaunchKernelGGL(cfm_rows_fill_kernel, dim3(1), dim3(CFM_ROW_CHUNK), 0, s, ch, n, rw + b0);
     GSV_HIP(hipGetLastError());
   }
   float *x, *v, *cs, *gx;
   void *xin, *ta, *tb, *tw, *hb, *c1, *nrm, *qkv, *ao, *ff;
-  GSV_RC(need(h, "cfm_x", (size_t)R * md * 4, (void**)&x));
+  GSV_RC(need(h, "cfm_x", (size_t)RX * md * 4, (void**)&x));
   GSV_RC(need(h, "cfm_v", (size_t)R * md * 4, (void**)&v));
   GSV_RC(need(h, "cfm_cs", (size_t)Tn * half * 2 * 4, (void**)&cs));
-  GSV_RC(need(h, "cfm_gx", (size_t)B * 2 * td * 4, (void**)&gx));
+  GSV_RC(need(h, "cfm_gx", (size_t)TB * 2 * td * 4, (void**)&gx));
   GSV_RC(need(h, "cfm_xin", (size_t)R * ldin * es, &xin));
   GSV_RC(need(h, "cfm_ta", (size_t)R * td * es, &ta));
   GSV_RC(need(h, "cfm_tb", (size_t)R * td * es, &tb));
@@ -389,30 +447,39 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
   auto rows = [&](void* p, int b, int width) { return (void*)((char*)p + (size_t)b * Tn * width * es); };
 
   // ---- per-utterance constants: text embedding (dit.py:50-72), cond columns, rotary table
-  CFM_LAUNCH_ROWS(cfm_text_pos_kernel<T>, (long long)Tn * td, B, mu, c->pos_table, Tn, td, (T*)ta);
+  CFM_LAUNCH_ROWS(cfm_text_pos_kernel<T>, (long long)Tn * td, TB, mu, B, c->pos_table, Tn, td, (T*)ta);
   for (auto& blk : c->text) {
-    CFM_LAUNCH_ROWS(cfm_dwconv7_kernel<T>, (long long)Tn * td, B, (const T*)ta, blk.dw, blk.db, Tn, td, (T*)tb);
-    GSV_RC(launch_layernorm(h->dtype, tb, 0, nullptr, 0, blk.ng, blk.nb, tb, 0, R, td, 1e-6f, s));
+    CFM_LAUNCH_ROWS(cfm_dwconv7_kernel<T>, (long long)Tn * td, TB, (const T*)ta, blk.dw, blk.db, Tn, td, (T*)tb);
+    GSV_RC(launch_layernorm(h->dtype, tb, 0, nullptr, 0, blk.ng, blk.nb, tb, 0, RT, td, 1e-6f, s));
     ConvOpt og; og.post_act = ACT_GELU;
-    GSV_RC(conv(h, s, blk.pw1, tb, td, R, tw, R, og));
-    // GRN statistics are per utterance (norm over its own frames): gx [B][2 td]
-    hipLaunchKernelGGL(cfm_grn_norm_kernel<T>, dim3(cdiv(2 * td, 64), B), dim3(256), 0, s, (const T*)tw, Tn, 2 * td, gx);
-    hipLaunchKernelGGL(cfm_grn_apply_kernel<T>, dim3(std::min(1024, nblk((long long)Tn * 2 * td)), B), dim3(256), 0, s, (T*)tw, gx,
+    GSV_RC(conv(h, s, blk.pw1, tb, td, RT, tw, RT, og));
+    // GRN statistics are per utterance (norm over its own frames): gx [TB][2 td]
+    hipLaunchKernelGGL(cfm_grn_norm_kernel<T>, dim3(cdiv(2 * td, 64), TB), dim3(256), 0, s, (const T*)tw, Tn, 2 * td, gx);
+    hipLaunchKernelGGL(cfm_grn_apply_kernel<T>, dim3(std::min(1024, nblk((long long)Tn * 2 * td)), TB), dim3(256), 0, s, (T*)tw, gx,
                        blk.gg, blk.gb, Tn, 2 * td);
     GSV_HIP(hipGetLastError());
     ConvOpt orr; orr.res = ta;
-    GSV_RC(conv(h, s, blk.pw2, tw, 2 * td, R, ta, R, orr));
+    GSV_RC(conv(h, s, blk.pw2, tw, 2 * td, RT, ta, RT, orr));
   }
   {
     const int W = md + (ldin - (2 * md + td));
-    CFM_LAUNCH_ROWS(cfm_cond_kernel<T>, (long long)Tn * W, B, rw, Tn, md, (T*)xin, ldin, md, 2 * md + td);
-    hipLaunchKernelGGL((cfm_copy_cols_kernel<T>), dim3(nblk((long long)R * td)), dim3(256), 0, s, (const T*)ta, td, R, td, (T*)xin,
+    CFM_LAUNCH_ROWS(cfm_cond_kernel<T>, (long long)Tn * W, DB, rw, Tn, md, (T*)xin, ldin, md, 2 * md + td);
+    hipLaunchKernelGGL((cfm_copy_cols_kernel<T>), dim3(nblk((long long)RX * td)), dim3(256), 0, s, (const T*)ta, td, RX, td, (T*)xin,
                        ldin, 2 * md);
     GSV_HIP(hipGetLastError());
+    if (guided)   // text row B of ta is the null text embedding: into the text columns of the B twins
+      CFM_LAUNCH_ROWS(cfm_bcast_cols_kernel<T>, (long long)Tn * td, B, (const T*)rows(ta, B, td), Tn, td, (T*)rows(xin, B, ldin), ldin,
+                      2 * md);
   }
   CFM_LAUNCH(cfm_rope_table_kernel, Tn * half, Tn, half, cs);
   CFM_LAUNCH_ROWS(cfm_init_x_kernel, (long long)Tn * md, B, noise, rw, temperature, Tn, md, x);
-  CFM_LAUNCH(cfm_euler_kernel<T>, (long long)R * md, x, (const float*)nullptr, 0.f, R, Tn, rw, md, (T*)xin, ldin);
+  // x -> the x columns of the DiT input (v null: no update yet), and after every step the Euler update
+  auto euler = [&](const float* vv, float dd) -> int {
+    if (guided) CFM_LAUNCH(cfm_euler_cfg_kernel<T>, (long long)RX * md, x, vv, dd, cfg_rate, RX, Tn, rw, md, (T*)xin, ldin);
+    else CFM_LAUNCH(cfm_euler_kernel<T>, (long long)RX * md, x, vv, dd, RX, Tn, rw, md, (T*)xin, ldin);
+    return GSV_OK;
+  };
+  GSV_RC(euler(nullptr, 0.f));
 
   const float d = (float)(1.0 / N);
   const float att_scale = 1.f / sqrtf((float)g.dim_head);
@@ -425,12 +492,12 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
   const int resident = per_block ? (int)std::min<size_t>((size_t)g.depth, (size_t)resident_mb * 1024 * 1024 / per_block) : g.depth;
   void* vtb = nullptr;
   const long long vtz = (long long)g.heads * 64 * ((Tn + 31) / 32 * 32);   // one V^T buffer per utterance
-  if (flash) GSV_RC(need(h, "cfm_vt", (size_t)B * vtz * 2, &vtb));
+  if (flash) GSV_RC(need(h, "cfm_vt", (size_t)DB * vtz * 2, &vtb));
   for (int step = 0; step < N; ++step) {
     // ---- InputEmbedding (dit.py:75-84): proj(cat(x, cond, text)) then + ConvPositionEmbedding
     ConvOpt o;
     GSV_RC(conv(h, s, c->in_proj, xin, ldin, R, hb, R, o));
-    for (int b = 0; b < B; ++b) {
+    for (int b = 0; b < DB; ++b) {
       ConvArgs a;
       const int cg = D / 16;
       a.x = rows(hb, b, D); a.w = c->pos1.w; a.bias = c->pos1.b; a.y = rows(c1, b, D);
@@ -452,7 +519,7 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
       // comes back as a heavier epilogue of the V column tiles on a grid that fills 75 % of the CUs), so the separate launch,
       // which the parity tests cover at every shape, stays the default
       static const bool want_fuse = getenv("GSV_CFM_QKV_FUSE") != nullptr;
-      const bool fuse_qkv = flash && B == 1 && R >= 512 && want_fuse && (2 * inner) % 128 == 0;
+      const bool fuse_qkv = flash && DB == 1 && R >= 512 && want_fuse && (2 * inner) % 128 == 0;
       {
         ConvOpt oq; oq.w_nt = wnt;
         if (fuse_qkv) {
@@ -465,9 +532,9 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
       if (flash) {   // every utterance in the same two launches (V^T + rotary, attention): the row is a grid dimension
         const _Float16* qb = (const _Float16*)qkv;
         GSV_RC(launch_flash_attn64_f16_rows(qb, 3 * inner, qb + inner, 3 * inner, qb + 2 * inner, 3 * inner, vtb, Tn, g.heads, att_scale,
-                                            ao, inner, s, cs, half, fuse_qkv, B, (long long)Tn * 3 * inner, vtz, (long long)Tn * inner));
+                                            ao, inner, s, cs, half, fuse_qkv, DB, (long long)Tn * 3 * inner, vtz, (long long)Tn * inner));
       } else {
-        for (int b = 0; b < B; ++b) {
+        for (int b = 0; b < DB; ++b) {
           const T* qb = (const T*)rows(qkv, b, 3 * inner);
           GSV_RC(attention(h, s, qb, 3 * inner, 0, qb, 3 * inner, inner, 2 * inner, Tn, Tn, g.heads, g.dim_head, att_scale, nullptr,
                            nullptr, rows(ao, b, inner), inner));
@@ -486,21 +553,33 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
     GSV_RC(launch_ln_mod<T>(hb, mf, mf + D, R, D, nrm, s));
     ConvOpt ov; ov.out_f32 = 1;
     GSV_RC(conv(h, s, c->proj_out, nrm, D, R, v, R, ov));
-    CFM_LAUNCH(cfm_euler_kernel<T>, (long long)R * md, x, (const float*)v, d, R, Tn, rw, md, (T*)xin, ldin);
+    GSV_RC(euler(v, d));
   }
   CFM_LAUNCH_ROWS(cfm_out_kernel, (long long)Tn * md, B, x, rw, Tn, md, out);
   return GSV_OK;
 }
 
 int cfm_run(gsv_cfm* c, hipStream_t s, const float* mu, const std::vector<CfmRow>& rows, int T, int N, const float* noise,
-            float temperature, float* out) {
+            float temperature, float cfg_rate, float* out) {
   float* mods = nullptr;
   if (c->ctx.dtype == GSV_F16) {
     GSV_RC(cfm_modulations<_Float16>(c, s, N, &mods));
-    return cfm_infer_batch<_Float16>(c, s, mods, mu, rows, T, N, noise, temperature, out);
+    return cfm_infer_batch<_Float16>(c, s, mods, mu, rows, T, N, noise, temperature, cfg_rate, out);
   }
   GSV_RC(cfm_modulations<float>(c, s, N, &mods));
-  return cfm_infer_batch<float>(c, s, mods, mu, rows, T, N, noise, temperature, out);
+  return cfm_infer_batch<float>(c, s, mods, mu, rows, T, N, noise, temperature, cfg_rate, out);
+}
+
+// the row table of the two rows-form entries, checked before anything is launched
+int cfm_row_table(gsv_cfm* c, const char* who, const float* const* prompts, const int* Tp, int B, int T, const uint64_t* seeds,
+                  std::vector<CfmRow>* rows) {
+  rows->resize(B);
+  for (int b = 0; b < B; ++b) {
+    GSV_REQUIRE(Tp[b] >= 0 && Tp[b] <= T && (Tp[b] == 0 || (prompts && prompts[b])),
+                "%s: row %d: prompt length %d does not fit %d frames, or its prompt is null", who, b, Tp[b], T);
+    (*rows)[b] = CfmRow{Tp[b] ? prompts[b] : nullptr, seeds ? (unsigned long long)seeds[b] : 0ull, Tp[b], 0};
+  }
+  return GSV_OK;
 }
 
 }  // namespace
@@ -605,7 +684,7 @@ int gsv_cfm_inference(gsv_cfm_t* c, const float* mu, const float* prompt, int B,
   std::vector<CfmRow> rows(B);
   for (int b = 0; b < B; ++b)
     rows[b] = CfmRow{Tp ? prompt + (size_t)b * c->cfg.mel_dim * Tp : nullptr, seed + 0x9E3779B97F4A7C15ull * (unsigned long long)b, Tp, 0};
-  return cfm_run(c, (hipStream_t)stream, mu, rows, T, n_steps, noise, temperature, out);
+  return cfm_run(c, (hipStream_t)stream, mu, rows, T, n_steps, noise, temperature, 0.f, out);
 }
 
 int gsv_cfm_inference_rows(gsv_cfm_t* c, const float* mu, const float* const* prompts, const int* Tp, int B, int T, int n_steps,
@@ -614,13 +693,24 @@ int gsv_cfm_inference_rows(gsv_cfm_t* c, const float* mu, const float* const* pr
   GSV_REQUIRE(mu && out && Tp && B > 0 && T > 0 && n_steps > 0 && n_steps <= 1024, "cfm_inference_rows: bad argument");
   GSV_REQUIRE(B <= 65535, "cfm_inference_rows: %d rows exceed the grid's 65535", B);
   GSV_REQUIRE(noise || seeds, "cfm_inference_rows: neither noise nor seeds given");
-  std::vector<CfmRow> rows(B);
-  for (int b = 0; b < B; ++b) {
-    GSV_REQUIRE(Tp[b] >= 0 && Tp[b] <= T && (Tp[b] == 0 || (prompts && prompts[b])),
-                "cfm_inference_rows: row %d: prompt length %d does not fit %d frames, or its prompt is null", b, Tp[b], T);
-    rows[b] = CfmRow{Tp[b] ? prompts[b] : nullptr, seeds ? (unsigned long long)seeds[b] : 0ull, Tp[b], 0};
-  }
-  return cfm_run(c, (hipStream_t)stream, mu, rows, T, n_steps, noise, temperature, out);
+  std::vector<CfmRow> rows;
+  GSV_RC(cfm_row_table(c, "cfm_inference_rows", prompts, Tp, B, T, seeds, &rows));
+  return cfm_run(c, (hipStream_t)stream, mu, rows, T, n_steps, noise, temperature, 0.f, out);
+}
+
+int gsv_cfm_inference_guided(gsv_cfm_t* c, const float* mu, const float* const* prompts, const int* Tp, int B, int T, int n_steps,
+                             const float* noise, const uint64_t* seeds, float temperature, float cfg_rate, float* out,
+                             gsv_stream_t stream) {
+  GSV_REQUIRE(c && c->finalized, "cfm_inference_guided: handle not finalized");
+  GSV_REQUIRE(mu && out && Tp && B > 0 && T > 0 && n_steps > 0 && n_steps <= 1024, "cfm_inference_guided: bad argument");
+  GSV_REQUIRE(std::isfinite(cfg_rate), "cfm_inference_guided: cfg_rate is not finite");
+  const bool guided = cfg_rate > CFM_CFG_THRESHOLD;
+  GSV_REQUIRE(B <= (guided ? 65535 / 2 : 65535), "cfm_inference_guided: %d rows (%d with their unconditioned twins) exceed the grid's 65535",
+              B, guided ? 2 * B : B);
+  GSV_REQUIRE(noise || seeds, "cfm_inference_guided: neither noise nor seeds given");
+  std::vector<CfmRow> rows;
+  GSV_RC(cfm_row_table(c, "cfm_inference_guided", prompts, Tp, B, T, seeds, &rows));
+  return cfm_run(c, (hipStream_t)stream, mu, rows, T, n_steps, noise, temperature, cfg_rate, out);
 }
 
 }  // extern "C"

@@ -29,7 +29,7 @@ import torch
 import torch.nn.functional as F
 
 from ..AR.models.t2s_model import Text2SemanticDecoder
-from ..module.models import SynthesizerTrn, SynthesizerTrnV3
+from ..module.models import SynthesizerTrn, SynthesizerTrnV3, cfg_guided
 from ..process_ckpt import load_sovits_new  # noqa: F401  (reference process_ckpt.py:129-138; re-exported)
 
 
@@ -664,9 +664,11 @@ class TTS:
 
     @torch.no_grad()
     def using_vocoder_synthesis(self, semantic_tokens: torch.Tensor, phones: torch.Tensor, speed: float = 1.0,
-                                sample_steps: int = 32, seed: int = 0, noise_fn: Optional[Callable] = None) -> torch.Tensor:
+                                sample_steps: int = 32, seed: int = 0, noise_fn: Optional[Callable] = None,
+                                inference_cfg_rate: float = 0) -> torch.Tensor:
         """TTS.py:1431-1494: one fragment; the mel is generated chunk by chunk, each chunk prompted with the tail of the
-        previous one.  `noise_fn(call_index, shape)` (tests) pins the randn draw of each cfm.inference call."""
+        previous one.  `noise_fn(call_index, shape)` (tests) pins the randn draw of each cfm.inference call.
+        `inference_cfg_rate` is CFM.inference_guided's (the reference passes 0 here: CFM.inference)."""
         spec, fea_ref, ge, mel2, T_min = self._prompt_features()
         chunk_len = self.vocoder_configs["T_chunk"] - T_min
         fea_todo, ge = self.vits_model.decode_encp(semantic_tokens, phones, spec, ge, speed)
@@ -678,7 +680,8 @@ class TTS:
             pos += chunk_len
             fea = torch.cat([fea_ref, chunk], 2).transpose(2, 1)
             nz = noise_fn(call, (1, 100, fea.shape[1])) if noise_fn else None
-            res = self.vits_model.cfm.inference(fea, None, mel2, sample_steps, inference_cfg_rate=0, noise=nz, seed=seed + call)
+            res = self.vits_model.cfm.inference_guided(fea, None, mel2, sample_steps, inference_cfg_rate=inference_cfg_rate,
+                                                       noise=nz, seed=seed + call)
             res = res[:, :, mel2.shape[2]:]
             call += 1
             mel2 = res[:, :, -T_min:]
@@ -689,14 +692,16 @@ class TTS:
     @torch.no_grad()
     def using_vocoder_synthesis_batched_infer(self, idx_list: List[int], semantic_tokens_list: List[torch.Tensor],
                                               batch_phones: List[torch.Tensor], speed: float = 1.0, sample_steps: int = 32,
-                                              seed: int = 0, noise_fn: Optional[Callable] = None) -> List[torch.Tensor]:
+                                              seed: int = 0, noise_fn: Optional[Callable] = None,
+                                              inference_cfg_rate: float = 0) -> List[torch.Tensor]:
         """TTS.py:1496-1609: all fragments of a batch concatenated, cut into overlapping chunks that go through ONE
         batched cfm.inference, vocoded as one sequence, re-joined with SOLA and split back per fragment."""
         prompt = self._prompt_features()
         fea, lens, pad_len = self._fold_chunks(prompt, idx_list, semantic_tokens_list, batch_phones, speed)
         mel2 = prompt[3]
         nz = noise_fn(0, (fea.shape[0], 100, fea.shape[1])) if noise_fn else None
-        pred = self.vits_model.cfm.inference(fea, None, mel2, sample_steps, inference_cfg_rate=0, noise=nz, seed=seed)
+        pred = self.vits_model.cfm.inference_guided(fea, None, mel2, sample_steps, inference_cfg_rate=inference_cfg_rate, noise=nz,
+                                                    seed=seed)
         return self._fold_audio(pred[:, :, mel2.shape[2]:], lens, pad_len)
 
     @staticmethod
@@ -841,21 +846,24 @@ class TTS:
 
     def _synthesize_batch(self, item: dict, pred: List[torch.Tensor], pred_list: List[torch.Tensor], idx_list: List[int],
                           seed_b: int, bi: int, actual_seed: int, speed_factor: float, parallel_infer: bool, sample_steps: int,
-                          refer: List[torch.Tensor], sv_kw: dict, up: int) -> List[torch.Tensor]:
+                          refer: List[torch.Tensor], sv_kw: dict, up: int, inference_cfg_rate: float = 0) -> List[torch.Tensor]:
         """run()'s post-AR stage of one to_batch batch `bi` (reference TTS.py:1259-1299): the fragments of its sentences from
-        the generated tokens `pred`, with the voice of self.prompt_cache (v3/v4) / `refer` + `sv_kw` (v1/v2/v2Pro)"""
+        the generated tokens `pred`, with the voice of self.prompt_cache (v3/v4) / `refer` + `sv_kw` (v1/v2/v2Pro);
+        `inference_cfg_rate` guides the v3/v4 flow-matching stage and is ignored by v1/v2/v2Pro"""
         frags: List[torch.Tensor] = []
         if self.configs.use_vocoder:
             # TTS.py:1283-1299
             dev_ph = [ph.to(self.configs.device) for ph in item["phones"]]
             if parallel_infer:
                 frags = self.using_vocoder_synthesis_batched_infer(idx_list, pred_list, dev_ph, speed=speed_factor,
-                                                                   sample_steps=sample_steps, seed=seed_b)
+                                                                   sample_steps=sample_steps, seed=seed_b,
+                                                                   inference_cfg_rate=inference_cfg_rate)
             else:
                 for k, idx in enumerate(idx_list):
                     frags.append(self.using_vocoder_synthesis(pred_list[k][-idx:].view(1, 1, -1), dev_ph[k].view(1, -1),
                                                               speed=speed_factor, sample_steps=sample_steps,
-                                                              seed=actual_seed + bi * 4096 + k))
+                                                              seed=actual_seed + bi * 4096 + k,
+                                                              inference_cfg_rate=inference_cfg_rate))
         elif speed_factor == 1.0:
             # one decode over the batch folded into the time axis (TTS.py:1259-1282)
             ends = np.cumsum([0] + [int(p.shape[0]) * 2 * up for p in pred])
@@ -953,7 +961,8 @@ class TTS:
                  batch_size=req.get("batch_size", 1), batch_threshold=req.get("batch_threshold", 0.75),
                  speed_factor=req.get("speed_factor", 1.0), split_bucket=req.get("split_bucket", True),
                  fragment_interval=req.get("fragment_interval", 0.3), parallel_infer=req.get("parallel_infer", True),
-                 repetition_penalty=req.get("repetition_penalty", 1.35), sample_steps=req.get("sample_steps", 32))
+                 repetition_penalty=req.get("repetition_penalty", 1.35), sample_steps=req.get("sample_steps", 32),
+                 inference_cfg_rate=req.get("inference_cfg_rate", 0))
         seed = req.get("seed", -1)
         o["seed"] = -1 if seed in ["", None] else seed
         if o["fragment_interval"] < 0.01:
@@ -1041,12 +1050,14 @@ class TTS:
         sentences of to_batch batch bi (0 when nothing was generated).  Shared: v3 / v4 folds of parallel_infer requests with
         at least one frame, at any speed.  A fold is cut into rows as using_vocoder_synthesis_batched_infer cuts it
         (_chunk_cuts with the voice's chunk_len = T_chunk - T_min); every row is T_chunk frames whatever its voice.  Folds
-        are grouped by sample_steps, and a group's rows fill passes of at most cfm_max_rows rows in (r, bi, k) order, so a
-        fold may span two passes.  Returns the passes, lists of (r, bi, k)."""
+        are grouped by sample_steps and guidance rate (every inference_cfg_rate <= 1e-5 is the one unguided group), and a
+        group's rows fill passes of at most cfm_max_rows rows in (r, bi, k) order, so a fold may span two passes.  A guided
+        row brings its unconditioned twin into the pass: a guided pass takes at most cfm_max_rows // 2 rows, so no pass runs
+        the DiT over more than cfm_max_rows rows.  Returns the passes, lists of (r, bi, k)."""
         if not getattr(self.configs, "use_vocoder", False):
             return []
         vc = self.vocoder_configs
-        groups: Dict[int, List[Tuple[int, int, int]]] = {}
+        groups: Dict[Tuple[int, float], List[Tuple[int, int, int]]] = {}
         for r, pl in enumerate(plans):
             o = pl["opts"]
             if not o["parallel_infer"]:
@@ -1055,9 +1066,11 @@ class TTS:
                 if frames <= 0:
                     continue
                 n = len(self._chunk_cuts(int(frames), vc["T_chunk"] - int(pl["T_min"]), vc["overlapped_len"]))
-                groups.setdefault(int(o["sample_steps"]), []).extend((r, bi, k) for k in range(n))
-        cap = max(1, int(self.cfm_max_rows))
-        return [rows[i:i + cap] for rows in groups.values() for i in range(0, len(rows), cap)]
+                rate = o.get("inference_cfg_rate", 0)
+                g = (int(o["sample_steps"]), float(rate) if cfg_guided(rate) else 0.0)
+                groups.setdefault(g, []).extend((r, bi, k) for k in range(n))
+        caps = {g: max(1, int(self.cfm_max_rows) // (2 if g[1] else 1)) for g in groups}
+        return [rows[i:i + caps[g]] for g, rows in groups.items() for i in range(0, len(rows), caps[g])]
 
     @torch.no_grad()
     def run_batch(self, requests: List[dict], shared_sovits: bool = False, shared_cfm: bool = False) -> List[Tuple[int, np.ndarray]]:
@@ -1068,7 +1081,8 @@ class TTS:
         shared_sovits=True: the waveform stage of v1 / v2 / v2Pro / v2ProPlus requests at speed 1 runs as shared segmented
         passes over all voices (plan_sovits, SynthesizerTrn.decode_segments) instead of one decode per to_batch batch.
         shared_cfm=True: the flow-matching stage of v3 / v4 parallel_infer requests runs as shared passes over all voices'
-        chunks (plan_cfm, CFM.inference_rows), every row with its own voice's prompt mel and the noise key run() gives it;
+        chunks (plan_cfm, CFM.inference_rows), every row with its own voice's prompt mel and the noise key run() gives it,
+        guided requests (key "inference_cfg_rate" > 1e-5) in passes of their own rate;
         vocoder and SOLA stay per fold.  Neither keyword changes anything for the other model family."""
         if self.t2s_model is None or self.vits_model is None:
             raise RuntimeError("init_t2s_weights / init_vits_weights first")
@@ -1181,7 +1195,9 @@ class TTS:
                 mu = torch.cat([fold_in[(r, bi)][0][k:k + 1] for r, bi, k in rows], 0)
                 mels = [prompts[plans[r]["cfm_voice"]][3] for r, _, _ in rows]
                 seeds = [(plans[r]["actual_seed"] + bi + 0x9E3779B97F4A7C15 * k) & 0xFFFFFFFFFFFFFFFF for r, bi, k in rows]
-                pred = self.vits_model.cfm.inference_rows(mu, mels, plans[rows[0][0]]["opts"]["sample_steps"], seeds=seeds)
+                o = plans[rows[0][0]]["opts"]           # a pass is of one (sample_steps, guidance rate) group
+                pred = self.vits_model.cfm.inference_rows(mu, mels, o["sample_steps"], seeds=seeds,
+                                                          inference_cfg_rate=o["inference_cfg_rate"])
                 for n, (r, bi, k) in enumerate(rows):
                     fold_out.setdefault((r, bi), []).append(pred[n:n + 1, :, mels[n].shape[2]:])
             for (r, bi), got in fold_out.items():        # a fold is finished when all its rows are back
@@ -1207,7 +1223,7 @@ class TTS:
                     pred, idx_list = kept(r, bi)
                     audio.append(self._synthesize_batch(item, pred, pred_list, idx_list, pl["actual_seed"] + bi, bi,
                                                         pl["actual_seed"], o["speed_factor"], o["parallel_infer"],
-                                                        o["sample_steps"], refer, sv_kw, up))
+                                                        o["sample_steps"], refer, sv_kw, up, o["inference_cfg_rate"]))
                 torch.cuda.current_stream(self.configs.device).synchronize()
                 results.append(self.audio_postprocess(audio, sr, pl["index"], o["speed_factor"], o["split_bucket"],
                                                       o["fragment_interval"], pl["super_sampling"]))
@@ -1299,7 +1315,8 @@ class TTS:
                     pred = [p[-i:] if i > 0 else p[:0] for p, i in zip(pred_list, idx_list)]
                 self.last_generated_tokens += int(sum(idx_list))
                 frags = self._synthesize_batch(item, pred, pred_list, idx_list, actual_seed + bi, bi, actual_seed, speed_factor,
-                                               parallel_infer, inputs.get("sample_steps", 32), refer, sv_kw, up)
+                                               parallel_infer, inputs.get("sample_steps", 32), refer, sv_kw, up,
+                                               inputs.get("inference_cfg_rate", 0))
                 # stream-level wait only: the engine calls above already synchronised their own streams, and a DEVICE-wide
                 # synchronize intermittently stalls 20-30 ms on this ROCm build
                 torch.cuda.current_stream(self.configs.device).synchronize()

@@ -119,6 +119,9 @@ _SIGS = {
                                     C.c_float, C.c_uint64, C.c_void_p, C.c_void_p]),
     "gsv_cfm_inference_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int,
                                          C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.c_float, C.c_void_p, C.c_void_p]),
+    "gsv_cfm_inference_guided": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int,
+                                           C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.c_float, C.c_float, C.c_void_p,
+                                           C.c_void_p]),
     "gsv_sola": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "gsv_postprocess": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "gsv_postprocess_f32": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_void_p,

@@ -345,13 +345,26 @@ class Generator:
         return self._e(x)
 
 
+def cfg_guided(rate) -> bool:
+    """Is classifier-free guidance active at this rate?  The reference's test `rate > 1e-5` (models.py:1063), taken in fp32
+    as the engine takes it (`cfg_rate > 1e-5f` on the float that crosses the C ABI), so the host mirror, the pass planner and
+    the engine agree on every rate.  False for NaN."""
+    return C.c_float(rate).value > C.c_float(1e-5).value
+
+
 class CFM:
     """Mirror of the reference's `CFM` (module/models.py:1013-1085): `inference` integrates the flow-matching ODE with
     `n_timesteps` Euler steps over the `DiT` estimator, entirely inside the HIP library (`gsv_cfm_inference`).
 
     `noise` (not in the reference signature) pins the `torch.randn` draw of models.py:1030 for parity tests; left
     None, the draw happens on the device from `seed`.
+
+    Classifier-free guidance (`inference_cfg_rate` > 1e-5, the reference's test, models.py:1063) is `inference_guided` /
+    `inference_rows(..., inference_cfg_rate=r)`: every row gets an unconditioned twin in the same DiT pass
+    (`gsv_cfm_inference_guided`).  `inference` is the unguided entry and refuses a positive rate; `inference_guided` is the
+    guided one.
     """
+    GOLDEN = 0x9E3779B97F4A7C15     # row b of `inference(seed=s)` draws with the key s + GOLDEN * b
 
     def __init__(self, in_channels, dit):
         self.in_channels = in_channels
@@ -362,8 +375,9 @@ class CFM:
     def inference(self, mu, x_lens, prompt, n_timesteps, temperature=1.0, inference_cfg_rate=0, noise=None, seed=0):
         """mu [B, T, text_dim]; x_lens unused (as in the reference); prompt [B, in_channels, Tp] -> [B, in_channels, T]"""
         if inference_cfg_rate > 1e-5:
-            raise NotImplementedError("classifier-free guidance: every caller in the reference passes inference_cfg_rate=0 "
-                                      "(TTS.py:1351, inference_webui.py:937)")
+            raise NotImplementedError("CFM.inference is the unguided entry (every caller in the reference passes "
+                                      "inference_cfg_rate=0, TTS.py:1351, inference_webui.py:937); classifier-free guidance "
+                                      "is CFM.inference_guided")
         dit = self.estimator
         if not dit._loaded:
             raise RuntimeError("DiT.load_state_dict() first")
@@ -391,11 +405,28 @@ class CFM:
         return out.to(mu.dtype if mu.dtype in (torch.float16, torch.float32) else torch.float32)
 
     @torch.no_grad()
-    def inference_rows(self, mu, prompts, n_timesteps, temperature=1.0, noise=None, seeds=None):
+    def inference_guided(self, mu, x_lens, prompt, n_timesteps, temperature=1.0, inference_cfg_rate=0, noise=None, seed=0):
+        """The reference's `CFM.inference(..., inference_cfg_rate=r)` with classifier-free guidance (models.py:1063-1081);
+        arguments as `inference`.  r > 1e-5: the rows entry with uniform prompts and seeds[b] = seed + GOLDEN * b, so the
+        noise is the unguided call's.  r <= 1e-5 (zero and negative rates included) is `inference` itself."""
+        if not math.isfinite(inference_cfg_rate):
+            raise ValueError(f"inference_cfg_rate must be finite, got {inference_cfg_rate}")
+        if not cfg_guided(inference_cfg_rate):
+            return self.inference(mu, x_lens, prompt, n_timesteps, temperature=temperature, noise=noise, seed=seed)
+        B = int(mu.shape[0]) if mu.dim() == 3 else 0
+        if prompt.dim() != 3 or prompt.shape[0] not in (1, B):
+            raise ValueError(f"expected prompt of shape [{B} or 1, {self.in_channels}, Tp], got {tuple(prompt.shape)}")
+        seeds = [(int(seed) + self.GOLDEN * b) & 0xFFFFFFFFFFFFFFFF for b in range(B)]
+        return self.inference_rows(mu, [prompt[b:b + 1] if prompt.shape[0] == B else prompt for b in range(B)], n_timesteps,
+                                   temperature=temperature, noise=noise, seeds=seeds, inference_cfg_rate=inference_cfg_rate)
+
+    @torch.no_grad()
+    def inference_rows(self, mu, prompts, n_timesteps, temperature=1.0, noise=None, seeds=None, inference_cfg_rate=0):
         """`inference` for B rows that each have their own prompt (`gsv_cfm_inference_rows`): mu [B, T, text_dim]; prompts a
         list of B tensors [1, in_channels, Tp_b], 0 <= Tp_b <= T -> [B, in_channels, T], row b's first Tp_b frames zero.
         `seeds` (B ints) are the rows' own noise keys, taken as they are: row b of `inference(seed=s)` is seeds[b] =
-        s + 0x9E3779B97F4A7C15 * b here.  `noise` [B, in_channels, T] pins the draw instead."""
+        s + 0x9E3779B97F4A7C15 * b here.  `noise` [B, in_channels, T] pins the draw instead.  `inference_cfg_rate` > 1e-5
+        guides every row with that rate (`gsv_cfm_inference_guided`, 2 B DiT rows); the noise of a row does not depend on it."""
         dit = self.estimator
         if not dit._loaded:
             raise RuntimeError("DiT.load_state_dict() first")
@@ -407,6 +438,8 @@ class CFM:
         for b, p in enumerate(prompts):
             if p.dim() != 3 or p.shape[0] != 1 or p.shape[1] != self.in_channels or p.shape[2] > T:
                 raise ValueError(f"expected prompt {b} of shape [1, {self.in_channels}, Tp<={T}], got {tuple(p.shape)}")
+        if not math.isfinite(inference_cfg_rate):
+            raise ValueError(f"inference_cfg_rate must be finite, got {inference_cfg_rate}")
         if noise is None and seeds is None:
             raise ValueError("inference_rows needs `noise` or `seeds`")
         if noise is not None and tuple(noise.shape) != (B, self.in_channels, T):
@@ -423,9 +456,15 @@ class CFM:
             tps = (C.c_int * B)(*[int(p.shape[2]) for p in ps])
             sd = (C.c_uint64 * B)(*[int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds]) if seeds is not None else None
             dit.stream.wait_stream(torch.cuda.current_stream(dev))
-            _lib.check(_lib.lib().gsv_cfm_inference_rows(dit._h, m.data_ptr(), ptrs, tps, B, T, int(n_timesteps),
-                                                         nz.data_ptr() if nz is not None else None, sd, float(temperature),
-                                                         out.data_ptr(), C.c_void_p(dit.stream.cuda_stream)),
-                       "gsv_cfm_inference_rows")
+            if cfg_guided(inference_cfg_rate):
+                _lib.check(_lib.lib().gsv_cfm_inference_guided(dit._h, m.data_ptr(), ptrs, tps, B, T, int(n_timesteps),
+                                                               nz.data_ptr() if nz is not None else None, sd, float(temperature),
+                                                               float(inference_cfg_rate), out.data_ptr(),
+                                                               C.c_void_p(dit.stream.cuda_stream)), "gsv_cfm_inference_guided")
+            else:
+                _lib.check(_lib.lib().gsv_cfm_inference_rows(dit._h, m.data_ptr(), ptrs, tps, B, T, int(n_timesteps),
+                                                             nz.data_ptr() if nz is not None else None, sd, float(temperature),
+                                                             out.data_ptr(), C.c_void_p(dit.stream.cuda_stream)),
+                           "gsv_cfm_inference_rows")
             dit.stream.synchronize()
         return out.to(mu.dtype if mu.dtype in (torch.float16, torch.float32) else torch.float32)

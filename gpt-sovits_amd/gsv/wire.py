@@ -126,7 +126,8 @@ def create_app(tts_pipeline):
         for k in ("top_k", "batch_size", "seed", "sample_steps"):
             if k in q:
                 q[k] = int(q[k])
-        for k in ("top_p", "temperature", "batch_threshold", "speed_factor", "fragment_interval", "repetition_penalty"):
+        for k in ("top_p", "temperature", "batch_threshold", "speed_factor", "fragment_interval", "repetition_penalty",
+                  "inference_cfg_rate"):
             if k in q:
                 q[k] = float(q[k])
         for k in ("split_bucket", "streaming_mode", "parallel_infer", "super_sampling"):

@@ -246,8 +246,9 @@ int gsv_vocoder_finalize(gsv_vocoder_t* h);
 int gsv_vocoder_forward(gsv_vocoder_t* h, const float* mel, int F, float* wav, gsv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
- * v3 / v4 flow-matching mel decoder (H14): CFM.inference (module/models.py:1027-1085, inference_cfg_rate = 0 as
- * every caller in the reference passes it) over the DiT estimator (f5_tts/model/backbones/dit.py:88-194).
+ * v3 / v4 flow-matching mel decoder (H14): CFM.inference (module/models.py:1027-1085) over the DiT estimator
+ * (f5_tts/model/backbones/dit.py:88-194).  gsv_cfm_inference and gsv_cfm_inference_rows are inference_cfg_rate = 0, as
+ * every caller in the reference passes it; gsv_cfm_inference_guided takes the rate (classifier-free guidance).
  * Tensor names = the DiT state-dict keys (the part after "cfm.estimator." in a v3/v4 SoVITS checkpoint).
  * The rotary embedding follows x_transformers' published definition (un-vendored dependency: parity unpinned).
  * ------------------------------------------------------------------------------------- */
@@ -276,6 +277,14 @@ int gsv_cfm_inference(gsv_cfm_t* h, const float* mu, const float* prompt, int B,
 int gsv_cfm_inference_rows(gsv_cfm_t* h, const float* mu, const float* const* prompts, const int* Tp, int B, int T,
                            int n_steps, const float* noise, const uint64_t* seeds, float temperature, float* out,
                            gsv_stream_t stream);
+/* gsv_cfm_inference_rows with classifier-free guidance (models.py:1063-1081): arguments, noise keys and output as there.
+ * cfg_rate > 1e-5 (the reference's own test) runs every row twice per Euler step inside ONE DiT pass over 2 B rows -- as
+ * given, and with the prompt columns and the text zeroed (the text before its positional table and ConvNeXt stack) -- and
+ * steps with v + (v - v_uncond) * cfg_rate.  cfg_rate <= 1e-5, negative rates included, is gsv_cfm_inference_rows itself.
+ * cfg_rate must be finite and 2 * B <= 65535 when guided; both are checked before anything is launched. */
+int gsv_cfm_inference_guided(gsv_cfm_t* h, const float* mu, const float* const* prompts, const int* Tp, int B, int T,
+                             int n_steps, const float* noise, const uint64_t* seeds, float temperature, float cfg_rate,
+                             float* out, gsv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * SOLA stitching of the chunked v3/v4 vocoder output (H17, TTS.sola_algorithm, TTS_infer_pack/TTS.py:1611-1637).

@@ -30,6 +30,8 @@ def main():
     ap.add_argument("--fp32", action="store_true")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1, help="chunks per call (the batched caller passes 4-8)")
+    ap.add_argument("--cfg-rate", type=float, default=0.0,
+                    help="classifier-free guidance rate; > 1e-5 runs every chunk with its unconditioned twin (2 x batch DiT rows)")
     a = ap.parse_args()
     from gsv.f5_tts.model.backbones.dit import DiT
     from gsv.module.models import CFM
@@ -42,17 +44,18 @@ def main():
     cfm = CFM(100, dit)
     mu = S.hash_symmetric("bench_mu", (a.batch, a.frames, cfg["text_dim"]), 1.0, 1).cuda()
     prompt = S.hash_symmetric("bench_prompt", (1, 100, a.prompt), 1.0, 1).cuda()
-    cfm.inference(mu, None, prompt, 2, seed=1)
+    cfm.inference_guided(mu, None, prompt, 2, seed=1, inference_cfg_rate=a.cfg_rate)
     torch.cuda.synchronize()
     best = 1e9
     for _ in range(a.reps):
         t0 = time.perf_counter()
-        out = cfm.inference(mu, None, prompt, a.steps, seed=1)
+        out = cfm.inference_guided(mu, None, prompt, a.steps, seed=1, inference_cfg_rate=a.cfg_rate)
         torch.cuda.synchronize()
         best = min(best, time.perf_counter() - t0)
-    fl = flops_per_step(cfg, a.frames) * a.batch
+    dit_rows = a.batch * (2 if a.cfg_rate > 1e-5 else 1)
+    fl = flops_per_step(cfg, a.frames) * dit_rows
     print(json.dumps({"what": "cfm_inference", "dtype": "f32" if a.fp32 else "f16", "frames": a.frames, "prompt": a.prompt,
-                      "depth": a.depth, "batch": a.batch, "steps": a.steps, "ms_total": best * 1e3, "ms_per_step": best * 1e3 / a.steps,
+                      "depth": a.depth, "batch": a.batch, "cfg_rate": a.cfg_rate, "dit_rows": dit_rows, "steps": a.steps, "ms_total": best * 1e3, "ms_per_step": best * 1e3 / a.steps,
                       "gflop_per_step": fl / 1e9, "tflops": fl * a.steps / best / 1e12,
                       "finite": bool(torch.isfinite(out).all())}))
 

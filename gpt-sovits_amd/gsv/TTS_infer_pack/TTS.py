@@ -29,7 +29,7 @@ import torch
 import torch.nn.functional as F
 
 from ..AR.models.t2s_model import Text2SemanticDecoder
-from ..module.models import SynthesizerTrn, SynthesizerTrnV3, cfg_guided
+from ..module.models import CFM, SynthesizerTrn, SynthesizerTrnV3, cfg_guided
 from ..process_ckpt import load_sovits_new  # noqa: F401  (reference process_ckpt.py:129-138; re-exported)
 
 
@@ -71,6 +71,16 @@ def set_seed(seed: int) -> int:
     np.random.seed(seed)
     torch.manual_seed(seed)
     return seed
+
+
+def silence() -> Tuple[int, np.ndarray]:
+    """what run() / run_batch return for no text, a stop and an error (reference TTS.py:1132, 1334, 1340, 1355): 1 s at 16 kHz"""
+    return 16000, np.zeros(16000, dtype=np.int16)
+
+
+def early_stop_num(configs) -> float:
+    """the AR decode horizon in tokens (reference TTS.py:1224): hz * max_sec of the AR checkpoint, 54 s where it names none"""
+    return configs.hz * (configs.max_sec if configs.max_sec is not None else 54)
 
 
 class TTS_Config:
@@ -628,7 +638,6 @@ class TTS:
         from gsv.hostcopy import to_host
         return to_host(t)
 
-
     # ---- v3 / v4 synthesis (reference TTS.py:1431-1637) -----------------------------------------
     def _prompt_features(self):
         pc = self.prompt_cache
@@ -844,42 +853,51 @@ class TTS:
                 segments = self.text_preprocessor.preprocess(text, text_lang, method, self.configs.version)
         return segments
 
+    def _voice_refer(self, voice: dict) -> Tuple[List[torch.Tensor], dict]:
+        """the device reference of a voice or prompt-cache dict as SynthesizerTrn.decode takes it: (`refer`, the spectrograms
+        on the device; `sv_kw`, the speaker embeddings as a keyword for v2Pro / v2ProPlus and nothing for the others)"""
+        refer = [spec.to(device=self.configs.device) for spec, _ in voice["refer_spec"]]
+        return refer, ({"sv_emb": voice["sv_emb"]} if getattr(self.vits_model, "is_v2pro", False) else {})
+
+    @staticmethod
+    def _kept_tokens(pred_list: List[torch.Tensor], idx_list: List[int], no_prompt: bool) -> Tuple[List[torch.Tensor], List[int]]:
+        """The AR output of one to_batch batch without the prompts -> (`pred`, the generated tokens per sentence; the
+        `idx_list` the waveform stage takes).  Prompt-free, y holds only generated tokens and idx is reported as 0
+        (t2s_model.py:916-917): all are kept, idx_list becomes the lengths.  Else the last idx; 0 keeps none, not p[-0:]."""
+        if no_prompt:
+            pred = list(pred_list)
+            return pred, [int(p.shape[0]) for p in pred]
+        return [p[-i:] if i > 0 else p[:0] for p, i in zip(pred_list, idx_list)], idx_list
+
     def _synthesize_batch(self, item: dict, pred: List[torch.Tensor], pred_list: List[torch.Tensor], idx_list: List[int],
-                          seed_b: int, bi: int, actual_seed: int, speed_factor: float, parallel_infer: bool, sample_steps: int,
-                          refer: List[torch.Tensor], sv_kw: dict, up: int, inference_cfg_rate: float = 0) -> List[torch.Tensor]:
+                          bi: int, actual_seed: int, opts: dict, voice_refer: Tuple[List[torch.Tensor], dict]) -> List[torch.Tensor]:
         """run()'s post-AR stage of one to_batch batch `bi` (reference TTS.py:1259-1299): the fragments of its sentences from
-        the generated tokens `pred`, with the voice of self.prompt_cache (v3/v4) / `refer` + `sv_kw` (v1/v2/v2Pro);
-        `inference_cfg_rate` guides the v3/v4 flow-matching stage and is ignored by v1/v2/v2Pro"""
+        the generated tokens (`pred`, `idx_list` = _kept_tokens(`pred_list`, ...)), with the voice of self.prompt_cache
+        (v3/v4) / `voice_refer` = _voice_refer(voice) (v1/v2/v2Pro), speed_factor, parallel_infer, sample_steps and
+        inference_cfg_rate (v3/v4 only) of the resolved `opts`, and the seed actual_seed + bi."""
+        speed_factor, seed_b = opts["speed_factor"], actual_seed + bi
+        refer, sv_kw = voice_refer
         frags: List[torch.Tensor] = []
-        if self.configs.use_vocoder:
-            # TTS.py:1283-1299
+        if self.configs.use_vocoder:                                    # TTS.py:1283-1299
             dev_ph = [ph.to(self.configs.device) for ph in item["phones"]]
-            if parallel_infer:
-                frags = self.using_vocoder_synthesis_batched_infer(idx_list, pred_list, dev_ph, speed=speed_factor,
-                                                                   sample_steps=sample_steps, seed=seed_b,
-                                                                   inference_cfg_rate=inference_cfg_rate)
+            cfm_kw = dict(speed=speed_factor, sample_steps=opts["sample_steps"], inference_cfg_rate=opts["inference_cfg_rate"])
+            if opts["parallel_infer"]:
+                frags = self.using_vocoder_synthesis_batched_infer(idx_list, pred_list, dev_ph, seed=seed_b, **cfm_kw)
             else:
                 for k, idx in enumerate(idx_list):
                     frags.append(self.using_vocoder_synthesis(pred_list[k][-idx:].view(1, 1, -1), dev_ph[k].view(1, -1),
-                                                              speed=speed_factor, sample_steps=sample_steps,
-                                                              seed=actual_seed + bi * 4096 + k,
-                                                              inference_cfg_rate=inference_cfg_rate))
+                                                              seed=actual_seed + bi * 4096 + k, **cfm_kw))
         elif speed_factor == 1.0:
             # one decode over the batch folded into the time axis (TTS.py:1259-1282)
-            ends = np.cumsum([0] + [int(p.shape[0]) * 2 * up for p in pred])
+            cut = [int(p.shape[0]) * 2 * math.prod(self.vits_model.upsample_rates) for p in pred]
             keep = [k for k, p in enumerate(pred) if p.shape[0] > 0]
             if keep:
                 all_pred = torch.cat([pred[k] for k in keep]).view(1, 1, -1)
                 all_ph = torch.cat([item["phones"][k] for k in keep]).view(1, -1)
-                wav = self.vits_model.decode(all_pred, all_ph, refer, speed=speed_factor,
-                                             seed=seed_b, **sv_kw)[0, 0]
+                wav = self.vits_model.decode(all_pred, all_ph, refer, speed=speed_factor, seed=seed_b, **sv_kw)[0, 0]
             else:
                 wav = torch.zeros(0, dtype=self.precision, device=self.configs.device)
-            o = 0
-            for k, p in enumerate(pred):
-                nsm = int(p.shape[0]) * 2 * up
-                frags.append(wav[o:o + nsm])
-                o += nsm
+            frags = list(torch.split(wav, cut))        # decode gives exactly 2 * up samples per token at speed 1
         else:
             for k, p in enumerate(pred):
                 frags.append(self.vits_model.decode(p.view(1, 1, -1), item["phones"][k].view(1, -1), refer,
@@ -956,17 +974,30 @@ class TTS:
 
     @staticmethod
     def _request_options(req: dict) -> dict:
-        """run()'s per-request options, resolved exactly as run() resolves them"""
+        """The keys run() accepts with the reference's defaults (TTS.py:1026-1046): the only place a request key is read
+        with a default.  An empty seed is -1 (random) and fragment_interval is at least 0.01; `split_bucket` and
+        `super_sampling` are as given -- _resolve_options applies the rules that depend on the loaded model."""
         o = dict(top_k=req.get("top_k", 5), top_p=req.get("top_p", 1), temperature=req.get("temperature", 1),
                  batch_size=req.get("batch_size", 1), batch_threshold=req.get("batch_threshold", 0.75),
                  speed_factor=req.get("speed_factor", 1.0), split_bucket=req.get("split_bucket", True),
-                 fragment_interval=req.get("fragment_interval", 0.3), parallel_infer=req.get("parallel_infer", True),
-                 repetition_penalty=req.get("repetition_penalty", 1.35), sample_steps=req.get("sample_steps", 32),
-                 inference_cfg_rate=req.get("inference_cfg_rate", 0))
+                 return_fragment=req.get("return_fragment", False), fragment_interval=req.get("fragment_interval", 0.3),
+                 parallel_infer=req.get("parallel_infer", True), repetition_penalty=req.get("repetition_penalty", 1.35),
+                 sample_steps=req.get("sample_steps", 32), inference_cfg_rate=req.get("inference_cfg_rate", 0),
+                 super_sampling=bool(req.get("super_sampling", False)))
         seed = req.get("seed", -1)
         o["seed"] = -1 if seed in ["", None] else seed
         if o["fragment_interval"] < 0.01:
             o["fragment_interval"] = 0.01
+        return o
+
+    def _resolve_options(self, req: dict) -> dict:
+        """_request_options(req) under the rules of the loaded model, what run() and run_batch work from: fragments, another
+        speed and v3 / v4 parallel runs are never bucketed (reference TTS.py:1048-1062), and AP_BWE super-sampling applies to
+        the v3 vocoder output only -- v1 / v2 / v2Pro / v4 ignore the key (TTS.py:1040, 1328, 1349)."""
+        o = self._request_options(req)
+        if o["return_fragment"] or o["speed_factor"] != 1.0 or (self.configs.use_vocoder and o["parallel_infer"]):
+            o["split_bucket"] = False
+        o["super_sampling"] = o["super_sampling"] and self.configs.use_vocoder and self.configs.version == "v3"
         return o
 
     def plan_batch(self, plans: List[dict]) -> List[List[dict]]:
@@ -982,8 +1013,7 @@ class TTS:
             o = pl["opts"]
             naive = pl["no_prompt"] or not o["parallel_infer"]
             P = 0 if pl["no_prompt"] else int(pl["P"])
-            hz_max = self.configs.hz * (self.configs.max_sec if self.configs.max_sec is not None else 54)
-            wanted = min(1500, int(hz_max) + 1)
+            wanted = min(1500, int(early_stop_num(self.configs)) + 1)
             for bi, item in enumerate(pl["data"]):
                 lens = [int(t.shape[-1]) for t in item["all_phones"]]
                 for j, n in enumerate(lens):
@@ -1072,48 +1102,34 @@ class TTS:
         caps = {g: max(1, int(self.cfm_max_rows) // (2 if g[1] else 1)) for g in groups}
         return [rows[i:i + caps[g]] for g, rows in groups.items() for i in range(0, len(rows), caps[g])]
 
-    @torch.no_grad()
-    def run_batch(self, requests: List[dict], shared_sovits: bool = False, shared_cfm: bool = False) -> List[Tuple[int, np.ndarray]]:
-        """Several requests, each with its own reference voice, through shared AR decodes.  Each request dict takes the
-        keys run() accepts plus an optional "voice" (make_voice); without one it uses its ref_audio_path / prompt_text
-        (through make_voice's LRU) or the current prompt cache.  Returns one (sr, int16 audio) per request, in order: what
-        run(request) alone returns.  self.prompt_cache is not changed.  return_fragment is not supported.
-        shared_sovits=True: the waveform stage of v1 / v2 / v2Pro / v2ProPlus requests at speed 1 runs as shared segmented
-        passes over all voices (plan_sovits, SynthesizerTrn.decode_segments) instead of one decode per to_batch batch.
-        shared_cfm=True: the flow-matching stage of v3 / v4 parallel_infer requests runs as shared passes over all voices'
-        chunks (plan_cfm, CFM.inference_rows), every row with its own voice's prompt mel and the noise key run() gives it,
-        guided requests (key "inference_cfg_rate" > 1e-5) in passes of their own rate;
-        vocoder and SOLA stay per fold.  Neither keyword changes anything for the other model family."""
-        if self.t2s_model is None or self.vits_model is None:
-            raise RuntimeError("init_t2s_weights / init_vits_weights first")
-        self.stop_flag = False
-        plans = []
-        for req in requests:
-            if req.get("return_fragment", False):
-                raise ValueError("run_batch returns whole utterances: return_fragment=True is not supported")
-            o = self._request_options(req)
-            voice = self._request_voice(req)
-            if o["speed_factor"] != 1.0:
-                o["split_bucket"] = False
-            elif getattr(self.configs, "use_vocoder", False) and o["parallel_infer"]:
-                o["split_bucket"] = False
-            actual_seed = set_seed(o["seed"])
-            segments = self._segments(req)
-            no_prompt = voice["phones"] is None
-            if no_prompt and self.configs.use_vocoder:
-                raise NO_PROMPT_ERROR("v3/v4 need the prompt text (phones) of the reference audio")
-            prompt_data = None if no_prompt else {"phones": voice["phones"], "bert_features": voice["bert_features"]}
-            data, index = ([], []) if len(segments) == 0 else self.to_batch(
-                segments, prompt_data=prompt_data, batch_size=o["batch_size"], threshold=o["batch_threshold"],
-                split_bucket=o["split_bucket"], device=torch.device("cpu"), precision=self.precision)
-            plans.append(dict(voice=voice, opts=o, actual_seed=actual_seed, data=data, index=index, no_prompt=no_prompt,
-                              P=0 if no_prompt else int(voice["prompt_semantic"].numel()),
-                              super_sampling=bool(req.get("super_sampling", False)) and
-                              getattr(self.configs, "use_vocoder", False) and self.configs.version == "v3"))
-        # ---- AR: every sentence of every request, in shared launches
-        preds = [[[None] * len(item["all_phones"]) for item in pl["data"]] for pl in plans]
-        idxs = [[[None] * len(item["all_phones"]) for item in pl["data"]] for pl in plans]
-        max_sec = self.configs.max_sec if self.configs.max_sec is not None else 54
+    # ---- run_batch's stages: a plan is one request's dict, and a stage reads what the earlier ones wrote on it
+    def _plan_request(self, req: dict) -> dict:
+        """Stage 1, per request, what run() does before its AR loop.  Reads the request and seeds the host generators (after
+        the voice is resolved).  Writes the plan: `opts`, `voice`, `actual_seed`, `data` / `index` (to_batch), `no_prompt`,
+        `P` (prompt tokens) and `frags`, one slot per to_batch batch for its sentences' waveforms, filled by later stages."""
+        o = self._resolve_options(req)
+        if o["return_fragment"]:
+            raise ValueError("run_batch returns whole utterances: return_fragment=True is not supported")
+        voice = self._request_voice(req)
+        actual_seed = set_seed(o["seed"])
+        segments = self._segments(req)
+        no_prompt = voice["phones"] is None
+        if no_prompt and self.configs.use_vocoder:
+            raise NO_PROMPT_ERROR("v3/v4 need the prompt text (phones) of the reference audio")
+        prompt_data = None if no_prompt else {"phones": voice["phones"], "bert_features": voice["bert_features"]}
+        data, index = ([], []) if len(segments) == 0 else self.to_batch(
+            segments, prompt_data=prompt_data, batch_size=o["batch_size"], threshold=o["batch_threshold"],
+            split_bucket=o["split_bucket"], device=torch.device("cpu"), precision=self.precision)
+        return dict(voice=voice, opts=o, actual_seed=actual_seed, data=data, index=index, no_prompt=no_prompt,
+                    P=0 if no_prompt else int(voice["prompt_semantic"].numel()), frags=[None] * len(data))
+
+    def _ar_stage(self, plans: List[dict]) -> None:
+        """Stage 2: every sentence of every request through the shared AR launches of plan_batch.  Reads `data`, `opts`,
+        `voice`, `no_prompt`, `P`, `actual_seed`.  Writes run()'s pred_list / idx_list per batch: `preds[bi][j]`, the tokens
+        of sentence j (prompt included), `idxs[bi][j]`, how many were generated (0 prompt-free), `kept[bi]` = _kept_tokens."""
+        for pl in plans:
+            pl["preds"] = [[None] * len(item["all_phones"]) for item in pl["data"]]
+            pl["idxs"] = [[None] * len(item["all_phones"]) for item in pl["data"]]
         for rows in self.plan_batch(plans):
             o = plans[rows[0]["r"]]["opts"]
             no_prompt = rows[0]["group"][5]
@@ -1122,143 +1138,142 @@ class TTS:
             x = [it["all_phones"][e["j"]] for it, e in zip(items, rows)]
             bert = [it["all_bert_features"][e["j"]] for it, e in zip(items, rows)]
             prompts = None if no_prompt else [plans[e["r"]]["voice"]["prompt_semantic"].view(-1) for e in rows]
-            y, idx = self.t2s_model._run(x, prompts, bert, o["top_k"], o["top_p"], self.configs.hz * max_sec, o["temperature"],
+            y, idx = self.t2s_model._run(x, prompts, bert, o["top_k"], o["top_p"], early_stop_num(self.configs), o["temperature"],
                                          o["repetition_penalty"], eos_mask_steps=11 if naive else 1,
                                          max_steps=rows[0]["group"][6], rng_keys=[e["key"] for e in rows])
             for e, y_, i_ in zip(rows, y, idx):
-                preds[e["r"]][e["bi"]][e["j"]] = y_
-                idxs[e["r"]][e["bi"]][e["j"]] = 0 if no_prompt else i_
-        torch.cuda.current_stream(self.configs.device).synchronize()
-        # ---- post-AR: each request with its own voice, as run() does it
+                plans[e["r"]]["preds"][e["bi"]][e["j"]] = y_
+                plans[e["r"]]["idxs"][e["bi"]][e["j"]] = 0 if no_prompt else i_
+        for pl in plans:
+            pl["kept"] = [self._kept_tokens(p, i, pl["no_prompt"]) for p, i in zip(pl["preds"], pl["idxs"])]
+        self._wait_stream()
+
+    def _shared_sovits_stage(self, plans: List[dict]) -> None:
+        """shared_sovits, v1 / v2 / v2Pro: every fold (request r, to_batch batch bi) that plan_sovits shares is one segment,
+        with r's voice, of a SynthesizerTrn.decode_segments pass.  Reads `kept`, `voice`, `opts`, `actual_seed`,
+        `data`.  Writes `folds` (kept tokens per batch, plan_sovits' input) and `frags[bi]` of every shared fold."""
         up = math.prod(self.vits_model.upsample_rates)
-        sr = self.configs.sampling_rate if not self.configs.use_vocoder else self.vocoder_configs["sr"]
+        for pl in plans:
+            pl["folds"] = [sum(int(p_.shape[0]) for p_ in pred) for pred, _ in pl["kept"]]
+        dev_voice: Dict[tuple, tuple] = {}          # one device refer list per distinct voice: one voice slot
+        for launch in self.plan_sovits(plans):
+            codes, phones, voices, seeds, cuts = [], [], [], [], []
+            for r, bi in launch:
+                pl = plans[r]
+                pred = pl["kept"][bi][0]
+                keep = [k for k, p_ in enumerate(pred) if p_.shape[0] > 0]
+                codes.append(torch.cat([pred[k] for k in keep]).view(1, 1, -1))
+                phones.append(torch.cat([pl["data"][bi]["phones"][k] for k in keep]).view(1, -1))
+                vk = self._voice_key(pl["voice"])
+                if vk not in dev_voice:
+                    refer, sv_kw = self._voice_refer(pl["voice"])
+                    dev_voice[vk] = (refer, sv_kw.get("sv_emb"))
+                voices.append(dev_voice[vk])
+                seeds.append(pl["actual_seed"] + bi)
+                cuts.append([int(p_.shape[0]) * 2 * up for p_ in pred])
+            wavs = self.vits_model.decode_segments(codes, phones, voices, seeds)
+            for (r, bi), wav, cut in zip(launch, wavs, cuts):
+                plans[r]["frags"][bi] = list(torch.split(wav[0, 0], cut))
+        self.vits_model.invalidate_refer()          # the engine's cached reference terms are the last slot's voice
+
+    def _shared_cfm_stage(self, plans: List[dict]) -> None:
+        """shared_cfm, v3 / v4: every chunk of every fold that plan_cfm shares is one row, with its voice's prompt mel and the
+        noise key run() gives it, of a CFM.inference_rows pass; vocoder and SOLA stay per fold.  Reads `preds`, `kept`,
+        `voice`, `opts`, `actual_seed`, `data`.  Writes `cfm_folds` (feature frames per batch) and `T_min` (the voice's
+        prompt length), plan_cfm's inputs, and `frags[bi]` of every shared fold."""
+        prompts: Dict[tuple, tuple] = {}            # _prompt_features() per distinct voice
+        fold_in: Dict[Tuple[int, int], tuple] = {}  # (rows [chunks, T_chunk, 512], lens, pad_len)
+        voice_of: List[Optional[tuple]] = [None] * len(plans)
+        for r, pl in enumerate(plans):
+            pl["cfm_folds"], pl["T_min"] = [0] * len(pl["data"]), 0
+            if not pl["opts"]["parallel_infer"] or not pl["data"]:
+                continue
+            with self._with_prompt_cache(dict(pl["voice"])):
+                vk = voice_of[r] = self._voice_key(pl["voice"], self._CFM_VOICE_FIELDS)
+                if vk not in prompts:
+                    prompts[vk] = self._prompt_features()
+                prompt = prompts[vk]
+                pl["T_min"] = prompt[4]
+                for bi, item in enumerate(pl["data"]):
+                    idx_list = pl["kept"][bi][1]
+                    if sum(int(i) for i in idx_list) <= 0:
+                        continue
+                    fold_in[(r, bi)] = self._fold_chunks(prompt, idx_list, pl["preds"][bi],
+                                                         [ph.to(self.configs.device) for ph in item["phones"]],
+                                                         pl["opts"]["speed_factor"])
+                    pl["cfm_folds"][bi] = sum(fold_in[(r, bi)][1])
+        fold_out: Dict[Tuple[int, int], list] = {}
+        for rows in self.plan_cfm(plans):
+            mu = torch.cat([fold_in[(r, bi)][0][k:k + 1] for r, bi, k in rows], 0)
+            mels = [prompts[voice_of[r]][3] for r, _, _ in rows]
+            seeds = [CFM.row_seed(plans[r]["actual_seed"] + bi, k) for r, bi, k in rows]
+            o = plans[rows[0][0]]["opts"]           # a pass is of one (sample_steps, guidance rate) group
+            pred = self.vits_model.cfm.inference_rows(mu, mels, o["sample_steps"], seeds=seeds,
+                                                      inference_cfg_rate=o["inference_cfg_rate"])
+            for n, (r, bi, k) in enumerate(rows):
+                fold_out.setdefault((r, bi), []).append(pred[n:n + 1, :, mels[n].shape[2]:])
+        for (r, bi), got in fold_out.items():        # a fold is finished when all its rows are back
+            fea, lens, pad_len = fold_in[(r, bi)]
+            assert len(got) == fea.shape[0]
+            plans[r]["frags"][bi] = self._fold_audio(torch.cat(got, 0), lens, pad_len)
+
+    def _finish_request(self, pl: dict, sr: int) -> Tuple[int, np.ndarray]:
+        """Last stage, per request, with its voice as the prompt cache: the batches no shared stage took go through
+        _synthesize_batch as in run(), then audio_postprocess.  Reads `frags`, `preds`, `kept`, `voice`, `opts`,
+        `actual_seed`, `data`, `index`; fills the rest of `frags`; returns the request's (sr, int16 audio)."""
+        if not pl["data"]:
+            return silence()
+        o = pl["opts"]
+        with self._with_prompt_cache(dict(pl["voice"])) as voice:
+            voice_refer = self._voice_refer(voice)
+            for bi, item in enumerate(pl["data"]):
+                if pl["frags"][bi] is None:
+                    pred, idx_list = pl["kept"][bi]
+                    pl["frags"][bi] = self._synthesize_batch(item, pred, pl["preds"][bi], idx_list, bi, pl["actual_seed"], o,
+                                                             voice_refer)
+            self._wait_stream()
+            return self.audio_postprocess(pl["frags"], sr, pl["index"], o["speed_factor"], o["split_bucket"],
+                                          o["fragment_interval"], o["super_sampling"])
+
+    def _output_sr(self) -> int:
+        """the rate of the waveform stage: the SoVITS model's, v3 / v4 the vocoder's (which must be loaded)"""
         if self.configs.use_vocoder and self.vocoder is None:
             raise RuntimeError("init_vocoder() first")
+        return self.vocoder_configs["sr"] if self.configs.use_vocoder else self.configs.sampling_rate
 
-        def kept(r, bi):
-            """the generated tokens of batch bi of request r without their prompts, and run()'s idx_list"""
-            pred_list, idx_list = preds[r][bi], idxs[r][bi]
-            if plans[r]["no_prompt"]:
-                pred = list(pred_list)
-                return pred, [int(p_.shape[0]) for p_ in pred]
-            return [p_[-i:] if i > 0 else p_[:0] for p_, i in zip(pred_list, idx_list)], idx_list
+    def _wait_stream(self) -> None:
+        # stream-level wait only: the engine calls before it already synchronised their own streams, and a DEVICE-wide
+        # synchronize intermittently stalls 20-30 ms on this ROCm build (DESIGN.md section 8)
+        torch.cuda.current_stream(self.configs.device).synchronize()
 
-        # ---- shared SoVITS passes: every fold (request r, to_batch batch bi) is one segment with r's voice
-        shared: Dict[Tuple[int, int], List[torch.Tensor]] = {}
+    @torch.no_grad()
+    def run_batch(self, requests: List[dict], shared_sovits: bool = False, shared_cfm: bool = False) -> List[Tuple[int, np.ndarray]]:
+        """Several requests, each with its own reference voice, through shared AR decodes.  Each request dict takes the
+        keys run() accepts plus an optional "voice" (make_voice); without one it uses its ref_audio_path / prompt_text
+        (through make_voice's LRU) or the current prompt cache.  Returns one (sr, int16 audio) per request, in order: what
+        run(request) alone returns.  self.prompt_cache is not changed.  return_fragment is not supported.
+        shared_sovits=True: v1 / v2 / v2Pro / v2ProPlus requests at speed 1 take their waveforms from shared segmented passes
+        over all voices (_shared_sovits_stage) instead of one decode per to_batch batch.  shared_cfm=True: v3 / v4
+        parallel_infer requests take their flow-matching stage from shared passes over all voices' chunks (_shared_cfm_stage).
+        Neither keyword changes anything for the other model family."""
+        if self.t2s_model is None or self.vits_model is None:
+            raise RuntimeError("init_t2s_weights / init_vits_weights first")
+        self.stop_flag = False
+        plans = [self._plan_request(req) for req in requests]
+        self._ar_stage(plans)
+        sr = self._output_sr()
         if shared_sovits and not self.configs.use_vocoder:
-            for r, pl in enumerate(plans):
-                pl["folds"] = [sum(int(p_.shape[0]) for p_ in kept(r, bi)[0]) for bi in range(len(pl["data"]))]
-            dev_voice: Dict[tuple, tuple] = {}          # one device refer list per distinct voice: one voice slot
-            for launch in self.plan_sovits(plans):
-                codes, phones, voices, seeds, cuts = [], [], [], [], []
-                for r, bi in launch:
-                    pl = plans[r]
-                    pred = kept(r, bi)[0]
-                    keep = [k for k, p_ in enumerate(pred) if p_.shape[0] > 0]
-                    codes.append(torch.cat([pred[k] for k in keep]).view(1, 1, -1))
-                    phones.append(torch.cat([pl["data"][bi]["phones"][k] for k in keep]).view(1, -1))
-                    vk = self._voice_key(pl["voice"])
-                    if vk not in dev_voice:
-                        dev_voice[vk] = ([spec.to(device=self.configs.device) for spec, _ in pl["voice"]["refer_spec"]],
-                                         pl["voice"]["sv_emb"] if getattr(self.vits_model, "is_v2pro", False) else None)
-                    voices.append(dev_voice[vk])
-                    seeds.append(pl["actual_seed"] + bi)
-                    cuts.append([int(p_.shape[0]) * 2 * up for p_ in pred])
-                wavs = self.vits_model.decode_segments(codes, phones, voices, seeds)
-                for (r, bi), wav, cut in zip(launch, wavs, cuts):
-                    shared[(r, bi)] = list(torch.split(wav[0, 0], cut))
-            self.vits_model.invalidate_refer()          # the engine's cached reference terms are the last slot's voice
-        # ---- shared flow-matching passes: every chunk of every fold is one row with its voice's prompt
+            self._shared_sovits_stage(plans)
         if shared_cfm and self.configs.use_vocoder:
-            dev = self.configs.device
-            prompts: Dict[tuple, tuple] = {}            # _prompt_features() per distinct voice
-            fold_in: Dict[Tuple[int, int], tuple] = {}  # (rows [chunks, T_chunk, 512], lens, pad_len)
-            for r, pl in enumerate(plans):
-                pl["cfm_folds"], pl["T_min"] = [0] * len(pl["data"]), 0
-                if not pl["opts"]["parallel_infer"] or not pl["data"]:
-                    continue
-                with self._with_prompt_cache(dict(pl["voice"])):
-                    vk = pl["cfm_voice"] = self._voice_key(pl["voice"], self._CFM_VOICE_FIELDS)
-                    if vk not in prompts:
-                        prompts[vk] = self._prompt_features()
-                    prompt = prompts[vk]
-                    pl["T_min"] = prompt[4]
-                    for bi, item in enumerate(pl["data"]):
-                        idx_list = kept(r, bi)[1]
-                        if sum(int(i) for i in idx_list) <= 0:
-                            continue
-                        fold_in[(r, bi)] = self._fold_chunks(prompt, idx_list, preds[r][bi], [ph.to(dev) for ph in item["phones"]],
-                                                             pl["opts"]["speed_factor"])
-                        pl["cfm_folds"][bi] = sum(fold_in[(r, bi)][1])
-            fold_out: Dict[Tuple[int, int], list] = {}
-            for rows in self.plan_cfm(plans):
-                mu = torch.cat([fold_in[(r, bi)][0][k:k + 1] for r, bi, k in rows], 0)
-                mels = [prompts[plans[r]["cfm_voice"]][3] for r, _, _ in rows]
-                seeds = [(plans[r]["actual_seed"] + bi + 0x9E3779B97F4A7C15 * k) & 0xFFFFFFFFFFFFFFFF for r, bi, k in rows]
-                o = plans[rows[0][0]]["opts"]           # a pass is of one (sample_steps, guidance rate) group
-                pred = self.vits_model.cfm.inference_rows(mu, mels, o["sample_steps"], seeds=seeds,
-                                                          inference_cfg_rate=o["inference_cfg_rate"])
-                for n, (r, bi, k) in enumerate(rows):
-                    fold_out.setdefault((r, bi), []).append(pred[n:n + 1, :, mels[n].shape[2]:])
-            for (r, bi), got in fold_out.items():        # a fold is finished when all its rows are back
-                fea, lens, pad_len = fold_in[(r, bi)]
-                assert len(got) == fea.shape[0]
-                shared[(r, bi)] = self._fold_audio(torch.cat(got, 0), lens, pad_len)
-        results = []
-        for r, pl in enumerate(plans):
-            o = pl["opts"]
-            if not pl["data"]:
-                results.append((16000, np.zeros(16000, dtype=np.int16)))
-                continue
-            voice = dict(pl["voice"])
-            with self._with_prompt_cache(voice):
-                refer = [spec.to(device=self.configs.device) for spec, _ in voice["refer_spec"]]
-                sv_kw = {"sv_emb": voice["sv_emb"]} if getattr(self.vits_model, "is_v2pro", False) else {}
-                audio = []
-                for bi, item in enumerate(pl["data"]):
-                    if (r, bi) in shared:
-                        audio.append(shared[(r, bi)])
-                        continue
-                    pred_list = preds[r][bi]
-                    pred, idx_list = kept(r, bi)
-                    audio.append(self._synthesize_batch(item, pred, pred_list, idx_list, pl["actual_seed"] + bi, bi,
-                                                        pl["actual_seed"], o["speed_factor"], o["parallel_infer"],
-                                                        o["sample_steps"], refer, sv_kw, up, o["inference_cfg_rate"]))
-                torch.cuda.current_stream(self.configs.device).synchronize()
-                results.append(self.audio_postprocess(audio, sr, pl["index"], o["speed_factor"], o["split_bucket"],
-                                                      o["fragment_interval"], pl["super_sampling"]))
-        return results
+            self._shared_cfm_stage(plans)
+        return [self._finish_request(pl, sr) for pl in plans]
 
     # ---- the pipeline (reference TTS.py:984-1365) ---------------------------------------------
     @torch.no_grad()
     def run(self, inputs: dict) -> Generator[Tuple[int, np.ndarray], None, None]:
         self.stop_flag = False
-        top_k = inputs.get("top_k", 5)
-        top_p = inputs.get("top_p", 1)
-        temperature = inputs.get("temperature", 1)
-        batch_size = inputs.get("batch_size", 1)
-        batch_threshold = inputs.get("batch_threshold", 0.75)
-        speed_factor = inputs.get("speed_factor", 1.0)
-        split_bucket = inputs.get("split_bucket", True)
-        return_fragment = inputs.get("return_fragment", False)
-        fragment_interval = inputs.get("fragment_interval", 0.3)
-        seed = inputs.get("seed", -1)
-        seed = -1 if seed in ["", None] else seed
-        actual_seed = set_seed(seed)
-        parallel_infer = inputs.get("parallel_infer", True)
-        repetition_penalty = inputs.get("repetition_penalty", 1.35)
-        if fragment_interval < 0.01:
-            fragment_interval = 0.01
-        if return_fragment and split_bucket:
-            split_bucket = False
-        if speed_factor != 1.0:
-            split_bucket = False
-        elif getattr(self.configs, "use_vocoder", False) and parallel_infer:
-            split_bucket = False           # v3 / v4 parallel runs are never bucketed (reference TTS.py:1060-1062)
-        # reference TTS.py:1040, 1328, 1349: AP_BWE super-sampling applies to the v3 vocoder output only; v1 / v2 / v2Pro / v4
-        # ignore the key
-        super_sampling = bool(inputs.get("super_sampling", False)) and getattr(self.configs, "use_vocoder", False) and \
-            self.configs.version == "v3"
+        o = self._resolve_options(inputs)
+        actual_seed = set_seed(o["seed"])
         try:
             if self.t2s_model is None or self.vits_model is None:
                 raise RuntimeError("init_t2s_weights / init_vits_weights first")
@@ -1267,82 +1282,66 @@ class TTS:
             t0 = time.perf_counter()
             segments = self._segments(inputs)
             if len(segments) == 0:
-                yield 16000, np.zeros(16000, dtype=np.int16)
+                yield silence()
                 return
-            prompt_data = None
-            if self.prompt_cache["phones"] is not None:
-                prompt_data = {"phones": self.prompt_cache["phones"], "bert_features": self.prompt_cache["bert_features"]}
+            pc = self.prompt_cache
+            prompt_data = None if pc["phones"] is None else {"phones": pc["phones"], "bert_features": pc["bert_features"]}
             t1 = time.perf_counter()
             # token ids stay on the host here: the engines pack a whole batch and move it with ONE copy
             # (the reference's per-item .to(device), TTS.py:899-912, is ~75 tiny transfers per batch of 32)
-            data, batch_index_list = self.to_batch(segments, prompt_data=prompt_data, batch_size=batch_size,
-                                                   threshold=batch_threshold, split_bucket=split_bucket,
+            data, batch_index_list = self.to_batch(segments, prompt_data=prompt_data, batch_size=o["batch_size"],
+                                                   threshold=o["batch_threshold"], split_bucket=o["split_bucket"],
                                                    device=torch.device("cpu"), precision=self.precision)
             t2 = time.perf_counter()
-            infer = (self.t2s_model.infer_panel_batch_infer if parallel_infer
-                     else self.t2s_model.infer_panel_naive_batched)
-            refer = [spec.to(device=self.configs.device) for spec, _ in self.prompt_cache["refer_spec"]]
-            sv_kw = {"sv_emb": self.prompt_cache["sv_emb"]} if getattr(self.vits_model, "is_v2pro", False) else {}
-            up = math.prod(self.vits_model.upsample_rates)
+            infer = self.t2s_model.infer_panel_batch_infer if o["parallel_infer"] else self.t2s_model.infer_panel_naive_batched
+            voice_refer = self._voice_refer(self.prompt_cache)
             audio, t_34, t_45 = [], 0.0, 0.0
-            sr = self.configs.sampling_rate if not self.configs.use_vocoder else self.vocoder_configs["sr"]
-            if self.configs.use_vocoder and self.vocoder is None:
-                raise RuntimeError("init_vocoder() first")
+            sr = self._output_sr()
             self.last_generated_tokens = 0
             for bi, item in enumerate(data):
                 t3 = time.perf_counter()
-                n = len(item["all_phones"])
                 # no prompt text (reference TTS.py:1124-1131, 1223-1226): nothing is prepended and the AR decoder runs
                 # prompt-free through the naive loop; v3/v4 require a prompt (TTS.py:1062-1063)
                 no_prompt = prompt_data is None
                 if no_prompt and self.configs.use_vocoder:
                     raise NO_PROMPT_ERROR("v3/v4 need the prompt text (phones) of the reference audio")
-                prompt = None if no_prompt else self.prompt_cache["prompt_semantic"].view(1, -1).expand(n, -1)
-                max_sec = self.configs.max_sec if self.configs.max_sec is not None else 54
+                prompt = None if no_prompt else self.prompt_cache["prompt_semantic"].view(1, -1).expand(len(item["all_phones"]), -1)
                 pred_list, idx_list = infer(item["all_phones"], item["all_phones_len"], prompt,
-                                            item["all_bert_features"], top_k=top_k, top_p=top_p, temperature=temperature,
-                                            early_stop_num=self.configs.hz * max_sec, max_len=item["max_len"],
-                                            repetition_penalty=repetition_penalty, seed=actual_seed + bi)
-                # stream-level wait only: the engine calls above already synchronised their own streams, and a DEVICE-wide
-                # synchronize intermittently stalls 20-30 ms on this ROCm build
-                torch.cuda.current_stream(self.configs.device).synchronize()
+                                            item["all_bert_features"], top_k=o["top_k"], top_p=o["top_p"],
+                                            temperature=o["temperature"], early_stop_num=early_stop_num(self.configs),
+                                            max_len=item["max_len"], repetition_penalty=o["repetition_penalty"],
+                                            seed=actual_seed + bi)
+                self._wait_stream()
                 t4 = time.perf_counter()
                 t_34 += t4 - t3
-                if no_prompt:     # idx is reported as 0 and y holds only generated tokens (t2s_model.py:916-917)
-                    pred = list(pred_list)
-                    idx_list = [int(p.shape[0]) for p in pred]
-                else:
-                    pred = [p[-i:] if i > 0 else p[:0] for p, i in zip(pred_list, idx_list)]
+                pred, idx_list = self._kept_tokens(pred_list, idx_list, no_prompt)
                 self.last_generated_tokens += int(sum(idx_list))
-                frags = self._synthesize_batch(item, pred, pred_list, idx_list, actual_seed + bi, bi, actual_seed, speed_factor,
-                                               parallel_infer, inputs.get("sample_steps", 32), refer, sv_kw, up,
-                                               inputs.get("inference_cfg_rate", 0))
-                # stream-level wait only: the engine calls above already synchronised their own streams, and a DEVICE-wide
-                # synchronize intermittently stalls 20-30 ms on this ROCm build
-                torch.cuda.current_stream(self.configs.device).synchronize()
+                frags = self._synthesize_batch(item, pred, pred_list, idx_list, bi, actual_seed, o, voice_refer)
+                self._wait_stream()
                 t5 = time.perf_counter()
                 t_45 += t5 - t4
-                if return_fragment:
-                    yield self.audio_postprocess([frags], sr, None, speed_factor, False, fragment_interval, super_sampling)
+                if o["return_fragment"]:
+                    yield self.audio_postprocess([frags], sr, None, o["speed_factor"], False, o["fragment_interval"],
+                                                 o["super_sampling"])
                 else:
                     audio.append(frags)
                 if self.stop_flag:
-                    yield 16000, np.zeros(16000, dtype=np.int16)
+                    yield silence()
                     return
             self.last_timing = (t1 - t0, t2 - t1, t_34, t_45)
-            if not return_fragment:
+            if not o["return_fragment"]:
                 if len(audio) == 0:
-                    yield 16000, np.zeros(16000, dtype=np.int16)
+                    yield silence()
                     return
                 t6 = time.perf_counter()
-                result = self.audio_postprocess(audio, sr, batch_index_list, speed_factor, split_bucket, fragment_interval,
-                                                super_sampling)
+                result = self.audio_postprocess(audio, sr, batch_index_list, o["speed_factor"], o["split_bucket"],
+                                                o["fragment_interval"], o["super_sampling"])
                 self.last_postprocess_s = time.perf_counter() - t6
                 yield result
         except Exception as e:
             traceback.print_exc()
             # the reference yields 1 s of silence, rebuilds both models, then re-raises (TTS.py:1352-1363)
-            yield 16000, np.zeros(16000, dtype=np.int16)
+            yield silence()
             try:
                 if self._t2s_state is not None and self._vits_state is not None:
                     self.t2s_model = None

@@ -371,6 +371,39 @@ class CFM:
         self.estimator = dit
         self.sigma_min = 1e-6
 
+    @classmethod
+    def row_seed(cls, seed: int, b: int) -> int:
+        """the 64-bit noise key of row b of a batch drawn with `seed`: what gsv_cfm_inference gives its row b"""
+        return (int(seed) + cls.GOLDEN * int(b)) & 0xFFFFFFFFFFFFFFFF
+
+    def _check_mu_noise(self, mu, noise):
+        """the checks `inference` and `inference_rows` share -> (B, T) of mu [B, T, text_dim]"""
+        dit = self.estimator
+        if not dit._loaded:
+            raise RuntimeError("DiT.load_state_dict() first")
+        if mu.dim() != 3 or mu.shape[2] != dit.text_dim or mu.shape[1] < 1:
+            raise ValueError(f"expected mu of shape [B, T>=1, {dit.text_dim}], got {tuple(mu.shape)}")
+        B, T = int(mu.shape[0]), int(mu.shape[1])
+        if noise is not None and tuple(noise.shape) != (B, self.in_channels, T):
+            raise ValueError(f"noise must have shape {(B, self.in_channels, T)}")
+        return B, T
+
+    def _launch(self, mu, prompts, noise, call):
+        """Around one C call on the DiT's stream: fp32 contiguous copies of mu, the prompts and the noise on its device, `out`
+        [B, in_channels, T] fp32, the wait for torch's current stream, `call(m, ps, nz_ptr, out, stream)`, the synchronize;
+        returns `out` in mu's dtype (fp16 / fp32, anything else fp32)."""
+        dit = self.estimator
+        dev = dit.device
+        with torch.cuda.device(dev):
+            m = mu.to(dev, torch.float32).contiguous()
+            ps = [p.to(dev, torch.float32).contiguous() for p in prompts]
+            nz = noise.to(dev, torch.float32).contiguous() if noise is not None else None
+            out = torch.empty(int(mu.shape[0]), self.in_channels, int(mu.shape[1]), dtype=torch.float32, device=dev)
+            dit.stream.wait_stream(torch.cuda.current_stream(dev))
+            call(m, ps, nz.data_ptr() if nz is not None else None, out, C.c_void_p(dit.stream.cuda_stream))
+            dit.stream.synchronize()
+        return out.to(mu.dtype if mu.dtype in (torch.float16, torch.float32) else torch.float32)
+
     @torch.no_grad()
     def inference(self, mu, x_lens, prompt, n_timesteps, temperature=1.0, inference_cfg_rate=0, noise=None, seed=0):
         """mu [B, T, text_dim]; x_lens unused (as in the reference); prompt [B, in_channels, Tp] -> [B, in_channels, T]"""
@@ -378,36 +411,23 @@ class CFM:
             raise NotImplementedError("CFM.inference is the unguided entry (every caller in the reference passes "
                                       "inference_cfg_rate=0, TTS.py:1351, inference_webui.py:937); classifier-free guidance "
                                       "is CFM.inference_guided")
-        dit = self.estimator
-        if not dit._loaded:
-            raise RuntimeError("DiT.load_state_dict() first")
-        if mu.dim() != 3 or mu.shape[2] != dit.text_dim or mu.shape[1] < 1:
-            raise ValueError(f"expected mu of shape [B, T>=1, {dit.text_dim}], got {tuple(mu.shape)}")
-        B, T = int(mu.shape[0]), int(mu.shape[1])
+        B, T = self._check_mu_noise(mu, noise)
         if prompt.dim() != 3 or prompt.shape[0] not in (1, B) or prompt.shape[1] != self.in_channels or prompt.shape[2] > T:
             raise ValueError(f"expected prompt of shape [{B} or 1, {self.in_channels}, Tp<={T}], got {tuple(prompt.shape)}")
         if prompt.shape[0] != B:           # one prompt broadcast over the batch (models.py:1036 assigns it into every row)
             prompt = prompt.expand(B, -1, -1)
         Tp = int(prompt.shape[2])
-        if noise is not None and tuple(noise.shape) != (B, self.in_channels, T):
-            raise ValueError(f"noise must have shape {(B, self.in_channels, T)}")
-        dev = dit.device
-        with torch.cuda.device(dev):
-            m = mu.to(dev, torch.float32).contiguous()
-            p = prompt.to(dev, torch.float32).contiguous()
-            nz = noise.to(dev, torch.float32).contiguous() if noise is not None else None
-            out = torch.empty(B, self.in_channels, T, dtype=torch.float32, device=dev)
-            dit.stream.wait_stream(torch.cuda.current_stream(dev))
-            _lib.check(_lib.lib().gsv_cfm_inference(dit._h, m.data_ptr(), p.data_ptr() if Tp else None, B, T, Tp, int(n_timesteps),
-                                                    nz.data_ptr() if nz is not None else None, float(temperature), int(seed),
-                                                    out.data_ptr(), C.c_void_p(dit.stream.cuda_stream)), "gsv_cfm_inference")
-            dit.stream.synchronize()
-        return out.to(mu.dtype if mu.dtype in (torch.float16, torch.float32) else torch.float32)
+
+        def call(m, ps, nz, out, stream):
+            _lib.check(_lib.lib().gsv_cfm_inference(self.estimator._h, m.data_ptr(), ps[0].data_ptr() if Tp else None, B, T, Tp,
+                                                    int(n_timesteps), nz, float(temperature), int(seed), out.data_ptr(), stream),
+                       "gsv_cfm_inference")
+        return self._launch(mu, [prompt], noise, call)
 
     @torch.no_grad()
     def inference_guided(self, mu, x_lens, prompt, n_timesteps, temperature=1.0, inference_cfg_rate=0, noise=None, seed=0):
         """The reference's `CFM.inference(..., inference_cfg_rate=r)` with classifier-free guidance (models.py:1063-1081);
-        arguments as `inference`.  r > 1e-5: the rows entry with uniform prompts and seeds[b] = seed + GOLDEN * b, so the
+        arguments as `inference`.  r > 1e-5: the rows entry with uniform prompts and seeds[b] = row_seed(seed, b), so the
         noise is the unguided call's.  r <= 1e-5 (zero and negative rates included) is `inference` itself."""
         if not math.isfinite(inference_cfg_rate):
             raise ValueError(f"inference_cfg_rate must be finite, got {inference_cfg_rate}")
@@ -416,23 +436,18 @@ class CFM:
         B = int(mu.shape[0]) if mu.dim() == 3 else 0
         if prompt.dim() != 3 or prompt.shape[0] not in (1, B):
             raise ValueError(f"expected prompt of shape [{B} or 1, {self.in_channels}, Tp], got {tuple(prompt.shape)}")
-        seeds = [(int(seed) + self.GOLDEN * b) & 0xFFFFFFFFFFFFFFFF for b in range(B)]
         return self.inference_rows(mu, [prompt[b:b + 1] if prompt.shape[0] == B else prompt for b in range(B)], n_timesteps,
-                                   temperature=temperature, noise=noise, seeds=seeds, inference_cfg_rate=inference_cfg_rate)
+                                   temperature=temperature, noise=noise, seeds=[self.row_seed(seed, b) for b in range(B)],
+                                   inference_cfg_rate=inference_cfg_rate)
 
     @torch.no_grad()
     def inference_rows(self, mu, prompts, n_timesteps, temperature=1.0, noise=None, seeds=None, inference_cfg_rate=0):
         """`inference` for B rows that each have their own prompt (`gsv_cfm_inference_rows`): mu [B, T, text_dim]; prompts a
         list of B tensors [1, in_channels, Tp_b], 0 <= Tp_b <= T -> [B, in_channels, T], row b's first Tp_b frames zero.
         `seeds` (B ints) are the rows' own noise keys, taken as they are: row b of `inference(seed=s)` is seeds[b] =
-        s + 0x9E3779B97F4A7C15 * b here.  `noise` [B, in_channels, T] pins the draw instead.  `inference_cfg_rate` > 1e-5
+        row_seed(s, b) here.  `noise` [B, in_channels, T] pins the draw instead.  `inference_cfg_rate` > 1e-5
         guides every row with that rate (`gsv_cfm_inference_guided`, 2 B DiT rows); the noise of a row does not depend on it."""
-        dit = self.estimator
-        if not dit._loaded:
-            raise RuntimeError("DiT.load_state_dict() first")
-        if mu.dim() != 3 or mu.shape[2] != dit.text_dim or mu.shape[1] < 1:
-            raise ValueError(f"expected mu of shape [B, T>=1, {dit.text_dim}], got {tuple(mu.shape)}")
-        B, T = int(mu.shape[0]), int(mu.shape[1])
+        B, T = self._check_mu_noise(mu, noise)
         if B < 1 or len(prompts) != B:
             raise ValueError(f"expected {B} >= 1 prompts, one per row of mu, got {len(prompts)}")
         for b, p in enumerate(prompts):
@@ -442,29 +457,18 @@ class CFM:
             raise ValueError(f"inference_cfg_rate must be finite, got {inference_cfg_rate}")
         if noise is None and seeds is None:
             raise ValueError("inference_rows needs `noise` or `seeds`")
-        if noise is not None and tuple(noise.shape) != (B, self.in_channels, T):
-            raise ValueError(f"noise must have shape {(B, self.in_channels, T)}")
         if seeds is not None and len(seeds) != B:
             raise ValueError(f"expected {B} seeds, got {len(seeds)}")
-        dev = dit.device
-        with torch.cuda.device(dev):
-            m = mu.to(dev, torch.float32).contiguous()
-            ps = [p.to(dev, torch.float32).contiguous() for p in prompts]
-            nz = noise.to(dev, torch.float32).contiguous() if noise is not None else None
-            out = torch.empty(B, self.in_channels, T, dtype=torch.float32, device=dev)
+
+        def call(m, ps, nz, out, stream):
             ptrs = (C.c_void_p * B)(*[p.data_ptr() if p.shape[2] else None for p in ps])
             tps = (C.c_int * B)(*[int(p.shape[2]) for p in ps])
             sd = (C.c_uint64 * B)(*[int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds]) if seeds is not None else None
-            dit.stream.wait_stream(torch.cuda.current_stream(dev))
+            h, lib = self.estimator._h, _lib.lib()
             if cfg_guided(inference_cfg_rate):
-                _lib.check(_lib.lib().gsv_cfm_inference_guided(dit._h, m.data_ptr(), ptrs, tps, B, T, int(n_timesteps),
-                                                               nz.data_ptr() if nz is not None else None, sd, float(temperature),
-                                                               float(inference_cfg_rate), out.data_ptr(),
-                                                               C.c_void_p(dit.stream.cuda_stream)), "gsv_cfm_inference_guided")
+                _lib.check(lib.gsv_cfm_inference_guided(h, m.data_ptr(), ptrs, tps, B, T, int(n_timesteps), nz, sd, float(temperature),
+                                                        float(inference_cfg_rate), out.data_ptr(), stream), "gsv_cfm_inference_guided")
             else:
-                _lib.check(_lib.lib().gsv_cfm_inference_rows(dit._h, m.data_ptr(), ptrs, tps, B, T, int(n_timesteps),
-                                                             nz.data_ptr() if nz is not None else None, sd, float(temperature),
-                                                             out.data_ptr(), C.c_void_p(dit.stream.cuda_stream)),
-                           "gsv_cfm_inference_rows")
-            dit.stream.synchronize()
-        return out.to(mu.dtype if mu.dtype in (torch.float16, torch.float32) else torch.float32)
+                _lib.check(lib.gsv_cfm_inference_rows(h, m.data_ptr(), ptrs, tps, B, T, int(n_timesteps), nz, sd, float(temperature),
+                                                      out.data_ptr(), stream), "gsv_cfm_inference_rows")
+        return self._launch(mu, prompts, noise, call)

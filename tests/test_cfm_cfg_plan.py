@@ -4,8 +4,10 @@ plans are what they were -- plus the option plumbing and the C ABI of the guided
 import inspect
 import os
 import re
+from types import SimpleNamespace
 
 import pytest
+import torch
 
 from conftest import ROOT
 from gsv.TTS_infer_pack.TTS import TTS
@@ -19,8 +21,27 @@ def _n(T_min, frames):
 def test_request_option_and_keywords():
     assert TTS._request_options({})["inference_cfg_rate"] == 0
     assert TTS._request_options({"inference_cfg_rate": 0.7})["inference_cfg_rate"] == 0.7
-    for fn in (TTS._synthesize_batch, TTS.using_vocoder_synthesis, TTS.using_vocoder_synthesis_batched_infer):
+    for fn in (TTS.using_vocoder_synthesis, TTS.using_vocoder_synthesis_batched_infer):
         assert inspect.signature(fn).parameters["inference_cfg_rate"].default == 0, fn.__name__
+    # _synthesize_batch hands the resolved options on: rate, steps, speed, and the seed of the batch / of each chunked sentence
+    calls = []
+    stub = SimpleNamespace(configs=SimpleNamespace(use_vocoder=True, device="cpu"),
+                           using_vocoder_synthesis_batched_infer=lambda idx, sem, ph, **kw: calls.append(kw) or [None] * len(idx),
+                           using_vocoder_synthesis=lambda sem, ph, **kw: calls.append(kw))
+    item = {"phones": [torch.arange(3), torch.arange(4)]}
+    pred_list, idx_list = [torch.arange(9), torch.arange(7)], [5, 2]
+    actual_seed, bi = 100, 3
+    for req, (rate, steps, speed) in (({}, (0, 32, 1.0)),
+                                      ({"inference_cfg_rate": 0.7, "sample_steps": 8, "speed_factor": 1.25}, (0.7, 8, 1.25))):
+        for parallel in (True, False):
+            del calls[:]
+            opts = TTS._request_options(dict(req, parallel_infer=parallel))
+            TTS._synthesize_batch(stub, item, [p[-i:] for p, i in zip(pred_list, idx_list)], pred_list, idx_list, bi, actual_seed,
+                                  opts, ([], {}))
+            assert len(calls) == (1 if parallel else len(idx_list))
+            assert all((kw["inference_cfg_rate"], kw["sample_steps"], kw["speed"]) == (rate, steps, speed) for kw in calls)
+            assert [kw["seed"] for kw in calls] == ([actual_seed + bi] if parallel else
+                                                    [actual_seed + bi * 4096 + k for k in range(len(idx_list))])
     from gsv.module.models import CFM
     assert inspect.signature(CFM.inference_rows).parameters["inference_cfg_rate"].default == 0
     assert inspect.signature(CFM.inference).parameters["inference_cfg_rate"].default == 0

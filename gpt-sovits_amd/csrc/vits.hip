@@ -305,6 +305,32 @@ __global__ void interp_linear_kernel(const T* __restrict__ x, int Tin, int Tout,
     y[(long long)t * C + c] = (T)(w0 * to_f(x[(long long)i0 * C + c]) + w1 * to_f(x[(long long)i1 * C + c]));
 }
 
+// segmented decode with per-segment speeds: interp_linear_kernel per segment.  x holds the pre layout (segment s: Tin = len_in[s]
+// rows from row start_in[s]), y the post layout (Tout = len_out[s] rows from row start_out[s]); seg_out names the segment of every
+// post row, -1 = gap (written as zeros).  Same arithmetic as above with the segment's own Tin / Tout: the clamps of i0 / i1 keep
+// every read inside the segment's pre rows.  Tin == Tout (speed 1) copies the row.
+template <typename T>
+__global__ void interp_linear_seg_kernel(const T* __restrict__ x, const int* __restrict__ seg_out, const int* __restrict__ start_in,
+                                         const int* __restrict__ len_in, const int* __restrict__ start_out,
+                                         const int* __restrict__ len_out, int rows, int C, T* __restrict__ y) {
+  const int row = blockIdx.x;
+  if (row >= rows) return;
+  T* dst = y + (long long)row * C;
+  const int sg = seg_out[row];
+  if (sg < 0) { for (int c = threadIdx.x; c < C; c += blockDim.x) dst[c] = (T)0.f; return; }
+  const int t = row - start_out[sg], Tin = len_in[sg], Tout = len_out[sg];
+  const T* xs = x + (long long)start_in[sg] * C;
+  if (Tin == Tout) { for (int c = threadIdx.x; c < C; c += blockDim.x) dst[c] = xs[(long long)t * C + c]; return; }
+  const float scale = (float)Tin / (float)Tout;
+  float src = scale * ((float)t + 0.5f) - 0.5f;
+  if (src < 0.f) src = 0.f;
+  const int i0 = min((int)src, Tin - 1);
+  const int i1 = min(i0 + 1, Tin - 1);
+  const float w1 = src - (float)i0, w0 = 1.f - w1;
+  for (int c = threadIdx.x; c < C; c += blockDim.x)
+    dst[c] = (T)(w0 * to_f(xs[(long long)i0 * C + c]) + w1 * to_f(xs[(long long)i1 * C + c]));
+}
+
 // F.interpolate(mode="nearest", scale_factor=sf) along time: src = min(floor(dst * (float)(1/sf)), Tin - 1)
 template <typename T>
 __global__ void interp_nearest_kernel(const T* __restrict__ x, int Tin, int Tout, int C, float scale, T* __restrict__ y) {
@@ -689,33 +715,46 @@ int seg_gap(const gsv_vits_config& c) {
 
 struct SegLayout {
   int n = 0, G = 0, F = 0, L = 0, Fn = 0;        // frames / phones with gaps; Fn = frames without gaps
-  std::vector<int> f0, l0, c0, p0, fn0;          // per segment: first frame / phone row, first packed code / phone, packed frame
-};
+  std::vector<int> f0, l0, c0, p0, fn0, nf;      // per segment: first frame / phone row, first packed code / phone, packed frame,
+};                                               // frames
 
-int seg_layout(const gsv_vits_config& c, int n, const int* code_lens, const int* phone_lens, SegLayout* o) {
+// speeds == null: the pre layout, 2 T_s frames per segment (codebook gather, enc_ssl, MRTE, enc2).  With speeds: the post layout,
+// F_s frames per segment as the speed interpolation of gsv_vits_decode leaves them (proj onwards); same gap, same phone axis.
+int seg_layout(const gsv_vits_config& c, int n, const int* code_lens, const int* phone_lens, const double* speeds, SegLayout* o) {
   GSV_REQUIRE(n >= 1 && n <= 4096 && code_lens && phone_lens, "vits segments: bad segment count %d", n);
   o->n = n; o->G = seg_gap(c);
-  o->f0.resize(n); o->l0.resize(n); o->c0.resize(n); o->p0.resize(n); o->fn0.resize(n);
-  long long f = 0, l = 0, cc = 0, pp = 0;
+  o->f0.resize(n); o->l0.resize(n); o->c0.resize(n); o->p0.resize(n); o->fn0.resize(n); o->nf.resize(n);
+  long long f = 0, l = 0, cc = 0, pp = 0, fn = 0;
   for (int i = 0; i < n; ++i) {
     GSV_REQUIRE(code_lens[i] >= 1 && phone_lens[i] >= 1, "vits segments: segment %d is empty (%d codes, %d phones)", i, code_lens[i],
                 phone_lens[i]);
+    GSV_REQUIRE(code_lens[i] < (1 << 23), "vits segments: too long");
+    long long fs = 2LL * code_lens[i];
+    if (speeds && speeds[i] != 1.0) {
+      GSV_REQUIRE(std::isfinite(speeds[i]) && speeds[i] > 0.0, "vits segments: speed of segment %d must be finite and positive", i);
+      const double q = (double)fs / speeds[i];
+      GSV_REQUIRE(q < (double)(1 << 24), "vits segments: too long");
+      fs = (long long)(int)q + 1;
+    }
     if (i) { f += o->G; l += o->G; }
-    o->f0[i] = (int)f; o->l0[i] = (int)l; o->c0[i] = (int)cc; o->p0[i] = (int)pp; o->fn0[i] = (int)(2 * cc);
-    f += 2LL * code_lens[i]; l += phone_lens[i]; cc += code_lens[i]; pp += phone_lens[i];
+    o->f0[i] = (int)f; o->l0[i] = (int)l; o->c0[i] = (int)cc; o->p0[i] = (int)pp; o->fn0[i] = (int)fn; o->nf[i] = (int)fs;
+    f += fs; l += phone_lens[i]; cc += code_lens[i]; pp += phone_lens[i]; fn += fs;
     GSV_REQUIRE(f < (1LL << 24) && l < (1LL << 24), "vits segments: too long");
   }
-  o->F = (int)f; o->L = (int)l; o->Fn = (int)(2 * cc);
+  o->F = (int)f; o->L = (int)l; o->Fn = (int)fn;
   return GSV_OK;
 }
 
 // device side of one segmented decode
 struct SegRun {
-  const SegLayout* lay = nullptr;
-  const int *seg_f = nullptr, *seg_l = nullptr;          // segment id per frame row / phone row, -1 = gap
+  const SegLayout *lay = nullptr, *post = nullptr;       // pre layout (up to enc2), post layout (after the speed interpolation,
+                                                         // proj onwards); post == lay when no segment changes its frame count
+  const int *seg_f = nullptr, *seg_l = nullptr;          // segment id per pre frame row / phone row, -1 = gap
+  const int* seg_p = nullptr;                            // segment id per post frame row (== seg_f when post == lay)
   const int *kr_f = nullptr, *kr_l = nullptr, *kr_x = nullptr;   // key ranges: frame and text self-attention, MRTE (phones)
   const int *src_code = nullptr, *src_phone = nullptr;   // packed code / phone index per row, -1 = gap
-  const int *start = nullptr, *noff = nullptr;           // per segment: first frame row, first packed noise column
+  const int *start = nullptr, *noff = nullptr;           // per segment: first post frame row, first packed noise column
+  const int *start_pre = nullptr, *len_pre = nullptr, *len_post = nullptr;   // per segment: first pre row, pre / post frames
   const unsigned long long* seeds = nullptr;
   std::vector<int*> seg_up;                              // segment id per row after each upsampling stage
   const float* bias = nullptr;                           // per-segment voice rows [n][voice_len]
@@ -723,11 +762,11 @@ struct SegRun {
 
 // A conv whose bias carries the speaker conditioning, x [F][c.cin] -> y [F][c.cout].  Plain decode: the handle's folded bias.
 // Segmented decode: the vector at `voff` of a voice row -- one segment takes its row as the bias; with several, the conv runs
-// without bias and a row pass over y adds each segment's own row and zeroes the gap rows (so y must feed nothing in between).
+// without bias and a row pass over y adds each segment's own row and zeroes the gap rows (so y must feed nothing in between);
+// seg_f is the row map of the layout x is in (sr->seg_f or sr->seg_p).
 static int conv_voice(gsv_vits* h, hipStream_t s, const Conv& c, const void* x, int F, void* y, ConvOpt o, const float* handle_bias,
-                      const SegRun* sr, size_t voff) {
+                      const SegRun* sr, size_t voff, const int* seg_f) {
   const float* vrow = sr ? sr->bias + voff : nullptr;
-  const int* seg_f = sr ? sr->seg_f : nullptr;
   o.bias_override = sr ? vrow : handle_bias;
   o.no_bias = seg_f != nullptr;
   GSV_RC(conv(h, s, c, x, c.cin, F, y, F, o));
@@ -737,7 +776,7 @@ static int conv_voice(gsv_vits* h, hipStream_t s, const Conv& c, const void* x, 
 
 // quantizer.decode + nearest x2 (H8) and TextEncoder.forward up to (and including) the speed interpolation (H10, reference
 // module/models.py:199-231): returns the hidden sequence y [F][hidden] (what `enc_p` returns as its first value)
-// sr != null: segmented (speed 1), Tc / L are ignored for the padded totals of sr->lay
+// sr != null: segmented, Tc / L / speed are ignored for the padded totals of sr->lay (in) and sr->post (out)
 template <typename T>
 int run_enc_p(gsv_vits* h, hipStream_t s, const int32_t* codes, int Tc, const int32_t* phones, int L, double speed, void** y_out,
               int* F_out, const SegRun* sr = nullptr) {
@@ -746,7 +785,7 @@ int run_enc_p(gsv_vits* h, hipStream_t s, const int32_t* codes, int Tc, const in
   const int H = c.hidden_channels, SSL = c.ssl_dim, MH = 512;
   if (sr) L = sr->lay->L;
   const int F0 = sr ? sr->lay->F : 2 * Tc;
-  const int F = (speed == 1.0 || sr) ? F0 : (int)((double)F0 / speed) + 1;   // frames after the speed interpolation
+  const int F = sr ? sr->post->F : speed == 1.0 ? F0 : (int)((double)F0 / speed) + 1;   // frames after the speed interpolation
   // ---- H8: codebook gather + nearest x2
   void *q768, *y, *tx;
   GSV_RC(need(h, "q768", (size_t)F0 * SSL * es, &q768));
@@ -777,14 +816,17 @@ int run_enc_p(gsv_vits* h, hipStream_t s, const int32_t* codes, int Tc, const in
     GSV_RC(attention(h, s, q512, MH, 0, kv512, 2 * MH, 0, MH, F0, L, 4, MH / 4, 1.f / sqrtf((float)(MH / 4)), nullptr, nullptr, o512, MH,
                      sr ? sr->kr_x : nullptr));
     ConvOpt om; om.res = s512; om.ldr = MH;
-    GSV_RC(conv_voice(h, s, h->mo, o512, F0, x512, om, h->mo_bias_eff, sr, 0));
+    GSV_RC(conv_voice(h, s, h->mo, o512, F0, x512, om, h->mo_bias_eff, sr, 0, seg_f));
     GSV_RC(conv(h, s, h->c_post, x512, MH, F0, y, F0, o));
   }
   GSV_RC(run_encoder(h, s, h->enc2, y, F0, seg_f, kr_f));
-  if (F != F0) {
+  if (seg_f ? sr->post != sr->lay : F != F0) {      // one segment (maps nulled) is the plain sequence
     void* yi;
     GSV_RC(need(h, "enc_x_speed", (size_t)F * H * es, &yi));
-    GSV_LAUNCH(interp_linear_kernel<T>, dim3(F), dim3(64), 0, s, (const T*)y, F0, F, H, (T*)yi);
+    if (seg_f)
+      GSV_LAUNCH(interp_linear_seg_kernel<T>, dim3(F), dim3(64), 0, s, (const T*)y, sr->seg_p, sr->start_pre, sr->len_pre, sr->start,
+                 sr->len_post, F, H, (T*)yi);
+    else GSV_LAUNCH(interp_linear_kernel<T>, dim3(F), dim3(64), 0, s, (const T*)y, F0, F, H, (T*)yi);
     y = yi;
   }
   *y_out = y;
@@ -1016,15 +1058,15 @@ int gsv_vits_set_refer_sv(gsv_vits_t* h, const float* const* specs, const int* f
 namespace gsveng {
 // modules.WN.forward (modules.py:  in -> gate -> res/skip) on hb [F][H]: hb accumulates the residual halves, wout [F][H] the skip
 // halves; xin [F][2H] and acts [F][H] are scratch.  The two ways rows are masked, and where the in-layer bias comes from:
-//   sr != null (segmented flow): voice-row biases at voff + li * 2H (conv_voice), sr->seg_f keeps the gap rows of hb zero;
+//   sr != null (segmented flow, post layout): voice-row biases at voff + li * 2H (conv_voice), sr->seg_p keeps the gap rows of hb zero;
 //   Lm < F (wns1, models.py:1252-1258): rows >= Lm of hb are zeroed after each residual add.
 template <typename T>
 static int run_wn(gsv_vits* h, hipStream_t s, const WNW& w, int F, void* hb, void* xin, void* acts, void* wout, const SegRun* sr,
                   size_t voff, int Lm) {
   const int NL = (int)w.in.size(), H = w.in[0].cin;
-  const int* seg_f = sr ? sr->seg_f : nullptr;
+  const int* seg_f = sr ? sr->seg_p : nullptr;
   for (int li = 0; li < NL; ++li) {
-    GSV_RC(conv_voice(h, s, w.in[li], hb, F, xin, ConvOpt(), w.in_bias_eff[li], sr, voff + (size_t)li * 2 * H));   // xin feeds only the gate
+    GSV_RC(conv_voice(h, s, w.in[li], hb, F, xin, ConvOpt(), w.in_bias_eff[li], sr, voff + (size_t)li * 2 * H, seg_f));   // xin feeds only the gate
     GSV_LAUNCH(gate_kernel<T>, dim3(nblk((long long)F * H)), dim3(256), 0, s, (const T*)xin, (long long)F * H, H, (T*)acts);
     if (li < NL - 1) {
       ConvOpt ores; ores.cout = H; ores.w_row0 = 0; ores.accumulate = 1; ores.row_seg = seg_f;   // h += rs[:H]
@@ -1041,7 +1083,7 @@ static int run_wn(gsv_vits* h, hipStream_t s, const WNW& w, int F, void* hb, voi
 }
 
 // the v1/v2 decode: enc_p -> proj -> z_p -> flow reverse -> generator; sr != null: segmented (gap rows masked, per-segment voice
-// biases and noise keys, the gaps dropped from the waveform)
+// biases and noise keys, the gaps dropped from the waveform); everything after run_enc_p is in the post layout
 template <typename T>
 static int decode_wav(gsv_vits* h, hipStream_t s, const int32_t* codes, int Tc, const int32_t* phones, int L, double speed,
                       const float* noise, float noise_scale, uint64_t seed, float* wav, const SegRun* sr) {
@@ -1051,7 +1093,7 @@ static int decode_wav(gsv_vits* h, hipStream_t s, const int32_t* codes, int Tc, 
   GSV_RC(run_enc_p<T>(h, s, codes, Tc, phones, L, speed, &y, &F, sr));
   const size_t es = sizeof(T);
   const int H = c.hidden_channels, IC = c.inter_channels;
-  const int* seg_f = sr ? sr->seg_f : nullptr;
+  const int* seg_f = sr ? sr->seg_p : nullptr;
   float* stats;
   GSV_RC(need(h, "stats", (size_t)F * 2 * IC * 4, (void**)&stats));
   { ConvOpt of; of.out_f32 = 1; GSV_RC(conv(h, s, h->proj, y, H, F, stats, F, of)); }
@@ -1064,7 +1106,7 @@ static int decode_wav(gsv_vits* h, hipStream_t s, const int32_t* codes, int Tc, 
   GSV_RC(need(h, "wn_acts", (size_t)F * H * es, &acts));
   GSV_RC(need(h, "wn_out", (size_t)F * H * es, &wout));
   GSV_LAUNCH(zp_kernel<T>, dim3(nblk((long long)F * IC)), dim3(256), 0, s, stats, F, IC, noise, noise_scale, (unsigned long long)seed, (T*)z,
-             seg_f, sr ? sr->start : nullptr, sr ? sr->noff : nullptr, sr ? sr->seeds : nullptr, sr ? sr->lay->Fn : 0);
+             seg_f, sr ? sr->start : nullptr, sr ? sr->noff : nullptr, sr ? sr->seeds : nullptr, sr ? sr->post->Fn : 0);
   const int half = IC / 2;
   for (int fi = 3; fi >= 0; --fi) {
     FlowW& f = h->flows[fi];
@@ -1088,7 +1130,7 @@ static int decode_wav(gsv_vits* h, hipStream_t s, const int32_t* codes, int Tc, 
   void* gb[5];
   GSV_RC(gen_buffers(h, h->gen, "g", F, gb));
   void* cur = gb[3];
-  GSV_RC(conv_voice(h, s, h->conv_pre, z, F, cur, ConvOpt(), h->conv_pre_bias_eff, sr, h->voice_off_pre));
+  GSV_RC(conv_voice(h, s, h->conv_pre, z, F, cur, ConvOpt(), h->conv_pre_bias_eff, sr, h->voice_off_pre, seg_f));
   int Tn = F;
   GSV_RC(run_generator_stages(h, s, h->gen, gb, &cur, &Tn, seg_f ? sr->seg_up.data() : nullptr));
   float* wout_p = wav;                 // segmented: the padded waveform, then the gaps are dropped into wav
@@ -1097,7 +1139,7 @@ static int decode_wav(gsv_vits* h, hipStream_t s, const int32_t* codes, int Tc, 
     GSV_RC(conv(h, s, h->conv_post, cur, h->conv_post.cin, Tn, wout_p, Tn, op)); }
   if (seg_f) {
     const int up = Tn / F;
-    GSV_LAUNCH(compact_wav_kernel, dim3(nblk(Tn)), dim3(256), 0, s, (const float*)wout_p, seg_f, up, (long long)sr->lay->G * up,
+    GSV_LAUNCH(compact_wav_kernel, dim3(nblk(Tn)), dim3(256), 0, s, (const float*)wout_p, seg_f, up, (long long)sr->post->G * up,
                (long long)Tn, wav);
   }
   GSV_HIP(hipEventRecord(h->ev[2], s));
@@ -1198,10 +1240,15 @@ int gsv_vits_segment_gap(const gsv_vits_config* cfg) {
 
 int gsv_vits_segment_map(const gsv_vits_config* cfg, int n, const int* code_lens, const int* phone_lens, int level, int32_t* seg,
                          int64_t cap, int64_t* rows) {
+  return gsv_vits_segment_map_speed(cfg, n, code_lens, phone_lens, nullptr, level, seg, cap, rows);
+}
+
+int gsv_vits_segment_map_speed(const gsv_vits_config* cfg, int n, const int* code_lens, const int* phone_lens, const double* speeds,
+                               int level, int32_t* seg, int64_t cap, int64_t* rows) {
   GSV_REQUIRE(cfg && rows && cfg->n_ups >= 1 && cfg->n_ups <= 8, "vits_segment_map: bad argument");
   GSV_REQUIRE(level >= -1 && level <= cfg->n_ups, "vits_segment_map: level %d outside [-1, %d]", level, cfg->n_ups);
   SegLayout lay;
-  GSV_RC(seg_layout(*cfg, n, code_lens, phone_lens, &lay));
+  GSV_RC(seg_layout(*cfg, n, code_lens, phone_lens, speeds, &lay));
   long long up = 1;
   for (int i = 0; i < level; ++i) up *= cfg->up_rates[i];
   const long long nr = level < 0 ? lay.L : (long long)lay.F * up;
@@ -1210,7 +1257,7 @@ int gsv_vits_segment_map(const gsv_vits_config* cfg, int n, const int* code_lens
   GSV_REQUIRE(cap >= nr, "vits_segment_map: buffer holds %lld rows, need %lld", (long long)cap, nr);
   for (long long t = 0; t < nr; ++t) seg[t] = -1;
   for (int i = 0; i < n; ++i) {
-    const long long a = level < 0 ? lay.l0[i] : lay.f0[i] * up, len = level < 0 ? phone_lens[i] : 2LL * code_lens[i] * up;
+    const long long a = level < 0 ? lay.l0[i] : lay.f0[i] * up, len = level < 0 ? phone_lens[i] : lay.nf[i] * up;
     for (long long t = a; t < a + len; ++t) seg[t] = i;
   }
   return GSV_OK;
@@ -1247,6 +1294,13 @@ int gsv_vits_store_voice(gsv_vits_t* h, int slot) {
 int gsv_vits_decode_segments(gsv_vits_t* h, int n, const int32_t* codes, const int* code_lens, const int32_t* phones,
                              const int* phone_lens, const int* voice_slots, const uint64_t* seeds, const float* noise, float noise_scale,
                              float* wav, gsv_stream_t stream) {
+  return gsv_vits_decode_segments_speed(h, n, codes, code_lens, phones, phone_lens, voice_slots, seeds, nullptr, noise, noise_scale, wav,
+                                        stream);
+}
+
+int gsv_vits_decode_segments_speed(gsv_vits_t* h, int n, const int32_t* codes, const int* code_lens, const int32_t* phones,
+                                   const int* phone_lens, const int* voice_slots, const uint64_t* seeds, const double* speeds,
+                                   const float* noise, float noise_scale, float* wav, gsv_stream_t stream) {
   GSV_REQUIRE(h, "vits_decode_segments: null handle");
   GSV_REQUIRE(h->cfg.flavor == 0, "vits_decode_segments: this handle is a v3/v4 model (segmented decode covers v1/v2 only)");
   GSV_REQUIRE(h->finalized, "vits_decode_segments: handle not finalized");
@@ -1254,17 +1308,22 @@ int gsv_vits_decode_segments(gsv_vits_t* h, int n, const int32_t* codes, const i
   for (int i = 0; i < n; ++i)
     GSV_REQUIRE(voice_slots[i] >= 0 && voice_slots[i] < GSV_VITS_MAX_VOICES && h->voice_ok.size() && h->voice_ok[voice_slots[i]],
                 "vits_decode_segments: segment %d names voice slot %d, which holds no voice (gsv_vits_store_voice)", i, voice_slots[i]);
-  SegLayout lay;
-  GSV_RC(seg_layout(h->cfg, n, code_lens, phone_lens, &lay));
+  SegLayout lay, post;
+  GSV_RC(seg_layout(h->cfg, n, code_lens, phone_lens, nullptr, &lay));
+  GSV_RC(seg_layout(h->cfg, n, code_lens, phone_lens, speeds, &post));
+  const bool interp = post.nf != lay.nf;     // some segment changes its frame count: the post layout is a second one
   hipStream_t s = (hipStream_t)stream;
-  const int F = lay.F, L = lay.L;
-  // host image of every map, one upload: seg_f | seg_l | kr_f | kr_l | kr_x | src_code | src_phone | start | noff | slot
+  const int F = lay.F, L = lay.L, Fp = post.F;
+  // host image of every map, one upload: seg_f | seg_l | kr_f | kr_l | kr_x | src_code | src_phone | start | noff | slot, and with
+  // a second layout: | seg_p | start_pre | len_pre | len_post
   if (!h->seg_ev) GSV_HIP(hipEventCreateWithFlags(&h->seg_ev, hipEventDisableTiming));
   GSV_HIP(hipEventSynchronize(h->seg_ev));   // the previous call's upload (any stream) is done before its host image is rewritten
   GSV_HIP(hipStreamWaitEvent(s, h->ev[3], 0));   // the voice slots are stored
   std::vector<int>& m = h->seg_host;
   const size_t o_sf = 0, o_sl = o_sf + F, o_kf = o_sl + L, o_kl = o_kf + 2 * (size_t)F, o_kx = o_kl + 2 * (size_t)L,
-               o_sc = o_kx + 2 * (size_t)F, o_sp = o_sc + F, o_st = o_sp + L, o_no = o_st + n, o_vs = o_no + n, total = o_vs + n;
+               o_sc = o_kx + 2 * (size_t)F, o_sp = o_sc + F, o_st = o_sp + L, o_no = o_st + n, o_vs = o_no + n,
+               o_pf = o_vs + n, o_ps = o_pf + (interp ? Fp : 0), o_pi = o_ps + (interp ? n : 0), o_po = o_pi + (interp ? n : 0),
+               total = o_po + (interp ? n : 0);
   m.assign(total, -1);
   for (int t = 0; t < F; ++t) { m[o_kf + 2 * t] = t; m[o_kf + 2 * t + 1] = t + 1; m[o_kx + 2 * t] = 0; m[o_kx + 2 * t + 1] = 0; }
   for (int t = 0; t < L; ++t) { m[o_kl + 2 * t] = t; m[o_kl + 2 * t + 1] = t + 1; }
@@ -1281,7 +1340,11 @@ int gsv_vits_decode_segments(gsv_vits_t* h, int n, const int32_t* codes, const i
       m[o_kl + 2 * t] = l0; m[o_kl + 2 * t + 1] = l0 + nl;
       m[o_sp + t] = lay.p0[i] + (t - l0);
     }
-    m[o_st + i] = f0; m[o_no + i] = lay.fn0[i]; m[o_vs + i] = voice_slots[i];
+    m[o_st + i] = post.f0[i]; m[o_no + i] = post.fn0[i]; m[o_vs + i] = voice_slots[i];
+    if (interp) {
+      for (int t = post.f0[i]; t < post.f0[i] + post.nf[i]; ++t) m[o_pf + t] = i;
+      m[o_ps + i] = f0; m[o_pi + i] = nf; m[o_po + i] = post.nf[i];
+    }
   }
   h->seed_host.assign(seeds, seeds + n);
   int* dm;
@@ -1295,19 +1358,21 @@ int gsv_vits_decode_segments(gsv_vits_t* h, int n, const int32_t* codes, const i
   GSV_HIP(hipEventRecord(h->seg_ev, s));
   GSV_LAUNCH(gather_voice_kernel, dim3(n), dim3(256), 0, s, (const float*)h->voices, (const int*)(dm + o_vs), h->voice_len, vb);
   SegRun sr;
-  sr.lay = &lay;
+  sr.lay = &lay; sr.post = interp ? &post : &lay;
   sr.seg_f = dm + o_sf; sr.seg_l = dm + o_sl; sr.kr_f = dm + o_kf; sr.kr_l = dm + o_kl; sr.kr_x = dm + o_kx;
   sr.src_code = dm + o_sc; sr.src_phone = dm + o_sp; sr.start = dm + o_st; sr.noff = dm + o_no; sr.seeds = dseed; sr.bias = vb;
+  sr.seg_p = interp ? dm + o_pf : sr.seg_f;
+  if (interp) { sr.start_pre = dm + o_ps; sr.len_pre = dm + o_pi; sr.len_post = dm + o_po; }
   if (n == 1) {     // one segment is laid out exactly as gsv_vits_decode: no gaps, nothing to mask, its voice row as the bias
-    sr.seg_f = sr.seg_l = sr.kr_f = sr.kr_l = sr.kr_x = nullptr;
+    sr.seg_f = sr.seg_l = sr.seg_p = sr.kr_f = sr.kr_l = sr.kr_x = nullptr;
   }
   long long up = 1;
   for (int i = 0; i < h->cfg.n_ups && n > 1; ++i) {
     up *= h->cfg.up_rates[i];
     const std::string nm = "seg_up" + std::to_string(i);
     int* su;
-    GSV_RC(need(h, nm.c_str(), (size_t)F * up * 4, (void**)&su));
-    GSV_LAUNCH(expand_seg_kernel, dim3(nblk((long long)F * up)), dim3(256), 0, s, (const int*)sr.seg_f, (int)up, (long long)F * up, su);
+    GSV_RC(need(h, nm.c_str(), (size_t)Fp * up * 4, (void**)&su));
+    GSV_LAUNCH(expand_seg_kernel, dim3(nblk((long long)Fp * up)), dim3(256), 0, s, (const int*)sr.seg_p, (int)up, (long long)Fp * up, su);
     sr.seg_up.push_back(su);
   }
   GSV_HIP(hipEventRecord(h->ev[0], s));

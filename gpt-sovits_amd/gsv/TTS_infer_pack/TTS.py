@@ -870,11 +870,13 @@ class TTS:
         return [p[-i:] if i > 0 else p[:0] for p, i in zip(pred_list, idx_list)], idx_list
 
     def _synthesize_batch(self, item: dict, pred: List[torch.Tensor], pred_list: List[torch.Tensor], idx_list: List[int],
-                          bi: int, actual_seed: int, opts: dict, voice_refer: Tuple[List[torch.Tensor], dict]) -> List[torch.Tensor]:
+                          bi: int, actual_seed: int, opts: dict, voice_refer: Tuple[List[torch.Tensor], dict],
+                          have: Optional[List[Optional[torch.Tensor]]] = None) -> List[torch.Tensor]:
         """run()'s post-AR stage of one to_batch batch `bi` (reference TTS.py:1259-1299): the fragments of its sentences from
         the generated tokens (`pred`, `idx_list` = _kept_tokens(`pred_list`, ...)), with the voice of self.prompt_cache
         (v3/v4) / `voice_refer` = _voice_refer(voice) (v1/v2/v2Pro), speed_factor, parallel_infer, sample_steps and
-        inference_cfg_rate (v3/v4 only) of the resolved `opts`, and the seed actual_seed + bi."""
+        inference_cfg_rate (v3/v4 only) of the resolved `opts`, and the seed actual_seed + bi.  `have` (v1/v2/v2Pro at
+        speed_factor != 1 only): the sentences a shared pass already decoded, None where it left one out."""
         speed_factor, seed_b = opts["speed_factor"], actual_seed + bi
         refer, sv_kw = voice_refer
         frags: List[torch.Tensor] = []
@@ -900,6 +902,9 @@ class TTS:
             frags = list(torch.split(wav, cut))        # decode gives exactly 2 * up samples per token at speed 1
         else:
             for k, p in enumerate(pred):
+                if have is not None and have[k] is not None:
+                    frags.append(have[k])
+                    continue
                 frags.append(self.vits_model.decode(p.view(1, 1, -1), item["phones"][k].view(1, -1), refer,
                                                     speed=speed_factor, seed=seed_b, **sv_kw)[0, 0])
         return frags
@@ -1071,6 +1076,39 @@ class TTS:
             launches.append(cur)
         return launches
 
+    def plan_sovits_rows(self, plans: List[dict]) -> List[List[Tuple[int, int, int]]]:
+        """The waveform launches of run_batch(shared_sovits=True, shared_speed=True).  `plans[r]` = {"voice", "opts",
+        "folds", "sentences"}: folds as for plan_sovits, sentences[bi][k] the kept semantic tokens of sentence k of batch bi.
+        A row is one segment of SynthesizerTrn.decode_segments(speeds=...): (r, bi, -1) is a whole speed-1 fold, as
+        plan_sovits shares it; (r, bi, k), k >= 0, is sentence k of a request at another speed, which run() decodes on its
+        own with speed_factor and seed actual_seed + bi.  Folds and sentences without tokens, and v3 / v4, are left out.
+        A row of T tokens is 2T frames before the speed interpolation and F_s = int(2T / speed) + 1 after it and costs the
+        larger; a launch holds at most sovits_max_frames frames, gaps included, and at most VITS_MAX_VOICES distinct
+        voices; a row larger than that gets a launch of its own.  Returns the launches, lists of (r, bi, k) in that order."""
+        from .. import _lib
+        if getattr(self.configs, "use_vocoder", False):
+            return []
+        gap = self.vits_model.segment_gap()
+        launches, cur, frames, voices = [], [], 0, set()
+        for r, pl in enumerate(plans):
+            speed = pl["opts"]["speed_factor"]
+            key = self._voice_key(pl["voice"])
+            for bi, tokens in enumerate(pl["folds"]):
+                rows = [(-1, tokens)] if speed == 1.0 else list(enumerate(pl["sentences"][bi]))
+                for k, t in rows:
+                    if t <= 0:
+                        continue
+                    need = 2 * int(t) if speed == 1.0 else max(2 * int(t), int(2 * int(t) / speed) + 1)
+                    if cur and (frames + gap + need > self.sovits_max_frames or len(voices | {key}) > _lib.VITS_MAX_VOICES):
+                        launches.append(cur)
+                        cur, frames, voices = [], 0, set()
+                    frames += need + (gap if cur else 0)
+                    cur.append((r, bi, k))
+                    voices.add(key)
+        if cur:
+            launches.append(cur)
+        return launches
+
     cfm_max_rows = 32             # rows (chunks of T_chunk frames) of one shared flow-matching pass: where the measured cost per
                                   # row stops falling (DESIGN.md section 4f), about 0.7 GB of workspace at T_chunk = 934
 
@@ -1148,32 +1186,44 @@ class TTS:
             pl["kept"] = [self._kept_tokens(p, i, pl["no_prompt"]) for p, i in zip(pl["preds"], pl["idxs"])]
         self._wait_stream()
 
-    def _shared_sovits_stage(self, plans: List[dict]) -> None:
+    def _shared_sovits_stage(self, plans: List[dict], shared_speed: bool = False) -> None:
         """shared_sovits, v1 / v2 / v2Pro: every fold (request r, to_batch batch bi) that plan_sovits shares is one segment,
-        with r's voice, of a SynthesizerTrn.decode_segments pass.  Reads `kept`, `voice`, `opts`, `actual_seed`,
-        `data`.  Writes `folds` (kept tokens per batch, plan_sovits' input) and `frags[bi]` of every shared fold."""
+        with r's voice, of a SynthesizerTrn.decode_segments pass; with shared_speed, so is every sentence of a request at
+        another speed that plan_sovits_rows shares, at that speed.  Reads `kept`, `voice`, `opts`, `actual_seed`, `data`.
+        Writes `folds` and `sentences` (kept tokens per batch / per sentence, the planners' inputs), `frags[bi]` of every
+        shared fold and `frags[bi][k]` of every shared sentence (None where a sentence was left out)."""
         up = math.prod(self.vits_model.upsample_rates)
         for pl in plans:
-            pl["folds"] = [sum(int(p_.shape[0]) for p_ in pred) for pred, _ in pl["kept"]]
+            pl["sentences"] = [[int(p_.shape[0]) for p_ in pred] for pred, _ in pl["kept"]]
+            pl["folds"] = [sum(t) for t in pl["sentences"]]
         dev_voice: Dict[tuple, tuple] = {}          # one device refer list per distinct voice: one voice slot
-        for launch in self.plan_sovits(plans):
-            codes, phones, voices, seeds, cuts = [], [], [], [], []
-            for r, bi in launch:
+        launches = self.plan_sovits_rows(plans) if shared_speed else [[(r, bi, -1) for r, bi in launch]
+                                                                      for launch in self.plan_sovits(plans)]
+        for launch in launches:
+            codes, phones, voices, seeds, speeds, cuts = [], [], [], [], [], []
+            for r, bi, k in launch:
                 pl = plans[r]
                 pred = pl["kept"][bi][0]
-                keep = [k for k, p_ in enumerate(pred) if p_.shape[0] > 0]
-                codes.append(torch.cat([pred[k] for k in keep]).view(1, 1, -1))
-                phones.append(torch.cat([pl["data"][bi]["phones"][k] for k in keep]).view(1, -1))
+                keep = [k] if k >= 0 else [j for j, p_ in enumerate(pred) if p_.shape[0] > 0]
+                codes.append(torch.cat([pred[j] for j in keep]).view(1, 1, -1))
+                phones.append(torch.cat([pl["data"][bi]["phones"][j] for j in keep]).view(1, -1))
                 vk = self._voice_key(pl["voice"])
                 if vk not in dev_voice:
                     refer, sv_kw = self._voice_refer(pl["voice"])
                     dev_voice[vk] = (refer, sv_kw.get("sv_emb"))
                 voices.append(dev_voice[vk])
                 seeds.append(pl["actual_seed"] + bi)
+                speeds.append(pl["opts"]["speed_factor"] if k >= 0 else 1.0)
                 cuts.append([int(p_.shape[0]) * 2 * up for p_ in pred])
-            wavs = self.vits_model.decode_segments(codes, phones, voices, seeds)
-            for (r, bi), wav, cut in zip(launch, wavs, cuts):
-                plans[r]["frags"][bi] = list(torch.split(wav[0, 0], cut))
+            speed_kw = {} if all(v == 1.0 for v in speeds) else dict(speeds=speeds)
+            wavs = self.vits_model.decode_segments(codes, phones, voices, seeds, **speed_kw)
+            for (r, bi, k), wav, cut in zip(launch, wavs, cuts):
+                if k < 0:
+                    plans[r]["frags"][bi] = list(torch.split(wav[0, 0], cut))
+                else:
+                    if plans[r]["frags"][bi] is None:
+                        plans[r]["frags"][bi] = [None] * len(cut)
+                    plans[r]["frags"][bi][k] = wav[0, 0]
         self.vits_model.invalidate_refer()          # the engine's cached reference terms are the last slot's voice
 
     def _shared_cfm_stage(self, plans: List[dict]) -> None:
@@ -1227,10 +1277,10 @@ class TTS:
         with self._with_prompt_cache(dict(pl["voice"])) as voice:
             voice_refer = self._voice_refer(voice)
             for bi, item in enumerate(pl["data"]):
-                if pl["frags"][bi] is None:
+                if pl["frags"][bi] is None or any(f is None for f in pl["frags"][bi]):
                     pred, idx_list = pl["kept"][bi]
                     pl["frags"][bi] = self._synthesize_batch(item, pred, pl["preds"][bi], idx_list, bi, pl["actual_seed"], o,
-                                                             voice_refer)
+                                                             voice_refer, have=pl["frags"][bi])
             self._wait_stream()
             return self.audio_postprocess(pl["frags"], sr, pl["index"], o["speed_factor"], o["split_bucket"],
                                           o["fragment_interval"], o["super_sampling"])
@@ -1247,7 +1297,8 @@ class TTS:
         torch.cuda.current_stream(self.configs.device).synchronize()
 
     @torch.no_grad()
-    def run_batch(self, requests: List[dict], shared_sovits: bool = False, shared_cfm: bool = False) -> List[Tuple[int, np.ndarray]]:
+    def run_batch(self, requests: List[dict], shared_sovits: bool = False, shared_cfm: bool = False,
+                  shared_speed: bool = False) -> List[Tuple[int, np.ndarray]]:
         """Several requests, each with its own reference voice, through shared AR decodes.  Each request dict takes the
         keys run() accepts plus an optional "voice" (make_voice); without one it uses its ref_audio_path / prompt_text
         (through make_voice's LRU) or the current prompt cache.  Returns one (sr, int16 audio) per request, in order: what
@@ -1255,7 +1306,9 @@ class TTS:
         shared_sovits=True: v1 / v2 / v2Pro / v2ProPlus requests at speed 1 take their waveforms from shared segmented passes
         over all voices (_shared_sovits_stage) instead of one decode per to_batch batch.  shared_cfm=True: v3 / v4
         parallel_infer requests take their flow-matching stage from shared passes over all voices' chunks (_shared_cfm_stage).
-        Neither keyword changes anything for the other model family."""
+        shared_speed=True (with shared_sovits=True): the sentences of v1 / v2 / v2Pro / v2ProPlus requests at speed_factor != 1
+        join the same segmented passes, each at its own speed, instead of one decode per sentence.
+        No keyword changes anything for the other model family."""
         if self.t2s_model is None or self.vits_model is None:
             raise RuntimeError("init_t2s_weights / init_vits_weights first")
         self.stop_flag = False
@@ -1263,7 +1316,7 @@ class TTS:
         self._ar_stage(plans)
         sr = self._output_sr()
         if shared_sovits and not self.configs.use_vocoder:
-            self._shared_sovits_stage(plans)
+            self._shared_sovits_stage(plans, shared_speed=shared_speed)
         if shared_cfm and self.configs.use_vocoder:
             self._shared_cfm_stage(plans)
         return [self._finish_request(pl, sr) for pl in plans]

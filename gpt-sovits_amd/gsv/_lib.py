@@ -103,9 +103,14 @@ _SIGS = {
     "gsv_vits_decode_segments": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int),
                                            C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.c_void_p, C.c_float, C.c_void_p,
                                            C.c_void_p]),
+    "gsv_vits_decode_segments_speed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int),
+                                                 C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.c_void_p,
+                                                 C.c_float, C.c_void_p, C.c_void_p]),
     "gsv_vits_segment_gap": (C.c_int, [C.POINTER(VitsConfig)]),
     "gsv_vits_segment_map": (C.c_int, [C.POINTER(VitsConfig), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
                                        C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64)]),
+    "gsv_vits_segment_map_speed": (C.c_int, [C.POINTER(VitsConfig), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                             C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64)]),
     "gsv_vocoder_create": (C.c_int, [C.POINTER(VocoderConfig), C.c_int, C.POINTER(C.c_void_p)]),
     "gsv_vocoder_destroy": (None, [C.c_void_p]),
     "gsv_vocoder_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),

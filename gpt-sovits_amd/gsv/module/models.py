@@ -179,12 +179,16 @@ class SynthesizerTrn:
 
     @torch.no_grad()
     def decode_segments(self, codes_list, text_list, voices, seeds, noise_scale: float = 0.5,
-                        noise: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
-        """Segmented decode (speed 1): segment s = (codes_list[s] [1,1,T_s], text_list[s] [1,L_s], voices[s], seeds[s]) in one
+                        noise: Optional[Sequence[torch.Tensor]] = None,
+                        speeds: Optional[Sequence[float]] = None) -> List[torch.Tensor]:
+        """Segmented decode: segment s = (codes_list[s] [1,1,T_s], text_list[s] [1,L_s], voices[s], seeds[s]) in one
         pass of enc_p, flow and generator (gsv_vits_decode_segments).  A voice is (refer, sv_emb) as taken by `decode`
         (sv_emb None except for v2Pro / v2ProPlus); distinct voices are stored into slots once per call.  `noise`
         (optional) holds one [inter, 2T_s] draw per segment.  Returns one waveform [1, 1, 2T_s * prod(upsample_rates)] per
-        segment, what `decode(codes_list[s], text_list[s], *voices[s], noise_scale, seed=seeds[s])` returns."""
+        segment, what `decode(codes_list[s], text_list[s], *voices[s], noise_scale, seed=seeds[s])` returns.
+        `speeds` (optional, one finite positive value per segment; gsv_vits_decode_segments_speed): segment s is decoded at
+        `speed=speeds[s]`, so it has F_s = 2T_s frames at speed 1 and int(2T_s / speeds[s]) + 1 otherwise; its noise is
+        [inter, F_s] and its waveform [1, 1, F_s * prod(upsample_rates)]."""
         if not self._loaded:
             raise RuntimeError("load_state_dict() first")
         n = len(codes_list)
@@ -195,6 +199,15 @@ class SynthesizerTrn:
         T = [int(c.shape[-1]) for c in codes_list]
         L = [int(t.shape[-1]) for t in text_list]
         up = math.prod(self.upsample_rates)
+        if speeds is None:
+            Fs = [2 * t for t in T]
+        else:
+            if len(speeds) != n:
+                raise ValueError("decode_segments: one speed per segment")
+            speeds = [float(v) for v in speeds]
+            if any(not math.isfinite(v) or v <= 0 for v in speeds):
+                raise ValueError("decode_segments: every speed must be finite and positive")
+            Fs = [2 * t if v == 1 else int(2 * t / v) + 1 for t, v in zip(T, speeds)]      # as in decode (models.py:226-228)
         self.decode_segments_calls += 1
         with torch.cuda.device(self.device):
             slot_of, slots = {}, []
@@ -213,20 +226,26 @@ class SynthesizerTrn:
             tx = torch.cat([t.reshape(-1) for t in text_list]).to(self.device, torch.int32).contiguous()
             nz = None
             if noise is not None:
-                nz = torch.cat([z.reshape(self.inter_channels, 2 * t).to(self.device, torch.float32) for z, t in zip(noise, T)],
+                nz = torch.cat([z.reshape(self.inter_channels, f).to(self.device, torch.float32) for z, f in zip(noise, Fs)],
                                dim=1).contiguous()
-            wav = torch.empty(2 * sum(T) * up, dtype=torch.float32, device=self.device)
+            wav = torch.empty(sum(Fs) * up, dtype=torch.float32, device=self.device)
             cl, pl = (C.c_int * n)(*T), (C.c_int * n)(*L)
             vs = (C.c_int * n)(*slots)
             sd = (C.c_uint64 * n)(*[int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds])
             self.stream.wait_stream(torch.cuda.current_stream(self.device))
-            _lib.check(_lib.lib().gsv_vits_decode_segments(self._h, n, cd.data_ptr(), cl, tx.data_ptr(), pl, vs, sd,
-                                                           nz.data_ptr() if nz is not None else None, float(noise_scale),
-                                                           wav.data_ptr(), C.c_void_p(self.stream.cuda_stream)),
-                       "gsv_vits_decode_segments")
+            nzp = nz.data_ptr() if nz is not None else None
+            if speeds is None:
+                _lib.check(_lib.lib().gsv_vits_decode_segments(self._h, n, cd.data_ptr(), cl, tx.data_ptr(), pl, vs, sd, nzp,
+                                                               float(noise_scale), wav.data_ptr(),
+                                                               C.c_void_p(self.stream.cuda_stream)), "gsv_vits_decode_segments")
+            else:
+                _lib.check(_lib.lib().gsv_vits_decode_segments_speed(self._h, n, cd.data_ptr(), cl, tx.data_ptr(), pl, vs, sd,
+                                                                     (C.c_double * n)(*speeds), nzp, float(noise_scale),
+                                                                     wav.data_ptr(), C.c_void_p(self.stream.cuda_stream)),
+                           "gsv_vits_decode_segments_speed")
             self.stream.synchronize()
         out = wav.to(self.dtype)
-        return [p.view(1, 1, -1) for p in torch.split(out, [2 * t * up for t in T])]
+        return [p.view(1, 1, -1) for p in torch.split(out, [f * up for f in Fs])]
 
     @torch.no_grad()
     def extract_latent(self, x: torch.Tensor) -> torch.Tensor:

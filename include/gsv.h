@@ -191,7 +191,7 @@ int gsv_vits_decode_encp(gsv_vits_t* h, const int32_t* codes, int T, const int32
  * ge = mean_r ge_r; the MRTE receives ge_to512(ge). */
 int gsv_vits_set_refer_sv(gsv_vits_t* h, const float* const* specs, const int* frames, int bins, const float* const* sv_embs,
                           int n_refs, gsv_stream_t stream);
-/* Segmented decode (v1 / v2 / v2Pro / v2ProPlus, speed 1): n independent sequences, each with its own voice and seed, in one
+/* Segmented decode (v1 / v2 / v2Pro / v2ProPlus): n independent sequences, each with its own voice and seed, in one
  * pass of enc_p, flow and generator.  The library lays the segments back to back with G zero "gap" frames between them
  * (G = gsv_vits_segment_gap(cfg), G * prod(up_rates[:i]) rows after upsampling stage i, G rows between phone runs); every
  * tensor a conv reads keeps its gap rows at 0 and attention is block-diagonal, so segment s yields what gsv_vits_decode of
@@ -200,17 +200,32 @@ int gsv_vits_set_refer_sv(gsv_vits_t* h, const float* const* specs, const int* f
  * (0 <= slot < GSV_VITS_MAX_VOICES).  gsv_vits_decode_segments: codes [dev] int32 [sum code_lens], phones [dev] int32
  * [sum phone_lens], both packed without gaps; code_lens / phone_lens / voice_slots / seeds [host] [n]; noise [dev] fp32
  * [inter][sum 2 code_lens] or NULL (segment s draws the counter RNG keyed by seeds[s]); wav [dev] fp32, segment s's
- * 2 * code_lens[s] * prod(up_rates) samples back to back. */
+ * 2 * code_lens[s] * prod(up_rates) samples back to back.
+ * gsv_vits_decode_segments_speed: the same with speeds [host] [n] (each finite and > 0; NULL = all 1, which is
+ * gsv_vits_decode_segments).  Two layouts share the gap G and the phone axis: the pre layout (2 * code_lens[s] frames per
+ * segment: codebook gather, enc_ssl, MRTE, enc2) and the post layout (F_s frames: proj, flow, generator, wav), F_s =
+ * 2 * code_lens[s] at speed 1, else (int)(2 * code_lens[s] / speeds[s]) + 1 as in gsv_vits_decode.  One kernel interpolates
+ * each segment from its own pre rows into its post rows (gap rows written as zeros); when no segment changes its frame count
+ * the post layout is the pre layout and nothing extra runs.  noise is [inter][sum F_s], wav holds segment s's
+ * F_s * prod(up_rates) samples back to back; segment s yields what gsv_vits_decode(speed = speeds[s], seed = seeds[s]) yields.
+ * A speed that is not finite or <= 0, or a layout of 2^24 rows or more, is an error code. */
 #define GSV_VITS_MAX_VOICES 128
 int gsv_vits_store_voice(gsv_vits_t* h, int slot);
 int gsv_vits_decode_segments(gsv_vits_t* h, int n, const int32_t* codes, const int* code_lens, const int32_t* phones,
                              const int* phone_lens, const int* voice_slots, const uint64_t* seeds, const float* noise,
                              float noise_scale, float* wav, gsv_stream_t stream);
+int gsv_vits_decode_segments_speed(gsv_vits_t* h, int n, const int32_t* codes, const int* code_lens, const int32_t* phones,
+                                   const int* phone_lens, const int* voice_slots, const uint64_t* seeds, const double* speeds,
+                                   const float* noise, float noise_scale, float* wav, gsv_stream_t stream);
 /* host-only planning helpers (no device needed): the gap G in frames, and the segment id (-1 = gap) of every row at `level`
- * (-1 = phones, 0 = frames, i = after upsampling stage i); *rows = row count (seg may be NULL to query it). */
+ * (-1 = phones, 0 = frames, i = after upsampling stage i); *rows = row count (seg may be NULL to query it).
+ * gsv_vits_segment_map_speed is the map of the post layout of gsv_vits_decode_segments_speed (level >= 0: frames after the
+ * speed interpolation x the upsampling so far; level -1: phones, unchanged). */
 int gsv_vits_segment_gap(const gsv_vits_config* cfg);
 int gsv_vits_segment_map(const gsv_vits_config* cfg, int n, const int* code_lens, const int* phone_lens, int level, int32_t* seg,
                          int64_t cap, int64_t* rows);
+int gsv_vits_segment_map_speed(const gsv_vits_config* cfg, int n, const int* code_lens, const int* phone_lens, const double* speeds,
+                               int level, int32_t* seg, int64_t cap, int64_t* rows);
 /* per-kernel timing hooks for bench.py: device ms of the last decode's generator section */
 int gsv_vits_last_timing(gsv_vits_t* h, float* total_ms, float* generator_ms);
 

@@ -229,8 +229,12 @@ struct ConvPairArgs {
   float scale = 1.f;
   int accumulate = 0;
 };
-bool conv_pair_eligible(int dtype, int C, int taps, int dil, int T);
+// supported: a kernel exists for the shape (what gsv_op_conv_pair / gsv_op_conv_pair_seg accept; C = 16 / 32, and 64 unmasked).
+// eligible: the generator runs the pair as that kernel (supported, and at C = 64 T >= 16 384 unless GSV_NO_CONV_PAIR64 is set).
+bool conv_pair_supported(int dtype, int C, int taps, int dil, int T, bool seg);
+bool conv_pair_eligible(int dtype, int C, int taps, int dil, int T, bool seg);
 int launch_conv_pair(const ConvPairArgs& a, hipStream_t s);
+int launch_conv_pair64(const ConvPairArgs& a, hipStream_t s);   // conv_pair64.hip: C = 64, reached through launch_conv_pair
 // the pair of a segmented decode: row_seg [T] int32, -1 = gap row (ConvArgs::row_seg).  Gap rows of the intermediate and of y are
 // 0, as after convs1 -> row pass -> convs2 -> row pass.  row_seg travels beside ConvPairArgs, whose layout the unmasked kernels keep.
 int launch_conv_pair_seg(const ConvPairArgs& a, const int* row_seg, hipStream_t s);

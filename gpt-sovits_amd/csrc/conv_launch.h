@@ -1,5 +1,5 @@
 // Host side of the conv / GEMM launchers (gemm_sk.hip, conv_wide.hip, gemm_lds.hip, conv_narrow.hip, conv_lds.hip, conv_gemm.hip,
-// conv_pair.hip): the A/B switches, the one routed launch, the run-time flag -> template argument dispatcher, the operand
+// conv_pair.hip, conv_pair64.hip): the A/B switches, the one routed launch, the run-time flag -> template argument dispatcher, the operand
 // alignment test and the in-kernel stamp buffer.  Nothing here is device code.
 #pragma once
 #include <stdlib.h>
@@ -48,6 +48,7 @@ struct ConvSwitches {
   int half_waves = (int)env_number("GSV_CONV_HALF_WAVES", 8);  // 4: the 4-wave geometry of the 128-step tiles
   int tile_waves = (int)env_number("GSV_CONV_TILE_WAVES", 8);  // 4: the 4-wave geometry of the 256-step tiles
   bool no_conv_pair = env_switch("GSV_NO_CONV_PAIR");          // set: conv_pair_eligible is false, the engines launch a pair's two convs
+  bool no_conv_pair64 = env_switch("GSV_NO_CONV_PAIR64");      // set: the 64-channel stage keeps a pair's two conv_narrow launches
   int pair_per_cu = std::max(1, (int)env_number("GSV_PAIR_PER_CU", 3));       // resident conv_pair workgroups per CU at most
 };
 inline const ConvSwitches& conv_switches() {

@@ -263,19 +263,30 @@ int launch_pair_taps(const ConvPairArgs& a, const int* row_seg, hipStream_t s) {
 
 }  // namespace
 
-bool conv_pair_eligible(int dtype, int C, int taps, int dil, int T) {
-  // taps: exactly the instantiated kernels (launch_pair_taps); any other count would read tap slabs past w1 / w2
+bool conv_pair_supported(int dtype, int C, int taps, int dil, int T, bool seg) {
+  // taps: exactly the instantiated kernels (launch_pair_taps, launch_conv_pair64); any other count would read tap slabs past w1 / w2
   const bool inst = taps == 3 || taps == 5 || taps == 7 || taps == 9 || taps == 11;
-  return !conv_switches().no_conv_pair && dtype == GSV_F16 && (C == 16 || C == 32) && inst && dil >= 1 && ((taps - 1) / 2) * dil <= 25 && T >= 256;
+  // C = 64 (conv_pair64.hip) has no masked instantiation: a segmented decode keeps its two convs there
+  const bool chan = C == 16 || C == 32 || (C == 64 && !seg);
+  return !conv_switches().no_conv_pair && dtype == GSV_F16 && chan && inst && dil >= 1 && ((taps - 1) / 2) * dil <= 25 && T >= 256;
+}
+
+bool conv_pair_eligible(int dtype, int C, int taps, int dil, int T, bool seg) {
+  if (!conv_pair_supported(dtype, C, taps, dil, T, seg)) return false;
+  // the 64-channel pair takes over where the persistent narrow conv does (conv_narrow.hip narrow_channels): below it the two
+  // convs are conv_lds launches that fill the GPU with small tiles, and one workgroup per CU of 128 / 256-step tiles does not
+  if (C == 64) return !conv_switches().no_conv_pair64 && T >= 16384;
+  return true;
 }
 
 namespace {
 int launch_conv_pair_any(const ConvPairArgs& a, const int* row_seg, hipStream_t s) {
   GSV_REQUIRE(a.x && a.y && a.w1 && a.w2 && a.b1 && a.b2, "conv_pair: null operand");
-  GSV_REQUIRE(conv_pair_eligible(GSV_F16, a.C, a.taps, a.dil, a.T) || conv_switches().no_conv_pair, "conv_pair: shape C=%d taps=%d dil=%d T=%d not supported",
+  GSV_REQUIRE(conv_pair_supported(GSV_F16, a.C, a.taps, a.dil, a.T, row_seg != nullptr) || conv_switches().no_conv_pair, "conv_pair: shape C=%d taps=%d dil=%d T=%d not supported",
               a.C, a.taps, a.dil, a.T);
   GSV_REQUIRE(a.ldx % 8 == 0 && a.ldy % 4 == 0 && ((uintptr_t)a.x % 16) == 0 && ((uintptr_t)a.w1 % 16) == 0 && ((uintptr_t)a.w2 % 16) == 0,
               "conv_pair: operands must be 16-byte aligned");
+  if (a.C == 64) return launch_conv_pair64(a, s);
   return a.C == 16 ? launch_pair_taps<16>(a, row_seg, s) : launch_pair_taps<32>(a, row_seg, s);
 }
 }  // namespace

@@ -180,8 +180,8 @@ int run_generator_stages(gsv_vits* h, hipStream_t s, const GenW& g, void* const*
         // segmented: the masked pair zeroes the gap rows of its LDS intermediate and of its output itself (conv_pair.hip, SEG);
         // GSV_NO_SEG_PAIR=1 is the A/B switch back to the two convs with their row passes
         static const bool no_seg_pair = getenv("GSV_NO_SEG_PAIR") != nullptr;
-        if (!big && !(seg_o && no_seg_pair) && c1.b && c2.b && c1.taps == c2.taps && conv_pair_eligible(h->dtype, ch, c1.taps, dil, Tout)) {
-          // narrow stages: the pair in one kernel, the intermediate tensor never leaves the CU (conv_pair.hip)
+        if (!big && !(seg_o && no_seg_pair) && c1.b && c2.b && c1.taps == c2.taps && conv_pair_eligible(h->dtype, ch, c1.taps, dil, Tout, seg_o != nullptr)) {
+          // narrow stages: the pair in one kernel, the intermediate tensor never leaves the CU (conv_pair.hip; 64 channels: conv_pair64.hip)
           ConvPairArgs pa;
           pa.x = (const _Float16*)xr; pa.w1 = (const _Float16*)c1.w; pa.b1 = c1.b; pa.w2 = (const _Float16*)c2.w; pa.b2 = c2.b;
           pa.T = Tout; pa.C = ch; pa.taps = c1.taps; pa.dil = dil; pa.ldx = ch; pa.ldy = ch;

@@ -327,7 +327,7 @@ int gsv_op_magnitude(const float* re_im, int T, int bins, float eps, int frame_l
 
 int gsv_op_conv_pair(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y, int T, int C, int taps,
                      int dil, float scale, int accumulate, gsv_stream_t stream) {
-  GSV_REQUIRE(gsv::conv_pair_eligible(GSV_F16, C, taps, dil, T), "op_conv_pair: C must be 16 or 32, taps 3, 5, 7, 9 or 11, (taps - 1) / 2 * dil <= 25, T >= 256");
+  GSV_REQUIRE(gsv::conv_pair_supported(GSV_F16, C, taps, dil, T, false), "op_conv_pair: C must be 16, 32 or 64, taps 3, 5, 7, 9 or 11, (taps - 1) / 2 * dil <= 25, T >= 256");
   gsv::ConvPairArgs a;
   a.x = (const _Float16*)x; a.w1 = (const _Float16*)w1; a.b1 = b1; a.w2 = (const _Float16*)w2; a.b2 = b2; a.y = (_Float16*)y;
   a.T = T; a.C = C; a.taps = taps; a.dil = dil; a.ldx = C; a.ldy = C; a.scale = scale; a.accumulate = accumulate;
@@ -337,7 +337,7 @@ int gsv_op_conv_pair(const void* x, const void* w1, const float* b1, const void*
 int gsv_op_conv_pair_seg(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y, int T, int C, int taps,
                          int dil, float scale, int accumulate, const int32_t* row_seg, gsv_stream_t stream) {
   GSV_REQUIRE(row_seg, "op_conv_pair_seg: row_seg is null (gsv_op_conv_pair is the unmasked pair)");
-  GSV_REQUIRE(gsv::conv_pair_eligible(GSV_F16, C, taps, dil, T), "op_conv_pair_seg: C must be 16 or 32, taps 3, 5, 7, 9 or 11, (taps - 1) / 2 * dil <= 25, T >= 256");
+  GSV_REQUIRE(gsv::conv_pair_supported(GSV_F16, C, taps, dil, T, true), "op_conv_pair_seg: C must be 16 or 32, taps 3, 5, 7, 9 or 11, (taps - 1) / 2 * dil <= 25, T >= 256");
   gsv::ConvPairArgs a;
   a.x = (const _Float16*)x; a.w1 = (const _Float16*)w1; a.b1 = b1; a.w2 = (const _Float16*)w2; a.b2 = b2; a.y = (_Float16*)y;
   a.T = T; a.C = C; a.taps = taps; a.dil = dil; a.ldx = C; a.ldy = C; a.scale = scale; a.accumulate = accumulate;

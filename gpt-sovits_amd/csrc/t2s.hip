@@ -16,6 +16,7 @@
 //    split-K across the waves of a workgroup with an LDS combine (no global partials), then logits + a one-wave-per-row
 //    sampling kernel; the step is captured once per batch size and replayed as one hipGraph.
 #include <math.h>
+#include <string.h>
 #include <stdlib.h>
 #include <algorithm>
 #include <string>
@@ -425,8 +426,9 @@ __global__ __launch_bounds__(64) void sample_step_kernel(const float* __restrict
   if (sp.noise)
     nrow = sp.noise + ((long long)step * sp.noise_rows + (sp.noise_rows > 1 ? b : 0)) * V;
   int smp, amx;
-  sample_row<NPL>(logits + (long long)b * V, V, Veff, yrow, prev_len, sp.top_k, sp.top_p, sp.temperature,
-                  sp.rep_penalty, nrow, sp.rng_seed[b], sp.rng_row[b], step, seen, &smp, &amx);
+  const RowSampling rs = row_sampling_of(sp, b);
+  sample_row<NPL>(logits + (long long)b * V, V, Veff, yrow, prev_len, rs.top_k, rs.top_p, rs.temperature,
+                  rs.rep_penalty, nrow, sp.rng_seed[b], sp.rng_row[b], step, seen, &smp, &amx);
   if (sp.dump)
     for (int v = lane; v < V; v += 64) sp.dump[((long long)step * gridDim.x + b) * V + v] = logits[(long long)b * V + v];
   if (sp.drawn && lane == 0) { int* dr = sp.drawn + ((long long)step * gridDim.x + b) * 2; dr[0] = smp; dr[1] = amx; }
@@ -458,10 +460,15 @@ __global__ __launch_bounds__(64) void sample_only_kernel(const float* __restrict
                                                          const int* __restrict__ prev, int prev_len, int top_k, float top_p,
                                                          float temperature, float rp, const float* __restrict__ noise,
                                                          unsigned long long seed, int step, int* __restrict__ sampled,
-                                                         int* __restrict__ argmax_tok) {
+                                                         int* __restrict__ argmax_tok,
+                                                         const RowSampling* __restrict__ rows /* [B] or null */) {
   extern __shared__ unsigned char seen[];
   const int b = blockIdx.x;
   int smp, amx;
+  if (rows) {
+    const RowSampling rs = load_row_sampling(rows, b);
+    top_k = rs.top_k; top_p = rs.top_p; temperature = rs.temperature; rp = rs.rep_penalty;
+  }
   sample_row<NPL>(logits + (long long)b * V, V, Veff, prev + (long long)b * prev_len, prev_len, top_k, top_p, temperature,
                   rp, noise ? noise + (long long)b * V : nullptr, seed, b, step, seen, &smp, &amx);
   if (threadIdx.x == 0) { sampled[b] = smp; argmax_tok[b] = amx; }
@@ -651,6 +658,10 @@ int decode_begin(gsv_t2s* h, const gsv_sampling_params* sp, const float* noise, 
   p.plen = h->d_plen; p.rng_seed = h->d_rng_seed; p.rng_row = h->d_rng_row;
   p.force = h->dbg_force; p.dump = h->dbg_dump; p.drawn = h->dbg_drawn;
   h->dbg_force = nullptr; h->dbg_dump = nullptr; h->dbg_drawn = nullptr;
+  // per-row sampling parameters: gsv_t2s_set_row_sampling's for this call (the four scalars above are then unused), else
+  // null.  row_sampling_next stays until gsv_t2s_decode returns: a fallback re-run of the batch reads the same device array.
+  const std::vector<gsv_row_sampling_t>& rsn = h->row_sampling_next;
+  p.row_sampling = rsn.empty() ? nullptr : h->d_row_sampling;
   // counter-RNG keys of the rows: gsv_t2s_set_row_rng's for this call, else (seed, b) -- the draws of a batch without keys
   const bool keyed = !h->rng_seed_next.empty();
   const int nkeys = (int)h->rng_seed_next.size();
@@ -662,6 +673,13 @@ int decode_begin(gsv_t2s* h, const gsv_sampling_params* sp, const float* noise, 
   }
   h->rng_seed_next.clear(); h->rng_row_next.clear();
   GSV_REQUIRE(!keyed || nkeys == h->B, "t2s_decode: gsv_t2s_set_row_rng gave %d keys for a batch of %d rows", nkeys, h->B);
+  GSV_REQUIRE(rsn.empty() || (int)rsn.size() == h->B, "t2s_decode: gsv_t2s_set_row_sampling gave %d rows for a batch of %d rows",
+              (int)rsn.size(), h->B);
+  if (!rsn.empty() && (rsn.size() != h->row_sampling_up.size() ||
+                       memcmp(rsn.data(), h->row_sampling_up.data(), rsn.size() * sizeof(gsv_row_sampling_t)) != 0)) {
+    GSV_HIP(hipMemcpyAsync(h->d_row_sampling, rsn.data(), rsn.size() * sizeof(gsv_row_sampling_t), hipMemcpyHostToDevice, s));
+    h->row_sampling_up = rsn;
+  }
   GSV_HIP(hipMemcpyAsync(h->d_sp, &p, sizeof(p), hipMemcpyHostToDevice, s));
   if (seeds != h->rng_seed_up || rows != h->rng_row_up) {
     GSV_HIP(hipMemcpyAsync(h->d_rng_seed, seeds.data(), (size_t)h->B * 8, hipMemcpyHostToDevice, s));
@@ -1031,6 +1049,7 @@ int gsv_t2s_finalize(gsv_t2s_t* h) {
   GSV_RC(dev_alloc(h, (void**)&h->d_plen, 2 * B * 4));
   GSV_RC(dev_alloc(h, (void**)&h->d_rng_seed, B * 8));
   GSV_RC(dev_alloc(h, (void**)&h->d_rng_row, B * 4));
+  GSV_RC(dev_alloc(h, (void**)&h->d_row_sampling, B * sizeof(RowSampling)));
   GSV_RC(dev_alloc(h, (void**)&h->d_sp, sizeof(StepParams)));
   GSV_HIP(hipHostMalloc((void**)&h->h_pinned, 64));
   GSV_RC(dev_alloc(h, (void**)&h->ybuf, B * d * 4));
@@ -1052,9 +1071,33 @@ int gsv_t2s_set_row_rng(gsv_t2s_t* h, const uint64_t* seeds, const int32_t* rows
   return GSV_OK;
 }
 
+// the value checks of gsv_t2s_set_row_sampling and gsv_op_sample_rows
+static int check_row_sampling(const char* who, const gsv_row_sampling_t* rows, int B) {
+  for (int b = 0; b < B; ++b) {
+    const gsv_row_sampling_t& r = rows[b];
+    GSV_REQUIRE(r.top_k >= 0, "%s: row %d: top_k %d must be >= 0", who, b, r.top_k);
+    GSV_REQUIRE(r.top_p > 0.f && r.top_p <= 1.f, "%s: row %d: top_p %g must be in (0, 1]", who, b, (double)r.top_p);
+    GSV_REQUIRE(isfinite(r.temperature) && r.temperature >= 0.f, "%s: row %d: temperature %g must be finite and >= 0", who,
+                b, (double)r.temperature);
+    GSV_REQUIRE(isfinite(r.repetition_penalty) && r.repetition_penalty > 0.f,
+                "%s: row %d: repetition_penalty %g must be finite and > 0", who, b, (double)r.repetition_penalty);
+  }
+  return GSV_OK;
+}
+
+int gsv_t2s_set_row_sampling(gsv_t2s_t* h, const gsv_row_sampling_t* rows, int B) {
+  GSV_REQUIRE(h && h->finalized, "t2s_set_row_sampling: handle not finalized");
+  GSV_REQUIRE(rows && B >= 1 && B <= h->max_batch, "t2s_set_row_sampling: bad argument (B = %d)", B);
+  GSV_RC(check_row_sampling("t2s_set_row_sampling", rows, B));
+  h->row_sampling_next.assign(rows, rows + B);
+  return GSV_OK;
+}
+
 int gsv_t2s_decode(gsv_t2s_t* h, const gsv_sampling_params* sp, const float* noise, int noise_rows,
                    int32_t* out_tokens, int32_t* out_len, int* steps_run, gsv_stream_t stream) {
   GSV_REQUIRE(h && h->finalized && h->B > 0, "t2s_decode: call gsv_t2s_prefill first");
+  // the per-row sampling parameters are this call's alone, whatever becomes of it
+  struct Clear { gsv_t2s_t* h; ~Clear() { h->row_sampling_next.clear(); } } clear{h};
   GSV_REQUIRE(sp && out_tokens && out_len, "t2s_decode: null argument");
   GSV_REQUIRE(sp->max_steps >= 1, "t2s_decode: max_steps must be >= 1");
   GSV_REQUIRE(noise == nullptr || noise_rows == 1 || noise_rows == h->B, "t2s_decode: noise_rows must be 1 or B");
@@ -1156,9 +1199,33 @@ int gsv_op_sample(const float* logits, int B, int vocab, int vocab_eff, const in
   return with_npl(vocab, [&](auto npl) -> int {
     GSV_LAUNCH(sample_only_kernel<decltype(npl)::value>, dim3(B), dim3(64), lds, s, logits, vocab, vocab_eff, prev, prev_len,
                sp->top_k, sp->top_p, sp->temperature, sp->repetition_penalty, noise, (unsigned long long)sp->seed, step, sampled,
-               argmax_tok);
+               argmax_tok, (const RowSampling*)nullptr);
     return GSV_OK;
   });
+}
+
+int gsv_op_sample_rows(const float* logits, int B, int vocab, int vocab_eff, const int32_t* prev, int prev_len,
+                       const gsv_row_sampling_t* rows, uint64_t seed, const float* noise, int step, int32_t* sampled,
+                       int32_t* argmax_tok, gsv_stream_t stream) {
+  GSV_REQUIRE(logits && rows && sampled && argmax_tok && B > 0, "op_sample_rows: null argument");
+  GSV_REQUIRE(vocab <= 2048 && vocab_eff <= vocab, "op_sample_rows: vocab too large");
+  GSV_RC(check_row_sampling("op_sample_rows", rows, B));
+  hipStream_t s = (hipStream_t)stream;
+  // a test hook, not a hot path: the rows travel through a scratch array and the call waits for the kernel
+  RowSampling* d_rows = nullptr;
+  GSV_HIP(hipMalloc((void**)&d_rows, (size_t)B * sizeof(RowSampling)));
+  int rc = hipMemcpy(d_rows, rows, (size_t)B * sizeof(RowSampling), hipMemcpyHostToDevice) == hipSuccess ? GSV_OK : GSV_ERR_HIP;
+  if (rc) set_error("op_sample_rows: upload of the rows failed");
+  const size_t lds = (size_t)((vocab + 15) & ~15);
+  if (!rc)
+    rc = with_npl(vocab, [&](auto npl) -> int {
+      GSV_LAUNCH(sample_only_kernel<decltype(npl)::value>, dim3(B), dim3(64), lds, s, logits, vocab, vocab_eff, prev, prev_len, 0,
+                 1.f, 1.f, 1.f, noise, (unsigned long long)seed, step, sampled, argmax_tok, (const RowSampling*)d_rows);
+      return GSV_OK;
+    });
+  if (!rc && hipStreamSynchronize(s) != hipSuccess) { set_error("op_sample_rows: the kernel failed"); rc = GSV_ERR_HIP; }
+  (void)hipFree(d_rows);
+  return rc;
 }
 
 }  // extern "C"

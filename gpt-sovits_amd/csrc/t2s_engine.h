@@ -36,6 +36,9 @@ struct gsv_t2s {
   unsigned long long* d_rng_seed = nullptr; int* d_rng_row = nullptr;   // [max_batch] counter-RNG keys of the rows
   std::vector<unsigned long long> rng_seed_up; std::vector<int> rng_row_up;   // what the device arrays hold (skip re-uploads)
   std::vector<unsigned long long> rng_seed_next; std::vector<int> rng_row_next;   // gsv_t2s_set_row_rng: NEXT decode only
+  gsv::RowSampling* d_row_sampling = nullptr;       // [max_batch] per-row sampling parameters
+  std::vector<gsv_row_sampling_t> row_sampling_up;   // what the device array holds (skip re-uploads)
+  std::vector<gsv_row_sampling_t> row_sampling_next; // gsv_t2s_set_row_sampling: NEXT decode only, cleared when it returns
   int* h_pinned = nullptr;
   gsv::StepParams* d_sp = nullptr;
   // decode buffers

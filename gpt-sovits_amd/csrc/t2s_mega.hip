@@ -724,19 +724,20 @@ __device__ __forceinline__ void kv_stage_store(const Ctx& q, int qd, int extra, 
     if (was_active && ok) { \
       const int step = st_step(q)[r]; \
       const int Veff = step < sp.eos_mask_steps ? V - 1 : V; \
+      const RowSampling rs = row_sampling_of(sp, b); \
       float x[17]; \
   _Pragma("unroll") \
       for (int i = 0; i < 17; ++i) { \
         const int v = q.lane + 64 * i; \
         if (v < V) a.logits_out[(size_t)b * V + v] = __uint_as_float(lv[i]); \
         x[i] = v < Veff ? __uint_as_float(lv[i]) : -INFINITY; \
-        if (sp.rep_penalty != 1.0f && v < Veff && seen[v]) x[i] = x[i] < 0.f ? x[i] * sp.rep_penalty : x[i] / sp.rep_penalty; \
+        if (rs.rep_penalty != 1.0f && v < Veff && seen[v]) x[i] = x[i] < 0.f ? x[i] * rs.rep_penalty : x[i] / rs.rep_penalty; \
       } \
       const float* nrow = nullptr; \
       if (sp.noise) nrow = sp.noise + ((size_t)step * sp.noise_rows + (sp.noise_rows > 1 ? b : 0)) * V; \
       int smp, amx; \
       const unsigned long long seed_b = ((unsigned long long)(unsigned)st_seed_hi(q)[r] << 32) | (unsigned)st_seed_lo(q)[r]; \
-      sample_core<17>(x, Veff, sp.top_k, sp.top_p, sp.temperature, nrow, seed_b, st_krow(q)[r], step, &smp, &amx); \
+      sample_core<17>(x, Veff, rs.top_k, rs.top_p, rs.temperature, nrow, seed_b, st_krow(q)[r], step, &smp, &amx); \
       if (sp.dump) { \
   _Pragma("unroll") \
         for (int i = 0; i < 17; ++i) { \

@@ -8,6 +8,14 @@ namespace gsv {
 // device-side parameter block shared by the step kernels (lives in HBM so that the captured
 // graph does not bake sampling parameters)
 // ---------------------------------------------------------------------------------------
+// sampling parameters of one batch row (gsv_row_sampling_t, gsv_t2s_set_row_sampling): 16 bytes, one load per row
+struct RowSampling {
+  int top_k;
+  float top_p;
+  float temperature;
+  float rep_penalty;
+};
+
 struct StepParams {
   int top_k;
   float top_p;
@@ -29,7 +37,22 @@ struct StepParams {
   const int* force;        // [B][max_steps]: the token taken at step s of row b instead of the sampled one
   float* dump;             // [max_steps][B][V]: logits of every executed step, before the repetition penalty
   int* drawn;              // [max_steps][B][2]: (token the sampler drew, argmax of the penalised logits) before any forcing
+  // [B] or null: row b samples with row_sampling[b] instead of top_k / top_p / temperature / rep_penalty above
+  const RowSampling* row_sampling;
 };
+
+// Row b's entry of a RowSampling array.  b is wave-uniform at every call site, so the four values are made scalars again:
+// sample_core branches on top_k / top_p around wave-wide ballots and DPP reductions.
+__device__ __forceinline__ RowSampling load_row_sampling(const RowSampling* __restrict__ rows, int b) {
+  const int4 v = *reinterpret_cast<const int4*>(rows + b);
+  return {__builtin_amdgcn_readfirstlane(v.x), __int_as_float(__builtin_amdgcn_readfirstlane(v.y)),
+          __int_as_float(__builtin_amdgcn_readfirstlane(v.z)), __int_as_float(__builtin_amdgcn_readfirstlane(v.w))};
+}
+// the sampling values of batch row b: its own when the host gave per-row values for this decode, else the call's
+__device__ __forceinline__ RowSampling row_sampling_of(const StepParams& sp, int b) {
+  if (sp.row_sampling) return load_row_sampling(sp.row_sampling, b);
+  return {sp.top_k, sp.top_p, sp.temperature, sp.rep_penalty};
+}
 
 
 // ---------------------------------------------------------------------------------------

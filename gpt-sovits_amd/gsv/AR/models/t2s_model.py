@@ -105,13 +105,16 @@ class Text2SemanticDecoder:
     # ---- engine call ---------------------------------------------------------------
     def _run(self, x: Sequence[torch.Tensor], prompts: torch.Tensor, bert: Sequence[torch.Tensor], top_k, top_p,
              early_stop_num, temperature, repetition_penalty, eos_mask_steps, noise=None, seed=0,
-             max_steps: int = 1500, force_tokens=None, dump_logits=False, rng_keys=None):
+             max_steps: int = 1500, force_tokens=None, dump_logits=False, rng_keys=None, row_sampling=None):
         """prompts: [B, P] (one prompt length for the batch; P = 0 or None: prompt-free) or a list of B 1-D prompts of
         lengths P_b >= 1 (ragged: gsv_t2s_prefill_ragged).  rng_keys: optional [(seed_b, row_b)] per row, the counter-RNG
-        key that replaces (seed, b) (gsv_t2s_set_row_rng)."""
+        key that replaces (seed, b) (gsv_t2s_set_row_rng).  row_sampling: optional [(top_k, top_p, temperature,
+        repetition_penalty)] per row, which replace the four scalar arguments for this call (gsv_t2s_set_row_sampling)."""
         if not self._loaded:
             raise RuntimeError("load_state_dict() first")
         B = len(x)
+        if row_sampling is not None and len(row_sampling) != B:
+            raise ValueError(f"{len(row_sampling)} sampling tuples for {B} rows")
         dev = self.device
         if prompts is None:                  # prompt-free (reference t2s_model.py:849-856): empty audio prefix
             prompts = torch.zeros(B, 0, dtype=torch.int64)
@@ -195,6 +198,10 @@ class Text2SemanticDecoder:
                 rows_h = (C.c_int32 * B)(*[int(k[1]) for k in rng_keys])
                 _lib.check(l.gsv_t2s_set_row_rng(self._h, C.cast(seeds_h, C.c_void_p), C.cast(rows_h, C.c_void_p), B),
                            "gsv_t2s_set_row_rng")
+            if row_sampling is not None:
+                rs_h = (_lib.RowSampling * B)(*[_lib.RowSampling(int(k) if k is not None else 0, float(p_ if p_ is not None else 1.0),
+                                                                 float(t), float(r)) for k, p_, t, r in row_sampling])
+                _lib.check(l.gsv_t2s_set_row_sampling(self._h, rs_h, B), "gsv_t2s_set_row_sampling")
             steps = C.c_int(0)
             dump = None
             if force_tokens is not None or dump_logits:
@@ -257,10 +264,14 @@ class Text2SemanticDecoder:
         `prompts` is the reference's [B, P] tensor, or a list of B 1-D prompts of different lengths (one reference voice
         per row, every length >= 1).  kwarg `rng_keys=[(seed, row), ...]`: row i draws with the counter-RNG key
         (seed, row) instead of (seed kwarg, its row in the launch), so it samples the same tokens whichever batch it
-        is decoded in."""
+        is decoded in.  kwarg `row_sampling=[(top_k, top_p, temperature, repetition_penalty), ...]`: row i samples with
+        its own tuple instead of the four arguments (parallel decode only; the prompt-free loop takes the arguments)."""
         rng_keys = kwargs.get("rng_keys")
         if rng_keys is not None and len(rng_keys) != len(x):
             raise ValueError(f"{len(rng_keys)} RNG keys for {len(x)} rows")
+        row_sampling = kwargs.get("row_sampling")
+        if row_sampling is not None and len(row_sampling) != len(x):
+            raise ValueError(f"{len(row_sampling)} sampling tuples for {len(x)} rows")
         if prompts is None:
             return self.infer_panel_naive_batched(x, x_lens, prompts, bert_feature, top_k=top_k, top_p=top_p,
                                                   early_stop_num=early_stop_num, temperature=temperature, **kwargs)
@@ -278,7 +289,8 @@ class Text2SemanticDecoder:
                              max_steps=kwargs.get("max_steps", 1500),
                              force_tokens=None if kwargs.get("force_tokens") is None else kwargs["force_tokens"][lo:hi],
                              dump_logits=kwargs.get("dump_logits", False),
-                             rng_keys=None if rng_keys is None else list(rng_keys[lo:hi]))
+                             rng_keys=None if rng_keys is None else list(rng_keys[lo:hi]),
+                             row_sampling=None if row_sampling is None else list(row_sampling[lo:hi]))
             ys[lo:hi] = y
             idxs[lo:hi] = i
         return ys, idxs

@@ -1005,13 +1005,16 @@ class TTS:
         o["super_sampling"] = o["super_sampling"] and self.configs.use_vocoder and self.configs.version == "v3"
         return o
 
-    def plan_batch(self, plans: List[dict]) -> List[List[dict]]:
+    def plan_batch(self, plans: List[dict], mixed_sampling: bool = False) -> List[List[dict]]:
         """The AR launches of run_batch.  `plans[r]` = {"data": request r's to_batch batches, "no_prompt", "actual_seed",
         "opts"}.  Sentence j of batch bi of request r draws with the counter-RNG key (actual_seed_r + bi, j mod max_batch)
         -- the key it has in run(r) (the naive / prompt-free loop decodes every sentence alone: row 0).  Sentences are
         grouped by what is per launch (sampling parameters, parallel_infer, prompt-free, the decode budget run() gives them),
         sorted by length inside a group and cut into launches of at most max_batch rows.  Returns the launches: lists of
-        {"r", "bi", "j", "len", "key"}."""
+        {"r", "bi", "j", "len", "key", "group"}.
+        mixed_sampling=True: the sampling parameters are per row (gsv_t2s_set_row_sampling) and no longer separate groups:
+        their four slots of the group tuple hold None and every row carries "sampling" = (top_k, top_p, temperature,
+        repetition_penalty) of its request."""
         mb, max_seq = self.t2s_model.max_batch, self.t2s_model.max_seq
         groups: Dict[tuple, List[dict]] = {}
         for r, pl in enumerate(plans):
@@ -1025,10 +1028,12 @@ class TTS:
                     # run() decodes this sentence in a launch of `lens` (naive: alone); the K/V arena bounds its budget there
                     need = (n if naive else max(lens[j - j % mb:j - j % mb + mb])) + P + 2
                     budget = min(wanted, max_seq - need)
-                    g = (o["top_k"], o["top_p"], o["temperature"], o["repetition_penalty"], bool(o["parallel_infer"]),
-                         bool(pl["no_prompt"]), budget)
-                    groups.setdefault(g, []).append(dict(r=r, bi=bi, j=j, len=n + P, group=g,
-                                                         key=(pl["actual_seed"] + bi, 0 if naive else j % mb)))
+                    sampling = (o["top_k"], o["top_p"], o["temperature"], o["repetition_penalty"])
+                    g = ((None,) * 4 if mixed_sampling else sampling) + (bool(o["parallel_infer"]), bool(pl["no_prompt"]), budget)
+                    e = dict(r=r, bi=bi, j=j, len=n + P, group=g, key=(pl["actual_seed"] + bi, 0 if naive else j % mb))
+                    if mixed_sampling:
+                        e["sampling"] = sampling
+                    groups.setdefault(g, []).append(e)
         launches = []
         for g in groups:
             rows = sorted(groups[g], key=lambda e: e["len"])
@@ -1161,15 +1166,19 @@ class TTS:
         return dict(voice=voice, opts=o, actual_seed=actual_seed, data=data, index=index, no_prompt=no_prompt,
                     P=0 if no_prompt else int(voice["prompt_semantic"].numel()), frags=[None] * len(data))
 
-    def _ar_stage(self, plans: List[dict]) -> None:
-        """Stage 2: every sentence of every request through the shared AR launches of plan_batch.  Reads `data`, `opts`,
+    def _ar_stage(self, plans: List[dict], mixed_sampling: bool = False) -> None:
+        """Stage 2: every sentence of every request through the shared AR launches of plan_batch (mixed_sampling: launches
+        shared across sampling parameters; a launch whose rows differ hands them over per row).  Reads `data`, `opts`,
         `voice`, `no_prompt`, `P`, `actual_seed`.  Writes run()'s pred_list / idx_list per batch: `preds[bi][j]`, the tokens
         of sentence j (prompt included), `idxs[bi][j]`, how many were generated (0 prompt-free), `kept[bi]` = _kept_tokens."""
         for pl in plans:
             pl["preds"] = [[None] * len(item["all_phones"]) for item in pl["data"]]
             pl["idxs"] = [[None] * len(item["all_phones"]) for item in pl["data"]]
-        for rows in self.plan_batch(plans):
+        for rows in (self.plan_batch(plans, mixed_sampling=True) if mixed_sampling else self.plan_batch(plans)):
             o = plans[rows[0]["r"]]["opts"]
+            kw = {}
+            if mixed_sampling and len({e["sampling"] for e in rows}) > 1:     # a uniform launch takes the scalar path
+                kw["row_sampling"] = [e["sampling"] for e in rows]
             no_prompt = rows[0]["group"][5]
             naive = no_prompt or not o["parallel_infer"]
             items = [plans[e["r"]]["data"][e["bi"]] for e in rows]
@@ -1178,7 +1187,7 @@ class TTS:
             prompts = None if no_prompt else [plans[e["r"]]["voice"]["prompt_semantic"].view(-1) for e in rows]
             y, idx = self.t2s_model._run(x, prompts, bert, o["top_k"], o["top_p"], early_stop_num(self.configs), o["temperature"],
                                          o["repetition_penalty"], eos_mask_steps=11 if naive else 1,
-                                         max_steps=rows[0]["group"][6], rng_keys=[e["key"] for e in rows])
+                                         max_steps=rows[0]["group"][6], rng_keys=[e["key"] for e in rows], **kw)
             for e, y_, i_ in zip(rows, y, idx):
                 plans[e["r"]]["preds"][e["bi"]][e["j"]] = y_
                 plans[e["r"]]["idxs"][e["bi"]][e["j"]] = 0 if no_prompt else i_
@@ -1298,7 +1307,7 @@ class TTS:
 
     @torch.no_grad()
     def run_batch(self, requests: List[dict], shared_sovits: bool = False, shared_cfm: bool = False,
-                  shared_speed: bool = False) -> List[Tuple[int, np.ndarray]]:
+                  shared_speed: bool = False, mixed_sampling: bool = False) -> List[Tuple[int, np.ndarray]]:
         """Several requests, each with its own reference voice, through shared AR decodes.  Each request dict takes the
         keys run() accepts plus an optional "voice" (make_voice); without one it uses its ref_audio_path / prompt_text
         (through make_voice's LRU) or the current prompt cache.  Returns one (sr, int16 audio) per request, in order: what
@@ -1308,12 +1317,15 @@ class TTS:
         parallel_infer requests take their flow-matching stage from shared passes over all voices' chunks (_shared_cfm_stage).
         shared_speed=True (with shared_sovits=True): the sentences of v1 / v2 / v2Pro / v2ProPlus requests at speed_factor != 1
         join the same segmented passes, each at its own speed, instead of one decode per sentence.
+        mixed_sampling=True: requests with different top_k / top_p / temperature / repetition_penalty share AR launches, each
+        row sampling with its own request's values (plan_batch(mixed_sampling=True)); every request still gets the tokens it
+        gets without the keyword.
         No keyword changes anything for the other model family."""
         if self.t2s_model is None or self.vits_model is None:
             raise RuntimeError("init_t2s_weights / init_vits_weights first")
         self.stop_flag = False
         plans = [self._plan_request(req) for req in requests]
-        self._ar_stage(plans)
+        self._ar_stage(plans, mixed_sampling=mixed_sampling)
         sr = self._output_sr()
         if shared_sovits and not self.configs.use_vocoder:
             self._shared_sovits_stage(plans, shared_speed=shared_speed)

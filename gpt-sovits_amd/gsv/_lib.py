@@ -21,6 +21,11 @@ class SamplingParams(C.Structure):
                 ("max_steps", C.c_int), ("seed", C.c_uint64)]
 
 
+class RowSampling(C.Structure):
+    """gsv_row_sampling_t: the sampling parameters of one batch row"""
+    _fields_ = [("top_k", C.c_int), ("top_p", C.c_float), ("temperature", C.c_float), ("repetition_penalty", C.c_float)]
+
+
 class VitsConfig(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("inter_channels", "hidden_channels", "filter_channels", "n_heads", "n_layers",
                                         "kernel_size", "gin_channels", "n_symbols", "ssl_dim", "n_bins",
@@ -72,6 +77,7 @@ _SIGS = {
     "gsv_t2s_prefill_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
     "gsv_t2s_set_row_rng": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "gsv_t2s_set_row_sampling": (C.c_int, [C.c_void_p, C.POINTER(RowSampling), C.c_int]),
     "gsv_t2s_decode": (C.c_int, [C.c_void_p, C.POINTER(SamplingParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                  C.POINTER(C.c_int), C.c_void_p]),
     "gsv_t2s_decode_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
@@ -162,6 +168,8 @@ _SIGS = {
                                      C.c_int, C.c_void_p, C.c_void_p]),
     "gsv_op_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                 C.POINTER(SamplingParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsv_op_sample_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(RowSampling),
+                                     C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTS = tuple(_SIGS)   # every symbol include/gsv.h declares

@@ -97,6 +97,20 @@ int gsv_t2s_prefill_ragged(gsv_t2s_t* h, const int32_t* phones, const int32_t* p
  * B must equal the batch of that call.  Without it the keys are (sp->seed, b). */
 int gsv_t2s_set_row_rng(gsv_t2s_t* h, const uint64_t* seeds, const int32_t* rows, int B);
 
+/* Sampling parameters of one batch row: the four per-request fields of gsv_sampling_params. */
+typedef struct {
+  int top_k;                /* 0 = off */
+  float top_p;              /* 0 < top_p <= 1; 1 = off */
+  float temperature;        /* finite, >= 0 (clamped at 1e-5 like the scalar) */
+  float repetition_penalty; /* finite, > 0; exactly 1 = off for this row */
+} gsv_row_sampling_t;
+
+/* Per-row sampling parameters for the NEXT gsv_t2s_decode call only (like gsv_t2s_set_row_rng): row b samples with
+ * rows[b] [host] instead of the call's top_k / top_p / temperature / repetition_penalty, which are then ignored; everything
+ * else still comes from the call's gsv_sampling_params.  B must equal the batch of that call.  A value outside the ranges
+ * above is refused here with GSV_ERR_ARG and nothing is kept.  Without this call every row uses the scalars. */
+int gsv_t2s_set_row_sampling(gsv_t2s_t* h, const gsv_row_sampling_t* rows, int B);
+
 /* Decode loop (H4+H5).  noise [dev] fp32 Exp(1) draws [max_steps][noise_rows][vocab] or NULL
  * (noise_rows is 1 = shared by all rows, or B).  out_tokens [dev] int32 [B][max_steps]: generated
  * tokens (the finishing EOS / overflow token is not counted); out_len [dev] int32 [B] = the
@@ -440,6 +454,11 @@ int gsv_op_channel_norm(const void* x, int T, int C, const float* gamma, const f
 int gsv_op_sample(const float* logits, int B, int vocab, int vocab_eff, const int32_t* prev, int prev_len,
                   const gsv_sampling_params* sp, const float* noise, int step, int32_t* sampled,
                   int32_t* argmax_tok, gsv_stream_t stream);
+/* the same with one gsv_row_sampling_t per row, rows [host] [B] (checked like gsv_t2s_set_row_sampling), and the counter-RNG
+ * seed as an argument; waits for the kernel (a test hook) */
+int gsv_op_sample_rows(const float* logits, int B, int vocab, int vocab_eff, const int32_t* prev, int prev_len,
+                       const gsv_row_sampling_t* rows, uint64_t seed, const float* noise, int step, int32_t* sampled,
+                       int32_t* argmax_tok, gsv_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -3,9 +3,11 @@ each, fp16 synthetic v2 weights.  TTS.run_batch (one shared AR decode) against N
 call, the only way before run_batch).  Prints one JSON line: audio-s/s of both, the speed-up, and the persistent engine's
 fallback count (gsv_t2s_engine_stats), which must stay 0.  --shared-sovits also times run_batch(shared_sovits=True) (one
 segmented SoVITS pass for all voices) in the same process and reports its SoVITS device time.  Every mode lists the wall
-time of each iteration, so the gain can be read against the spread.
+time of each iteration, so the gain can be read against the spread.  --mixed-sampling spreads the requests evenly over four
+(top_k, top_p, temperature) settings and times run_batch() against run_batch(mixed_sampling=True) only (both with
+shared_sovits when --shared-sovits is given): ms per call, AR launches per call and AR wall time per call of both.
 
-    python tools/multivoice_bench.py [--requests 32] [--tokens 100] [--iters 3] [--shared-sovits]
+    python tools/multivoice_bench.py [--requests 32] [--tokens 100] [--iters 3] [--shared-sovits] [--mixed-sampling]
 """
 import argparse
 import json
@@ -27,6 +29,8 @@ def main():
     ap.add_argument("--tokens", type=int, default=100, help="AR tokens per request (25 tokens = 1 s)")
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--shared-sovits", action="store_true", help="also time run_batch(shared_sovits=True)")
+    ap.add_argument("--mixed-sampling", action="store_true",
+                    help="four sampling settings over the requests: run_batch() against run_batch(mixed_sampling=True)")
     a = ap.parse_args()
     from bench import build_tts, make_segments
     from gsv import synthetic as S
@@ -82,6 +86,35 @@ def main():
     def batch_shared():
         return tts.run_batch(reqs, shared_sovits=True)
 
+    if a.mixed_sampling:
+        four = [(15, 1.0, 1.0), (5, 1.0, 0.8), (30, 0.9, 1.0), (0, 0.8, 1.2)]
+        for i, r in enumerate(reqs):
+            r["top_k"], r["top_p"], r["temperature"] = four[i * 4 // N]
+        ar = {"launches": 0, "s": 0.0}
+        run = tts.t2s_model._run
+
+        def counted(*args, **kw):
+            t0 = time.perf_counter()                       # _run returns the ids on the host: the wall time covers the decode
+            out = run(*args, **kw)
+            ar["launches"] += 1
+            ar["s"] += time.perf_counter() - t0
+            return out
+
+        tts.t2s_model._run = counted
+        res = {"requests": N, "tokens_per_request": TOK, "settings": four, "shared_sovits": bool(a.shared_sovits)}
+        outs = {}
+        for name, mixed in (("split", False), ("mixed", True)):
+            fn = lambda mixed=mixed: tts.run_batch(reqs, shared_sovits=a.shared_sovits, mixed_sampling=mixed)  # noqa: E731
+            ar["launches"], ar["s"] = 0, 0.0
+            outs[name], best = timed(fn)
+            res.update({f"{name}_ms_per_call": round(best * 1e3, 2), f"{name}_iters_s": times[fn],
+                        f"{name}_ar_launches_per_call": ar["launches"] // (a.iters + 1),
+                        f"{name}_ar_ms_per_call_mean": round(ar["s"] * 1e3 / (a.iters + 1), 2)})
+        res["outputs_identical"] = f"{sum(int(x[1].shape == y[1].shape and (x[1] == y[1]).all()) for x, y in zip(outs['split'], outs['mixed']))}/{N}"
+        res["ar_ratio_split_over_mixed"] = round(res["split_ar_ms_per_call_mean"] / res["mixed_ar_ms_per_call_mean"], 2)
+        res["engine_fallbacks"], res["decode_mode"] = tts.t2s_model.engine_stats()[1], tts.t2s_model.decode_info()[0]
+        print(json.dumps(res))
+        return
     so, st = timed(sequential)
     bo, bt = timed(batch)
     _avail, fallbacks, _err = tts.t2s_model.engine_stats()

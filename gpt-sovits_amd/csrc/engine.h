@@ -134,8 +134,24 @@ void gen_shape(const Cfg& c, GenW* g) {
 int load_generator(gsv_vits* h, const std::string& prefix, bool bigvgan, GenW* g);
 // the 5 (BigVGAN: 6) ping-pong workspaces `name`0.. of a generator fed with F frames
 int gen_buffers(gsv_vits* h, const GenW& g, const char* name, int F, void** gb);
+// the rows of one resolution of a segmented pass as BigVGAN's activation needs them (device pointers): row_seg [rows] int32,
+// -1 = gap row; segment s covers rows [start[s], start[s] + len[s])
+struct SegRows { const int* row_seg = nullptr; const int* start = nullptr; const int* len = nullptr; };
 // all upsampling stages on *cur = gb[3] ([*Tn][g.uic], the conv_pre output) -> *cur [*Tn][g.uic >> g.n_ups], one of gb[3], gb[4].
-// seg_up != null (segmented decode): per-stage row maps, gap rows of every stage output are 0
-int run_generator_stages(gsv_vits* h, hipStream_t s, const GenW& g, void* const* gb, void** cur, int* Tn, int* const* seg_up = nullptr);
+// seg_up != null (segmented decode): per-stage row maps, gap rows of every stage output are 0; a BigVGAN generator also takes
+// seg_act[i] = the rows of stage i's output (row_seg = seg_up[i]) for its activations
+int run_generator_stages(gsv_vits* h, hipStream_t s, const GenW& g, void* const* gb, void** cur, int* Tn, int* const* seg_up = nullptr,
+                         const SegRows* seg_act = nullptr);
+
+// segmented passes (vits.hip: gsv_vits_decode_segments, generator.hip: gsv_vocoder_forward_segments): n sequences back to back on
+// one time axis with G zero "gap" rows between neighbours at the frame rate, G * prod(rates[:i]) after upsampling stage i
+// one-sided input reach of a conv with `taps` taps at dilation `dil` ("same" padding)
+inline int conv_reach(int taps, int dil) { return (taps - 1) / 2 * dil; }
+// the smallest G that covers, at every resolution, the reach of the generator's convs (conv_pre and conv_post included)
+int gen_gap(const GenW& g);
+// out[i] = seg[i / up], i < n: the row map of an upsampled resolution
+int launch_expand_seg(hipStream_t s, const int* seg, int up, long long n, int* out);
+// drop the gaps from the padded waveform src [n] (seg_f = frame-rate map, up samples per frame, gap = G * up samples) into wav
+int launch_compact_wav(hipStream_t s, const float* src, const int* seg_f, int up, long long gap, long long n, float* wav);
 
 }  // namespace gsveng

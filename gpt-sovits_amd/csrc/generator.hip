@@ -12,15 +12,25 @@ namespace gsv {
 // alias_free_activation/torch/act.py:25-30): 2x zero-stuffed 12-tap up-FIR -> x + sin^2(a x)/(b+1e-9)
 // -> 12-tap stride-2 down-FIR, replicate padding as in aa.hip.  A workgroup owns 64 time steps x 64
 // channels: rows are read/written 128 B wide (lane = channel), the 2x-rate intermediate lives in LDS.
-template <typename T>
+// SEG = the activation of a segmented pass (gsv_vocoder_forward_segments): row_seg holds one int32 per row, -1 = gap row, and
+// segment s covers rows [seg_start[s], seg_start[s] + seg_len[s]).  Both replicate paddings stop at the row's own segment: the
+// up-FIR clamps its x index to the segment's rows [a, b - 1], the down-FIR clamps its 2x-rate index to [2a, 2b - 1], so the
+// intermediate is only ever computed at positions inside a segment (where it belongs to that segment alone) and the taps of an
+// output row reach it through the clamp.  Gap rows of x are staged but never named by a clamped index; gap rows of y are stored
+// as 0.  The clamps move an index towards the row it serves, so the staged halos of the plain kernel hold every row they can
+// name, however many segments a tile holds.  Everything SEG adds sits under `if constexpr (SEG)`; the three maps are trailing
+// kernel arguments the plain instantiations never read.
+template <typename T, bool SEG = false>
 __global__ __launch_bounds__(256) void aa_act_cl_kernel(const T* __restrict__ x, T* __restrict__ y, int Tn, int C, int ld,
                                                         const float* __restrict__ alpha, const float* __restrict__ beta,
                                                         int logscale, const float* __restrict__ up12,
-                                                        const float* __restrict__ dn12) {
+                                                        const float* __restrict__ dn12, const int* __restrict__ row_seg,
+                                                        const int* __restrict__ seg_start, const int* __restrict__ seg_len) {
   constexpr int TT = 64, CW = 64;
   __shared__ float xs[TT + 16][CW];
   __shared__ float as[2 * TT + 16][CW];
   __shared__ float uf[12], df[12];
+  __shared__ int sa[SEG ? TT + 16 : 1], sl[SEG ? TT + 16 : 1];   // SEG: first and last row of the staged row's segment, -1 = none
   const int t0 = blockIdx.x * TT, c0 = blockIdx.y * CW;
   const int cl = threadIdx.x & 63, tq = threadIdx.x >> 6;
   const int c = c0 + cl;
@@ -31,6 +41,17 @@ __global__ __launch_bounds__(256) void aa_act_cl_kernel(const T* __restrict__ x,
     a = logscale ? expf(alpha[c]) : alpha[c];
     ib = 1.f / ((logscale ? expf(beta[c]) : beta[c]) + 1e-9f);
   }
+  if constexpr (SEG) {
+    if (threadIdx.x < TT + 16) {
+      const int r = t0 - 8 + (int)threadIdx.x;
+      int fa = -1, fl = -1;
+      if (r >= 0 && r < Tn) {
+        const int sg = row_seg[r];
+        if (sg >= 0) { fa = seg_start[sg]; fl = fa + seg_len[sg] - 1; }
+      }
+      sa[threadIdx.x] = fa; sl[threadIdx.x] = fl;
+    }
+  }
   for (int i = tq; i < TT + 16; i += 4) {
     const int t = min(max(t0 - 8 + i, 0), Tn - 1);
     xs[i][cl] = cok ? to_f(x[(long long)t * ld + c]) : 0.f;
@@ -38,7 +59,15 @@ __global__ __launch_bounds__(256) void aa_act_cl_kernel(const T* __restrict__ x,
   __syncthreads();
   const int n0 = 2 * t0 - 8;
   for (int k = tq; k < 2 * TT + 16; k += 4) {
-    const int n = min(max(n0 + k, 0), 2 * Tn - 1);
+    int n, xlo = 0, xhi = Tn - 1;
+    if constexpr (SEG) {
+      n = n0 + k;                               // the position itself: it is read through the down-FIR's clamp
+      const int ri = (n >> 1) - (t0 - 8);       // its row among the staged ones, 4 .. TT + 11
+      xlo = sa[ri]; xhi = sl[ri];
+      if (xlo < 0) { as[k][cl] = 0.f; continue; }   // a gap or past the ends: no clamped index names it
+    } else {
+      n = min(max(n0 + k, 0), 2 * Tn - 1);
+    }
     const int ilo = (n + 5) >> 1;
     float acc = 0.f;
 #pragma unroll
@@ -46,7 +75,7 @@ __global__ __launch_bounds__(256) void aa_act_cl_kernel(const T* __restrict__ x,
       const int i = ilo + j;
       const int f = n + 15 - 2 * i;
       if (f >= 0 && f < 12) {
-        const int xo = min(max(i - 5, 0), Tn - 1);
+        const int xo = min(max(i - 5, xlo), xhi);
         acc += xs[xo - (t0 - 8)][cl] * uf[f];
       }
     }
@@ -59,9 +88,43 @@ __global__ __launch_bounds__(256) void aa_act_cl_kernel(const T* __restrict__ x,
     const int t = t0 + i;
     if (t >= Tn || !cok) continue;
     float acc = 0.f;
+    if constexpr (SEG) {
+      const int fa = sa[i + 8];
+      if (fa >= 0) {
+        const int lo = 2 * fa - n0, hi = 2 * sl[i + 8] + 1 - n0;
 #pragma unroll
-    for (int f = 0; f < 12; ++f) acc += df[f] * as[2 * i + f + 3][cl];
+        for (int f = 0; f < 12; ++f) acc += df[f] * as[min(max(2 * i + f + 3, lo), hi)][cl];
+      }
+    } else {
+#pragma unroll
+      for (int f = 0; f < 12; ++f) acc += df[f] * as[2 * i + f + 3][cl];
+    }
     y[(long long)t * ld + c] = (T)acc;
+  }
+}
+
+// mel fp32 channels-first [C][Fn], the segments packed without gaps -> channels-last [F][ldd] in the gapped layout of a
+// segmented pass: row t of segment row_seg[t] is packed column t - row_seg[t] * G (every gap before it is G rows); gap rows and
+// the columns C .. ldd are 0
+template <typename T>
+__global__ void pack_mel_seg_kernel(const float* __restrict__ src, int Fn, int C, const int* __restrict__ row_seg, int G, int F,
+                                    T* __restrict__ dst, int ldd) {
+  __shared__ float tile[32][33];
+  const int t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
+  {
+    const int t = t0 + tx;
+    const int sg = t < F ? row_seg[t] : -1;
+    const int col = sg >= 0 ? t - sg * G : -1;
+    for (int i = ty; i < 32; i += 8) {
+      const int c = c0 + i;
+      tile[i][tx] = (c < C && col >= 0 && col < Fn) ? src[(long long)c * Fn + col] : 0.f;
+    }
+  }
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    const int t = t0 + i, c = c0 + tx;
+    if (t < F && c < ldd) dst[(long long)t * ldd + c] = (T)tile[tx][i];
   }
 }
 
@@ -101,11 +164,47 @@ void kaiser_sinc12(float* out) {
   for (int n = 0; n < K; ++n) out[n] = (float)(f[n] / sum);
 }
 
+// the anti-aliased activation on x [Tn][C] -> y; m != null (segmented pass): replicate padding per segment, gap rows of y = 0
 template <typename T>
-static int voc_act(gsv_vits* h, hipStream_t s, const GenW& g, const VocAct& a, const void* x, void* y, int Tn, int C) {
-  GSV_LAUNCH(aa_act_cl_kernel<T>, dim3(cdiv(Tn, 64), cdiv(C, 64)), dim3(256), 0, s, (const T*)x, (T*)y, Tn, C, C, a.alpha, a.beta,
-             g.snake_logscale, g.up12, g.dn12);
+static int launch_aa_act(hipStream_t s, const void* x, void* y, int Tn, int C, const float* alpha, const float* beta, int logscale,
+                         const float* up12, const float* dn12, const SegRows* m) {
+  const dim3 grid(cdiv(Tn, 64), cdiv(C, 64));
+  if (m) {
+    auto kern = aa_act_cl_kernel<T, true>;
+    GSV_LAUNCH(kern, grid, dim3(256), 0, s, (const T*)x, (T*)y, Tn, C, C, alpha, beta, logscale, up12, dn12, m->row_seg, m->start, m->len);
+  } else {
+    auto kern = aa_act_cl_kernel<T, false>;
+    GSV_LAUNCH(kern, grid, dim3(256), 0, s, (const T*)x, (T*)y, Tn, C, C, alpha, beta, logscale, up12, dn12, (const int*)nullptr,
+               (const int*)nullptr, (const int*)nullptr);
+  }
   return GSV_OK;
+}
+
+template <typename T>
+static int voc_act(gsv_vits* h, hipStream_t s, const GenW& g, const VocAct& a, const void* x, void* y, int Tn, int C,
+                   const SegRows* m = nullptr) {
+  return launch_aa_act<T>(s, x, y, Tn, C, a.alpha, a.beta, g.snake_logscale, g.up12, g.dn12, m);
+}
+
+// The gap of a segmented pass, in frames, as far as a generator decides it: at every resolution it covers the one-sided input
+// reach of each conv reading that resolution -- conv_pre and conv_post (7 taps), the transposed ups[i], every ResBlock conv -- so a
+// conv of a segment row reads zeros (its isolated zero padding) wherever it would reach past the segment's edge, and never the
+// neighbour's rows.  BigVGAN's activation adds nothing: it never reads a gap row (aa_act_cl_kernel, SEG).
+int gen_gap(const GenW& c) {
+  auto need_at = [](int r, long long cum) { return (int)((r + cum - 1) / cum); };
+  int g = std::max(1, conv_reach(7, 1));          // conv_pre
+  long long cum = 1;
+  for (int i = 0; i < c.n_ups; ++i) {
+    // ups[i] reads resolution `cum`: transposed conv, kernel k, stride u, padding (k - u) / 2; output row t reads input rows
+    // (t + p - j) / u, j < k: ceil((k - 1 - p) / u) to the left of a segment, floor((u - 1 + p) / u) to its right
+    const int u = c.up_rates[i], k = c.up_kernels[i], p = (k - u) / 2;
+    g = std::max(g, need_at(std::max((k - 1 - p + u - 1) / u, (u - 1 + p) / u), cum));
+    cum *= u;
+    for (int j = 0; j < c.n_resblocks; ++j)        // ResBlock1 convs1 (dilated) and convs2 (dilation 1); a conv_pair counts as both
+      for (int d = 0; d < 3; ++d) g = std::max(g, need_at(conv_reach(c.rb_kernels[j], c.rb_dilations[j][d]), cum));
+  }
+  g = std::max(g, need_at(conv_reach(7, 1), cum));   // conv_post
+  return g;
 }
 
 int load_generator(gsv_vits* h, const std::string& prefix, bool bigvgan, GenW* g) {
@@ -158,15 +257,18 @@ int gen_buffers(gsv_vits* h, const GenW& g, const char* name, int F, void** gb) 
   return GSV_OK;
 }
 
-int run_generator_stages(gsv_vits* h, hipStream_t s, const GenW& g, void* const* gb, void** cur_io, int* Tn_io, int* const* seg_up) {
+int run_generator_stages(gsv_vits* h, hipStream_t s, const GenW& g, void* const* gb, void** cur_io, int* Tn_io, int* const* seg_up,
+                         const SegRows* seg_act) {
   const bool big = !g.acts.empty();
   void* cur = *cur_io;
   int Tn = *Tn_io, ch = g.uic, ai = 0;
+  GSV_REQUIRE(!(big && seg_up) || seg_act, "generator: a segmented BigVGAN pass needs the activation's rows");
   for (int i = 0; i < g.n_ups; ++i) {
     const int Tout = Tn * g.up_rates[i];
     ch >>= 1;
     void* xup = gb[0]; void* xt = gb[1]; void* R = gb[2]; void* xa = big ? gb[5] : nullptr; void* xs = (cur == gb[3]) ? gb[4] : gb[3];
     const int* seg_o = seg_up ? seg_up[i] : nullptr;   // gap rows of this stage's outputs
+    const SegRows* seg_a = seg_o && big ? &seg_act[i] : nullptr;   // BigVGAN: the same rows with each segment's first row and count
     h->dbg_last_in = cur; h->dbg_last_T = Tn; h->dbg_last_C = 2 * ch;
     { ConvOpt ou; ou.row_seg = seg_o;
       if (!big) { ou.pre_act = ACT_LRELU; ou.pre_slope = 0.1f; }
@@ -199,9 +301,9 @@ int run_generator_stages(gsv_vits* h, hipStream_t s, const GenW& g, void* const*
         ConvOpt o2; o2.res = xr; o2.ldr = ch; o2.row_seg = seg_o;
         const void *in1 = xr, *in2 = xt;
         if (!big) { o1.pre_act = ACT_LRELU; o1.pre_slope = 0.1f; o2.pre_act = ACT_LRELU; o2.pre_slope = 0.1f; }
-        if (big) { GSV_RC(GSV_WITH_T(h, voc_act<T>(h, s, g, g.acts[ai + 2 * k], xr, xa, Tout, ch))); in1 = xa; }
+        if (big) { GSV_RC(GSV_WITH_T(h, voc_act<T>(h, s, g, g.acts[ai + 2 * k], xr, xa, Tout, ch, seg_a))); in1 = xa; }
         GSV_RC(conv(h, s, c1, in1, ch, Tout, xt, Tout, o1));
-        if (big) { GSV_RC(GSV_WITH_T(h, voc_act<T>(h, s, g, g.acts[ai + 2 * k + 1], xt, xa, Tout, ch))); in2 = xa; }
+        if (big) { GSV_RC(GSV_WITH_T(h, voc_act<T>(h, s, g, g.acts[ai + 2 * k + 1], xt, xa, Tout, ch, seg_a))); in2 = xa; }
         if (k < 2) {
           GSV_RC(conv(h, s, c2, in2, ch, Tout, R, Tout, o2));
           xr = R;
@@ -219,6 +321,69 @@ int run_generator_stages(gsv_vits* h, hipStream_t s, const GenW& g, void* const*
 }
 
 }  // namespace gsveng
+
+// ---------------------------------------------------------------------------------------
+// segmented pass: n mels back to back with G zero gap frames between neighbours
+// ---------------------------------------------------------------------------------------
+namespace {
+
+struct VocLayout {
+  int G = 0;
+  long long F = 0, Fn = 0, up = 1;     // frames with / without gaps, samples per frame
+  std::vector<int> f0;                 // first frame row of each segment
+};
+
+// checks n and frames and lays the segments out; fails before anything is launched
+int voc_layout(const gsv_vocoder_config& c, int n, const int* frames, VocLayout* o) {
+  GSV_REQUIRE(c.n_ups >= 1 && c.n_ups <= 8 && c.n_resblocks >= 1 && c.n_resblocks <= 4, "vocoder segments: bad config");
+  GSV_REQUIRE(frames, "vocoder segments: frames is null");
+  GSV_REQUIRE(n >= 1 && n <= 4096, "vocoder segments: bad segment count %d", n);
+  GenW shape;
+  gen_shape(c, &shape);
+  o->G = gen_gap(shape);
+  o->up = 1;
+  for (int i = 0; i < c.n_ups; ++i) {
+    GSV_REQUIRE(c.up_rates[i] >= 1, "vocoder segments: bad config");
+    o->up *= c.up_rates[i];
+  }
+  o->f0.resize(n);
+  long long f = 0, fn = 0;
+  for (int i = 0; i < n; ++i) {
+    GSV_REQUIRE(frames[i] >= 1, "vocoder segments: segment %d is empty (%d frames)", i, frames[i]);
+    if (i) f += o->G;
+    o->f0[i] = (int)f;
+    f += frames[i]; fn += frames[i];
+    GSV_REQUIRE(f * o->up < (1LL << 24), "vocoder segments: too long (2^24 rows or more at the output rate)");
+  }
+  o->F = f; o->Fn = fn;
+  return GSV_OK;
+}
+
+template <typename T>
+int pack_mel(hipStream_t s, const float* mel, int Fn, int C, const int* row_seg, int G, int F, void* dst, int ldd) {
+  GSV_LAUNCH(pack_mel_seg_kernel<T>, dim3(cdiv(F, 32), cdiv(ldd, 32)), dim3(256), 0, s, mel, Fn, C, row_seg, G, F, (T*)dst, ldd);
+  return GSV_OK;
+}
+
+// the 12 Kaiser-sinc taps on the current device for gsv_op_aa_act_cl (an engine keeps its own)
+int op_filter(const float** out) {
+  static float* taps[64] = {};
+  int dev = 0;
+  GSV_HIP(hipGetDevice(&dev));
+  GSV_REQUIRE(dev >= 0 && dev < 64, "op_aa_act_cl: device %d", dev);
+  if (!taps[dev]) {
+    float f[12];
+    kaiser_sinc12(f);
+    float* p = nullptr;
+    GSV_HIP(hipMalloc((void**)&p, sizeof(f)));
+    GSV_HIP(hipMemcpy(p, f, sizeof(f), hipMemcpyHostToDevice));
+    taps[dev] = p;
+  }
+  *out = taps[dev];
+  return GSV_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -241,6 +406,7 @@ int gsv_vocoder_create(const gsv_vocoder_config* cfg, int dtype, gsv_vocoder_t**
 void gsv_vocoder_destroy(gsv_vocoder_t* v) {
   if (!v) return;
   free_ctx(&v->ctx);
+  if (v->ctx.seg_ev) (void)hipEventDestroy(v->ctx.seg_ev);
   delete v;
 }
 
@@ -292,6 +458,110 @@ int gsv_vocoder_forward(gsv_vocoder_t* v, const float* mel, int F, float* wav, g
   op.post_act = c.tanh_at_final ? ACT_TANH : ACT_CLAMP1;
   GSV_RC(conv(h, s, v->conv_post, pin, ch, Tn, wav, Tn, op));
   return GSV_OK;
+}
+
+int gsv_vocoder_segment_gap(const gsv_vocoder_config* cfg) {
+  if (!cfg || cfg->n_ups < 1 || cfg->n_ups > 8 || cfg->n_resblocks < 1 || cfg->n_resblocks > 4) return -1;
+  GenW shape;
+  gen_shape(*cfg, &shape);
+  return gen_gap(shape);
+}
+
+int gsv_vocoder_segment_map(const gsv_vocoder_config* cfg, int n, const int* frames, int level, int32_t* seg, int64_t cap) {
+  GSV_REQUIRE(cfg && seg, "vocoder_segment_map: null argument");
+  VocLayout lay;
+  GSV_RC(voc_layout(*cfg, n, frames, &lay));
+  GSV_REQUIRE(level >= 0 && level <= cfg->n_ups, "vocoder_segment_map: level %d outside [0, %d]", level, cfg->n_ups);
+  long long up = 1;
+  for (int i = 0; i < level; ++i) up *= cfg->up_rates[i];
+  const long long nr = lay.F * up;
+  GSV_REQUIRE(cap >= nr, "vocoder_segment_map: buffer holds %lld rows, need %lld", (long long)cap, nr);
+  for (long long t = 0; t < nr; ++t) seg[t] = -1;
+  for (int i = 0; i < n; ++i)
+    for (long long t = lay.f0[i] * up; t < (lay.f0[i] + (long long)frames[i]) * up; ++t) seg[t] = i;
+  return GSV_OK;
+}
+
+int gsv_vocoder_forward_segments(gsv_vocoder_t* v, const float* mel, int n, const int* frames, float* wav, gsv_stream_t stream) {
+  GSV_REQUIRE(v && v->finalized, "vocoder_forward_segments: handle not finalized");
+  GSV_REQUIRE(mel && wav && frames, "vocoder_forward_segments: null argument");
+  VocLayout lay;
+  GSV_RC(voc_layout(v->cfg, n, frames, &lay));
+  if (n == 1) return gsv_vocoder_forward(v, mel, frames[0], wav, stream);   // no gap, no maps: the plain path itself
+  hipStream_t s = (hipStream_t)stream;
+  gsv_vits* h = &v->ctx;
+  const auto& c = v->cfg;
+  const size_t es = esz(h);
+  const bool big = c.kind == 1;
+  const int F = (int)lay.F, nu = c.n_ups;
+  // host image of the maps, one upload: seg_f [F] | per level 1 .. n_ups: first row [n] | rows [n]
+  if (!h->seg_ev) GSV_HIP(hipEventCreateWithFlags(&h->seg_ev, hipEventDisableTiming));
+  GSV_HIP(hipEventSynchronize(h->seg_ev));   // the previous call's upload (any stream) is done before its host image is rewritten
+  std::vector<int>& m = h->seg_host;
+  const size_t o_sl = (size_t)F, total = o_sl + 2 * (size_t)nu * n;
+  m.assign(total, -1);
+  for (int i = 0; i < n; ++i)
+    for (int t = lay.f0[i]; t < lay.f0[i] + frames[i]; ++t) m[t] = i;
+  {
+    long long up = 1;
+    for (int l = 0; l < nu; ++l) {
+      up *= c.up_rates[l];
+      for (int i = 0; i < n; ++i) {
+        m[o_sl + (size_t)(2 * l) * n + i] = (int)(lay.f0[i] * up);
+        m[o_sl + (size_t)(2 * l + 1) * n + i] = (int)(frames[i] * up);
+      }
+    }
+  }
+  int* dm;
+  GSV_RC(need(h, "voc_seg_maps", total * 4, (void**)&dm));
+  GSV_HIP(hipMemcpyAsync(dm, m.data(), total * 4, hipMemcpyHostToDevice, s));
+  GSV_HIP(hipEventRecord(h->seg_ev, s));
+  const int* seg_f = dm;
+  std::vector<int*> seg_up(nu);
+  std::vector<SegRows> seg_act(nu);
+  {
+    long long up = 1;
+    for (int l = 0; l < nu; ++l) {
+      up *= c.up_rates[l];
+      GSV_RC(need(h, ("voc_seg_up" + std::to_string(l)).c_str(), (size_t)F * up * 4, (void**)&seg_up[l]));
+      GSV_RC(launch_expand_seg(s, seg_f, (int)up, (long long)F * up, seg_up[l]));
+      seg_act[l].row_seg = seg_up[l];
+      seg_act[l].start = dm + o_sl + (size_t)(2 * l) * n;
+      seg_act[l].len = dm + o_sl + (size_t)(2 * l + 1) * n;
+    }
+  }
+  void* xin;
+  GSV_RC(need(h, "voc_in", (size_t)F * v->cin_pad * es, &xin));
+  GSV_RC(GSV_WITH_T(h, pack_mel<T>(s, mel, (int)lay.Fn, c.in_channels, seg_f, lay.G, F, xin, v->cin_pad)));
+  void* gb[6];
+  GSV_RC(gen_buffers(h, v->gen, "v", F, gb));
+  void* cur = gb[3];
+  { ConvOpt o; o.row_seg = seg_f; GSV_RC(conv(h, s, v->conv_pre, xin, v->cin_pad, F, cur, F, o)); }
+  int Tn = F;
+  const int ch = c.upsample_initial_channel >> c.n_ups;
+  GSV_RC(run_generator_stages(h, s, v->gen, gb, &cur, &Tn, seg_up.data(), seg_act.data()));
+  ConvOpt op; op.out_f32 = 1;
+  const void* pin = cur;
+  if (big) { GSV_RC(GSV_WITH_T(h, voc_act<T>(h, s, v->gen, v->gen.acts.back(), cur, gb[5], Tn, ch, &seg_act[nu - 1]))); pin = gb[5]; }
+  else { op.pre_act = ACT_LRELU; op.pre_slope = 0.01f; }
+  op.post_act = c.tanh_at_final ? ACT_TANH : ACT_CLAMP1;
+  float* wpad;                         // the padded waveform, then the gaps are dropped into wav
+  GSV_RC(need(h, "voc_wav_pad", (size_t)Tn * 4, (void**)&wpad));
+  GSV_RC(conv(h, s, v->conv_post, pin, ch, Tn, wpad, Tn, op));
+  GSV_RC(launch_compact_wav(s, wpad, seg_f, (int)lay.up, lay.G * lay.up, (long long)Tn, wav));
+  return GSV_OK;
+}
+
+int gsv_op_aa_act_cl(const void* x, void* y, int Tn, int C, const float* alpha, const float* beta, int logscale, const int32_t* row_seg,
+                     const int32_t* seg_start, const int32_t* seg_len, int n_seg, int dtype, gsv_stream_t stream) {
+  GSV_REQUIRE(x && y && alpha && beta && Tn >= 1 && C >= 1, "op_aa_act_cl: bad argument");
+  GSV_REQUIRE(dtype == GSV_F16 || dtype == GSV_F32, "op_aa_act_cl: bad dtype");
+  GSV_REQUIRE(!row_seg || (seg_start && seg_len && n_seg >= 1), "op_aa_act_cl: a row map needs seg_start, seg_len and n_seg >= 1");
+  const float* taps = nullptr;
+  GSV_RC(op_filter(&taps));
+  SegRows m;
+  m.row_seg = row_seg; m.start = seg_start; m.len = seg_len;
+  return GSV_WITH_DTYPE(dtype, launch_aa_act<T>((hipStream_t)stream, x, y, Tn, C, alpha, beta, logscale, taps, taps, row_seg ? &m : nullptr));
 }
 
 }  // extern "C"

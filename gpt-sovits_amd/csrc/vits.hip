@@ -68,6 +68,19 @@ __global__ void compact_wav_kernel(const float* __restrict__ src, const int* __r
   if (sg >= 0) wav[t - sg * gap] = src[t];
 }
 
+}  // namespace gsv
+namespace gsveng {
+int launch_expand_seg(hipStream_t s, const int* seg, int up, long long n, int* out) {
+  GSV_LAUNCH(gsv::expand_seg_kernel, dim3(nblk(n)), dim3(256), 0, s, seg, up, n, out);
+  return GSV_OK;
+}
+int launch_compact_wav(hipStream_t s, const float* src, const int* seg_f, int up, long long gap, long long n, float* wav) {
+  GSV_LAUNCH(gsv::compact_wav_kernel, dim3(nblk(n)), dim3(256), 0, s, src, seg_f, up, gap, n, wav);
+  return GSV_OK;
+}
+}  // namespace gsveng
+namespace gsv {
+
 // fp32 channels-first [C_total][T] -> T channels-last [T][C] (first C channels)
 template <typename T>
 __global__ void cf_to_cl_kernel(const float* __restrict__ src, int Tn, int C, T* __restrict__ dst, int ldd = 0) {
@@ -689,28 +702,15 @@ namespace gsveng {
 // segmented decode (gsv_vits_decode_segments): n independent sequences back to back on one time axis, G zero "gap" rows
 // between neighbours at the frame rate (G * prod(rates[:i]) after upsampling stage i) and G between their phones
 // ---------------------------------------------------------------------------------------
-// one-sided input reach of a conv with `taps` taps at dilation `dil` ("same" padding)
-static int reach(int taps, int dil) { return (taps - 1) / 2 * dil; }
 // the gap, in frames: at every resolution it covers the reach of each conv reading that resolution, so a conv of a segment row
 // reads zeros (its isolated zero padding) wherever it would reach past the segment's edge, and never the neighbour's rows
 int seg_gap(const gsv_vits_config& c) {
-  auto need_at = [](int r, long long cum) { return (int)((r + cum - 1) / cum); };
   int g = 1;
-  g = std::max(g, reach(c.kernel_size, 1));      // encoder FFN convs (frame and text axes)
-  g = std::max(g, reach(5, 1));                  // flow WN in_layers (kernel 5, dilation rate 1)
-  g = std::max(g, reach(7, 1));                  // generator conv_pre
-  long long cum = 1;
-  for (int i = 0; i < c.n_ups; ++i) {
-    // ups[i] reads resolution `cum`: transposed conv, kernel k, stride u, padding (k - u) / 2; output row t reads input rows
-    // (t + p - j) / u, j < k: ceil((k - 1 - p) / u) to the left of a segment, floor((u - 1 + p) / u) to its right
-    const int u = c.up_rates[i], k = c.up_kernels[i], p = (k - u) / 2;
-    g = std::max(g, need_at(std::max((k - 1 - p + u - 1) / u, (u - 1 + p) / u), cum));
-    cum *= u;
-    for (int j = 0; j < c.n_resblocks; ++j)        // ResBlock1 convs1 (dilated) and convs2 (dilation 1); a conv_pair counts as both
-      for (int d = 0; d < 3; ++d) g = std::max(g, need_at(reach(c.rb_kernels[j], c.rb_dilations[j][d]), cum));
-  }
-  g = std::max(g, need_at(reach(7, 1), cum));    // conv_post
-  return g;
+  g = std::max(g, conv_reach(c.kernel_size, 1));   // encoder FFN convs (frame and text axes)
+  g = std::max(g, conv_reach(5, 1));               // flow WN in_layers (kernel 5, dilation rate 1)
+  GenW shape;
+  gen_shape(c, &shape);
+  return std::max(g, gen_gap(shape));              // conv_pre, ups, ResBlocks, conv_post: the rule the vocoders share (generator.hip)
 }
 
 struct SegLayout {
@@ -1139,8 +1139,7 @@ static int decode_wav(gsv_vits* h, hipStream_t s, const int32_t* codes, int Tc, 
     GSV_RC(conv(h, s, h->conv_post, cur, h->conv_post.cin, Tn, wout_p, Tn, op)); }
   if (seg_f) {
     const int up = Tn / F;
-    GSV_LAUNCH(compact_wav_kernel, dim3(nblk(Tn)), dim3(256), 0, s, (const float*)wout_p, seg_f, up, (long long)sr->post->G * up,
-               (long long)Tn, wav);
+    GSV_RC(launch_compact_wav(s, wout_p, seg_f, up, (long long)sr->post->G * up, (long long)Tn, wav));
   }
   GSV_HIP(hipEventRecord(h->ev[2], s));
   return GSV_OK;
@@ -1372,7 +1371,7 @@ int gsv_vits_decode_segments_speed(gsv_vits_t* h, int n, const int32_t* codes, c
     const std::string nm = "seg_up" + std::to_string(i);
     int* su;
     GSV_RC(need(h, nm.c_str(), (size_t)Fp * up * 4, (void**)&su));
-    GSV_LAUNCH(expand_seg_kernel, dim3(nblk((long long)Fp * up)), dim3(256), 0, s, (const int*)sr.seg_p, (int)up, (long long)Fp * up, su);
+    GSV_RC(launch_expand_seg(s, sr.seg_p, (int)up, (long long)Fp * up, su));
     sr.seg_up.push_back(su);
   }
   GSV_HIP(hipEventRecord(h->ev[0], s));

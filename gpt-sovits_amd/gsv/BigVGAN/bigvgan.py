@@ -36,3 +36,11 @@ class BigVGAN:
 
     def __call__(self, x):
         return self._e(x)
+
+    def forward_segments(self, mels):
+        """mels[s] [1, num_mels, F_s] -> waveforms [1, 1, F_s * prod(upsample_rates)], each what self(mels[s]) gives, from one
+        generator pass over all of them (no counterpart in the reference, which vocodes one mel per call)"""
+        return self._e.forward_segments(mels)
+
+    def segment_gap(self) -> int:
+        return self._e.segment_gap()

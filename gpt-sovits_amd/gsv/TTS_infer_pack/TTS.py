@@ -751,10 +751,20 @@ class TTS:
 
     def _fold_audio(self, pred: torch.Tensor, lens: List[int], pad_len: int) -> List[torch.Tensor]:
         """the generated frames [chunks, 100, chunk_len] of one fold -> its sentences' waveforms (TTS.py:1581-1609)"""
+        audio = self.vocoder(self._fold_mel(pred))[0][0]
+        return self._fold_tail(audio, int(pred.shape[2]), lens, pad_len)
+
+    @staticmethod
+    def _fold_mel(pred: torch.Tensor) -> torch.Tensor:
+        """the generated frames [chunks, 100, chunk_len] of one fold as the one mel [1, 100, chunks * chunk_len] its vocoder
+        call takes (TTS.py:1581-1583)"""
+        return denorm_spec(pred.permute(1, 0, 2).contiguous().view(pred.shape[1], -1).unsqueeze(0))
+
+    def _fold_tail(self, audio: torch.Tensor, chunk_len: int, lens: List[int], pad_len: int) -> List[torch.Tensor]:
+        """the vocoded fold [chunks * chunk_len * upsample_rate] -> its sentences' waveforms: cut into the chunks' pieces, SOLA,
+        trim, split per sentence (TTS.py:1585-1609)"""
         vc = self.vocoder_configs
-        ov, up, chunk_len = vc["overlapped_len"], vc["upsample_rate"], pred.shape[2]
-        pred = pred.permute(1, 0, 2).contiguous().view(pred.shape[1], -1).unsqueeze(0)
-        audio = self.vocoder(denorm_spec(pred))[0][0]
+        ov, up = vc["overlapped_len"], vc["upsample_rate"]
         pieces, p = [], 0
         while p < audio.shape[-1]:
             pieces.append(audio[p:p + chunk_len * up])
@@ -1145,6 +1155,41 @@ class TTS:
         caps = {g: max(1, int(self.cfm_max_rows) // (2 if g[1] else 1)) for g in groups}
         return [rows[i:i + caps[g]] for g, rows in groups.items() for i in range(0, len(rows), caps[g])]
 
+    vocoder_max_frames = 32768    # mel frames of one shared vocoder pass.  No sweep of the cost per frame has been run yet
+                                  # (DESIGN.md section 4h): this is the initial cap, which keeps every gapped layout far
+                                  # below the engine's limit of 2^24 rows at the output rate for the v3 (x256) and v4 (x480)
+                                  # vocoders (plan_vocoder checks the limit itself, gaps included)
+
+    def plan_vocoder(self, plans: List[dict], gap: int = 0) -> List[List[Tuple[int, int]]]:
+        """The vocoder passes of run_batch(shared_cfm=True, shared_vocoder=True).  `plans[r]` = {"opts", "T_min", "cfm_folds"}
+        as plan_cfm takes them, after _shared_cfm_stage's flow-matching passes.  Shared: the folds plan_cfm shares (v3 / v4,
+        parallel_infer, at least one frame).  A fold's mel is chunks * chunk_len frames, chunks as _chunk_cuts cuts it with
+        its voice's chunk_len = T_chunk - T_min.  The folds fill passes in (r, bi) order; a pass ends before the fold that
+        would take it past vocoder_max_frames frames, or past the engine's 2^24 output rows (`gap` = the vocoder's
+        segment_gap() frames between neighbours), so a fold longer than the cap is a pass of its own.  Returns the passes,
+        lists of (r, bi)."""
+        if not getattr(self.configs, "use_vocoder", False):
+            return []
+        vc = self.vocoder_configs
+        rows_cap = (1 << 24) // int(vc["upsample_rate"])     # gapped frames of a pass stay below this
+        passes, cur, frames = [], [], 0
+        for r, pl in enumerate(plans):
+            if not pl["opts"]["parallel_infer"]:
+                continue
+            for bi, fold in enumerate(pl["cfm_folds"]):
+                if fold <= 0:
+                    continue
+                chunk_len = vc["T_chunk"] - int(pl["T_min"])
+                need = len(self._chunk_cuts(int(fold), chunk_len, vc["overlapped_len"])) * chunk_len
+                if cur and (frames + need > int(self.vocoder_max_frames) or frames + need + len(cur) * gap >= rows_cap):
+                    passes.append(cur)
+                    cur, frames = [], 0
+                cur.append((r, bi))
+                frames += need
+        if cur:
+            passes.append(cur)
+        return passes
+
     # ---- run_batch's stages: a plan is one request's dict, and a stage reads what the earlier ones wrote on it
     def _plan_request(self, req: dict) -> dict:
         """Stage 1, per request, what run() does before its AR loop.  Reads the request and seeds the host generators (after
@@ -1235,11 +1280,12 @@ class TTS:
                     plans[r]["frags"][bi][k] = wav[0, 0]
         self.vits_model.invalidate_refer()          # the engine's cached reference terms are the last slot's voice
 
-    def _shared_cfm_stage(self, plans: List[dict]) -> None:
+    def _shared_cfm_stage(self, plans: List[dict], shared_vocoder: bool = False) -> None:
         """shared_cfm, v3 / v4: every chunk of every fold that plan_cfm shares is one row, with its voice's prompt mel and the
-        noise key run() gives it, of a CFM.inference_rows pass; vocoder and SOLA stay per fold.  Reads `preds`, `kept`,
-        `voice`, `opts`, `actual_seed`, `data`.  Writes `cfm_folds` (feature frames per batch) and `T_min` (the voice's
-        prompt length), plan_cfm's inputs, and `frags[bi]` of every shared fold."""
+        noise key run() gives it, of a CFM.inference_rows pass; vocoder and SOLA stay per fold, unless shared_vocoder: then
+        the folds' mels go through the plan_vocoder passes of the vocoder's forward_segments, and only SOLA and the cuts stay
+        per fold.  Reads `preds`, `kept`, `voice`, `opts`, `actual_seed`, `data`.  Writes `cfm_folds` (feature frames per
+        batch) and `T_min` (the voice's prompt length), plan_cfm's inputs, and `frags[bi]` of every shared fold."""
         prompts: Dict[tuple, tuple] = {}            # _prompt_features() per distinct voice
         fold_in: Dict[Tuple[int, int], tuple] = {}  # (rows [chunks, T_chunk, 512], lens, pad_len)
         voice_of: List[Optional[tuple]] = [None] * len(plans)
@@ -1272,9 +1318,17 @@ class TTS:
             for n, (r, bi, k) in enumerate(rows):
                 fold_out.setdefault((r, bi), []).append(pred[n:n + 1, :, mels[n].shape[2]:])
         for (r, bi), got in fold_out.items():        # a fold is finished when all its rows are back
-            fea, lens, pad_len = fold_in[(r, bi)]
-            assert len(got) == fea.shape[0]
-            plans[r]["frags"][bi] = self._fold_audio(torch.cat(got, 0), lens, pad_len)
+            assert len(got) == fold_in[(r, bi)][0].shape[0]
+        if not shared_vocoder:
+            for (r, bi), got in fold_out.items():
+                _, lens, pad_len = fold_in[(r, bi)]
+                plans[r]["frags"][bi] = self._fold_audio(torch.cat(got, 0), lens, pad_len)
+            return
+        for folds in self.plan_vocoder(plans, gap=self.vocoder.segment_gap()):
+            audios = self.vocoder.forward_segments([self._fold_mel(torch.cat(fold_out[f], 0)) for f in folds])
+            for (r, bi), audio in zip(folds, audios):
+                _, lens, pad_len = fold_in[(r, bi)]
+                plans[r]["frags"][bi] = self._fold_tail(audio[0][0], int(fold_out[(r, bi)][0].shape[2]), lens, pad_len)
 
     def _finish_request(self, pl: dict, sr: int) -> Tuple[int, np.ndarray]:
         """Last stage, per request, with its voice as the prompt cache: the batches no shared stage took go through
@@ -1307,7 +1361,8 @@ class TTS:
 
     @torch.no_grad()
     def run_batch(self, requests: List[dict], shared_sovits: bool = False, shared_cfm: bool = False,
-                  shared_speed: bool = False, mixed_sampling: bool = False) -> List[Tuple[int, np.ndarray]]:
+                  shared_speed: bool = False, mixed_sampling: bool = False,
+                  shared_vocoder: bool = False) -> List[Tuple[int, np.ndarray]]:
         """Several requests, each with its own reference voice, through shared AR decodes.  Each request dict takes the
         keys run() accepts plus an optional "voice" (make_voice); without one it uses its ref_audio_path / prompt_text
         (through make_voice's LRU) or the current prompt cache.  Returns one (sr, int16 audio) per request, in order: what
@@ -1320,9 +1375,14 @@ class TTS:
         mixed_sampling=True: requests with different top_k / top_p / temperature / repetition_penalty share AR launches, each
         row sampling with its own request's values (plan_batch(mixed_sampling=True)); every request still gets the tokens it
         gets without the keyword.
+        shared_vocoder=True (with shared_cfm=True; ValueError without it on a v3 / v4 model): the folds of the shared
+        flow-matching stage are vocoded in shared segmented passes over all voices (plan_vocoder, the vocoder's
+        forward_segments) instead of one vocoder call per fold.
         No keyword changes anything for the other model family."""
         if self.t2s_model is None or self.vits_model is None:
             raise RuntimeError("init_t2s_weights / init_vits_weights first")
+        if shared_vocoder and self.configs.use_vocoder and not shared_cfm:
+            raise ValueError("shared_vocoder=True vocodes the folds of the shared flow-matching stage: pass shared_cfm=True too")
         self.stop_flag = False
         plans = [self._plan_request(req) for req in requests]
         self._ar_stage(plans, mixed_sampling=mixed_sampling)
@@ -1330,7 +1390,7 @@ class TTS:
         if shared_sovits and not self.configs.use_vocoder:
             self._shared_sovits_stage(plans, shared_speed=shared_speed)
         if shared_cfm and self.configs.use_vocoder:
-            self._shared_cfm_stage(plans)
+            self._shared_cfm_stage(plans, shared_vocoder=shared_vocoder)
         return [self._finish_request(pl, sr) for pl in plans]
 
     # ---- the pipeline (reference TTS.py:984-1365) ---------------------------------------------

@@ -122,6 +122,10 @@ _SIGS = {
     "gsv_vocoder_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
     "gsv_vocoder_finalize": (C.c_int, [C.c_void_p]),
     "gsv_vocoder_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "gsv_vocoder_forward_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
+    "gsv_vocoder_segment_gap": (C.c_int, [C.POINTER(VocoderConfig)]),
+    "gsv_vocoder_segment_map": (C.c_int, [C.POINTER(VocoderConfig), C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int32),
+                                          C.c_int64]),
     "gsv_cfm_create": (C.c_int, [C.POINTER(DitConfig), C.c_int, C.POINTER(C.c_void_p)]),
     "gsv_cfm_destroy": (None, [C.c_void_p]),
     "gsv_cfm_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
@@ -158,6 +162,8 @@ _SIGS = {
                                   C.c_int, C.c_float, C.c_int, C.c_void_p]),
     "gsv_op_conv_pair_seg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                       C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
+    "gsv_op_aa_act_cl": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "gsv_op_aff_mix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
     "gsv_op_time_mean": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "gsv_op_channel_norm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p,

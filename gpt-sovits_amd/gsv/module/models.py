@@ -363,6 +363,14 @@ class Generator:
             raise NotImplementedError("conditioning input g")
         return self._e(x)
 
+    def forward_segments(self, mels):
+        """mels[s] [1, initial_channel, F_s] -> waveforms [1, 1, F_s * prod(upsample_rates)], each what self(mels[s]) gives, from
+        one generator pass over all of them (no counterpart in the reference, which vocodes one mel per call)"""
+        return self._e.forward_segments(mels)
+
+    def segment_gap(self) -> int:
+        return self._e.segment_gap()
+
 
 def cfg_guided(rate) -> bool:
     """Is classifier-free guidance active at this rate?  The reference's test `rate > 1e-5` (models.py:1063), taken in fp32

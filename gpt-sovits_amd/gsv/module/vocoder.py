@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict
+from typing import Dict, List
 
 import torch
 
@@ -35,6 +35,7 @@ class _VocoderEngine:
                 cfg.rb_dilations[j][c] = d
         cfg.bias_at_final, cfg.tanh_at_final, cfg.snake_logscale = int(bias_at_final), int(tanh_at_final), int(snake_logscale)
         self.in_channels = in_channels
+        self._cfg = cfg
         with torch.cuda.device(self.device):
             _lib.init(idx)
             h = C.c_void_p()
@@ -80,5 +81,32 @@ class _VocoderEngine:
                                                       C.c_void_p(self.stream.cuda_stream)), "gsv_vocoder_forward")
             self.stream.synchronize()
         return wav.to(self.dtype).view(1, 1, -1)
+
+    def segment_gap(self) -> int:
+        """the gap G, in mel frames, forward_segments puts between neighbouring segments (host only)"""
+        return int(_lib.lib().gsv_vocoder_segment_gap(C.byref(self._cfg)))
+
+    @torch.no_grad()
+    def forward_segments(self, mels: List[torch.Tensor]) -> List[torch.Tensor]:
+        """mels[s] [1, in_channels, F_s] -> waveforms [1, 1, F_s * prod(upsample_rates)], each what forward(mels[s]) gives, from ONE
+        pass of the generator over all of them (`gsv_vocoder_forward_segments`): one pack, one call, one split"""
+        if not self._loaded:
+            raise RuntimeError("load_state_dict() first")
+        if len(mels) < 1:
+            raise ValueError("forward_segments needs at least one mel")
+        for mel in mels:
+            if mel.dim() != 3 or mel.shape[0] != 1 or mel.shape[1] != self.in_channels or mel.shape[2] < 1:
+                raise ValueError(f"expected mels of shape [1, {self.in_channels}, F>=1], got {tuple(mel.shape)}")
+        frames = [int(mel.shape[2]) for mel in mels]
+        up = math.prod(self.upsample_rates)
+        with torch.cuda.device(self.device):
+            m = torch.cat([mel[0].to(self.device, torch.float32) for mel in mels], 1).contiguous()
+            wav = torch.empty(sum(frames) * up, dtype=torch.float32, device=self.device)
+            self.stream.wait_stream(torch.cuda.current_stream(self.device))   # after the packing above
+            _lib.check(_lib.lib().gsv_vocoder_forward_segments(self._h, m.data_ptr(), len(frames), (C.c_int * len(frames))(*frames),
+                                                               wav.data_ptr(), C.c_void_p(self.stream.cuda_stream)),
+                       "gsv_vocoder_forward_segments")
+            self.stream.synchronize()
+        return [w.view(1, 1, -1) for w in torch.split(wav.to(self.dtype), [f * up for f in frames])]
 
     __call__ = forward

@@ -273,6 +273,21 @@ int gsv_vocoder_load_tensor(gsv_vocoder_t* h, const char* name, const float* dat
 int gsv_vocoder_finalize(gsv_vocoder_t* h);
 /* mel [dev] fp32 [in_channels][F] channels-first (as the reference passes it), wav [dev] fp32 [F * prod(up_rates)] */
 int gsv_vocoder_forward(gsv_vocoder_t* h, const float* mel, int F, float* wav, gsv_stream_t stream);
+/* Segmented pass: n independent mels (e.g. one per voice) through ONE pass of the generator.  The library lays the segments
+ * back to back with G zero "gap" frames between neighbours (G = gsv_vocoder_segment_gap(cfg), G * prod(up_rates[:i]) rows after
+ * upsampling stage i).  Every tensor a conv reads keeps its gap rows at 0, and BigVGAN's anti-aliased activation replicates
+ * each segment's own edge rows at both rates and never reads a gap row, so segment s yields what gsv_vocoder_forward of
+ * segment s alone yields.  mel [dev] fp32 [in_channels][sum frames], the segments packed without gaps; frames [host] [n];
+ * wav [dev] fp32 [sum frames * prod(up_rates)], segment s's samples back to back.  n == 1 is gsv_vocoder_forward itself.
+ * Errors before anything is launched: a null argument, n < 1 or n > 4096, a frames[s] < 1, a gapped layout of 2^24 rows or
+ * more at the output rate. */
+int gsv_vocoder_forward_segments(gsv_vocoder_t* h, const float* mel, int n, const int* frames, float* wav, gsv_stream_t stream);
+/* host-only planning helpers (no device needed), the counterparts of gsv_vits_segment_gap / gsv_vits_segment_map: the gap G in
+ * frames (-1 for a bad config), taken from the generator's shape by the rule of the SoVITS segmented decode (conv_pre, the
+ * transposed ups, every ResBlock conv at its resolution, conv_post), and the segment id (-1 = gap) of every row at `level`
+ * (0 = mel frames, i = after upsampling stage i): (sum frames + (n - 1) G) * prod(up_rates[:level]) rows into seg [cap]. */
+int gsv_vocoder_segment_gap(const gsv_vocoder_config* cfg);
+int gsv_vocoder_segment_map(const gsv_vocoder_config* cfg, int n, const int* frames, int level, int32_t* seg, int64_t cap);
 
 /* ---------------------------------------------------------------------------------------
  * v3 / v4 flow-matching mel decoder (H14): CFM.inference (module/models.py:1027-1085) over the DiT estimator
@@ -445,6 +460,14 @@ int gsv_op_conv_pair(const void* x, const void* w1, const float* b1, const void*
  * row_seg == NULL is GSV_ERR_ARG. */
 int gsv_op_conv_pair_seg(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y, int T, int C, int taps,
                          int dil, float scale, int accumulate, const int32_t* row_seg, gsv_stream_t stream);
+/* BigVGAN's anti-aliased snake / snakebeta on channels-last activations, the kernel the vocoder engine runs: x, y [dev] [T][C] of
+ * dtype, alpha / beta [dev] fp32 [C] (logscale != 0: stored as logarithms).  row_seg == NULL: replicate padding at rows 0 and
+ * T - 1.  Otherwise the form of a segmented pass (gsv_vocoder_forward_segments): row_seg [dev] int32 [T], the row's segment or -1
+ * for a gap row; seg_start / seg_len [dev] int32 [n_seg], segment s covers rows [seg_start[s], seg_start[s] + seg_len[s]).  Both
+ * replicate paddings stop at the row's own segment, gap rows of y are stored as 0 and gap rows of x are never used. */
+int gsv_op_aa_act_cl(const void* x, void* y, int T, int C, const float* alpha, const float* beta, int logscale,
+                     const int32_t* row_seg, const int32_t* seg_start, const int32_t* seg_len, int n_seg, int dtype,
+                     gsv_stream_t stream);
 int gsv_op_aff_mix(const float* x, const float* y, const float* t, long long n, float* out, gsv_stream_t stream);
 int gsv_op_time_mean(const float* x, int T, int ld, float* out, gsv_stream_t stream);
 int gsv_op_channel_norm(const void* x, int T, int C, const float* gamma, const float* beta, float eps, int act, float* scratch,

@@ -7,9 +7,15 @@ mixed prompt lengths.  Prints one JSON line; every mode lists the wall time of e
 gain can be read against the spread.
 
     python tools/multivoice_v3_bench.py [--requests 32] [--tokens 100] [--iters 3] [--plain-only] [--no-sweep] [--once]
+    python tools/multivoice_v3_bench.py --shared-vocoder [--no-sweep] [--once]
 
 --plain-only times run_batch() alone (also runs on a tree without shared_cfm); --once makes one shared call after the
 warm-up and nothing else (the run a kernel trace is taken of).
+--shared-vocoder: run_batch(shared_cfm=True, shared_vocoder=True) (all folds vocoded in shared segmented passes) against
+run_batch(shared_cfm=True) (one vocoder call per fold) in the same process, timed calls alternating, with the vocoder
+stage's own time per call under HIP events; then the sweep of frames per pass: forward_segments over segments of 600 frames
+up to 1 k ... 32 k frames in all, ms per 1 k frames and the device memory the pass added.  On a tree without the keyword it
+times run_batch(shared_cfm=True) alone (the parent's side of an alternating-process comparison).
 """
 import argparse
 import copy
@@ -50,6 +56,100 @@ def spread(xs):
     return {"median": round(statistics.median(xs), 4), "min": round(min(xs), 4), "max": round(max(xs), 4), "each": [round(x, 4) for x in xs]}
 
 
+class TimedVocoder:
+    """the vocoder with HIP events around every call: ms[i] = (start, end) of call i on the current stream (the engine's
+    stream waits for it and is synchronised before the call returns)"""
+
+    def __init__(self, inner):
+        self.inner, self.events = inner, []
+
+    def _timed(self, fn, *a):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn(*a)
+        e1.record()
+        self.events.append((e0, e1))
+        return out
+
+    def __call__(self, x):
+        return self._timed(self.inner, x)
+
+    def forward_segments(self, mels):
+        return self._timed(self.inner.forward_segments, mels)
+
+    def segment_gap(self):
+        return self.inner.segment_gap()
+
+    def take_ms(self):
+        torch.cuda.synchronize()
+        ms, self.events = sum(a.elapsed_time(b) for a, b in self.events), []
+        return ms
+
+
+def shared_vocoder_mode(a, tts, reqs, res, record, TTS):
+    from gsv import synthetic as S
+    has_kw = "shared_vocoder" in inspect.signature(TTS.run_batch).parameters
+    voc = tts.vocoder = TimedVocoder(tts.vocoder)
+    modes = {"run_batch_shared_cfm": dict(shared_cfm=True)}
+    if has_kw:
+        modes["run_batch_shared_vocoder"] = dict(shared_cfm=True, shared_vocoder=True)
+    if a.once:
+        kw = modes["run_batch_shared_vocoder" if has_kw else "run_batch_shared_cfm"]
+        for _ in range(2):
+            tts.run_batch(reqs, **kw)
+            torch.cuda.synchronize()
+        print(json.dumps(dict(res, mode="once", keywords=sorted(kw))))
+        return
+    outs, each, voc_ms, calls = {}, {m: [] for m in modes}, {m: [] for m in modes}, {}
+    for it in range(a.iters + 1):                        # first round: warm-up; the modes alternate call by call
+        for m, kw in modes.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            outs[m] = tts.run_batch(reqs, **kw)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            calls[m] = len(voc.events)
+            ms = voc.take_ms()
+            if it > 0:
+                each[m].append(dt)
+                voc_ms[m].append(ms)
+    for m in modes:
+        res[m] = dict(record(outs[m], each[m]), vocoder_calls_per_call=calls[m],
+                      vocoder_stage_ms={"median": round(statistics.median(voc_ms[m]), 2), "min": round(min(voc_ms[m]), 2),
+                                        "max": round(max(voc_ms[m]), 2)})
+    if has_kw:
+        x, y = outs["run_batch_shared_cfm"], outs["run_batch_shared_vocoder"]
+        res["vocoder_max_frames"] = tts.vocoder_max_frames
+        res["equal_lengths"] = f"{sum(int(p[1].shape == q[1].shape) for p, q in zip(x, y))}/{len(x)}"
+        res["speedup_shared_vocoder_over_shared_cfm"] = round(statistics.median(each["run_batch_shared_cfm"]) /
+                                                              statistics.median(each["run_batch_shared_vocoder"]), 3)
+        if not a.no_sweep:
+            sweep, seg = [], 600
+            for cap in (1024, 2048, 4096, 8192, 16384, 32768):
+                n = max(1, cap // seg)
+                mels = [S.hash_symmetric("mv3_voc", (1, 100, seg), 2.0, i).to(tts.configs.device) for i in range(n)]
+                free0 = torch.cuda.mem_get_info()[0]
+                ts = []
+                for it in range(a.iters + 1):            # first pass: warm-up (workspaces)
+                    voc.forward_segments(mels)
+                    ms = voc.take_ms()
+                    if it:
+                        ts.append(ms)
+                grown = free0 - torch.cuda.mem_get_info()[0]
+                ms = statistics.median(ts)
+                sweep.append({"cap": cap, "segments": n, "frames": n * seg, "ms": round(ms, 2), "ms_per_1k_frames": round(ms * 1000 / (n * seg), 3),
+                              "min_max_ms": [round(min(ts), 2), round(max(ts), 2)], "device_memory_added_mb": round(grown / 2 ** 20, 1)})
+                del mels
+            one = [S.hash_symmetric("mv3_voc", (1, 100, seg), 2.0, 0).to(tts.configs.device)]
+            ts = []
+            for it in range(a.iters + 1):
+                voc(one[0])
+                ts.append(voc.take_ms())
+            res["single_forward_600_frames_ms"] = round(statistics.median(ts[1:]), 2)
+            res["vocoder_frames_sweep"] = sweep
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--requests", type=int, default=32)
@@ -59,6 +159,7 @@ def main():
     ap.add_argument("--plain-only", action="store_true")
     ap.add_argument("--no-sweep", action="store_true")
     ap.add_argument("--once", action="store_true")
+    ap.add_argument("--shared-vocoder", action="store_true")
     a = ap.parse_args()
     from bench import make_segments
     from gsv import synthetic as S
@@ -98,6 +199,8 @@ def main():
         return {"audio_s": round(audio, 2), "ms_per_call": round(med * 1e3, 1), "audio_s_per_s": round(audio / med, 1), "call_s": spread(each)}
 
     res = {"requests": N, "tokens_per_request": a.tokens, "sample_steps": a.steps, "dtype": "f16"}
+    if a.shared_vocoder:
+        return shared_vocoder_mode(a, tts, reqs, res, record, TTS)
     if a.once:
         tts.run_batch(reqs, shared_cfm=True)
         torch.cuda.synchronize()

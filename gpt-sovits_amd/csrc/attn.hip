@@ -425,8 +425,8 @@ int launch_flash_rel96_f16(const void* q, int ldq, const void* k, int ldk, const
 // `rows` utterances of T frames in two launches.  q / k: [T][ld] with head h at columns h*64..; v likewise; row b of q, k and v
 // starts xz elements after row b-1, of out oz elements after; vt_buf: rows * vtz halfs of scratch, vtz >= heads * 64 * ceil32(T)
 int launch_flash_attn64_f16_rows(const void* q, int ldq, const void* k, int ldk, const void* v, int ldvv, void* vt_buf, int T, int heads,
-                                 float scale, void* out, int ldo, hipStream_t s, const float* rope_cs, int rope_half, bool vt_ready,
-                                 int rows, long long xz, long long vtz, long long oz) {
+                                 float scale, void* out, int ldo, hipStream_t s, const float* rope_cs, int rope_half, int rows,
+                                 long long xz, long long vtz, long long oz) {
   GSV_REQUIRE(T >= 1 && heads >= 1 && rows >= 1, "flash_attn: empty problem");
   GSV_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldo % 4 == 0 && ((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)out % 8) == 0,
               "flash_attn: operands must be 16-byte aligned with leading dims multiple of 8");
@@ -435,10 +435,8 @@ int launch_flash_attn64_f16_rows(const void* q, int ldq, const void* k, int ldk,
   GSV_REQUIRE(rows == 1 || (xz % 8 == 0 && vtz % 8 == 0 && oz % 4 == 0 && vtz >= (long long)heads * 64 * ldv),
               "flash_attn: row strides must keep every row 16-byte aligned and its V^T buffer apart");
   GSV_REQUIRE((long long)rows * planes <= 65535 && (long long)rows * heads <= 65535, "flash_attn: %d rows x %d heads exceed the grid", rows, heads);
-  if (!vt_ready)
-    hipLaunchKernelGGL(vt_kernel, dim3(ldv / 32, 2, rows * planes), dim3(256), 0, s, (const _Float16*)v, ldvv, T, ldv, (_Float16*)vt_buf,
-                       heads, (_Float16*)const_cast<void*>(q), ldq, (_Float16*)const_cast<void*>(k), ldk, rope_cs, rope_half, planes, xz,
-                       vtz);
+  hipLaunchKernelGGL(vt_kernel, dim3(ldv / 32, 2, rows * planes), dim3(256), 0, s, (const _Float16*)v, ldvv, T, ldv, (_Float16*)vt_buf, heads,
+                     (_Float16*)const_cast<void*>(q), ldq, (_Float16*)const_cast<void*>(k), ldk, rope_cs, rope_half, planes, xz, vtz);
   static const int qt_env = getenv("GSV_FLASH_QT") ? atoi(getenv("GSV_FLASH_QT")) : 0;     // A/B switch
   // more query tiles per workgroup = fewer K / V fragment loads per query, but fewer workgroups: keep >= ~1 per CU.  Chosen
   // from ONE row's size whatever `rows` is, so that a row computes the same bits alone and in a batch.
@@ -449,8 +447,8 @@ int launch_flash_attn64_f16_rows(const void* q, int ldq, const void* k, int ldk,
 }
 
 int launch_flash_attn64_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldvv, void* vt_buf, int T, int heads,
-                            float scale, void* out, int ldo, hipStream_t s, const float* rope_cs, int rope_half, bool vt_ready) {
-  return launch_flash_attn64_f16_rows(q, ldq, k, ldk, v, ldvv, vt_buf, T, heads, scale, out, ldo, s, rope_cs, rope_half, vt_ready, 1, 0, 0, 0);
+                            float scale, void* out, int ldo, hipStream_t s, const float* rope_cs, int rope_half) {
+  return launch_flash_attn64_f16_rows(q, ldq, k, ldk, v, ldvv, vt_buf, T, heads, scale, out, ldo, s, rope_cs, rope_half, 1, 0, 0, 0);
 }
 
 }  // namespace gsv

@@ -146,17 +146,18 @@ __global__ __launch_bounds__(256) void cfm_ln_mod_kernel(const T* __restrict__ x
 
 template <typename T>
 int launch_ln_mod(const void* x, const float* scale, const float* shift, int rows, int C, void* y, hipStream_t s) {
-  const dim3 grid(cdiv(rows, 4)), block(256);
+  auto launch = [&](auto npl) -> int {
+    GSV_LAUNCH((cfm_ln_mod_kernel<T, decltype(npl)::value>), dim3(cdiv(rows, 4)), dim3(256), 0, s, (const T*)x, scale, shift, rows, C, (T*)y);
+    return GSV_OK;
+  };
   switch (C / 64) {
-    case 2: hipLaunchKernelGGL((cfm_ln_mod_kernel<T, 2>), grid, block, 0, s, (const T*)x, scale, shift, rows, C, (T*)y); break;
-    case 4: hipLaunchKernelGGL((cfm_ln_mod_kernel<T, 4>), grid, block, 0, s, (const T*)x, scale, shift, rows, C, (T*)y); break;
-    case 8: hipLaunchKernelGGL((cfm_ln_mod_kernel<T, 8>), grid, block, 0, s, (const T*)x, scale, shift, rows, C, (T*)y); break;
-    case 16: hipLaunchKernelGGL((cfm_ln_mod_kernel<T, 16>), grid, block, 0, s, (const T*)x, scale, shift, rows, C, (T*)y); break;
-    case 32: hipLaunchKernelGGL((cfm_ln_mod_kernel<T, 32>), grid, block, 0, s, (const T*)x, scale, shift, rows, C, (T*)y); break;
+    case 2: return launch(std::integral_constant<int, 2>{});
+    case 4: return launch(std::integral_constant<int, 4>{});
+    case 8: return launch(std::integral_constant<int, 8>{});
+    case 16: return launch(std::integral_constant<int, 16>{});
+    case 32: return launch(std::integral_constant<int, 32>{});
     default: set_error("cfm: dim %d is not one of 128, 256, 512, 1024, 2048", C); return GSV_ERR_ARG;
   }
-  GSV_HIP(hipGetLastError());
-  return GSV_OK;
 }
 
 // rotary embedding on the first 2*half channels of the q and k projections (x_transformers' apply_rotary_pos_emb on the
@@ -233,27 +234,14 @@ __global__ void cfm_init_x_kernel(const float* __restrict__ noise, const CfmRow*
 }
 
 // Euler update x += d * v (frames >= Tp; prompt frames stay 0, models.py:1083-1084) and refresh the x columns of the DiT input;
-// rows = batch * Tn, the prompt region restarts per utterance with that utterance's own length
-template <typename T>
-__global__ void cfm_euler_kernel(float* __restrict__ x, const float* __restrict__ v, float d, int rows, int Tn,
+// rows = batch * Tn, the prompt region restarts per utterance with that utterance's own length.
+// GUIDED (models.py:1063-1084): v holds the conditioned estimate of request b in DiT row b and the unconditioned one in its
+// twin, row B + b (rows = B * Tn frames of requests, so the twin of frame i is frame rows + i).  x += d * (v_pos + (v_pos -
+// v_neg) * rate) in fp32, and the refreshed x goes into the x columns of BOTH rows: the two estimates of the next step see the
+// same state.  The unguided form reads one estimate and never sees `rate`.
+template <typename T, bool GUIDED>
+__global__ void cfm_euler_kernel(float* __restrict__ x, const float* __restrict__ v, float d, float rate, int rows, int Tn,
                                  const CfmRow* __restrict__ rw, int C, T* __restrict__ xin, int ldin) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long long)rows * C) return;
-  int row = (int)(i / C), c = (int)(i - (long long)row * C);
-  const int b = row / Tn, t = row - b * Tn;
-  const int Tp = rw[b].Tp;
-  float u = t < Tp ? 0.f : x[i] + (v ? d * v[i] : 0.f);
-  x[i] = u;
-  xin[(long long)row * ldin + c] = (T)u;
-}
-
-// The Euler update of a guided pass (models.py:1063-1084): v holds the conditioned estimate of request b in DiT row b and the
-// unconditioned one in its twin, row B + b (rows = B * Tn frames of requests, so the twin of frame i is frame rows + i).
-// x += d * (v_pos + (v_pos - v_neg) * rate) in fp32, prompt frames held at 0, and the refreshed x goes into the x columns of
-// BOTH rows: the two estimates of the next step see the same state.
-template <typename T>
-__global__ void cfm_euler_cfg_kernel(float* __restrict__ x, const float* __restrict__ v, float d, float rate, int rows, int Tn,
-                                     const CfmRow* __restrict__ rw, int C, T* __restrict__ xin, int ldin) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long n = (long long)rows * C;
   if (i >= n) return;
@@ -262,15 +250,19 @@ __global__ void cfm_euler_cfg_kernel(float* __restrict__ x, const float* __restr
   const int Tp = rw[b].Tp;
   float u = 0.f;
   if (t >= Tp) {
-    u = x[i];
-    if (v) {
-      const float vp = v[i], vn = v[n + i];
-      u += d * (vp + (vp - vn) * rate);
+    if constexpr (GUIDED) {
+      u = x[i];
+      if (v) {
+        const float vp = v[i], vn = v[n + i];
+        u += d * (vp + (vp - vn) * rate);
+      }
+    } else {
+      u = x[i] + (v ? d * v[i] : 0.f);
     }
   }
   x[i] = u;
   xin[(long long)row * ldin + c] = (T)u;
-  xin[((long long)rows + row) * ldin + c] = (T)u;
+  if constexpr (GUIDED) xin[((long long)rows + row) * ldin + c] = (T)u;
 }
 
 // prompt mel (channels-first [C][Tp]) -> the cond columns of the DiT input, zero after the prompt; also zeroes the pad columns
@@ -330,20 +322,10 @@ struct gsv_cfm {
   bool materialized_attn = false;   // GSV_CFM_MATERIALIZED_ATTN=1: A/B switch back to the 4-launch scores/softmax/PV path
 };
 
-#define CFM_LAUNCH(kern, n, ...)                                                                         \
-  do {                                                                                                   \
-    hipLaunchKernelGGL(kern, dim3(nblk((long long)(n))), dim3(256), 0, s, __VA_ARGS__);                 \
-    GSV_HIP(hipGetLastError());                                                                          \
-  } while (0)
-
-// the same over B utterances: blockIdx.y = utterance
-#define CFM_LAUNCH_ROWS(kern, n, B, ...)                                                                 \
-  do {                                                                                                   \
-    hipLaunchKernelGGL(kern, dim3(nblk((long long)(n)), (B)), dim3(256), 0, s, __VA_ARGS__);            \
-    GSV_HIP(hipGetLastError());                                                                          \
-  } while (0)
-
 namespace {
+
+// grid of the elementwise kernels: one thread of a 256-thread workgroup per element of n, blockIdx.y = utterance
+inline dim3 cfm_grid(long long n, int B = 1) { return dim3(nblk(n), B); }
 
 // time-independent precomputation for all n steps: mods[l][i][6D] (l < depth) and mods[depth][i][2D]
 template <typename T>
@@ -369,8 +351,8 @@ int cfm_modulations(gsv_cfm* c, hipStream_t s, int N, float** mods_out) {
     GSV_HIP(hipMemcpyAsync(tvals, tv.data(), tv.size() * 4, hipMemcpyHostToDevice, s));
     GSV_HIP(hipStreamSynchronize(s));   // tv lives on this stack frame
   }
-  CFM_LAUNCH(cfm_sinus_kernel, 2 * N * 128, tvals, 2 * N, 128, sinus);
-  CFM_LAUNCH(cfm_cast_rows_kernel<T>, 2 * N * 256, sinus, 256, 2 * N, 256, (T*)sin_t, 256, 0);
+  GSV_LAUNCH(cfm_sinus_kernel, cfm_grid(2 * N * 128), dim3(256), 0, s, tvals, 2 * N, 128, sinus);
+  GSV_LAUNCH(cfm_cast_rows_kernel<T>, cfm_grid(2 * N * 256), dim3(256), 0, s, sinus, 256, 2 * N, 256, (T*)sin_t, 256, 0);
   ConvOpt o1; o1.post_act = ACT_SILU;
   ConvOpt o2; o2.out_f32 = 1;
   // rows [0, N): time_embed(t_i); rows [N, 2N): d_embed(d)   (dit.py:149-153)
@@ -378,7 +360,7 @@ int cfm_modulations(gsv_cfm* c, hipStream_t s, int N, float** mods_out) {
   GSV_RC(conv(h, s, c->t2, mid_t, D, N, temb, N, o2));
   GSV_RC(conv(h, s, c->d0, (const T*)sin_t + (size_t)N * 256, 256, N, (T*)mid_t + (size_t)N * D, N, o1));
   GSV_RC(conv(h, s, c->d2, (const T*)mid_t + (size_t)N * D, D, N, temb + (size_t)N * D, N, o2));
-  CFM_LAUNCH(cfm_add_silu_kernel<T>, (long long)N * D, temb, temb + (size_t)N * D, (long long)N * D, (T*)stemb);
+  GSV_LAUNCH(cfm_add_silu_kernel<T>, cfm_grid((long long)N * D), dim3(256), 0, s, temb, temb + (size_t)N * D, (long long)N * D, (T*)stemb);
   for (int l = 0; l < g.depth; ++l)
     GSV_RC(conv(h, s, c->blocks[l].mod, stemb, D, N, mods + (size_t)l * N * 6 * D, N, o2));
   GSV_RC(conv(h, s, c->final_mod, stemb, D, N, mods + (size_t)g.depth * N * 6 * D, N, o2));
@@ -396,7 +378,7 @@ int cfm_modulations(gsv_cfm* c, hipStream_t s, int N, float** mods_out) {
 // Classifier-free guidance (cfg_rate > CFM_CFG_THRESHOLD, models.py:1063-1081): the DiT runs over 2 B rows.  Rows [0, B) are
 // the requests as above; row B + b is request b's unconditioned twin -- the same x columns, zero cond columns, and the null
 // text embedding (the text stack run on ONE extra row of zero text, then copied into every twin: it depends on Tn alone).
-// The Euler state, the noise draw and the output stay B rows; cfm_euler_cfg_kernel combines the two estimates.  Unguided,
+// The Euler state, the noise draw and the output stay B rows; cfm_euler_kernel<T, true> combines the two estimates.  Unguided,
 // DB == B and every launch below is the one it was.
 constexpr float CFM_CFG_THRESHOLD = 1e-5f;
 
@@ -425,8 +407,7 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
     const int n = std::min(CFM_ROW_CHUNK, DB - b0);
     CfmRowChunk ch{};
     std::copy_n(table.begin() + b0, n, ch.r);
-    hipLaunchKernelGGL(cfm_rows_fill_kernel, dim3(1), dim3(CFM_ROW_CHUNK), 0, s, ch, n, rw + b0);
-    GSV_HIP(hipGetLastError());
+    GSV_LAUNCH(cfm_rows_fill_kernel, dim3(1), dim3(CFM_ROW_CHUNK), 0, s, ch, n, rw + b0);
   }
   float *x, *v, *cs, *gx;
   void *xin, *ta, *tb, *tw, *hb, *c1, *nrm, *qkv, *ao, *ff;
@@ -447,37 +428,37 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
   auto rows = [&](void* p, int b, int width) { return (void*)((char*)p + (size_t)b * Tn * width * es); };
 
   // ---- per-utterance constants: text embedding (dit.py:50-72), cond columns, rotary table
-  CFM_LAUNCH_ROWS(cfm_text_pos_kernel<T>, (long long)Tn * td, TB, mu, B, c->pos_table, Tn, td, (T*)ta);
+  GSV_LAUNCH(cfm_text_pos_kernel<T>, cfm_grid((long long)Tn * td, TB), dim3(256), 0, s, mu, B, c->pos_table, Tn, td, (T*)ta);
   for (auto& blk : c->text) {
-    CFM_LAUNCH_ROWS(cfm_dwconv7_kernel<T>, (long long)Tn * td, TB, (const T*)ta, blk.dw, blk.db, Tn, td, (T*)tb);
+    GSV_LAUNCH(cfm_dwconv7_kernel<T>, cfm_grid((long long)Tn * td, TB), dim3(256), 0, s, (const T*)ta, blk.dw, blk.db, Tn, td, (T*)tb);
     GSV_RC(launch_layernorm(h->dtype, tb, 0, nullptr, 0, blk.ng, blk.nb, tb, 0, RT, td, 1e-6f, s));
     ConvOpt og; og.post_act = ACT_GELU;
     GSV_RC(conv(h, s, blk.pw1, tb, td, RT, tw, RT, og));
     // GRN statistics are per utterance (norm over its own frames): gx [TB][2 td]
-    hipLaunchKernelGGL(cfm_grn_norm_kernel<T>, dim3(cdiv(2 * td, 64), TB), dim3(256), 0, s, (const T*)tw, Tn, 2 * td, gx);
-    hipLaunchKernelGGL(cfm_grn_apply_kernel<T>, dim3(std::min(1024, nblk((long long)Tn * 2 * td)), TB), dim3(256), 0, s, (T*)tw, gx,
-                       blk.gg, blk.gb, Tn, 2 * td);
-    GSV_HIP(hipGetLastError());
+    GSV_LAUNCH(cfm_grn_norm_kernel<T>, dim3(cdiv(2 * td, 64), TB), dim3(256), 0, s, (const T*)tw, Tn, 2 * td, gx);
+    GSV_LAUNCH(cfm_grn_apply_kernel<T>, dim3(std::min(1024, nblk((long long)Tn * 2 * td)), TB), dim3(256), 0, s, (T*)tw, gx, blk.gg, blk.gb,
+               Tn, 2 * td);
     ConvOpt orr; orr.res = ta;
     GSV_RC(conv(h, s, blk.pw2, tw, 2 * td, RT, ta, RT, orr));
   }
   {
     const int W = md + (ldin - (2 * md + td));
-    CFM_LAUNCH_ROWS(cfm_cond_kernel<T>, (long long)Tn * W, DB, rw, Tn, md, (T*)xin, ldin, md, 2 * md + td);
-    hipLaunchKernelGGL((cfm_copy_cols_kernel<T>), dim3(nblk((long long)RX * td)), dim3(256), 0, s, (const T*)ta, td, RX, td, (T*)xin,
-                       ldin, 2 * md);
-    GSV_HIP(hipGetLastError());
+    GSV_LAUNCH(cfm_cond_kernel<T>, cfm_grid((long long)Tn * W, DB), dim3(256), 0, s, rw, Tn, md, (T*)xin, ldin, md, 2 * md + td);
+    GSV_LAUNCH(cfm_copy_cols_kernel<T>, cfm_grid((long long)RX * td), dim3(256), 0, s, (const T*)ta, td, RX, td, (T*)xin, ldin, 2 * md);
     if (guided)   // text row B of ta is the null text embedding: into the text columns of the B twins
-      CFM_LAUNCH_ROWS(cfm_bcast_cols_kernel<T>, (long long)Tn * td, B, (const T*)rows(ta, B, td), Tn, td, (T*)rows(xin, B, ldin), ldin,
-                      2 * md);
+      GSV_LAUNCH(cfm_bcast_cols_kernel<T>, cfm_grid((long long)Tn * td, B), dim3(256), 0, s, (const T*)rows(ta, B, td), Tn, td,
+                 (T*)rows(xin, B, ldin), ldin, 2 * md);
   }
-  CFM_LAUNCH(cfm_rope_table_kernel, Tn * half, Tn, half, cs);
-  CFM_LAUNCH_ROWS(cfm_init_x_kernel, (long long)Tn * md, B, noise, rw, temperature, Tn, md, x);
+  GSV_LAUNCH(cfm_rope_table_kernel, cfm_grid(Tn * half), dim3(256), 0, s, Tn, half, cs);
+  GSV_LAUNCH(cfm_init_x_kernel, cfm_grid((long long)Tn * md, B), dim3(256), 0, s, noise, rw, temperature, Tn, md, x);
   // x -> the x columns of the DiT input (v null: no update yet), and after every step the Euler update
   auto euler = [&](const float* vv, float dd) -> int {
-    if (guided) CFM_LAUNCH(cfm_euler_cfg_kernel<T>, (long long)RX * md, x, vv, dd, cfg_rate, RX, Tn, rw, md, (T*)xin, ldin);
-    else CFM_LAUNCH(cfm_euler_kernel<T>, (long long)RX * md, x, vv, dd, RX, Tn, rw, md, (T*)xin, ldin);
-    return GSV_OK;
+    auto launch = [&](auto G) -> int {
+      GSV_LAUNCH((cfm_euler_kernel<T, decltype(G)::value>), cfm_grid((long long)RX * md), dim3(256), 0, s, x, vv, dd, cfg_rate, RX, Tn, rw, md,
+                 (T*)xin, ldin);
+      return GSV_OK;
+    };
+    return guided ? launch(std::true_type{}) : launch(std::false_type{});
   };
   GSV_RC(euler(nullptr, 0.f));
 
@@ -514,26 +495,14 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
       const float* m = mods + ((size_t)l * N + step) * 6 * D;   // shift_a, scale_a, gate_a, shift_m, scale_m, gate_m
       GSV_RC(launch_ln_mod<T>(hb, m + D, m, R, D, nrm, s));
       const int wnt = l >= resident ? 1 : 0;
-      // OPT-IN (GSV_CFM_QKV_FUSE=1): the QKV GEMM's epilogue applies the rotary embedding and stores V transposed, one launch per
-      // block less.  Measured at the v3 shape (T = 934): 2.472 vs 2.474 ms per Euler step -- no gain (the 5 us launch it removes
-      // comes back as a heavier epilogue of the V column tiles on a grid that fills 75 % of the CUs), so the separate launch,
-      // which the parity tests cover at every shape, stays the default
-      static const bool want_fuse = getenv("GSV_CFM_QKV_FUSE") != nullptr;
-      const bool fuse_qkv = flash && DB == 1 && R >= 512 && want_fuse && (2 * inner) % 128 == 0;
-      {
-        ConvOpt oq; oq.w_nt = wnt;
-        if (fuse_qkv) {
-          oq.vt_out = vtb; oq.vt_col0 = 2 * inner; oq.vt_ld = (Tn + 31) / 32 * 32;
-          oq.rope_cs = cs; oq.rope_half = half; oq.rope_q0 = 0; oq.rope_k0 = inner;
-        }
-        GSV_RC(conv(h, s, blk.qkv, nrm, D, R, qkv, R, oq));
-      }
-      if (!flash) CFM_LAUNCH(cfm_rope_kernel<T>, R * half * 2, (T*)qkv, 3 * inner, inner, R, Tn, half, cs);   // else inside the V^T launch
+      ConvOpt oq; oq.w_nt = wnt;   // rotary + V^T as this GEMM's epilogue was tried: no gain over the V^T launch
+      GSV_RC(conv(h, s, blk.qkv, nrm, D, R, qkv, R, oq));
       if (flash) {   // every utterance in the same two launches (V^T + rotary, attention): the row is a grid dimension
         const _Float16* qb = (const _Float16*)qkv;
         GSV_RC(launch_flash_attn64_f16_rows(qb, 3 * inner, qb + inner, 3 * inner, qb + 2 * inner, 3 * inner, vtb, Tn, g.heads, att_scale,
-                                            ao, inner, s, cs, half, fuse_qkv, DB, (long long)Tn * 3 * inner, vtz, (long long)Tn * inner));
+                                            ao, inner, s, cs, half, DB, (long long)Tn * 3 * inner, vtz, (long long)Tn * inner));
       } else {
+        GSV_LAUNCH(cfm_rope_kernel<T>, cfm_grid(R * half * 2), dim3(256), 0, s, (T*)qkv, 3 * inner, inner, R, Tn, half, cs);
         for (int b = 0; b < DB; ++b) {
           const T* qb = (const T*)rows(qkv, b, 3 * inner);
           GSV_RC(attention(h, s, qb, 3 * inner, 0, qb, 3 * inner, inner, 2 * inner, Tn, Tn, g.heads, g.dim_head, att_scale, nullptr,
@@ -555,31 +524,34 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
     GSV_RC(conv(h, s, c->proj_out, nrm, D, R, v, R, ov));
     GSV_RC(euler(v, d));
   }
-  CFM_LAUNCH_ROWS(cfm_out_kernel, (long long)Tn * md, B, x, rw, Tn, md, out);
+  GSV_LAUNCH(cfm_out_kernel, cfm_grid((long long)Tn * md, B), dim3(256), 0, s, x, rw, Tn, md, out);
   return GSV_OK;
 }
 
-int cfm_run(gsv_cfm* c, hipStream_t s, const float* mu, const std::vector<CfmRow>& rows, int T, int N, const float* noise,
+template <typename T>
+int cfm_run(gsv_cfm* c, hipStream_t s, const float* mu, const std::vector<CfmRow>& rows, int Tn, int N, const float* noise,
             float temperature, float cfg_rate, float* out) {
   float* mods = nullptr;
-  if (c->ctx.dtype == GSV_F16) {
-    GSV_RC(cfm_modulations<_Float16>(c, s, N, &mods));
-    return cfm_infer_batch<_Float16>(c, s, mods, mu, rows, T, N, noise, temperature, cfg_rate, out);
-  }
-  GSV_RC(cfm_modulations<float>(c, s, N, &mods));
-  return cfm_infer_batch<float>(c, s, mods, mu, rows, T, N, noise, temperature, cfg_rate, out);
+  GSV_RC(cfm_modulations<T>(c, s, N, &mods));
+  return cfm_infer_batch<T>(c, s, mods, mu, rows, Tn, N, noise, temperature, cfg_rate, out);
 }
 
-// the row table of the two rows-form entries, checked before anything is launched
-int cfm_row_table(gsv_cfm* c, const char* who, const float* const* prompts, const int* Tp, int B, int T, const uint64_t* seeds,
-                  std::vector<CfmRow>* rows) {
-  rows->resize(B);
+// What the three entry points share: the argument checks, the row table (row b: its own prompt, prompt length and noise key),
+// all before anything is launched, then the pass.  `who` names the entry point in the messages.
+int cfm_entry(gsv_cfm* c, const char* who, const float* mu, const float* const* prompts, const int* Tp, int B, int Tn, int n_steps,
+              const float* noise, const uint64_t* seeds, float temperature, float cfg_rate, float* out, gsv_stream_t stream) {
+  GSV_REQUIRE(c && c->finalized, "%s: handle not finalized", who);
+  GSV_REQUIRE(mu && out && Tp && B > 0 && Tn > 0 && n_steps > 0 && n_steps <= 1024, "%s: bad argument", who);
+  const bool guided = cfg_rate > CFM_CFG_THRESHOLD;           // the DiT then sees every row and its unconditioned twin
+  GSV_REQUIRE(B <= 65535 / (guided ? 2 : 1), "%s: %d rows%s exceed the grid's 65535", who, B, guided ? " and their unconditioned twins" : "");
+  GSV_REQUIRE(noise || seeds, "%s: neither noise nor seeds given", who);
+  std::vector<CfmRow> rows(B);
   for (int b = 0; b < B; ++b) {
-    GSV_REQUIRE(Tp[b] >= 0 && Tp[b] <= T && (Tp[b] == 0 || (prompts && prompts[b])),
-                "%s: row %d: prompt length %d does not fit %d frames, or its prompt is null", who, b, Tp[b], T);
-    (*rows)[b] = CfmRow{Tp[b] ? prompts[b] : nullptr, seeds ? (unsigned long long)seeds[b] : 0ull, Tp[b], 0};
+    GSV_REQUIRE(Tp[b] >= 0 && Tp[b] <= Tn && (Tp[b] == 0 || (prompts && prompts[b])),
+                "%s: row %d: prompt length %d does not fit %d frames, or its prompt is null", who, b, Tp[b], Tn);
+    rows[b] = CfmRow{Tp[b] ? prompts[b] : nullptr, seeds ? (unsigned long long)seeds[b] : 0ull, Tp[b], 0};
   }
-  return GSV_OK;
+  return GSV_WITH_T(&c->ctx, cfm_run<T>(c, (hipStream_t)stream, mu, rows, Tn, n_steps, noise, temperature, cfg_rate, out));
 }
 
 }  // namespace
@@ -678,39 +650,29 @@ int gsv_cfm_finalize(gsv_cfm_t* c) {
 
 int gsv_cfm_inference(gsv_cfm_t* c, const float* mu, const float* prompt, int B, int T, int Tp, int n_steps, const float* noise,
                       float temperature, uint64_t seed, float* out, gsv_stream_t stream) {
-  GSV_REQUIRE(c && c->finalized, "cfm_inference: handle not finalized");
-  GSV_REQUIRE(mu && out && B > 0 && T > 0 && n_steps > 0 && n_steps <= 1024, "cfm_inference: bad argument");
-  GSV_REQUIRE(Tp >= 0 && Tp <= T && (Tp == 0 || prompt), "cfm_inference: prompt length %d does not fit %d frames", Tp, T);
-  std::vector<CfmRow> rows(B);
-  for (int b = 0; b < B; ++b)
-    rows[b] = CfmRow{Tp ? prompt + (size_t)b * c->cfg.mel_dim * Tp : nullptr, seed + 0x9E3779B97F4A7C15ull * (unsigned long long)b, Tp, 0};
-  return cfm_run(c, (hipStream_t)stream, mu, rows, T, n_steps, noise, temperature, 0.f, out);
+  // the uniform table: row b's prompt is slab b of `prompt`, its noise key is derived from `seed`.  A call that cfm_entry
+  // rejects before it reads a row (no handle, B out of range) gets an empty one.
+  const int n = c && B > 0 && B <= 65535 ? B : 0;
+  std::vector<const float*> prompts(n);
+  std::vector<int> tps(n, Tp);
+  std::vector<uint64_t> seeds(n);
+  for (int b = 0; b < n; ++b) {
+    prompts[b] = prompt && Tp > 0 ? prompt + (size_t)b * c->cfg.mel_dim * Tp : nullptr;
+    seeds[b] = seed + 0x9E3779B97F4A7C15ull * (uint64_t)b;
+  }
+  return cfm_entry(c, "cfm_inference", mu, prompts.data(), tps.data(), B, T, n_steps, noise, seeds.data(), temperature, 0.f, out, stream);
 }
 
 int gsv_cfm_inference_rows(gsv_cfm_t* c, const float* mu, const float* const* prompts, const int* Tp, int B, int T, int n_steps,
                            const float* noise, const uint64_t* seeds, float temperature, float* out, gsv_stream_t stream) {
-  GSV_REQUIRE(c && c->finalized, "cfm_inference_rows: handle not finalized");
-  GSV_REQUIRE(mu && out && Tp && B > 0 && T > 0 && n_steps > 0 && n_steps <= 1024, "cfm_inference_rows: bad argument");
-  GSV_REQUIRE(B <= 65535, "cfm_inference_rows: %d rows exceed the grid's 65535", B);
-  GSV_REQUIRE(noise || seeds, "cfm_inference_rows: neither noise nor seeds given");
-  std::vector<CfmRow> rows;
-  GSV_RC(cfm_row_table(c, "cfm_inference_rows", prompts, Tp, B, T, seeds, &rows));
-  return cfm_run(c, (hipStream_t)stream, mu, rows, T, n_steps, noise, temperature, 0.f, out);
+  return cfm_entry(c, "cfm_inference_rows", mu, prompts, Tp, B, T, n_steps, noise, seeds, temperature, 0.f, out, stream);
 }
 
 int gsv_cfm_inference_guided(gsv_cfm_t* c, const float* mu, const float* const* prompts, const int* Tp, int B, int T, int n_steps,
                              const float* noise, const uint64_t* seeds, float temperature, float cfg_rate, float* out,
                              gsv_stream_t stream) {
-  GSV_REQUIRE(c && c->finalized, "cfm_inference_guided: handle not finalized");
-  GSV_REQUIRE(mu && out && Tp && B > 0 && T > 0 && n_steps > 0 && n_steps <= 1024, "cfm_inference_guided: bad argument");
   GSV_REQUIRE(std::isfinite(cfg_rate), "cfm_inference_guided: cfg_rate is not finite");
-  const bool guided = cfg_rate > CFM_CFG_THRESHOLD;
-  GSV_REQUIRE(B <= (guided ? 65535 / 2 : 65535), "cfm_inference_guided: %d rows (%d with their unconditioned twins) exceed the grid's 65535",
-              B, guided ? 2 * B : B);
-  GSV_REQUIRE(noise || seeds, "cfm_inference_guided: neither noise nor seeds given");
-  std::vector<CfmRow> rows;
-  GSV_RC(cfm_row_table(c, "cfm_inference_guided", prompts, Tp, B, T, seeds, &rows));
-  return cfm_run(c, (hipStream_t)stream, mu, rows, T, n_steps, noise, temperature, cfg_rate, out);
+  return cfm_entry(c, "cfm_inference_guided", mu, prompts, Tp, B, T, n_steps, noise, seeds, temperature, cfg_rate, out, stream);
 }
 
 }  // extern "C"

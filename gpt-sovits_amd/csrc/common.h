@@ -177,14 +177,6 @@ struct ConvArgs {
   int xcd_order = 0;                         // set by the launcher: 1 = decode tile ids through xcd_virtual_id
   int w_nt = 0;                              // weights are loaded non-temporal (streamed once per step: keep them out of the
                                              // Infinity Cache so that OTHER layers' weights stay resident), GEMM paths only
-  // DiT QKV projection (gemm_lds_kernel, fp16 only): the epilogue of the q / k column tiles applies the rotary embedding to the
-  // first 2 * rope_half channels of q (columns rope_q0 ..) and k (rope_k0 ..), and the v column tiles (columns >= vt_col0) are
-  // stored TRANSPOSED as vt[(col - vt_col0)][t] (leading dim vt_ld >= T_virt rounded up to 32, zeros beyond T_virt) instead of
-  // into y -- what attn.hip's vt_kernel did in a launch of its own
-  void* vt_out = nullptr;
-  int vt_col0 = 0, vt_ld = 0;
-  const float* rope_cs = nullptr;            // [T][rope_half][2] cos, sin
-  int rope_half = 0, rope_q0 = 0, rope_k0 = 0;
   int z_res = 0;                             // batched launch (Z > 1) whose residual has its own slice stride rz: takes the LDS GEMM
                                              // path (bwe.hip; other batched launches with a residual keep the generic kernel)
   // segmented decode (vits.hip gsv_vits_decode_segments): one int32 per OUTPUT row, the row's segment or -1 for a gap row.
@@ -242,13 +234,12 @@ int launch_conv_pair_seg(const ConvPairArgs& a, const int* row_seg, hipStream_t 
 // fused attention, fp16, head dim 64 (attn.hip); vt_buf: heads * 64 * ceil32(T) halfs of scratch
 // rope_cs != null: rotate the first 2*rope_half channels of q and k in place first (cos|sin table [T][rope_half][2])
 int launch_flash_attn64_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* vt_buf, int T, int heads,
-                            float scale, void* out, int ldo, hipStream_t s, const float* rope_cs = nullptr, int rope_half = 0,
-                            bool vt_ready = false);   // vt_ready: V^T (and the rotary embedding) already produced by the QKV GEMM's epilogue
+                            float scale, void* out, int ldo, hipStream_t s, const float* rope_cs = nullptr, int rope_half = 0);
 // the same over `rows` utterances of T frames in the same two launches: row b's q / k / v start xz elements after row b-1's,
 // its output oz elements after, its V^T scratch vtz halfs after (vtz >= heads * 64 * ceil32(T))
 int launch_flash_attn64_f16_rows(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* vt_buf, int T, int heads,
-                                 float scale, void* out, int ldo, hipStream_t s, const float* rope_cs, int rope_half, bool vt_ready,
-                                 int rows, long long xz, long long vtz, long long oz);
+                                 float scale, void* out, int ldo, hipStream_t s, const float* rope_cs, int rope_half, int rows,
+                                 long long xz, long long vtz, long long oz);
 
 // enc_p self-attention with window-4 relative positions, fp16, head dim 96 (attn.hip)
 int launch_flash_rel96_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* vt_buf, int T, int heads,

@@ -227,7 +227,7 @@ static int launch_conv_gemm_kernel(int dtype, const ConvArgs& a_in, hipStream_t 
 
 int launch_conv_gemm(int dtype, const ConvArgs& a, hipStream_t s) {
   if (!a.row_seg) return launch_conv_gemm_kernel(dtype, a, s);
-  GSV_REQUIRE(a.Z == 1 && !a.vt_out && !a.rope_cs, "conv_gemm: a segment mask needs a plain (Z = 1) launch");
+  GSV_REQUIRE(a.Z == 1, "conv_gemm: a segment mask needs a plain (Z = 1) launch");
   GSV_RC(launch_conv_gemm_kernel(dtype, a, s));      // records the conv's route; the row pass records none
   const int C = a.ups_u > 0 ? a.ups_cout : a.Cout;
   return launch_seg_rows(dtype, a.out_f32, a.y, a.ldy ? a.ldy : C, a.y_col0, C, a.T_out, a.row_seg, nullptr, 0, s);
@@ -239,15 +239,12 @@ static int launch_conv_gemm_kernel(int dtype, const ConvArgs& a_in, hipStream_t 
   if (a.T_virt == 0) a.T_virt = a.T_out;
   if (a.ups_u > 0 && a.ups_cout == 0) { set_error("conv_gemm: ups_cout missing"); return GSV_ERR_ARG; }
   const ConvSwitches& sw = conv_switches();
-  const bool fused_qkv = a.vt_out || a.rope_cs;      // the rotary / V^T epilogue exists in gemm_lds_kernel only
   // gemm_sk -> conv_wide -> gemm_lds -> conv_narrow -> conv_lds -> conv_gemm: the first kernel that is eligible takes the launch
   int rc = launch_gemm_sk(dtype, a, s);
   if (rc <= 0) return rc;
-  if (sw.no_conv_lds && fused_qkv) { set_error("conv_gemm: fused QKV epilogue needs the LDS GEMM path"); return GSV_ERR_ARG; }
   if (!sw.no_conv_lds) {
     if ((rc = launch_conv_wide(dtype, a, s)) <= 0) return rc;
     if ((rc = launch_gemm_lds(dtype, a, s)) <= 0) return rc;
-    if (fused_qkv) { set_error("gemm: the fused rotary / V^T epilogue exists in gemm_lds_kernel only (shape not eligible)"); return GSV_ERR_ARG; }
     if ((rc = launch_conv_narrow(dtype, a, s)) <= 0) return rc;
     if ((rc = launch_conv_lds(dtype, a, s)) <= 0) return rc;
   }

@@ -277,7 +277,7 @@ __global__ __launch_bounds__(256) void gemm_t64_f16_kernel(ConvArgs a) {
 // 0 = launched, 1 = not eligible, < 0 error
 int launch_gemm_sk(int dtype, const ConvArgs& a, hipStream_t s) {
   const ConvSwitches& sw = conv_switches();
-  if (sw.no_gemm_sk || dtype != GSV_F16 || a.vt_out || a.rope_cs) return 1;     // fused QKV epilogues live in gemm_lds_kernel
+  if (sw.no_gemm_sk || dtype != GSV_F16) return 1;
   if (a.taps != 1 || a.stride != 1 || a.ups_u > 0 || a.accumulate || a.pad != 0 || a.Z != 1 || a.pre_act != ACT_NONE) return 1;
   if (a.Cin % 64 != 0 || a.Cin < 256 || a.Cout < 64) return 1;
   if (!operands_aligned<8>(a)) return 1;

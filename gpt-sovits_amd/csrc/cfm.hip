@@ -11,6 +11,7 @@
 // concatenation are built once per utterance (the reference caches the first two the same way, models.py:1046-1062).
 // Gate * (W a + b) + residual is the GEMM epilogue (ConvArgs::gate), GELU / Mish too.
 #include <cmath>
+#include <cstddef>
 
 #include "engine.h"
 
@@ -197,10 +198,11 @@ __device__ __forceinline__ unsigned long long cfm_mix64(unsigned long long z) {
 // what differs between the utterances of one call: the prompt mel (channels-first [C][Tp], device) and its length, and the key
 // of the noise draw.  A small device array, one entry per utterance, read by the kernels below.  A guided pass appends one
 // entry per unconditioned twin: prompt null (its cond columns are zeros whatever Tp says), Tp the conditioned row's.
+// slot: the row's LoRA adapter (gsv_cfm_adapter_*), -1 = the base model; a twin takes its request's.
 struct CfmRow {
   const float* prompt;
   unsigned long long seed;
-  int Tp, pad_;
+  int Tp, slot;
 };
 
 // the table reaches the device as kernel arguments, up to CFM_ROW_CHUNK entries per launch: the runtime copies arguments at
@@ -310,6 +312,12 @@ __global__ void cfm_out_kernel(const float* __restrict__ x, const CfmRow* __rest
 struct DitBlockW { Conv mod, qkv, out, ff1, ff2; };
 struct TextBlockW { float *dw = nullptr, *db = nullptr, *ng = nullptr, *nb = nullptr, *gg = nullptr, *gb = nullptr; Conv pw1, pw2; };
 
+// one stored LoRA adapter: `dev` is one block in the engine dtype, per DiT block l (rp = rank padded to 16, inner = heads *
+// dim_head, everything in units of rp elements from l * 4 (D + inner)):
+//   q|k|v lora_A stacked [3 rp][D] at 0, q|k|v lora_B [3 inner][rp] at 3 D, out lora_A [rp][inner] at 3 D + 3 inner,
+//   out lora_B [D][rp] at 3 D + 4 inner; alpha / rank is folded into the lora_B matrices.  dev null = free slot.
+struct CfmAdapter { void* dev = nullptr; int rank = 0, rp = 0; };
+
 struct gsv_cfm {
   gsv_vits ctx;
   gsv_dit_config cfg;
@@ -320,6 +328,14 @@ struct gsv_cfm {
   std::vector<DitBlockW> blocks;
   float* pos_table = nullptr;   // fp32 [4096][text_dim]
   bool materialized_attn = false;   // GSV_CFM_MATERIALIZED_ATTN=1: A/B switch back to the 4-launch scores/softmax/PV path
+  // LoRA adapters: the store by slot, its device image (base pointer and rp per slot, what lora.hip indexes by a row's
+  // slot), and the adapter being staged between adapter_begin and adapter_finalize
+  std::vector<CfmAdapter> adapters;
+  LoraSlot* lora_tab = nullptr;     // device [GSV_CFM_MAX_ADAPTERS], allocated with the first adapter
+  bool a_open = false;
+  int a_rank = 0;
+  float a_alpha = 0.f;
+  std::map<std::string, std::vector<float>> a_staged;
 };
 
 namespace {
@@ -380,11 +396,16 @@ int cfm_modulations(gsv_cfm* c, hipStream_t s, int N, float** mods_out) {
 // text embedding (the text stack run on ONE extra row of zero text, then copied into every twin: it depends on Tn alone).
 // The Euler state, the noise draw and the output stay B rows; cfm_euler_kernel<T, true> combines the two estimates.  Unguided,
 // DB == B and every launch below is the one it was.
+//
+// LoRA adapters (max_rp > 0: some row carries a slot, max_rp the largest padded rank among them): two more launches per
+// block, the low-rank delta on qkv right after the q/k/v GEMM (before rotary / V^T / attention read it) and on hb right after
+// the out-projection GEMM, under the same gate.  Workgroups of rows without a slot return at once.  max_rp == 0: no such
+// launch, the pass is the one it was.
 constexpr float CFM_CFG_THRESHOLD = 1e-5f;
 
 template <typename T>
 int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* mu, const std::vector<CfmRow>& host_rows, int Tn, int N,
-                    const float* noise, float temperature, float cfg_rate, float* out) {
+                    const float* noise, float temperature, float cfg_rate, int max_rp, float* out) {
   gsv_vits* h = &c->ctx;
   const auto& g = c->cfg;
   const int D = g.dim, td = g.text_dim, md = g.mel_dim, inner = g.heads * g.dim_head, FF = D * g.ff_mult, ldin = c->ldin;
@@ -398,7 +419,7 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
   std::vector<CfmRow> with_twins;             // guided only: the requests' entries, then one per twin
   if (guided) {
     with_twins = host_rows;
-    for (int b = 0; b < B; ++b) with_twins.push_back(CfmRow{nullptr, 0ull, host_rows[b].Tp, 0});
+    for (int b = 0; b < B; ++b) with_twins.push_back(CfmRow{nullptr, 0ull, host_rows[b].Tp, host_rows[b].slot});
   }
   const std::vector<CfmRow>& table = guided ? with_twins : host_rows;
   CfmRow* rw;
@@ -474,6 +495,9 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
   void* vtb = nullptr;
   const long long vtz = (long long)g.heads * 64 * ((Tn + 31) / 32 * 32);   // one V^T buffer per utterance
   if (flash) GSV_RC(need(h, "cfm_vt", (size_t)DB * vtz * 2, &vtb));
+  const int* row_slot = (const int*)((const char*)rw + offsetof(CfmRow, slot));   // device: row b's slot, every slot_ld ints
+  const int slot_ld = (int)(sizeof(CfmRow) / sizeof(int));
+  const long long lora_blk = 4ll * (D + inner);   // an adapter's elements per DiT block, in units of rp (CfmAdapter)
   for (int step = 0; step < N; ++step) {
     // ---- InputEmbedding (dit.py:75-84): proj(cat(x, cond, text)) then + ConvPositionEmbedding
     ConvOpt o;
@@ -497,6 +521,9 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
       const int wnt = l >= resident ? 1 : 0;
       ConvOpt oq; oq.w_nt = wnt;   // rotary + V^T as this GEMM's epilogue was tried: no gain over the V^T launch
       GSV_RC(conv(h, s, blk.qkv, nrm, D, R, qkv, R, oq));
+      if (max_rp)
+        GSV_RC(launch_lora_delta(h->dtype, nrm, qkv, Tn, DB, D, 3 * inner, 3, row_slot, slot_ld, c->lora_tab, max_rp, l * lora_blk,
+                                 l * lora_blk + 3 * D, nullptr, s));
       if (flash) {   // every utterance in the same two launches (V^T + rotary, attention): the row is a grid dimension
         const _Float16* qb = (const _Float16*)qkv;
         GSV_RC(launch_flash_attn64_f16_rows(qb, 3 * inner, qb + inner, 3 * inner, qb + 2 * inner, 3 * inner, vtb, Tn, g.heads, att_scale,
@@ -511,6 +538,9 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
       }
       ConvOpt og; og.gate = m + 2 * D; og.res = hb; og.w_nt = wnt;
       GSV_RC(conv(h, s, blk.out, ao, inner, R, hb, R, og));
+      if (max_rp)
+        GSV_RC(launch_lora_delta(h->dtype, ao, hb, Tn, DB, inner, D, 1, row_slot, slot_ld, c->lora_tab, max_rp,
+                                 l * lora_blk + 3 * D + 3 * inner, l * lora_blk + 3 * D + 4 * inner, m + 2 * D, s));
       GSV_RC(launch_ln_mod<T>(hb, m + 4 * D, m + 3 * D, R, D, nrm, s));
       ConvOpt of; of.post_act = ACT_GELU_TANH; of.w_nt = wnt;
       GSV_RC(conv(h, s, blk.ff1, nrm, D, R, ff, R, of));
@@ -530,28 +560,38 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
 
 template <typename T>
 int cfm_run(gsv_cfm* c, hipStream_t s, const float* mu, const std::vector<CfmRow>& rows, int Tn, int N, const float* noise,
-            float temperature, float cfg_rate, float* out) {
+            float temperature, float cfg_rate, int max_rp, float* out) {
   float* mods = nullptr;
   GSV_RC(cfm_modulations<T>(c, s, N, &mods));
-  return cfm_infer_batch<T>(c, s, mods, mu, rows, Tn, N, noise, temperature, cfg_rate, out);
+  return cfm_infer_batch<T>(c, s, mods, mu, rows, Tn, N, noise, temperature, cfg_rate, max_rp, out);
 }
 
-// What the three entry points share: the argument checks, the row table (row b: its own prompt, prompt length and noise key),
-// all before anything is launched, then the pass.  `who` names the entry point in the messages.
-int cfm_entry(gsv_cfm* c, const char* who, const float* mu, const float* const* prompts, const int* Tp, int B, int Tn, int n_steps,
-              const float* noise, const uint64_t* seeds, float temperature, float cfg_rate, float* out, gsv_stream_t stream) {
+// What the entry points share: the argument checks, the row table (row b: its own prompt, prompt length, noise key and
+// adapter slot; `adapters` null = every row the base model), all before anything is launched, then the pass.  `who` names
+// the entry point in the messages.
+int cfm_entry(gsv_cfm* c, const char* who, const float* mu, const float* const* prompts, const int* Tp, const int* adapters, int B,
+              int Tn, int n_steps, const float* noise, const uint64_t* seeds, float temperature, float cfg_rate, float* out,
+              gsv_stream_t stream) {
   GSV_REQUIRE(c && c->finalized, "%s: handle not finalized", who);
   GSV_REQUIRE(mu && out && Tp && B > 0 && Tn > 0 && n_steps > 0 && n_steps <= 1024, "%s: bad argument", who);
   const bool guided = cfg_rate > CFM_CFG_THRESHOLD;           // the DiT then sees every row and its unconditioned twin
   GSV_REQUIRE(B <= 65535 / (guided ? 2 : 1), "%s: %d rows%s exceed the grid's 65535", who, B, guided ? " and their unconditioned twins" : "");
   GSV_REQUIRE(noise || seeds, "%s: neither noise nor seeds given", who);
   std::vector<CfmRow> rows(B);
+  int max_rp = 0;
   for (int b = 0; b < B; ++b) {
     GSV_REQUIRE(Tp[b] >= 0 && Tp[b] <= Tn && (Tp[b] == 0 || (prompts && prompts[b])),
                 "%s: row %d: prompt length %d does not fit %d frames, or its prompt is null", who, b, Tp[b], Tn);
-    rows[b] = CfmRow{Tp[b] ? prompts[b] : nullptr, seeds ? (unsigned long long)seeds[b] : 0ull, Tp[b], 0};
+    const int slot = adapters ? adapters[b] : -1;
+    GSV_REQUIRE(slot >= -1 && slot < GSV_CFM_MAX_ADAPTERS, "%s: row %d: adapter slot %d is outside [-1, %d)", who, b, slot,
+                GSV_CFM_MAX_ADAPTERS);
+    if (slot >= 0) {
+      GSV_REQUIRE(slot < (int)c->adapters.size() && c->adapters[slot].dev, "%s: row %d: no adapter in slot %d", who, b, slot);
+      max_rp = std::max(max_rp, c->adapters[slot].rp);
+    }
+    rows[b] = CfmRow{Tp[b] ? prompts[b] : nullptr, seeds ? (unsigned long long)seeds[b] : 0ull, Tp[b], slot};
   }
-  return GSV_WITH_T(&c->ctx, cfm_run<T>(c, (hipStream_t)stream, mu, rows, Tn, n_steps, noise, temperature, cfg_rate, out));
+  return GSV_WITH_T(&c->ctx, cfm_run<T>(c, (hipStream_t)stream, mu, rows, Tn, n_steps, noise, temperature, cfg_rate, max_rp, out));
 }
 
 }  // namespace
@@ -579,6 +619,8 @@ int gsv_cfm_create(const gsv_dit_config* cfg, int dtype, gsv_cfm_t** out) {
 
 void gsv_cfm_destroy(gsv_cfm_t* c) {
   if (!c) return;
+  for (auto& a : c->adapters) if (a.dev) (void)hipFree(a.dev);
+  if (c->lora_tab) (void)hipFree(c->lora_tab);
   free_ctx(&c->ctx);
   delete c;
 }
@@ -660,19 +702,132 @@ int gsv_cfm_inference(gsv_cfm_t* c, const float* mu, const float* prompt, int B,
     prompts[b] = prompt && Tp > 0 ? prompt + (size_t)b * c->cfg.mel_dim * Tp : nullptr;
     seeds[b] = seed + 0x9E3779B97F4A7C15ull * (uint64_t)b;
   }
-  return cfm_entry(c, "cfm_inference", mu, prompts.data(), tps.data(), B, T, n_steps, noise, seeds.data(), temperature, 0.f, out, stream);
+  return cfm_entry(c, "cfm_inference", mu, prompts.data(), tps.data(), nullptr, B, T, n_steps, noise, seeds.data(), temperature, 0.f, out, stream);
 }
 
 int gsv_cfm_inference_rows(gsv_cfm_t* c, const float* mu, const float* const* prompts, const int* Tp, int B, int T, int n_steps,
                            const float* noise, const uint64_t* seeds, float temperature, float* out, gsv_stream_t stream) {
-  return cfm_entry(c, "cfm_inference_rows", mu, prompts, Tp, B, T, n_steps, noise, seeds, temperature, 0.f, out, stream);
+  return cfm_entry(c, "cfm_inference_rows", mu, prompts, Tp, nullptr, B, T, n_steps, noise, seeds, temperature, 0.f, out, stream);
 }
 
 int gsv_cfm_inference_guided(gsv_cfm_t* c, const float* mu, const float* const* prompts, const int* Tp, int B, int T, int n_steps,
                              const float* noise, const uint64_t* seeds, float temperature, float cfg_rate, float* out,
                              gsv_stream_t stream) {
   GSV_REQUIRE(std::isfinite(cfg_rate), "cfm_inference_guided: cfg_rate is not finite");
-  return cfm_entry(c, "cfm_inference_guided", mu, prompts, Tp, B, T, n_steps, noise, seeds, temperature, cfg_rate, out, stream);
+  return cfm_entry(c, "cfm_inference_guided", mu, prompts, Tp, nullptr, B, T, n_steps, noise, seeds, temperature, cfg_rate, out, stream);
+}
+
+int gsv_cfm_inference_adapted(gsv_cfm_t* c, const float* mu, const float* const* prompts, const int* Tp, const int* adapters, int B,
+                              int T, int n_steps, const float* noise, const uint64_t* seeds, float temperature, float cfg_rate,
+                              float* out, gsv_stream_t stream) {
+  GSV_REQUIRE(std::isfinite(cfg_rate), "cfm_inference_adapted: cfg_rate is not finite");
+  return cfm_entry(c, "cfm_inference_adapted", mu, prompts, Tp, adapters, B, T, n_steps, noise, seeds, temperature, cfg_rate, out, stream);
+}
+
+int gsv_cfm_adapter_begin(gsv_cfm_t* c, int rank, float alpha) {
+  GSV_REQUIRE(c && c->finalized, "cfm_adapter_begin: handle not finalized");
+  GSV_REQUIRE(rank >= 1 && rank <= GSV_LORA_MAX_RANK, "cfm_adapter_begin: rank %d is outside [1, %d]", rank, GSV_LORA_MAX_RANK);
+  GSV_REQUIRE(std::isfinite(alpha) && alpha > 0.f, "cfm_adapter_begin: lora_alpha must be positive and finite");
+  GSV_REQUIRE((c->cfg.heads * c->cfg.dim_head) % 32 == 0, "cfm_adapter_begin: heads * dim_head = %d must be a multiple of 32",
+              c->cfg.heads * c->cfg.dim_head);
+  c->a_staged.clear();
+  c->a_open = true;
+  c->a_rank = rank;
+  c->a_alpha = alpha;
+  return GSV_OK;
+}
+
+int gsv_cfm_adapter_load_tensor(gsv_cfm_t* c, const char* name, const float* data, int64_t numel) {
+  GSV_REQUIRE(c && name && data && numel > 0, "cfm_adapter_load_tensor: bad argument");
+  GSV_REQUIRE(c->a_open, "cfm_adapter_load_tensor: no adapter_begin before '%s'", name);
+  c->a_staged[name].assign(data, data + numel);
+  return GSV_OK;
+}
+
+int gsv_cfm_adapter_finalize(gsv_cfm_t* c, int* slot_out) {
+  GSV_REQUIRE(c && slot_out, "cfm_adapter_finalize: null argument");
+  GSV_REQUIRE(c->a_open, "cfm_adapter_finalize: no adapter_begin");
+  // whatever happens below, the staged adapter is gone afterwards; the store changes only at the very end
+  std::map<std::string, std::vector<float>> staged;
+  staged.swap(c->a_staged);
+  c->a_open = false;
+  const auto& g = c->cfg;
+  const int D = g.dim, inner = g.heads * g.dim_head, r = c->a_rank, rp = (r + 15) / 16 * 16;
+  const float scale = c->a_alpha / (float)r;
+  GSV_REQUIRE((int)staged.size() == 8 * g.depth, "cfm_adapter_finalize: %zu tensors staged, a rank-%d adapter of this DiT has %d", staged.size(),
+              r, 8 * g.depth);
+  int slot = -1;
+  for (size_t i = 0; i < c->adapters.size() && slot < 0; ++i)
+    if (!c->adapters[i].dev) slot = (int)i;
+  if (slot < 0) slot = (int)c->adapters.size();
+  GSV_REQUIRE(slot < GSV_CFM_MAX_ADAPTERS, "cfm_adapter_finalize: all %d adapter slots are in use", GSV_CFM_MAX_ADAPTERS);
+  const size_t per_block = (size_t)4 * (D + inner) * rp, total = per_block * g.depth;
+  std::vector<float> host(total, 0.f);
+  // lora_A [r][in] -> rows [row0, row0 + r) of a [.][in] matrix; lora_B [out][r] -> columns [0, r) of [out][rp], scaled
+  auto put = [&](const std::string& name, bool is_b, int n_in_or_out, float* dst) -> int {
+    auto it = staged.find(name);
+    GSV_REQUIRE(it != staged.end(), "cfm_adapter_finalize: '%s' is missing", name.c_str());
+    GSV_REQUIRE(it->second.size() == (size_t)r * n_in_or_out, "cfm_adapter_finalize: '%s' has %zu elements, expected %d x %d", name.c_str(),
+                it->second.size(), is_b ? n_in_or_out : r, is_b ? r : n_in_or_out);
+    const float* src = it->second.data();
+    if (!is_b) std::copy(src, src + (size_t)r * n_in_or_out, dst);
+    else
+      for (int o = 0; o < n_in_or_out; ++o)
+        for (int q = 0; q < r; ++q) dst[(size_t)o * rp + q] = scale * src[(size_t)o * r + q];
+    return GSV_OK;
+  };
+  for (int l = 0; l < g.depth; ++l) {
+    const std::string p = "transformer_blocks." + std::to_string(l) + ".attn.";
+    float* blk = host.data() + (size_t)l * per_block;
+    const char* qkv_names[3] = {"to_q", "to_k", "to_v"};
+    for (int j = 0; j < 3; ++j) {
+      GSV_RC(put(p + qkv_names[j] + ".lora_A", false, D, blk + (size_t)j * rp * D));
+      GSV_RC(put(p + qkv_names[j] + ".lora_B", true, inner, blk + (size_t)3 * D * rp + (size_t)j * inner * rp));
+    }
+    GSV_RC(put(p + "to_out.0.lora_A", false, inner, blk + (size_t)(3 * D + 3 * inner) * rp));
+    GSV_RC(put(p + "to_out.0.lora_B", true, D, blk + (size_t)(3 * D + 4 * inner) * rp));
+  }
+  const size_t es = dt_size(c->ctx.dtype);
+  void* dev = nullptr;
+  GSV_HIP(hipMalloc(&dev, total * es));
+  hipError_t e;
+  if (c->ctx.dtype == GSV_F32) e = hipMemcpy(dev, host.data(), total * 4, hipMemcpyHostToDevice);
+  else {
+    std::vector<_Float16> tmp(total);
+    for (size_t i = 0; i < total; ++i) tmp[i] = (_Float16)host[i];
+    e = hipMemcpy(dev, tmp.data(), total * 2, hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess && !c->lora_tab) {
+    e = hipMalloc((void**)&c->lora_tab, sizeof(LoraSlot) * GSV_CFM_MAX_ADAPTERS);
+    if (e == hipSuccess) e = hipMemset(c->lora_tab, 0, sizeof(LoraSlot) * GSV_CFM_MAX_ADAPTERS);
+  }
+  const LoraSlot entry{dev, rp, 0};
+  if (e == hipSuccess) e = hipMemcpy(c->lora_tab + slot, &entry, sizeof(entry), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(dev);
+    set_error("cfm_adapter_finalize: upload failed: %s", hipGetErrorString(e));
+    return GSV_ERR_HIP;
+  }
+  if (slot == (int)c->adapters.size()) c->adapters.emplace_back();
+  c->adapters[slot] = CfmAdapter{dev, r, rp};
+  *slot_out = slot;
+  return GSV_OK;
+}
+
+int gsv_cfm_adapter_remove(gsv_cfm_t* c, int slot) {
+  GSV_REQUIRE(c, "cfm_adapter_remove: null handle");
+  GSV_REQUIRE(slot >= 0 && slot < (int)c->adapters.size() && c->adapters[slot].dev, "cfm_adapter_remove: no adapter in slot %d", slot);
+  GSV_HIP(hipDeviceSynchronize());   // nothing may still read the block
+  (void)hipFree(c->adapters[slot].dev);
+  c->adapters[slot] = CfmAdapter{};
+  return GSV_OK;
+}
+
+int gsv_cfm_adapter_count(gsv_cfm_t* c) {
+  GSV_REQUIRE(c, "cfm_adapter_count: null handle");
+  int n = 0;
+  for (const auto& a : c->adapters) n += a.dev != nullptr;
+  return n;
 }
 
 }  // extern "C"

@@ -246,6 +246,14 @@ int launch_flash_rel96_f16(const void* q, int ldq, const void* k, int ldk, const
                            float scale, const float* rel_k, const float* rel_v, void* out, int ldo, hipStream_t s,
                            const int* kr = nullptr);   // kr: per-query key range [kr[2i], kr[2i+1]), non-decreasing (block-diagonal)
 
+// per-row low-rank delta of the adapted DiT passes (lora.hip).  tab[s] = slot s's block of weights (engine dtype) and its
+// padded rank rp; the site's A [n_proj * rp][K] starts coef_a * rp elements into the block and its B [N][rp] coef_b * rp.
+// Row b (Tn frames of x [.][K] and y [.][N]) with s = slot[b * slot_stride] >= 0 gets y += gate (.) ((x A^T) B^T); max_rp =
+// the largest rp among the slots of this launch (it sizes the LDS tile).
+struct LoraSlot { const void* base; int rp, pad_; };
+int launch_lora_delta(int dtype, const void* x, void* y, int Tn, int DB, int K, int N, int n_proj, const int* slot, int slot_stride,
+                      const LoraSlot* tab, int max_rp, long long coef_a, long long coef_b, const float* gate, hipStream_t s);
+
 // elementwise / small ops (ops.hip)
 int launch_layernorm(int dtype, const void* x, int x_f32, const void* res, int res_f32, const float* gamma,
                      const float* beta, void* y, int y_f32, int rows, int C, float eps, hipStream_t s,

@@ -225,6 +225,7 @@ class TTS:
         from .TextPreprocessor import TextPreprocessor
         self.text_preprocessor = TextPreprocessor(bert_fn=None, device="cpu")      # reference TTS.py:431-433
         self.vocoder_configs: dict = {"sr": None, "T_ref": None, "T_chunk": None, "upsample_rate": None, "overlapped_len": None}
+        self._lora_voices: Dict[str, dict] = {}      # add_lora_voice: name -> {"slot", "engine", "state"}
 
     # ---- weights (reference TTS.py:484-603) ------------------------------------------------
     def init_t2s_weights(self, weights_path: Optional[str] = None, state: Optional[dict] = None):
@@ -260,8 +261,7 @@ class TTS:
             state = dict(state, weight=merge_lora_v3(base_state["weight"], state["weight"], int(state["lora_rank"])))
         self._vits_state = state
         hps = state["config"]
-        d, mcfg = hps["data"], dict(hps["model"])
-        mcfg.pop("version", None)
+        d = hps["data"]
         self.configs.filter_length = d["filter_length"]
         self.configs.segment_size = hps["train"]["segment_size"]
         self.configs.sampling_rate = d["sampling_rate"]
@@ -269,21 +269,91 @@ class TTS:
         self.configs.win_length = d["win_length"]
         self.configs.n_speakers = d["n_speakers"]
         self.configs.vits_weights_path = weights_path
+        self.vits_model = self._build_vits_model(hps, state["weight"])
+        v = self.vits_model
+        self._lora_voices = {}           # they lived in the engines this call replaced: add_lora_voice again
+        if getattr(v, "is_v2pro", False) and self.sv_model is None:
+            from .. import sv
+            if os.path.exists(sv.sv_path):            # reference TTS.py:487-488 loads it here; without the file: init_sv_model(state_dict=)
+                self.init_sv_model()
+
+    def _build_vits_model(self, hps: dict, weight: dict, cfm: Optional[CFM] = None) -> SynthesizerTrn:
+        """the SoVITS engine of `hps` (a checkpoint's config) loaded with `weight`; `cfm` (v3 / v4): share that flow-matching
+        decoder instead of building and loading a DiT (the encoder-side engine of a LoRA voice)"""
+        d, mcfg = hps["data"], dict(hps["model"])
+        mcfg.pop("version", None)
         extra = {}
         cls = SynthesizerTrn
         if self.configs.use_vocoder:
             cls = SynthesizerTrnV3
             if "dit" in hps:             # synthetic / test checkpoints may carry a smaller DiT than models.py:1219-1222
                 extra["dit_kwargs"] = hps["dit"]
+            if cfm is not None:
+                extra["cfm"] = cfm
         v = cls(d["filter_length"] // 2 + 1, hps["train"]["segment_size"] // d["hop_length"],
                 n_speakers=d["n_speakers"], version=self.configs.version, device=self.configs.device,
                 dtype=self.precision, n_symbols=hps.get("n_symbols"), **extra, **mcfg)
-        v.load_state_dict(state["weight"])
-        self.vits_model = v
-        if getattr(v, "is_v2pro", False) and self.sv_model is None:
-            from .. import sv
-            if os.path.exists(sv.sv_path):            # reference TTS.py:487-488 loads it here; without the file: init_sv_model(state_dict=)
-                self.init_sv_model()
+        v.load_state_dict(weight)
+        return v
+
+    # ---- LoRA voices served beside the base model (v3 / v4) ---------------------------------------------------------
+    def add_lora_voice(self, name: str, weights_path: Optional[str] = None, state: Optional[dict] = None) -> None:
+        """A fine-tuned v3 / v4 voice (a LoRA checkpoint: version code 03 / 04, or `state` = {"weight", "lora_rank"[,
+        "lora_alpha"]}) under `name`, next to the loaded base model instead of merged into it (init_vits_weights): requests
+        select it with the key "lora_voice", and requests of different LoRA voices and of none share flow-matching passes.
+        The adapters go into the base model's DiT engine (CFM.add_adapter).  Whatever else the file holds of the base
+        model's parameters (the voice's own ref_enc / bridge / wns1 / ...) gets an encoder-side engine of its own, the base
+        weights with these laid over them, around the same DiT; a file of adapters alone reuses the base one.  The DiT's
+        own non-adapter weights stay the base model's: a file that changes them raises ValueError (merge it instead).
+        init_vits_weights drops all LoRA voices; enable_half_precision / set_device add them again."""
+        from ..process_ckpt import split_lora_v3
+        if self.vits_model is None or not self.configs.use_vocoder:
+            raise ValueError("add_lora_voice needs a loaded v3 / v4 base model (init_vits_weights)")
+        if name is None or name in self._lora_voices:
+            raise ValueError(f"LoRA voice {name!r}: " + ("a name is required" if name is None else "already added"))
+        if state is None:
+            state = load_sovits_new(weights_path)
+        if "lora_rank" not in state:
+            raise ValueError("not a LoRA checkpoint: no lora_rank")
+        rank, alpha = int(state["lora_rank"]), state.get("lora_alpha")
+        adapter, overrides = split_lora_v3(state["weight"], rank, alpha)
+        base = self._vits_state["weight"]
+        enc = {}
+        for k, v in overrides.items():
+            if k not in base:
+                continue
+            if not k.startswith("cfm."):
+                enc[k] = v
+            elif v.shape != base[k].shape or not torch.equal(v.to(base[k].dtype), base[k]):
+                raise ValueError(f"LoRA voice {name!r} changes {k}, a DiT weight outside the adapters: merge it with "
+                                 "init_vits_weights instead")
+        cfm = self.vits_model.cfm
+        slot = cfm.add_adapter(adapter, rank, alpha)
+        engine = None
+        if enc:
+            try:
+                weight = {k: v for k, v in base.items() if not k.startswith("cfm.")}
+                weight.update(enc)
+                engine = self._build_vits_model(self._vits_state["config"], weight, cfm=cfm)
+            except Exception:
+                cfm.remove_adapter(slot)
+                raise
+        self._lora_voices[name] = dict(slot=slot, engine=engine, state=state)
+
+    def remove_lora_voice(self, name: str) -> None:
+        if name not in self._lora_voices:
+            raise ValueError(f"unknown LoRA voice {name!r}")
+        v = self._lora_voices.pop(name)
+        self.vits_model.cfm.remove_adapter(v["slot"])
+
+    def _lora_voice(self, name: Optional[str]) -> Tuple[SynthesizerTrn, Optional[int]]:
+        """a request's "lora_voice" -> (the engine of its decode_encp and style vector, its adapter slot); None: the base"""
+        if name is None:
+            return self.vits_model, None
+        v = getattr(self, "_lora_voices", {}).get(name)
+        if v is None:
+            raise ValueError(f"unknown LoRA voice {name!r}: add_lora_voice first")
+        return v["engine"] or self.vits_model, v["slot"]
 
     def init_vocoder(self, version: Optional[str] = None, state: Optional[dict] = None, weights_path: Optional[str] = None):
         """reference TTS.py:605-660: v3 -> BigVGAN-v2 24 kHz x256, v4 -> the HiFi-GAN `Generator` 48 kHz x480.
@@ -387,7 +457,10 @@ class TTS:
             self.init_t2s_weights(self.configs.t2s_weights_path, state=self._t2s_state)
         if self._vits_state is not None:
             self.vits_model = None
+            lora_voices = self._lora_voices
             self.init_vits_weights(self.configs.vits_weights_path, state=self._vits_state)
+            for name, v in lora_voices.items():
+                self.add_lora_voice(name, state=v["state"])
         if getattr(self, "_hubert_state", None) is not None:
             self.init_cnhuhbert_weights(state_dict=self._hubert_state)
         if self.sr_model is not None:               # reference TTS.py:734-735 moves it; here it follows the dtype as well
@@ -639,7 +712,9 @@ class TTS:
         return to_host(t)
 
     # ---- v3 / v4 synthesis (reference TTS.py:1431-1637) -----------------------------------------
-    def _prompt_features(self):
+    def _prompt_features(self, lora_voice: Optional[str] = None):
+        """... `lora_voice`: the encoder-side engine of that LoRA voice computes fea_ref and holds the style vector"""
+        enc_model = self.vits_model if lora_voice is None else self._lora_voice(lora_voice)[0]
         pc = self.prompt_cache
         if pc.get("ref_mel") is None and pc.get("raw_audio") is not None:
             pc["ref_mel"] = self._ref_mel_from_audio(pc["raw_audio"], pc["raw_sr"])
@@ -649,7 +724,7 @@ class TTS:
         spec = pc["refer_spec"][0]
         spec = spec[0] if isinstance(spec, tuple) else spec
         spec = spec.to(dev)
-        fea_ref, ge = self.vits_model.decode_encp(pc["prompt_semantic"].view(1, 1, -1), torch.as_tensor(pc["phones"]).view(1, -1), spec)
+        fea_ref, ge = enc_model.decode_encp(pc["prompt_semantic"].view(1, 1, -1), torch.as_tensor(pc["phones"]).view(1, -1), spec)
         mel2 = norm_spec(pc["ref_mel"].to(dev, torch.float32))
         T_min = min(mel2.shape[2], fea_ref.shape[2])
         mel2, fea_ref = mel2[:, :, :T_min], fea_ref[:, :, :T_min]
@@ -674,13 +749,16 @@ class TTS:
     @torch.no_grad()
     def using_vocoder_synthesis(self, semantic_tokens: torch.Tensor, phones: torch.Tensor, speed: float = 1.0,
                                 sample_steps: int = 32, seed: int = 0, noise_fn: Optional[Callable] = None,
-                                inference_cfg_rate: float = 0) -> torch.Tensor:
+                                inference_cfg_rate: float = 0, lora_voice: Optional[str] = None) -> torch.Tensor:
         """TTS.py:1431-1494: one fragment; the mel is generated chunk by chunk, each chunk prompted with the tail of the
         previous one.  `noise_fn(call_index, shape)` (tests) pins the randn draw of each cfm.inference call.
-        `inference_cfg_rate` is CFM.inference_guided's (the reference passes 0 here: CFM.inference)."""
-        spec, fea_ref, ge, mel2, T_min = self._prompt_features()
+        `inference_cfg_rate` is CFM.inference_guided's (the reference passes 0 here: CFM.inference).  `lora_voice`: a name
+        given to add_lora_voice; its encoder-side engine and its adapters in the DiT replace the base model's."""
+        enc_model, slot = (self.vits_model, None) if lora_voice is None else self._lora_voice(lora_voice)
+        lora_kw = {} if slot is None else dict(adapters=[slot])
+        spec, fea_ref, ge, mel2, T_min = self._prompt_features(lora_voice)
         chunk_len = self.vocoder_configs["T_chunk"] - T_min
-        fea_todo, ge = self.vits_model.decode_encp(semantic_tokens, phones, spec, ge, speed)
+        fea_todo, ge = enc_model.decode_encp(semantic_tokens, phones, spec, ge, speed)
         outs, pos, call = [], 0, 0
         while True:
             chunk = fea_todo[:, :, pos:pos + chunk_len]
@@ -690,7 +768,7 @@ class TTS:
             fea = torch.cat([fea_ref, chunk], 2).transpose(2, 1)
             nz = noise_fn(call, (1, 100, fea.shape[1])) if noise_fn else None
             res = self.vits_model.cfm.inference_guided(fea, None, mel2, sample_steps, inference_cfg_rate=inference_cfg_rate,
-                                                       noise=nz, seed=seed + call)
+                                                       noise=nz, seed=seed + call, **lora_kw)
             res = res[:, :, mel2.shape[2]:]
             call += 1
             mel2 = res[:, :, -T_min:]
@@ -702,15 +780,18 @@ class TTS:
     def using_vocoder_synthesis_batched_infer(self, idx_list: List[int], semantic_tokens_list: List[torch.Tensor],
                                               batch_phones: List[torch.Tensor], speed: float = 1.0, sample_steps: int = 32,
                                               seed: int = 0, noise_fn: Optional[Callable] = None,
-                                              inference_cfg_rate: float = 0) -> List[torch.Tensor]:
+                                              inference_cfg_rate: float = 0, lora_voice: Optional[str] = None) -> List[torch.Tensor]:
         """TTS.py:1496-1609: all fragments of a batch concatenated, cut into overlapping chunks that go through ONE
-        batched cfm.inference, vocoded as one sequence, re-joined with SOLA and split back per fragment."""
-        prompt = self._prompt_features()
-        fea, lens, pad_len = self._fold_chunks(prompt, idx_list, semantic_tokens_list, batch_phones, speed)
+        batched cfm.inference, vocoded as one sequence, re-joined with SOLA and split back per fragment.  `lora_voice` as in
+        using_vocoder_synthesis: every row of the pass takes its adapter."""
+        slot = None if lora_voice is None else self._lora_voice(lora_voice)[1]
+        prompt = self._prompt_features(lora_voice)
+        fea, lens, pad_len = self._fold_chunks(prompt, idx_list, semantic_tokens_list, batch_phones, speed, lora_voice)
         mel2 = prompt[3]
         nz = noise_fn(0, (fea.shape[0], 100, fea.shape[1])) if noise_fn else None
+        lora_kw = {} if slot is None else dict(adapters=[slot] * int(fea.shape[0]))
         pred = self.vits_model.cfm.inference_guided(fea, None, mel2, sample_steps, inference_cfg_rate=inference_cfg_rate, noise=nz,
-                                                    seed=seed)
+                                                    seed=seed, **lora_kw)
         return self._fold_audio(pred[:, :, mel2.shape[2]:], lens, pad_len)
 
     @staticmethod
@@ -727,15 +808,17 @@ class TTS:
             pos += chunk_len
 
     def _fold_chunks(self, prompt: tuple, idx_list: List[int], semantic_tokens_list: List[torch.Tensor],
-                     batch_phones: List[torch.Tensor], speed: float) -> Tuple[torch.Tensor, List[int], int]:
-        """the CFM input rows of one fold with the voice of `prompt` (= _prompt_features()): [chunks, T_chunk, 512], every
-        row the voice's fea_ref followed by one chunk; the sentences' frame counts; the padding of the last chunk"""
+                     batch_phones: List[torch.Tensor], speed: float,
+                     lora_voice: Optional[str] = None) -> Tuple[torch.Tensor, List[int], int]:
+        """the CFM input rows of one fold with the voice of `prompt` (= _prompt_features(lora_voice)): [chunks, T_chunk, 512],
+        every row the voice's fea_ref followed by one chunk; the sentences' frame counts; the padding of the last chunk"""
+        enc_model = self.vits_model if lora_voice is None else self._lora_voice(lora_voice)[0]
         spec, fea_ref, ge, mel2, T_min = prompt
         vc = self.vocoder_configs
         chunk_len, ov = vc["T_chunk"] - T_min, vc["overlapped_len"]
         feats, lens = [], []
         for i, idx in enumerate(idx_list):
-            f, _ = self.vits_model.decode_encp(semantic_tokens_list[i][-idx:].view(1, 1, -1), batch_phones[i].view(1, -1), spec, ge, speed)
+            f, _ = enc_model.decode_encp(semantic_tokens_list[i][-idx:].view(1, 1, -1), batch_phones[i].view(1, -1), spec, ge, speed)
             feats.append(f)
             lens.append(int(f.shape[2]))
         padded = F.pad(torch.cat(feats, 2), (ov, 0))
@@ -893,6 +976,8 @@ class TTS:
         if self.configs.use_vocoder:                                    # TTS.py:1283-1299
             dev_ph = [ph.to(self.configs.device) for ph in item["phones"]]
             cfm_kw = dict(speed=speed_factor, sample_steps=opts["sample_steps"], inference_cfg_rate=opts["inference_cfg_rate"])
+            if opts.get("lora_voice") is not None:
+                cfm_kw["lora_voice"] = opts["lora_voice"]
             if opts["parallel_infer"]:
                 frags = self.using_vocoder_synthesis_batched_infer(idx_list, pred_list, dev_ph, seed=seed_b, **cfm_kw)
             else:
@@ -929,14 +1014,17 @@ class TTS:
         reference terms (ge) are dropped on the way in and out, so no voice ever reuses another's style vector"""
         saved = self.prompt_cache
         self.prompt_cache = cache
-        if self.vits_model is not None:
-            self.vits_model.invalidate_refer()
+        engines = [self.vits_model] + [v["engine"] for v in getattr(self, "_lora_voices", {}).values()]
+        for e in engines:
+            if e is not None:
+                e.invalidate_refer()
         try:
             yield cache
         finally:
             self.prompt_cache = saved
-            if self.vits_model is not None:
-                self.vits_model.invalidate_refer()
+            for e in engines:
+                if e is not None:
+                    e.invalidate_refer()
 
     def _empty_prompt_cache(self) -> dict:
         return {"ref_audio_path": None, "prompt_semantic": None, "refer_spec": [], "prompt_text": None, "prompt_lang": None,
@@ -991,7 +1079,9 @@ class TTS:
     def _request_options(req: dict) -> dict:
         """The keys run() accepts with the reference's defaults (TTS.py:1026-1046): the only place a request key is read
         with a default.  An empty seed is -1 (random) and fragment_interval is at least 0.01; `split_bucket` and
-        `super_sampling` are as given -- _resolve_options applies the rules that depend on the loaded model."""
+        `super_sampling` are as given -- _resolve_options applies the rules that depend on the loaded model.
+        "lora_voice" (a name given to add_lora_voice) is carried only when the request names one: absent or None is the base
+        model, and the options of such a request are the ones they were (read it with o.get("lora_voice"))."""
         o = dict(top_k=req.get("top_k", 5), top_p=req.get("top_p", 1), temperature=req.get("temperature", 1),
                  batch_size=req.get("batch_size", 1), batch_threshold=req.get("batch_threshold", 0.75),
                  speed_factor=req.get("speed_factor", 1.0), split_bucket=req.get("split_bucket", True),
@@ -1003,13 +1093,18 @@ class TTS:
         o["seed"] = -1 if seed in ["", None] else seed
         if o["fragment_interval"] < 0.01:
             o["fragment_interval"] = 0.01
+        if req.get("lora_voice") is not None:
+            o["lora_voice"] = req["lora_voice"]
         return o
 
     def _resolve_options(self, req: dict) -> dict:
         """_request_options(req) under the rules of the loaded model, what run() and run_batch work from: fragments, another
         speed and v3 / v4 parallel runs are never bucketed (reference TTS.py:1048-1062), and AP_BWE super-sampling applies to
-        the v3 vocoder output only -- v1 / v2 / v2Pro / v4 ignore the key (TTS.py:1040, 1328, 1349)."""
+        the v3 vocoder output only -- v1 / v2 / v2Pro / v4 ignore the key (TTS.py:1040, 1328, 1349).  A "lora_voice" that was
+        not added raises ValueError here, before any GPU work."""
         o = self._request_options(req)
+        if "lora_voice" in o:
+            self._lora_voice(o["lora_voice"])
         if o["return_fragment"] or o["speed_factor"] != 1.0 or (self.configs.use_vocoder and o["parallel_infer"]):
             o["split_bucket"] = False
         o["super_sampling"] = o["super_sampling"] and self.configs.use_vocoder and self.configs.version == "v3"
@@ -1281,8 +1376,8 @@ class TTS:
         self.vits_model.invalidate_refer()          # the engine's cached reference terms are the last slot's voice
 
     def _shared_cfm_stage(self, plans: List[dict], shared_vocoder: bool = False) -> None:
-        """shared_cfm, v3 / v4: every chunk of every fold that plan_cfm shares is one row, with its voice's prompt mel and the
-        noise key run() gives it, of a CFM.inference_rows pass; vocoder and SOLA stay per fold, unless shared_vocoder: then
+        """shared_cfm, v3 / v4: every chunk of every fold that plan_cfm shares is one row, with its voice's prompt mel, the
+        noise key run() gives it and its request's LoRA adapter (the key "lora_voice"), of a CFM.inference_rows pass; vocoder and SOLA stay per fold, unless shared_vocoder: then
         the folds' mels go through the plan_vocoder passes of the vocoder's forward_segments, and only SOLA and the cuts stay
         per fold.  Reads `preds`, `kept`, `voice`, `opts`, `actual_seed`, `data`.  Writes `cfm_folds` (feature frames per
         batch) and `T_min` (the voice's prompt length), plan_cfm's inputs, and `frags[bi]` of every shared fold."""
@@ -1293,10 +1388,14 @@ class TTS:
             pl["cfm_folds"], pl["T_min"] = [0] * len(pl["data"]), 0
             if not pl["opts"]["parallel_infer"] or not pl["data"]:
                 continue
+            lora = pl["opts"].get("lora_voice")
             with self._with_prompt_cache(dict(pl["voice"])):
+                # a LoRA voice with an encoder-side engine of its own has its own prompt features of the same reference audio
                 vk = voice_of[r] = self._voice_key(pl["voice"], self._CFM_VOICE_FIELDS)
+                if lora is not None:
+                    vk = voice_of[r] = vk + (id(self._lora_voice(lora)[0]),)
                 if vk not in prompts:
-                    prompts[vk] = self._prompt_features()
+                    prompts[vk] = self._prompt_features(*([] if lora is None else [lora]))
                 prompt = prompts[vk]
                 pl["T_min"] = prompt[4]
                 for bi, item in enumerate(pl["data"]):
@@ -1305,7 +1404,7 @@ class TTS:
                         continue
                     fold_in[(r, bi)] = self._fold_chunks(prompt, idx_list, pl["preds"][bi],
                                                          [ph.to(self.configs.device) for ph in item["phones"]],
-                                                         pl["opts"]["speed_factor"])
+                                                         pl["opts"]["speed_factor"], *([] if lora is None else [lora]))
                     pl["cfm_folds"][bi] = sum(fold_in[(r, bi)][1])
         fold_out: Dict[Tuple[int, int], list] = {}
         for rows in self.plan_cfm(plans):
@@ -1313,8 +1412,10 @@ class TTS:
             mels = [prompts[voice_of[r]][3] for r, _, _ in rows]
             seeds = [CFM.row_seed(plans[r]["actual_seed"] + bi, k) for r, bi, k in rows]
             o = plans[rows[0][0]]["opts"]           # a pass is of one (sample_steps, guidance rate) group
+            names = [plans[r]["opts"].get("lora_voice") for r, _, _ in rows]            # rows of any voice share the pass
+            lora_kw = dict(adapters=[None if n is None else self._lora_voice(n)[1] for n in names]) if any(names) else {}
             pred = self.vits_model.cfm.inference_rows(mu, mels, o["sample_steps"], seeds=seeds,
-                                                      inference_cfg_rate=o["inference_cfg_rate"])
+                                                      inference_cfg_rate=o["inference_cfg_rate"], **lora_kw)
             for n, (r, bi, k) in enumerate(rows):
                 fold_out.setdefault((r, bi), []).append(pred[n:n + 1, :, mels[n].shape[2]:])
         for (r, bi), got in fold_out.items():        # a fold is finished when all its rows are back
@@ -1471,8 +1572,11 @@ class TTS:
                 if self._t2s_state is not None and self._vits_state is not None:
                     self.t2s_model = None
                     self.vits_model = None
+                    lora_voices = self._lora_voices
                     self.init_t2s_weights(self.configs.t2s_weights_path, state=self._t2s_state)
                     self.init_vits_weights(self.configs.vits_weights_path, state=self._vits_state)
+                    for name, v in lora_voices.items():
+                        self.add_lora_voice(name, state=v["state"])
             finally:
                 raise e
 

@@ -137,6 +137,14 @@ _SIGS = {
     "gsv_cfm_inference_guided": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int,
                                            C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.c_float, C.c_float, C.c_void_p,
                                            C.c_void_p]),
+    "gsv_cfm_adapter_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    "gsv_cfm_adapter_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
+    "gsv_cfm_adapter_finalize": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "gsv_cfm_adapter_remove": (C.c_int, [C.c_void_p, C.c_int]),
+    "gsv_cfm_adapter_count": (C.c_int, [C.c_void_p]),
+    "gsv_cfm_inference_adapted": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                            C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.c_float, C.c_float,
+                                            C.c_void_p, C.c_void_p]),
     "gsv_sola": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "gsv_postprocess": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "gsv_postprocess_f32": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -170,6 +178,8 @@ _SIGS = {
                                       C.c_void_p, C.c_int, C.c_void_p]),
     "gsv_op_layernorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                    C.c_float, C.c_int, C.c_void_p]),
+    "gsv_op_lora_delta": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int,
+                                   C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p, C.c_int, C.c_void_p]),
     "gsv_op_decode_attn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.c_void_p, C.c_void_p]),
     "gsv_op_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
@@ -180,6 +190,8 @@ _SIGS = {
 
 EXPORTS = tuple(_SIGS)   # every symbol include/gsv.h declares
 VITS_MAX_VOICES = 128    # GSV_VITS_MAX_VOICES (gsv.h): voice slots of the segmented decode
+CFM_MAX_ADAPTERS = 256   # GSV_CFM_MAX_ADAPTERS (gsv.h): LoRA adapters one DiT engine holds at once
+LORA_MAX_RANK = 128      # GSV_LORA_MAX_RANK (gsv.h)
 
 _lib = None
 

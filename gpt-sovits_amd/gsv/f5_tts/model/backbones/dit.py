@@ -37,6 +37,7 @@ class DiT:
             self._h = h
             self.stream = torch.cuda.Stream(device=self.device)
         self._loaded = False
+        self._adapters = set()          # live adapter slots (add_adapter)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -62,6 +63,41 @@ class DiT:
             _lib.check(l.gsv_cfm_finalize(self._h), "gsv_cfm_finalize")
         self._loaded = True
         return self
+
+    # ---- LoRA adapters held beside the base weights (gsv_cfm_adapter_*): rows of one pass may each use their own ------------
+    ADAPTER_SITES = ("to_q", "to_k", "to_v", "to_out.0")
+
+    def add_adapter(self, adapter: Dict[str, torch.Tensor], rank: int, alpha=None) -> int:
+        """`adapter`: `transformer_blocks.<i>.attn.{to_q,to_k,to_v,to_out.0}.lora_{A,B}` -> tensor (lora_A [rank, in], lora_B
+        [out, rank]; what process_ckpt.split_lora_v3 returns), all 4 * depth pairs.  `alpha` is peft's lora_alpha, None =
+        rank as the reference trains.  Returns the slot CFM.inference_rows(adapters=...) takes; the engine holds at most
+        _lib.CFM_MAX_ADAPTERS at once."""
+        if not self._loaded:
+            raise RuntimeError("DiT.load_state_dict() first")
+        rank = int(rank)
+        if not 1 <= rank <= _lib.LORA_MAX_RANK:
+            raise ValueError(f"LoRA rank must be in [1, {_lib.LORA_MAX_RANK}], got {rank}")
+        alpha = float(rank if alpha is None else alpha)
+        l = _lib.lib()
+        slot = C.c_int(-1)
+        with torch.cuda.device(self.device):
+            _lib.check(l.gsv_cfm_adapter_begin(self._h, rank, alpha), "gsv_cfm_adapter_begin")
+            for k, v in adapter.items():
+                t = v.detach().to("cpu", torch.float32).contiguous()
+                _lib.check(l.gsv_cfm_adapter_load_tensor(self._h, k.encode(), t.data_ptr(), t.numel()), f"load {k}")
+            _lib.check(l.gsv_cfm_adapter_finalize(self._h, C.byref(slot)), "gsv_cfm_adapter_finalize")
+        self._adapters.add(slot.value)
+        return slot.value
+
+    def remove_adapter(self, slot: int) -> None:
+        if slot not in self._adapters:
+            raise ValueError(f"no adapter in slot {slot}")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().gsv_cfm_adapter_remove(self._h, int(slot)), "gsv_cfm_adapter_remove")
+        self._adapters.discard(slot)
+
+    def adapter_count(self) -> int:
+        return int(_lib.lib().gsv_cfm_adapter_count(self._h))
 
     def eval(self):
         return self

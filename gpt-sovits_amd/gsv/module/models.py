@@ -283,11 +283,20 @@ class SynthesizerTrnV3(SynthesizerTrn):
     """Mirror of the reference's `SynthesizerTrnV3` inference interface (module/models.py:1128-1272) for v3 / v4:
     `decode_encp` (enc_p -> bridge -> nearest x1.875 | x2 -> wns1) in the same HIP engine as v2's enc_p, and `cfm`,
     the flow-matching decoder (`CFM` over `DiT`).  The checkpoint's `cfm.estimator.*` keys go to the DiT engine, the
-    rest to the encoder engine."""
+    rest to the encoder engine.  `cfm` (no counterpart in the reference): build the encoder engine around that loaded `CFM`
+    instead of creating and loading a DiT of its own -- the encoder-side engine of a LoRA voice that is served beside the
+    base model (TTS.add_lora_voice); load_state_dict then takes the encoder weights only."""
     _VERSIONS = ("v3", "v4")
 
-    def __init__(self, *args, version="v3", device="cuda:0", dtype=torch.float16, dit_kwargs: Optional[dict] = None, **kwargs):
+    def __init__(self, *args, version="v3", device="cuda:0", dtype=torch.float16, dit_kwargs: Optional[dict] = None,
+                 cfm: Optional["CFM"] = None, **kwargs):
         super().__init__(*args, version=version, device=device, dtype=dtype, **kwargs)
+        self._shared_cfm = cfm is not None
+        if cfm is not None:
+            if cfm.estimator.dtype != dtype or cfm.estimator.device != self.device:
+                raise ValueError("the shared CFM must be on this engine's device, in its dtype")
+            self.cfm = cfm
+            return
         from ..f5_tts.model.backbones.dit import DiT
         dk = dict(dim=1024, depth=22, heads=16, ff_mult=2, text_dim=512, conv_layers=4)     # models.py:1219-1222
         if dit_kwargs:
@@ -298,7 +307,8 @@ class SynthesizerTrnV3(SynthesizerTrn):
         enc = {k: v for k, v in state_dict.items() if not k.startswith("cfm.")}
         dit = {k: v for k, v in state_dict.items() if k.startswith("cfm.estimator.")}
         super().load_state_dict(enc, strict)
-        self.cfm.estimator.load_state_dict(dit)
+        if not self._shared_cfm:
+            self.cfm.estimator.load_state_dict(dit)
         return self
 
     def decode(self, *a, **k):
@@ -431,9 +441,29 @@ class CFM:
             dit.stream.synchronize()
         return out.to(mu.dtype if mu.dtype in (torch.float16, torch.float32) else torch.float32)
 
+    def add_adapter(self, adapter, rank, alpha=None) -> int:
+        """A LoRA voice's adapter into the estimator (DiT.add_adapter) -> its slot, for `adapters=` below"""
+        return self.estimator.add_adapter(adapter, rank, alpha)
+
+    def remove_adapter(self, slot: int) -> None:
+        self.estimator.remove_adapter(slot)
+
+    def _adapter_slots(self, adapters, B):
+        """`adapters` (B slots or None entries, or None) -> B ints, -1 = the base model, or None when no row is adapted"""
+        if adapters is None:
+            return None
+        if len(adapters) != B:
+            raise ValueError(f"expected {B} adapters, one per row of mu (None = the base model), got {len(adapters)}")
+        slots = [-1 if a is None else int(a) for a in adapters]
+        for b, a in enumerate(slots):
+            if a != -1 and a not in self.estimator._adapters:
+                raise ValueError(f"row {b}: no adapter in slot {a}")
+        return slots if any(a >= 0 for a in slots) else None
+
     @torch.no_grad()
-    def inference(self, mu, x_lens, prompt, n_timesteps, temperature=1.0, inference_cfg_rate=0, noise=None, seed=0):
-        """mu [B, T, text_dim]; x_lens unused (as in the reference); prompt [B, in_channels, Tp] -> [B, in_channels, T]"""
+    def inference(self, mu, x_lens, prompt, n_timesteps, temperature=1.0, inference_cfg_rate=0, noise=None, seed=0, adapters=None):
+        """mu [B, T, text_dim]; x_lens unused (as in the reference); prompt [B, in_channels, Tp] -> [B, in_channels, T].
+        `adapters` (B slots or None entries) with a slot among them: the rows entry, as `inference_guided` takes it."""
         if inference_cfg_rate > 1e-5:
             raise NotImplementedError("CFM.inference is the unguided entry (every caller in the reference passes "
                                       "inference_cfg_rate=0, TTS.py:1351, inference_webui.py:937); classifier-free guidance "
@@ -441,6 +471,9 @@ class CFM:
         B, T = self._check_mu_noise(mu, noise)
         if prompt.dim() != 3 or prompt.shape[0] not in (1, B) or prompt.shape[1] != self.in_channels or prompt.shape[2] > T:
             raise ValueError(f"expected prompt of shape [{B} or 1, {self.in_channels}, Tp<={T}], got {tuple(prompt.shape)}")
+        if self._adapter_slots(adapters, B) is not None:
+            return self.inference_guided(mu, x_lens, prompt, n_timesteps, temperature=temperature, noise=noise, seed=seed,
+                                         adapters=adapters)
         if prompt.shape[0] != B:           # one prompt broadcast over the batch (models.py:1036 assigns it into every row)
             prompt = prompt.expand(B, -1, -1)
         Tp = int(prompt.shape[2])
@@ -452,29 +485,37 @@ class CFM:
         return self._launch(mu, [prompt], noise, call)
 
     @torch.no_grad()
-    def inference_guided(self, mu, x_lens, prompt, n_timesteps, temperature=1.0, inference_cfg_rate=0, noise=None, seed=0):
+    def inference_guided(self, mu, x_lens, prompt, n_timesteps, temperature=1.0, inference_cfg_rate=0, noise=None, seed=0,
+                         adapters=None):
         """The reference's `CFM.inference(..., inference_cfg_rate=r)` with classifier-free guidance (models.py:1063-1081);
         arguments as `inference`.  r > 1e-5: the rows entry with uniform prompts and seeds[b] = row_seed(seed, b), so the
-        noise is the unguided call's.  r <= 1e-5 (zero and negative rates included) is `inference` itself."""
+        noise is the unguided call's.  r <= 1e-5 (zero and negative rates included) is `inference` itself.
+        `adapters` (B slots or None entries): as in `inference_rows`; with an adapted row every rate takes the rows entry."""
         if not math.isfinite(inference_cfg_rate):
             raise ValueError(f"inference_cfg_rate must be finite, got {inference_cfg_rate}")
-        if not cfg_guided(inference_cfg_rate):
+        if adapters is not None and mu.dim() == 3:
+            adapters = self._adapter_slots(adapters, int(mu.shape[0]))
+        if not cfg_guided(inference_cfg_rate) and adapters is None:
             return self.inference(mu, x_lens, prompt, n_timesteps, temperature=temperature, noise=noise, seed=seed)
         B = int(mu.shape[0]) if mu.dim() == 3 else 0
         if prompt.dim() != 3 or prompt.shape[0] not in (1, B):
             raise ValueError(f"expected prompt of shape [{B} or 1, {self.in_channels}, Tp], got {tuple(prompt.shape)}")
         return self.inference_rows(mu, [prompt[b:b + 1] if prompt.shape[0] == B else prompt for b in range(B)], n_timesteps,
                                    temperature=temperature, noise=noise, seeds=[self.row_seed(seed, b) for b in range(B)],
-                                   inference_cfg_rate=inference_cfg_rate)
+                                   inference_cfg_rate=inference_cfg_rate, adapters=adapters)
 
     @torch.no_grad()
-    def inference_rows(self, mu, prompts, n_timesteps, temperature=1.0, noise=None, seeds=None, inference_cfg_rate=0):
+    def inference_rows(self, mu, prompts, n_timesteps, temperature=1.0, noise=None, seeds=None, inference_cfg_rate=0, adapters=None):
         """`inference` for B rows that each have their own prompt (`gsv_cfm_inference_rows`): mu [B, T, text_dim]; prompts a
         list of B tensors [1, in_channels, Tp_b], 0 <= Tp_b <= T -> [B, in_channels, T], row b's first Tp_b frames zero.
         `seeds` (B ints) are the rows' own noise keys, taken as they are: row b of `inference(seed=s)` is seeds[b] =
         row_seed(s, b) here.  `noise` [B, in_channels, T] pins the draw instead.  `inference_cfg_rate` > 1e-5
-        guides every row with that rate (`gsv_cfm_inference_guided`, 2 B DiT rows); the noise of a row does not depend on it."""
+        guides every row with that rate (`gsv_cfm_inference_guided`, 2 B DiT rows); the noise of a row does not depend on it.
+        `adapters` (B entries: a slot `add_adapter` returned, or None = the base model): row b runs the DiT with that LoRA
+        adapter (`gsv_cfm_inference_adapted`; a guided row's twin takes the row's).  None, or no slot among them, is the
+        call without the keyword."""
         B, T = self._check_mu_noise(mu, noise)
+        slots = self._adapter_slots(adapters, B)
         if B < 1 or len(prompts) != B:
             raise ValueError(f"expected {B} >= 1 prompts, one per row of mu, got {len(prompts)}")
         for b, p in enumerate(prompts):
@@ -492,7 +533,11 @@ class CFM:
             tps = (C.c_int * B)(*[int(p.shape[2]) for p in ps])
             sd = (C.c_uint64 * B)(*[int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds]) if seeds is not None else None
             h, lib = self.estimator._h, _lib.lib()
-            if cfg_guided(inference_cfg_rate):
+            if slots is not None:
+                _lib.check(lib.gsv_cfm_inference_adapted(h, m.data_ptr(), ptrs, tps, (C.c_int * B)(*slots), B, T, int(n_timesteps), nz,
+                                                         sd, float(temperature), float(inference_cfg_rate), out.data_ptr(), stream),
+                           "gsv_cfm_inference_adapted")
+            elif cfg_guided(inference_cfg_rate):
                 _lib.check(lib.gsv_cfm_inference_guided(h, m.data_ptr(), ptrs, tps, B, T, int(n_timesteps), nz, sd, float(temperature),
                                                         float(inference_cfg_rate), out.data_ptr(), stream), "gsv_cfm_inference_guided")
             else:

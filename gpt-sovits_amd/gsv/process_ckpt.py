@@ -109,3 +109,50 @@ def merge_lora_v3(base_weight: dict, lora_weight: dict, lora_rank: int, lora_alp
     if merged == 0:
         raise ValueError("no lora_A / lora_B pairs in the LoRA checkpoint")
     return out
+
+
+_LORA_SITES = ("to_q", "to_k", "to_v", "to_out.0")
+
+
+def split_lora_v3(lora_weight: dict, lora_rank: int, lora_alpha: int = None) -> Tuple[dict, dict]:
+    """A v3 / v4 LoRA checkpoint's state dict taken apart instead of merged (`merge_lora_v3`), for a voice that is served
+    beside the base model: -> (adapter, overrides).
+    `adapter`: `transformer_blocks.<i>.attn.{to_q,to_k,to_v,to_out.0}.lora_{A,B}` -> fp32 tensor, the names
+    `DiT.add_adapter` takes; the factors are as stored, `lora_alpha / lora_rank` (None = 1, as the reference trains) is applied
+    by the engine.  `overrides`: every other entry, under the base model's name for it (as `merge_lora_v3` lays it over the
+    base weights), tensors untouched; entries that name no base parameter are dropped there as they are by the merge.
+    Accepts both spellings `merge_lora_v3` accepts and raises what it raises: KeyError for a lora_A without its lora_B and
+    for a target outside the DiT's attention projections, ValueError for a rank that is not `lora_rank` and for a file
+    without any pair.  `lora_alpha` is only checked here (positive)."""
+    if lora_alpha is not None and not lora_alpha > 0:
+        raise ValueError(f"lora_alpha must be positive, got {lora_alpha}")
+    adapter, overrides = {}, {}
+    for k, a in lora_weight.items():
+        if k.endswith(".lora_A.default.weight") or k.endswith(".lora_A.weight"):
+            stem = k[:k.index(".lora_A.")]
+            kb = k.replace(".lora_A.", ".lora_B.")
+            if kb not in lora_weight:
+                raise KeyError(f"{k} has no matching lora_B")
+            b = lora_weight[kb]
+            if a.shape[0] != lora_rank or b.shape[1] != lora_rank:
+                raise ValueError(f"{k}: rank {a.shape[0]} / {b.shape[1]} does not match lora_rank {lora_rank}")
+            path = stem[len(_PEFT_PREFIX):] if stem.startswith(_PEFT_PREFIX) else stem
+            target = ("cfm." + path if stem.startswith(_PEFT_PREFIX) else path) + ".weight"
+            pre = "cfm.estimator."
+            name = target[len(pre):-len(".weight")] if target.startswith(pre) else ""
+            parts = name.split(".attn.")
+            if not (len(parts) == 2 and parts[0].startswith("transformer_blocks.") and parts[0][len("transformer_blocks."):].isdigit()
+                    and parts[1] in _LORA_SITES):
+                raise KeyError(f"LoRA target {target} is not a parameter of the base model")
+            adapter[name + ".lora_A"] = a.float()
+            adapter[name + ".lora_B"] = b.float()
+        elif ".lora_B." in k:
+            continue
+        else:
+            kk = k
+            if kk.startswith(_PEFT_PREFIX):
+                kk = "cfm." + kk[len(_PEFT_PREFIX):]
+            overrides[kk.replace(".base_layer.", ".")] = lora_weight[k]
+    if not adapter:
+        raise ValueError("no lora_A / lora_B pairs in the LoRA checkpoint")
+    return adapter, overrides

@@ -330,6 +330,31 @@ int gsv_cfm_inference_guided(gsv_cfm_t* h, const float* mu, const float* const* 
                              int n_steps, const float* noise, const uint64_t* seeds, float temperature, float cfg_rate,
                              float* out, gsv_stream_t stream);
 
+/* LoRA adapters (fine-tuned v3 / v4 voices, reference s2_train_v3_lora.py:134-139: rank-r adapters on to_q / to_k / to_v /
+ * to_out.0 of every DiT block) held beside the base weights, so rows of ONE pass may each use their own voice.  An adapter is
+ * staged like the base weights: begin (rank 1 .. GSV_LORA_MAX_RANK, alpha > 0; the reference trains with alpha = rank), one
+ * load_tensor per matrix -- names transformer_blocks.<i>.attn.{to_q,to_k,to_v,to_out.0}.lora_{A,B}, host fp32, lora_A
+ * [rank][in], lora_B [out][rank] -- then finalize, which checks that all 4 * depth pairs are there with the right sizes and
+ * nothing else, uploads them (engine dtype, rank padded to a multiple of 16, alpha / rank folded into lora_B in fp32) and
+ * returns the slot: a small integer, reused after gsv_cfm_adapter_remove, at most GSV_CFM_MAX_ADAPTERS live at once.  A
+ * failed finalize drops the staged tensors and leaves the store as it was.  None of these may run while a pass of the same
+ * handle is in flight. */
+#define GSV_CFM_MAX_ADAPTERS 256
+#define GSV_LORA_MAX_RANK 128
+int gsv_cfm_adapter_begin(gsv_cfm_t* h, int rank, float alpha);
+int gsv_cfm_adapter_load_tensor(gsv_cfm_t* h, const char* name, const float* data, int64_t numel);
+int gsv_cfm_adapter_finalize(gsv_cfm_t* h, int* slot);
+int gsv_cfm_adapter_remove(gsv_cfm_t* h, int slot);
+int gsv_cfm_adapter_count(gsv_cfm_t* h);   /* live adapters, or a negative error code */
+/* gsv_cfm_inference_guided (cfg_rate <= 1e-5: gsv_cfm_inference_rows) whose row b runs the DiT with adapter adapters[b]
+ * ([host] B slots; -1 = the base model; NULL = every row the base model): after the q/k/v GEMM and after the out-projection
+ * GEMM of every block the rows with a slot receive (alpha / r) * B A x, under the out-projection's gate.  A guided row's
+ * unconditioned twin takes the row's slot.  A pass without an adapted row issues exactly the launches of the entry above.
+ * A slot that is out of range or not live returns an error before anything is launched. */
+int gsv_cfm_inference_adapted(gsv_cfm_t* h, const float* mu, const float* const* prompts, const int* Tp, const int* adapters,
+                              int B, int T, int n_steps, const float* noise, const uint64_t* seeds, float temperature,
+                              float cfg_rate, float* out, gsv_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * SOLA stitching of the chunked v3/v4 vocoder output (H17, TTS.sola_algorithm, TTS_infer_pack/TTS.py:1611-1637).
  * frags [dev] fp32: the n fragments back to back (lens [host] samples each, every one >= 2 * overlap); modified in
@@ -436,6 +461,14 @@ uint64_t gsv_debug_last_pair_route(int reset);
 /* y = LN(x (+res)) over the last dim C; all buffers of `dtype`, gamma/beta fp32 */
 int gsv_op_layernorm(const void* x, const void* res, const float* gamma, const float* beta, void* y, int rows,
                      int C, float eps, int dtype, gsv_stream_t stream);
+/* the per-row low-rank delta of the adapted DiT passes (csrc/lora.hip), a test hook that waits for the kernel: x [dev]
+ * [DB * Tn][K] and y [dev] [DB * Tn][N] of `dtype`; row b (its Tn frames) with s = slots[b] >= 0 ([host] DB ints, -1 = leave
+ * the row alone) gets y += gate (.) ((x A_s^T) B_s^T).  blocks [host] n_slots device pointers: block s is A_s
+ * [n_proj * rp[s]][K] followed by B_s [N][rp[s]] in `dtype`, rp[s] ([host]) the rank padded to a multiple of 16 (16 .. 128);
+ * output column c contracts with columns [p * rp, (p + 1) * rp) of x A_s^T, p = c / (N / n_proj).  gate [dev] fp32 [N] or
+ * NULL.  K a multiple of 32, N / n_proj a multiple of 16, n_proj 1 .. 3. */
+int gsv_op_lora_delta(const void* x, void* y, int Tn, int DB, int K, int N, int n_proj, const int* slots, int n_slots,
+                      const void* const* blocks, const int* rp, const float* gate, int dtype, gsv_stream_t stream);
 /* reference-audio front-end helpers (host orchestration in gsv/module/mel_processing.py and
  * gsv/feature_extractor/cnhubert.py, the GEMMs are gsv_op_conv1d):
  *  gsv_op_frame: out[t][k] = x[reflect(t*hop + k - pad)], k < frame_len, zero up to ld; x [dev] fp32 [n]; out [T_out][ld] of dtype

@@ -222,10 +222,9 @@ std::vector<float> sinc_kernel(int orig, int nw, int* o_out, int* q_out, int* wi
 
 }  // namespace
 
-struct gsv_bwe {
-  gsv_vits ctx;
+struct gsv_bwe : gsveng::Ctx {
+  gsv_bwe() : Ctx("bwe") {}
   gsv_bwe_config cfg;
-  bool finalized = false;
   int bins = 0, bp = 0, lds = 0;     // n_fft / 2 + 1, conv_pre operand width (16-aligned), spectrum row (4-aligned)
   float *fwd = nullptr, *inv = nullptr, *win = nullptr;   // fp32 [2 bins][n_fft], [n_fft][lds], [n_fft]
   void *pre_w = nullptr, *pw1 = nullptr, *pw2 = nullptr;   // [2][C][7 bp], [L][2][3C][C], [L][2][C][3C] (engine dtype)
@@ -254,7 +253,7 @@ int bwe_resample_tab(gsv_bwe* b, int orig, ResampleTab** out) {
     std::vector<float> k = sinc_kernel(orig, b->cfg.hr_sampling_rate, &r.o, &r.q, &r.width);
     r.L = 2 * r.width + r.o;
     if (orig == b->cfg.hr_sampling_rate) r.L = 1;
-    GSV_RC(up_f32(&b->ctx, k.data(), k.size(), &r.k));
+    GSV_RC(up_f32(b, k.data(), k.size(), &r.k));
     it = b->rtabs.emplace(orig, r).first;
   }
   *out = &it->second;
@@ -270,7 +269,7 @@ int branch_gemm(gsv_bwe* b, hipStream_t s, const void* x, int K, const void* w, 
   a.ldx = K; a.ldw = K; a.ldy = N; a.ldr = N; a.post_act = act;
   a.Z = 2; a.xz = (long long)Tn * K; a.wz = (long long)N * K; a.yz = (long long)Tn * N; a.rz = a.yz; a.bz = N;
   a.z_res = res ? 1 : 0;
-  return launch_conv_gemm(b->ctx.dtype, a, s);
+  return launch_conv_gemm(b->dtype, a, s);
 }
 
 template <typename T>
@@ -304,26 +303,25 @@ int launch_mix(const void* x, int Tn, int C, const float* dww, const float* dwb,
 
 template <typename T, typename TI>
 int bwe_forward_t(gsv_bwe* b, hipStream_t s, const TI* wav, int n, const ResampleTab& rt, int n_new, float* out) {
-  gsv_vits* h = &b->ctx;
   const auto& g = b->cfg;
   const int F = g.n_fft, hop = g.hop_size, C = g.channels, B = b->bins, bp = b->bp, ld = b->lds;
   const int Tn = 1 + n_new / hop, L = hop * (n_new / hop);
   const size_t es = sizeof(T);
   float *res, *frames, *ri, *la, *pha, *mag, *phawb, *spec;
   void *x0, *xb, *rb, *ab, *hb;
-  GSV_RC(need(h, "bwe_res", (size_t)n_new * 4, (void**)&res));
-  GSV_RC(need(h, "bwe_frames", (size_t)Tn * F * 4, (void**)&frames));
-  GSV_RC(need(h, "bwe_ri", (size_t)Tn * 2 * B * 4, (void**)&ri));
-  GSV_RC(need(h, "bwe_la", (size_t)Tn * B * 4, (void**)&la));
-  GSV_RC(need(h, "bwe_pha", (size_t)Tn * B * 4, (void**)&pha));
-  GSV_RC(need(h, "bwe_mag", (size_t)Tn * B * 4, (void**)&mag));
-  GSV_RC(need(h, "bwe_phawb", (size_t)Tn * B * 4, (void**)&phawb));
-  GSV_RC(need(h, "bwe_spec", (size_t)Tn * ld * 4, (void**)&spec));
-  GSV_RC(need(h, "bwe_x0", (size_t)2 * Tn * bp * es, &x0));
-  GSV_RC(need(h, "bwe_x", (size_t)2 * Tn * C * es, &xb));
-  GSV_RC(need(h, "bwe_r", (size_t)2 * Tn * C * es, &rb));
-  GSV_RC(need(h, "bwe_a", (size_t)2 * Tn * C * es, &ab));
-  GSV_RC(need(h, "bwe_h", (size_t)2 * Tn * 3 * C * es, &hb));
+  GSV_RC(need(b, "bwe_res", (size_t)n_new * 4, (void**)&res));
+  GSV_RC(need(b, "bwe_frames", (size_t)Tn * F * 4, (void**)&frames));
+  GSV_RC(need(b, "bwe_ri", (size_t)Tn * 2 * B * 4, (void**)&ri));
+  GSV_RC(need(b, "bwe_la", (size_t)Tn * B * 4, (void**)&la));
+  GSV_RC(need(b, "bwe_pha", (size_t)Tn * B * 4, (void**)&pha));
+  GSV_RC(need(b, "bwe_mag", (size_t)Tn * B * 4, (void**)&mag));
+  GSV_RC(need(b, "bwe_phawb", (size_t)Tn * B * 4, (void**)&phawb));
+  GSV_RC(need(b, "bwe_spec", (size_t)Tn * ld * 4, (void**)&spec));
+  GSV_RC(need(b, "bwe_x0", (size_t)2 * Tn * bp * es, &x0));
+  GSV_RC(need(b, "bwe_x", (size_t)2 * Tn * C * es, &xb));
+  GSV_RC(need(b, "bwe_r", (size_t)2 * Tn * C * es, &rb));
+  GSV_RC(need(b, "bwe_a", (size_t)2 * Tn * C * es, &ab));
+  GSV_RC(need(b, "bwe_h", (size_t)2 * Tn * 3 * C * es, &hb));
 
   // ---- resample + STFT (audio_sr.py:47-48, dataset.py:9-27)
   hipLaunchKernelGGL(bwe_frame_kernel<TI>, dim3(cdiv(F, 256), Tn), dim3(256), 0, s, wav, n, rt.k, rt.o, rt.q, rt.width, rt.L, n_new, F,
@@ -344,11 +342,11 @@ int bwe_forward_t(gsv_bwe* b, hipStream_t s, const TI* wav, int n, const Resampl
     a.T_in = a.T_out = a.T_virt = Tn; a.Cin = bp; a.Cout = C; a.taps = 7; a.pad = 3;
     a.ldx = bp; a.ldw = 7 * bp; a.ldy = C; a.ldr = C;
     a.Z = 2; a.xz = (long long)Tn * bp; a.wz = (long long)C * 7 * bp; a.yz = (long long)Tn * C; a.bz = C;
-    GSV_RC(launch_conv_gemm(h->dtype, a, s));
+    GSV_RC(launch_conv_gemm(b->dtype, a, s));
   }
   for (int z = 0; z < 2; ++z) {
     void* p = (char*)xb + (size_t)z * Tn * C * es;
-    GSV_RC(launch_layernorm(h->dtype, p, 0, nullptr, 0, b->pre_g + z * C, b->pre_beta + z * C, p, 0, Tn, C, 1e-6f, s));
+    GSV_RC(launch_layernorm(b->dtype, p, 0, nullptr, 0, b->pre_g + z * C, b->pre_beta + z * C, p, 0, Tn, C, 1e-6f, s));
   }
 
   // ---- ConvNeXt layers (model.py:129-133)
@@ -363,14 +361,14 @@ int bwe_forward_t(gsv_bwe* b, hipStream_t s, const TI* wav, int n, const Resampl
   // ---- post head (model.py:135-141)
   for (int z = 0; z < 2; ++z) {
     const size_t off = (size_t)z * Tn * C * es;
-    GSV_RC(launch_layernorm(h->dtype, (char*)xb + off, 0, nullptr, 0, b->post_g + z * C, b->post_beta + z * C, (char*)ab + off, 0, Tn, C,
+    GSV_RC(launch_layernorm(b->dtype, (char*)xb + off, 0, nullptr, 0, b->post_g + z * C, b->post_beta + z * C, (char*)ab + off, 0, Tn, C,
                             1e-6f, s));
   }
   {
     ConvOpt om; om.out_f32 = 1; om.res = la; om.res_f32 = 1; om.ldr = B;
-    GSV_RC(conv(h, s, b->post_mag, ab, C, Tn, mag, Tn, om));
+    GSV_RC(conv(b, s, b->post_mag, ab, C, Tn, mag, Tn, om));
     ConvOpt op; op.out_f32 = 1;
-    GSV_RC(conv(h, s, b->post_pha, (char*)ab + (size_t)Tn * C * es, C, Tn, ri, Tn, op));
+    GSV_RC(conv(b, s, b->post_pha, (char*)ab + (size_t)Tn * C * es, C, Tn, ri, Tn, op));
   }
   BWE_LAUNCH(bwe_spec_kernel, (long long)Tn * ld, mag, ri, Tn, B, ld, phawb, spec);
 
@@ -387,12 +385,10 @@ int bwe_forward_t(gsv_bwe* b, hipStream_t s, const TI* wav, int n, const Resampl
   return GSV_OK;
 }
 
-int fetch_into(gsv_vits* h, const std::string& name, size_t n, std::vector<float>& dst) {
+// appends the staged tensor to dst
+int fetch_into(Ctx* h, const std::string& name, size_t n, std::vector<float>& dst) {
   std::vector<float> v;
-  if (!fetch(h, name, n, (int)n, v)) {
-    if (h->staged.find(name) == h->staged.end()) set_error("bwe: tensor '%s' missing", name.c_str());
-    return GSV_ERR_ARG;
-  }
+  if (!fetch(h, name, n, (int)n, v)) return GSV_ERR_ARG;
   dst.insert(dst.end(), v.begin(), v.end());
   return GSV_OK;
 }
@@ -412,11 +408,10 @@ int gsv_bwe_create(const gsv_bwe_config* cfg, int dtype, gsv_bwe_t** out) {
   GSV_REQUIRE(C == 64 || C == 128 || C == 256 || C == 512 || C == 768 || C == 1024,
               "bwe_create: ConvNeXt_channels=%d must be 64, 128, 256, 512, 768 or 1024", C);
   GSV_REQUIRE(cfg->layers >= 0 && cfg->hr_sampling_rate > 0, "bwe_create: bad layers / hr_sampling_rate");
-  int n = 0;
-  GSV_HIP(hipGetDeviceCount(&n));
+  GSV_RC(require_device());
   gsv_bwe* b = new gsv_bwe();
   b->cfg = *cfg;
-  b->ctx.dtype = dtype;
+  b->dtype = dtype;
   b->bins = cfg->n_fft / 2 + 1;
   b->bp = (b->bins + 15) / 16 * 16;
   b->lds = (2 * b->bins + 3) / 4 * 4;
@@ -426,37 +421,33 @@ int gsv_bwe_create(const gsv_bwe_config* cfg, int dtype, gsv_bwe_t** out) {
 
 void gsv_bwe_destroy(gsv_bwe_t* b) {
   if (!b) return;
-  free_ctx(&b->ctx);
+  free_ctx(b);
   delete b;
 }
 
 int gsv_bwe_load_tensor(gsv_bwe_t* b, const char* name, const float* data, int64_t numel) {
-  GSV_REQUIRE(b && name && data && numel > 0, "bwe_load_tensor: bad argument");
-  GSV_REQUIRE(!b->finalized, "bwe_load_tensor: handle already finalized");
-  b->ctx.staged[name].assign(data, data + numel);
-  return GSV_OK;
+  return stage_tensor(b, name, data, numel);
 }
 
 int gsv_bwe_finalize(gsv_bwe_t* b) {
   GSV_REQUIRE(b && !b->finalized, "bwe_finalize: bad handle");
-  gsv_vits* h = &b->ctx;
   const auto& g = b->cfg;
   const int F = g.n_fft, C = g.channels, B = b->bins, bp = b->bp, ld = b->lds, NL = g.layers;
   // DFT bases (gsv/module/mel_processing.py::_dft_basis): forward [2 bins][n_fft], inverse [n_fft][2 bins] -> rows padded to lds
   {
     std::vector<float> fw, iv;
-    GSV_RC(fetch_into(h, "dft.forward", (size_t)2 * B * F, fw));
-    GSV_RC(fetch_into(h, "dft.inverse", (size_t)F * 2 * B, iv));
+    GSV_RC(fetch_into(b, "dft.forward", (size_t)2 * B * F, fw));
+    GSV_RC(fetch_into(b, "dft.inverse", (size_t)F * 2 * B, iv));
     // the DC and Nyquist rows of the imaginary half are exact zeros, as an FFT computes them (sin(pi n) of the float64 basis
     // is 1e-16, not 0: its sign would flip the phase of a bin with a negative real part between +pi and -pi)
     std::fill(fw.begin() + (size_t)B * F, fw.begin() + (size_t)(B + 1) * F, 0.f);
     std::fill(fw.begin() + (size_t)(2 * B - 1) * F, fw.end(), 0.f);
-    GSV_RC(up_f32(h, fw.data(), fw.size(), &b->fwd));
+    GSV_RC(up_f32(b, fw.data(), fw.size(), &b->fwd));
     std::vector<float> ip((size_t)F * ld, 0.f), w(F);
     for (int r = 0; r < F; ++r) std::copy(iv.begin() + (size_t)r * 2 * B, iv.begin() + (size_t)(r + 1) * 2 * B, ip.begin() + (size_t)r * ld);
-    GSV_RC(up_f32(h, ip.data(), ip.size(), &b->inv));
+    GSV_RC(up_f32(b, ip.data(), ip.size(), &b->inv));
     for (int k = 0; k < F; ++k) w[k] = fw[k];                 // row 0 of the forward basis = the centred window (cos 0 = 1)
-    GSV_RC(up_f32(h, w.data(), w.size(), &b->win));
+    GSV_RC(up_f32(b, w.data(), w.size(), &b->win));
   }
   const char* br[2] = {"mag", "pha"};
   {
@@ -464,22 +455,22 @@ int gsv_bwe_finalize(gsv_bwe_t* b) {
     for (int z = 0; z < 2; ++z) {
       const std::string p = std::string("conv_pre_") + br[z];
       std::vector<float> w;
-      if (!fetch(h, p + ".weight", (size_t)C * B * 7, C, w)) return GSV_ERR_ARG;
+      if (!fetch(b, p + ".weight", (size_t)C * B * 7, C, w)) return GSV_ERR_ARG;
       for (int o = 0; o < C; ++o)
         for (int i = 0; i < B; ++i)
           for (int j = 0; j < 7; ++j) pw[(((size_t)z * C + o) * 7 + j) * bp + i] = w[((size_t)o * B + i) * 7 + j];
-      GSV_RC(fetch_into(h, p + ".bias", C, pb));
-      GSV_RC(fetch_into(h, std::string("norm_pre_") + br[z] + ".weight", C, pg));
-      GSV_RC(fetch_into(h, std::string("norm_pre_") + br[z] + ".bias", C, pbeta));
-      GSV_RC(fetch_into(h, std::string("norm_post_") + br[z] + ".weight", C, qg));
-      GSV_RC(fetch_into(h, std::string("norm_post_") + br[z] + ".bias", C, qbeta));
+      GSV_RC(fetch_into(b, p + ".bias", C, pb));
+      GSV_RC(fetch_into(b, std::string("norm_pre_") + br[z] + ".weight", C, pg));
+      GSV_RC(fetch_into(b, std::string("norm_pre_") + br[z] + ".bias", C, pbeta));
+      GSV_RC(fetch_into(b, std::string("norm_post_") + br[z] + ".weight", C, qg));
+      GSV_RC(fetch_into(b, std::string("norm_post_") + br[z] + ".bias", C, qbeta));
     }
-    GSV_RC(up_t(h, pw, &b->pre_w));
-    GSV_RC(up_f32(h, pb.data(), pb.size(), &b->pre_b));
-    GSV_RC(up_f32(h, pg.data(), pg.size(), &b->pre_g));
-    GSV_RC(up_f32(h, pbeta.data(), pbeta.size(), &b->pre_beta));
-    GSV_RC(up_f32(h, qg.data(), qg.size(), &b->post_g));
-    GSV_RC(up_f32(h, qbeta.data(), qbeta.size(), &b->post_beta));
+    GSV_RC(up_t(b, pw, &b->pre_w));
+    GSV_RC(up_f32(b, pb.data(), pb.size(), &b->pre_b));
+    GSV_RC(up_f32(b, pg.data(), pg.size(), &b->pre_g));
+    GSV_RC(up_f32(b, pbeta.data(), pbeta.size(), &b->pre_beta));
+    GSV_RC(up_f32(b, qg.data(), qg.size(), &b->post_g));
+    GSV_RC(up_f32(b, qbeta.data(), qbeta.size(), &b->post_beta));
   }
   // ConvNeXt blocks, layer-major then branch: [L][2][...]
   {
@@ -487,31 +478,31 @@ int gsv_bwe_finalize(gsv_bwe_t* b) {
     for (int l = 0; l < NL; ++l)
       for (int z = 0; z < 2; ++z) {
         const std::string p = std::string("convnext_") + br[z] + "." + std::to_string(l) + ".";
-        GSV_RC(fetch_into(h, p + "dwconv.weight", (size_t)C * 7, dw));
-        GSV_RC(fetch_into(h, p + "dwconv.bias", C, db));
-        GSV_RC(fetch_into(h, p + "norm.weight", C, lg));
-        GSV_RC(fetch_into(h, p + "norm.bias", C, lb));
-        GSV_RC(fetch_into(h, p + "pwconv1.weight", (size_t)3 * C * C, w1));
-        GSV_RC(fetch_into(h, p + "pwconv1.bias", (size_t)3 * C, b1));
-        GSV_RC(fetch_into(h, p + "pwconv2.weight", (size_t)3 * C * C, w2));
-        GSV_RC(fetch_into(h, p + "pwconv2.bias", C, b2));
-        GSV_RC(fetch_into(h, p + "gamma", C, gm));
+        GSV_RC(fetch_into(b, p + "dwconv.weight", (size_t)C * 7, dw));
+        GSV_RC(fetch_into(b, p + "dwconv.bias", C, db));
+        GSV_RC(fetch_into(b, p + "norm.weight", C, lg));
+        GSV_RC(fetch_into(b, p + "norm.bias", C, lb));
+        GSV_RC(fetch_into(b, p + "pwconv1.weight", (size_t)3 * C * C, w1));
+        GSV_RC(fetch_into(b, p + "pwconv1.bias", (size_t)3 * C, b1));
+        GSV_RC(fetch_into(b, p + "pwconv2.weight", (size_t)3 * C * C, w2));
+        GSV_RC(fetch_into(b, p + "pwconv2.bias", C, b2));
+        GSV_RC(fetch_into(b, p + "gamma", C, gm));
       }
     if (NL > 0) {
-      GSV_RC(up_f32(h, dw.data(), dw.size(), &b->dw_w));
-      GSV_RC(up_f32(h, db.data(), db.size(), &b->dw_b));
-      GSV_RC(up_f32(h, lg.data(), lg.size(), &b->ln_g));
-      GSV_RC(up_f32(h, lb.data(), lb.size(), &b->ln_b));
-      GSV_RC(up_t(h, w1, &b->pw1));
-      GSV_RC(up_f32(h, b1.data(), b1.size(), &b->pw1_b));
-      GSV_RC(up_t(h, w2, &b->pw2));
-      GSV_RC(up_f32(h, b2.data(), b2.size(), &b->pw2_b));
-      GSV_RC(up_f32(h, gm.data(), gm.size(), &b->gamma));
+      GSV_RC(up_f32(b, dw.data(), dw.size(), &b->dw_w));
+      GSV_RC(up_f32(b, db.data(), db.size(), &b->dw_b));
+      GSV_RC(up_f32(b, lg.data(), lg.size(), &b->ln_g));
+      GSV_RC(up_f32(b, lb.data(), lb.size(), &b->ln_b));
+      GSV_RC(up_t(b, w1, &b->pw1));
+      GSV_RC(up_f32(b, b1.data(), b1.size(), &b->pw1_b));
+      GSV_RC(up_t(b, w2, &b->pw2));
+      GSV_RC(up_f32(b, b2.data(), b2.size(), &b->pw2_b));
+      GSV_RC(up_f32(b, gm.data(), gm.size(), &b->gamma));
     }
   }
-  GSV_RC(make_conv(h, "linear_post_mag", B, C, 1, true, &b->post_mag));
-  GSV_RC(make_stacked(h, {"linear_post_pha_r", "linear_post_pha_i"}, B, C, &b->post_pha));
-  h->staged.clear();
+  GSV_RC(make_conv(b, "linear_post_mag", B, C, 1, true, &b->post_mag));
+  GSV_RC(make_stacked(b, {"linear_post_pha_r", "linear_post_pha_i"}, B, C, &b->post_pha));
+  b->staged.clear();
   b->finalized = true;
   return GSV_OK;
 }
@@ -546,7 +537,7 @@ int gsv_bwe_forward(gsv_bwe_t* b, const void* wav, int n, int dtype, int orig_sr
   GSV_RC(bwe_resample_tab(b, orig_sr, &rt));
   hipStream_t s = (hipStream_t)stream;
   const int nn = (int)n_new;
-  if (b->ctx.dtype == GSV_F16) {
+  if (b->dtype == GSV_F16) {
     if (dtype == GSV_F16) return bwe_forward_t<_Float16, _Float16>(b, s, (const _Float16*)wav, n, *rt, nn, out);
     return bwe_forward_t<_Float16, float>(b, s, (const float*)wav, n, *rt, nn, out);
   }

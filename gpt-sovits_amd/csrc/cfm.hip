@@ -318,10 +318,9 @@ struct TextBlockW { float *dw = nullptr, *db = nullptr, *ng = nullptr, *nb = nul
 //   out lora_B [D][rp] at 3 D + 4 inner; alpha / rank is folded into the lora_B matrices.  dev null = free slot.
 struct CfmAdapter { void* dev = nullptr; int rank = 0, rp = 0; };
 
-struct gsv_cfm {
-  gsv_vits ctx;
+struct gsv_cfm : gsveng::Ctx {
+  gsv_cfm() : Ctx("cfm") {}
   gsv_dit_config cfg;
-  bool finalized = false;
   int ldin = 0;
   Conv t0, t2, d0, d2, in_proj, pos1, pos2, final_mod, proj_out;
   std::vector<TextBlockW> text;
@@ -346,19 +345,18 @@ inline dim3 cfm_grid(long long n, int B = 1) { return dim3(nblk(n), B); }
 // time-independent precomputation for all n steps: mods[l][i][6D] (l < depth) and mods[depth][i][2D]
 template <typename T>
 int cfm_modulations(gsv_cfm* c, hipStream_t s, int N, float** mods_out) {
-  gsv_vits* h = &c->ctx;
   const auto& g = c->cfg;
   const int D = g.dim;
   const size_t es = sizeof(T);
   float *tvals, *sinus, *temb, *mods;
   void *sin_t, *mid_t, *stemb;
-  GSV_RC(need(h, "cfm_tvals", (size_t)2 * N * 4, (void**)&tvals));
-  GSV_RC(need(h, "cfm_sinus", (size_t)2 * N * 256 * 4, (void**)&sinus));
-  GSV_RC(need(h, "cfm_sin_t", (size_t)2 * N * 256 * es, &sin_t));
-  GSV_RC(need(h, "cfm_mid_t", (size_t)2 * N * D * es, &mid_t));
-  GSV_RC(need(h, "cfm_temb", (size_t)2 * N * D * 4, (void**)&temb));
-  GSV_RC(need(h, "cfm_stemb", (size_t)N * D * es, &stemb));
-  GSV_RC(need(h, "cfm_mods", ((size_t)g.depth * 6 + 2) * N * D * 4, (void**)&mods));
+  GSV_RC(need(c, "cfm_tvals", (size_t)2 * N * 4, (void**)&tvals));
+  GSV_RC(need(c, "cfm_sinus", (size_t)2 * N * 256 * 4, (void**)&sinus));
+  GSV_RC(need(c, "cfm_sin_t", (size_t)2 * N * 256 * es, &sin_t));
+  GSV_RC(need(c, "cfm_mid_t", (size_t)2 * N * D * es, &mid_t));
+  GSV_RC(need(c, "cfm_temb", (size_t)2 * N * D * 4, (void**)&temb));
+  GSV_RC(need(c, "cfm_stemb", (size_t)N * D * es, &stemb));
+  GSV_RC(need(c, "cfm_mods", ((size_t)g.depth * 6 + 2) * N * D * 4, (void**)&mods));
   {
     std::vector<float> tv(2 * N);
     double t = 0.0;
@@ -372,14 +370,14 @@ int cfm_modulations(gsv_cfm* c, hipStream_t s, int N, float** mods_out) {
   ConvOpt o1; o1.post_act = ACT_SILU;
   ConvOpt o2; o2.out_f32 = 1;
   // rows [0, N): time_embed(t_i); rows [N, 2N): d_embed(d)   (dit.py:149-153)
-  GSV_RC(conv(h, s, c->t0, sin_t, 256, N, mid_t, N, o1));
-  GSV_RC(conv(h, s, c->t2, mid_t, D, N, temb, N, o2));
-  GSV_RC(conv(h, s, c->d0, (const T*)sin_t + (size_t)N * 256, 256, N, (T*)mid_t + (size_t)N * D, N, o1));
-  GSV_RC(conv(h, s, c->d2, (const T*)mid_t + (size_t)N * D, D, N, temb + (size_t)N * D, N, o2));
+  GSV_RC(conv(c, s, c->t0, sin_t, 256, N, mid_t, N, o1));
+  GSV_RC(conv(c, s, c->t2, mid_t, D, N, temb, N, o2));
+  GSV_RC(conv(c, s, c->d0, (const T*)sin_t + (size_t)N * 256, 256, N, (T*)mid_t + (size_t)N * D, N, o1));
+  GSV_RC(conv(c, s, c->d2, (const T*)mid_t + (size_t)N * D, D, N, temb + (size_t)N * D, N, o2));
   GSV_LAUNCH(cfm_add_silu_kernel<T>, cfm_grid((long long)N * D), dim3(256), 0, s, temb, temb + (size_t)N * D, (long long)N * D, (T*)stemb);
   for (int l = 0; l < g.depth; ++l)
-    GSV_RC(conv(h, s, c->blocks[l].mod, stemb, D, N, mods + (size_t)l * N * 6 * D, N, o2));
-  GSV_RC(conv(h, s, c->final_mod, stemb, D, N, mods + (size_t)g.depth * N * 6 * D, N, o2));
+    GSV_RC(conv(c, s, c->blocks[l].mod, stemb, D, N, mods + (size_t)l * N * 6 * D, N, o2));
+  GSV_RC(conv(c, s, c->final_mod, stemb, D, N, mods + (size_t)g.depth * N * 6 * D, N, o2));
   *mods_out = mods;
   return GSV_OK;
 }
@@ -406,7 +404,6 @@ constexpr float CFM_CFG_THRESHOLD = 1e-5f;
 template <typename T>
 int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* mu, const std::vector<CfmRow>& host_rows, int Tn, int N,
                     const float* noise, float temperature, float cfg_rate, int max_rp, float* out) {
-  gsv_vits* h = &c->ctx;
   const auto& g = c->cfg;
   const int D = g.dim, td = g.text_dim, md = g.mel_dim, inner = g.heads * g.dim_head, FF = D * g.ff_mult, ldin = c->ldin;
   const int half = g.dim_head / 2;
@@ -423,7 +420,7 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
   }
   const std::vector<CfmRow>& table = guided ? with_twins : host_rows;
   CfmRow* rw;
-  GSV_RC(need(h, "cfm_rows", (size_t)DB * sizeof(CfmRow), (void**)&rw));
+  GSV_RC(need(c, "cfm_rows", (size_t)DB * sizeof(CfmRow), (void**)&rw));
   for (int b0 = 0; b0 < DB; b0 += CFM_ROW_CHUNK) {
     const int n = std::min(CFM_ROW_CHUNK, DB - b0);
     CfmRowChunk ch{};
@@ -432,35 +429,35 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
   }
   float *x, *v, *cs, *gx;
   void *xin, *ta, *tb, *tw, *hb, *c1, *nrm, *qkv, *ao, *ff;
-  GSV_RC(need(h, "cfm_x", (size_t)RX * md * 4, (void**)&x));
-  GSV_RC(need(h, "cfm_v", (size_t)R * md * 4, (void**)&v));
-  GSV_RC(need(h, "cfm_cs", (size_t)Tn * half * 2 * 4, (void**)&cs));
-  GSV_RC(need(h, "cfm_gx", (size_t)TB * 2 * td * 4, (void**)&gx));
-  GSV_RC(need(h, "cfm_xin", (size_t)R * ldin * es, &xin));
-  GSV_RC(need(h, "cfm_ta", (size_t)R * td * es, &ta));
-  GSV_RC(need(h, "cfm_tb", (size_t)R * td * es, &tb));
-  GSV_RC(need(h, "cfm_tw", (size_t)R * 2 * td * es, &tw));
-  GSV_RC(need(h, "cfm_h", (size_t)R * D * es, &hb));
-  GSV_RC(need(h, "cfm_c1", (size_t)R * D * es, &c1));
-  GSV_RC(need(h, "cfm_nrm", (size_t)R * D * es, &nrm));
-  GSV_RC(need(h, "cfm_qkv", (size_t)R * 3 * inner * es, &qkv));
-  GSV_RC(need(h, "cfm_ao", (size_t)R * inner * es, &ao));
-  GSV_RC(need(h, "cfm_ff", (size_t)R * FF * es, &ff));
+  GSV_RC(need(c, "cfm_x", (size_t)RX * md * 4, (void**)&x));
+  GSV_RC(need(c, "cfm_v", (size_t)R * md * 4, (void**)&v));
+  GSV_RC(need(c, "cfm_cs", (size_t)Tn * half * 2 * 4, (void**)&cs));
+  GSV_RC(need(c, "cfm_gx", (size_t)TB * 2 * td * 4, (void**)&gx));
+  GSV_RC(need(c, "cfm_xin", (size_t)R * ldin * es, &xin));
+  GSV_RC(need(c, "cfm_ta", (size_t)R * td * es, &ta));
+  GSV_RC(need(c, "cfm_tb", (size_t)R * td * es, &tb));
+  GSV_RC(need(c, "cfm_tw", (size_t)R * 2 * td * es, &tw));
+  GSV_RC(need(c, "cfm_h", (size_t)R * D * es, &hb));
+  GSV_RC(need(c, "cfm_c1", (size_t)R * D * es, &c1));
+  GSV_RC(need(c, "cfm_nrm", (size_t)R * D * es, &nrm));
+  GSV_RC(need(c, "cfm_qkv", (size_t)R * 3 * inner * es, &qkv));
+  GSV_RC(need(c, "cfm_ao", (size_t)R * inner * es, &ao));
+  GSV_RC(need(c, "cfm_ff", (size_t)R * FF * es, &ff));
   auto rows = [&](void* p, int b, int width) { return (void*)((char*)p + (size_t)b * Tn * width * es); };
 
   // ---- per-utterance constants: text embedding (dit.py:50-72), cond columns, rotary table
   GSV_LAUNCH(cfm_text_pos_kernel<T>, cfm_grid((long long)Tn * td, TB), dim3(256), 0, s, mu, B, c->pos_table, Tn, td, (T*)ta);
   for (auto& blk : c->text) {
     GSV_LAUNCH(cfm_dwconv7_kernel<T>, cfm_grid((long long)Tn * td, TB), dim3(256), 0, s, (const T*)ta, blk.dw, blk.db, Tn, td, (T*)tb);
-    GSV_RC(launch_layernorm(h->dtype, tb, 0, nullptr, 0, blk.ng, blk.nb, tb, 0, RT, td, 1e-6f, s));
+    GSV_RC(launch_layernorm(c->dtype, tb, 0, nullptr, 0, blk.ng, blk.nb, tb, 0, RT, td, 1e-6f, s));
     ConvOpt og; og.post_act = ACT_GELU;
-    GSV_RC(conv(h, s, blk.pw1, tb, td, RT, tw, RT, og));
+    GSV_RC(conv(c, s, blk.pw1, tb, td, RT, tw, RT, og));
     // GRN statistics are per utterance (norm over its own frames): gx [TB][2 td]
     GSV_LAUNCH(cfm_grn_norm_kernel<T>, dim3(cdiv(2 * td, 64), TB), dim3(256), 0, s, (const T*)tw, Tn, 2 * td, gx);
     GSV_LAUNCH(cfm_grn_apply_kernel<T>, dim3(std::min(1024, nblk((long long)Tn * 2 * td)), TB), dim3(256), 0, s, (T*)tw, gx, blk.gg, blk.gb,
                Tn, 2 * td);
     ConvOpt orr; orr.res = ta;
-    GSV_RC(conv(h, s, blk.pw2, tw, 2 * td, RT, ta, RT, orr));
+    GSV_RC(conv(c, s, blk.pw2, tw, 2 * td, RT, ta, RT, orr));
   }
   {
     const int W = md + (ldin - (2 * md + td));
@@ -485,7 +482,7 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
 
   const float d = (float)(1.0 / N);
   const float att_scale = 1.f / sqrtf((float)g.dim_head);
-  const bool flash = h->dtype == GSV_F16 && g.dim_head == 64 && !c->materialized_attn;
+  const bool flash = c->dtype == GSV_F16 && g.dim_head == 64 && !c->materialized_attn;
   // Infinity-Cache partition: the block weights (16.8 MB per block at the v3 shape, 370 MB in all) are re-read every Euler
   // step and do not fit the 256 MB cache, so a plain cyclic sweep keeps evicting what the next step needs first.  The
   // first `resident` blocks are loaded with the default policy (they stay), the rest non-temporal (they stream past).
@@ -494,14 +491,14 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
   const int resident = per_block ? (int)std::min<size_t>((size_t)g.depth, (size_t)resident_mb * 1024 * 1024 / per_block) : g.depth;
   void* vtb = nullptr;
   const long long vtz = (long long)g.heads * 64 * ((Tn + 31) / 32 * 32);   // one V^T buffer per utterance
-  if (flash) GSV_RC(need(h, "cfm_vt", (size_t)DB * vtz * 2, &vtb));
+  if (flash) GSV_RC(need(c, "cfm_vt", (size_t)DB * vtz * 2, &vtb));
   const int* row_slot = (const int*)((const char*)rw + offsetof(CfmRow, slot));   // device: row b's slot, every slot_ld ints
   const int slot_ld = (int)(sizeof(CfmRow) / sizeof(int));
   const long long lora_blk = 4ll * (D + inner);   // an adapter's elements per DiT block, in units of rp (CfmAdapter)
   for (int step = 0; step < N; ++step) {
     // ---- InputEmbedding (dit.py:75-84): proj(cat(x, cond, text)) then + ConvPositionEmbedding
     ConvOpt o;
-    GSV_RC(conv(h, s, c->in_proj, xin, ldin, R, hb, R, o));
+    GSV_RC(conv(c, s, c->in_proj, xin, ldin, R, hb, R, o));
     for (int b = 0; b < DB; ++b) {
       ConvArgs a;
       const int cg = D / 16;
@@ -509,9 +506,9 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
       a.T_in = Tn; a.T_out = Tn; a.T_virt = Tn; a.Cin = cg; a.Cout = cg; a.taps = 31; a.pad = 15;
       a.ldx = D; a.ldw = 31 * cg; a.ldy = D; a.ldr = D; a.post_act = ACT_MISH;
       a.Z = 16; a.xz = cg; a.wz = (long long)cg * 31 * cg; a.yz = cg; a.bz = cg;
-      GSV_RC(launch_conv_gemm(h->dtype, a, s));
+      GSV_RC(launch_conv_gemm(c->dtype, a, s));
       a.x = rows(c1, b, D); a.w = c->pos2.w; a.bias = c->pos2.b; a.y = rows(hb, b, D); a.accumulate = 1;   // h += mish(conv2(.))
-      GSV_RC(launch_conv_gemm(h->dtype, a, s));
+      GSV_RC(launch_conv_gemm(c->dtype, a, s));
     }
     // ---- DiT blocks (modules.py:550-594)
     for (int l = 0; l < g.depth; ++l) {
@@ -520,9 +517,9 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
       GSV_RC(launch_ln_mod<T>(hb, m + D, m, R, D, nrm, s));
       const int wnt = l >= resident ? 1 : 0;
       ConvOpt oq; oq.w_nt = wnt;   // rotary + V^T as this GEMM's epilogue was tried: no gain over the V^T launch
-      GSV_RC(conv(h, s, blk.qkv, nrm, D, R, qkv, R, oq));
+      GSV_RC(conv(c, s, blk.qkv, nrm, D, R, qkv, R, oq));
       if (max_rp)
-        GSV_RC(launch_lora_delta(h->dtype, nrm, qkv, Tn, DB, D, 3 * inner, 3, row_slot, slot_ld, c->lora_tab, max_rp, l * lora_blk,
+        GSV_RC(launch_lora_delta(c->dtype, nrm, qkv, Tn, DB, D, 3 * inner, 3, row_slot, slot_ld, c->lora_tab, max_rp, l * lora_blk,
                                  l * lora_blk + 3 * D, nullptr, s));
       if (flash) {   // every utterance in the same two launches (V^T + rotary, attention): the row is a grid dimension
         const _Float16* qb = (const _Float16*)qkv;
@@ -532,26 +529,26 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
         GSV_LAUNCH(cfm_rope_kernel<T>, cfm_grid(R * half * 2), dim3(256), 0, s, (T*)qkv, 3 * inner, inner, R, Tn, half, cs);
         for (int b = 0; b < DB; ++b) {
           const T* qb = (const T*)rows(qkv, b, 3 * inner);
-          GSV_RC(attention(h, s, qb, 3 * inner, 0, qb, 3 * inner, inner, 2 * inner, Tn, Tn, g.heads, g.dim_head, att_scale, nullptr,
+          GSV_RC(attention(c, s, qb, 3 * inner, 0, qb, 3 * inner, inner, 2 * inner, Tn, Tn, g.heads, g.dim_head, att_scale, nullptr,
                            nullptr, rows(ao, b, inner), inner));
         }
       }
       ConvOpt og; og.gate = m + 2 * D; og.res = hb; og.w_nt = wnt;
-      GSV_RC(conv(h, s, blk.out, ao, inner, R, hb, R, og));
+      GSV_RC(conv(c, s, blk.out, ao, inner, R, hb, R, og));
       if (max_rp)
-        GSV_RC(launch_lora_delta(h->dtype, ao, hb, Tn, DB, inner, D, 1, row_slot, slot_ld, c->lora_tab, max_rp,
+        GSV_RC(launch_lora_delta(c->dtype, ao, hb, Tn, DB, inner, D, 1, row_slot, slot_ld, c->lora_tab, max_rp,
                                  l * lora_blk + 3 * D + 3 * inner, l * lora_blk + 3 * D + 4 * inner, m + 2 * D, s));
       GSV_RC(launch_ln_mod<T>(hb, m + 4 * D, m + 3 * D, R, D, nrm, s));
       ConvOpt of; of.post_act = ACT_GELU_TANH; of.w_nt = wnt;
-      GSV_RC(conv(h, s, blk.ff1, nrm, D, R, ff, R, of));
+      GSV_RC(conv(c, s, blk.ff1, nrm, D, R, ff, R, of));
       ConvOpt o2; o2.gate = m + 5 * D; o2.res = hb; o2.w_nt = wnt;
-      GSV_RC(conv(h, s, blk.ff2, ff, FF, R, hb, R, o2));
+      GSV_RC(conv(c, s, blk.ff2, ff, FF, R, hb, R, o2));
     }
     // ---- AdaLayerNormZero_Final (scale, shift) + proj_out, then the Euler step (models.py:1080-1084)
     const float* mf = mods + (size_t)g.depth * N * 6 * D + (size_t)step * 2 * D;
     GSV_RC(launch_ln_mod<T>(hb, mf, mf + D, R, D, nrm, s));
     ConvOpt ov; ov.out_f32 = 1;
-    GSV_RC(conv(h, s, c->proj_out, nrm, D, R, v, R, ov));
+    GSV_RC(conv(c, s, c->proj_out, nrm, D, R, v, R, ov));
     GSV_RC(euler(v, d));
   }
   GSV_LAUNCH(cfm_out_kernel, cfm_grid((long long)Tn * md, B), dim3(256), 0, s, x, rw, Tn, md, out);
@@ -591,7 +588,7 @@ int cfm_entry(gsv_cfm* c, const char* who, const float* mu, const float* const* 
     }
     rows[b] = CfmRow{Tp[b] ? prompts[b] : nullptr, seeds ? (unsigned long long)seeds[b] : 0ull, Tp[b], slot};
   }
-  return GSV_WITH_T(&c->ctx, cfm_run<T>(c, (hipStream_t)stream, mu, rows, Tn, n_steps, noise, temperature, cfg_rate, max_rp, out));
+  return GSV_WITH_T(c, cfm_run<T>(c, (hipStream_t)stream, mu, rows, Tn, n_steps, noise, temperature, cfg_rate, max_rp, out));
 }
 
 }  // namespace
@@ -606,11 +603,10 @@ int gsv_cfm_create(const gsv_dit_config* cfg, int dtype, gsv_cfm_t** out) {
               "cfm_create: dim=%d must be 128, 256, 512, 1024 or 2048 (row-in-registers LayerNorm)", cfg->dim);
   GSV_REQUIRE(cfg->dim_head % 16 == 0 && cfg->heads > 0 && cfg->depth > 0, "cfm_create: bad head configuration");
   GSV_REQUIRE(cfg->text_dim % 8 == 0 && cfg->mel_dim % 4 == 0 && cfg->ff_mult > 0 && cfg->conv_layers >= 0, "cfm_create: bad dims");
-  int n = 0;
-  GSV_HIP(hipGetDeviceCount(&n));
+  GSV_RC(require_device());
   gsv_cfm* c = new gsv_cfm();
   c->cfg = *cfg;
-  c->ctx.dtype = dtype;
+  c->dtype = dtype;
   const char* e = getenv("GSV_CFM_MATERIALIZED_ATTN");
   c->materialized_attn = e && e[0] == '1';
   *out = c;
@@ -621,56 +617,52 @@ void gsv_cfm_destroy(gsv_cfm_t* c) {
   if (!c) return;
   for (auto& a : c->adapters) if (a.dev) (void)hipFree(a.dev);
   if (c->lora_tab) (void)hipFree(c->lora_tab);
-  free_ctx(&c->ctx);
+  free_ctx(c);
   delete c;
 }
 
 int gsv_cfm_load_tensor(gsv_cfm_t* c, const char* name, const float* data, int64_t numel) {
-  GSV_REQUIRE(c && name && data && numel > 0, "cfm_load_tensor: bad argument");
-  GSV_REQUIRE(!c->finalized, "cfm_load_tensor: handle already finalized");
-  c->ctx.staged[name].assign(data, data + numel);
-  return GSV_OK;
+  return stage_tensor(c, name, data, numel);
 }
 
 int gsv_cfm_finalize(gsv_cfm_t* c) {
   GSV_REQUIRE(c && !c->finalized, "cfm_finalize: bad handle");
-  gsv_vits* h = &c->ctx;
   const auto& g = c->cfg;
   const int D = g.dim, td = g.text_dim, md = g.mel_dim, inner = g.heads * g.dim_head;
-  GSV_RC(make_conv(h, "time_embed.time_mlp.0", D, 256, 1, true, &c->t0));
-  GSV_RC(make_conv(h, "time_embed.time_mlp.2", D, D, 1, true, &c->t2));
-  GSV_RC(make_conv(h, "d_embed.time_mlp.0", D, 256, 1, true, &c->d0));
-  GSV_RC(make_conv(h, "d_embed.time_mlp.2", D, D, 1, true, &c->d2));
+  GSV_RC(make_conv(c, "time_embed.time_mlp.0", D, 256, 1, true, &c->t0));
+  GSV_RC(make_conv(c, "time_embed.time_mlp.2", D, D, 1, true, &c->t2));
+  GSV_RC(make_conv(c, "d_embed.time_mlp.0", D, 256, 1, true, &c->d0));
+  GSV_RC(make_conv(c, "d_embed.time_mlp.2", D, D, 1, true, &c->d2));
   c->text.resize(g.conv_layers);
   for (int i = 0; i < g.conv_layers; ++i) {
     const std::string p = "text_embed.text_blocks." + std::to_string(i) + ".";
     TextBlockW& b = c->text[i];
-    GSV_RC(make_vec(h, p + "dwconv.weight", (size_t)td * 7, &b.dw));
-    GSV_RC(make_vec(h, p + "dwconv.bias", td, &b.db));
-    GSV_RC(make_vec(h, p + "norm.weight", td, &b.ng));
-    GSV_RC(make_vec(h, p + "norm.bias", td, &b.nb));
-    GSV_RC(make_conv(h, p + "pwconv1", 2 * td, td, 1, true, &b.pw1));
-    GSV_RC(make_vec(h, p + "grn.gamma", (size_t)2 * td, &b.gg));
-    GSV_RC(make_vec(h, p + "grn.beta", (size_t)2 * td, &b.gb));
-    GSV_RC(make_conv(h, p + "pwconv2", td, 2 * td, 1, true, &b.pw2));
+    GSV_RC(make_vec(c, p + "dwconv.weight", (size_t)td * 7, &b.dw));
+    GSV_RC(make_vec(c, p + "dwconv.bias", td, &b.db));
+    GSV_RC(make_vec(c, p + "norm.weight", td, &b.ng));
+    GSV_RC(make_vec(c, p + "norm.bias", td, &b.nb));
+    GSV_RC(make_conv(c, p + "pwconv1", 2 * td, td, 1, true, &b.pw1));
+    GSV_RC(make_vec(c, p + "grn.gamma", (size_t)2 * td, &b.gg));
+    GSV_RC(make_vec(c, p + "grn.beta", (size_t)2 * td, &b.gb));
+    GSV_RC(make_conv(c, p + "pwconv2", td, 2 * td, 1, true, &b.pw2));
   }
   const int cin = 2 * md + td;
   c->ldin = (cin + 31) / 32 * 32;
-  GSV_RC(make_conv_padded(h, "input_embed.proj", D, cin, c->ldin, 1, true, &c->in_proj));
-  GSV_RC(make_conv(h, "input_embed.conv_pos_embed.conv1d.0", D, D / 16, 31, true, &c->pos1));
-  GSV_RC(make_conv(h, "input_embed.conv_pos_embed.conv1d.2", D, D / 16, 31, true, &c->pos2));
+  GSV_RC(make_conv_padded(c, "input_embed.proj", D, cin, c->ldin, 1, true, &c->in_proj));
+  GSV_RC(make_conv(c, "input_embed.conv_pos_embed.conv1d.0", D, D / 16, 31, true, &c->pos1));
+  GSV_RC(make_conv(c, "input_embed.conv_pos_embed.conv1d.2", D, D / 16, 31, true, &c->pos2));
   c->blocks.resize(g.depth);
   for (int i = 0; i < g.depth; ++i) {
     const std::string p = "transformer_blocks." + std::to_string(i) + ".";
     DitBlockW& b = c->blocks[i];
-    GSV_RC(make_conv(h, p + "attn_norm.linear", 6 * D, D, 1, true, &b.mod));
-    GSV_RC(make_stacked(h, {p + "attn.to_q", p + "attn.to_k", p + "attn.to_v"}, inner, D, &b.qkv));
-    GSV_RC(make_conv(h, p + "attn.to_out.0", D, inner, 1, true, &b.out));
-    GSV_RC(make_conv(h, p + "ff.ff.0.0", D * g.ff_mult, D, 1, true, &b.ff1));
-    GSV_RC(make_conv(h, p + "ff.ff.2", D, D * g.ff_mult, 1, true, &b.ff2));
+    GSV_RC(make_conv(c, p + "attn_norm.linear", 6 * D, D, 1, true, &b.mod));
+    GSV_RC(make_stacked(c, {p + "attn.to_q", p + "attn.to_k", p + "attn.to_v"}, inner, D, &b.qkv));
+    GSV_RC(make_conv(c, p + "attn.to_out.0", D, inner, 1, true, &b.out));
+    GSV_RC(make_conv(c, p + "ff.ff.0.0", D * g.ff_mult, D, 1, true, &b.ff1));
+    GSV_RC(make_conv(c, p + "ff.ff.2", D, D * g.ff_mult, 1, true, &b.ff2));
   }
-  GSV_RC(make_conv(h, "norm_out.linear", 2 * D, D, 1, true, &c->final_mod));
-  GSV_RC(make_conv(h, "proj_out", md, D, 1, true, &c->proj_out));
+  GSV_RC(make_conv(c, "norm_out.linear", 2 * D, D, 1, true, &c->final_mod));
+  GSV_RC(make_conv(c, "proj_out", md, D, 1, true, &c->proj_out));
   // precompute_freqs_cis(text_dim, 4096) (modules.py:127-137): [pos][cos(pos f_j) | sin(pos f_j)]
   {
     std::vector<float> tab((size_t)4096 * td);
@@ -683,9 +675,9 @@ int gsv_cfm_finalize(gsv_cfm_t* c) {
         tab[(size_t)p * td + j] = cosf(a);
         tab[(size_t)p * td + half + j] = sinf(a);
       }
-    GSV_RC(up_f32(h, tab.data(), tab.size(), &c->pos_table));
+    GSV_RC(up_f32(c, tab.data(), tab.size(), &c->pos_table));
   }
-  h->staged.clear();
+  c->staged.clear();
   c->finalized = true;
   return GSV_OK;
 }
@@ -787,11 +779,11 @@ int gsv_cfm_adapter_finalize(gsv_cfm_t* c, int* slot_out) {
     GSV_RC(put(p + "to_out.0.lora_A", false, inner, blk + (size_t)(3 * D + 3 * inner) * rp));
     GSV_RC(put(p + "to_out.0.lora_B", true, D, blk + (size_t)(3 * D + 4 * inner) * rp));
   }
-  const size_t es = dt_size(c->ctx.dtype);
+  const size_t es = dt_size(c->dtype);
   void* dev = nullptr;
   GSV_HIP(hipMalloc(&dev, total * es));
   hipError_t e;
-  if (c->ctx.dtype == GSV_F32) e = hipMemcpy(dev, host.data(), total * 4, hipMemcpyHostToDevice);
+  if (c->dtype == GSV_F32) e = hipMemcpy(dev, host.data(), total * 4, hipMemcpyHostToDevice);
   else {
     std::vector<_Float16> tmp(total);
     for (size_t i = 0; i < total; ++i) tmp[i] = (_Float16)host[i];

@@ -1,6 +1,7 @@
-// Engine context shared by the SoVITS decoder (vits.hip), the generator and vocoders (generator.hip), the flow-matching DiT
-// (cfm.hip) and the AP-BWE super-sampler (bwe.hip): weight staging / upload, workspace arena, and the conv / attention /
-// generator launch helpers.
+// What the five engines stand on: the context every handle derives from (gsveng::Ctx: dtype, staged tensors, device
+// allocations, workspace arena) with its staging / upload / workspace / conv / attention helpers (engine.hip), and the generator
+// shared by the SoVITS decoder and the vocoders (generator.hip).  gsv_vits (vits.hip), gsv_vocoder (generator.hip), gsv_cfm
+// (cfm.hip), gsv_bwe (bwe.hip) and gsv_t2s (t2s_engine.h) are each a Ctx plus what their own model owns.
 #pragma once
 #include <math.h>
 #include <map>
@@ -16,11 +17,6 @@ struct Conv {
   int ups_u = 0, ups_pad = 0, ups_cout = 0;
 };
 
-struct AttnLayerW { Conv qkv, o; float *rel_k = nullptr, *rel_v = nullptr; float *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr; Conv f1, f2; };
-// modules.WN: per layer in_layers (kernel 5) and res_skip_layers (1x1); in_bias_eff = in_layers bias + cond_layer(ge) (fp32 [2H])
-struct WNW { std::vector<Conv> in, res; std::vector<float*> in_bias_eff; Conv cond; };
-struct FlowW { Conv pre, post; WNW wn; };
-
 // HiFi-GAN / BigVGAN upsampling stages (everything between conv_pre and conv_post) with the shape they need
 struct VocAct { float *alpha = nullptr, *beta = nullptr; };
 struct GenW {
@@ -34,53 +30,6 @@ struct GenW {
 };
 
 struct Buf { void* p = nullptr; size_t cap = 0; };
-
-struct gsv_vits {
-  gsv_vits_config cfg;
-  int dtype;
-  bool finalized = false, has_ref = false;
-  std::map<std::string, std::vector<float>> staged;
-  std::vector<void*> allocs;
-  // weights
-  Conv ssl_proj_enc, proj, c_pre, text_pre, c_post, mq, mkv, mo;
-  std::vector<AttnLayerW> enc_ssl, enc_text, enc2;
-  float *text_emb = nullptr, *codebook = nullptr, *code_ee = nullptr;
-  Conv top_ssl_proj;
-  void* codebook_t = nullptr;
-  FlowW flows[4];
-  Conv conv_pre, conv_post, cond;
-  float* conv_pre_bias_eff = nullptr;
-  GenW gen;
-  // v3 / v4: bridge + wns1 (Encoder with an 8-layer WN)
-  Conv bridge, w1_pre, w1_proj;
-  WNW w1;
-  // v2Pro: speaker-verification conditioning
-  Conv sv_emb, ge_to512;
-  float *prelu_w = nullptr, *ge_ref = nullptr, *sv_proj = nullptr, *ge512 = nullptr;
-  void* sv_t = nullptr;
-  // ref_enc
-  Conv r_sp0, r_sp3, r_t0, r_t1, r_qkv, r_fc, r_out;
-  float* ge = nullptr;         // fp32 [gin]
-  void* ge_t = nullptr;        // T [gin]
-  float* mo_bias_eff = nullptr;
-  // voice slots of the segmented decode (gsv_vits_store_voice): [GSV_VITS_MAX_VOICES][voice_len] fp32, one row per slot holding
-  // mo_bias_eff | conv_pre_bias_eff | the 16 WN in_bias_eff vectors (offsets voice_off_*)
-  float* voices = nullptr;
-  int voice_len = 0, voice_off_pre = 0, voice_off_in = 0;
-  std::vector<char> voice_ok;
-  std::vector<int> seg_host;                    // host image of the last segmented decode's maps (alive until its copy is done:
-  std::vector<unsigned long long> seed_host;    // seg_ev, recorded after the upload)
-  hipEvent_t seg_ev = nullptr;
-  hipStream_t ref_stream = nullptr;             // stream of the last set_refer (store_voice copies on it, then records ev[3])
-  const void* dbg_last_in = nullptr;            // input of the last generator stage (intact after a decode) for the debug hook
-  int dbg_last_T = 0, dbg_last_C = 0;
-  // workspace
-  std::map<std::string, Buf> bufs;
-  // last decode bookkeeping
-  int lastF = 0;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  float last_total_ms = 0.f, last_gen_ms = 0.f;
-};
 
 struct ConvOpt {
   int dil = 1, pad = -1, stride = 1;
@@ -98,26 +47,50 @@ struct ConvOpt {
 namespace gsveng {
 
 inline int nblk(long long n, int b = 256) { return (int)((n + b - 1) / b); }
-inline size_t esz(const gsv_vits* h) { return gsv::dt_size(h->dtype); }
 
-int dalloc(gsv_vits* h, void** p, size_t bytes);
-int up_f32(gsv_vits* h, const float* v, size_t n, float** out);
-int up_t(gsv_vits* h, const std::vector<float>& v, void** out);
+// The context of one engine handle.  The handles are opaque to C, so each handle struct derives from it and passes itself to the
+// helpers below.  `who` prefixes the messages about the handle's tensors ("vits", "vocoder", "cfm", "bwe", "t2s").
+struct Ctx {
+  explicit Ctx(const char* w) : who(w) {}
+  int dtype = GSV_F32;
+  bool finalized = false;
+  const char* who;
+  std::map<std::string, std::vector<float>> staged;   // load_tensor .. finalize: fp32 host copies by name
+  std::vector<void*> allocs;                          // device memory released at destroy (free_ctx)
+  std::map<std::string, Buf> bufs;                    // workspace arena by name (need)
+};
+
+inline size_t esz(const Ctx* h) { return gsv::dt_size(h->dtype); }
+
+// a usable HIP device exists: checked when a handle is created, not at its first upload
+int require_device();
+// gsv_*_load_tensor: stages a copy of data [numel] under `name` until finalize
+int stage_tensor(Ctx* h, const char* name, const float* data, int64_t numel);
+
+int dalloc(Ctx* h, void** p, size_t bytes);
+int up_f32(Ctx* h, const float* v, size_t n, float** out);
+int up_t(Ctx* h, const std::vector<float>& v, void** out);
 // staged tensor (or a folded weight_g / weight_v pair) as an fp32 host vector
-bool fetch(gsv_vits* h, const std::string& name, size_t n, int dim0, std::vector<float>& out);
-int make_conv(gsv_vits* h, const std::string& name, int cout, int cin, int k, bool bias, Conv* c);
-int make_conv_padded(gsv_vits* h, const std::string& name, int cout, int cin, int cin_pad, int k, bool bias, Conv* c);
-int make_stacked(gsv_vits* h, const std::vector<std::string>& names, int cout_each, int cin, Conv* c);
-int make_ups(gsv_vits* h, const std::string& name, int cin, int cout, int k, int u, Conv* c);
-int make_vec(gsv_vits* h, const std::string& name, size_t n, float** out);
-int need(gsv_vits* h, const char* name, size_t bytes, void** out);
-int conv(gsv_vits* h, hipStream_t s, const Conv& c, const void* x, int ldx, int T_in, void* y, int T_out, const ConvOpt& o);
-int attention(gsv_vits* h, hipStream_t s, const void* q, int ldq, int qcol0, const void* kv, int ldkv, int kcol0, int vcol0,
+bool fetch(Ctx* h, const std::string& name, size_t n, int dim0, std::vector<float>& out);
+// torch Conv1d weight [cout][cin][k] (+ bias) -> Conv; padded: the input channels zero-padded to cin_pad
+int make_conv_padded(Ctx* h, const std::string& name, int cout, int cin, int cin_pad, int k, bool bias, Conv* c);
+inline int make_conv(Ctx* h, const std::string& name, int cout, int cin, int k, bool bias, Conv* c) {
+  return make_conv_padded(h, name, cout, cin, cin, k, bias, c);
+}
+int make_stacked(Ctx* h, const std::vector<std::string>& names, int cout_each, int cin, Conv* c);
+int make_ups(Ctx* h, const std::string& name, int cin, int cout, int k, int u, Conv* c);
+// a staged tensor of n elements uploaded as it is: make_vec in fp32, make_mat in the engine dtype
+int make_vec(Ctx* h, const std::string& name, size_t n, float** out);
+int make_mat(Ctx* h, const std::string& name, size_t n, void** out);
+int need(Ctx* h, const char* name, size_t bytes, void** out);
+int conv(Ctx* h, hipStream_t s, const Conv& c, const void* x, int ldx, int T_in, void* y, int T_out, const ConvOpt& o);
+int attention(Ctx* h, hipStream_t s, const void* q, int ldq, int qcol0, const void* kv, int ldkv, int kcol0, int vcol0,
               int Tq, int Tk, int nh, int kc, float scale, const float* rel_k, const float* rel_v, void* out, int ldo,
               const int* kr = nullptr);   // kr: per-query key range [kr[2i], kr[2i+1]) (segmented decode)
-void free_ctx(gsv_vits* h);
+// releases allocs and bufs: the one place that does; a destroy function adds what its own handle owns
+void free_ctx(Ctx* h);
 // fp32 channels-first [C][Tn] -> engine dtype channels-last [Tn][ldd] (first C columns; ldd = 0: C)
-int cf_to_cl(gsv_vits* h, hipStream_t s, const float* src, int Tn, int C, void* dst, int ldd = 0);
+int cf_to_cl(Ctx* h, hipStream_t s, const float* src, int Tn, int C, void* dst, int ldd = 0);
 
 // generator.hip
 // copies the generator's shape out of either config struct (gsv_vits_config, gsv_vocoder_config: same field names)
@@ -128,20 +101,32 @@ void gen_shape(const Cfg& c, GenW* g) {
   for (int j = 0; j < 4; ++j) { g->rb_kernels[j] = c.rb_kernels[j]; for (int d = 0; d < 3; ++d) g->rb_dilations[j][d] = c.rb_dilations[j][d]; }
 }
 // ups / resblocks (BigVGAN: + activations and FIRs) named `prefix`ups.N, `prefix`resblocks.N; g's shape is already set
-int load_generator(gsv_vits* h, const std::string& prefix, bool bigvgan, GenW* g);
+int load_generator(Ctx* h, const std::string& prefix, bool bigvgan, GenW* g);
 // the 5 (BigVGAN: 6) ping-pong workspaces `name`0.. of a generator fed with F frames
-int gen_buffers(gsv_vits* h, const GenW& g, const char* name, int F, void** gb);
+int gen_buffers(Ctx* h, const GenW& g, const char* name, int F, void** gb);
 // the rows of one resolution of a segmented pass as BigVGAN's activation needs them (device pointers): row_seg [rows] int32,
 // -1 = gap row; segment s covers rows [start[s], start[s] + len[s])
 struct SegRows { const int* row_seg = nullptr; const int* start = nullptr; const int* len = nullptr; };
 // all upsampling stages on *cur = gb[3] ([*Tn][g.uic], the conv_pre output) -> *cur [*Tn][g.uic >> g.n_ups], one of gb[3], gb[4].
 // seg_up != null (segmented decode): per-stage row maps, gap rows of every stage output are 0; a BigVGAN generator also takes
 // seg_act[i] = the rows of stage i's output (row_seg = seg_up[i]) for its activations
-int run_generator_stages(gsv_vits* h, hipStream_t s, const GenW& g, void* const* gb, void** cur, int* Tn, int* const* seg_up = nullptr,
-                         const SegRows* seg_act = nullptr);
+// tap != null: the input of the last stage (intact after the pass), for a debug hook
+struct GenTap { const void* in = nullptr; int T = 0, C = 0; };
+int run_generator_stages(Ctx* h, hipStream_t s, const GenW& g, void* const* gb, void** cur, int* Tn, int* const* seg_up = nullptr,
+                         const SegRows* seg_act = nullptr, GenTap* tap = nullptr);
 
 // segmented passes (vits.hip: gsv_vits_decode_segments, generator.hip: gsv_vocoder_forward_segments): n sequences back to back on
 // one time axis with G zero "gap" rows between neighbours at the frame rate, G * prod(rates[:i]) after upsampling stage i
+// upload state of a segmented pass: the host image of its maps (and noise keys), which has to stay alive until its copy is done,
+// and the event recorded after the upload.  seg_upload_begin waits for the previous pass's upload (on any stream) before the
+// caller rewrites the image.
+struct SegUpload {
+  std::vector<int> maps;
+  std::vector<unsigned long long> seeds;
+  hipEvent_t ev = nullptr;
+  ~SegUpload() { if (ev) (void)hipEventDestroy(ev); }
+};
+int seg_upload_begin(SegUpload* u);
 // one-sided input reach of a conv with `taps` taps at dilation `dil` ("same" padding)
 inline int conv_reach(int taps, int dil) { return (taps - 1) / 2 * dil; }
 // the smallest G that covers, at every resolution, the reach of the generator's convs (conv_pre and conv_post included)

@@ -133,13 +133,13 @@ __global__ void pack_mel_seg_kernel(const float* __restrict__ src, int Fn, int C
 using namespace gsv;
 using namespace gsveng;
 
-struct gsv_vocoder {
-  gsv_vits ctx;               // the allocation / staging / workspace context of the engine helpers
+struct gsv_vocoder : gsveng::Ctx {
+  gsv_vocoder() : Ctx("vocoder") {}
   gsv_vocoder_config cfg;
   int cin_pad = 0;
   Conv conv_pre, conv_post;
   GenW gen;
-  bool finalized = false;
+  SegUpload seg;              // maps of the last segmented pass
 };
 
 namespace gsveng {
@@ -181,7 +181,7 @@ static int launch_aa_act(hipStream_t s, const void* x, void* y, int Tn, int C, c
 }
 
 template <typename T>
-static int voc_act(gsv_vits* h, hipStream_t s, const GenW& g, const VocAct& a, const void* x, void* y, int Tn, int C,
+static int voc_act(Ctx* h, hipStream_t s, const GenW& g, const VocAct& a, const void* x, void* y, int Tn, int C,
                    const SegRows* m = nullptr) {
   return launch_aa_act<T>(s, x, y, Tn, C, a.alpha, a.beta, g.snake_logscale, g.up12, g.dn12, m);
 }
@@ -207,7 +207,7 @@ int gen_gap(const GenW& c) {
   return g;
 }
 
-int load_generator(gsv_vits* h, const std::string& prefix, bool bigvgan, GenW* g) {
+int load_generator(Ctx* h, const std::string& prefix, bool bigvgan, GenW* g) {
   auto load_act = [&](const std::string& name, int C) -> int {
     VocAct a;
     GSV_RC(make_vec(h, name + ".alpha", C, &a.alpha));
@@ -247,7 +247,7 @@ int load_generator(gsv_vits* h, const std::string& prefix, bool bigvgan, GenW* g
   return GSV_OK;
 }
 
-int gen_buffers(gsv_vits* h, const GenW& g, const char* name, int F, void** gb) {
+int gen_buffers(Ctx* h, const GenW& g, const char* name, int F, void** gb) {
   size_t maxel = (size_t)F * g.uic;
   long long Tn = F;
   int ch = g.uic;
@@ -257,8 +257,8 @@ int gen_buffers(gsv_vits* h, const GenW& g, const char* name, int F, void** gb) 
   return GSV_OK;
 }
 
-int run_generator_stages(gsv_vits* h, hipStream_t s, const GenW& g, void* const* gb, void** cur_io, int* Tn_io, int* const* seg_up,
-                         const SegRows* seg_act) {
+int run_generator_stages(Ctx* h, hipStream_t s, const GenW& g, void* const* gb, void** cur_io, int* Tn_io, int* const* seg_up,
+                         const SegRows* seg_act, GenTap* tap) {
   const bool big = !g.acts.empty();
   void* cur = *cur_io;
   int Tn = *Tn_io, ch = g.uic, ai = 0;
@@ -269,7 +269,7 @@ int run_generator_stages(gsv_vits* h, hipStream_t s, const GenW& g, void* const*
     void* xup = gb[0]; void* xt = gb[1]; void* R = gb[2]; void* xa = big ? gb[5] : nullptr; void* xs = (cur == gb[3]) ? gb[4] : gb[3];
     const int* seg_o = seg_up ? seg_up[i] : nullptr;   // gap rows of this stage's outputs
     const SegRows* seg_a = seg_o && big ? &seg_act[i] : nullptr;   // BigVGAN: the same rows with each segment's first row and count
-    h->dbg_last_in = cur; h->dbg_last_T = Tn; h->dbg_last_C = 2 * ch;
+    if (tap) *tap = GenTap{cur, Tn, 2 * ch};
     { ConvOpt ou; ou.row_seg = seg_o;
       if (!big) { ou.pre_act = ACT_LRELU; ou.pre_slope = 0.1f; }
       GSV_RC(conv(h, s, g.ups[i], cur, ch * 2, Tn, xup, Tout, ou)); }
@@ -393,11 +393,10 @@ int gsv_vocoder_create(const gsv_vocoder_config* cfg, int dtype, gsv_vocoder_t**
   GSV_REQUIRE(cfg->n_ups >= 1 && cfg->n_ups <= 8 && cfg->n_resblocks >= 1 && cfg->n_resblocks <= 4, "vocoder_create: bad shape");
   GSV_REQUIRE(cfg->kind == 0 || cfg->kind == 1, "vocoder_create: kind must be 0 (HiFi-GAN) or 1 (BigVGAN)");
   GSV_REQUIRE((cfg->upsample_initial_channel >> cfg->n_ups) % 8 == 0, "vocoder_create: final channel count must be a multiple of 8");
-  int n = 0;
-  GSV_HIP(hipGetDeviceCount(&n));
+  GSV_RC(require_device());
   gsv_vocoder* v = new gsv_vocoder();
   v->cfg = *cfg;
-  v->ctx.dtype = dtype;
+  v->dtype = dtype;
   v->cin_pad = (cfg->in_channels + 7) / 8 * 8;
   *out = v;
   return GSV_OK;
@@ -405,29 +404,23 @@ int gsv_vocoder_create(const gsv_vocoder_config* cfg, int dtype, gsv_vocoder_t**
 
 void gsv_vocoder_destroy(gsv_vocoder_t* v) {
   if (!v) return;
-  free_ctx(&v->ctx);
-  if (v->ctx.seg_ev) (void)hipEventDestroy(v->ctx.seg_ev);
+  free_ctx(v);
   delete v;
 }
 
 int gsv_vocoder_load_tensor(gsv_vocoder_t* v, const char* name, const float* data, int64_t numel) {
-  GSV_REQUIRE(v && name && data && numel > 0, "vocoder_load_tensor: bad argument");
-  GSV_REQUIRE(!v->finalized, "vocoder_load_tensor: handle already finalized");
-  v->ctx.staged[name].assign(data, data + numel);
-  return GSV_OK;
+  return stage_tensor(v, name, data, numel);
 }
 
 int gsv_vocoder_finalize(gsv_vocoder_t* v) {
   GSV_REQUIRE(v && !v->finalized, "vocoder_finalize: bad handle");
-  gsv_vits* h = &v->ctx;
   const auto& c = v->cfg;
-  GSV_RC(make_conv_padded(h, "conv_pre", c.upsample_initial_channel, c.in_channels, v->cin_pad, 7, true, &v->conv_pre));
+  GSV_RC(make_conv_padded(v, "conv_pre", c.upsample_initial_channel, c.in_channels, v->cin_pad, 7, true, &v->conv_pre));
   gen_shape(c, &v->gen);
   v->gen.snake_logscale = c.snake_logscale;
-  GSV_RC(load_generator(h, "", c.kind == 1, &v->gen));
-  GSV_RC(make_conv(h, "conv_post", 1, c.upsample_initial_channel >> c.n_ups, 7, c.bias_at_final != 0, &v->conv_post));
-  h->staged.clear();
-  h->finalized = true;
+  GSV_RC(load_generator(v, "", c.kind == 1, &v->gen));
+  GSV_RC(make_conv(v, "conv_post", 1, c.upsample_initial_channel >> c.n_ups, 7, c.bias_at_final != 0, &v->conv_post));
+  v->staged.clear();
   v->finalized = true;
   return GSV_OK;
 }
@@ -436,27 +429,26 @@ int gsv_vocoder_forward(gsv_vocoder_t* v, const float* mel, int F, float* wav, g
   GSV_REQUIRE(v && v->finalized, "vocoder_forward: handle not finalized");
   GSV_REQUIRE(mel && wav && F >= 1, "vocoder_forward: empty input");
   hipStream_t s = (hipStream_t)stream;
-  gsv_vits* h = &v->ctx;
   const auto& c = v->cfg;
-  const size_t es = esz(h);
+  const size_t es = esz(v);
   const bool big = c.kind == 1;
   void* xin;
-  GSV_RC(need(h, "voc_in", (size_t)F * v->cin_pad * es, &xin));
+  GSV_RC(need(v, "voc_in", (size_t)F * v->cin_pad * es, &xin));
   GSV_HIP(hipMemsetAsync(xin, 0, (size_t)F * v->cin_pad * es, s));
-  GSV_RC(cf_to_cl(h, s, mel, F, c.in_channels, xin, v->cin_pad));
+  GSV_RC(cf_to_cl(v, s, mel, F, c.in_channels, xin, v->cin_pad));
   void* gb[6];
-  GSV_RC(gen_buffers(h, v->gen, "v", F, gb));
+  GSV_RC(gen_buffers(v, v->gen, "v", F, gb));
   void* cur = gb[3];
-  { ConvOpt o; GSV_RC(conv(h, s, v->conv_pre, xin, v->cin_pad, F, cur, F, o)); }
+  { ConvOpt o; GSV_RC(conv(v, s, v->conv_pre, xin, v->cin_pad, F, cur, F, o)); }
   int Tn = F;
   const int ch = c.upsample_initial_channel >> c.n_ups;
-  GSV_RC(run_generator_stages(h, s, v->gen, gb, &cur, &Tn));
+  GSV_RC(run_generator_stages(v, s, v->gen, gb, &cur, &Tn));
   ConvOpt op; op.out_f32 = 1;
   const void* pin = cur;
-  if (big) { GSV_RC(GSV_WITH_T(h, voc_act<T>(h, s, v->gen, v->gen.acts.back(), cur, gb[5], Tn, ch))); pin = gb[5]; }
+  if (big) { GSV_RC(GSV_WITH_T(v, voc_act<T>(v, s, v->gen, v->gen.acts.back(), cur, gb[5], Tn, ch))); pin = gb[5]; }
   else { op.pre_act = ACT_LRELU; op.pre_slope = 0.01f; }
   op.post_act = c.tanh_at_final ? ACT_TANH : ACT_CLAMP1;
-  GSV_RC(conv(h, s, v->conv_post, pin, ch, Tn, wav, Tn, op));
+  GSV_RC(conv(v, s, v->conv_post, pin, ch, Tn, wav, Tn, op));
   return GSV_OK;
 }
 
@@ -489,15 +481,13 @@ int gsv_vocoder_forward_segments(gsv_vocoder_t* v, const float* mel, int n, cons
   GSV_RC(voc_layout(v->cfg, n, frames, &lay));
   if (n == 1) return gsv_vocoder_forward(v, mel, frames[0], wav, stream);   // no gap, no maps: the plain path itself
   hipStream_t s = (hipStream_t)stream;
-  gsv_vits* h = &v->ctx;
   const auto& c = v->cfg;
-  const size_t es = esz(h);
+  const size_t es = esz(v);
   const bool big = c.kind == 1;
   const int F = (int)lay.F, nu = c.n_ups;
   // host image of the maps, one upload: seg_f [F] | per level 1 .. n_ups: first row [n] | rows [n]
-  if (!h->seg_ev) GSV_HIP(hipEventCreateWithFlags(&h->seg_ev, hipEventDisableTiming));
-  GSV_HIP(hipEventSynchronize(h->seg_ev));   // the previous call's upload (any stream) is done before its host image is rewritten
-  std::vector<int>& m = h->seg_host;
+  GSV_RC(seg_upload_begin(&v->seg));         // the previous call's upload (any stream) is done before its host image is rewritten
+  std::vector<int>& m = v->seg.maps;
   const size_t o_sl = (size_t)F, total = o_sl + 2 * (size_t)nu * n;
   m.assign(total, -1);
   for (int i = 0; i < n; ++i)
@@ -513,9 +503,9 @@ int gsv_vocoder_forward_segments(gsv_vocoder_t* v, const float* mel, int n, cons
     }
   }
   int* dm;
-  GSV_RC(need(h, "voc_seg_maps", total * 4, (void**)&dm));
+  GSV_RC(need(v, "voc_seg_maps", total * 4, (void**)&dm));
   GSV_HIP(hipMemcpyAsync(dm, m.data(), total * 4, hipMemcpyHostToDevice, s));
-  GSV_HIP(hipEventRecord(h->seg_ev, s));
+  GSV_HIP(hipEventRecord(v->seg.ev, s));
   const int* seg_f = dm;
   std::vector<int*> seg_up(nu);
   std::vector<SegRows> seg_act(nu);
@@ -523,7 +513,7 @@ int gsv_vocoder_forward_segments(gsv_vocoder_t* v, const float* mel, int n, cons
     long long up = 1;
     for (int l = 0; l < nu; ++l) {
       up *= c.up_rates[l];
-      GSV_RC(need(h, ("voc_seg_up" + std::to_string(l)).c_str(), (size_t)F * up * 4, (void**)&seg_up[l]));
+      GSV_RC(need(v, ("voc_seg_up" + std::to_string(l)).c_str(), (size_t)F * up * 4, (void**)&seg_up[l]));
       GSV_RC(launch_expand_seg(s, seg_f, (int)up, (long long)F * up, seg_up[l]));
       seg_act[l].row_seg = seg_up[l];
       seg_act[l].start = dm + o_sl + (size_t)(2 * l) * n;
@@ -531,23 +521,23 @@ int gsv_vocoder_forward_segments(gsv_vocoder_t* v, const float* mel, int n, cons
     }
   }
   void* xin;
-  GSV_RC(need(h, "voc_in", (size_t)F * v->cin_pad * es, &xin));
-  GSV_RC(GSV_WITH_T(h, pack_mel<T>(s, mel, (int)lay.Fn, c.in_channels, seg_f, lay.G, F, xin, v->cin_pad)));
+  GSV_RC(need(v, "voc_in", (size_t)F * v->cin_pad * es, &xin));
+  GSV_RC(GSV_WITH_T(v, pack_mel<T>(s, mel, (int)lay.Fn, c.in_channels, seg_f, lay.G, F, xin, v->cin_pad)));
   void* gb[6];
-  GSV_RC(gen_buffers(h, v->gen, "v", F, gb));
+  GSV_RC(gen_buffers(v, v->gen, "v", F, gb));
   void* cur = gb[3];
-  { ConvOpt o; o.row_seg = seg_f; GSV_RC(conv(h, s, v->conv_pre, xin, v->cin_pad, F, cur, F, o)); }
+  { ConvOpt o; o.row_seg = seg_f; GSV_RC(conv(v, s, v->conv_pre, xin, v->cin_pad, F, cur, F, o)); }
   int Tn = F;
   const int ch = c.upsample_initial_channel >> c.n_ups;
-  GSV_RC(run_generator_stages(h, s, v->gen, gb, &cur, &Tn, seg_up.data(), seg_act.data()));
+  GSV_RC(run_generator_stages(v, s, v->gen, gb, &cur, &Tn, seg_up.data(), seg_act.data()));
   ConvOpt op; op.out_f32 = 1;
   const void* pin = cur;
-  if (big) { GSV_RC(GSV_WITH_T(h, voc_act<T>(h, s, v->gen, v->gen.acts.back(), cur, gb[5], Tn, ch, &seg_act[nu - 1]))); pin = gb[5]; }
+  if (big) { GSV_RC(GSV_WITH_T(v, voc_act<T>(v, s, v->gen, v->gen.acts.back(), cur, gb[5], Tn, ch, &seg_act[nu - 1]))); pin = gb[5]; }
   else { op.pre_act = ACT_LRELU; op.pre_slope = 0.01f; }
   op.post_act = c.tanh_at_final ? ACT_TANH : ACT_CLAMP1;
   float* wpad;                         // the padded waveform, then the gaps are dropped into wav
-  GSV_RC(need(h, "voc_wav_pad", (size_t)Tn * 4, (void**)&wpad));
-  GSV_RC(conv(h, s, v->conv_post, pin, ch, Tn, wpad, Tn, op));
+  GSV_RC(need(v, "voc_wav_pad", (size_t)Tn * 4, (void**)&wpad));
+  GSV_RC(conv(v, s, v->conv_post, pin, ch, Tn, wpad, Tn, op));
   GSV_RC(launch_compact_wav(s, wpad, seg_f, (int)lay.up, lay.G * lay.up, (long long)Tn, wav));
   return GSV_OK;
 }

@@ -480,35 +480,9 @@ __global__ __launch_bounds__(64) void sample_only_kernel(const float* __restrict
 // engine
 // =======================================================================================
 using namespace gsv;
+using namespace gsveng;
 
 namespace {
-
-int upload_f32(gsv_t2s* h, const std::vector<float>& v, float** out) {
-  int rc = dev_alloc(h, (void**)out, v.size() * 4);
-  if (rc) return rc;
-  GSV_HIP(hipMemcpy(*out, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-  return GSV_OK;
-}
-
-int upload_t(gsv_t2s* h, const std::vector<float>& v, void** out) {
-  if (h->dtype == GSV_F32) return upload_f32(h, v, (float**)out);
-  std::vector<_Float16> tmp(v.size());
-  for (size_t i = 0; i < v.size(); ++i) tmp[i] = (_Float16)v[i];
-  int rc = dev_alloc(h, out, tmp.size() * 2);
-  if (rc) return rc;
-  GSV_HIP(hipMemcpy(*out, tmp.data(), tmp.size() * 2, hipMemcpyHostToDevice));
-  return GSV_OK;
-}
-
-const std::vector<float>* find(gsv_t2s* h, const std::string& k, size_t n) {
-  auto it = h->staged.find(k);
-  if (it == h->staged.end()) { set_error("t2s: missing tensor '%s'", k.c_str()); return nullptr; }
-  if (it->second.size() != n) {
-    set_error("t2s: tensor '%s' has %zu elements, expected %zu", k.c_str(), it->second.size(), n);
-    return nullptr;
-  }
-  return &it->second;
-}
 
 template <typename T, int CB, int NW, int KSL, int KV4>
 int launch_dec_gemm_inst(const DecGemmArgs& a, hipStream_t s) {
@@ -929,8 +903,7 @@ int gsv_t2s_create(const gsv_t2s_config* cfg, int dtype, int max_batch, int max_
   GSV_REQUIRE(cfg->dim / cfg->n_head == 32, "t2s_create: head_dim must be 32 (got %d)", cfg->dim / cfg->n_head);
   GSV_REQUIRE(cfg->vocab <= 2048, "t2s_create: vocab %d > 2048", cfg->vocab);
   GSV_REQUIRE(max_batch >= 1 && max_batch <= (dtype == GSV_F32 ? 64 : 128), "t2s_create: max_batch %d out of range", max_batch);
-  int n_dev = 0;
-  GSV_HIP(hipGetDeviceCount(&n_dev));   // no usable device: refused here, not at the first upload
+  GSV_RC(require_device());
   gsv_t2s* h = new gsv_t2s();
   h->cfg = *cfg;
   h->dtype = dtype;
@@ -944,7 +917,7 @@ int gsv_t2s_create(const gsv_t2s_config* cfg, int dtype, int max_batch, int max_
 void gsv_t2s_destroy(gsv_t2s_t* h) {
   if (!h) return;
   for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.second);
-  for (void* p : h->allocs) (void)hipFree(p);
+  free_ctx(h);
   if (h->h_pinned) (void)hipHostFree(h->h_pinned);
   if (h->mega.h_err) (void)hipHostFree(h->mega.h_err);
   for (auto& e : h->mega_ev) if (e) (void)hipEventDestroy(e);
@@ -952,57 +925,55 @@ void gsv_t2s_destroy(gsv_t2s_t* h) {
 }
 
 int gsv_t2s_load_tensor(gsv_t2s_t* h, const char* name, const float* data, int64_t numel) {
-  GSV_REQUIRE(h && name && data && numel > 0, "t2s_load_tensor: bad argument");
-  GSV_REQUIRE(!h->finalized, "t2s_load_tensor: handle already finalized");
-  std::string k(name);
-  if (k.rfind("model.", 0) == 0) k = k.substr(6);
-  h->staged[k].assign(data, data + numel);
-  return GSV_OK;
+  if (name && strncmp(name, "model.", 6) == 0) name += 6;
+  return stage_tensor(h, name, data, numel);
 }
 
 int gsv_t2s_finalize(gsv_t2s_t* h) {
   GSV_REQUIRE(h && !h->finalized, "t2s_finalize: bad handle");
   const auto& c = h->cfg;
   const size_t d = c.dim, ff = c.ffn_dim, V = c.vocab, PV = c.phoneme_vocab, BD = c.bert_dim;
-  const std::vector<float>* t;
-#define GSV_GET(key, n) if (!(t = find(h, key, n))) return GSV_ERR_ARG
-  GSV_GET("bert_proj.weight", d * BD); GSV_RC(upload_t(h, *t, &h->bert_w));
-  GSV_GET("bert_proj.bias", d); GSV_RC(upload_f32(h, *t, &h->bert_b));
-  GSV_GET("ar_text_embedding.word_embeddings.weight", PV * d); GSV_RC(upload_f32(h, *t, &h->e_text));
-  GSV_GET("ar_audio_embedding.word_embeddings.weight", V * d); GSV_RC(upload_f32(h, *t, &h->e_audio));
-  GSV_GET("ar_text_position.alpha", 1); h->alpha_t = (*t)[0];
-  GSV_GET("ar_audio_position.alpha", 1); h->alpha_a = (*t)[0];
+  GSV_RC(make_mat(h, "bert_proj.weight", d * BD, &h->bert_w));
+  GSV_RC(make_vec(h, "bert_proj.bias", d, &h->bert_b));
+  GSV_RC(make_vec(h, "ar_text_embedding.word_embeddings.weight", PV * d, &h->e_text));
+  GSV_RC(make_vec(h, "ar_audio_embedding.word_embeddings.weight", V * d, &h->e_audio));
+  {
+    std::vector<float> a;
+    if (!fetch(h, "ar_text_position.alpha", 1, 1, a)) return GSV_ERR_ARG;
+    h->alpha_t = a[0];
+    if (!fetch(h, "ar_audio_position.alpha", 1, 1, a)) return GSV_ERR_ARG;
+    h->alpha_a = a[0];
+  }
   {
     auto it = h->staged.find("pe");
     GSV_REQUIRE(it != h->staged.end() && it->second.size() % d == 0, "t2s: missing sinusoid table 'pe' [n_pos][dim]");
     h->pe_rows = (int)(it->second.size() / d);
     GSV_REQUIRE(h->max_seq <= h->pe_rows, "t2s: max_seq %d exceeds the position table (%d rows)", h->max_seq, h->pe_rows);
-    GSV_RC(upload_f32(h, it->second, &h->pe));
+    GSV_RC(up_f32(h, it->second.data(), it->second.size(), &h->pe));
   }
-  GSV_GET("ar_predict_layer.weight", V * d); GSV_RC(upload_t(h, *t, &h->pred_w));
+  GSV_RC(make_mat(h, "ar_predict_layer.weight", V * d, &h->pred_w));
   for (int i = 0; i < c.n_layer; ++i) {
     std::string p = "h.layers." + std::to_string(i) + ".";
     LayerW& L = h->layers[i];
-    GSV_GET(p + "self_attn.in_proj_weight", 3 * d * d); GSV_RC(upload_t(h, *t, &L.qkv_w));
-    GSV_GET(p + "self_attn.in_proj_bias", 3 * d); GSV_RC(upload_f32(h, *t, &L.qkv_b));
-    GSV_GET(p + "self_attn.out_proj.weight", d * d); GSV_RC(upload_t(h, *t, &L.out_w));
-    GSV_GET(p + "self_attn.out_proj.bias", d); GSV_RC(upload_f32(h, *t, &L.out_b));
-    GSV_GET(p + "linear1.weight", ff * d); GSV_RC(upload_t(h, *t, &L.w1));
-    GSV_GET(p + "linear1.bias", ff); GSV_RC(upload_f32(h, *t, &L.b1));
-    GSV_GET(p + "linear2.weight", d * ff); GSV_RC(upload_t(h, *t, &L.w2));
-    GSV_GET(p + "linear2.bias", d); GSV_RC(upload_f32(h, *t, &L.b2));
-    GSV_GET(p + "norm1.weight", d); GSV_RC(upload_f32(h, *t, &L.n1w));
-    GSV_GET(p + "norm1.bias", d); GSV_RC(upload_f32(h, *t, &L.n1b));
-    GSV_GET(p + "norm2.weight", d); GSV_RC(upload_f32(h, *t, &L.n2w));
-    GSV_GET(p + "norm2.bias", d); GSV_RC(upload_f32(h, *t, &L.n2b));
+    GSV_RC(make_mat(h, p + "self_attn.in_proj_weight", 3 * d * d, &L.qkv_w));
+    GSV_RC(make_vec(h, p + "self_attn.in_proj_bias", 3 * d, &L.qkv_b));
+    GSV_RC(make_mat(h, p + "self_attn.out_proj.weight", d * d, &L.out_w));
+    GSV_RC(make_vec(h, p + "self_attn.out_proj.bias", d, &L.out_b));
+    GSV_RC(make_mat(h, p + "linear1.weight", ff * d, &L.w1));
+    GSV_RC(make_vec(h, p + "linear1.bias", ff, &L.b1));
+    GSV_RC(make_mat(h, p + "linear2.weight", d * ff, &L.w2));
+    GSV_RC(make_vec(h, p + "linear2.bias", d, &L.b2));
+    GSV_RC(make_vec(h, p + "norm1.weight", d, &L.n1w));
+    GSV_RC(make_vec(h, p + "norm1.bias", d, &L.n1b));
+    GSV_RC(make_vec(h, p + "norm2.weight", d, &L.n2w));
+    GSV_RC(make_vec(h, p + "norm2.bias", d, &L.n2b));
   }
-#undef GSV_GET
   if (h->dtype == GSV_F16 && mega_shape_ok(c.dim, c.n_head, c.ffn_dim, c.vocab) && !getenv("GSV_T2S_NO_MEGA")) {
     // second copy of the decoder weights in the persistent engine's load order (every wave load = 1 KiB contiguous)
     MegaState& m = h->mega;
     const size_t lh = mega_layer_pack_halfs(), gh = mega_logits_pack_halfs();
-    GSV_RC(dev_alloc(h, &m.wpack, (size_t)c.n_layer * lh * 2));
-    GSV_RC(dev_alloc(h, &m.lpack, gh * 2));
+    GSV_RC(dalloc(h, &m.wpack, (size_t)c.n_layer * lh * 2));
+    GSV_RC(dalloc(h, &m.lpack, gh * 2));
     std::vector<_Float16> tmp(std::max(lh, gh));
     for (int i = 0; i < c.n_layer; ++i) {
       std::string p = "h.layers." + std::to_string(i) + ".";
@@ -1013,7 +984,7 @@ int gsv_t2s_finalize(gsv_t2s_t* h) {
     mega_pack_logits(h->staged["ar_predict_layer.weight"].data(), c.vocab, tmp.data());
     GSV_HIP(hipMemcpy(m.lpack, tmp.data(), gh * 2, hipMemcpyHostToDevice));
     // fp32 parameters of a layer side by side (no pointer chasing inside the kernel)
-    GSV_RC(dev_alloc(h, (void**)&m.fpack, (size_t)c.n_layer * MEGA_FP_LAYER * 4));
+    GSV_RC(dalloc(h, (void**)&m.fpack, (size_t)c.n_layer * MEGA_FP_LAYER * 4));
     for (int i = 0; i < c.n_layer; ++i) {
       const LayerW& L = h->layers[i];
       float* dst = m.fpack + (size_t)i * MEGA_FP_LAYER;
@@ -1026,9 +997,9 @@ int gsv_t2s_finalize(gsv_t2s_t* h) {
     }
     m.ring = 1;                                            // one hop buffer set (t2s_mega.hip hop_slot)
     m.hop_bytes = mega_hop_bytes(m.ring);
-    GSV_RC(dev_alloc(h, (void**)&m.hop, m.hop_bytes));
-    GSV_RC(dev_alloc(h, (void**)&m.err, 64));
-    GSV_RC(dev_alloc(h, (void**)&m.snap, ((size_t)4 * h->max_batch + 4) * 4));
+    GSV_RC(dalloc(h, (void**)&m.hop, m.hop_bytes));
+    GSV_RC(dalloc(h, (void**)&m.err, 64));
+    GSV_RC(dalloc(h, (void**)&m.snap, ((size_t)4 * h->max_batch + 4) * 4));
     GSV_HIP(hipHostMalloc((void**)&m.h_err, 64));
     GSV_HIP(hipEventCreate(&h->mega_ev[0]));
     GSV_HIP(hipEventCreate(&h->mega_ev[1]));
@@ -1037,27 +1008,27 @@ int gsv_t2s_finalize(gsv_t2s_t* h) {
   h->staged.clear();
   const size_t B = h->max_batch, es = esz(h);
   h->kv_layer_stride = B * d * (size_t)h->max_seq;
-  GSV_RC(dev_alloc(h, &h->kv, (size_t)c.n_layer * 2 * h->kv_layer_stride * es));
-  GSV_RC(dev_alloc(h, (void**)&h->d_x_len, B * 4));
-  GSV_RC(dev_alloc(h, (void**)&h->d_row_off, B * 4));
-  GSV_RC(dev_alloc(h, (void**)&h->d_ph_off, B * 4));
+  GSV_RC(dalloc(h, &h->kv, (size_t)c.n_layer * 2 * h->kv_layer_stride * es));
+  GSV_RC(dalloc(h, (void**)&h->d_x_len, B * 4));
+  GSV_RC(dalloc(h, (void**)&h->d_row_off, B * 4));
+  GSV_RC(dalloc(h, (void**)&h->d_ph_off, B * 4));
   // one block [kv_len | active | step | n_active]: the persistent engine's fallback saves and restores it with one copy
-  GSV_RC(dev_alloc(h, (void**)&h->d_kv_len, (3 * B + 4) * 4));
+  GSV_RC(dalloc(h, (void**)&h->d_kv_len, (3 * B + 4) * 4));
   h->d_active = h->d_kv_len + B; h->d_step = h->d_kv_len + 2 * B; h->d_n_active = h->d_kv_len + 3 * B;
   h->ycap = h->max_seq + 8;
-  GSV_RC(dev_alloc(h, (void**)&h->d_ytok, B * h->ycap * 4));
-  GSV_RC(dev_alloc(h, (void**)&h->d_plen, 2 * B * 4));
-  GSV_RC(dev_alloc(h, (void**)&h->d_rng_seed, B * 8));
-  GSV_RC(dev_alloc(h, (void**)&h->d_rng_row, B * 4));
-  GSV_RC(dev_alloc(h, (void**)&h->d_row_sampling, B * sizeof(RowSampling)));
-  GSV_RC(dev_alloc(h, (void**)&h->d_sp, sizeof(StepParams)));
+  GSV_RC(dalloc(h, (void**)&h->d_ytok, B * h->ycap * 4));
+  GSV_RC(dalloc(h, (void**)&h->d_plen, 2 * B * 4));
+  GSV_RC(dalloc(h, (void**)&h->d_rng_seed, B * 8));
+  GSV_RC(dalloc(h, (void**)&h->d_rng_row, B * 4));
+  GSV_RC(dalloc(h, (void**)&h->d_row_sampling, B * sizeof(RowSampling)));
+  GSV_RC(dalloc(h, (void**)&h->d_sp, sizeof(StepParams)));
   GSV_HIP(hipHostMalloc((void**)&h->h_pinned, 64));
-  GSV_RC(dev_alloc(h, (void**)&h->ybuf, B * d * 4));
-  GSV_RC(dev_alloc(h, (void**)&h->xres, B * d * 4));
-  GSV_RC(dev_alloc(h, (void**)&h->logits, B * V * 4));
-  GSV_RC(dev_alloc(h, &h->qbuf, B * d * es));
-  GSV_RC(dev_alloc(h, &h->abuf, B * d * es));
-  GSV_RC(dev_alloc(h, &h->hbuf, B * ff * es));
+  GSV_RC(dalloc(h, (void**)&h->ybuf, B * d * 4));
+  GSV_RC(dalloc(h, (void**)&h->xres, B * d * 4));
+  GSV_RC(dalloc(h, (void**)&h->logits, B * V * 4));
+  GSV_RC(dalloc(h, &h->qbuf, B * d * es));
+  GSV_RC(dalloc(h, &h->abuf, B * d * es));
+  GSV_RC(dalloc(h, &h->hbuf, B * ff * es));
   GSV_HIP(hipMemset(h->logits, 0, B * V * 4));
   h->finalized = true;
   return GSV_OK;

@@ -1,11 +1,7 @@
 // AR decoder engine state (the gsv_t2s handle) shared by t2s.hip (load / finalize, decode, debug and timing hooks) and
 // t2s_prefill.hip (prefill).
 #pragma once
-#include <map>
-#include <string>
-#include <vector>
-
-#include "common.h"
+#include "engine.h"
 #include "t2s_sample.h"
 #include "t2s_mega.h"
 
@@ -15,11 +11,10 @@ struct LayerW {
   float *n1w = nullptr, *n1b = nullptr, *n2w = nullptr, *n2b = nullptr;
 };
 
-struct gsv_t2s {
+struct gsv_t2s : gsveng::Ctx {
+  gsv_t2s() : Ctx("t2s") {}
   gsv_t2s_config cfg;
-  int dtype, max_batch, max_seq;
-  bool finalized = false;
-  std::map<std::string, std::vector<float>> staged;
+  int max_batch, max_seq;
   std::vector<LayerW> layers;
   void* bert_w = nullptr; float* bert_b = nullptr;
   float *e_text = nullptr, *e_audio = nullptr, *pe = nullptr;
@@ -61,17 +56,8 @@ struct gsv_t2s {
   bool mega_on = true;      // gsv_t2s_set_mega (A/B inside one process); GSV_T2S_NO_MEGA=1 never builds the engine
   const int* dbg_force = nullptr; float* dbg_dump = nullptr; int* dbg_drawn = nullptr; int dbg_stall = 0;   // gsv_t2s_set_debug / gsv_t2s_debug_stall: apply to the NEXT decode call only
   std::map<int, hipGraphExec_t> graphs;
-  std::vector<void*> allocs;
 };
 
-inline size_t esz(const gsv_t2s* h) { return gsv::dt_size(h->dtype); }
-
-inline int dev_alloc(gsv_t2s* h, void** p, size_t bytes) {
-  GSV_HIP(hipMalloc(p, bytes ? bytes : 16));
-  h->allocs.push_back(*p);
-  return GSV_OK;
-}
-
 inline void* kv_ptr(gsv_t2s* h, int layer, int which) {
-  return (char*)h->kv + ((size_t)(layer * 2 + which) * h->kv_layer_stride) * esz(h);
+  return (char*)h->kv + ((size_t)(layer * 2 + which) * h->kv_layer_stride) * gsveng::esz(h);
 }

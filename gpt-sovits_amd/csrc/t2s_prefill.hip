@@ -282,6 +282,7 @@ __global__ void prompt_copy_kernel(const int* __restrict__ prompts, const int* _
 }  // namespace gsv
 
 using namespace gsv;
+using namespace gsveng;
 
 namespace {
 
@@ -290,13 +291,13 @@ int grow_prefill(gsv_t2s* h, size_t rows) {
   const size_t d = h->cfg.dim, ff = h->cfg.ffn_dim, es = esz(h);
   rows = (rows + 255) & ~(size_t)255;
   // old buffers stay registered in allocs and are released at destroy; growth is rare
-  GSV_RC(dev_alloc(h, &h->pf_x, rows * d * es));
-  GSV_RC(dev_alloc(h, &h->pf_qkv, rows * 3 * d * es));
-  GSV_RC(dev_alloc(h, &h->pf_attn, rows * d * es));
-  GSV_RC(dev_alloc(h, &h->pf_h, rows * ff * es));
-  GSV_RC(dev_alloc(h, (void**)&h->pf_y, rows * d * 4));
-  GSV_RC(dev_alloc(h, (void**)&h->pf_bert, rows * d * 4));
-  GSV_RC(dev_alloc(h, &h->pf_bert_t, rows * (size_t)h->cfg.bert_dim * es));
+  GSV_RC(dalloc(h, &h->pf_x, rows * d * es));
+  GSV_RC(dalloc(h, &h->pf_qkv, rows * 3 * d * es));
+  GSV_RC(dalloc(h, &h->pf_attn, rows * d * es));
+  GSV_RC(dalloc(h, &h->pf_h, rows * ff * es));
+  GSV_RC(dalloc(h, (void**)&h->pf_y, rows * d * 4));
+  GSV_RC(dalloc(h, (void**)&h->pf_bert, rows * d * 4));
+  GSV_RC(dalloc(h, &h->pf_bert_t, rows * (size_t)h->cfg.bert_dim * es));
   h->pf_rows = rows;
   return GSV_OK;
 }
@@ -371,7 +372,7 @@ int t2s_prefill_rows(gsv_t2s* h, const int32_t* phones, const int32_t* phone_len
   GSV_RC(grow_prefill(h, M));
   if (h->dtype == GSV_F16) {
     const size_t need_vt = (size_t)B * H * 32 * ((maxS + 31) / 32 * 32) * 2;
-    if (need_vt > h->pf_vt_cap) { GSV_RC(dev_alloc(h, &h->pf_vt, need_vt + need_vt / 4)); h->pf_vt_cap = need_vt + need_vt / 4; }
+    if (need_vt > h->pf_vt_cap) { GSV_RC(dalloc(h, &h->pf_vt, need_vt + need_vt / 4)); h->pf_vt_cap = need_vt + need_vt / 4; }
   }
   h->B = B; h->P = maxP; h->max_kv0 = maxS;
   GSV_HIP(hipMemcpyAsync(h->d_x_len, phone_lens, B * 4, hipMemcpyHostToDevice, s));

@@ -91,13 +91,8 @@ class Text2SemanticDecoder:
             raise RuntimeError("weights already loaded; create a new Text2SemanticDecoder")
         l = _lib.lib()
         with torch.cuda.device(self.device):
-            for k, v in state_dict.items():
-                if not torch.is_tensor(v):
-                    continue
-                t = v.detach().to("cpu", torch.float32).contiguous()
-                _lib.check(l.gsv_t2s_load_tensor(self._h, k.encode(), t.data_ptr(), t.numel()), f"load {k}")
-            pe = _sine_pe(4000, self.embedding_dim).contiguous()
-            _lib.check(l.gsv_t2s_load_tensor(self._h, b"pe", pe.data_ptr(), pe.numel()), "load pe")
+            _lib.load_tensors(l.gsv_t2s_load_tensor, self._h, ((k, v) for k, v in state_dict.items() if torch.is_tensor(v)))
+            _lib.load_tensors(l.gsv_t2s_load_tensor, self._h, [("pe", _sine_pe(4000, self.embedding_dim))])
             _lib.check(l.gsv_t2s_finalize(self._h), "gsv_t2s_finalize")
         self._loaded = True
         return self

@@ -223,6 +223,14 @@ def check(rc: int, what: str = ""):
         raise RuntimeError(f"libgsv_hip {what} failed (rc={rc}): {msg}")
 
 
+def load_tensors(fn, handle, items):
+    """stages every (name, tensor) of `items` in an engine handle through its gsv_*_load_tensor `fn`, as fp32 host copies"""
+    import torch
+    for k, v in items:
+        t = v.detach().to("cpu", torch.float32).contiguous()
+        check(fn(handle, k.encode(), t.data_ptr(), t.numel()), f"load {k}")
+
+
 _inited = set()
 
 

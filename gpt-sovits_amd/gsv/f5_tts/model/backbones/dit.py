@@ -51,15 +51,18 @@ class DiT:
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
         """keys as in the reference DiT, with or without the `cfm.estimator.` / `estimator.` prefix of a SoVITS checkpoint"""
         l = _lib.lib()
-        with torch.cuda.device(self.device):
+
+        def items():
             for k, v in state_dict.items():
                 for pre in ("cfm.estimator.", "estimator."):
                     if k.startswith(pre):
                         k = k[len(pre):]
                 if not torch.is_tensor(v) or k.startswith("rotary_embed") or k.startswith("text_embed.freqs_cis"):
                     continue            # buffers the library rebuilds
-                t = v.detach().to("cpu", torch.float32).contiguous()
-                _lib.check(l.gsv_cfm_load_tensor(self._h, k.encode(), t.data_ptr(), t.numel()), f"load {k}")
+                yield k, v
+
+        with torch.cuda.device(self.device):
+            _lib.load_tensors(l.gsv_cfm_load_tensor, self._h, items())
             _lib.check(l.gsv_cfm_finalize(self._h), "gsv_cfm_finalize")
         self._loaded = True
         return self
@@ -82,9 +85,7 @@ class DiT:
         slot = C.c_int(-1)
         with torch.cuda.device(self.device):
             _lib.check(l.gsv_cfm_adapter_begin(self._h, rank, alpha), "gsv_cfm_adapter_begin")
-            for k, v in adapter.items():
-                t = v.detach().to("cpu", torch.float32).contiguous()
-                _lib.check(l.gsv_cfm_adapter_load_tensor(self._h, k.encode(), t.data_ptr(), t.numel()), f"load {k}")
+            _lib.load_tensors(l.gsv_cfm_adapter_load_tensor, self._h, adapter.items())
             _lib.check(l.gsv_cfm_adapter_finalize(self._h, C.byref(slot)), "gsv_cfm_adapter_finalize")
         self._adapters.add(slot.value)
         return slot.value

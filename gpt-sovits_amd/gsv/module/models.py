@@ -89,13 +89,9 @@ class SynthesizerTrn:
             raise RuntimeError("weights already loaded; create a new SynthesizerTrn")
         l = _lib.lib()
         with torch.cuda.device(self.device):
-            for k, v in state_dict.items():
-                if not torch.is_tensor(v) or k.startswith("enc_q."):
-                    continue
-                t = v.detach().to("cpu", torch.float32).contiguous()
-                if t.numel() == 0:
-                    continue
-                _lib.check(l.gsv_vits_load_tensor(self._h, k.encode(), t.data_ptr(), t.numel()), f"load {k}")
+            _lib.load_tensors(l.gsv_vits_load_tensor, self._h,
+                              ((k, v) for k, v in state_dict.items()
+                               if torch.is_tensor(v) and not k.startswith("enc_q.") and v.numel()))
             _lib.check(l.gsv_vits_finalize(self._h), "gsv_vits_finalize")
         self._loaded = True
         return self

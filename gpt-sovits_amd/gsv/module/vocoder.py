@@ -56,11 +56,9 @@ class _VocoderEngine:
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
         l = _lib.lib()
         with torch.cuda.device(self.device):
-            for k, v in state_dict.items():
-                if not torch.is_tensor(v) or "filter" in k or v.numel() == 0:
-                    continue            # Kaiser-sinc filters are constants rebuilt in the library
-                t = v.detach().to("cpu", torch.float32).contiguous()
-                _lib.check(l.gsv_vocoder_load_tensor(self._h, k.encode(), t.data_ptr(), t.numel()), f"load {k}")
+            # Kaiser-sinc filters are constants rebuilt in the library
+            _lib.load_tensors(l.gsv_vocoder_load_tensor, self._h,
+                              ((k, v) for k, v in state_dict.items() if torch.is_tensor(v) and "filter" not in k and v.numel()))
             _lib.check(l.gsv_vocoder_finalize(self._h), "gsv_vocoder_finalize")
         self._loaded = True
         return self

@@ -104,11 +104,7 @@ class AP_BWE:
             tensors = dict(self._sd)
             tensors["dft.forward"] = _dft_basis(c["n_fft"], c["win_size"], "cpu")
             tensors["dft.inverse"] = _dft_basis(c["n_fft"], c["win_size"], "cpu", inverse=True)
-            for k, v in tensors.items():
-                if not torch.is_tensor(v) or v.numel() == 0:
-                    continue
-                t = v.detach().to("cpu", torch.float32).contiguous()
-                _lib.check(l.gsv_bwe_load_tensor(h, k.encode(), t.data_ptr(), t.numel()), f"load {k}")
+            _lib.load_tensors(l.gsv_bwe_load_tensor, h, ((k, v) for k, v in tensors.items() if torch.is_tensor(v) and v.numel()))
             _lib.check(l.gsv_bwe_finalize(h), "gsv_bwe_finalize")
             self.stream = torch.cuda.Stream(device=device)
 

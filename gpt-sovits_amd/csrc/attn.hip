@@ -16,7 +16,7 @@
 // hold O^T[.][q]: no cross-lane traffic except two xor-shuffles per reduction.
 #include <stdlib.h>
 
-#include "common.h"
+#include "engine.h"
 
 // order fence for the software pipelines: the empty asm stops IR-level sinking / hoisting of the loads across it, the
 // sched_barrier stops the machine scheduler
@@ -69,25 +69,17 @@ __global__ __launch_bounds__(256) void vt_kernel(const _Float16* __restrict__ v,
 // QT = 16-query tiles per workgroup.  Every K / V^T fragment a wave loads feeds QT score tiles and QT output tiles:
 // fragment-shaped global loads cost ~120 clocks of the CU's texture-address path each (measured),
 // and with QT = 1 those loads, not MFMA or latency, set the kernel's time.
-// Several utterances in one launch: gridDim.y = rows * heads.  Row b's q / k start xz elements after row b-1's, its V^T vtz
-// and its output oz elements after.
+// The body both launch shapes share: q / k / out point at the first row of the sequence (a row of the batch, or a segment of a
+// packed pass), vt at the first V^T column of that sequence (head 0), T is the sequence's own length.
 template <int QT>
-__global__ __launch_bounds__(256) void flash_attn64_f16_kernel(const _Float16* __restrict__ q, int ldq, const _Float16* __restrict__ k,
-                                                               int ldk, const _Float16* __restrict__ vt, int ldv, int T, float scale,
-                                                               _Float16* __restrict__ out, int ldo, int heads, long long xz,
-                                                               long long vtz, long long oz) {
+__device__ __forceinline__ void flash_attn64_tile(const _Float16* __restrict__ q, int ldq, const _Float16* __restrict__ k, int ldk,
+                                                  const _Float16* __restrict__ vt, int ldv, int T, float scale,
+                                                  _Float16* __restrict__ out, int ldo, int head, int q0) {
   constexpr int LDO = 68, BQ = 16 * QT;
   extern __shared__ float smem[];
   float* Os = smem;                                  // [4][BQ][LDO]
   float* Ms = smem + 4 * BQ * LDO;                   // [4][BQ]
   float* Ls = Ms + 4 * BQ;                           // [4][BQ]
-  // (row, head) pairs are dealt to XCDs in contiguous runs (2 heads per XCD at 16 heads and one row, 2 * rows with more):
-  // all query tiles of a pair run on one XCD, so its K / V^T stay in one L2.  The pair is the slow index of the virtual id,
-  // so an XCD works through its pairs one after the other and holds only the few in flight (DESIGN.md section 4f).
-  const int vid = xcd_virtual_id(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
-  const int pair = vid / gridDim.x, q0 = (vid % gridDim.x) * BQ;
-  const int row = pair / heads, head = pair - row * heads;
-  q += row * xz; k += row * xz; vt += row * vtz; out += row * oz;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = lane & 15, g = lane >> 4;
   h8 qf0[QT], qf1[QT];
@@ -197,6 +189,22 @@ __global__ __launch_bounds__(256) void flash_attn64_f16_kernel(const _Float16* _
   }
 }
 
+// Several utterances in one launch: gridDim.y = rows * heads.  Row b's q / k start xz elements after row b-1's, its V^T vtz
+// and its output oz elements after.
+template <int QT>
+__global__ __launch_bounds__(256) void flash_attn64_f16_kernel(const _Float16* __restrict__ q, int ldq, const _Float16* __restrict__ k,
+                                                               int ldk, const _Float16* __restrict__ vt, int ldv, int T, float scale,
+                                                               _Float16* __restrict__ out, int ldo, int heads, long long xz,
+                                                               long long vtz, long long oz) {
+  // (row, head) pairs are dealt to XCDs in contiguous runs (2 heads per XCD at 16 heads and one row, 2 * rows with more):
+  // all query tiles of a pair run on one XCD, so its K / V^T stay in one L2.  The pair is the slow index of the virtual id,
+  // so an XCD works through its pairs one after the other and holds only the few in flight (DESIGN.md section 4f).
+  const int vid = xcd_virtual_id(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
+  const int pair = vid / gridDim.x, q0 = (vid % gridDim.x) * (16 * QT);
+  const int row = pair / heads, head = pair - row * heads;
+  flash_attn64_tile<QT>(q + row * xz, ldq, k + row * xz, ldk, vt + row * vtz, ldv, T, scale, out + row * oz, ldo, head, q0);
+}
+
 template <int QT>
 static int launch_flash_qt(const void* q, int ldq, const void* k, int ldk, const void* vt_buf, int ldv, int T, int heads, float scale,
                            void* out, int ldo, hipStream_t s, int rows, long long xz, long long vtz, long long oz) {
@@ -209,6 +217,71 @@ static int launch_flash_qt(const void* q, int ldq, const void* k, int ldk, const
   hipLaunchKernelGGL(flash_attn64_f16_kernel<QT>, dim3(cdiv(T, 16 * QT), rows * heads), dim3(256), lds, s, (const _Float16*)q, ldq,
                      (const _Float16*)k, ldk, (const _Float16*)vt_buf, ldv, T, scale, (_Float16*)out, ldo, heads, xz, vtz, oz);
   GSV_HIP(hipGetLastError());
+  return GSV_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// Segmented (variable-length) form: n_seg sequences back to back in one [sum T][ld] matrix (the packed BERT pass,
+// gsv/feature_extractor/bert.py), query i of segment s attends to the keys of segment s only.  The segment takes the place of
+// the row above: a query tile never spans two segments (tiles are counted per segment, so every segment ends in a partial
+// tile), and a workgroup finds its segment in the table by the tile prefix.  Table, one int4 per segment:
+//   x = first row of the segment in the packed matrix      y = its length T_s
+//   z = its first V^T column, 32 * sum_{s' < s} ceil(T_s' / 32): every segment starts on a 32-key boundary, so the aligned
+//       16-byte V^T loads of the tile body stay aligned and a chunk never reads another segment's columns
+//   w = query tiles of the segments before it
+// The last segment whose prefix is <= x (binary search; wave-uniform, so the loads are scalar).
+__device__ __forceinline__ int4 seg_find(const int4* __restrict__ tab, int n_seg, int x, bool by_tile) {
+  int lo = 0, hi = n_seg - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    const int4 e = tab[mid];
+    if ((by_tile ? e.w : e.z) <= x) lo = mid; else hi = mid - 1;
+  }
+  return tab[lo];
+}
+
+// Vt[head][d][z_s + j] = V[x_s + j][head * 64 + d] for j < T_s and 0 for T_s <= j < 32 * ceil(T_s / 32): the padding columns are
+// WRITTEN, the scratch buffer arrives uninitialised and a masked probability of 0 times a NaN left there is NaN.
+// grid: (ldv / 32 key chunks, 2 halves of the head's 64 channels, heads); a 32-column chunk lies in one segment.
+__global__ __launch_bounds__(256) void vt_seg_kernel(const _Float16* __restrict__ v, int ld, const int4* __restrict__ tab, int n_seg,
+                                                     int ldv, _Float16* __restrict__ vt) {
+  __shared__ _Float16 tile[32][34];
+  const int head = blockIdx.z, j0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  const int4 sg = seg_find(tab, n_seg, j0, false);
+  const int k0 = j0 - sg.z;                         // first key of this chunk inside its segment
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  for (int i = ty; i < 32; i += 8) {
+    const int j = k0 + i;
+    tile[i][tx] = j < sg.y ? v[(long long)(sg.x + j) * ld + head * 64 + c0 + tx] : (_Float16)0.f;
+  }
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) vt[((long long)head * 64 + c0 + i) * ldv + j0 + tx] = tile[tx][i];
+}
+
+// grid: (query tiles of all segments, heads).  A head's tiles are a contiguous run of virtual ids, as a (row, head) pair's above.
+template <int QT>
+__global__ __launch_bounds__(256) void flash_attn64_seg_f16_kernel(const _Float16* __restrict__ q, int ldq, const _Float16* __restrict__ k,
+                                                                   int ldk, const _Float16* __restrict__ vt, int ldv,
+                                                                   const int4* __restrict__ tab, int n_seg, float scale,
+                                                                   _Float16* __restrict__ out, int ldo) {
+  const int vid = xcd_virtual_id(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
+  const int head = vid / gridDim.x, tile = vid % gridDim.x;
+  const int4 sg = seg_find(tab, n_seg, tile, true);
+  flash_attn64_tile<QT>(q + (long long)sg.x * ldq, ldq, k + (long long)sg.x * ldk, ldk, vt + sg.z, ldv, sg.y, scale,
+                        out + (long long)sg.x * ldo, ldo, head, (tile - sg.w) * (16 * QT));
+}
+
+template <int QT>
+static int launch_flash_seg_qt(const void* q, int ldq, const void* k, int ldk, const void* vt_buf, int ldv, const int4* tab, int n_seg,
+                               int tiles, int heads, float scale, void* out, int ldo, hipStream_t s) {
+  const size_t lds = ((size_t)4 * 16 * QT * 68 + 8 * 16 * QT) * 4;
+  static bool attr = false;
+  if (!attr) {
+    GSV_HIP(hipFuncSetAttribute((const void*)flash_attn64_seg_f16_kernel<QT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    attr = true;
+  }
+  GSV_LAUNCH(flash_attn64_seg_f16_kernel<QT>, dim3(tiles, heads), dim3(256), lds, s, (const _Float16*)q, ldq, (const _Float16*)k, ldk,
+             (const _Float16*)vt_buf, ldv, tab, n_seg, scale, (_Float16*)out, ldo);
   return GSV_OK;
 }
 
@@ -449,6 +522,46 @@ int launch_flash_attn64_f16_rows(const void* q, int ldq, const void* k, int ldk,
 int launch_flash_attn64_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldvv, void* vt_buf, int T, int heads,
                             float scale, void* out, int ldo, hipStream_t s, const float* rope_cs, int rope_half) {
   return launch_flash_attn64_f16_rows(q, ldq, k, ldk, v, ldvv, vt_buf, T, heads, scale, out, ldo, s, rope_cs, rope_half, 1, 0, 0, 0);
+}
+
+// n_seg sequences of seg_lens[s] rows back to back in q / k / v / out, two launches for all of them (vt_seg_kernel, then the
+// segmented kernel); vt_buf: heads * 64 * 32 * sum ceil(T_s / 32) halfs of scratch.  The segment table goes to the device through
+// the library context's staging slots (engine.h): one small async copy on `s`, none when `s` already carries the same table.
+int launch_flash_attn64_f16_seg(const void* q, int ldq, const void* k, int ldk, const void* v, int ldvv, void* vt_buf, int n_seg,
+                                const int* seg_lens, int heads, float scale, void* out, int ldo, hipStream_t s) {
+  GSV_REQUIRE(q && k && v && vt_buf && out && seg_lens, "flash_attn_seg: null argument");
+  GSV_REQUIRE(n_seg >= 1 && heads >= 1 && heads <= 65535, "flash_attn_seg: %d segments, %d heads", n_seg, heads);
+  GSV_REQUIRE(n_seg <= gsveng::kSegTableMax, "flash_attn_seg: %d segments exceed the table's %d", n_seg, gsveng::kSegTableMax);
+  GSV_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldo % 4 == 0 && ((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)out % 8) == 0 &&
+              ((uintptr_t)vt_buf % 16) == 0, "flash_attn_seg: operands must be 16-byte aligned with leading dims multiple of 8");
+  long long rows = 0, t32 = 0, t64 = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    GSV_REQUIRE(seg_lens[i] >= 1, "flash_attn_seg: segment %d has length %d", i, seg_lens[i]);
+    rows += seg_lens[i]; t32 += cdiv(seg_lens[i], 32); t64 += cdiv(seg_lens[i], 64);
+  }
+  GSV_REQUIRE(rows + 32LL * n_seg <= 0x7fffffffLL, "flash_attn_seg: %lld rows exceed the index range", rows);
+  static const int qt_env = getenv("GSV_FLASH_QT") ? atoi(getenv("GSV_FLASH_QT")) : 0;     // A/B switch, as for the rows
+  // the row kernel's rule on the packed problem: keep >= ~1 workgroup per CU.  Tiles are counted per segment, so the counts are sums.
+  const int qt = qt_env ? (qt_env >= 4 ? 4 : qt_env >= 2 ? 2 : 1) : (t64 * heads >= 200 ? 4 : (t32 * heads >= 200 ? 2 : 1));
+  gsveng::SegTable tb;                              // holds the library context until it goes out of scope
+  GSV_RC(gsveng::seg_table_begin(&tb));
+  long long row0 = 0, col0 = 0, tile0 = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    tb.image[4 * i] = (int)row0; tb.image[4 * i + 1] = seg_lens[i]; tb.image[4 * i + 2] = (int)col0; tb.image[4 * i + 3] = (int)tile0;
+    row0 += seg_lens[i]; col0 += 32 * cdiv(seg_lens[i], 32); tile0 += cdiv(seg_lens[i], 16 * qt);
+  }
+  const int ldv = (int)col0, tiles = (int)tile0;
+  // both grids (x = tiles or chunks, <= rows) and the virtual workgroup id tiles * heads have to fit an int
+  GSV_REQUIRE(tile0 * heads <= 0x7fffffffLL, "flash_attn_seg: %lld query tiles x %d heads exceed the grid", tile0, heads);
+  GSV_RC(gsveng::seg_table_upload(&tb, n_seg, s));
+  const int4* tab = (const int4*)tb.dev;
+  GSV_LAUNCH(vt_seg_kernel, dim3(ldv / 32, 2, heads), dim3(256), 0, s, (const _Float16*)v, ldvv, tab, n_seg, ldv, (_Float16*)vt_buf);
+  int rc;
+  if (qt == 4) rc = launch_flash_seg_qt<4>(q, ldq, k, ldk, vt_buf, ldv, tab, n_seg, tiles, heads, scale, out, ldo, s);
+  else if (qt == 2) rc = launch_flash_seg_qt<2>(q, ldq, k, ldk, vt_buf, ldv, tab, n_seg, tiles, heads, scale, out, ldo, s);
+  else rc = launch_flash_seg_qt<1>(q, ldq, k, ldk, vt_buf, ldv, tab, n_seg, tiles, heads, scale, out, ldo, s);
+  GSV_RC(rc);
+  return gsveng::seg_table_end(&tb, s);
 }
 
 }  // namespace gsv

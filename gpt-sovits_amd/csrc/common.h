@@ -241,6 +241,11 @@ int launch_flash_attn64_f16_rows(const void* q, int ldq, const void* k, int ldk,
                                  float scale, void* out, int ldo, hipStream_t s, const float* rope_cs, int rope_half, int rows,
                                  long long xz, long long vtz, long long oz);
 
+// the segmented form: n_seg sequences of seg_lens[s] ([host]) rows back to back, each attending to its own keys only, in the same
+// two launches; vt_buf: heads * 64 * 32 * sum ceil(seg_lens[s] / 32) halfs of scratch (may arrive uninitialised)
+int launch_flash_attn64_f16_seg(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* vt_buf, int n_seg,
+                                const int* seg_lens, int heads, float scale, void* out, int ldo, hipStream_t s);
+
 // enc_p self-attention with window-4 relative positions, fp16, head dim 96 (attn.hip)
 int launch_flash_rel96_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* vt_buf, int T, int heads,
                            float scale, const float* rel_k, const float* rel_v, void* out, int ldo, hipStream_t s,

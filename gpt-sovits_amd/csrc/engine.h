@@ -5,6 +5,7 @@
 #pragma once
 #include <math.h>
 #include <map>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -91,6 +92,32 @@ int attention(Ctx* h, hipStream_t s, const void* q, int ldq, int qcol0, const vo
 void free_ctx(Ctx* h);
 // fp32 channels-first [C][Tn] -> engine dtype channels-last [Tn][ldd] (first C columns; ldd = 0: C)
 int cf_to_cl(Ctx* h, hipStream_t s, const float* src, int Tn, int C, void* dst, int ldd = 0);
+
+// The library's own context, one per device and created at its first use: what an op entry point, which has no handle, needs
+// beyond its arguments.  Today that is the segment table of gsv_op_flash_attn64_seg (attn.hip): kSegSlots slots of a page-locked
+// staging buffer, a device table and an event each, all allocated when the context is created, so a call allocates nothing.
+// A call fills `image` and uploads it with one async copy on its stream into the next slot; the slot's event is recorded after
+// the kernels that read the table, and a slot is rewritten only when that event has passed (kSegSlots tables later, so the wait
+// finds it done).  A call whose table equals the newest slot's and runs on the same stream reuses that slot without a copy: the
+// 22 layers of one packed BERT pass upload their table once.  The context lives until the process ends.
+constexpr int kSegTableMax = 8192, kSegSlots = 4;
+struct SegSlot { int* host = nullptr; int* dev = nullptr; hipEvent_t ev = nullptr; hipStream_t stream = nullptr; int n = 0; };
+struct LibCtx {
+  std::mutex mu;
+  SegSlot slot[kSegSlots];
+  int cur = 0;
+  std::vector<int> image;                             // 4 ints per segment, kSegTableMax segments
+};
+// a call's hold on the context: the lock is released when it goes out of scope
+struct SegTable {
+  std::unique_lock<std::mutex> lock;
+  LibCtx* ctx = nullptr;
+  int* image = nullptr;                               // [4 * kSegTableMax], filled by the caller
+  const int* dev = nullptr;                           // set by seg_table_upload
+};
+int seg_table_begin(SegTable* t);
+int seg_table_upload(SegTable* t, int n_seg, hipStream_t s);
+int seg_table_end(SegTable* t, hipStream_t s);        // after the last launch that reads t->dev
 
 // generator.hip
 // copies the generator's shape out of either config struct (gsv_vits_config, gsv_vocoder_config: same field names)

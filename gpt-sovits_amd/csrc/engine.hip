@@ -407,6 +407,57 @@ int seg_upload_begin(SegUpload* u) {
   return GSV_OK;
 }
 
+// the library context of the current device (engine.h)
+static int lib_ctx(LibCtx** out) {
+  static std::mutex mu;
+  static std::map<int, LibCtx*> ctxs;
+  int dev = 0;
+  GSV_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> g(mu);
+  LibCtx*& c = ctxs[dev];
+  if (!c) {
+    LibCtx* n = new LibCtx;
+    n->image.resize((size_t)4 * kSegTableMax);
+    for (SegSlot& sl : n->slot) {
+      GSV_HIP(hipHostMalloc((void**)&sl.host, (size_t)16 * kSegTableMax, hipHostMallocDefault));
+      GSV_HIP(hipMalloc((void**)&sl.dev, (size_t)16 * kSegTableMax));
+      GSV_HIP(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
+    }
+    c = n;
+  }
+  *out = c;
+  return GSV_OK;
+}
+
+int seg_table_begin(SegTable* t) {
+  GSV_RC(lib_ctx(&t->ctx));
+  t->lock = std::unique_lock<std::mutex>(t->ctx->mu);
+  t->image = t->ctx->image.data();
+  return GSV_OK;
+}
+
+int seg_table_upload(SegTable* t, int n_seg, hipStream_t s) {
+  LibCtx* c = t->ctx;
+  const size_t bytes = (size_t)16 * n_seg;
+  SegSlot* sl = &c->slot[c->cur];
+  if (!(sl->n == n_seg && sl->stream == s && memcmp(sl->host, t->image, bytes) == 0)) {
+    c->cur = (c->cur + 1) % kSegSlots;
+    sl = &c->slot[c->cur];
+    sl->n = 0;
+    GSV_HIP(hipEventSynchronize(sl->ev));             // the launches that read this slot, kSegSlots tables ago
+    memcpy(sl->host, t->image, bytes);
+    GSV_HIP(hipMemcpyAsync(sl->dev, sl->host, bytes, hipMemcpyHostToDevice, s));
+    sl->n = n_seg; sl->stream = s;
+  }
+  t->dev = sl->dev;
+  return GSV_OK;
+}
+
+int seg_table_end(SegTable* t, hipStream_t s) {
+  GSV_HIP(hipEventRecord(t->ctx->slot[t->ctx->cur].ev, s));
+  return GSV_OK;
+}
+
 void free_ctx(Ctx* h) {
   for (void* p : h->allocs) (void)hipFree(p);
   for (auto& b : h->bufs) if (b.second.p) (void)hipFree(b.second.p);

@@ -91,6 +91,48 @@ __global__ void layernorm_kernel(const TX* __restrict__ x, const TR* __restrict_
   }
 }
 
+// BERT's embedding stage: y[i] = LN(word[ids[i]] + pos[pos_ids[i]] + add) * gamma + beta, fp32 tables, sums and statistics, fp16
+// rows out.  One wave per row, the row held in registers (C <= 1024): the tables are read once.  A row whose id or position
+// lies outside its table reads nothing and is stored as NaN: the host checks its own ids, the device cannot report.
+__global__ __launch_bounds__(256) void embed_ln_kernel(const float* __restrict__ word, const float* __restrict__ pos,
+                                                       const float* __restrict__ add, const int* __restrict__ ids,
+                                                       const int* __restrict__ pos_ids, const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, _Float16* __restrict__ y, int rows, int C,
+                                                       int n_word, int n_pos, float eps) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int id = ids[row], pi = pos_ids[row];
+  _Float16* yr = y + (long long)row * C;
+  if (id < 0 || id >= n_word || pi < 0 || pi >= n_pos) {
+    for (int c = lane; c < C; c += 64) yr[c] = (_Float16)__builtin_nanf("");
+    return;
+  }
+  const float* wr = word + (long long)id * C;
+  const float* pr = pos + (long long)pi * C;
+  float v[16];
+  float s1 = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int c = lane + 64 * i;
+    v[i] = c < C ? wr[c] + pr[c] + (add ? add[c] : 0.f) : 0.f;
+    s1 += v[i];
+  }
+  const float mean = wave_sum(s1) / (float)C;
+  float q1 = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const float d = (lane + 64 * i < C) ? v[i] - mean : 0.f;
+    q1 += d * d;
+  }
+  const float rstd = rsqrtf(wave_sum(q1) / (float)C + eps);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int c = lane + 64 * i;
+    if (c < C) yr[c] = (_Float16)((v[i] - mean) * rstd * gamma[c] + beta[c]);
+  }
+}
+
 template <typename TX, typename TR, typename TY>
 static int ln_launch(const void* x, const void* res, const float* g, const float* b, void* y, int rows, int C, float eps,
                      hipStream_t s, const int* row_seg) {
@@ -266,6 +308,24 @@ int gsv_op_flash_attn64(const void* qkv, int T, int heads, float scale, void* vt
   const int inner = heads * 64;
   return gsv::launch_flash_attn64_f16(qkv, 3 * inner, (const _Float16*)qkv + inner, 3 * inner, (const _Float16*)qkv + 2 * inner, 3 * inner,
                                       vt_scratch, T, heads, scale, out, inner, (hipStream_t)stream);
+}
+
+int gsv_op_flash_attn64_seg(const void* qkv, int n_seg, const int32_t* seg_lens, int heads, float scale, void* vt_scratch, void* out,
+                            gsv_stream_t stream) {
+  const int inner = heads * 64;
+  return gsv::launch_flash_attn64_f16_seg(qkv, 3 * inner, (const _Float16*)qkv + inner, 3 * inner, (const _Float16*)qkv + 2 * inner,
+                                          3 * inner, vt_scratch, n_seg, seg_lens, heads, scale, out, inner, (hipStream_t)stream);
+}
+
+int gsv_op_embed_ln(const float* word, int n_word, const float* pos, int n_pos, const float* add, const int32_t* ids,
+                    const int32_t* pos_ids, const float* gamma, const float* beta, void* y, int rows, int C, float eps,
+                    gsv_stream_t stream) {
+  GSV_REQUIRE(word && pos && ids && pos_ids && gamma && beta && y && rows > 0 && n_word > 0 && n_pos > 0, "op_embed_ln: bad argument");
+  GSV_REQUIRE(C >= 1 && C <= 1024, "op_embed_ln: C = %d, the row is held in registers up to 1024", C);
+  hipLaunchKernelGGL(gsv::embed_ln_kernel, dim3(gsv::cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, word, pos, add, ids, pos_ids,
+                     gamma, beta, (_Float16*)y, rows, C, n_word, n_pos, eps);
+  GSV_HIP(hipGetLastError());
+  return GSV_OK;
 }
 
 int gsv_op_flash_rel96(const void* qkv, int T, int heads, float scale, const float* rel_k, const float* rel_v, void* vt_scratch,

@@ -207,6 +207,9 @@ class TTS:
         self.t2s_model: Optional[Text2SemanticDecoder] = None
         self.vits_model: Optional[SynthesizerTrn] = None
         self.text_frontend: Optional[Callable] = None
+        # True: a request's raw text goes through TextPreprocessor.preprocess_many, so all its sentences' zh BERT features come
+        # from one packed pass (BertFeature.batch) instead of one engine call per sentence
+        self.batched_bert = False
         self.prompt_cache: dict = {
             "ref_audio_path": None, "prompt_semantic": None, "refer_spec": [], "prompt_text": None,
             "prompt_lang": None, "phones": None, "bert_features": None, "norm_text": None, "aux_ref_audio_paths": [],
@@ -943,8 +946,28 @@ class TTS:
             else:
                 if text_lang not in self.configs.languages:
                     raise ValueError(f"text_lang {text_lang!r} is not one of {self.configs.languages}")
-                segments = self.text_preprocessor.preprocess(text, text_lang, method, self.configs.version)
+                if self.batched_bert:
+                    segments = self.text_preprocessor.preprocess_many([(text, text_lang, method)], self.configs.version)[0]
+                else:
+                    segments = self.text_preprocessor.preprocess(text, text_lang, method, self.configs.version)
         return segments
+
+    def _with_shared_segments(self, requests: List[dict]) -> List[dict]:
+        """run_batch(shared_bert=True): the raw texts of all requests through ONE preprocess_many, each such request returned
+        as a copy with its `segments` filled in.  Requests that bring `segments` pass through, and so does every request when a
+        `text_frontend` replaces the preprocessor.  Raises what _segments raises for the request alone."""
+        if self.text_frontend is not None:
+            return list(requests)
+        todo = [i for i, req in enumerate(requests) if req.get("segments") is None]
+        for i in todo:
+            if requests[i].get("text_lang", "") not in self.configs.languages:
+                raise ValueError(f"text_lang {requests[i].get('text_lang', '')!r} is not one of {self.configs.languages}")
+        items = [(requests[i].get("text", ""), requests[i].get("text_lang", ""), requests[i].get("text_split_method", "cut0"))
+                 for i in todo]
+        out = list(requests)
+        for i, segments in zip(todo, self.text_preprocessor.preprocess_many(items, self.configs.version) if items else []):
+            out[i] = dict(requests[i], segments=segments)
+        return out
 
     def _voice_refer(self, voice: dict) -> Tuple[List[torch.Tensor], dict]:
         """the device reference of a voice or prompt-cache dict as SynthesizerTrn.decode takes it: (`refer`, the spectrograms
@@ -1463,7 +1486,7 @@ class TTS:
     @torch.no_grad()
     def run_batch(self, requests: List[dict], shared_sovits: bool = False, shared_cfm: bool = False,
                   shared_speed: bool = False, mixed_sampling: bool = False,
-                  shared_vocoder: bool = False) -> List[Tuple[int, np.ndarray]]:
+                  shared_vocoder: bool = False, shared_bert: bool = False) -> List[Tuple[int, np.ndarray]]:
         """Several requests, each with its own reference voice, through shared AR decodes.  Each request dict takes the
         keys run() accepts plus an optional "voice" (make_voice); without one it uses its ref_audio_path / prompt_text
         (through make_voice's LRU) or the current prompt cache.  Returns one (sr, int16 audio) per request, in order: what
@@ -1479,12 +1502,17 @@ class TTS:
         shared_vocoder=True (with shared_cfm=True; ValueError without it on a v3 / v4 model): the folds of the shared
         flow-matching stage are vocoded in shared segmented passes over all voices (plan_vocoder, the vocoder's
         forward_segments) instead of one vocoder call per fold.
+        shared_bert=True: the raw texts of all requests go through one TextPreprocessor.preprocess_many before stage 1, so the
+        zh BERT features of every sentence of every request come from one packed pass (requests that bring `segments`, and all
+        requests under a `text_frontend`, are left as they are).
         No keyword changes anything for the other model family."""
         if self.t2s_model is None or self.vits_model is None:
             raise RuntimeError("init_t2s_weights / init_vits_weights first")
         if shared_vocoder and self.configs.use_vocoder and not shared_cfm:
             raise ValueError("shared_vocoder=True vocodes the folds of the shared flow-matching stage: pass shared_cfm=True too")
         self.stop_flag = False
+        if shared_bert:
+            requests = self._with_shared_segments(requests)
         plans = [self._plan_request(req) for req in requests]
         self._ar_stage(plans, mixed_sampling=mixed_sampling)
         sr = self._output_sr()

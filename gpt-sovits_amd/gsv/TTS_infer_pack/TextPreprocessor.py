@@ -115,6 +115,65 @@ class TextPreprocessor:
             result.append({"phones": phones, "bert_features": bert_features, "norm_text": norm_text})
         return result
 
+    # ---- the same for many requests, with the zh BERT features of all of them computed in one call
+    def preprocess_many(self, items: List[Tuple[str, str, str]], version: str = "v2") -> List[List[Dict]]:
+        """`items`: (text, lang, text_split_method) per request -> what `preprocess` returns for each, in order.
+        Phase 1 is host work only (splitting, language runs, G2P, the short-sentence retry: all of it depends on phones alone);
+        phase 2 hands the norm_text of every zh run to `bert_fn.batch` in ONE call (a `bert_fn` without `batch` is called per
+        text, as `preprocess` does); phase 3 repeats the features by word2ph and concatenates the runs of each sentence."""
+        with self.bert_lock:
+            plans = []                                               # per item: [(phones, [(lang, n_phones, word2ph, norm)], norm_text)]
+            zh: List[str] = []
+            for text, lang, method in items:
+                sentences = []
+                for piece in self.pre_seg_text(self.replace_consecutive_punctuation(text), lang, method):
+                    phones, runs, norm_text = self._phones_and_runs(piece, lang, version)
+                    if norm_text == "":
+                        continue
+                    zh += [norm for rl, _, _, norm in runs if rl == "zh"]
+                    sentences.append((phones, runs, norm_text))
+                plans.append(sentences)
+            feats: List[torch.Tensor] = []
+            if zh:
+                if self.bert_fn is None:
+                    self.get_bert_feature(zh[0], [])                  # raises what preprocess raises
+                batch = getattr(self.bert_fn, "batch", None)
+                feats = list(batch(zh)) if batch is not None else [self.bert_fn(t) for t in zh]
+            nxt = iter(feats)
+            result = []
+            for sentences in plans:
+                segs = []
+                for phones, runs, norm_text in sentences:
+                    berts = []
+                    for rl, n_ph, word2ph, norm in runs:
+                        if rl == "zh":
+                            res = next(nxt).float().cpu()
+                            assert len(word2ph) == len(norm) == res.shape[0]
+                            rep = torch.as_tensor(word2ph, dtype=torch.long)
+                            berts.append(torch.repeat_interleave(res, rep, dim=0).T.to(self.device))
+                        else:
+                            berts.append(torch.zeros((1024, n_ph), dtype=torch.float32, device=self.device))
+                    segs.append({"phones": phones, "bert_features": torch.cat(berts, dim=1), "norm_text": norm_text})
+                result.append(segs)
+            return result
+
+    def _phones_and_runs(self, text: str, language: str, version: str, final: bool = False):
+        """the host half of get_phones_and_bert: phones, the runs (language, phone count, word2ph, norm_text) and norm_text.
+        Kept beside it, not under it: get_phones_and_bert computes each run's features inside its loop, before the retry, and
+        that order of engine calls stays what it is"""
+        text = re.sub(r" {2,}", " ", text)
+        phones: List[int] = []
+        runs = []
+        norm_text = ""
+        for lang, piece in self._runs(text, language):
+            ph, word2ph, norm = self.clean_text_inf(piece, lang, version)
+            runs.append((lang.replace("all_", ""), len(ph), word2ph, norm))
+            phones += ph
+            norm_text += norm
+        if not final and len(phones) < 6:
+            return self._phones_and_runs("." + text, language, version, final=True)
+        return phones, runs, norm_text
+
     # ---- reference :79-117, as a chain of small stages
     def pre_seg_text(self, text: str, lang: str, text_split_method: str) -> List[str]:
         stop = "." if lang == "en" else "。"

@@ -7,6 +7,11 @@ Tokenisation: one token per character through vocab.txt (lower-cased, unknown ->
 for CJK text and punctuation, and the only case the reference accepts (it asserts len(word2ph) == len(text)).
 Embedding rows are gathered and summed on the host (<= 512 x 1024 values); the 22 encoder layers run as `gsv_op_conv1d` /
 `gsv_op_flash_attn64` / `gsv_op_layernorm` calls in fp16 with fp32 accumulation and normalisation statistics.
+
+`BertFeature.batch(texts) -> [Tensor[len(text), 1024]]` runs many texts in one packed pass: their tokens
+lie back to back in one [sum T, 1024] matrix, the embedding rows are gathered and normalised on the device (`gsv_op_embed_ln`),
+the GEMMs and LayerNorms are the row-wise launches above at M = sum T, and `gsv_op_flash_attn64_seg` keeps every text to its
+own keys: 1 + 22 x 8 launches, one upload of ids and positions, one of the segment table and one download, whatever the count.
 """
 from __future__ import annotations
 
@@ -86,6 +91,8 @@ class BertFeature:
             put(f"l{i}.ln2_w", sd[p + "output.LayerNorm.weight"], False)
             put(f"l{i}.ln2_b", sd[p + "output.LayerNorm.bias"], False)
         self.ffn = int(self.w["l0.f1_w"].shape[0])
+        self.passes = 0                  # packed passes issued by batch(), for tests and tools/text_frontend_bench.py
+        self._tables = None              # fp32 device copies of the embedding tables, made by the first batch()
 
     def tokenize(self, text: str) -> List[int]:
         unk = self.tok["[UNK]"]
@@ -131,3 +138,72 @@ class BertFeature:
                 f2 = self._gemm(st, f, T, self.ffn, w[f"l{i}.f2_w"], h, w[f"l{i}.f2_b"], res=x)
                 x = self._ln(st, f2, T, w[f"l{i}.ln2_w"], w[f"l{i}.ln2_b"])
         return x[1:-1].float()
+
+    # Tokens of one packed pass unless the caller says otherwise, from the sweep of tools/text_frontend_bench.py on an MI355X
+    # (140 sentences of 60 characters = 8680 tokens; ms per batch() call, median of 7): 512 -> 52.4 (18 passes), 1024 -> 31.2 (9),
+    # 2048 -> 24.5 (5), 4096 -> 21.1 (3), 8192 -> 18.1 (2), 16384 -> 18.3 (1).  The time stops falling at 8192, where the pass's
+    # workspace is still under 200 MB (the [sum T, 4096] FFN activation is 64 MB).
+    MAX_TOKENS = 8192
+    MAX_TEXTS = 8192                     # segments one gsv_op_flash_attn64_seg call takes (include/gsv.h)
+
+    def _device_tables(self):
+        if self._tables is None:
+            dev = self.device
+            self._tables = tuple(t.to(dev, torch.float32).contiguous() for t in (self.emb_word, self.emb_pos, self.emb_type0))
+        return self._tables
+
+    @torch.no_grad()
+    def _packed_pass(self, ids: List[List[int]]) -> List[torch.Tensor]:
+        """one pass over the token lists `ids` ([CLS] .. [SEP] each): fp32 host tensors without the first and last row"""
+        lens = [len(t) for t in ids]
+        M, n = sum(lens), len(ids)
+        h, w, l, dev = self.hidden, self.w, _lib.lib(), self.device
+        word, pos, type0 = self._device_tables()
+        host = torch.empty(2, M, dtype=torch.int32, pin_memory=True)
+        host[0] = torch.tensor([t for row in ids for t in row], dtype=torch.int32)
+        host[1] = torch.cat([torch.arange(k, dtype=torch.int32) for k in lens])
+        seg = (C.c_int32 * n)(*lens)
+        with torch.cuda.device(dev):
+            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            idx = host.to(dev, non_blocking=True)
+            x = torch.empty(M, h, dtype=torch.float16, device=dev)
+            _lib.check(l.gsv_op_embed_ln(word.data_ptr(), word.shape[0], pos.data_ptr(), pos.shape[0], type0.data_ptr(),
+                                         idx[0].data_ptr(), idx[1].data_ptr(), w["emb_ln_w"].data_ptr(), w["emb_ln_b"].data_ptr(),
+                                         x.data_ptr(), M, h, self.eps, st), "gsv_op_embed_ln")
+            vt = torch.empty(h * 32 * sum((k + 31) // 32 for k in lens), dtype=torch.float16, device=dev)
+            for i in range(self.layers_used):
+                qkv = self._gemm(st, x, M, h, w[f"l{i}.qkv_w"], 3 * h, w[f"l{i}.qkv_b"])
+                att = torch.empty(M, h, dtype=torch.float16, device=dev)
+                _lib.check(l.gsv_op_flash_attn64_seg(qkv.data_ptr(), n, seg, self.heads, 0.125, vt.data_ptr(), att.data_ptr(), st),
+                           "gsv_op_flash_attn64_seg")
+                o = self._gemm(st, att, M, h, w[f"l{i}.o_w"], h, w[f"l{i}.o_b"], res=x)
+                x = self._ln(st, o, M, w[f"l{i}.ln1_w"], w[f"l{i}.ln1_b"])
+                f = self._gemm(st, x, M, h, w[f"l{i}.f1_w"], self.ffn, w[f"l{i}.f1_b"], act=ACT_GELU)
+                f2 = self._gemm(st, f, M, self.ffn, w[f"l{i}.f2_w"], h, w[f"l{i}.f2_b"], res=x)
+                x = self._ln(st, f2, M, w[f"l{i}.ln2_w"], w[f"l{i}.ln2_b"])
+            out = torch.empty(M, h, dtype=torch.float16, pin_memory=True)
+            out.copy_(x, non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()
+        self.passes += 1
+        return [rows[1:-1].float() for rows in out.split(lens)]
+
+    def batch(self, texts: List[str], max_tokens: Optional[int] = None) -> List[torch.Tensor]:
+        """features of every text, [len(text), 1024] fp32 host tensors in input order.  Texts are packed into passes of at most
+        `max_tokens` tokens ([CLS] / [SEP] included) and MAX_TEXTS texts, in input order; a text is never split."""
+        max_tokens = self.MAX_TOKENS if max_tokens is None else int(max_tokens)
+        if max_tokens < 512:
+            raise ValueError(f"max_tokens = {max_tokens}: a pass has to hold one text of BERT's 512 positions")
+        ids = [self.tokenize(t) for t in texts]
+        for t in ids:
+            if len(t) > self.emb_pos.shape[0]:
+                raise ValueError(f"{len(t)} tokens exceed BERT's {self.emb_pos.shape[0]} positions (the front-end splits above 510 characters)")
+        out: List[torch.Tensor] = []
+        group: List[List[int]] = []
+        for t in ids:
+            if group and (sum(map(len, group)) + len(t) > max_tokens or len(group) == self.MAX_TEXTS):
+                out += self._packed_pass(group)
+                group = []
+            group.append(t)
+        if group:
+            out += self._packed_pass(group)
+        return out

@@ -435,6 +435,20 @@ typedef struct {
 /* fused softmax attention of the DiT blocks alone (fp16, head dim 64): qkv [dev] f16 [T][3*heads*64] (q | k | v column
  * blocks), vt_scratch [dev] heads*64*ceil32(T) halfs, out [dev] f16 [T][heads*64] */
 int gsv_op_flash_attn64(const void* qkv, int T, int heads, float scale, void* vt_scratch, void* out, gsv_stream_t stream);
+/* the same attention over n_seg sequences packed back to back (the batched zh BERT pass): qkv [dev] f16 [sum T][3*heads*64],
+ * seg_lens [host] n_seg lengths T_s >= 1, out [dev] f16 [sum T][heads*64]; query i of segment s attends to the keys of segment s
+ * only.  Two launches for all segments, no host synchronisation and no allocation in the call (the segment table travels in one
+ * small async copy on `stream` from a page-locked buffer the library owns).  vt_scratch [dev]: heads * 64 * 32 * sum ceil(T_s / 32)
+ * halfs, 16-byte aligned, may arrive uninitialised (segment s owns V^T columns 32 * sum_{s' < s} ceil(T_s' / 32) onwards, its
+ * padding columns are written as 0).  n_seg < 1, n_seg > 8192 or a T_s < 1 is GSV_ERR_ARG. */
+int gsv_op_flash_attn64_seg(const void* qkv, int n_seg, const int32_t* seg_lens, int heads, float scale, void* vt_scratch, void* out,
+                            gsv_stream_t stream);
+/* BERT's embedding stage: y[i] = LayerNorm(word[ids[i]] + pos[pos_ids[i]] + add) * gamma + beta as f16 rows [rows][C]; word [dev]
+ * fp32 [n_word][C], pos [dev] fp32 [n_pos][C], add [dev] fp32 [C] or NULL, ids / pos_ids [dev] int32 [rows], gamma / beta [dev] fp32
+ * [C]; sums and statistics in fp32.  C <= 1024.  A row whose id or position is outside its table is stored as NaN. */
+int gsv_op_embed_ln(const float* word, int n_word, const float* pos, int n_pos, const float* add, const int32_t* ids,
+                    const int32_t* pos_ids, const float* gamma, const float* beta, void* y, int rows, int C, float eps,
+                    gsv_stream_t stream);
 /* enc_p self-attention with window-4 relative positions alone (fp16, head dim 96, module/attentions.py:227-258):
  * qkv [dev] f16 [T][3*heads*96], rel_k / rel_v [dev] fp32 [9][96], vt_scratch heads*96*ceil32(T) halfs, out f16 [T][heads*96] */
 int gsv_op_flash_rel96(const void* qkv, int T, int heads, float scale, const float* rel_k, const float* rel_v, void* vt_scratch,

@@ -553,22 +553,33 @@ class TTS:
                 audio16k = audio16k.half()
         return spec, audio16k
 
-    def _set_prompt_semantic(self, ref_wav_path: str):
-        """reference TTS.py:802-819: 16 kHz audio (3..10 s or OSError) + 0.3 s of silence -> HuBERT last_hidden_state ->
-        SynthesizerTrn.extract_latent codes."""
+    def _prompt_wav16k(self, ref_wav_path: str) -> np.ndarray:
+        """reference TTS.py:802-810: the prompt audio at 16 kHz (3..10 s or OSError) with 0.3 s of silence behind it"""
         from ..audio_io import load_wav, resample
-        if getattr(self, "cnhuhbert_model", None) is None:
-            raise RuntimeError("init_cnhuhbert_weights() first")
-        if self.vits_model is None:
-            raise RuntimeError("init_vits_weights() first")
         raw, raw_sr = load_wav(ref_wav_path)
         wav16k = resample(raw.mean(0), raw_sr, 16000)
         if wav16k.shape[0] > 160000 or wav16k.shape[0] < 48000:
             raise OSError("参考音频在3~10秒范围外，请更换！")
         zero_wav = np.zeros(int(self.configs.sampling_rate * 0.3), dtype=np.float32)
-        wav = torch.from_numpy(np.concatenate([wav16k, zero_wav])).to(self.configs.device)
-        hubert_feature = self.cnhuhbert_model.model(wav.unsqueeze(0))["last_hidden_state"].transpose(1, 2)
-        codes = self.vits_model.extract_latent(hubert_feature)
+        return np.concatenate([wav16k, zero_wav])
+
+    def _set_prompt_semantic(self, ref_wav_path: str, hubert_feature: Optional[torch.Tensor] = None,
+                             codes: Optional[torch.Tensor] = None, wav16k: Optional[np.ndarray] = None):
+        """reference TTS.py:802-819: 16 kHz audio (3..10 s or OSError) + 0.3 s of silence -> HuBERT last_hidden_state ->
+        SynthesizerTrn.extract_latent codes.  `hubert_feature` [1, 768, T50]: HuBERT is skipped; `codes` [1, 1, T50 // 2]:
+        extract_latent too (make_voices computes both for many voices at once); `wav16k`: what _prompt_wav16k returned for
+        this path, so that the file is not read again."""
+        if getattr(self, "cnhuhbert_model", None) is None:
+            raise RuntimeError("init_cnhuhbert_weights() first")
+        if self.vits_model is None:
+            raise RuntimeError("init_vits_weights() first")
+        if wav16k is None:
+            wav16k = self._prompt_wav16k(ref_wav_path)
+        if codes is None:
+            if hubert_feature is None:
+                wav = torch.from_numpy(wav16k).to(self.configs.device)
+                hubert_feature = self.cnhuhbert_model.model(wav.unsqueeze(0))["last_hidden_state"].transpose(1, 2)
+            codes = self.vits_model.extract_latent(hubert_feature)
         self.prompt_cache["prompt_semantic"] = codes[0, 0].to(self.configs.device)
 
     def stop(self):
@@ -1088,6 +1099,77 @@ class TTS:
 
     voice_cache_size = 8
 
+    def make_voices(self, specs: Sequence[dict]) -> List[dict]:
+        """make_voice(ref_audio_path=..., prompt_text=..., prompt_lang=..., aux_ref_audio_paths=...) for many specs (dicts of
+        those keywords) with ONE packed HuBERT pass (HubertModel.batch) and one extract_latent_many over the reference audios
+        that the voice LRU does not hold; every distinct ref_audio_path is loaded and encoded once.  The spectrogram, speaker
+        embedding, auxiliary references and prompt text of each voice are computed by the code make_voice runs.  Returns one
+        voice per spec, in order -- all of them, also when there are more than voice_cache_size; every new voice enters the
+        LRU, which evicts as make_voice's does.  A missing file (ValueError) or a prompt outside 3..10 s (OSError) is raised
+        before any device work.  self.prompt_cache is not changed."""
+        lru = self.__dict__.setdefault("_voice_lru", collections.OrderedDict())
+        keys, out, missing = [], {}, []
+        for spec in specs:
+            unknown = set(spec) - {"ref_audio_path", "prompt_text", "prompt_lang", "aux_ref_audio_paths"}
+            if unknown or spec.get("ref_audio_path") in [None, ""]:
+                raise ValueError(f"make_voices: a spec takes ref_audio_path (required), prompt_text, prompt_lang and "
+                                 f"aux_ref_audio_paths, got {sorted(spec)}")
+            key = (spec["ref_audio_path"], spec.get("prompt_text"), spec.get("prompt_lang", ""),
+                   tuple(spec.get("aux_ref_audio_paths") or ()))
+            keys.append(key)
+            if key in out or key in missing:
+                continue
+            if key in lru:
+                lru.move_to_end(key)
+                out[key] = lru[key]
+            else:
+                missing.append(key)
+        if missing:
+            if getattr(self, "cnhuhbert_model", None) is None:
+                raise RuntimeError("init_cnhuhbert_weights() first")
+            if self.vits_model is None:
+                raise RuntimeError("init_vits_weights() first")
+            wavs: Dict[str, np.ndarray] = {}
+            for key in missing:                                   # host side first: every file error before any device work
+                path = key[0]
+                if path not in wavs:
+                    if not os.path.exists(path):
+                        raise ValueError(f"{path} not exists")
+                    wavs[path] = self._prompt_wav16k(path)
+            paths = list(wavs)
+            feats = self.cnhuhbert_model.model.batch([torch.from_numpy(wavs[p]) for p in paths])
+            codes = dict(zip(paths, self.vits_model.extract_latent_many([f.transpose(1, 2) for f in feats])))
+            spec_of = {key: spec for key, spec in zip(keys, specs)}
+            for key in missing:
+                path, spec = key[0], spec_of[key]
+                req = {"ref_audio_path": path, "prompt_text": spec.get("prompt_text"), "prompt_lang": spec.get("prompt_lang", "")}
+                if spec.get("aux_ref_audio_paths") is not None:
+                    req["aux_ref_audio_paths"] = list(spec["aux_ref_audio_paths"])
+                with self._with_prompt_cache(self._empty_prompt_cache()) as pc:
+                    # set_ref_audio with the codes handed in; _prepare_prompt then finds the path current and goes on to the
+                    # auxiliary references and the prompt text
+                    self._set_prompt_semantic(path, codes=codes[path], wav16k=wavs[path])
+                    self._set_ref_spec(path)
+                    pc["ref_audio_path"] = path
+                    self._prepare_prompt(req)
+                out[key] = lru[key] = {k: pc.get(k) for k in self._VOICE_KEYS}
+                while len(lru) > self.voice_cache_size:
+                    lru.popitem(last=False)
+        return [out[key] for key in keys]
+
+    def _with_shared_voices(self, requests: List[dict]) -> List[dict]:
+        """run_batch(shared_hubert=True): the requests that name a ref_audio_path and bring no `voice` get theirs from ONE
+        make_voices call, each returned as a copy with its `voice` filled in; the others pass through"""
+        todo = [i for i, req in enumerate(requests) if req.get("voice") is None and req.get("ref_audio_path") not in [None, ""]]
+        out = list(requests)
+        if todo:
+            specs = [{"ref_audio_path": requests[i]["ref_audio_path"], "prompt_text": requests[i].get("prompt_text"),
+                      "prompt_lang": requests[i].get("prompt_lang", ""),
+                      "aux_ref_audio_paths": requests[i].get("aux_ref_audio_paths")} for i in todo]
+            for i, voice in zip(todo, self.make_voices(specs)):
+                out[i] = dict(requests[i], voice=voice)
+        return out
+
     def _request_voice(self, req: dict) -> dict:
         if req.get("voice") is not None:
             return req["voice"]
@@ -1486,7 +1568,8 @@ class TTS:
     @torch.no_grad()
     def run_batch(self, requests: List[dict], shared_sovits: bool = False, shared_cfm: bool = False,
                   shared_speed: bool = False, mixed_sampling: bool = False,
-                  shared_vocoder: bool = False, shared_bert: bool = False) -> List[Tuple[int, np.ndarray]]:
+                  shared_vocoder: bool = False, shared_bert: bool = False,
+                  shared_hubert: bool = False) -> List[Tuple[int, np.ndarray]]:
         """Several requests, each with its own reference voice, through shared AR decodes.  Each request dict takes the
         keys run() accepts plus an optional "voice" (make_voice); without one it uses its ref_audio_path / prompt_text
         (through make_voice's LRU) or the current prompt cache.  Returns one (sr, int16 audio) per request, in order: what
@@ -1505,6 +1588,9 @@ class TTS:
         shared_bert=True: the raw texts of all requests go through one TextPreprocessor.preprocess_many before stage 1, so the
         zh BERT features of every sentence of every request come from one packed pass (requests that bring `segments`, and all
         requests under a `text_frontend`, are left as they are).
+        shared_hubert=True: the requests that name a `ref_audio_path` and bring no `voice` get their voices from one make_voices
+        call before planning: one packed HuBERT pass over the reference audios the voice LRU does not hold, instead of one
+        pass per voice.
         No keyword changes anything for the other model family."""
         if self.t2s_model is None or self.vits_model is None:
             raise RuntimeError("init_t2s_weights / init_vits_weights first")
@@ -1513,6 +1599,8 @@ class TTS:
         self.stop_flag = False
         if shared_bert:
             requests = self._with_shared_segments(requests)
+        if shared_hubert:
+            requests = self._with_shared_voices(requests)
         plans = [self._plan_request(req) for req in requests]
         self._ar_stage(plans, mixed_sampling=mixed_sampling)
         sr = self._output_sr()

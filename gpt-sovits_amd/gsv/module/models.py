@@ -259,6 +259,26 @@ class SynthesizerTrn:
             self.stream.synchronize()
         return out.long().view(1, 1, -1)
 
+    @torch.no_grad()
+    def extract_latent_many(self, features) -> list:
+        """extract_latent for many voices: `features` [1, 768, T50] each -> [1, 1, T50 // 2] int64 codes each, in order.  The
+        engine call is issued once per voice on the engine stream, with one wait on the caller's stream before all of them and
+        one synchronisation after."""
+        if not self._loaded:
+            raise RuntimeError("load_state_dict() first")
+        outs, held = [], []
+        with torch.cuda.device(self.device):
+            for x in features:
+                T50 = int(x.shape[-1])
+                held.append(x.reshape(768, T50).to(self.device, torch.float32).contiguous())
+                outs.append(torch.empty((T50 - 2) // 2 + 1, dtype=torch.int32, device=self.device))
+            self.stream.wait_stream(torch.cuda.current_stream(self.device))
+            for xs, out in zip(held, outs):
+                _lib.check(_lib.lib().gsv_vits_extract_latent(self._h, xs.data_ptr(), int(xs.shape[1]), out.data_ptr(),
+                                                              C.c_void_p(self.stream.cuda_stream)), "gsv_vits_extract_latent")
+            self.stream.synchronize()
+        return [out.long().view(1, 1, -1) for out in outs]
+
     # ---- test / bench hooks -------------------------------------------------------------
     def debug_tensor(self, name: str, numel: int) -> torch.Tensor:
         out = torch.empty(numel, dtype=torch.float32, device=self.device)

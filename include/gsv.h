@@ -519,6 +519,24 @@ int gsv_op_aff_mix(const float* x, const float* y, const float* t, long long n, 
 int gsv_op_time_mean(const float* x, int T, int ld, float* out, gsv_stream_t stream);
 int gsv_op_channel_norm(const void* x, int T, int C, const float* gamma, const float* beta, float eps, int act, float* scratch,
                         void* y, int dtype, gsv_stream_t stream);
+/* gsv_op_channel_norm over n_seg row ranges of one channels-last array (the packed HuBERT pass, gsv/feature_extractor/cnhubert.py
+ * HubertModel.batch: GroupNorm(C, C) over each audio's own rows): x, y [dev] [T][C] of dtype (f16 / f32), 16-byte aligned, C a
+ * multiple of 8 (f16) / 4 (f32); seg_start / seg_len [host] n_seg ranges [start, start + len), disjoint and ascending, len >= 1,
+ * inside [0, T).  Rows of segment s: y = act((x - mean_{s,c}) * rstd_{s,c} * gamma[c] + beta[c]), mean and biased variance over the
+ * segment's own rows (fp32 partial sums of x minus the segment's first row, per 256 rows counted from that row, summed in order in
+ * double precision);
+ * every other row of y is stored as 0.  A segment's output bits depend on its own rows alone, not on its position or on the other
+ * segments of the call.  Three launches, no host synchronisation and no allocation in the call (the table travels like
+ * gsv_op_flash_attn64_seg's).  scratch [dev] fp32: 2 * C * (sum_s ceil(len_s / 256) + n_seg) floats, may arrive uninitialised.
+ * n_seg < 1, n_seg > 8192, a len < 1, overlapping or descending segments, or one that ends past T: GSV_ERR_ARG. */
+int gsv_op_channel_norm_seg(const void* x, int T, int C, int n_seg, const int32_t* seg_start, const int32_t* seg_len,
+                            const float* gamma, const float* beta, float eps, int act, float* scratch, void* y, int dtype,
+                            gsv_stream_t stream);
+/* y[r] = x[idx[r]] for r < rows_out: x [dev] [rows_in][C], y [dev] [rows_out][C] of dtype (f16 / f32), rows a multiple of 16 bytes
+ * and both arrays 16-byte aligned, idx [dev] int32 [rows_out].  idx[r] < 0 stores a zero row (the gap rows the packed HuBERT pass
+ * puts between audios in front of the positional conv); idx[r] >= rows_in stores a NaN row, as gsv_op_embed_ln does for an id
+ * outside its table.  x and y must not overlap. */
+int gsv_op_gather_rows(const void* x, int rows_in, const int32_t* idx, int rows_out, int C, void* y, int dtype, gsv_stream_t stream);
 /* sampling kernel alone: logits [dev] fp32 [B][vocab], prev [dev] int32 [B][prev_len], noise [dev]
  * fp32 [B][vocab] or NULL; outputs [dev] int32 [B]: sampled token, argmax of penalised logits */
 int gsv_op_sample(const float* logits, int B, int vocab, int vocab_eff, const int32_t* prev, int prev_len,

@@ -314,24 +314,35 @@ ConvArgs linear(const void* x, const void* w, const float* bias, void* y, int ro
 bool scalar_prefill_attn() { static const bool v = getenv("GSV_SCALAR_PREFILL_ATTN") != nullptr; return v; }      // thread-per-query VALU kernel
 bool prefill_split_scatter() { static const bool v = getenv("GSV_PREFILL_SPLIT_SCATTER") != nullptr; return v; }  // K/V scatter and V^T as two launches
 
-// One layer's K/V into the cache and its attention, pf_qkv -> pf_attn, by one of three routes: fp16 with head dim 32 runs the
-// MFMA flash kernel behind prefill_kvt_kernel (scatter + V^T in one launch) or, with GSV_PREFILL_SPLIT_SCATTER, behind
-// kv_scatter + prefill_vt; fp32 and GSV_SCALAR_PREFILL_ATTN take kv_scatter + the scalar kernel.
+// One layer's K/V fill and attention without the engine handle: what prefill_attention (the engine) and gsv_op_prefill_attn
+// (the test hook) both launch through.  row_off / x_len / plen are device arrays of B ints, vt the V^T scratch of
+// B * H * 32 * ceil32(maxS) halfs (fp16 flash routes only), kc / vc one layer's head-major cache [B][H][smax][32].
+struct PrefillAttnArgs {
+  const void* qkv = nullptr;
+  void *kc = nullptr, *vc = nullptr, *vt = nullptr, *out = nullptr;
+  const int *row_off = nullptr, *x_len = nullptr, *plen = nullptr;
+  int B = 0, H = 0, d = 0, smax = 0, maxS = 0;
+  bool scalar = false;          // thread-per-query VALU kernel instead of the MFMA flash kernel
+  bool split_scatter = false;   // K/V scatter and V^T as two launches
+};
+
+// By one of three routes: fp16 with head dim 32 runs the MFMA flash kernel behind prefill_kvt_kernel (scatter + V^T in one
+// launch) or, with split_scatter, behind kv_scatter + prefill_vt; fp32 and `scalar` take kv_scatter + the scalar kernel.
 template <typename T>
-int prefill_attention(gsv_t2s* h, int li, int maxS, hipStream_t s) {
-  const int d = h->cfg.dim, H = h->cfg.n_head, B = h->B, smax = h->max_seq;
-  const T* qkv = (const T*)h->pf_qkv;
-  T* kc = (T*)kv_ptr(h, li, 0);
-  T* vc = (T*)kv_ptr(h, li, 1);
-  T* out = (T*)h->pf_attn;
-  const int *row_off = h->d_row_off, *x_len = h->d_x_len, *plen = h->d_plen;
-  const bool mfma = std::is_same<T, _Float16>::value && d / H == 32 && !scalar_prefill_attn();
-  const bool fused_kvt = mfma && !prefill_split_scatter();
+int launch_prefill_attention(const PrefillAttnArgs& a, hipStream_t s) {
+  const int d = a.d, H = a.H, B = a.B, smax = a.smax, maxS = a.maxS;
+  const T* qkv = (const T*)a.qkv;
+  T* kc = (T*)a.kc;
+  T* vc = (T*)a.vc;
+  T* out = (T*)a.out;
+  const int *row_off = a.row_off, *x_len = a.x_len, *plen = a.plen;
+  const bool mfma = std::is_same<T, _Float16>::value && d / H == 32 && !a.scalar;
+  const bool fused_kvt = mfma && !a.split_scatter;
   if (!fused_kvt) GSV_LAUNCH(kv_scatter_kernel<T>, dim3(maxS, B), dim3(128), 0, s, qkv, row_off, x_len, plen, d, H, smax, kc, vc);
   if constexpr (std::is_same<T, _Float16>::value) {
     if (mfma) {
       const int spad = (maxS + 31) / 32 * 32;
-      _Float16* vt = (_Float16*)h->pf_vt;
+      _Float16* vt = (_Float16*)a.vt;
       if (fused_kvt)
         GSV_LAUNCH(prefill_kvt_kernel, dim3(spad / 32, H, B), dim3(256), 0, s, qkv, row_off, x_len, plen, d, H, smax, spad, kc, vc, vt);
       else
@@ -344,6 +355,49 @@ int prefill_attention(gsv_t2s* h, int li, int maxS, hipStream_t s) {
   GSV_LAUNCH((prefill_attn_kernel<T, 32>), dim3(cdiv(maxS, 64), H, B), dim3(64), 0, s, qkv, (const T*)kc, (const T*)vc, row_off,
              x_len, plen, d, H, smax, out);
   return GSV_OK;
+}
+
+// the engine's layer li: pf_qkv -> pf_attn, routes from GSV_SCALAR_PREFILL_ATTN / GSV_PREFILL_SPLIT_SCATTER
+template <typename T>
+int prefill_attention(gsv_t2s* h, int li, int maxS, hipStream_t s) {
+  PrefillAttnArgs a;
+  a.qkv = h->pf_qkv; a.kc = kv_ptr(h, li, 0); a.vc = kv_ptr(h, li, 1); a.vt = h->pf_vt; a.out = h->pf_attn;
+  a.row_off = h->d_row_off; a.x_len = h->d_x_len; a.plen = h->d_plen;
+  a.B = h->B; a.H = h->cfg.n_head; a.d = h->cfg.dim; a.smax = h->max_seq; a.maxS = maxS;
+  a.scalar = scalar_prefill_attn(); a.split_scatter = prefill_split_scatter();
+  return launch_prefill_attention<T>(a, s);
+}
+
+// gsv_op_prefill_attn: the row table of t2s_prefill_rows, scratch of its own, one launch_prefill_attention, wait, free
+template <typename T>
+int op_prefill_attn(PrefillAttnArgs a, const int32_t* x_len, const int32_t* p_len, hipStream_t s) {
+  const int B = a.B;
+  std::vector<int> tab(3 * (size_t)B);   // [row_off | x_len | plen]
+  int M = 0, maxS = 0;
+  for (int b = 0; b < B; ++b) {
+    const int S = x_len[b] + p_len[b];
+    tab[b] = M; tab[B + b] = x_len[b]; tab[2 * (size_t)B + b] = p_len[b];
+    M += S;
+    maxS = S > maxS ? S : maxS;
+  }
+  a.maxS = maxS;
+  int* d_tab = nullptr;
+  void* vt = nullptr;
+  int rc = GSV_OK;
+  if (hipMalloc((void**)&d_tab, tab.size() * 4) != hipSuccess) rc = GSV_ERR_HIP;
+  if (!rc && std::is_same<T, _Float16>::value && !a.scalar &&
+      hipMalloc(&vt, (size_t)B * a.H * 32 * ((maxS + 31) / 32 * 32) * 2) != hipSuccess)
+    rc = GSV_ERR_HIP;
+  if (!rc && hipMemcpy(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess) rc = GSV_ERR_HIP;
+  if (rc) set_error("op_prefill_attn: scratch allocation or upload failed");
+  if (!rc) {
+    a.row_off = d_tab; a.x_len = d_tab + B; a.plen = d_tab + 2 * (size_t)B; a.vt = vt;
+    rc = launch_prefill_attention<T>(a, s);
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) { set_error("op_prefill_attn: a kernel failed"); rc = GSV_ERR_HIP; }
+  }
+  (void)hipFree(vt);
+  (void)hipFree(d_tab);
+  return rc;
 }
 
 // Prefill of B rows with prompts of P_b = plen[b] tokens, packed back to back in `prompts` (device) from poff[b] on.
@@ -457,6 +511,32 @@ int gsv_t2s_prefill_ragged(gsv_t2s_t* h, const int32_t* phones, const int32_t* p
     poff[b] = o; o += prompt_lens[b];
   }
   return GSV_WITH_T(h, t2s_prefill_rows<T>(h, phones, phone_lens, B, bert, prompts_packed, prompt_lens, poff.data(), (hipStream_t)stream));
+}
+
+int gsv_op_prefill_attn(const void* qkv, const int32_t* x_len, const int32_t* p_len, int B, int H, int d, int smax, int dtype,
+                        int route, void* kc, void* vc, void* out, gsv_stream_t stream) {
+  GSV_REQUIRE(qkv && x_len && p_len && kc && vc && out, "op_prefill_attn: null pointer");
+  GSV_REQUIRE(dtype == GSV_F16 || dtype == GSV_F32, "op_prefill_attn: bad dtype %d", dtype);
+  GSV_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && H <= 65535 && smax >= 1, "op_prefill_attn: bad shape B=%d H=%d smax=%d", B, H, smax);
+  GSV_REQUIRE(d == 32 * H, "op_prefill_attn: d = %d is not 32 * H (H = %d): the kernels are built for head dim 32", d, H);
+  GSV_REQUIRE(route >= 0 && route <= 3, "op_prefill_attn: unknown route %d", route);
+  GSV_REQUIRE(dtype == GSV_F16 || route == 0 || route == 3, "op_prefill_attn: route %d (MFMA flash) is fp16 only", route);
+  long long M = 0;
+  for (int b = 0; b < B; ++b) {
+    GSV_REQUIRE(x_len[b] >= 1, "op_prefill_attn: empty phoneme sequence in row %d", b);
+    GSV_REQUIRE(p_len[b] >= 0, "op_prefill_attn: negative prompt length %d in row %d", p_len[b], b);
+    GSV_REQUIRE((long long)x_len[b] + p_len[b] + 2 <= smax, "op_prefill_attn: row %d needs %lld positions, smax is %d", b,
+                (long long)x_len[b] + p_len[b] + 2, smax);
+    M += x_len[b] + p_len[b];
+  }
+  GSV_REQUIRE(M <= 0x7fffffffLL, "op_prefill_attn: %lld packed rows", M);
+  PrefillAttnArgs a;
+  a.qkv = qkv; a.kc = kc; a.vc = vc; a.out = out;
+  a.B = B; a.H = H; a.d = d; a.smax = smax;
+  // route 0: the engine's own choice, its two process-wide switches included
+  a.scalar = route == 3 || (route == 0 && scalar_prefill_attn());
+  a.split_scatter = route == 2 || (route == 0 && prefill_split_scatter());
+  return GSV_WITH_DTYPE(dtype, op_prefill_attn<T>(a, x_len, p_len, (hipStream_t)stream));
 }
 
 }  // extern "C"

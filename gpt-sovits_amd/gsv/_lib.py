@@ -189,6 +189,8 @@ _SIGS = {
                                    C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p, C.c_int, C.c_void_p]),
     "gsv_op_decode_attn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.c_void_p, C.c_void_p]),
+    "gsv_op_prefill_attn": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsv_op_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                 C.POINTER(SamplingParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsv_op_sample_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(RowSampling),

@@ -459,6 +459,18 @@ int gsv_op_flash_rel96(const void* qkv, int T, int heads, float scale, const flo
  * out [dev] [B][H*32].  dtype GSV_F16 / GSV_F32 applies to q, kc, vc, out. */
 int gsv_op_decode_attn(const void* q, const void* kc, const void* vc, const int32_t* kv_len, const int32_t* active, int B, int H,
                        int smax, int dtype, void* out, gsv_stream_t stream);
+/* the AR prefill's K/V fill and attention alone (csrc/t2s_prefill.hip; mask of t2s_model.py:655-683: text queries see the text
+ * keys, audio queries all text keys plus the causal audio keys), through the routing code the engine itself launches with.  A
+ * test hook: it uploads the row table, allocates the V^T scratch, waits for the kernels and frees.  qkv [dev] [M][3*d], the
+ * rows of every utterance packed back to back ([x_0 .. x_{X_b-1} | y_0 .. y_{P_b-1}], M = sum S_b, S_b = x_len[b] + p_len[b]);
+ * x_len / p_len [host] int32 [B]; d = 32 * H; kc / vc [dev] [B][H][smax][32], written at positions j < S_b only; out [dev]
+ * [M][d].  dtype GSV_F16 / GSV_F32 applies to qkv, kc, vc, out.  route: 0 = what the engine takes for this dtype (the
+ * GSV_SCALAR_PREFILL_ATTN / GSV_PREFILL_SPLIT_SCATTER switches included), 1 = fused K/V + V^T launch, then the MFMA flash kernel
+ * (fp16 only), 2 = K/V scatter and V^T as two launches, then the flash kernel (fp16 only), 3 = K/V scatter + the scalar kernel.
+ * GSV_ERR_ARG before any launch: a null pointer, d != 32 * H, x_len[b] < 1, p_len[b] < 0, S_b + 2 > smax, route 1 / 2 with
+ * GSV_F32, an unknown route or dtype. */
+int gsv_op_prefill_attn(const void* qkv, const int32_t* x_len, const int32_t* p_len, int B, int H, int d, int smax, int dtype,
+                        int route, void* kc, void* vc, void* out, gsv_stream_t stream);
 /* channels-last conv1d: x [T_in][Cin], w [Cout][taps*Cin] (tap-major, cin fastest), y [T_out][Cout] */
 int gsv_op_conv1d(const gsv_conv_desc* d, int dtype, gsv_stream_t stream);
 /* test hook: which kernel instantiation the last gsv_op_conv1d / gsv_op_conv_pair / engine conv launch on this thread ran

@@ -1,5 +1,6 @@
 // Small shared kernels: error state, dtype conversion, row LayerNorm.
 #include "common.h"
+#include "engine.h"
 
 namespace gsv {
 
@@ -236,6 +237,52 @@ __global__ __launch_bounds__(1024) void time_mean_kernel(const float* __restrict
   }
 }
 
+// The packed speaker-embedding pass (ERes2NetV2.forward3_segments): the audios lie back to back on the time
+// axis, and these two kernels keep each to itself.
+// zero_rows: 0 to rows[0 .. n_rows) of n_maps maps [T][4 * pieces] (blockIdx.y = map), one thread per 16-byte piece.  The base
+// pointers are kernel arguments: no table in memory, one launch for the four sub-band maps of a block.
+__global__ __launch_bounds__(256) void zero_rows_kernel(gsv_zero_maps maps, int T, int pieces, const int* __restrict__ rows, int n_rows) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)n_rows * pieces) return;
+  const int r = (int)(i / pieces), p = (int)(i - (long long)r * pieces);
+  const int row = rows[r];
+  if (row < 0 || row >= T) return;             // the host checked its copy of the list; the device's own is not trusted further
+  f4* base = (f4*)maps.p[blockIdx.y];
+  base[(long long)row * pieces + p] = f4{0.f, 0.f, 0.f, 0.f};
+}
+
+// out[s][c] = mean over the rows of segment s of x[t][c], in time_mean_kernel's order counted from the segment's first row, so the
+// bits of a segment depend on its own rows alone.  A lane owns four adjacent columns (16-byte loads, a wave reads 1 KiB of a
+// row), a workgroup 256 columns x 16 time slices; tab: int4 per segment (first row, rows, -, -).
+__global__ __launch_bounds__(1024) void time_mean_seg_kernel(const float* __restrict__ x, int ld, const int4* __restrict__ tab,
+                                                             float* __restrict__ out) {
+  __shared__ float part[16][4][64];
+  const int lane = threadIdx.x & 63, sl = threadIdx.x >> 6;
+  const int c = blockIdx.x * 256 + lane * 4;
+  const int4 sg = tab[blockIdx.y];
+  const float* xs = x + (long long)sg.x * ld;
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+  if (c < ld)
+    for (int t = sl; t < sg.y; t += 16) {
+      const f4 v = *(const f4*)(xs + (long long)t * ld + c);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[j] += v[j];
+    }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) part[sl][j][lane] = s[j];
+  __syncthreads();
+  if (sl == 0 && c < ld) {
+    f4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float v = 0.f;
+      for (int k = 0; k < 16; ++k) v += part[k][j][lane];
+      o[j] = v / (float)sg.y;
+    }
+    *(f4*)(out + (long long)blockIdx.y * ld + c) = o;
+  }
+}
+
 // y[t][c] = act((x[t][c] - mean_c) * rstd_c * gamma[c] + beta[c]), statistics over t (biased variance), channels-last.
 // Two kernels: per-(channel block, time slice) partial sums -> finalize + apply.
 template <typename T>
@@ -416,6 +463,48 @@ int gsv_op_time_mean(const float* x, int T, int ld, float* out, gsv_stream_t str
   hipLaunchKernelGGL(gsv::time_mean_kernel, dim3(gsv::cdiv(ld, 64)), dim3(1024), 0, (hipStream_t)stream, x, T, ld, out);
   GSV_HIP(hipGetLastError());
   return GSV_OK;
+}
+
+int gsv_op_zero_rows(const gsv_zero_maps* maps, int n_maps, int T, int ld, const int32_t* rows, const int32_t* rows_host, int n_rows,
+                     gsv_stream_t stream) {
+  GSV_REQUIRE(maps && rows && rows_host && T > 0 && ld > 0 && n_rows >= 0, "op_zero_rows: bad argument");
+  GSV_REQUIRE(n_maps >= 1 && n_maps <= 8, "op_zero_rows: %d maps (1 .. 8)", n_maps);
+  GSV_REQUIRE(ld % 4 == 0, "op_zero_rows: ld = %d must be a multiple of 4 floats", ld);
+  for (int i = 0; i < n_maps; ++i)
+    GSV_REQUIRE(maps->p[i] && ((uintptr_t)maps->p[i] % 16) == 0, "op_zero_rows: map %d is null or not 16-byte aligned", i);
+  for (int i = 0; i < n_rows; ++i)
+    GSV_REQUIRE(rows_host[i] >= 0 && rows_host[i] < T, "op_zero_rows: row %d (entry %d) is outside [0, %d)", rows_host[i], i, T);
+  if (n_rows == 0) return GSV_OK;
+  const int pieces = ld / 4;
+  const long long blocks = ((long long)n_rows * pieces + 255) / 256;
+  GSV_REQUIRE(blocks <= 0x7fffffffLL, "op_zero_rows: %d rows of %d floats are too many for one launch", n_rows, ld);
+  GSV_LAUNCH(gsv::zero_rows_kernel, dim3((unsigned)blocks, n_maps), dim3(256), 0, (hipStream_t)stream, *maps, T, pieces, rows, n_rows);
+  return GSV_OK;
+}
+
+int gsv_op_time_mean_seg(const float* x, int T, int ld, int n_seg, const int32_t* seg_start, const int32_t* seg_len, float* out,
+                         gsv_stream_t stream) {
+  GSV_REQUIRE(x && out && seg_start && seg_len && T > 0 && ld > 0, "op_time_mean_seg: bad argument");
+  GSV_REQUIRE(n_seg >= 1 && n_seg <= gsveng::kSegTableMax, "op_time_mean_seg: %d segments (1 .. %d)", n_seg, gsveng::kSegTableMax);
+  GSV_REQUIRE(ld % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0,
+              "op_time_mean_seg: ld = %d must be a multiple of 4 and x / out 16-byte aligned", ld);
+  long long end = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    GSV_REQUIRE(seg_len[i] >= 1, "op_time_mean_seg: segment %d has length %d", i, seg_len[i]);
+    GSV_REQUIRE(seg_start[i] >= end, "op_time_mean_seg: segment %d starts at row %d, before row %lld where the one before it ends "
+                "(segments are disjoint and ascending)", i, seg_start[i], end);
+    end = (long long)seg_start[i] + seg_len[i];
+    GSV_REQUIRE(end <= T, "op_time_mean_seg: segment %d ends at row %lld of %d", i, end, T);
+  }
+  gsveng::SegTable tb;                              // holds the library context until it goes out of scope
+  GSV_RC(gsveng::seg_table_begin(&tb));
+  for (int i = 0; i < n_seg; ++i) {
+    tb.image[4 * i] = seg_start[i]; tb.image[4 * i + 1] = seg_len[i]; tb.image[4 * i + 2] = 0; tb.image[4 * i + 3] = 0;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  GSV_RC(gsveng::seg_table_upload(&tb, n_seg, s));
+  GSV_LAUNCH(gsv::time_mean_seg_kernel, dim3(gsv::cdiv(ld, 256), n_seg), dim3(1024), 0, s, x, ld, (const int4*)tb.dev, out);
+  return gsveng::seg_table_end(&tb, s);
 }
 
 int gsv_op_channel_norm(const void* x, int T, int C, const float* gamma, const float* beta, float eps, int act, float* scratch,

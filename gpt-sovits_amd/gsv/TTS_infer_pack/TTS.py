@@ -500,15 +500,25 @@ class TTS:
         self._set_ref_spec(ref_audio_path)
         self.prompt_cache["ref_audio_path"] = ref_audio_path
 
-    def _set_ref_spec(self, ref_audio_path: str):
-        spec_audio = self._get_ref_spec(ref_audio_path)
+    def _ref_spec_or_handed(self, path: str, handed: Optional[dict]):
+        """_get_ref_spec(path) and its speaker embedding (None: not computed yet), or, with `handed` (make_voices(shared_sv=True):
+        path -> what _get_ref_spec returned and left in the prompt cache, plus the embedding of the shared pass), that entry"""
+        if handed is None or path not in handed:
+            return self._get_ref_spec(path), None
+        h = handed[path]
+        self.prompt_cache.update(raw_audio=h["raw_audio"], raw_sr=h["raw_sr"], ref_mel=None)
+        return h["spec_audio"], h["sv_emb"]
+
+    def _set_ref_spec(self, ref_audio_path: str, handed: Optional[dict] = None):
+        spec_audio, emb = self._ref_spec_or_handed(ref_audio_path, handed)
         if self.prompt_cache["refer_spec"] in [[], None]:
             self.prompt_cache["refer_spec"] = [spec_audio]
         else:
             self.prompt_cache["refer_spec"][0] = spec_audio
         if spec_audio[1] is not None:
             # the reference recomputes the embedding inside every run() (TTS.py:1233-1238); it only depends on the reference audio
-            emb = self.sv_model.compute_embedding3(spec_audio[1])
+            if emb is None:
+                emb = self.sv_model.compute_embedding3(spec_audio[1])
             cur = self.prompt_cache.get("sv_emb")
             if cur:
                 cur[0] = emb
@@ -892,9 +902,10 @@ class TTS:
                                            C.c_void_p(st.cuda_stream)), "gsv_sola")
         return out[:n_out.value].to(dt)
 
-    def _prepare_prompt(self, inputs: dict) -> None:
+    def _prepare_prompt(self, inputs: dict, handed: Optional[dict] = None) -> None:
         """run()'s reference-audio / prompt-text handling (reference TTS.py:1078-1120): brings self.prompt_cache up to date
-        with the request's ref_audio_path, aux_ref_audio_paths and prompt_text / prompt_lang."""
+        with the request's ref_audio_path, aux_ref_audio_paths and prompt_text / prompt_lang.  `handed`: spectrograms and
+        speaker embeddings computed ahead for the auxiliary references (_ref_spec_or_handed)."""
         ref_audio_path = inputs.get("ref_audio_path")
         prompt_text, prompt_lang = inputs.get("prompt_text"), inputs.get("prompt_lang", "")
         if ref_audio_path in [None, ""] and inputs.get("segments") is None and "text" in inputs and (
@@ -921,10 +932,10 @@ class TTS:
                 if not os.path.exists(path):
                     print("音频文件不存在，跳过：", path)
                     continue
-                spec_audio = self._get_ref_spec(path)
+                spec_audio, emb = self._ref_spec_or_handed(path, handed)
                 self.prompt_cache["refer_spec"].append(spec_audio)
                 if spec_audio[1] is not None:
-                    self.prompt_cache["sv_emb"].append(self.sv_model.compute_embedding3(spec_audio[1]))
+                    self.prompt_cache["sv_emb"].append(self.sv_model.compute_embedding3(spec_audio[1]) if emb is None else emb)
             self.vits_model.invalidate_refer()
         if prompt_text not in [None, ""]:
             from .text_segmentation_method import splits
@@ -1099,14 +1110,17 @@ class TTS:
 
     voice_cache_size = 8
 
-    def make_voices(self, specs: Sequence[dict]) -> List[dict]:
+    def make_voices(self, specs: Sequence[dict], shared_sv: bool = False) -> List[dict]:
         """make_voice(ref_audio_path=..., prompt_text=..., prompt_lang=..., aux_ref_audio_paths=...) for many specs (dicts of
         those keywords) with ONE packed HuBERT pass (HubertModel.batch) and one extract_latent_many over the reference audios
         that the voice LRU does not hold; every distinct ref_audio_path is loaded and encoded once.  The spectrogram, speaker
         embedding, auxiliary references and prompt text of each voice are computed by the code make_voice runs.  Returns one
         voice per spec, in order -- all of them, also when there are more than voice_cache_size; every new voice enters the
         LRU, which evicts as make_voice's does.  A missing file (ValueError) or a prompt outside 3..10 s (OSError) is raised
-        before any device work.  self.prompt_cache is not changed."""
+        before any device work.  self.prompt_cache is not changed.
+        shared_sv=True (v2Pro / v2ProPlus; nothing changes on another model): the reference spectrograms of every distinct main
+        and auxiliary path of the missing voices are computed first, then ONE SV.compute_embedding3_many runs over their 16 kHz
+        audios (packed ERes2NetV2 passes) instead of one encoder pass per reference; the voices take their embeddings from it."""
         lru = self.__dict__.setdefault("_voice_lru", collections.OrderedDict())
         keys, out, missing = [], {}, []
         for spec in specs:
@@ -1140,6 +1154,7 @@ class TTS:
             feats = self.cnhuhbert_model.model.batch([torch.from_numpy(wavs[p]) for p in paths])
             codes = dict(zip(paths, self.vits_model.extract_latent_many([f.transpose(1, 2) for f in feats])))
             spec_of = {key: spec for key, spec in zip(keys, specs)}
+            handed = self._shared_sv_refs(missing) if shared_sv else None
             for key in missing:
                 path, spec = key[0], spec_of[key]
                 req = {"ref_audio_path": path, "prompt_text": spec.get("prompt_text"), "prompt_lang": spec.get("prompt_lang", "")}
@@ -1149,24 +1164,44 @@ class TTS:
                     # set_ref_audio with the codes handed in; _prepare_prompt then finds the path current and goes on to the
                     # auxiliary references and the prompt text
                     self._set_prompt_semantic(path, codes=codes[path], wav16k=wavs[path])
-                    self._set_ref_spec(path)
+                    self._set_ref_spec(path, handed)
                     pc["ref_audio_path"] = path
-                    self._prepare_prompt(req)
+                    self._prepare_prompt(req, handed)
                 out[key] = lru[key] = {k: pc.get(k) for k in self._VOICE_KEYS}
                 while len(lru) > self.voice_cache_size:
                     lru.popitem(last=False)
         return [out[key] for key in keys]
 
-    def _with_shared_voices(self, requests: List[dict]) -> List[dict]:
-        """run_batch(shared_hubert=True): the requests that name a ref_audio_path and bring no `voice` get theirs from ONE
-        make_voices call, each returned as a copy with its `voice` filled in; the others pass through"""
+    def _shared_sv_refs(self, missing) -> Optional[dict]:
+        """make_voices(shared_sv=True): path -> dict(spec_audio, raw_audio, raw_sr, sv_emb) for every distinct main and auxiliary
+        reference of the `missing` voice keys that make_voice would read, the embeddings from one compute_embedding3_many;
+        None on a model without speaker embeddings"""
+        if not (getattr(self.vits_model, "is_v2pro", False) or self.configs.version in ("v2Pro", "v2ProPlus")):
+            return None
+        paths = []
+        for key in missing:
+            for path in (key[0],) + tuple(p for p in key[3] if p not in [None, ""] and os.path.exists(p)):
+                if path not in paths:
+                    paths.append(path)
+        handed = {}
+        for path in paths:
+            with self._with_prompt_cache(self._empty_prompt_cache()) as pc:
+                handed[path] = dict(spec_audio=self._get_ref_spec(path), raw_audio=pc["raw_audio"], raw_sr=pc["raw_sr"])
+        embs = self.sv_model.compute_embedding3_many([handed[p]["spec_audio"][1] for p in paths])
+        for path, emb in zip(paths, embs):
+            handed[path]["sv_emb"] = emb
+        return handed
+
+    def _with_shared_voices(self, requests: List[dict], shared_sv: bool = False) -> List[dict]:
+        """run_batch(shared_hubert=True / shared_sv=True): the requests that name a ref_audio_path and bring no `voice` get
+        theirs from ONE make_voices call, each returned as a copy with its `voice` filled in; the others pass through"""
         todo = [i for i, req in enumerate(requests) if req.get("voice") is None and req.get("ref_audio_path") not in [None, ""]]
         out = list(requests)
         if todo:
             specs = [{"ref_audio_path": requests[i]["ref_audio_path"], "prompt_text": requests[i].get("prompt_text"),
                       "prompt_lang": requests[i].get("prompt_lang", ""),
                       "aux_ref_audio_paths": requests[i].get("aux_ref_audio_paths")} for i in todo]
-            for i, voice in zip(todo, self.make_voices(specs)):
+            for i, voice in zip(todo, self.make_voices(specs, shared_sv=shared_sv)):
                 out[i] = dict(requests[i], voice=voice)
         return out
 
@@ -1569,7 +1604,7 @@ class TTS:
     def run_batch(self, requests: List[dict], shared_sovits: bool = False, shared_cfm: bool = False,
                   shared_speed: bool = False, mixed_sampling: bool = False,
                   shared_vocoder: bool = False, shared_bert: bool = False,
-                  shared_hubert: bool = False) -> List[Tuple[int, np.ndarray]]:
+                  shared_hubert: bool = False, shared_sv: bool = False) -> List[Tuple[int, np.ndarray]]:
         """Several requests, each with its own reference voice, through shared AR decodes.  Each request dict takes the
         keys run() accepts plus an optional "voice" (make_voice); without one it uses its ref_audio_path / prompt_text
         (through make_voice's LRU) or the current prompt cache.  Returns one (sr, int16 audio) per request, in order: what
@@ -1591,6 +1626,8 @@ class TTS:
         shared_hubert=True: the requests that name a `ref_audio_path` and bring no `voice` get their voices from one make_voices
         call before planning: one packed HuBERT pass over the reference audios the voice LRU does not hold, instead of one
         pass per voice.
+        shared_sv=True (implies the make_voices route of shared_hubert): on a v2Pro / v2ProPlus model those voices also take their
+        speaker embeddings, main and auxiliary, from one packed ERes2NetV2 pass (make_voices(shared_sv=True)).
         No keyword changes anything for the other model family."""
         if self.t2s_model is None or self.vits_model is None:
             raise RuntimeError("init_t2s_weights / init_vits_weights first")
@@ -1599,8 +1636,8 @@ class TTS:
         self.stop_flag = False
         if shared_bert:
             requests = self._with_shared_segments(requests)
-        if shared_hubert:
-            requests = self._with_shared_voices(requests)
+        if shared_hubert or shared_sv:
+            requests = self._with_shared_voices(requests, shared_sv=shared_sv)
         plans = [self._plan_request(req) for req in requests]
         self._ar_stage(plans, mixed_sampling=mixed_sampling)
         sr = self._output_sr()

@@ -64,6 +64,11 @@ class ConvDesc(C.Structure):
                 ("res_dtype", C.c_int), ("y_col0", C.c_int), ("w_nt", C.c_int), ("z_res", C.c_int)]
 
 
+class ZeroMaps(C.Structure):
+    """gsv_zero_maps: the base pointers of the maps one gsv_op_zero_rows launch covers"""
+    _fields_ = [("p", C.c_void_p * 8)]
+
+
 _SIGS = {
     "gsv_init": (C.c_int, [C.c_int]),
     "gsv_last_error": (C.c_char_p, []),
@@ -183,6 +188,9 @@ _SIGS = {
     "gsv_op_channel_norm_seg": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
                                           C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "gsv_op_gather_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "gsv_op_zero_rows": (C.c_int, [C.POINTER(ZeroMaps), C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p]),
+    "gsv_op_time_mean_seg": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
+                                       C.c_void_p]),
     "gsv_op_layernorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                    C.c_float, C.c_int, C.c_void_p]),
     "gsv_op_lora_delta": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int,

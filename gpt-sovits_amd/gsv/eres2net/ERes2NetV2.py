@@ -9,6 +9,11 @@ zero rows supply the frequency padding.  1 x 1 convs are the same call with taps
 bias at load time; channel concatenations never materialise (a conv over cat(a, b) is two calls chained through the residual
 input); the clipped ReLU, SiLU and tanh are GEMM epilogues.  The only non-GEMM kernels are the AFF mix and the final time mean.
 fp32 throughout (exact-f32 MFMA): this runs once per reference audio, not per synthesis step.
+
+Many audios (`forward3_segments`): time-major maps let the audios of a pass lie back to back on the time axis
+with gap rows between them (`plan_segments`); the launches above then run once over all of them, `gsv_op_zero_rows` puts zeros
+into the gap rows of every map a conv over time reads next, and `gsv_op_time_mean_seg` averages each audio's own rows.  `forward3`
+and its launches are unchanged.
 """
 from __future__ import annotations
 
@@ -22,13 +27,98 @@ from .. import _lib
 
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SILU, ACT_RELU20 = 0, 1, 2, 6, 11          # csrc/common.h
 
+N_LEVELS = 4                     # time resolutions of the network: T, T / 2, T / 4, T / 8 (layer strides 1, 2, 2, 2)
+SLOT_ALIGN = 1 << (N_LEVELS - 1)
+# slot frames of one packed pass, from the sweep of tools/sv_enrol_bench.py on the 32 x 10 s job: 286 ms
+# and 3.2 GB of workspace (0.4 MB per slot frame) here; 4096 is 23 % slower, 32768 (one pass) 18 % faster for 11.1 GB.
+DEFAULT_MAX_FRAMES = 8192
+
+
+def plan_segments(frame_counts, max_frames: int = DEFAULT_MAX_FRAMES, row_elems: int = 82 * 256):
+    """The packed layout of forward3_segments.  Audio s with m_s = frame_counts[s] fbank frames gets a slot
+    of 8 * (ceil(m_s / 8) + 1) frames, the slots stand back to back in the order given, and a pass takes slots while their sum
+    stays within `max_frames` (an audio whose own slot is larger gets a pass to itself).  A slot starts on a multiple of 8, so
+    at level k (rows of 2^k frames, k = 0 .. 3) audio s covers the ceil(m_s / 2^k) rows from slot_start_s / 2^k and at least
+    one gap row follows it: a 3-tap conv over time with pad 1 and a stride-2 conv (output row o / 2 + t reads input rows
+    o + 2t - 1 .. o + 2t + 1) then read what they read for the audio alone, given zeros in the gap rows.
+    `row_elems`: elements per frame of the largest map; frames * row_elems stays below 2^31 whatever max_frames says.
+    Returns one dict per pass: audios (indices into frame_counts), m, slot_start, frames (sum of the slots), levels[k] = dict(rows,
+    seg_start, seg_len, gap_rows).  A frame count below 1 (an audio shorter than one 400-sample window) is a ValueError."""
+    counts = [int(m) for m in frame_counts]
+    for s, m in enumerate(counts):
+        if m < 1:
+            raise ValueError(f"audio {s} has no fbank frame (shorter than the 400-sample window)")
+    if int(max_frames) < 1:
+        raise ValueError(f"max_frames = {max_frames}")
+    cap = ((1 << 31) - 1) // int(row_elems) // SLOT_ALIGN * SLOT_ALIGN
+    limit = min(int(max_frames), cap)
+    groups, cur, used = [], [], 0
+    for s, m in enumerate(counts):
+        slot = SLOT_ALIGN * (-(-m // SLOT_ALIGN) + 1)
+        if slot > cap:
+            raise ValueError(f"audio {s}: {m} frames make a map of {slot * row_elems} elements, 2^31 or more")
+        if cur and used + slot > limit:
+            groups.append(cur)
+            cur, used = [], 0
+        cur.append((s, m, slot))
+        used += slot
+    if cur:
+        groups.append(cur)
+    passes = []
+    for g in groups:
+        starts, pos = [], 0
+        for _, _, slot in g:
+            starts.append(pos)
+            pos += slot
+        levels = []
+        for k in range(N_LEVELS):
+            seg_start = [o >> k for o in starts]
+            seg_len = [-(-m // (1 << k)) for _, m, _ in g]
+            inside = set()
+            for a, n in zip(seg_start, seg_len):
+                inside.update(range(a, a + n))
+            levels.append(dict(rows=pos >> k, seg_start=seg_start, seg_len=seg_len,
+                               gap_rows=[r for r in range(pos >> k) if r not in inside]))
+        passes.append(dict(audios=[s for s, _, _ in g], m=[m for _, m, _ in g], slot_start=starts, frames=pos, levels=levels))
+    return passes
+
+
+class _Gaps:
+    """the gap rows of one packed pass on the device and on the host, per level, keyed by the level's row count"""
+
+    def __init__(self, levels, device):
+        flat = [r for lv in levels for r in lv["gap_rows"]]
+        self.dev = torch.tensor(flat, dtype=torch.int32).to(device)
+        self.by_rows, off = {}, 0
+        for lv in levels:
+            n = len(lv["gap_rows"])
+            self.by_rows[lv["rows"]] = (self.dev.data_ptr() + 4 * off, (C.c_int32 * n)(*lv["gap_rows"]), n)
+            off += n
+
+
+class _Arena:
+    """one zero-filled allocation that the maps of a block of the packed pass are carved from: one fill instead of one per map"""
+
+    def __init__(self, numel: int, device):
+        self.buf, self.off = torch.zeros(numel, dtype=torch.float32, device=device), 0
+
+    def take(self, *shape) -> torch.Tensor:
+        n = math.prod(shape)
+        if self.off + n > self.buf.numel():
+            raise RuntimeError("the block's arena is smaller than its maps")
+        self.off += n
+        return self.buf[self.off - n:self.off].view(*shape)
+
 
 class _Map:
     """feature map [T][F + 2][C] fp32 (rows 0 and F + 1 of the frequency axis stay zero)"""
 
-    def __init__(self, T: int, Fq: int, Cn: int, device, zero: bool = True):
+    def __init__(self, T: int, Fq: int, Cn: int, device, zero: bool = True, arena: Optional[_Arena] = None):
         self.T, self.F, self.C = T, Fq, Cn
-        self.t = (torch.zeros if zero else torch.empty)(T, Fq + 2, Cn, dtype=torch.float32, device=device)
+        if arena is not None:
+            self.t = arena.take(T, Fq + 2, Cn)
+        else:
+            self.t = (torch.zeros if zero else torch.empty)(T, Fq + 2, Cn, dtype=torch.float32, device=device)
 
     @property
     def ld(self):
@@ -40,11 +130,16 @@ class _Map:
 
 class ERes2NetV2:
     def __init__(self, state_dict: Optional[Dict[str, torch.Tensor]] = None, device="cuda:0", m_channels: int = 64, feat_dim: int = 80,
-                 baseWidth: int = 26, scale: int = 2, expansion: int = 2, num_blocks=(3, 4, 6, 3), **unused):
+                 baseWidth: int = 26, scale: int = 2, expansion: int = 2, num_blocks=(3, 4, 6, 3),
+                 max_frames: int = DEFAULT_MAX_FRAMES, **unused):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("the gsv ERes2NetV2 engine runs on an MI355X (cuda/HIP device) only")
         self.m_channels, self.feat_dim, self.baseWidth, self.scale, self.expansion = m_channels, feat_dim, baseWidth, scale, expansion
+        self.max_frames = int(max_frames)          # slot frames per packed pass (forward3_segments)
+        # counters the tests read: library launches issued by this object, per-audio passes (_one), packed passes
+        self.launches = self.one_passes = self.seg_passes = 0
+        self._arena: Optional[_Arena] = None       # set while a block of the packed pass runs
         self.plan = []
         in_planes = m_channels
         for li, (planes, nb, stride) in enumerate(zip((m_channels, 2 * m_channels, 4 * m_channels, 8 * m_channels), num_blocks, (1, 2, 2, 2)), 1):
@@ -140,13 +235,27 @@ class ERes2NetV2:
         if Z > 1:
             d.Z, d.xz, d.wz, d.yz, d.bz = Z, xz, 0, yz, 0
         _lib.check(_lib.lib().gsv_op_conv1d(C.byref(d), _lib.GSV_F32, st), "gsv_op_conv1d")
+        self.launches += 1
+
+    def _zero_gaps(self, st, gaps: Optional[_Gaps], maps):
+        """packed pass: 0 into the gap rows of `maps` (same shape, up to 8), which a conv over time reads next"""
+        if gaps is None:
+            return
+        ts = [m.t if isinstance(m, _Map) else m for m in maps]
+        T, ld = int(ts[0].shape[0]), ts[0][0].numel()
+        rows_dev, rows_host, n = gaps.by_rows[T]
+        zm = _lib.ZeroMaps()
+        for i, t in enumerate(ts):
+            zm.p[i] = t.data_ptr()
+        _lib.check(_lib.lib().gsv_op_zero_rows(C.byref(zm), len(ts), T, ld, rows_dev, rows_host, n, st), "gsv_op_zero_rows")
+        self.launches += 1
 
     def _conv3x3(self, st, x: _Map, name: str, Cout: int, stride: int, act: int, out: Optional[_Map] = None, res: bool = False,
                  bias: bool = True) -> _Map:
         """Conv2d(C, Cout, 3, padding=1, stride) (+ folded BN, + activation); res: add what `out` already holds before the activation"""
         T_out, F_out = (x.T - 1) // stride + 1, (x.F - 1) // stride + 1
         if out is None:
-            out = _Map(T_out, F_out, Cout, self.device)
+            out = _Map(T_out, F_out, Cout, self.device, arena=self._arena)
         w = self.w[name + ".w"]
         self._gemm(st, x.t.data_ptr(), x.ld, x.T, 3 * x.C, w, 0, 9 * x.C, Cout, out.interior(), out.ld, T_out, taps=3, stride=stride, pad=1,
                    bias=self.w[name + ".b"] if bias else None, act=act, res_ptr=out.interior() if res else None, Z=F_out,
@@ -167,24 +276,40 @@ class ERes2NetV2:
     def _aff(self, st, p: str, x: _Map, y: _Map) -> _Map:
         """fusion.py:22-27: t = tanh(BN(conv(silu(BN(conv(cat(x, y))))))); x (1 + t) + y (1 - t)"""
         Cn, inter = x.C, x.C // 4
-        h = _Map(x.T, x.F, inter, self.device, zero=False)
-        t = _Map(x.T, x.F, Cn, self.device)                          # zero rows stay finite for the whole-row mix below
-        out = _Map(x.T, x.F, Cn, self.device)
+        h = _Map(x.T, x.F, inter, self.device, zero=False, arena=self._arena)
+        t = _Map(x.T, x.F, Cn, self.device, arena=self._arena)       # zero rows stay finite for the whole-row mix below
+        out = _Map(x.T, x.F, Cn, self.device, arena=self._arena)
         self._conv1x1(st, x, p + ".a", inter, h, bias=False, cin_off=0, cin=Cn)
         self._conv1x1(st, y, p + ".a", inter, h, act=ACT_SILU, res_ptr=h.interior(), cin_off=Cn, cin=Cn)
         self._conv1x1(st, h, p + ".b", Cn, t, act=ACT_TANH)
         # the mix runs over whole rows, zero frequency rows included: they hold 0 in x, y and t, so 0 comes out
         _lib.check(_lib.lib().gsv_op_aff_mix(x.t.data_ptr(), y.t.data_ptr(), t.t.data_ptr(), x.t.numel(), out.t.data_ptr(), st), "gsv_op_aff_mix")
+        self.launches += 1
         return out
 
-    def _block(self, st, x: _Map, blk) -> _Map:
+    def _block(self, st, x: _Map, blk, gaps: Optional[_Gaps] = None) -> _Map:
+        if gaps is None:
+            return self._block_maps(st, x, blk, None)
+        # packed pass: every map of the block from one zero fill (sub-bands, 3 x 3 outputs, the AFF's three maps, the output)
+        s, wd = blk["stride"], blk["width"]
+        per = ((x.T - 1) // s + 1) * ((x.F - 1) // s + 3)
+        chans = 2 * self.scale * wd + blk["planes"] + ((self.scale - 1) * (wd // 4 + 2 * wd) if blk["fuse"] else 0)
+        self._arena = _Arena(per * chans, self.device)
+        try:
+            return self._block_maps(st, x, blk, gaps)
+        finally:
+            self._arena = None
+
+    def _block_maps(self, st, x: _Map, blk, gaps: Optional[_Gaps]) -> _Map:
         p, s, wd = blk["p"], blk["stride"], blk["width"]
         T2, F2 = (x.T - 1) // s + 1, (x.F - 1) // s + 1
         spx = []
         for i in range(self.scale):                                  # conv1 + bn1 + clipped ReLU, one map per sub-band
-            m = _Map(T2, F2, wd, self.device)
+            m = _Map(T2, F2, wd, self.device, arena=self._arena)
             self._conv1x1(st, x, p + ".conv1", wd, m, stride=s, act=ACT_RELU20, cout_off=i * wd)
             spx.append(m)
+        for i in range(0, self.scale, 8):
+            self._zero_gaps(st, gaps, spx[i:i + 8])
         outs, sp = [], None
         for i in range(self.scale):
             name = p + f".convs.{i}"
@@ -195,8 +320,10 @@ class ERes2NetV2:
             else:                                                    # conv(sp + spx[i]) = conv(sp) + conv(spx[i])
                 o = self._conv3x3(st, sp, name, wd, 1, ACT_NONE, bias=False)
                 sp = self._conv3x3(st, spx[i], name, wd, 1, ACT_RELU20, out=o, res=True)
+            if i < self.scale - 1:                                   # the next sub-band's 3 x 3 conv reads it (through the AFF mix
+                self._zero_gaps(st, gaps, [sp])                      # where there is one: 0 where both its inputs are)
             outs.append(sp)
-        out = _Map(T2, F2, blk["planes"], self.device)
+        out = _Map(T2, F2, blk["planes"], self.device, arena=self._arena)
         if blk["shortcut"]:
             self._conv1x1(st, x, p + ".shortcut", blk["planes"], out, stride=s)
             first_res = out.interior()
@@ -221,22 +348,99 @@ class ERes2NetV2:
             st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             return torch.stack([self._one(st, f) for f in x.to(self.device, torch.float32)])
 
-    def _one(self, st, feat: torch.Tensor) -> torch.Tensor:
+    def _trunk(self, st, feat: torch.Tensor, gaps: Optional[_Gaps] = None) -> _Map:
+        """feat [T, feat_dim] -> the fused layer3 / layer4 map at T / 8; `gaps`: the packed pass, which zeroes the gap rows of every
+        map in front of a conv that reads across time"""
         T, Fq, Cm = int(feat.shape[0]), self.feat_dim, self.m_channels
-        xin = torch.zeros(T, self.stem_ld, dtype=torch.float32, device=self.device)
+        ends = None
+        if gaps is not None:                                        # packed pass: the maps outside the blocks from one zero fill
+            T8, F8, C4 = T >> (N_LEVELS - 1), (Fq - 1) // (1 << (N_LEVELS - 1)) + 3, self.plan[-1]["planes"]
+            ends = _Arena(T * self.stem_ld + T * (Fq + 2) * Cm + T8 * F8 * (3 * C4 + C4 // 4), self.device)
+        xin = ends.take(T, self.stem_ld) if ends else torch.zeros(T, self.stem_ld, dtype=torch.float32, device=self.device)
         xin[:, 1:Fq + 1] = feat
-        out = _Map(T, Fq, Cm, self.device)
+        self._zero_gaps(st, gaps, [xin])                            # frames past an audio's last one read into its neighbour
+        out = _Map(T, Fq, Cm, self.device, arena=ends)
         self._gemm(st, xin.data_ptr(), self.stem_ld, T, self.stem_ld, self.w["stem.w"], 0, 3 * self.stem_ld, Fq * Cm, out.interior(), out.ld, T,
                    taps=3, stride=1, pad=1, bias=self.w["stem.b"], act=ACT_RELU)
         out3 = None
         for blk in self.plan:
-            out = self._block(st, out, blk)
+            out = self._block(st, out, blk, gaps)
             if blk["last3"]:
                 out3 = out
-        out3_ds = self._conv3x3(st, out3, "layer3_ds", out.C, 2, ACT_NONE)
-        if (out3_ds.T, out3_ds.F) != (out.T, out.F):
-            raise RuntimeError("layer3_ds and layer4 disagree on the map size")
-        fused = self._aff(st, "fuse34", out, out3_ds)
+        self._zero_gaps(st, gaps, [out3])
+        self._arena = ends
+        try:
+            out3_ds = self._conv3x3(st, out3, "layer3_ds", out.C, 2, ACT_NONE)
+            if (out3_ds.T, out3_ds.F) != (out.T, out.F):
+                raise RuntimeError("layer3_ds and layer4 disagree on the map size")
+            return self._aff(st, "fuse34", out, out3_ds)
+        finally:
+            self._arena = None
+
+    def _one(self, st, feat: torch.Tensor) -> torch.Tensor:
+        self.one_passes += 1
+        fused = self._trunk(st, feat)
         mean = torch.empty(fused.ld, dtype=torch.float32, device=self.device)
         _lib.check(_lib.lib().gsv_op_time_mean(fused.t.data_ptr(), fused.T, fused.ld, mean.data_ptr(), st), "gsv_op_time_mean")
+        self.launches += 1
         return mean.view(fused.F + 2, fused.C)[1:-1].t().reshape(-1)                # (c, f) order of flatten(1, 2)
+
+    # ---- packed pass (DESIGN.md section 4l) ------------------------------------------------------------------------
+    def plan_segments(self, frame_counts, max_frames: Optional[int] = None):
+        return plan_segments(frame_counts, self.max_frames if max_frames is None else max_frames,
+                             (self.feat_dim + 2) * self.m_channels * self.expansion)
+
+    @torch.no_grad()
+    def forward3_segments(self, feats, plan=None, max_frames: Optional[int] = None) -> torch.Tensor:
+        """forward3 for many audios of different lengths in packed passes: the audios of a pass lie back to back on the time axis
+        (plan_segments), every launch of the network runs once over all of them, gsv_op_zero_rows keeps zeros between them
+        wherever a conv reads across time, and gsv_op_time_mean_seg averages each audio's own rows.  The launches of a pass do
+        not depend on the number of audios in it, and nothing waits for the device.
+        feats: a list of [m_s, feat_dim] feature tensors (plan=None: planned here with `max_frames`, default self.max_frames), or,
+        with `plan` (plan_segments' result), one packed [frames, feat_dim] matrix per pass, audio s at rows slot_start_s (what
+        lies in the other rows is ignored).  Returns [n, 20480]-shaped fp32, rows in the order of the plan's audio indices."""
+        if not self._loaded:
+            raise RuntimeError("load_state_dict() first")
+        feats = list(feats)
+        if plan is None:
+            for f in feats:
+                if f.dim() != 2 or f.shape[1] != self.feat_dim:
+                    raise ValueError(f"expected [m, {self.feat_dim}] features, got {tuple(f.shape)}")
+            plan = self.plan_segments([int(f.shape[0]) for f in feats], max_frames)
+            packed = None
+        else:
+            if len(feats) != len(plan) or any(f.dim() != 2 or tuple(f.shape) != (ps["frames"], self.feat_dim) for f, ps in zip(feats, plan)):
+                raise ValueError("with a plan, feats is one packed [frames, feat_dim] matrix per pass")
+            packed = feats
+        n = sum(len(ps["audios"]) for ps in plan)
+        if n == 0:
+            raise ValueError("no audio")
+        l = _lib.lib()
+        with torch.cuda.device(self.device):
+            _lib.init(self.device.index if self.device.index is not None else torch.cuda.current_device())
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            means = []
+            for pi, ps in enumerate(plan):
+                if packed is not None:
+                    x = packed[pi].to(self.device, torch.float32)
+                else:
+                    x = torch.zeros(ps["frames"], self.feat_dim, dtype=torch.float32, device=self.device)
+                    for s, o, m in zip(ps["audios"], ps["slot_start"], ps["m"]):
+                        x[o:o + m] = feats[s].to(self.device, torch.float32)
+                self.seg_passes += 1
+                fused = self._trunk(st, x, _Gaps(ps["levels"], self.device))
+                lv, k = ps["levels"][-1], len(ps["audios"])
+                if fused.T != lv["rows"]:
+                    raise RuntimeError("the plan and the network disagree on the rows of the last level")
+                width = (fused.F, fused.C)
+                mean = torch.empty(k, fused.ld, dtype=torch.float32, device=self.device)
+                _lib.check(l.gsv_op_time_mean_seg(fused.t.data_ptr(), fused.T, fused.ld, k, (C.c_int32 * k)(*lv["seg_start"]),
+                                                  (C.c_int32 * k)(*lv["seg_len"]), mean.data_ptr(), st), "gsv_op_time_mean_seg")
+                self.launches += 1
+                means.append(mean)
+            out = means[0] if len(means) == 1 else torch.cat(means)
+            order = [s for ps in plan for s in ps["audios"]]
+            if order != list(range(n)):                             # a plan of the caller's that is not in order
+                out = out[torch.tensor(sorted(range(n), key=order.__getitem__), device=self.device)]
+            Fq, Cn = width
+            return out.view(n, Fq + 2, Cn)[:, 1:-1].transpose(1, 2).reshape(n, -1)            # (c, f) order of flatten(1, 2)

@@ -549,6 +549,24 @@ int gsv_op_channel_norm_seg(const void* x, int T, int C, int n_seg, const int32_
  * puts between audios in front of the positional conv); idx[r] >= rows_in stores a NaN row, as gsv_op_embed_ln does for an id
  * outside its table.  x and y must not overlap. */
 int gsv_op_gather_rows(const void* x, int rows_in, const int32_t* idx, int rows_out, int C, void* y, int dtype, gsv_stream_t stream);
+/* the two segmented kernels of the packed speaker-embedding pass (gsv/eres2net/ERes2NetV2.py forward3_segments, DESIGN.md
+ * section 4l), where the audios lie back to back on the time axis with gap rows between them.
+ * gsv_op_zero_rows: stores 0 to rows rows[0 .. n_rows) of n_maps (1 .. 8) fp32 maps [T][ld] of one shape, in one launch: the gap
+ *   rows in front of a conv that reads across time.  maps->p[0 .. n_maps) [dev], 16-byte aligned, ld a multiple of 4 floats; the
+ *   row list comes twice, rows [dev] int32 [n_rows] for the kernel and rows_host [host], the same n_rows values, for the check
+ *   (so the call neither waits for the device nor copies): a row outside [0, T), ld % 4 != 0 or n_maps outside 1 .. 8 is
+ *   GSV_ERR_ARG.  The kernel skips a device row outside [0, T).  Every other element of the maps is left as it is.
+ * gsv_op_time_mean_seg: x [dev] fp32 [T][ld] -> out [dev] fp32 [n_seg][ld], out[s] = mean over the rows [seg_start[s],
+ *   seg_start[s] + seg_len[s]) in gsv_op_time_mean's order counted from the segment's first row (16 strided slices, the 16
+ *   partials in order, divided by the length): a segment's bits depend on its own rows alone, and one segment [0, T) gives
+ *   gsv_op_time_mean's bits.  seg_start / seg_len [host], checked as gsv_op_channel_norm_seg checks them (1 .. 8192 segments,
+ *   len >= 1, disjoint and ascending, inside [0, T)); ld a multiple of 4, x and out 16-byte aligned; the table travels like
+ *   gsv_op_flash_attn64_seg's, so the call neither waits nor allocates. */
+typedef struct gsv_zero_maps { float* p[8]; } gsv_zero_maps;
+int gsv_op_zero_rows(const gsv_zero_maps* maps, int n_maps, int T, int ld, const int32_t* rows, const int32_t* rows_host, int n_rows,
+                     gsv_stream_t stream);
+int gsv_op_time_mean_seg(const float* x, int T, int ld, int n_seg, const int32_t* seg_start, const int32_t* seg_len, float* out,
+                         gsv_stream_t stream);
 /* sampling kernel alone: logits [dev] fp32 [B][vocab], prev [dev] int32 [B][prev_len], noise [dev]
  * fp32 [B][vocab] or NULL; outputs [dev] int32 [B]: sampled token, argmax of penalised logits */
 int gsv_op_sample(const float* logits, int B, int vocab, int vocab_eff, const int32_t* prev, int prev_len,

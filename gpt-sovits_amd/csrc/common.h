@@ -190,7 +190,7 @@ struct ConvArgs {
 // instantiation it launched, as one 64-bit code of byte fields (include/gsv.h has the layout).  A plain store on the host:
 // no formatting, allocation or synchronisation on the launch path.
 enum { ROUTE_GEMM_SK = 1, ROUTE_GEMM_T64 = 2, ROUTE_CONV_WIDE = 3, ROUTE_GEMM_LDS = 4, ROUTE_CONV_LDS = 5, ROUTE_CONV_NARROW = 6,
-       ROUTE_CONV_GEMM = 7, ROUTE_CONV_PAIR = 8 };
+       ROUTE_CONV_GEMM = 7, ROUTE_CONV_PAIR = 8, ROUTE_GEMM_PANEL = 9 };
 enum { ROUTE_RES = 1, ROUTE_ACCU = 2, ROUTE_ALLW = 4, ROUTE_WNT = 8, ROUTE_SEG = 16 };
 constexpr unsigned long long route_code(int family, int dtype, int p0 = 0, int p1 = 0, int p2 = 0, int p3 = 0, int p4 = 0, int flags = 0) {
   return (unsigned long long)(family & 255) | (unsigned long long)(dtype & 255) << 8 | (unsigned long long)(p0 & 255) << 16 |
@@ -208,6 +208,14 @@ int launch_seg_rows(int dtype, int out_f32, void* y, int ldy, int col0, int C, i
 
 // picks the kernel for the shape (conv_gemm.hip; the kernels it chooses from are declared in conv_launch.h)
 int launch_conv_gemm(int dtype, const ConvArgs& a, hipStream_t s);
+// the prefill's panel GEMM (gemm_panel.hip), called IN FRONT of the dispatcher by the prefill itself: 0 = launched, 1 = not
+// eligible (go on to launch_conv_gemm), < 0 = error.  tile: 0 = the launcher's choice by shape, 1..3 = one member of the family,
+// 4 = tile 3 with the two-accumulator sum of gemm_t64
+bool gemm_panel_eligible(int dtype, const ConvArgs& a);
+int gemm_panel_auto_tile(const ConvArgs& a, int* wgs_out);   // the launcher's tile (1..3) for the shape and its workgroup count
+int launch_gemm_panel(int dtype, const ConvArgs& a, int tile, hipStream_t s);
+// the same, in the form (tile and summation) that computes the bits launch_conv_gemm would compute for the descriptor; 1 = none
+int launch_gemm_panel_as_dispatcher(int dtype, const ConvArgs& a, hipStream_t s);
 
 // fused ResBlock pair of the generator's narrow stages (conv_pair.hip): y = (convs2(lrelu(convs1(lrelu(x)))) + x) * scale [+ y]
 struct ConvPairArgs {

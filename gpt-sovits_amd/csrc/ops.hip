@@ -382,7 +382,8 @@ int gsv_op_flash_rel96(const void* qkv, int T, int heads, float scale, const flo
                                      scale, rel_k, rel_v, out, H, (hipStream_t)stream);
 }
 
-int gsv_op_conv1d(const gsv_conv_desc* d, int dtype, gsv_stream_t stream) {
+// gsv_conv_desc -> the launchers' argument block (gsv_op_conv1d and gsv_op_gemm_panel take the same descriptor)
+static gsv::ConvArgs conv_desc_args(const gsv_conv_desc* d) {
   gsv::ConvArgs a;
   a.x = d->x; a.w = d->w; a.bias = d->bias; a.y = d->y; a.res = d->res; a.gate = d->gate;
   a.T_in = d->T_in; a.T_out = d->T_out; a.Cin = d->Cin; a.Cout = d->Cout; a.taps = d->taps;
@@ -406,7 +407,21 @@ int gsv_op_conv1d(const gsv_conv_desc* d, int dtype, gsv_stream_t stream) {
   if (d->ldy > 0) { a.ldy = d->ldy; a.ldr = d->ldy; }
   if (d->ldr > 0) a.ldr = d->ldr;
   if (d->Z > 1) { a.Z = d->Z; a.xz = d->xz; a.wz = d->wz; a.yz = d->yz; a.bz = d->bz; a.rz = d->rz ? d->rz : d->yz; }
-  return gsv::launch_conv_gemm(dtype, a, (hipStream_t)stream);
+  return a;
+}
+
+int gsv_op_conv1d(const gsv_conv_desc* d, int dtype, gsv_stream_t stream) {
+  return gsv::launch_conv_gemm(dtype, conv_desc_args(d), (hipStream_t)stream);
+}
+
+int gsv_op_gemm_panel(const gsv_conv_desc* d, int dtype, int tile, gsv_stream_t stream) {
+  GSV_REQUIRE(d, "op_gemm_panel: null descriptor");
+  GSV_REQUIRE(tile >= 0 && tile <= 4, "op_gemm_panel: tile %d is not a member of the family (0 = by shape, 1..4)", tile);
+  const gsv::ConvArgs a = conv_desc_args(d);
+  GSV_REQUIRE(gsv::gemm_panel_eligible(dtype, a), "op_gemm_panel: the descriptor is not one of the prefill's three GEMM forms");
+  const int rc = gsv::launch_gemm_panel(dtype, a, tile, (hipStream_t)stream);
+  GSV_REQUIRE(rc != 1, "op_gemm_panel: not eligible");
+  return rc;
 }
 
 int gsv_op_frame(const float* x, int n, int frame_len, int hop, int pad, int ld, int T_out, void* out, int dtype, gsv_stream_t stream) {

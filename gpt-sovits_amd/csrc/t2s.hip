@@ -1081,6 +1081,24 @@ int gsv_t2s_set_mega(gsv_t2s_t* h, int on) {
   return GSV_OK;
 }
 
+int gsv_t2s_debug_kv(gsv_t2s_t* h, int layer, int which, int row, int n_pos, void* out) {
+  GSV_REQUIRE(h && h->finalized && out, "t2s_debug_kv: null argument or handle not finalized");
+  GSV_REQUIRE(layer >= 0 && layer < h->cfg.n_layer && (which == 0 || which == 1) && row >= 0 && row < h->max_batch && n_pos >= 1 &&
+                  n_pos <= h->max_seq, "t2s_debug_kv: layer %d / which %d / row %d / n_pos %d outside the arena", layer, which, row, n_pos);
+  const size_t es = esz(h), H = h->cfg.n_head, pitch = (size_t)h->max_seq * 32 * es;
+  GSV_HIP(hipDeviceSynchronize());
+  GSV_HIP(hipMemcpy2D(out, (size_t)n_pos * 32 * es, (const char*)kv_ptr(h, layer, which) + (size_t)row * H * pitch, pitch,
+                      (size_t)n_pos * 32 * es, H, hipMemcpyDeviceToHost));
+  return GSV_OK;
+}
+
+int gsv_t2s_set_prefill_gemm(gsv_t2s_t* h, int mode) {
+  GSV_REQUIRE(h, "t2s_set_prefill_gemm: null handle");
+  GSV_REQUIRE(mode >= 0 && mode <= 2, "t2s_set_prefill_gemm: mode %d (0 dispatcher, 1 panel, 2 panel from the threshold)", mode);
+  h->prefill_gemm = mode;
+  return GSV_OK;
+}
+
 int gsv_t2s_set_debug(gsv_t2s_t* h, const int32_t* force_tokens, float* logits_dump, int32_t* drawn_dump) {
   GSV_REQUIRE(h && h->finalized, "t2s_set_debug: handle not finalized");
   h->dbg_force = force_tokens; h->dbg_dump = logits_dump; h->dbg_drawn = drawn_dump;

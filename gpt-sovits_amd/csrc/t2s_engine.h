@@ -54,6 +54,7 @@ struct gsv_t2s : gsveng::Ctx {
   hipEvent_t mega_ev[2] = {nullptr, nullptr};
   float last_decode_ms = 0.f; int last_decode_steps = 0; int last_decode_mode = 0;
   bool mega_on = true;      // gsv_t2s_set_mega (A/B inside one process); GSV_T2S_NO_MEGA=1 never builds the engine
+  int prefill_gemm = 2;     // gsv_t2s_set_prefill_gemm: 0 dispatcher only, 1 panel GEMM wherever eligible, 2 from PANEL_MIN_ROWS rows upwards
   const int* dbg_force = nullptr; float* dbg_dump = nullptr; int* dbg_drawn = nullptr; int dbg_stall = 0;   // gsv_t2s_set_debug / gsv_t2s_debug_stall: apply to the NEXT decode call only
   std::map<int, hipGraphExec_t> graphs;
 };

@@ -312,7 +312,34 @@ ConvArgs linear(const void* x, const void* w, const float* bias, void* y, int ro
 
 // A/B switches, read once per process
 bool scalar_prefill_attn() { static const bool v = getenv("GSV_SCALAR_PREFILL_ATTN") != nullptr; return v; }      // thread-per-query VALU kernel
+bool no_prefill_panel() { static const bool v = getenv("GSV_NO_PREFILL_PANEL") != nullptr; return v; }           // the four per-layer GEMMs stay on the dispatcher
 bool prefill_split_scatter() { static const bool v = getenv("GSV_PREFILL_SPLIT_SCATTER") != nullptr; return v; }  // K/V scatter and V^T as two launches
+
+// The four per-layer GEMMs: the panel kernel (gemm_panel.hip) in front of the dispatcher, the way the generator calls conv_pair.
+// launch_gemm_panel_as_dispatcher picks the form of the kernel that computes the dispatcher's bits for the shape (gemm_lds' single sum,
+// or gemm_t64's two accumulators where the dispatcher launches that one: up to 2048 rows) and declines where it has none, so the
+// mode is a speed choice only, at every row count.
+// PANEL_MIN_ROWS (mode 2): below it the dispatcher's skinny kernels (gemm_sk / gemm_t64) and under-filled gemm_lds grids serve and
+// single-utterance latency stays what it is; tools/gemm_probe.py --panel has the sweep (profiles/prefill_panel_probe.txt).
+// One (shape, M range) above the threshold stays on the dispatcher: where gemm_lds still fits ONE round of its
+// 8-wave form (<= 256 tiles of 128 x 128) while the panel kernel's tiling needs a second round -- QKV at M = 2049 .. 2560,
+// measured 12.3 us against 14.5 us at M = 2160.
+constexpr int PANEL_MIN_ROWS = 2049;
+bool panel_pays(const ConvArgs& g) {
+  if (g.T_in < PANEL_MIN_ROWS) return false;
+  int wgs = 0;
+  gemm_panel_auto_tile(g, &wgs);
+  const long long tiles128 = (long long)((g.T_in + 127) / 128) * ((g.Cout + 127) / 128);
+  return !(tiles128 <= 256 && wgs > 256);
+}
+int prefill_gemm(gsv_t2s* h, const ConvArgs& g, hipStream_t s) {
+  const int mode = no_prefill_panel() ? 0 : h->prefill_gemm;
+  if (mode == 1 || (mode == 2 && panel_pays(g))) {
+    const int rc = launch_gemm_panel_as_dispatcher(h->dtype, g, s);
+    if (rc != 1) return rc;
+  }
+  return launch_conv_gemm(h->dtype, g, s);
+}
 
 // One layer's K/V fill and attention without the engine handle: what prefill_attention (the engine) and gsv_op_prefill_attn
 // (the test hook) both launch through.  row_off / x_len / plen are device arrays of B ints, vt the V^T scratch of
@@ -462,20 +489,20 @@ int t2s_prefill_rows(gsv_t2s* h, const int32_t* phones, const int32_t* phone_len
 
   for (int li = 0; li < c.n_layer; ++li) {
     const LayerW& L = h->layers[li];
-    GSV_RC(launch_conv_gemm(h->dtype, linear(h->pf_x, L.qkv_w, L.qkv_b, h->pf_qkv, M, d, 3 * d), s));
+    GSV_RC(prefill_gemm(h, linear(h->pf_x, L.qkv_w, L.qkv_b, h->pf_qkv, M, d, 3 * d), s));
     GSV_RC(prefill_attention<T>(h, li, maxS, s));
     // y1 = attn Wo^T + bo + x  (fp32) ; x1 = LN1(y1)
     ConvArgs o = linear(h->pf_attn, L.out_w, L.out_b, h->pf_y, M, d, d);
     o.out_f32 = 1; o.res = h->pf_x; o.ldr = d;
-    GSV_RC(launch_conv_gemm(h->dtype, o, s));
+    GSV_RC(prefill_gemm(h, o, s));
     GSV_RC(launch_layernorm(h->dtype, h->pf_y, 1, nullptr, 0, L.n1w, L.n1b, h->pf_x, 0, M, d, 1e-5f, s));
     // y2 = relu(x1 W1^T + b1) W2^T + b2 + x1  (fp32) ; x = LN2(y2) for the next layer (the decode step applies the last one)
     ConvArgs f1 = linear(h->pf_x, L.w1, L.b1, h->pf_h, M, d, c.ffn_dim);
     f1.post_act = ACT_RELU;
-    GSV_RC(launch_conv_gemm(h->dtype, f1, s));
+    GSV_RC(prefill_gemm(h, f1, s));
     ConvArgs f2 = linear(h->pf_h, L.w2, L.b2, h->pf_y, M, c.ffn_dim, d);
     f2.out_f32 = 1; f2.res = h->pf_x; f2.ldr = d;
-    GSV_RC(launch_conv_gemm(h->dtype, f2, s));
+    GSV_RC(prefill_gemm(h, f2, s));
     if (li + 1 < c.n_layer)
       GSV_RC(launch_layernorm(h->dtype, h->pf_y, 1, nullptr, 0, L.n2w, L.n2b, h->pf_x, 0, M, d, 1e-5f, s));
   }

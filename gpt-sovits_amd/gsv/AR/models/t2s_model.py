@@ -188,6 +188,8 @@ class Text2SemanticDecoder:
                                              bert_dev.data_ptr() if bert_dev is not None else None,
                                              pr.data_ptr() if P > 0 else None, P, s),
                            "gsv_t2s_prefill")
+            # the prefill's last conv / GEMM launch (FFN2 of the last layer): which kernel family served it (include/gsv.h)
+            self.last_prefill_route = int(l.gsv_debug_last_conv_route(0))
             if rng_keys is not None:
                 seeds_h = (C.c_uint64 * B)(*[int(k[0]) & 0xFFFFFFFFFFFFFFFF for k in rng_keys])
                 rows_h = (C.c_int32 * B)(*[int(k[1]) for k in rng_keys])
@@ -321,6 +323,18 @@ class Text2SemanticDecoder:
         """A/B switch: False makes later calls use the launch-per-phase decode step instead of the persistent engine
         (csrc/t2s_mega.hip; fp16, v1/v2 shape, batch <= 128 in one launch)."""
         _lib.check(_lib.lib().gsv_t2s_set_mega(self._h, int(bool(on))), "gsv_t2s_set_mega")
+
+    def set_prefill_gemm(self, mode: int):
+        """A/B switch of the prefill's per-layer GEMMs: 0 = the dispatcher only, 1 = the panel kernel (csrc/gemm_panel.hip)
+        wherever it is eligible, 2 (default) = the panel kernel from the measured row-count threshold upwards.  Same bits
+        either way; GSV_NO_PREFILL_PANEL in the environment forces 0."""
+        _lib.check(_lib.lib().gsv_t2s_set_prefill_gemm(self._h, int(mode)), "gsv_t2s_set_prefill_gemm")
+
+    def debug_kv(self, layer: int, which: int, row: int, n_pos: int):
+        """test hook: cached positions 0 .. n_pos - 1 of batch row `row` in one layer's K (which = 0) or V (1): [heads][n_pos][32]"""
+        out = torch.empty(self.num_head, n_pos, 32, dtype=self.dtype)
+        _lib.check(_lib.lib().gsv_t2s_debug_kv(self._h, layer, which, row, n_pos, out.data_ptr()), "gsv_t2s_debug_kv")
+        return out
 
     def debug_stall(self, member: int):
         """test hook: the next persistent launch loses one hand-off publish of `member` (group 0)"""

@@ -87,6 +87,8 @@ _SIGS = {
                                  C.POINTER(C.c_int), C.c_void_p]),
     "gsv_t2s_decode_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "gsv_t2s_set_mega": (C.c_int, [C.c_void_p, C.c_int]),
+    "gsv_t2s_set_prefill_gemm": (C.c_int, [C.c_void_p, C.c_int]),
+    "gsv_t2s_debug_kv": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "gsv_t2s_engine_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
     "gsv_t2s_set_debug": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsv_t2s_debug_stall": (C.c_int, [C.c_void_p, C.c_int]),
@@ -171,6 +173,7 @@ _SIGS = {
     "gsv_op_flash_rel96": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
     "gsv_op_conv1d": (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_void_p]),
+    "gsv_op_gemm_panel": (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int, C.c_void_p]),
     "gsv_debug_last_conv_route": (C.c_uint64, [C.c_int]),
     "gsv_debug_last_pair_route": (C.c_uint64, [C.c_int]),
     "gsv_op_frame": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),

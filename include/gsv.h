@@ -125,6 +125,12 @@ int gsv_t2s_decode(gsv_t2s_t* h, const gsv_sampling_params* sp, const float* noi
 int gsv_t2s_decode_info(gsv_t2s_t* h, int* mode, float* device_ms, int* steps);
 /* A/B switch inside one process: on = 0 makes later decode calls of this handle use the launch-per-phase step */
 int gsv_t2s_set_mega(gsv_t2s_t* h, int on);
+/* A/B switch of the prefill's four per-layer GEMMs (fp16): mode 0 = the conv / GEMM dispatcher only, 1 = the panel kernel
+ * (csrc/gemm_panel.hip) wherever it is eligible, whatever the row count, 2 (default) = the panel kernel from the measured row-count
+ * threshold upwards.  Either way the prefill computes the same bits: the kernel takes the summation form of the kernel the
+ * dispatcher would launch for the shape, and a GEMM for which it has no such form stays on the dispatcher.  GSV_NO_PREFILL_PANEL (set, read once per process) forces
+ * mode 0 for every handle.  Another mode is GSV_ERR_ARG. */
+int gsv_t2s_set_prefill_gemm(gsv_t2s_t* h, int mode);
 /* Robustness report.  A persistent launch whose hand-off timed out (a member workgroup was not running: its CU was held
  * by another kernel) does not fail the request: the row state is restored, the batch is re-run on the launch-per-phase
  * step and the handle stops using the engine.  engine_available = 0 after that (or when the engine was never built),
@@ -144,6 +150,9 @@ int gsv_t2s_set_debug(gsv_t2s_t* h, const int32_t* force_tokens, float* logits_d
 int gsv_t2s_debug_stall(gsv_t2s_t* h, int member);
 /* test hook: logits of each row's last sampled step [dev] fp32 [B][vocab] (either decode path) */
 int gsv_t2s_debug_logits(gsv_t2s_t* h, float* out, gsv_stream_t stream);
+/* test hook: positions 0 .. n_pos - 1 of batch row `row` in one layer's K (which = 0) or V (which = 1) cache, copied to out
+ * [host] [heads][n_pos][32] in the handle's dtype; waits for the device.  GSV_ERR_ARG: a layer, row or n_pos outside the arena. */
+int gsv_t2s_debug_kv(gsv_t2s_t* h, int layer, int which, int row, int n_pos, void* out);
 /* per-kernel timing of the decode step: average device time (ms) of one step over `iters`
  * replays at the current cache length, and of the decode-attention kernel alone. */
 int gsv_t2s_time_step(gsv_t2s_t* h, int iters, float* step_ms, float* attn_ms, gsv_stream_t stream);
@@ -473,12 +482,22 @@ int gsv_op_prefill_attn(const void* qkv, const int32_t* x_len, const int32_t* p_
                         int route, void* kc, void* vc, void* out, gsv_stream_t stream);
 /* channels-last conv1d: x [T_in][Cin], w [Cout][taps*Cin] (tap-major, cin fastest), y [T_out][Cout] */
 int gsv_op_conv1d(const gsv_conv_desc* d, int dtype, gsv_stream_t stream);
+/* test hook: the same descriptor through the prefill's panel GEMM (csrc/gemm_panel.hip) instead of the dispatcher.  tile: 0 = the
+ * launcher's choice by shape, 1 = 192 x 256, 2 = 192 x 192, 3 = 96 x 128 (rows x output channels), 4 = 96 x 128 with the
+ * two-accumulator sum of gemm_t64 (even / odd k-steps of 16), which is what the dispatcher computes up to 2048 rows.  Eligible: GSV_F16, taps 1,
+ * stride 1, pad 0, Z <= 1, Cin % 64 == 0, Cout % 8 == 0, y_col0 0, 16-byte aligned operands, a bias, no gate / accumulate /
+ * pre-activation / transposed form, and one of: fp16 out (post_act none or ReLU) | fp32 out + fp16 residual (res_dtype 2, no
+ * activation).  Anything else, or an unknown tile, is GSV_ERR_ARG before any HIP call; outputs are then untouched.  Bit-identical
+ * to what gemm_lds (tiles 0..3) or gemm_t64 (tile 4) computes for the same rows. */
+int gsv_op_gemm_panel(const gsv_conv_desc* d, int dtype, int tile, gsv_stream_t stream);
 /* test hook: which kernel instantiation the last gsv_op_conv1d / gsv_op_conv_pair / engine conv launch on this thread ran
  * (0 = none since the last reset).  Byte fields, low to high: family, dtype (GSV_F32 / GSV_F16), five template parameters p0..p4,
  * flags (1 RES, 2 ACCU, 4 ALLW, 8 WNT, 16 SEG).  Families and their parameters:
  *   1 gemm_sk_f16 | 2 gemm_t64_f16 p0 = SLAB / 16 | 3 conv_wide_f16 p0 = waves | 4 gemm_lds p0 = waves, p1 = xcd_order
  *   5 conv_lds p0..p4 = TM, TN, WM, WN, CC | 6 conv_narrow_f16 p0..p3 = CC, TM, TN, WN | 7 conv_gemm (generic) p0..p3 = TM, TN, WM, WN
  *   8 conv_pair_f16 p0 = C, p1 = taps; flag SEG = the masked pair of a segmented decode (gsv_op_conv_pair_seg).
+ *   9 gemm_panel_f16 p0 = tile rows / 32, p1 = tile output channels / 32, p2 = 1: gemm_t64's two-accumulator sum (the prefill's own
+ *     GEMM, launched in front of the dispatcher)
  * reset != 0 clears the record after reading it. */
 uint64_t gsv_debug_last_conv_route(int reset);
 /* the same record for the last family-8 launch (gsv_op_conv_pair / gsv_op_conv_pair_seg / a fused pair inside an engine decode)

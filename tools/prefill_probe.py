@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Wall time of the AR prefill (+ step 0 + one engine step) at the BASELINE configs[1] shape: B = 32 rows of 80 phonemes + 100
 prompt tokens (measurement tool; `rocprofv3 --kernel-trace --stats -- python3 tools/prefill_probe.py` gives the kernel split).
+PROF_B=128 probes the B = 128 shape; GSV_NO_PREFILL_PANEL=1 keeps the per-layer GEMMs on the dispatcher (the A/B of gemm_panel.hip).
 
     python tools/prefill_probe.py
 """
@@ -17,7 +18,7 @@ from gsv.AR.models.t2s_model import Text2SemanticDecoder  # noqa: E402
 
 B = int(os.environ.get("PROF_B", "32"))
 cfg = S.T2S_V2_CONFIG
-eng = Text2SemanticDecoder(cfg, device="cuda:0", dtype=torch.float16, max_batch=32, max_seq=320)
+eng = Text2SemanticDecoder(cfg, device="cuda:0", dtype=torch.float16, max_batch=max(32, B), max_seq=320)
 eng.load_state_dict(S.make_t2s_state_dict(cfg, seed=0, suppress_eos=True))
 utt = S.make_utterances(B)
 xs = [torch.tensor(it["all_phones"]) for it in utt["items"]]

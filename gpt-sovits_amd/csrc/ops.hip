@@ -181,6 +181,33 @@ __global__ void frame_kernel(const float* __restrict__ x, int n, int flen, int h
   }
 }
 
+// frame_kernel per segment: row r of segment s = (tab[s].z <= r < tab[s].z + tab[s].w) frames the audio x[tab[s].x ..][tab[s].y],
+// reflected at that audio's own ends; a row between segments is left alone.  tab: int4 (first sample, samples, first row, rows).
+template <typename T>
+__global__ void frame_seg_kernel(const float* __restrict__ x, const int4* __restrict__ tab, int n_seg, int flen, int hop, int pad, int ld,
+                                 int row0, T* __restrict__ out) {
+  const int row = row0 + blockIdx.x;
+  int lo = 0, hi = n_seg - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[mid].z <= row) lo = mid; else hi = mid - 1;
+  }
+  const int4 sg = tab[lo];
+  const int t = row - sg.z, n = sg.y;
+  if (t < 0 || t >= sg.w) return;
+  const float* xs = x + (long long)sg.x;
+  for (int k = threadIdx.x; k < ld; k += blockDim.x) {
+    float v = 0.f;
+    if (k < flen) {
+      int i = t * hop + k - pad;
+      if (i < 0) i = -i;
+      if (i >= n) i = 2 * (n - 1) - i;
+      v = (i >= 0 && i < n) ? xs[i] : 0.f;
+    }
+    out[(long long)row * ld + k] = (T)v;
+  }
+}
+
 // spec[b][t] = sqrt(re^2 + im^2 + eps), ri [T][2 * bins] (re | im column blocks) -> spec [bins][T]  (mel_processing.py:73)
 __global__ void magnitude_kernel(const float* __restrict__ ri, int T, int bins, float eps, float* __restrict__ spec) {
   __shared__ float tile[32][33];
@@ -434,6 +461,42 @@ int gsv_op_frame(const float* x, int n, int frame_len, int hop, int pad, int ld,
   else hipLaunchKernelGGL(gsv::frame_kernel<float>, dim3(T_out), dim3(256), 0, s, x, n, frame_len, hop, pad, ld, T_out, (float*)out);
   GSV_HIP(hipGetLastError());
   return GSV_OK;
+}
+
+int gsv_op_frame_seg(const float* x, int n_x, int frame_len, int hop, int pad, int ld, int n_seg, const int32_t* x_start,
+                     const int32_t* x_len, const int32_t* row_start, const int32_t* row_len, int rows, void* out, int dtype,
+                     gsv_stream_t stream) {
+  GSV_REQUIRE(x && out && x_start && x_len && row_start && row_len && n_x > 0 && frame_len > 0 && hop > 0 && ld >= frame_len && rows > 0 &&
+              pad >= 0, "op_frame_seg: bad argument");
+  GSV_REQUIRE(dtype == GSV_F16 || dtype == GSV_F32, "op_frame_seg: bad dtype");
+  GSV_REQUIRE(n_seg >= 1 && n_seg <= gsveng::kSegTableMax, "op_frame_seg: %d segments (1 .. %d)", n_seg, gsveng::kSegTableMax);
+  long long x_end = 0, r_end = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    const int n = x_len[i], T = row_len[i];
+    GSV_REQUIRE(n >= 1 && T >= 1, "op_frame_seg: segment %d has %d samples and %d frames", i, n, T);
+    GSV_REQUIRE(pad < n, "op_frame_seg: reflect padding %d needs more than %d samples, segment %d has %d", pad, pad, i, n);
+    GSV_REQUIRE((long long)(T - 1) * hop + frame_len - pad <= (long long)n + pad, "op_frame_seg: the frames of segment %d run past its "
+                "(padded) signal", i);
+    GSV_REQUIRE(x_start[i] >= x_end && row_start[i] >= r_end, "op_frame_seg: segment %d starts before the one before it ends (sample and "
+                "row ranges are disjoint and ascending)", i);
+    x_end = (long long)x_start[i] + n;
+    r_end = (long long)row_start[i] + T;
+    GSV_REQUIRE(x_end <= n_x && r_end <= rows, "op_frame_seg: segment %d ends at sample %lld of %d, row %lld of %d", i, x_end, n_x, r_end, rows);
+  }
+  gsveng::SegTable tb;                              // holds the library context until it goes out of scope
+  GSV_RC(gsveng::seg_table_begin(&tb));
+  for (int i = 0; i < n_seg; ++i) {
+    tb.image[4 * i] = x_start[i]; tb.image[4 * i + 1] = x_len[i]; tb.image[4 * i + 2] = row_start[i]; tb.image[4 * i + 3] = row_len[i];
+  }
+  hipStream_t s = (hipStream_t)stream;
+  GSV_RC(gsveng::seg_table_upload(&tb, n_seg, s));
+  const int4* tab = (const int4*)tb.dev;
+  const int r0 = row_start[0], nr = (int)r_end - r0;  // rows in front of the first segment and behind the last get no workgroup
+  if (dtype == GSV_F16)
+    GSV_LAUNCH(gsv::frame_seg_kernel<_Float16>, dim3(nr), dim3(256), 0, s, x, tab, n_seg, frame_len, hop, pad, ld, r0, (_Float16*)out);
+  else
+    GSV_LAUNCH(gsv::frame_seg_kernel<float>, dim3(nr), dim3(256), 0, s, x, tab, n_seg, frame_len, hop, pad, ld, r0, (float*)out);
+  return gsveng::seg_table_end(&tb, s);
 }
 
 int gsv_op_magnitude(const float* re_im, int T, int bins, float eps, int frame_ld, float* spec, gsv_stream_t stream) {

@@ -22,7 +22,7 @@ import os
 import random
 import time
 import traceback
-from typing import Callable, Dict, Generator, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, Generator, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -573,6 +573,160 @@ class TTS:
         zero_wav = np.zeros(int(self.configs.sampling_rate * 0.3), dtype=np.float32)
         return np.concatenate([wav16k, zero_wav])
 
+    device_frontend_calls = 0            # _load_refs_device calls that reached the device, for tests and tools/voice_enrol_bench.py
+
+    def _load_refs_device(self, paths: Sequence[str], prompt_paths: Optional[Sequence[str]] = None) -> Dict[str, dict]:
+        """The reference-audio front-end of make_voices(device_frontend=True): what _prompt_wav16k and
+        _get_ref_spec compute for every distinct path of `paths`, with the files read on the host, uploaded in ONE copy from one
+        page-locked buffer, and resampled, normalised and framed on the device in packed launches (one
+        gsv_op_resample_poly_seg per (input rate, target rate), one spectrogram_torch_segments).  `prompt_paths` (default: all):
+        the paths whose 16 kHz prompt is wanted and whose length is checked (3..10 s or OSError); an auxiliary reference only needs
+        its spectrogram.  A missing file (ValueError) and a prompt outside 3..10 s are raised before any device work.
+        -> path -> dict(wav16k: 1-D fp32 device prompt + 0.3 s of zeros (None outside prompt_paths), audio: [1, n] fp32 at the model
+        rate divided by min(2, peak) where peak > 1, audio16k: [1, n16] of the engine dtype on v2Pro / v2ProPlus else None,
+        spec: [1, bins, T] of the engine dtype, raw_audio / raw_sr: the file as load_wav returned it, on the host)."""
+        from .. import audio_io as A
+        from ..module.mel_processing import spectrogram_torch_segments
+        cfg = self.configs
+        dev = torch.device(cfg.device)
+        sr_model = int(cfg.sampling_rate)
+        is_v2pro = getattr(self.vits_model, "is_v2pro", False) or cfg.version in ("v2Pro", "v2ProPlus")
+        if is_v2pro and getattr(self, "sv_model", None) is None:
+            raise RuntimeError("v2Pro / v2ProPlus: init_sv_model() first (ERes2NetV2 speaker embedding, sv.py:11-32)")
+        paths = list(dict.fromkeys(paths))
+        prompts = set(paths if prompt_paths is None else prompt_paths)
+        tail = int(cfg.sampling_rate * 0.3)
+        # ---- host: read every file, settle every length, raise every file error ----
+        chunks: List[np.ndarray] = []                             # what is uploaded, back to back
+        jobs = {"w16": [], "aud": []}                             # target -> (path, chunk index, rate of the chunk)
+        raws = {}
+        for path in paths:
+            if not os.path.exists(path):
+                raise ValueError(f"{path} not exists")
+            raw, sr = A.load_wav(path)
+            raws[path] = (raw, sr)
+            spec_mono = raw.mean(0) if raw.shape[0] == 2 else raw[0]
+            srcs = {"aud": spec_mono}
+            if path in prompts:
+                n16 = A.resampled_len(raw.shape[1], sr, 16000)
+                if n16 > 160000 or n16 < 48000:
+                    raise OSError("参考音频在3~10秒范围外，请更换！")
+                srcs["w16"] = spec_mono if raw.shape[0] <= 2 else raw.mean(0)
+            staged = {}
+            for target, rate in (("w16", 16000), ("aud", sr_model)):
+                if target not in srcs:
+                    continue
+                mono, r = srcs[target], sr
+                if r != rate and not A.device_resample_supported(r, rate):
+                    mono, r = A.resample(mono, r, rate), rate   # a pair the kernel refuses: this file's host resampler
+                k = (id(mono), r) if r == sr else (target, r)
+                if k not in staged:
+                    staged[k] = len(chunks)
+                    chunks.append(np.ascontiguousarray(mono, dtype=np.float32))
+                jobs[target].append((path, staged[k], r))
+        offs = np.concatenate([[0], np.cumsum([c.shape[0] for c in chunks])]).astype(np.int64)
+        # ---- one page-locked buffer, one upload ----
+        self.device_frontend_calls += 1
+        with torch.cuda.device(dev):
+            host = torch.empty(int(offs[-1]), dtype=torch.float32, pin_memory=True)
+            hv = host.numpy()
+            for c, o in zip(chunks, offs):
+                hv[o:o + c.shape[0]] = c
+            stream = host.to(dev, non_blocking=True)
+
+            def run(job, target_rate, out, out_starts, peaks):
+                """one launch per input rate of `job` into out at out_starts (by job index); a chunk at the target rate is copied"""
+                for r, idx in A.group_by_rate([j[2] for j in job]).items():
+                    st = [int(offs[job[i][1]]) for i in idx]
+                    ln = [int(chunks[job[i][1]].shape[0]) for i in idx]
+                    if r == target_rate:
+                        for i, a, n in zip(idx, st, ln):
+                            out[out_starts[i]:out_starts[i] + n].copy_(stream[a:a + n])
+                            if peaks is not None:
+                                peaks[i] = out[out_starts[i]:out_starts[i] + n].abs().max()
+                        continue
+                    order = sorted(range(len(idx)), key=lambda q: st[q])    # the op takes ascending ranges; so are out_starts
+                    _, _, pk = A.resample_segments(stream, [st[q] for q in order], [ln[q] for q in order], r, target_rate, out=out,
+                                                   out_starts=[out_starts[idx[q]] for q in order], peak=peaks is not None)
+                    if peaks is not None and len(idx) == len(job):
+                        peaks.copy_(pk)
+                    elif peaks is not None:
+                        peaks[torch.tensor([idx[q] for q in order], device=dev)] = pk
+
+            # the prompts at 16 kHz, each followed by `tail` zeros
+            res = {p: dict(wav16k=None, audio16k=None, raw_audio=raws[p][0], raw_sr=raws[p][1]) for p in paths}
+            job = jobs["w16"]
+            if job:
+                m16 = [A.resampled_len(chunks[j[1]].shape[0], j[2], 16000) for j in job]
+                starts = [0] * len(job)
+                for i in range(1, len(job)):
+                    starts[i] = starts[i - 1] + m16[i - 1] + tail
+                w16 = torch.zeros(starts[-1] + m16[-1] + tail, dtype=torch.float32, device=dev)
+                run(job, 16000, w16, starts, None)
+                for j, a, m in zip(job, starts, m16):
+                    res[j[0]]["wav16k"] = w16[a:a + m + tail]
+            # the model-rate audios with their peaks, normalised on the device
+            job = jobs["aud"]
+            ms = [A.resampled_len(chunks[j[1]].shape[0], j[2], sr_model) for j in job]
+            starts = [0] * len(job)
+            for i in range(1, len(job)):
+                starts[i] = starts[i - 1] + ms[i - 1]
+            aud = torch.empty(sum(ms), dtype=torch.float32, device=dev)
+            peaks = torch.zeros(len(job), dtype=torch.float32, device=dev)
+            run(job, sr_model, aud, starts, peaks)
+            aud = self._normalise_refs(aud, ms, peaks)
+            specs = spectrogram_torch_segments(aud, starts, ms, cfg.filter_length, sr_model, cfg.hop_length, cfg.win_length)
+            a16 = None
+            if is_v2pro:                                          # the normalised audio again at 16 kHz for the SV model
+                if sr_model == 16000:
+                    a16, tab16 = aud, list(zip(starts, ms))
+                elif A.device_resample_supported(sr_model, 16000):
+                    a16, tab16, _ = A.resample_segments(aud, starts, ms, sr_model, 16000)
+                else:
+                    parts = [torch.from_numpy(A.resample(aud[a:a + m].cpu().numpy(), sr_model, 16000)).to(dev) for a, m in zip(starts, ms)]
+                    a16, tab16, o = torch.cat(parts), [], 0
+                    for p in parts:
+                        tab16.append((o, int(p.numel())))
+                        o += int(p.numel())
+                if cfg.is_half:
+                    a16 = a16.half()
+            for i, (j, a, m) in enumerate(zip(job, starts, ms)):
+                r = res[j[0]]
+                r["audio"] = aud[a:a + m].unsqueeze(0)
+                r["spec"] = specs[i].half() if cfg.is_half else specs[i]
+                if a16 is not None:
+                    r["audio16k"] = a16[tab16[i][0]:tab16[i][0] + tab16[i][1]].unsqueeze(0)
+        return res
+
+    @staticmethod
+    def _normalise_refs(aud: torch.Tensor, lens: Sequence[int], peaks: torch.Tensor) -> torch.Tensor:
+        """_get_ref_spec's `audio / min(2, peak)` where peak > 1, for the audios of `lens` samples back to back in `aud`, from their
+        device peaks: no readback.  Dividing by 1 leaves the other audios' bits as they are."""
+        div = torch.where(peaks > 1, peaks.clamp(max=2.0), torch.ones_like(peaks))
+        reps = torch.tensor(list(lens), dtype=torch.int64).to(aud.device, non_blocking=True)
+        return aud / torch.repeat_interleave(div, reps, output_size=int(sum(lens)))
+
+    def _device_refs(self, missing, shared_sv: bool) -> Tuple[Dict[str, dict], Dict[str, torch.Tensor]]:
+        """make_voices(device_frontend=True): one _load_refs_device over every distinct main and auxiliary reference of the
+        `missing` voice keys -> (handed: path -> dict(spec_audio, raw_audio, raw_sr, sv_emb) for _ref_spec_or_handed, sv_emb None
+        unless shared_sv on a model with speaker embeddings; wav16k: main path -> the device prompt)"""
+        mains = list(dict.fromkeys(key[0] for key in missing))
+        for path in mains:                                        # the main references first: theirs are the errors make_voices raises
+            if not os.path.exists(path):
+                raise ValueError(f"{path} not exists")
+        paths = list(mains)
+        for key in missing:
+            for path in key[3]:
+                if path not in [None, ""] and os.path.exists(path) and path not in paths:
+                    paths.append(path)
+        refs = self._load_refs_device(paths, prompt_paths=mains)
+        handed = {p: dict(spec_audio=(r["spec"], r["audio16k"]), raw_audio=r["raw_audio"], raw_sr=r["raw_sr"], sv_emb=None)
+                  for p, r in refs.items()}
+        if shared_sv and all(r["audio16k"] is not None for r in refs.values()):
+            for path, emb in zip(paths, self.sv_model.compute_embedding3_many([refs[p]["audio16k"] for p in paths])):
+                handed[path]["sv_emb"] = emb
+        return handed, {p: refs[p]["wav16k"] for p in mains}
+
     def _set_prompt_semantic(self, ref_wav_path: str, hubert_feature: Optional[torch.Tensor] = None,
                              codes: Optional[torch.Tensor] = None, wav16k: Optional[np.ndarray] = None):
         """reference TTS.py:802-819: 16 kHz audio (3..10 s or OSError) + 0.3 s of silence -> HuBERT last_hidden_state ->
@@ -1110,7 +1264,7 @@ class TTS:
 
     voice_cache_size = 8
 
-    def make_voices(self, specs: Sequence[dict], shared_sv: bool = False) -> List[dict]:
+    def make_voices(self, specs: Sequence[dict], shared_sv: bool = False, device_frontend: bool = False) -> List[dict]:
         """make_voice(ref_audio_path=..., prompt_text=..., prompt_lang=..., aux_ref_audio_paths=...) for many specs (dicts of
         those keywords) with ONE packed HuBERT pass (HubertModel.batch) and one extract_latent_many over the reference audios
         that the voice LRU does not hold; every distinct ref_audio_path is loaded and encoded once.  The spectrogram, speaker
@@ -1120,7 +1274,11 @@ class TTS:
         before any device work.  self.prompt_cache is not changed.
         shared_sv=True (v2Pro / v2ProPlus; nothing changes on another model): the reference spectrograms of every distinct main
         and auxiliary path of the missing voices are computed first, then ONE SV.compute_embedding3_many runs over their 16 kHz
-        audios (packed ERes2NetV2 passes) instead of one encoder pass per reference; the voices take their embeddings from it."""
+        audios (packed ERes2NetV2 passes) instead of one encoder pass per reference; the voices take their embeddings from it.
+        device_frontend=True: the main and auxiliary references of the missing voices are read on the host, uploaded once, and
+        resampled, normalised and framed on the device (_load_refs_device): HuBERT takes the device prompts, the spectrograms (and,
+        with shared_sv, the embeddings) reach the voices as shared_sv's do.  The waveforms differ from the host resampler's by fp32
+        rounding; errors, LRU and order are as above."""
         lru = self.__dict__.setdefault("_voice_lru", collections.OrderedDict())
         keys, out, missing = [], {}, []
         for spec in specs:
@@ -1143,7 +1301,10 @@ class TTS:
                 raise RuntimeError("init_cnhuhbert_weights() first")
             if self.vits_model is None:
                 raise RuntimeError("init_vits_weights() first")
-            wavs: Dict[str, np.ndarray] = {}
+            wavs: Dict[str, Union[np.ndarray, torch.Tensor]] = {}
+            handed = None
+            if device_frontend:
+                handed, wavs = self._device_refs(missing, shared_sv)
             for key in missing:                                   # host side first: every file error before any device work
                 path = key[0]
                 if path not in wavs:
@@ -1151,10 +1312,11 @@ class TTS:
                         raise ValueError(f"{path} not exists")
                     wavs[path] = self._prompt_wav16k(path)
             paths = list(wavs)
-            feats = self.cnhuhbert_model.model.batch([torch.from_numpy(wavs[p]) for p in paths])
+            feats = self.cnhuhbert_model.model.batch([wavs[p] if device_frontend else torch.from_numpy(wavs[p]) for p in paths])
             codes = dict(zip(paths, self.vits_model.extract_latent_many([f.transpose(1, 2) for f in feats])))
             spec_of = {key: spec for key, spec in zip(keys, specs)}
-            handed = self._shared_sv_refs(missing) if shared_sv else None
+            if not device_frontend:
+                handed = self._shared_sv_refs(missing) if shared_sv else None
             for key in missing:
                 path, spec = key[0], spec_of[key]
                 req = {"ref_audio_path": path, "prompt_text": spec.get("prompt_text"), "prompt_lang": spec.get("prompt_lang", "")}
@@ -1192,7 +1354,7 @@ class TTS:
             handed[path]["sv_emb"] = emb
         return handed
 
-    def _with_shared_voices(self, requests: List[dict], shared_sv: bool = False) -> List[dict]:
+    def _with_shared_voices(self, requests: List[dict], shared_sv: bool = False, device_frontend: bool = False) -> List[dict]:
         """run_batch(shared_hubert=True / shared_sv=True): the requests that name a ref_audio_path and bring no `voice` get
         theirs from ONE make_voices call, each returned as a copy with its `voice` filled in; the others pass through"""
         todo = [i for i, req in enumerate(requests) if req.get("voice") is None and req.get("ref_audio_path") not in [None, ""]]
@@ -1201,7 +1363,7 @@ class TTS:
             specs = [{"ref_audio_path": requests[i]["ref_audio_path"], "prompt_text": requests[i].get("prompt_text"),
                       "prompt_lang": requests[i].get("prompt_lang", ""),
                       "aux_ref_audio_paths": requests[i].get("aux_ref_audio_paths")} for i in todo]
-            for i, voice in zip(todo, self.make_voices(specs, shared_sv=shared_sv)):
+            for i, voice in zip(todo, self.make_voices(specs, shared_sv=shared_sv, device_frontend=device_frontend)):
                 out[i] = dict(requests[i], voice=voice)
         return out
 
@@ -1604,7 +1766,8 @@ class TTS:
     def run_batch(self, requests: List[dict], shared_sovits: bool = False, shared_cfm: bool = False,
                   shared_speed: bool = False, mixed_sampling: bool = False,
                   shared_vocoder: bool = False, shared_bert: bool = False,
-                  shared_hubert: bool = False, shared_sv: bool = False) -> List[Tuple[int, np.ndarray]]:
+                  shared_hubert: bool = False, shared_sv: bool = False,
+                  device_frontend: bool = False) -> List[Tuple[int, np.ndarray]]:
         """Several requests, each with its own reference voice, through shared AR decodes.  Each request dict takes the
         keys run() accepts plus an optional "voice" (make_voice); without one it uses its ref_audio_path / prompt_text
         (through make_voice's LRU) or the current prompt cache.  Returns one (sr, int16 audio) per request, in order: what
@@ -1628,16 +1791,20 @@ class TTS:
         pass per voice.
         shared_sv=True (implies the make_voices route of shared_hubert): on a v2Pro / v2ProPlus model those voices also take their
         speaker embeddings, main and auxiliary, from one packed ERes2NetV2 pass (make_voices(shared_sv=True)).
+        device_frontend=True (with shared_hubert or shared_sv, else ValueError): that make_voices call reads the reference files on
+        the host and resamples, normalises and frames them on the device (make_voices(device_frontend=True)).
         No keyword changes anything for the other model family."""
         if self.t2s_model is None or self.vits_model is None:
             raise RuntimeError("init_t2s_weights / init_vits_weights first")
         if shared_vocoder and self.configs.use_vocoder and not shared_cfm:
             raise ValueError("shared_vocoder=True vocodes the folds of the shared flow-matching stage: pass shared_cfm=True too")
+        if device_frontend and not (shared_hubert or shared_sv):
+            raise ValueError("device_frontend=True is the front-end of the shared make_voices call: pass shared_hubert=True or shared_sv=True too")
         self.stop_flag = False
         if shared_bert:
             requests = self._with_shared_segments(requests)
         if shared_hubert or shared_sv:
-            requests = self._with_shared_voices(requests, shared_sv=shared_sv)
+            requests = self._with_shared_voices(requests, shared_sv=shared_sv, device_frontend=device_frontend)
         plans = [self._plan_request(req) for req in requests]
         self._ar_stage(plans, mixed_sampling=mixed_sampling)
         sr = self._output_sr()

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import wave
 from math import gcd
-from typing import Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -43,3 +43,94 @@ def resample(x: np.ndarray, sr_in: int, sr_out: int) -> np.ndarray:
     from scipy.signal import resample_poly
     g = gcd(int(sr_in), int(sr_out))
     return resample_poly(x.astype(np.float64), sr_out // g, sr_in // g, axis=-1).astype(np.float32)
+
+
+# ---- the same resampler on the device (gsv_op_resample_poly_seg) -------------------------------------------
+# PARITY UNPINNED against torchaudio / soxr, as above: the device path is pinned against `resample` (this module's host resampler).
+_filters: Dict[Tuple[int, int], Tuple[np.ndarray, int, int]] = {}
+_filters_dev: Dict[Tuple[int, int, str], "torch.Tensor"] = {}
+
+
+def resample_filter(sr_in: int, sr_out: int) -> Tuple[np.ndarray, int, int]:
+    """-> (h float32 [L], up, down): the filter scipy.signal.resample_poly(x, up, down) designs by default, scaled by `up` as it
+    applies it; L = 2 * 10 * max(up, down) + 1.  Cached per rate pair."""
+    key = (int(sr_in), int(sr_out))
+    if key not in _filters:
+        from scipy.signal import firwin
+        g = gcd(*key)
+        up, down = key[1] // g, key[0] // g
+        mx = max(up, down)
+        h = firwin(2 * 10 * mx + 1, 1.0 / mx, window=("kaiser", 5.0)) * up
+        _filters[key] = (h.astype(np.float32), up, down)
+    return _filters[key]
+
+
+def resampled_len(n: int, sr_in: int, sr_out: int) -> int:
+    """the length of resample(x [n], sr_in, sr_out): ceil(n * up / down)"""
+    g = gcd(int(sr_in), int(sr_out))
+    up, down = int(sr_out) // g, int(sr_in) // g
+    return (int(n) * up + down - 1) // down
+
+
+def group_by_rate(rates: Sequence[int]) -> Dict[int, List[int]]:
+    """indices of `rates` grouped by value, groups in order of first appearance: one resample launch per group and target rate"""
+    groups: Dict[int, List[int]] = {}
+    for i, sr in enumerate(rates):
+        groups.setdefault(int(sr), []).append(i)
+    return groups
+
+
+def resample_segments(stream, starts: Sequence[int], lens: Sequence[int], sr_in: int, sr_out: int, out=None,
+                      out_starts: Optional[Sequence[int]] = None, peak: bool = False):
+    """gsv_op_resample_poly_seg over the audios stream[starts[s] : starts[s] + lens[s]] of one fp32 device vector: each resampled
+    sr_in -> sr_out as `resample` does (same filter, fp32 accumulation) into out[out_starts[s] : out_starts[s] + m_s], m_s =
+    resampled_len(lens[s]).  out=None: a new vector with the outputs back to back (out_starts must be None); else an fp32 device
+    vector whose other samples are left as they are.  -> (out, [(start, m_s)], peaks fp32 [n_seg] on the device or None).
+    One launch, no synchronisation.  A pair the kernel refuses (its filter or input window is too large) raises RuntimeError."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    if int(sr_in) == int(sr_out):
+        raise ValueError("resample_segments: sr_in == sr_out is a copy, not a resampling")
+    if stream.dtype != torch.float32 or stream.dim() != 1 or stream.device.type != "cuda" or not stream.is_contiguous():
+        raise ValueError("resample_segments: the stream is a contiguous 1-D float32 tensor on the GPU")
+    h, up, down = resample_filter(sr_in, sr_out)
+    dev = stream.device
+    key = (int(sr_in), int(sr_out), str(dev))
+    if key not in _filters_dev:
+        _filters_dev[key] = torch.from_numpy(h).to(dev)
+    hd = _filters_dev[key]
+    n_seg = len(starts)
+    ms = [(int(n) * up + down - 1) // down for n in lens]
+    if out is None:
+        if out_starts is not None:
+            raise ValueError("resample_segments: out_starts without out")
+        out_starts = [0] * n_seg
+        for s in range(1, n_seg):
+            out_starts[s] = out_starts[s - 1] + ms[s - 1]
+        out = torch.empty(max(1, sum(ms)), dtype=torch.float32, device=dev)
+    elif out_starts is None:
+        raise ValueError("resample_segments: out needs out_starts")
+    elif out.dtype != torch.float32 or out.dim() != 1 or out.device != dev or not out.is_contiguous():
+        raise ValueError("resample_segments: out is a contiguous 1-D float32 tensor on the stream's device")
+    pk = torch.empty(max(1, n_seg), dtype=torch.float32, device=dev) if peak else None
+    i32 = C.c_int32 * max(1, n_seg)
+    with torch.cuda.device(dev):
+        _lib.init(dev.index if dev.index is not None else torch.cuda.current_device())
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().gsv_op_resample_poly_seg(
+            stream.data_ptr(), int(stream.numel()), hd.data_ptr(), int(hd.numel()), up, down, n_seg, i32(*[int(v) for v in starts]),
+            i32(*[int(v) for v in lens]), i32(*[int(v) for v in out_starts]), out.data_ptr(), int(out.numel()),
+            pk.data_ptr() if peak else None, st), "gsv_op_resample_poly_seg")
+    return out, [(int(a), m) for a, m in zip(out_starts, ms)], pk
+
+
+RS_TILE, RS_LDS_FLOATS, RS_MAX_FILTER = 1024, 16384, 65535   # csrc/resample.hip: kRsTile, kRsLdsFloats, kRsMaxFilter
+
+
+def device_resample_supported(sr_in: int, sr_out: int) -> bool:
+    """whether gsv_op_resample_poly_seg takes this pair (include/gsv.h: its filter and its input window per tile fit the kernel)"""
+    h, up, down = resample_filter(sr_in, sr_out)
+    return len(h) <= RS_MAX_FILTER and ((RS_TILE - 1) * down + len(h) - 1) // up + 2 <= RS_LDS_FLOATS

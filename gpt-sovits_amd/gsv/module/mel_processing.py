@@ -99,6 +99,56 @@ def spectrogram_torch(y: torch.Tensor, n_fft: int, sampling_rate: int, hop_size:
     return spec.unsqueeze(0)
 
 
+@torch.no_grad()
+def spectrogram_torch_segments(stream: torch.Tensor, starts, lens, n_fft: int, sampling_rate: int, hop_size: int, win_size: int):
+    """spectrogram_torch of the audios stream[starts[s] : starts[s] + lens[s]] of one fp32 device vector (ascending, disjoint):
+    one gsv_op_frame_seg into a [sum T_s][n_fft] operand (each audio reflected at its own ends), ONE DFT GEMM at M = sum T_s, then
+    gsv_op_magnitude on each audio's row range -> a list of [1, n_fft // 2 + 1, T_s] fp32, in the order given.  An audio not
+    longer than the reflect padding raises ValueError before any launch."""
+    dev = stream.device
+    if dev.type != "cuda":
+        raise RuntimeError("gsv spectrograms run on an MI355X (cuda/HIP device) only")
+    if stream.dtype != torch.float32 or stream.dim() != 1 or not stream.is_contiguous():
+        raise ValueError("spectrogram_torch_segments: the stream is a contiguous 1-D float32 tensor")
+    if len(starts) != len(lens) or len(lens) == 0:
+        raise ValueError("spectrogram_torch_segments: starts and lens are two lists of one length >= 1")
+    pad = int((n_fft - hop_size) / 2)
+    bins = n_fft // 2 + 1
+    Ts, rows = [], []
+    for n in lens:
+        n = int(n)
+        if n <= pad:
+            raise ValueError(f"waveform of {n} samples is shorter than the reflect padding {pad}")
+        rows.append(sum(Ts))
+        Ts.append((n + 2 * pad - n_fft) // hop_size + 1)
+        if Ts[-1] < 1:
+            raise ValueError(f"waveform of {n} samples is shorter than one frame of {n_fft}")
+    M, n_seg = sum(Ts), len(lens)
+    i32 = C.c_int32 * n_seg
+    with torch.cuda.device(dev):
+        l = _lib.lib()
+        _lib.init(dev.index if dev.index is not None else torch.cuda.current_device())
+        basis = _dft_basis(n_fft, win_size, dev)
+        frames = torch.empty(M, n_fft, dtype=torch.float32, device=dev)
+        ri = torch.empty(M, 2 * bins, dtype=torch.float32, device=dev)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(l.gsv_op_frame_seg(stream.data_ptr(), int(stream.numel()), n_fft, hop_size, pad, n_fft, n_seg,
+                                      i32(*[int(v) for v in starts]), i32(*[int(v) for v in lens]), i32(*rows), i32(*Ts), M,
+                                      frames.data_ptr(), _lib.dtype_code(torch.float32), st), "gsv_op_frame_seg")
+        d = _lib.ConvDesc()
+        d.x, d.w, d.y = frames.data_ptr(), basis.data_ptr(), ri.data_ptr()
+        d.T_in = d.T_out = M
+        d.Cin, d.Cout, d.taps, d.stride, d.dil, d.pad = n_fft, 2 * bins, 1, 1, 1, 0
+        d.scale, d.out_f32 = 1.0, 1
+        _lib.check(l.gsv_op_conv1d(C.byref(d), _lib.dtype_code(torch.float32), st), "gsv_op_conv1d (DFT)")
+        out = []
+        for r0, T in zip(rows, Ts):
+            spec = torch.empty(bins, T, dtype=torch.float32, device=dev)
+            _lib.check(l.gsv_op_magnitude(ri[r0:r0 + T].data_ptr(), T, bins, 1e-8, 0, spec.data_ptr(), st), "gsv_op_magnitude")
+            out.append(spec.unsqueeze(0))
+    return out
+
+
 # ---- mel spectrogram of the v3 / v4 reference audio (reference module/mel_processing.py:93-143) -------------------------
 def _hz_to_mel(f):
     """Slaney scale (librosa.convert.hz_to_mel, htk=False): linear below 1 kHz (200/3 Hz per mel), logarithmic above"""

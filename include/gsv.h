@@ -586,6 +586,31 @@ int gsv_op_zero_rows(const gsv_zero_maps* maps, int n_maps, int T, int ld, const
                      gsv_stream_t stream);
 int gsv_op_time_mean_seg(const float* x, int T, int ld, int n_seg, const int32_t* seg_start, const int32_t* seg_len, float* out,
                          gsv_stream_t stream);
+/* the device front-end of a voice enrolment (TTS.make_voices(device_frontend=True)): the reference audios
+ * lie back to back in one fp32 stream.
+ * gsv_op_resample_poly_seg: rational polyphase FIR resampling of n_seg segments of x [dev] fp32 [n_x] into y [dev] fp32 [n_y], the
+ *   arithmetic of scipy.signal.resample_poly(x, up, down, padtype="constant") with the filter handed in: h [dev] fp32 [h_len],
+ *   h_len = 2 * half + 1 (odd); the op designs nothing.  Segment s = x[in_start[s] .. + in_len[s]) has m_s = ceil(in_len[s] * up /
+ *   down) outputs at y[out_start[s] .. + m_s):  y_s[i] = sum_j h[i * down + half - j * up] * x_s[j] over the j in [0, in_len[s])
+ *   whose filter index lies in [0, h_len) -- samples of other segments never enter, the edges see zeros.  One fp32 accumulator per
+ *   output over its taps in ascending j (fused multiply-add): a segment's output bits depend on its own samples alone, not on its
+ *   position, its neighbours or the call's other segments.  Elements of y outside every output range are left as they are.
+ *   peak [dev] fp32 [n_seg] or NULL: peak[s] = max_i |y_s[i]| (the call zeroes it first).  in_start / in_len / out_start [host]
+ *   travel like gsv_op_flash_attn64_seg's table: the call neither waits nor allocates.  GSV_ERR_ARG before any launch: n_seg
+ *   outside 1 .. 8192, a length < 1, up or down < 1, an even h_len, input or output ranges that overlap, descend or leave
+ *   [0, n_x) / [0, n_y), h_len > 65535, or an input window per 1024 outputs ((1023 * down + h_len - 1) / up + 2 samples) above
+ *   16384.  The filter is staged in LDS when window + h_len <= 16384 floats (every pair among 16 / 22.05 / 24 / 32 / 44.1 / 48 kHz
+ *   with resample_poly's default filter, h_len = 20 * max(up, down) + 1 <= 12801), else it is read through L2.
+ * gsv_op_frame_seg: gsv_op_frame per segment: rows [row_start[s], row_start[s] + row_len[s]) of out [dev] [rows][ld] of dtype hold
+ *   x[x_start[s] + reflect_s(t * hop + k - pad)], t counted from the segment's first row, reflected at the segment's own ends,
+ *   zero up to ld -- the bits of gsv_op_frame on that audio alone.  Rows outside every range are left as they are.  x_start /
+ *   x_len / row_start / row_len [host], 1 .. 8192 segments, sample and row ranges disjoint and ascending inside [0, n_x) and
+ *   [0, rows), pad < x_len[s], and the frames of a segment inside its padded signal; else GSV_ERR_ARG.  One launch. */
+int gsv_op_resample_poly_seg(const float* x, int n_x, const float* h, int h_len, int up, int down, int n_seg, const int32_t* in_start,
+                             const int32_t* in_len, const int32_t* out_start, float* y, int n_y, float* peak, gsv_stream_t stream);
+int gsv_op_frame_seg(const float* x, int n_x, int frame_len, int hop, int pad, int ld, int n_seg, const int32_t* x_start,
+                     const int32_t* x_len, const int32_t* row_start, const int32_t* row_len, int rows, void* out, int dtype,
+                     gsv_stream_t stream);
 /* sampling kernel alone: logits [dev] fp32 [B][vocab], prev [dev] int32 [B][prev_len], noise [dev]
  * fp32 [B][vocab] or NULL; outputs [dev] int32 [B]: sampled token, argmax of penalised logits */
 int gsv_op_sample(const float* logits, int B, int vocab, int vocab_eff, const int32_t* prev, int prev_len,

@@ -8,7 +8,13 @@ with the host part (load + resample, timed alone) and the rest (device part) rep
 around work that ends in a device synchronise, medians of --reps runs after --warmup runs (measurement tool, not product code;
 not part of bench.py).
 
+--device-frontend: only the front-end comparison of DESIGN.md section 4m, on --voices WAV files of 6 s at each of --rates: (a) host
+load_wav alone, (b) host load + resample alone (the prompt's, as above, and with the spectrogram's second read and resampling),
+(c) make_voices, (d) make_voices(device_frontend=True), (c) and (d) alternating, and (e) the resample launches alone by device
+events against their byte floor (input + output at 6.3 TB/s).
+
     python tools/voice_enrol_bench.py > profiles/voice_enrol.json         # prints one JSON line
+    python tools/voice_enrol_bench.py --device-frontend > profiles/device_frontend.json
 """
 import argparse
 import ctypes as C
@@ -35,6 +41,8 @@ ap.add_argument("--counts", type=int, nargs="*", default=[1, 8, 32])
 ap.add_argument("--seconds", type=float, nargs="*", default=[3, 6, 10])
 ap.add_argument("--sweep", type=int, nargs="*", default=[2 ** 19, 2 ** 20, 2 ** 21, 2 ** 22, 2 ** 23])
 ap.add_argument("--voices", type=int, default=32, help="WAV files of the pipeline pair (0: skip it)")
+ap.add_argument("--device-frontend", action="store_true", help="only the host / device front-end comparison (DESIGN.md 4m)")
+ap.add_argument("--rates", type=int, nargs="*", default=[32000, 44100], help="file rates of --device-frontend")
 args = ap.parse_args()
 if not torch.cuda.is_available():
     sys.exit("voice_enrol_bench needs the MI355X: there is no CPU path to time")
@@ -71,6 +79,100 @@ def median_pair(a, b):
         ta.append(timed(a)); tb.append(timed(b))
     return statistics.median(ta), statistics.median(tb), max(ta) - min(ta), max(tb) - min(tb)
 
+
+def make_tts():
+    from gsv.TTS_infer_pack.TTS import TTS
+    tts = TTS({"device": DEV, "is_half": True, "version": "v2", "max_batch": 4, "max_seq": 600})
+    tts.init_t2s_weights(state={"weight": S.make_t2s_state_dict(S.T2S_V2_CONFIG, seed=0, suppress_eos=True), "config": S.T2S_V2_CONFIG})
+    tts.init_vits_weights(state={"weight": S.make_vits_state_dict(S.VITS_V2_CONFIG, seed=0), "config": dict(S.VITS_V2_CONFIG)})
+    tts.init_cnhuhbert_weights(state_dict=hubert_sd)
+    return tts
+
+
+def write_wavs(d, n, sr):
+    specs = []
+    for k in range(n):
+        p = os.path.join(d, f"v{sr}_{k}.wav")
+        wav = S.make_waveform(6 * sr + 411 * k, 200 + k, sr=sr).numpy()
+        with wave.open(p, "wb") as f:
+            f.setnchannels(1); f.setsampwidth(2); f.setframerate(sr)
+            f.writeframes((np.clip(wav, -1, 1) * 32767).astype("<i2").tobytes())
+        specs.append({"ref_audio_path": p})
+    return specs
+
+
+def device_frontend_bench():
+    from gsv import audio_io as A
+    tts = make_tts()
+    out = []
+    with tempfile.TemporaryDirectory() as d:
+        for sr in args.rates:
+            specs = write_wavs(d, args.voices, sr)
+            paths = [sp["ref_audio_path"] for sp in specs]
+            sr_model = tts.configs.sampling_rate
+
+            def fresh():
+                tts.__dict__.pop("_voice_lru", None)
+
+            def load_only():
+                return [A.load_wav(p) for p in paths]
+
+            def host_prompt():
+                return [tts._prompt_wav16k(p) for p in paths]
+
+            def host_all():                                   # what make_voices does on the host per voice: two reads, two rates
+                for p in paths:
+                    tts._prompt_wav16k(p)
+                    raw, raw_sr = A.load_wav(p)
+                    A.resample(raw[:1], raw_sr, sr_model)
+
+            def host_path():
+                fresh()
+                return tts.make_voices(specs)
+
+            def device_path():
+                fresh()
+                return tts.make_voices(specs, device_frontend=True)
+
+            va, vb = host_path(), device_path()
+            same = sum(bool(torch.equal(x["prompt_semantic"], y["prompt_semantic"])) for x, y in zip(va, vb))
+            spec_diff = max(float((x["refer_spec"][0][0].float() - y["refer_spec"][0][0].float()).abs().max()) for x, y in zip(va, vb))
+            ta, tb, sa, sb = median_pair(load_only, host_prompt)
+            tball, _, sball, _ = median_pair(host_all, host_all)
+            tc, td, sc, sd = median_pair(host_path, device_path)
+            # (e) the resample launches alone, by device events
+            raws = [A.load_wav(p)[0][0] for p in paths]
+            stream = torch.from_numpy(np.concatenate(raws)).to(DEV)
+            lens = [int(r.shape[0]) for r in raws]
+            starts = [0] + list(np.cumsum(lens)[:-1])
+            targets = sorted({16000, sr_model} - {sr})
+
+            def launches():
+                for t in targets:
+                    A.resample_segments(stream, starts, lens, sr, t, peak=True)
+
+            for _ in range(3):
+                launches()
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.reps)]
+            for a, b in ev:
+                a.record(); launches(); b.record()
+            torch.cuda.synchronize()
+            e_ms = statistics.median(a.elapsed_time(b) for a, b in ev)
+            e_bytes = sum(4 * (sum(lens) + sum(A.resampled_len(n, sr, t) for n in lens)) for t in targets)
+            out.append({"file_rate": sr, "voices": args.voices, "seconds": 6, "a_load_wav_ms": round(ta, 3), "a_spread_ms": round(sa, 3),
+                        "b_load_resample_prompt_ms": round(tb, 3), "b_spread_ms": round(sb, 3),
+                        "b_load_resample_prompt_and_spec_ms": round(tball, 3), "b_all_spread_ms": round(sball, 3),
+                        "c_make_voices_ms": round(tc, 3), "c_spread_ms": round(sc, 3),
+                        "d_make_voices_device_frontend_ms": round(td, 3), "d_spread_ms": round(sd, 3),
+                        "e_resample_launches": len(targets), "e_resample_ms": round(e_ms, 4), "e_bytes": e_bytes,
+                        "e_floor_ms_at_6.3_tb_per_s": round(e_bytes / 6.3e9, 5),
+                        "voices_with_equal_prompt_codes": same, "max_abs_spec_diff": round(spec_diff, 5)})
+    return {"tool": "voice_enrol_bench --device-frontend", "device": torch.cuda.get_device_name(0), "reps": args.reps, "rates": out}
+
+
+if args.device_frontend:
+    print(json.dumps(device_frontend_bench()))
+    sys.exit(0)
 
 rows = []
 for sec in args.seconds:

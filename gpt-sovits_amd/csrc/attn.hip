@@ -483,6 +483,7 @@ int launch_flash_rel96_f16(const void* q, int ldq, const void* k, int ldk, const
   const int ldv = (T + 31) / 32 * 32;
   hipLaunchKernelGGL(vt96_kernel, dim3(ldv / 32, 3, heads), dim3(256), 0, s, (const _Float16*)v, ldvv, T, ldv, (_Float16*)vt_buf);
   constexpr int QT = 2;
+  set_attn_route(ATTN_REL96, QT);
   const size_t lds = ((size_t)4 * 16 * QT * 100 + 8 * 16 * QT + 2 * 16 * QT * 9) * 4;
   static bool attr = false;
   if (!attr) {
@@ -499,8 +500,9 @@ int launch_flash_rel96_f16(const void* q, int ldq, const void* k, int ldk, const
 // starts xz elements after row b-1, of out oz elements after; vt_buf: rows * vtz halfs of scratch, vtz >= heads * 64 * ceil32(T)
 int launch_flash_attn64_f16_rows(const void* q, int ldq, const void* k, int ldk, const void* v, int ldvv, void* vt_buf, int T, int heads,
                                  float scale, void* out, int ldo, hipStream_t s, const float* rope_cs, int rope_half, int rows,
-                                 long long xz, long long vtz, long long oz) {
+                                 long long xz, long long vtz, long long oz, int qt_arg) {
   GSV_REQUIRE(T >= 1 && heads >= 1 && rows >= 1, "flash_attn: empty problem");
+  GSV_REQUIRE(qt_arg == 0 || qt_arg == 1 || qt_arg == 2 || qt_arg == 4, "flash_attn: qt %d is not 0 (by shape), 1, 2 or 4", qt_arg);
   GSV_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldo % 4 == 0 && ((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)out % 8) == 0,
               "flash_attn: operands must be 16-byte aligned with leading dims multiple of 8");
   const int ldv = (T + 31) / 32 * 32;
@@ -513,7 +515,9 @@ int launch_flash_attn64_f16_rows(const void* q, int ldq, const void* k, int ldk,
   static const int qt_env = getenv("GSV_FLASH_QT") ? atoi(getenv("GSV_FLASH_QT")) : 0;     // A/B switch
   // more query tiles per workgroup = fewer K / V fragment loads per query, but fewer workgroups: keep >= ~1 per CU.  Chosen
   // from ONE row's size whatever `rows` is, so that a row computes the same bits alone and in a batch.
-  int qt = qt_env ? qt_env : ((long long)cdiv(T, 64) * heads >= 200 ? 4 : ((long long)cdiv(T, 32) * heads >= 200 ? 2 : 1));
+  // qt_arg (test hooks): one instantiation, whatever the rule and the switch say
+  int qt = qt_arg ? qt_arg : qt_env ? qt_env : ((long long)cdiv(T, 64) * heads >= 200 ? 4 : ((long long)cdiv(T, 32) * heads >= 200 ? 2 : 1));
+  set_attn_route(ATTN_ROWS, qt >= 4 ? 4 : qt >= 2 ? 2 : 1);
   if (qt >= 4) return launch_flash_qt<4>(q, ldq, k, ldk, vt_buf, ldv, T, heads, scale, out, ldo, s, rows, xz, vtz, oz);
   if (qt >= 2) return launch_flash_qt<2>(q, ldq, k, ldk, vt_buf, ldv, T, heads, scale, out, ldo, s, rows, xz, vtz, oz);
   return launch_flash_qt<1>(q, ldq, k, ldk, vt_buf, ldv, T, heads, scale, out, ldo, s, rows, xz, vtz, oz);
@@ -528,8 +532,9 @@ int launch_flash_attn64_f16(const void* q, int ldq, const void* k, int ldk, cons
 // segmented kernel); vt_buf: heads * 64 * 32 * sum ceil(T_s / 32) halfs of scratch.  The segment table goes to the device through
 // the library context's staging slots (engine.h): one small async copy on `s`, none when `s` already carries the same table.
 int launch_flash_attn64_f16_seg(const void* q, int ldq, const void* k, int ldk, const void* v, int ldvv, void* vt_buf, int n_seg,
-                                const int* seg_lens, int heads, float scale, void* out, int ldo, hipStream_t s) {
+                                const int* seg_lens, int heads, float scale, void* out, int ldo, hipStream_t s, int qt_arg) {
   GSV_REQUIRE(q && k && v && vt_buf && out && seg_lens, "flash_attn_seg: null argument");
+  GSV_REQUIRE(qt_arg == 0 || qt_arg == 1 || qt_arg == 2 || qt_arg == 4, "flash_attn_seg: qt %d is not 0 (by shape), 1, 2 or 4", qt_arg);
   GSV_REQUIRE(n_seg >= 1 && heads >= 1 && heads <= 65535, "flash_attn_seg: %d segments, %d heads", n_seg, heads);
   GSV_REQUIRE(n_seg <= gsveng::kSegTableMax, "flash_attn_seg: %d segments exceed the table's %d", n_seg, gsveng::kSegTableMax);
   GSV_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldo % 4 == 0 && ((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)out % 8) == 0 &&
@@ -542,7 +547,7 @@ int launch_flash_attn64_f16_seg(const void* q, int ldq, const void* k, int ldk, 
   GSV_REQUIRE(rows + 32LL * n_seg <= 0x7fffffffLL, "flash_attn_seg: %lld rows exceed the index range", rows);
   static const int qt_env = getenv("GSV_FLASH_QT") ? atoi(getenv("GSV_FLASH_QT")) : 0;     // A/B switch, as for the rows
   // the row kernel's rule on the packed problem: keep >= ~1 workgroup per CU.  Tiles are counted per segment, so the counts are sums.
-  const int qt = qt_env ? (qt_env >= 4 ? 4 : qt_env >= 2 ? 2 : 1) : (t64 * heads >= 200 ? 4 : (t32 * heads >= 200 ? 2 : 1));
+  const int qt = qt_arg ? qt_arg : qt_env ? (qt_env >= 4 ? 4 : qt_env >= 2 ? 2 : 1) : (t64 * heads >= 200 ? 4 : (t32 * heads >= 200 ? 2 : 1));
   gsveng::SegTable tb;                              // holds the library context until it goes out of scope
   GSV_RC(gsveng::seg_table_begin(&tb));
   long long row0 = 0, col0 = 0, tile0 = 0;
@@ -556,6 +561,7 @@ int launch_flash_attn64_f16_seg(const void* q, int ldq, const void* k, int ldk, 
   GSV_RC(gsveng::seg_table_upload(&tb, n_seg, s));
   const int4* tab = (const int4*)tb.dev;
   GSV_LAUNCH(vt_seg_kernel, dim3(ldv / 32, 2, heads), dim3(256), 0, s, (const _Float16*)v, ldvv, tab, n_seg, ldv, (_Float16*)vt_buf);
+  set_attn_route(ATTN_SEG, qt);
   int rc;
   if (qt == 4) rc = launch_flash_seg_qt<4>(q, ldq, k, ldk, vt_buf, ldv, tab, n_seg, tiles, heads, scale, out, ldo, s);
   else if (qt == 2) rc = launch_flash_seg_qt<2>(q, ldq, k, ldk, vt_buf, ldv, tab, n_seg, tiles, heads, scale, out, ldo, s);

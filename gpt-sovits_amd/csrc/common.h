@@ -239,6 +239,11 @@ int launch_conv_pair64(const ConvPairArgs& a, hipStream_t s);   // conv_pair64.h
 // 0, as after convs1 -> row pass -> convs2 -> row pass.  row_seg travels beside ConvPairArgs, whose layout the unmasked kernels keep.
 int launch_conv_pair_seg(const ConvPairArgs& a, const int* row_seg, hipStream_t s);
 
+// Attention route record (gsv_debug_last_attn_route): every attention launcher stores which family it launched and with how
+// many 16-query tiles per workgroup (0 for the materialised path).  A plain store on the host, as set_conv_route.
+enum { ATTN_ROWS = 1, ATTN_SEG = 2, ATTN_REL96 = 3, ATTN_MAT = 4 };
+void set_attn_route(int family, int qt);
+
 // fused attention, fp16, head dim 64 (attn.hip); vt_buf: heads * 64 * ceil32(T) halfs of scratch
 // rope_cs != null: rotate the first 2*rope_half channels of q and k in place first (cos|sin table [T][rope_half][2])
 int launch_flash_attn64_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* vt_buf, int T, int heads,
@@ -247,12 +252,14 @@ int launch_flash_attn64_f16(const void* q, int ldq, const void* k, int ldk, cons
 // its output oz elements after, its V^T scratch vtz halfs after (vtz >= heads * 64 * ceil32(T))
 int launch_flash_attn64_f16_rows(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* vt_buf, int T, int heads,
                                  float scale, void* out, int ldo, hipStream_t s, const float* rope_cs, int rope_half, int rows,
-                                 long long xz, long long vtz, long long oz);
+                                 long long xz, long long vtz, long long oz, int qt = 0);
+// qt (both launchers): 0 = query tiles per workgroup by the launcher's rule (and the GSV_FLASH_QT switch), 1 / 2 / 4 = that
+// instantiation (test hooks)
 
 // the segmented form: n_seg sequences of seg_lens[s] ([host]) rows back to back, each attending to its own keys only, in the same
 // two launches; vt_buf: heads * 64 * 32 * sum ceil(seg_lens[s] / 32) halfs of scratch (may arrive uninitialised)
 int launch_flash_attn64_f16_seg(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* vt_buf, int n_seg,
-                                const int* seg_lens, int heads, float scale, void* out, int ldo, hipStream_t s);
+                                const int* seg_lens, int heads, float scale, void* out, int ldo, hipStream_t s, int qt = 0);
 
 // enc_p self-attention with window-4 relative positions, fp16, head dim 96 (attn.hip)
 int launch_flash_rel96_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* vt_buf, int T, int heads,

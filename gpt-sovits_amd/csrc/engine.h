@@ -88,6 +88,13 @@ int conv(Ctx* h, hipStream_t s, const Conv& c, const void* x, int ldx, int T_in,
 int attention(Ctx* h, hipStream_t s, const void* q, int ldq, int qcol0, const void* kv, int ldkv, int kcol0, int vcol0,
               int Tq, int Tk, int nh, int kc, float scale, const float* rel_k, const float* rel_v, void* out, int ldo,
               const int* kr = nullptr);   // kr: per-query key range [kr[2i], kr[2i+1]) (segmented decode)
+// attention()'s choice (the GSV_MATERIALIZED_ENC_ATTN switch included) and its two routes: fused = the flash_rel96 kernel
+// (fp16, kc 96, both relative tables, Tq == Tk), else the materialised path in the handle's element type
+bool attention_is_fused(const Ctx* h, const void* q, int ldq, const void* kv, int ldkv, int Tq, int Tk, int kc, const float* rel_k,
+                        const float* rel_v);
+int attention_routed(Ctx* h, hipStream_t s, const void* q, int ldq, int qcol0, const void* kv, int ldkv, int kcol0, int vcol0,
+                     int Tq, int Tk, int nh, int kc, float scale, const float* rel_k, const float* rel_v, void* out, int ldo,
+                     const int* kr, bool fused);
 // releases allocs and bufs: the one place that does; a destroy function adds what its own handle owns
 void free_ctx(Ctx* h);
 // fp32 channels-first [C][Tn] -> engine dtype channels-last [Tn][ldd] (first C columns; ldd = 0: C)

@@ -348,6 +348,7 @@ static int attention_mat(Ctx* h, hipStream_t s, const void* q, int ldq, int qcol
   GSV_RC(need(h, "att_P", (size_t)nh * Tq * ldp * es, &P));
   GSV_RC(need(h, "att_Vt", (size_t)nh * kc * ldp * es, &Vt));
   GSV_RC(need(h, "att_band", (size_t)nh * Tq * 9 * 4 + 64, &band));
+  set_attn_route(ATTN_MAT, 0);
   ConvArgs a;
   a.x = (const char*)q + (size_t)qcol0 * es; a.w = (const char*)kv + (size_t)kcol0 * es; a.y = scores;
   a.T_in = Tq; a.T_out = Tq; a.T_virt = Tq; a.Cin = kc; a.Cout = Tk; a.taps = 1;
@@ -368,13 +369,27 @@ static int attention_mat(Ctx* h, hipStream_t s, const void* q, int ldq, int qcol
   return GSV_OK;
 }
 
+// attention()'s choice: the fused fp16 kernel where it applies (the static switch is read once per process)
+bool attention_is_fused(const Ctx* h, const void* q, int ldq, const void* kv, int ldkv, int Tq, int Tk, int kc, const float* rel_k,
+                        const float* rel_v) {
+  static const bool no_flash = getenv("GSV_MATERIALIZED_ENC_ATTN") != nullptr;    // A/B switch
+  return !no_flash && h->dtype == GSV_F16 && kc == 96 && rel_k && rel_v && Tq == Tk && q == kv && ldq == ldkv;
+}
+
 // multi-head attention: q [Tq][ldq] cols qcol0.., k/v [Tk][ldkv] cols kcol0/vcol0.. -> out [Tq][ldo] (heads concatenated).
 // rel_k/rel_v non-null: window-4 relative positions.  Called with the handle's runtime dtype (also from cfm.hip and bwe.hip):
 // the fused fp16 kernel where it applies, else the materialised path in the handle's element type.
 int attention(Ctx* h, hipStream_t s, const void* q, int ldq, int qcol0, const void* kv, int ldkv, int kcol0, int vcol0,
               int Tq, int Tk, int nh, int kc, float scale, const float* rel_k, const float* rel_v, void* out, int ldo, const int* kr) {
-  static const bool no_flash = getenv("GSV_MATERIALIZED_ENC_ATTN") != nullptr;    // A/B switch
-  if (!no_flash && h->dtype == GSV_F16 && kc == 96 && rel_k && rel_v && Tq == Tk && q == kv && ldq == ldkv) {
+  return attention_routed(h, s, q, ldq, qcol0, kv, ldkv, kcol0, vcol0, Tq, Tk, nh, kc, scale, rel_k, rel_v, out, ldo, kr,
+                          attention_is_fused(h, q, ldq, kv, ldkv, Tq, Tk, kc, rel_k, rel_v));
+}
+
+// the two routes of attention(): what the engines (through the wrapper above) and gsv_op_attention (the test hook) launch through
+int attention_routed(Ctx* h, hipStream_t s, const void* q, int ldq, int qcol0, const void* kv, int ldkv, int kcol0, int vcol0,
+                     int Tq, int Tk, int nh, int kc, float scale, const float* rel_k, const float* rel_v, void* out, int ldo, const int* kr,
+                     bool fused) {
+  if (fused) {
     void* vtb;
     GSV_RC(need(h, "att_vt96", (size_t)nh * 96 * ((Tk + 31) / 32 * 32) * 2, &vtb));
     return launch_flash_rel96_f16((const _Float16*)q + qcol0, ldq, (const _Float16*)kv + kcol0, ldkv, (const _Float16*)kv + vcol0, ldkv,

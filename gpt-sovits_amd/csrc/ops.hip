@@ -19,6 +19,8 @@ void set_conv_route(unsigned long long code) {
   g_conv_route = code;
   if ((code & 255) == ROUTE_CONV_PAIR) g_pair_route = code;
 }
+static thread_local unsigned g_attn_route = 0;             // family | qt << 8 of the last attention launch (common.h)
+void set_attn_route(int family, int qt) { g_attn_route = (unsigned)(family & 255) | (unsigned)(qt & 255) << 8; }
 
 template <typename T> __global__ void convert_kernel(const float* __restrict__ s, T* __restrict__ d, long long n) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -352,6 +354,11 @@ uint64_t gsv_debug_last_pair_route(int reset) {
   if (reset) gsv::g_pair_route = 0;
   return r;
 }
+uint64_t gsv_debug_last_attn_route(int reset) {
+  const uint64_t r = gsv::g_attn_route;
+  if (reset) gsv::g_attn_route = 0;
+  return r;
+}
 int gsv_init(int device) {
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
@@ -389,6 +396,77 @@ int gsv_op_flash_attn64_seg(const void* qkv, int n_seg, const int32_t* seg_lens,
   const int inner = heads * 64;
   return gsv::launch_flash_attn64_f16_seg(qkv, 3 * inner, (const _Float16*)qkv + inner, 3 * inner, (const _Float16*)qkv + 2 * inner,
                                           3 * inner, vt_scratch, n_seg, seg_lens, heads, scale, out, inner, (hipStream_t)stream);
+}
+
+int gsv_op_flash_attn64_rows(const void* qkv, int T, int heads, int rows, float scale, const float* rope_cs, int rope_half, int qt,
+                             void* vt_scratch, void* out, gsv_stream_t stream) {
+  GSV_REQUIRE(qkv && vt_scratch && out, "op_flash_attn64_rows: null pointer");
+  GSV_REQUIRE(T >= 1 && rows >= 1 && heads >= 1, "op_flash_attn64_rows: bad shape T=%d rows=%d heads=%d", T, rows, heads);
+  GSV_REQUIRE(qt == 0 || qt == 1 || qt == 2 || qt == 4, "op_flash_attn64_rows: qt %d is not 0 (by shape), 1, 2 or 4", qt);
+  GSV_REQUIRE((long long)heads * 64 * 3 * ((long long)T + 8) <= 0x7fffffffLL, "op_flash_attn64_rows: T=%d x heads=%d exceeds the index range", T, heads);
+  const int inner = heads * 64;
+  GSV_REQUIRE(rope_half >= 0 && 2 * (long long)rope_half <= inner, "op_flash_attn64_rows: rope_half %d outside [0, %d]", rope_half, inner / 2);
+  GSV_REQUIRE(rope_cs || rope_half == 0, "op_flash_attn64_rows: rope_half %d without a cos / sin table", rope_half);
+  const int ld = 3 * inner, ldv = (T + 31) / 32 * 32;
+  const long long xz = ((long long)T + 8) * ld, vtz = (long long)inner * ldv + 64, oz = ((long long)T + 8) * inner;
+  return gsv::launch_flash_attn64_f16_rows(qkv, ld, (const _Float16*)qkv + inner, ld, (const _Float16*)qkv + 2 * inner, ld, vt_scratch, T, heads,
+                                           scale, out, inner, (hipStream_t)stream, rope_cs, rope_cs ? rope_half : 0, rows, xz, vtz, oz, qt);
+}
+
+int gsv_op_flash_attn64_seg_qt(const void* qkv, int n_seg, const int32_t* seg_lens, int heads, float scale, int qt, void* vt_scratch,
+                               void* out, gsv_stream_t stream) {
+  const int inner = heads * 64;
+  return gsv::launch_flash_attn64_f16_seg(qkv, 3 * inner, (const _Float16*)qkv + inner, 3 * inner, (const _Float16*)qkv + 2 * inner,
+                                          3 * inner, vt_scratch, n_seg, seg_lens, heads, scale, out, inner, (hipStream_t)stream, qt);
+}
+
+int gsv_op_attention(const void* q, int ldq, int qcol0, const void* kv, int ldkv, int kcol0, int vcol0, int Tq, int Tk, int heads, int kc,
+                     float scale, const float* rel_k, const float* rel_v, const int32_t* kr, int dtype, int route, void* out, int ldo,
+                     gsv_stream_t stream) {
+  GSV_REQUIRE(q && kv && out, "op_attention: null pointer");
+  GSV_REQUIRE(dtype == GSV_F16 || dtype == GSV_F32, "op_attention: bad dtype %d", dtype);
+  GSV_REQUIRE(route >= 0 && route <= 2, "op_attention: unknown route %d", route);
+  GSV_REQUIRE(Tq >= 1 && Tk >= 1 && heads >= 1 && heads <= 65535 && kc >= 1, "op_attention: bad shape Tq=%d Tk=%d heads=%d kc=%d", Tq, Tk, heads, kc);
+  GSV_REQUIRE(qcol0 >= 0 && kcol0 >= 0 && vcol0 >= 0 && (long long)qcol0 + (long long)heads * kc <= ldq &&
+              (long long)(kcol0 > vcol0 ? kcol0 : vcol0) + (long long)heads * kc <= ldkv && (long long)heads * kc <= ldo,
+              "op_attention: the head columns do not fit the leading dimensions");
+  GSV_REQUIRE((long long)heads * Tq * Tk <= 0x7fffffffLL / 4, "op_attention: %d x %d x %d scores exceed the index range", heads, Tq, Tk);
+  GSV_REQUIRE(!rel_k == !rel_v, "op_attention: rel_k and rel_v come together");
+  if (route == 1) {
+    GSV_REQUIRE(dtype == GSV_F16, "op_attention: route 1 (fused) is fp16 only");
+    GSV_REQUIRE(kc == 96, "op_attention: route 1 (fused) is built for kc 96, not %d", kc);
+    GSV_REQUIRE(rel_k && rel_v, "op_attention: route 1 (fused) needs rel_k and rel_v");
+    GSV_REQUIRE(Tq == Tk, "op_attention: route 1 (fused) needs Tq == Tk");
+  }
+  gsveng::Ctx c("op_attention");
+  c.dtype = dtype;
+  const bool fused = route == 1 || (route == 0 && gsveng::attention_is_fused(&c, q, ldq, kv, ldkv, Tq, Tk, kc, rel_k, rel_v));
+  if (kr) {
+    for (int i = 0; i < Tq; ++i) {
+      const int lo = kr[2 * i], hi = kr[2 * i + 1];
+      GSV_REQUIRE(lo >= 0 && hi <= Tk && lo <= hi, "op_attention: key range [%d, %d) of query %d leaves [0, %d]", lo, hi, i, Tk);
+      // the fused kernel skips the chunks in front of its first row's lo and behind its last row's hi, and divides by the row's mass
+      GSV_REQUIRE(!fused || (lo < hi && (i == 0 || (lo >= kr[2 * i - 2] && hi >= kr[2 * i - 1]))),
+                  "op_attention: key range [%d, %d) of query %d is empty or descends (the fused kernel needs non-decreasing, non-empty ranges)",
+                  lo, hi, i);
+    }
+  }
+  hipStream_t s = (hipStream_t)stream;
+  int* d_kr = nullptr;
+  int rc = GSV_OK;
+  if (kr) {
+    if (hipMalloc((void**)&d_kr, (size_t)Tq * 8) != hipSuccess || hipMemcpy(d_kr, kr, (size_t)Tq * 8, hipMemcpyHostToDevice) != hipSuccess) {
+      gsv::set_error("op_attention: key-range upload failed");
+      rc = GSV_ERR_HIP;
+    }
+  }
+  if (!rc) {
+    rc = gsveng::attention_routed(&c, s, q, ldq, qcol0, kv, ldkv, kcol0, vcol0, Tq, Tk, heads, kc, scale, rel_k, rel_v, out, ldo, d_kr, fused);
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) { gsv::set_error("op_attention: a kernel failed"); rc = GSV_ERR_HIP; }
+  }
+  gsveng::free_ctx(&c);
+  (void)hipFree(d_kr);
+  return rc;
 }
 
 int gsv_op_embed_ln(const float* word, int n_word, const float* pos, int n_pos, const float* add, const int32_t* ids,

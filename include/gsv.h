@@ -452,6 +452,36 @@ int gsv_op_flash_attn64(const void* qkv, int T, int heads, float scale, void* vt
  * padding columns are written as 0).  n_seg < 1, n_seg > 8192 or a T_s < 1 is GSV_ERR_ARG. */
 int gsv_op_flash_attn64_seg(const void* qkv, int n_seg, const int32_t* seg_lens, int heads, float scale, void* vt_scratch, void* out,
                             gsv_stream_t stream);
+/* test hook: gsv_op_flash_attn64 over `rows` utterances of T frames in one call (launch_flash_attn64_f16_rows, the DiT's batched
+ * launch), with the rotary plane and a choice of kernel instantiation.  Strides are padded so that a stride mistake shows:
+ * qkv [dev] f16 [rows][T + 8][3*heads*64] (the 8 rows behind every utterance are never read), out [dev] f16 [rows][T + 8][heads*64]
+ * (the 8 rows are never written), vt_scratch [dev] rows * (heads*64*ceil32(T) + 64) halfs, may arrive uninitialised.  rope_cs
+ * [dev] fp32 [T][rope_half][2] (cos, sin) or NULL: q and k are rotated IN PLACE on the first 2*rope_half channels of the un-split
+ * projection (interleaved pairs (2p, 2p+1)) before the attention, every row with the same table.  qt: 0 = query tiles per
+ * workgroup by the launcher's rule (GSV_FLASH_QT included), 1 / 2 / 4 = that instantiation.  GSV_ERR_ARG before any launch: a null
+ * pointer, T / rows / heads < 1, qt outside {0, 1, 2, 4}, rope_half < 0 or 2*rope_half > heads*64, rope_half > 0 without a table. */
+int gsv_op_flash_attn64_rows(const void* qkv, int T, int heads, int rows, float scale, const float* rope_cs, int rope_half, int qt,
+                             void* vt_scratch, void* out, gsv_stream_t stream);
+/* test hook: gsv_op_flash_attn64_seg with the same qt argument */
+int gsv_op_flash_attn64_seg_qt(const void* qkv, int n_seg, const int32_t* seg_lens, int heads, float scale, int qt, void* vt_scratch,
+                               void* out, gsv_stream_t stream);
+/* test hook: one multi-head attention through the engines' own attention() (csrc/engine.hip) on a temporary context: it allocates
+ * the workspaces, uploads kr, waits for the kernels and frees.  q [dev] [Tq][ldq], head h at columns qcol0 + h*kc ..; kv [dev]
+ * [Tk][ldkv] with K at kcol0 + h*kc .. and V at vcol0 + h*kc ..; out [dev] [Tq][ldo]; dtype GSV_F16 / GSV_F32 applies to all
+ * three.  rel_k / rel_v [dev] fp32 [9][kc] or both NULL: window-4 relative positions (key j of query i at offset j - i).  kr [host] int32 [2*Tq] or
+ * NULL: query i sees keys [kr[2i], kr[2i+1]) only; an empty range gives a zero row on the materialised route.  route: 0 = what the
+ * engine takes (fused for fp16, kc 96, both tables, q == kv, ldq == ldkv, unless GSV_MATERIALIZED_ENC_ATTN is set), 1 = the fused
+ * flash_rel96 kernel, 2 = the materialised path (scores GEMM, row softmax, V transpose, PV GEMM, relative-value add).
+ * GSV_ERR_ARG before any launch: a null q / kv / out, an unknown route or dtype, a shape < 1, head columns outside a leading
+ * dimension, one relative table without the other, route 1 with GSV_F32, kc != 96, no tables or Tq != Tk, a key range outside
+ * [0, Tk] or with hi < lo, and on the fused route a range that is empty or whose lo or hi is below the previous query's (the
+ * kernel skips chunks by its first row's lo and last row's hi). */
+int gsv_op_attention(const void* q, int ldq, int qcol0, const void* kv, int ldkv, int kcol0, int vcol0, int Tq, int Tk, int heads, int kc,
+                     float scale, const float* rel_k, const float* rel_v, const int32_t* kr, int dtype, int route, void* out, int ldo,
+                     gsv_stream_t stream);
+/* test hook: the last attention launch on this thread (0 = none since the last reset): byte 0 = family (1 flash_attn64 rows,
+ * 2 flash_attn64 segmented, 3 flash_rel96, 4 materialised), byte 1 = 16-query tiles per workgroup (0 for family 4). */
+uint64_t gsv_debug_last_attn_route(int reset);
 /* BERT's embedding stage: y[i] = LayerNorm(word[ids[i]] + pos[pos_ids[i]] + add) * gamma + beta as f16 rows [rows][C]; word [dev]
  * fp32 [n_word][C], pos [dev] fp32 [n_pos][C], add [dev] fp32 [C] or NULL, ids / pos_ids [dev] int32 [rows], gamma / beta [dev] fp32
  * [C]; sums and statistics in fp32.  C <= 1024.  A row whose id or position is outside its table is stored as NaN. */

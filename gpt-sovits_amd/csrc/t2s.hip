@@ -15,6 +15,8 @@
 //    launches (QKV+append, out-proj, FFN1, FFN2) and one attention launch, LayerNorm fused into the consumer's prologue,
 //    split-K across the waves of a workgroup with an LDS combine (no global partials), then logits + a one-wave-per-row
 //    sampling kernel; the step is captured once per batch size and replayed as one hipGraph.
+// gsv_t2s_session_* (bottom of the engine section) run the same two paths a chunk of steps at a time over slots that are admitted
+// and freed one by one; their kernels are in t2s_session.hip.
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
@@ -891,6 +893,200 @@ int time_step(gsv_t2s* h, int iters, float* step_ms, float* attn_ms, hipStream_t
   return rc;
 }
 
+// ---- decode sessions (gsv_t2s_session_*): admit = prefill + step 0 in the staging copies, then the adopt launch; advance =
+// ---- the embedding rewrite, then run_mega / run_steps for a chunk.  Kernels in t2s_session.hip. ----
+
+// Points the handle at the session's staging copies of the arena and the row state for the lifetime of the object, so that the
+// prefill and launch_tail run unchanged on rows 0 .. n - 1 of the staging side; the destructor puts the session's own back.
+struct StagingScope {
+  gsv_t2s* h;
+  void* kv; size_t stride; int max_seq;
+  int *kv_len, *active, *step, *n_active, *ytok, *plen, *rng_row;
+  unsigned long long* rng_seed;
+  RowSampling* row_sampling; StepParams* sp;
+  float *ybuf, *logits;
+  int B, P, max_kv0;
+  StagingScope(gsv_t2s* h_, void* st_kv, size_t st_stride, int st_smax)
+      : h(h_), kv(h_->kv), stride(h_->kv_layer_stride), max_seq(h_->max_seq), kv_len(h_->d_kv_len), active(h_->d_active),
+        step(h_->d_step), n_active(h_->d_n_active), ytok(h_->d_ytok), plen(h_->d_plen), rng_row(h_->d_rng_row),
+        rng_seed(h_->d_rng_seed), row_sampling(h_->d_row_sampling), sp(h_->d_sp), ybuf(h_->ybuf), logits(h_->logits), B(h_->B),
+        P(h_->P), max_kv0(h_->max_kv0) {
+    const T2SSession& z = h->ses;
+    const size_t mb = (size_t)h->max_batch;
+    h->kv = st_kv; h->kv_layer_stride = st_stride; h->max_seq = st_smax;
+    h->d_kv_len = z.st_state; h->d_active = z.st_state + mb; h->d_step = z.st_state + 2 * mb; h->d_n_active = z.st_state + 3 * mb;
+    h->d_ytok = z.st_ytok; h->d_plen = z.st_plen; h->d_rng_row = z.st_rng_row; h->d_rng_seed = z.st_rng_seed;
+    h->d_row_sampling = z.st_row_sampling; h->d_sp = z.st_sp; h->ybuf = z.st_ybuf; h->logits = z.st_logits;
+  }
+  ~StagingScope() {
+    h->kv = kv; h->kv_layer_stride = stride; h->max_seq = max_seq;
+    h->d_kv_len = kv_len; h->d_active = active; h->d_step = step; h->d_n_active = n_active;
+    h->d_ytok = ytok; h->d_plen = plen; h->d_rng_row = rng_row; h->d_rng_seed = rng_seed;
+    h->d_row_sampling = row_sampling; h->d_sp = sp; h->ybuf = ybuf; h->logits = logits;
+    h->B = B; h->P = P; h->max_kv0 = max_kv0;
+  }
+};
+
+// the session's StepParams: its own arrays (staging = false) or the staging copies an admission's step 0 runs on
+StepParams session_params(const gsv_t2s* h, bool staging) {
+  const T2SSession& z = h->ses;
+  StepParams p;
+  memset(&p, 0, sizeof(p));
+  p.top_k = z.sp.top_k; p.top_p = z.sp.top_p; p.temperature = z.sp.temperature; p.rep_penalty = z.sp.repetition_penalty;
+  p.early_stop_num = z.sp.early_stop_num; p.eos_mask_steps = z.sp.eos_mask_steps; p.max_steps = z.sp.max_steps;
+  p.seed = z.sp.seed;
+  if (staging) {
+    p.out_tokens = z.st_out_tokens; p.out_len = z.st_out_len; p.plen = z.st_plen; p.rng_seed = z.st_rng_seed;
+    p.rng_row = z.st_rng_row; p.force = z.force ? z.st_force : nullptr; p.dump = z.dump ? z.st_dump : nullptr;
+    p.drawn = z.drawn ? z.st_drawn : nullptr; p.row_sampling = z.row_sampling ? z.st_row_sampling : nullptr;
+  } else {
+    p.out_tokens = z.out_tokens; p.out_len = z.out_len; p.plen = h->d_plen; p.rng_seed = h->d_rng_seed; p.rng_row = h->d_rng_row;
+    p.force = z.force; p.dump = z.dump; p.drawn = z.drawn; p.row_sampling = z.row_sampling ? h->d_row_sampling : nullptr;
+  }
+  return p;
+}
+
+int session_budget(const gsv_sampling_params& sp) {
+  int budget = sp.max_steps;
+  if (sp.early_stop_num >= 0 && sp.early_stop_num + 1 < budget) budget = sp.early_stop_num + 1;
+  return budget;
+}
+
+int session_begin(gsv_t2s* h, const gsv_sampling_params* sp, int slots, int row_sampling, int32_t* out_tokens, int32_t* out_len) {
+  T2SSession& z = h->ses;
+  const size_t mb = (size_t)h->max_batch, d = h->cfg.dim, V = h->cfg.vocab, ms = (size_t)sp->max_steps;
+  // staging copies of everything a prefill and a step-0 tail write (the staging K/V arena is sized by each admission)
+  GSV_RC(need(h, "ses_state", (3 * mb + 4) * 4, (void**)&z.st_state));
+  GSV_RC(need(h, "ses_plen", 2 * mb * 4, (void**)&z.st_plen));
+  GSV_RC(need(h, "ses_ytok", mb * h->ycap * 4, (void**)&z.st_ytok));
+  GSV_RC(need(h, "ses_rng_row", mb * 4, (void**)&z.st_rng_row));
+  GSV_RC(need(h, "ses_rng_seed", mb * 8, (void**)&z.st_rng_seed));
+  GSV_RC(need(h, "ses_row_sampling", mb * sizeof(RowSampling), (void**)&z.st_row_sampling));
+  GSV_RC(need(h, "ses_sp", sizeof(StepParams), (void**)&z.st_sp));
+  GSV_RC(need(h, "ses_out_tokens", mb * ms * 4, (void**)&z.st_out_tokens));
+  GSV_RC(need(h, "ses_out_len", mb * 4, (void**)&z.st_out_len));
+  GSV_RC(need(h, "ses_slot", mb * 4, (void**)&z.st_slot));
+  GSV_RC(need(h, "ses_force", mb * ms * 4, (void**)&z.st_force));
+  GSV_RC(need(h, "ses_drawn", mb * 2 * 4, (void**)&z.st_drawn));
+  GSV_RC(need(h, "ses_ybuf", mb * d * 4, (void**)&z.st_ybuf));
+  GSV_RC(need(h, "ses_logits", mb * V * 4, (void**)&z.st_logits));
+  GSV_RC(need(h, "ses_dump", mb * V * 4, (void**)&z.st_dump));
+  GSV_HIP(hipMemset(z.st_logits, 0, mb * V * 4));
+  for (auto& e : z.ev) if (!e) GSV_HIP(hipEventCreate(&e));
+  z.sp = *sp; z.slots = slots; z.budget = session_budget(*sp); z.row_sampling = row_sampling != 0;
+  z.out_tokens = out_tokens; z.out_len = out_len;
+  z.force = h->dbg_force; z.dump = h->dbg_dump; z.drawn = h->dbg_drawn;
+  h->dbg_force = nullptr; h->dbg_dump = nullptr; h->dbg_drawn = nullptr;
+  // every slot free: active = 0, and every per-row array the kernels load for a free slot holds zeros
+  GSV_HIP(hipMemset(h->d_kv_len, 0, (3 * mb + 4) * 4));
+  GSV_HIP(hipMemset(h->d_plen, 0, 2 * mb * 4));
+  GSV_HIP(hipMemset(h->d_rng_seed, 0, mb * 8));
+  GSV_HIP(hipMemset(h->d_rng_row, 0, mb * 4));
+  GSV_HIP(hipMemset(h->d_row_sampling, 0, mb * sizeof(RowSampling)));
+  GSV_HIP(hipMemset(h->ybuf, 0, mb * d * 4));
+  h->rng_seed_up.clear(); h->rng_row_up.clear(); h->row_sampling_up.clear();   // the device arrays are the session's now
+  h->rng_seed_next.clear(); h->rng_row_next.clear(); h->row_sampling_next.clear();
+  const StepParams p = session_params(h, false), ps = session_params(h, true);
+  GSV_HIP(hipMemcpy(h->d_sp, &p, sizeof(p), hipMemcpyHostToDevice));
+  GSV_HIP(hipMemcpy(z.st_sp, &ps, sizeof(ps), hipMemcpyHostToDevice));
+  h->B = slots; h->P = 0; h->max_kv0 = 0;
+  z.live.assign(slots, 0);
+  z.last_adopt_ms = 0.f; z.last_adopt_bytes = 0;
+  z.open = true;
+  return GSV_OK;
+}
+
+template <typename T>
+int session_admit(gsv_t2s* h, int n, const int32_t* slot_ids, const int32_t* phones, const int32_t* phone_lens, const float* bert,
+                  const int32_t* prompts_packed, const int32_t* prompt_lens, const uint64_t* rng_seeds, const int32_t* rng_rows,
+                  const gsv_row_sampling_t* row_sampling, hipStream_t s) {
+  T2SSession& z = h->ses;
+  const auto& c = h->cfg;
+  const size_t mb = (size_t)h->max_batch, ms = (size_t)z.sp.max_steps;
+  int maxS = 0;
+  long long positions = 0;
+  for (int i = 0; i < n; ++i) {
+    const int S = phone_lens[i] + prompt_lens[i];
+    maxS = S > maxS ? S : maxS;
+    positions += S;
+  }
+  const int st_smax = maxS + 2;
+  const size_t st_stride = (size_t)n * c.dim * st_smax;
+  void* st_kv = nullptr;
+  GSV_RC(need(h, "ses_kv", (size_t)c.n_layer * 2 * st_stride * esz(h), &st_kv));
+  GSV_HIP(hipMemcpyAsync(z.st_rng_seed, rng_seeds, (size_t)n * 8, hipMemcpyHostToDevice, s));
+  GSV_HIP(hipMemcpyAsync(z.st_rng_row, rng_rows, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  GSV_HIP(hipMemcpyAsync(z.st_slot, slot_ids, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  if (z.row_sampling)
+    GSV_HIP(hipMemcpyAsync(z.st_row_sampling, row_sampling, (size_t)n * sizeof(RowSampling), hipMemcpyHostToDevice, s));
+  GSV_HIP(hipMemsetAsync(z.st_out_len, 0xFF, (size_t)n * 4, s));     // -1: not finished
+  if (z.force)   // step 0 of row i is forced with its slot's entry
+    for (int i = 0; i < n; ++i)
+      GSV_HIP(hipMemcpyAsync(z.st_force + (size_t)i * ms, z.force + (size_t)slot_ids[i] * ms, 4, hipMemcpyDeviceToDevice, s));
+  int rc;
+  {
+    StagingScope staging(h, st_kv, st_stride, st_smax);
+    rc = t2s_prefill_into(h, phones, phone_lens, n, bert, prompts_packed, prompt_lens, s);
+    if (!rc) rc = launch_tail<T>(h, s);   // step 0: the rows now stand where gsv_t2s_decode's rows stand after its step 0
+  }
+  if (rc) return rc;
+  AdoptArgs a;
+  a.src_kv = st_kv; a.dst_kv = h->kv; a.src_layer_stride = st_stride; a.dst_layer_stride = h->kv_layer_stride;
+  a.src_smax = st_smax; a.dst_smax = h->max_seq; a.L = c.n_layer; a.H = c.n_head; a.esize = (int)esz(h);
+  a.n = n; a.slots = z.slots; a.mb = (int)mb; a.ycap = h->ycap; a.d = c.dim; a.V = c.vocab;
+  a.src_steps = (int)ms; a.dst_steps = (int)ms;
+  a.slot = z.st_slot;
+  a.src_state = z.st_state; a.src_plen = z.st_plen; a.src_ytok = z.st_ytok; a.src_rng_row = z.st_rng_row;
+  a.src_out_tokens = z.st_out_tokens; a.src_out_len = z.st_out_len; a.src_drawn = z.st_drawn; a.src_rng_seed = z.st_rng_seed;
+  a.src_row_sampling = z.st_row_sampling; a.src_ybuf = z.st_ybuf; a.src_dump = z.st_dump;
+  a.dst_state = h->d_kv_len; a.dst_plen = h->d_plen; a.dst_ytok = h->d_ytok; a.dst_rng_row = h->d_rng_row;
+  a.dst_out_tokens = z.out_tokens; a.dst_out_len = z.out_len; a.dst_drawn = z.drawn; a.dst_rng_seed = h->d_rng_seed;
+  a.dst_row_sampling = z.row_sampling ? h->d_row_sampling : nullptr; a.dst_ybuf = h->ybuf; a.dst_dump = z.dump;
+  GSV_HIP(hipEventRecord(z.ev[0], s));
+  GSV_RC(launch_session_adopt(a, s));
+  GSV_HIP(hipEventRecord(z.ev[1], s));
+  std::vector<int> act(n);
+  GSV_HIP(hipMemcpyAsync(act.data(), z.st_state + mb, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  GSV_HIP(hipStreamSynchronize(s));
+  for (int i = 0; i < n; ++i) z.live[slot_ids[i]] = act[i] != 0;
+  (void)hipEventElapsedTime(&z.last_adopt_ms, z.ev[0], z.ev[1]);
+  z.last_adopt_bytes = positions * c.n_layer * 2 * c.dim * (long long)esz(h);
+  return GSV_OK;
+}
+
+template <typename T>
+int session_advance(gsv_t2s* h, int n_steps, int* live_out, int* steps_out, hipStream_t s) {
+  T2SSession& z = h->ses;
+  const size_t mb = (size_t)h->max_batch;
+  bool any = false;
+  for (char l : z.live) any = any || l;
+  h->last_decode_mode = 0; h->last_decode_ms = 0.f; h->last_decode_steps = 0;
+  if (any) {
+    GSV_RC(launch_session_embed(h->d_kv_len, (int)mb, h->d_plen, h->d_ytok, h->ycap, h->e_audio, h->pe, h->alpha_a, h->cfg.dim,
+                                h->cfg.vocab, z.slots, h->ybuf, s));
+    // a chunk is a decode call whose step 0 has been run: n_steps steps of run_mega / run_steps are "budget" n_steps + 1
+    bool done = false;
+    if (h->mega.ready && h->mega_on && z.slots <= MEGA_MAX_B) {
+      const int r = run_mega(h, n_steps + 1, z.out_len, s);
+      if (r < 0) return r;
+      done = r == MEGA_DONE;   // else the snapshot is back: this chunk runs on the launch-per-phase step
+    }
+    if (!done) {
+      GSV_RC(run_steps<T>(h, n_steps + 1, nullptr, s));
+      h->last_decode_steps = n_steps;
+    }
+  }
+  std::vector<int> st(3 * mb);
+  GSV_HIP(hipMemcpyAsync(st.data(), h->d_kv_len, 3 * mb * 4, hipMemcpyDeviceToHost, s));
+  GSV_HIP(hipStreamSynchronize(s));
+  for (int b = 0; b < z.slots; ++b) {
+    z.live[b] = st[mb + b] != 0;
+    if (live_out) live_out[b] = st[mb + b] != 0;
+    if (steps_out) steps_out[b] = st[2 * mb + b];
+  }
+  return GSV_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -921,6 +1117,7 @@ void gsv_t2s_destroy(gsv_t2s_t* h) {
   if (h->h_pinned) (void)hipHostFree(h->h_pinned);
   if (h->mega.h_err) (void)hipHostFree(h->mega.h_err);
   for (auto& e : h->mega_ev) if (e) (void)hipEventDestroy(e);
+  for (auto& e : h->ses.ev) if (e) (void)hipEventDestroy(e);
   delete h;
 }
 
@@ -1066,13 +1263,113 @@ int gsv_t2s_set_row_sampling(gsv_t2s_t* h, const gsv_row_sampling_t* rows, int B
 
 int gsv_t2s_decode(gsv_t2s_t* h, const gsv_sampling_params* sp, const float* noise, int noise_rows,
                    int32_t* out_tokens, int32_t* out_len, int* steps_run, gsv_stream_t stream) {
-  GSV_REQUIRE(h && h->finalized && h->B > 0, "t2s_decode: call gsv_t2s_prefill first");
+  GSV_REQUIRE(h && h->finalized, "t2s_decode: handle not finalized");
+  if (h->ses.open) {
+    set_error("t2s_decode: a decode session is open on this handle (gsv_t2s_session_end closes it)");
+    return GSV_ERR_STATE;
+  }
+  GSV_REQUIRE(h->B > 0, "t2s_decode: call gsv_t2s_prefill first");
   // the per-row sampling parameters are this call's alone, whatever becomes of it
   struct Clear { gsv_t2s_t* h; ~Clear() { h->row_sampling_next.clear(); } } clear{h};
   GSV_REQUIRE(sp && out_tokens && out_len, "t2s_decode: null argument");
   GSV_REQUIRE(sp->max_steps >= 1, "t2s_decode: max_steps must be >= 1");
   GSV_REQUIRE(noise == nullptr || noise_rows == 1 || noise_rows == h->B, "t2s_decode: noise_rows must be 1 or B");
   return GSV_WITH_T(h, decode<T>(h, sp, noise, noise_rows, out_tokens, out_len, steps_run, (hipStream_t)stream));
+}
+
+int gsv_t2s_session_begin(gsv_t2s_t* h, const gsv_sampling_params* sp, int slots, int row_sampling, int32_t* out_tokens,
+                          int32_t* out_len) {
+  GSV_REQUIRE(h && h->finalized, "t2s_session_begin: handle not finalized");
+  if (h->ses.open) {
+    set_error("t2s_session_begin: a decode session is already open on this handle");
+    return GSV_ERR_STATE;
+  }
+  GSV_REQUIRE(sp && out_tokens && out_len, "t2s_session_begin: null argument");
+  GSV_REQUIRE(slots >= 1 && slots <= h->max_batch, "t2s_session_begin: %d slots, max_batch is %d", slots, h->max_batch);
+  GSV_REQUIRE(sp->max_steps >= 1, "t2s_session_begin: max_steps must be >= 1");
+  return session_begin(h, sp, slots, row_sampling, out_tokens, out_len);
+}
+
+int gsv_t2s_session_admit(gsv_t2s_t* h, int n, const int32_t* slot_ids, const int32_t* phones, const int32_t* phone_lens,
+                          const float* bert, const int32_t* prompts_packed, const int32_t* prompt_lens, const uint64_t* rng_seeds,
+                          const int32_t* rng_rows, const gsv_row_sampling_t* row_sampling, gsv_stream_t stream) {
+  GSV_REQUIRE(h && h->finalized, "t2s_session_admit: handle not finalized");
+  if (!h->ses.open) {
+    set_error("t2s_session_admit: no decode session is open (gsv_t2s_session_begin)");
+    return GSV_ERR_STATE;
+  }
+  const T2SSession& z = h->ses;
+  GSV_REQUIRE(slot_ids && phones && phone_lens && prompts_packed && prompt_lens && rng_seeds && rng_rows,
+              "t2s_session_admit: null argument");
+  GSV_REQUIRE(n >= 1 && n <= z.slots, "t2s_session_admit: %d rows for a session of %d slots", n, z.slots);
+  GSV_REQUIRE(!z.row_sampling || row_sampling, "t2s_session_admit: the session samples per row, row_sampling is null");
+  GSV_REQUIRE(z.row_sampling || !row_sampling, "t2s_session_admit: row_sampling given, but the session was opened without it");
+  if (row_sampling) GSV_RC(check_row_sampling("t2s_session_admit", row_sampling, n));
+  // everything that can refuse the admission is checked here, before the first launch: a refused admission changes nothing
+  std::vector<char> taken(z.slots, 0);
+  for (int i = 0; i < n; ++i) {
+    const int sl = slot_ids[i], P = prompt_lens[i];
+    GSV_REQUIRE(sl >= 0 && sl < z.slots, "t2s_session_admit: row %d: slot %d outside the session's %d slots", i, sl, z.slots);
+    GSV_REQUIRE(!z.live[sl], "t2s_session_admit: row %d: slot %d holds a live row", i, sl);
+    GSV_REQUIRE(!taken[sl], "t2s_session_admit: slot %d is given twice", sl);
+    taken[sl] = 1;
+    GSV_REQUIRE(phone_lens[i] >= 1, "t2s_session_admit: empty phoneme sequence in row %d", i);
+    GSV_REQUIRE(P >= 1, "t2s_session_admit: row %d has prompt length %d (must be >= 1)", i, P);
+    GSV_REQUIRE((long long)phone_lens[i] + P + 2 + z.budget <= h->max_seq,
+                "t2s_session_admit: row %d: %d positions + 2 + %d steps exceed the K/V arena (max_seq %d)", i, phone_lens[i] + P,
+                z.budget, h->max_seq);
+    GSV_REQUIRE(phone_lens[i] <= h->pe_rows && (long long)P + z.budget <= h->pe_rows,
+                "t2s_session_admit: row %d: prompt %d + %d steps exceed the position table (%d rows)", i, P, z.budget, h->pe_rows);
+    GSV_REQUIRE((long long)P + z.budget <= h->ycap, "t2s_session_admit: row %d: prompt %d + %d steps exceed the token history (%d)",
+                i, P, z.budget, h->ycap);
+  }
+  return GSV_WITH_T(h, session_admit<T>(h, n, slot_ids, phones, phone_lens, bert, prompts_packed, prompt_lens, rng_seeds, rng_rows,
+                                        row_sampling, (hipStream_t)stream));
+}
+
+int gsv_t2s_session_advance(gsv_t2s_t* h, int n_steps, int* live_out, int* steps_out, gsv_stream_t stream) {
+  GSV_REQUIRE(h && h->finalized, "t2s_session_advance: handle not finalized");
+  if (!h->ses.open) {
+    set_error("t2s_session_advance: no decode session is open (gsv_t2s_session_begin)");
+    return GSV_ERR_STATE;
+  }
+  GSV_REQUIRE(n_steps >= 1, "t2s_session_advance: n_steps %d must be >= 1", n_steps);
+  return GSV_WITH_T(h, session_advance<T>(h, n_steps, live_out, steps_out, (hipStream_t)stream));
+}
+
+int gsv_t2s_session_end(gsv_t2s_t* h) {
+  GSV_REQUIRE(h && h->finalized, "t2s_session_end: handle not finalized");
+  if (!h->ses.open) {
+    set_error("t2s_session_end: no decode session is open");
+    return GSV_ERR_STATE;
+  }
+  GSV_HIP(hipDeviceSynchronize());
+  T2SSession& z = h->ses;
+  z.open = false; z.live.clear();
+  z.out_tokens = nullptr; z.out_len = nullptr; z.force = nullptr; z.dump = nullptr; z.drawn = nullptr;
+  h->B = 0;   // the next decode needs a prefill of its own, as on a fresh handle
+  h->rng_seed_up.clear(); h->rng_row_up.clear(); h->row_sampling_up.clear();
+  return GSV_OK;
+}
+
+int gsv_t2s_session_state(gsv_t2s_t* h, int32_t* state) {
+  GSV_REQUIRE(h && h->finalized && state, "t2s_session_state: null argument or handle not finalized");
+  if (!h->ses.open) {
+    set_error("t2s_session_state: no decode session is open");
+    return GSV_ERR_STATE;
+  }
+  const size_t mb = (size_t)h->max_batch, n = (size_t)h->ses.slots;
+  GSV_HIP(hipDeviceSynchronize());
+  for (int k = 0; k < 3; ++k) GSV_HIP(hipMemcpy(state + k * n, h->d_kv_len + k * mb, n * 4, hipMemcpyDeviceToHost));
+  GSV_HIP(hipMemcpy(state + 3 * n, h->d_plen, n * 4, hipMemcpyDeviceToHost));
+  return GSV_OK;
+}
+
+int gsv_t2s_session_adopt_info(gsv_t2s_t* h, float* device_ms, int64_t* kv_bytes) {
+  GSV_REQUIRE(h && h->finalized, "t2s_session_adopt_info: handle not finalized");
+  if (device_ms) *device_ms = h->ses.last_adopt_ms;
+  if (kv_bytes) *kv_bytes = h->ses.last_adopt_bytes;
+  return GSV_OK;
 }
 
 int gsv_t2s_set_mega(gsv_t2s_t* h, int on) {

@@ -11,6 +11,28 @@ struct LayerW {
   float *n1w = nullptr, *n1b = nullptr, *n2w = nullptr, *n2b = nullptr;
 };
 
+// A decode session (gsv_t2s_session_*): `slots` rows of the main arena that are admitted, advanced and freed one by one.  An
+// admission prefills its rows in the staging copies below (rows 0 .. n - 1, the arena only as long as the admission's longest
+// row) and one adopt launch moves them into their slots; see t2s_session.hip.
+struct T2SSession {
+  bool open = false;
+  int slots = 0, budget = 0;
+  bool row_sampling = false;
+  gsv_sampling_params sp;
+  int32_t *out_tokens = nullptr, *out_len = nullptr;         // the caller's, [slots][max_steps] and [slots]
+  const int* force = nullptr; float* dump = nullptr; int* drawn = nullptr;   // gsv_t2s_set_debug's, held for the whole session
+  std::vector<char> live;                                    // host view of active[], refreshed by every admit / advance
+  // staging: what a prefill and the step-0 tail write, sized for max_batch rows (the K/V arena grows with the admissions)
+  int *st_state = nullptr, *st_plen = nullptr, *st_ytok = nullptr, *st_rng_row = nullptr, *st_out_tokens = nullptr,
+      *st_out_len = nullptr, *st_slot = nullptr, *st_force = nullptr, *st_drawn = nullptr;
+  unsigned long long* st_rng_seed = nullptr;
+  gsv::RowSampling* st_row_sampling = nullptr;
+  gsv::StepParams* st_sp = nullptr;
+  float *st_ybuf = nullptr, *st_logits = nullptr, *st_dump = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};                     // around the adopt launch
+  float last_adopt_ms = 0.f; long long last_adopt_bytes = 0;
+};
+
 struct gsv_t2s : gsveng::Ctx {
   gsv_t2s() : Ctx("t2s") {}
   gsv_t2s_config cfg;
@@ -57,8 +79,41 @@ struct gsv_t2s : gsveng::Ctx {
   int prefill_gemm = 2;     // gsv_t2s_set_prefill_gemm: 0 dispatcher only, 1 panel GEMM wherever eligible, 2 from PANEL_MIN_ROWS rows upwards
   const int* dbg_force = nullptr; float* dbg_dump = nullptr; int* dbg_drawn = nullptr; int dbg_stall = 0;   // gsv_t2s_set_debug / gsv_t2s_debug_stall: apply to the NEXT decode call only
   std::map<int, hipGraphExec_t> graphs;
+  T2SSession ses;
 };
 
 inline void* kv_ptr(gsv_t2s* h, int layer, int which) {
   return (char*)h->kv + ((size_t)(layer * 2 + which) * h->kv_layer_stride) * gsveng::esz(h);
 }
+
+// t2s_prefill.hip: the ragged prefill of rows 0 .. B - 1 into whatever arena and row state the handle points at (an admission
+// points it at the session's staging copies)
+int t2s_prefill_into(gsv_t2s* h, const int32_t* phones, const int32_t* phone_lens, int B, const float* bert,
+                     const int32_t* prompts_packed, const int32_t* prompt_lens, hipStream_t s);
+
+// t2s_session.hip
+namespace gsv {
+// what the adopt launch moves for admitted row i -> slot[i]: src_* are the staging copies, dst_* the session's own
+struct AdoptArgs {
+  const void* src_kv = nullptr; void* dst_kv = nullptr;
+  unsigned long long src_layer_stride = 0, dst_layer_stride = 0;   // elements per (layer, k|v)
+  int src_smax = 0, dst_smax = 0, L = 0, H = 0, esize = 0;
+  int n = 0, slots = 0, mb = 0, ycap = 0, d = 0, V = 0, src_steps = 0, dst_steps = 0;
+  const int* slot = nullptr;                                       // [n] device
+  const int *src_state = nullptr, *src_plen = nullptr, *src_ytok = nullptr, *src_rng_row = nullptr, *src_out_tokens = nullptr,
+            *src_out_len = nullptr, *src_drawn = nullptr;
+  const unsigned long long* src_rng_seed = nullptr;
+  const RowSampling* src_row_sampling = nullptr;
+  const float *src_ybuf = nullptr, *src_dump = nullptr;
+  int *dst_state = nullptr, *dst_plen = nullptr, *dst_ytok = nullptr, *dst_rng_row = nullptr, *dst_out_tokens = nullptr,
+      *dst_out_len = nullptr, *dst_drawn = nullptr;
+  unsigned long long* dst_rng_seed = nullptr;
+  RowSampling* dst_row_sampling = nullptr;
+  float *dst_ybuf = nullptr, *dst_dump = nullptr;
+};
+int launch_session_adopt(const AdoptArgs& a, hipStream_t s);
+// ybuf[b] = e_audio[tok] + alpha_a * pe[P_b + step - 1], tok = ytok[b][P_b + step - 1], for every live row: the input embedding
+// of the row's next step, which the last step of a launch does not leave behind
+int launch_session_embed(const int* state, int mb, const int* plen, const int* ytok, int ycap, const float* e_audio, const float* pe,
+                         float alpha_a, int d, int V, int slots, float* ybuf, hipStream_t s);
+}  // namespace gsv

@@ -512,11 +512,29 @@ int t2s_prefill_rows(gsv_t2s* h, const int32_t* phones, const int32_t* phone_len
 
 }  // namespace
 
+int t2s_prefill_into(gsv_t2s* h, const int32_t* phones, const int32_t* phone_lens, int B, const float* bert,
+                     const int32_t* prompts_packed, const int32_t* prompt_lens, hipStream_t s) {
+  std::vector<int> poff(B);
+  int o = 0;
+  for (int b = 0; b < B; ++b) { poff[b] = o; o += prompt_lens[b]; }
+  return GSV_WITH_T(h, t2s_prefill_rows<T>(h, phones, phone_lens, B, bert, prompts_packed, prompt_lens, poff.data(), s));
+}
+
+// while a decode session is open the handle's arena and row state are the session's
+#define GSV_T2S_NO_SESSION(h, who)                                                                                      \
+  do {                                                                                                                  \
+    if ((h)->ses.open) {                                                                                                \
+      gsv::set_error(who ": a decode session is open on this handle (gsv_t2s_session_end closes it)");                  \
+      return GSV_ERR_STATE;                                                                                             \
+    }                                                                                                                   \
+  } while (0)
+
 extern "C" {
 
 int gsv_t2s_prefill(gsv_t2s_t* h, const int32_t* phones, const int32_t* phone_lens, int B, const float* bert,
                     const int32_t* prompts, int P, gsv_stream_t stream) {
   GSV_REQUIRE(h && h->finalized, "t2s_prefill: handle not finalized");
+  GSV_T2S_NO_SESSION(h, "t2s_prefill");
   GSV_REQUIRE(phones && phone_lens && (prompts || P == 0), "t2s_prefill: null argument");
   GSV_REQUIRE(B >= 1 && B <= h->max_batch, "t2s_prefill: batch %d exceeds max_batch %d", B, h->max_batch);
   GSV_REQUIRE(P >= 0, "t2s_prefill: negative prompt length %d", P);   // P == 0: prompt-free decode (t2s_model.py:849-856)
@@ -528,6 +546,7 @@ int gsv_t2s_prefill(gsv_t2s_t* h, const int32_t* phones, const int32_t* phone_le
 int gsv_t2s_prefill_ragged(gsv_t2s_t* h, const int32_t* phones, const int32_t* phone_lens, int B, const float* bert,
                            const int32_t* prompts_packed, const int32_t* prompt_lens, gsv_stream_t stream) {
   GSV_REQUIRE(h && h->finalized, "t2s_prefill_ragged: handle not finalized");
+  GSV_T2S_NO_SESSION(h, "t2s_prefill_ragged");
   GSV_REQUIRE(phones && phone_lens && prompts_packed && prompt_lens, "t2s_prefill_ragged: null argument");
   GSV_REQUIRE(B >= 1 && B <= h->max_batch, "t2s_prefill_ragged: batch %d exceeds max_batch %d", B, h->max_batch);
   std::vector<int> poff(B);

@@ -39,6 +39,199 @@ def _host_nonzero(t: torch.Tensor) -> bool:
         return bool(t.any())
 
 
+def admit_count(free: int, queued: int, live: int, admit_min: int) -> int:
+    """The admission policy of a decode session: how many rows of the queue go into free slots now.  Rows wait until
+    `admit_min` slots are free, so that a prefill is shared by several rows -- unless fewer than that are left in the queue
+    (its tail) or nothing is decoding (the engine would otherwise idle)."""
+    if queued <= 0 or free <= 0:
+        return 0
+    if free >= min(admit_min, queued) or live == 0:
+        return min(free, queued)
+    return 0
+
+
+def plan_continuous(lengths: Sequence[int], slots: int, chunk: int, admit_min: Optional[int] = None):
+    """The schedule `infer_panel_continuous` follows for a queue whose row i needs lengths[i] further steps after its step 0
+    (0: it ends at its admission), as a pure function: a list of ("admit", [(row, slot), ...]) and
+    ("advance", chunk, [rows reported finished, in slot order]) events.  Rows are admitted in the order given, into the lowest
+    free slots; a slot is free again once the advance that saw its row finish has returned."""
+    if slots < 1 or chunk < 1:
+        raise ValueError("slots and chunk must be >= 1")
+    admit_min = max(1, slots // 4) if admit_min is None else int(admit_min)
+    if admit_min < 1:
+        raise ValueError("admit_min must be >= 1")
+    trace = []
+    owner: List[Optional[int]] = [None] * slots      # row in each slot
+    left: List[int] = [0] * slots
+    q, n = 0, len(lengths)
+    while q < n or any(o is not None for o in owner):
+        free = [s for s in range(slots) if owner[s] is None]
+        k = admit_count(len(free), n - q, slots - len(free), admit_min)
+        if k:
+            pairs = []
+            for s in free[:k]:
+                owner[s], left[s] = q, int(lengths[q])
+                pairs.append((q, s))
+                q += 1
+            trace.append(("admit", pairs))
+        done = []
+        for s in range(slots):
+            if owner[s] is None:
+                continue
+            left[s] -= min(chunk, left[s])
+            if left[s] == 0:
+                done.append(owner[s])
+                owner[s] = None
+        trace.append(("advance", chunk, done))
+    return trace
+
+
+class T2SSession:
+    """An open decode session of a Text2SemanticDecoder (gsv_t2s_session_*): `slots` rows of its K/V arena that are admitted,
+    advanced a chunk of steps at a time and admitted again when their row has finished.  Use as a context manager."""
+
+    def __init__(self, dec: "Text2SemanticDecoder", slots, top_k, top_p, temperature, repetition_penalty, early_stop_num,
+                 eos_mask_steps, max_steps, row_sampling=False, force=False, dump_logits=False):
+        if not dec._loaded:
+            raise RuntimeError("load_state_dict() first")
+        self.dec, self.slots, self.per_row = dec, int(slots), bool(row_sampling)
+        dev = dec.device
+        wanted = max_steps if early_stop_num in (-1, None) else min(max_steps, int(early_stop_num) + 1)
+        self.budget = int(wanted)
+        self._owner: List[Optional[int]] = [None] * self.slots     # ticket of the row in each slot
+        self._prompt: List[Optional[torch.Tensor]] = [None] * self.slots
+        self._next_ticket = 0
+        self.modes: List[int] = []          # decode_info mode of every advance that ran a step
+        self.logits: Dict[int, torch.Tensor] = {}   # dump_logits: ticket -> [steps run][vocab]
+        self.adopt: List[tuple] = []        # (rows, device ms, K/V bytes) of every admission
+        self.history: List[tuple] = []      # (ticket, slot) of every admitted row
+        self._open = False
+        with torch.cuda.device(dev):
+            self.out_tokens = torch.zeros(self.slots, self.budget, dtype=torch.int32, device=dev)
+            self.out_len = torch.full((self.slots,), -1, dtype=torch.int32, device=dev)
+            self.force = torch.zeros(self.slots, self.budget, dtype=torch.int32, device=dev) if force else None
+            self.dump = torch.zeros(self.budget, self.slots, dec.vocab_size, dtype=torch.float32, device=dev) if dump_logits else None
+            sp = _lib.SamplingParams(int(top_k) if top_k is not None else 0, float(top_p if top_p is not None else 1.0),
+                                     float(temperature), float(repetition_penalty),
+                                     -1 if early_stop_num is None else int(early_stop_num), int(eos_mask_steps),
+                                     self.budget, 0)
+            torch.cuda.current_stream(dev).synchronize()
+            l = _lib.lib()
+            if force or dump_logits:
+                _lib.check(l.gsv_t2s_set_debug(dec._h, self.force.data_ptr() if force else None,
+                                               self.dump.data_ptr() if dump_logits else None, None), "gsv_t2s_set_debug")
+            _lib.check(l.gsv_t2s_session_begin(dec._h, C.byref(sp), self.slots, int(self.per_row), self.out_tokens.data_ptr(),
+                                               self.out_len.data_ptr()), "gsv_t2s_session_begin")
+        self._open = True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def close(self):
+        if self._open:
+            self._open = False
+            _lib.check(_lib.lib().gsv_t2s_session_end(self.dec._h), "gsv_t2s_session_end")
+
+    @property
+    def free(self) -> List[int]:
+        """slots that hold no row (a finished row keeps its slot until an advance has reported it)"""
+        return [s for s in range(self.slots) if self._owner[s] is None]
+
+    @property
+    def live(self) -> int:
+        return sum(o is not None for o in self._owner)
+
+    def admit(self, rows: Sequence[dict], slots: Optional[Sequence[int]] = None) -> List[int]:
+        """rows: dict(x, bert, prompt, key=(seed, row), sampling=None[, force=tokens]); each goes into the next free slot (or
+        slots[i]) and has run its step 0 when this returns.  Returns one ticket per row."""
+        dec, dev, n = self.dec, self.dec.device, len(rows)
+        if slots is None:
+            slots = self.free[:n]
+            if len(slots) < n:
+                raise ValueError(f"{n} rows for {len(slots)} free slots")
+        slots = [int(s) for s in slots]
+        if len(slots) != n:
+            raise ValueError(f"{len(slots)} slots for {n} rows")
+        if self.per_row and any(r.get("sampling") is None for r in rows):
+            raise ValueError("the session samples per row: every row needs a sampling tuple")
+        l = _lib.lib()
+        with torch.cuda.device(dev):
+            lens = [int(r["x"].shape[-1]) for r in rows]
+            prompts = [r["prompt"].reshape(-1) for r in rows]
+            plens = [int(p_.shape[0]) for p_ in prompts]
+            phones = torch.cat([r["x"].reshape(-1) for r in rows]).to(dev, torch.int32).contiguous()
+            bert_dev = dec._bert_rows([r.get("bert") for r in rows], lens)
+            pr = torch.cat(prompts).to(dev, torch.int32).contiguous()
+            if self.force is not None:
+                for r, s in zip(rows, slots):
+                    if r.get("force") is not None and 0 <= s < self.slots:
+                        f = r["force"].reshape(-1).to(dev, torch.int32)[:self.budget]
+                        self.force[s].zero_()
+                        self.force[s, :f.shape[0]] = f
+            dec.stream.wait_stream(torch.cuda.current_stream(dev))
+            torch.cuda.current_stream(dev).synchronize()
+            slots_h, lens_h, plens_h = (C.c_int32 * n)(*slots), (C.c_int32 * n)(*lens), (C.c_int32 * n)(*plens)
+            seeds_h = (C.c_uint64 * n)(*[int(r["key"][0]) & 0xFFFFFFFFFFFFFFFF for r in rows])
+            rrows_h = (C.c_int32 * n)(*[int(r["key"][1]) for r in rows])
+            rs_h = None
+            if self.per_row:
+                rs_h = (_lib.RowSampling * n)(*[_lib.RowSampling(int(k) if k is not None else 0, float(p_ if p_ is not None else 1.0),
+                                                                 float(t), float(rp)) for k, p_, t, rp in (r["sampling"] for r in rows)])
+            _lib.check(l.gsv_t2s_session_admit(dec._h, n, C.cast(slots_h, C.c_void_p), phones.data_ptr(), C.cast(lens_h, C.c_void_p),
+                                               bert_dev.data_ptr() if bert_dev is not None else None, pr.data_ptr(),
+                                               C.cast(plens_h, C.c_void_p), C.cast(seeds_h, C.c_void_p), C.cast(rrows_h, C.c_void_p),
+                                               C.cast(rs_h, C.c_void_p) if rs_h is not None else None,
+                                               C.c_void_p(dec.stream.cuda_stream)), "gsv_t2s_session_admit")
+            torch.cuda.current_stream(dev).wait_stream(dec.stream)
+            ms, nb = C.c_float(0), C.c_int64(0)
+            _lib.check(l.gsv_t2s_session_adopt_info(dec._h, C.byref(ms), C.byref(nb)), "gsv_t2s_session_adopt_info")
+            self.adopt.append((n, ms.value, nb.value))
+        tickets = []
+        for s, p_ in zip(slots, prompts):
+            self._owner[s] = self._next_ticket
+            self._prompt[s] = p_.to(dev, torch.int64)
+            tickets.append(self._next_ticket)
+            self.history.append((self._next_ticket, s))
+            self._next_ticket += 1
+        return tickets
+
+    def state(self) -> np.ndarray:
+        """test hook: int32 [4][slots] = cached positions | live | step counter | prompt length of every slot"""
+        st = np.zeros((4, self.slots), dtype=np.int32)
+        _lib.check(_lib.lib().gsv_t2s_session_state(self.dec._h, st.ctypes.data), "gsv_t2s_session_state")
+        return st
+
+    def advance(self, steps: int):
+        """at most `steps` further steps for every live row; returns [(ticket, y, idx)] of the rows that have finished, y = prompt +
+        generated tokens and idx = their count, as `Text2SemanticDecoder._run` returns them.  Their slots are free again."""
+        dec, dev = self.dec, self.dec.device
+        l = _lib.lib()
+        live_h, steps_h = (C.c_int * self.slots)(), (C.c_int * self.slots)()
+        with torch.cuda.device(dev):
+            dec.stream.wait_stream(torch.cuda.current_stream(dev))
+            _lib.check(l.gsv_t2s_session_advance(dec._h, int(steps), live_h, steps_h, C.c_void_p(dec.stream.cuda_stream)),
+                       "gsv_t2s_session_advance")
+            torch.cuda.current_stream(dev).wait_stream(dec.stream)
+            mode, _, ran = dec.decode_info()
+            if ran or mode:
+                self.modes.append(mode)
+            done = [s for s in range(self.slots) if self._owner[s] is not None and not live_h[s]]
+            out = []
+            if done:
+                idx = self.out_len.cpu().tolist()
+                for s in done:
+                    n = idx[s]
+                    out.append((self._owner[s], torch.cat([self._prompt[s], self.out_tokens[s, :n].long()]), n))
+                    if self.dump is not None:
+                        self.logits[self._owner[s]] = self.dump[:steps_h[s], s].clone()
+                    self._owner[s], self._prompt[s] = None, None
+        return out
+
+
 class Text2SemanticDecoder:
     def __init__(self, config: dict, device="cuda:0", dtype=torch.float16, max_batch: int = 32,
                  max_seq: int = 2048, norm_first: bool = False, top_k: int = 3):
@@ -98,6 +291,30 @@ class Text2SemanticDecoder:
         return self
 
     # ---- engine call ---------------------------------------------------------------
+    def _bert_rows(self, bert, lens):
+        """the rows' BERT features [1024, X_b] as one device tensor [sum(X_b), 1024], or None where they are all zero"""
+        dev = self.device
+        bert_dev = None
+        if bert is not None and any(b_ is not None for b_ in bert):
+            # None or all-zero features (non-zh text): bert_proj(0) is its bias, handled in the engine.  Host tensors are
+            # tested on the host and travel as ONE copy (the pipeline hands over 32 zero blocks of 330 KB per batch: as 32
+            # pageable uploads + a device-side any() + sync they were ~1 ms of idle GPU in front of every prefill)
+            on_host = all(b_ is None or b_.device.type == "cpu" for b_ in bert)
+            if on_host:
+                # numpy on the host view: a torch reduction costs ~1.3 ms per block on a many-core host (thread wake-up), i.e.
+                # 40 ms per batch of 32 (tools/prefill_probe.py)
+                if any(b_ is not None and _host_nonzero(b_) for b_ in bert):
+                    cols = [(torch.zeros(lens[i], 1024) if b_ is None else b_.reshape(1024, -1).t().float())
+                            for i, b_ in enumerate(bert)]
+                    bert_dev = torch.cat(cols, 0).contiguous().to(dev)
+            else:
+                cols = [(torch.zeros(lens[i], 1024, device=dev) if b_ is None
+                         else b_.reshape(1024, -1).t().to(dev, torch.float32)) for i, b_ in enumerate(bert)]
+                allb = torch.cat(cols, 0).contiguous()
+                if bool(torch.any(allb)):            # one host sync for the whole batch
+                    bert_dev = allb
+        return bert_dev
+
     def _run(self, x: Sequence[torch.Tensor], prompts: torch.Tensor, bert: Sequence[torch.Tensor], top_k, top_p,
              early_stop_num, temperature, repetition_penalty, eos_mask_steps, noise=None, seed=0,
              max_steps: int = 1500, force_tokens=None, dump_logits=False, rng_keys=None, row_sampling=None):
@@ -138,25 +355,7 @@ class Text2SemanticDecoder:
             arena_bound = budget < wanted
             phones = torch.cat([t.reshape(-1) for t in x]).to(dev, torch.int32).contiguous()
             lens_h = (C.c_int32 * B)(*lens)
-            bert_dev = None
-            if bert is not None and any(b_ is not None for b_ in bert):
-                # None or all-zero features (non-zh text): bert_proj(0) is its bias, handled in the engine.  Host tensors are
-                # tested on the host and travel as ONE copy (the pipeline hands over 32 zero blocks of 330 KB per batch: as 32
-                # pageable uploads + a device-side any() + sync they were ~1 ms of idle GPU in front of every prefill)
-                on_host = all(b_ is None or b_.device.type == "cpu" for b_ in bert)
-                if on_host:
-                    # numpy on the host view: a torch reduction costs ~1.3 ms per block on a many-core host (thread wake-up), i.e.
-                    # 40 ms per batch of 32 (tools/prefill_probe.py)
-                    if any(b_ is not None and _host_nonzero(b_) for b_ in bert):
-                        cols = [(torch.zeros(lens[i], 1024) if b_ is None else b_.reshape(1024, -1).t().float())
-                                for i, b_ in enumerate(bert)]
-                        bert_dev = torch.cat(cols, 0).contiguous().to(dev)
-                else:
-                    cols = [(torch.zeros(lens[i], 1024, device=dev) if b_ is None
-                             else b_.reshape(1024, -1).t().to(dev, torch.float32)) for i, b_ in enumerate(bert)]
-                    allb = torch.cat(cols, 0).contiguous()
-                    if bool(torch.any(allb)):            # one host sync for the whole batch
-                        bert_dev = allb
+            bert_dev = self._bert_rows(bert, lens)
             if ragged:
                 pr = torch.cat([p_.reshape(-1) for p_ in prompts]).to(dev, torch.int32).contiguous()
             else:
@@ -290,6 +489,81 @@ class Text2SemanticDecoder:
                              row_sampling=None if row_sampling is None else list(row_sampling[lo:hi]))
             ys[lo:hi] = y
             idxs[lo:hi] = i
+        return ys, idxs
+
+    # ---- decode sessions: continuous batching ------------------------------------------
+    def open_session(self, slots: int, top_k, top_p, temperature, repetition_penalty, early_stop_num, eos_mask_steps: int = 1,
+                     max_steps: int = 1500, row_sampling: bool = False, **debug) -> T2SSession:
+        """Opens a decode session of `slots` rows (<= max_batch); until it is closed the other entry points of this decoder
+        raise.  The four sampling values hold for every row unless row_sampling=True, in which case each admitted row brings
+        its own tuple.  debug: force=True / dump_logits=True, the parity hooks of `_run`, per slot."""
+        return T2SSession(self, slots, top_k, top_p, temperature, repetition_penalty, early_stop_num, eos_mask_steps, max_steps,
+                          row_sampling=row_sampling, **debug)
+
+    @torch.no_grad()
+    def infer_panel_continuous(self, x: List[torch.LongTensor], prompts, bert_feature: List[torch.Tensor], top_k: int = -100,
+                               top_p: int = 100, early_stop_num: int = -1, temperature: float = 1.0,
+                               repetition_penalty: float = 1.35, rng_keys=None, row_sampling=None, slots: Optional[int] = None,
+                               chunk: int = 32, admit_min: Optional[int] = None, max_steps: int = 1500, force_tokens=None,
+                               dump_logits: bool = False):
+        """`infer_panel_batch_infer` for a queue of any length through ONE decode session: rows are admitted in the order given
+        whenever `admit_min` slots are free (default max(1, slots // 4); see admit_count), `chunk` steps run between admissions
+        (both defaults from the sweep of tools/continuous_ar_bench.py, profiles/continuous_ar.txt),
+        and a row that has finished hands its slot to the next row of the queue while its neighbours go on decoding.  Returns
+        (ys, idx) in input order.  rng_keys=[(seed, row)] is required: a row's draws must not depend on where and when it is
+        decoded.  A row whose text + prompt leave the K/V arena less than the full step budget is decoded on its own by the
+        ordinary path after the session (and listed in last_truncated if the arena cuts it), as it would be there.
+        force_tokens [N][steps] / dump_logits: the parity hooks of `_run` (tests); last_logits_dump is then a list of N
+        [steps run][vocab] tensors.  last_session is the closed session (its history, modes and adopt times)."""
+        N = len(x)
+        if rng_keys is None or len(rng_keys) != N:
+            raise ValueError("infer_panel_continuous needs one RNG key (seed, row) per row")
+        if row_sampling is not None and len(row_sampling) != N:
+            raise ValueError(f"{len(row_sampling)} sampling tuples for {N} rows")
+        if prompts is None:
+            raise ValueError("prompt-free rows are decoded by infer_panel_batch_infer (the naive loop)")
+        slots = self.max_batch if slots is None else int(slots)
+        admit_min = max(1, slots // 4) if admit_min is None else int(admit_min)
+        wanted = max_steps if early_stop_num in (-1, None) else min(max_steps, int(early_stop_num) + 1)
+        rows = [dict(x=x[i], bert=bert_feature[i] if bert_feature is not None else None, prompt=prompts[i].reshape(-1),
+                     key=rng_keys[i], sampling=None if row_sampling is None else row_sampling[i]) for i in range(N)]
+        if force_tokens is not None:
+            for i, r in enumerate(rows):
+                r["force"] = force_tokens[i]
+        fits = [int(r["x"].shape[-1]) + int(r["prompt"].shape[0]) + 2 + wanted <= self.max_seq for r in rows]
+        if (force_tokens is not None or dump_logits) and not all(fits):
+            raise ValueError("the parity hooks need every row to fit the K/V arena with its full budget")
+        queue = [i for i in range(N) if fits[i]]
+        ys: List[Optional[torch.Tensor]] = [None] * N
+        idxs: List[Optional[int]] = [None] * N
+        if queue:
+            with self.open_session(slots, top_k, top_p, temperature, repetition_penalty, early_stop_num, 1, max_steps,
+                                   row_sampling=row_sampling is not None, force=force_tokens is not None,
+                                   dump_logits=dump_logits) as ses:
+                q, where = 0, {}
+                while q < len(queue) or ses.live:
+                    k = admit_count(len(ses.free), len(queue) - q, ses.live, admit_min)
+                    if k:
+                        for t, i in zip(ses.admit([rows[i] for i in queue[q:q + k]]), queue[q:q + k]):
+                            where[t] = i
+                        q += k
+                    for t, y, n in ses.advance(chunk):
+                        ys[where[t]], idxs[where[t]] = y, n
+                self.last_session = ses
+                if dump_logits:
+                    by_row = {i: ses.logits[t] for t, i in where.items()}
+                    self.last_logits_dump = [by_row[i] for i in range(N)]
+        truncated = []
+        for i in range(N):
+            if fits[i]:
+                continue
+            r = rows[i]
+            sk = (top_k, top_p, temperature, repetition_penalty) if r["sampling"] is None else r["sampling"]
+            y, n = self._run([r["x"]], [r["prompt"]], [r["bert"]], sk[0], sk[1], early_stop_num, sk[2], sk[3], eos_mask_steps=1,
+                             max_steps=max_steps, rng_keys=[r["key"]])
+            ys[i], idxs[i] = y[0], n[0]
+            truncated += [i] * bool(self.last_truncated)
+        self.last_truncated = truncated
         return ys, idxs
 
     @torch.no_grad()

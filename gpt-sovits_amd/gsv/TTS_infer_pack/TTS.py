@@ -1608,15 +1608,34 @@ class TTS:
         return dict(voice=voice, opts=o, actual_seed=actual_seed, data=data, index=index, no_prompt=no_prompt,
                     P=0 if no_prompt else int(voice["prompt_semantic"].numel()), frags=[None] * len(data))
 
-    def _ar_stage(self, plans: List[dict], mixed_sampling: bool = False) -> None:
+    @staticmethod
+    def plan_sessions(launches: List[List[dict]]) -> List[Tuple[bool, List[dict]]]:
+        """run_batch(continuous_ar=True): plan_batch's launches put back together by group.  Returns (session, rows) in
+        plan_batch's order: the launches of a parallel-decode group with prompts become ONE queue for a decode session
+        (Text2SemanticDecoder.infer_panel_continuous), rows in plan_batch's order with the keys and sampling tuples it gave
+        them; prompt-free and naive groups stay the launches they are."""
+        out: List[Tuple[bool, List[dict]]] = []
+        for rows in launches:
+            g = rows[0]["group"]
+            session = g[4] and not g[5]          # parallel_infer and not prompt-free
+            if session and out and out[-1][0] and out[-1][1][0]["group"] == g:
+                out[-1][1].extend(rows)
+            else:
+                out.append((session, list(rows)))
+        return out
+
+    def _ar_stage(self, plans: List[dict], mixed_sampling: bool = False, continuous_ar: bool = False) -> None:
         """Stage 2: every sentence of every request through the shared AR launches of plan_batch (mixed_sampling: launches
         shared across sampling parameters; a launch whose rows differ hands them over per row).  Reads `data`, `opts`,
         `voice`, `no_prompt`, `P`, `actual_seed`.  Writes run()'s pred_list / idx_list per batch: `preds[bi][j]`, the tokens
-        of sentence j (prompt included), `idxs[bi][j]`, how many were generated (0 prompt-free), `kept[bi]` = _kept_tokens."""
+        of sentence j (prompt included), `idxs[bi][j]`, how many were generated (0 prompt-free), `kept[bi]` = _kept_tokens.
+        continuous_ar: a group's launches are one decode session instead (plan_sessions)."""
         for pl in plans:
             pl["preds"] = [[None] * len(item["all_phones"]) for item in pl["data"]]
             pl["idxs"] = [[None] * len(item["all_phones"]) for item in pl["data"]]
-        for rows in (self.plan_batch(plans, mixed_sampling=True) if mixed_sampling else self.plan_batch(plans)):
+        launches = self.plan_batch(plans, mixed_sampling=True) if mixed_sampling else self.plan_batch(plans)
+        work = self.plan_sessions(launches) if continuous_ar else [(False, rows) for rows in launches]
+        for session, rows in work:
             o = plans[rows[0]["r"]]["opts"]
             kw = {}
             if mixed_sampling and len({e["sampling"] for e in rows}) > 1:     # a uniform launch takes the scalar path
@@ -1627,9 +1646,14 @@ class TTS:
             x = [it["all_phones"][e["j"]] for it, e in zip(items, rows)]
             bert = [it["all_bert_features"][e["j"]] for it, e in zip(items, rows)]
             prompts = None if no_prompt else [plans[e["r"]]["voice"]["prompt_semantic"].view(-1) for e in rows]
-            y, idx = self.t2s_model._run(x, prompts, bert, o["top_k"], o["top_p"], early_stop_num(self.configs), o["temperature"],
-                                         o["repetition_penalty"], eos_mask_steps=11 if naive else 1,
-                                         max_steps=rows[0]["group"][6], rng_keys=[e["key"] for e in rows], **kw)
+            if session:
+                y, idx = self.t2s_model.infer_panel_continuous(
+                    x, prompts, bert, o["top_k"], o["top_p"], early_stop_num(self.configs), o["temperature"],
+                    o["repetition_penalty"], rng_keys=[e["key"] for e in rows], max_steps=rows[0]["group"][6], **kw)
+            else:
+                y, idx = self.t2s_model._run(x, prompts, bert, o["top_k"], o["top_p"], early_stop_num(self.configs), o["temperature"],
+                                             o["repetition_penalty"], eos_mask_steps=11 if naive else 1,
+                                             max_steps=rows[0]["group"][6], rng_keys=[e["key"] for e in rows], **kw)
             for e, y_, i_ in zip(rows, y, idx):
                 plans[e["r"]]["preds"][e["bi"]][e["j"]] = y_
                 plans[e["r"]]["idxs"][e["bi"]][e["j"]] = 0 if no_prompt else i_
@@ -1767,7 +1791,7 @@ class TTS:
                   shared_speed: bool = False, mixed_sampling: bool = False,
                   shared_vocoder: bool = False, shared_bert: bool = False,
                   shared_hubert: bool = False, shared_sv: bool = False,
-                  device_frontend: bool = False) -> List[Tuple[int, np.ndarray]]:
+                  device_frontend: bool = False, continuous_ar: bool = False) -> List[Tuple[int, np.ndarray]]:
         """Several requests, each with its own reference voice, through shared AR decodes.  Each request dict takes the
         keys run() accepts plus an optional "voice" (make_voice); without one it uses its ref_audio_path / prompt_text
         (through make_voice's LRU) or the current prompt cache.  Returns one (sr, int16 audio) per request, in order: what
@@ -1793,6 +1817,9 @@ class TTS:
         speaker embeddings, main and auxiliary, from one packed ERes2NetV2 pass (make_voices(shared_sv=True)).
         device_frontend=True (with shared_hubert or shared_sv, else ValueError): that make_voices call reads the reference files on
         the host and resamples, normalises and frames them on the device (make_voices(device_frontend=True)).
+        continuous_ar=True: each group of plan_batch (parallel decode with prompts) is decoded through one decode session
+        (plan_sessions, Text2SemanticDecoder.infer_panel_continuous) instead of launches of max_batch rows: a sentence that
+        ends early hands its slot to the next one.  Same keys, same sampling values, the same tokens per sentence.
         No keyword changes anything for the other model family."""
         if self.t2s_model is None or self.vits_model is None:
             raise RuntimeError("init_t2s_weights / init_vits_weights first")
@@ -1806,7 +1833,7 @@ class TTS:
         if shared_hubert or shared_sv:
             requests = self._with_shared_voices(requests, shared_sv=shared_sv, device_frontend=device_frontend)
         plans = [self._plan_request(req) for req in requests]
-        self._ar_stage(plans, mixed_sampling=mixed_sampling)
+        self._ar_stage(plans, mixed_sampling=mixed_sampling, **({"continuous_ar": True} if continuous_ar else {}))
         sr = self._output_sr()
         if shared_sovits and not self.configs.use_vocoder:
             self._shared_sovits_stage(plans, shared_speed=shared_speed)

@@ -85,6 +85,13 @@ _SIGS = {
     "gsv_t2s_set_row_sampling": (C.c_int, [C.c_void_p, C.POINTER(RowSampling), C.c_int]),
     "gsv_t2s_decode": (C.c_int, [C.c_void_p, C.POINTER(SamplingParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                  C.POINTER(C.c_int), C.c_void_p]),
+    "gsv_t2s_session_begin": (C.c_int, [C.c_void_p, C.POINTER(SamplingParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "gsv_t2s_session_admit": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsv_t2s_session_advance": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsv_t2s_session_end": (C.c_int, [C.c_void_p]),
+    "gsv_t2s_session_state": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gsv_t2s_session_adopt_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int64)]),
     "gsv_t2s_decode_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "gsv_t2s_set_mega": (C.c_int, [C.c_void_p, C.c_int]),
     "gsv_t2s_set_prefill_gemm": (C.c_int, [C.c_void_p, C.c_int]),

@@ -118,6 +118,41 @@ int gsv_t2s_set_row_sampling(gsv_t2s_t* h, const gsv_row_sampling_t* rows, int B
 int gsv_t2s_decode(gsv_t2s_t* h, const gsv_sampling_params* sp, const float* noise, int noise_rows,
                    int32_t* out_tokens, int32_t* out_len, int* steps_run, gsv_stream_t stream);
 
+/* Decode sessions: continuous batching of the AR decode.  A session owns `slots` rows of the handle's K/V arena; rows are admitted
+ * into free slots, all live rows advance together a chunk of steps at a time, and a slot whose row has finished can be admitted
+ * again while its neighbours go on decoding.  A row decodes exactly what gsv_t2s_prefill_ragged + gsv_t2s_decode decode for it
+ * with the same counter-RNG key (fp32: the same bits whatever the chunks and the neighbours are).
+ *
+ * begin: slots <= max_batch.  The scalars of sp (early_stop_num, eos_mask_steps, max_steps; top_k .. repetition_penalty unless
+ *   row_sampling != 0) hold for the whole session; sp->seed is unused, every row brings its key.  out_tokens [dev] int32
+ *   [slots][sp->max_steps] and out_len [dev] int32 [slots] stay the caller's and must outlive the session; slot b's entries are
+ *   valid from the advance that reports it finished until the slot is admitted again.  Hooks set by gsv_t2s_set_debug before
+ *   begin hold for the session, indexed by slot ([slots][max_steps], [max_steps][slots][vocab], [max_steps][slots][2]) and by
+ *   the row's own step.  Sessions draw with the counter RNG only.  While a session is open gsv_t2s_prefill,
+ *   gsv_t2s_prefill_ragged and gsv_t2s_decode return GSV_ERR_STATE and change nothing; a second begin is GSV_ERR_STATE too.
+ * admit: prefills n rows (arguments as gsv_t2s_prefill_ragged, row i's key = (rng_seeds[i], rng_rows[i]) [host], its sampling
+ *   tuple row_sampling[i] [host] if the session has per-row sampling, else NULL) and runs their step 0, then puts row i into
+ *   slot_ids[i] [host].  No other slot is touched.  GSV_ERR_ARG before any launch: a slot that is live or out of range, a
+ *   repeated slot, a row with phone_lens + P_b + 2 + budget > max_seq, or P_b + budget beyond the position table or the token
+ *   history (budget = min(max_steps, early_stop_num + 1)).
+ * advance: at most n_steps further steps for every live slot; live_out / steps_out [host] int[slots] receive which slots are
+ *   still live and every slot's step counter (either may be NULL).  fp16 on the v1/v2 shape with slots <= 128 runs the chunk as
+ *   one launch of the persistent engine (a hand-off timeout re-runs the chunk on the launch-per-phase step), otherwise as
+ *   n_steps replays of the step graph.  gsv_t2s_decode_info then describes this chunk.
+ * end: closes the session; the handle behaves as before. */
+int gsv_t2s_session_begin(gsv_t2s_t* h, const gsv_sampling_params* sp, int slots, int row_sampling, int32_t* out_tokens,
+                          int32_t* out_len);
+int gsv_t2s_session_admit(gsv_t2s_t* h, int n, const int32_t* slot_ids, const int32_t* phones, const int32_t* phone_lens,
+                          const float* bert, const int32_t* prompts_packed, const int32_t* prompt_lens, const uint64_t* rng_seeds,
+                          const int32_t* rng_rows, const gsv_row_sampling_t* row_sampling, gsv_stream_t stream);
+int gsv_t2s_session_advance(gsv_t2s_t* h, int n_steps, int* live_out, int* steps_out, gsv_stream_t stream);
+int gsv_t2s_session_end(gsv_t2s_t* h);
+/* test hook: the slots' row state, state [host] int32 [4][slots] = cached positions | live | step counter | prompt length;
+ * waits for the device */
+int gsv_t2s_session_state(gsv_t2s_t* h, int32_t* state);
+/* measurement hook: HIP-event time (ms) of the last admission's adopt launch and the K/V bytes it read (it writes as many) */
+int gsv_t2s_session_adopt_info(gsv_t2s_t* h, float* device_ms, int64_t* kv_bytes);
+
 /* How the last gsv_t2s_decode call ran: mode 1 = the persistent engine (csrc/t2s_mega.hip: fp16, d=512/16 heads/FFN 2048,
  * B <= 128 -- up to four quads of rows per row group, B <= 32 is one quad; all steps after step 0 in ONE launch, hand-offs on the chip), mode 0 = one hipGraph of 122 launches per step
  * (fp32, other shapes, GSV_T2S_NO_MEGA=1, or a device on which the engine's 256 workgroups are not co-resident);

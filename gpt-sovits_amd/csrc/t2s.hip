@@ -1087,6 +1087,16 @@ int session_advance(gsv_t2s* h, int n_steps, int* live_out, int* steps_out, hipS
   return GSV_OK;
 }
 
+// the slots are distinct and inside the session (checked by the caller): one launch on the state block, then the host mirror
+int session_release(gsv_t2s* h, int n, const int32_t* slot_ids, hipStream_t s) {
+  T2SSession& z = h->ses;
+  GSV_HIP(hipMemcpyAsync(z.st_slot, slot_ids, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  GSV_RC(launch_session_release(h->d_kv_len, h->max_batch, z.st_slot, n, z.slots, s));
+  GSV_HIP(hipStreamSynchronize(s));
+  for (int i = 0; i < n; ++i) z.live[slot_ids[i]] = 0;
+  return GSV_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1335,6 +1345,25 @@ int gsv_t2s_session_advance(gsv_t2s_t* h, int n_steps, int* live_out, int* steps
   }
   GSV_REQUIRE(n_steps >= 1, "t2s_session_advance: n_steps %d must be >= 1", n_steps);
   return GSV_WITH_T(h, session_advance<T>(h, n_steps, live_out, steps_out, (hipStream_t)stream));
+}
+
+int gsv_t2s_session_release(gsv_t2s_t* h, int n, const int32_t* slot_ids, gsv_stream_t stream) {
+  GSV_REQUIRE(h && h->finalized, "t2s_session_release: handle not finalized");
+  if (!h->ses.open) {
+    set_error("t2s_session_release: no decode session is open (gsv_t2s_session_begin)");
+    return GSV_ERR_STATE;
+  }
+  const T2SSession& z = h->ses;
+  GSV_REQUIRE(slot_ids, "t2s_session_release: null argument");
+  GSV_REQUIRE(n >= 1 && n <= z.slots, "t2s_session_release: %d slots named in a session of %d slots", n, z.slots);
+  std::vector<char> taken(z.slots, 0);
+  for (int i = 0; i < n; ++i) {
+    const int sl = slot_ids[i];
+    GSV_REQUIRE(sl >= 0 && sl < z.slots, "t2s_session_release: slot %d outside the session's %d slots", sl, z.slots);
+    GSV_REQUIRE(!taken[sl], "t2s_session_release: slot %d is given twice", sl);
+    taken[sl] = 1;
+  }
+  return session_release(h, n, slot_ids, (hipStream_t)stream);
 }
 
 int gsv_t2s_session_end(gsv_t2s_t* h) {

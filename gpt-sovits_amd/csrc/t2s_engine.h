@@ -116,4 +116,7 @@ int launch_session_adopt(const AdoptArgs& a, hipStream_t s);
 // of the row's next step, which the last step of a launch does not leave behind
 int launch_session_embed(const int* state, int mb, const int* plen, const int* ytok, int ycap, const float* e_audio, const float* pe,
                          float alpha_a, int d, int V, int slots, float* ybuf, hipStream_t s);
+// clears the live word of slot[0 .. n - 1] (distinct, < slots) in the state block [kv_len | active | step | n_active] and takes
+// the rows that were live out of n_active
+int launch_session_release(int* state, int mb, const int* slot, int n, int slots, hipStream_t s);
 }  // namespace gsv

@@ -1,6 +1,6 @@
 // Kernels of the AR decode sessions (gsv_t2s_session_*, host side in t2s.hip): the adopt launch that moves freshly prefilled rows
-// from the staging arena into their slots of the main arena, and the launch that rebuilds the next step's input embedding of
-// every live row in front of an advance.
+// from the staging arena into their slots of the main arena, the launch that rebuilds the next step's input embedding of
+// every live row in front of an advance, and the launch that takes rows out of the decode (a cancelled request).
 //
 // Adopt.  An admission prefills its n rows as rows 0 .. n - 1 of a staging arena [layer][k|v][n][head][src_smax][32] (src_smax =
 // the admission's longest row + 2, not max_seq) with the unchanged prefill kernels, and runs their step 0 on staging row state.
@@ -92,6 +92,21 @@ __global__ __launch_bounds__(64) void session_embed_kernel(const int* __restrict
   for (int c = lane; c < d; c += 64) ybuf[(long long)b * d + c] = e[c] + alpha_a * p[c];
 }
 
+// Release: thread i clears the live word of slot[i].  The host has checked that the slots are distinct and inside the session, so
+// no two threads meet on a word; n_active loses one per row that was live (a finished row has left it already).  Nothing else of
+// the slot is touched: the next admission overwrites its state, and a slot that is not live is skipped by every kernel.
+__global__ __launch_bounds__(64) void session_release_kernel(int* __restrict__ state, int mb, const int* __restrict__ slot, int n,
+                                                             int slots) {
+  for (int i = threadIdx.x; i < n; i += 64) {
+    const int b = slot[i];
+    if (b < 0 || b >= slots) continue;
+    if (state[mb + b]) {
+      state[mb + b] = 0;
+      atomicSub(state + 3 * mb, 1);
+    }
+  }
+}
+
 int launch_session_adopt(const AdoptArgs& a, hipStream_t s) {
   const int hg = a.H % 4 == 0 ? 4 : 1;
   const int runs = a.L * 2 * (a.H / hg);
@@ -102,6 +117,11 @@ int launch_session_adopt(const AdoptArgs& a, hipStream_t s) {
 int launch_session_embed(const int* state, int mb, const int* plen, const int* ytok, int ycap, const float* e_audio, const float* pe,
                          float alpha_a, int d, int V, int slots, float* ybuf, hipStream_t s) {
   GSV_LAUNCH(session_embed_kernel, dim3(slots), dim3(64), 0, s, state, mb, plen, ytok, ycap, e_audio, pe, alpha_a, d, V, ybuf);
+  return GSV_OK;
+}
+
+int launch_session_release(int* state, int mb, const int* slot, int n, int slots, hipStream_t s) {
+  GSV_LAUNCH(session_release_kernel, dim3(1), dim3(64), 0, s, state, mb, slot, n, slots);
   return GSV_OK;
 }
 

@@ -199,6 +199,30 @@ class T2SSession:
             self._next_ticket += 1
         return tickets
 
+    def release(self, tickets: Sequence[int]) -> List[int]:
+        """takes the rows of these tickets out of the session (gsv_t2s_session_release): no advance reports them, and their
+        slots are free for the next admission.  A ticket that holds no slot (finished and reported, or never admitted) is
+        skipped.  Returns the slots that were released."""
+        wanted = set(int(t) for t in tickets)
+        slots = [s for s in range(self.slots) if self._owner[s] is not None and self._owner[s] in wanted]
+        return self.release_slots(slots)
+
+    def release_slots(self, slots: Sequence[int]) -> List[int]:
+        """`release` by slot number, unchecked on this side: the engine refuses a slot out of range or given twice"""
+        slots = [int(s) for s in slots]
+        if not slots:
+            return []
+        dev, n = self.dec.device, len(slots)
+        with torch.cuda.device(dev):
+            self.dec.stream.wait_stream(torch.cuda.current_stream(dev))
+            slots_h = (C.c_int32 * n)(*slots)
+            _lib.check(_lib.lib().gsv_t2s_session_release(self.dec._h, n, C.cast(slots_h, C.c_void_p),
+                                                          C.c_void_p(self.dec.stream.cuda_stream)), "gsv_t2s_session_release")
+            torch.cuda.current_stream(dev).wait_stream(self.dec.stream)
+        for s in slots:
+            self._owner[s], self._prompt[s] = None, None
+        return slots
+
     def state(self) -> np.ndarray:
         """test hook: int32 [4][slots] = cached positions | live | step counter | prompt length of every slot"""
         st = np.zeros((4, self.slots), dtype=np.int32)

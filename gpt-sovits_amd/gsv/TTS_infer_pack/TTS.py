@@ -1841,6 +1841,13 @@ class TTS:
             self._shared_cfm_stage(plans, shared_vocoder=shared_vocoder)
         return [self._finish_request(pl, sr) for pl in plans]
 
+    def serve(self, **scheduler_kw):
+        """Requests as they arrive instead of a closed list: a started `gsv.serving.Server` over a `Scheduler` of this
+        pipeline (keywords: slots, chunk, admit_min, wave_hold and the shared_* flags).  `submit(request)` returns a Future of
+        what run_batch([request]) returns; until `shutdown()` the server's loop thread owns the pipeline."""
+        from ..serving import Scheduler, Server
+        return Server(Scheduler(self, **scheduler_kw))
+
     # ---- the pipeline (reference TTS.py:984-1365) ---------------------------------------------
     @torch.no_grad()
     def run(self, inputs: dict) -> Generator[Tuple[int, np.ndarray], None, None]:

@@ -89,6 +89,7 @@ _SIGS = {
     "gsv_t2s_session_admit": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsv_t2s_session_advance": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsv_t2s_session_release": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "gsv_t2s_session_end": (C.c_int, [C.c_void_p]),
     "gsv_t2s_session_state": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gsv_t2s_session_adopt_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int64)]),

@@ -89,15 +89,22 @@ def streaming_generator(tts_generator, media_type: str):
         yield pack_audio(BytesIO(), chunk, sr, media_type).getvalue()
 
 
-def tts_handle(tts_pipeline, req: dict):
+def tts_handle(tts_pipeline, req: dict, server=None):
     """api_v2.py:300-373 without the web framework: -> (status code, media type, payload); payload is bytes, an iterator of
-    bytes (streaming_mode) or, on failure, the reference's error dict."""
+    bytes (streaming_mode) or, on failure, the reference's error dict.
+    server (gsv.serving.Server, e.g. tts_pipeline.serve()): the request is submitted to it and this call waits for its
+    future, so that calls from several threads share the server's decode session and waveform passes; a streaming /
+    return_fragment request goes through it as an exclusive request and its fragments are framed here."""
     streaming_mode = req.get("streaming_mode", False)
     media_type = req.get("media_type", "wav")
     if streaming_mode or req.get("return_fragment", False):
         req = dict(req, return_fragment=True)
     try:
-        gen = tts_pipeline.run(req)
+        if server is not None:
+            result = server.submit(req).result()
+            gen = iter(result if isinstance(result, list) else [result])
+        else:
+            gen = tts_pipeline.run(req)
         if streaming_mode:
             return 200, f"audio/{media_type}", streaming_generator(gen, media_type)
         sr, audio = next(gen)
@@ -106,22 +113,28 @@ def tts_handle(tts_pipeline, req: dict):
         return 400, "application/json", {"message": "tts failed", "Exception": str(e)}
 
 
-def create_app(tts_pipeline):
-    """the reference's /tts routes (api_v2.py:416-470) over `tts_handle`; needs fastapi (present in this image)"""
+def create_app(tts_pipeline, server=None):
+    """the reference's /tts routes (api_v2.py:416-470) over `tts_handle`; needs fastapi (present in this image).
+    server (gsv.serving.Server): every request waits for its future on a worker thread, off the event loop, so concurrent
+    HTTP requests overlap in the server's decode session instead of being served one after the other."""
+    import asyncio
     from fastapi import FastAPI, Request
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     app = FastAPI()
 
-    def respond(req: dict):
-        code, mt, payload = tts_handle(tts_pipeline, req)
+    def answer(code, mt, payload):
         if code != 200:
             return JSONResponse(status_code=code, content=payload)
         if isinstance(payload, (bytes, bytearray)):
             return Response(payload, media_type=mt)
         return StreamingResponse(payload, media_type=mt)
 
-    @app.get("/tts")
-    async def tts_get(request: Request):
+    async def respond(req: dict):
+        if server is None:
+            return answer(*tts_handle(tts_pipeline, req))
+        return answer(*await asyncio.get_running_loop().run_in_executor(None, tts_handle, tts_pipeline, req, server))
+
+    async def tts_get(request):
         q = dict(request.query_params)
         for k in ("top_k", "batch_size", "seed", "sample_steps"):
             if k in q:
@@ -133,9 +146,13 @@ def create_app(tts_pipeline):
         for k in ("split_bucket", "streaming_mode", "parallel_infer", "super_sampling"):
             if k in q:
                 q[k] = str(q[k]).lower() in ("1", "true")
-        return respond(q)
+        return await respond(q)
 
-    @app.post("/tts")
-    async def tts_post(request: Request):
-        return respond(await request.json())
+    async def tts_post(request):
+        return await respond(await request.json())
+    # this module's annotations are strings, and FastAPI cannot resolve one that names a local import (it then asks for a
+    # query parameter "request" and answers 422): hand it the class itself
+    for route, fn in ((app.get, tts_get), (app.post, tts_post)):
+        fn.__annotations__["request"] = Request
+        route("/tts")(fn)
     return app

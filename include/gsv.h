@@ -139,6 +139,9 @@ int gsv_t2s_decode(gsv_t2s_t* h, const gsv_sampling_params* sp, const float* noi
  *   still live and every slot's step counter (either may be NULL).  fp16 on the v1/v2 shape with slots <= 128 runs the chunk as
  *   one launch of the persistent engine (a hand-off timeout re-runs the chunk on the launch-per-phase step), otherwise as
  *   n_steps replays of the step graph.  gsv_t2s_decode_info then describes this chunk.
+ * release: takes the rows of the n named slots [host] out of the decode (a cancelled request): one small launch clears their
+ *   live words, the next advance skips them and the slots can be admitted again.  A slot that holds no live row is left as it
+ *   is; no other slot, and no K/V, is touched.  GSV_ERR_ARG before the launch: a slot out of range or given twice.
  * end: closes the session; the handle behaves as before. */
 int gsv_t2s_session_begin(gsv_t2s_t* h, const gsv_sampling_params* sp, int slots, int row_sampling, int32_t* out_tokens,
                           int32_t* out_len);
@@ -146,6 +149,7 @@ int gsv_t2s_session_admit(gsv_t2s_t* h, int n, const int32_t* slot_ids, const in
                           const float* bert, const int32_t* prompts_packed, const int32_t* prompt_lens, const uint64_t* rng_seeds,
                           const int32_t* rng_rows, const gsv_row_sampling_t* row_sampling, gsv_stream_t stream);
 int gsv_t2s_session_advance(gsv_t2s_t* h, int n_steps, int* live_out, int* steps_out, gsv_stream_t stream);
+int gsv_t2s_session_release(gsv_t2s_t* h, int n, const int32_t* slot_ids, gsv_stream_t stream);
 int gsv_t2s_session_end(gsv_t2s_t* h);
 /* test hook: the slots' row state, state [host] int32 [4][slots] = cached positions | live | step counter | prompt length;
  * waits for the device */

@@ -1,0 +1,191 @@
+"""Open-arrival serving: the same seeded Poisson arrival trace, replayed in wall time, through three servers in ONE process
+(full-size synthetic v2 weights, fp16, --voices enrolled voices, requests of 1-4 sentences x 4 s):
+
+  (A) run() per request in arrival order -- what `wire.create_app` did before gsv.serving;
+  (B) windowed batching: collect for W ms from the first waiting request, then run_batch with the shared flags (W swept);
+  (C) gsv.serving.Server (chunk, admit_min, wave_hold swept).
+
+The offered loads are fractions of the closed-batch throughput that this process measures first with
+run_batch(all requests, shared_sovits=True).  Per server, setting and load: p50 / p95 of the time from submit to result,
+delivered audio-seconds per second, and for (C) the mean slot occupancy and the waveform passes per second -- medians over
+--repeats replays.  One JSON line per (server, setting, load), then a summary line.
+
+    python tools/serving_bench.py [--requests 96] [--voices 32] [--slots 32] [--loads 0.3,0.6,0.9] [--windows-ms 10,40]
+                                  [--chunks 8,32] [--admit-mins 1,8] [--wave-holds 0,2] [--repeats 7]
+"""
+import argparse
+import json
+import os
+import queue
+import random
+import statistics
+import sys
+import threading
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "gpt-sovits_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import torch  # noqa: E402
+
+
+def _pct(xs, q):
+    xs = sorted(xs)
+    return xs[min(len(xs) - 1, int(q * len(xs)))] if xs else float("nan")
+
+
+def _replay(arrivals, submit):
+    """calls submit(i) at arrivals[i] seconds after the start; returns the start time"""
+    t0 = time.perf_counter()
+    for i, at in enumerate(arrivals):
+        wait = t0 + at - time.perf_counter()
+        if wait > 0:
+            time.sleep(wait)
+        submit(i)
+    return t0
+
+
+def _report(t0, arrivals, done_at, audio_s):
+    lat = [done_at[i] - (t0 + arrivals[i]) for i in range(len(arrivals))]
+    span = max(done_at) - t0
+    return dict(p50_ms=round(1e3 * _pct(lat, 0.5), 1), p95_ms=round(1e3 * _pct(lat, 0.95), 1),
+                audio_s_per_s=round(sum(audio_s) / span, 1))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--requests", type=int, default=96)
+    ap.add_argument("--voices", type=int, default=32)
+    ap.add_argument("--slots", type=int, default=32)
+    ap.add_argument("--tokens", type=int, default=100, help="AR tokens per sentence (25 tokens = 1 s)")
+    ap.add_argument("--loads", default="0.3,0.6,0.9")
+    ap.add_argument("--windows-ms", default="10,40")
+    ap.add_argument("--chunks", default="8,32")
+    ap.add_argument("--admit-mins", default="1,8")
+    ap.add_argument("--wave-holds", default="0,2")
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args()
+    from bench import build_tts, make_segments
+    from gsv import synthetic as S
+    dev = torch.device("cuda:0")
+    N, TOK = a.requests, a.tokens
+    tts = build_tts(dev, TOK, a.slots, dtype_half=True)
+    tts.configs.max_seq = 80 + 160 + TOK + 16          # room for the longest voice's prompt
+    tts.t2s_model = None
+    tts.init_t2s_weights(tts.configs.t2s_weights_path, state=tts._t2s_state)
+    rng = random.Random(a.seed)
+    counts = [rng.randint(1, 4) for _ in range(N)]
+    utt, segs = make_segments(sum(counts))
+    n_ph = len(utt["prompt_phones"])
+    voices = [tts.make_voice(torch.from_numpy(S.hash_ints(f"sv_sem{i}", 60 + (i * 37) % 100, 1024, 1)),
+                             [S.make_refer_spec(frames=150 + 7 * i, seed=100 + i).to(dev).half()],
+                             phones=S.hash_ints(f"sv_ph{i}", n_ph, 732, 1).tolist(), bert_features=torch.zeros(1024, n_ph),
+                             norm_text="x" * n_ph) for i in range(a.voices)]
+    params = dict(top_k=15, top_p=1.0, temperature=1.0, repetition_penalty=1.35, fragment_interval=0.01)
+    reqs, at = [], 0
+    for i, c in enumerate(counts):
+        reqs.append(dict(params, segments=segs[at:at + c], batch_size=c, seed=7 + i, voice=voices[i % a.voices]))
+        at += c
+
+    def alone(r):
+        v = r["voice"]
+        tts.set_prompt_cache(v["prompt_semantic"], [s for s, _ in v["refer_spec"]], phones=v["phones"],
+                             bert_features=v["bert_features"], norm_text=v["norm_text"])
+        return list(tts.run({k: x for k, x in r.items() if k != "voice"}))[0]
+
+    # closed-batch capacity: everything at once through the shared stages (second of two passes: the first warms up)
+    for _ in range(2):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        outs = tts.run_batch(reqs, shared_sovits=True)
+        torch.cuda.synchronize()
+        closed_s = time.perf_counter() - t0
+    audio_s = [w.shape[0] / sr for sr, w in outs]
+    capacity = sum(audio_s) / closed_s
+    alone(reqs[0])
+    print(json.dumps(dict(record="closed_batch", requests=N, sentences=sum(counts), audio_s=round(sum(audio_s), 1),
+                          seconds=round(closed_s, 4), audio_s_per_s=round(capacity, 1))), flush=True)
+
+    def trace(load, rep):
+        r_ = random.Random(1000 * a.seed + rep)
+        rate = load * capacity / (sum(audio_s) / N)       # requests per second
+        t, out = 0.0, []
+        for _ in range(N):
+            t += r_.expovariate(rate)
+            out.append(t)
+        return out
+
+    def serve_a(arrivals):
+        q, done_at = queue.Queue(), [0.0] * N
+
+        def worker():
+            for _ in range(N):
+                i = q.get()
+                alone(reqs[i])
+                done_at[i] = time.perf_counter()
+        th = threading.Thread(target=worker)
+        th.start()
+        t0 = _replay(arrivals, q.put)
+        th.join()
+        return _report(t0, arrivals, done_at, audio_s)
+
+    def serve_b(arrivals, window):
+        q, done_at = queue.Queue(), [0.0] * N
+
+        def worker():
+            left = N
+            while left:
+                batch = [q.get()]
+                end = time.perf_counter() + window
+                while True:
+                    try:
+                        batch.append(q.get(timeout=max(0.0, end - time.perf_counter())))
+                    except queue.Empty:
+                        break
+                tts.run_batch([reqs[i] for i in batch], shared_sovits=True)
+                now = time.perf_counter()
+                for i in batch:
+                    done_at[i] = now
+                left -= len(batch)
+        th = threading.Thread(target=worker)
+        th.start()
+        t0 = _replay(arrivals, q.put)
+        th.join()
+        return _report(t0, arrivals, done_at, audio_s)
+
+    def serve_c(arrivals, **kw):
+        done_at, futs = [0.0] * N, [None] * N
+        server = tts.serve(slots=a.slots, **kw)
+
+        def submit(i):
+            futs[i] = server.submit(reqs[i])
+            futs[i].add_done_callback(lambda f, i=i: done_at.__setitem__(i, time.perf_counter()))
+        t0 = _replay(arrivals, submit)
+        for f in futs:
+            f.result()
+        server.shutdown()
+        st = server.scheduler.stats
+        out = _report(t0, arrivals, done_at, audio_s)
+        span = max(done_at) - t0
+        out.update(occupancy=round(statistics.mean(st["occupancy"]) / a.slots, 3) if st["occupancy"] else 0.0,
+                   waves_per_s=round(st["waves"] / span, 1), advances=st["advances"], admissions=st["admissions"],
+                   sessions=st["sessions"])
+        return out
+
+    settings = [("A", "run() per request", serve_a, {})]
+    settings += [("B", f"window {w} ms", serve_b, dict(window=float(w) / 1e3)) for w in a.windows_ms.split(",") if w]
+    settings += [("C", f"chunk {c} admit_min {m} wave_hold {h}", serve_c, dict(chunk=int(c), admit_min=int(m), wave_hold=int(h)))
+                 for c in a.chunks.split(",") if c for m in a.admit_mins.split(",") if m for h in a.wave_holds.split(",") if h]
+    for load in [float(x) for x in a.loads.split(",") if x]:
+        for kind, name, fn, kw in settings:
+            runs = [fn(trace(load, rep), **kw) for rep in range(a.repeats)]
+            med = {k: statistics.median(r[k] for r in runs) for k in runs[0]}
+            print(json.dumps(dict(record="serve", server=kind, setting=name, load=load, repeats=a.repeats, **med)), flush=True)
+    print(json.dumps(dict(record="engine", fallbacks=tts.t2s_model.engine_stats()[1])), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -435,6 +435,16 @@ __global__ __launch_bounds__(64) void sample_step_kernel(const float* __restrict
     for (int v = lane; v < V; v += 64) sp.dump[((long long)step * gridDim.x + b) * V + v] = logits[(long long)b * V + v];
   if (sp.drawn && lane == 0) { int* dr = sp.drawn + ((long long)step * gridDim.x + b) * 2; dr[0] = smp; dr[1] = amx; }
   if (sp.force) { smp = sp.force[(long long)b * sp.max_steps + step]; amx = smp; }    // teacher forcing (parity hook)
+  if (sp.logp) {     // the taken token's log-probability from the raw logits (sample_row penalised its own copy)
+    float xr[NPL];
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) {
+      const int v = lane + 64 * i;
+      xr[i] = v < Veff ? logits[(long long)b * V + v] : -INFINITY;
+    }
+    const float lp = token_logprob<NPL>(xr, Veff, smp);
+    if (lane == 0) sp.logp[(long long)b * sp.max_steps + step] = lp;
+  }
   const bool fin = (smp == EOS) || (amx == EOS);
   const bool early = (sp.early_stop_num != -1 && (step + 1) > sp.early_stop_num) || (step >= sp.max_steps - 1);
   if (lane == 0) {
@@ -474,6 +484,21 @@ __global__ __launch_bounds__(64) void sample_only_kernel(const float* __restrict
   sample_row<NPL>(logits + (long long)b * V, V, Veff, prev + (long long)b * prev_len, prev_len, top_k, top_p, temperature,
                   rp, noise ? noise + (long long)b * V : nullptr, seed, b, step, seen, &smp, &amx);
   if (threadIdx.x == 0) { sampled[b] = smp; argmax_tok[b] = amx; }
+}
+
+// the logits' rows of a batch -> out[b] = token_logprob of tokens[b] (gsv_op_token_logprob): grid = B, block = 64
+template <int NPL>
+__global__ __launch_bounds__(64) void token_logprob_kernel(const float* __restrict__ logits, int V, int Veff,
+                                                           const int* __restrict__ tokens, float* __restrict__ out) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  float x[NPL];
+#pragma unroll
+  for (int i = 0; i < NPL; ++i) {
+    const int v = lane + 64 * i;
+    x[i] = v < Veff ? logits[(long long)b * V + v] : -INFINITY;
+  }
+  const float lp = token_logprob<NPL>(x, Veff, tokens[b]);
+  if (lane == 0) out[b] = lp;
 }
 
 }  // namespace gsv
@@ -634,6 +659,8 @@ int decode_begin(gsv_t2s* h, const gsv_sampling_params* sp, const float* noise, 
   p.plen = h->d_plen; p.rng_seed = h->d_rng_seed; p.rng_row = h->d_rng_row;
   p.force = h->dbg_force; p.dump = h->dbg_dump; p.drawn = h->dbg_drawn;
   h->dbg_force = nullptr; h->dbg_dump = nullptr; h->dbg_drawn = nullptr;
+  p.logp = h->logp_next; h->logp_next = nullptr;
+  h->logp_on = p.logp != nullptr;
   // per-row sampling parameters: gsv_t2s_set_row_sampling's for this call (the four scalars above are then unused), else
   // null.  row_sampling_next stays until gsv_t2s_decode returns: a fallback re-run of the batch reads the same device array.
   const std::vector<gsv_row_sampling_t>& rsn = h->row_sampling_next;
@@ -769,7 +796,7 @@ int run_mega(gsv_t2s* h, int budget, int32_t* out_len, hipStream_t s) {
   MegaArgs a = mega_args(h, budget);
   GSV_RC(mega_prof_arm(a, budget, s));
   GSV_HIP(hipEventRecord(h->mega_ev[0], s));
-  GSV_RC(launch_t2s_mega(a, s));
+  GSV_RC(launch_t2s_mega(a, h->logp_on, s));
   GSV_HIP(hipEventRecord(h->mega_ev[1], s));
   GSV_HIP(hipMemcpyAsync(m.h_err, m.err, 16, hipMemcpyDeviceToHost, s));
   GSV_HIP(hipMemcpyAsync(h->h_pinned, h->d_step, 4, hipMemcpyDeviceToHost, s));
@@ -939,9 +966,11 @@ StepParams session_params(const gsv_t2s* h, bool staging) {
     p.out_tokens = z.st_out_tokens; p.out_len = z.st_out_len; p.plen = z.st_plen; p.rng_seed = z.st_rng_seed;
     p.rng_row = z.st_rng_row; p.force = z.force ? z.st_force : nullptr; p.dump = z.dump ? z.st_dump : nullptr;
     p.drawn = z.drawn ? z.st_drawn : nullptr; p.row_sampling = z.row_sampling ? z.st_row_sampling : nullptr;
+    p.logp = z.logp ? z.st_logp : nullptr;
   } else {
     p.out_tokens = z.out_tokens; p.out_len = z.out_len; p.plen = h->d_plen; p.rng_seed = h->d_rng_seed; p.rng_row = h->d_rng_row;
     p.force = z.force; p.dump = z.dump; p.drawn = z.drawn; p.row_sampling = z.row_sampling ? h->d_row_sampling : nullptr;
+    p.logp = z.logp;
   }
   return p;
 }
@@ -971,12 +1000,15 @@ int session_begin(gsv_t2s* h, const gsv_sampling_params* sp, int slots, int row_
   GSV_RC(need(h, "ses_ybuf", mb * d * 4, (void**)&z.st_ybuf));
   GSV_RC(need(h, "ses_logits", mb * V * 4, (void**)&z.st_logits));
   GSV_RC(need(h, "ses_dump", mb * V * 4, (void**)&z.st_dump));
+  GSV_RC(need(h, "ses_logp", mb * ms * 4, (void**)&z.st_logp));
   GSV_HIP(hipMemset(z.st_logits, 0, mb * V * 4));
   for (auto& e : z.ev) if (!e) GSV_HIP(hipEventCreate(&e));
   z.sp = *sp; z.slots = slots; z.budget = session_budget(*sp); z.row_sampling = row_sampling != 0;
   z.out_tokens = out_tokens; z.out_len = out_len;
   z.force = h->dbg_force; z.dump = h->dbg_dump; z.drawn = h->dbg_drawn;
   h->dbg_force = nullptr; h->dbg_dump = nullptr; h->dbg_drawn = nullptr;
+  z.logp = h->logp_next; h->logp_next = nullptr;
+  h->logp_on = z.logp != nullptr;
   // every slot free: active = 0, and every per-row array the kernels load for a free slot holds zeros
   GSV_HIP(hipMemset(h->d_kv_len, 0, (3 * mb + 4) * 4));
   GSV_HIP(hipMemset(h->d_plen, 0, 2 * mb * 4));
@@ -1042,6 +1074,7 @@ int session_admit(gsv_t2s* h, int n, const int32_t* slot_ids, const int32_t* pho
   a.dst_state = h->d_kv_len; a.dst_plen = h->d_plen; a.dst_ytok = h->d_ytok; a.dst_rng_row = h->d_rng_row;
   a.dst_out_tokens = z.out_tokens; a.dst_out_len = z.out_len; a.dst_drawn = z.drawn; a.dst_rng_seed = h->d_rng_seed;
   a.dst_row_sampling = z.row_sampling ? h->d_row_sampling : nullptr; a.dst_ybuf = h->ybuf; a.dst_dump = z.dump;
+  a.src_logp = z.st_logp; a.dst_logp = z.logp;
   GSV_HIP(hipEventRecord(z.ev[0], s));
   GSV_RC(launch_session_adopt(a, s));
   GSV_HIP(hipEventRecord(z.ev[1], s));
@@ -1375,7 +1408,7 @@ int gsv_t2s_session_end(gsv_t2s_t* h) {
   GSV_HIP(hipDeviceSynchronize());
   T2SSession& z = h->ses;
   z.open = false; z.live.clear();
-  z.out_tokens = nullptr; z.out_len = nullptr; z.force = nullptr; z.dump = nullptr; z.drawn = nullptr;
+  z.out_tokens = nullptr; z.out_len = nullptr; z.force = nullptr; z.dump = nullptr; z.drawn = nullptr; z.logp = nullptr;
   h->B = 0;   // the next decode needs a prefill of its own, as on a fresh handle
   h->rng_seed_up.clear(); h->rng_row_up.clear(); h->row_sampling_up.clear();
   return GSV_OK;
@@ -1428,6 +1461,12 @@ int gsv_t2s_set_prefill_gemm(gsv_t2s_t* h, int mode) {
 int gsv_t2s_set_debug(gsv_t2s_t* h, const int32_t* force_tokens, float* logits_dump, int32_t* drawn_dump) {
   GSV_REQUIRE(h && h->finalized, "t2s_set_debug: handle not finalized");
   h->dbg_force = force_tokens; h->dbg_dump = logits_dump; h->dbg_drawn = drawn_dump;
+  return GSV_OK;
+}
+
+int gsv_t2s_set_logprobs(gsv_t2s_t* h, float* out_logp) {
+  GSV_REQUIRE(h && h->finalized, "t2s_set_logprobs: handle not finalized");
+  h->logp_next = out_logp;
   return GSV_OK;
 }
 
@@ -1515,6 +1554,18 @@ int gsv_op_sample(const float* logits, int B, int vocab, int vocab_eff, const in
     GSV_LAUNCH(sample_only_kernel<decltype(npl)::value>, dim3(B), dim3(64), lds, s, logits, vocab, vocab_eff, prev, prev_len,
                sp->top_k, sp->top_p, sp->temperature, sp->repetition_penalty, noise, (unsigned long long)sp->seed, step, sampled,
                argmax_tok, (const RowSampling*)nullptr);
+    return GSV_OK;
+  });
+}
+
+int gsv_op_token_logprob(const float* logits, int B, int vocab, int vocab_eff, const int32_t* tokens, float* out,
+                         gsv_stream_t stream) {
+  GSV_REQUIRE(logits && tokens && out && B > 0, "op_token_logprob: null argument");
+  GSV_REQUIRE(vocab >= 1 && vocab <= 2048 && vocab_eff >= 1 && vocab_eff <= vocab, "op_token_logprob: bad vocab %d / %d", vocab,
+              vocab_eff);
+  return with_npl(vocab, [&](auto npl) -> int {
+    GSV_LAUNCH(token_logprob_kernel<decltype(npl)::value>, dim3(B), dim3(64), 0, (hipStream_t)stream, logits, vocab, vocab_eff,
+               tokens, out);
     return GSV_OK;
   });
 }

@@ -21,6 +21,7 @@ struct T2SSession {
   gsv_sampling_params sp;
   int32_t *out_tokens = nullptr, *out_len = nullptr;         // the caller's, [slots][max_steps] and [slots]
   const int* force = nullptr; float* dump = nullptr; int* drawn = nullptr;   // gsv_t2s_set_debug's, held for the whole session
+  float* logp = nullptr;                                     // gsv_t2s_set_logprobs', [slots][max_steps], likewise
   std::vector<char> live;                                    // host view of active[], refreshed by every admit / advance
   // staging: what a prefill and the step-0 tail write, sized for max_batch rows (the K/V arena grows with the admissions)
   int *st_state = nullptr, *st_plen = nullptr, *st_ytok = nullptr, *st_rng_row = nullptr, *st_out_tokens = nullptr,
@@ -28,7 +29,7 @@ struct T2SSession {
   unsigned long long* st_rng_seed = nullptr;
   gsv::RowSampling* st_row_sampling = nullptr;
   gsv::StepParams* st_sp = nullptr;
-  float *st_ybuf = nullptr, *st_logits = nullptr, *st_dump = nullptr;
+  float *st_ybuf = nullptr, *st_logits = nullptr, *st_dump = nullptr, *st_logp = nullptr;
   hipEvent_t ev[2] = {nullptr, nullptr};                     // around the adopt launch
   float last_adopt_ms = 0.f; long long last_adopt_bytes = 0;
 };
@@ -78,6 +79,8 @@ struct gsv_t2s : gsveng::Ctx {
   bool mega_on = true;      // gsv_t2s_set_mega (A/B inside one process); GSV_T2S_NO_MEGA=1 never builds the engine
   int prefill_gemm = 2;     // gsv_t2s_set_prefill_gemm: 0 dispatcher only, 1 panel GEMM wherever eligible, 2 from PANEL_MIN_ROWS rows upwards
   const int* dbg_force = nullptr; float* dbg_dump = nullptr; int* dbg_drawn = nullptr; int dbg_stall = 0;   // gsv_t2s_set_debug / gsv_t2s_debug_stall: apply to the NEXT decode call only
+  float* logp_next = nullptr;   // gsv_t2s_set_logprobs: the NEXT decode call (or the session begun next) only
+  bool logp_on = false;         // the StepParams at d_sp hold a log-probability pointer: run_mega launches a LOGP kernel
   std::map<int, hipGraphExec_t> graphs;
   T2SSession ses;
 };
@@ -104,12 +107,12 @@ struct AdoptArgs {
             *src_out_len = nullptr, *src_drawn = nullptr;
   const unsigned long long* src_rng_seed = nullptr;
   const RowSampling* src_row_sampling = nullptr;
-  const float *src_ybuf = nullptr, *src_dump = nullptr;
+  const float *src_ybuf = nullptr, *src_dump = nullptr, *src_logp = nullptr;
   int *dst_state = nullptr, *dst_plen = nullptr, *dst_ytok = nullptr, *dst_rng_row = nullptr, *dst_out_tokens = nullptr,
       *dst_out_len = nullptr, *dst_drawn = nullptr;
   unsigned long long* dst_rng_seed = nullptr;
   RowSampling* dst_row_sampling = nullptr;
-  float *dst_ybuf = nullptr, *dst_dump = nullptr;
+  float *dst_ybuf = nullptr, *dst_dump = nullptr, *dst_logp = nullptr;
 };
 int launch_session_adopt(const AdoptArgs& a, hipStream_t s);
 // ybuf[b] = e_audio[tok] + alpha_a * pe[P_b + step - 1], tok = ytok[b][P_b + step - 1], for every live row: the input embedding

@@ -704,7 +704,12 @@ __device__ __forceinline__ void kv_stage_store(const Ctx& q, int qd, int extra, 
 // logits of every quad have been published, so that the samplers of all quads work side by side.  A MACRO, not a function: as an
 // (inlined) function taking the context by reference the same text cost > 1000 spilled VGPRs in every kernel variant.
 // Expects a, q, sp, s, ep0, EPS, seen in scope.
-#define MG_RUN_SAMPLER() do { \
+// LOGP (a compile-time constant): the taken token's log-probability goes to sp.logp (gsv_t2s_set_logprobs), computed from
+// the raw logits this lane has just stored to logits_out and reads back -- taken from lv[] they stay live across sample_core
+// next to its own 17 registers: ~400 spilled VGPRs.  As a run-time branch on the pointer alone even the read-back form costs
+// the kernels that never take it 13 VGPRs and 80 bytes of scratch per lane, so those carry no trace of it and
+// launch_t2s_mega picks a LOGP kernel only when the pointer is set (DESIGN.md section 4p has the table).
+#define MG_RUN_SAMPLER(LOGP) do { \
   const int V = a.V, EOS = a.V - 1; \
   const unsigned epE = ep0 + 4 * a.L + 2; \
     relaunder(q); \
@@ -747,6 +752,16 @@ __device__ __forceinline__ void kv_stage_store(const Ctx& q, int qd, int extra, 
       } \
       if (sp.drawn && q.lane == 0) { int* dr = sp.drawn + ((size_t)step * a.B + b) * 2; dr[0] = smp; dr[1] = amx; } \
       if (sp.force) { smp = sp.force[(size_t)b * sp.max_steps + step]; amx = smp; } \
+      if constexpr (LOGP) if (sp.logp) { \
+        float xr[17]; \
+  _Pragma("unroll") \
+        for (int i = 0; i < 17; ++i) { \
+          const int v = q.lane + 64 * i; \
+          xr[i] = v < Veff ? a.logits_out[(size_t)b * V + v] : -INFINITY;   /* this lane's own stores above: the raw logits */ \
+        } \
+        const float lpv = token_logprob<17>(xr, Veff, smp); \
+        if (q.lane == 0) sp.logp[(size_t)b * sp.max_steps + step] = lpv; \
+      } \
       const bool fin = smp == EOS || amx == EOS; \
       const bool early = (sp.early_stop_num != -1 && (step + 1) > sp.early_stop_num) || step >= sp.max_steps - 1; \
       const int P_b = st_plen(q)[r]; \
@@ -1022,7 +1037,7 @@ __device__ __forceinline__ void logits_publish(unsigned char* smem, int lane, in
 // One quad per group (B <= 32).  Every phase waits out its hop: the comm waves sweep it into the operand image, B1, the
 // compute waves multiply, B2, reduce and publish.
 // ---------------------------------------------------------------------------------------------------------------
-template <bool PROF>
+template <bool PROF, bool LOGP>
 __device__ __forceinline__ void comm_role(const MegaArgs& a, const Ctx& c0, const StepParams& sp) {
   Ctx q = c0;
   unsigned char* smem = c0.smem;
@@ -1100,7 +1115,7 @@ __device__ __forceinline__ void comm_role(const MegaArgs& a, const Ctx& c0, cons
     sweep_ln<false>(q, ra, q.hop + HOP_A, ep0 + 4 * a.L + 1, 6u, a.hint_mask & 1, nullptr, 0, 0, true, gA, bA);
     MG_BAR();                                                             // B1
     MG_BAR();                                                            // B2
-    if (sampler) MG_RUN_SAMPLER();
+    if (sampler) MG_RUN_SAMPLER(LOGP);
   }
 }
 
@@ -1240,6 +1255,7 @@ __device__ __forceinline__ void compute_role(const MegaArgs& a, const Ctx& c0) {
 // LN(hop A) of this quad is in its XS copy) and B_b (the image of this quad is stored; the QKV partials are parked).
 // The member's 16 residual columns of every row are parked per quad by the LayerNorm itself (no XRES image).
 // ---------------------------------------------------------------------------------------------------------------
+template <bool LOGP>
 __device__ __forceinline__ void comm_role_pipe(const MegaArgs& a, const Ctx& c0, const StepParams& sp) {
   Ctx q = c0;
   unsigned char* smem = c0.smem;
@@ -1330,7 +1346,7 @@ __device__ __forceinline__ void comm_role_pipe(const MegaArgs& a, const Ctx& c0,
       if (qd + 1 < nq) sweep_t(qd + 1);
     }
     MG_BAR();                 // end of the step's GEMMs: the last logits GEMM has read its XS copy (the next step's first sweep rewrites copy 0)
-    if (sampler) MG_RUN_SAMPLER();
+    if (sampler) MG_RUN_SAMPLER(LOGP);
   }
 }
 
@@ -1441,7 +1457,8 @@ __device__ __forceinline__ void compute_role_pipe(const MegaArgs& a, const Ctx& 
 // PIPE = false: one quad per group (B <= 32); true: several quads, pipelined (32 < B <= 128)
 // PROF: the in-kernel stamps (tools/mega_prof.py) are compiled in only for measurement launches -- as run-time tests they
 // cost ~100 scalar instructions per layer and wave.  Only the single-quad roles carry stamps.
-template <bool PIPE, bool PROF>
+// LOGP: the sampler also writes the taken token's log-probability (MG_RUN_SAMPLER).
+template <bool PIPE, bool PROF, bool LOGP>
 __global__ __launch_bounds__(MG_THREADS, 1) void t2s_mega_kernel(MegaArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   Ctx c;
@@ -1521,10 +1538,10 @@ __global__ __launch_bounds__(MG_THREADS, 1) void t2s_mega_kernel(MegaArgs a) {
   __syncthreads();
   if (group_done(c)) return;
   if constexpr (PIPE) {
-    if (c.comm) comm_role_pipe(a, c, sp);
+    if (c.comm) comm_role_pipe<LOGP>(a, c, sp);
     else compute_role_pipe(a, c);
   } else {
-    if (c.comm) comm_role<PROF>(a, c, sp);
+    if (c.comm) comm_role<PROF, LOGP>(a, c, sp);
     else compute_role<PROF>(a, c);
   }
 }
@@ -1603,20 +1620,23 @@ int mega_census(hipStream_t s, unsigned* d_scratch, unsigned* h_pinned) {
   return (h_pinned[0] == (unsigned)MG_NWG && h_pinned[1] == 0u) ? 1 : 0;
 }
 
-int launch_t2s_mega(const MegaArgs& a, hipStream_t s) {
+int launch_t2s_mega(const MegaArgs& a, bool logp, hipStream_t s) {
   // every launch: the attribute belongs to the (function, device) pair, and TTS.set_device may have moved the handle's owner
   // to another GPU of the process since the last launch (mega_census does the same)
-#define GSV_MEGA_LAUNCH(PIPE, PROF)                                                                                              \
-  do {                                                                                                                          \
-    GSV_HIP(hipFuncSetAttribute((const void*)t2s_mega_kernel<PIPE, PROF>, hipFuncAttributeMaxDynamicSharedMemorySize, L_TOTAL)); \
-    hipLaunchKernelGGL((t2s_mega_kernel<PIPE, PROF>), dim3(MG_NWG), dim3(MG_THREADS), L_TOTAL, s, a);                            \
+#define GSV_MEGA_LAUNCH(PIPE, PROF, LOGP)                                                                                              \
+  do {                                                                                                                                \
+    GSV_HIP(hipFuncSetAttribute((const void*)t2s_mega_kernel<PIPE, PROF, LOGP>, hipFuncAttributeMaxDynamicSharedMemorySize, L_TOTAL)); \
+    hipLaunchKernelGGL((t2s_mega_kernel<PIPE, PROF, LOGP>), dim3(MG_NWG), dim3(MG_THREADS), L_TOTAL, s, a);                            \
   } while (0)
   // Three kernels.  More than one quad per group (B > 32): pipelined quads, which carry no stamps -- a profiling request
   // (a.prof, tools/mega_prof.py) at B > 32 runs this kernel all the same and its stamp buffer stays zero.  One quad: stamps
-  // compiled in for measurement launches only.
-  if (a.B > RMAX * MG_GROUPS) GSV_MEGA_LAUNCH(true, false);
-  else if (a.prof != nullptr) GSV_MEGA_LAUNCH(false, true);
-  else GSV_MEGA_LAUNCH(false, false);
+  // compiled in for measurement launches only.  logp (the decode's StepParams hold a log-probability pointer): the two
+  // kernels whose sampler writes it, which carry no stamps either.
+  if (logp && a.B > RMAX * MG_GROUPS) GSV_MEGA_LAUNCH(true, false, true);
+  else if (logp) GSV_MEGA_LAUNCH(false, false, true);
+  else if (a.B > RMAX * MG_GROUPS) GSV_MEGA_LAUNCH(true, false, false);
+  else if (a.prof != nullptr) GSV_MEGA_LAUNCH(false, true, false);
+  else GSV_MEGA_LAUNCH(false, false, false);
 #undef GSV_MEGA_LAUNCH
   GSV_HIP(hipGetLastError());
   return GSV_OK;

@@ -39,6 +39,9 @@ struct StepParams {
   int* drawn;              // [max_steps][B][2]: (token the sampler drew, argmax of the penalised logits) before any forcing
   // [B] or null: row b samples with row_sampling[b] instead of top_k / top_p / temperature / rep_penalty above
   const RowSampling* row_sampling;
+  // [B][max_steps] or null (gsv_t2s_set_logprobs), indexed like out_tokens: the log-probability of the token row b takes at
+  // step s under the model's own distribution (token_logprob below); the step that ends the row has its entry too
+  float* logp;
 };
 
 // Row b's entry of a RowSampling array.  b is wave-uniform at every call site, so the four values are made scalars again:
@@ -246,6 +249,32 @@ __device__ __forceinline__ void sample_core(float (&x)[NPL], int Veff, int top_k
   *out_sample = sm.i;
 }
 
+
+// Log-probability of token `tok` under the softmax of the RAW logits x[] (temperature 1, no repetition penalty, no top-k /
+// top-p cut) over the first Veff tokens: x[tok] - max - log(sum exp(x - max)).  One wave per row, this lane's tokens
+// v = lane + 64 i as in sample_core; tok is wave-uniform.  A token outside [0, Veff) -- the masked EOS column, which only
+// forcing can take -- has probability 0: -inf.  Every lane returns the value.
+template <int NPL>
+__device__ __forceinline__ float token_logprob(const float (&x)[NPL], int Veff, int tok) {
+  const int lane = threadIdx.x & 63;
+  tok = __builtin_amdgcn_readfirstlane(tok);
+  float m = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < NPL; ++i) if (lane + 64 * i < Veff) m = fmaxf(m, x[i]);
+  m = wave_max(m);
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < NPL; ++i) if (lane + 64 * i < Veff) s += expf(x[i] - m);
+  const float S = wave_sum(s);
+  if (tok < 0 || tok >= Veff) return -INFINITY;
+  // the owner lane picks its register by comparing token numbers: selected by the register index tok >> 6 the compiler turns
+  // the chain into an indexed load of x[] from scratch (80 bytes per lane in every kernel that inlines this)
+  float xi = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < NPL; ++i) xi = lane + 64 * i == tok ? x[i] : xi;
+  const float xt = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, xi), tok & 63));
+  return (xt - m) - logf(S);
+}
 
 template <int NPL>
 __device__ void sample_row(const float* __restrict__ lg_row, int V, int Veff, const int* __restrict__ prev, int prev_len,

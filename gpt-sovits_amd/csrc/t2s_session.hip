@@ -69,6 +69,7 @@ __global__ __launch_bounds__(256) void session_adopt_kernel(AdoptArgs a, int hg 
     a.dst_out_len[slot] = a.src_out_len[i];
     a.dst_out_tokens[(size_t)slot * a.dst_steps] = a.src_out_tokens[(size_t)i * a.src_steps];
     if (a.dst_drawn) { a.dst_drawn[2 * slot] = a.src_drawn[2 * i]; a.dst_drawn[2 * slot + 1] = a.src_drawn[2 * i + 1]; }
+    if (a.dst_logp) a.dst_logp[(size_t)slot * a.dst_steps] = a.src_logp[(size_t)i * a.src_steps];   // step 0's log-probability
   }
   const int hist = min(P + step, a.ycap);                                // prompt + the tokens sampled so far
   for (int t = tid; t < hist; t += 256) a.dst_ytok[(size_t)slot * a.ycap + t] = a.src_ytok[(size_t)i * a.ycap + t];

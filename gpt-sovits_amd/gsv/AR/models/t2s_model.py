@@ -91,7 +91,7 @@ class T2SSession:
     advanced a chunk of steps at a time and admitted again when their row has finished.  Use as a context manager."""
 
     def __init__(self, dec: "Text2SemanticDecoder", slots, top_k, top_p, temperature, repetition_penalty, early_stop_num,
-                 eos_mask_steps, max_steps, row_sampling=False, force=False, dump_logits=False):
+                 eos_mask_steps, max_steps, row_sampling=False, force=False, dump_logits=False, logprobs=False):
         if not dec._loaded:
             raise RuntimeError("load_state_dict() first")
         self.dec, self.slots, self.per_row = dec, int(slots), bool(row_sampling)
@@ -103,6 +103,8 @@ class T2SSession:
         self._next_ticket = 0
         self.modes: List[int] = []          # decode_info mode of every advance that ran a step
         self.logits: Dict[int, torch.Tensor] = {}   # dump_logits: ticket -> [steps run][vocab]
+        self.logprobs: Dict[int, torch.Tensor] = {} # logprobs: ticket -> [idx + 1], the taken tokens' log-probabilities
+        self.cut: Dict[int, bool] = {}              # logprobs: ticket -> the step budget ended the row, not EOS
         self.adopt: List[tuple] = []        # (rows, device ms, K/V bytes) of every admission
         self.history: List[tuple] = []      # (ticket, slot) of every admitted row
         self._open = False
@@ -111,6 +113,7 @@ class T2SSession:
             self.out_len = torch.full((self.slots,), -1, dtype=torch.int32, device=dev)
             self.force = torch.zeros(self.slots, self.budget, dtype=torch.int32, device=dev) if force else None
             self.dump = torch.zeros(self.budget, self.slots, dec.vocab_size, dtype=torch.float32, device=dev) if dump_logits else None
+            self.logp = torch.full((self.slots, self.budget), float("nan"), dtype=torch.float32, device=dev) if logprobs else None
             sp = _lib.SamplingParams(int(top_k) if top_k is not None else 0, float(top_p if top_p is not None else 1.0),
                                      float(temperature), float(repetition_penalty),
                                      -1 if early_stop_num is None else int(early_stop_num), int(eos_mask_steps),
@@ -120,6 +123,8 @@ class T2SSession:
             if force or dump_logits:
                 _lib.check(l.gsv_t2s_set_debug(dec._h, self.force.data_ptr() if force else None,
                                                self.dump.data_ptr() if dump_logits else None, None), "gsv_t2s_set_debug")
+            if logprobs:
+                _lib.check(l.gsv_t2s_set_logprobs(dec._h, self.logp.data_ptr()), "gsv_t2s_set_logprobs")
             _lib.check(l.gsv_t2s_session_begin(dec._h, C.byref(sp), self.slots, int(self.per_row), self.out_tokens.data_ptr(),
                                                self.out_len.data_ptr()), "gsv_t2s_session_begin")
         self._open = True
@@ -252,6 +257,9 @@ class T2SSession:
                     out.append((self._owner[s], torch.cat([self._prompt[s], self.out_tokens[s, :n].long()]), n))
                     if self.dump is not None:
                         self.logits[self._owner[s]] = self.dump[:steps_h[s], s].clone()
+                    if self.logp is not None:
+                        self.logprobs[self._owner[s]] = self.logp[s, :n + 1].clone()
+                        self.cut[self._owner[s]] = n >= self.budget - 1
                     self._owner[s], self._prompt[s] = None, None
         return out
 
@@ -341,11 +349,14 @@ class Text2SemanticDecoder:
 
     def _run(self, x: Sequence[torch.Tensor], prompts: torch.Tensor, bert: Sequence[torch.Tensor], top_k, top_p,
              early_stop_num, temperature, repetition_penalty, eos_mask_steps, noise=None, seed=0,
-             max_steps: int = 1500, force_tokens=None, dump_logits=False, rng_keys=None, row_sampling=None):
+             max_steps: int = 1500, force_tokens=None, dump_logits=False, rng_keys=None, row_sampling=None, logprobs=False):
         """prompts: [B, P] (one prompt length for the batch; P = 0 or None: prompt-free) or a list of B 1-D prompts of
         lengths P_b >= 1 (ragged: gsv_t2s_prefill_ragged).  rng_keys: optional [(seed_b, row_b)] per row, the counter-RNG
         key that replaces (seed, b) (gsv_t2s_set_row_rng).  row_sampling: optional [(top_k, top_p, temperature,
-        repetition_penalty)] per row, which replace the four scalar arguments for this call (gsv_t2s_set_row_sampling)."""
+        repetition_penalty)] per row, which replace the four scalar arguments for this call (gsv_t2s_set_row_sampling).
+        logprobs=True leaves last_logprobs: B 1-D fp32 tensors, row b's idx[b] + 1 log-probabilities of the tokens it took
+        under the model's own distribution (gsv_t2s_set_logprobs): the generated tokens, then the finishing step; and
+        last_cut: per row, whether the step budget ended it instead of EOS."""
         if not self._loaded:
             raise RuntimeError("load_state_dict() first")
         B = len(x)
@@ -386,6 +397,7 @@ class Text2SemanticDecoder:
                 pr = prompts.to(dev, torch.int32).contiguous()
             out_tokens = torch.zeros(B, budget, dtype=torch.int32, device=dev)
             out_len = torch.full((B,), -1, dtype=torch.int32, device=dev)
+            logp = torch.full((B, budget), float("nan"), dtype=torch.float32, device=dev) if logprobs else None
             noise_dev, noise_rows = None, 0
             if noise is not None:
                 noise_dev = noise.to(dev, torch.float32).contiguous()
@@ -442,6 +454,8 @@ class Text2SemanticDecoder:
                                                drawn.data_ptr() if drawn is not None else None), "gsv_t2s_set_debug")
                 self.last_drawn_dump = drawn
             self.last_logits_dump = dump
+            if logp is not None:
+                _lib.check(l.gsv_t2s_set_logprobs(self._h, logp.data_ptr()), "gsv_t2s_set_logprobs")
             _lib.check(l.gsv_t2s_decode(self._h, C.byref(sp), noise_dev.data_ptr() if noise_dev is not None else None,
                                         noise_rows, out_tokens.data_ptr(), out_len.data_ptr(), C.byref(steps), s),
                        "gsv_t2s_decode")
@@ -470,6 +484,9 @@ class Text2SemanticDecoder:
                     y_list.append(torch.cat([pr_all[offs[b]:offs[b + 1]], gen_all[b, :n]]))
                 else:
                     y_list.append(y_all[b, :P + n])
+            self.last_logprob_buffer = logp     # [B][budget], NaN where a row ran no step; last_logprobs are views of it
+            self.last_logprobs = None if logp is None else [logp[b, :idx[b] + 1] for b in range(B)]
+            self.last_cut = None if logp is None else [idx[b] >= budget - 1 for b in range(B)]
         return y_list, idx
 
     # ---- reference entry points -----------------------------------------------------
@@ -485,7 +502,8 @@ class Text2SemanticDecoder:
         per row, every length >= 1).  kwarg `rng_keys=[(seed, row), ...]`: row i draws with the counter-RNG key
         (seed, row) instead of (seed kwarg, its row in the launch), so it samples the same tokens whichever batch it
         is decoded in.  kwarg `row_sampling=[(top_k, top_p, temperature, repetition_penalty), ...]`: row i samples with
-        its own tuple instead of the four arguments (parallel decode only; the prompt-free loop takes the arguments)."""
+        its own tuple instead of the four arguments (parallel decode only; the prompt-free loop takes the arguments).
+        kwarg `logprobs=True`: last_logprobs / last_cut of `_run`, for all rows in input order (parallel decode only)."""
         rng_keys = kwargs.get("rng_keys")
         if rng_keys is not None and len(rng_keys) != len(x):
             raise ValueError(f"{len(rng_keys)} RNG keys for {len(x)} rows")
@@ -498,6 +516,8 @@ class Text2SemanticDecoder:
         out = []
         ys: List[Optional[torch.Tensor]] = [None] * len(x)
         idxs: List[Optional[int]] = [None] * len(x)
+        want_lp = bool(kwargs.get("logprobs", False))
+        lps, cuts = [], []
         noise = kwargs.get("noise")
         for lo in range(0, len(x), self.max_batch):
             hi = min(lo + self.max_batch, len(x))
@@ -510,9 +530,13 @@ class Text2SemanticDecoder:
                              force_tokens=None if kwargs.get("force_tokens") is None else kwargs["force_tokens"][lo:hi],
                              dump_logits=kwargs.get("dump_logits", False),
                              rng_keys=None if rng_keys is None else list(rng_keys[lo:hi]),
-                             row_sampling=None if row_sampling is None else list(row_sampling[lo:hi]))
+                             row_sampling=None if row_sampling is None else list(row_sampling[lo:hi]), logprobs=want_lp)
             ys[lo:hi] = y
             idxs[lo:hi] = i
+            if want_lp:
+                lps += self.last_logprobs
+                cuts += self.last_cut
+        self.last_logprobs, self.last_cut = (lps, cuts) if want_lp else (None, None)
         return ys, idxs
 
     # ---- decode sessions: continuous batching ------------------------------------------
@@ -520,7 +544,9 @@ class Text2SemanticDecoder:
                      max_steps: int = 1500, row_sampling: bool = False, **debug) -> T2SSession:
         """Opens a decode session of `slots` rows (<= max_batch); until it is closed the other entry points of this decoder
         raise.  The four sampling values hold for every row unless row_sampling=True, in which case each admitted row brings
-        its own tuple.  debug: force=True / dump_logits=True, the parity hooks of `_run`, per slot."""
+        its own tuple.  debug: force=True / dump_logits=True, the parity hooks of `_run`, per slot.  logprobs=True: the
+        session fills `logprobs[ticket]` / `cut[ticket]` (what `_run(logprobs=True)` leaves for a row) when `advance` reports
+        the row."""
         return T2SSession(self, slots, top_k, top_p, temperature, repetition_penalty, early_stop_num, eos_mask_steps, max_steps,
                           row_sampling=row_sampling, **debug)
 
@@ -529,7 +555,7 @@ class Text2SemanticDecoder:
                                top_p: int = 100, early_stop_num: int = -1, temperature: float = 1.0,
                                repetition_penalty: float = 1.35, rng_keys=None, row_sampling=None, slots: Optional[int] = None,
                                chunk: int = 32, admit_min: Optional[int] = None, max_steps: int = 1500, force_tokens=None,
-                               dump_logits: bool = False):
+                               dump_logits: bool = False, logprobs: bool = False):
         """`infer_panel_batch_infer` for a queue of any length through ONE decode session: rows are admitted in the order given
         whenever `admit_min` slots are free (default max(1, slots // 4); see admit_count), `chunk` steps run between admissions
         (both defaults from the sweep of tools/continuous_ar_bench.py, profiles/continuous_ar.txt),
@@ -538,7 +564,8 @@ class Text2SemanticDecoder:
         decoded.  A row whose text + prompt leave the K/V arena less than the full step budget is decoded on its own by the
         ordinary path after the session (and listed in last_truncated if the arena cuts it), as it would be there.
         force_tokens [N][steps] / dump_logits: the parity hooks of `_run` (tests); last_logits_dump is then a list of N
-        [steps run][vocab] tensors.  last_session is the closed session (its history, modes and adopt times)."""
+        [steps run][vocab] tensors.  logprobs=True: last_logprobs / last_cut of `_run`, in input order.  last_session is the
+        closed session (its history, modes and adopt times)."""
         N = len(x)
         if rng_keys is None or len(rng_keys) != N:
             raise ValueError("infer_panel_continuous needs one RNG key (seed, row) per row")
@@ -560,10 +587,12 @@ class Text2SemanticDecoder:
         queue = [i for i in range(N) if fits[i]]
         ys: List[Optional[torch.Tensor]] = [None] * N
         idxs: List[Optional[int]] = [None] * N
+        lps: List[Optional[torch.Tensor]] = [None] * N
+        cuts: List[Optional[bool]] = [None] * N
         if queue:
             with self.open_session(slots, top_k, top_p, temperature, repetition_penalty, early_stop_num, 1, max_steps,
                                    row_sampling=row_sampling is not None, force=force_tokens is not None,
-                                   dump_logits=dump_logits) as ses:
+                                   dump_logits=dump_logits, logprobs=logprobs) as ses:
                 q, where = 0, {}
                 while q < len(queue) or ses.live:
                     k = admit_count(len(ses.free), len(queue) - q, ses.live, admit_min)
@@ -577,6 +606,9 @@ class Text2SemanticDecoder:
                 if dump_logits:
                     by_row = {i: ses.logits[t] for t, i in where.items()}
                     self.last_logits_dump = [by_row[i] for i in range(N)]
+                if logprobs:
+                    for t, i in where.items():
+                        lps[i], cuts[i] = ses.logprobs[t], ses.cut[t]
         truncated = []
         for i in range(N):
             if fits[i]:
@@ -584,10 +616,13 @@ class Text2SemanticDecoder:
             r = rows[i]
             sk = (top_k, top_p, temperature, repetition_penalty) if r["sampling"] is None else r["sampling"]
             y, n = self._run([r["x"]], [r["prompt"]], [r["bert"]], sk[0], sk[1], early_stop_num, sk[2], sk[3], eos_mask_steps=1,
-                             max_steps=max_steps, rng_keys=[r["key"]])
+                             max_steps=max_steps, rng_keys=[r["key"]], logprobs=logprobs)
             ys[i], idxs[i] = y[0], n[0]
+            if logprobs:
+                lps[i], cuts[i] = self.last_logprobs[0], self.last_cut[0]
             truncated += [i] * bool(self.last_truncated)
         self.last_truncated = truncated
+        self.last_logprobs, self.last_cut = (lps, cuts) if logprobs else (None, None)
         return ys, idxs
 
     @torch.no_grad()

@@ -83,6 +83,60 @@ def early_stop_num(configs) -> float:
     return configs.hz * (configs.max_sec if configs.max_sec is not None else 54)
 
 
+BEST_OF_MAX = 16            # candidates per sentence: row + 1024 * 15 fits the 24 bits the counter RNG's hash gives the row
+BEST_OF_ROW_STRIDE = 1024   # candidate c of the sentence with the key (seed, row) draws with (seed, row + 1024 c)
+
+
+def _mean_logprob(cand: dict) -> float:
+    """mean log-probability of a candidate's `n` generated tokens, in float64 on the host; the finishing step's entry is not
+    counted, and a candidate that generated nothing scores -inf"""
+    n = int(cand["n"])
+    if n <= 0:
+        return float("-inf")
+    lp = cand["logprobs"]
+    lp = lp.detach().cpu().numpy() if torch.is_tensor(lp) else np.asarray(lp)
+    return float(lp[:n].astype(np.float64).mean())
+
+
+def select_candidate(cands: Sequence[dict]) -> int:
+    """The default choice among the candidates of one sentence ("best_of").  Each is dict(tokens, logprobs, n, cut): the
+    generated tokens, the log-probabilities of the taken tokens (n generated ones, then the finishing step), their count and
+    whether the row was ended by early_stop_num, max_steps or the K/V arena instead of EOS.  Candidates that were not cut come
+    before cut ones; among those the highest mean log-probability of the n generated tokens wins; ties go to the lowest index."""
+    best, best_key = 0, None
+    for i, c in enumerate(cands):
+        key = (not c["cut"], _mean_logprob(c))
+        if best_key is None or key > best_key:
+            best, best_key = i, key
+    return best
+
+
+def check_best_of(o: dict, no_prompt: Optional[bool] = None) -> None:
+    """ValueError unless the options' "best_of" (present only when the request named one other than 1) is an int in
+    2 .. BEST_OF_MAX on a parallel decode with a prompt (no_prompt=None: the prompt is not known yet and not checked)"""
+    if "best_of" not in o:
+        return
+    n = o["best_of"]
+    if type(n) is not int or not 1 <= n <= BEST_OF_MAX:
+        raise ValueError(f"best_of must be an int in 1..{BEST_OF_MAX}, got {n!r}")
+    if "best_of_score" in o and not callable(o["best_of_score"]):
+        raise ValueError("best_of_score must be a callable: candidates -> index")
+    if not o["parallel_infer"]:
+        raise ValueError("best_of > 1 needs parallel_infer=True: the naive loop decodes a sentence alone")
+    if no_prompt:
+        raise ValueError("best_of > 1 needs a prompt: the prompt-free loop decodes a sentence alone")
+
+
+def choose_candidate(o: dict, cands: Sequence[dict]) -> Tuple[int, List[dict]]:
+    """(index of the chosen candidate, the record of the choice: dict(n, mean_logprob, cut, chosen) per candidate) under the
+    request's "best_of_score" callable, or select_candidate without one"""
+    k = o.get("best_of_score", select_candidate)(cands)
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k < len(cands):
+        raise ValueError(f"best_of_score returned {k!r} for {len(cands)} candidates")
+    return int(k), [dict(n=int(c["n"]), mean_logprob=_mean_logprob(c), cut=bool(c["cut"]), chosen=i == k)
+                    for i, c in enumerate(cands)]
+
+
 class TTS_Config:
     """The reference's TTS_Config surface (TTS.py:217-410): `configs` is a dict (the sections "v1" ... "v2ProPlus" and / or
     "custom", or directly the custom section's keys), a YAML file path, or None (defaults).  Differences, all forced by the
@@ -229,6 +283,7 @@ class TTS:
         self.text_preprocessor = TextPreprocessor(bert_fn=None, device="cpu")      # reference TTS.py:431-433
         self.vocoder_configs: dict = {"sr": None, "T_ref": None, "T_chunk": None, "upsample_rate": None, "overlapped_len": None}
         self._lora_voices: Dict[str, dict] = {}      # add_lora_voice: name -> {"slot", "engine", "state"}
+        self.last_candidates: list = []              # "best_of": the choices of the last run / run_batch call, [request][batch][sentence]
 
     # ---- weights (reference TTS.py:484-603) ------------------------------------------------
     def init_t2s_weights(self, weights_path: Optional[str] = None, state: Optional[dict] = None):
@@ -1161,6 +1216,37 @@ class TTS:
             return pred, [int(p.shape[0]) for p in pred]
         return [p[-i:] if i > 0 else p[:0] for p, i in zip(pred_list, idx_list)], idx_list
 
+    def _decode_best_of(self, item: dict, prompt: torch.Tensor, o: dict, seed_b: int):
+        """run()'s AR decode of one to_batch batch under "best_of" = n: every sentence n times, as n rows of the same
+        prefill.  Sentence j has the key (seed_b, j mod max_batch) in the plain decode; candidate c draws with
+        (seed_b, j mod max_batch + 1024 c), and each group of max_batch sentences keeps the step budget the plain decode
+        gives it, so candidate 0 is the plain draw.  Returns (pred_list, idx_list) of the chosen candidates and the record of
+        the choices per sentence (choose_candidate)."""
+        t2s, n = self.t2s_model, o["best_of"]
+        mb = t2s.max_batch
+        x, bert = item["all_phones"], item["all_bert_features"]
+        lens = [int(t.shape[-1]) for t in x]
+        wanted = min(1500, int(early_stop_num(self.configs)) + 1)
+        pred_list, idx_list, rec = [], [], []
+        for lo in range(0, len(x), mb):
+            js = [j for j in range(lo, min(lo + mb, len(x))) for _ in range(n)]
+            budget = min(wanted, t2s.max_seq - (max(lens[lo:lo + mb]) + int(prompt.shape[1]) + 2))
+            keys = [(seed_b, j % mb + BEST_OF_ROW_STRIDE * c) for j in range(lo, min(lo + mb, len(x))) for c in range(n)]
+            ys, idx = t2s.infer_panel_batch_infer([x[j] for j in js], None, prompt[:1].expand(len(js), -1), [bert[j] for j in js],
+                                                  top_k=o["top_k"], top_p=o["top_p"], temperature=o["temperature"],
+                                                  early_stop_num=early_stop_num(self.configs),
+                                                  repetition_penalty=o["repetition_penalty"], rng_keys=keys, max_steps=budget,
+                                                  logprobs=True)
+            lps, cuts = t2s.last_logprobs, t2s.last_cut
+            for s0 in range(0, len(js), n):
+                cands = [dict(tokens=ys[k][-idx[k]:] if idx[k] > 0 else ys[k][:0], logprobs=lps[k].cpu().numpy(), n=idx[k],
+                              cut=cuts[k]) for k in range(s0, s0 + n)]
+                k, r = choose_candidate(o, cands)
+                pred_list.append(ys[s0 + k])
+                idx_list.append(idx[s0 + k])
+                rec.append(r)
+        return pred_list, idx_list, rec
+
     def _synthesize_batch(self, item: dict, pred: List[torch.Tensor], pred_list: List[torch.Tensor], idx_list: List[int],
                           bi: int, actual_seed: int, opts: dict, voice_refer: Tuple[List[torch.Tensor], dict],
                           have: Optional[List[Optional[torch.Tensor]]] = None) -> List[torch.Tensor]:
@@ -1383,7 +1469,9 @@ class TTS:
         with a default.  An empty seed is -1 (random) and fragment_interval is at least 0.01; `split_bucket` and
         `super_sampling` are as given -- _resolve_options applies the rules that depend on the loaded model.
         "lora_voice" (a name given to add_lora_voice) is carried only when the request names one: absent or None is the base
-        model, and the options of such a request are the ones they were (read it with o.get("lora_voice"))."""
+        model, and the options of such a request are the ones they were (read it with o.get("lora_voice")).  "best_of"
+        (candidates per sentence) likewise only when the request names one other than 1, as given, with
+        its "best_of_score" callable if it brings one: _resolve_options checks both."""
         o = dict(top_k=req.get("top_k", 5), top_p=req.get("top_p", 1), temperature=req.get("temperature", 1),
                  batch_size=req.get("batch_size", 1), batch_threshold=req.get("batch_threshold", 0.75),
                  speed_factor=req.get("speed_factor", 1.0), split_bucket=req.get("split_bucket", True),
@@ -1397,14 +1485,21 @@ class TTS:
             o["fragment_interval"] = 0.01
         if req.get("lora_voice") is not None:
             o["lora_voice"] = req["lora_voice"]
+        n = req.get("best_of")
+        if n is not None and not (type(n) is int and n == 1):
+            o["best_of"] = n
+            if req.get("best_of_score") is not None:
+                o["best_of_score"] = req["best_of_score"]
         return o
 
     def _resolve_options(self, req: dict) -> dict:
         """_request_options(req) under the rules of the loaded model, what run() and run_batch work from: fragments, another
         speed and v3 / v4 parallel runs are never bucketed (reference TTS.py:1048-1062), and AP_BWE super-sampling applies to
         the v3 vocoder output only -- v1 / v2 / v2Pro / v4 ignore the key (TTS.py:1040, 1328, 1349).  A "lora_voice" that was
-        not added raises ValueError here, before any GPU work."""
+        not added raises ValueError here, before any GPU work, and so does a "best_of" that is no int in 1..16 or that comes
+        with parallel_infer=False (check_best_of; the prompt-free case is refused as soon as the voice is known)."""
         o = self._request_options(req)
+        check_best_of(o)
         if "lora_voice" in o:
             self._lora_voice(o["lora_voice"])
         if o["return_fragment"] or o["speed_factor"] != 1.0 or (self.configs.use_vocoder and o["parallel_infer"]):
@@ -1418,7 +1513,8 @@ class TTS:
         -- the key it has in run(r) (the naive / prompt-free loop decodes every sentence alone: row 0).  Sentences are
         grouped by what is per launch (sampling parameters, parallel_infer, prompt-free, the decode budget run() gives them),
         sorted by length inside a group and cut into launches of at most max_batch rows.  Returns the launches: lists of
-        {"r", "bi", "j", "len", "key", "group"}.
+        {"r", "bi", "j", "len", "key", "group"}.  A request with "best_of" = n > 1 gives n entries per sentence, candidate c
+        with "cand" = c and the key (seed, row + 1024 c): candidate 0 is the entry the request has without the key.
         mixed_sampling=True: the sampling parameters are per row (gsv_t2s_set_row_sampling) and no longer separate groups:
         their four slots of the group tuple hold None and every row carries "sampling" = (top_k, top_p, temperature,
         repetition_penalty) of its request."""
@@ -1440,6 +1536,10 @@ class TTS:
                     e = dict(r=r, bi=bi, j=j, len=n + P, group=g, key=(pl["actual_seed"] + bi, 0 if naive else j % mb))
                     if mixed_sampling:
                         e["sampling"] = sampling
+                    if o.get("best_of", 1) > 1:
+                        for c in range(o["best_of"]):
+                            groups.setdefault(g, []).append(dict(e, cand=c, key=(e["key"][0], e["key"][1] + BEST_OF_ROW_STRIDE * c)))
+                        continue
                     groups.setdefault(g, []).append(e)
         launches = []
         for g in groups:
@@ -1599,6 +1699,7 @@ class TTS:
         actual_seed = set_seed(o["seed"])
         segments = self._segments(req)
         no_prompt = voice["phones"] is None
+        check_best_of(o, no_prompt)
         if no_prompt and self.configs.use_vocoder:
             raise NO_PROMPT_ERROR("v3/v4 need the prompt text (phones) of the reference audio")
         prompt_data = None if no_prompt else {"phones": voice["phones"], "bert_features": voice["bert_features"]}
@@ -1629,10 +1730,13 @@ class TTS:
         shared across sampling parameters; a launch whose rows differ hands them over per row).  Reads `data`, `opts`,
         `voice`, `no_prompt`, `P`, `actual_seed`.  Writes run()'s pred_list / idx_list per batch: `preds[bi][j]`, the tokens
         of sentence j (prompt included), `idxs[bi][j]`, how many were generated (0 prompt-free), `kept[bi]` = _kept_tokens.
-        continuous_ar: a group's launches are one decode session instead (plan_sessions)."""
+        continuous_ar: a group's launches are one decode session instead (plan_sessions).
+        A launch that holds candidate rows ("best_of") is decoded with log-probabilities; once every launch is back each such
+        sentence keeps the tokens of the candidate choose_candidate picks, and `candidates[bi][j]` records the choice."""
         for pl in plans:
             pl["preds"] = [[None] * len(item["all_phones"]) for item in pl["data"]]
             pl["idxs"] = [[None] * len(item["all_phones"]) for item in pl["data"]]
+        cands: Dict[tuple, Dict[int, tuple]] = {}       # (r, bi, j) -> candidate -> (its dict, y)
         launches = self.plan_batch(plans, mixed_sampling=True) if mixed_sampling else self.plan_batch(plans)
         work = self.plan_sessions(launches) if continuous_ar else [(False, rows) for rows in launches]
         for session, rows in work:
@@ -1642,6 +1746,9 @@ class TTS:
                 kw["row_sampling"] = [e["sampling"] for e in rows]
             no_prompt = rows[0]["group"][5]
             naive = no_prompt or not o["parallel_infer"]
+            want_lp = any("cand" in e for e in rows)
+            if want_lp:
+                kw["logprobs"] = True
             items = [plans[e["r"]]["data"][e["bi"]] for e in rows]
             x = [it["all_phones"][e["j"]] for it, e in zip(items, rows)]
             bert = [it["all_bert_features"][e["j"]] for it, e in zip(items, rows)]
@@ -1654,9 +1761,19 @@ class TTS:
                 y, idx = self.t2s_model._run(x, prompts, bert, o["top_k"], o["top_p"], early_stop_num(self.configs), o["temperature"],
                                              o["repetition_penalty"], eos_mask_steps=11 if naive else 1,
                                              max_steps=rows[0]["group"][6], rng_keys=[e["key"] for e in rows], **kw)
-            for e, y_, i_ in zip(rows, y, idx):
+            for k, (e, y_, i_) in enumerate(zip(rows, y, idx)):
+                if "cand" in e:
+                    c = dict(tokens=y_[-i_:] if i_ > 0 else y_[:0], logprobs=self.t2s_model.last_logprobs[k].cpu().numpy(), n=i_,
+                             cut=self.t2s_model.last_cut[k])
+                    cands.setdefault((e["r"], e["bi"], e["j"]), {})[e["cand"]] = (c, y_)
+                    continue
                 plans[e["r"]]["preds"][e["bi"]][e["j"]] = y_
                 plans[e["r"]]["idxs"][e["bi"]][e["j"]] = 0 if no_prompt else i_
+        for (r, bi, j), by_c in sorted(cands.items()):
+            pl = plans[r]
+            k, rec = choose_candidate(pl["opts"], [by_c[c][0] for c in sorted(by_c)])
+            pl["preds"][bi][j], pl["idxs"][bi][j] = by_c[k][1], by_c[k][0]["n"]
+            pl.setdefault("candidates", [[None] * len(item["all_phones"]) for item in pl["data"]])[bi][j] = rec
         for pl in plans:
             pl["kept"] = [self._kept_tokens(p, i, pl["no_prompt"]) for p, i in zip(pl["preds"], pl["idxs"])]
         self._wait_stream()
@@ -1820,6 +1937,9 @@ class TTS:
         continuous_ar=True: each group of plan_batch (parallel decode with prompts) is decoded through one decode session
         (plan_sessions, Text2SemanticDecoder.infer_panel_continuous) instead of launches of max_batch rows: a sentence that
         ends early hands its slot to the next one.  Same keys, same sampling values, the same tokens per sentence.
+        A request with "best_of" = n > 1 decodes n candidates per sentence as further rows of the shared launches and keeps
+        one (plan_batch, select_candidate; "best_of_score": a callable in its place); last_candidates[r][bi][j] then lists
+        dict(n, mean_logprob, cut, chosen) per candidate, and is [] for a request without the key.
         No keyword changes anything for the other model family."""
         if self.t2s_model is None or self.vits_model is None:
             raise RuntimeError("init_t2s_weights / init_vits_weights first")
@@ -1834,6 +1954,7 @@ class TTS:
             requests = self._with_shared_voices(requests, shared_sv=shared_sv, device_frontend=device_frontend)
         plans = [self._plan_request(req) for req in requests]
         self._ar_stage(plans, mixed_sampling=mixed_sampling, **({"continuous_ar": True} if continuous_ar else {}))
+        self.last_candidates = [pl.get("candidates", []) for pl in plans]
         sr = self._output_sr()
         if shared_sovits and not self.configs.use_vocoder:
             self._shared_sovits_stage(plans, shared_speed=shared_speed)
@@ -1866,6 +1987,8 @@ class TTS:
                 return
             pc = self.prompt_cache
             prompt_data = None if pc["phones"] is None else {"phones": pc["phones"], "bert_features": pc["bert_features"]}
+            check_best_of(o, prompt_data is None)
+            self.last_candidates = [[]] if "best_of" in o else []
             t1 = time.perf_counter()
             # token ids stay on the host here: the engines pack a whole batch and move it with ONE copy
             # (the reference's per-item .to(device), TTS.py:899-912, is ~75 tiny transfers per batch of 32)
@@ -1886,11 +2009,15 @@ class TTS:
                 if no_prompt and self.configs.use_vocoder:
                     raise NO_PROMPT_ERROR("v3/v4 need the prompt text (phones) of the reference audio")
                 prompt = None if no_prompt else self.prompt_cache["prompt_semantic"].view(1, -1).expand(len(item["all_phones"]), -1)
-                pred_list, idx_list = infer(item["all_phones"], item["all_phones_len"], prompt,
-                                            item["all_bert_features"], top_k=o["top_k"], top_p=o["top_p"],
-                                            temperature=o["temperature"], early_stop_num=early_stop_num(self.configs),
-                                            max_len=item["max_len"], repetition_penalty=o["repetition_penalty"],
-                                            seed=actual_seed + bi)
+                if "best_of" in o:
+                    pred_list, idx_list, rec = self._decode_best_of(item, prompt, o, actual_seed + bi)
+                    self.last_candidates[0].append(rec)
+                else:
+                    pred_list, idx_list = infer(item["all_phones"], item["all_phones_len"], prompt,
+                                                item["all_bert_features"], top_k=o["top_k"], top_p=o["top_p"],
+                                                temperature=o["temperature"], early_stop_num=early_stop_num(self.configs),
+                                                max_len=item["max_len"], repetition_penalty=o["repetition_penalty"],
+                                                seed=actual_seed + bi)
                 self._wait_stream()
                 t4 = time.perf_counter()
                 t_34 += t4 - t3

@@ -99,6 +99,7 @@ _SIGS = {
     "gsv_t2s_debug_kv": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "gsv_t2s_engine_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
     "gsv_t2s_set_debug": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsv_t2s_set_logprobs": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gsv_t2s_debug_stall": (C.c_int, [C.c_void_p, C.c_int]),
     "gsv_t2s_debug_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsv_t2s_time_step": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p]),
@@ -227,6 +228,7 @@ _SIGS = {
                                 C.POINTER(SamplingParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsv_op_sample_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(RowSampling),
                                      C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsv_op_token_logprob": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTS = tuple(_SIGS)   # every symbol include/gsv.h declares

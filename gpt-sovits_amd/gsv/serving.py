@@ -7,7 +7,7 @@
   the live rows a chunk of steps, and sends the requests whose sentences have all come back through the shared waveform stage
   of `run_batch` -- so a short request is delivered when it is finished, and a new one takes a free slot while the others
   decode.  A request that cannot decode in the session (prompt-free, `parallel_infer=False`, a row the K/V arena would cut,
-  `return_fragment` / streaming) is *exclusive*: a FIFO barrier that is served with `run_batch([request])` once nothing is live.
+  `return_fragment` / streaming, `best_of` candidates) is *exclusive*: a FIFO barrier that is served with `run_batch([request])` once nothing is live.
 * `plan_online` is the schedule as a pure function, `plan_continuous` with arrivals: the event trace `Scheduler` records in
   `stats["events"]`.  Both are driven by the same `_Policy`, which holds every decision and touches no GPU.
 * `Server` puts one loop thread around a scheduler: the only thread that makes GPU calls.  `submit` returns a
@@ -393,8 +393,8 @@ class Scheduler:
 
     def _session_rows(self, pl: dict) -> Optional[List[dict]]:
         """the request's rows in (bi, j) order with plan_batch's keys and sampling tuples -- or None: the request is exclusive
-        (prompt-free, the naive loop, or a row that does not fit the K/V arena with the full step budget)"""
-        if pl["no_prompt"] or not pl["opts"]["parallel_infer"]:
+        (prompt-free, the naive loop, "best_of" candidates, or a row that does not fit the K/V arena with the full step budget)"""
+        if pl["no_prompt"] or not pl["opts"]["parallel_infer"] or "best_of" in pl["opts"]:
             return None
         rows = [e for launch in self.tts.plan_batch([pl], mixed_sampling=True) for e in launch]
         if any(e["len"] + 2 + self._budget() > self.tts.t2s_model.max_seq for e in rows):

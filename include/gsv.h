@@ -184,6 +184,16 @@ int gsv_t2s_engine_stats(gsv_t2s_t* h, int* engine_available, int* fallbacks, un
  *     step run, recorded BEFORE forcing -- lets a test replay the engine's sampling (noise indexing, counter RNG, repetition
  *     bookkeeping) step by step with gsv_op_sample / the oracle on the dumped logits. */
 int gsv_t2s_set_debug(gsv_t2s_t* h, const int32_t* force_tokens, float* logits_dump, int32_t* drawn_dump);
+/* Per-token log-probabilities for the NEXT gsv_t2s_decode call only (like gsv_t2s_set_debug; NULL: none, the default).
+ * out_logp [dev] fp32 [B][max_steps], indexed like out_tokens: entry [b][s] = x[t] - max(x[:Veff]) - log(sum_{v < Veff}
+ * exp(x[v] - max)) with x the raw logits of row b at step s (what logits_dump records: temperature 1, no repetition penalty,
+ * no top-k / top-p cut), Veff the step's unmasked vocabulary (EOS masked while s < eos_mask_steps) and t the token the row
+ * takes: the sampled one, or the forced one under force_tokens (a token in the masked EOS column: -inf).  The step that ends
+ * a row has its entry too, at [b][out_len[b]]; entries of steps a row never ran are left as the caller filled them.  Both
+ * decode paths write it, and a persistent launch that falls back and re-runs on the launch path rewrites the same values.
+ * Set before gsv_t2s_session_begin it holds for the session as [slots][max_steps], indexed by slot and the row's own step.
+ * Sampling is not changed by it: the same tokens with and without. */
+int gsv_t2s_set_logprobs(gsv_t2s_t* h, float* out_logp);
 /* test hook: member `member` (0..31) of row group 0 skips ONE hand-off publish in the next persistent launch, which must then
  * end through its bounded waits (never hang), be re-run on the launch-per-phase step and be counted by gsv_t2s_engine_stats */
 int gsv_t2s_debug_stall(gsv_t2s_t* h, int member);
@@ -690,6 +700,10 @@ int gsv_op_sample(const float* logits, int B, int vocab, int vocab_eff, const in
 int gsv_op_sample_rows(const float* logits, int B, int vocab, int vocab_eff, const int32_t* prev, int prev_len,
                        const gsv_row_sampling_t* rows, uint64_t seed, const float* noise, int step, int32_t* sampled,
                        int32_t* argmax_tok, gsv_stream_t stream);
+/* the log-probability of gsv_t2s_set_logprobs alone, one wave per row: logits [dev] fp32 [B][vocab], tokens [dev] int32 [B];
+ * out [dev] fp32 [B] = log softmax(logits[b][:vocab_eff])[tokens[b]], -inf for a token outside [0, vocab_eff) */
+int gsv_op_token_logprob(const float* logits, int B, int vocab, int vocab_eff, const int32_t* tokens, float* out,
+                         gsv_stream_t stream);
 
 #ifdef __cplusplus
 }

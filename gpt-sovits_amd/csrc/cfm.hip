@@ -13,10 +13,11 @@
 #include <cmath>
 #include <cstddef>
 
-#include "engine.h"
+#include "cfm_engine.h"
 
 using namespace gsv;
 using namespace gsveng;
+using namespace gsvcfm;
 
 namespace gsv {
 
@@ -123,11 +124,9 @@ __global__ void cfm_grn_apply_kernel(T* __restrict__ y, const float* __restrict_
 // AdaLN-Zero modulation: y = LN(x) * (1 + scale) + shift, LN without affine, eps 1e-6 (modules.py:275-312).  One wave per
 // row; the row is read ONCE into registers (three dependent passes over global memory cost 10 us per call at T = 934).
 template <typename T, int NPL>   // NPL = elements per lane, C == 64 * NPL
-__global__ __launch_bounds__(256) void cfm_ln_mod_kernel(const T* __restrict__ x, const float* __restrict__ scale,
-                                                         const float* __restrict__ shift, int rows, int C, T* __restrict__ y) {
+__device__ __forceinline__ void cfm_ln_mod_row(const T* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ shift, int row,
+                                               int C, T* __restrict__ y) {
   const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (row >= rows) return;
   const T* xr = x + (long long)row * C + lane * NPL;
   float v[NPL];
   float sum = 0.f;
@@ -144,11 +143,32 @@ __global__ __launch_bounds__(256) void cfm_ln_mod_kernel(const T* __restrict__ x
 #pragma unroll
   for (int i = 0; i < NPL; ++i) yr[i] = (T)((v[i] - mean) * rstd * (1.f + sc[i]) + sh[i]);
 }
+template <typename T, int NPL>
+__global__ __launch_bounds__(256) void cfm_ln_mod_kernel(const T* __restrict__ x, const float* __restrict__ scale,
+                                                         const float* __restrict__ shift, int rows, int C, T* __restrict__ y) {
+  const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  cfm_ln_mod_row<T, NPL>(x, scale, shift, row, C, y);
+}
+// the per-row form (sessions): utterance row b = row / Tn has its own scale / shift vectors, ld floats after row b - 1's
+template <typename T, int NPL>
+__global__ __launch_bounds__(256) void cfm_ln_mod_rows_kernel(const T* __restrict__ x, const float* __restrict__ scale,
+                                                              const float* __restrict__ shift, int rows, int C, T* __restrict__ y, int Tn, int ld) {
+  const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long long o = (long long)(row / Tn) * ld;
+  cfm_ln_mod_row<T, NPL>(x, scale + o, shift + o, row, C, y);
+}
 
+// Tn > 0: the per-row form
 template <typename T>
-int launch_ln_mod(const void* x, const float* scale, const float* shift, int rows, int C, void* y, hipStream_t s) {
+int launch_ln_mod(const void* x, const float* scale, const float* shift, int rows, int C, void* y, hipStream_t s, int Tn = 0, int ld = 0) {
   auto launch = [&](auto npl) -> int {
-    GSV_LAUNCH((cfm_ln_mod_kernel<T, decltype(npl)::value>), dim3(cdiv(rows, 4)), dim3(256), 0, s, (const T*)x, scale, shift, rows, C, (T*)y);
+    if (Tn > 0)
+      GSV_LAUNCH((cfm_ln_mod_rows_kernel<T, decltype(npl)::value>), dim3(cdiv(rows, 4)), dim3(256), 0, s, (const T*)x, scale, shift, rows, C, (T*)y,
+                 Tn, ld);
+    else
+      GSV_LAUNCH((cfm_ln_mod_kernel<T, decltype(npl)::value>), dim3(cdiv(rows, 4)), dim3(256), 0, s, (const T*)x, scale, shift, rows, C, (T*)y);
     return GSV_OK;
   };
   switch (C / 64) {
@@ -194,21 +214,6 @@ __device__ __forceinline__ unsigned long long cfm_mix64(unsigned long long z) {
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
 }
-
-// what differs between the utterances of one call: the prompt mel (channels-first [C][Tp], device) and its length, and the key
-// of the noise draw.  A small device array, one entry per utterance, read by the kernels below.  A guided pass appends one
-// entry per unconditioned twin: prompt null (its cond columns are zeros whatever Tp says), Tp the conditioned row's.
-// slot: the row's LoRA adapter (gsv_cfm_adapter_*), -1 = the base model; a twin takes its request's.
-struct CfmRow {
-  const float* prompt;
-  unsigned long long seed;
-  int Tp, slot;
-};
-
-// the table reaches the device as kernel arguments, up to CFM_ROW_CHUNK entries per launch: the runtime copies arguments at
-// launch, so the host vector may go away at once and the host never waits for the stream
-constexpr int CFM_ROW_CHUNK = 64;
-struct CfmRowChunk { CfmRow r[CFM_ROW_CHUNK]; };
 
 __global__ void cfm_rows_fill_kernel(CfmRowChunk ch, int n, CfmRow* __restrict__ rw) {
   const int b = threadIdx.x;
@@ -309,42 +314,11 @@ __global__ void cfm_out_kernel(const float* __restrict__ x, const CfmRow* __rest
 
 }  // namespace gsv
 
-struct DitBlockW { Conv mod, qkv, out, ff1, ff2; };
-struct TextBlockW { float *dw = nullptr, *db = nullptr, *ng = nullptr, *nb = nullptr, *gg = nullptr, *gb = nullptr; Conv pw1, pw2; };
-
-// one stored LoRA adapter: `dev` is one block in the engine dtype, per DiT block l (rp = rank padded to 16, inner = heads *
-// dim_head, everything in units of rp elements from l * 4 (D + inner)):
-//   q|k|v lora_A stacked [3 rp][D] at 0, q|k|v lora_B [3 inner][rp] at 3 D, out lora_A [rp][inner] at 3 D + 3 inner,
-//   out lora_B [D][rp] at 3 D + 4 inner; alpha / rank is folded into the lora_B matrices.  dev null = free slot.
-struct CfmAdapter { void* dev = nullptr; int rank = 0, rp = 0; };
-
-struct gsv_cfm : gsveng::Ctx {
-  gsv_cfm() : Ctx("cfm") {}
-  gsv_dit_config cfg;
-  int ldin = 0;
-  Conv t0, t2, d0, d2, in_proj, pos1, pos2, final_mod, proj_out;
-  std::vector<TextBlockW> text;
-  std::vector<DitBlockW> blocks;
-  float* pos_table = nullptr;   // fp32 [4096][text_dim]
-  bool materialized_attn = false;   // GSV_CFM_MATERIALIZED_ATTN=1: A/B switch back to the 4-launch scores/softmax/PV path
-  // LoRA adapters: the store by slot, its device image (base pointer and rp per slot, what lora.hip indexes by a row's
-  // slot), and the adapter being staged between adapter_begin and adapter_finalize
-  std::vector<CfmAdapter> adapters;
-  LoraSlot* lora_tab = nullptr;     // device [GSV_CFM_MAX_ADAPTERS], allocated with the first adapter
-  bool a_open = false;
-  int a_rank = 0;
-  float a_alpha = 0.f;
-  std::map<std::string, std::vector<float>> a_staged;
-};
-
-namespace {
-
-// grid of the elementwise kernels: one thread of a 256-thread workgroup per element of n, blockIdx.y = utterance
-inline dim3 cfm_grid(long long n, int B = 1) { return dim3(nblk(n), B); }
+namespace gsvcfm {
 
 // time-independent precomputation for all n steps: mods[l][i][6D] (l < depth) and mods[depth][i][2D]
 template <typename T>
-int cfm_modulations(gsv_cfm* c, hipStream_t s, int N, float** mods_out) {
+int modulations(gsv_cfm* c, hipStream_t s, int N, float** mods_out) {
   const auto& g = c->cfg;
   const int D = g.dim;
   const size_t es = sizeof(T);
@@ -382,71 +356,11 @@ int cfm_modulations(gsv_cfm* c, hipStream_t s, int N, float** mods_out) {
   return GSV_OK;
 }
 
-// B utterances of Tn frames: mu [B][Tn][text_dim] fp32, noise [B][mel][Tn] fp32 or null -> out [B][mel][Tn] fp32; `host_rows`
-// holds every utterance's own prompt ([mel][Tp_b] fp32, device), prompt length and noise key.  All row-wise work (Linear
-// layers, AdaLN, rotary, Euler) runs over the B * Tn rows at once, which is what fills the chip and reads the 370 MB of
-// weights once per step instead of once per chunk.  The ops that look along time (depthwise convs, GRN, fused attention)
-// take the utterance as a grid dimension: one launch for all of them.  Only the two grouped position convs and the
-// materialised attention (the parity path) are issued per utterance.
-//
-// Classifier-free guidance (cfg_rate > CFM_CFG_THRESHOLD, models.py:1063-1081): the DiT runs over 2 B rows.  Rows [0, B) are
-// the requests as above; row B + b is request b's unconditioned twin -- the same x columns, zero cond columns, and the null
-// text embedding (the text stack run on ONE extra row of zero text, then copied into every twin: it depends on Tn alone).
-// The Euler state, the noise draw and the output stay B rows; cfm_euler_kernel<T, true> combines the two estimates.  Unguided,
-// DB == B and every launch below is the one it was.
-//
-// LoRA adapters (max_rp > 0: some row carries a slot, max_rp the largest padded rank among them): two more launches per
-// block, the low-rank delta on qkv right after the q/k/v GEMM (before rotary / V^T / attention read it) and on hb right after
-// the out-projection GEMM, under the same gate.  Workgroups of rows without a slot return at once.  max_rp == 0: no such
-// launch, the pass is the one it was.
-constexpr float CFM_CFG_THRESHOLD = 1e-5f;
-
+// the text embedding stack (TextEmbedding.forward, dit.py:50-72): position table, then the ConvNeXt-V2 blocks
 template <typename T>
-int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* mu, const std::vector<CfmRow>& host_rows, int Tn, int N,
-                    const float* noise, float temperature, float cfg_rate, int max_rp, float* out) {
-  const auto& g = c->cfg;
-  const int D = g.dim, td = g.text_dim, md = g.mel_dim, inner = g.heads * g.dim_head, FF = D * g.ff_mult, ldin = c->ldin;
-  const int half = g.dim_head / 2;
-  const size_t es = sizeof(T);
-  const bool guided = cfg_rate > CFM_CFG_THRESHOLD;
-  const int B = (int)host_rows.size();        // requests: rows of x, noise and out
-  const int DB = guided ? 2 * B : B;          // rows the DiT sees
-  const int TB = guided ? B + 1 : B;          // rows of the text stack: the requests, then the null text row
-  const int RX = B * Tn, R = DB * Tn, RT = TB * Tn;
-  std::vector<CfmRow> with_twins;             // guided only: the requests' entries, then one per twin
-  if (guided) {
-    with_twins = host_rows;
-    for (int b = 0; b < B; ++b) with_twins.push_back(CfmRow{nullptr, 0ull, host_rows[b].Tp, host_rows[b].slot});
-  }
-  const std::vector<CfmRow>& table = guided ? with_twins : host_rows;
-  CfmRow* rw;
-  GSV_RC(need(c, "cfm_rows", (size_t)DB * sizeof(CfmRow), (void**)&rw));
-  for (int b0 = 0; b0 < DB; b0 += CFM_ROW_CHUNK) {
-    const int n = std::min(CFM_ROW_CHUNK, DB - b0);
-    CfmRowChunk ch{};
-    std::copy_n(table.begin() + b0, n, ch.r);
-    GSV_LAUNCH(cfm_rows_fill_kernel, dim3(1), dim3(CFM_ROW_CHUNK), 0, s, ch, n, rw + b0);
-  }
-  float *x, *v, *cs, *gx;
-  void *xin, *ta, *tb, *tw, *hb, *c1, *nrm, *qkv, *ao, *ff;
-  GSV_RC(need(c, "cfm_x", (size_t)RX * md * 4, (void**)&x));
-  GSV_RC(need(c, "cfm_v", (size_t)R * md * 4, (void**)&v));
-  GSV_RC(need(c, "cfm_cs", (size_t)Tn * half * 2 * 4, (void**)&cs));
-  GSV_RC(need(c, "cfm_gx", (size_t)TB * 2 * td * 4, (void**)&gx));
-  GSV_RC(need(c, "cfm_xin", (size_t)R * ldin * es, &xin));
-  GSV_RC(need(c, "cfm_ta", (size_t)R * td * es, &ta));
-  GSV_RC(need(c, "cfm_tb", (size_t)R * td * es, &tb));
-  GSV_RC(need(c, "cfm_tw", (size_t)R * 2 * td * es, &tw));
-  GSV_RC(need(c, "cfm_h", (size_t)R * D * es, &hb));
-  GSV_RC(need(c, "cfm_c1", (size_t)R * D * es, &c1));
-  GSV_RC(need(c, "cfm_nrm", (size_t)R * D * es, &nrm));
-  GSV_RC(need(c, "cfm_qkv", (size_t)R * 3 * inner * es, &qkv));
-  GSV_RC(need(c, "cfm_ao", (size_t)R * inner * es, &ao));
-  GSV_RC(need(c, "cfm_ff", (size_t)R * FF * es, &ff));
-  auto rows = [&](void* p, int b, int width) { return (void*)((char*)p + (size_t)b * Tn * width * es); };
-
-  // ---- per-utterance constants: text embedding (dit.py:50-72), cond columns, rotary table
-  GSV_LAUNCH(cfm_text_pos_kernel<T>, cfm_grid((long long)Tn * td, TB), dim3(256), 0, s, mu, B, c->pos_table, Tn, td, (T*)ta);
+int text_stack(gsv_cfm* c, hipStream_t s, const float* mu, int mu_rows, int TB, int Tn, void* ta, void* tb, void* tw, float* gx) {
+  const int td = c->cfg.text_dim, RT = TB * Tn;
+  GSV_LAUNCH(cfm_text_pos_kernel<T>, cfm_grid((long long)Tn * td, TB), dim3(256), 0, s, mu, mu_rows, c->pos_table, Tn, td, (T*)ta);
   for (auto& blk : c->text) {
     GSV_LAUNCH(cfm_dwconv7_kernel<T>, cfm_grid((long long)Tn * td, TB), dim3(256), 0, s, (const T*)ta, blk.dw, blk.db, Tn, td, (T*)tb);
     GSV_RC(launch_layernorm(c->dtype, tb, 0, nullptr, 0, blk.ng, blk.nb, tb, 0, RT, td, 1e-6f, s));
@@ -459,6 +373,176 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
     ConvOpt orr; orr.res = ta;
     GSV_RC(conv(c, s, blk.pw2, tw, 2 * td, RT, ta, RT, orr));
   }
+  return GSV_OK;
+}
+
+// One DiT forward over DB packed rows of Tn frames.  LoRA adapters (max_rp > 0: some row carries a slot, max_rp the largest
+// padded rank among them): two more launches per block, the low-rank delta on qkv right after the q/k/v GEMM (before rotary /
+// V^T / attention read it) and on hb right after the out-projection GEMM, under the same gate.  Workgroups of rows without a
+// slot return at once.  max_rp == 0: no such launch.  mods.rows: every launch that reads a modulation vector takes its per-row
+// form (cfm_ln_mod_rows_kernel, the GROWS GEMM epilogues, the *_rows LoRA kernels); 0: the launches are the ones they were.
+template <typename T>
+int dit_forward(gsv_cfm* c, hipStream_t s, const void* xin, int DB, int Tn, const DitMods& mods, const int* row_slot, int slot_ld, int max_rp,
+                const float* cs, float* v) {
+  const auto& g = c->cfg;
+  const int D = g.dim, inner = g.heads * g.dim_head, FF = D * g.ff_mult, ldin = c->ldin;
+  const int half = g.dim_head / 2;
+  const size_t es = sizeof(T);
+  const int R = DB * Tn;
+  void *hb, *c1, *nrm, *qkv, *ao, *ff;
+  GSV_RC(need(c, "cfm_h", (size_t)R * D * es, &hb));
+  GSV_RC(need(c, "cfm_c1", (size_t)R * D * es, &c1));
+  GSV_RC(need(c, "cfm_nrm", (size_t)R * D * es, &nrm));
+  GSV_RC(need(c, "cfm_qkv", (size_t)R * 3 * inner * es, &qkv));
+  GSV_RC(need(c, "cfm_ao", (size_t)R * inner * es, &ao));
+  GSV_RC(need(c, "cfm_ff", (size_t)R * FF * es, &ff));
+  auto rows = [&](void* p, int b, int width) { return (void*)((char*)p + (size_t)b * Tn * width * es); };
+  const float att_scale = 1.f / sqrtf((float)g.dim_head);
+  const bool flash = c->dtype == GSV_F16 && g.dim_head == 64 && !c->materialized_attn;
+  // Infinity-Cache partition: the block weights (16.8 MB per block at the v3 shape, 370 MB in all) are re-read every Euler
+  // step and do not fit the 256 MB cache, so a plain cyclic sweep keeps evicting what the next step needs first.  The
+  // first `resident` blocks are loaded with the default policy (they stay), the rest non-temporal (they stream past).
+  const size_t per_block = ((size_t)D * 3 * inner + (size_t)inner * D + 2 * (size_t)D * FF) * es;
+  static const int resident_mb = getenv("GSV_CFM_RESIDENT_MB") ? atoi(getenv("GSV_CFM_RESIDENT_MB")) : 150;   // scan: 1000 -> 3.03, 200 -> 2.95, 150 -> 2.94, 60 -> 2.97, 0 -> 2.99 ms per step
+  const int resident = per_block ? (int)std::min<size_t>((size_t)g.depth, (size_t)resident_mb * 1024 * 1024 / per_block) : g.depth;
+  void* vtb = nullptr;
+  const long long vtz = (long long)g.heads * 64 * ((Tn + 31) / 32 * 32);   // one V^T buffer per utterance
+  if (flash) GSV_RC(need(c, "cfm_vt", (size_t)DB * vtz * 2, &vtb));
+  const long long lora_blk = 4ll * (D + inner);   // an adapter's elements per DiT block, in units of rp (CfmAdapter)
+  const int pr = mods.rows ? Tn : 0;              // per-row modulations: frames per vector, 0 = one vector for all rows
+  // ---- InputEmbedding (dit.py:75-84): proj(cat(x, cond, text)) then + ConvPositionEmbedding
+  ConvOpt o;
+  GSV_RC(conv(c, s, c->in_proj, xin, ldin, R, hb, R, o));
+  for (int b = 0; b < DB; ++b) {
+    ConvArgs a;
+    const int cg = D / 16;
+    a.x = rows(hb, b, D); a.w = c->pos1.w; a.bias = c->pos1.b; a.y = rows(c1, b, D);
+    a.T_in = Tn; a.T_out = Tn; a.T_virt = Tn; a.Cin = cg; a.Cout = cg; a.taps = 31; a.pad = 15;
+    a.ldx = D; a.ldw = 31 * cg; a.ldy = D; a.ldr = D; a.post_act = ACT_MISH;
+    a.Z = 16; a.xz = cg; a.wz = (long long)cg * 31 * cg; a.yz = cg; a.bz = cg;
+    GSV_RC(launch_conv_gemm(c->dtype, a, s));
+    a.x = rows(c1, b, D); a.w = c->pos2.w; a.bias = c->pos2.b; a.y = rows(hb, b, D); a.accumulate = 1;   // h += mish(conv2(.))
+    GSV_RC(launch_conv_gemm(c->dtype, a, s));
+  }
+  // ---- DiT blocks (modules.py:550-594)
+  for (int l = 0; l < g.depth; ++l) {
+    const DitBlockW& blk = c->blocks[l];
+    const float* m = mods.blk + (size_t)l * mods.blk_stride;   // shift_a, scale_a, gate_a, shift_m, scale_m, gate_m
+    GSV_RC(launch_ln_mod<T>(hb, m + D, m, R, D, nrm, s, pr, 6 * D));
+    const int wnt = l >= resident ? 1 : 0;
+    ConvOpt oq; oq.w_nt = wnt;   // rotary + V^T as this GEMM's epilogue was tried: no gain over the V^T launch
+    GSV_RC(conv(c, s, blk.qkv, nrm, D, R, qkv, R, oq));
+    if (max_rp)
+      GSV_RC(launch_lora_delta(c->dtype, nrm, qkv, Tn, DB, D, 3 * inner, 3, row_slot, slot_ld, c->lora_tab, max_rp, l * lora_blk,
+                               l * lora_blk + 3 * D, nullptr, s));
+    if (flash) {   // every utterance in the same two launches (V^T + rotary, attention): the row is a grid dimension
+      const _Float16* qb = (const _Float16*)qkv;
+      GSV_RC(launch_flash_attn64_f16_rows(qb, 3 * inner, qb + inner, 3 * inner, qb + 2 * inner, 3 * inner, vtb, Tn, g.heads, att_scale,
+                                          ao, inner, s, cs, half, DB, (long long)Tn * 3 * inner, vtz, (long long)Tn * inner));
+    } else {
+      GSV_LAUNCH(cfm_rope_kernel<T>, cfm_grid(R * half * 2), dim3(256), 0, s, (T*)qkv, 3 * inner, inner, R, Tn, half, cs);
+      for (int b = 0; b < DB; ++b) {
+        const T* qb = (const T*)rows(qkv, b, 3 * inner);
+        GSV_RC(attention(c, s, qb, 3 * inner, 0, qb, 3 * inner, inner, 2 * inner, Tn, Tn, g.heads, g.dim_head, att_scale, nullptr,
+                         nullptr, rows(ao, b, inner), inner));
+      }
+    }
+    ConvOpt og; og.gate = m + 2 * D; og.res = hb; og.w_nt = wnt; og.gate_rows = pr; og.gate_ld = pr ? 6 * D : 0;
+    GSV_RC(conv(c, s, blk.out, ao, inner, R, hb, R, og));
+    if (max_rp)
+      GSV_RC(launch_lora_delta(c->dtype, ao, hb, Tn, DB, inner, D, 1, row_slot, slot_ld, c->lora_tab, max_rp,
+                               l * lora_blk + 3 * D + 3 * inner, l * lora_blk + 3 * D + 4 * inner, m + 2 * D, s, pr ? 6 * D : 0));
+    GSV_RC(launch_ln_mod<T>(hb, m + 4 * D, m + 3 * D, R, D, nrm, s, pr, 6 * D));
+    ConvOpt of; of.post_act = ACT_GELU_TANH; of.w_nt = wnt;
+    GSV_RC(conv(c, s, blk.ff1, nrm, D, R, ff, R, of));
+    ConvOpt o2; o2.gate = m + 5 * D; o2.res = hb; o2.w_nt = wnt; o2.gate_rows = pr; o2.gate_ld = pr ? 6 * D : 0;
+    GSV_RC(conv(c, s, blk.ff2, ff, FF, R, hb, R, o2));
+  }
+  // ---- AdaLayerNormZero_Final (scale, shift) + proj_out (models.py:1080)
+  GSV_RC(launch_ln_mod<T>(hb, mods.fin, mods.fin + D, R, D, nrm, s, pr, 2 * D));
+  ConvOpt ov; ov.out_f32 = 1;
+  GSV_RC(conv(c, s, c->proj_out, nrm, D, R, v, R, ov));
+  return GSV_OK;
+}
+
+template int modulations<_Float16>(gsv_cfm*, hipStream_t, int, float**);
+template int modulations<float>(gsv_cfm*, hipStream_t, int, float**);
+template int text_stack<_Float16>(gsv_cfm*, hipStream_t, const float*, int, int, int, void*, void*, void*, float*);
+template int text_stack<float>(gsv_cfm*, hipStream_t, const float*, int, int, int, void*, void*, void*, float*);
+template int dit_forward<_Float16>(gsv_cfm*, hipStream_t, const void*, int, int, const DitMods&, const int*, int, int, const float*, float*);
+template int dit_forward<float>(gsv_cfm*, hipStream_t, const void*, int, int, const DitMods&, const int*, int, int, const float*, float*);
+
+int rows_upload(hipStream_t s, const CfmRow* host, int n, CfmRow* dev) {
+  for (int b0 = 0; b0 < n; b0 += CFM_ROW_CHUNK) {
+    const int m = std::min(CFM_ROW_CHUNK, n - b0);
+    CfmRowChunk ch{};
+    std::copy_n(host + b0, m, ch.r);
+    GSV_LAUNCH(cfm_rows_fill_kernel, dim3(1), dim3(CFM_ROW_CHUNK), 0, s, ch, m, dev + b0);
+  }
+  return GSV_OK;
+}
+
+int rope_table(hipStream_t s, int Tn, int half, float* cs) {
+  GSV_LAUNCH(cfm_rope_table_kernel, cfm_grid(Tn * half), dim3(256), 0, s, Tn, half, cs);
+  return GSV_OK;
+}
+
+int init_x(hipStream_t s, const float* noise, const CfmRow* rw, float temperature, int Tn, int C, int B, float* x) {
+  GSV_LAUNCH(cfm_init_x_kernel, cfm_grid((long long)Tn * C, B), dim3(256), 0, s, noise, rw, temperature, Tn, C, x);
+  return GSV_OK;
+}
+
+}  // namespace gsvcfm
+
+namespace {
+
+// B utterances of Tn frames: mu [B][Tn][text_dim] fp32, noise [B][mel][Tn] fp32 or null -> out [B][mel][Tn] fp32; `host_rows`
+// holds every utterance's own prompt ([mel][Tp_b] fp32, device), prompt length and noise key.  All row-wise work (Linear
+// layers, AdaLN, rotary, Euler) runs over the B * Tn rows at once, which is what fills the chip and reads the 370 MB of
+// weights once per step instead of once per chunk.  The ops that look along time (depthwise convs, GRN, fused attention)
+// take the utterance as a grid dimension: one launch for all of them.  Only the two grouped position convs and the
+// materialised attention (the parity path) are issued per utterance.
+//
+// Classifier-free guidance (cfg_rate > CFM_CFG_THRESHOLD, models.py:1063-1081): the DiT runs over 2 B rows.  Rows [0, B) are
+// the requests as above; row B + b is request b's unconditioned twin -- the same x columns, zero cond columns, and the null
+// text embedding (the text stack run on ONE extra row of zero text, then copied into every twin: it depends on Tn alone).
+// The Euler state, the noise draw and the output stay B rows; cfm_euler_kernel<T, true> combines the two estimates.  Unguided,
+// DB == B and every launch below is the one it was.
+template <typename T>
+int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* mu, const std::vector<CfmRow>& host_rows, int Tn, int N,
+                    const float* noise, float temperature, float cfg_rate, int max_rp, float* out) {
+  const auto& g = c->cfg;
+  const int D = g.dim, td = g.text_dim, md = g.mel_dim, ldin = c->ldin;
+  const int half = g.dim_head / 2;
+  const size_t es = sizeof(T);
+  const bool guided = cfg_rate > CFM_CFG_THRESHOLD;
+  const int B = (int)host_rows.size();        // requests: rows of x, noise and out
+  const int DB = guided ? 2 * B : B;          // rows the DiT sees
+  const int TB = guided ? B + 1 : B;          // rows of the text stack: the requests, then the null text row
+  const int RX = B * Tn, R = DB * Tn;
+  std::vector<CfmRow> with_twins;             // guided only: the requests' entries, then one per twin
+  if (guided) {
+    with_twins = host_rows;
+    for (int b = 0; b < B; ++b) with_twins.push_back(CfmRow{nullptr, 0ull, host_rows[b].Tp, host_rows[b].slot});
+  }
+  const std::vector<CfmRow>& table = guided ? with_twins : host_rows;
+  CfmRow* rw;
+  GSV_RC(need(c, "cfm_rows", (size_t)DB * sizeof(CfmRow), (void**)&rw));
+  GSV_RC(rows_upload(s, table.data(), DB, rw));
+  float *x, *v, *cs, *gx;
+  void *xin, *ta, *tb, *tw;
+  GSV_RC(need(c, "cfm_x", (size_t)RX * md * 4, (void**)&x));
+  GSV_RC(need(c, "cfm_v", (size_t)R * md * 4, (void**)&v));
+  GSV_RC(need(c, "cfm_cs", (size_t)Tn * half * 2 * 4, (void**)&cs));
+  GSV_RC(need(c, "cfm_gx", (size_t)TB * 2 * td * 4, (void**)&gx));
+  GSV_RC(need(c, "cfm_xin", (size_t)R * ldin * es, &xin));
+  GSV_RC(need(c, "cfm_ta", (size_t)R * td * es, &ta));
+  GSV_RC(need(c, "cfm_tb", (size_t)R * td * es, &tb));
+  GSV_RC(need(c, "cfm_tw", (size_t)R * 2 * td * es, &tw));
+  auto rows = [&](void* p, int b, int width) { return (void*)((char*)p + (size_t)b * Tn * width * es); };
+
+  // ---- per-utterance constants: text embedding (dit.py:50-72), cond columns, rotary table
+  GSV_RC(text_stack<T>(c, s, mu, B, TB, Tn, ta, tb, tw, gx));
   {
     const int W = md + (ldin - (2 * md + td));
     GSV_LAUNCH(cfm_cond_kernel<T>, cfm_grid((long long)Tn * W, DB), dim3(256), 0, s, rw, Tn, md, (T*)xin, ldin, md, 2 * md + td);
@@ -467,8 +551,8 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
       GSV_LAUNCH(cfm_bcast_cols_kernel<T>, cfm_grid((long long)Tn * td, B), dim3(256), 0, s, (const T*)rows(ta, B, td), Tn, td,
                  (T*)rows(xin, B, ldin), ldin, 2 * md);
   }
-  GSV_LAUNCH(cfm_rope_table_kernel, cfm_grid(Tn * half), dim3(256), 0, s, Tn, half, cs);
-  GSV_LAUNCH(cfm_init_x_kernel, cfm_grid((long long)Tn * md, B), dim3(256), 0, s, noise, rw, temperature, Tn, md, x);
+  GSV_RC(rope_table(s, Tn, half, cs));
+  GSV_RC(init_x(s, noise, rw, temperature, Tn, md, B, x));
   // x -> the x columns of the DiT input (v null: no update yet), and after every step the Euler update
   auto euler = [&](const float* vv, float dd) -> int {
     auto launch = [&](auto G) -> int {
@@ -481,75 +565,14 @@ int cfm_infer_batch(gsv_cfm* c, hipStream_t s, const float* mods, const float* m
   GSV_RC(euler(nullptr, 0.f));
 
   const float d = (float)(1.0 / N);
-  const float att_scale = 1.f / sqrtf((float)g.dim_head);
-  const bool flash = c->dtype == GSV_F16 && g.dim_head == 64 && !c->materialized_attn;
-  // Infinity-Cache partition: the block weights (16.8 MB per block at the v3 shape, 370 MB in all) are re-read every Euler
-  // step and do not fit the 256 MB cache, so a plain cyclic sweep keeps evicting what the next step needs first.  The
-  // first `resident` blocks are loaded with the default policy (they stay), the rest non-temporal (they stream past).
-  const size_t per_block = ((size_t)D * 3 * inner + (size_t)inner * D + 2 * (size_t)D * FF) * es;
-  static const int resident_mb = getenv("GSV_CFM_RESIDENT_MB") ? atoi(getenv("GSV_CFM_RESIDENT_MB")) : 150;   // scan: 1000 -> 3.03, 200 -> 2.95, 150 -> 2.94, 60 -> 2.97, 0 -> 2.99 ms per step
-  const int resident = per_block ? (int)std::min<size_t>((size_t)g.depth, (size_t)resident_mb * 1024 * 1024 / per_block) : g.depth;
-  void* vtb = nullptr;
-  const long long vtz = (long long)g.heads * 64 * ((Tn + 31) / 32 * 32);   // one V^T buffer per utterance
-  if (flash) GSV_RC(need(c, "cfm_vt", (size_t)DB * vtz * 2, &vtb));
   const int* row_slot = (const int*)((const char*)rw + offsetof(CfmRow, slot));   // device: row b's slot, every slot_ld ints
   const int slot_ld = (int)(sizeof(CfmRow) / sizeof(int));
-  const long long lora_blk = 4ll * (D + inner);   // an adapter's elements per DiT block, in units of rp (CfmAdapter)
   for (int step = 0; step < N; ++step) {
-    // ---- InputEmbedding (dit.py:75-84): proj(cat(x, cond, text)) then + ConvPositionEmbedding
-    ConvOpt o;
-    GSV_RC(conv(c, s, c->in_proj, xin, ldin, R, hb, R, o));
-    for (int b = 0; b < DB; ++b) {
-      ConvArgs a;
-      const int cg = D / 16;
-      a.x = rows(hb, b, D); a.w = c->pos1.w; a.bias = c->pos1.b; a.y = rows(c1, b, D);
-      a.T_in = Tn; a.T_out = Tn; a.T_virt = Tn; a.Cin = cg; a.Cout = cg; a.taps = 31; a.pad = 15;
-      a.ldx = D; a.ldw = 31 * cg; a.ldy = D; a.ldr = D; a.post_act = ACT_MISH;
-      a.Z = 16; a.xz = cg; a.wz = (long long)cg * 31 * cg; a.yz = cg; a.bz = cg;
-      GSV_RC(launch_conv_gemm(c->dtype, a, s));
-      a.x = rows(c1, b, D); a.w = c->pos2.w; a.bias = c->pos2.b; a.y = rows(hb, b, D); a.accumulate = 1;   // h += mish(conv2(.))
-      GSV_RC(launch_conv_gemm(c->dtype, a, s));
-    }
-    // ---- DiT blocks (modules.py:550-594)
-    for (int l = 0; l < g.depth; ++l) {
-      const DitBlockW& blk = c->blocks[l];
-      const float* m = mods + ((size_t)l * N + step) * 6 * D;   // shift_a, scale_a, gate_a, shift_m, scale_m, gate_m
-      GSV_RC(launch_ln_mod<T>(hb, m + D, m, R, D, nrm, s));
-      const int wnt = l >= resident ? 1 : 0;
-      ConvOpt oq; oq.w_nt = wnt;   // rotary + V^T as this GEMM's epilogue was tried: no gain over the V^T launch
-      GSV_RC(conv(c, s, blk.qkv, nrm, D, R, qkv, R, oq));
-      if (max_rp)
-        GSV_RC(launch_lora_delta(c->dtype, nrm, qkv, Tn, DB, D, 3 * inner, 3, row_slot, slot_ld, c->lora_tab, max_rp, l * lora_blk,
-                                 l * lora_blk + 3 * D, nullptr, s));
-      if (flash) {   // every utterance in the same two launches (V^T + rotary, attention): the row is a grid dimension
-        const _Float16* qb = (const _Float16*)qkv;
-        GSV_RC(launch_flash_attn64_f16_rows(qb, 3 * inner, qb + inner, 3 * inner, qb + 2 * inner, 3 * inner, vtb, Tn, g.heads, att_scale,
-                                            ao, inner, s, cs, half, DB, (long long)Tn * 3 * inner, vtz, (long long)Tn * inner));
-      } else {
-        GSV_LAUNCH(cfm_rope_kernel<T>, cfm_grid(R * half * 2), dim3(256), 0, s, (T*)qkv, 3 * inner, inner, R, Tn, half, cs);
-        for (int b = 0; b < DB; ++b) {
-          const T* qb = (const T*)rows(qkv, b, 3 * inner);
-          GSV_RC(attention(c, s, qb, 3 * inner, 0, qb, 3 * inner, inner, 2 * inner, Tn, Tn, g.heads, g.dim_head, att_scale, nullptr,
-                           nullptr, rows(ao, b, inner), inner));
-        }
-      }
-      ConvOpt og; og.gate = m + 2 * D; og.res = hb; og.w_nt = wnt;
-      GSV_RC(conv(c, s, blk.out, ao, inner, R, hb, R, og));
-      if (max_rp)
-        GSV_RC(launch_lora_delta(c->dtype, ao, hb, Tn, DB, inner, D, 1, row_slot, slot_ld, c->lora_tab, max_rp,
-                                 l * lora_blk + 3 * D + 3 * inner, l * lora_blk + 3 * D + 4 * inner, m + 2 * D, s));
-      GSV_RC(launch_ln_mod<T>(hb, m + 4 * D, m + 3 * D, R, D, nrm, s));
-      ConvOpt of; of.post_act = ACT_GELU_TANH; of.w_nt = wnt;
-      GSV_RC(conv(c, s, blk.ff1, nrm, D, R, ff, R, of));
-      ConvOpt o2; o2.gate = m + 5 * D; o2.res = hb; o2.w_nt = wnt;
-      GSV_RC(conv(c, s, blk.ff2, ff, FF, R, hb, R, o2));
-    }
-    // ---- AdaLayerNormZero_Final (scale, shift) + proj_out, then the Euler step (models.py:1080-1084)
-    const float* mf = mods + (size_t)g.depth * N * 6 * D + (size_t)step * 2 * D;
-    GSV_RC(launch_ln_mod<T>(hb, mf, mf + D, R, D, nrm, s));
-    ConvOpt ov; ov.out_f32 = 1;
-    GSV_RC(conv(c, s, c->proj_out, nrm, D, R, v, R, ov));
-    GSV_RC(euler(v, d));
+    DitMods m;   // this step's vectors: block l's at mods[l][step], the final layer's at mods[depth][step]
+    m.blk = mods + (size_t)step * 6 * D; m.blk_stride = (size_t)N * 6 * D;
+    m.fin = mods + (size_t)g.depth * N * 6 * D + (size_t)step * 2 * D;
+    GSV_RC(dit_forward<T>(c, s, xin, DB, Tn, m, row_slot, slot_ld, max_rp, cs, v));
+    GSV_RC(euler(v, d));   // models.py:1082-1084
   }
   GSV_LAUNCH(cfm_out_kernel, cfm_grid((long long)Tn * md, B), dim3(256), 0, s, x, rw, Tn, md, out);
   return GSV_OK;
@@ -559,7 +582,7 @@ template <typename T>
 int cfm_run(gsv_cfm* c, hipStream_t s, const float* mu, const std::vector<CfmRow>& rows, int Tn, int N, const float* noise,
             float temperature, float cfg_rate, int max_rp, float* out) {
   float* mods = nullptr;
-  GSV_RC(cfm_modulations<T>(c, s, N, &mods));
+  GSV_RC(modulations<T>(c, s, N, &mods));
   return cfm_infer_batch<T>(c, s, mods, mu, rows, Tn, N, noise, temperature, cfg_rate, max_rp, out);
 }
 
@@ -570,6 +593,7 @@ int cfm_entry(gsv_cfm* c, const char* who, const float* mu, const float* const* 
               int Tn, int n_steps, const float* noise, const uint64_t* seeds, float temperature, float cfg_rate, float* out,
               gsv_stream_t stream) {
   GSV_REQUIRE(c && c->finalized, "%s: handle not finalized", who);
+  GSV_REQUIRE(!session_open(c), "%s: a flow-matching session is open on this handle and owns its workspace (gsv_cfm_session_end first)", who);
   GSV_REQUIRE(mu && out && Tp && B > 0 && Tn > 0 && n_steps > 0 && n_steps <= 1024, "%s: bad argument", who);
   const bool guided = cfg_rate > CFM_CFG_THRESHOLD;           // the DiT then sees every row and its unconditioned twin
   GSV_REQUIRE(B <= 65535 / (guided ? 2 : 1), "%s: %d rows%s exceed the grid's 65535", who, B, guided ? " and their unconditioned twins" : "");
@@ -617,6 +641,7 @@ void gsv_cfm_destroy(gsv_cfm_t* c) {
   if (!c) return;
   for (auto& a : c->adapters) if (a.dev) (void)hipFree(a.dev);
   if (c->lora_tab) (void)hipFree(c->lora_tab);
+  session_destroy(c);
   free_ctx(c);
   delete c;
 }
@@ -809,6 +834,7 @@ int gsv_cfm_adapter_finalize(gsv_cfm_t* c, int* slot_out) {
 int gsv_cfm_adapter_remove(gsv_cfm_t* c, int slot) {
   GSV_REQUIRE(c, "cfm_adapter_remove: null handle");
   GSV_REQUIRE(slot >= 0 && slot < (int)c->adapters.size() && c->adapters[slot].dev, "cfm_adapter_remove: no adapter in slot %d", slot);
+  GSV_REQUIRE(!session_uses_adapter(c, slot), "cfm_adapter_remove: a live row of the open session runs with slot %d (fetch or release it first)", slot);
   GSV_HIP(hipDeviceSynchronize());   // nothing may still read the block
   (void)hipFree(c->adapters[slot].dev);
   c->adapters[slot] = CfmAdapter{};

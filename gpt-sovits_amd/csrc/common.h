@@ -185,13 +185,18 @@ struct ConvArgs {
   // same route as an unmasked one, and the conv kernels never read it: their code and registers are the unmasked ones.
   // Null = unmasked.  (One 8-byte field: three of them regrouped the kernel arguments and cost gemm_lds a 64-byte spill.)
   const int* row_seg = nullptr;
+  // per-row gates (flow-matching sessions, cfm_session.hip): gate_rows > 0 = output row t is gated by the vector
+  // gate + (t / gate_rows) * gate_ld instead of the one vector at gate (gate_rows = frames per utterance: the lookup is per
+  // output row, a tile may span several utterances).  Z == 1, no transposed-conv scatter.  Only the *_GROWS instantiations of
+  // gemm_sk / gemm_t64 / gemm_lds / conv_gemm read the two fields; 0 = one vector, the kernels and routes of before.
+  int gate_rows = 0, gate_ld = 0;
 };
 // Route record (gsv_debug_last_conv_route): every launch site of launch_conv_gemm / launch_conv_pair stores which kernel
 // instantiation it launched, as one 64-bit code of byte fields (include/gsv.h has the layout).  A plain store on the host:
 // no formatting, allocation or synchronisation on the launch path.
 enum { ROUTE_GEMM_SK = 1, ROUTE_GEMM_T64 = 2, ROUTE_CONV_WIDE = 3, ROUTE_GEMM_LDS = 4, ROUTE_CONV_LDS = 5, ROUTE_CONV_NARROW = 6,
        ROUTE_CONV_GEMM = 7, ROUTE_CONV_PAIR = 8, ROUTE_GEMM_PANEL = 9 };
-enum { ROUTE_RES = 1, ROUTE_ACCU = 2, ROUTE_ALLW = 4, ROUTE_WNT = 8, ROUTE_SEG = 16 };
+enum { ROUTE_RES = 1, ROUTE_ACCU = 2, ROUTE_ALLW = 4, ROUTE_WNT = 8, ROUTE_SEG = 16, ROUTE_GROWS = 32 };
 constexpr unsigned long long route_code(int family, int dtype, int p0 = 0, int p1 = 0, int p2 = 0, int p3 = 0, int p4 = 0, int flags = 0) {
   return (unsigned long long)(family & 255) | (unsigned long long)(dtype & 255) << 8 | (unsigned long long)(p0 & 255) << 16 |
          (unsigned long long)(p1 & 255) << 24 | (unsigned long long)(p2 & 255) << 32 | (unsigned long long)(p3 & 255) << 40 |
@@ -272,7 +277,8 @@ int launch_flash_rel96_f16(const void* q, int ldq, const void* k, int ldk, const
 // the largest rp among the slots of this launch (it sizes the LDS tile).
 struct LoraSlot { const void* base; int rp, pad_; };
 int launch_lora_delta(int dtype, const void* x, void* y, int Tn, int DB, int K, int N, int n_proj, const int* slot, int slot_stride,
-                      const LoraSlot* tab, int max_rp, long long coef_a, long long coef_b, const float* gate, hipStream_t s);
+                      const LoraSlot* tab, int max_rp, long long coef_a, long long coef_b, const float* gate, hipStream_t s,
+                      int gate_ld = 0);   // gate_ld > 0: row b's gate vector is gate + b * gate_ld (the per-row kernels)
 
 // elementwise / small ops (ops.hip)
 int launch_layernorm(int dtype, const void* x, int x_f32, const void* res, int res_f32, const float* gamma,

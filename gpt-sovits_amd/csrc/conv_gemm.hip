@@ -46,7 +46,8 @@ __device__ __forceinline__ f4 lrelu_frag(f4 v, float slope) {
 __device__ __forceinline__ h8 relu_frag(h8 v) { return __builtin_elementwise_max(v, zero_frag<h8>()); }
 __device__ __forceinline__ f4 relu_frag(f4 v) { return __builtin_elementwise_max(v, zero_frag<f4>()); }
 
-template <typename T, int TM, int TN, int WM, int WN>
+// GROWS: per-row gates (ConvArgs::gate_rows), output row orow takes the vector gate + (orow / gate_rows) * gate_ld
+template <typename T, int TM, int TN, int WM, int WN, bool GROWS = false>
 __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(ConvArgs a) {
   typedef typename Frag<T>::type F;
   constexpr int G = DT<T>::G;
@@ -148,7 +149,8 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(ConvArgs a) {
           if (j >= nvalid) break;
           float u = v[j];
           if (a.bias) u += a.bias[z * a.bz + oc + j];
-          if (a.gate) u *= a.gate[z * a.bz + oc + j];
+          if constexpr (GROWS) u *= a.gate[(long long)(orow / a.gate_rows) * a.gate_ld + oc + j];
+          else if (a.gate) u *= a.gate[z * a.bz + oc + j];
           if (a.res) u += a.res_f32 ? ((const float*)a.res)[roff + j] : to_f(((const T*)a.res)[roff + j]);
           u *= a.scale;
           if (has_act) u = post_act_f(a.post_act, u);
@@ -175,6 +177,9 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(ConvArgs a) {
 
 template <typename T, int TM, int TN, int WM, int WN> static int launch_direct(const ConvArgs& a, hipStream_t s) {
   const dim3 grid(cdiv(a.T_virt, WN * TN * 32), cdiv(a.Cout, WM * TM * 32), a.Z);
+  if (a.gate_rows)
+    return launch_routed<conv_gemm_kernel<T, TM, TN, WM, WN, true>, 0>(route_code(ROUTE_CONV_GEMM, DT<T>::id, TM, TN, WM, WN, 0, ROUTE_GROWS), grid,
+                                                                        dim3(WM * WN * 64), 0, s, a);
   return launch_routed<conv_gemm_kernel<T, TM, TN, WM, WN>, 0>(route_code(ROUTE_CONV_GEMM, DT<T>::id, TM, TN, WM, WN), grid, dim3(WM * WN * 64), 0, s, a);
 }
 
@@ -238,6 +243,10 @@ static int launch_conv_gemm_kernel(int dtype, const ConvArgs& a_in, hipStream_t 
   set_conv_route(0);
   if (a.T_virt == 0) a.T_virt = a.T_out;
   if (a.ups_u > 0 && a.ups_cout == 0) { set_error("conv_gemm: ups_cout missing"); return GSV_ERR_ARG; }
+  // per-row gates: gemm_sk / gemm_t64, gemm_lds (residual form) and conv_gemm have the instantiation; conv_wide, conv_narrow and
+  // conv_lds refuse any gate, so nothing else can take such a launch
+  GSV_REQUIRE(a.gate_rows == 0 || (a.gate_rows > 0 && a.gate && a.gate_ld >= a.Cout && a.Z == 1 && a.ups_u == 0 && !a.row_seg),
+              "conv_gemm: per-row gates need a gate table, gate_ld >= Cout, Z = 1 and a plain (not transposed, not segmented) launch");
   const ConvSwitches& sw = conv_switches();
   // gemm_sk -> conv_wide -> gemm_lds -> conv_narrow -> conv_lds -> conv_gemm: the first kernel that is eligible takes the launch
   int rc = launch_gemm_sk(dtype, a, s);

@@ -40,6 +40,7 @@ struct ConvOpt {
   int ldy = 0, y_col0 = 0;
   const float* bias_override = nullptr; bool no_bias = false;
   const float* gate = nullptr;   // per-output-channel gate: y = ((W x + b) * gate + res) * scale
+  int gate_rows = 0, gate_ld = 0;   // per-row gates: output row t takes gate + (t / gate_rows) * gate_ld (ConvArgs::gate_rows)
   int w_nt = 0;                  // stream the weights non-temporal (ConvArgs::w_nt)
   int w_row0 = 0, cout = -1;   // use a row slice of the weight matrix
   const int* row_seg = nullptr;   // segmented decode: gap rows of the output stored as 0 (ConvArgs::row_seg)

@@ -312,7 +312,7 @@ int conv(Ctx* h, hipStream_t s, const Conv& c, const void* x, int ldx, int T_in,
   const int cout = o.cout >= 0 ? o.cout : c.cout;
   a.w = (const char*)c.w + (size_t)o.w_row0 * c.taps * c.cin * esz(h);
   a.bias = o.no_bias ? nullptr : (o.bias_override ? o.bias_override : (c.b ? c.b + (c.ups_u ? 0 : o.w_row0) : nullptr));
-  a.gate = o.gate;
+  a.gate = o.gate; a.gate_rows = o.gate_rows; a.gate_ld = o.gate_ld;
   a.w_nt = o.w_nt;
   a.T_in = T_in; a.T_out = T_out; a.Cin = c.cin; a.Cout = cout; a.taps = c.taps;
   a.stride = o.stride; a.dil = o.dil;

@@ -12,7 +12,9 @@ namespace gsv {
 #ifndef GSV_GEMM_W8_BK
 #define GSV_GEMM_W8_BK 128
 #endif
-template <typename T, bool RES, bool WNT = false, int NW = 4>
+// GROWS: per-row gates (ConvArgs::gate_rows): the gate vector is looked up per OUTPUT ROW in the epilogue (a 128-row tile spans
+// several utterances) instead of once per thread in the prologue; everything else, the summation order included, is the same
+template <typename T, bool RES, bool WNT = false, int NW = 4, bool GROWS = false>
 __global__ __launch_bounds__(NW * 64) void gemm_lds_kernel(ConvArgs a) {
   typedef typename FragL<T>::type F;
   constexpr int G = DT<T>::G, KC = 2 * G;
@@ -53,7 +55,8 @@ __global__ __launch_bounds__(NW * 64) void gemm_lds_kernel(ConvArgs a) {
   f4 ebias = (f4){0.f, 0.f, 0.f, 0.f};
   if (a.bias) for (int j = 0; j < env; ++j) ebias[j] = a.bias[z * a.bz + ec + j];
   f4 egate = (f4){1.f, 1.f, 1.f, 1.f};
-  if (a.gate) for (int j = 0; j < env; ++j) egate[j] = a.gate[z * a.bz + ec + j];
+  if constexpr (!GROWS)
+    if (a.gate) for (int j = 0; j < env; ++j) egate[j] = a.gate[z * a.bz + ec + j];
   T4 rv[RES ? WN * NI : 1];
   rv[0] = (T4){(T)0.f, (T)0.f, (T)0.f, (T)0.f};
   if (RES) {
@@ -166,6 +169,8 @@ __global__ __launch_bounds__(NW * 64) void gemm_lds_kernel(ConvArgs a) {
   }
 
   float* os = (float*)smem;                           // [PR][LDO]
+  int gb = 0, glim = 0, gcur = -1;                    // GROWS: utterance of the row at hand, first row of the next one, the one loaded
+  if constexpr (GROWS) { gb = t0 / a.gate_rows; glim = (gb + 1) * a.gate_rows; }
 #pragma unroll
   for (int pass = 0; pass < WN; ++pass) {
     __syncthreads();
@@ -192,6 +197,16 @@ __global__ __launch_bounds__(NW * 64) void gemm_lds_kernel(ConvArgs a) {
         const int t = t0 + pass * PR + tl;
         if (!(t < a.T_virt && env > 0)) continue;
         const f4 av = *(const f4*)(os + (size_t)tl * LDO + 4 * ecg);
+        if constexpr (GROWS) {
+          // the thread's items come in ascending t and its four channels are fixed: walk the utterance index forward from the
+          // tile's first (one uniform division per workgroup) and reload the gate values only when the utterance changes
+          while (t >= glim) { ++gb; glim += a.gate_rows; }
+          if (gb != gcur) {
+            gcur = gb;
+            const float* gp = a.gate + (long long)gb * a.gate_ld + ec;
+            for (int j = 0; j < env; ++j) egate[j] = gp[j];
+          }
+        }
         float v[4];
   #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -247,6 +262,15 @@ template <typename T> static int launch_gemm_lds_t(const ConvArgs& a, hipStream_
     return launch_routed<gemm_lds_kernel<T, R.value, NTW.value, NW>, LDS_CAP>(
         route_code(ROUTE_GEMM_LDS, DT<T>::id, NW, b.xcd_order, 0, 0, 0, route_flags(R.value, false, false, NTW.value)), grid, dim3(NW * 64), lds, s, b);
   };
+  // per-row gates: the residual form only (the DiT's gated GEMMs carry one); without a residual the launch goes on to conv_gemm
+  if (a.gate_rows) {
+    if (!a.res || a.Z != 1) return 1;
+    return with_flags([&](auto W8) {
+      constexpr int NW = W8.value ? 8 : 4;
+      return launch_routed<gemm_lds_kernel<T, true, false, NW, true>, LDS_CAP>(
+          route_code(ROUTE_GEMM_LDS, DT<T>::id, NW, b.xcd_order, 0, 0, 0, route_flags(true, false) | ROUTE_GROWS), grid, dim3(NW * 64), lds, s, b);
+    }, w8);
+  }
   // the residual form has no non-temporal variant
   if (a.res) return with_flags([&](auto W8) { return launch(std::true_type{}, std::false_type{}, W8); }, w8);
   return with_flags([&](auto NTW, auto W8) { return launch(std::false_type{}, NTW, W8); }, a.w_nt != 0, w8);

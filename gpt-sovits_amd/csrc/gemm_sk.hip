@@ -25,8 +25,12 @@ namespace {
 __device__ __forceinline__ void mma32(f16v& acc, h8 a, h8 b) { acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc, 0, 0, 0); }
 
 // bias / gate / residual / scale / activation on 16 consecutive output channels of row t, stored as two 16-byte pieces
+// GROWS: per-row gates (ConvArgs::gate_rows), row t's vector is gate + (t / gate_rows) * gate_ld
+template <bool GROWS = false>
 __device__ __forceinline__ void row_epilogue(const ConvArgs& a, float (&v)[16], int t, int cbase_in) {
   const int cbase = cbase_in;
+  const float* gate = a.gate;
+  if constexpr (GROWS) gate += (long long)(t / a.gate_rows) * a.gate_ld;
   const int nv = max(0, min(16, a.Cout - cbase));
   if (nv == 0) return;
   const long long yoff = (long long)t * a.ldy + a.y_col0 + cbase;
@@ -49,7 +53,7 @@ __device__ __forceinline__ void row_epilogue(const ConvArgs& a, float (&v)[16], 
     if (e >= nv) break;
     float u = v[e];
     if (a.bias) u += a.bias[cbase + e];
-    if (a.gate) u *= a.gate[cbase + e];
+    if (a.gate) u *= gate[cbase + e];
     if (a.res) u += rr[e];
     u *= a.scale;
     v[e] = has_act ? post_act_f(a.post_act, u) : u;
@@ -75,6 +79,7 @@ __device__ __forceinline__ void row_epilogue(const ConvArgs& a, float (&v)[16], 
 
 struct Frag { h8 a[2][4], b[2][4]; };
 
+template <bool GROWS = false>
 __global__ __launch_bounds__(256) void gemm_sk_f16_kernel(ConvArgs a) {
   constexpr int LDO = 68;
   extern __shared__ float os[];                     // [4 waves][64 t][LDO]
@@ -159,7 +164,7 @@ __global__ __launch_bounds__(256) void gemm_sk_f16_kernel(ConvArgs a) {
     for (int ww = 1; ww < 4; ++ww) s4 += *(const f4*)(os + ((size_t)ww * 64 + tl) * LDO + cs + e);
     v[e] = s4[0]; v[e + 1] = s4[1]; v[e + 2] = s4[2]; v[e + 3] = s4[3];
   }
-  row_epilogue(a, v, t, c0 + cs);
+  row_epilogue<GROWS>(a, v, t, c0 + cs);
 }
 
 
@@ -172,7 +177,7 @@ __global__ __launch_bounds__(256) void gemm_sk_f16_kernel(ConvArgs a) {
 // at T = 934) run in one round instead of two)
 template <int SLAB> struct SlabT { h8 a[SLAB / 32], b[SLAB / 32]; };
 
-template <bool WNT, int SLAB>
+template <bool WNT, int SLAB, bool GROWS = false>
 __global__ __launch_bounds__(256) void gemm_t64_f16_kernel(ConvArgs a) {
   constexpr int LDO = 68;
   constexpr int RB = SLAB * 2;                      // bytes per staged row
@@ -269,7 +274,7 @@ __global__ __launch_bounds__(256) void gemm_t64_f16_kernel(ConvArgs a) {
     const f4 s4 = *(const f4*)(os + (size_t)tl * LDO + cs + e);
     v[e] = s4[0]; v[e + 1] = s4[1]; v[e + 2] = s4[2]; v[e + 3] = s4[3];
   }
-  row_epilogue(a, v, t, c0 + cs);
+  row_epilogue<GROWS>(a, v, t, c0 + cs);
 }
 
 }  // namespace
@@ -292,14 +297,16 @@ int launch_gemm_sk(int dtype, const ConvArgs& a, hipStream_t s) {
   const dim3 grid(cdiv(a.T_virt, 64), cdiv(a.Cout, 64));
   if (sw.gemm_t64 && a.Cin % 512 == 0) {
     // 128-half stages (two workgroups per CU) by default; GSV_T64_SLAB=256 restores round 2's single resident workgroup
-    return with_flags([&](auto WNT, auto S128) {
+    return with_flags([&](auto WNT, auto S128, auto GR) {
       constexpr int SLAB = S128.value ? 128 : 256, LDS = 2 * 2 * 64 * SLAB * 2;   // two buffers of two 64-row operands of SLAB halfs
-      return launch_routed<gemm_t64_f16_kernel<WNT.value, SLAB>, LDS>(
-          route_code(ROUTE_GEMM_T64, GSV_F16, sw.t64_slab / 16, 0, 0, 0, 0, route_flags(false, false, false, WNT.value)), grid, dim3(256), LDS, s, a);
-    }, a.w_nt != 0, sw.t64_slab == 128);
+      return launch_routed<gemm_t64_f16_kernel<WNT.value, SLAB, GR.value>, LDS>(
+          route_code(ROUTE_GEMM_T64, GSV_F16, sw.t64_slab / 16, 0, 0, 0, 0, route_flags(false, false, false, WNT.value) | (GR.value ? ROUTE_GROWS : 0)),
+          grid, dim3(256), LDS, s, a);
+    }, a.w_nt != 0, sw.t64_slab == 128, a.gate_rows != 0);
   }
   constexpr int LDS = 4 * 64 * 68 * 4;              // the four waves' partial tiles
-  return launch_routed<gemm_sk_f16_kernel, LDS>(route_code(ROUTE_GEMM_SK, GSV_F16), grid, dim3(256), LDS, s, a);
+  if (a.gate_rows) return launch_routed<gemm_sk_f16_kernel<true>, LDS>(route_code(ROUTE_GEMM_SK, GSV_F16, 0, 0, 0, 0, 0, ROUTE_GROWS), grid, dim3(256), LDS, s, a);
+  return launch_routed<gemm_sk_f16_kernel<false>, LDS>(route_code(ROUTE_GEMM_SK, GSV_F16), grid, dim3(256), LDS, s, a);
 }
 
 }  // namespace gsv

@@ -24,10 +24,12 @@ namespace gsv {
 
 __device__ __forceinline__ f4 lora_mma16(h8 a, h8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 
-__global__ __launch_bounds__(256) void lora_delta_f16_kernel(const _Float16* __restrict__ x, _Float16* __restrict__ y, int Tn, int K, int N,
-                                                             int n_proj, const int* __restrict__ slot, int slot_stride,
-                                                             const LoraSlot* __restrict__ tab, long long coef_a, long long coef_b,
-                                                             const float* __restrict__ gate) {
+// The kernels' bodies are written once; the __global__ entries below differ in where row b finds its gate vector: the one
+// vector of the launch, or (the *_rows entries of a flow-matching session, where every row has its own time) gate + b * gate_ld.
+__device__ __forceinline__ void lora_delta_f16_body(const _Float16* __restrict__ x, _Float16* __restrict__ y, int Tn, int K, int N,
+                                                    int n_proj, const int* __restrict__ slot, int slot_stride,
+                                                    const LoraSlot* __restrict__ tab, long long coef_a, long long coef_b,
+                                                    const float* __restrict__ gate) {
   extern __shared__ __attribute__((aligned(16))) _Float16 lora_u16[];   // [64][R + 8]
   const int b = blockIdx.y;
   const int sl = slot[(long long)b * slot_stride];
@@ -105,10 +107,23 @@ __global__ __launch_bounds__(256) void lora_delta_f16_kernel(const _Float16* __r
   }
 }
 
-__global__ __launch_bounds__(256) void lora_delta_f32_kernel(const float* __restrict__ x, float* __restrict__ y, int Tn, int K, int N,
+__global__ __launch_bounds__(256) void lora_delta_f16_kernel(const _Float16* __restrict__ x, _Float16* __restrict__ y, int Tn, int K, int N,
                                                              int n_proj, const int* __restrict__ slot, int slot_stride,
                                                              const LoraSlot* __restrict__ tab, long long coef_a, long long coef_b,
                                                              const float* __restrict__ gate) {
+  lora_delta_f16_body(x, y, Tn, K, N, n_proj, slot, slot_stride, tab, coef_a, coef_b, gate);
+}
+__global__ __launch_bounds__(256) void lora_delta_f16_rows_kernel(const _Float16* __restrict__ x, _Float16* __restrict__ y, int Tn, int K, int N,
+                                                                  int n_proj, const int* __restrict__ slot, int slot_stride,
+                                                                  const LoraSlot* __restrict__ tab, long long coef_a, long long coef_b,
+                                                                  const float* __restrict__ gate, int gate_ld) {
+  lora_delta_f16_body(x, y, Tn, K, N, n_proj, slot, slot_stride, tab, coef_a, coef_b, gate + (long long)blockIdx.y * gate_ld);
+}
+
+__device__ __forceinline__ void lora_delta_f32_body(const float* __restrict__ x, float* __restrict__ y, int Tn, int K, int N,
+                                                    int n_proj, const int* __restrict__ slot, int slot_stride,
+                                                    const LoraSlot* __restrict__ tab, long long coef_a, long long coef_b,
+                                                    const float* __restrict__ gate) {
   extern __shared__ __attribute__((aligned(16))) float lora_u32[];   // [16][R]
   const int b = blockIdx.y;
   const int sl = slot[(long long)b * slot_stride];
@@ -142,8 +157,22 @@ __global__ __launch_bounds__(256) void lora_delta_f32_kernel(const float* __rest
   }
 }
 
+__global__ __launch_bounds__(256) void lora_delta_f32_kernel(const float* __restrict__ x, float* __restrict__ y, int Tn, int K, int N,
+                                                             int n_proj, const int* __restrict__ slot, int slot_stride,
+                                                             const LoraSlot* __restrict__ tab, long long coef_a, long long coef_b,
+                                                             const float* __restrict__ gate) {
+  lora_delta_f32_body(x, y, Tn, K, N, n_proj, slot, slot_stride, tab, coef_a, coef_b, gate);
+}
+__global__ __launch_bounds__(256) void lora_delta_f32_rows_kernel(const float* __restrict__ x, float* __restrict__ y, int Tn, int K, int N,
+                                                                  int n_proj, const int* __restrict__ slot, int slot_stride,
+                                                                  const LoraSlot* __restrict__ tab, long long coef_a, long long coef_b,
+                                                                  const float* __restrict__ gate, int gate_ld) {
+  lora_delta_f32_body(x, y, Tn, K, N, n_proj, slot, slot_stride, tab, coef_a, coef_b, gate + (long long)blockIdx.y * gate_ld);
+}
+
 int launch_lora_delta(int dtype, const void* x, void* y, int Tn, int DB, int K, int N, int n_proj, const int* slot, int slot_stride,
-                      const LoraSlot* tab, int max_rp, long long coef_a, long long coef_b, const float* gate, hipStream_t s) {
+                      const LoraSlot* tab, int max_rp, long long coef_a, long long coef_b, const float* gate, hipStream_t s, int gate_ld) {
+  GSV_REQUIRE(gate_ld == 0 || (gate && gate_ld >= N), "lora_delta: per-row gates need a gate table with gate_ld >= N");
   GSV_REQUIRE(x && y && slot && tab && Tn > 0 && DB > 0 && DB <= 65535, "lora_delta: bad argument");
   GSV_REQUIRE(n_proj >= 1 && n_proj <= 3 && N > 0 && N % (16 * n_proj) == 0, "lora_delta: N=%d must be a multiple of 16 per projection (%d)", N,
               n_proj);
@@ -151,6 +180,15 @@ int launch_lora_delta(int dtype, const void* x, void* y, int Tn, int DB, int K, 
   GSV_REQUIRE(max_rp >= 16 && max_rp <= GSV_LORA_MAX_RANK && max_rp % 16 == 0, "lora_delta: padded rank %d is not a multiple of 16 in [16, %d]",
               max_rp, GSV_LORA_MAX_RANK);
   const int R = n_proj * max_rp;
+  if (gate_ld) {   // per-row gates: the same bodies, the same geometry
+    if (dtype == GSV_F16)
+      GSV_LAUNCH(lora_delta_f16_rows_kernel, dim3(cdiv(Tn, 64), DB), dim3(256), (size_t)64 * (R + 8) * 2, s, (const _Float16*)x, (_Float16*)y, Tn, K,
+                 N, n_proj, slot, slot_stride, tab, coef_a, coef_b, gate, gate_ld);
+    else
+      GSV_LAUNCH(lora_delta_f32_rows_kernel, dim3(cdiv(Tn, 16), DB), dim3(256), (size_t)16 * R * 4, s, (const float*)x, (float*)y, Tn, K, N, n_proj,
+                 slot, slot_stride, tab, coef_a, coef_b, gate, gate_ld);
+    return GSV_OK;
+  }
   if (dtype == GSV_F16) {
     GSV_LAUNCH(lora_delta_f16_kernel, dim3(cdiv(Tn, 64), DB), dim3(256), (size_t)64 * (R + 8) * 2, s, (const _Float16*)x, (_Float16*)y, Tn, K, N,
                n_proj, slot, slot_stride, tab, coef_a, coef_b, gate);

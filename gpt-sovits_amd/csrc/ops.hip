@@ -498,6 +498,7 @@ static gsv::ConvArgs conv_desc_args(const gsv_conv_desc* d) {
   a.accumulate = d->accumulate; a.out_f32 = d->out_f32;
   a.res_f32 = d->res_dtype == 0 ? d->out_f32 : d->res_dtype == 1;
   a.y_col0 = d->y_col0; a.w_nt = d->w_nt; a.z_res = d->z_res;
+  a.gate_rows = d->gate_rows; a.gate_ld = d->gate_ld;
   if (d->ups_u > 0) {
     // transposed conv restated as a polyphase conv: Cout = u * real_cout virtual channels
     a.ups_u = d->ups_u; a.ups_pad = d->ups_pad; a.ups_cout = d->Cout / d->ups_u;

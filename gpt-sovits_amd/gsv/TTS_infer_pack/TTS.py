@@ -29,6 +29,7 @@ import torch
 import torch.nn.functional as F
 
 from ..AR.models.t2s_model import Text2SemanticDecoder
+from .._lib import CFM_SESSION_MAX_ROWS
 from ..module.models import CFM, SynthesizerTrn, SynthesizerTrnV3, cfg_guided
 from ..process_ckpt import load_sovits_new  # noqa: F401  (reference process_ckpt.py:129-138; re-exported)
 
@@ -135,6 +136,41 @@ def choose_candidate(o: dict, cands: Sequence[dict]) -> Tuple[int, List[dict]]:
         raise ValueError(f"best_of_score returned {k!r} for {len(cands)} candidates")
     return int(k), [dict(n=int(c["n"]), mean_logprob=_mean_logprob(c), cut=bool(c["cut"]), chosen=i == k)
                     for i, c in enumerate(cands)]
+
+
+def plan_cfm_session(rows: Sequence[Tuple[int, bool]], cap: int) -> List[Tuple[List[int], int]]:
+    """The schedule of a flow-matching session (CFM.open_session) for `rows` = [(sample_steps, guided)] in arrival order and
+    a cap of `cap` live DiT rows, a guided row counting 2 (itself and its unconditioned twin).  Pure: no engine, no tensors.
+    Returns [(admit, k)]: before the call step(k) the rows `admit` (indices into `rows`, possibly none) are admitted.
+    Admission is FIFO -- a row never overtakes an earlier one, so a guided row at the head of the queue waits for two free
+    DiT rows even when a later unguided row would fit the one that is free -- and as many rows as fit are admitted at once.
+    Every step() call runs until the next live row finishes (k = the smallest number of steps any live row still has to
+    take), so a place is refilled as soon as it is free.  Every row takes exactly its sample_steps steps."""
+    cap = int(cap)
+    need = [2 if g else 1 for _, g in rows]
+    for i, (steps, _) in enumerate(rows):
+        if int(steps) < 1:
+            raise ValueError(f"row {i}: sample_steps {steps} < 1")
+        if need[i] > cap:
+            raise ValueError(f"row {i} needs {need[i]} DiT rows, the session has {cap}")
+    schedule: List[Tuple[List[int], int]] = []
+    left: Dict[int, int] = {}           # live row -> steps it still has to take
+    nxt, used = 0, 0
+    while nxt < len(rows) or left:
+        admit = []
+        while nxt < len(rows) and used + need[nxt] <= cap:
+            admit.append(nxt)
+            left[nxt] = int(rows[nxt][0])
+            used += need[nxt]
+            nxt += 1
+        k = min(left.values())
+        schedule.append((admit, k))
+        for i in list(left):
+            left[i] -= k
+            if left[i] == 0:
+                del left[i]
+                used -= need[i]
+    return schedule
 
 
 class TTS_Config:
@@ -1634,10 +1670,20 @@ class TTS:
         group's rows fill passes of at most cfm_max_rows rows in (r, bi, k) order, so a fold may span two passes.  A guided
         row brings its unconditioned twin into the pass: a guided pass takes at most cfm_max_rows // 2 rows, so no pass runs
         the DiT over more than cfm_max_rows rows.  Returns the passes, lists of (r, bi, k)."""
+        groups: Dict[Tuple[int, float], List[Tuple[int, int, int]]] = {}
+        for row, steps, rate in TTS.plan_cfm_rows(self, plans):
+            groups.setdefault((steps, rate), []).append(row)
+        caps = {g: max(1, int(self.cfm_max_rows) // (2 if g[1] else 1)) for g in groups}
+        return [rows[i:i + caps[g]] for g, rows in groups.items() for i in range(0, len(rows), caps[g])]
+
+    def plan_cfm_rows(self, plans: List[dict]) -> List[Tuple[Tuple[int, int, int], int, float]]:
+        """The rows of the shared flow-matching stage in (r, bi, k) order, as plan_cfm cuts them, each with its request's
+        sample_steps and guidance rate (0.0 for every rate <= 1e-5): [((r, bi, k), sample_steps, rate)].  plan_cfm groups them
+        into one-shot passes; run_batch(continuous_cfm=True) feeds them, in this order, to plan_cfm_session."""
         if not getattr(self.configs, "use_vocoder", False):
             return []
         vc = self.vocoder_configs
-        groups: Dict[Tuple[int, float], List[Tuple[int, int, int]]] = {}
+        out = []
         for r, pl in enumerate(plans):
             o = pl["opts"]
             if not o["parallel_infer"]:
@@ -1647,10 +1693,8 @@ class TTS:
                     continue
                 n = len(self._chunk_cuts(int(frames), vc["T_chunk"] - int(pl["T_min"]), vc["overlapped_len"]))
                 rate = o.get("inference_cfg_rate", 0)
-                g = (int(o["sample_steps"]), float(rate) if cfg_guided(rate) else 0.0)
-                groups.setdefault(g, []).extend((r, bi, k) for k in range(n))
-        caps = {g: max(1, int(self.cfm_max_rows) // (2 if g[1] else 1)) for g in groups}
-        return [rows[i:i + caps[g]] for g, rows in groups.items() for i in range(0, len(rows), caps[g])]
+                out.extend(((r, bi, k), int(o["sample_steps"]), float(rate) if cfg_guided(rate) else 0.0) for k in range(n))
+        return out
 
     vocoder_max_frames = 32768    # mel frames of one shared vocoder pass.  No sweep of the cost per frame has been run yet
                                   # (DESIGN.md section 4h): this is the initial cap, which keeps every gapped layout far
@@ -1818,7 +1862,47 @@ class TTS:
                     plans[r]["frags"][bi][k] = wav[0, 0]
         self.vits_model.invalidate_refer()          # the engine's cached reference terms are the last slot's voice
 
-    def _shared_cfm_stage(self, plans: List[dict], shared_vocoder: bool = False) -> None:
+    def _continuous_cfm_passes(self, plans: List[dict], fold_in: dict, prompts: dict, voice_of: list) -> Dict[Tuple[int, int], list]:
+        """continuous_cfm: the rows of every (sample_steps, guidance rate) group through ONE flow-matching session
+        (CFM.open_session) on the schedule of plan_cfm_session: FIFO admission into at most cfm_max_rows DiT rows, every step()
+        call runs until the next row finishes, and a finished row's slot goes to the next waiting row.  The session's cap is
+        cfm_max_rows clipped to the engine's 64 DiT rows per session, and at least 2 when a row is guided.  Each row carries the
+        prompt, seed, adapter, step count and rate it carries in the one-shot passes.  -> fold_out as _shared_cfm_stage builds it."""
+        rows = self.plan_cfm_rows(plans)
+        fold_out: Dict[Tuple[int, int], list] = {}
+        if not rows:
+            return fold_out
+        # a session has at most CFM_SESSION_MAX_ROWS (64) DiT rows: a larger cfm_max_rows is clipped to it (the grouped passes
+        # have no such limit).  cfm_max_rows = 1 still serves a guided row, as plan_cfm does (a pass of one row and its twin)
+        cap = min(int(self.cfm_max_rows), CFM_SESSION_MAX_ROWS)
+        cap = max(cap, 2 if any(rate > 0.0 for _, _, rate in rows) else 1)
+        schedule = plan_cfm_session([(steps, rate > 0.0) for _, steps, rate in rows], cap)
+        got: Dict[Tuple[int, int], dict] = {}
+        T_chunk = int(fold_in[rows[0][0][:2]][0].shape[1])
+        with self.vits_model.cfm.open_session(cap, T_chunk) as sess:
+            in_slot: Dict[int, int] = {}
+            for admit, k in schedule:
+                if admit:
+                    at = [rows[i][0] for i in admit]
+                    mu = torch.cat([fold_in[(r, bi)][0][kk:kk + 1] for r, bi, kk in at], 0)
+                    mels = [prompts[voice_of[r]][3] for r, _, _ in at]
+                    seeds = [CFM.row_seed(plans[r]["actual_seed"] + bi, kk) for r, bi, kk in at]
+                    names = [plans[r]["opts"].get("lora_voice") for r, _, _ in at]
+                    lora_kw = dict(adapters=[None if n is None else self._lora_voice(n)[1] for n in names]) if any(names) else {}
+                    slots = sess.admit(mu, mels, [rows[i][1] for i in admit], [rows[i][2] for i in admit], seeds=seeds, **lora_kw)
+                    in_slot.update(zip(slots, admit))
+                for slot in sess.step(k):
+                    (r, bi, kk), _, _ = rows[in_slot.pop(slot)]
+                    Tp = int(prompts[voice_of[r]][3].shape[2])
+                    dt = fold_in[(r, bi)][0].dtype           # what CFM.inference_rows returns for this mu
+                    pred = sess.fetch(slot).to(dt if dt in (torch.float16, torch.float32) else torch.float32)
+                    got.setdefault((r, bi), {})[kk] = pred[None, :, Tp:]
+            assert not in_slot, "plan_cfm_session left rows in the session"
+        for key in sorted(got):
+            fold_out[key] = [got[key][kk] for kk in sorted(got[key])]
+        return fold_out
+
+    def _shared_cfm_stage(self, plans: List[dict], shared_vocoder: bool = False, continuous_cfm: bool = False) -> None:
         """shared_cfm, v3 / v4: every chunk of every fold that plan_cfm shares is one row, with its voice's prompt mel, the
         noise key run() gives it and its request's LoRA adapter (the key "lora_voice"), of a CFM.inference_rows pass; vocoder and SOLA stay per fold, unless shared_vocoder: then
         the folds' mels go through the plan_vocoder passes of the vocoder's forward_segments, and only SOLA and the cuts stay
@@ -1849,6 +1933,14 @@ class TTS:
                                                          [ph.to(self.configs.device) for ph in item["phones"]],
                                                          pl["opts"]["speed_factor"], *([] if lora is None else [lora]))
                     pl["cfm_folds"][bi] = sum(fold_in[(r, bi)][1])
+        if continuous_cfm:
+            fold_out = self._continuous_cfm_passes(plans, fold_in, prompts, voice_of)
+        else:
+            fold_out = self._grouped_cfm_passes(plans, fold_in, prompts, voice_of)
+        self._vocode_folds(plans, fold_in, fold_out, shared_vocoder)
+
+    def _grouped_cfm_passes(self, plans: List[dict], fold_in: dict, prompts: dict, voice_of: list) -> Dict[Tuple[int, int], list]:
+        """the one-shot passes of plan_cfm: one CFM.inference_rows call per pass -> fold_out[(r, bi)] = the fold's rows in order"""
         fold_out: Dict[Tuple[int, int], list] = {}
         for rows in self.plan_cfm(plans):
             mu = torch.cat([fold_in[(r, bi)][0][k:k + 1] for r, bi, k in rows], 0)
@@ -1861,6 +1953,10 @@ class TTS:
                                                       inference_cfg_rate=o["inference_cfg_rate"], **lora_kw)
             for n, (r, bi, k) in enumerate(rows):
                 fold_out.setdefault((r, bi), []).append(pred[n:n + 1, :, mels[n].shape[2]:])
+        return fold_out
+
+    def _vocode_folds(self, plans: List[dict], fold_in: dict, fold_out: dict, shared_vocoder: bool) -> None:
+        """the folds' mels (fold_out) -> `frags[bi]`: one vocoder call per fold, or the plan_vocoder passes of forward_segments"""
         for (r, bi), got in fold_out.items():        # a fold is finished when all its rows are back
             assert len(got) == fold_in[(r, bi)][0].shape[0]
         if not shared_vocoder:
@@ -1908,7 +2004,8 @@ class TTS:
                   shared_speed: bool = False, mixed_sampling: bool = False,
                   shared_vocoder: bool = False, shared_bert: bool = False,
                   shared_hubert: bool = False, shared_sv: bool = False,
-                  device_frontend: bool = False, continuous_ar: bool = False) -> List[Tuple[int, np.ndarray]]:
+                  device_frontend: bool = False, continuous_ar: bool = False,
+                  continuous_cfm: bool = False) -> List[Tuple[int, np.ndarray]]:
         """Several requests, each with its own reference voice, through shared AR decodes.  Each request dict takes the
         keys run() accepts plus an optional "voice" (make_voice); without one it uses its ref_audio_path / prompt_text
         (through make_voice's LRU) or the current prompt cache.  Returns one (sr, int16 audio) per request, in order: what
@@ -1937,6 +2034,10 @@ class TTS:
         continuous_ar=True: each group of plan_batch (parallel decode with prompts) is decoded through one decode session
         (plan_sessions, Text2SemanticDecoder.infer_panel_continuous) instead of launches of max_batch rows: a sentence that
         ends early hands its slot to the next one.  Same keys, same sampling values, the same tokens per sentence.
+        continuous_cfm=True (with shared_cfm=True, else ValueError): the shared flow-matching stage runs through one session
+        (CFM.open_session) on the schedule of plan_cfm_session instead of one pass per (sample_steps, guidance rate) group:
+        requests with different settings share the DiT launches, each row with its own step count and rate, and a finished
+        row's place goes to the next waiting row.  Seeds, prompts, LoRA adapters, the vocoder and SOLA are those of shared_cfm.
         A request with "best_of" = n > 1 decodes n candidates per sentence as further rows of the shared launches and keeps
         one (plan_batch, select_candidate; "best_of_score": a callable in its place); last_candidates[r][bi][j] then lists
         dict(n, mean_logprob, cut, chosen) per candidate, and is [] for a request without the key.
@@ -1945,6 +2046,8 @@ class TTS:
             raise RuntimeError("init_t2s_weights / init_vits_weights first")
         if shared_vocoder and self.configs.use_vocoder and not shared_cfm:
             raise ValueError("shared_vocoder=True vocodes the folds of the shared flow-matching stage: pass shared_cfm=True too")
+        if continuous_cfm and not shared_cfm:
+            raise ValueError("continuous_cfm=True runs the shared flow-matching stage through a session: pass shared_cfm=True too")
         if device_frontend and not (shared_hubert or shared_sv):
             raise ValueError("device_frontend=True is the front-end of the shared make_voices call: pass shared_hubert=True or shared_sv=True too")
         self.stop_flag = False
@@ -1959,7 +2062,8 @@ class TTS:
         if shared_sovits and not self.configs.use_vocoder:
             self._shared_sovits_stage(plans, shared_speed=shared_speed)
         if shared_cfm and self.configs.use_vocoder:
-            self._shared_cfm_stage(plans, shared_vocoder=shared_vocoder)
+            # the keyword goes along only when it is set: a stage that predates it (a subclass, a stub) keeps working without it
+            self._shared_cfm_stage(plans, shared_vocoder=shared_vocoder, **({"continuous_cfm": True} if continuous_cfm else {}))
         return [self._finish_request(pl, sr) for pl in plans]
 
     def serve(self, **scheduler_kw):

@@ -61,7 +61,9 @@ class ConvDesc(C.Structure):
                 ("rz", C.c_longlong), ("ldr", C.c_int),
                 # optional, 0 = default: residual dtype (0 follows out_f32, 1 fp32, 2 engine dtype), slice column offset in y,
                 # non-temporal weights, batched residual slices (include/gsv.h)
-                ("res_dtype", C.c_int), ("y_col0", C.c_int), ("w_nt", C.c_int), ("z_res", C.c_int)]
+                ("res_dtype", C.c_int), ("y_col0", C.c_int), ("w_nt", C.c_int), ("z_res", C.c_int),
+                # optional, 0 = one gate vector: per-row gates (output row t takes gate + (t / gate_rows) * gate_ld)
+                ("gate_rows", C.c_int), ("gate_ld", C.c_int)]
 
 
 class ZeroMaps(C.Structure):
@@ -161,6 +163,15 @@ _SIGS = {
     "gsv_cfm_inference_adapted": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                             C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.c_float, C.c_float,
                                             C.c_void_p, C.c_void_p]),
+    "gsv_cfm_session_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "gsv_cfm_session_admit": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int),
+                                        C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_void_p, C.POINTER(C.c_uint64),
+                                        C.c_void_p]),
+    "gsv_cfm_session_step": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "gsv_cfm_session_fetch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "gsv_cfm_session_release": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]),
+    "gsv_cfm_session_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "gsv_cfm_session_end": (C.c_int, [C.c_void_p]),
     "gsv_sola": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "gsv_postprocess": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "gsv_postprocess_f32": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -235,6 +246,7 @@ EXPORTS = tuple(_SIGS)   # every symbol include/gsv.h declares
 VITS_MAX_VOICES = 128    # GSV_VITS_MAX_VOICES (gsv.h): voice slots of the segmented decode
 CFM_MAX_ADAPTERS = 256   # GSV_CFM_MAX_ADAPTERS (gsv.h): LoRA adapters one DiT engine holds at once
 LORA_MAX_RANK = 128      # GSV_LORA_MAX_RANK (gsv.h)
+CFM_SESSION_MAX_ROWS = 64   # GSV_CFM_SESSION_MAX_ROWS (gsv.h): slots / live DiT rows of one flow-matching session
 
 _lib = None
 

@@ -529,8 +529,15 @@ class CFM:
         guides every row with that rate (`gsv_cfm_inference_guided`, 2 B DiT rows); the noise of a row does not depend on it.
         `adapters` (B entries: a slot `add_adapter` returned, or None = the base model): row b runs the DiT with that LoRA
         adapter (`gsv_cfm_inference_adapted`; a guided row's twin takes the row's).  None, or no slot among them, is the
-        call without the keyword."""
+        call without the keyword.
+        `n_timesteps` and `inference_cfg_rate` may each be a list / tuple of B values, one per row: the rows then run through a
+        flow-matching session opened and closed here (`open_session`), every row with its own step count and rate; row b
+        equals the row of a call with its own scalars.  Scalars keep the one-shot entries above and their launches.  A session
+        holds at most 64 DiT rows (a guided row counts 2): the sequence form raises ValueError above that, the scalar form has no
+        such limit."""
         B, T = self._check_mu_noise(mu, noise)
+        if isinstance(n_timesteps, (list, tuple)) or isinstance(inference_cfg_rate, (list, tuple)):
+            return self._inference_rows_session(mu, prompts, n_timesteps, temperature, noise, seeds, inference_cfg_rate, adapters)
         slots = self._adapter_slots(adapters, B)
         if B < 1 or len(prompts) != B:
             raise ValueError(f"expected {B} >= 1 prompts, one per row of mu, got {len(prompts)}")
@@ -560,3 +567,141 @@ class CFM:
                 _lib.check(lib.gsv_cfm_inference_rows(h, m.data_ptr(), ptrs, tps, B, T, int(n_timesteps), nz, sd, float(temperature),
                                                       out.data_ptr(), stream), "gsv_cfm_inference_rows")
         return self._launch(mu, prompts, noise, call)
+
+    def _inference_rows_session(self, mu, prompts, n_timesteps, temperature, noise, seeds, rates, adapters):
+        """`inference_rows` with per-row step counts / rates: one session, every row admitted at once, stepped to the largest count"""
+        B, T = int(mu.shape[0]), int(mu.shape[1])
+        steps = [int(n) for n in n_timesteps] if isinstance(n_timesteps, (list, tuple)) else [int(n_timesteps)] * B
+        rates = [float(r) for r in rates] if isinstance(rates, (list, tuple)) else [float(rates)] * B
+        if len(steps) != B or len(rates) != B:
+            raise ValueError(f"expected {B} step counts and {B} rates, one per row of mu, got {len(steps)} and {len(rates)}")
+        cap = sum(2 if cfg_guided(r) else 1 for r in rates)
+        if cap > _lib.CFM_SESSION_MAX_ROWS:
+            raise ValueError(f"{cap} DiT rows (a guided row counts 2) exceed the {_lib.CFM_SESSION_MAX_ROWS} of one session")
+        sess = self.open_session(cap, T, temperature)
+        try:
+            slots = sess.admit(mu, prompts, steps, rates, seeds=seeds, noise=noise, adapters=adapters)
+            sess.step(max(steps))
+            out = torch.stack([sess.fetch(sl) for sl in slots])
+        finally:
+            sess.close()
+        return out.to(mu.dtype if mu.dtype in (torch.float16, torch.float32) else torch.float32)
+
+    def open_session(self, rows_cap, T, temperature=1.0) -> "CFMSession":
+        """A flow-matching session (`gsv_cfm_session_*`) for rows of T frames: rows with their own step count, guidance rate and
+        LoRA slot enter (`admit`) and leave (`fetch`, `release`) between Euler steps (`step`).  `rows_cap` counts DiT rows: a guided
+        row (`cfg_guided(rate)`) takes two; at most 64 (`_lib.CFM_SESSION_MAX_ROWS`), more is an error of the engine.  One session
+        per DiT at a time; the one-shot entries raise while it is open, and so does `remove_adapter` of a slot a live row uses."""
+        return CFMSession(self, rows_cap, T, temperature)
+
+
+class CFMSession:
+    """One open flow-matching session of a `CFM` (see `CFM.open_session`).  Every method issues its launches on the DiT's
+    stream and waits for them, so the tensors given to `admit` may go afterwards and `fetch` returns a finished tensor."""
+    FREE, LIVE, FINISHED = 0, 1, 2
+
+    def __init__(self, cfm, rows_cap, T, temperature=1.0):
+        dit = cfm.estimator
+        if not dit._loaded:
+            raise RuntimeError("DiT.load_state_dict() first")
+        self.cfm, self.rows_cap, self.T = cfm, int(rows_cap), int(T)
+        self._open = False
+        with torch.cuda.device(dit.device):
+            dit.stream.wait_stream(torch.cuda.current_stream(dit.device))
+            _lib.check(_lib.lib().gsv_cfm_session_begin(dit._h, self.rows_cap, self.T, float(temperature),
+                                                        C.c_void_p(dit.stream.cuda_stream)), "gsv_cfm_session_begin")
+        self._open = True
+
+    @property
+    def state(self):
+        """per slot (state, steps taken, n_steps), state one of FREE / LIVE / FINISHED: host bookkeeping, no device wait"""
+        buf = (C.c_int32 * (3 * self.rows_cap))()
+        _lib.check(_lib.lib().gsv_cfm_session_state(self.cfm.estimator._h, buf), "gsv_cfm_session_state")
+        n = self.rows_cap
+        return [(buf[s], buf[n + s], buf[2 * n + s]) for s in range(n)]
+
+    def free_slots(self):
+        return [s for s, st in enumerate(self.state) if st[0] == self.FREE]
+
+    @torch.no_grad()
+    def admit(self, mu, prompts, n_timesteps, inference_cfg_rate, seeds=None, noise=None, adapters=None, slots=None):
+        """Admits the B rows of mu [B, T, text_dim] (prompts, seeds, noise, adapters as `CFM.inference_rows`); `n_timesteps` and
+        `inference_cfg_rate` are a scalar or one value per row.  `slots` (B free slots) defaults to the lowest free ones.
+        Returns the slots.  The engine refuses, before it launches anything, an admission that does not fit `rows_cap`."""
+        cfm, dit = self.cfm, self.cfm.estimator
+        B, T = cfm._check_mu_noise(mu, noise)
+        if T != self.T:
+            raise ValueError(f"the session holds rows of {self.T} frames, got {T}")
+        steps = [int(n) for n in n_timesteps] if isinstance(n_timesteps, (list, tuple)) else [int(n_timesteps)] * B
+        rates = [float(r) for r in inference_cfg_rate] if isinstance(inference_cfg_rate, (list, tuple)) else [float(inference_cfg_rate)] * B
+        if len(steps) != B or len(rates) != B or len(prompts) != B:
+            raise ValueError(f"expected {B} prompts, step counts and rates, one per row of mu")
+        for b, p in enumerate(prompts):
+            if p is not None and (p.dim() != 3 or p.shape[0] != 1 or p.shape[1] != cfm.in_channels):
+                raise ValueError(f"expected prompt {b} of shape [1, {cfm.in_channels}, Tp], got {tuple(p.shape)}")
+        if noise is None and seeds is None:
+            raise ValueError("admit needs `noise` or `seeds`")
+        if seeds is not None and len(seeds) != B:
+            raise ValueError(f"expected {B} seeds, got {len(seeds)}")
+        ad = cfm._adapter_slots(adapters, B)
+        if slots is None:
+            slots = self.free_slots()[:B]
+            if len(slots) < B:
+                raise RuntimeError(f"libgsv_hip gsv_cfm_session_admit refused: {B} rows, {len(slots)} free slots")
+        slots = [int(s) for s in slots]
+        dev = dit.device
+        with torch.cuda.device(dev):
+            m = mu.to(dev, torch.float32).contiguous()
+            ps = [None if p is None else p.to(dev, torch.float32).contiguous() for p in prompts]
+            nz = noise.to(dev, torch.float32).contiguous() if noise is not None else None
+            ptrs = (C.c_void_p * B)(*[p.data_ptr() if p is not None and p.shape[2] else None for p in ps])
+            tps = (C.c_int * B)(*[0 if p is None else int(p.shape[2]) for p in ps])
+            sd = (C.c_uint64 * B)(*[int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds]) if seeds is not None else None
+            dit.stream.wait_stream(torch.cuda.current_stream(dev))
+            _lib.check(_lib.lib().gsv_cfm_session_admit(dit._h, B, (C.c_int32 * B)(*slots), m.data_ptr(), ptrs, tps,
+                                                        (C.c_int * B)(*ad) if ad is not None else None, (C.c_int * B)(*steps),
+                                                        (C.c_float * B)(*rates), nz.data_ptr() if nz is not None else None, sd,
+                                                        C.c_void_p(dit.stream.cuda_stream)), "gsv_cfm_session_admit")
+            dit.stream.synchronize()
+        return slots
+
+    @torch.no_grad()
+    def step(self, k=1):
+        """k Euler steps of every live row -> the slots that finished during the call (ascending)"""
+        dit = self.cfm.estimator
+        before = self.state
+        with torch.cuda.device(dit.device):
+            _lib.check(_lib.lib().gsv_cfm_session_step(dit._h, int(k), C.c_void_p(dit.stream.cuda_stream)), "gsv_cfm_session_step")
+            dit.stream.synchronize()
+        after = self.state
+        return [s for s in range(self.rows_cap) if before[s][0] == self.LIVE and after[s][0] == self.FINISHED]
+
+    @torch.no_grad()
+    def fetch(self, slot, out=None):
+        """a finished row -> [in_channels, T] fp32, its prompt frames zero; frees the slot"""
+        dit = self.cfm.estimator
+        with torch.cuda.device(dit.device):
+            if out is None:
+                out = torch.empty(self.cfm.in_channels, self.T, dtype=torch.float32, device=dit.device)
+            dit.stream.wait_stream(torch.cuda.current_stream(dit.device))
+            _lib.check(_lib.lib().gsv_cfm_session_fetch(dit._h, int(slot), out.data_ptr(), C.c_void_p(dit.stream.cuda_stream)),
+                       "gsv_cfm_session_fetch")
+            dit.stream.synchronize()
+        return out
+
+    def release(self, slots):
+        """drops live or finished rows (cancellation); the others are not touched"""
+        slots = [int(s) for s in slots]
+        _lib.check(_lib.lib().gsv_cfm_session_release(self.cfm.estimator._h, len(slots), (C.c_int32 * max(1, len(slots)))(*slots)),
+                   "gsv_cfm_session_release")
+
+    def close(self):
+        if self._open:
+            self._open = False
+            _lib.check(_lib.lib().gsv_cfm_session_end(self.cfm.estimator._h), "gsv_cfm_session_end")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

@@ -402,7 +402,7 @@ int gsv_cfm_inference_guided(gsv_cfm_t* h, const float* mu, const float* const* 
 int gsv_cfm_adapter_begin(gsv_cfm_t* h, int rank, float alpha);
 int gsv_cfm_adapter_load_tensor(gsv_cfm_t* h, const char* name, const float* data, int64_t numel);
 int gsv_cfm_adapter_finalize(gsv_cfm_t* h, int* slot);
-int gsv_cfm_adapter_remove(gsv_cfm_t* h, int slot);
+int gsv_cfm_adapter_remove(gsv_cfm_t* h, int slot);   /* an error while a live row of an open session uses the slot */
 int gsv_cfm_adapter_count(gsv_cfm_t* h);   /* live adapters, or a negative error code */
 /* gsv_cfm_inference_guided (cfg_rate <= 1e-5: gsv_cfm_inference_rows) whose row b runs the DiT with adapter adapters[b]
  * ([host] B slots; -1 = the base model; NULL = every row the base model): after the q/k/v GEMM and after the out-projection
@@ -412,6 +412,42 @@ int gsv_cfm_adapter_count(gsv_cfm_t* h);   /* live adapters, or a negative error
 int gsv_cfm_inference_adapted(gsv_cfm_t* h, const float* mu, const float* const* prompts, const int* Tp, const int* adapters,
                               int B, int T, int n_steps, const float* noise, const uint64_t* seeds, float temperature,
                               float cfg_rate, float* out, gsv_stream_t stream);
+
+/* Flow-matching sessions (csrc/cfm_session.hip): a pass whose rows carry their own time -- their own step count, step index,
+ * guidance rate and LoRA slot -- and enter and leave between Euler steps.  One session per handle, rows of T frames.
+ * rows_cap (1 .. GSV_CFM_SESSION_MAX_ROWS) is the number of slots and the cap on live DiT rows; a guided row (cfg_rate > 1e-5)
+ * counts 2, it brings its unconditioned twin.  While a session is open the one-shot entries above return an error.
+ * The session issues nothing on its own: every launch happens inside the call that asks for it, on that call's stream;
+ * the calls of one session must be ordered (one stream, or the caller's own events).
+ *
+ * admit: n rows into the free slots `slots` ([host] n distinct ints): mu [dev] fp32 [n][T][text_dim], prompts / Tp / adapters
+ *   ([host], adapters NULL = the base model) as gsv_cfm_inference_adapted, n_steps ([host] n ints, each 1 .. 1024) and cfg_rate
+ *   ([host] n floats) per row, noise [dev] fp32 [n][mel_dim][T] or NULL and seeds ([host] n keys) as gsv_cfm_inference_rows.
+ *   Runs the text stack and the noise draw of these rows and keeps the results (and a copy of the prompt frames) in the slots:
+ *   nothing of the caller's is read once the call's launches have run.  Refused, before anything is launched: an occupied or
+ *   repeated slot, live DiT rows + new ones above rows_cap, n_steps outside [1, 1024], Tp > T, a null prompt with Tp > 0, an
+ *   adapter that is not live, more than 8 distinct step counts among the live rows (the modulation tables are cached per
+ *   step count on the handle, at most 8 tables and 1 GiB, least recently used dropped first; a new step count costs one
+ *   stream synchronisation).
+ * step: k Euler steps of every live row; a row that has taken its n_steps steps is finished and takes no part in later
+ *   steps of the same call.  Row b at its step i uses exactly the modulations and the d of step i of a one-shot call with
+ *   n_steps_b steps.  The DiT of one step runs over the live rows in ascending slot order, then the twins of the guided ones in
+ *   the same order; free and finished slots cost nothing.  Returns at once when no row is live.
+ * fetch: a finished row as out [dev] fp32 [mel_dim][T], its prompt frames zero; frees the slot.  A live or free slot is an error.
+ * release: drops live or finished rows; the others are not touched.
+ * gsv_cfm_adapter_remove refuses a slot that a live row of the open session still runs with.
+ * state: [host] int32 [3][rows_cap] = 0 free / 1 live / 2 finished | steps taken | n_steps.  Host bookkeeping, no device wait.
+ * end: closes the session (rows still in it are dropped); the one-shot entries work again. */
+#define GSV_CFM_SESSION_MAX_ROWS 64
+int gsv_cfm_session_begin(gsv_cfm_t* h, int rows_cap, int T, float temperature, gsv_stream_t stream);
+int gsv_cfm_session_admit(gsv_cfm_t* h, int n, const int32_t* slots, const float* mu, const float* const* prompts, const int* Tp,
+                          const int* adapters, const int* n_steps, const float* cfg_rate, const float* noise,
+                          const uint64_t* seeds, gsv_stream_t stream);
+int gsv_cfm_session_step(gsv_cfm_t* h, int k, gsv_stream_t stream);
+int gsv_cfm_session_fetch(gsv_cfm_t* h, int slot, float* out, gsv_stream_t stream);
+int gsv_cfm_session_release(gsv_cfm_t* h, int n, const int32_t* slots);
+int gsv_cfm_session_state(gsv_cfm_t* h, int32_t* state);
+int gsv_cfm_session_end(gsv_cfm_t* h);
 
 /* ---------------------------------------------------------------------------------------
  * SOLA stitching of the chunked v3/v4 vocoder output (H17, TTS.sola_algorithm, TTS_infer_pack/TTS.py:1611-1637).
@@ -489,6 +525,8 @@ typedef struct {
   int y_col0;          /* column offset of the written slice inside each y row (ldy must cover it) */
   int w_nt;            /* weights loaded non-temporal (GEMM paths) */
   int z_res;           /* batched launch (Z > 1) with a residual of its own slice stride rz: may take the LDS GEMM path */
+  int gate_rows;       /* > 0: per-row gates, output row t is gated by gate + (t / gate_rows) * gate_ld (fp32 [rows / gate_rows][gate_ld]) */
+  int gate_ld;         /*      instead of the one vector at gate; Z = 1, taps-1 GEMMs and the generic kernel (csrc/common.h ConvArgs) */
 } gsv_conv_desc;
 /* fused softmax attention of the DiT blocks alone (fp16, head dim 64): qkv [dev] f16 [T][3*heads*64] (q | k | v column
  * blocks), vt_scratch [dev] heads*64*ceil32(T) halfs, out [dev] f16 [T][heads*64] */
@@ -571,7 +609,7 @@ int gsv_op_conv1d(const gsv_conv_desc* d, int dtype, gsv_stream_t stream);
 int gsv_op_gemm_panel(const gsv_conv_desc* d, int dtype, int tile, gsv_stream_t stream);
 /* test hook: which kernel instantiation the last gsv_op_conv1d / gsv_op_conv_pair / engine conv launch on this thread ran
  * (0 = none since the last reset).  Byte fields, low to high: family, dtype (GSV_F32 / GSV_F16), five template parameters p0..p4,
- * flags (1 RES, 2 ACCU, 4 ALLW, 8 WNT, 16 SEG).  Families and their parameters:
+ * flags (1 RES, 2 ACCU, 4 ALLW, 8 WNT, 16 SEG, 32 GROWS = the per-row-gate instantiation of families 1, 2, 4, 7).  Families and their parameters:
  *   1 gemm_sk_f16 | 2 gemm_t64_f16 p0 = SLAB / 16 | 3 conv_wide_f16 p0 = waves | 4 gemm_lds p0 = waves, p1 = xcd_order
  *   5 conv_lds p0..p4 = TM, TN, WM, WN, CC | 6 conv_narrow_f16 p0..p3 = CC, TM, TN, WN | 7 conv_gemm (generic) p0..p3 = TM, TN, WM, WN
  *   8 conv_pair_f16 p0 = C, p1 = taps; flag SEG = the masked pair of a segmented decode (gsv_op_conv_pair_seg).

@@ -164,6 +164,39 @@ __global__ void cfm_sess_out_kernel(const float* __restrict__ x, int Tp, int Tn,
   out[i] = t < Tp ? 0.f : x[(long long)t * C + c];
 }
 
+// Finished slots straight into the vocoder's layout (fetch_mel): entry i (blockIdx.z) is slot tab.slot[i]; its generated frames
+// t in [Tp, Tn) go, de-normalised and channels-first, to out[c][col0 + t - Tp] of the matrix out [C][ld].  One block moves a tile
+// of kMelTile frames x kMelTile channels through LDS: a wave reads kMelTile consecutive channels of one frame and writes
+// kMelTile consecutive frames of one channel, so both sides are contiguous (cfm_sess_out_kernel reads with a stride of C floats).
+// The tile rows are padded by one float: the column reads of the write phase then fall into distinct banks.
+// The arithmetic is TTS.denorm_spec's, in its order and uncontracted, so the bits are torch's: ((x + 1) / 2) * w + lo, w = hi - lo.
+constexpr int kMelTile = 64;
+struct MelTab { int slot[kMaxRows], Tp[kMaxRows], col0[kMaxRows]; };
+
+__global__ __launch_bounds__(256) void cfm_sess_mel_kernel(MelTab tab, const float* __restrict__ xs, int Tn, int C, float w, float lo,
+                                                           float* __restrict__ out, long long ld) {
+  __shared__ float tile[kMelTile][kMelTile + 1];
+  const int e = blockIdx.z, Tp = tab.Tp[e], len = Tn - Tp;
+  const int g0 = blockIdx.x * kMelTile, c0 = blockIdx.y * kMelTile;
+  if (g0 >= len) return;                                   // the whole block leaves: no barrier is missed
+  const float* x = xs + ((long long)tab.slot[e] * Tn + Tp) * C;
+  const int lane = threadIdx.x & (kMelTile - 1), row = threadIdx.x / kMelTile;       // 256 threads: 4 tile rows per pass
+  for (int r = row; r < kMelTile; r += 256 / kMelTile) {
+    const int g = g0 + r, c = c0 + lane;
+    if (g < len && c < C) tile[r][lane] = x[(long long)g * C + c];
+  }
+  __syncthreads();
+  float* o = out + tab.col0[e];
+  for (int r = row; r < kMelTile; r += 256 / kMelTile) {
+    const int c = c0 + r, g = g0 + lane;
+    if (c < C && g < len) {
+#pragma clang fp contract(off)
+      const float v = tile[lane][r];
+      o[(long long)c * ld + g] = ((v + 1.f) / 2.f) * w + lo;
+    }
+  }
+}
+
 int live_dit_rows(const CfmSession* ss) {
   int n = 0;
   for (const auto& sl : ss->slots) if (sl.state == SLOT_LIVE) n += sl.guided ? 2 : 1;
@@ -425,6 +458,35 @@ int gsv_cfm_session_fetch(gsv_cfm_t* c, int slot, float* out, gsv_stream_t strea
   GSV_LAUNCH(cfm_sess_out_kernel, cfm_grid((long long)ss->Tn * md), dim3(256), 0, (hipStream_t)stream,
              (const float*)(ss->xs + (size_t)slot * ss->Tn * md), sl.Tp, ss->Tn, md, out);
   sl = SessSlot{};
+  return GSV_OK;
+}
+
+int gsv_cfm_session_fetch_mel(gsv_cfm_t* c, int n, const int32_t* slots, const int* col0, long long ld, float lo, float hi, float* out,
+                              gsv_stream_t stream) {
+  GSV_REQUIRE(session_open(c), "cfm_session_fetch_mel: no open session");
+  CfmSession* ss = c->sess;
+  GSV_REQUIRE(n >= 1 && n <= ss->cap, "cfm_session_fetch_mel: n = %d is outside [1, %d]", n, ss->cap);
+  GSV_REQUIRE(slots && col0 && out, "cfm_session_fetch_mel: null argument");
+  GSV_REQUIRE(std::isfinite(lo) && std::isfinite(hi), "cfm_session_fetch_mel: lo or hi is not finite");
+  MelTab tab{};
+  int max_len = 0;
+  for (int i = 0; i < n; ++i) {
+    GSV_REQUIRE(slots[i] >= 0 && slots[i] < ss->cap, "cfm_session_fetch_mel: entry %d: slot %d is outside [0, %d)", i, slots[i], ss->cap);
+    const SessSlot& sl = ss->slots[slots[i]];
+    GSV_REQUIRE(sl.state == SLOT_DONE, "cfm_session_fetch_mel: entry %d: slot %d is %s", i, slots[i], sl.state == SLOT_LIVE ? "still live" : "free");
+    for (int a = 0; a < i; ++a) GSV_REQUIRE(slots[a] != slots[i], "cfm_session_fetch_mel: slot %d is given twice", slots[i]);
+    const int len = ss->Tn - sl.Tp;
+    GSV_REQUIRE(col0[i] >= 0 && (long long)col0[i] + len <= ld,
+                "cfm_session_fetch_mel: entry %d: columns [%d, %d + %d) do not fit a row of %lld", i, col0[i], col0[i], len, ld);
+    tab.slot[i] = slots[i]; tab.Tp[i] = sl.Tp; tab.col0[i] = col0[i];
+    max_len = std::max(max_len, len);
+  }
+  // ---- nothing was launched or changed up to here
+  const int md = c->cfg.mel_dim;
+  if (max_len > 0)
+    GSV_LAUNCH(cfm_sess_mel_kernel, dim3(nblk(max_len, kMelTile), nblk(md, kMelTile), n), dim3(256), 0, (hipStream_t)stream, tab,
+               (const float*)ss->xs, ss->Tn, md, hi - lo, lo, out, ld);
+  for (int i = 0; i < n; ++i) ss->slots[slots[i]] = SessSlot{};
   return GSV_OK;
 }
 

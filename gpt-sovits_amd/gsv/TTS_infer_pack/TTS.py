@@ -1908,7 +1908,20 @@ class TTS:
         the folds' mels go through the plan_vocoder passes of the vocoder's forward_segments, and only SOLA and the cuts stay
         per fold.  Reads `preds`, `kept`, `voice`, `opts`, `actual_seed`, `data`.  Writes `cfm_folds` (feature frames per
         batch) and `T_min` (the voice's prompt length), plan_cfm's inputs, and `frags[bi]` of every shared fold."""
-        prompts: Dict[tuple, tuple] = {}            # _prompt_features() per distinct voice
+        prompts, fold_in, voice_of = self._cfm_encode(plans)
+        if continuous_cfm:
+            fold_out = self._continuous_cfm_passes(plans, fold_in, prompts, voice_of)
+        else:
+            fold_out = self._grouped_cfm_passes(plans, fold_in, prompts, voice_of)
+        self._vocode_folds(plans, fold_in, fold_out, shared_vocoder)
+
+    def _cfm_encode(self, plans: List[dict], prompts: Optional[Dict[tuple, tuple]] = None) -> Tuple[dict, dict, list]:
+        """The first half of the shared flow-matching stage, up to the rows the DiT takes: per distinct voice (and LoRA
+        encoder) one _prompt_features(), per fold with generated tokens one _fold_chunks().  Reads `kept`, `preds`, `voice`,
+        `opts`, `data`; writes `cfm_folds` and `T_min`.  `prompts`: a cache of _prompt_features() by voice key that the
+        caller keeps between calls (gsv.serving encodes request by request); entries are added to it.
+        -> (prompts, fold_in[(r, bi)] = (rows [chunks, T_chunk, 512], lens, pad_len), voice_of[r] = r's key in prompts)"""
+        prompts = {} if prompts is None else prompts            # _prompt_features() per distinct voice
         fold_in: Dict[Tuple[int, int], tuple] = {}  # (rows [chunks, T_chunk, 512], lens, pad_len)
         voice_of: List[Optional[tuple]] = [None] * len(plans)
         for r, pl in enumerate(plans):
@@ -1933,11 +1946,7 @@ class TTS:
                                                          [ph.to(self.configs.device) for ph in item["phones"]],
                                                          pl["opts"]["speed_factor"], *([] if lora is None else [lora]))
                     pl["cfm_folds"][bi] = sum(fold_in[(r, bi)][1])
-        if continuous_cfm:
-            fold_out = self._continuous_cfm_passes(plans, fold_in, prompts, voice_of)
-        else:
-            fold_out = self._grouped_cfm_passes(plans, fold_in, prompts, voice_of)
-        self._vocode_folds(plans, fold_in, fold_out, shared_vocoder)
+        return prompts, fold_in, voice_of
 
     def _grouped_cfm_passes(self, plans: List[dict], fold_in: dict, prompts: dict, voice_of: list) -> Dict[Tuple[int, int], list]:
         """the one-shot passes of plan_cfm: one CFM.inference_rows call per pass -> fold_out[(r, bi)] = the fold's rows in order"""
@@ -2068,7 +2077,8 @@ class TTS:
 
     def serve(self, **scheduler_kw):
         """Requests as they arrive instead of a closed list: a started `gsv.serving.Server` over a `Scheduler` of this
-        pipeline (keywords: slots, chunk, admit_min, wave_hold and the shared_* flags).  `submit(request)` returns a Future of
+        pipeline (keywords: slots, chunk, admit_min, wave_hold, the shared_* flags, and on v3 / v4 continuous_cfm, cfm_rows,
+        cfm_chunk: the waveform stage as an open flow-matching session).  `submit(request)` returns a Future of
         what run_batch([request]) returns; until `shutdown()` the server's loop thread owns the pipeline."""
         from ..serving import Scheduler, Server
         return Server(Scheduler(self, **scheduler_kw))

@@ -169,6 +169,8 @@ _SIGS = {
                                         C.c_void_p]),
     "gsv_cfm_session_step": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "gsv_cfm_session_fetch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "gsv_cfm_session_fetch_mel": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.c_longlong, C.c_float,
+                                            C.c_float, C.c_void_p, C.c_void_p]),
     "gsv_cfm_session_release": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]),
     "gsv_cfm_session_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "gsv_cfm_session_end": (C.c_int, [C.c_void_p]),

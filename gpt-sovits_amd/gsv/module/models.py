@@ -689,6 +689,30 @@ class CFMSession:
             dit.stream.synchronize()
         return out
 
+    @torch.no_grad()
+    def fetch_mel(self, slots, col0, out, lo, hi):
+        """Finished rows straight into the vocoder's layout, one launch and one stream wait for all of them: the generated frames
+        [Tp, T) of slot slots[i], de-normalised as `denorm_spec` does it (((x + 1) / 2) * (hi - lo) + lo), go to columns
+        [col0[i], col0[i] + T - Tp) of `out`, a contiguous fp32 matrix [in_channels, ld] on the DiT's device (a leading dimension
+        of 1 is allowed).  The bits are those of denorm_spec(fetch(slot)[:, Tp:]).  Frees the slots.  The
+        engine refuses, before it launches anything, a slot that is not FINISHED or given twice, a negative col0 and a range
+        that does not fit `out`; the ranges are not checked against each other."""
+        dit = self.cfm.estimator
+        slots, col0 = [int(s) for s in slots], [int(c) for c in col0]
+        if len(slots) != len(col0):
+            raise ValueError(f"{len(slots)} slots, {len(col0)} columns")
+        m = out[0] if out.dim() == 3 and out.shape[0] == 1 else out
+        if m.dim() != 2 or m.shape[0] != self.cfm.in_channels or m.dtype != torch.float32 or not m.is_cuda or not m.is_contiguous():
+            raise ValueError(f"out must be a contiguous fp32 matrix [{self.cfm.in_channels}, ld] on {dit.device}")
+        n = len(slots)
+        with torch.cuda.device(dit.device):
+            dit.stream.wait_stream(torch.cuda.current_stream(dit.device))
+            _lib.check(_lib.lib().gsv_cfm_session_fetch_mel(dit._h, n, (C.c_int32 * max(1, n))(*slots), (C.c_int * max(1, n))(*col0),
+                                                            int(m.shape[1]), float(lo), float(hi),
+                                                            m.data_ptr(), C.c_void_p(dit.stream.cuda_stream)), "gsv_cfm_session_fetch_mel")
+            dit.stream.synchronize()
+        return out
+
     def release(self, slots):
         """drops live or finished rows (cancellation); the others are not touched"""
         slots = [int(s) for s in slots]

@@ -12,6 +12,13 @@
   `stats["events"]`.  Both are driven by the same `_Policy`, which holds every decision and touches no GPU.
 * `Server` puts one loop thread around a scheduler: the only thread that makes GPU calls.  `submit` returns a
   `concurrent.futures.Future` from any thread.
+* `Scheduler(continuous_cfm=True)` (v3 / v4) keeps a second session open behind the first: a flow-matching session
+  (`CFMSession`) whose rows carry their own step count, guidance rate and LoRA slot.  A request whose sentences are back is
+  encoded at once and its rows queue for the session's slots; a scheduler step runs at most `cfm_chunk` Euler steps, fetches
+  the rows that finished with one `fetch_mel` launch -- de-normalised and channels-first, the vocoder's input as it stands --
+  vocodes the folds that are complete and delivers the requests that are.  `_CfmPolicy` holds these decisions next to
+  `_Policy`, and `plan_online(cfm_folds=...)` replays them.  An exclusive request waits for both sessions and closes both.
+  AR launches, Euler steps and vocoder calls still run strictly one after the other, on the one thread.
 
 What a request returns is what `run_batch([request])` returns for it alone: its rows carry the RNG keys and sampling tuples
 `plan_batch` gives them, sampling is per row, admissions and releases leave the neighbouring slots untouched, and the waveform
@@ -113,16 +120,26 @@ class _Policy:
         self.dirty = True
         return out
 
-    def exclusive_head(self):
-        """the exclusive request to serve now, or None: it is the head of the queue and nothing is live"""
-        if self.fifo and self.fifo[0][3] and not self.live:
+    def take_ready(self) -> list:
+        """continuous_cfm: the requests whose sentences are all back, at once -- wave_hold does not apply, the flow-matching
+        session is the company a held request would have waited for"""
+        out = [req for req, _ in self.ready]
+        self.ready = []
+        if out:
+            self.dirty = True
+        return out
+
+    def exclusive_head(self, busy: bool = False):
+        """the exclusive request to serve now, or None: it is the head of the queue and nothing is live (`busy`: the
+        flow-matching session still has live or queued rows)"""
+        if self.fifo and self.fifo[0][3] and not self.live and not busy:
             self.dirty = True
             return self.fifo.popleft()[0]
         return None
 
-    def close_due(self) -> bool:
+    def close_due(self, busy: bool = False) -> bool:
         """end of a step: nothing live, nothing queued -> the decoder is handed back (once per burst)"""
-        if self.live or self.fifo or not self.dirty:
+        if self.live or self.fifo or busy or not self.dirty:
             return False
         self.open = self.dirty = False
         return True
@@ -140,16 +157,134 @@ class _Policy:
         return slots
 
 
+class _CfmPolicy:
+    """Every decision of the flow-matching session behind the decode session (`Scheduler(continuous_cfm=True)`), as host-only
+    state: the FIFO of rows that wait, the row in each slot with the Euler steps it still needs, the rows each fold still
+    misses and the folds each request still misses.  A row is (request, fold bi, chunk k) with its step count and whether it
+    is guided; a guided row is two DiT rows."""
+    TABLES = 8                 # distinct step counts among the live rows: the engine's modulation cache
+
+    def __init__(self, rows: int, chunk: int):
+        if rows < 1 or chunk < 1:
+            raise ValueError("cfm_rows and cfm_chunk must be >= 1")
+        self.rows, self.chunk = int(rows), int(chunk)
+        self.owner: List[Optional[Tuple[Any, int, int]]] = [None] * self.rows     # (request, bi, k) in each slot
+        self.left, self.steps, self.guided = [0] * self.rows, [0] * self.rows, [False] * self.rows
+        self.fifo: collections.deque = collections.deque()                     # (request, bi, k, steps, guided)
+        self.pending: Dict[Tuple[Any, int], int] = {}                          # (request, bi) -> rows not back yet
+        self.folds: Dict[Any, int] = {}                                        # request -> folds not vocoded yet
+        self.open = False
+
+    @property
+    def live(self) -> List[int]:
+        return [s for s in range(self.rows) if self.owner[s] is not None]
+
+    @property
+    def dit_rows(self) -> int:
+        return sum(2 if self.guided[s] else 1 for s in self.live)
+
+    @property
+    def busy(self) -> bool:
+        """a row is live or queued"""
+        return bool(self.fifo) or any(o is not None for o in self.owner)
+
+    def enqueue(self, req, folds: Sequence[Sequence[Tuple[int, bool]]]) -> bool:
+        """the rows of an encoded request, folds[bi] = [(steps, guided), ...] (empty: the fold has no frames), join the
+        FIFO in (bi, k) order; False: the request brings no row at all and goes straight to delivery"""
+        n = 0
+        for bi, rows in enumerate(folds):
+            for k, (steps, guided) in enumerate(rows):
+                if int(steps) < 1:
+                    raise ValueError("a row needs at least one Euler step")
+                self.fifo.append((req, bi, k, int(steps), bool(guided)))
+            if rows:
+                self.pending[(req, bi)] = len(rows)
+                n += 1
+        if n:
+            self.folds[req] = n
+        return n > 0
+
+    def admit(self) -> List[Tuple[Any, int, int, int]]:
+        """rows from the head of the FIFO into the lowest free slots while the live DiT rows fit `rows` and the distinct
+        step counts fit TABLES; the head that does not fit blocks the rows behind it.  -> [(request, bi, k, slot)]"""
+        out = []
+        while self.fifo:
+            req, bi, k, steps, guided = self.fifo[0]
+            if guided and self.rows == 1 and not self.live:       # a guided row and its twin: two DiT rows at least
+                self.rows = 2
+                self.owner, self.left, self.steps, self.guided = [None] * 2, [0] * 2, [0] * 2, [False] * 2
+            live = self.live
+            if self.dit_rows + (2 if guided else 1) > self.rows or len({self.steps[s] for s in live} | {steps}) > self.TABLES:
+                break
+            s = min(set(range(self.rows)) - set(live))             # live rows <= live DiT rows < rows: a slot is free
+            self.owner[s], self.left[s], self.steps[s], self.guided[s] = (req, bi, k), steps, steps, guided
+            self.fifo.popleft()
+            out.append((req, bi, k, s))
+        if out:
+            self.open = True
+        return out
+
+    def step(self) -> Tuple[int, List[Tuple[Tuple[Any, int, int], int]], List[Tuple[Any, int]]]:
+        """one sess.step(k) of the live rows, k = min(chunk, fewest steps a live row still needs) -> (k, the rows that
+        finished with their slots [((request, bi, k), slot)] in slot order, the folds whose rows are now all back)"""
+        live = self.live
+        k = min(self.chunk, min(self.left[s] for s in live))
+        done, folds = [], []
+        for s in live:
+            self.left[s] -= k
+            if self.left[s] == 0:
+                row = self.owner[s]
+                done.append((row, s))
+                self.owner[s] = None
+                self.pending[row[:2]] -= 1
+                if self.pending[row[:2]] == 0:
+                    del self.pending[row[:2]]
+                    folds.append(row[:2])
+        return k, done, folds
+
+    def vocoded(self, folds: Iterable[Tuple[Any, int]]) -> list:
+        """the folds went through the vocoder -> the requests whose folds are now all back, in that order"""
+        out = []
+        for req, _ in folds:
+            self.folds[req] -= 1
+            if self.folds[req] == 0:
+                del self.folds[req]
+                out.append(req)
+        return out
+
+    def cancel(self, req) -> List[int]:
+        """forgets the request; returns the slots its live rows held"""
+        self.fifo = collections.deque(e for e in self.fifo if e[0] != req)
+        self.pending = {f: n for f, n in self.pending.items() if f[0] != req}
+        self.folds.pop(req, None)
+        slots = [s for s in self.live if self.owner[s][0] == req]
+        for s in slots:
+            self.owner[s] = None
+        return slots
+
+
 def plan_online(arrivals: Sequence[int], rows_per_request: Sequence[int], lengths: Sequence[int], slots: int, chunk: int,
-                admit_min: Optional[int] = None, wave_hold: int = 0, exclusive=(), with_steps: bool = False):
+                admit_min: Optional[int] = None, wave_hold: int = 0, exclusive=(), with_steps: bool = False,
+                cfm_folds: Optional[Sequence[Sequence[Sequence[Tuple[int, bool]]]]] = None, cfm_rows: Optional[int] = None,
+                cfm_chunk: Optional[int] = None):
     """The schedule `Scheduler` follows, as a pure function.  Request r is submitted in front of step arrivals[r] (requests
     arriving in the same step keep their order) and brings rows_per_request[r] rows; `lengths` lists, request after request and
     row after row, how many further steps each row needs after its step 0 (0: it ends at its admission), as `plan_continuous`
     takes them.  The requests named in `exclusive` bring no rows (their entry of rows_per_request is not read).  Returns the
     events ("admit", [(req, row, slot), ...]), ("advance", chunk, [(req, row) reported finished, in slot order]),
     ("wave", [reqs]), ("exclusive", req) and ("close",); with_steps=True, (step, event) pairs.  With every arrival at step 0 and
-    no exclusive request the admit / advance events are `plan_continuous`'s."""
+    no exclusive request the admit / advance events are `plan_continuous`'s.
+    `cfm_folds` given (with `cfm_rows` and `cfm_chunk`): the schedule of `Scheduler(continuous_cfm=True)`.  cfm_folds[r][bi] lists
+    the flow-matching rows of request r's fold bi as (sample_steps, guided) pairs -- an empty list is a fold without frames, an
+    exclusive request's entry is not read.  No ("wave", ...) is emitted; instead, after the advance of a step: ("cfm_admit",
+    [(req, bi, k, slot), ...]), ("cfm_step", k, [(req, bi, k) finished, in slot order]), ("vocode", [(req, bi) of the folds
+    completed in this step]) and ("deliver", [reqs]): the requests without rows that became ready in this step, then those
+    whose last fold was vocoded in it.  An exclusive request waits until neither session has a live or queued row, and
+    ("close",) closes both sessions.  Without `cfm_folds` the trace is the one described above."""
     n = len(arrivals)
+    if cfm_folds is not None and (cfm_rows is None or cfm_chunk is None or len(cfm_folds) != n):
+        raise ValueError("cfm_folds needs cfm_rows, cfm_chunk and one entry per request")
+    cp = _CfmPolicy(cfm_rows, cfm_chunk) if cfm_folds is not None else None
     if len(rows_per_request) != n:
         raise ValueError(f"{len(rows_per_request)} row counts for {n} arrivals")
     excl = set(exclusive)
@@ -163,8 +298,9 @@ def plan_online(arrivals: Sequence[int], rows_per_request: Sequence[int], length
     order = sorted(range(n), key=lambda r: (int(arrivals[r]), r))
     left = [0] * pol.slots
     trace, nxt, step = [], 0, 0
-    while nxt < n or not pol.idle:
-        if pol.idle and int(arrivals[order[nxt]]) > step:
+    busy = (lambda: cp.busy) if cp is not None else (lambda: False)
+    while nxt < n or not pol.idle or busy():
+        if pol.idle and not busy() and int(arrivals[order[nxt]]) > step:
             step = int(arrivals[order[nxt]])            # nothing to do until the next arrival
         while nxt < n and int(arrivals[order[nxt]]) <= step:
             r = order[nxt]
@@ -185,19 +321,37 @@ def plan_online(arrivals: Sequence[int], rows_per_request: Sequence[int], length
                     done.append(pol.owner[s])
             trace.append((step, ("advance", pol.chunk, done)))
             pol.finish(done, step)
-        ready = pol.wave(step)
-        if ready:
-            trace.append((step, ("wave", ready)))
+        if cp is None:
+            ready = pol.wave(step)
+            if ready:
+                trace.append((step, ("wave", ready)))
+        else:
+            deliver = [r for r in pol.take_ready() if not cp.enqueue(r, cfm_folds[r])]
+            admitted = cp.admit()
+            if admitted:
+                trace.append((step, ("cfm_admit", admitted)))
+            if cp.live:
+                k, done, folds = cp.step()
+                trace.append((step, ("cfm_step", k, [row for row, _ in done])))
+                if folds:
+                    trace.append((step, ("vocode", folds)))
+                    deliver += cp.vocoded(folds)
+            if deliver:
+                trace.append((step, ("deliver", deliver)))
         while True:
-            was_open = pol.open
-            r = pol.exclusive_head()
+            was_open = pol.open or (cp is not None and cp.open)
+            r = pol.exclusive_head(busy())
             if r is None:
                 break
             if was_open:
                 pol.open = False
+                if cp is not None:
+                    cp.open = False
                 trace.append((step, ("close",)))
             trace.append((step, ("exclusive", r)))
-        if pol.close_due():
+        if pol.close_due(busy()):
+            if cp is not None:
+                cp.open = False
             trace.append((step, ("close",)))
         step += 1
     return trace if with_steps else [e for _, e in trace]
@@ -208,13 +362,24 @@ class Scheduler:
     slots: rows of the decode session (default: the decoder's max_batch); chunk: steps per advance; admit_min: as `admit_count`
     (default max(1, slots // 4)); wave_hold: steps a finished request may wait for others to share its waveform pass.
     shared_hubert / shared_bert / shared_sv / device_frontend / shared_vocoder: as `run_batch`'s keywords, applied to the
-    requests one step takes in (front-ends) and to the requests one step finishes (vocoder)."""
+    requests one step takes in (front-ends) and to the requests one step finishes (vocoder).
+    continuous_cfm (v3 / v4 only, off by default): the waveform stage is a second open session behind the first.  A request
+    whose sentences are all back is encoded at once (`TTS._cfm_encode`) and its flow-matching rows join a FIFO; every step admits
+    rows from its head into the free slots of ONE flow-matching session (`CFMSession`, per-row step count, guidance rate and
+    LoRA slot), runs min(cfm_chunk, fewest steps a live row still needs) Euler steps, fetches the rows that finished with one
+    `fetch_mel` call, vocodes the folds whose rows are all back and delivers the requests whose folds are all back.  cfm_rows:
+    the session's DiT rows (default min(tts.cfm_max_rows, 64); a guided row counts 2, and 1 is raised to 2 when a guided row
+    waits); cfm_chunk: the most Euler steps one scheduler step runs before it takes in new arrivals.  wave_hold does not apply
+    to this path: the session is the company a held request would have waited for.  Without the keyword the scheduler issues
+    exactly the launches it issued before the keyword existed."""
 
     def __init__(self, tts, slots: Optional[int] = None, chunk: int = 32, admit_min: Optional[int] = None, wave_hold: int = 0,
                  shared_hubert: bool = True, shared_bert: bool = True, shared_sv: bool = False, device_frontend: bool = False,
-                 shared_vocoder: bool = False):
+                 shared_vocoder: bool = False, continuous_cfm: bool = False, cfm_rows: Optional[int] = None, cfm_chunk: int = 2):
         if tts.t2s_model is None or tts.vits_model is None:
             raise RuntimeError("init_t2s_weights / init_vits_weights first")
+        if continuous_cfm and not getattr(tts.configs, "use_vocoder", False):
+            raise ValueError("continuous_cfm=True is the flow-matching stage of v3 / v4: this model has no vocoder")
         if device_frontend and not (shared_hubert or shared_sv):
             raise ValueError("device_frontend=True is the front-end of the shared make_voices call: pass shared_hubert=True or shared_sv=True too")
         self.tts = tts
@@ -225,6 +390,15 @@ class Scheduler:
         self._front = dict(shared_hubert=bool(shared_hubert), shared_bert=bool(shared_bert), shared_sv=bool(shared_sv),
                            device_frontend=bool(device_frontend))
         self._shared_vocoder = bool(shared_vocoder)
+        self._cpol: Optional[_CfmPolicy] = None
+        if continuous_cfm:
+            from ._lib import CFM_SESSION_MAX_ROWS
+            self._cpol = _CfmPolicy(min(int(tts.cfm_max_rows), CFM_SESSION_MAX_ROWS) if cfm_rows is None else int(cfm_rows), cfm_chunk)
+            if self._cpol.rows > CFM_SESSION_MAX_ROWS:
+                raise ValueError(f"cfm_rows {self._cpol.rows}: a flow-matching session holds at most {CFM_SESSION_MAX_ROWS} DiT rows")
+        self._cfm = None                            # the open CFMSession
+        self._cfm_req: Dict[int, dict] = {}         # ticket -> dict(vk, fold_in {bi: (rows, lens, pad_len)}, mel {bi: packed mel})
+        self._cfm_prompts: Dict[tuple, tuple] = {}  # _prompt_features() of the voices of the requests in _cfm_req
         self._inbox: List[Tuple[int, dict]] = []
         self._requests: Dict[int, dict] = {}        # ticket -> request (exclusive) or plan (session), until delivered
         self._rows: Dict[int, List[dict]] = {}      # ticket -> its rows in queue order: dict(bi, j, key, sampling)
@@ -236,6 +410,9 @@ class Scheduler:
         self.sessions: list = []                    # every closed T2SSession, in order (history, modes, adopt times)
         self.stats: Dict[str, Any] = dict(steps=0, admissions=0, rows=0, advances=0, waves=0, exclusive=0, sessions=0, released=0,
                                           occupancy=[], events=[], tickets={})
+        if continuous_cfm:                          # admissions, rows, Euler steps, live DiT rows per step call, vocoder calls, and
+            self.stats.update(cfm_admissions=0, cfm_rows=0, cfm_steps=0, cfm_occupancy=[], vocoder_calls=0, cfm_sessions=0,
+                              cfm_released=0, cfm_folds={})     # per ticket the rows per fold as plan_online takes them
 
     # -- public
     def __enter__(self):
@@ -247,7 +424,7 @@ class Scheduler:
 
     @property
     def idle(self) -> bool:
-        return not self._inbox and not self._done and self._pol.idle
+        return not self._inbox and not self._done and self._pol.idle and not (self._cpol is not None and self._cpol.busy)
 
     def submit(self, request: dict) -> int:
         """enqueues the request (the dict `run_batch` takes) for the next step; returns its ticket.  No GPU work."""
@@ -260,8 +437,9 @@ class Scheduler:
         return t
 
     def cancel(self, ticket: int) -> bool:
-        """drops the request's queued rows and releases its live ones; its result, returned by the next step, is
-        CancelledError.  False if the ticket is not outstanding (unknown, or delivered)."""
+        """drops the request's queued rows and releases its live ones -- in the decode session and, continuous_cfm, in the
+        flow-matching session, with its partial fold buffers and its voice's cached prompt features; its result, returned by
+        the next step, is CancelledError.  False if the ticket is not outstanding (unknown, or delivered)."""
         if any(t == ticket for t, _ in self._inbox):
             self._inbox = [(t, r) for t, r in self._inbox if t != ticket]
         elif ticket in self._requests:
@@ -271,6 +449,7 @@ class Scheduler:
                 self.stats["released"] += len(slots)
                 self.stats["events"].append(("release", slots))
             self._where = {k: v for k, v in self._where.items() if v[0] != ticket}
+            self._drop_cfm(ticket)
             self._requests.pop(ticket)
             self._rows.pop(ticket, None)
         else:
@@ -279,7 +458,7 @@ class Scheduler:
         return True
 
     def close(self) -> None:
-        """drops what is outstanding (no step will return it) and closes the session: `tts.run` / `run_batch` work again"""
+        """drops what is outstanding (no step will return it) and closes the sessions: `tts.run` / `run_batch` work again"""
         for t in [t for t, _ in self._inbox] + list(self._requests):
             self.cancel(t)
         self._done = []
@@ -287,7 +466,8 @@ class Scheduler:
         self._closed = True
 
     def step(self) -> List[Tuple[int, Any]]:
-        """One round: intake, admit, advance, finish, exclusive requests, close when idle (module docstring).  Returns the
+        """One round: intake, admit, advance, finish (continuous_cfm: encode, flow-matching admit, step, fetch, vocode,
+        deliver), exclusive requests, close when idle (module docstring).  Returns the
         (ticket, result) pairs of the requests that ended in it; a result is (sr, int16 audio), the list of fragments of a
         `return_fragment` request, or the exception the request raised."""
         import torch
@@ -315,14 +495,19 @@ class Scheduler:
             self.stats["advances"] += 1
             ev.append(("advance", pol.chunk, done))
             pol.finish(done, step)
-        ready = pol.wave(step)
-        if ready:
-            ev.append(("wave", ready))
-            self.stats["waves"] += 1
-            self._wave(ready, out)
+        cp = self._cpol
+        if cp is None:
+            ready = pol.wave(step)
+            if ready:
+                ev.append(("wave", ready))
+                self.stats["waves"] += 1
+                self._wave(ready, out)
+        else:
+            self._cfm_round(out)
+        busy = cp is not None and cp.busy
         while True:
-            was_open = pol.open
-            t = pol.exclusive_head()
+            was_open = pol.open or (cp is not None and cp.open)
+            t = pol.exclusive_head(busy)
             if t is None:
                 break
             if was_open:
@@ -332,7 +517,7 @@ class Scheduler:
             ev.append(("exclusive", t))
             self.stats["exclusive"] += 1
             self._exclusive(t, out)
-        if pol.close_due():
+        if pol.close_due(busy):
             self._close_session()
             ev.append(("close",))
         for t, _ in out:
@@ -457,12 +642,195 @@ class Scheduler:
         except Exception as e:                                          # noqa: BLE001 -- the request's own result
             out.append((t, e))
 
+    # -- continuous_cfm: the second session (class docstring)
+    def _cfm_round(self, out: list) -> None:
+        """stages 2-6 of a continuous_cfm step: encode the ready requests, admit rows, one session step, one fetch, vocode the
+        completed folds, deliver the completed requests.  A stage that raises fails the requests it was working on."""
+        pol, cp, ev, st = self._pol, self._cpol, self.stats["events"], self.stats
+        deliver = [t for t in pol.take_ready() if not self._encode(t, out)]
+        admitted = cp.admit()
+        if admitted:
+            ev.append(("cfm_admit", admitted))
+            self._cfm_admit(admitted, out)
+        if cp.live:
+            st["cfm_occupancy"].append(cp.dit_rows)
+            holders = sorted({cp.owner[s][0] for s in cp.live})
+            k, done, folds = cp.step()
+            ev.append(("cfm_step", k, [row for row, _ in done]))
+            try:
+                finished = self._cfm.step(k)
+                assert finished == sorted(s for _, s in done), f"the session reports slots {finished}, the policy {done}"
+                st["cfm_steps"] += k
+                staged = self._fetch(done) if done else {}
+            except Exception as e:                                      # noqa: BLE001 -- every request with a live row
+                self._close_cfm()                                       # the session goes; queued rows open the next one
+                self._fail(holders, e, out)
+                folds = []
+            if folds:
+                ev.append(("vocode", folds))
+                deliver += self._vocode(folds, staged, out)
+        deliver = [t for t in deliver if t in self._requests]           # a failed stage has answered for the others
+        if deliver:
+            ev.append(("deliver", deliver))
+            tts = self.tts
+            for t in deliver:
+                pl = self._requests.pop(t)
+                self._rows.pop(t, None)
+                self._drop_cfm(t)
+                try:
+                    tts._wait_stream()
+                    out.append((t, tts._finish_request(pl, tts._output_sr())))
+                except Exception as e:                                  # noqa: BLE001 -- the request's own result
+                    out.append((t, e))
+
+    def _encode(self, t: int, out: list) -> bool:
+        """the first half of the shared flow-matching stage for one request; its rows join the FIFO.  False: it has no row"""
+        tts, pl = self.tts, self._requests[t]
+        try:
+            pl["kept"] = [tts._kept_tokens(p, i, pl["no_prompt"]) for p, i in zip(pl["preds"], pl["idxs"])]
+            tts._wait_stream()
+            _, fold_in, voice_of = tts._cfm_encode([pl], self._cfm_prompts)
+            folds: List[List[Tuple[int, bool]]] = [[] for _ in pl["data"]]
+            for (_, bi, _), steps, rate in tts.plan_cfm_rows([pl]):
+                folds[bi].append((steps, rate > 0.0))
+            self._cfm_req[t] = dict(vk=voice_of[0], fold_in={bi: v for (_, bi), v in fold_in.items()}, mel={})
+            self.stats["cfm_folds"][t] = folds
+            return self._cpol.enqueue(t, folds)
+        except Exception as e:                                          # noqa: BLE001 -- the request's own result
+            self._fail([t], e, out)
+            return True
+
+    def _cfm_admit(self, admitted: List[Tuple[int, int, int, int]], out: list) -> None:
+        from .module.models import CFM
+        tts, cp = self.tts, self._cpol
+        try:
+            import torch
+            rows = [(self._requests[t], self._cfm_req[t], bi, k) for t, bi, k, _ in admitted]
+            mu = torch.cat([c["fold_in"][bi][0][k:k + 1] for _, c, bi, k in rows], 0)
+            if self._cfm is not None and self._cfm.rows_cap != cp.rows:      # 1 raised to 2 for a guided row: nothing is live
+                self._close_cfm()
+            if self._cfm is None:
+                self._cfm = tts.vits_model.cfm.open_session(cp.rows, int(mu.shape[1]))
+                self.stats["cfm_sessions"] += 1
+            names = [pl["opts"].get("lora_voice") for pl, _, _, _ in rows]
+            rates = [float(pl["opts"].get("inference_cfg_rate", 0)) for pl, _, _, _ in rows]
+            guided = [cp.guided[s] for _, _, _, s in admitted]
+            self._cfm.admit(mu, [self._cfm_prompts[c["vk"]][3] for _, c, _, _ in rows], [int(pl["opts"]["sample_steps"]) for pl, _, _, _ in rows],
+                            [r if g else 0.0 for r, g in zip(rates, guided)],
+                            seeds=[CFM.row_seed(pl["actual_seed"] + bi, k) for pl, _, bi, k in rows],
+                            adapters=[None if n is None else tts._lora_voice(n)[1] for n in names] if any(names) else None,
+                            slots=[s for _, _, _, s in admitted])
+            self.stats["cfm_admissions"] += 1
+            self.stats["cfm_rows"] += len(admitted)
+        except Exception as e:                                          # noqa: BLE001 -- the rows of this admission
+            self._fail(sorted({t for t, _, _, _ in admitted}), e, out)
+
+    def _fetch(self, done: list) -> Dict[Tuple[int, int], Any]:
+        """ONE fetch_mel call for the slots that finished in this step, into a matrix of this step [mel][sum of the rows' frames]
+        in (request, bi, k) order -- so the rows of a fold that finished together are its packed mel [mel][chunks * chunk_len],
+        _fold_mel's layout, as they stand.  A fold whose rows come back in several steps is put together in a buffer of its own.
+        -> {(request, bi): the packed mel [1, mel, chunks * chunk_len] of every fold that is complete}"""
+        import torch
+        from .TTS_infer_pack.TTS import spec_max, spec_min
+        sess = self._cfm
+        order = sorted(done)                                            # ((t, bi, k), slot)
+        lens = [sess.T - int(self._cfm_prompts[self._cfm_req[t]["vk"]][3].shape[2]) for (t, _, _), _ in order]
+        col0 = [sum(lens[:i]) for i in range(len(order))]
+        stage = torch.empty(sess.cfm.in_channels, sum(lens), dtype=torch.float32, device=sess.cfm.estimator.device)
+        sess.fetch_mel([s for _, s in order], col0, stage, spec_min, spec_max)
+        got: Dict[Tuple[int, int], Any] = {}
+        i = 0
+        while i < len(order):
+            (t, bi, _), _ = order[i]
+            j = i
+            while j < len(order) and order[j][0][:2] == (t, bi):
+                j += 1
+            c = self._cfm_req[t]
+            chunks, L = int(c["fold_in"][bi][0].shape[0]), lens[i]
+            if j - i == chunks and bi not in c["mel"]:                  # the whole fold in this step: a column range of `stage`
+                got[(t, bi)] = stage[:, col0[i]:col0[i] + chunks * L].unsqueeze(0)
+            else:
+                buf = c["mel"].setdefault(bi, [0, torch.empty(1, stage.shape[0], chunks * L, dtype=torch.float32, device=stage.device)])
+                for n in range(i, j):
+                    k = order[n][0][2]
+                    buf[1][0, :, k * L:(k + 1) * L] = stage[:, col0[n]:col0[n] + L]
+                buf[0] += j - i
+                if buf[0] == chunks:
+                    got[(t, bi)] = c["mel"].pop(bi)[1]
+            i = j
+        return got
+
+    def _vocode(self, folds: List[Tuple[int, int]], staged: dict, out: list) -> List[int]:
+        """the completed folds through the vocoder -- one forward_segments pass (at most vocoder_max_frames frames each) when
+        shared_vocoder, one call per fold otherwise -- and _fold_tail -> the requests whose folds are now all back"""
+        import torch
+        tts = self.tts
+        calls: List[List[Tuple[int, int]]] = []
+        frames = 0
+        for f in folds:
+            n = int(staged[f].shape[2])
+            if not calls or not self._shared_vocoder or frames + n > int(tts.vocoder_max_frames):
+                calls.append([])
+                frames = 0
+            calls[-1].append(f)
+            frames += n
+        for call in calls:
+            try:
+                mels = []
+                for t, bi in call:
+                    dt = self._cfm_req[t]["fold_in"][bi][0].dtype       # the dtype _fold_mel hands the vocoder in run_batch
+                    mels.append(staged[(t, bi)].to(dt if dt in (torch.float16, torch.float32) else torch.float32).contiguous())
+                if self._shared_vocoder:
+                    audios = [a[0][0] for a in tts.vocoder.forward_segments(mels)]
+                else:
+                    audios = [tts.vocoder(m)[0][0] for m in mels]
+                self.stats["vocoder_calls"] += 1 if self._shared_vocoder else len(mels)
+                for (t, bi), m, audio in zip(call, mels, audios):
+                    rows, lens, pad_len = self._cfm_req[t]["fold_in"][bi]
+                    self._requests[t]["frags"][bi] = tts._fold_tail(audio, int(m.shape[2]) // int(rows.shape[0]), lens, pad_len)
+            except Exception as e:                                      # noqa: BLE001 -- the folds of this vocoder call
+                self._fail(sorted({t for t, _ in call}), e, out)
+        return self._cpol.vocoded(f for f in folds if f[0] in self._requests)
+
+    def _fail(self, tickets: Iterable[int], exc: BaseException, out: list) -> None:
+        """the requests get `exc` as their result; their rows, slots and buffers are dropped"""
+        for t in tickets:
+            if t in self._requests:
+                self._drop_cfm(t)
+                self._requests.pop(t)
+                self._rows.pop(t, None)
+                out.append((t, exc))
+
+    def _drop_cfm(self, t: int) -> None:
+        """forgets the request's flow-matching state: queued rows, live slots (released), fold buffers and, when no other
+        request speaks with it, its voice's cached prompt features"""
+        if self._cpol is None:
+            return
+        slots = self._cpol.cancel(t)
+        if slots and self._cfm is not None:
+            self._cfm.release(slots)
+            self.stats["cfm_released"] += len(slots)
+            self.stats["events"].append(("cfm_release", slots))
+        c = self._cfm_req.pop(t, None)
+        if c is not None and all(o["vk"] != c["vk"] for o in self._cfm_req.values()):
+            self._cfm_prompts.pop(c["vk"], None)
+
+    def _close_cfm(self) -> None:
+        if self._cfm is not None:
+            try:
+                self._cfm.close()
+            finally:
+                self._cfm = None
+        if self._cpol is not None:
+            self._cpol.open = False
+
     def _close_session(self) -> None:
         if self._ses is not None:
             self._ses.close()
             self.sessions.append(self._ses)
             self._ses = None
         self._pol.open = False
+        self._close_cfm()
 
 
 class Server:

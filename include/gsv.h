@@ -434,6 +434,14 @@ int gsv_cfm_inference_adapted(gsv_cfm_t* h, const float* mu, const float* const*
  *   n_steps_b steps.  The DiT of one step runs over the live rows in ascending slot order, then the twins of the guided ones in
  *   the same order; free and finished slots cost nothing.  Returns at once when no row is live.
  * fetch: a finished row as out [dev] fp32 [mel_dim][T], its prompt frames zero; frees the slot.  A live or free slot is an error.
+ * fetch_mel: n finished rows (slots [host] n distinct ints, 1 <= n <= rows_cap) in ONE launch, straight into the layout the
+ *   vocoder reads: entry i writes the generated frames t in [Tp_i, T) of slot slots[i] -- Tp_i the prompt length recorded at
+ *   admission -- de-normalised, ((x + 1) / 2) * (hi - lo) + lo in that order and uncontracted, channels-first, to columns
+ *   [col0[i], col0[i] + T - Tp_i) of out [dev] fp32 [mel_dim][ld] (col0 [host] n ints).  The bits are those of
+ *   denorm_spec(fetch(slot)[:, Tp_i:]).  The [T][mel] -> [mel][T] transpose goes through an LDS tile, so a wave reads and writes
+ *   contiguously.  Frees the slots, as fetch does.  Refused, before anything is launched and with every slot left as it was: a
+ *   slot that is not finished, a repeated slot, n outside [1, rows_cap], a null pointer, col0[i] < 0, col0[i] + T - Tp_i > ld.
+ *   The destination ranges are NOT checked against each other: entries whose column ranges overlap race, the caller keeps them apart.
  * release: drops live or finished rows; the others are not touched.
  * gsv_cfm_adapter_remove refuses a slot that a live row of the open session still runs with.
  * state: [host] int32 [3][rows_cap] = 0 free / 1 live / 2 finished | steps taken | n_steps.  Host bookkeeping, no device wait.
@@ -445,6 +453,8 @@ int gsv_cfm_session_admit(gsv_cfm_t* h, int n, const int32_t* slots, const float
                           const uint64_t* seeds, gsv_stream_t stream);
 int gsv_cfm_session_step(gsv_cfm_t* h, int k, gsv_stream_t stream);
 int gsv_cfm_session_fetch(gsv_cfm_t* h, int slot, float* out, gsv_stream_t stream);
+int gsv_cfm_session_fetch_mel(gsv_cfm_t* h, int n, const int32_t* slots, const int* col0, long long ld, float lo, float hi,
+                              float* out, gsv_stream_t stream);
 int gsv_cfm_session_release(gsv_cfm_t* h, int n, const int32_t* slots);
 int gsv_cfm_session_state(gsv_cfm_t* h, int32_t* state);
 int gsv_cfm_session_end(gsv_cfm_t* h);

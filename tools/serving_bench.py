@@ -12,6 +12,16 @@ delivered audio-seconds per second, and for (C) the mean slot occupancy and the 
 
     python tools/serving_bench.py [--requests 96] [--voices 32] [--slots 32] [--loads 0.3,0.6,0.9] [--windows-ms 10,40]
                                   [--chunks 8,32] [--admit-mins 1,8] [--wave-holds 0,2] [--repeats 7]
+
+--version v3 | v4: the full-size synthetic v3 / v4 pipeline instead (DiT 1024 x 22, BigVGAN-v2 / the v4 HiFi-GAN), every voice with
+its own prompt mel, --sample-steps (comma list, dealt round-robin to the requests).  The closed batch and (B) are
+run_batch(shared_cfm=True), (A) is left out, (C) is Server() with the settings above -- the waveform stage as closed
+_shared_cfm_stage passes -- and (D) is Server(continuous_cfm=True) for every --cfm-chunks x --cfm-rows at the first (C) setting:
+the waveform stage as an open flow-matching session.  --handoff prints, before the replays, the device time of
+CFMSession.fetch_mel for 1 / 8 / 32 finished rows of T_chunk frames against the per-slot fetch + slice + denorm_spec + cat it
+replaces, next to the byte floor 2 * rows * (T - Tp) * 100 * 4 B.
+
+    python tools/serving_bench.py --version v3 --sample-steps 8,16,32 [--cfm-chunks 1,2,4,8] [--cfm-rows 16,32,64] [--handoff]
 """
 import argparse
 import json
@@ -67,27 +77,49 @@ def main():
     ap.add_argument("--wave-holds", default="0,2")
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--version", default="v2", choices=["v2", "v3", "v4"])
+    ap.add_argument("--sample-steps", default="32", help="v3 / v4: comma list, dealt round-robin to the requests")
+    ap.add_argument("--cfm-chunks", default="1,2,4,8")
+    ap.add_argument("--cfm-rows", default="16,32,64")
+    ap.add_argument("--handoff", action="store_true", help="v3 / v4: time fetch_mel against the per-slot hand-off first")
     a = ap.parse_args()
     from bench import build_tts, make_segments
     from gsv import synthetic as S
     dev = torch.device("cuda:0")
     N, TOK = a.requests, a.tokens
-    tts = build_tts(dev, TOK, a.slots, dtype_half=True)
-    tts.configs.max_seq = 80 + 160 + TOK + 16          # room for the longest voice's prompt
-    tts.t2s_model = None
-    tts.init_t2s_weights(tts.configs.t2s_weights_path, state=tts._t2s_state)
+    v3 = a.version != "v2"
+    shared = dict(shared_cfm=True) if v3 else dict(shared_sovits=True)
+    if v3:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        from multivoice_v3_bench import build_v3
+        tts = build_v3(dev, TOK, a.slots)
+        if a.version == "v4":
+            tts.configs.version = "v4"
+            tts.init_vocoder("v4", state={"weight": S.make_vocoder_state_dict(dict(S.HIFIGAN_V4_CONFIG), seed=4),
+                                          "config": dict(S.HIFIGAN_V4_CONFIG)})
+        if a.handoff:
+            handoff(tts, dev)
+    else:
+        tts = build_tts(dev, TOK, a.slots, dtype_half=True)
+        tts.configs.max_seq = 80 + 160 + TOK + 16          # room for the longest voice's prompt
+        tts.t2s_model = None
+        tts.init_t2s_weights(tts.configs.t2s_weights_path, state=tts._t2s_state)
     rng = random.Random(a.seed)
     counts = [rng.randint(1, 4) for _ in range(N)]
     utt, segs = make_segments(sum(counts))
     n_ph = len(utt["prompt_phones"])
+    mel_kw = (lambda i: dict(ref_mel=S.hash_symmetric(f"sv_mel{i}", (1, 100, 200 + (i * 53) % 400), 5.0, 3) - 5.0)) if v3 else (lambda i: {})
     voices = [tts.make_voice(torch.from_numpy(S.hash_ints(f"sv_sem{i}", 60 + (i * 37) % 100, 1024, 1)),
                              [S.make_refer_spec(frames=150 + 7 * i, seed=100 + i).to(dev).half()],
                              phones=S.hash_ints(f"sv_ph{i}", n_ph, 732, 1).tolist(), bert_features=torch.zeros(1024, n_ph),
-                             norm_text="x" * n_ph) for i in range(a.voices)]
+                             norm_text="x" * n_ph, **mel_kw(i)) for i in range(a.voices)]
     params = dict(top_k=15, top_p=1.0, temperature=1.0, repetition_penalty=1.35, fragment_interval=0.01)
     reqs, at = [], 0
     for i, c in enumerate(counts):
         reqs.append(dict(params, segments=segs[at:at + c], batch_size=c, seed=7 + i, voice=voices[i % a.voices]))
+        if v3:
+            steps = [int(x) for x in a.sample_steps.split(",") if x]
+            reqs[-1]["sample_steps"] = steps[i % len(steps)]
         at += c
 
     def alone(r):
@@ -100,13 +132,14 @@ def main():
     for _ in range(2):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        outs = tts.run_batch(reqs, shared_sovits=True)
+        outs = tts.run_batch(reqs, **shared)
         torch.cuda.synchronize()
         closed_s = time.perf_counter() - t0
     audio_s = [w.shape[0] / sr for sr, w in outs]
     capacity = sum(audio_s) / closed_s
-    alone(reqs[0])
-    print(json.dumps(dict(record="closed_batch", requests=N, sentences=sum(counts), audio_s=round(sum(audio_s), 1),
+    if not v3:
+        alone(reqs[0])
+    print(json.dumps(dict(record="closed_batch", version=a.version, requests=N, sentences=sum(counts), audio_s=round(sum(audio_s), 1),
                           seconds=round(closed_s, 4), audio_s_per_s=round(capacity, 1))), flush=True)
 
     def trace(load, rep):
@@ -145,7 +178,7 @@ def main():
                         batch.append(q.get(timeout=max(0.0, end - time.perf_counter())))
                     except queue.Empty:
                         break
-                tts.run_batch([reqs[i] for i in batch], shared_sovits=True)
+                tts.run_batch([reqs[i] for i in batch], **shared)
                 now = time.perf_counter()
                 for i in batch:
                     done_at[i] = now
@@ -173,18 +206,60 @@ def main():
         out.update(occupancy=round(statistics.mean(st["occupancy"]) / a.slots, 3) if st["occupancy"] else 0.0,
                    waves_per_s=round(st["waves"] / span, 1), advances=st["advances"], admissions=st["admissions"],
                    sessions=st["sessions"])
+        if kw.get("continuous_cfm"):
+            out.update(cfm_live_dit_rows=round(statistics.mean(st["cfm_occupancy"]), 2) if st["cfm_occupancy"] else 0.0,
+                       cfm_euler_steps=st["cfm_steps"], cfm_admissions=st["cfm_admissions"], vocoder_calls=st["vocoder_calls"])
         return out
 
-    settings = [("A", "run() per request", serve_a, {})]
+    settings = [] if v3 else [("A", "run() per request", serve_a, {})]
     settings += [("B", f"window {w} ms", serve_b, dict(window=float(w) / 1e3)) for w in a.windows_ms.split(",") if w]
     settings += [("C", f"chunk {c} admit_min {m} wave_hold {h}", serve_c, dict(chunk=int(c), admit_min=int(m), wave_hold=int(h)))
                  for c in a.chunks.split(",") if c for m in a.admit_mins.split(",") if m for h in a.wave_holds.split(",") if h]
+    if v3:
+        first = dict(next((kw for kind, _, _, kw in settings if kind == "C"), {}))
+        settings += [("D", f"continuous_cfm cfm_chunk {k} cfm_rows {r} ({' '.join(f'{x} {y}' for x, y in first.items())})", serve_c,
+                      dict(first, continuous_cfm=True, cfm_chunk=int(k), cfm_rows=int(r)))
+                     for k in a.cfm_chunks.split(",") if k for r in a.cfm_rows.split(",") if r]
     for load in [float(x) for x in a.loads.split(",") if x]:
         for kind, name, fn, kw in settings:
             runs = [fn(trace(load, rep), **kw) for rep in range(a.repeats)]
             med = {k: statistics.median(r[k] for r in runs) for k in runs[0]}
             print(json.dumps(dict(record="serve", server=kind, setting=name, load=load, repeats=a.repeats, **med)), flush=True)
     print(json.dumps(dict(record="engine", fallbacks=tts.t2s_model.engine_stats()[1])), flush=True)
+
+
+def handoff(tts, dev):
+    """device time of fetch_mel for 1 / 8 / 32 finished rows of T_chunk frames (Tp = 468) against the hand-off it replaces"""
+    from gsv import synthetic as S
+    from gsv.TTS_infer_pack.TTS import denorm_spec, spec_max, spec_min
+    cfm, T, Tp = tts.vits_model.cfm, tts.vocoder_configs["T_chunk"], 468
+    for B in (1, 8, 32):
+        mu = S.hash_symmetric("ho_mu", (B, T, 512), 1.0, B).to(dev).half()
+        pr = [S.hash_symmetric("ho_p", (1, 100, Tp), 1.0, b).to(dev).half() for b in range(B)]
+        L = T - Tp
+        out = torch.empty(100, B * L, dtype=torch.float32, device=dev)
+        ms = {"fetch_mel": [], "per_slot": []}
+        for it in range(8):
+            for mode in ms:
+                with cfm.open_session(B, T) as s:
+                    slots = s.admit(mu, pr, 1, 0.0, seeds=list(range(1, B + 1)))
+                    s.step(1)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    e0.record()
+                    if mode == "fetch_mel":
+                        s.fetch_mel(slots, [b * L for b in range(B)], out, spec_min, spec_max)
+                    else:
+                        pred = torch.stack([s.fetch(sl)[:, Tp:] for sl in slots])
+                        denorm_spec(pred.permute(1, 0, 2).contiguous().view(100, -1).unsqueeze(0))
+                    e1.record()
+                    torch.cuda.synchronize()
+                    if it:
+                        ms[mode].append(e0.elapsed_time(e1))
+        floor_bytes = 2 * B * L * 100 * 4
+        print(json.dumps(dict(record="handoff", rows=B, T=T, Tp=Tp, fetch_mel_ms=round(statistics.median(ms["fetch_mel"]), 4),
+                              per_slot_ms=round(statistics.median(ms["per_slot"]), 4), floor_bytes=floor_bytes,
+                              floor_us_at_6p3_TBps=round(floor_bytes / 6.3e12 * 1e6, 3))), flush=True)
 
 
 if __name__ == "__main__":

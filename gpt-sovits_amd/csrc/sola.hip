@@ -135,6 +135,126 @@ __global__ __launch_bounds__(1024) void postprocess_kernel(PostTable tab, int ga
   for (int i = threadIdx.x; i < gap; i += 1024) o[n + i] = (O)0;
 }
 
+// ---- gsv_postprocess_groups: the same arithmetic, tiled ----------------------------------------------------------------
+// A server step hands over the fragments of several requests at once: n sentences in groups, each group with its own gap.
+// Every sentence is cut into tiles of kGroupTile samples (an empty sentence keeps one tile, which writes its gap), one
+// workgroup per tile, so one long sentence is spread over many CUs.  Two launches: the first reduces each tile's peak and
+// combines the tiles of a sentence with an atomic max on the bit pattern of |x| -- order-preserving for non-negative floats,
+// and a NaN (> 0x7f800000) outranks every number, so the one word carries the NaN flag too; the second converts and writes.
+// The table (sentences, then tiles) is filled on the host, uploaded with one copy and read from device memory.
+constexpr int kGroupTile = 4096;
+struct GroupSent {
+  const void* src;
+  long long dst;       // first output sample
+  int len, gap;
+  unsigned peak;       // max over the sentence of the bits of |x|; uploaded as 0
+  int pad;
+};
+struct GroupTile { int sent, start; };
+static_assert(sizeof(GroupSent) == 32 && sizeof(GroupTile) == 8, "table layout");
+
+template <typename T> struct GroupVec;
+template <> struct GroupVec<float> { typedef float type __attribute__((ext_vector_type(4))); };
+template <> struct GroupVec<_Float16> { typedef _Float16 type __attribute__((ext_vector_type(8))); };
+typedef short short8_t __attribute__((ext_vector_type(8)));
+
+template <typename T>
+__device__ __forceinline__ unsigned abs_bits(T v) { return __float_as_uint(fabsf((float)v)); }
+
+// elements from p to the next 16-byte boundary (p is element-aligned), at most n
+template <typename T>
+__device__ __forceinline__ int head_count(const T* p, int n) {
+  const int h = (int)(((16u - (unsigned)((size_t)p & 15u)) & 15u) / sizeof(T));
+  return h < n ? h : n;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void post_groups_peak_kernel(GroupSent* __restrict__ sent, const GroupTile* __restrict__ tiles) {
+  typedef typename GroupVec<T>::type V;
+  constexpr int E = 16 / sizeof(T);
+  __shared__ unsigned red[4];
+  const GroupTile t = tiles[blockIdx.x];
+  const T* __restrict__ x = (const T*)sent[t.sent].src + t.start;
+  const int left = sent[t.sent].len - t.start, n = left < kGroupTile ? left : kGroupTile;
+  const int tid = threadIdx.x;
+  unsigned m = 0;
+  const int head = head_count(x, n);                            // the loads of the body are 16-byte aligned
+  if (tid < head) m = abs_bits(x[tid]);
+  const int body = (n - head) / E;
+  const V* __restrict__ xv = (const V*)(x + head);
+  for (int i = tid; i < body; i += 256) {
+    const V v = xv[i];
+#pragma unroll
+    for (int k = 0; k < E; ++k) { const unsigned b = abs_bits((T)v[k]); m = b > m ? b : m; }
+  }
+  const int tail = head + body * E;
+  if (tail + tid < n) { const unsigned b = abs_bits(x[tail + tid]); m = b > m ? b : m; }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { const unsigned b = (unsigned)__shfl_xor((int)m, o, 64); m = b > m ? b : m; }
+  if ((tid & 63) == 0) red[tid >> 6] = m;
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 4; ++w) m = red[w] > m ? red[w] : m;
+    if (m) atomicMax(&sent[t.sent].peak, m);
+  }
+}
+
+// zeros into o[0..n), 16-byte stores where o allows
+__device__ __forceinline__ void zero_fill(short* __restrict__ o, int n, int tid) {
+  const int head = head_count(o, n);
+  if (tid < head) o[tid] = 0;
+  const int body = (n - head) / 8;
+  short8_t* __restrict__ ov = (short8_t*)(o + head);
+  const short8_t z = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = tid; i < body; i += 256) ov[i] = z;
+  const int tail = head + body * 8;
+  if (tail + tid < n) o[tail + tid] = 0;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void post_groups_write_kernel(const GroupSent* __restrict__ sent, const GroupTile* __restrict__ tiles,
+                                                                short* __restrict__ out) {
+  typedef typename GroupVec<T>::type V;
+  const GroupTile t = tiles[blockIdx.x];
+  const GroupSent S = sent[t.sent];
+  const T* __restrict__ x = (const T*)S.src + t.start;
+  short* __restrict__ o = out + S.dst + t.start;
+  const int left = S.len - t.start, n = left < kGroupTile ? left : kGroupTile;
+  const int tid = threadIdx.x;
+  const bool divide = S.peak > 0x3f800000u && S.peak <= 0x7f800000u;     // peak > 1 and no NaN
+  const T denom = (T)__uint_as_float(S.peak);                            // exact: the peak is one of the sentence's values
+  auto pcm = [&](T v) -> short {                                         // postprocess_kernel's arithmetic, in T
+    if (divide) v = (T)((float)v / (float)denom);
+    const T m = (T)((float)v * 32768.f);
+    return (short)(int)(float)m;
+  };
+  // the stores of the body are 16-byte aligned; its loads are aligned to the element only (a torch.split view)
+  const int head = head_count(o, n);
+  if (tid < head) o[tid] = pcm(x[tid]);
+  const int body = (n - head) / 8;
+  short8_t* __restrict__ ov = (short8_t*)(o + head);
+  for (int i = tid; i < body; i += 256) {
+    const T* p = x + head + 8 * i;
+    short8_t r;
+    if constexpr (sizeof(T) == 2) {
+      V v;
+      __builtin_memcpy(&v, p, 16);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) r[k] = pcm((T)v[k]);
+    } else {
+      V v0, v1;
+      __builtin_memcpy(&v0, p, 16);
+      __builtin_memcpy(&v1, p + 4, 16);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { r[k] = pcm((T)v0[k]); r[4 + k] = pcm((T)v1[k]); }
+    }
+    ov[i] = r;
+  }
+  const int tail = head + body * 8;
+  if (tail + tid < n) o[tail + tid] = pcm(x[tail + tid]);
+  if (left <= kGroupTile) zero_fill(o + n, S.gap, tid);                  // the sentence's last tile (its only one when empty)
+}
+
 }  // namespace gsv
 
 extern "C" int gsv_sola(float* frags, const int* lens, int n, int overlap, float* out, int* out_len, gsv_stream_t stream) {
@@ -225,4 +345,64 @@ extern "C" int gsv_postprocess(const void* const* frags, const int* lens, int n,
 extern "C" int gsv_postprocess_f32(const void* const* frags, const int* lens, int n, int dtype, int gap, float* out,
                                    gsv_stream_t stream) {
   return gsv::postprocess_t<float>(frags, lens, n, dtype, gap, out, stream);
+}
+
+static inline long long groups_tiles(int len) { return len <= 0 ? 1 : ((long long)len + gsv::kGroupTile - 1) / gsv::kGroupTile; }
+
+extern "C" long long gsv_postprocess_groups_workspace(const int* lens, int n) {
+  if (n < 0 || (n > 0 && !lens)) return -1;
+  long long tiles = 0;
+  for (int i = 0; i < n; ++i) {
+    if (lens[i] < 0) return -1;
+    tiles += groups_tiles(lens[i]);
+  }
+  return (long long)n * (long long)sizeof(gsv::GroupSent) + tiles * (long long)sizeof(gsv::GroupTile);
+}
+
+extern "C" int gsv_postprocess_groups(const void* const* frags, const int* lens, int n, int dtype, const int* group_n,
+                                      const int* group_gap, int n_groups, int16_t* out, long long* group_off, void* table,
+                                      void* workspace, gsv_stream_t stream) {
+  using namespace gsv;
+  GSV_REQUIRE(n >= 0 && n_groups >= 0 && (dtype == GSV_F16 || dtype == GSV_F32), "postprocess_groups: bad argument");
+  GSV_REQUIRE(n_groups == 0 || (group_n && group_gap && group_off), "postprocess_groups: null group table");
+  long long in_groups = 0;
+  for (int g = 0; g < n_groups; ++g) {
+    GSV_REQUIRE(group_n[g] >= 0 && group_gap[g] >= 0, "postprocess_groups: group %d has %d sentences, gap %d", g, group_n[g], group_gap[g]);
+    in_groups += group_n[g];
+  }
+  GSV_REQUIRE(in_groups == n, "postprocess_groups: the groups hold %lld sentences, n is %d", in_groups, n);
+  if (n == 0) {
+    for (int g = 0; g <= n_groups && group_off; ++g) group_off[g] = 0;
+    return GSV_OK;
+  }
+  GSV_REQUIRE(frags && lens && out && table && workspace, "postprocess_groups: null pointer");
+  GroupSent* sent = (GroupSent*)table;
+  GroupTile* tiles = (GroupTile*)(sent + n);
+  long long off = 0, n_tiles = 0;
+  int i = 0;
+  for (int g = 0; g < n_groups; ++g) {
+    group_off[g] = off;
+    for (int k = 0; k < group_n[g]; ++k, ++i) {
+      GSV_REQUIRE(lens[i] >= 0 && (lens[i] == 0 || frags[i]), "postprocess_groups: sentence %d is null", i);
+      sent[i] = GroupSent{frags[i], off, lens[i], group_gap[g], 0u, 0};
+      for (long long t = 0, nt = groups_tiles(lens[i]); t < nt; ++t) tiles[n_tiles++] = GroupTile{i, (int)(t * kGroupTile)};
+      off += (long long)lens[i] + group_gap[g];
+    }
+  }
+  group_off[n_groups] = off;
+  GSV_REQUIRE(n_tiles <= 0x7fffffffLL, "postprocess_groups: %lld tiles", n_tiles);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t bytes = (size_t)n * sizeof(GroupSent) + (size_t)n_tiles * sizeof(GroupTile);
+  GSV_HIP(hipMemcpyAsync(workspace, table, bytes, hipMemcpyHostToDevice, s));
+  GroupSent* dsent = (GroupSent*)workspace;
+  const GroupTile* dtiles = (const GroupTile*)(dsent + n);
+  if (dtype == GSV_F16) {
+    hipLaunchKernelGGL((post_groups_peak_kernel<_Float16>), dim3((unsigned)n_tiles), dim3(256), 0, s, dsent, dtiles);
+    hipLaunchKernelGGL((post_groups_write_kernel<_Float16>), dim3((unsigned)n_tiles), dim3(256), 0, s, (const GroupSent*)dsent, dtiles, (short*)out);
+  } else {
+    hipLaunchKernelGGL((post_groups_peak_kernel<float>), dim3((unsigned)n_tiles), dim3(256), 0, s, dsent, dtiles);
+    hipLaunchKernelGGL((post_groups_write_kernel<float>), dim3((unsigned)n_tiles), dim3(256), 0, s, (const GroupSent*)dsent, dtiles, (short*)out);
+  }
+  GSV_HIP(hipGetLastError());
+  return GSV_OK;
 }

@@ -22,7 +22,7 @@ import os
 import random
 import time
 import traceback
-from typing import Callable, Dict, Generator, List, Optional, Sequence, Tuple, Union
+from typing import Callable, Dict, Generator, Iterable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -976,6 +976,46 @@ class TTS:
                        "gsv_postprocess")
         return sr, self._to_host(pcm)
 
+    def postprocess_fragments(self, groups: Sequence[Tuple[Sequence[torch.Tensor], float]]) -> List[np.ndarray]:
+        """audio_postprocess([frags], sr, None, speed, False, fragment_interval) of several fragments in ONE launch pair and
+        ONE device-to-host copy (`gsv_postprocess_groups`, csrc/sola.hip): groups[g] = (the sentences of one fragment, its
+        fragment_interval) -> the int16 audio of each, what audio_postprocess returns for it alone (super_sampling is not
+        handled here: AP-BWE runs per fragment).  The table and the workspace are kept on the pipeline and grow on demand;
+        the call waits for its copy, so the next call may rewrite them."""
+        import ctypes as C
+        from .. import _lib
+        dev = torch.device(self.configs.device)
+        if dev.type != "cuda":
+            raise RuntimeError("postprocess_fragments is a HIP kernel (gsv_postprocess_groups); there is no CPU path")
+        if not groups:
+            return []
+        flat = [f.to(dev, self.precision).contiguous().view(-1) for frags, _ in groups for f in frags]
+        gaps = [int(self.configs.sampling_rate * interval) for _, interval in groups]
+        counts = [len(frags) for frags, _ in groups]
+        n, code = len(flat), _lib.GSV_F16 if self.precision == torch.float16 else _lib.GSV_F32
+        lens = (C.c_int * max(n, 1))(*[int(f.shape[0]) for f in flat])
+        ptrs = (C.c_void_p * max(n, 1))(*[f.data_ptr() for f in flat])
+        group_n, group_gap = (C.c_int * len(groups))(*counts), (C.c_int * len(groups))(*gaps)
+        off = (C.c_longlong * (len(groups) + 1))()
+        l = _lib.lib()
+        need = int(l.gsv_postprocess_groups_workspace(lens, n))
+        if need < 0:
+            raise RuntimeError("gsv_postprocess_groups_workspace: bad lengths")
+        with torch.cuda.device(dev):
+            ws = getattr(self, "_post_groups_ws", None)
+            if ws is None or ws[0].numel() < need:
+                size = max(1 << 16, 2 * need)
+                ws = self._post_groups_ws = (torch.empty(size, dtype=torch.uint8).pin_memory(),
+                                             torch.empty(size, dtype=torch.uint8, device=dev))
+            total = sum(int(f.shape[0]) for f in flat) + sum(c * g for c, g in zip(counts, gaps))
+            pcm = torch.empty(max(total, 1), dtype=torch.int16, device=dev)
+            st = torch.cuda.current_stream(dev)
+            _lib.check(l.gsv_postprocess_groups(ptrs, lens, n, code, group_n, group_gap, len(groups), pcm.data_ptr(), off,
+                                                ws[0].data_ptr(), ws[1].data_ptr(), C.c_void_p(st.cuda_stream)), "gsv_postprocess_groups")
+            host = self._to_host(pcm)                                   # waits for the stream: `flat` and the table are done with
+        assert int(off[len(groups)]) == total
+        return [host[int(off[g]):int(off[g + 1])].copy() for g in range(len(groups))]
+
     def _to_host(self, t: torch.Tensor) -> np.ndarray:
         from gsv.hostcopy import to_host
         return to_host(t)
@@ -1732,12 +1772,13 @@ class TTS:
         return passes
 
     # ---- run_batch's stages: a plan is one request's dict, and a stage reads what the earlier ones wrote on it
-    def _plan_request(self, req: dict) -> dict:
+    def _plan_request(self, req: dict, fragments: bool = False) -> dict:
         """Stage 1, per request, what run() does before its AR loop.  Reads the request and seeds the host generators (after
         the voice is resolved).  Writes the plan: `opts`, `voice`, `actual_seed`, `data` / `index` (to_batch), `no_prompt`,
-        `P` (prompt tokens) and `frags`, one slot per to_batch batch for its sentences' waveforms, filled by later stages."""
+        `P` (prompt tokens) and `frags`, one slot per to_batch batch for its sentences' waveforms, filled by later stages.
+        fragments=True (gsv.serving only, which delivers a request fold by fold): a return_fragment request is planned too."""
         o = self._resolve_options(req)
-        if o["return_fragment"]:
+        if o["return_fragment"] and not fragments:
             raise ValueError("run_batch returns whole utterances: return_fragment=True is not supported")
         voice = self._request_voice(req)
         actual_seed = set_seed(o["seed"])
@@ -1822,15 +1863,20 @@ class TTS:
             pl["kept"] = [self._kept_tokens(p, i, pl["no_prompt"]) for p, i in zip(pl["preds"], pl["idxs"])]
         self._wait_stream()
 
-    def _shared_sovits_stage(self, plans: List[dict], shared_speed: bool = False) -> None:
+    def _shared_sovits_stage(self, plans: List[dict], shared_speed: bool = False,
+                             folds: Optional[Iterable[Tuple[int, int]]] = None) -> None:
         """shared_sovits, v1 / v2 / v2Pro: every fold (request r, to_batch batch bi) that plan_sovits shares is one segment,
         with r's voice, of a SynthesizerTrn.decode_segments pass; with shared_speed, so is every sentence of a request at
         another speed that plan_sovits_rows shares, at that speed.  Reads `kept`, `voice`, `opts`, `actual_seed`, `data`.
         Writes `folds` and `sentences` (kept tokens per batch / per sentence, the planners' inputs), `frags[bi]` of every
-        shared fold and `frags[bi][k]` of every shared sentence (None where a sentence was left out)."""
+        shared fold and `frags[bi][k]` of every shared sentence (None where a sentence was left out).
+        `folds` (gsv.serving, which delivers a streaming request fold by fold): only these (r, bi) are planned and decoded;
+        `kept[bi]` of the others is not read (it may still be None)."""
         up = math.prod(self.vits_model.upsample_rates)
-        for pl in plans:
-            pl["sentences"] = [[int(p_.shape[0]) for p_ in pred] for pred, _ in pl["kept"]]
+        only = None if folds is None else set(folds)
+        for r, pl in enumerate(plans):
+            pl["sentences"] = [[int(p_.shape[0]) for p_ in pl["kept"][bi][0]] if only is None or (r, bi) in only else []
+                               for bi in range(len(pl["kept"]))]
             pl["folds"] = [sum(t) for t in pl["sentences"]]
         dev_voice: Dict[tuple, tuple] = {}          # one device refer list per distinct voice: one voice slot
         launches = self.plan_sovits_rows(plans) if shared_speed else [[(r, bi, -1) for r, bi in launch]
@@ -1902,28 +1948,33 @@ class TTS:
             fold_out[key] = [got[key][kk] for kk in sorted(got[key])]
         return fold_out
 
-    def _shared_cfm_stage(self, plans: List[dict], shared_vocoder: bool = False, continuous_cfm: bool = False) -> None:
+    def _shared_cfm_stage(self, plans: List[dict], shared_vocoder: bool = False, continuous_cfm: bool = False,
+                          folds: Optional[Iterable[Tuple[int, int]]] = None) -> None:
         """shared_cfm, v3 / v4: every chunk of every fold that plan_cfm shares is one row, with its voice's prompt mel, the
         noise key run() gives it and its request's LoRA adapter (the key "lora_voice"), of a CFM.inference_rows pass; vocoder and SOLA stay per fold, unless shared_vocoder: then
         the folds' mels go through the plan_vocoder passes of the vocoder's forward_segments, and only SOLA and the cuts stay
         per fold.  Reads `preds`, `kept`, `voice`, `opts`, `actual_seed`, `data`.  Writes `cfm_folds` (feature frames per
-        batch) and `T_min` (the voice's prompt length), plan_cfm's inputs, and `frags[bi]` of every shared fold."""
-        prompts, fold_in, voice_of = self._cfm_encode(plans)
+        batch) and `T_min` (the voice's prompt length), plan_cfm's inputs, and `frags[bi]` of every shared fold.
+        `folds` (gsv.serving): only these (r, bi) go through the stage, as for _shared_sovits_stage."""
+        prompts, fold_in, voice_of = self._cfm_encode(plans, **({} if folds is None else {"folds": folds}))
         if continuous_cfm:
             fold_out = self._continuous_cfm_passes(plans, fold_in, prompts, voice_of)
         else:
             fold_out = self._grouped_cfm_passes(plans, fold_in, prompts, voice_of)
         self._vocode_folds(plans, fold_in, fold_out, shared_vocoder)
 
-    def _cfm_encode(self, plans: List[dict], prompts: Optional[Dict[tuple, tuple]] = None) -> Tuple[dict, dict, list]:
+    def _cfm_encode(self, plans: List[dict], prompts: Optional[Dict[tuple, tuple]] = None,
+                    folds: Optional[Iterable[Tuple[int, int]]] = None) -> Tuple[dict, dict, list]:
         """The first half of the shared flow-matching stage, up to the rows the DiT takes: per distinct voice (and LoRA
         encoder) one _prompt_features(), per fold with generated tokens one _fold_chunks().  Reads `kept`, `preds`, `voice`,
         `opts`, `data`; writes `cfm_folds` and `T_min`.  `prompts`: a cache of _prompt_features() by voice key that the
-        caller keeps between calls (gsv.serving encodes request by request); entries are added to it.
+        caller keeps between calls (gsv.serving encodes request by request); entries are added to it.  `folds`: only these
+        (r, bi) are encoded, the others count as folds without frames and their `kept[bi]` is not read.
         -> (prompts, fold_in[(r, bi)] = (rows [chunks, T_chunk, 512], lens, pad_len), voice_of[r] = r's key in prompts)"""
         prompts = {} if prompts is None else prompts            # _prompt_features() per distinct voice
         fold_in: Dict[Tuple[int, int], tuple] = {}  # (rows [chunks, T_chunk, 512], lens, pad_len)
         voice_of: List[Optional[tuple]] = [None] * len(plans)
+        only = None if folds is None else set(folds)
         for r, pl in enumerate(plans):
             pl["cfm_folds"], pl["T_min"] = [0] * len(pl["data"]), 0
             if not pl["opts"]["parallel_infer"] or not pl["data"]:
@@ -1939,6 +1990,8 @@ class TTS:
                 prompt = prompts[vk]
                 pl["T_min"] = prompt[4]
                 for bi, item in enumerate(pl["data"]):
+                    if only is not None and (r, bi) not in only:
+                        continue
                     idx_list = pl["kept"][bi][1]
                     if sum(int(i) for i in idx_list) <= 0:
                         continue

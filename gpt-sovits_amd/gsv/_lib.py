@@ -178,6 +178,10 @@ _SIGS = {
     "gsv_postprocess": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "gsv_postprocess_f32": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_void_p,
                                       C.c_void_p]),
+    "gsv_postprocess_groups_workspace": (C.c_longlong, [C.POINTER(C.c_int), C.c_int]),
+    "gsv_postprocess_groups": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int), C.c_int, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
     "gsv_bwe_create": (C.c_int, [C.POINTER(BweConfig), C.c_int, C.POINTER(C.c_void_p)]),
     "gsv_bwe_destroy": (None, [C.c_void_p]),
     "gsv_bwe_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),

@@ -7,7 +7,13 @@
   the live rows a chunk of steps, and sends the requests whose sentences have all come back through the shared waveform stage
   of `run_batch` -- so a short request is delivered when it is finished, and a new one takes a free slot while the others
   decode.  A request that cannot decode in the session (prompt-free, `parallel_infer=False`, a row the K/V arena would cut,
-  `return_fragment` / streaming, `best_of` candidates) is *exclusive*: a FIFO barrier that is served with `run_batch([request])` once nothing is live.
+  `best_of` candidates) is *exclusive*: a FIFO barrier that is served with `run_batch([request])` once nothing is live.
+* A streaming request (`return_fragment` / `streaming_mode`) is a session citizen like any other, delivered fold by fold: a fold
+  (one `to_batch` batch, what `run()` yields a fragment for) whose sentences are all back goes into that step's waveform pass
+  at once -- or, `continuous_cfm`, its rows join the flow-matching FIFO at once -- and its fragment is emitted as soon as its
+  audio exists and every earlier fold of the request has been emitted.  All fragments of a step are converted by one
+  `gsv_postprocess_groups` launch pair and one copy (`TTS.postprocess_fragments`).  `Scheduler.take_fragments()` hands out the
+  fragments of the last step, `Server.submit_stream` an iterator over one request's; the request's result is the list of all.
 * `plan_online` is the schedule as a pure function, `plan_continuous` with arrivals: the event trace `Scheduler` records in
   `stats["events"]`.  Both are driven by the same `_Policy`, which holds every decision and touches no GPU.
 * `Server` puts one loop thread around a scheduler: the only thread that makes GPU calls.  `submit` returns a
@@ -29,6 +35,7 @@ from __future__ import annotations
 
 import collections
 import concurrent.futures
+import queue
 import threading
 from concurrent.futures import CancelledError
 from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple
@@ -53,6 +60,11 @@ class _Policy:
         self.fifo: collections.deque = collections.deque()                     # [request, rows, next row, exclusive]
         self.missing: Dict[Any, int] = {}                                      # session request -> rows not back yet
         self.ready: List[Tuple[Any, int]] = []                                 # (request, step it became ready)
+        # streaming requests (fragment by fragment, one fragment per fold): request -> dict(fold: the fold of each row,
+        # missing: {fold: rows not back yet}, voiced: the folds whose audio exists and that wait for an earlier one, nxt: the
+        # next fold to emit, n: its folds)
+        self.stream: Dict[Any, dict] = {}
+        self.fold_ready: List[Tuple[Any, int]] = []                            # folds whose rows are all back, not taken yet
         self.open = False          # a decode session is open
         self.dirty = False         # something ran since the last ("close",)
 
@@ -73,10 +85,11 @@ class _Policy:
 
     @property
     def idle(self) -> bool:
-        return not self.fifo and not self.missing and not self.ready
+        return not self.fifo and not self.missing and not self.ready and not self.stream
 
     # -- one step, in the order Scheduler.step documents
-    def arrive(self, req, rows: int, exclusive: bool, step: int) -> None:
+    def arrive(self, req, rows: int, exclusive: bool, step: int, folds: Optional[Sequence[int]] = None) -> None:
+        """folds (a streaming request): its rows per fold, rows being in fold order; every fold has at least one row"""
         if exclusive:
             self.fifo.append([req, 0, 0, True])
         elif rows <= 0:
@@ -84,6 +97,11 @@ class _Policy:
         else:
             self.fifo.append([req, int(rows), 0, False])
             self.missing[req] = int(rows)
+            if folds is not None:
+                if sum(folds) != rows or min(folds) < 1:
+                    raise ValueError(f"folds of {list(folds)} rows for a request of {rows}")
+                self.stream[req] = dict(fold=[bi for bi, n in enumerate(folds) for _ in range(n)],
+                                        missing={bi: int(n) for bi, n in enumerate(folds)}, voiced=set(), nxt=0, n=len(folds))
 
     def admit(self) -> List[Tuple[Any, int, int]]:
         free = [s for s in range(self.slots) if self.owner[s] is None]
@@ -104,16 +122,52 @@ class _Policy:
         for req, row in rows:
             self.owner[self.owner.index((req, row))] = None
             self.missing[req] -= 1
+            st = self.stream.get(req)
+            if st is not None:                      # a streaming request is ready fold by fold, never as a whole
+                bi = st["fold"][row]
+                st["missing"][bi] -= 1
+                if st["missing"][bi] == 0:
+                    del st["missing"][bi]
+                    self.fold_ready.append((req, bi))
             if self.missing[req] == 0:
                 del self.missing[req]
-                self.ready.append((req, step))
+                if st is None:
+                    self.ready.append((req, step))
 
-    def wave(self, step: int) -> list:
+    def take_folds(self) -> List[Tuple[Any, int]]:
+        """the folds of streaming requests whose rows are all back, at once: a fragment does not wait for company"""
+        out, self.fold_ready = self.fold_ready, []
+        if out:
+            self.dirty = True
+        return out
+
+    def voiced(self, req, bi: int) -> List[int]:
+        """the audio of fold bi exists -> the folds to emit now, in order: bi and what waited for it, or nothing while an
+        earlier fold is outstanding"""
+        st = self.stream[req]
+        st["voiced"].add(bi)
+        out = []
+        while st["nxt"] in st["voiced"]:
+            st["voiced"].remove(st["nxt"])
+            out.append(st["nxt"])
+            st["nxt"] += 1
+        return out
+
+    def stream_done(self, req) -> bool:
+        """every fold of the streaming request has been emitted: it is forgotten"""
+        st = self.stream[req]
+        if st["nxt"] < st["n"]:
+            return False
+        del self.stream[req]
+        return True
+
+    def wave(self, step: int, force: bool = False) -> list:
         """the requests of this step's waveform pass: all that are ready, once the oldest has waited wave_hold steps -- or at
-        once when no row is live or admissible, since no company can come"""
+        once when no row is live or admissible, since no company can come, or when the pass runs anyway (`force`: a
+        streaming request's fold is in it)"""
         if not self.ready:
             return []
-        if step - self.ready[0][1] < self.wave_hold and (self.live or self.queued):
+        if not force and step - self.ready[0][1] < self.wave_hold and (self.live or self.queued):
             return []
         out = [req for req, _ in self.ready]
         self.ready = []
@@ -150,6 +204,8 @@ class _Policy:
             if e[0] == req:
                 self.fifo.remove(e)
         self.missing.pop(req, None)
+        self.stream.pop(req, None)
+        self.fold_ready = [f for f in self.fold_ready if f[0] != req]
         self.ready = [(r, t) for r, t in self.ready if r != req]
         slots = [s for s, o in enumerate(self.owner) if o is not None and o[0] == req]
         for s in slots:
@@ -204,6 +260,17 @@ class _CfmPolicy:
             self.folds[req] = n
         return n > 0
 
+    def enqueue_fold(self, req, bi: int, rows: Sequence[Tuple[int, bool]]) -> bool:
+        """one fold of a streaming request, encoded as soon as its sentences are back: its rows join the FIFO in k order.  The
+        request is not counted in `folds` (it is delivered fragment by fragment); False: the fold has no frames"""
+        for k, (steps, guided) in enumerate(rows):
+            if int(steps) < 1:
+                raise ValueError("a row needs at least one Euler step")
+            self.fifo.append((req, bi, k, int(steps), bool(guided)))
+        if rows:
+            self.pending[(req, bi)] = len(rows)
+        return len(rows) > 0
+
     def admit(self) -> List[Tuple[Any, int, int, int]]:
         """rows from the head of the FIFO into the lowest free slots while the live DiT rows fit `rows` and the distinct
         step counts fit TABLES; the head that does not fit blocks the rows behind it.  -> [(request, bi, k, slot)]"""
@@ -246,6 +313,8 @@ class _CfmPolicy:
         """the folds went through the vocoder -> the requests whose folds are now all back, in that order"""
         out = []
         for req, _ in folds:
+            if req not in self.folds:               # a streaming request: its folds are emitted one by one
+                continue
             self.folds[req] -= 1
             if self.folds[req] == 0:
                 del self.folds[req]
@@ -266,7 +335,7 @@ class _CfmPolicy:
 def plan_online(arrivals: Sequence[int], rows_per_request: Sequence[int], lengths: Sequence[int], slots: int, chunk: int,
                 admit_min: Optional[int] = None, wave_hold: int = 0, exclusive=(), with_steps: bool = False,
                 cfm_folds: Optional[Sequence[Sequence[Sequence[Tuple[int, bool]]]]] = None, cfm_rows: Optional[int] = None,
-                cfm_chunk: Optional[int] = None):
+                cfm_chunk: Optional[int] = None, streaming: Optional[Dict[int, Sequence[int]]] = None):
     """The schedule `Scheduler` follows, as a pure function.  Request r is submitted in front of step arrivals[r] (requests
     arriving in the same step keep their order) and brings rows_per_request[r] rows; `lengths` lists, request after request and
     row after row, how many further steps each row needs after its step 0 (0: it ends at its admission), as `plan_continuous`
@@ -280,7 +349,14 @@ def plan_online(arrivals: Sequence[int], rows_per_request: Sequence[int], length
     [(req, bi, k, slot), ...]), ("cfm_step", k, [(req, bi, k) finished, in slot order]), ("vocode", [(req, bi) of the folds
     completed in this step]) and ("deliver", [reqs]): the requests without rows that became ready in this step, then those
     whose last fold was vocoded in it.  An exclusive request waits until neither session has a live or queued row, and
-    ("close",) closes both sessions.  Without `cfm_folds` the trace is the one described above."""
+    ("close",) closes both sessions.  Without `cfm_folds` the trace is the one described above.
+    `streaming`: {r: the rows of each of its folds} names the streaming requests (a request also named in `exclusive` stays
+    exclusive and its entry is not read).  Such a request is never in a ("wave", ...) or ("deliver", ...) list: a fold whose
+    rows are all back goes into that step's pass -- ("wave", [reqs], [(req, bi), ...]), the pass fires at once and every ready
+    request rides along -- or, with `cfm_folds`, its rows join the flow-matching FIFO at once, so the ("cfm_admit", ...) events
+    are fold-granular.  ("fragment", req, bi) follows the pass (the ("vocode", ...) event) that made fold bi's audio, once every
+    earlier fold of the request has been emitted: bi = 0, 1, ... per request.  With no streaming request the trace is
+    unchanged."""
     n = len(arrivals)
     if cfm_folds is not None and (cfm_rows is None or cfm_chunk is None or len(cfm_folds) != n):
         raise ValueError("cfm_folds needs cfm_rows, cfm_chunk and one entry per request")
@@ -294,17 +370,27 @@ def plan_online(arrivals: Sequence[int], rows_per_request: Sequence[int], length
         total += 0 if r in excl else int(rows_per_request[r])
     if total != len(lengths):
         raise ValueError(f"{len(lengths)} lengths for {total} rows")
+    streaming = {int(r): [int(k) for k in f] for r, f in (streaming or {}).items() if r not in excl}
+    for r, f in streaming.items():
+        if sum(f) != int(rows_per_request[r]):
+            raise ValueError(f"request {r}: folds of {f} rows, {rows_per_request[r]} rows")
     pol = _Policy(slots, chunk, admit_min, wave_hold)
     order = sorted(range(n), key=lambda r: (int(arrivals[r]), r))
     left = [0] * pol.slots
     trace, nxt, step = [], 0, 0
     busy = (lambda: cp.busy) if cp is not None else (lambda: False)
+
+    def fragments(folds):
+        for r, bi in folds:
+            for b in pol.voiced(r, bi):
+                trace.append((step, ("fragment", r, b)))
+            pol.stream_done(r)
     while nxt < n or not pol.idle or busy():
         if pol.idle and not busy() and int(arrivals[order[nxt]]) > step:
             step = int(arrivals[order[nxt]])            # nothing to do until the next arrival
         while nxt < n and int(arrivals[order[nxt]]) <= step:
             r = order[nxt]
-            pol.arrive(r, 0 if r in excl else int(rows_per_request[r]), r in excl, step)
+            pol.arrive(r, 0 if r in excl else int(rows_per_request[r]), r in excl, step, streaming.get(r) or None)
             nxt += 1
         admitted = pol.admit()
         if admitted:
@@ -322,11 +408,14 @@ def plan_online(arrivals: Sequence[int], rows_per_request: Sequence[int], length
             trace.append((step, ("advance", pol.chunk, done)))
             pol.finish(done, step)
         if cp is None:
-            ready = pol.wave(step)
-            if ready:
-                trace.append((step, ("wave", ready)))
+            sfolds = pol.take_folds()
+            ready = pol.wave(step, force=bool(sfolds))
+            if ready or sfolds:
+                trace.append((step, ("wave", ready, sfolds) if sfolds else ("wave", ready)))
+                fragments(sfolds)
         else:
             deliver = [r for r in pol.take_ready() if not cp.enqueue(r, cfm_folds[r])]
+            voiced = [(r, bi) for r, bi in pol.take_folds() if not cp.enqueue_fold(r, bi, cfm_folds[r][bi])]
             admitted = cp.admit()
             if admitted:
                 trace.append((step, ("cfm_admit", admitted)))
@@ -336,6 +425,8 @@ def plan_online(arrivals: Sequence[int], rows_per_request: Sequence[int], length
                 if folds:
                     trace.append((step, ("vocode", folds)))
                     deliver += cp.vocoded(folds)
+                    voiced += [f for f in folds if f[0] in pol.stream]
+            fragments(voiced)
             if deliver:
                 trace.append((step, ("deliver", deliver)))
         while True:
@@ -404,6 +495,7 @@ class Scheduler:
         self._rows: Dict[int, List[dict]] = {}      # ticket -> its rows in queue order: dict(bi, j, key, sampling)
         self._where: Dict[int, Tuple[int, int]] = {}    # session ticket -> (ticket, row)
         self._done: List[Tuple[int, Any]] = []      # results that wait for the next step to return them
+        self._frags: List[Tuple[int, int, Any]] = []    # (ticket, bi, (sr, audio)) emitted in the last step (take_fragments)
         self._ses = None
         self._next, self._step = 0, 0
         self._closed = False
@@ -443,19 +535,29 @@ class Scheduler:
         if any(t == ticket for t, _ in self._inbox):
             self._inbox = [(t, r) for t, r in self._inbox if t != ticket]
         elif ticket in self._requests:
-            slots = self._pol.cancel(ticket)
-            if slots:
-                self._ses.release_slots(slots)
-                self.stats["released"] += len(slots)
-                self.stats["events"].append(("release", slots))
-            self._where = {k: v for k, v in self._where.items() if v[0] != ticket}
-            self._drop_cfm(ticket)
-            self._requests.pop(ticket)
-            self._rows.pop(ticket, None)
+            self._forget(ticket)
         else:
             return False
         self._done.append((ticket, CancelledError()))
         return True
+
+    def _forget(self, ticket: int) -> None:
+        """drops an outstanding request: queued rows, live rows of both sessions (released), fold buffers, its plan"""
+        slots = self._pol.cancel(ticket)
+        if slots:
+            self._ses.release_slots(slots)
+            self.stats["released"] += len(slots)
+            self.stats["events"].append(("release", slots))
+        self._where = {k: v for k, v in self._where.items() if v[0] != ticket}
+        self._drop_cfm(ticket)
+        self._requests.pop(ticket)
+        self._rows.pop(ticket, None)
+
+    def take_fragments(self) -> List[Tuple[int, int, Any]]:
+        """the fragments the last step emitted, in emission order: [(ticket, bi, (sr, int16 audio))] -- per streaming request
+        bi = 0, 1, ...; the request's final result (the list of all of them) comes from the step that emits the last one"""
+        out, self._frags = self._frags, []
+        return out
 
     def close(self) -> None:
         """drops what is outstanding (no step will return it) and closes the sessions: `tts.run` / `run_batch` work again"""
@@ -469,7 +571,8 @@ class Scheduler:
         """One round: intake, admit, advance, finish (continuous_cfm: encode, flow-matching admit, step, fetch, vocode,
         deliver), exclusive requests, close when idle (module docstring).  Returns the
         (ticket, result) pairs of the requests that ended in it; a result is (sr, int16 audio), the list of fragments of a
-        `return_fragment` request, or the exception the request raised."""
+        `return_fragment` request (returned by the step that emits the last one; `take_fragments` has each as it is made), or
+        the exception the request raised."""
         import torch
         with torch.no_grad():
             return self._do_step()
@@ -478,6 +581,7 @@ class Scheduler:
     def _do_step(self) -> List[Tuple[int, Any]]:
         pol, step, ev = self._pol, self._step, self.stats["events"]
         out, self._done = self._done, []
+        self._frags = []
         self._intake(out)
         admitted = pol.admit()
         if admitted:
@@ -497,11 +601,12 @@ class Scheduler:
             pol.finish(done, step)
         cp = self._cpol
         if cp is None:
-            ready = pol.wave(step)
-            if ready:
-                ev.append(("wave", ready))
+            sfolds = pol.take_folds()
+            ready = pol.wave(step, force=bool(sfolds))
+            if ready or sfolds:
+                ev.append(("wave", ready, sfolds) if sfolds else ("wave", ready))
                 self.stats["waves"] += 1
-                self._wave(ready, out)
+                self._wave(ready, out, sfolds)
         else:
             self._cfm_round(out)
         busy = cp is not None and cp.busy
@@ -552,25 +657,28 @@ class Scheduler:
 
     def _intake(self, out: list) -> None:
         taken, self._inbox = self._inbox, []
-        streaming = [(t, r) for t, r in taken if r.get("return_fragment") or r.get("streaming_mode")]
-        plain = self._resolve([(t, r) for t, r in taken if not (r.get("return_fragment") or r.get("streaming_mode"))], out)
+        # a streaming request is planned like any other (the planner's `fragments` keyword is passed for it alone)
+        taken = [(t, dict(r, return_fragment=True) if r.get("return_fragment") or r.get("streaming_mode") else r) for t, r in taken]
         plans = {}
-        for t, req in plain:
+        for t, req in self._resolve(taken, out):
             try:
-                plans[t] = (req, self.tts._plan_request(req))
+                plans[t] = (req, self.tts._plan_request(req, **({"fragments": True} if req.get("return_fragment") else {})))
             except Exception as e:                                      # noqa: BLE001 -- the request's own result
                 out.append((t, e))
-        for t, req in sorted(streaming + [(t, rp[0]) for t, rp in plans.items()], key=lambda x: x[0]):    # arrival order
-            rows = self._session_rows(plans[t][1]) if t in plans else None
+        for t, (req, pl) in sorted(plans.items()):                      # arrival order
+            rows = self._session_rows(pl)
             if rows is None:
                 self._requests[t] = req
                 self._pol.arrive(t, 0, True, self._step)
             else:
-                pl = plans[t][1]
                 pl["preds"] = [[None] * len(item["all_phones"]) for item in pl["data"]]
                 pl["idxs"] = [[None] * len(item["all_phones"]) for item in pl["data"]]
                 self._requests[t], self._rows[t] = pl, rows
-                self._pol.arrive(t, len(rows), False, self._step)
+                folds = None
+                if pl["opts"]["return_fragment"]:                       # delivered fold by fold: (bi, j) order is fold order
+                    pl["kept"], pl["stream"] = [None] * len(pl["data"]), []
+                    folds = [len(item["all_phones"]) for item in pl["data"]]
+                self._pol.arrive(t, len(rows), False, self._step, folds or None)
 
     def _budget(self) -> int:
         from .TTS_infer_pack.TTS import early_stop_num
@@ -607,36 +715,114 @@ class Scheduler:
         self.stats["admissions"] += 1
         self.stats["rows"] += len(rows)
 
-    def _wave(self, ready: List[int], out: list) -> None:
+    def _wave(self, ready: List[int], out: list, sfolds: Sequence[Tuple[int, int]] = ()) -> None:
         """the ready requests through run_batch's waveform stages, called with the ready subset, then each through
-        _finish_request; a stage that raises fails the requests of this pass, nobody else"""
+        _finish_request; a stage that raises fails the requests of this pass, nobody else.  sfolds: the ready folds of
+        streaming requests, which go through the same pass -- the stage is then restricted to them and to every fold of the
+        ready requests -- and are emitted after it (_emit)."""
         tts = self.tts
         plans = [self._requests.pop(t) for t in ready]
         for t in ready:
             self._rows.pop(t, None)
+        streams = sorted({t for t, _ in sfolds})
         try:
             for pl in plans:
                 pl["kept"] = [tts._kept_tokens(p, i, pl["no_prompt"]) for p, i in zip(pl["preds"], pl["idxs"])]
+            kw = {}
+            if sfolds:
+                at = {t: len(plans) + n for n, t in enumerate(streams)}
+                for t, bi in sfolds:
+                    pl = self._requests[t]
+                    pl["kept"][bi] = tts._kept_tokens(pl["preds"][bi], pl["idxs"][bi], pl["no_prompt"])
+                kw["folds"] = [(r, bi) for r, pl in enumerate(plans) for bi in range(len(pl["data"]))] + [(at[t], bi) for t, bi in sfolds]
             tts._wait_stream()
             sr = tts._output_sr()
             if tts.configs.use_vocoder:
-                tts._shared_cfm_stage(plans, shared_vocoder=self._shared_vocoder)
+                tts._shared_cfm_stage(plans + [self._requests[t] for t in streams], shared_vocoder=self._shared_vocoder, **kw)
             else:
-                tts._shared_sovits_stage(plans)
+                tts._shared_sovits_stage(plans + [self._requests[t] for t in streams], **kw)
         except Exception as e:                                          # noqa: BLE001 -- the pass's requests' result
             out.extend((t, e) for t in ready)
+            self._fail(streams, e, out)
             return
         for t, pl in zip(ready, plans):
             try:
-                out.append((t, tts._finish_request(pl, sr)))
+                out.append((t, self._finished(t, pl, tts._finish_request(pl, sr))))
             except Exception as e:                                      # noqa: BLE001 -- the request's own result
                 out.append((t, e))
+        self._emit(sfolds, out)
+
+    def _finished(self, t: int, pl: dict, result):
+        """what _finish_request returned, as the request's result: a streaming request that reaches it has no sentence at
+        all, and run() yields that second of silence as its one fragment"""
+        if not pl["opts"]["return_fragment"]:
+            return result
+        self._frags.append((t, 0, result))
+        return [result]
+
+    def _emit(self, voiced: Sequence[Tuple[int, int]], out: list) -> None:
+        """the audio of these folds of streaming requests exists (a fold no shared stage took goes through _synthesize_batch
+        here, as in _finish_request): the fragments that are due -- per request in fold order, none before an earlier one --
+        are what run() yields for them, audio_postprocess([frags], ...), all through ONE postprocess_fragments call
+        (super_sampling fragments: audio_postprocess each, AP-BWE runs per fragment).  A request whose last fragment is
+        emitted gets the list of all of them as its result."""
+        tts, pol, ev = self.tts, self._pol, self.stats["events"]
+        due: List[Tuple[int, int]] = []
+        for t, bi in voiced:
+            if t in self._requests:
+                due += [(t, b) for b in pol.voiced(t, bi)]
+        got: Dict[Tuple[int, int], Any] = {}
+        batch: List[Tuple[int, int]] = []
+        for t, b in due:
+            if t not in self._requests:
+                continue
+            pl = self._requests[t]
+            o = pl["opts"]
+            try:
+                if pl["frags"][b] is None or any(f is None for f in pl["frags"][b]):
+                    with tts._with_prompt_cache(dict(pl["voice"])) as voice:
+                        pred, idx_list = pl["kept"][b]
+                        pl["frags"][b] = tts._synthesize_batch(pl["data"][b], pred, pl["preds"][b], idx_list, b, pl["actual_seed"], o,
+                                                               tts._voice_refer(voice), have=pl["frags"][b])
+                if o["super_sampling"]:
+                    tts._wait_stream()
+                    got[(t, b)] = tts.audio_postprocess([pl["frags"][b]], tts._output_sr(), None, o["speed_factor"], False,
+                                                        o["fragment_interval"], True)
+                else:
+                    batch.append((t, b))
+            except Exception as e:                                      # noqa: BLE001 -- the request's own result
+                self._fail([t], e, out)
+        batch = [(t, b) for t, b in batch if t in self._requests]
+        try:
+            if batch:
+                tts._wait_stream()
+                sr = tts._output_sr()
+                audios = tts.postprocess_fragments([(self._requests[t]["frags"][b], self._requests[t]["opts"]["fragment_interval"])
+                                                    for t, b in batch])
+                got.update({f: (sr, a) for f, a in zip(batch, audios)})
+        except Exception as e:                                          # noqa: BLE001 -- the requests of this launch
+            self._fail(sorted({t for t, _ in batch}), e, out)
+        for t, b in due:
+            if t not in self._requests:
+                continue
+            pl = self._requests[t]
+            pl["stream"].append(got[(t, b)])
+            pl["frags"][b] = []                                         # the waveforms are delivered: the device memory goes
+            self._frags.append((t, b, got[(t, b)]))
+            ev.append(("fragment", t, b))
+        for t in dict.fromkeys(t for t, _ in due):                      # after the last fragment: the request's result
+            if t in self._requests and pol.stream_done(t):
+                pl = self._requests.pop(t)
+                self._rows.pop(t, None)
+                self._drop_cfm(t)
+                out.append((t, pl["stream"]))
 
     def _exclusive(self, t: int, out: list) -> None:
         req = self._requests.pop(t)
         try:
             if req.get("return_fragment") or req.get("streaming_mode"):
                 out.append((t, list(self.tts.run(dict(req, return_fragment=True)))))
+                self._frags += [(t, bi, f) for bi, f in enumerate(out[-1][1])]
             else:
                 out.append((t, self.tts.run_batch([req])[0]))
         except Exception as e:                                          # noqa: BLE001 -- the request's own result
@@ -648,6 +834,7 @@ class Scheduler:
         completed folds, deliver the completed requests.  A stage that raises fails the requests it was working on."""
         pol, cp, ev, st = self._pol, self._cpol, self.stats["events"], self.stats
         deliver = [t for t in pol.take_ready() if not self._encode(t, out)]
+        voiced = [(t, bi) for t, bi in pol.take_folds() if t in self._requests and not self._encode(t, out, bi)]
         admitted = cp.admit()
         if admitted:
             ev.append(("cfm_admit", admitted))
@@ -669,6 +856,8 @@ class Scheduler:
             if folds:
                 ev.append(("vocode", folds))
                 deliver += self._vocode(folds, staged, out)
+                voiced += [f for f in folds if f[0] in pol.stream]
+        self._emit(voiced, out)
         deliver = [t for t in deliver if t in self._requests]           # a failed stage has answered for the others
         if deliver:
             ev.append(("deliver", deliver))
@@ -679,13 +868,27 @@ class Scheduler:
                 self._drop_cfm(t)
                 try:
                     tts._wait_stream()
-                    out.append((t, tts._finish_request(pl, tts._output_sr())))
+                    out.append((t, self._finished(t, pl, tts._finish_request(pl, tts._output_sr()))))
                 except Exception as e:                                  # noqa: BLE001 -- the request's own result
                     out.append((t, e))
 
-    def _encode(self, t: int, out: list) -> bool:
-        """the first half of the shared flow-matching stage for one request; its rows join the FIFO.  False: it has no row"""
+    def _encode(self, t: int, out: list, fold: Optional[int] = None) -> bool:
+        """the first half of the shared flow-matching stage for one request; its rows join the FIFO.  False: it has no row.
+        fold: the same for that one fold of a streaming request, whose sentences are back (False: the fold has no frames)"""
         tts, pl = self.tts, self._requests[t]
+        if fold is not None:
+            try:
+                pl["kept"][fold] = tts._kept_tokens(pl["preds"][fold], pl["idxs"][fold], pl["no_prompt"])
+                tts._wait_stream()
+                _, fold_in, voice_of = tts._cfm_encode([pl], self._cfm_prompts, folds=[(0, fold)])
+                rows = [(steps, rate > 0.0) for _, steps, rate in tts.plan_cfm_rows([pl])]     # only `fold` has frames
+                c = self._cfm_req.setdefault(t, dict(vk=voice_of[0], fold_in={}, mel={}))
+                c["fold_in"].update({bi: v for (_, bi), v in fold_in.items()})
+                self.stats["cfm_folds"].setdefault(t, [[] for _ in pl["data"]])[fold] = rows
+                return self._cpol.enqueue_fold(t, fold, rows)
+            except Exception as e:                                      # noqa: BLE001 -- the request's own result
+                self._fail([t], e, out)
+                return True
         try:
             pl["kept"] = [tts._kept_tokens(p, i, pl["no_prompt"]) for p, i in zip(pl["preds"], pl["idxs"])]
             tts._wait_stream()
@@ -796,9 +999,7 @@ class Scheduler:
         """the requests get `exc` as their result; their rows, slots and buffers are dropped"""
         for t in tickets:
             if t in self._requests:
-                self._drop_cfm(t)
-                self._requests.pop(t)
-                self._rows.pop(t, None)
+                self._forget(t)                     # a streaming request may still have rows in the decode session
                 out.append((t, exc))
 
     def _drop_cfm(self, t: int) -> None:
@@ -833,6 +1034,34 @@ class Scheduler:
         self._close_cfm()
 
 
+_END = object()      # closes a Stream's queue
+
+
+class Stream:
+    """What `Server.submit_stream` returns: the iterator over one streaming request's fragments (see there)."""
+
+    def __init__(self, server: "Server", future: concurrent.futures.Future):
+        self._server, self.future = server, future
+        self._over: Any = None
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self._over is None:
+            item = self.future.fragments.get()
+            if item is not _END and not isinstance(item, BaseException):
+                return item
+            self._over = item
+        if self._over is _END:
+            raise StopIteration
+        raise self._over
+
+    def cancel(self) -> None:
+        """asks the server to cancel the request: the stream ends with CancelledError after the fragments already emitted"""
+        self._server.cancel(self.future)
+
+
 class Server:
     """One loop thread around a `Scheduler`: the only thread that touches the GPU.  `submit` works from any thread and returns
     a Future that resolves to the request's result (or raises its exception).  The loop sleeps on a condition variable while
@@ -862,6 +1091,7 @@ class Server:
 
     def submit(self, request: dict) -> concurrent.futures.Future:
         fut: concurrent.futures.Future = concurrent.futures.Future()
+        fut.fragments = queue.SimpleQueue()     # (sr, audio) as emitted, then _END or the exception: read by Stream
         with self._cv:
             if self.error is not None:
                 raise RuntimeError(f"the server stopped: {self.error!r}") from self.error
@@ -870,6 +1100,14 @@ class Server:
             self._cmds.append(("submit", request, fut))
             self._cv.notify_all()
         return fut
+
+    def submit_stream(self, request: dict) -> "Stream":
+        """a streaming request (`return_fragment` is set for it): an iterator over its fragments (sr, int16 audio) as the
+        scheduler emits them.  `__next__` blocks until the next fragment is there and re-raises the request's exception
+        (CancelledError after `cancel()`) once the fragments emitted before it are consumed; `.future` resolves to the list of
+        all fragments."""
+        stream = Stream(self, self.submit(dict(request, return_fragment=True)))
+        return stream
 
     def cancel(self, future: concurrent.futures.Future) -> None:
         """asks the loop to cancel the request: its future raises CancelledError (unless it was delivered first)"""
@@ -886,14 +1124,20 @@ class Server:
         if threading.current_thread() is not self._thread:
             self._thread.join(timeout)
 
-    def _deliver(self, results) -> None:
+    def _deliver(self, results, fragments=()) -> None:
+        for ticket, _, frag in fragments:
+            fut = self._futures.get(ticket)
+            if fut is not None:
+                fut.fragments.put(frag)
         for ticket, result in results:
             fut = self._futures.pop(ticket, None)
             if fut is None:
                 continue
             if isinstance(result, BaseException):
+                fut.fragments.put(result)
                 fut.set_exception(result)
             else:
+                fut.fragments.put(_END)
                 fut.set_result(result)
 
     def _loop(self) -> None:
@@ -915,7 +1159,9 @@ class Server:
                         for ticket, f in list(self._futures.items()):
                             if f is fut:
                                 sched.cancel(ticket)
-                self._deliver(sched.step())
+                results = sched.step()
+                take = getattr(sched, "take_fragments", None)
+                self._deliver(results, take() if take is not None else ())
         except BaseException as e:                                      # noqa: BLE001 -- handed to every waiting future
             self.error = e
         finally:
@@ -926,7 +1172,9 @@ class Server:
             left += list(self._futures.values())
             self._futures.clear()
             for fut in left:
-                fut.set_exception(self.error if self.error is not None else CancelledError())
+                exc = self.error if self.error is not None else CancelledError()
+                fut.fragments.put(exc)
+                fut.set_exception(exc)
             try:
                 sched.close()
             except Exception:                                           # noqa: BLE001 -- the loop is gone either way

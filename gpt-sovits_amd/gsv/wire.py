@@ -93,14 +93,18 @@ def tts_handle(tts_pipeline, req: dict, server=None):
     """api_v2.py:300-373 without the web framework: -> (status code, media type, payload); payload is bytes, an iterator of
     bytes (streaming_mode) or, on failure, the reference's error dict.
     server (gsv.serving.Server, e.g. tts_pipeline.serve()): the request is submitted to it and this call waits for its
-    future, so that calls from several threads share the server's decode session and waveform passes; a streaming /
-    return_fragment request goes through it as an exclusive request and its fragments are framed here."""
+    future, so that calls from several threads share the server's decode session and waveform passes.  A streaming_mode
+    request goes through `server.submit_stream` where the server has it: the payload then frames each fragment when the
+    scheduler emits it (a failure after the first fragment is raised by the iterator); a server without it, and a
+    return_fragment request that is not streamed, hand back the list of fragments at the end."""
     streaming_mode = req.get("streaming_mode", False)
     media_type = req.get("media_type", "wav")
     if streaming_mode or req.get("return_fragment", False):
         req = dict(req, return_fragment=True)
     try:
-        if server is not None:
+        if server is not None and streaming_mode and hasattr(server, "submit_stream"):
+            gen = server.submit_stream(req)
+        elif server is not None:
             result = server.submit(req).result()
             gen = iter(result if isinstance(result, list) else [result])
         else:

@@ -477,6 +477,18 @@ int gsv_postprocess(const void* const* frags, const int* lens, int n, int dtype,
 /* the same fragments, peak rule, gaps and order, written as fp32 without the x32768 / int16 step (out capacity as above): the
  * float concatenation the reference's super-sampling path feeds to AP_BWE (TTS.py:1397-1417) */
 int gsv_postprocess_f32(const void* const* frags, const int* lens, int n, int dtype, int gap, float* out, gsv_stream_t stream);
+/* gsv_postprocess for the fragments of several requests at once: n sentences (frags, lens [host], as above) in n_groups groups,
+ * group g the next group_n[g] sentences with its own gap group_gap[g] (both [host]).  out [dev] int16 is one packed buffer:
+ * group g starts at sample group_off[g] ([host], n_groups + 1 entries, written by the call; the last one is the total, which is
+ * the capacity out needs: sum over the sentences of len + their group's gap) and holds exactly what gsv_postprocess writes for
+ * that group alone.  Sentences are cut into tiles over the whole GPU (two launches: peaks, then conversion), and any number of
+ * sentences is taken.  table [host] and workspace [dev]: gsv_postprocess_groups_workspace(lens, n) bytes each (-1: a negative
+ * length); the call fills `table`, uploads it to `workspace` with one copy on `stream` and allocates nothing.  `table` must stay
+ * untouched until the stream has passed that copy (page-locked memory keeps the call asynchronous).  n = 0 is GSV_OK and
+ * touches neither. */
+long long gsv_postprocess_groups_workspace(const int* lens, int n);
+int gsv_postprocess_groups(const void* const* frags, const int* lens, int n, int dtype, const int* group_n, const int* group_gap,
+                           int n_groups, int16_t* out, long long* group_off, void* table, void* workspace, gsv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * AP-BWE audio super-resolution (tools/audio_sr.py::AP_BWE.__call__): torchaudio resample to hr_sampling_rate

@@ -22,6 +22,19 @@ CFMSession.fetch_mel for 1 / 8 / 32 finished rows of T_chunk frames against the 
 replaces, next to the byte floor 2 * rows * (T - Tp) * 100 * 4 B.
 
     python tools/serving_bench.py --version v3 --sample-steps 8,16,32 [--cfm-chunks 1,2,4,8] [--cfm-rows 16,32,64] [--handoff]
+
+--streaming: instead of the sweep, the same replay with --stream-share of the requests streaming (`return_fragment`, sent with
+`Server.submit_stream`), through Server() at the first (C) setting -- streaming requests inside the sessions -- against the
+scheduler as it was before: the same class with every streaming request exclusive (sessions drained and closed, run() alone,
+all fragments at the end; `_ExclusiveStreams`).  Both in this process, --repeats alternating pairs over the same arrival
+traces (the order within a pair flips from pair to pair).  Per load: submit-to-first-fragment and submit-to-last-fragment
+p50 / p95 of the streaming requests, p50 / p95 of the others, audio-s/s -- medians over the pairs with the min..max spread of
+the p50s -- and the same pairs with no streaming request at all (the two must not separate beyond that spread).
+--postprocess prints first the cost of one gsv_postprocess_groups call for 32 fragments x 4 s against 32 gsv_postprocess
+calls (device time between events, and wall time through the pipeline's methods with the copy to the host) next to the byte
+floor (each sample read twice, written once).
+
+    python tools/serving_bench.py --streaming [--stream-share 0.25] [--loads 0.3,0.6,0.9] [--postprocess]
 """
 import argparse
 import json
@@ -82,6 +95,9 @@ def main():
     ap.add_argument("--cfm-chunks", default="1,2,4,8")
     ap.add_argument("--cfm-rows", default="16,32,64")
     ap.add_argument("--handoff", action="store_true", help="v3 / v4: time fetch_mel against the per-slot hand-off first")
+    ap.add_argument("--streaming", action="store_true", help="streaming requests in the sessions against the exclusive path")
+    ap.add_argument("--stream-share", type=float, default=0.25)
+    ap.add_argument("--postprocess", action="store_true", help="time gsv_postprocess_groups against per-fragment gsv_postprocess first")
     a = ap.parse_args()
     from bench import build_tts, make_segments
     from gsv import synthetic as S
@@ -104,6 +120,8 @@ def main():
         tts.configs.max_seq = 80 + 160 + TOK + 16          # room for the longest voice's prompt
         tts.t2s_model = None
         tts.init_t2s_weights(tts.configs.t2s_weights_path, state=tts._t2s_state)
+    if a.postprocess:
+        postprocess_cost(tts, dev)
     rng = random.Random(a.seed)
     counts = [rng.randint(1, 4) for _ in range(N)]
     utt, segs = make_segments(sum(counts))
@@ -211,6 +229,13 @@ def main():
                        cfm_euler_steps=st["cfm_steps"], cfm_admissions=st["cfm_admissions"], vocoder_calls=st["vocoder_calls"])
         return out
 
+    if a.streaming:
+        kw = dict(chunk=int(a.chunks.split(",")[0]), admit_min=int(a.admit_mins.split(",")[0]), wave_hold=int(a.wave_holds.split(",")[0]))
+        if v3:
+            kw.update(continuous_cfm=True, cfm_chunk=int(a.cfm_chunks.split(",")[0]), cfm_rows=int(a.cfm_rows.split(",")[0]))
+        streaming_pairs(a, tts, reqs, audio_s, trace, kw)
+        print(json.dumps(dict(record="engine", fallbacks=tts.t2s_model.engine_stats()[1])), flush=True)
+        return
     settings = [] if v3 else [("A", "run() per request", serve_a, {})]
     settings += [("B", f"window {w} ms", serve_b, dict(window=float(w) / 1e3)) for w in a.windows_ms.split(",") if w]
     settings += [("C", f"chunk {c} admit_min {m} wave_hold {h}", serve_c, dict(chunk=int(c), admit_min=int(m), wave_hold=int(h)))
@@ -226,6 +251,125 @@ def main():
             med = {k: statistics.median(r[k] for r in runs) for k in runs[0]}
             print(json.dumps(dict(record="serve", server=kind, setting=name, load=load, repeats=a.repeats, **med)), flush=True)
     print(json.dumps(dict(record="engine", fallbacks=tts.t2s_model.engine_stats()[1])), flush=True)
+
+
+def streaming_pairs(a, tts, reqs, audio_s, trace, kw):
+    """--streaming (module docstring)"""
+    from gsv.serving import Scheduler, Server
+    N = len(reqs)
+
+    class _ExclusiveStreams(Scheduler):
+        """the scheduler before streaming requests were session citizens: each is a FIFO barrier served by run() alone"""
+        def _session_rows(self, pl):
+            return None if pl["opts"]["return_fragment"] else super()._session_rows(pl)
+
+    def serve(arrivals, streams, cls, reqs):
+        first_at, done_at, handles = [0.0] * N, [0.0] * N, [None] * N
+        server = Server(cls(tts, slots=a.slots, **kw))
+        readers = []
+
+        def read(i, stream):
+            for n, _ in enumerate(stream):
+                if n == 0:
+                    first_at[i] = time.perf_counter()
+            done_at[i] = time.perf_counter()
+
+        def submit(i):
+            if i in streams:
+                handles[i] = server.submit_stream(reqs[i])
+                readers.append(threading.Thread(target=read, args=(i, handles[i])))
+                readers[-1].start()
+            else:
+                handles[i] = server.submit(reqs[i])
+                handles[i].add_done_callback(lambda f, i=i: done_at.__setitem__(i, time.perf_counter()))
+        t0 = _replay(arrivals, submit)
+        for i, h in enumerate(handles):
+            (h.future if i in streams else h).result()
+        for th in readers:
+            th.join()
+        server.shutdown()
+        st = server.scheduler.stats
+        lat = lambda at, ids: [at[i] - (t0 + arrivals[i]) for i in ids]
+        plain = [i for i in range(N) if i not in streams]
+        ss = sorted(streams)
+        ms = lambda xs, q: round(1e3 * _pct(xs, q), 1) if xs else None
+        return dict(first_p50_ms=ms(lat(first_at, ss), 0.5), first_p95_ms=ms(lat(first_at, ss), 0.95),
+                    last_p50_ms=ms(lat(done_at, ss), 0.5), last_p95_ms=ms(lat(done_at, ss), 0.95),
+                    plain_p50_ms=ms(lat(done_at, plain), 0.5), plain_p95_ms=ms(lat(done_at, plain), 0.95),
+                    audio_s_per_s=round(sum(audio_s) / (max(done_at) - t0), 1), sessions=st["sessions"], exclusive=st["exclusive"])
+
+    servers = (("sessions", Scheduler), ("exclusive", _ExclusiveStreams))
+    for load in [float(x) for x in a.loads.split(",") if x]:
+        for share in (a.stream_share, 0.0):
+            r_ = random.Random(77 + a.seed)
+            streams = {i for i in range(N) if r_.random() < share}
+            # an interactive caller streams sentence by sentence: batch_size 1, one fragment per sentence, for both servers
+            rq = [dict(r, batch_size=1) if i in streams else r for i, r in enumerate(reqs)]
+            runs = {name: [] for name, _ in servers}
+            for rep in range(a.repeats):
+                for name, cls in (servers if rep % 2 == 0 else servers[::-1]):
+                    runs[name].append(serve(trace(load, rep), streams, cls, rq))
+            for name, _ in servers:
+                med = {k: (statistics.median(r[k] for r in runs[name]) if runs[name][0][k] is not None else None) for k in runs[name][0]}
+                spread = {k: [min(r[k] for r in runs[name]), max(r[k] for r in runs[name])]
+                          for k in ("first_p50_ms", "last_p50_ms", "plain_p50_ms", "audio_s_per_s") if runs[name][0][k] is not None}
+                print(json.dumps(dict(record="stream", server=name, load=load, stream_share=share, streams=len(streams), requests=N,
+                                      pairs=a.repeats, setting=kw, **med, spread=spread)), flush=True)
+
+
+def postprocess_cost(tts, dev):
+    """--postprocess (module docstring): 32 fragments of 4 s at the pipeline's rate and precision"""
+    import ctypes as C
+    from gsv import _lib
+    sr, n = int(tts.configs.sampling_rate), 32
+    L = 4 * sr
+    wav = (torch.rand(n * L + 8, device=dev) * 2.4 - 1.2).to(tts.precision)
+    frags = [wav[3 + i * L:3 + (i + 1) * L] for i in range(n)]                 # views, not 16-byte aligned
+    gap = int(sr * 0.3)
+    code = _lib.GSV_F16 if tts.precision == torch.float16 else _lib.GSV_F32
+    l, st = _lib.lib(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    lens = (C.c_int * n)(*[L] * n)
+    ptrs = (C.c_void_p * n)(*[f.data_ptr() for f in frags])
+    gn, gg, off = (C.c_int * n)(*[1] * n), (C.c_int * n)(*[gap] * n), (C.c_longlong * (n + 1))()
+    need = int(l.gsv_postprocess_groups_workspace(lens, n))
+    table, work = torch.empty(need, dtype=torch.uint8).pin_memory(), torch.empty(need, dtype=torch.uint8, device=dev)
+    pcm = torch.empty(n * (L + gap), dtype=torch.int16, device=dev)
+    one = [((C.c_void_p * 1)(f.data_ptr()), (C.c_int * 1)(L)) for f in frags]
+
+    def grouped():
+        _lib.check(l.gsv_postprocess_groups(ptrs, lens, n, code, gn, gg, n, pcm.data_ptr(), off, table.data_ptr(), work.data_ptr(), st), "groups")
+
+    def single():
+        for i, (p, k) in enumerate(one):
+            _lib.check(l.gsv_postprocess(p, k, 1, code, gap, pcm.data_ptr() + 2 * i * (L + gap), st), "postprocess")
+    dev_ms = {}
+    for name, fn in (("groups_one_call", grouped), ("postprocess_32_calls", single)):
+        ts = []
+        for it in range(12):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if it >= 2:
+                ts.append(e0.elapsed_time(e1))
+        dev_ms[name] = round(statistics.median(ts), 4)
+    wall_ms = {}
+    for name, fn in (("postprocess_fragments", lambda: tts.postprocess_fragments([([f], 0.3) for f in frags])),
+                     ("audio_postprocess_x32", lambda: [tts.audio_postprocess([[f]], sr, None, 1.0, False, 0.3, False) for f in frags])):
+        ts = []
+        for it in range(9):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            ts.append(1e3 * (time.perf_counter() - t0))
+        wall_ms[name] = round(statistics.median(ts[2:]), 4)
+    esz = 2 if tts.precision == torch.float16 else 4
+    floor = n * L * (2 * esz + 2) + n * gap * 2
+    print(json.dumps(dict(record="postprocess", fragments=n, samples_each=L, dtype="f16" if esz == 2 else "f32", gap=gap,
+                          device_ms=dev_ms, wall_ms_with_host_copy=wall_ms, floor_bytes=floor,
+                          floor_us_at_6p3_TBps=round(floor / 6.3e12 * 1e6, 2))), flush=True)
 
 
 def handoff(tts, dev):

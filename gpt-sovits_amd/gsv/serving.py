@@ -15,7 +15,10 @@
   `gsv_postprocess_groups` launch pair and one copy (`TTS.postprocess_fragments`).  `Scheduler.take_fragments()` hands out the
   fragments of the last step, `Server.submit_stream` an iterator over one request's; the request's result is the list of all.
 * `plan_online` is the schedule as a pure function, `plan_continuous` with arrivals: the event trace `Scheduler` records in
-  `stats["events"]`.  Both are driven by the same `_Policy`, which holds every decision and touches no GPU.
+  `stats["events"]`.  The two share the policies -- `_Policy` and `_CfmPolicy` hold every decision and touch no GPU -- and the
+  step itself: `_run_step` is the one place that asks the policies in order, appends the events and, for everything that is
+  not a decision, calls a backend.  `plan_online`'s backend is `_Replay`, which counts the `lengths` down and looks the
+  flow-matching rows up in `cfm_folds`; `Scheduler` is its own backend and makes the GPU calls.
 * `Server` puts one loop thread around a scheduler: the only thread that makes GPU calls.  `submit` returns a
   `concurrent.futures.Future` from any thread.
 * `Scheduler(continuous_cfm=True)` (v3 / v4) keeps a second session open behind the first: a flow-matching session
@@ -23,8 +26,8 @@
   encoded at once and its rows queue for the session's slots; a scheduler step runs at most `cfm_chunk` Euler steps, fetches
   the rows that finished with one `fetch_mel` launch -- de-normalised and channels-first, the vocoder's input as it stands --
   vocodes the folds that are complete and delivers the requests that are.  `_CfmPolicy` holds these decisions next to
-  `_Policy`, and `plan_online(cfm_folds=...)` replays them.  An exclusive request waits for both sessions and closes both.
-  AR launches, Euler steps and vocoder calls still run strictly one after the other, on the one thread.
+  `_Policy`, and `plan_online(cfm_folds=...)` runs the same step over them.  An exclusive request waits for both sessions and
+  closes both.  AR launches, Euler steps and vocoder calls still run strictly one after the other, on the one thread.
 
 What a request returns is what `run_batch([request])` returns for it alone: its rows carry the RNG keys and sampling tuples
 `plan_batch` gives them, sampling is per row, admissions and releases leave the neighbouring slots untouched, and the waveform
@@ -41,6 +44,20 @@ from concurrent.futures import CancelledError
 from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple
 
 from .AR.models.t2s_model import admit_count
+
+
+class _Stream:
+    """What `_Policy` knows of a streaming request, which is delivered fragment by fragment, one fragment per fold."""
+    __slots__ = ("fold", "missing", "voiced", "nxt", "n")
+
+    def __init__(self, folds: Sequence[int]):
+        self.fold = [bi for bi, n in enumerate(folds) for _ in range(n)]       # the fold of each row, rows being in fold order
+        self.missing = {bi: int(n) for bi, n in enumerate(folds)}              # fold -> rows not back yet
+        self.voiced: set = set()                   # the folds whose audio exists and that wait for an earlier one
+        self.nxt, self.n = 0, len(folds)           # the next fold to emit; its folds
+
+    def __getitem__(self, field: str):             # st["fold"] is st.fold: the state still reads by key, as a dict did
+        return getattr(self, field)
 
 
 class _Policy:
@@ -60,13 +77,10 @@ class _Policy:
         self.fifo: collections.deque = collections.deque()                     # [request, rows, next row, exclusive]
         self.missing: Dict[Any, int] = {}                                      # session request -> rows not back yet
         self.ready: List[Tuple[Any, int]] = []                                 # (request, step it became ready)
-        # streaming requests (fragment by fragment, one fragment per fold): request -> dict(fold: the fold of each row,
-        # missing: {fold: rows not back yet}, voiced: the folds whose audio exists and that wait for an earlier one, nxt: the
-        # next fold to emit, n: its folds)
-        self.stream: Dict[Any, dict] = {}
+        self.stream: Dict[Any, _Stream] = {}                                   # the streaming requests not yet emitted in full
         self.fold_ready: List[Tuple[Any, int]] = []                            # folds whose rows are all back, not taken yet
         self.open = False          # a decode session is open
-        self.dirty = False         # something ran since the last ("close",)
+        self.dirty = False         # something ran since the sessions were last closed
 
     # -- state
     @property
@@ -100,8 +114,7 @@ class _Policy:
             if folds is not None:
                 if sum(folds) != rows or min(folds) < 1:
                     raise ValueError(f"folds of {list(folds)} rows for a request of {rows}")
-                self.stream[req] = dict(fold=[bi for bi, n in enumerate(folds) for _ in range(n)],
-                                        missing={bi: int(n) for bi, n in enumerate(folds)}, voiced=set(), nxt=0, n=len(folds))
+                self.stream[req] = _Stream(folds)
 
     def admit(self) -> List[Tuple[Any, int, int]]:
         free = [s for s in range(self.slots) if self.owner[s] is None]
@@ -124,10 +137,10 @@ class _Policy:
             self.missing[req] -= 1
             st = self.stream.get(req)
             if st is not None:                      # a streaming request is ready fold by fold, never as a whole
-                bi = st["fold"][row]
-                st["missing"][bi] -= 1
-                if st["missing"][bi] == 0:
-                    del st["missing"][bi]
+                bi = st.fold[row]
+                st.missing[bi] -= 1
+                if st.missing[bi] == 0:
+                    del st.missing[bi]
                     self.fold_ready.append((req, bi))
             if self.missing[req] == 0:
                 del self.missing[req]
@@ -145,26 +158,27 @@ class _Policy:
         """the audio of fold bi exists -> the folds to emit now, in order: bi and what waited for it, or nothing while an
         earlier fold is outstanding"""
         st = self.stream[req]
-        st["voiced"].add(bi)
+        st.voiced.add(bi)
         out = []
-        while st["nxt"] in st["voiced"]:
-            st["voiced"].remove(st["nxt"])
-            out.append(st["nxt"])
-            st["nxt"] += 1
+        while st.nxt in st.voiced:
+            st.voiced.remove(st.nxt)
+            out.append(st.nxt)
+            st.nxt += 1
         return out
 
     def stream_done(self, req) -> bool:
         """every fold of the streaming request has been emitted: it is forgotten"""
         st = self.stream[req]
-        if st["nxt"] < st["n"]:
+        if st.nxt < st.n:
             return False
         del self.stream[req]
         return True
 
     def wave(self, step: int, force: bool = False) -> list:
         """the requests of this step's waveform pass: all that are ready, once the oldest has waited wave_hold steps -- or at
-        once when no row is live or admissible, since no company can come, or when the pass runs anyway (`force`: a
-        streaming request's fold is in it)"""
+        once when no row is live or admissible, since no company can come, or when nothing is gained by holding (`force`: the
+        pass runs anyway, a streaming request's fold is in it; or, continuous_cfm, the flow-matching session is the company a
+        held request would have waited for)"""
         if not self.ready:
             return []
         if not force and step - self.ready[0][1] < self.wave_hold and (self.live or self.queued):
@@ -172,15 +186,6 @@ class _Policy:
         out = [req for req, _ in self.ready]
         self.ready = []
         self.dirty = True
-        return out
-
-    def take_ready(self) -> list:
-        """continuous_cfm: the requests whose sentences are all back, at once -- wave_hold does not apply, the flow-matching
-        session is the company a held request would have waited for"""
-        out = [req for req, _ in self.ready]
-        self.ready = []
-        if out:
-            self.dirty = True
         return out
 
     def exclusive_head(self, busy: bool = False):
@@ -244,11 +249,13 @@ class _CfmPolicy:
         """a row is live or queued"""
         return bool(self.fifo) or any(o is not None for o in self.owner)
 
-    def enqueue(self, req, folds: Sequence[Sequence[Tuple[int, bool]]]) -> bool:
-        """the rows of an encoded request, folds[bi] = [(steps, guided), ...] (empty: the fold has no frames), join the
-        FIFO in (bi, k) order; False: the request brings no row at all and goes straight to delivery"""
+    def enqueue(self, req, folds: Dict[int, Sequence[Tuple[int, bool]]], whole: bool) -> bool:
+        """the rows of the encoded folds, folds[bi] = [(steps, guided), ...] (empty: the fold has no frames), join the FIFO in
+        (bi, k) order; False: they bring no row at all.  whole: these are all the folds of the request, which is delivered
+        when they are vocoded (`vocoded`); else one fold of a streaming request, encoded as soon as its sentences are back
+        and not counted in `folds`: such a request is delivered fragment by fragment"""
         n = 0
-        for bi, rows in enumerate(folds):
+        for bi, rows in sorted(folds.items()):
             for k, (steps, guided) in enumerate(rows):
                 if int(steps) < 1:
                     raise ValueError("a row needs at least one Euler step")
@@ -256,20 +263,9 @@ class _CfmPolicy:
             if rows:
                 self.pending[(req, bi)] = len(rows)
                 n += 1
-        if n:
+        if whole and n:
             self.folds[req] = n
         return n > 0
-
-    def enqueue_fold(self, req, bi: int, rows: Sequence[Tuple[int, bool]]) -> bool:
-        """one fold of a streaming request, encoded as soon as its sentences are back: its rows join the FIFO in k order.  The
-        request is not counted in `folds` (it is delivered fragment by fragment); False: the fold has no frames"""
-        for k, (steps, guided) in enumerate(rows):
-            if int(steps) < 1:
-                raise ValueError("a row needs at least one Euler step")
-            self.fifo.append((req, bi, k, int(steps), bool(guided)))
-        if rows:
-            self.pending[(req, bi)] = len(rows)
-        return len(rows) > 0
 
     def admit(self) -> List[Tuple[Any, int, int, int]]:
         """rows from the head of the FIFO into the lowest free slots while the live DiT rows fit `rows` and the distinct
@@ -332,6 +328,145 @@ class _CfmPolicy:
         return slots
 
 
+def _run_step(pol: _Policy, cp: Optional[_CfmPolicy], be, step: int, ev: list) -> None:
+    """One scheduler step behind its arrivals (`_Policy.arrive`, which the caller has done), written once for `Scheduler` and
+    `plan_online`: admit, advance, finish, then the waveform pass or -- `cp` given -- the flow-matching round (encode, admit,
+    Euler steps, vocode), fragments and deliveries, then the exclusive requests that are due, then the close of an idle
+    burst.  The decisions are the policies', the events are appended to `ev` here and nowhere else, and everything else is a
+    method of the backend `be` (`_Replay` lists them).  A stage that raises fails the requests it was working on
+    (`be._fail(requests, exception)`, which takes their rows out of both policies with `cancel`) and nobody else; a backend
+    may also fail requests inside a stage, so no request is expected to be still known after one."""
+    def attempt(reqs, stage, *args):
+        try:
+            return stage(*args)
+        except Exception as e:                                          # noqa: BLE001 -- the result of the stage's requests
+            be._fail(reqs, e)                                           # and the stage's result is None
+
+    def fragments(voiced):
+        """the audio of these folds exists: the fragments that are due, per request in fold order"""
+        due = [(r, b) for r, bi in voiced if r in pol.stream for b in pol.voiced(r, bi)]
+        if due:
+            ends = [r for r in dict.fromkeys(r for r, _ in due) if pol.stream_done(r)]
+            for r, b in attempt(sorted({r for r, _ in due}), be._emit, due, ends) or ():
+                ev.append(("fragment", r, b))
+
+    def encode(r, bi=None):
+        """request r (or its fold bi) joins the flow-matching FIFO -> True: it brings no row and has nothing to wait for"""
+        return attempt([r], lambda: not cp.enqueue(r, be._encode(r, bi), whole=bi is None))
+
+    admitted = pol.admit()
+    if admitted:
+        be._admit(admitted)
+        ev.append(("admit", admitted))
+    if pol.live:
+        done = be._advance(pol.chunk)
+        ev.append(("advance", pol.chunk, done))
+        pol.finish(done, step)
+    if cp is None:
+        sfolds = pol.take_folds()
+        ready = pol.wave(step, force=bool(sfolds))
+        if ready or sfolds:
+            ev.append(("wave", ready) + ((sfolds,) if sfolds else ()))
+            attempt(ready + sorted({r for r, _ in sfolds}), be._wave, ready, sfolds)
+            be._deliver(ready)
+            fragments(sfolds)
+    else:
+        deliver = [r for r in pol.wave(step, force=True) if encode(r)]
+        voiced = [(r, bi) for r, bi in pol.take_folds() if r in pol.stream and encode(r, bi)]
+        admitted = cp.admit()
+        if admitted:
+            ev.append(("cfm_admit", admitted))
+            attempt(sorted({r for r, _, _, _ in admitted}), be._cfm_admit, admitted)
+        if cp.live:
+            holders = sorted({cp.owner[s][0] for s in cp.live})
+            k, done, folds = cp.step()
+            ev.append(("cfm_step", k, [row for row, _ in done]))
+            mels = attempt(holders, be._cfm_step, k, done)
+            if mels is None:
+                cp.open = False                     # the session went with the step; queued rows open the next one
+            elif folds:
+                ev.append(("vocode", folds))
+                attempt(sorted({r for r, _ in folds}), be._vocode, folds, mels)
+                deliver += cp.vocoded(folds)
+                voiced += [f for f in folds if f[0] in pol.stream]
+        fragments(voiced)
+        deliver = be._deliver(deliver)
+        if deliver:
+            ev.append(("deliver", deliver))
+
+    def close():
+        pol.open = False
+        if cp is not None:
+            cp.open = False
+        be._close_sessions()
+        ev.append(("close",))
+    busy = cp is not None and cp.busy
+    while True:
+        was_open = pol.open or (cp is not None and cp.open)
+        r = pol.exclusive_head(busy)
+        if r is None:
+            break
+        if was_open:
+            close()
+        ev.append(("exclusive", r))
+        be._exclusive(r)
+    if pol.close_due(busy):
+        close()
+
+
+class _Replay:
+    """`plan_online`'s backend: the stages of `_run_step` with nothing behind them but the rows' `lengths`, counted down, and
+    the flow-matching rows of `cfm_folds`, looked up.  Its docstrings are the contract of each backend method."""
+
+    def __init__(self, slots: int, lengths: Sequence[int], first: Dict[int, int], cfm_folds):
+        self.lengths, self.first, self.cfm_folds = lengths, first, cfm_folds
+        self.row: List[Optional[Tuple[int, int]]] = [None] * slots
+        self.left = [0] * slots
+
+    def _admit(self, admitted) -> None:
+        """[(request, row, slot)] take their slots in the decode session"""
+        for r, row, s in admitted:
+            self.row[s], self.left[s] = (r, row), int(self.lengths[self.first[r] + row])
+
+    def _advance(self, chunk: int) -> List[Tuple[int, int]]:
+        """the live rows go `chunk` steps -> the (request, row) that finished, in slot order"""
+        done = []
+        for s, row in enumerate(self.row):
+            if row is not None:
+                self.left[s] -= min(chunk, self.left[s])
+                if self.left[s] == 0:
+                    done.append(row)
+                    self.row[s] = None
+        return done
+
+    def _encode(self, r, bi):
+        """-> {bi: [(steps, guided), ...]}: the flow-matching rows of request r's folds, or of its fold bi alone"""
+        return dict(enumerate(self.cfm_folds[r])) if bi is None else {bi: self.cfm_folds[r][bi]}
+
+    def _cfm_step(self, k: int, done):
+        """k Euler steps; `done` [((request, bi, k), slot)] finished with them -> their mels for `_vocode`, never None"""
+        return ()
+
+    def _emit(self, due, ends):
+        """the fragments `due` [(request, bi)]; the requests `ends` have their last one among them -> the fragments emitted"""
+        return due
+
+    def _deliver(self, reqs):
+        """the requests are finished and answered -> those that were still outstanding"""
+        return reqs
+
+    def _launch(self, *args) -> None:
+        """the stages that return nothing: `_wave(ready, sfolds)`, the waveform pass of the requests `ready` and the folds
+        `sfolds` [(request, bi)] of streaming requests; `_cfm_admit([(request, bi, k, slot), ...])` into the flow-matching session;
+        `_vocode(folds, mels)`, the completed folds [(request, bi)]; `_exclusive(request)`, alone; `_close_sessions()`, both"""
+    _wave = _cfm_admit = _vocode = _exclusive = _close_sessions = _launch
+
+    def _fail(self, reqs, exc: BaseException) -> None:
+        """a stage working on these requests raised: they get `exc` as their result and leave both policies (`cancel`).
+        Nothing fails in a replay but its arguments (a row of no Euler steps), and that is the caller's exception"""
+        raise exc
+
+
 def plan_online(arrivals: Sequence[int], rows_per_request: Sequence[int], lengths: Sequence[int], slots: int, chunk: int,
                 admit_min: Optional[int] = None, wave_hold: int = 0, exclusive=(), with_steps: bool = False,
                 cfm_folds: Optional[Sequence[Sequence[Sequence[Tuple[int, bool]]]]] = None, cfm_rows: Optional[int] = None,
@@ -376,76 +511,20 @@ def plan_online(arrivals: Sequence[int], rows_per_request: Sequence[int], length
             raise ValueError(f"request {r}: folds of {f} rows, {rows_per_request[r]} rows")
     pol = _Policy(slots, chunk, admit_min, wave_hold)
     order = sorted(range(n), key=lambda r: (int(arrivals[r]), r))
-    left = [0] * pol.slots
+    be = _Replay(pol.slots, lengths, first, cfm_folds)
     trace, nxt, step = [], 0, 0
-    busy = (lambda: cp.busy) if cp is not None else (lambda: False)
-
-    def fragments(folds):
-        for r, bi in folds:
-            for b in pol.voiced(r, bi):
-                trace.append((step, ("fragment", r, b)))
-            pol.stream_done(r)
-    while nxt < n or not pol.idle or busy():
-        if pol.idle and not busy() and int(arrivals[order[nxt]]) > step:
+    while nxt < n or not pol.idle or (cp is not None and cp.busy):
+        if pol.idle and not (cp is not None and cp.busy) and int(arrivals[order[nxt]]) > step:
             step = int(arrivals[order[nxt]])            # nothing to do until the next arrival
         while nxt < n and int(arrivals[order[nxt]]) <= step:
             r = order[nxt]
             pol.arrive(r, 0 if r in excl else int(rows_per_request[r]), r in excl, step, streaming.get(r) or None)
             nxt += 1
-        admitted = pol.admit()
-        if admitted:
-            for r, row, s in admitted:
-                left[s] = int(lengths[first[r] + row])
-            trace.append((step, ("admit", admitted)))
-        if pol.live:
-            done = []
-            for s in range(pol.slots):
-                if pol.owner[s] is None:
-                    continue
-                left[s] -= min(pol.chunk, left[s])
-                if left[s] == 0:
-                    done.append(pol.owner[s])
-            trace.append((step, ("advance", pol.chunk, done)))
-            pol.finish(done, step)
-        if cp is None:
-            sfolds = pol.take_folds()
-            ready = pol.wave(step, force=bool(sfolds))
-            if ready or sfolds:
-                trace.append((step, ("wave", ready, sfolds) if sfolds else ("wave", ready)))
-                fragments(sfolds)
-        else:
-            deliver = [r for r in pol.take_ready() if not cp.enqueue(r, cfm_folds[r])]
-            voiced = [(r, bi) for r, bi in pol.take_folds() if not cp.enqueue_fold(r, bi, cfm_folds[r][bi])]
-            admitted = cp.admit()
-            if admitted:
-                trace.append((step, ("cfm_admit", admitted)))
-            if cp.live:
-                k, done, folds = cp.step()
-                trace.append((step, ("cfm_step", k, [row for row, _ in done])))
-                if folds:
-                    trace.append((step, ("vocode", folds)))
-                    deliver += cp.vocoded(folds)
-                    voiced += [f for f in folds if f[0] in pol.stream]
-            fragments(voiced)
-            if deliver:
-                trace.append((step, ("deliver", deliver)))
-        while True:
-            was_open = pol.open or (cp is not None and cp.open)
-            r = pol.exclusive_head(busy())
-            if r is None:
-                break
-            if was_open:
-                pol.open = False
-                if cp is not None:
-                    cp.open = False
-                trace.append((step, ("close",)))
-            trace.append((step, ("exclusive", r)))
-        if pol.close_due(busy()):
-            if cp is not None:
-                cp.open = False
-            trace.append((step, ("close",)))
+        ev: list = []
+        _run_step(pol, cp, be, step, ev)
+        trace += [(step, e) for e in ev] if with_steps else ev
         step += 1
-    return trace if with_steps else [e for _, e in trace]
+    return trace
 
 
 class Scheduler:
@@ -494,7 +573,7 @@ class Scheduler:
         self._requests: Dict[int, dict] = {}        # ticket -> request (exclusive) or plan (session), until delivered
         self._rows: Dict[int, List[dict]] = {}      # ticket -> its rows in queue order: dict(bi, j, key, sampling)
         self._where: Dict[int, Tuple[int, int]] = {}    # session ticket -> (ticket, row)
-        self._done: List[Tuple[int, Any]] = []      # results that wait for the next step to return them
+        self._done: List[Tuple[int, Any]] = []      # results the running step, or the next one, returns (cancel adds between steps)
         self._frags: List[Tuple[int, int, Any]] = []    # (ticket, bi, (sr, audio)) emitted in the last step (take_fragments)
         self._ses = None
         self._next, self._step = 0, 0
@@ -546,7 +625,7 @@ class Scheduler:
         slots = self._pol.cancel(ticket)
         if slots:
             self._ses.release_slots(slots)
-            self.stats["released"] += len(slots)
+            self._count(released=len(slots))
             self.stats["events"].append(("release", slots))
         self._where = {k: v for k, v in self._where.items() if v[0] != ticket}
         self._drop_cfm(ticket)
@@ -564,73 +643,32 @@ class Scheduler:
         for t in [t for t, _ in self._inbox] + list(self._requests):
             self.cancel(t)
         self._done = []
-        self._close_session()
+        self._close_sessions()
         self._closed = True
 
     def step(self) -> List[Tuple[int, Any]]:
         """One round: intake, admit, advance, finish (continuous_cfm: encode, flow-matching admit, step, fetch, vocode,
-        deliver), exclusive requests, close when idle (module docstring).  Returns the
+        deliver), exclusive requests, close when idle (`_run_step`, behind the intake).  Returns the
         (ticket, result) pairs of the requests that ended in it; a result is (sr, int16 audio), the list of fragments of a
         `return_fragment` request (returned by the step that emits the last one; `take_fragments` has each as it is made), or
         the exception the request raised."""
         import torch
-        with torch.no_grad():
-            return self._do_step()
-
-    # -- the step
-    def _do_step(self) -> List[Tuple[int, Any]]:
-        pol, step, ev = self._pol, self._step, self.stats["events"]
-        out, self._done = self._done, []
         self._frags = []
-        self._intake(out)
-        admitted = pol.admit()
-        if admitted:
-            self._admit(admitted)
-            ev.append(("admit", admitted))
-        if pol.live:
-            self.stats["occupancy"].append(pol.live)
-            done = []
-            for st, y, n in self._ses.advance(pol.chunk):
-                t, row = self._where.pop(st)
-                e = self._rows[t][row]
-                pl = self._requests[t]
-                pl["preds"][e["bi"]][e["j"]], pl["idxs"][e["bi"]][e["j"]] = y, n
-                done.append((t, row))
-            self.stats["advances"] += 1
-            ev.append(("advance", pol.chunk, done))
-            pol.finish(done, step)
-        cp = self._cpol
-        if cp is None:
-            sfolds = pol.take_folds()
-            ready = pol.wave(step, force=bool(sfolds))
-            if ready or sfolds:
-                ev.append(("wave", ready, sfolds) if sfolds else ("wave", ready))
-                self.stats["waves"] += 1
-                self._wave(ready, out, sfolds)
-        else:
-            self._cfm_round(out)
-        busy = cp is not None and cp.busy
-        while True:
-            was_open = pol.open or (cp is not None and cp.open)
-            t = pol.exclusive_head(busy)
-            if t is None:
-                break
-            if was_open:
-                pol.open = False
-                self._close_session()
-                ev.append(("close",))
-            ev.append(("exclusive", t))
-            self.stats["exclusive"] += 1
-            self._exclusive(t, out)
-        if pol.close_due(busy):
-            self._close_session()
-            ev.append(("close",))
+        with torch.no_grad():
+            self._intake(self._done)
+            _run_step(self._pol, self._cpol, self, self._step, self.stats["events"])
+        out, self._done = self._done, []
         for t, _ in out:
-            self.stats["tickets"][t][2] = step
+            self.stats["tickets"][t][2] = self._step
         self._step += 1
         self.stats["steps"] = self._step
         return out
 
+    def _count(self, **counts: int) -> None:
+        for name, n in counts.items():
+            self.stats[name] += n
+
+    # -- the step: what `_run_step` calls (`_Replay` says what each does for the schedule), behind the intake
     def _resolve(self, taken: List[Tuple[int, dict]], out: list) -> List[Tuple[int, dict]]:
         """voices and texts of one intake through the shared front-ends, as ONE call each; a call that raises is repeated
         request by request, so that only the request at fault gets the exception"""
@@ -673,10 +711,11 @@ class Scheduler:
             else:
                 pl["preds"] = [[None] * len(item["all_phones"]) for item in pl["data"]]
                 pl["idxs"] = [[None] * len(item["all_phones"]) for item in pl["data"]]
+                pl["kept"] = [None] * len(pl["data"])                   # per fold, filled when its sentences are back (_keep)
                 self._requests[t], self._rows[t] = pl, rows
                 folds = None
                 if pl["opts"]["return_fragment"]:                       # delivered fold by fold: (bi, j) order is fold order
-                    pl["kept"], pl["stream"] = [None] * len(pl["data"]), []
+                    pl["stream"] = []
                     folds = [len(item["all_phones"]) for item in pl["data"]]
                 self._pol.arrive(t, len(rows), False, self._step, folds or None)
 
@@ -708,69 +747,78 @@ class Scheduler:
             k, p, temp, rp = rows[0]["sampling"]        # placeholders: every row brings its own tuple
             self._ses = self.tts.t2s_model.open_session(self._pol.slots, k, p, temp, rp, early_stop_num(self.tts.configs), 1,
                                                         self._budget(), row_sampling=True)
-            self.stats["sessions"] += 1
+            self._count(sessions=1)
         tickets = self._ses.admit(rows, slots=[s for _, _, s in admitted])
         for st, (t, row, _) in zip(tickets, admitted):
             self._where[st] = (t, row)
-        self.stats["admissions"] += 1
-        self.stats["rows"] += len(rows)
+        self._count(admissions=1, rows=len(rows))
 
-    def _wave(self, ready: List[int], out: list, sfolds: Sequence[Tuple[int, int]] = ()) -> None:
-        """the ready requests through run_batch's waveform stages, called with the ready subset, then each through
-        _finish_request; a stage that raises fails the requests of this pass, nobody else.  sfolds: the ready folds of
-        streaming requests, which go through the same pass -- the stage is then restricted to them and to every fold of the
-        ready requests -- and are emitted after it (_emit)."""
+    def _advance(self, chunk: int) -> List[Tuple[int, int]]:
+        self.stats["occupancy"].append(self._pol.live)
+        done = []
+        for st, y, n in self._ses.advance(chunk):
+            t, row = self._where.pop(st)
+            e = self._rows[t][row]
+            pl = self._requests[t]
+            pl["preds"][e["bi"]][e["j"]], pl["idxs"][e["bi"]][e["j"]] = y, n
+            done.append((t, row))
+        self._count(advances=1)
+        return done
+
+    def _keep(self, pl: dict, folds: Iterable[int]) -> None:
+        """the sentences of these folds are back: their AR output without the prompts, as the waveform stages take it"""
+        for bi in folds:
+            pl["kept"][bi] = self.tts._kept_tokens(pl["preds"][bi], pl["idxs"][bi], pl["no_prompt"])
+
+    def _wave(self, ready: List[int], sfolds: Sequence[Tuple[int, int]]) -> None:
+        """the ready requests through run_batch's waveform stages, called with the ready subset (a stage that raises fails
+        the requests of this pass).  sfolds: the ready folds of streaming requests, which go through the same pass -- the
+        stage is then restricted to them and to every fold of the ready requests."""
         tts = self.tts
-        plans = [self._requests.pop(t) for t in ready]
-        for t in ready:
-            self._rows.pop(t, None)
+        self._count(waves=1)
+        plans = [self._requests[t] for t in ready]
         streams = sorted({t for t, _ in sfolds})
-        try:
-            for pl in plans:
-                pl["kept"] = [tts._kept_tokens(p, i, pl["no_prompt"]) for p, i in zip(pl["preds"], pl["idxs"])]
-            kw = {}
-            if sfolds:
-                at = {t: len(plans) + n for n, t in enumerate(streams)}
-                for t, bi in sfolds:
-                    pl = self._requests[t]
-                    pl["kept"][bi] = tts._kept_tokens(pl["preds"][bi], pl["idxs"][bi], pl["no_prompt"])
-                kw["folds"] = [(r, bi) for r, pl in enumerate(plans) for bi in range(len(pl["data"]))] + [(at[t], bi) for t, bi in sfolds]
-            tts._wait_stream()
-            sr = tts._output_sr()
-            if tts.configs.use_vocoder:
-                tts._shared_cfm_stage(plans + [self._requests[t] for t in streams], shared_vocoder=self._shared_vocoder, **kw)
-            else:
-                tts._shared_sovits_stage(plans + [self._requests[t] for t in streams], **kw)
-        except Exception as e:                                          # noqa: BLE001 -- the pass's requests' result
-            out.extend((t, e) for t in ready)
-            self._fail(streams, e, out)
-            return
-        for t, pl in zip(ready, plans):
+        for pl in plans:
+            self._keep(pl, range(len(pl["data"])))
+        kw = {}
+        if sfolds:
+            at = {t: len(plans) + n for n, t in enumerate(streams)}
+            for t, bi in sfolds:
+                self._keep(self._requests[t], [bi])
+            kw["folds"] = [(r, bi) for r, pl in enumerate(plans) for bi in range(len(pl["data"]))] + [(at[t], bi) for t, bi in sfolds]
+        tts._wait_stream()
+        tts._output_sr()                                                # a model without its vocoder fails the whole pass
+        if tts.configs.use_vocoder:
+            tts._shared_cfm_stage(plans + [self._requests[t] for t in streams], shared_vocoder=self._shared_vocoder, **kw)
+        else:
+            tts._shared_sovits_stage(plans + [self._requests[t] for t in streams], **kw)
+
+    def _deliver(self, reqs: Iterable[int]) -> List[int]:
+        """the requests that are still outstanding, each through _finish_request; a streaming request that reaches it has no
+        sentence at all, and run() yields that second of silence as its one fragment"""
+        tts = self.tts
+        reqs = [t for t in reqs if t in self._requests]                 # a failed stage has answered for the others
+        for t in reqs:
+            pl = self._requests.pop(t)
+            self._rows.pop(t, None)
+            self._drop_cfm(t)
             try:
-                out.append((t, self._finished(t, pl, tts._finish_request(pl, sr))))
+                result = tts._finish_request(pl, tts._output_sr())
+                if pl["opts"]["return_fragment"]:
+                    self._frags.append((t, 0, result))
+                    result = [result]
+                self._done.append((t, result))
             except Exception as e:                                      # noqa: BLE001 -- the request's own result
-                out.append((t, e))
-        self._emit(sfolds, out)
+                self._done.append((t, e))
+        return reqs
 
-    def _finished(self, t: int, pl: dict, result):
-        """what _finish_request returned, as the request's result: a streaming request that reaches it has no sentence at
-        all, and run() yields that second of silence as its one fragment"""
-        if not pl["opts"]["return_fragment"]:
-            return result
-        self._frags.append((t, 0, result))
-        return [result]
-
-    def _emit(self, voiced: Sequence[Tuple[int, int]], out: list) -> None:
-        """the audio of these folds of streaming requests exists (a fold no shared stage took goes through _synthesize_batch
-        here, as in _finish_request): the fragments that are due -- per request in fold order, none before an earlier one --
-        are what run() yields for them, audio_postprocess([frags], ...), all through ONE postprocess_fragments call
-        (super_sampling fragments: audio_postprocess each, AP-BWE runs per fragment).  A request whose last fragment is
-        emitted gets the list of all of them as its result."""
-        tts, pol, ev = self.tts, self._pol, self.stats["events"]
-        due: List[Tuple[int, int]] = []
-        for t, bi in voiced:
-            if t in self._requests:
-                due += [(t, b) for b in pol.voiced(t, bi)]
+    def _emit(self, due: Sequence[Tuple[int, int]], ends: Iterable[int]) -> List[Tuple[int, int]]:
+        """the fragments that are due -- folds of streaming requests whose audio exists (a fold no shared stage took goes
+        through _synthesize_batch here, as in _finish_request), per request in fold order -- are what run() yields for them,
+        audio_postprocess([frags], ...), all through ONE postprocess_fragments call (super_sampling fragments:
+        audio_postprocess each, AP-BWE runs per fragment).  A request of `ends`, whose last fragment is among them, gets the
+        list of all of them as its result.  -> the fragments emitted"""
+        tts = self.tts
         got: Dict[Tuple[int, int], Any] = {}
         batch: List[Tuple[int, int]] = []
         for t, b in due:
@@ -791,7 +839,7 @@ class Scheduler:
                 else:
                     batch.append((t, b))
             except Exception as e:                                      # noqa: BLE001 -- the request's own result
-                self._fail([t], e, out)
+                self._fail([t], e)
         batch = [(t, b) for t, b in batch if t in self._requests]
         try:
             if batch:
@@ -801,132 +849,87 @@ class Scheduler:
                                                     for t, b in batch])
                 got.update({f: (sr, a) for f, a in zip(batch, audios)})
         except Exception as e:                                          # noqa: BLE001 -- the requests of this launch
-            self._fail(sorted({t for t, _ in batch}), e, out)
-        for t, b in due:
-            if t not in self._requests:
-                continue
+            self._fail(sorted({t for t, _ in batch}), e)
+        emitted = [f for f in due if f[0] in self._requests]
+        for t, b in emitted:
             pl = self._requests[t]
             pl["stream"].append(got[(t, b)])
             pl["frags"][b] = []                                         # the waveforms are delivered: the device memory goes
             self._frags.append((t, b, got[(t, b)]))
-            ev.append(("fragment", t, b))
-        for t in dict.fromkeys(t for t, _ in due):                      # after the last fragment: the request's result
-            if t in self._requests and pol.stream_done(t):
+        for t in ends:                                                  # after the last fragment: the request's result
+            if t in self._requests:
                 pl = self._requests.pop(t)
                 self._rows.pop(t, None)
                 self._drop_cfm(t)
-                out.append((t, pl["stream"]))
+                self._done.append((t, pl["stream"]))
+        return emitted
 
-    def _exclusive(self, t: int, out: list) -> None:
+    def _exclusive(self, t: int) -> None:
+        self._count(exclusive=1)
         req = self._requests.pop(t)
         try:
             if req.get("return_fragment") or req.get("streaming_mode"):
-                out.append((t, list(self.tts.run(dict(req, return_fragment=True)))))
-                self._frags += [(t, bi, f) for bi, f in enumerate(out[-1][1])]
+                frags = list(self.tts.run(dict(req, return_fragment=True)))
+                self._done.append((t, frags))
+                self._frags += [(t, bi, f) for bi, f in enumerate(frags)]
             else:
-                out.append((t, self.tts.run_batch([req])[0]))
+                self._done.append((t, self.tts.run_batch([req])[0]))
         except Exception as e:                                          # noqa: BLE001 -- the request's own result
-            out.append((t, e))
+            self._done.append((t, e))
 
     # -- continuous_cfm: the second session (class docstring)
-    def _cfm_round(self, out: list) -> None:
-        """stages 2-6 of a continuous_cfm step: encode the ready requests, admit rows, one session step, one fetch, vocode the
-        completed folds, deliver the completed requests.  A stage that raises fails the requests it was working on."""
-        pol, cp, ev, st = self._pol, self._cpol, self.stats["events"], self.stats
-        deliver = [t for t in pol.take_ready() if not self._encode(t, out)]
-        voiced = [(t, bi) for t, bi in pol.take_folds() if t in self._requests and not self._encode(t, out, bi)]
-        admitted = cp.admit()
-        if admitted:
-            ev.append(("cfm_admit", admitted))
-            self._cfm_admit(admitted, out)
-        if cp.live:
-            st["cfm_occupancy"].append(cp.dit_rows)
-            holders = sorted({cp.owner[s][0] for s in cp.live})
-            k, done, folds = cp.step()
-            ev.append(("cfm_step", k, [row for row, _ in done]))
-            try:
-                finished = self._cfm.step(k)
-                assert finished == sorted(s for _, s in done), f"the session reports slots {finished}, the policy {done}"
-                st["cfm_steps"] += k
-                staged = self._fetch(done) if done else {}
-            except Exception as e:                                      # noqa: BLE001 -- every request with a live row
-                self._close_cfm()                                       # the session goes; queued rows open the next one
-                self._fail(holders, e, out)
-                folds = []
-            if folds:
-                ev.append(("vocode", folds))
-                deliver += self._vocode(folds, staged, out)
-                voiced += [f for f in folds if f[0] in pol.stream]
-        self._emit(voiced, out)
-        deliver = [t for t in deliver if t in self._requests]           # a failed stage has answered for the others
-        if deliver:
-            ev.append(("deliver", deliver))
-            tts = self.tts
-            for t in deliver:
-                pl = self._requests.pop(t)
-                self._rows.pop(t, None)
-                self._drop_cfm(t)
-                try:
-                    tts._wait_stream()
-                    out.append((t, self._finished(t, pl, tts._finish_request(pl, tts._output_sr()))))
-                except Exception as e:                                  # noqa: BLE001 -- the request's own result
-                    out.append((t, e))
-
-    def _encode(self, t: int, out: list, fold: Optional[int] = None) -> bool:
-        """the first half of the shared flow-matching stage for one request; its rows join the FIFO.  False: it has no row.
-        fold: the same for that one fold of a streaming request, whose sentences are back (False: the fold has no frames)"""
+    def _encode(self, t: int, fold: Optional[int]) -> Dict[int, List[Tuple[int, bool]]]:
+        """the first half of the shared flow-matching stage for one request -- or for that one fold of a streaming request,
+        whose sentences are back -> the rows of each fold it encoded, which join the FIFO"""
         tts, pl = self.tts, self._requests[t]
-        if fold is not None:
-            try:
-                pl["kept"][fold] = tts._kept_tokens(pl["preds"][fold], pl["idxs"][fold], pl["no_prompt"])
-                tts._wait_stream()
-                _, fold_in, voice_of = tts._cfm_encode([pl], self._cfm_prompts, folds=[(0, fold)])
-                rows = [(steps, rate > 0.0) for _, steps, rate in tts.plan_cfm_rows([pl])]     # only `fold` has frames
-                c = self._cfm_req.setdefault(t, dict(vk=voice_of[0], fold_in={}, mel={}))
-                c["fold_in"].update({bi: v for (_, bi), v in fold_in.items()})
-                self.stats["cfm_folds"].setdefault(t, [[] for _ in pl["data"]])[fold] = rows
-                return self._cpol.enqueue_fold(t, fold, rows)
-            except Exception as e:                                      # noqa: BLE001 -- the request's own result
-                self._fail([t], e, out)
-                return True
-        try:
-            pl["kept"] = [tts._kept_tokens(p, i, pl["no_prompt"]) for p, i in zip(pl["preds"], pl["idxs"])]
-            tts._wait_stream()
-            _, fold_in, voice_of = tts._cfm_encode([pl], self._cfm_prompts)
-            folds: List[List[Tuple[int, bool]]] = [[] for _ in pl["data"]]
-            for (_, bi, _), steps, rate in tts.plan_cfm_rows([pl]):
-                folds[bi].append((steps, rate > 0.0))
-            self._cfm_req[t] = dict(vk=voice_of[0], fold_in={bi: v for (_, bi), v in fold_in.items()}, mel={})
-            self.stats["cfm_folds"][t] = folds
-            return self._cpol.enqueue(t, folds)
-        except Exception as e:                                          # noqa: BLE001 -- the request's own result
-            self._fail([t], e, out)
-            return True
+        folds = range(len(pl["data"])) if fold is None else [fold]
+        self._keep(pl, folds)
+        tts._wait_stream()
+        _, fold_in, voice_of = tts._cfm_encode([pl], self._cfm_prompts, **({} if fold is None else {"folds": [(0, fold)]}))
+        rows: Dict[int, List[Tuple[int, bool]]] = {bi: [] for bi in folds}
+        for (_, bi, _), steps, rate in tts.plan_cfm_rows([pl]):         # only the folds just encoded have frames
+            rows[bi].append((steps, rate > 0.0))
+        c = self._cfm_req.setdefault(t, dict(vk=voice_of[0], fold_in={}, mel={}))
+        c["fold_in"].update({bi: v for (_, bi), v in fold_in.items()})
+        self.stats["cfm_folds"].setdefault(t, [[] for _ in pl["data"]])
+        for bi in folds:
+            self.stats["cfm_folds"][t][bi] = rows[bi]
+        return rows
 
-    def _cfm_admit(self, admitted: List[Tuple[int, int, int, int]], out: list) -> None:
+    def _cfm_admit(self, admitted: List[Tuple[int, int, int, int]]) -> None:
         from .module.models import CFM
         tts, cp = self.tts, self._cpol
+        import torch
+        rows = [(self._requests[t], self._cfm_req[t], bi, k) for t, bi, k, _ in admitted]
+        mu = torch.cat([c["fold_in"][bi][0][k:k + 1] for _, c, bi, k in rows], 0)
+        if self._cfm is not None and self._cfm.rows_cap != cp.rows:      # 1 raised to 2 for a guided row: nothing is live
+            self._close_cfm()
+        if self._cfm is None:
+            self._cfm = tts.vits_model.cfm.open_session(cp.rows, int(mu.shape[1]))
+            self._count(cfm_sessions=1)
+        names = [pl["opts"].get("lora_voice") for pl, _, _, _ in rows]
+        rates = [float(pl["opts"].get("inference_cfg_rate", 0)) for pl, _, _, _ in rows]
+        guided = [cp.guided[s] for _, _, _, s in admitted]
+        self._cfm.admit(mu, [self._cfm_prompts[c["vk"]][3] for _, c, _, _ in rows], [int(pl["opts"]["sample_steps"]) for pl, _, _, _ in rows],
+                        [r if g else 0.0 for r, g in zip(rates, guided)],
+                        seeds=[CFM.row_seed(pl["actual_seed"] + bi, k) for pl, _, bi, k in rows],
+                        adapters=[None if n is None else tts._lora_voice(n)[1] for n in names] if any(names) else None,
+                        slots=[s for _, _, _, s in admitted])
+        self._count(cfm_admissions=1, cfm_rows=len(admitted))
+
+    def _cfm_step(self, k: int, done: list) -> Dict[Tuple[int, int], Any]:
+        """k Euler steps of the live rows and ONE fetch of those that finished (`done`, with their slots) -> the packed mel of
+        every fold that is now complete.  A step that raises takes the session with it: every request with a live row fails."""
+        cp = self._cpol
+        self.stats["cfm_occupancy"].append(cp.dit_rows + sum(2 if cp.guided[s] else 1 for _, s in done))   # live at its start
         try:
-            import torch
-            rows = [(self._requests[t], self._cfm_req[t], bi, k) for t, bi, k, _ in admitted]
-            mu = torch.cat([c["fold_in"][bi][0][k:k + 1] for _, c, bi, k in rows], 0)
-            if self._cfm is not None and self._cfm.rows_cap != cp.rows:      # 1 raised to 2 for a guided row: nothing is live
-                self._close_cfm()
-            if self._cfm is None:
-                self._cfm = tts.vits_model.cfm.open_session(cp.rows, int(mu.shape[1]))
-                self.stats["cfm_sessions"] += 1
-            names = [pl["opts"].get("lora_voice") for pl, _, _, _ in rows]
-            rates = [float(pl["opts"].get("inference_cfg_rate", 0)) for pl, _, _, _ in rows]
-            guided = [cp.guided[s] for _, _, _, s in admitted]
-            self._cfm.admit(mu, [self._cfm_prompts[c["vk"]][3] for _, c, _, _ in rows], [int(pl["opts"]["sample_steps"]) for pl, _, _, _ in rows],
-                            [r if g else 0.0 for r, g in zip(rates, guided)],
-                            seeds=[CFM.row_seed(pl["actual_seed"] + bi, k) for pl, _, bi, k in rows],
-                            adapters=[None if n is None else tts._lora_voice(n)[1] for n in names] if any(names) else None,
-                            slots=[s for _, _, _, s in admitted])
-            self.stats["cfm_admissions"] += 1
-            self.stats["cfm_rows"] += len(admitted)
-        except Exception as e:                                          # noqa: BLE001 -- the rows of this admission
-            self._fail(sorted({t for t, _, _, _ in admitted}), e, out)
+            finished = self._cfm.step(k)
+            assert finished == sorted(s for _, s in done), f"the session reports slots {finished}, the policy {done}"
+            self._count(cfm_steps=k)
+            return self._fetch(done) if done else {}
+        except Exception:
+            self._close_cfm()
+            raise
 
     def _fetch(self, done: list) -> Dict[Tuple[int, int], Any]:
         """ONE fetch_mel call for the slots that finished in this step, into a matrix of this step [mel][sum of the rows' frames]
@@ -963,9 +966,9 @@ class Scheduler:
             i = j
         return got
 
-    def _vocode(self, folds: List[Tuple[int, int]], staged: dict, out: list) -> List[int]:
+    def _vocode(self, folds: List[Tuple[int, int]], staged: dict) -> None:
         """the completed folds through the vocoder -- one forward_segments pass (at most vocoder_max_frames frames each) when
-        shared_vocoder, one call per fold otherwise -- and _fold_tail -> the requests whose folds are now all back"""
+        shared_vocoder, one call per fold otherwise -- and _fold_tail; a call that raises fails the requests of its folds"""
         import torch
         tts = self.tts
         calls: List[List[Tuple[int, int]]] = []
@@ -987,20 +990,19 @@ class Scheduler:
                     audios = [a[0][0] for a in tts.vocoder.forward_segments(mels)]
                 else:
                     audios = [tts.vocoder(m)[0][0] for m in mels]
-                self.stats["vocoder_calls"] += 1 if self._shared_vocoder else len(mels)
+                self._count(vocoder_calls=1 if self._shared_vocoder else len(mels))
                 for (t, bi), m, audio in zip(call, mels, audios):
                     rows, lens, pad_len = self._cfm_req[t]["fold_in"][bi]
                     self._requests[t]["frags"][bi] = tts._fold_tail(audio, int(m.shape[2]) // int(rows.shape[0]), lens, pad_len)
             except Exception as e:                                      # noqa: BLE001 -- the folds of this vocoder call
-                self._fail(sorted({t for t, _ in call}), e, out)
-        return self._cpol.vocoded(f for f in folds if f[0] in self._requests)
+                self._fail(sorted({t for t, _ in call}), e)
 
-    def _fail(self, tickets: Iterable[int], exc: BaseException, out: list) -> None:
+    def _fail(self, tickets: Iterable[int], exc: BaseException) -> None:
         """the requests get `exc` as their result; their rows, slots and buffers are dropped"""
         for t in tickets:
             if t in self._requests:
                 self._forget(t)                     # a streaming request may still have rows in the decode session
-                out.append((t, exc))
+                self._done.append((t, exc))
 
     def _drop_cfm(self, t: int) -> None:
         """forgets the request's flow-matching state: queued rows, live slots (released), fold buffers and, when no other
@@ -1010,7 +1012,7 @@ class Scheduler:
         slots = self._cpol.cancel(t)
         if slots and self._cfm is not None:
             self._cfm.release(slots)
-            self.stats["cfm_released"] += len(slots)
+            self._count(cfm_released=len(slots))
             self.stats["events"].append(("cfm_release", slots))
         c = self._cfm_req.pop(t, None)
         if c is not None and all(o["vk"] != c["vk"] for o in self._cfm_req.values()):
@@ -1022,15 +1024,12 @@ class Scheduler:
                 self._cfm.close()
             finally:
                 self._cfm = None
-        if self._cpol is not None:
-            self._cpol.open = False
 
-    def _close_session(self) -> None:
+    def _close_sessions(self) -> None:
         if self._ses is not None:
             self._ses.close()
             self.sessions.append(self._ses)
             self._ses = None
-        self._pol.open = False
         self._close_cfm()
 
 

@@ -6,7 +6,9 @@ import types
 import pytest
 
 from gsv.serving import Scheduler, plan_online
-from test_serving_plan import CASES, _case
+from _serving_cases import plan_case as _case
+
+CASES = 300
 
 U, G = False, True
 

@@ -1,30 +1,13 @@
 """CPU: gsv.serving.plan_online, the schedule the serving Scheduler follows, as a pure function: properties over seeded random
 arrival traces (slots 1-8, chunk 1-16, arrivals spread over 0-20 steps), and its equality with plan_continuous for a closed
 queue."""
-import random
-
 import pytest
 
 from gsv.AR.models.t2s_model import plan_continuous
 from gsv.serving import plan_online
+from _serving_cases import plan_case as _case
 
 CASES = 300
-
-
-def _case(seed, closed=False, with_exclusive=True):
-    rng = random.Random(seed)
-    n = rng.randint(1, 9)
-    slots, chunk = rng.randint(1, 8), rng.randint(1, 16)
-    admit_min = rng.choice([None, 1, rng.randint(1, slots)])
-    wave_hold = rng.choice([0, 0, 1, 3])
-    arrivals = [0] * n if closed else sorted(rng.randint(0, 20) for _ in range(n))
-    if not closed and rng.random() < 0.5:
-        rng.shuffle(arrivals)                       # request numbers need not follow arrival order
-    exclusive = {r for r in range(n) if with_exclusive and not closed and rng.random() < 0.2}
-    rows = [0 if r in exclusive else rng.randint(1, 5) for r in range(n)]
-    lengths = [rng.choice([0, rng.randint(1, 40)]) if rng.random() < 0.15 else rng.randint(1, 40) for _ in range(sum(rows))]
-    return dict(arrivals=arrivals, rows_per_request=rows, lengths=lengths, slots=slots, chunk=chunk, admit_min=admit_min,
-                wave_hold=wave_hold, exclusive=exclusive)
 
 
 def _fifo(c):

@@ -1,32 +1,14 @@
 """CPU: streaming requests in gsv.serving.plan_online -- the schedule of a Scheduler that delivers a `return_fragment` request
 fold by fold from inside its sessions -- as properties over seeded random traces, with and without the flow-matching session;
 and the scheduler's own intake decision (which streaming requests stay exclusive) over a pipeline stub that does no GPU work."""
-import random
 import types
 
 import pytest
 
 from gsv.serving import Scheduler, plan_online
+from _serving_cases import stream_case as _case
 
 CASES = 200
-
-
-def _case(seed, cfm=False):
-    rng = random.Random(seed)
-    n = rng.randint(1, 8)
-    slots, chunk = rng.randint(1, 8), rng.randint(1, 16)
-    arrivals = [rng.randint(0, 12) for _ in range(n)]
-    exclusive = {r for r in range(n) if rng.random() < 0.15}
-    folds = [[rng.randint(1, 3) for _ in range(rng.randint(1, 4))] for _ in range(n)]       # rows per fold, every request
-    rows = [0 if r in exclusive else sum(folds[r]) for r in range(n)]
-    lengths = [rng.choice([0, rng.randint(1, 40)]) for _ in range(sum(rows))]
-    streaming = {r: folds[r] for r in range(n) if rng.random() < 0.5}                   # may name exclusive requests too
-    c = dict(arrivals=arrivals, rows_per_request=rows, lengths=lengths, slots=slots, chunk=chunk,
-             admit_min=rng.choice([None, 1]), wave_hold=rng.choice([0, 1, 3]), exclusive=exclusive)
-    if cfm:
-        c.update(cfm_folds=[[[(rng.choice([1, 2, 4, 7]), rng.random() < 0.2) for _ in range(rng.choice([0, 1, 1, 2, 3]))] for _ in f]
-                            for f in folds], cfm_rows=rng.randint(2, 6), cfm_chunk=rng.randint(1, 3))
-    return c, streaming, folds
 
 
 @pytest.mark.parametrize("cfm", [False, True], ids=["sovits", "cfm"])

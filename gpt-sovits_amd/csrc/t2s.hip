@@ -1,5 +1,6 @@
-// AR semantic-token decoder engine (H1-H5) for gfx950: load / finalize, decode, and the debug / timing hooks.  The engine
-// state (gsv_t2s) is in t2s_engine.h, the prefill in t2s_prefill.hip, the persistent decode engine in t2s_mega.hip.
+// AR semantic-token decoder engine (H1-H5) for gfx950: the kernels and launchers of the decode step, load / finalize,
+// gsv_t2s_decode, and the debug / timing hooks.  The engine state (gsv_t2s, RowState) is in t2s_engine.h, the prefill in
+// t2s_prefill.hip, the persistent decode engine in t2s_mega.hip, the decode sessions in t2s_session.hip.
 //
 // State lives in HBM behind an opaque handle: weights in the engine dtype, a head-major KV
 // arena [layer][k|v][row][head][pos][head_dim] (so one (row, head) stream is contiguous and a
@@ -15,8 +16,8 @@
 //    launches (QKV+append, out-proj, FFN1, FFN2) and one attention launch, LayerNorm fused into the consumer's prologue,
 //    split-K across the waves of a workgroup with an LDS combine (no global partials), then logits + a one-wave-per-row
 //    sampling kernel; the step is captured once per batch size and replayed as one hipGraph.
-// gsv_t2s_session_* (bottom of the engine section) run the same two paths a chunk of steps at a time over slots that are admitted
-// and freed one by one; their kernels are in t2s_session.hip.
+// gsv_t2s_session_* (t2s_session.hip) run the same two paths, through run_chunk, a chunk of steps at a time over slots that are
+// admitted and freed one by one.
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
@@ -571,19 +572,20 @@ int with_npl(int V, F&& f) {
   return f(std::integral_constant<int, 32>{});
 }
 
-// The two X-operand forms of the decode GEMMs.  LayerNorm prologue: X = LN(ybuf) with gamma / beta (null: plain convert),
+// The two X-operand forms of the decode GEMMs.  LayerNorm prologue: X = LN(r.ybuf) with gamma / beta (null: plain convert),
 // the normalised fp32 rows also go to xres, the residual of the layer's next EPI_RESID; the caller adds the epilogue targets.
-DecGemmArgs ln_gemm(const gsv_t2s* h, const float* gamma, const float* beta, const void* w, const float* bias, int N, int epi) {
+DecGemmArgs ln_gemm(const gsv_t2s* h, const RowState& r, const float* gamma, const float* beta, const void* w, const float* bias,
+                    int N, int epi) {
   DecGemmArgs a;
-  a.yin = h->ybuf; a.gamma = gamma; a.beta = beta; a.xres_out = h->xres;
-  a.w = w; a.bias = bias; a.B = h->B; a.K = h->cfg.dim; a.N = N; a.epi = epi;
+  a.yin = r.ybuf; a.gamma = gamma; a.beta = beta; a.xres_out = h->xres;
+  a.w = w; a.bias = bias; a.B = r.B; a.K = h->cfg.dim; a.N = N; a.epi = epi;
   return a;
 }
 // Plain form: ybuf = xin W^T + bias + xres, xin [B][K] in the engine dtype
 DecGemmArgs resid_gemm(const gsv_t2s* h, const void* xin, const void* w, const float* bias, int K) {
   DecGemmArgs a;
-  a.xin = xin; a.w = w; a.bias = bias; a.B = h->B; a.K = K; a.N = h->cfg.dim; a.epi = EPI_RESID;
-  a.out_f = h->ybuf; a.xres = h->xres;
+  a.xin = xin; a.w = w; a.bias = bias; a.B = h->rows.B; a.K = K; a.N = h->cfg.dim; a.epi = EPI_RESID;
+  a.out_f = h->rows.ybuf; a.xres = h->xres;
   return a;
 }
 
@@ -595,26 +597,27 @@ int launch_decode_attn(const void* q, const void* kc, const void* vc, const int*
   return GSV_OK;
 }
 
-// the layers of one decode step; only_attn: the attention launches alone (gsv_t2s_time_step)
+// the layers of one decode step of h->rows; only_attn: the attention launches alone (gsv_t2s_time_step)
 template <typename T>
 int launch_decode_layers(gsv_t2s* h, hipStream_t s, bool only_attn) {
   const auto& c = h->cfg;
+  const RowState& r = h->rows;
   const int d = c.dim, H = c.n_head;
   for (int li = 0; li < c.n_layer; ++li) {
     const LayerW& L = h->layers[li];
     if (!only_attn) {
       // the previous layer's LN2 is this GEMM's prologue (layer 0: ybuf is the embedding, converted as it is)
       const LayerW* prev = li > 0 ? &h->layers[li - 1] : nullptr;
-      DecGemmArgs a = ln_gemm(h, prev ? prev->n2w : nullptr, prev ? prev->n2b : nullptr, L.qkv_w, L.qkv_b, 3 * d, EPI_QKV);
-      a.out_t = h->qbuf; a.kc = kv_ptr(h, li, 0); a.vc = kv_ptr(h, li, 1); a.kv_len = h->d_kv_len; a.active = h->d_active;
-      a.d = d; a.H = H; a.smax = h->max_seq;
+      DecGemmArgs a = ln_gemm(h, r, prev ? prev->n2w : nullptr, prev ? prev->n2b : nullptr, L.qkv_w, L.qkv_b, 3 * d, EPI_QKV);
+      a.out_t = h->qbuf; a.kc = kv_ptr(h, r, li, 0); a.vc = kv_ptr(h, r, li, 1); a.kv_len = r.kv_len(); a.active = r.active();
+      a.d = d; a.H = H; a.smax = r.max_seq;
       GSV_RC(launch_dec_gemm<T>(a, true, s));
     }
-    GSV_RC(launch_decode_attn<T>(h->qbuf, kv_ptr(h, li, 0), kv_ptr(h, li, 1), h->d_kv_len, h->d_active, h->B, H, h->max_seq,
+    GSV_RC(launch_decode_attn<T>(h->qbuf, kv_ptr(h, r, li, 0), kv_ptr(h, r, li, 1), r.kv_len(), r.active(), r.B, H, r.max_seq,
                                  h->abuf, s));
     if (only_attn) continue;
     GSV_RC(launch_dec_gemm<T>(resid_gemm(h, h->abuf, L.out_w, L.out_b, d), false, s));
-    DecGemmArgs f1 = ln_gemm(h, L.n1w, L.n1b, L.w1, L.b1, c.ffn_dim, EPI_RELU);
+    DecGemmArgs f1 = ln_gemm(h, r, L.n1w, L.n1b, L.w1, L.b1, c.ffn_dim, EPI_RELU);
     f1.out_t = h->hbuf;
     GSV_RC(launch_dec_gemm<T>(f1, true, s));
     GSV_RC(launch_dec_gemm<T>(resid_gemm(h, h->hbuf, L.w2, L.b2, c.ffn_dim), false, s));
@@ -622,20 +625,19 @@ int launch_decode_layers(gsv_t2s* h, hipStream_t s, bool only_attn) {
   return GSV_OK;
 }
 
-// logits (LN2 prologue of the last layer) + sampling/state update
+// logits (LN2 prologue of the last layer) + sampling/state update of the rows of r
 template <typename T>
-int launch_tail(gsv_t2s* h, hipStream_t s) {
+int launch_tail(gsv_t2s* h, RowState& r, hipStream_t s) {
   const auto& c = h->cfg;
   const LayerW& L = h->layers[c.n_layer - 1];
-  DecGemmArgs a = ln_gemm(h, L.n2w, L.n2b, h->pred_w, nullptr, c.vocab, EPI_LOGITS);
+  DecGemmArgs a = ln_gemm(h, r, L.n2w, L.n2b, h->pred_w, nullptr, c.vocab, EPI_LOGITS);
   a.xres_out = nullptr;   // no residual follows the last LayerNorm
-  a.out_f = h->logits;
+  a.out_f = r.logits;
   GSV_RC(launch_dec_gemm<T>(a, true, s));
   const int V = c.vocab, EOS = c.vocab - 1;
   return with_npl(V, [&](auto npl) -> int {
-    GSV_LAUNCH(sample_step_kernel<decltype(npl)::value>, dim3(h->B), dim3(64), (size_t)((V + 15) & ~15), s, h->logits, V, EOS,
-               h->d_sp, h->d_ytok, h->ycap, h->d_kv_len, h->d_active, h->d_step, h->d_n_active, h->e_audio, h->pe, h->alpha_a,
-               c.dim, h->ybuf);
+    GSV_LAUNCH(sample_step_kernel<decltype(npl)::value>, dim3(r.B), dim3(64), (size_t)((V + 15) & ~15), s, r.logits, V, EOS, r.sp,
+               r.ytok, h->ycap, r.kv_len(), r.active(), r.step(), r.n_active(), h->e_audio, h->pe, h->alpha_a, c.dim, r.ybuf);
     return GSV_OK;
   });
 }
@@ -643,65 +645,57 @@ int launch_tail(gsv_t2s* h, hipStream_t s) {
 template <typename T>
 int launch_step(gsv_t2s* h, hipStream_t s) {
   GSV_RC(launch_decode_layers<T>(h, s, false));
-  return launch_tail<T>(h, s);
+  return launch_tail<T>(h, h->rows, s);
 }
 
-// ---- gsv_t2s_decode in the order it runs: decode_begin, step 0 (launch_tail), then run_mega and / or run_steps ----
+// ---- gsv_t2s_decode in the order it runs: decode_begin, step 0 (launch_tail), then run_chunk: run_mega and / or run_steps, all
+// ---- three on h->rows ----
 
 // Uploads the call's sampling parameters and the rows' counter-RNG keys and checks that the request fits the arena, the
 // position table and the token history.  Returns the step budget (>= 1) or an error code (< 0).
 int decode_begin(gsv_t2s* h, const gsv_sampling_params* sp, const float* noise, int noise_rows, int32_t* out_tokens,
                  int32_t* out_len, hipStream_t s) {
-  StepParams p;
-  p.top_k = sp->top_k; p.top_p = sp->top_p; p.temperature = sp->temperature; p.rep_penalty = sp->repetition_penalty;
-  p.early_stop_num = sp->early_stop_num; p.eos_mask_steps = sp->eos_mask_steps; p.max_steps = sp->max_steps;
-  p.noise_rows = noise ? noise_rows : 0; p.seed = sp->seed; p.noise = noise; p.out_tokens = out_tokens; p.out_len = out_len;
-  p.plen = h->d_plen; p.rng_seed = h->d_rng_seed; p.rng_row = h->d_rng_row;
-  p.force = h->dbg_force; p.dump = h->dbg_dump; p.drawn = h->dbg_drawn;
-  h->dbg_force = nullptr; h->dbg_dump = nullptr; h->dbg_drawn = nullptr;
-  p.logp = h->logp_next; h->logp_next = nullptr;
-  h->logp_on = p.logp != nullptr;
-  // per-row sampling parameters: gsv_t2s_set_row_sampling's for this call (the four scalars above are then unused), else
+  const RowState& r = h->rows;
+  // per-row sampling parameters: gsv_t2s_set_row_sampling's for this call (the call's four scalars are then unused), else
   // null.  row_sampling_next stays until gsv_t2s_decode returns: a fallback re-run of the batch reads the same device array.
   const std::vector<gsv_row_sampling_t>& rsn = h->row_sampling_next;
-  p.row_sampling = rsn.empty() ? nullptr : h->d_row_sampling;
+  StepParams p = step_params(*sp, r, take_outputs(h, out_tokens, out_len), !rsn.empty());
+  p.noise = noise; p.noise_rows = noise ? noise_rows : 0;
   // counter-RNG keys of the rows: gsv_t2s_set_row_rng's for this call, else (seed, b) -- the draws of a batch without keys
   const bool keyed = !h->rng_seed_next.empty();
   const int nkeys = (int)h->rng_seed_next.size();
-  std::vector<unsigned long long> seeds(h->B);
-  std::vector<int> rows(h->B);
-  for (int b = 0; b < h->B && (!keyed || nkeys == h->B); ++b) {
+  std::vector<unsigned long long> seeds(r.B);
+  std::vector<int> rows(r.B);
+  for (int b = 0; b < r.B && (!keyed || nkeys == r.B); ++b) {
     seeds[b] = keyed ? h->rng_seed_next[b] : (unsigned long long)sp->seed;
     rows[b] = keyed ? h->rng_row_next[b] : b;
   }
   h->rng_seed_next.clear(); h->rng_row_next.clear();
-  GSV_REQUIRE(!keyed || nkeys == h->B, "t2s_decode: gsv_t2s_set_row_rng gave %d keys for a batch of %d rows", nkeys, h->B);
-  GSV_REQUIRE(rsn.empty() || (int)rsn.size() == h->B, "t2s_decode: gsv_t2s_set_row_sampling gave %d rows for a batch of %d rows",
-              (int)rsn.size(), h->B);
+  GSV_REQUIRE(!keyed || nkeys == r.B, "t2s_decode: gsv_t2s_set_row_rng gave %d keys for a batch of %d rows", nkeys, r.B);
+  GSV_REQUIRE(rsn.empty() || (int)rsn.size() == r.B, "t2s_decode: gsv_t2s_set_row_sampling gave %d rows for a batch of %d rows",
+              (int)rsn.size(), r.B);
   if (!rsn.empty() && (rsn.size() != h->row_sampling_up.size() ||
                        memcmp(rsn.data(), h->row_sampling_up.data(), rsn.size() * sizeof(gsv_row_sampling_t)) != 0)) {
-    GSV_HIP(hipMemcpyAsync(h->d_row_sampling, rsn.data(), rsn.size() * sizeof(gsv_row_sampling_t), hipMemcpyHostToDevice, s));
+    GSV_HIP(hipMemcpyAsync(r.row_sampling, rsn.data(), rsn.size() * sizeof(gsv_row_sampling_t), hipMemcpyHostToDevice, s));
     h->row_sampling_up = rsn;
   }
-  GSV_HIP(hipMemcpyAsync(h->d_sp, &p, sizeof(p), hipMemcpyHostToDevice, s));
+  GSV_HIP(hipMemcpyAsync(r.sp, &p, sizeof(p), hipMemcpyHostToDevice, s));
   if (seeds != h->rng_seed_up || rows != h->rng_row_up) {
-    GSV_HIP(hipMemcpyAsync(h->d_rng_seed, seeds.data(), (size_t)h->B * 8, hipMemcpyHostToDevice, s));
-    GSV_HIP(hipMemcpyAsync(h->d_rng_row, rows.data(), (size_t)h->B * 4, hipMemcpyHostToDevice, s));
+    GSV_HIP(hipMemcpyAsync(r.rng_seed, seeds.data(), (size_t)r.B * 8, hipMemcpyHostToDevice, s));
+    GSV_HIP(hipMemcpyAsync(r.rng_row, rows.data(), (size_t)r.B * 4, hipMemcpyHostToDevice, s));
     h->rng_seed_up = seeds; h->rng_row_up = rows;
   }
   GSV_HIP(hipStreamSynchronize(s));
-  // budget: step 0 samples from the prefill's last position, every later step appends one K/V position, so the
-  // longest row ends at max_kv0 + budget - 1 cached positions; the sampling tail of row b reads pe[P_b + step] and writes
-  // token history [P_b + step] (h->P is the longest prompt).  A request that does not fit is refused here: the kernels clamp out-of-range
-  // appends, which would otherwise yield silently wrong tokens with rc 0.
-  int budget = sp->max_steps;
-  if (sp->early_stop_num >= 0 && sp->early_stop_num + 1 < budget) budget = sp->early_stop_num + 1;
-  GSV_REQUIRE(h->max_kv0 + budget <= h->max_seq,
+  // the longest row ends at max_kv0 + budget - 1 cached positions; the sampling tail of row b reads pe[P_b + step] and writes
+  // token history [P_b + step] (r.P is the longest prompt).  A request that does not fit is refused here: the kernels clamp
+  // out-of-range appends, which would otherwise yield silently wrong tokens with rc 0.
+  const int budget = step_budget(*sp);
+  GSV_REQUIRE(r.max_kv0 + budget <= r.max_seq,
               "t2s_decode: %d cached positions + %d steps exceed the K/V arena (max_seq %d); lower max_steps / early_stop_num "
-              "or create the engine with a larger max_seq", h->max_kv0, budget, h->max_seq);
-  GSV_REQUIRE(h->P + budget <= h->pe_rows, "t2s_decode: prompt %d + %d steps exceed the position table (%d rows)", h->P, budget,
+              "or create the engine with a larger max_seq", r.max_kv0, budget, r.max_seq);
+  GSV_REQUIRE(r.P + budget <= h->pe_rows, "t2s_decode: prompt %d + %d steps exceed the position table (%d rows)", r.P, budget,
               h->pe_rows);
-  GSV_REQUIRE(h->P + budget <= h->ycap, "t2s_decode: prompt %d + %d steps exceed the token history (%d)", h->P, budget, h->ycap);
+  GSV_REQUIRE(r.P + budget <= h->ycap, "t2s_decode: prompt %d + %d steps exceed the token history (%d)", r.P, budget, h->ycap);
   return budget;
 }
 
@@ -720,13 +714,14 @@ MegaArgs mega_args(gsv_t2s* h, int budget) {
   // still be missing when sweep2's full passes start (logits hop)
   static const int hint_mask = env_int("GSV_MEGA_HINT", 13 | (1 << 7) | (2 << 8));
   MegaState& m = h->mega;
+  const RowState& r = h->rows;
   MegaArgs a;
   memset(&a, 0, sizeof(a));
   a.wpack = (const h8*)m.wpack; a.lpack = (const h8*)m.lpack; a.fpack = m.fpack;
-  a.kv = (_Float16*)h->kv; a.kv_layer_stride = h->kv_layer_stride; a.smax = h->max_seq;
-  a.kv_len = h->d_kv_len; a.active = h->d_active; a.step_ctr = h->d_step; a.n_active = h->d_n_active;
-  a.ytok = h->d_ytok; a.ycap = h->ycap; a.sp = h->d_sp; a.e_audio = h->e_audio; a.pe = h->pe; a.alpha_a = h->alpha_a;
-  a.ybuf = h->ybuf; a.logits_out = h->logits; a.hop = m.hop; a.err = m.err; a.B = h->B; a.L = h->cfg.n_layer; a.V = h->cfg.vocab;
+  a.kv = (_Float16*)r.kv; a.kv_layer_stride = r.kv_layer_stride; a.smax = r.max_seq;
+  a.kv_len = r.kv_len(); a.active = r.active(); a.step_ctr = r.step(); a.n_active = r.n_active();
+  a.ytok = r.ytok; a.ycap = h->ycap; a.sp = r.sp; a.e_audio = h->e_audio; a.pe = h->pe; a.alpha_a = h->alpha_a;
+  a.ybuf = r.ybuf; a.logits_out = r.logits; a.hop = m.hop; a.err = m.err; a.B = r.B; a.L = h->cfg.n_layer; a.V = h->cfg.vocab;
   a.nsteps = budget - 1; a.map_shared = map_local ? 0 : map_mode;
   a.hint_mask = hint_mask;
   a.ring = m.ring;
@@ -790,16 +785,17 @@ int run_mega(gsv_t2s* h, int budget, int32_t* out_len, hipStream_t s) {
   // launch-per-phase path (the engine only appends K/V behind kv_len and token history behind P_b + step: restoring the
   // counters makes both invisible again; ybuf, the first step's input, is read-only for the engine; P_b and the RNG keys
   // are read-only during a decode call)
-  const size_t mb = (size_t)h->max_batch;
-  GSV_HIP(hipMemcpyAsync(m.snap, h->d_kv_len, (3 * mb + 4) * 4, hipMemcpyDeviceToDevice, s));
-  GSV_HIP(hipMemcpyAsync(m.snap + 3 * mb + 4, out_len, h->B * 4, hipMemcpyDeviceToDevice, s));
+  const RowState& r = h->rows;
+  const size_t ns = r.state_ints();
+  GSV_HIP(hipMemcpyAsync(m.snap, r.state, ns * 4, hipMemcpyDeviceToDevice, s));
+  GSV_HIP(hipMemcpyAsync(m.snap + ns, out_len, r.B * 4, hipMemcpyDeviceToDevice, s));
   MegaArgs a = mega_args(h, budget);
   GSV_RC(mega_prof_arm(a, budget, s));
   GSV_HIP(hipEventRecord(h->mega_ev[0], s));
   GSV_RC(launch_t2s_mega(a, h->logp_on, s));
   GSV_HIP(hipEventRecord(h->mega_ev[1], s));
   GSV_HIP(hipMemcpyAsync(m.h_err, m.err, 16, hipMemcpyDeviceToHost, s));
-  GSV_HIP(hipMemcpyAsync(h->h_pinned, h->d_step, 4, hipMemcpyDeviceToHost, s));
+  GSV_HIP(hipMemcpyAsync(h->h_pinned, r.step(), 4, hipMemcpyDeviceToHost, s));
   GSV_HIP(hipStreamSynchronize(s));
   if (m.h_err[0] != 0u) {
     // A hand-off timed out (a member was not running: another kernel held its CU, or a fault).  The request is not
@@ -814,8 +810,8 @@ int run_mega(gsv_t2s* h, int budget, int32_t* out_len, hipStream_t s) {
     m.last_err[0] = m.h_err[1]; m.last_err[1] = m.h_err[2]; m.last_err[2] = m.h_err[3];
     if (a.prof) (void)hipFree(a.prof);
     if (getenv("GSV_MEGA_STRICT")) return GSV_ERR_STATE;
-    GSV_HIP(hipMemcpyAsync(h->d_kv_len, m.snap, (3 * mb + 4) * 4, hipMemcpyDeviceToDevice, s));
-    GSV_HIP(hipMemcpyAsync(out_len, m.snap + 3 * mb + 4, h->B * 4, hipMemcpyDeviceToDevice, s));
+    GSV_HIP(hipMemcpyAsync(r.state, m.snap, ns * 4, hipMemcpyDeviceToDevice, s));
+    GSV_HIP(hipMemcpyAsync(out_len, m.snap + ns, r.B * 4, hipMemcpyDeviceToDevice, s));
     return MEGA_FELL_BACK;
   }
   (void)hipEventElapsedTime(&h->last_decode_ms, h->mega_ev[0], h->mega_ev[1]);
@@ -830,8 +826,9 @@ int run_mega(gsv_t2s* h, int budget, int32_t* out_len, hipStream_t s) {
 // every 8 steps so a batch whose rows have all finished stops early.  Returns the steps run, step 0 included, in *steps_run.
 template <typename T>
 int run_steps(gsv_t2s* h, int budget, int* steps_run, hipStream_t s) {
+  const int B = h->rows.B;
   hipGraphExec_t exec = nullptr;
-  auto it = h->graphs.find(h->B);
+  auto it = h->graphs.find(B);
   if (it != h->graphs.end()) exec = it->second;
   else if (s != nullptr && !getenv("GSV_T2S_NO_GRAPH") && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
     hipGraph_t graph;
@@ -841,7 +838,7 @@ int run_steps(gsv_t2s* h, int budget, int* steps_run, hipStream_t s) {
     GSV_HIP(e);
     GSV_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
     (void)hipGraphDestroy(graph);
-    h->graphs[h->B] = exec;
+    h->graphs[B] = exec;
   } else {
     (void)hipGetLastError();  // legacy default stream cannot capture: eager launches instead
   }
@@ -852,7 +849,7 @@ int run_steps(gsv_t2s* h, int budget, int* steps_run, hipStream_t s) {
     else GSV_RC(launch_step<T>(h, s));
     ++steps;
     if (steps % check_every == 0 || steps == budget) {
-      GSV_HIP(hipMemcpyAsync(h->h_pinned, h->d_n_active, 4, hipMemcpyDeviceToHost, s));
+      GSV_HIP(hipMemcpyAsync(h->h_pinned, h->rows.n_active(), 4, hipMemcpyDeviceToHost, s));
       GSV_HIP(hipStreamSynchronize(s));
       if (h->h_pinned[0] <= 0) break;
     }
@@ -862,22 +859,13 @@ int run_steps(gsv_t2s* h, int budget, int* steps_run, hipStream_t s) {
   return GSV_OK;
 }
 
-template <typename T>
 int decode(gsv_t2s* h, const gsv_sampling_params* sp, const float* noise, int noise_rows, int32_t* out_tokens, int32_t* out_len,
            int* steps_run, hipStream_t s) {
   const int budget = decode_begin(h, sp, noise, noise_rows, out_tokens, out_len, s);
   if (budget < 0) return budget;
-  GSV_RC(launch_tail<T>(h, s));   // step 0: logits of the last prefill position, sample, emit the first embedding
+  GSV_RC(t2s_step0_tail(h, h->rows, s));
   h->last_decode_mode = 0; h->last_decode_ms = 0.f; h->last_decode_steps = 0;
-  if (h->mega.ready && h->mega_on && h->B <= MEGA_MAX_B && budget > 1) {
-    const int r = run_mega(h, budget, out_len, s);
-    if (r < 0) return r;
-    if (r == MEGA_DONE) {
-      if (steps_run) *steps_run = budget;
-      return GSV_OK;
-    }
-  }
-  return run_steps<T>(h, budget, steps_run, s);
+  return run_chunk(h, budget, out_len, steps_run, s);
 }
 
 // gsv_t2s_time_step: in-situ timing of the launch-per-phase step at the current cache state.  (a) The full per-layer kernel
@@ -886,10 +874,11 @@ int decode(gsv_t2s* h, const gsv_sampling_params* sp, const float* noise, int no
 // restored afterwards; no row state advances because the sampling tail is not launched.
 template <typename T>
 int time_step(gsv_t2s* h, int iters, float* step_ms, float* attn_ms, hipStream_t s) {
-  const int L = h->cfg.n_layer, B = h->B;
+  const int L = h->cfg.n_layer, B = h->rows.B;
+  int* d_active = h->rows.active();
   std::vector<int> saved(B), ones(B, 1);
-  GSV_HIP(hipMemcpy(saved.data(), h->d_active, B * 4, hipMemcpyDeviceToHost));
-  GSV_HIP(hipMemcpy(h->d_active, ones.data(), B * 4, hipMemcpyHostToDevice));
+  GSV_HIP(hipMemcpy(saved.data(), d_active, B * 4, hipMemcpyDeviceToHost));
+  GSV_HIP(hipMemcpy(d_active, ones.data(), B * 4, hipMemcpyHostToDevice));
   hipEvent_t ev[4];
   for (auto& e : ev) GSV_HIP(hipEventCreate(&e));
   int rc = GSV_OK;
@@ -909,7 +898,7 @@ int time_step(gsv_t2s* h, int iters, float* step_ms, float* attn_ms, hipStream_t
     GSV_HIP(hipStreamSynchronize(s));
     if (!rc) GSV_HIP(hipEventElapsedTime(&attn_total, ev[0], ev[1]));
   }
-  GSV_HIP(hipMemcpy(h->d_active, saved.data(), B * 4, hipMemcpyHostToDevice));
+  GSV_HIP(hipMemcpy(d_active, saved.data(), B * 4, hipMemcpyHostToDevice));
   if (!rc) {
     if (attn_ms) *attn_ms = attn_total / (float)(iters * L);
     float ms = 0.f;
@@ -920,217 +909,34 @@ int time_step(gsv_t2s* h, int iters, float* step_ms, float* attn_ms, hipStream_t
   return rc;
 }
 
-// ---- decode sessions (gsv_t2s_session_*): admit = prefill + step 0 in the staging copies, then the adopt launch; advance =
-// ---- the embedding rewrite, then run_mega / run_steps for a chunk.  Kernels in t2s_session.hip. ----
-
-// Points the handle at the session's staging copies of the arena and the row state for the lifetime of the object, so that the
-// prefill and launch_tail run unchanged on rows 0 .. n - 1 of the staging side; the destructor puts the session's own back.
-struct StagingScope {
-  gsv_t2s* h;
-  void* kv; size_t stride; int max_seq;
-  int *kv_len, *active, *step, *n_active, *ytok, *plen, *rng_row;
-  unsigned long long* rng_seed;
-  RowSampling* row_sampling; StepParams* sp;
-  float *ybuf, *logits;
-  int B, P, max_kv0;
-  StagingScope(gsv_t2s* h_, void* st_kv, size_t st_stride, int st_smax)
-      : h(h_), kv(h_->kv), stride(h_->kv_layer_stride), max_seq(h_->max_seq), kv_len(h_->d_kv_len), active(h_->d_active),
-        step(h_->d_step), n_active(h_->d_n_active), ytok(h_->d_ytok), plen(h_->d_plen), rng_row(h_->d_rng_row),
-        rng_seed(h_->d_rng_seed), row_sampling(h_->d_row_sampling), sp(h_->d_sp), ybuf(h_->ybuf), logits(h_->logits), B(h_->B),
-        P(h_->P), max_kv0(h_->max_kv0) {
-    const T2SSession& z = h->ses;
-    const size_t mb = (size_t)h->max_batch;
-    h->kv = st_kv; h->kv_layer_stride = st_stride; h->max_seq = st_smax;
-    h->d_kv_len = z.st_state; h->d_active = z.st_state + mb; h->d_step = z.st_state + 2 * mb; h->d_n_active = z.st_state + 3 * mb;
-    h->d_ytok = z.st_ytok; h->d_plen = z.st_plen; h->d_rng_row = z.st_rng_row; h->d_rng_seed = z.st_rng_seed;
-    h->d_row_sampling = z.st_row_sampling; h->d_sp = z.st_sp; h->ybuf = z.st_ybuf; h->logits = z.st_logits;
-  }
-  ~StagingScope() {
-    h->kv = kv; h->kv_layer_stride = stride; h->max_seq = max_seq;
-    h->d_kv_len = kv_len; h->d_active = active; h->d_step = step; h->d_n_active = n_active;
-    h->d_ytok = ytok; h->d_plen = plen; h->d_rng_row = rng_row; h->d_rng_seed = rng_seed;
-    h->d_row_sampling = row_sampling; h->d_sp = sp; h->ybuf = ybuf; h->logits = logits;
-    h->B = B; h->P = P; h->max_kv0 = max_kv0;
-  }
-};
-
-// the session's StepParams: its own arrays (staging = false) or the staging copies an admission's step 0 runs on
-StepParams session_params(const gsv_t2s* h, bool staging) {
-  const T2SSession& z = h->ses;
-  StepParams p;
-  memset(&p, 0, sizeof(p));
-  p.top_k = z.sp.top_k; p.top_p = z.sp.top_p; p.temperature = z.sp.temperature; p.rep_penalty = z.sp.repetition_penalty;
-  p.early_stop_num = z.sp.early_stop_num; p.eos_mask_steps = z.sp.eos_mask_steps; p.max_steps = z.sp.max_steps;
-  p.seed = z.sp.seed;
-  if (staging) {
-    p.out_tokens = z.st_out_tokens; p.out_len = z.st_out_len; p.plen = z.st_plen; p.rng_seed = z.st_rng_seed;
-    p.rng_row = z.st_rng_row; p.force = z.force ? z.st_force : nullptr; p.dump = z.dump ? z.st_dump : nullptr;
-    p.drawn = z.drawn ? z.st_drawn : nullptr; p.row_sampling = z.row_sampling ? z.st_row_sampling : nullptr;
-    p.logp = z.logp ? z.st_logp : nullptr;
-  } else {
-    p.out_tokens = z.out_tokens; p.out_len = z.out_len; p.plen = h->d_plen; p.rng_seed = h->d_rng_seed; p.rng_row = h->d_rng_row;
-    p.force = z.force; p.dump = z.dump; p.drawn = z.drawn; p.row_sampling = z.row_sampling ? h->d_row_sampling : nullptr;
-    p.logp = z.logp;
-  }
-  return p;
-}
-
-int session_budget(const gsv_sampling_params& sp) {
-  int budget = sp.max_steps;
-  if (sp.early_stop_num >= 0 && sp.early_stop_num + 1 < budget) budget = sp.early_stop_num + 1;
-  return budget;
-}
-
-int session_begin(gsv_t2s* h, const gsv_sampling_params* sp, int slots, int row_sampling, int32_t* out_tokens, int32_t* out_len) {
-  T2SSession& z = h->ses;
-  const size_t mb = (size_t)h->max_batch, d = h->cfg.dim, V = h->cfg.vocab, ms = (size_t)sp->max_steps;
-  // staging copies of everything a prefill and a step-0 tail write (the staging K/V arena is sized by each admission)
-  GSV_RC(need(h, "ses_state", (3 * mb + 4) * 4, (void**)&z.st_state));
-  GSV_RC(need(h, "ses_plen", 2 * mb * 4, (void**)&z.st_plen));
-  GSV_RC(need(h, "ses_ytok", mb * h->ycap * 4, (void**)&z.st_ytok));
-  GSV_RC(need(h, "ses_rng_row", mb * 4, (void**)&z.st_rng_row));
-  GSV_RC(need(h, "ses_rng_seed", mb * 8, (void**)&z.st_rng_seed));
-  GSV_RC(need(h, "ses_row_sampling", mb * sizeof(RowSampling), (void**)&z.st_row_sampling));
-  GSV_RC(need(h, "ses_sp", sizeof(StepParams), (void**)&z.st_sp));
-  GSV_RC(need(h, "ses_out_tokens", mb * ms * 4, (void**)&z.st_out_tokens));
-  GSV_RC(need(h, "ses_out_len", mb * 4, (void**)&z.st_out_len));
-  GSV_RC(need(h, "ses_slot", mb * 4, (void**)&z.st_slot));
-  GSV_RC(need(h, "ses_force", mb * ms * 4, (void**)&z.st_force));
-  GSV_RC(need(h, "ses_drawn", mb * 2 * 4, (void**)&z.st_drawn));
-  GSV_RC(need(h, "ses_ybuf", mb * d * 4, (void**)&z.st_ybuf));
-  GSV_RC(need(h, "ses_logits", mb * V * 4, (void**)&z.st_logits));
-  GSV_RC(need(h, "ses_dump", mb * V * 4, (void**)&z.st_dump));
-  GSV_RC(need(h, "ses_logp", mb * ms * 4, (void**)&z.st_logp));
-  GSV_HIP(hipMemset(z.st_logits, 0, mb * V * 4));
-  for (auto& e : z.ev) if (!e) GSV_HIP(hipEventCreate(&e));
-  z.sp = *sp; z.slots = slots; z.budget = session_budget(*sp); z.row_sampling = row_sampling != 0;
-  z.out_tokens = out_tokens; z.out_len = out_len;
-  z.force = h->dbg_force; z.dump = h->dbg_dump; z.drawn = h->dbg_drawn;
-  h->dbg_force = nullptr; h->dbg_dump = nullptr; h->dbg_drawn = nullptr;
-  z.logp = h->logp_next; h->logp_next = nullptr;
-  h->logp_on = z.logp != nullptr;
-  // every slot free: active = 0, and every per-row array the kernels load for a free slot holds zeros
-  GSV_HIP(hipMemset(h->d_kv_len, 0, (3 * mb + 4) * 4));
-  GSV_HIP(hipMemset(h->d_plen, 0, 2 * mb * 4));
-  GSV_HIP(hipMemset(h->d_rng_seed, 0, mb * 8));
-  GSV_HIP(hipMemset(h->d_rng_row, 0, mb * 4));
-  GSV_HIP(hipMemset(h->d_row_sampling, 0, mb * sizeof(RowSampling)));
-  GSV_HIP(hipMemset(h->ybuf, 0, mb * d * 4));
-  h->rng_seed_up.clear(); h->rng_row_up.clear(); h->row_sampling_up.clear();   // the device arrays are the session's now
-  h->rng_seed_next.clear(); h->rng_row_next.clear(); h->row_sampling_next.clear();
-  const StepParams p = session_params(h, false), ps = session_params(h, true);
-  GSV_HIP(hipMemcpy(h->d_sp, &p, sizeof(p), hipMemcpyHostToDevice));
-  GSV_HIP(hipMemcpy(z.st_sp, &ps, sizeof(ps), hipMemcpyHostToDevice));
-  h->B = slots; h->P = 0; h->max_kv0 = 0;
-  z.live.assign(slots, 0);
-  z.last_adopt_ms = 0.f; z.last_adopt_bytes = 0;
-  z.open = true;
-  return GSV_OK;
-}
-
-template <typename T>
-int session_admit(gsv_t2s* h, int n, const int32_t* slot_ids, const int32_t* phones, const int32_t* phone_lens, const float* bert,
-                  const int32_t* prompts_packed, const int32_t* prompt_lens, const uint64_t* rng_seeds, const int32_t* rng_rows,
-                  const gsv_row_sampling_t* row_sampling, hipStream_t s) {
-  T2SSession& z = h->ses;
-  const auto& c = h->cfg;
-  const size_t mb = (size_t)h->max_batch, ms = (size_t)z.sp.max_steps;
-  int maxS = 0;
-  long long positions = 0;
-  for (int i = 0; i < n; ++i) {
-    const int S = phone_lens[i] + prompt_lens[i];
-    maxS = S > maxS ? S : maxS;
-    positions += S;
-  }
-  const int st_smax = maxS + 2;
-  const size_t st_stride = (size_t)n * c.dim * st_smax;
-  void* st_kv = nullptr;
-  GSV_RC(need(h, "ses_kv", (size_t)c.n_layer * 2 * st_stride * esz(h), &st_kv));
-  GSV_HIP(hipMemcpyAsync(z.st_rng_seed, rng_seeds, (size_t)n * 8, hipMemcpyHostToDevice, s));
-  GSV_HIP(hipMemcpyAsync(z.st_rng_row, rng_rows, (size_t)n * 4, hipMemcpyHostToDevice, s));
-  GSV_HIP(hipMemcpyAsync(z.st_slot, slot_ids, (size_t)n * 4, hipMemcpyHostToDevice, s));
-  if (z.row_sampling)
-    GSV_HIP(hipMemcpyAsync(z.st_row_sampling, row_sampling, (size_t)n * sizeof(RowSampling), hipMemcpyHostToDevice, s));
-  GSV_HIP(hipMemsetAsync(z.st_out_len, 0xFF, (size_t)n * 4, s));     // -1: not finished
-  if (z.force)   // step 0 of row i is forced with its slot's entry
-    for (int i = 0; i < n; ++i)
-      GSV_HIP(hipMemcpyAsync(z.st_force + (size_t)i * ms, z.force + (size_t)slot_ids[i] * ms, 4, hipMemcpyDeviceToDevice, s));
-  int rc;
-  {
-    StagingScope staging(h, st_kv, st_stride, st_smax);
-    rc = t2s_prefill_into(h, phones, phone_lens, n, bert, prompts_packed, prompt_lens, s);
-    if (!rc) rc = launch_tail<T>(h, s);   // step 0: the rows now stand where gsv_t2s_decode's rows stand after its step 0
-  }
-  if (rc) return rc;
-  AdoptArgs a;
-  a.src_kv = st_kv; a.dst_kv = h->kv; a.src_layer_stride = st_stride; a.dst_layer_stride = h->kv_layer_stride;
-  a.src_smax = st_smax; a.dst_smax = h->max_seq; a.L = c.n_layer; a.H = c.n_head; a.esize = (int)esz(h);
-  a.n = n; a.slots = z.slots; a.mb = (int)mb; a.ycap = h->ycap; a.d = c.dim; a.V = c.vocab;
-  a.src_steps = (int)ms; a.dst_steps = (int)ms;
-  a.slot = z.st_slot;
-  a.src_state = z.st_state; a.src_plen = z.st_plen; a.src_ytok = z.st_ytok; a.src_rng_row = z.st_rng_row;
-  a.src_out_tokens = z.st_out_tokens; a.src_out_len = z.st_out_len; a.src_drawn = z.st_drawn; a.src_rng_seed = z.st_rng_seed;
-  a.src_row_sampling = z.st_row_sampling; a.src_ybuf = z.st_ybuf; a.src_dump = z.st_dump;
-  a.dst_state = h->d_kv_len; a.dst_plen = h->d_plen; a.dst_ytok = h->d_ytok; a.dst_rng_row = h->d_rng_row;
-  a.dst_out_tokens = z.out_tokens; a.dst_out_len = z.out_len; a.dst_drawn = z.drawn; a.dst_rng_seed = h->d_rng_seed;
-  a.dst_row_sampling = z.row_sampling ? h->d_row_sampling : nullptr; a.dst_ybuf = h->ybuf; a.dst_dump = z.dump;
-  a.src_logp = z.st_logp; a.dst_logp = z.logp;
-  GSV_HIP(hipEventRecord(z.ev[0], s));
-  GSV_RC(launch_session_adopt(a, s));
-  GSV_HIP(hipEventRecord(z.ev[1], s));
-  std::vector<int> act(n);
-  GSV_HIP(hipMemcpyAsync(act.data(), z.st_state + mb, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-  GSV_HIP(hipStreamSynchronize(s));
-  for (int i = 0; i < n; ++i) z.live[slot_ids[i]] = act[i] != 0;
-  (void)hipEventElapsedTime(&z.last_adopt_ms, z.ev[0], z.ev[1]);
-  z.last_adopt_bytes = positions * c.n_layer * 2 * c.dim * (long long)esz(h);
-  return GSV_OK;
-}
-
-template <typename T>
-int session_advance(gsv_t2s* h, int n_steps, int* live_out, int* steps_out, hipStream_t s) {
-  T2SSession& z = h->ses;
-  const size_t mb = (size_t)h->max_batch;
-  bool any = false;
-  for (char l : z.live) any = any || l;
-  h->last_decode_mode = 0; h->last_decode_ms = 0.f; h->last_decode_steps = 0;
-  if (any) {
-    GSV_RC(launch_session_embed(h->d_kv_len, (int)mb, h->d_plen, h->d_ytok, h->ycap, h->e_audio, h->pe, h->alpha_a, h->cfg.dim,
-                                h->cfg.vocab, z.slots, h->ybuf, s));
-    // a chunk is a decode call whose step 0 has been run: n_steps steps of run_mega / run_steps are "budget" n_steps + 1
-    bool done = false;
-    if (h->mega.ready && h->mega_on && z.slots <= MEGA_MAX_B) {
-      const int r = run_mega(h, n_steps + 1, z.out_len, s);
-      if (r < 0) return r;
-      done = r == MEGA_DONE;   // else the snapshot is back: this chunk runs on the launch-per-phase step
-    }
-    if (!done) {
-      GSV_RC(run_steps<T>(h, n_steps + 1, nullptr, s));
-      h->last_decode_steps = n_steps;
-    }
-  }
-  std::vector<int> st(3 * mb);
-  GSV_HIP(hipMemcpyAsync(st.data(), h->d_kv_len, 3 * mb * 4, hipMemcpyDeviceToHost, s));
-  GSV_HIP(hipStreamSynchronize(s));
-  for (int b = 0; b < z.slots; ++b) {
-    z.live[b] = st[mb + b] != 0;
-    if (live_out) live_out[b] = st[mb + b] != 0;
-    if (steps_out) steps_out[b] = st[2 * mb + b];
-  }
-  return GSV_OK;
-}
-
-// the slots are distinct and inside the session (checked by the caller): one launch on the state block, then the host mirror
-int session_release(gsv_t2s* h, int n, const int32_t* slot_ids, hipStream_t s) {
-  T2SSession& z = h->ses;
-  GSV_HIP(hipMemcpyAsync(z.st_slot, slot_ids, (size_t)n * 4, hipMemcpyHostToDevice, s));
-  GSV_RC(launch_session_release(h->d_kv_len, h->max_batch, z.st_slot, n, z.slots, s));
-  GSV_HIP(hipStreamSynchronize(s));
-  for (int i = 0; i < n; ++i) z.live[slot_ids[i]] = 0;
-  return GSV_OK;
-}
-
 }  // namespace
+
+int t2s_step0_tail(gsv_t2s* h, RowState& r, hipStream_t s) { return GSV_WITH_T(h, launch_tail<T>(h, r, s)); }
+
+int run_chunk(gsv_t2s* h, int budget, int32_t* out_len, int* steps_run, hipStream_t s) {
+  if (h->mega.ready && h->mega_on && h->rows.B <= MEGA_MAX_B && budget > 1) {
+    const int r = run_mega(h, budget, out_len, s);
+    if (r < 0) return r;
+    if (r == MEGA_DONE) {
+      if (steps_run) *steps_run = budget;
+      return GSV_OK;
+    }
+  }
+  return GSV_WITH_T(h, run_steps<T>(h, budget, steps_run, s));   // also after MEGA_FELL_BACK: the snapshot is back
+}
+
+int check_row_sampling(const char* who, const gsv_row_sampling_t* rows, int B) {
+  for (int b = 0; b < B; ++b) {
+    const gsv_row_sampling_t& r = rows[b];
+    GSV_REQUIRE(r.top_k >= 0, "%s: row %d: top_k %d must be >= 0", who, b, r.top_k);
+    GSV_REQUIRE(r.top_p > 0.f && r.top_p <= 1.f, "%s: row %d: top_p %g must be in (0, 1]", who, b, (double)r.top_p);
+    GSV_REQUIRE(isfinite(r.temperature) && r.temperature >= 0.f, "%s: row %d: temperature %g must be finite and >= 0", who,
+                b, (double)r.temperature);
+    GSV_REQUIRE(isfinite(r.repetition_penalty) && r.repetition_penalty > 0.f,
+                "%s: row %d: repetition_penalty %g must be finite and > 0", who, b, (double)r.repetition_penalty);
+  }
+  return GSV_OK;
+}
 
 extern "C" {
 
@@ -1147,7 +953,7 @@ int gsv_t2s_create(const gsv_t2s_config* cfg, int dtype, int max_batch, int max_
   h->cfg = *cfg;
   h->dtype = dtype;
   h->max_batch = max_batch;
-  h->max_seq = max_seq;
+  h->rows.max_seq = max_seq; h->rows.mb = max_batch;
   h->layers.resize(cfg->n_layer);
   *out = h;
   return GSV_OK;
@@ -1188,7 +994,7 @@ int gsv_t2s_finalize(gsv_t2s_t* h) {
     auto it = h->staged.find("pe");
     GSV_REQUIRE(it != h->staged.end() && it->second.size() % d == 0, "t2s: missing sinusoid table 'pe' [n_pos][dim]");
     h->pe_rows = (int)(it->second.size() / d);
-    GSV_REQUIRE(h->max_seq <= h->pe_rows, "t2s: max_seq %d exceeds the position table (%d rows)", h->max_seq, h->pe_rows);
+    GSV_REQUIRE(h->rows.max_seq <= h->pe_rows, "t2s: max_seq %d exceeds the position table (%d rows)", h->rows.max_seq, h->pe_rows);
     GSV_RC(up_f32(h, it->second.data(), it->second.size(), &h->pe));
   }
   GSV_RC(make_mat(h, "ar_predict_layer.weight", V * d, &h->pred_w));
@@ -1247,29 +1053,28 @@ int gsv_t2s_finalize(gsv_t2s_t* h) {
   }
   h->staged.clear();
   const size_t B = h->max_batch, es = esz(h);
-  h->kv_layer_stride = B * d * (size_t)h->max_seq;
-  GSV_RC(dalloc(h, &h->kv, (size_t)c.n_layer * 2 * h->kv_layer_stride * es));
+  RowState& r = h->rows;   // max_seq and mb are gsv_t2s_create's
+  r.kv_layer_stride = B * d * (size_t)r.max_seq;
+  GSV_RC(dalloc(h, &r.kv, (size_t)c.n_layer * 2 * r.kv_layer_stride * es));
   GSV_RC(dalloc(h, (void**)&h->d_x_len, B * 4));
   GSV_RC(dalloc(h, (void**)&h->d_row_off, B * 4));
   GSV_RC(dalloc(h, (void**)&h->d_ph_off, B * 4));
-  // one block [kv_len | active | step | n_active]: the persistent engine's fallback saves and restores it with one copy
-  GSV_RC(dalloc(h, (void**)&h->d_kv_len, (3 * B + 4) * 4));
-  h->d_active = h->d_kv_len + B; h->d_step = h->d_kv_len + 2 * B; h->d_n_active = h->d_kv_len + 3 * B;
-  h->ycap = h->max_seq + 8;
-  GSV_RC(dalloc(h, (void**)&h->d_ytok, B * h->ycap * 4));
-  GSV_RC(dalloc(h, (void**)&h->d_plen, 2 * B * 4));
-  GSV_RC(dalloc(h, (void**)&h->d_rng_seed, B * 8));
-  GSV_RC(dalloc(h, (void**)&h->d_rng_row, B * 4));
-  GSV_RC(dalloc(h, (void**)&h->d_row_sampling, B * sizeof(RowSampling)));
-  GSV_RC(dalloc(h, (void**)&h->d_sp, sizeof(StepParams)));
+  GSV_RC(dalloc(h, (void**)&r.state, r.state_ints() * 4));
+  h->ycap = r.max_seq + 8;
+  GSV_RC(dalloc(h, (void**)&r.ytok, B * h->ycap * 4));
+  GSV_RC(dalloc(h, (void**)&r.plen, 2 * B * 4));
+  GSV_RC(dalloc(h, (void**)&r.rng_seed, B * 8));
+  GSV_RC(dalloc(h, (void**)&r.rng_row, B * 4));
+  GSV_RC(dalloc(h, (void**)&r.row_sampling, B * sizeof(RowSampling)));
+  GSV_RC(dalloc(h, (void**)&r.sp, sizeof(StepParams)));
   GSV_HIP(hipHostMalloc((void**)&h->h_pinned, 64));
-  GSV_RC(dalloc(h, (void**)&h->ybuf, B * d * 4));
+  GSV_RC(dalloc(h, (void**)&r.ybuf, B * d * 4));
   GSV_RC(dalloc(h, (void**)&h->xres, B * d * 4));
-  GSV_RC(dalloc(h, (void**)&h->logits, B * V * 4));
+  GSV_RC(dalloc(h, (void**)&r.logits, B * V * 4));
   GSV_RC(dalloc(h, &h->qbuf, B * d * es));
   GSV_RC(dalloc(h, &h->abuf, B * d * es));
   GSV_RC(dalloc(h, &h->hbuf, B * ff * es));
-  GSV_HIP(hipMemset(h->logits, 0, B * V * 4));
+  GSV_HIP(hipMemset(r.logits, 0, B * V * 4));
   h->finalized = true;
   return GSV_OK;
 }
@@ -1279,20 +1084,6 @@ int gsv_t2s_set_row_rng(gsv_t2s_t* h, const uint64_t* seeds, const int32_t* rows
   GSV_REQUIRE(seeds && rows && B >= 1 && B <= h->max_batch, "t2s_set_row_rng: bad argument (B = %d)", B);
   h->rng_seed_next.assign(seeds, seeds + B);
   h->rng_row_next.assign(rows, rows + B);
-  return GSV_OK;
-}
-
-// the value checks of gsv_t2s_set_row_sampling and gsv_op_sample_rows
-static int check_row_sampling(const char* who, const gsv_row_sampling_t* rows, int B) {
-  for (int b = 0; b < B; ++b) {
-    const gsv_row_sampling_t& r = rows[b];
-    GSV_REQUIRE(r.top_k >= 0, "%s: row %d: top_k %d must be >= 0", who, b, r.top_k);
-    GSV_REQUIRE(r.top_p > 0.f && r.top_p <= 1.f, "%s: row %d: top_p %g must be in (0, 1]", who, b, (double)r.top_p);
-    GSV_REQUIRE(isfinite(r.temperature) && r.temperature >= 0.f, "%s: row %d: temperature %g must be finite and >= 0", who,
-                b, (double)r.temperature);
-    GSV_REQUIRE(isfinite(r.repetition_penalty) && r.repetition_penalty > 0.f,
-                "%s: row %d: repetition_penalty %g must be finite and > 0", who, b, (double)r.repetition_penalty);
-  }
   return GSV_OK;
 }
 
@@ -1307,131 +1098,14 @@ int gsv_t2s_set_row_sampling(gsv_t2s_t* h, const gsv_row_sampling_t* rows, int B
 int gsv_t2s_decode(gsv_t2s_t* h, const gsv_sampling_params* sp, const float* noise, int noise_rows,
                    int32_t* out_tokens, int32_t* out_len, int* steps_run, gsv_stream_t stream) {
   GSV_REQUIRE(h && h->finalized, "t2s_decode: handle not finalized");
-  if (h->ses.open) {
-    set_error("t2s_decode: a decode session is open on this handle (gsv_t2s_session_end closes it)");
-    return GSV_ERR_STATE;
-  }
-  GSV_REQUIRE(h->B > 0, "t2s_decode: call gsv_t2s_prefill first");
+  GSV_T2S_NO_SESSION(h, "t2s_decode");
+  GSV_REQUIRE(h->rows.B > 0, "t2s_decode: call gsv_t2s_prefill first");
   // the per-row sampling parameters are this call's alone, whatever becomes of it
   struct Clear { gsv_t2s_t* h; ~Clear() { h->row_sampling_next.clear(); } } clear{h};
   GSV_REQUIRE(sp && out_tokens && out_len, "t2s_decode: null argument");
   GSV_REQUIRE(sp->max_steps >= 1, "t2s_decode: max_steps must be >= 1");
-  GSV_REQUIRE(noise == nullptr || noise_rows == 1 || noise_rows == h->B, "t2s_decode: noise_rows must be 1 or B");
-  return GSV_WITH_T(h, decode<T>(h, sp, noise, noise_rows, out_tokens, out_len, steps_run, (hipStream_t)stream));
-}
-
-int gsv_t2s_session_begin(gsv_t2s_t* h, const gsv_sampling_params* sp, int slots, int row_sampling, int32_t* out_tokens,
-                          int32_t* out_len) {
-  GSV_REQUIRE(h && h->finalized, "t2s_session_begin: handle not finalized");
-  if (h->ses.open) {
-    set_error("t2s_session_begin: a decode session is already open on this handle");
-    return GSV_ERR_STATE;
-  }
-  GSV_REQUIRE(sp && out_tokens && out_len, "t2s_session_begin: null argument");
-  GSV_REQUIRE(slots >= 1 && slots <= h->max_batch, "t2s_session_begin: %d slots, max_batch is %d", slots, h->max_batch);
-  GSV_REQUIRE(sp->max_steps >= 1, "t2s_session_begin: max_steps must be >= 1");
-  return session_begin(h, sp, slots, row_sampling, out_tokens, out_len);
-}
-
-int gsv_t2s_session_admit(gsv_t2s_t* h, int n, const int32_t* slot_ids, const int32_t* phones, const int32_t* phone_lens,
-                          const float* bert, const int32_t* prompts_packed, const int32_t* prompt_lens, const uint64_t* rng_seeds,
-                          const int32_t* rng_rows, const gsv_row_sampling_t* row_sampling, gsv_stream_t stream) {
-  GSV_REQUIRE(h && h->finalized, "t2s_session_admit: handle not finalized");
-  if (!h->ses.open) {
-    set_error("t2s_session_admit: no decode session is open (gsv_t2s_session_begin)");
-    return GSV_ERR_STATE;
-  }
-  const T2SSession& z = h->ses;
-  GSV_REQUIRE(slot_ids && phones && phone_lens && prompts_packed && prompt_lens && rng_seeds && rng_rows,
-              "t2s_session_admit: null argument");
-  GSV_REQUIRE(n >= 1 && n <= z.slots, "t2s_session_admit: %d rows for a session of %d slots", n, z.slots);
-  GSV_REQUIRE(!z.row_sampling || row_sampling, "t2s_session_admit: the session samples per row, row_sampling is null");
-  GSV_REQUIRE(z.row_sampling || !row_sampling, "t2s_session_admit: row_sampling given, but the session was opened without it");
-  if (row_sampling) GSV_RC(check_row_sampling("t2s_session_admit", row_sampling, n));
-  // everything that can refuse the admission is checked here, before the first launch: a refused admission changes nothing
-  std::vector<char> taken(z.slots, 0);
-  for (int i = 0; i < n; ++i) {
-    const int sl = slot_ids[i], P = prompt_lens[i];
-    GSV_REQUIRE(sl >= 0 && sl < z.slots, "t2s_session_admit: row %d: slot %d outside the session's %d slots", i, sl, z.slots);
-    GSV_REQUIRE(!z.live[sl], "t2s_session_admit: row %d: slot %d holds a live row", i, sl);
-    GSV_REQUIRE(!taken[sl], "t2s_session_admit: slot %d is given twice", sl);
-    taken[sl] = 1;
-    GSV_REQUIRE(phone_lens[i] >= 1, "t2s_session_admit: empty phoneme sequence in row %d", i);
-    GSV_REQUIRE(P >= 1, "t2s_session_admit: row %d has prompt length %d (must be >= 1)", i, P);
-    GSV_REQUIRE((long long)phone_lens[i] + P + 2 + z.budget <= h->max_seq,
-                "t2s_session_admit: row %d: %d positions + 2 + %d steps exceed the K/V arena (max_seq %d)", i, phone_lens[i] + P,
-                z.budget, h->max_seq);
-    GSV_REQUIRE(phone_lens[i] <= h->pe_rows && (long long)P + z.budget <= h->pe_rows,
-                "t2s_session_admit: row %d: prompt %d + %d steps exceed the position table (%d rows)", i, P, z.budget, h->pe_rows);
-    GSV_REQUIRE((long long)P + z.budget <= h->ycap, "t2s_session_admit: row %d: prompt %d + %d steps exceed the token history (%d)",
-                i, P, z.budget, h->ycap);
-  }
-  return GSV_WITH_T(h, session_admit<T>(h, n, slot_ids, phones, phone_lens, bert, prompts_packed, prompt_lens, rng_seeds, rng_rows,
-                                        row_sampling, (hipStream_t)stream));
-}
-
-int gsv_t2s_session_advance(gsv_t2s_t* h, int n_steps, int* live_out, int* steps_out, gsv_stream_t stream) {
-  GSV_REQUIRE(h && h->finalized, "t2s_session_advance: handle not finalized");
-  if (!h->ses.open) {
-    set_error("t2s_session_advance: no decode session is open (gsv_t2s_session_begin)");
-    return GSV_ERR_STATE;
-  }
-  GSV_REQUIRE(n_steps >= 1, "t2s_session_advance: n_steps %d must be >= 1", n_steps);
-  return GSV_WITH_T(h, session_advance<T>(h, n_steps, live_out, steps_out, (hipStream_t)stream));
-}
-
-int gsv_t2s_session_release(gsv_t2s_t* h, int n, const int32_t* slot_ids, gsv_stream_t stream) {
-  GSV_REQUIRE(h && h->finalized, "t2s_session_release: handle not finalized");
-  if (!h->ses.open) {
-    set_error("t2s_session_release: no decode session is open (gsv_t2s_session_begin)");
-    return GSV_ERR_STATE;
-  }
-  const T2SSession& z = h->ses;
-  GSV_REQUIRE(slot_ids, "t2s_session_release: null argument");
-  GSV_REQUIRE(n >= 1 && n <= z.slots, "t2s_session_release: %d slots named in a session of %d slots", n, z.slots);
-  std::vector<char> taken(z.slots, 0);
-  for (int i = 0; i < n; ++i) {
-    const int sl = slot_ids[i];
-    GSV_REQUIRE(sl >= 0 && sl < z.slots, "t2s_session_release: slot %d outside the session's %d slots", sl, z.slots);
-    GSV_REQUIRE(!taken[sl], "t2s_session_release: slot %d is given twice", sl);
-    taken[sl] = 1;
-  }
-  return session_release(h, n, slot_ids, (hipStream_t)stream);
-}
-
-int gsv_t2s_session_end(gsv_t2s_t* h) {
-  GSV_REQUIRE(h && h->finalized, "t2s_session_end: handle not finalized");
-  if (!h->ses.open) {
-    set_error("t2s_session_end: no decode session is open");
-    return GSV_ERR_STATE;
-  }
-  GSV_HIP(hipDeviceSynchronize());
-  T2SSession& z = h->ses;
-  z.open = false; z.live.clear();
-  z.out_tokens = nullptr; z.out_len = nullptr; z.force = nullptr; z.dump = nullptr; z.drawn = nullptr; z.logp = nullptr;
-  h->B = 0;   // the next decode needs a prefill of its own, as on a fresh handle
-  h->rng_seed_up.clear(); h->rng_row_up.clear(); h->row_sampling_up.clear();
-  return GSV_OK;
-}
-
-int gsv_t2s_session_state(gsv_t2s_t* h, int32_t* state) {
-  GSV_REQUIRE(h && h->finalized && state, "t2s_session_state: null argument or handle not finalized");
-  if (!h->ses.open) {
-    set_error("t2s_session_state: no decode session is open");
-    return GSV_ERR_STATE;
-  }
-  const size_t mb = (size_t)h->max_batch, n = (size_t)h->ses.slots;
-  GSV_HIP(hipDeviceSynchronize());
-  for (int k = 0; k < 3; ++k) GSV_HIP(hipMemcpy(state + k * n, h->d_kv_len + k * mb, n * 4, hipMemcpyDeviceToHost));
-  GSV_HIP(hipMemcpy(state + 3 * n, h->d_plen, n * 4, hipMemcpyDeviceToHost));
-  return GSV_OK;
-}
-
-int gsv_t2s_session_adopt_info(gsv_t2s_t* h, float* device_ms, int64_t* kv_bytes) {
-  GSV_REQUIRE(h && h->finalized, "t2s_session_adopt_info: handle not finalized");
-  if (device_ms) *device_ms = h->ses.last_adopt_ms;
-  if (kv_bytes) *kv_bytes = h->ses.last_adopt_bytes;
-  return GSV_OK;
+  GSV_REQUIRE(noise == nullptr || noise_rows == 1 || noise_rows == h->rows.B, "t2s_decode: noise_rows must be 1 or B");
+  return decode(h, sp, noise, noise_rows, out_tokens, out_len, steps_run, (hipStream_t)stream);
 }
 
 int gsv_t2s_set_mega(gsv_t2s_t* h, int on) {
@@ -1443,10 +1117,10 @@ int gsv_t2s_set_mega(gsv_t2s_t* h, int on) {
 int gsv_t2s_debug_kv(gsv_t2s_t* h, int layer, int which, int row, int n_pos, void* out) {
   GSV_REQUIRE(h && h->finalized && out, "t2s_debug_kv: null argument or handle not finalized");
   GSV_REQUIRE(layer >= 0 && layer < h->cfg.n_layer && (which == 0 || which == 1) && row >= 0 && row < h->max_batch && n_pos >= 1 &&
-                  n_pos <= h->max_seq, "t2s_debug_kv: layer %d / which %d / row %d / n_pos %d outside the arena", layer, which, row, n_pos);
-  const size_t es = esz(h), H = h->cfg.n_head, pitch = (size_t)h->max_seq * 32 * es;
+                  n_pos <= h->rows.max_seq, "t2s_debug_kv: layer %d / which %d / row %d / n_pos %d outside the arena", layer, which, row, n_pos);
+  const size_t es = esz(h), H = h->cfg.n_head, pitch = (size_t)h->rows.max_seq * 32 * es;
   GSV_HIP(hipDeviceSynchronize());
-  GSV_HIP(hipMemcpy2D(out, (size_t)n_pos * 32 * es, (const char*)kv_ptr(h, layer, which) + (size_t)row * H * pitch, pitch,
+  GSV_HIP(hipMemcpy2D(out, (size_t)n_pos * 32 * es, (const char*)kv_ptr(h, h->rows, layer, which) + (size_t)row * H * pitch, pitch,
                       (size_t)n_pos * 32 * es, H, hipMemcpyDeviceToHost));
   return GSV_OK;
 }
@@ -1460,13 +1134,13 @@ int gsv_t2s_set_prefill_gemm(gsv_t2s_t* h, int mode) {
 
 int gsv_t2s_set_debug(gsv_t2s_t* h, const int32_t* force_tokens, float* logits_dump, int32_t* drawn_dump) {
   GSV_REQUIRE(h && h->finalized, "t2s_set_debug: handle not finalized");
-  h->dbg_force = force_tokens; h->dbg_dump = logits_dump; h->dbg_drawn = drawn_dump;
+  h->next.force = force_tokens; h->next.dump = logits_dump; h->next.drawn = drawn_dump;
   return GSV_OK;
 }
 
 int gsv_t2s_set_logprobs(gsv_t2s_t* h, float* out_logp) {
   GSV_REQUIRE(h && h->finalized, "t2s_set_logprobs: handle not finalized");
-  h->logp_next = out_logp;
+  h->next.logp = out_logp;
   return GSV_OK;
 }
 
@@ -1493,8 +1167,8 @@ int gsv_t2s_decode_info(gsv_t2s_t* h, int* mode, float* device_ms, int* steps) {
 }
 
 int gsv_t2s_debug_logits(gsv_t2s_t* h, float* out, gsv_stream_t stream) {
-  GSV_REQUIRE(h && h->finalized && out && h->B > 0, "t2s_debug_logits: bad state");
-  GSV_HIP(hipMemcpyAsync(out, h->logits, (size_t)h->B * h->cfg.vocab * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  GSV_REQUIRE(h && h->finalized && out && h->rows.B > 0, "t2s_debug_logits: bad state");
+  GSV_HIP(hipMemcpyAsync(out, h->rows.logits, (size_t)h->rows.B * h->cfg.vocab * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return GSV_OK;
 }
 
@@ -1502,21 +1176,22 @@ int64_t gsv_t2s_step_bytes(gsv_t2s_t* h, int64_t* attn_bytes) {
   if (!h || !h->finalized) return 0;
   const auto& c = h->cfg;
   const int64_t es = (int64_t)esz(h), d = c.dim, ff = c.ffn_dim;
-  std::vector<int> kvl(h->B > 0 ? h->B : 1, 0), act(h->B > 0 ? h->B : 1, 0);
+  const int B = h->rows.B;
+  std::vector<int> kvl(B > 0 ? B : 1, 0);
   int64_t keys = 0;
-  if (h->B > 0) {
-    (void)hipMemcpy(kvl.data(), h->d_kv_len, h->B * 4, hipMemcpyDeviceToHost);
-    for (int b = 0; b < h->B; ++b) keys += kvl[b] + 1;
+  if (B > 0) {
+    (void)hipMemcpy(kvl.data(), h->rows.kv_len(), B * 4, hipMemcpyDeviceToHost);
+    for (int b = 0; b < B; ++b) keys += kvl[b] + 1;
   }
   // per cached key and layer: K and V rows of d elements
   const int64_t attn = keys * 2 * d * es;              // one layer's launch
   const int64_t weights = ((int64_t)c.n_layer * (3 * d * d + d * d + 2 * d * ff) + (int64_t)c.vocab * d) * es;
   if (attn_bytes) *attn_bytes = attn;
-  return weights + attn * c.n_layer + (int64_t)h->B * 2 * d * es * c.n_layer;
+  return weights + attn * c.n_layer + (int64_t)B * 2 * d * es * c.n_layer;
 }
 
 int gsv_t2s_time_step(gsv_t2s_t* h, int iters, float* step_ms, float* attn_ms, gsv_stream_t stream) {
-  GSV_REQUIRE(h && h->finalized && h->B > 0 && iters > 0, "t2s_time_step: bad state");
+  GSV_REQUIRE(h && h->finalized && h->rows.B > 0 && iters > 0, "t2s_time_step: bad state");
   return GSV_WITH_T(h, time_step<T>(h, iters, step_ms, attn_ms, (hipStream_t)stream));
 }
 
@@ -1524,14 +1199,15 @@ int gsv_t2s_debug_set_state(gsv_t2s_t* h, int B, int kv_len) {
   // measurement hook: pretend B rows hold kv_len cached positions each (cache contents are whatever the
   // arena holds); used by tools/attn_sweep.py to time the decode-attention kernel at other (B, S) points
   GSV_REQUIRE(h && h->finalized, "t2s_debug_set_state: handle not finalized");
-  GSV_REQUIRE(B >= 1 && B <= h->max_batch && kv_len >= 1 && kv_len + 2 <= h->max_seq, "t2s_debug_set_state: out of range");
-  std::vector<int> kv(B, kv_len), zero(B, 0), plen(B, h->P);
-  GSV_HIP(hipMemcpy(h->d_kv_len, kv.data(), B * 4, hipMemcpyHostToDevice));
-  GSV_HIP(hipMemcpy(h->d_plen, plen.data(), B * 4, hipMemcpyHostToDevice));   // every row: the last prefill's longest prompt
-  GSV_HIP(hipMemcpy(h->d_active, zero.data(), B * 4, hipMemcpyHostToDevice));
-  GSV_HIP(hipMemset(h->ybuf, 0, (size_t)B * h->cfg.dim * 4));
-  GSV_HIP(hipMemset(h->kv, 0, (size_t)h->cfg.n_layer * 2 * h->kv_layer_stride * esz(h)));
-  h->B = B;
+  RowState& r = h->rows;
+  GSV_REQUIRE(B >= 1 && B <= h->max_batch && kv_len >= 1 && kv_len + 2 <= r.max_seq, "t2s_debug_set_state: out of range");
+  std::vector<int> kv(B, kv_len), zero(B, 0), plen(B, r.P);
+  GSV_HIP(hipMemcpy(r.kv_len(), kv.data(), B * 4, hipMemcpyHostToDevice));
+  GSV_HIP(hipMemcpy(r.plen, plen.data(), B * 4, hipMemcpyHostToDevice));   // every row: the last prefill's longest prompt
+  GSV_HIP(hipMemcpy(r.active(), zero.data(), B * 4, hipMemcpyHostToDevice));
+  GSV_HIP(hipMemset(r.ybuf, 0, (size_t)B * h->cfg.dim * 4));
+  GSV_HIP(hipMemset(r.kv, 0, (size_t)h->cfg.n_layer * 2 * r.kv_layer_stride * esz(h)));
+  r.B = B;
   return GSV_OK;
 }
 

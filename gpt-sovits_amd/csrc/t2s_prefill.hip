@@ -384,13 +384,13 @@ int launch_prefill_attention(const PrefillAttnArgs& a, hipStream_t s) {
   return GSV_OK;
 }
 
-// the engine's layer li: pf_qkv -> pf_attn, routes from GSV_SCALAR_PREFILL_ATTN / GSV_PREFILL_SPLIT_SCATTER
+// the engine's layer li: pf_qkv -> pf_attn and r's arena, routes from GSV_SCALAR_PREFILL_ATTN / GSV_PREFILL_SPLIT_SCATTER
 template <typename T>
-int prefill_attention(gsv_t2s* h, int li, int maxS, hipStream_t s) {
+int prefill_attention(gsv_t2s* h, const RowState& r, int li, int maxS, hipStream_t s) {
   PrefillAttnArgs a;
-  a.qkv = h->pf_qkv; a.kc = kv_ptr(h, li, 0); a.vc = kv_ptr(h, li, 1); a.vt = h->pf_vt; a.out = h->pf_attn;
-  a.row_off = h->d_row_off; a.x_len = h->d_x_len; a.plen = h->d_plen;
-  a.B = h->B; a.H = h->cfg.n_head; a.d = h->cfg.dim; a.smax = h->max_seq; a.maxS = maxS;
+  a.qkv = h->pf_qkv; a.kc = kv_ptr(h, r, li, 0); a.vc = kv_ptr(h, r, li, 1); a.vt = h->pf_vt; a.out = h->pf_attn;
+  a.row_off = h->d_row_off; a.x_len = h->d_x_len; a.plen = r.plen;
+  a.B = r.B; a.H = h->cfg.n_head; a.d = h->cfg.dim; a.smax = r.max_seq; a.maxS = maxS;
   a.scalar = scalar_prefill_attn(); a.split_scatter = prefill_split_scatter();
   return launch_prefill_attention<T>(a, s);
 }
@@ -429,9 +429,10 @@ int op_prefill_attn(PrefillAttnArgs a, const int32_t* x_len, const int32_t* p_le
 
 // Prefill of B rows with prompts of P_b = plen[b] tokens, packed back to back in `prompts` (device) from poff[b] on.
 // The uniform entry (every P_b = P, poff[b] = b P) and the ragged one share this body: the kernels read P_b per row either
-// way, so a uniform batch computes exactly what it computed when P was a kernel argument.
+// way, so a uniform batch computes exactly what it computed when P was a kernel argument.  The rows land in r: the handle's own
+// or, for an admission, a session's staging rows.
 template <typename T>
-int t2s_prefill_rows(gsv_t2s* h, const int32_t* phones, const int32_t* phone_lens, int B, const float* bert,
+int t2s_prefill_rows(gsv_t2s* h, RowState& r, const int32_t* phones, const int32_t* phone_lens, int B, const float* bert,
                      const int32_t* prompts, const int* plen, const int* poff, hipStream_t s) {
   const auto& c = h->cfg;
   const int d = c.dim, H = c.n_head;
@@ -442,7 +443,7 @@ int t2s_prefill_rows(gsv_t2s* h, const int32_t* phones, const int32_t* phone_len
     row_off[b] = M; ph_off[b] = SX;
     const int P = plen[b];
     const int S = phone_lens[b] + P;
-    GSV_REQUIRE(S + 2 <= h->max_seq, "t2s_prefill: row %d needs %d positions, max_seq is %d", b, S + 2, h->max_seq);
+    GSV_REQUIRE(S + 2 <= r.max_seq, "t2s_prefill: row %d needs %d positions, max_seq is %d", b, S + 2, r.max_seq);
     GSV_REQUIRE(phone_lens[b] <= h->pe_rows, "t2s_prefill: sequence exceeds the position table");
     GSV_REQUIRE(P <= h->pe_rows, "t2s_prefill: row %d's prompt of %d tokens exceeds the position table (%d rows)", b, P, h->pe_rows);
     GSV_REQUIRE(P + 1 <= h->ycap, "t2s_prefill: row %d's prompt of %d tokens exceeds the token history (%d)", b, P, h->ycap);
@@ -455,25 +456,25 @@ int t2s_prefill_rows(gsv_t2s* h, const int32_t* phones, const int32_t* phone_len
     const size_t need_vt = (size_t)B * H * 32 * ((maxS + 31) / 32 * 32) * 2;
     if (need_vt > h->pf_vt_cap) { GSV_RC(dalloc(h, &h->pf_vt, need_vt + need_vt / 4)); h->pf_vt_cap = need_vt + need_vt / 4; }
   }
-  h->B = B; h->P = maxP; h->max_kv0 = maxS;
+  r.B = B; r.P = maxP; r.max_kv0 = maxS;
   GSV_HIP(hipMemcpyAsync(h->d_x_len, phone_lens, B * 4, hipMemcpyHostToDevice, s));
   GSV_HIP(hipMemcpyAsync(h->d_row_off, row_off.data(), B * 4, hipMemcpyHostToDevice, s));
   GSV_HIP(hipMemcpyAsync(h->d_ph_off, ph_off.data(), B * 4, hipMemcpyHostToDevice, s));
-  const int* d_plen = h->d_plen;
-  const int* d_poff = h->d_plen + h->max_batch;
-  std::vector<int> pl(2 * (size_t)h->max_batch, 0);
-  for (int b = 0; b < B; ++b) { pl[b] = plen[b]; pl[h->max_batch + b] = poff[b]; }
-  GSV_HIP(hipMemcpyAsync(h->d_plen, pl.data(), pl.size() * 4, hipMemcpyHostToDevice, s));
+  const int* d_plen = r.plen;
+  const int* d_poff = r.plen + r.mb;
+  std::vector<int> pl(2 * (size_t)r.mb, 0);
+  for (int b = 0; b < B; ++b) { pl[b] = plen[b]; pl[r.mb + b] = poff[b]; }
+  GSV_HIP(hipMemcpyAsync(r.plen, pl.data(), pl.size() * 4, hipMemcpyHostToDevice, s));
   {
     // row state [kv_len | active | step | n_active] is one block: one upload
-    const size_t mb = (size_t)h->max_batch;
-    std::vector<int> st(3 * mb + 4, 0);
+    const size_t mb = (size_t)r.mb;
+    std::vector<int> st(r.state_ints(), 0);
     for (int b = 0; b < B; ++b) { st[b] = kvl[b]; st[mb + b] = 1; }
     st[3 * mb] = B;
-    GSV_HIP(hipMemcpyAsync(h->d_kv_len, st.data(), st.size() * 4, hipMemcpyHostToDevice, s));
+    GSV_HIP(hipMemcpyAsync(r.state, st.data(), st.size() * 4, hipMemcpyHostToDevice, s));
     GSV_HIP(hipStreamSynchronize(s));
   }
-  if (maxP > 0) GSV_LAUNCH(prompt_copy_kernel, dim3(B), dim3(64), 0, s, prompts, d_plen, d_poff, h->ycap, h->d_ytok);
+  if (maxP > 0) GSV_LAUNCH(prompt_copy_kernel, dim3(B), dim3(64), 0, s, prompts, d_plen, d_poff, h->ycap, r.ytok);
   GSV_HIP(hipStreamSynchronize(s));  // host vectors above go out of scope
 
   const float* bertp = nullptr;
@@ -490,7 +491,7 @@ int t2s_prefill_rows(gsv_t2s* h, const int32_t* phones, const int32_t* phone_len
   for (int li = 0; li < c.n_layer; ++li) {
     const LayerW& L = h->layers[li];
     GSV_RC(prefill_gemm(h, linear(h->pf_x, L.qkv_w, L.qkv_b, h->pf_qkv, M, d, 3 * d), s));
-    GSV_RC(prefill_attention<T>(h, li, maxS, s));
+    GSV_RC(prefill_attention<T>(h, r, li, maxS, s));
     // y1 = attn Wo^T + bo + x  (fp32) ; x1 = LN1(y1)
     ConvArgs o = linear(h->pf_attn, L.out_w, L.out_b, h->pf_y, M, d, d);
     o.out_f32 = 1; o.res = h->pf_x; o.ldr = d;
@@ -506,28 +507,19 @@ int t2s_prefill_rows(gsv_t2s* h, const int32_t* phones, const int32_t* phone_len
     if (li + 1 < c.n_layer)
       GSV_RC(launch_layernorm(h->dtype, h->pf_y, 1, nullptr, 0, L.n2w, L.n2b, h->pf_x, 0, M, d, 1e-5f, s));
   }
-  GSV_LAUNCH(gather_last_kernel, dim3(B), dim3(128), 0, s, h->pf_y, h->d_row_off, h->d_x_len, d_plen, d, h->ybuf);
+  GSV_LAUNCH(gather_last_kernel, dim3(B), dim3(128), 0, s, h->pf_y, h->d_row_off, h->d_x_len, d_plen, d, r.ybuf);
   return GSV_OK;
 }
 
 }  // namespace
 
-int t2s_prefill_into(gsv_t2s* h, const int32_t* phones, const int32_t* phone_lens, int B, const float* bert,
+int t2s_prefill_into(gsv_t2s* h, RowState& r, const int32_t* phones, const int32_t* phone_lens, int B, const float* bert,
                      const int32_t* prompts_packed, const int32_t* prompt_lens, hipStream_t s) {
   std::vector<int> poff(B);
   int o = 0;
   for (int b = 0; b < B; ++b) { poff[b] = o; o += prompt_lens[b]; }
-  return GSV_WITH_T(h, t2s_prefill_rows<T>(h, phones, phone_lens, B, bert, prompts_packed, prompt_lens, poff.data(), s));
+  return GSV_WITH_T(h, t2s_prefill_rows<T>(h, r, phones, phone_lens, B, bert, prompts_packed, prompt_lens, poff.data(), s));
 }
-
-// while a decode session is open the handle's arena and row state are the session's
-#define GSV_T2S_NO_SESSION(h, who)                                                                                      \
-  do {                                                                                                                  \
-    if ((h)->ses.open) {                                                                                                \
-      gsv::set_error(who ": a decode session is open on this handle (gsv_t2s_session_end closes it)");                  \
-      return GSV_ERR_STATE;                                                                                             \
-    }                                                                                                                   \
-  } while (0)
 
 extern "C" {
 
@@ -540,7 +532,7 @@ int gsv_t2s_prefill(gsv_t2s_t* h, const int32_t* phones, const int32_t* phone_le
   GSV_REQUIRE(P >= 0, "t2s_prefill: negative prompt length %d", P);   // P == 0: prompt-free decode (t2s_model.py:849-856)
   std::vector<int> plen(B, P), poff(B);
   for (int b = 0; b < B; ++b) poff[b] = b * P;
-  return GSV_WITH_T(h, t2s_prefill_rows<T>(h, phones, phone_lens, B, bert, prompts, plen.data(), poff.data(), (hipStream_t)stream));
+  return GSV_WITH_T(h, t2s_prefill_rows<T>(h, h->rows, phones, phone_lens, B, bert, prompts, plen.data(), poff.data(), (hipStream_t)stream));
 }
 
 int gsv_t2s_prefill_ragged(gsv_t2s_t* h, const int32_t* phones, const int32_t* phone_lens, int B, const float* bert,
@@ -556,7 +548,7 @@ int gsv_t2s_prefill_ragged(gsv_t2s_t* h, const int32_t* phones, const int32_t* p
     GSV_REQUIRE(prompt_lens[b] >= 1, "t2s_prefill_ragged: row %d has prompt length %d (must be >= 1)", b, prompt_lens[b]);
     poff[b] = o; o += prompt_lens[b];
   }
-  return GSV_WITH_T(h, t2s_prefill_rows<T>(h, phones, phone_lens, B, bert, prompts_packed, prompt_lens, poff.data(), (hipStream_t)stream));
+  return GSV_WITH_T(h, t2s_prefill_rows<T>(h, h->rows, phones, phone_lens, B, bert, prompts_packed, prompt_lens, poff.data(), (hipStream_t)stream));
 }
 
 int gsv_op_prefill_attn(const void* qkv, const int32_t* x_len, const int32_t* p_len, int B, int H, int d, int smax, int dtype,

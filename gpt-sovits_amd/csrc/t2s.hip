@@ -408,8 +408,9 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const T* __restrict__ 
 }
 
 // step tail: sample every row, update row state, emit the next step's input embedding
-// (t2s_model.py:714-769).  grid = B, block = 64.
-template <int NPL>
+// (t2s_model.py:714-769).  grid = B, block = 64.  LIMITS: row b's EOS horizon, early stop and budget come from
+// sp.row_limits[b] (gsv_t2s_set_row_limits) -- a kernel of its own, so that the default one keeps its registers.
+template <int NPL, bool LIMITS>
 __global__ __launch_bounds__(64) void sample_step_kernel(const float* __restrict__ logits, int V, int EOS,
                                                          const StepParams* __restrict__ spp, int* __restrict__ ytok,
                                                          int ycap, int* __restrict__ kv_len, int* __restrict__ active,
@@ -421,7 +422,8 @@ __global__ __launch_bounds__(64) void sample_step_kernel(const float* __restrict
   const StepParams sp = *spp;
   const int step = step_ctr[b];
   if (!active[b]) return;
-  const int Veff = (step < sp.eos_mask_steps) ? V - 1 : V;
+  const RowLimits rl = row_limits_of<LIMITS>(sp, b);
+  const int Veff = (step < rl.eos_mask_steps) ? V - 1 : V;
   const int P = sp.plen[b];
   const int prev_len = P + step;
   int* yrow = ytok + (long long)b * ycap;
@@ -447,7 +449,7 @@ __global__ __launch_bounds__(64) void sample_step_kernel(const float* __restrict
     if (lane == 0) sp.logp[(long long)b * sp.max_steps + step] = lp;
   }
   const bool fin = (smp == EOS) || (amx == EOS);
-  const bool early = (sp.early_stop_num != -1 && (step + 1) > sp.early_stop_num) || (step >= sp.max_steps - 1);
+  const bool early = (rl.early_stop_num != -1 && (step + 1) > rl.early_stop_num) || (step >= rl.max_steps - 1);
   if (lane == 0) {
     if (prev_len < ycap) yrow[prev_len] = smp;
     if (fin || early) {
@@ -636,7 +638,9 @@ int launch_tail(gsv_t2s* h, RowState& r, hipStream_t s) {
   GSV_RC(launch_dec_gemm<T>(a, true, s));
   const int V = c.vocab, EOS = c.vocab - 1;
   return with_npl(V, [&](auto npl) -> int {
-    GSV_LAUNCH(sample_step_kernel<decltype(npl)::value>, dim3(r.B), dim3(64), (size_t)((V + 15) & ~15), s, r.logits, V, EOS, r.sp,
+    constexpr int NPL = decltype(npl)::value;
+    auto kern = h->limits_on ? sample_step_kernel<NPL, true> : sample_step_kernel<NPL, false>;
+    GSV_LAUNCH(kern, dim3(r.B), dim3(64), (size_t)((V + 15) & ~15), s, r.logits, V, EOS, r.sp,
                r.ytok, h->ycap, r.kv_len(), r.active(), r.step(), r.n_active(), h->e_audio, h->pe, h->alpha_a, c.dim, r.ybuf);
     return GSV_OK;
   });
@@ -659,7 +663,9 @@ int decode_begin(gsv_t2s* h, const gsv_sampling_params* sp, const float* noise, 
   // per-row sampling parameters: gsv_t2s_set_row_sampling's for this call (the call's four scalars are then unused), else
   // null.  row_sampling_next stays until gsv_t2s_decode returns: a fallback re-run of the batch reads the same device array.
   const std::vector<gsv_row_sampling_t>& rsn = h->row_sampling_next;
-  StepParams p = step_params(*sp, r, take_outputs(h, out_tokens, out_len), !rsn.empty());
+  const std::vector<gsv_row_limits_t>& rln = h->row_limits_next;   // gsv_t2s_set_row_limits' for this call
+  const bool limits = !rln.empty();
+  StepParams p = step_params(*sp, r, take_outputs(h, out_tokens, out_len), !rsn.empty(), limits);
   p.noise = noise; p.noise_rows = noise ? noise_rows : 0;
   // counter-RNG keys of the rows: gsv_t2s_set_row_rng's for this call, else (seed, b) -- the draws of a batch without keys
   const bool keyed = !h->rng_seed_next.empty();
@@ -674,22 +680,44 @@ int decode_begin(gsv_t2s* h, const gsv_sampling_params* sp, const float* noise, 
   GSV_REQUIRE(!keyed || nkeys == r.B, "t2s_decode: gsv_t2s_set_row_rng gave %d keys for a batch of %d rows", nkeys, r.B);
   GSV_REQUIRE(rsn.empty() || (int)rsn.size() == r.B, "t2s_decode: gsv_t2s_set_row_sampling gave %d rows for a batch of %d rows",
               (int)rsn.size(), r.B);
+  // Per-row limits are checked against the call before anything is uploaded or launched; every row is held to its own budget
+  // (row b ends at kv0[b] + budget_b - 1 cached positions) and the launch runs the largest.
+  int budget = step_budget(*sp);
+  if (limits) {
+    GSV_REQUIRE((int)rln.size() == r.B, "t2s_decode: gsv_t2s_set_row_limits gave %d rows for a batch of %d rows", (int)rln.size(),
+                r.B);
+    GSV_RC(check_row_limits_steps("t2s_decode", rln, sp->max_steps));
+    budget = 1;
+    for (int b = 0; b < r.B; ++b) {
+      const int bb = step_budget(rln[b]);
+      budget = bb > budget ? bb : budget;
+      GSV_REQUIRE(r.kv0[b] + bb <= r.max_seq,
+                  "t2s_decode: row %d: %d cached positions + %d steps exceed the K/V arena (max_seq %d); lower the row's max_steps / "
+                  "early_stop_num or create the engine with a larger max_seq", b, r.kv0[b], bb, r.max_seq);
+      GSV_REQUIRE(r.pl[b] + bb <= h->pe_rows, "t2s_decode: row %d: prompt %d + %d steps exceed the position table (%d rows)", b,
+                  r.pl[b], bb, h->pe_rows);
+      GSV_REQUIRE(r.pl[b] + bb <= h->ycap, "t2s_decode: row %d: prompt %d + %d steps exceed the token history (%d)", b, r.pl[b], bb,
+                  h->ycap);
+    }
+    GSV_HIP(hipMemcpyAsync(r.row_limits, rln.data(), rln.size() * sizeof(gsv_row_limits_t), hipMemcpyHostToDevice, s));
+  }
   if (!rsn.empty() && (rsn.size() != h->row_sampling_up.size() ||
                        memcmp(rsn.data(), h->row_sampling_up.data(), rsn.size() * sizeof(gsv_row_sampling_t)) != 0)) {
     GSV_HIP(hipMemcpyAsync(r.row_sampling, rsn.data(), rsn.size() * sizeof(gsv_row_sampling_t), hipMemcpyHostToDevice, s));
     h->row_sampling_up = rsn;
   }
   GSV_HIP(hipMemcpyAsync(r.sp, &p, sizeof(p), hipMemcpyHostToDevice, s));
+  h->limits_on = limits;   // with the StepParams it describes
   if (seeds != h->rng_seed_up || rows != h->rng_row_up) {
     GSV_HIP(hipMemcpyAsync(r.rng_seed, seeds.data(), (size_t)r.B * 8, hipMemcpyHostToDevice, s));
     GSV_HIP(hipMemcpyAsync(r.rng_row, rows.data(), (size_t)r.B * 4, hipMemcpyHostToDevice, s));
     h->rng_seed_up = seeds; h->rng_row_up = rows;
   }
   GSV_HIP(hipStreamSynchronize(s));
+  if (limits) return budget;
   // the longest row ends at max_kv0 + budget - 1 cached positions; the sampling tail of row b reads pe[P_b + step] and writes
   // token history [P_b + step] (r.P is the longest prompt).  A request that does not fit is refused here: the kernels clamp
   // out-of-range appends, which would otherwise yield silently wrong tokens with rc 0.
-  const int budget = step_budget(*sp);
   GSV_REQUIRE(r.max_kv0 + budget <= r.max_seq,
               "t2s_decode: %d cached positions + %d steps exceed the K/V arena (max_seq %d); lower max_steps / early_stop_num "
               "or create the engine with a larger max_seq", r.max_kv0, budget, r.max_seq);
@@ -792,7 +820,7 @@ int run_mega(gsv_t2s* h, int budget, int32_t* out_len, hipStream_t s) {
   MegaArgs a = mega_args(h, budget);
   GSV_RC(mega_prof_arm(a, budget, s));
   GSV_HIP(hipEventRecord(h->mega_ev[0], s));
-  GSV_RC(launch_t2s_mega(a, h->logp_on, s));
+  GSV_RC(launch_t2s_mega(a, h->logp_on, h->limits_on, s));
   GSV_HIP(hipEventRecord(h->mega_ev[1], s));
   GSV_HIP(hipMemcpyAsync(m.h_err, m.err, 16, hipMemcpyDeviceToHost, s));
   GSV_HIP(hipMemcpyAsync(h->h_pinned, r.step(), 4, hipMemcpyDeviceToHost, s));
@@ -828,7 +856,8 @@ template <typename T>
 int run_steps(gsv_t2s* h, int budget, int* steps_run, hipStream_t s) {
   const int B = h->rows.B;
   hipGraphExec_t exec = nullptr;
-  auto it = h->graphs.find(B);
+  const int gkey = B + (h->limits_on ? 1 << 16 : 0);   // the step with the LIMITS sampler is a graph of its own
+  auto it = h->graphs.find(gkey);
   if (it != h->graphs.end()) exec = it->second;
   else if (s != nullptr && !getenv("GSV_T2S_NO_GRAPH") && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
     hipGraph_t graph;
@@ -838,7 +867,7 @@ int run_steps(gsv_t2s* h, int budget, int* steps_run, hipStream_t s) {
     GSV_HIP(e);
     GSV_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
     (void)hipGraphDestroy(graph);
-    h->graphs[B] = exec;
+    h->graphs[gkey] = exec;
   } else {
     (void)hipGetLastError();  // legacy default stream cannot capture: eager launches instead
   }
@@ -923,6 +952,13 @@ int run_chunk(gsv_t2s* h, int budget, int32_t* out_len, int* steps_run, hipStrea
     }
   }
   return GSV_WITH_T(h, run_steps<T>(h, budget, steps_run, s));   // also after MEGA_FELL_BACK: the snapshot is back
+}
+
+int check_row_limits_steps(const char* who, const std::vector<gsv_row_limits_t>& rows, int max_steps) {
+  for (size_t b = 0; b < rows.size(); ++b)
+    GSV_REQUIRE(rows[b].max_steps <= max_steps, "%s: row %d: its limits' max_steps %d exceed the call's %d", who, (int)b,
+                rows[b].max_steps, max_steps);
+  return GSV_OK;
 }
 
 int check_row_sampling(const char* who, const gsv_row_sampling_t* rows, int B) {
@@ -1066,6 +1102,7 @@ int gsv_t2s_finalize(gsv_t2s_t* h) {
   GSV_RC(dalloc(h, (void**)&r.rng_seed, B * 8));
   GSV_RC(dalloc(h, (void**)&r.rng_row, B * 4));
   GSV_RC(dalloc(h, (void**)&r.row_sampling, B * sizeof(RowSampling)));
+  GSV_RC(dalloc(h, (void**)&r.row_limits, B * sizeof(RowLimits)));
   GSV_RC(dalloc(h, (void**)&r.sp, sizeof(StepParams)));
   GSV_HIP(hipHostMalloc((void**)&h->h_pinned, 64));
   GSV_RC(dalloc(h, (void**)&r.ybuf, B * d * 4));
@@ -1095,13 +1132,29 @@ int gsv_t2s_set_row_sampling(gsv_t2s_t* h, const gsv_row_sampling_t* rows, int B
   return GSV_OK;
 }
 
+int gsv_t2s_set_row_limits(gsv_t2s_t* h, const gsv_row_limits_t* rows, int B) {
+  GSV_REQUIRE(h && h->finalized, "t2s_set_row_limits: handle not finalized");
+  GSV_REQUIRE(rows && B >= 1 && B <= h->max_batch, "t2s_set_row_limits: bad argument (B = %d)", B);
+  for (int b = 0; b < B; ++b) {
+    const gsv_row_limits_t& r = rows[b];
+    GSV_REQUIRE(r.eos_mask_steps >= 0, "t2s_set_row_limits: row %d: eos_mask_steps %d must be >= 0", b, r.eos_mask_steps);
+    GSV_REQUIRE(r.early_stop_num >= -1, "t2s_set_row_limits: row %d: early_stop_num %d must be >= -1", b, r.early_stop_num);
+    GSV_REQUIRE(r.max_steps >= 1, "t2s_set_row_limits: row %d: max_steps %d must be >= 1", b, r.max_steps);
+    GSV_REQUIRE(r.reserved == 0, "t2s_set_row_limits: row %d: reserved must be 0", b);
+  }
+  if (h->ses.open)
+    GSV_RC(check_row_limits_steps("t2s_set_row_limits", std::vector<gsv_row_limits_t>(rows, rows + B), h->ses.sp.max_steps));
+  h->row_limits_next.assign(rows, rows + B);
+  return GSV_OK;
+}
+
 int gsv_t2s_decode(gsv_t2s_t* h, const gsv_sampling_params* sp, const float* noise, int noise_rows,
                    int32_t* out_tokens, int32_t* out_len, int* steps_run, gsv_stream_t stream) {
   GSV_REQUIRE(h && h->finalized, "t2s_decode: handle not finalized");
   GSV_T2S_NO_SESSION(h, "t2s_decode");
   GSV_REQUIRE(h->rows.B > 0, "t2s_decode: call gsv_t2s_prefill first");
-  // the per-row sampling parameters are this call's alone, whatever becomes of it
-  struct Clear { gsv_t2s_t* h; ~Clear() { h->row_sampling_next.clear(); } } clear{h};
+  // the per-row sampling parameters and limits are this call's alone, whatever becomes of it
+  struct Clear { gsv_t2s_t* h; ~Clear() { h->row_sampling_next.clear(); h->row_limits_next.clear(); } } clear{h};
   GSV_REQUIRE(sp && out_tokens && out_len, "t2s_decode: null argument");
   GSV_REQUIRE(sp->max_steps >= 1, "t2s_decode: max_steps must be >= 1");
   GSV_REQUIRE(noise == nullptr || noise_rows == 1 || noise_rows == h->rows.B, "t2s_decode: noise_rows must be 1 or B");

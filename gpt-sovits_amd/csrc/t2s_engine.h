@@ -38,11 +38,13 @@ struct RowState {
   int* plen = nullptr;      // [2][mb]: prompt length P_b | offset of row b's prompt in the packed prompt buffer
   unsigned long long* rng_seed = nullptr; int* rng_row = nullptr;   // [mb] counter-RNG keys of the rows
   gsv::RowSampling* row_sampling = nullptr;        // [mb] per-row sampling parameters
+  gsv::RowLimits* row_limits = nullptr;            // [mb] per-row step limits (gsv_t2s_set_row_limits)
   gsv::StepParams* sp = nullptr;                   // the device StepParams of these rows
   float *ybuf = nullptr, *logits = nullptr;        // [mb][dim] next step's input embedding, [mb][vocab]
   // host view of the current batch
   int B = 0, P = 0;         // P: the longest row's prompt (uniform prefill: every row's)
   int max_kv0 = 0;          // longest row's cached positions after prefill (host copy: bounds the decode budget)
+  std::vector<int> kv0, pl; // every row's cached positions and prompt length after prefill: bound a decode with per-row limits
 };
 
 // where a decode writes: the caller's results, the parity hooks (gsv_t2s_set_debug) and the log-probabilities
@@ -59,6 +61,7 @@ struct T2SSession {
   bool open = false;
   int slots = 0, budget = 0;
   bool row_sampling = false;
+  bool row_limits = false;                                   // from the first admission that brought limits on: every slot has its own
   gsv_sampling_params sp;
   RowOutputs out;                                            // the caller's and the hooks', held for the whole session
   std::vector<char> live;                                    // host view of active[], refreshed by every admit / advance
@@ -103,6 +106,8 @@ struct gsv_t2s : gsveng::Ctx {
   float last_decode_ms = 0.f; int last_decode_steps = 0; int last_decode_mode = 0;
   bool mega_on = true;      // gsv_t2s_set_mega (A/B inside one process); GSV_T2S_NO_MEGA=1 never builds the engine
   int prefill_gemm = 2;     // gsv_t2s_set_prefill_gemm: 0 dispatcher only, 1 panel GEMM wherever eligible, 2 from PANEL_MIN_ROWS rows upwards
+  std::vector<gsv_row_limits_t> row_limits_next;     // gsv_t2s_set_row_limits: NEXT decode / admission only
+  bool limits_on = false;   // the StepParams at rows.sp hold a row-limits pointer: the LIMITS kernels run (both decode paths)
   RowOutputs next;          // gsv_t2s_set_debug / gsv_t2s_set_logprobs: the NEXT decode call (or the session begun next) only
   int dbg_stall = 0;        // gsv_t2s_debug_stall: likewise
   bool logp_on = false;     // the StepParams at rows.sp hold a log-probability pointer: run_mega launches a LOGP kernel
@@ -125,23 +130,28 @@ inline RowOutputs take_outputs(gsv_t2s* h, int32_t* out_tokens, int32_t* out_len
   return o;
 }
 
-// the StepParams of a decode over the rows of r that writes to o; per_row: row b samples with r.row_sampling[b]
-inline gsv::StepParams step_params(const gsv_sampling_params& sp, const RowState& r, const RowOutputs& o, bool per_row) {
+// the StepParams of a decode over the rows of r that writes to o; per_row: row b samples with r.row_sampling[b]; limits: row b
+// ends by r.row_limits[b]
+inline gsv::StepParams step_params(const gsv_sampling_params& sp, const RowState& r, const RowOutputs& o, bool per_row,
+                                   bool limits = false) {
   gsv::StepParams p;
   memset(&p, 0, sizeof(p));
   p.top_k = sp.top_k; p.top_p = sp.top_p; p.temperature = sp.temperature; p.rep_penalty = sp.repetition_penalty;
   p.early_stop_num = sp.early_stop_num; p.eos_mask_steps = sp.eos_mask_steps; p.max_steps = sp.max_steps; p.seed = sp.seed;
   p.out_tokens = o.out_tokens; p.out_len = o.out_len; p.force = o.force; p.dump = o.dump; p.drawn = o.drawn; p.logp = o.logp;
   p.plen = r.plen; p.rng_seed = r.rng_seed; p.rng_row = r.rng_row; p.row_sampling = per_row ? r.row_sampling : nullptr;
+  p.row_limits = limits ? r.row_limits : nullptr;
   return p;
 }
 
 // steps a row can run: step 0 samples from the prefill's last position, every later step appends one K/V position
-inline int step_budget(const gsv_sampling_params& sp) {
-  int budget = sp.max_steps;
-  if (sp.early_stop_num >= 0 && sp.early_stop_num + 1 < budget) budget = sp.early_stop_num + 1;
+inline int step_budget(int early_stop_num, int max_steps) {
+  int budget = max_steps;
+  if (early_stop_num >= 0 && early_stop_num + 1 < budget) budget = early_stop_num + 1;
   return budget;
 }
+inline int step_budget(const gsv_sampling_params& sp) { return step_budget(sp.early_stop_num, sp.max_steps); }
+inline int step_budget(const gsv_row_limits_t& rl) { return step_budget(rl.early_stop_num, rl.max_steps); }
 
 // while a decode session is open the handle's arena and row state are the session's
 #define GSV_T2S_NO_SESSION(h, who)                                                                                      \
@@ -171,3 +181,7 @@ int t2s_step0_tail(gsv_t2s* h, RowState& r, hipStream_t s);
 int run_chunk(gsv_t2s* h, int budget, int32_t* out_len, int* steps_run, hipStream_t s);
 // the value checks of gsv_t2s_set_row_sampling, gsv_t2s_session_admit and gsv_op_sample_rows
 int check_row_sampling(const char* who, const gsv_row_sampling_t* rows, int B);
+// the limits of a call with the scalars of sp: what a row without limits of its own gets in a decode that has them
+inline gsv_row_limits_t limits_of(const gsv_sampling_params& sp) { return {sp.eos_mask_steps, sp.early_stop_num, sp.max_steps, 0}; }
+// gsv_t2s_set_row_limits' rows against the max_steps of the call / session that consumes them
+int check_row_limits_steps(const char* who, const std::vector<gsv_row_limits_t>& rows, int max_steps);

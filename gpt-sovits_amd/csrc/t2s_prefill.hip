@@ -457,6 +457,7 @@ int t2s_prefill_rows(gsv_t2s* h, RowState& r, const int32_t* phones, const int32
     if (need_vt > h->pf_vt_cap) { GSV_RC(dalloc(h, &h->pf_vt, need_vt + need_vt / 4)); h->pf_vt_cap = need_vt + need_vt / 4; }
   }
   r.B = B; r.P = maxP; r.max_kv0 = maxS;
+  r.kv0 = kvl; r.pl.assign(plen, plen + B);
   GSV_HIP(hipMemcpyAsync(h->d_x_len, phone_lens, B * 4, hipMemcpyHostToDevice, s));
   GSV_HIP(hipMemcpyAsync(h->d_row_off, row_off.data(), B * 4, hipMemcpyHostToDevice, s));
   GSV_HIP(hipMemcpyAsync(h->d_ph_off, ph_off.data(), B * 4, hipMemcpyHostToDevice, s));
@@ -539,15 +540,27 @@ int gsv_t2s_prefill_ragged(gsv_t2s_t* h, const int32_t* phones, const int32_t* p
                            const int32_t* prompts_packed, const int32_t* prompt_lens, gsv_stream_t stream) {
   GSV_REQUIRE(h && h->finalized, "t2s_prefill_ragged: handle not finalized");
   GSV_T2S_NO_SESSION(h, "t2s_prefill_ragged");
-  GSV_REQUIRE(phones && phone_lens && prompts_packed && prompt_lens, "t2s_prefill_ragged: null argument");
+  // Row limits pending for the decode that follows (gsv_t2s_set_row_limits): a row may then be prompt-free, its EOS horizon is
+  // its own.  The kernels read P_b per row and never touch `prompts` for a row with P_b = 0: embed_prefill_kernel reads it at
+  // i >= X only, prompt_copy_kernel loops over t < P_b (and is not launched when every row is prompt-free), gather_last_kernel
+  // reads position X + P_b - 1 >= 0, and the attention kernels treat such a row as text only -- what the uniform P = 0 entry runs.
+  const bool limits = !h->row_limits_next.empty();
+  GSV_REQUIRE(phones && phone_lens && prompt_lens, "t2s_prefill_ragged: null argument");
   GSV_REQUIRE(B >= 1 && B <= h->max_batch, "t2s_prefill_ragged: batch %d exceeds max_batch %d", B, h->max_batch);
+  if (limits && (int)h->row_limits_next.size() != B) {
+    set_error("t2s_prefill_ragged: gsv_t2s_set_row_limits gave %d rows for a batch of %d rows", (int)h->row_limits_next.size(), B);
+    h->row_limits_next.clear();
+    return GSV_ERR_ARG;
+  }
   std::vector<int> poff(B);
   int o = 0;
   for (int b = 0; b < B; ++b) {
-    // prompt-free rows keep the uniform entry (P = 0 there also masks EOS for 11 steps: t2s_model.py:849-856)
-    GSV_REQUIRE(prompt_lens[b] >= 1, "t2s_prefill_ragged: row %d has prompt length %d (must be >= 1)", b, prompt_lens[b]);
+    // without limits prompt-free rows keep the uniform entry (P = 0 there also masks EOS for 11 steps: t2s_model.py:849-856)
+    GSV_REQUIRE(prompt_lens[b] >= (limits ? 0 : 1), "t2s_prefill_ragged: row %d has prompt length %d (must be >= 1)", b,
+                prompt_lens[b]);
     poff[b] = o; o += prompt_lens[b];
   }
+  GSV_REQUIRE(prompts_packed || (limits && o == 0), "t2s_prefill_ragged: null argument");
   return GSV_WITH_T(h, t2s_prefill_rows<T>(h, h->rows, phones, phone_lens, B, bert, prompts_packed, prompt_lens, poff.data(), (hipStream_t)stream));
 }
 

@@ -16,6 +16,14 @@ struct RowSampling {
   float rep_penalty;
 };
 
+// step limits of one batch row (gsv_row_limits_t, gsv_t2s_set_row_limits): 16 bytes, one load per row
+struct RowLimits {
+  int eos_mask_steps;
+  int early_stop_num;
+  int max_steps;
+  int reserved;
+};
+
 struct StepParams {
   int top_k;
   float top_p;
@@ -42,6 +50,9 @@ struct StepParams {
   // [B][max_steps] or null (gsv_t2s_set_logprobs), indexed like out_tokens: the log-probability of the token row b takes at
   // step s under the model's own distribution (token_logprob below); the step that ends the row has its entry too
   float* logp;
+  // [B] or null: row b masks EOS, stops early and ends with row_limits[b] instead of eos_mask_steps / early_stop_num / max_steps
+  // above; max_steps stays the row pitch of out_tokens, logp and the hooks.  Only the LIMITS kernels read it.
+  const RowLimits* row_limits;
 };
 
 // Row b's entry of a RowSampling array.  b is wave-uniform at every call site, so the four values are made scalars again:
@@ -56,7 +67,18 @@ __device__ __forceinline__ RowSampling row_sampling_of(const StepParams& sp, int
   if (sp.row_sampling) return load_row_sampling(sp.row_sampling, b);
   return {sp.top_k, sp.top_p, sp.temperature, sp.rep_penalty};
 }
-
+// Row b's entry of a RowLimits array, read like load_row_sampling: one 16-byte load, wave-uniform values
+__device__ __forceinline__ RowLimits load_row_limits(const RowLimits* __restrict__ rows, int b) {
+  const int4 v = *reinterpret_cast<const int4*>(rows + b);
+  return {__builtin_amdgcn_readfirstlane(v.x), __builtin_amdgcn_readfirstlane(v.y), __builtin_amdgcn_readfirstlane(v.z), 0};
+}
+// The limits of batch row b.  LIMITS is a compile-time constant: the kernels built without it carry no trace of the per-row
+// form (as a run-time branch it would sit in every launch's sampler, like the log-probabilities did: DESIGN.md 4p).
+template <bool LIMITS>
+__device__ __forceinline__ RowLimits row_limits_of(const StepParams& sp, int b) {
+  if constexpr (LIMITS) if (sp.row_limits) return load_row_limits(sp.row_limits, b);
+  return {sp.eos_mask_steps, sp.early_stop_num, sp.max_steps, 0};
+}
 
 // ---------------------------------------------------------------------------------------
 // Sampling (H5): one wave per row, the whole row in registers (NPL values per lane), all

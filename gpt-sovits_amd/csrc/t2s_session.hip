@@ -20,14 +20,15 @@ namespace gsv {
 
 typedef unsigned u4v __attribute__((ext_vector_type(4)));
 
-// One side of the adopt launch: the arena and the per-row arrays of a RowState plus where its decode writes.  row_sampling, drawn,
-// dump and logp are null on BOTH sides when the session lacks them: the kernel tests dst's and only then reads src's.
+// One side of the adopt launch: the arena and the per-row arrays of a RowState plus where its decode writes.  row_sampling,
+// row_limits, drawn, dump and logp are null on BOTH sides when the session lacks them: the kernel tests dst's and only then reads src's.
 struct AdoptView {
   void* kv; unsigned long long layer_stride;   // elements per (layer, k|v)
   int smax;                                    // positions per (row, head) of the arena
   int *state, *plen, *ytok, *rng_row, *out_tokens, *out_len, *drawn;
   unsigned long long* rng_seed;
   RowSampling* row_sampling;
+  RowLimits* row_limits;
   float *ybuf, *dump, *logp;
 };
 // what the adopt launch moves for admitted row i -> slot[i]: src is the staging side, dst the session's own
@@ -89,6 +90,7 @@ __global__ __launch_bounds__(256) void session_adopt_kernel(AdoptArgs a, int hg 
     a.dst.rng_seed[slot] = a.src.rng_seed[i];
     a.dst.rng_row[slot] = a.src.rng_row[i];
     if (a.dst.row_sampling) a.dst.row_sampling[slot] = a.src.row_sampling[i];
+    if (a.dst.row_limits) a.dst.row_limits[slot] = a.src.row_limits[i];
     a.dst.out_len[slot] = a.src.out_len[i];
     a.dst.out_tokens[(size_t)slot * a.steps] = a.src.out_tokens[(size_t)i * a.steps];
     if (a.dst.drawn) { a.dst.drawn[2 * slot] = a.src.drawn[2 * i]; a.dst.drawn[2 * slot + 1] = a.src.drawn[2 * i + 1]; }
@@ -160,12 +162,12 @@ int launch_session_release(int* state, int mb, const int* slot, int n, int slots
   return GSV_OK;
 }
 
-// r's side of the adopt launch, with where its decode writes; per_row as in step_params
-AdoptView adopt_view(const RowState& r, const RowOutputs& o, bool per_row) {
+// r's side of the adopt launch, with where its decode writes; per_row and limits as in step_params
+AdoptView adopt_view(const RowState& r, const RowOutputs& o, bool per_row, bool limits) {
   AdoptView v;
   v.kv = r.kv; v.layer_stride = r.kv_layer_stride; v.smax = r.max_seq;
   v.state = r.state; v.plen = r.plen; v.ytok = r.ytok; v.rng_row = r.rng_row; v.rng_seed = r.rng_seed;
-  v.row_sampling = per_row ? r.row_sampling : nullptr; v.ybuf = r.ybuf;
+  v.row_sampling = per_row ? r.row_sampling : nullptr; v.row_limits = limits ? r.row_limits : nullptr; v.ybuf = r.ybuf;
   v.out_tokens = o.out_tokens; v.out_len = o.out_len; v.drawn = o.drawn; v.dump = o.dump; v.logp = o.logp;
   return v;
 }
@@ -183,6 +185,7 @@ int session_begin(gsv_t2s* h, const gsv_sampling_params* sp, int slots, int row_
   GSV_RC(need(h, "ses_rng_row", mb * 4, (void**)&st.rng_row));
   GSV_RC(need(h, "ses_rng_seed", mb * 8, (void**)&st.rng_seed));
   GSV_RC(need(h, "ses_row_sampling", mb * sizeof(RowSampling), (void**)&st.row_sampling));
+  GSV_RC(need(h, "ses_row_limits", mb * sizeof(RowLimits), (void**)&st.row_limits));
   GSV_RC(need(h, "ses_sp", sizeof(StepParams), (void**)&st.sp));
   GSV_RC(need(h, "ses_out_tokens", mb * ms * 4, (void**)&so.out_tokens));
   GSV_RC(need(h, "ses_out_len", mb * 4, (void**)&so.out_len));
@@ -198,6 +201,7 @@ int session_begin(gsv_t2s* h, const gsv_sampling_params* sp, int slots, int row_
   GSV_HIP(hipMemset(st.logits, 0, mb * V * 4));
   for (auto& e : z.ev) if (!e) GSV_HIP(hipEventCreate(&e));
   z.sp = *sp; z.slots = slots; z.budget = step_budget(*sp); z.row_sampling = row_sampling != 0;
+  z.row_limits = false; h->limits_on = false; h->row_limits_next.clear();
   z.out = take_outputs(h, out_tokens, out_len);
   // a hook the session lacks is off in an admission's step 0 as well
   so.force = z.out.force ? z.staging_force : nullptr; so.dump = z.out.dump ? dump : nullptr;
@@ -223,7 +227,7 @@ int session_begin(gsv_t2s* h, const gsv_sampling_params* sp, int slots, int row_
 
 int session_admit(gsv_t2s* h, int n, const int32_t* slot_ids, const int32_t* phones, const int32_t* phone_lens, const float* bert,
                   const int32_t* prompts_packed, const int32_t* prompt_lens, const uint64_t* rng_seeds, const int32_t* rng_rows,
-                  const gsv_row_sampling_t* row_sampling, hipStream_t s) {
+                  const gsv_row_sampling_t* row_sampling, const std::vector<gsv_row_limits_t>& limits, hipStream_t s) {
   T2SSession& z = h->ses;
   RowState& st = z.staging;
   const RowOutputs& so = z.staging_out;
@@ -244,6 +248,20 @@ int session_admit(gsv_t2s* h, int n, const int32_t* slot_ids, const int32_t* pho
   GSV_HIP(hipMemcpyAsync(z.st_slot, slot_ids, (size_t)n * 4, hipMemcpyHostToDevice, s));
   if (z.row_sampling)
     GSV_HIP(hipMemcpyAsync(st.row_sampling, row_sampling, (size_t)n * sizeof(RowSampling), hipMemcpyHostToDevice, s));
+  if (!limits.empty() && !z.row_limits) {
+    // The first admission that brings limits: from here on every slot has its own (the session's scalars until a row brings
+    // others) and both sets of StepParams point at them, so that the LIMITS kernels run.  The stream is idle between calls.
+    const std::vector<gsv_row_limits_t> all((size_t)h->max_batch, limits_of(z.sp));
+    GSV_HIP(hipMemcpy(h->rows.row_limits, all.data(), all.size() * sizeof(RowLimits), hipMemcpyHostToDevice));
+    const StepParams p = step_params(z.sp, h->rows, z.out, z.row_sampling, true), ps = step_params(z.sp, st, so, z.row_sampling, true);
+    GSV_HIP(hipMemcpy(h->rows.sp, &p, sizeof(p), hipMemcpyHostToDevice));
+    GSV_HIP(hipMemcpy(st.sp, &ps, sizeof(ps), hipMemcpyHostToDevice));
+    z.row_limits = true; h->limits_on = true;
+  }
+  // this admission's rows: their own limits, or the session's scalars, which also wipe what the slot's last occupant had
+  const std::vector<gsv_row_limits_t> mine = !limits.empty() ? limits : std::vector<gsv_row_limits_t>((size_t)n, limits_of(z.sp));
+  if (z.row_limits)
+    GSV_HIP(hipMemcpyAsync(st.row_limits, mine.data(), (size_t)n * sizeof(RowLimits), hipMemcpyHostToDevice, s));
   GSV_HIP(hipMemsetAsync(so.out_len, 0xFF, (size_t)n * 4, s));     // -1: not finished
   if (so.force)   // step 0 of row i is forced with its slot's entry
     for (int i = 0; i < n; ++i)
@@ -251,7 +269,7 @@ int session_admit(gsv_t2s* h, int n, const int32_t* slot_ids, const int32_t* pho
   GSV_RC(t2s_prefill_into(h, st, phones, phone_lens, n, bert, prompts_packed, prompt_lens, s));
   GSV_RC(t2s_step0_tail(h, st, s));   // the rows now stand where gsv_t2s_decode's rows stand after its step 0
   AdoptArgs a;
-  a.src = adopt_view(st, so, z.row_sampling); a.dst = adopt_view(h->rows, z.out, z.row_sampling);
+  a.src = adopt_view(st, so, z.row_sampling, z.row_limits); a.dst = adopt_view(h->rows, z.out, z.row_sampling, z.row_limits);
   a.n = n; a.slots = z.slots; a.mb = h->max_batch; a.ycap = h->ycap; a.d = c.dim; a.V = c.vocab; a.L = c.n_layer; a.H = c.n_head;
   a.esize = (int)esz(h); a.steps = (int)ms; a.slot = z.st_slot;
   GSV_HIP(hipEventRecord(z.ev[0], s));
@@ -325,9 +343,18 @@ int gsv_t2s_session_admit(gsv_t2s_t* h, int n, const int32_t* slot_ids, const in
   GSV_T2S_IN_SESSION(h, "t2s_session_admit", " (gsv_t2s_session_begin)");
   const T2SSession& z = h->ses;
   const int max_seq = h->rows.max_seq;
-  GSV_REQUIRE(slot_ids && phones && phone_lens && prompts_packed && prompt_lens && rng_seeds && rng_rows,
-              "t2s_session_admit: null argument");
+  // gsv_t2s_set_row_limits' rows are this admission's alone, whatever becomes of it
+  std::vector<gsv_row_limits_t> limits;
+  limits.swap(h->row_limits_next);
+  const bool lim = !limits.empty();
+  GSV_REQUIRE(slot_ids && phones && phone_lens && prompt_lens && rng_seeds && rng_rows, "t2s_session_admit: null argument");
   GSV_REQUIRE(n >= 1 && n <= z.slots, "t2s_session_admit: %d rows for a session of %d slots", n, z.slots);
+  GSV_REQUIRE(!lim || (int)limits.size() == n, "t2s_session_admit: gsv_t2s_set_row_limits gave %d rows for an admission of %d rows",
+              (int)limits.size(), n);
+  if (lim) GSV_RC(check_row_limits_steps("t2s_session_admit", limits, z.sp.max_steps));
+  long long packed = 0;
+  for (int i = 0; i < n; ++i) packed += prompt_lens[i] > 0 ? prompt_lens[i] : 0;
+  GSV_REQUIRE(prompts_packed || (lim && packed == 0), "t2s_session_admit: null argument");
   GSV_REQUIRE(!z.row_sampling || row_sampling, "t2s_session_admit: the session samples per row, row_sampling is null");
   GSV_REQUIRE(z.row_sampling || !row_sampling, "t2s_session_admit: row_sampling given, but the session was opened without it");
   if (row_sampling) GSV_RC(check_row_sampling("t2s_session_admit", row_sampling, n));
@@ -340,16 +367,18 @@ int gsv_t2s_session_admit(gsv_t2s_t* h, int n, const int32_t* slot_ids, const in
     GSV_REQUIRE(!taken[sl], "t2s_session_admit: slot %d is given twice", sl);
     taken[sl] = 1;
     GSV_REQUIRE(phone_lens[i] >= 1, "t2s_session_admit: empty phoneme sequence in row %d", i);
-    GSV_REQUIRE(P >= 1, "t2s_session_admit: row %d has prompt length %d (must be >= 1)", i, P);
-    GSV_REQUIRE((long long)phone_lens[i] + P + 2 + z.budget <= max_seq,
+    // a prompt-free row only with limits of its own: its EOS horizon is then its own too (gsv_t2s_prefill_ragged)
+    GSV_REQUIRE(P >= (lim ? 0 : 1), "t2s_session_admit: row %d has prompt length %d (must be >= 1)", i, P);
+    const int budget = lim ? step_budget(limits[i]) : z.budget;
+    GSV_REQUIRE((long long)phone_lens[i] + P + 2 + budget <= max_seq,
                 "t2s_session_admit: row %d: %d positions + 2 + %d steps exceed the K/V arena (max_seq %d)", i, phone_lens[i] + P,
-                z.budget, max_seq);
-    GSV_REQUIRE(phone_lens[i] <= h->pe_rows && (long long)P + z.budget <= h->pe_rows,
-                "t2s_session_admit: row %d: prompt %d + %d steps exceed the position table (%d rows)", i, P, z.budget, h->pe_rows);
-    GSV_REQUIRE((long long)P + z.budget <= h->ycap, "t2s_session_admit: row %d: prompt %d + %d steps exceed the token history (%d)",
-                i, P, z.budget, h->ycap);
+                budget, max_seq);
+    GSV_REQUIRE(phone_lens[i] <= h->pe_rows && (long long)P + budget <= h->pe_rows,
+                "t2s_session_admit: row %d: prompt %d + %d steps exceed the position table (%d rows)", i, P, budget, h->pe_rows);
+    GSV_REQUIRE((long long)P + budget <= h->ycap, "t2s_session_admit: row %d: prompt %d + %d steps exceed the token history (%d)",
+                i, P, budget, h->ycap);
   }
-  return session_admit(h, n, slot_ids, phones, phone_lens, bert, prompts_packed, prompt_lens, rng_seeds, rng_rows, row_sampling,
+  return session_admit(h, n, slot_ids, phones, phone_lens, bert, prompts_packed, prompt_lens, rng_seeds, rng_rows, row_sampling, limits,
                        (hipStream_t)stream);
 }
 
@@ -383,6 +412,7 @@ int gsv_t2s_session_end(gsv_t2s_t* h) {
   T2SSession& z = h->ses;
   z.open = false; z.live.clear();
   z.out = RowOutputs();
+  z.row_limits = false; h->limits_on = false; h->row_limits_next.clear();
   h->rows.B = 0;   // the next decode needs a prefill of its own, as on a fresh handle
   h->rng_seed_up.clear(); h->rng_row_up.clear(); h->row_sampling_up.clear();
   return GSV_OK;

@@ -86,18 +86,37 @@ def plan_continuous(lengths: Sequence[int], slots: int, chunk: int, admit_min: O
     return trace
 
 
+def row_limit_tuples(row_limits, needs, max_seq):
+    """The per-row limits as the engine takes them.  row_limits: [(eos_mask_steps, early_stop_num | None, max_steps)], needs:
+    the positions each row's text + prompt use (+ 2).  A row's budget is min(wanted_b, max_seq - need_b), wanted_b =
+    min(max_steps_b, early_stop_num_b + 1): where the arena is the smaller bound it becomes the row's max_steps.  Returns
+    (tuples, budgets, whether the arena bounds any row)."""
+    out, budgets, short = [], [], False
+    for (eos, es, ms), need in zip(row_limits, needs):
+        es = -1 if es is None else int(es)
+        want = int(ms) if es == -1 else min(int(ms), es + 1)
+        b = min(want, max_seq - need)
+        short = short or b < want
+        out.append((int(eos), es if es != -1 and es + 1 <= b else -1, max(b, 1)))
+        budgets.append(b)
+    return out, budgets, short
+
+
 class T2SSession:
     """An open decode session of a Text2SemanticDecoder (gsv_t2s_session_*): `slots` rows of its K/V arena that are admitted,
     advanced a chunk of steps at a time and admitted again when their row has finished.  Use as a context manager."""
 
     def __init__(self, dec: "Text2SemanticDecoder", slots, top_k, top_p, temperature, repetition_penalty, early_stop_num,
-                 eos_mask_steps, max_steps, row_sampling=False, force=False, dump_logits=False, logprobs=False):
+                 eos_mask_steps, max_steps, row_sampling=False, force=False, dump_logits=False, logprobs=False, row_limits=False):
         if not dec._loaded:
             raise RuntimeError("load_state_dict() first")
         self.dec, self.slots, self.per_row = dec, int(slots), bool(row_sampling)
+        self.row_limits = bool(row_limits)
+        self.scalars = (int(eos_mask_steps), -1 if early_stop_num is None else int(early_stop_num))
         dev = dec.device
         wanted = max_steps if early_stop_num in (-1, None) else min(max_steps, int(early_stop_num) + 1)
         self.budget = int(wanted)
+        self._row_budget = [self.budget] * self.slots              # the budget of the row in each slot (its own with limits)
         self._owner: List[Optional[int]] = [None] * self.slots     # ticket of the row in each slot
         self._prompt: List[Optional[torch.Tensor]] = [None] * self.slots
         self._next_ticket = 0
@@ -151,8 +170,10 @@ class T2SSession:
         return sum(o is not None for o in self._owner)
 
     def admit(self, rows: Sequence[dict], slots: Optional[Sequence[int]] = None) -> List[int]:
-        """rows: dict(x, bert, prompt, key=(seed, row), sampling=None[, force=tokens]); each goes into the next free slot (or
-        slots[i]) and has run its step 0 when this returns.  Returns one ticket per row."""
+        """rows: dict(x, bert, prompt, key=(seed, row), sampling=None[, force=tokens][, limits=(eos_mask_steps, early_stop_num,
+        max_steps)]); each goes into the next free slot (or slots[i]) and has run its step 0 when this returns.  In a session
+        opened with row_limits=True a row may bring limits, which replace the session's three for it (its budget also bounded by
+        the K/V arena), and prompt=None: a prompt-free row.  Returns one ticket per row."""
         dec, dev, n = self.dec, self.dec.device, len(rows)
         if slots is None:
             slots = self.free[:n]
@@ -166,11 +187,22 @@ class T2SSession:
         l = _lib.lib()
         with torch.cuda.device(dev):
             lens = [int(r["x"].shape[-1]) for r in rows]
-            prompts = [r["prompt"].reshape(-1) for r in rows]
+            prompts = [torch.zeros(0, dtype=torch.int64) if r.get("prompt") is None else r["prompt"].reshape(-1) for r in rows]
             plens = [int(p_.shape[0]) for p_ in prompts]
+            limits, budgets = None, [self.budget] * n
+            if any(r.get("limits") is not None for r in rows) or min(plens) < 1:
+                if not self.row_limits:
+                    raise ValueError("limits or a prompt-free row in a session opened without row_limits=True")
+                mine = [r["limits"] if r.get("limits") is not None else (self.scalars[0], self.scalars[1], self.budget) for r in rows]
+                needs = [a + b + 2 for a, b in zip(lens, plens)]
+                limits, budgets, _ = row_limit_tuples(mine, needs, dec.max_seq)
+                if min(budgets) < 1:
+                    raise ValueError(f"sequence of {needs[budgets.index(min(budgets))]} positions does not fit max_seq={dec.max_seq}")
+                if max(budgets) > self.budget:
+                    raise ValueError(f"a row's budget of {max(budgets)} steps exceeds the session's {self.budget}")
             phones = torch.cat([r["x"].reshape(-1) for r in rows]).to(dev, torch.int32).contiguous()
             bert_dev = dec._bert_rows([r.get("bert") for r in rows], lens)
-            pr = torch.cat(prompts).to(dev, torch.int32).contiguous()
+            pr = torch.cat([p_.to(dev, torch.int32) for p_ in prompts]).contiguous()
             if self.force is not None:
                 for r, s in zip(rows, slots):
                     if r.get("force") is not None and 0 <= s < self.slots:
@@ -186,8 +218,12 @@ class T2SSession:
             if self.per_row:
                 rs_h = (_lib.RowSampling * n)(*[_lib.RowSampling(int(k) if k is not None else 0, float(p_ if p_ is not None else 1.0),
                                                                  float(t), float(rp)) for k, p_, t, rp in (r["sampling"] for r in rows)])
+            if limits is not None:
+                rl_h = (_lib.RowLimits * n)(*[_lib.RowLimits(e, es, ms, 0) for e, es, ms in limits])
+                _lib.check(l.gsv_t2s_set_row_limits(dec._h, rl_h, n), "gsv_t2s_set_row_limits")
             _lib.check(l.gsv_t2s_session_admit(dec._h, n, C.cast(slots_h, C.c_void_p), phones.data_ptr(), C.cast(lens_h, C.c_void_p),
-                                               bert_dev.data_ptr() if bert_dev is not None else None, pr.data_ptr(),
+                                               bert_dev.data_ptr() if bert_dev is not None else None,
+                                               pr.data_ptr() if pr.numel() else None,
                                                C.cast(plens_h, C.c_void_p), C.cast(seeds_h, C.c_void_p), C.cast(rrows_h, C.c_void_p),
                                                C.cast(rs_h, C.c_void_p) if rs_h is not None else None,
                                                C.c_void_p(dec.stream.cuda_stream)), "gsv_t2s_session_admit")
@@ -196,7 +232,8 @@ class T2SSession:
             _lib.check(l.gsv_t2s_session_adopt_info(dec._h, C.byref(ms), C.byref(nb)), "gsv_t2s_session_adopt_info")
             self.adopt.append((n, ms.value, nb.value))
         tickets = []
-        for s, p_ in zip(slots, prompts):
+        for s, p_, b_ in zip(slots, prompts, budgets):
+            self._row_budget[s] = b_
             self._owner[s] = self._next_ticket
             self._prompt[s] = p_.to(dev, torch.int64)
             tickets.append(self._next_ticket)
@@ -259,7 +296,7 @@ class T2SSession:
                         self.logits[self._owner[s]] = self.dump[:steps_h[s], s].clone()
                     if self.logp is not None:
                         self.logprobs[self._owner[s]] = self.logp[s, :n + 1].clone()
-                        self.cut[self._owner[s]] = n >= self.budget - 1
+                        self.cut[self._owner[s]] = n >= self._row_budget[s] - 1
                     self._owner[s], self._prompt[s] = None, None
         return out
 
@@ -349,19 +386,25 @@ class Text2SemanticDecoder:
 
     def _run(self, x: Sequence[torch.Tensor], prompts: torch.Tensor, bert: Sequence[torch.Tensor], top_k, top_p,
              early_stop_num, temperature, repetition_penalty, eos_mask_steps, noise=None, seed=0,
-             max_steps: int = 1500, force_tokens=None, dump_logits=False, rng_keys=None, row_sampling=None, logprobs=False):
+             max_steps: int = 1500, force_tokens=None, dump_logits=False, rng_keys=None, row_sampling=None, logprobs=False,
+             row_limits=None):
         """prompts: [B, P] (one prompt length for the batch; P = 0 or None: prompt-free) or a list of B 1-D prompts of
         lengths P_b >= 1 (ragged: gsv_t2s_prefill_ragged).  rng_keys: optional [(seed_b, row_b)] per row, the counter-RNG
         key that replaces (seed, b) (gsv_t2s_set_row_rng).  row_sampling: optional [(top_k, top_p, temperature,
         repetition_penalty)] per row, which replace the four scalar arguments for this call (gsv_t2s_set_row_sampling).
         logprobs=True leaves last_logprobs: B 1-D fp32 tensors, row b's idx[b] + 1 log-probabilities of the tokens it took
         under the model's own distribution (gsv_t2s_set_logprobs): the generated tokens, then the finishing step; and
-        last_cut: per row, whether the step budget ended it instead of EOS."""
+        last_cut: per row, whether the step budget ended it instead of EOS.  row_limits: optional [(eos_mask_steps,
+        early_stop_num, max_steps)] per row, which replace eos_mask_steps, early_stop_num and max_steps for this call
+        (gsv_t2s_set_row_limits); every row is then held to its own budget, the K/V arena's bound included, and a list of
+        prompts may hold None or empty prompts: prompt-free rows."""
         if not self._loaded:
             raise RuntimeError("load_state_dict() first")
         B = len(x)
         if row_sampling is not None and len(row_sampling) != B:
             raise ValueError(f"{len(row_sampling)} sampling tuples for {B} rows")
+        if row_limits is not None and len(row_limits) != B:
+            raise ValueError(f"{len(row_limits)} limit tuples for {B} rows")
         dev = self.device
         if prompts is None:                  # prompt-free (reference t2s_model.py:849-856): empty audio prefix
             prompts = torch.zeros(B, 0, dtype=torch.int64)
@@ -369,8 +412,9 @@ class Text2SemanticDecoder:
         if ragged:
             if len(prompts) != B:
                 raise ValueError(f"{len(prompts)} prompts for {B} rows")
+            prompts = [torch.zeros(0, dtype=torch.int64) if p_ is None else p_ for p_ in prompts]
             plens = [int(p_.reshape(-1).shape[0]) for p_ in prompts]
-            if min(plens) < 1:
+            if min(plens) < 1 and row_limits is None:
                 raise ValueError("ragged prompts must each hold at least one token (prompt-free rows: prompts=None)")
         if rng_keys is not None and len(rng_keys) != B:
             raise ValueError(f"{len(rng_keys)} RNG keys for {B} rows")
@@ -385,14 +429,20 @@ class Text2SemanticDecoder:
                 need = max(lens) + P + 2
             wanted = max_steps if early_stop_num in (-1, None) else min(max_steps, int(early_stop_num) + 1)
             budget = min(wanted, self.max_seq - need)
+            limits = None
+            if row_limits is not None:
+                needs = [n_ + (p_ if ragged else P) + 2 for n_, p_ in zip(lens, plens if ragged else lens)]
+                limits, budgets, short = row_limit_tuples(row_limits, needs, self.max_seq)
+                need = needs[budgets.index(min(budgets))]
+                budget = max(budgets) if min(budgets) >= 1 else 0
             if budget < 1:
                 raise ValueError(f"sequence of {need} positions does not fit max_seq={self.max_seq}")
-            arena_bound = budget < wanted
+            arena_bound = budget < wanted if limits is None else short
             phones = torch.cat([t.reshape(-1) for t in x]).to(dev, torch.int32).contiguous()
             lens_h = (C.c_int32 * B)(*lens)
             bert_dev = self._bert_rows(bert, lens)
             if ragged:
-                pr = torch.cat([p_.reshape(-1) for p_ in prompts]).to(dev, torch.int32).contiguous()
+                pr = torch.cat([p_.reshape(-1).to(dev, torch.int32) for p_ in prompts]).contiguous()
             else:
                 pr = prompts.to(dev, torch.int32).contiguous()
             out_tokens = torch.zeros(B, budget, dtype=torch.int32, device=dev)
@@ -412,11 +462,14 @@ class Text2SemanticDecoder:
             if early_stop_num not in (-1, None) and budget < int(early_stop_num) + 1:
                 sp.early_stop_num = -1   # the arena bound (max_steps) ends generation first
             s = C.c_void_p(self.stream.cuda_stream)
+            if limits is not None:   # in front of the prefill: they are what lets it take prompt-free rows
+                rl_h = (_lib.RowLimits * B)(*[_lib.RowLimits(e, es, ms, 0) for e, es, ms in limits])
+                _lib.check(l.gsv_t2s_set_row_limits(self._h, rl_h, B), "gsv_t2s_set_row_limits")
             if ragged:
                 plens_h = (C.c_int32 * B)(*plens)
                 _lib.check(l.gsv_t2s_prefill_ragged(self._h, phones.data_ptr(), C.cast(lens_h, C.c_void_p), B,
                                                     bert_dev.data_ptr() if bert_dev is not None else None,
-                                                    pr.data_ptr(), C.cast(plens_h, C.c_void_p), s),
+                                                    pr.data_ptr() if pr.numel() else None, C.cast(plens_h, C.c_void_p), s),
                            "gsv_t2s_prefill_ragged")
             else:
                 _lib.check(l.gsv_t2s_prefill(self._h, phones.data_ptr(), C.cast(lens_h, C.c_void_p), B,
@@ -486,7 +539,7 @@ class Text2SemanticDecoder:
                     y_list.append(y_all[b, :P + n])
             self.last_logprob_buffer = logp     # [B][budget], NaN where a row ran no step; last_logprobs are views of it
             self.last_logprobs = None if logp is None else [logp[b, :idx[b] + 1] for b in range(B)]
-            self.last_cut = None if logp is None else [idx[b] >= budget - 1 for b in range(B)]
+            self.last_cut = None if logp is None else [idx[b] >= (budget if limits is None else budgets[b]) - 1 for b in range(B)]
         return y_list, idx
 
     # ---- reference entry points -----------------------------------------------------
@@ -541,21 +594,22 @@ class Text2SemanticDecoder:
 
     # ---- decode sessions: continuous batching ------------------------------------------
     def open_session(self, slots: int, top_k, top_p, temperature, repetition_penalty, early_stop_num, eos_mask_steps: int = 1,
-                     max_steps: int = 1500, row_sampling: bool = False, **debug) -> T2SSession:
+                     max_steps: int = 1500, row_sampling: bool = False, row_limits: bool = False, **debug) -> T2SSession:
         """Opens a decode session of `slots` rows (<= max_batch); until it is closed the other entry points of this decoder
         raise.  The four sampling values hold for every row unless row_sampling=True, in which case each admitted row brings
         its own tuple.  debug: force=True / dump_logits=True, the parity hooks of `_run`, per slot.  logprobs=True: the
         session fills `logprobs[ticket]` / `cut[ticket]` (what `_run(logprobs=True)` leaves for a row) when `advance` reports
-        the row."""
+        the row.  row_limits=True: admitted rows may bring limits=(eos_mask_steps, early_stop_num, max_steps) of their own, none
+        above this session's budget, and prompt=None (T2SSession.admit)."""
         return T2SSession(self, slots, top_k, top_p, temperature, repetition_penalty, early_stop_num, eos_mask_steps, max_steps,
-                          row_sampling=row_sampling, **debug)
+                          row_sampling=row_sampling, row_limits=row_limits, **debug)
 
     @torch.no_grad()
     def infer_panel_continuous(self, x: List[torch.LongTensor], prompts, bert_feature: List[torch.Tensor], top_k: int = -100,
                                top_p: int = 100, early_stop_num: int = -1, temperature: float = 1.0,
                                repetition_penalty: float = 1.35, rng_keys=None, row_sampling=None, slots: Optional[int] = None,
                                chunk: int = 32, admit_min: Optional[int] = None, max_steps: int = 1500, force_tokens=None,
-                               dump_logits: bool = False, logprobs: bool = False):
+                               dump_logits: bool = False, logprobs: bool = False, row_limits=None):
         """`infer_panel_batch_infer` for a queue of any length through ONE decode session: rows are admitted in the order given
         whenever `admit_min` slots are free (default max(1, slots // 4); see admit_count), `chunk` steps run between admissions
         (both defaults from the sweep of tools/continuous_ar_bench.py, profiles/continuous_ar.txt),
@@ -565,8 +619,13 @@ class Text2SemanticDecoder:
         ordinary path after the session (and listed in last_truncated if the arena cuts it), as it would be there.
         force_tokens [N][steps] / dump_logits: the parity hooks of `_run` (tests); last_logits_dump is then a list of N
         [steps run][vocab] tensors.  logprobs=True: last_logprobs / last_cut of `_run`, in input order.  last_session is the
-        closed session (its history, modes and adopt times)."""
+        closed session (its history, modes and adopt times).  row_limits=True: a row short of arena room is admitted with its
+        smaller budget instead; row_limits=[(eos_mask_steps, early_stop_num, max_steps) | None, ...]: the rows' own limits
+        as well (none above this call's budget), and prompts[i] may be None: a prompt-free row."""
         N = len(x)
+        per_limits = row_limits if isinstance(row_limits, (list, tuple)) else None
+        if per_limits is not None and len(per_limits) != N:
+            raise ValueError(f"{len(per_limits)} limit tuples for {N} rows")
         if rng_keys is None or len(rng_keys) != N:
             raise ValueError("infer_panel_continuous needs one RNG key (seed, row) per row")
         if row_sampling is not None and len(row_sampling) != N:
@@ -576,12 +635,19 @@ class Text2SemanticDecoder:
         slots = self.max_batch if slots is None else int(slots)
         admit_min = max(1, slots // 4) if admit_min is None else int(admit_min)
         wanted = max_steps if early_stop_num in (-1, None) else min(max_steps, int(early_stop_num) + 1)
-        rows = [dict(x=x[i], bert=bert_feature[i] if bert_feature is not None else None, prompt=prompts[i].reshape(-1),
+        rows = [dict(x=x[i], bert=bert_feature[i] if bert_feature is not None else None,
+                     prompt=torch.zeros(0, dtype=torch.int64) if prompts[i] is None else prompts[i].reshape(-1),
                      key=rng_keys[i], sampling=None if row_sampling is None else row_sampling[i]) for i in range(N)]
+        es = -1 if early_stop_num is None else int(early_stop_num)
+        for i, r in enumerate(rows):
+            if per_limits is not None and per_limits[i] is not None:
+                r["limits"] = tuple(per_limits[i])
+            elif row_limits and int(r["x"].shape[-1]) + int(r["prompt"].shape[0]) + 2 + wanted > self.max_seq:
+                r["limits"] = (1, es, int(max_steps))       # the session's scalars: admit() bounds the budget by the arena
         if force_tokens is not None:
             for i, r in enumerate(rows):
                 r["force"] = force_tokens[i]
-        fits = [int(r["x"].shape[-1]) + int(r["prompt"].shape[0]) + 2 + wanted <= self.max_seq for r in rows]
+        fits = [bool(row_limits) or int(r["x"].shape[-1]) + int(r["prompt"].shape[0]) + 2 + wanted <= self.max_seq for r in rows]
         if (force_tokens is not None or dump_logits) and not all(fits):
             raise ValueError("the parity hooks need every row to fit the K/V arena with its full budget")
         queue = [i for i in range(N) if fits[i]]
@@ -592,7 +658,7 @@ class Text2SemanticDecoder:
         if queue:
             with self.open_session(slots, top_k, top_p, temperature, repetition_penalty, early_stop_num, 1, max_steps,
                                    row_sampling=row_sampling is not None, force=force_tokens is not None,
-                                   dump_logits=dump_logits, logprobs=logprobs) as ses:
+                                   dump_logits=dump_logits, logprobs=logprobs, row_limits=bool(row_limits)) as ses:
                 q, where = 0, {}
                 while q < len(queue) or ses.live:
                     k = admit_count(len(ses.free), len(queue) - q, ses.live, admit_min)

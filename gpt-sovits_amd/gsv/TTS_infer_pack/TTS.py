@@ -1583,7 +1583,7 @@ class TTS:
         o["super_sampling"] = o["super_sampling"] and self.configs.use_vocoder and self.configs.version == "v3"
         return o
 
-    def plan_batch(self, plans: List[dict], mixed_sampling: bool = False) -> List[List[dict]]:
+    def plan_batch(self, plans: List[dict], mixed_sampling: bool = False, mixed_limits: bool = False) -> List[List[dict]]:
         """The AR launches of run_batch.  `plans[r]` = {"data": request r's to_batch batches, "no_prompt", "actual_seed",
         "opts"}.  Sentence j of batch bi of request r draws with the counter-RNG key (actual_seed_r + bi, j mod max_batch)
         -- the key it has in run(r) (the naive / prompt-free loop decodes every sentence alone: row 0).  Sentences are
@@ -1593,7 +1593,11 @@ class TTS:
         with "cand" = c and the key (seed, row + 1024 c): candidate 0 is the entry the request has without the key.
         mixed_sampling=True: the sampling parameters are per row (gsv_t2s_set_row_sampling) and no longer separate groups:
         their four slots of the group tuple hold None and every row carries "sampling" = (top_k, top_p, temperature,
-        repetition_penalty) of its request."""
+        repetition_penalty) of its request.
+        mixed_limits=True: the EOS horizon, the early stop and the step budget are per row (gsv_t2s_set_row_limits) and
+        parallel_infer, prompt-free and the budget no longer separate groups: their three slots hold None and every row
+        carries "limits" = (eos_mask_steps, early_stop_num, max_steps) -- (11 naive / prompt-free else 1, the configured early
+        stop, the budget run() gives the sentence) -- and "no_prompt".  The keys are unchanged: naive rows keep row 0."""
         mb, max_seq = self.t2s_model.max_batch, self.t2s_model.max_seq
         groups: Dict[tuple, List[dict]] = {}
         for r, pl in enumerate(plans):
@@ -1608,10 +1612,14 @@ class TTS:
                     need = (n if naive else max(lens[j - j % mb:j - j % mb + mb])) + P + 2
                     budget = min(wanted, max_seq - need)
                     sampling = (o["top_k"], o["top_p"], o["temperature"], o["repetition_penalty"])
-                    g = ((None,) * 4 if mixed_sampling else sampling) + (bool(o["parallel_infer"]), bool(pl["no_prompt"]), budget)
+                    per_launch = (bool(o["parallel_infer"]), bool(pl["no_prompt"]), budget)
+                    g = ((None,) * 4 if mixed_sampling else sampling) + ((None,) * 3 if mixed_limits else per_launch)
                     e = dict(r=r, bi=bi, j=j, len=n + P, group=g, key=(pl["actual_seed"] + bi, 0 if naive else j % mb))
                     if mixed_sampling:
                         e["sampling"] = sampling
+                    if mixed_limits:
+                        e["limits"] = (11 if naive else 1, int(early_stop_num(self.configs)), budget)
+                        e["no_prompt"] = bool(pl["no_prompt"])
                     if o.get("best_of", 1) > 1:
                         for c in range(o["best_of"]):
                             groups.setdefault(g, []).append(dict(e, cand=c, key=(e["key"][0], e["key"][1] + BEST_OF_ROW_STRIDE * c)))
@@ -1799,61 +1807,77 @@ class TTS:
         """run_batch(continuous_ar=True): plan_batch's launches put back together by group.  Returns (session, rows) in
         plan_batch's order: the launches of a parallel-decode group with prompts become ONE queue for a decode session
         (Text2SemanticDecoder.infer_panel_continuous), rows in plan_batch's order with the keys and sampling tuples it gave
-        them; prompt-free and naive groups stay the launches they are."""
+        them; prompt-free and naive groups stay the launches they are, unless plan_batch(mixed_limits=True) made the launches:
+        their rows bring limits and all of them go through the session."""
         out: List[Tuple[bool, List[dict]]] = []
         for rows in launches:
             g = rows[0]["group"]
-            session = g[4] and not g[5]          # parallel_infer and not prompt-free
+            session = g[4] is None or (g[4] and not g[5])   # mixed limits: every row; else parallel_infer and not prompt-free
             if session and out and out[-1][0] and out[-1][1][0]["group"] == g:
                 out[-1][1].extend(rows)
             else:
                 out.append((session, list(rows)))
         return out
 
-    def _ar_stage(self, plans: List[dict], mixed_sampling: bool = False, continuous_ar: bool = False) -> None:
+    def _ar_stage(self, plans: List[dict], mixed_sampling: bool = False, continuous_ar: bool = False,
+                  mixed_limits: bool = False) -> None:
         """Stage 2: every sentence of every request through the shared AR launches of plan_batch (mixed_sampling: launches
         shared across sampling parameters; a launch whose rows differ hands them over per row).  Reads `data`, `opts`,
         `voice`, `no_prompt`, `P`, `actual_seed`.  Writes run()'s pred_list / idx_list per batch: `preds[bi][j]`, the tokens
         of sentence j (prompt included), `idxs[bi][j]`, how many were generated (0 prompt-free), `kept[bi]` = _kept_tokens.
         continuous_ar: a group's launches are one decode session instead (plan_sessions).
+        mixed_limits: launches shared across parallel_infer, prompt-free and budgets as well; a launch whose rows differ in
+        them hands over limits and prompts per row (None for a prompt-free row), one that agrees takes the scalar path.
         A launch that holds candidate rows ("best_of") is decoded with log-probabilities; once every launch is back each such
         sentence keeps the tokens of the candidate choose_candidate picks, and `candidates[bi][j]` records the choice."""
         for pl in plans:
             pl["preds"] = [[None] * len(item["all_phones"]) for item in pl["data"]]
             pl["idxs"] = [[None] * len(item["all_phones"]) for item in pl["data"]]
         cands: Dict[tuple, Dict[int, tuple]] = {}       # (r, bi, j) -> candidate -> (its dict, y)
-        launches = self.plan_batch(plans, mixed_sampling=True) if mixed_sampling else self.plan_batch(plans)
+        pkw = dict(mixed_sampling=True) if mixed_sampling else {}
+        if mixed_limits:
+            pkw["mixed_limits"] = True
+        launches = self.plan_batch(plans, **pkw)
         work = self.plan_sessions(launches) if continuous_ar else [(False, rows) for rows in launches]
         for session, rows in work:
             o = plans[rows[0]["r"]]["opts"]
             kw = {}
             if mixed_sampling and len({e["sampling"] for e in rows}) > 1:     # a uniform launch takes the scalar path
                 kw["row_sampling"] = [e["sampling"] for e in rows]
-            no_prompt = rows[0]["group"][5]
-            naive = no_prompt or not o["parallel_infer"]
+            if mixed_limits:
+                lims, free = [e["limits"] for e in rows], [e["no_prompt"] for e in rows]
+                uniform = len(set(lims)) == 1 and len(set(free)) == 1
+                no_prompt, eos_steps, steps = uniform and free[0], lims[0][0], max(l_[2] for l_ in lims)
+                if not uniform or (session and (no_prompt or eos_steps != 1)):
+                    kw["row_limits"] = lims
+            else:
+                no_prompt = rows[0]["group"][5]
+                free = [no_prompt] * len(rows)
+                eos_steps, steps = 11 if no_prompt or not o["parallel_infer"] else 1, rows[0]["group"][6]
             want_lp = any("cand" in e for e in rows)
             if want_lp:
                 kw["logprobs"] = True
             items = [plans[e["r"]]["data"][e["bi"]] for e in rows]
             x = [it["all_phones"][e["j"]] for it, e in zip(items, rows)]
             bert = [it["all_bert_features"][e["j"]] for it, e in zip(items, rows)]
-            prompts = None if no_prompt else [plans[e["r"]]["voice"]["prompt_semantic"].view(-1) for e in rows]
+            prompts = None if no_prompt and "row_limits" not in kw else \
+                [None if f else plans[e["r"]]["voice"]["prompt_semantic"].view(-1) for e, f in zip(rows, free)]
             if session:
                 y, idx = self.t2s_model.infer_panel_continuous(
                     x, prompts, bert, o["top_k"], o["top_p"], early_stop_num(self.configs), o["temperature"],
-                    o["repetition_penalty"], rng_keys=[e["key"] for e in rows], max_steps=rows[0]["group"][6], **kw)
+                    o["repetition_penalty"], rng_keys=[e["key"] for e in rows], max_steps=steps, **kw)
             else:
                 y, idx = self.t2s_model._run(x, prompts, bert, o["top_k"], o["top_p"], early_stop_num(self.configs), o["temperature"],
-                                             o["repetition_penalty"], eos_mask_steps=11 if naive else 1,
-                                             max_steps=rows[0]["group"][6], rng_keys=[e["key"] for e in rows], **kw)
-            for k, (e, y_, i_) in enumerate(zip(rows, y, idx)):
+                                             o["repetition_penalty"], eos_mask_steps=eos_steps,
+                                             max_steps=steps, rng_keys=[e["key"] for e in rows], **kw)
+            for k, (e, y_, i_, f) in enumerate(zip(rows, y, idx, free)):
                 if "cand" in e:
                     c = dict(tokens=y_[-i_:] if i_ > 0 else y_[:0], logprobs=self.t2s_model.last_logprobs[k].cpu().numpy(), n=i_,
                              cut=self.t2s_model.last_cut[k])
                     cands.setdefault((e["r"], e["bi"], e["j"]), {})[e["cand"]] = (c, y_)
                     continue
                 plans[e["r"]]["preds"][e["bi"]][e["j"]] = y_
-                plans[e["r"]]["idxs"][e["bi"]][e["j"]] = 0 if no_prompt else i_
+                plans[e["r"]]["idxs"][e["bi"]][e["j"]] = 0 if f else i_
         for (r, bi, j), by_c in sorted(cands.items()):
             pl = plans[r]
             k, rec = choose_candidate(pl["opts"], [by_c[c][0] for c in sorted(by_c)])
@@ -2067,7 +2091,7 @@ class TTS:
                   shared_vocoder: bool = False, shared_bert: bool = False,
                   shared_hubert: bool = False, shared_sv: bool = False,
                   device_frontend: bool = False, continuous_ar: bool = False,
-                  continuous_cfm: bool = False) -> List[Tuple[int, np.ndarray]]:
+                  continuous_cfm: bool = False, mixed_limits: bool = False) -> List[Tuple[int, np.ndarray]]:
         """Several requests, each with its own reference voice, through shared AR decodes.  Each request dict takes the
         keys run() accepts plus an optional "voice" (make_voice); without one it uses its ref_audio_path / prompt_text
         (through make_voice's LRU) or the current prompt cache.  Returns one (sr, int16 audio) per request, in order: what
@@ -2100,6 +2124,10 @@ class TTS:
         (CFM.open_session) on the schedule of plan_cfm_session instead of one pass per (sample_steps, guidance rate) group:
         requests with different settings share the DiT launches, each row with its own step count and rate, and a finished
         row's place goes to the next waiting row.  Seeds, prompts, LoRA adapters, the vocoder and SOLA are those of shared_cfm.
+        mixed_limits=True: naive (parallel_infer=False), prompt-free and arena-bound sentences share AR launches (or, with
+        continuous_ar=True, the decode session) with the others: each row brings its EOS horizon, early stop and step budget
+        (plan_batch(mixed_limits=True), gsv_t2s_set_row_limits) and every request still gets the tokens it gets without the
+        keyword.
         A request with "best_of" = n > 1 decodes n candidates per sentence as further rows of the shared launches and keeps
         one (plan_batch, select_candidate; "best_of_score": a callable in its place); last_candidates[r][bi][j] then lists
         dict(n, mean_logprob, cut, chosen) per candidate, and is [] for a request without the key.
@@ -2118,7 +2146,8 @@ class TTS:
         if shared_hubert or shared_sv:
             requests = self._with_shared_voices(requests, shared_sv=shared_sv, device_frontend=device_frontend)
         plans = [self._plan_request(req) for req in requests]
-        self._ar_stage(plans, mixed_sampling=mixed_sampling, **({"continuous_ar": True} if continuous_ar else {}))
+        self._ar_stage(plans, mixed_sampling=mixed_sampling, **({"continuous_ar": True} if continuous_ar else {}),
+                       **({"mixed_limits": True} if mixed_limits else {}))
         self.last_candidates = [pl.get("candidates", []) for pl in plans]
         sr = self._output_sr()
         if shared_sovits and not self.configs.use_vocoder:

@@ -26,6 +26,11 @@ class RowSampling(C.Structure):
     _fields_ = [("top_k", C.c_int), ("top_p", C.c_float), ("temperature", C.c_float), ("repetition_penalty", C.c_float)]
 
 
+class RowLimits(C.Structure):
+    """gsv_row_limits_t: the EOS horizon, early stop and step budget of one batch row"""
+    _fields_ = [("eos_mask_steps", C.c_int), ("early_stop_num", C.c_int), ("max_steps", C.c_int), ("reserved", C.c_int)]
+
+
 class VitsConfig(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("inter_channels", "hidden_channels", "filter_channels", "n_heads", "n_layers",
                                         "kernel_size", "gin_channels", "n_symbols", "ssl_dim", "n_bins",
@@ -85,6 +90,7 @@ _SIGS = {
                                          C.c_void_p, C.c_void_p]),
     "gsv_t2s_set_row_rng": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "gsv_t2s_set_row_sampling": (C.c_int, [C.c_void_p, C.POINTER(RowSampling), C.c_int]),
+    "gsv_t2s_set_row_limits": (C.c_int, [C.c_void_p, C.POINTER(RowLimits), C.c_int]),
     "gsv_t2s_decode": (C.c_int, [C.c_void_p, C.POINTER(SamplingParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                  C.POINTER(C.c_int), C.c_void_p]),
     "gsv_t2s_session_begin": (C.c_int, [C.c_void_p, C.POINTER(SamplingParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -541,11 +541,19 @@ class Scheduler:
     the session's DiT rows (default min(tts.cfm_max_rows, 64); a guided row counts 2, and 1 is raised to 2 when a guided row
     waits); cfm_chunk: the most Euler steps one scheduler step runs before it takes in new arrivals.  wave_hold does not apply
     to this path: the session is the company a held request would have waited for.  Without the keyword the scheduler issues
-    exactly the launches it issued before the keyword existed."""
+    exactly the launches it issued before the keyword existed.
+    mixed_limits (off by default): prompt-free requests, parallel_infer=False requests, "best_of" requests and requests with a
+    row short of arena room are no longer exclusive.  Their rows enter the decode session with limits of their own
+    (plan_batch(mixed_limits=True): EOS horizon 11 for the naive and prompt-free ones, the arena-bound budget for the short
+    ones), a prompt-free row without a prompt, a "best_of" sentence as its n candidate rows; the session is opened with per-row
+    limits and log-probabilities, and a sentence is back when all its candidates are (choose_candidate then fills its tokens
+    and the request's `candidates`, as TTS._ar_stage does).  Only a request with a row that has no room at all (budget < 1)
+    stays exclusive: run_batch([request]) raises its own error for it alone.  Without the keyword nothing changes."""
 
     def __init__(self, tts, slots: Optional[int] = None, chunk: int = 32, admit_min: Optional[int] = None, wave_hold: int = 0,
                  shared_hubert: bool = True, shared_bert: bool = True, shared_sv: bool = False, device_frontend: bool = False,
-                 shared_vocoder: bool = False, continuous_cfm: bool = False, cfm_rows: Optional[int] = None, cfm_chunk: int = 2):
+                 shared_vocoder: bool = False, continuous_cfm: bool = False, cfm_rows: Optional[int] = None, cfm_chunk: int = 2,
+                 mixed_limits: bool = False):
         if tts.t2s_model is None or tts.vits_model is None:
             raise RuntimeError("init_t2s_weights / init_vits_weights first")
         if continuous_cfm and not getattr(tts.configs, "use_vocoder", False):
@@ -560,6 +568,8 @@ class Scheduler:
         self._front = dict(shared_hubert=bool(shared_hubert), shared_bert=bool(shared_bert), shared_sv=bool(shared_sv),
                            device_frontend=bool(device_frontend))
         self._shared_vocoder = bool(shared_vocoder)
+        self._mixed_limits = bool(mixed_limits)
+        self._cands: Dict[Tuple[int, int, int], Dict[int, tuple]] = {}  # (ticket, bi, j) -> candidate -> (its dict, y), until all are back
         self._cpol: Optional[_CfmPolicy] = None
         if continuous_cfm:
             from ._lib import CFM_SESSION_MAX_ROWS
@@ -631,6 +641,7 @@ class Scheduler:
         self._drop_cfm(ticket)
         self._requests.pop(ticket)
         self._rows.pop(ticket, None)
+        self._cands = {k: v for k, v in self._cands.items() if k[0] != ticket}
 
     def take_fragments(self) -> List[Tuple[int, int, Any]]:
         """the fragments the last step emitted, in emission order: [(ticket, bi, (sr, int16 audio))] -- per streaming request
@@ -716,7 +727,7 @@ class Scheduler:
                 folds = None
                 if pl["opts"]["return_fragment"]:                       # delivered fold by fold: (bi, j) order is fold order
                     pl["stream"] = []
-                    folds = [len(item["all_phones"]) for item in pl["data"]]
+                    folds = [sum(e["bi"] == bi for e in rows) for bi in range(len(pl["data"]))]     # candidate rows included
                 self._pol.arrive(t, len(rows), False, self._step, folds or None)
 
     def _budget(self) -> int:
@@ -725,7 +736,14 @@ class Scheduler:
 
     def _session_rows(self, pl: dict) -> Optional[List[dict]]:
         """the request's rows in (bi, j) order with plan_batch's keys and sampling tuples -- or None: the request is exclusive
-        (prompt-free, the naive loop, "best_of" candidates, or a row that does not fit the K/V arena with the full step budget)"""
+        (prompt-free, the naive loop, "best_of" candidates, or a row that does not fit the K/V arena with the full step budget).
+        mixed_limits: all of those bring rows too, with "limits", "no_prompt" and, for candidates, "cand" as plan_batch gives
+        them, in (bi, j, candidate) order; None only if a row has no room at all."""
+        if self._mixed_limits:
+            rows = [e for launch in self.tts.plan_batch([pl], mixed_sampling=True, mixed_limits=True) for e in launch]
+            if any(e["limits"][2] < 1 for e in rows):
+                return None
+            return sorted(rows, key=lambda e: (e["bi"], e["j"], e.get("cand", 0)))
         if pl["no_prompt"] or not pl["opts"]["parallel_infer"] or "best_of" in pl["opts"]:
             return None
         rows = [e for launch in self.tts.plan_batch([pl], mixed_sampling=True) for e in launch]
@@ -740,13 +758,17 @@ class Scheduler:
             pl, e = self._requests[t], self._rows[t][row]
             item = pl["data"][e["bi"]]
             rows.append(dict(x=item["all_phones"][e["j"]], bert=item["all_bert_features"][e["j"]],
-                             prompt=pl["voice"]["prompt_semantic"].view(-1), key=e["key"], sampling=e["sampling"]))
+                             prompt=None if e.get("no_prompt") else pl["voice"]["prompt_semantic"].view(-1), key=e["key"],
+                             sampling=e["sampling"]))
+            if self._mixed_limits:
+                rows[-1]["limits"] = e["limits"]
             if self.stats["tickets"][t][1] is None:
                 self.stats["tickets"][t][1] = self._step
         if self._ses is None:
             k, p, temp, rp = rows[0]["sampling"]        # placeholders: every row brings its own tuple
             self._ses = self.tts.t2s_model.open_session(self._pol.slots, k, p, temp, rp, early_stop_num(self.tts.configs), 1,
-                                                        self._budget(), row_sampling=True)
+                                                        self._budget(), row_sampling=True,
+                                                        **(dict(row_limits=True, logprobs=True) if self._mixed_limits else {}))
             self._count(sessions=1)
         tickets = self._ses.admit(rows, slots=[s for _, _, s in admitted])
         for st, (t, row, _) in zip(tickets, admitted):
@@ -760,8 +782,19 @@ class Scheduler:
             t, row = self._where.pop(st)
             e = self._rows[t][row]
             pl = self._requests[t]
-            pl["preds"][e["bi"]][e["j"]], pl["idxs"][e["bi"]][e["j"]] = y, n
             done.append((t, row))
+            if "cand" in e:                                             # a sentence is back when all its candidates are
+                from .TTS_infer_pack.TTS import choose_candidate
+                c = dict(tokens=y[-n:] if n > 0 else y[:0], logprobs=self._ses.logprobs[st].cpu().numpy(), n=n, cut=self._ses.cut[st])
+                by_c = self._cands.setdefault((t, e["bi"], e["j"]), {})
+                by_c[e["cand"]] = (c, y)
+                if len(by_c) < pl["opts"]["best_of"]:
+                    continue
+                del self._cands[(t, e["bi"], e["j"])]
+                k, rec = choose_candidate(pl["opts"], [by_c[c_][0] for c_ in sorted(by_c)])
+                y, n = by_c[k][1], by_c[k][0]["n"]
+                pl.setdefault("candidates", [[None] * len(item["all_phones"]) for item in pl["data"]])[e["bi"]][e["j"]] = rec
+            pl["preds"][e["bi"]][e["j"]], pl["idxs"][e["bi"]][e["j"]] = y, (0 if e.get("no_prompt") else n)
         self._count(advances=1)
         return done
 

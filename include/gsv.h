@@ -89,7 +89,11 @@ int gsv_t2s_prefill(gsv_t2s_t* h, const int32_t* phones, const int32_t* phone_le
  * int32, row b's P_b = prompt_lens[b] [host] tokens back to back in row order; every P_b >= 1 (prompt-free rows keep
  * gsv_t2s_prefill with P = 0).  Row b needs phone_lens[b] + P_b + 2 <= max_seq; its generated tokens sit at audio
  * positions P_b, P_b + 1, ... and its repetition history is its own prompt plus what it generated.  With every P_b equal
- * this computes exactly what gsv_t2s_prefill computes. */
+ * this computes exactly what gsv_t2s_prefill computes.
+ * After gsv_t2s_set_row_limits (pending for the decode that follows; B must match) a row may be prompt-free, P_b == 0: it has
+ * no entry in prompts_packed, its audio sequence starts empty at position 0 and its EOS horizon is its limits' (the
+ * reference's prompt-free loop uses 11); prompts_packed may be NULL when every row is prompt-free.  The same holds for
+ * gsv_t2s_session_admit.  Without pending limits P_b == 0 is refused as before. */
 int gsv_t2s_prefill_ragged(gsv_t2s_t* h, const int32_t* phones, const int32_t* phone_lens, int B, const float* bert,
                            const int32_t* prompts_packed, const int32_t* prompt_lens, gsv_stream_t stream);
 /* Counter-RNG keys for the NEXT gsv_t2s_decode call only (like gsv_t2s_set_debug): row b draws with the key
@@ -110,6 +114,28 @@ typedef struct {
  * else still comes from the call's gsv_sampling_params.  B must equal the batch of that call.  A value outside the ranges
  * above is refused here with GSV_ERR_ARG and nothing is kept.  Without this call every row uses the scalars. */
 int gsv_t2s_set_row_sampling(gsv_t2s_t* h, const gsv_row_sampling_t* rows, int B);
+
+/* Step limits of one batch row: the three limit fields of gsv_sampling_params. */
+typedef struct {
+  int eos_mask_steps;       /* >= 0: EOS column dropped while the row's step < this */
+  int early_stop_num;       /* -1: none; else >= 0, the row stops once it generated > early_stop_num */
+  int max_steps;            /* >= 1 and <= the max_steps of the call / session: the row ends at step max_steps - 1 at the latest */
+  int reserved;             /* 0 */
+} gsv_row_limits_t;
+
+/* Per-row limits for the NEXT gsv_t2s_decode call or the NEXT gsv_t2s_session_admit only (like gsv_t2s_set_row_rng and
+ * gsv_t2s_set_row_sampling): row b masks EOS, stops early and ends by rows[b] [host] instead of the call's (session's)
+ * eos_mask_steps / early_stop_num / max_steps.  The call's max_steps stays the row pitch of out_tokens, of the
+ * log-probabilities and of the debug hooks, and a row that reaches its own budget ends like a row that reaches the scalar one:
+ * out_len[b] and its last log-probability are written.  The arena, position-table and history checks are made per row with
+ * budget_b = min(max_steps_b, early_stop_num_b + 1): phone_lens[b] + P_b + 2 + budget_b <= max_seq.
+ * Call it BEFORE the prefill of that decode: a gsv_t2s_prefill_ragged (or an admission) that follows it accepts prompt-free
+ * rows (see there).  GSV_ERR_ARG with nothing kept: eos_mask_steps < 0, early_stop_num < -1, max_steps < 1, reserved != 0,
+ * B outside 1 .. max_batch; the consuming call refuses, before any launch and dropping the limits, a B different from its
+ * rows and a max_steps above its own.  A session keeps a slot's limits with the slot's row state until the row is finished or
+ * released; a row admitted without limits runs by the session's scalars.  Without this call nothing changes: the kernels that
+ * read per-row limits are separate instantiations and are launched only for such a decode. */
+int gsv_t2s_set_row_limits(gsv_t2s_t* h, const gsv_row_limits_t* rows, int B);
 
 /* Decode loop (H4+H5).  noise [dev] fp32 Exp(1) draws [max_steps][noise_rows][vocab] or NULL
  * (noise_rows is 1 = shared by all rows, or B).  out_tokens [dev] int32 [B][max_steps]: generated

@@ -34,7 +34,12 @@ the p50s -- and the same pairs with no streaming request at all (the two must no
 calls (device time between events, and wall time through the pipeline's methods with the copy to the host) next to the byte
 floor (each sample read twice, written once).
 
+--mixed-limits: instead of the sweep, the same replay with --odd-share of the requests drawn from the four kinds that are
+exclusive without Scheduler(mixed_limits=True) (prompt-free, parallel_infer=False, best_of=2, arena-short), served with the
+keyword and without it in alternating pairs: submit-to-result p50 / p95 of the odd and of the plain requests, audio-s/s.
+
     python tools/serving_bench.py --streaming [--stream-share 0.25] [--loads 0.3,0.6,0.9] [--postprocess]
+    python tools/serving_bench.py --mixed-limits [--odd-share 0.1] [--loads 0.3,0.6,0.9]
 """
 import argparse
 import json
@@ -97,6 +102,9 @@ def main():
     ap.add_argument("--handoff", action="store_true", help="v3 / v4: time fetch_mel against the per-slot hand-off first")
     ap.add_argument("--streaming", action="store_true", help="streaming requests in the sessions against the exclusive path")
     ap.add_argument("--stream-share", type=float, default=0.25)
+    ap.add_argument("--mixed-limits", action="store_true",
+                    help="a share of prompt-free / naive / best_of / arena-short requests: Scheduler(mixed_limits=True) against without")
+    ap.add_argument("--odd-share", type=float, default=0.1)
     ap.add_argument("--postprocess", action="store_true", help="time gsv_postprocess_groups against per-fragment gsv_postprocess first")
     a = ap.parse_args()
     from bench import build_tts, make_segments
@@ -229,6 +237,13 @@ def main():
                        cfm_euler_steps=st["cfm_steps"], cfm_admissions=st["cfm_admissions"], vocoder_calls=st["vocoder_calls"])
         return out
 
+    if a.mixed_limits:
+        kw = dict(chunk=int(a.chunks.split(",")[0]), admit_min=int(a.admit_mins.split(",")[0]), wave_hold=int(a.wave_holds.split(",")[0]))
+        vfree = tts.make_voice(torch.from_numpy(S.hash_ints("sv_sem_free", 60, 1024, 1)),
+                               [S.make_refer_spec(frames=150, seed=99).to(dev).half()])
+        mixed_limits_pairs(a, tts, reqs, audio_s, trace, kw, vfree)
+        print(json.dumps(dict(record="engine", fallbacks=tts.t2s_model.engine_stats()[1])), flush=True)
+        return
     if a.streaming:
         kw = dict(chunk=int(a.chunks.split(",")[0]), admit_min=int(a.admit_mins.split(",")[0]), wave_hold=int(a.wave_holds.split(",")[0]))
         if v3:
@@ -251,6 +266,76 @@ def main():
             med = {k: statistics.median(r[k] for r in runs) for k in runs[0]}
             print(json.dumps(dict(record="serve", server=kind, setting=name, load=load, repeats=a.repeats, **med)), flush=True)
     print(json.dumps(dict(record="engine", fallbacks=tts.t2s_model.engine_stats()[1])), flush=True)
+
+
+def mixed_limits_pairs(a, tts, reqs, audio_s, trace, kw, vfree):
+    """--mixed-limits: the Poisson replay with --odd-share of the requests drawn from the four kinds that are exclusive without
+    Scheduler(mixed_limits=True) -- prompt-free, parallel_infer=False, best_of=2, a sentence short of arena room -- served by
+    that scheduler and by the same class without the keyword: same process, alternating pairs, medians of --repeats, per load.
+    Reported separately for the odd and the plain requests of the mix: submit-to-result p50 / p95; and audio-s/s of the run
+    (the audio seconds are those of each server's own results: an odd request's length is not the closed batch's)."""
+    from gsv.serving import Scheduler, Server
+    N = len(reqs)
+    r_ = random.Random(99 + a.seed)
+    odd = {i: n % 4 for n, i in enumerate(i for i in range(N) if r_.random() < a.odd_share)}   # the four kinds dealt in turn
+    from gsv.TTS_infer_pack.TTS import early_stop_num
+    budget = min(1500, int(early_stop_num(tts.configs)) + 1)
+    rq = []
+    for i, r in enumerate(reqs):
+        kind = odd.get(i)
+        if kind == 0:
+            r = dict(r, voice=vfree)
+        elif kind == 1:
+            r = dict(r, parallel_infer=False)
+        elif kind == 2:
+            r = dict(r, best_of=2)
+        elif kind == 3:          # several sentences' phones in one, until text + prompt leave the arena less than the full budget
+            fixed = len(r["voice"]["phones"]) + int(r["voice"]["prompt_semantic"].numel()) + 2
+            parts, k = [r["segments"][0]], 1
+            room = lambda ps: tts.t2s_model.max_seq - fixed - sum(len(p_["phones"]) for p_ in ps)
+            while room(parts) >= budget:
+                parts.append(reqs[(i + k) % N]["segments"][0])
+                k += 1
+            if room(parts) < 1:
+                raise SystemExit(f"request {i}: {room(parts)} steps of room: no arena-short sentence can be built from these segments")
+            long = dict(parts[0], phones=[x for p_ in parts for x in p_["phones"]], norm_text="".join(p_["norm_text"] for p_ in parts),
+                        bert_features=torch.cat([p_["bert_features"] for p_ in parts], 1))
+            r = dict(r, segments=[long] + list(r["segments"][1:]))
+        rq.append(r)
+
+    def serve(arrivals, mixed):
+        done_at, futs, secs = [0.0] * N, [None] * N, [0.0] * N
+        server = Server(Scheduler(tts, slots=a.slots, **kw, **(dict(mixed_limits=True) if mixed else {})))
+
+        def submit(i):
+            futs[i] = server.submit(rq[i])
+            futs[i].add_done_callback(lambda f, i=i: done_at.__setitem__(i, time.perf_counter()))
+        t0 = _replay(arrivals, submit)
+        for i, f in enumerate(futs):
+            sr, w = f.result()
+            secs[i] = w.shape[0] / sr
+        server.shutdown()
+        st = server.scheduler.stats
+        lat = lambda ids: [done_at[i] - (t0 + arrivals[i]) for i in ids]
+        plain = [i for i in range(N) if i not in odd]
+        ms = lambda xs, q: round(1e3 * _pct(xs, q), 1) if xs else None
+        return dict(odd_p50_ms=ms(lat(sorted(odd)), 0.5), odd_p95_ms=ms(lat(sorted(odd)), 0.95),
+                    plain_p50_ms=ms(lat(plain), 0.5), plain_p95_ms=ms(lat(plain), 0.95),
+                    audio_s_per_s=round(sum(secs) / (max(done_at) - t0), 1), sessions=st["sessions"], exclusive=st["exclusive"])
+
+    servers = (("mixed_limits", True), ("exclusive", False))
+    for load in [float(x) for x in a.loads.split(",") if x]:
+        runs = {name: [] for name, _ in servers}
+        for rep_ in range(a.repeats):
+            for name, mixed in (servers if rep_ % 2 == 0 else servers[::-1]):
+                runs[name].append(serve(trace(load, rep_), mixed))
+        for name, _ in servers:
+            med = {k: (statistics.median(r[k] for r in runs[name]) if runs[name][0][k] is not None else None) for k in runs[name][0]}
+            spread = {k: [min(r[k] for r in runs[name]), max(r[k] for r in runs[name])]
+                      for k in ("odd_p50_ms", "plain_p50_ms", "audio_s_per_s") if runs[name][0][k] is not None}
+            print(json.dumps(dict(record="mixed_limits", server=name, load=load, odd_share=a.odd_share, odd=len(odd),
+                                  kinds=[sum(k == j for k in odd.values()) for j in range(4)], requests=N, pairs=a.repeats,
+                                  setting=kw, **med, spread=spread)), flush=True)
 
 
 def streaming_pairs(a, tts, reqs, audio_s, trace, kw):

@@ -974,6 +974,12 @@ int check_row_sampling(const char* who, const gsv_row_sampling_t* rows, int B) {
   return GSV_OK;
 }
 
+int check_rng_rows(const char* who, const int32_t* rows, int B) {
+  for (int b = 0; b < B; ++b)
+    GSV_REQUIRE(rows[b] >= 0 && rows[b] < (1 << 24), "%s: row %d: RNG row %d must be in [0, 2^24)", who, b, rows[b]);
+  return GSV_OK;
+}
+
 extern "C" {
 
 int gsv_t2s_create(const gsv_t2s_config* cfg, int dtype, int max_batch, int max_seq, gsv_t2s_t** out) {
@@ -1119,6 +1125,7 @@ int gsv_t2s_finalize(gsv_t2s_t* h) {
 int gsv_t2s_set_row_rng(gsv_t2s_t* h, const uint64_t* seeds, const int32_t* rows, int B) {
   GSV_REQUIRE(h && h->finalized, "t2s_set_row_rng: handle not finalized");
   GSV_REQUIRE(seeds && rows && B >= 1 && B <= h->max_batch, "t2s_set_row_rng: bad argument (B = %d)", B);
+  GSV_RC(check_rng_rows("t2s_set_row_rng", rows, B));
   h->rng_seed_next.assign(seeds, seeds + B);
   h->rng_row_next.assign(rows, rows + B);
   return GSV_OK;

@@ -181,6 +181,9 @@ int t2s_step0_tail(gsv_t2s* h, RowState& r, hipStream_t s);
 int run_chunk(gsv_t2s* h, int budget, int32_t* out_len, int* steps_run, hipStream_t s);
 // the value checks of gsv_t2s_set_row_sampling, gsv_t2s_session_admit and gsv_op_sample_rows
 int check_row_sampling(const char* who, const gsv_row_sampling_t* rows, int B);
+// the RNG rows of gsv_t2s_set_row_rng and gsv_t2s_session_admit: the key holds 24 bits of the row (row << 40), so a row
+// outside [0, 2^24) would draw the stream of another row ("The counter RNG as a contract")
+int check_rng_rows(const char* who, const int32_t* rows, int B);
 // the limits of a call with the scalars of sp: what a row without limits of its own gets in a decode that has them
 inline gsv_row_limits_t limits_of(const gsv_sampling_params& sp) { return {sp.eos_mask_steps, sp.early_stop_num, sp.max_steps, 0}; }
 // gsv_t2s_set_row_limits' rows against the max_steps of the call / session that consumes them

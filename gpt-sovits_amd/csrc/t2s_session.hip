@@ -358,6 +358,7 @@ int gsv_t2s_session_admit(gsv_t2s_t* h, int n, const int32_t* slot_ids, const in
   GSV_REQUIRE(!z.row_sampling || row_sampling, "t2s_session_admit: the session samples per row, row_sampling is null");
   GSV_REQUIRE(z.row_sampling || !row_sampling, "t2s_session_admit: row_sampling given, but the session was opened without it");
   if (row_sampling) GSV_RC(check_row_sampling("t2s_session_admit", row_sampling, n));
+  GSV_RC(check_rng_rows("t2s_session_admit", rng_rows, n));
   // everything that can refuse the admission is checked here, before the first launch: a refused admission changes nothing
   std::vector<char> taken(z.slots, 0);
   for (int i = 0; i < n; ++i) {

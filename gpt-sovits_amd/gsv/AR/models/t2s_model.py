@@ -390,7 +390,7 @@ class Text2SemanticDecoder:
              row_limits=None):
         """prompts: [B, P] (one prompt length for the batch; P = 0 or None: prompt-free) or a list of B 1-D prompts of
         lengths P_b >= 1 (ragged: gsv_t2s_prefill_ragged).  rng_keys: optional [(seed_b, row_b)] per row, the counter-RNG
-        key that replaces (seed, b) (gsv_t2s_set_row_rng).  row_sampling: optional [(top_k, top_p, temperature,
+        key that replaces (seed, b) (gsv_t2s_set_row_rng; row_b in [0, 2**24), anything else is refused).  row_sampling: optional [(top_k, top_p, temperature,
         repetition_penalty)] per row, which replace the four scalar arguments for this call (gsv_t2s_set_row_sampling).
         logprobs=True leaves last_logprobs: B 1-D fp32 tensors, row b's idx[b] + 1 log-probabilities of the tokens it took
         under the model's own distribution (gsv_t2s_set_logprobs): the generated tokens, then the finishing step; and

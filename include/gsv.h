@@ -98,7 +98,9 @@ int gsv_t2s_prefill_ragged(gsv_t2s_t* h, const int32_t* phones, const int32_t* p
                            const int32_t* prompts_packed, const int32_t* prompt_lens, gsv_stream_t stream);
 /* Counter-RNG keys for the NEXT gsv_t2s_decode call only (like gsv_t2s_set_debug): row b draws with the key
  * (seeds[b], rows[b]) [host] instead of (sp->seed, b), so a row draws the same tokens wherever it sits in a batch.
- * B must equal the batch of that call.  Without it the keys are (sp->seed, b). */
+ * B must equal the batch of that call.  Without it the keys are (sp->seed, b).  The key holds 24 bits of the row (DESIGN.md
+ * section 4d, "The counter RNG as a contract"): a row outside [0, 2^24) is refused with GSV_ERR_ARG and nothing is kept, here and
+ * in gsv_t2s_session_admit. */
 int gsv_t2s_set_row_rng(gsv_t2s_t* h, const uint64_t* seeds, const int32_t* rows, int B);
 
 /* Sampling parameters of one batch row: the four per-request fields of gsv_sampling_params. */
@@ -159,7 +161,7 @@ int gsv_t2s_decode(gsv_t2s_t* h, const gsv_sampling_params* sp, const float* noi
  * admit: prefills n rows (arguments as gsv_t2s_prefill_ragged, row i's key = (rng_seeds[i], rng_rows[i]) [host], its sampling
  *   tuple row_sampling[i] [host] if the session has per-row sampling, else NULL) and runs their step 0, then puts row i into
  *   slot_ids[i] [host].  No other slot is touched.  GSV_ERR_ARG before any launch: a slot that is live or out of range, a
- *   repeated slot, a row with phone_lens + P_b + 2 + budget > max_seq, or P_b + budget beyond the position table or the token
+ *   repeated slot, an RNG row outside [0, 2^24), a row with phone_lens + P_b + 2 + budget > max_seq, or P_b + budget beyond the position table or the token
  *   history (budget = min(max_steps, early_stop_num + 1)).
  * advance: at most n_steps further steps for every live slot; live_out / steps_out [host] int[slots] receive which slots are
  *   still live and every slot's step counter (either may be NULL).  fp16 on the v1/v2 shape with slots <= 128 runs the chunk as

@@ -408,9 +408,9 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const T* __restrict__ 
 }
 
 // step tail: sample every row, update row state, emit the next step's input embedding
-// (t2s_model.py:714-769).  grid = B, block = 64.  LIMITS: row b's EOS horizon, early stop and budget come from
-// sp.row_limits[b] (gsv_t2s_set_row_limits) -- a kernel of its own, so that the default one keeps its registers.
-template <int NPL, bool LIMITS>
+// (t2s_model.py:714-769).  grid = B, block = 64.  Row b's sampling values, EOS horizon, early stop and budget come from
+// sp.row_sampling[b] / sp.row_limits[b], which decode_begin and the sessions' admissions fill for every row.
+template <int NPL>
 __global__ __launch_bounds__(64) void sample_step_kernel(const float* __restrict__ logits, int V, int EOS,
                                                          const StepParams* __restrict__ spp, int* __restrict__ ytok,
                                                          int ycap, int* __restrict__ kv_len, int* __restrict__ active,
@@ -422,7 +422,7 @@ __global__ __launch_bounds__(64) void sample_step_kernel(const float* __restrict
   const StepParams sp = *spp;
   const int step = step_ctr[b];
   if (!active[b]) return;
-  const RowLimits rl = row_limits_of<LIMITS>(sp, b);
+  const RowLimits rl = load_row_limits(sp.row_limits, b);
   const int Veff = (step < rl.eos_mask_steps) ? V - 1 : V;
   const int P = sp.plen[b];
   const int prev_len = P + step;
@@ -431,7 +431,7 @@ __global__ __launch_bounds__(64) void sample_step_kernel(const float* __restrict
   if (sp.noise)
     nrow = sp.noise + ((long long)step * sp.noise_rows + (sp.noise_rows > 1 ? b : 0)) * V;
   int smp, amx;
-  const RowSampling rs = row_sampling_of(sp, b);
+  const RowSampling rs = load_row_sampling(sp.row_sampling, b);
   sample_row<NPL>(logits + (long long)b * V, V, Veff, yrow, prev_len, rs.top_k, rs.top_p, rs.temperature,
                   rs.rep_penalty, nrow, sp.rng_seed[b], sp.rng_row[b], step, seen, &smp, &amx);
   if (sp.dump)
@@ -638,9 +638,7 @@ int launch_tail(gsv_t2s* h, RowState& r, hipStream_t s) {
   GSV_RC(launch_dec_gemm<T>(a, true, s));
   const int V = c.vocab, EOS = c.vocab - 1;
   return with_npl(V, [&](auto npl) -> int {
-    constexpr int NPL = decltype(npl)::value;
-    auto kern = h->limits_on ? sample_step_kernel<NPL, true> : sample_step_kernel<NPL, false>;
-    GSV_LAUNCH(kern, dim3(r.B), dim3(64), (size_t)((V + 15) & ~15), s, r.logits, V, EOS, r.sp,
+    GSV_LAUNCH(sample_step_kernel<decltype(npl)::value>, dim3(r.B), dim3(64), (size_t)((V + 15) & ~15), s, r.logits, V, EOS, r.sp,
                r.ytok, h->ycap, r.kv_len(), r.active(), r.step(), r.n_active(), h->e_audio, h->pe, h->alpha_a, c.dim, r.ybuf);
     return GSV_OK;
   });
@@ -655,75 +653,65 @@ int launch_step(gsv_t2s* h, hipStream_t s) {
 // ---- gsv_t2s_decode in the order it runs: decode_begin, step 0 (launch_tail), then run_chunk: run_mega and / or run_steps, all
 // ---- three on h->rows ----
 
-// Uploads the call's sampling parameters and the rows' counter-RNG keys and checks that the request fits the arena, the
-// position table and the token history.  Returns the step budget (>= 1) or an error code (< 0).
+// rows -> the device array dst, unless `up`, the host copy of what dst holds, says that they are there already
+template <typename R>
+int upload_rows(const std::vector<R>& rows, std::vector<R>& up, void* dst, hipStream_t s) {
+  if (rows.size() == up.size() && memcmp(rows.data(), up.data(), rows.size() * sizeof(R)) == 0) return GSV_OK;
+  GSV_HIP(hipMemcpyAsync(dst, rows.data(), rows.size() * sizeof(R), hipMemcpyHostToDevice, s));
+  up = rows;
+  return GSV_OK;
+}
+
+// Builds and uploads the call's row tables -- every row's sampling values, limits and counter-RNG key -- and checks that the
+// request fits the arena, the position table and the token history.  Returns the step budget (>= 1) or an error code (< 0).
 int decode_begin(gsv_t2s* h, const gsv_sampling_params* sp, const float* noise, int noise_rows, int32_t* out_tokens,
                  int32_t* out_len, hipStream_t s) {
   const RowState& r = h->rows;
-  // per-row sampling parameters: gsv_t2s_set_row_sampling's for this call (the call's four scalars are then unused), else
-  // null.  row_sampling_next stays until gsv_t2s_decode returns: a fallback re-run of the batch reads the same device array.
-  const std::vector<gsv_row_sampling_t>& rsn = h->row_sampling_next;
-  const std::vector<gsv_row_limits_t>& rln = h->row_limits_next;   // gsv_t2s_set_row_limits' for this call
-  const bool limits = !rln.empty();
-  StepParams p = step_params(*sp, r, take_outputs(h, out_tokens, out_len), !rsn.empty(), limits);
+  const size_t B = (size_t)r.B;
+  StepParams p = step_params(sp->max_steps, r, take_outputs(h, out_tokens, out_len));
   p.noise = noise; p.noise_rows = noise ? noise_rows : 0;
-  // counter-RNG keys of the rows: gsv_t2s_set_row_rng's for this call, else (seed, b) -- the draws of a batch without keys
+  // The tables: what gsv_t2s_set_row_rng / _row_sampling / _row_limits gave for this call, else the call's scalars for every
+  // row ((seed, b) for the keys: the draws of a batch without keys).  The setters' vectors stay until gsv_t2s_decode returns.
+  const std::vector<gsv_row_sampling_t>& rsn = h->row_sampling_next;
+  const std::vector<gsv_row_limits_t>& rln = h->row_limits_next;
   const bool keyed = !h->rng_seed_next.empty();
   const int nkeys = (int)h->rng_seed_next.size();
-  std::vector<unsigned long long> seeds(r.B);
-  std::vector<int> rows(r.B);
-  for (int b = 0; b < r.B && (!keyed || nkeys == r.B); ++b) {
-    seeds[b] = keyed ? h->rng_seed_next[b] : (unsigned long long)sp->seed;
-    rows[b] = keyed ? h->rng_row_next[b] : b;
-  }
+  std::vector<unsigned long long> seeds(B, (unsigned long long)sp->seed);
+  std::vector<int> rows(B);
+  for (size_t b = 0; b < B; ++b) rows[b] = (int)b;
+  if (keyed && nkeys == r.B) { seeds = h->rng_seed_next; rows = h->rng_row_next; }
   h->rng_seed_next.clear(); h->rng_row_next.clear();
   GSV_REQUIRE(!keyed || nkeys == r.B, "t2s_decode: gsv_t2s_set_row_rng gave %d keys for a batch of %d rows", nkeys, r.B);
-  GSV_REQUIRE(rsn.empty() || (int)rsn.size() == r.B, "t2s_decode: gsv_t2s_set_row_sampling gave %d rows for a batch of %d rows",
+  GSV_REQUIRE(rsn.empty() || rsn.size() == B, "t2s_decode: gsv_t2s_set_row_sampling gave %d rows for a batch of %d rows",
               (int)rsn.size(), r.B);
-  // Per-row limits are checked against the call before anything is uploaded or launched; every row is held to its own budget
-  // (row b ends at kv0[b] + budget_b - 1 cached positions) and the launch runs the largest.
-  int budget = step_budget(*sp);
-  if (limits) {
-    GSV_REQUIRE((int)rln.size() == r.B, "t2s_decode: gsv_t2s_set_row_limits gave %d rows for a batch of %d rows", (int)rln.size(),
-                r.B);
-    GSV_RC(check_row_limits_steps("t2s_decode", rln, sp->max_steps));
-    budget = 1;
-    for (int b = 0; b < r.B; ++b) {
-      const int bb = step_budget(rln[b]);
-      budget = bb > budget ? bb : budget;
-      GSV_REQUIRE(r.kv0[b] + bb <= r.max_seq,
-                  "t2s_decode: row %d: %d cached positions + %d steps exceed the K/V arena (max_seq %d); lower the row's max_steps / "
-                  "early_stop_num or create the engine with a larger max_seq", b, r.kv0[b], bb, r.max_seq);
-      GSV_REQUIRE(r.pl[b] + bb <= h->pe_rows, "t2s_decode: row %d: prompt %d + %d steps exceed the position table (%d rows)", b,
-                  r.pl[b], bb, h->pe_rows);
-      GSV_REQUIRE(r.pl[b] + bb <= h->ycap, "t2s_decode: row %d: prompt %d + %d steps exceed the token history (%d)", b, r.pl[b], bb,
-                  h->ycap);
-    }
-    GSV_HIP(hipMemcpyAsync(r.row_limits, rln.data(), rln.size() * sizeof(gsv_row_limits_t), hipMemcpyHostToDevice, s));
+  GSV_REQUIRE(rln.empty() || rln.size() == B, "t2s_decode: gsv_t2s_set_row_limits gave %d rows for a batch of %d rows",
+              (int)rln.size(), r.B);
+  GSV_RC(check_row_limits_steps("t2s_decode", rln, sp->max_steps));
+  const std::vector<gsv_row_sampling_t> sampling = rsn.empty() ? std::vector<gsv_row_sampling_t>(B, sampling_of(*sp)) : rsn;
+  const std::vector<gsv_row_limits_t> limits = rln.empty() ? std::vector<gsv_row_limits_t>(B, limits_of(*sp)) : rln;
+  // Every row is held to its own budget before anything is uploaded or launched: row b ends at kv0[b] + budget_b - 1 cached
+  // positions, and its sampling tail reads pe[P_b + step] and writes token history [P_b + step].  A request that does not fit
+  // is refused here: the kernels clamp out-of-range appends, which would otherwise yield silently wrong tokens with rc 0.
+  // The launch runs the largest budget.
+  int budget = 1;
+  for (int b = 0; b < r.B; ++b) {
+    const int bb = step_budget(limits[b]);
+    budget = bb > budget ? bb : budget;
+    GSV_REQUIRE(r.kv0[b] + bb <= r.max_seq,
+                "t2s_decode: row %d: %d cached positions + %d steps exceed the K/V arena (max_seq %d); lower max_steps / "
+                "early_stop_num (the row's own, if it has limits) or create the engine with a larger max_seq", b, r.kv0[b], bb,
+                r.max_seq);
+    GSV_REQUIRE(r.pl[b] + bb <= h->pe_rows, "t2s_decode: row %d: prompt %d + %d steps exceed the position table (%d rows)", b,
+                r.pl[b], bb, h->pe_rows);
+    GSV_REQUIRE(r.pl[b] + bb <= h->ycap, "t2s_decode: row %d: prompt %d + %d steps exceed the token history (%d)", b, r.pl[b], bb,
+                h->ycap);
   }
-  if (!rsn.empty() && (rsn.size() != h->row_sampling_up.size() ||
-                       memcmp(rsn.data(), h->row_sampling_up.data(), rsn.size() * sizeof(gsv_row_sampling_t)) != 0)) {
-    GSV_HIP(hipMemcpyAsync(r.row_sampling, rsn.data(), rsn.size() * sizeof(gsv_row_sampling_t), hipMemcpyHostToDevice, s));
-    h->row_sampling_up = rsn;
-  }
+  GSV_RC(upload_rows(sampling, h->row_sampling_up, r.row_sampling, s));
+  GSV_RC(upload_rows(limits, h->row_limits_up, r.row_limits, s));
+  GSV_RC(upload_rows(seeds, h->rng_seed_up, r.rng_seed, s));
+  GSV_RC(upload_rows(rows, h->rng_row_up, r.rng_row, s));
   GSV_HIP(hipMemcpyAsync(r.sp, &p, sizeof(p), hipMemcpyHostToDevice, s));
-  h->limits_on = limits;   // with the StepParams it describes
-  if (seeds != h->rng_seed_up || rows != h->rng_row_up) {
-    GSV_HIP(hipMemcpyAsync(r.rng_seed, seeds.data(), (size_t)r.B * 8, hipMemcpyHostToDevice, s));
-    GSV_HIP(hipMemcpyAsync(r.rng_row, rows.data(), (size_t)r.B * 4, hipMemcpyHostToDevice, s));
-    h->rng_seed_up = seeds; h->rng_row_up = rows;
-  }
   GSV_HIP(hipStreamSynchronize(s));
-  if (limits) return budget;
-  // the longest row ends at max_kv0 + budget - 1 cached positions; the sampling tail of row b reads pe[P_b + step] and writes
-  // token history [P_b + step] (r.P is the longest prompt).  A request that does not fit is refused here: the kernels clamp
-  // out-of-range appends, which would otherwise yield silently wrong tokens with rc 0.
-  GSV_REQUIRE(r.max_kv0 + budget <= r.max_seq,
-              "t2s_decode: %d cached positions + %d steps exceed the K/V arena (max_seq %d); lower max_steps / early_stop_num "
-              "or create the engine with a larger max_seq", r.max_kv0, budget, r.max_seq);
-  GSV_REQUIRE(r.P + budget <= h->pe_rows, "t2s_decode: prompt %d + %d steps exceed the position table (%d rows)", r.P, budget,
-              h->pe_rows);
-  GSV_REQUIRE(r.P + budget <= h->ycap, "t2s_decode: prompt %d + %d steps exceed the token history (%d)", r.P, budget, h->ycap);
   return budget;
 }
 
@@ -820,7 +808,7 @@ int run_mega(gsv_t2s* h, int budget, int32_t* out_len, hipStream_t s) {
   MegaArgs a = mega_args(h, budget);
   GSV_RC(mega_prof_arm(a, budget, s));
   GSV_HIP(hipEventRecord(h->mega_ev[0], s));
-  GSV_RC(launch_t2s_mega(a, h->logp_on, h->limits_on, s));
+  GSV_RC(launch_t2s_mega(a, h->logp_on, s));
   GSV_HIP(hipEventRecord(h->mega_ev[1], s));
   GSV_HIP(hipMemcpyAsync(m.h_err, m.err, 16, hipMemcpyDeviceToHost, s));
   GSV_HIP(hipMemcpyAsync(h->h_pinned, r.step(), 4, hipMemcpyDeviceToHost, s));
@@ -856,8 +844,7 @@ template <typename T>
 int run_steps(gsv_t2s* h, int budget, int* steps_run, hipStream_t s) {
   const int B = h->rows.B;
   hipGraphExec_t exec = nullptr;
-  const int gkey = B + (h->limits_on ? 1 << 16 : 0);   // the step with the LIMITS sampler is a graph of its own
-  auto it = h->graphs.find(gkey);
+  auto it = h->graphs.find(B);
   if (it != h->graphs.end()) exec = it->second;
   else if (s != nullptr && !getenv("GSV_T2S_NO_GRAPH") && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
     hipGraph_t graph;
@@ -867,7 +854,7 @@ int run_steps(gsv_t2s* h, int budget, int* steps_run, hipStream_t s) {
     GSV_HIP(e);
     GSV_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
     (void)hipGraphDestroy(graph);
-    h->graphs[gkey] = exec;
+    h->graphs[B] = exec;
   } else {
     (void)hipGetLastError();  // legacy default stream cannot capture: eager launches instead
   }
@@ -1267,7 +1254,7 @@ int gsv_t2s_debug_set_state(gsv_t2s_t* h, int B, int kv_len) {
   GSV_HIP(hipMemcpy(r.active(), zero.data(), B * 4, hipMemcpyHostToDevice));
   GSV_HIP(hipMemset(r.ybuf, 0, (size_t)B * h->cfg.dim * 4));
   GSV_HIP(hipMemset(r.kv, 0, (size_t)h->cfg.n_layer * 2 * r.kv_layer_stride * esz(h)));
-  r.B = B;
+  r.B = B; r.kv0.assign(B, kv_len); r.pl.assign(B, r.P);
   return GSV_OK;
 }
 

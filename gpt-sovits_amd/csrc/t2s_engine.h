@@ -37,14 +37,13 @@ struct RowState {
   int* ytok = nullptr;      // [mb][ycap] token history
   int* plen = nullptr;      // [2][mb]: prompt length P_b | offset of row b's prompt in the packed prompt buffer
   unsigned long long* rng_seed = nullptr; int* rng_row = nullptr;   // [mb] counter-RNG keys of the rows
-  gsv::RowSampling* row_sampling = nullptr;        // [mb] per-row sampling parameters
-  gsv::RowLimits* row_limits = nullptr;            // [mb] per-row step limits (gsv_t2s_set_row_limits)
+  gsv::RowSampling* row_sampling = nullptr;        // [mb] every row's sampling values and step limits: its own, or the call's /
+  gsv::RowLimits* row_limits = nullptr;            // session's scalars (decode_begin, session_begin / session_admit fill them)
   gsv::StepParams* sp = nullptr;                   // the device StepParams of these rows
   float *ybuf = nullptr, *logits = nullptr;        // [mb][dim] next step's input embedding, [mb][vocab]
   // host view of the current batch
   int B = 0, P = 0;         // P: the longest row's prompt (uniform prefill: every row's)
-  int max_kv0 = 0;          // longest row's cached positions after prefill (host copy: bounds the decode budget)
-  std::vector<int> kv0, pl; // every row's cached positions and prompt length after prefill: bound a decode with per-row limits
+  std::vector<int> kv0, pl; // every row's cached positions and prompt length after prefill: bound the rows' decode budgets
 };
 
 // where a decode writes: the caller's results, the parity hooks (gsv_t2s_set_debug) and the log-probabilities
@@ -60,8 +59,7 @@ struct RowOutputs {
 struct T2SSession {
   bool open = false;
   int slots = 0, budget = 0;
-  bool row_sampling = false;
-  bool row_limits = false;                                   // from the first admission that brought limits on: every slot has its own
+  bool row_sampling = false;                                 // what gsv_t2s_session_admit checks its row_sampling argument against
   gsv_sampling_params sp;
   RowOutputs out;                                            // the caller's and the hooks', held for the whole session
   std::vector<char> live;                                    // host view of active[], refreshed by every admit / advance
@@ -87,7 +85,8 @@ struct gsv_t2s : gsveng::Ctx {
   int ycap = 0;
   std::vector<unsigned long long> rng_seed_up; std::vector<int> rng_row_up;   // what the device arrays hold (skip re-uploads)
   std::vector<unsigned long long> rng_seed_next; std::vector<int> rng_row_next;   // gsv_t2s_set_row_rng: NEXT decode only
-  std::vector<gsv_row_sampling_t> row_sampling_up;   // what the device array holds (skip re-uploads)
+  std::vector<gsv_row_sampling_t> row_sampling_up;   // what the device arrays hold (skip re-uploads)
+  std::vector<gsv_row_limits_t> row_limits_up;
   std::vector<gsv_row_sampling_t> row_sampling_next; // gsv_t2s_set_row_sampling: NEXT decode only, cleared when it returns
   int* h_pinned = nullptr;
   // decode buffers
@@ -107,7 +106,6 @@ struct gsv_t2s : gsveng::Ctx {
   bool mega_on = true;      // gsv_t2s_set_mega (A/B inside one process); GSV_T2S_NO_MEGA=1 never builds the engine
   int prefill_gemm = 2;     // gsv_t2s_set_prefill_gemm: 0 dispatcher only, 1 panel GEMM wherever eligible, 2 from PANEL_MIN_ROWS rows upwards
   std::vector<gsv_row_limits_t> row_limits_next;     // gsv_t2s_set_row_limits: NEXT decode / admission only
-  bool limits_on = false;   // the StepParams at rows.sp hold a row-limits pointer: the LIMITS kernels run (both decode paths)
   RowOutputs next;          // gsv_t2s_set_debug / gsv_t2s_set_logprobs: the NEXT decode call (or the session begun next) only
   int dbg_stall = 0;        // gsv_t2s_debug_stall: likewise
   bool logp_on = false;     // the StepParams at rows.sp hold a log-probability pointer: run_mega launches a LOGP kernel
@@ -130,18 +128,20 @@ inline RowOutputs take_outputs(gsv_t2s* h, int32_t* out_tokens, int32_t* out_len
   return o;
 }
 
-// the StepParams of a decode over the rows of r that writes to o; per_row: row b samples with r.row_sampling[b]; limits: row b
-// ends by r.row_limits[b]
-inline gsv::StepParams step_params(const gsv_sampling_params& sp, const RowState& r, const RowOutputs& o, bool per_row,
-                                   bool limits = false) {
+// the StepParams of a decode over the rows of r that writes to o with row pitch max_steps; whoever uploads them has filled
+// r's per-row arrays for every row that can be live
+inline gsv::StepParams step_params(int max_steps, const RowState& r, const RowOutputs& o) {
   gsv::StepParams p;
   memset(&p, 0, sizeof(p));
-  p.top_k = sp.top_k; p.top_p = sp.top_p; p.temperature = sp.temperature; p.rep_penalty = sp.repetition_penalty;
-  p.early_stop_num = sp.early_stop_num; p.eos_mask_steps = sp.eos_mask_steps; p.max_steps = sp.max_steps; p.seed = sp.seed;
+  p.max_steps = max_steps;
   p.out_tokens = o.out_tokens; p.out_len = o.out_len; p.force = o.force; p.dump = o.dump; p.drawn = o.drawn; p.logp = o.logp;
-  p.plen = r.plen; p.rng_seed = r.rng_seed; p.rng_row = r.rng_row; p.row_sampling = per_row ? r.row_sampling : nullptr;
-  p.row_limits = limits ? r.row_limits : nullptr;
+  p.plen = r.plen; p.rng_seed = r.rng_seed; p.rng_row = r.rng_row; p.row_sampling = r.row_sampling; p.row_limits = r.row_limits;
   return p;
+}
+
+// forgets what the device row tables of h->rows hold: a session writes them itself
+inline void forget_row_tables(gsv_t2s* h) {
+  h->rng_seed_up.clear(); h->rng_row_up.clear(); h->row_sampling_up.clear(); h->row_limits_up.clear();
 }
 
 // steps a row can run: step 0 samples from the prefill's last position, every later step appends one K/V position
@@ -184,7 +184,8 @@ int check_row_sampling(const char* who, const gsv_row_sampling_t* rows, int B);
 // the RNG rows of gsv_t2s_set_row_rng and gsv_t2s_session_admit: the key holds 24 bits of the row (row << 40), so a row
 // outside [0, 2^24) would draw the stream of another row ("The counter RNG as a contract")
 int check_rng_rows(const char* who, const int32_t* rows, int B);
-// the limits of a call with the scalars of sp: what a row without limits of its own gets in a decode that has them
+// the sampling values and the limits of a call with the scalars of sp: what a row that brings none of its own gets
+inline gsv_row_sampling_t sampling_of(const gsv_sampling_params& sp) { return {sp.top_k, sp.top_p, sp.temperature, sp.repetition_penalty}; }
 inline gsv_row_limits_t limits_of(const gsv_sampling_params& sp) { return {sp.eos_mask_steps, sp.early_stop_num, sp.max_steps, 0}; }
 // gsv_t2s_set_row_limits' rows against the max_steps of the call / session that consumes them
 int check_row_limits_steps(const char* who, const std::vector<gsv_row_limits_t>& rows, int max_steps);

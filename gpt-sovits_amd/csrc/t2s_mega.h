@@ -58,7 +58,7 @@ size_t mega_hop_bytes(int ring);
 constexpr int MEGA_FP_LAYER = 6656;      // floats per layer in fpack
 
 int mega_census(hipStream_t s, unsigned* d_scratch, unsigned* h_pinned);   // 1 ok, 0 not co-resident, <0 error
-// logp / limits: the StepParams at a.sp hold a log-probability / a row-limits pointer
-int launch_t2s_mega(const MegaArgs& a, bool logp, bool limits, hipStream_t s);
+// logp: the StepParams at a.sp hold a log-probability pointer
+int launch_t2s_mega(const MegaArgs& a, bool logp, hipStream_t s);
 
 }  // namespace gsv

@@ -709,9 +709,9 @@ __device__ __forceinline__ void kv_stage_store(const Ctx& q, int qd, int extra, 
 // next to its own 17 registers: ~400 spilled VGPRs.  As a run-time branch on the pointer alone even the read-back form costs
 // the kernels that never take it 13 VGPRs and 80 bytes of scratch per lane, so those carry no trace of it and
 // launch_t2s_mega picks a LOGP kernel only when the pointer is set (DESIGN.md section 4p has the table).
-// LIMITS (likewise a compile-time constant): the row's EOS horizon, early stop and budget come from sp.row_limits[b]
-// (gsv_t2s_set_row_limits), one 16-byte load per sampled step; the kernels built without it read the call's scalars as before.
-#define MG_RUN_SAMPLER(LOGP, LIMITS) do { \
+// The row's sampling values and its EOS horizon, early stop and budget come from sp.row_sampling[b] / sp.row_limits[b], one
+// 16-byte load each per sampled step: the host fills both for every row (decode_begin, the sessions' admissions).
+#define MG_RUN_SAMPLER(LOGP) do { \
   const int V = a.V, EOS = a.V - 1; \
   const unsigned epE = ep0 + 4 * a.L + 2; \
     relaunder(q); \
@@ -730,9 +730,9 @@ __device__ __forceinline__ void kv_stage_store(const Ctx& q, int qd, int extra, 
     const bool ok = sweep<17>(q, q.hop + HOP_E + r * VPAD, V, epE, lv, 7u); \
     if (was_active && ok) { \
       const int step = st_step(q)[r]; \
-      const RowLimits rl = row_limits_of<LIMITS>(sp, b); \
+      const RowLimits rl = load_row_limits(sp.row_limits, b); \
       const int Veff = step < rl.eos_mask_steps ? V - 1 : V; \
-      const RowSampling rs = row_sampling_of(sp, b); \
+      const RowSampling rs = load_row_sampling(sp.row_sampling, b); \
       float x[17]; \
   _Pragma("unroll") \
       for (int i = 0; i < 17; ++i) { \
@@ -1040,7 +1040,7 @@ __device__ __forceinline__ void logits_publish(unsigned char* smem, int lane, in
 // One quad per group (B <= 32).  Every phase waits out its hop: the comm waves sweep it into the operand image, B1, the
 // compute waves multiply, B2, reduce and publish.
 // ---------------------------------------------------------------------------------------------------------------
-template <bool PROF, bool LOGP, bool LIMITS>
+template <bool PROF, bool LOGP>
 __device__ __forceinline__ void comm_role(const MegaArgs& a, const Ctx& c0, const StepParams& sp) {
   Ctx q = c0;
   unsigned char* smem = c0.smem;
@@ -1118,7 +1118,7 @@ __device__ __forceinline__ void comm_role(const MegaArgs& a, const Ctx& c0, cons
     sweep_ln<false>(q, ra, q.hop + HOP_A, ep0 + 4 * a.L + 1, 6u, a.hint_mask & 1, nullptr, 0, 0, true, gA, bA);
     MG_BAR();                                                             // B1
     MG_BAR();                                                            // B2
-    if (sampler) MG_RUN_SAMPLER(LOGP, LIMITS);
+    if (sampler) MG_RUN_SAMPLER(LOGP);
   }
 }
 
@@ -1258,7 +1258,7 @@ __device__ __forceinline__ void compute_role(const MegaArgs& a, const Ctx& c0) {
 // LN(hop A) of this quad is in its XS copy) and B_b (the image of this quad is stored; the QKV partials are parked).
 // The member's 16 residual columns of every row are parked per quad by the LayerNorm itself (no XRES image).
 // ---------------------------------------------------------------------------------------------------------------
-template <bool LOGP, bool LIMITS>
+template <bool LOGP>
 __device__ __forceinline__ void comm_role_pipe(const MegaArgs& a, const Ctx& c0, const StepParams& sp) {
   Ctx q = c0;
   unsigned char* smem = c0.smem;
@@ -1349,7 +1349,7 @@ __device__ __forceinline__ void comm_role_pipe(const MegaArgs& a, const Ctx& c0,
       if (qd + 1 < nq) sweep_t(qd + 1);
     }
     MG_BAR();                 // end of the step's GEMMs: the last logits GEMM has read its XS copy (the next step's first sweep rewrites copy 0)
-    if (sampler) MG_RUN_SAMPLER(LOGP, LIMITS);
+    if (sampler) MG_RUN_SAMPLER(LOGP);
   }
 }
 
@@ -1461,8 +1461,7 @@ __device__ __forceinline__ void compute_role_pipe(const MegaArgs& a, const Ctx& 
 // PROF: the in-kernel stamps (tools/mega_prof.py) are compiled in only for measurement launches -- as run-time tests they
 // cost ~100 scalar instructions per layer and wave.  Only the single-quad roles carry stamps.
 // LOGP: the sampler also writes the taken token's log-probability (MG_RUN_SAMPLER).
-// LIMITS: the sampler reads the row's own limits (MG_RUN_SAMPLER); built together with LOGP only, whose pointer may be null.
-template <bool PIPE, bool PROF, bool LOGP, bool LIMITS>
+template <bool PIPE, bool PROF, bool LOGP>
 __global__ __launch_bounds__(MG_THREADS, 1) void t2s_mega_kernel(MegaArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   Ctx c;
@@ -1542,10 +1541,10 @@ __global__ __launch_bounds__(MG_THREADS, 1) void t2s_mega_kernel(MegaArgs a) {
   __syncthreads();
   if (group_done(c)) return;
   if constexpr (PIPE) {
-    if (c.comm) comm_role_pipe<LOGP, LIMITS>(a, c, sp);
+    if (c.comm) comm_role_pipe<LOGP>(a, c, sp);
     else compute_role_pipe(a, c);
   } else {
-    if (c.comm) comm_role<PROF, LOGP, LIMITS>(a, c, sp);
+    if (c.comm) comm_role<PROF, LOGP>(a, c, sp);
     else compute_role<PROF>(a, c);
   }
 }
@@ -1624,28 +1623,24 @@ int mega_census(hipStream_t s, unsigned* d_scratch, unsigned* h_pinned) {
   return (h_pinned[0] == (unsigned)MG_NWG && h_pinned[1] == 0u) ? 1 : 0;
 }
 
-int launch_t2s_mega(const MegaArgs& a, bool logp, bool limits, hipStream_t s) {
+int launch_t2s_mega(const MegaArgs& a, bool logp, hipStream_t s) {
   // every launch: the attribute belongs to the (function, device) pair, and TTS.set_device may have moved the handle's owner
   // to another GPU of the process since the last launch (mega_census does the same)
-#define GSV_MEGA_LAUNCH(PIPE, PROF, LOGP, LIMITS)                                                                              \
+#define GSV_MEGA_LAUNCH(PIPE, PROF, LOGP)                                                                                      \
   do {                                                                                                                        \
-    GSV_HIP(hipFuncSetAttribute((const void*)t2s_mega_kernel<PIPE, PROF, LOGP, LIMITS>,                                       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, L_TOTAL));                                        \
-    hipLaunchKernelGGL((t2s_mega_kernel<PIPE, PROF, LOGP, LIMITS>), dim3(MG_NWG), dim3(MG_THREADS), L_TOTAL, s, a);           \
+    GSV_HIP(hipFuncSetAttribute((const void*)t2s_mega_kernel<PIPE, PROF, LOGP>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
+                                L_TOTAL));                                                                                    \
+    hipLaunchKernelGGL((t2s_mega_kernel<PIPE, PROF, LOGP>), dim3(MG_NWG), dim3(MG_THREADS), L_TOTAL, s, a);                   \
   } while (0)
-  // Seven kernels.  More than one quad per group (B > 32): pipelined quads, which carry no stamps -- a profiling request
+  // Five kernels.  More than one quad per group (B > 32): pipelined quads, which carry no stamps -- a profiling request
   // (a.prof, tools/mega_prof.py) at B > 32 runs this kernel all the same and its stamp buffer stays zero.  One quad: stamps
   // compiled in for measurement launches only.  logp (the decode's StepParams hold a log-probability pointer): the two
   // kernels whose sampler writes it, which carry no stamps either.
-  // limits (the StepParams hold a row-limits pointer): two more, which carry the log-probability code as well and
-  // test its pointer at run time -- a decode with limits is the rarer launch, and two kernels are cheaper to build than four.
-  if (limits && a.B > RMAX * MG_GROUPS) GSV_MEGA_LAUNCH(true, false, true, true);
-  else if (limits) GSV_MEGA_LAUNCH(false, false, true, true);
-  else if (logp && a.B > RMAX * MG_GROUPS) GSV_MEGA_LAUNCH(true, false, true, false);
-  else if (logp) GSV_MEGA_LAUNCH(false, false, true, false);
-  else if (a.B > RMAX * MG_GROUPS) GSV_MEGA_LAUNCH(true, false, false, false);
-  else if (a.prof != nullptr) GSV_MEGA_LAUNCH(false, true, false, false);
-  else GSV_MEGA_LAUNCH(false, false, false, false);
+  if (logp && a.B > RMAX * MG_GROUPS) GSV_MEGA_LAUNCH(true, false, true);
+  else if (logp) GSV_MEGA_LAUNCH(false, false, true);
+  else if (a.B > RMAX * MG_GROUPS) GSV_MEGA_LAUNCH(true, false, false);
+  else if (a.prof != nullptr) GSV_MEGA_LAUNCH(false, true, false);
+  else GSV_MEGA_LAUNCH(false, false, false);
 #undef GSV_MEGA_LAUNCH
   GSV_HIP(hipGetLastError());
   return GSV_OK;

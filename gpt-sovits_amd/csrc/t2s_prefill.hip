@@ -456,7 +456,7 @@ int t2s_prefill_rows(gsv_t2s* h, RowState& r, const int32_t* phones, const int32
     const size_t need_vt = (size_t)B * H * 32 * ((maxS + 31) / 32 * 32) * 2;
     if (need_vt > h->pf_vt_cap) { GSV_RC(dalloc(h, &h->pf_vt, need_vt + need_vt / 4)); h->pf_vt_cap = need_vt + need_vt / 4; }
   }
-  r.B = B; r.P = maxP; r.max_kv0 = maxS;
+  r.B = B; r.P = maxP;
   r.kv0 = kvl; r.pl.assign(plen, plen + B);
   GSV_HIP(hipMemcpyAsync(h->d_x_len, phone_lens, B * 4, hipMemcpyHostToDevice, s));
   GSV_HIP(hipMemcpyAsync(h->d_row_off, row_off.data(), B * 4, hipMemcpyHostToDevice, s));

@@ -25,15 +25,8 @@ struct RowLimits {
 };
 
 struct StepParams {
-  int top_k;
-  float top_p;
-  float temperature;
-  float rep_penalty;
-  int early_stop_num;
-  int eos_mask_steps;
-  int max_steps;
+  int max_steps;           // row pitch of out_tokens, logp and the hooks (a row's own budget is row_limits[b].max_steps)
   int noise_rows;          // 0: counter RNG, 1: shared noise, B: per-row noise
-  unsigned long long seed;
   const float* noise;      // [max_steps][noise_rows][V] or null
   int* out_tokens;         // [B][max_steps]
   int* out_len;            // [B]
@@ -45,14 +38,13 @@ struct StepParams {
   const int* force;        // [B][max_steps]: the token taken at step s of row b instead of the sampled one
   float* dump;             // [max_steps][B][V]: logits of every executed step, before the repetition penalty
   int* drawn;              // [max_steps][B][2]: (token the sampler drew, argmax of the penalised logits) before any forcing
-  // [B] or null: row b samples with row_sampling[b] instead of top_k / top_p / temperature / rep_penalty above
+  // [B], never null: row b samples with row_sampling[b] and masks EOS, stops early and ends with row_limits[b].  The host
+  // fills both for every row, with the call's scalars where the caller gave no rows (decode_begin, session_admit).
   const RowSampling* row_sampling;
+  const RowLimits* row_limits;
   // [B][max_steps] or null (gsv_t2s_set_logprobs), indexed like out_tokens: the log-probability of the token row b takes at
   // step s under the model's own distribution (token_logprob below); the step that ends the row has its entry too
   float* logp;
-  // [B] or null: row b masks EOS, stops early and ends with row_limits[b] instead of eos_mask_steps / early_stop_num / max_steps
-  // above; max_steps stays the row pitch of out_tokens, logp and the hooks.  Only the LIMITS kernels read it.
-  const RowLimits* row_limits;
 };
 
 // Row b's entry of a RowSampling array.  b is wave-uniform at every call site, so the four values are made scalars again:
@@ -62,22 +54,10 @@ __device__ __forceinline__ RowSampling load_row_sampling(const RowSampling* __re
   return {__builtin_amdgcn_readfirstlane(v.x), __int_as_float(__builtin_amdgcn_readfirstlane(v.y)),
           __int_as_float(__builtin_amdgcn_readfirstlane(v.z)), __int_as_float(__builtin_amdgcn_readfirstlane(v.w))};
 }
-// the sampling values of batch row b: its own when the host gave per-row values for this decode, else the call's
-__device__ __forceinline__ RowSampling row_sampling_of(const StepParams& sp, int b) {
-  if (sp.row_sampling) return load_row_sampling(sp.row_sampling, b);
-  return {sp.top_k, sp.top_p, sp.temperature, sp.rep_penalty};
-}
 // Row b's entry of a RowLimits array, read like load_row_sampling: one 16-byte load, wave-uniform values
 __device__ __forceinline__ RowLimits load_row_limits(const RowLimits* __restrict__ rows, int b) {
   const int4 v = *reinterpret_cast<const int4*>(rows + b);
   return {__builtin_amdgcn_readfirstlane(v.x), __builtin_amdgcn_readfirstlane(v.y), __builtin_amdgcn_readfirstlane(v.z), 0};
-}
-// The limits of batch row b.  LIMITS is a compile-time constant: the kernels built without it carry no trace of the per-row
-// form (as a run-time branch it would sit in every launch's sampler, like the log-probabilities did: DESIGN.md 4p).
-template <bool LIMITS>
-__device__ __forceinline__ RowLimits row_limits_of(const StepParams& sp, int b) {
-  if constexpr (LIMITS) if (sp.row_limits) return load_row_limits(sp.row_limits, b);
-  return {sp.eos_mask_steps, sp.early_stop_num, sp.max_steps, 0};
 }
 
 // ---------------------------------------------------------------------------------------

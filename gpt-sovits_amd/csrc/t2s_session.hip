@@ -20,8 +20,8 @@ namespace gsv {
 
 typedef unsigned u4v __attribute__((ext_vector_type(4)));
 
-// One side of the adopt launch: the arena and the per-row arrays of a RowState plus where its decode writes.  row_sampling,
-// row_limits, drawn, dump and logp are null on BOTH sides when the session lacks them: the kernel tests dst's and only then reads src's.
+// One side of the adopt launch: the arena and the per-row arrays of a RowState plus where its decode writes.  drawn, dump and
+// logp are null on BOTH sides when the session lacks them: the kernel tests dst's and only then reads src's.
 struct AdoptView {
   void* kv; unsigned long long layer_stride;   // elements per (layer, k|v)
   int smax;                                    // positions per (row, head) of the arena
@@ -89,8 +89,8 @@ __global__ __launch_bounds__(256) void session_adopt_kernel(AdoptArgs a, int hg 
     if (act) atomicAdd(a.dst.state + 3 * mb, 1);
     a.dst.rng_seed[slot] = a.src.rng_seed[i];
     a.dst.rng_row[slot] = a.src.rng_row[i];
-    if (a.dst.row_sampling) a.dst.row_sampling[slot] = a.src.row_sampling[i];
-    if (a.dst.row_limits) a.dst.row_limits[slot] = a.src.row_limits[i];
+    a.dst.row_sampling[slot] = a.src.row_sampling[i];
+    a.dst.row_limits[slot] = a.src.row_limits[i];
     a.dst.out_len[slot] = a.src.out_len[i];
     a.dst.out_tokens[(size_t)slot * a.steps] = a.src.out_tokens[(size_t)i * a.steps];
     if (a.dst.drawn) { a.dst.drawn[2 * slot] = a.src.drawn[2 * i]; a.dst.drawn[2 * slot + 1] = a.src.drawn[2 * i + 1]; }
@@ -162,12 +162,12 @@ int launch_session_release(int* state, int mb, const int* slot, int n, int slots
   return GSV_OK;
 }
 
-// r's side of the adopt launch, with where its decode writes; per_row and limits as in step_params
-AdoptView adopt_view(const RowState& r, const RowOutputs& o, bool per_row, bool limits) {
+// r's side of the adopt launch, with where its decode writes
+AdoptView adopt_view(const RowState& r, const RowOutputs& o) {
   AdoptView v;
   v.kv = r.kv; v.layer_stride = r.kv_layer_stride; v.smax = r.max_seq;
   v.state = r.state; v.plen = r.plen; v.ytok = r.ytok; v.rng_row = r.rng_row; v.rng_seed = r.rng_seed;
-  v.row_sampling = per_row ? r.row_sampling : nullptr; v.row_limits = limits ? r.row_limits : nullptr; v.ybuf = r.ybuf;
+  v.row_sampling = r.row_sampling; v.row_limits = r.row_limits; v.ybuf = r.ybuf;
   v.out_tokens = o.out_tokens; v.out_len = o.out_len; v.drawn = o.drawn; v.dump = o.dump; v.logp = o.logp;
   return v;
 }
@@ -201,24 +201,29 @@ int session_begin(gsv_t2s* h, const gsv_sampling_params* sp, int slots, int row_
   GSV_HIP(hipMemset(st.logits, 0, mb * V * 4));
   for (auto& e : z.ev) if (!e) GSV_HIP(hipEventCreate(&e));
   z.sp = *sp; z.slots = slots; z.budget = step_budget(*sp); z.row_sampling = row_sampling != 0;
-  z.row_limits = false; h->limits_on = false; h->row_limits_next.clear();
   z.out = take_outputs(h, out_tokens, out_len);
   // a hook the session lacks is off in an admission's step 0 as well
   so.force = z.out.force ? z.staging_force : nullptr; so.dump = z.out.dump ? dump : nullptr;
   so.drawn = z.out.drawn ? drawn : nullptr; so.logp = z.out.logp ? logp : nullptr;
-  // every slot free: active = 0, and every per-row array the kernels load for a free slot holds zeros
+  // every slot free: active = 0, and every per-row array the kernels load for a free slot holds zeros, or the session's
+  // scalars where an admission may leave them: the sampling values and limits, on the staging rows too
   GSV_HIP(hipMemset(r.state, 0, r.state_ints() * 4));
   GSV_HIP(hipMemset(r.plen, 0, 2 * mb * 4));
   GSV_HIP(hipMemset(r.rng_seed, 0, mb * 8));
   GSV_HIP(hipMemset(r.rng_row, 0, mb * 4));
-  GSV_HIP(hipMemset(r.row_sampling, 0, mb * sizeof(RowSampling)));
+  const std::vector<gsv_row_sampling_t> sampling(mb, sampling_of(z.sp));
+  const std::vector<gsv_row_limits_t> limits(mb, limits_of(z.sp));
+  for (const RowState* rs : {&r, &st}) {
+    GSV_HIP(hipMemcpy(rs->row_sampling, sampling.data(), mb * sizeof(RowSampling), hipMemcpyHostToDevice));
+    GSV_HIP(hipMemcpy(rs->row_limits, limits.data(), mb * sizeof(RowLimits), hipMemcpyHostToDevice));
+  }
   GSV_HIP(hipMemset(r.ybuf, 0, mb * d * 4));
-  h->rng_seed_up.clear(); h->rng_row_up.clear(); h->row_sampling_up.clear();   // the device arrays are the session's now
-  h->rng_seed_next.clear(); h->rng_row_next.clear(); h->row_sampling_next.clear();
-  const StepParams p = step_params(z.sp, r, z.out, z.row_sampling), ps = step_params(z.sp, st, so, z.row_sampling);
+  forget_row_tables(h);   // the device arrays are the session's now
+  h->rng_seed_next.clear(); h->rng_row_next.clear(); h->row_sampling_next.clear(); h->row_limits_next.clear();
+  const StepParams p = step_params(z.sp.max_steps, r, z.out), ps = step_params(z.sp.max_steps, st, so);
   GSV_HIP(hipMemcpy(r.sp, &p, sizeof(p), hipMemcpyHostToDevice));
   GSV_HIP(hipMemcpy(st.sp, &ps, sizeof(ps), hipMemcpyHostToDevice));
-  r.B = slots; r.P = 0; r.max_kv0 = 0;
+  r.B = slots; r.P = 0;
   z.live.assign(slots, 0);
   z.last_adopt_ms = 0.f; z.last_adopt_bytes = 0;
   z.open = true;
@@ -246,22 +251,13 @@ int session_admit(gsv_t2s* h, int n, const int32_t* slot_ids, const int32_t* pho
   GSV_HIP(hipMemcpyAsync(st.rng_seed, rng_seeds, (size_t)n * 8, hipMemcpyHostToDevice, s));
   GSV_HIP(hipMemcpyAsync(st.rng_row, rng_rows, (size_t)n * 4, hipMemcpyHostToDevice, s));
   GSV_HIP(hipMemcpyAsync(z.st_slot, slot_ids, (size_t)n * 4, hipMemcpyHostToDevice, s));
-  if (z.row_sampling)
-    GSV_HIP(hipMemcpyAsync(st.row_sampling, row_sampling, (size_t)n * sizeof(RowSampling), hipMemcpyHostToDevice, s));
-  if (!limits.empty() && !z.row_limits) {
-    // The first admission that brings limits: from here on every slot has its own (the session's scalars until a row brings
-    // others) and both sets of StepParams point at them, so that the LIMITS kernels run.  The stream is idle between calls.
-    const std::vector<gsv_row_limits_t> all((size_t)h->max_batch, limits_of(z.sp));
-    GSV_HIP(hipMemcpy(h->rows.row_limits, all.data(), all.size() * sizeof(RowLimits), hipMemcpyHostToDevice));
-    const StepParams p = step_params(z.sp, h->rows, z.out, z.row_sampling, true), ps = step_params(z.sp, st, so, z.row_sampling, true);
-    GSV_HIP(hipMemcpy(h->rows.sp, &p, sizeof(p), hipMemcpyHostToDevice));
-    GSV_HIP(hipMemcpy(st.sp, &ps, sizeof(ps), hipMemcpyHostToDevice));
-    z.row_limits = true; h->limits_on = true;
-  }
-  // this admission's rows: their own limits, or the session's scalars, which also wipe what the slot's last occupant had
+  // this admission's rows: their own sampling values and limits, or the session's scalars, which the adopt launch also puts
+  // in the place of what the slot's last occupant had
+  const std::vector<gsv_row_sampling_t> sampling = row_sampling ? std::vector<gsv_row_sampling_t>(row_sampling, row_sampling + n)
+                                                                : std::vector<gsv_row_sampling_t>((size_t)n, sampling_of(z.sp));
   const std::vector<gsv_row_limits_t> mine = !limits.empty() ? limits : std::vector<gsv_row_limits_t>((size_t)n, limits_of(z.sp));
-  if (z.row_limits)
-    GSV_HIP(hipMemcpyAsync(st.row_limits, mine.data(), (size_t)n * sizeof(RowLimits), hipMemcpyHostToDevice, s));
+  GSV_HIP(hipMemcpyAsync(st.row_sampling, sampling.data(), (size_t)n * sizeof(RowSampling), hipMemcpyHostToDevice, s));
+  GSV_HIP(hipMemcpyAsync(st.row_limits, mine.data(), (size_t)n * sizeof(RowLimits), hipMemcpyHostToDevice, s));
   GSV_HIP(hipMemsetAsync(so.out_len, 0xFF, (size_t)n * 4, s));     // -1: not finished
   if (so.force)   // step 0 of row i is forced with its slot's entry
     for (int i = 0; i < n; ++i)
@@ -269,7 +265,7 @@ int session_admit(gsv_t2s* h, int n, const int32_t* slot_ids, const int32_t* pho
   GSV_RC(t2s_prefill_into(h, st, phones, phone_lens, n, bert, prompts_packed, prompt_lens, s));
   GSV_RC(t2s_step0_tail(h, st, s));   // the rows now stand where gsv_t2s_decode's rows stand after its step 0
   AdoptArgs a;
-  a.src = adopt_view(st, so, z.row_sampling, z.row_limits); a.dst = adopt_view(h->rows, z.out, z.row_sampling, z.row_limits);
+  a.src = adopt_view(st, so); a.dst = adopt_view(h->rows, z.out);
   a.n = n; a.slots = z.slots; a.mb = h->max_batch; a.ycap = h->ycap; a.d = c.dim; a.V = c.vocab; a.L = c.n_layer; a.H = c.n_head;
   a.esize = (int)esz(h); a.steps = (int)ms; a.slot = z.st_slot;
   GSV_HIP(hipEventRecord(z.ev[0], s));
@@ -413,9 +409,9 @@ int gsv_t2s_session_end(gsv_t2s_t* h) {
   T2SSession& z = h->ses;
   z.open = false; z.live.clear();
   z.out = RowOutputs();
-  z.row_limits = false; h->limits_on = false; h->row_limits_next.clear();
   h->rows.B = 0;   // the next decode needs a prefill of its own, as on a fresh handle
-  h->rng_seed_up.clear(); h->rng_row_up.clear(); h->row_sampling_up.clear();
+  forget_row_tables(h);
+  h->row_limits_next.clear();
   return GSV_OK;
 }
 

@@ -102,6 +102,17 @@ def row_limit_tuples(row_limits, needs, max_seq):
     return out, budgets, short
 
 
+def row_sampling_array(rows):
+    """[(top_k | None, top_p | None, temperature, repetition_penalty)] as the gsv_row_sampling_t array the engine takes"""
+    return (_lib.RowSampling * len(rows))(*[_lib.RowSampling(int(k) if k is not None else 0, float(p if p is not None else 1.0),
+                                                             float(t), float(rp)) for k, p, t, rp in rows])
+
+
+def row_limits_array(limits):
+    """row_limit_tuples' tuples as the gsv_row_limits_t array the engine takes"""
+    return (_lib.RowLimits * len(limits))(*[_lib.RowLimits(e, es, ms, 0) for e, es, ms in limits])
+
+
 class T2SSession:
     """An open decode session of a Text2SemanticDecoder (gsv_t2s_session_*): `slots` rows of its K/V arena that are admitted,
     advanced a chunk of steps at a time and admitted again when their row has finished.  Use as a context manager."""
@@ -214,13 +225,9 @@ class T2SSession:
             slots_h, lens_h, plens_h = (C.c_int32 * n)(*slots), (C.c_int32 * n)(*lens), (C.c_int32 * n)(*plens)
             seeds_h = (C.c_uint64 * n)(*[int(r["key"][0]) & 0xFFFFFFFFFFFFFFFF for r in rows])
             rrows_h = (C.c_int32 * n)(*[int(r["key"][1]) for r in rows])
-            rs_h = None
-            if self.per_row:
-                rs_h = (_lib.RowSampling * n)(*[_lib.RowSampling(int(k) if k is not None else 0, float(p_ if p_ is not None else 1.0),
-                                                                 float(t), float(rp)) for k, p_, t, rp in (r["sampling"] for r in rows)])
+            rs_h = row_sampling_array([r["sampling"] for r in rows]) if self.per_row else None
             if limits is not None:
-                rl_h = (_lib.RowLimits * n)(*[_lib.RowLimits(e, es, ms, 0) for e, es, ms in limits])
-                _lib.check(l.gsv_t2s_set_row_limits(dec._h, rl_h, n), "gsv_t2s_set_row_limits")
+                _lib.check(l.gsv_t2s_set_row_limits(dec._h, row_limits_array(limits), n), "gsv_t2s_set_row_limits")
             _lib.check(l.gsv_t2s_session_admit(dec._h, n, C.cast(slots_h, C.c_void_p), phones.data_ptr(), C.cast(lens_h, C.c_void_p),
                                                bert_dev.data_ptr() if bert_dev is not None else None,
                                                pr.data_ptr() if pr.numel() else None,
@@ -463,8 +470,7 @@ class Text2SemanticDecoder:
                 sp.early_stop_num = -1   # the arena bound (max_steps) ends generation first
             s = C.c_void_p(self.stream.cuda_stream)
             if limits is not None:   # in front of the prefill: they are what lets it take prompt-free rows
-                rl_h = (_lib.RowLimits * B)(*[_lib.RowLimits(e, es, ms, 0) for e, es, ms in limits])
-                _lib.check(l.gsv_t2s_set_row_limits(self._h, rl_h, B), "gsv_t2s_set_row_limits")
+                _lib.check(l.gsv_t2s_set_row_limits(self._h, row_limits_array(limits), B), "gsv_t2s_set_row_limits")
             if ragged:
                 plens_h = (C.c_int32 * B)(*plens)
                 _lib.check(l.gsv_t2s_prefill_ragged(self._h, phones.data_ptr(), C.cast(lens_h, C.c_void_p), B,
@@ -484,9 +490,7 @@ class Text2SemanticDecoder:
                 _lib.check(l.gsv_t2s_set_row_rng(self._h, C.cast(seeds_h, C.c_void_p), C.cast(rows_h, C.c_void_p), B),
                            "gsv_t2s_set_row_rng")
             if row_sampling is not None:
-                rs_h = (_lib.RowSampling * B)(*[_lib.RowSampling(int(k) if k is not None else 0, float(p_ if p_ is not None else 1.0),
-                                                                 float(t), float(r)) for k, p_, t, r in row_sampling])
-                _lib.check(l.gsv_t2s_set_row_sampling(self._h, rs_h, B), "gsv_t2s_set_row_sampling")
+                _lib.check(l.gsv_t2s_set_row_sampling(self._h, row_sampling_array(row_sampling), B), "gsv_t2s_set_row_sampling")
             steps = C.c_int(0)
             dump = None
             if force_tokens is not None or dump_logits:

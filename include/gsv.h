@@ -135,8 +135,8 @@ typedef struct {
  * rows (see there).  GSV_ERR_ARG with nothing kept: eos_mask_steps < 0, early_stop_num < -1, max_steps < 1, reserved != 0,
  * B outside 1 .. max_batch; the consuming call refuses, before any launch and dropping the limits, a B different from its
  * rows and a max_steps above its own.  A session keeps a slot's limits with the slot's row state until the row is finished or
- * released; a row admitted without limits runs by the session's scalars.  Without this call nothing changes: the kernels that
- * read per-row limits are separate instantiations and are launched only for such a decode. */
+ * released; a row admitted without limits runs by the session's scalars.  Without this call every row runs by the scalars of the
+ * call: the engine fills the rows' limits with them, and the kernels read only the rows'. */
 int gsv_t2s_set_row_limits(gsv_t2s_t* h, const gsv_row_limits_t* rows, int B);
 
 /* Decode loop (H4+H5).  noise [dev] fp32 Exp(1) draws [max_steps][noise_rows][vocab] or NULL

@@ -11,8 +11,8 @@ under horizon 11 the same rows run past step 10) before any device work.
 * fp16 persistent engine, a 2-layer model of the v1/v2 shape, B = 8 (one quad) and B = 40 (pipelined quads): mixed against
   alone, mode 1, no fallback, on rows whose oracle top-2 margins are all clear of fp16 noise (V2_CLEAR, checked on the CPU);
   and on the full 24-layer model, 20 rows (one quad) and 34 rows (pipelined), every row of the mixed decode against the same
-  batch decoded with that row's limits as the scalars, i.e. each kernel with limits against its twin without, where the bits
-  must agree whatever the margins are;
+  batch decoded with that row's limits as the scalars, i.e. the same kernel with the rows' limits against itself with the
+  call's scalars in every row's entry, where the bits must agree whatever the margins are;
 * housekeeping: B copies of the scalars = no limits, limits hold for one call, bad values / wrong B refused, P_b = 0 without
   limits refused with today's message;
 * session: 9 rows through 4 slots in chunks of 1, 3 and 7 steps equal their one-shot decodes, a reused slot keeps nothing of
@@ -296,8 +296,9 @@ def v2_full():
 @pytest.mark.parametrize("B", [24, 40])
 def test_fp16_engine_with_limits_equals_the_scalar_decode_of_the_same_batch(v2_full, B):
     """Full-size engine, single-quad (20 rows) and pipelined (34 rows) kernel: every row of the decode with limits against the
-    SAME batch decoded with that row's limits as the scalars -- the kernel with limits against its twin without, the same
-    sums in the same order, so the bits must agree whatever the margins are."""
+    SAME batch decoded with that row's limits as the scalars -- the same kernel, reading the rows' own limits in one decode and
+    the call's scalars from every row's entry in the other, the same sums in the same order, so the bits must agree whatever the
+    margins are."""
     cfg, sd, eng = v2_full
     xs, berts, prompts, lims, keys = _case(cfg, B, seed=41)
     rows = [b for b in range(B) if prompts[b] is not None]           # the scalar path takes no prompt-free row in a ragged batch

@@ -4,17 +4,9 @@
 //   y_s[i] = sum_j h[i * down + half - j * up] * x_s[j],  j in [0, n_s) with the filter index in [0, L),  L = 2 * half + 1.
 #include "common.h"
 #include "engine.h"
+#include "resample.h"
 
 namespace gsv {
-
-constexpr int kRsTile = 1024;                // consecutive outputs of one segment per workgroup (256 threads, 4 outputs each)
-constexpr int kRsLdsFloats = 16384;          // 64 KiB of LDS per workgroup: the input window, and the filter where it still fits
-constexpr int kRsMaxFilter = 65535;          // the largest h_len (a filter that does not fit in LDS is read through L2)
-
-// the input window of `tile` consecutive outputs is at most this many samples
-static inline long long rs_window(int tile, int up, int down, int L) {
-  return ((long long)(tile - 1) * down + (L - 1)) / up + 2;
-}
 
 // the segment that owns workgroup `tile`: the last one whose first tile (tab[].w) is <= tile
 __device__ __forceinline__ int rs_find(const int4* __restrict__ tab, int n_seg, int tile) {

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "common.h"
+#include "resample.h"
 
 namespace gsv {
 
@@ -255,6 +256,143 @@ __global__ __launch_bounds__(256) void post_groups_write_kernel(const GroupSent*
   if (left <= kGroupTile) zero_fill(o + n, S.gap, tid);                  // the sentence's last tile (its only one when empty)
 }
 
+// ---- gsv_postprocess_groups_rate: the groups at another sample rate and in another encoding -------------
+// Group g is the virtual stream X_g = concat_i [norm(x_i), gap zeros] (what postprocess_kernel<T, float> writes for it alone),
+// resampled as resample_poly_seg_kernel does (resample.hip: one thread per output, one fp32 accumulator, fmaf over its taps in
+// ascending input index) and converted.  The peaks come from post_groups_peak_kernel; GroupSent::dst is here the sentence's first
+// sample in its group's stream.  One workgroup per kRsTile consecutive outputs of one group: it finds the sentence under the first
+// sample of its input window once, walks sentences and gaps from there and stages the window in LDS as normalised fp32 (the gaps
+// are zeros written to LDS, never loaded), with the filter behind it where HLDS.  The LDS reads of the tap loop are those of
+// resample_poly_seg_kernel, whose header counts their bank conflicts.  The results go back to LDS, over the window, so that the
+// conversion can store 16 bytes per lane where the output's address allows.
+struct RateGroup {
+  long long out;       // first output sample
+  long long n;         // N_g: samples of the virtual stream
+  int sent0, n_sent;   // its sentences in the table
+  int m, tile0;        // outputs, first workgroup
+};
+static_assert(sizeof(RateGroup) == 32, "table layout");
+
+__device__ __forceinline__ short rate_s16(float y) {                     // saturates; a NaN ends at the lower bound
+  return (short)(int)fminf(fmaxf(y * 32768.f, -32768.f), 32767.f);
+}
+// ITU-T G.711 of an int16 sample, segment search by the position of the highest set bit
+__device__ __forceinline__ unsigned char rate_mulaw(short s) {
+  int v = (int)s >> 2;                                                   // 14 bits
+  const int mask = v < 0 ? 0x7f : 0xff;
+  v = v < 0 ? -v : v;
+  v = (v > 8159 ? 8159 : v) + 33;                                        // clip, bias
+  const int seg = max(0, 26 - __clz(v));                                 // first segment whose end 0x3f << seg | ... holds v
+  return (unsigned char)((seg >= 8 ? 0x7f : ((seg << 4) | ((v >> (seg + 1)) & 0xf))) ^ mask);
+}
+__device__ __forceinline__ unsigned char rate_alaw(short s) {
+  int v = (int)s >> 3;                                                   // 13 bits
+  const int mask = v < 0 ? 0x55 : 0xd5;
+  v = v < 0 ? -v - 1 : v;
+  const int seg = max(0, 27 - __clz(v));                                 // v <= 4095: seg <= 7
+  return (unsigned char)(((seg << 4) | ((v >> (seg < 2 ? 1 : seg)) & 0xf)) ^ mask);
+}
+
+template <int FMT> struct RateOut;
+template <> struct RateOut<GSV_OUT_S16> { typedef short type; static __device__ __forceinline__ short cvt(float y) { return rate_s16(y); } };
+template <> struct RateOut<GSV_OUT_MULAW> { typedef unsigned char type; static __device__ __forceinline__ unsigned char cvt(float y) { return rate_mulaw(rate_s16(y)); } };
+template <> struct RateOut<GSV_OUT_ALAW> { typedef unsigned char type; static __device__ __forceinline__ unsigned char cvt(float y) { return rate_alaw(rate_s16(y)); } };
+template <> struct RateOut<GSV_OUT_F32> { typedef float type; static __device__ __forceinline__ float cvt(float y) { return y; } };
+
+template <typename T, int FMT, bool HLDS>
+__global__ __launch_bounds__(256) void post_groups_rate_kernel(const GroupSent* __restrict__ sent, const RateGroup* __restrict__ groups,
+                                                               int n_groups, const float* __restrict__ h, int L, int up, int down,
+                                                               void* __restrict__ out, int win_cap) {
+  typedef typename RateOut<FMT>::type O;
+  constexpr int E = 16 / sizeof(O);
+  typedef O OV __attribute__((ext_vector_type(E)));
+  extern __shared__ float rate_lds[];
+  float* xs = rate_lds;                                                  // max(win_cap, kRsTile) floats
+  const int h_at = win_cap > kRsTile ? win_cap : kRsTile;
+  const float* hs = HLDS ? rate_lds + h_at : h;
+  const int tid = threadIdx.x;
+  int lo = 0, hi = n_groups - 1;                                         // the last group whose first workgroup is <= this one
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (groups[mid].tile0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+  }
+  const RateGroup G = groups[lo];
+  const long long n = G.n;
+  const int half = L >> 1;
+  const int o0 = ((int)blockIdx.x - G.tile0) * kRsTile, o1 = min(G.m, o0 + kRsTile);
+  if (o0 >= o1) return;                                                  // the host launches no such tile
+  // the window [w0, w0 + wn) of the stream that outputs [o0, o1) read
+  const long long a0 = (long long)o0 * down + half - (L - 1);
+  const long long w0 = a0 <= 0 ? 0 : (a0 + up - 1) / up;
+  const long long wl = min(n - 1, ((long long)(o1 - 1) * down + half) / up);
+  const int wn = (int)min((long long)win_cap, max(0LL, wl - w0 + 1));
+  const long long w1 = w0 + wn;
+  // the sentence under w0: the last one that starts at or before it (an empty sentence without a gap covers nothing)
+  int sa = G.sent0, sb = G.sent0 + G.n_sent - 1;
+  while (sa < sb) {
+    const int mid = (sa + sb + 1) >> 1;
+    if (sent[mid].dst <= w0) sa = mid; else sb = mid - 1;
+  }
+  for (int si = sa; si < G.sent0 + G.n_sent; ++si) {
+    const GroupSent S = sent[si];
+    if (S.dst >= w1) break;
+    const long long b = S.dst > w0 ? S.dst : w0;                        // [b, e): this sentence and its gap inside the window
+    const long long e = min(S.dst + S.len + S.gap, w1);
+    const int cnt = (int)(e - b), at = (int)(b - w0);
+    const int first = (int)(b - S.dst);                                  // sample of the sentence at b (>= len: inside the gap)
+    const int live = max(0, min(cnt, S.len - first));                    // samples that are loaded; the rest are the gap's zeros
+    const T* __restrict__ x = (const T*)S.src + first;
+    const bool divide = S.peak > 0x3f800000u && S.peak <= 0x7f800000u;   // peak > 1 and no NaN
+    const T denom = (T)__uint_as_float(S.peak);
+    for (int i = tid; i < cnt; i += 256) {
+      float f = 0.f;
+      if (i < live) {
+        T v = x[i];
+        if (divide) v = (T)((float)v / (float)denom);                    // postprocess_kernel's arithmetic, in T
+        f = (float)v;
+      }
+      xs[at + i] = f;
+    }
+  }
+  if (HLDS) for (int i = tid; i < L; i += 256) rate_lds[h_at + i] = h[i];
+  __syncthreads();
+  float acc[kRsTile / 256];
+#pragma unroll
+  for (int r = 0; r < kRsTile / 256; ++r) {
+    const int o = o0 + tid + 256 * r;
+    acc[r] = 0.f;
+    if (o < o1) {
+      const long long c = (long long)o * down + half;
+      const long long a = c - (L - 1);
+      const long long ja = a <= 0 ? 0 : (a + up - 1) / up;
+      const long long jb = min(n - 1, c / up);
+      int k = (int)(c - ja * up);                                        // filter index of the first tap, in [0, L)
+      const int q0 = (int)(ja - w0), q1 = min((int)(jb - w0), wn - 1);
+      float s = 0.f;
+      for (int q = q0; q <= q1; ++q, k -= up) s = fmaf(hs[k], xs[q], s);
+      acc[r] = s;
+    }
+  }
+  __syncthreads();                                                       // every tap is read: the results take the window's place
+#pragma unroll
+  for (int r = 0; r < kRsTile / 256; ++r) xs[tid + 256 * r] = acc[r];
+  __syncthreads();
+  const int cnt = o1 - o0;
+  O* __restrict__ o = (O*)out + G.out + o0;
+  const int head = head_count(o, cnt);                                   // the stores of the body are 16-byte aligned
+  if (tid < head) o[tid] = RateOut<FMT>::cvt(xs[tid]);
+  const int body = (cnt - head) / E;
+  OV* __restrict__ ov = (OV*)(o + head);
+  for (int i = tid; i < body; i += 256) {
+    OV r;
+#pragma unroll
+    for (int k = 0; k < E; ++k) r[k] = RateOut<FMT>::cvt(xs[head + E * i + k]);
+    ov[i] = r;
+  }
+  const int tail = head + body * E;
+  if (tail + tid < cnt) o[tail + tid] = RateOut<FMT>::cvt(xs[tail + tid]);
+}
+
 }  // namespace gsv
 
 extern "C" int gsv_sola(float* frags, const int* lens, int n, int overlap, float* out, int* out_len, gsv_stream_t stream) {
@@ -405,4 +543,109 @@ extern "C" int gsv_postprocess_groups(const void* const* frags, const int* lens,
   }
   GSV_HIP(hipGetLastError());
   return GSV_OK;
+}
+
+extern "C" long long gsv_postprocess_groups_rate_workspace(const int* lens, int n, int n_groups) {
+  if (n < 0 || n_groups < 0 || (n > 0 && !lens)) return -1;
+  long long tiles = 0;
+  for (int i = 0; i < n; ++i) {
+    if (lens[i] < 0) return -1;
+    tiles += ((long long)lens[i] + gsv::kGroupTile - 1) / gsv::kGroupTile;       // the peak pass; an empty sentence has none
+  }
+  return (long long)n * (long long)sizeof(gsv::GroupSent) + (long long)n_groups * (long long)sizeof(gsv::RateGroup) +
+         tiles * (long long)sizeof(gsv::GroupTile);
+}
+
+namespace gsv {
+
+template <typename T, int FMT>
+static int rate_launch(bool hlds, unsigned tiles, size_t lds, hipStream_t s, const GroupSent* sent, const RateGroup* groups, int n_groups,
+                       const float* h, int L, int up, int down, void* out, int win_cap) {
+  if (hlds) GSV_LAUNCH((post_groups_rate_kernel<T, FMT, true>), dim3(tiles), dim3(256), lds, s, sent, groups, n_groups, h, L, up, down, out, win_cap);
+  else GSV_LAUNCH((post_groups_rate_kernel<T, FMT, false>), dim3(tiles), dim3(256), lds, s, sent, groups, n_groups, h, L, up, down, out, win_cap);
+  return GSV_OK;
+}
+
+template <typename T, typename... A>
+static int rate_launch_fmt(int out_fmt, A... a) {
+  switch (out_fmt) {
+    case GSV_OUT_S16: return rate_launch<T, GSV_OUT_S16>(a...);
+    case GSV_OUT_MULAW: return rate_launch<T, GSV_OUT_MULAW>(a...);
+    case GSV_OUT_ALAW: return rate_launch<T, GSV_OUT_ALAW>(a...);
+    default: return rate_launch<T, GSV_OUT_F32>(a...);
+  }
+}
+
+}  // namespace gsv
+
+extern "C" int gsv_postprocess_groups_rate(const void* const* frags, const int* lens, int n, int dtype, const int* group_n,
+                                           const int* group_gap, int n_groups, void* out, long long* group_off, void* table,
+                                           void* workspace, const float* h, int h_len, int up, int down, int out_fmt,
+                                           gsv_stream_t stream) {
+  using namespace gsv;
+  GSV_REQUIRE(n >= 0 && n_groups >= 0 && (dtype == GSV_F16 || dtype == GSV_F32), "postprocess_groups_rate: bad argument");
+  GSV_REQUIRE(out_fmt == GSV_OUT_S16 || out_fmt == GSV_OUT_MULAW || out_fmt == GSV_OUT_ALAW || out_fmt == GSV_OUT_F32,
+              "postprocess_groups_rate: out_fmt = %d is none of GSV_OUT_S16, _MULAW, _ALAW, _F32", out_fmt);
+  GSV_REQUIRE(up >= 1 && down >= 1, "postprocess_groups_rate: up = %d, down = %d (both >= 1)", up, down);
+  GSV_REQUIRE(h_len >= 1 && (h_len & 1), "postprocess_groups_rate: h_len = %d must be odd (the filter is centred)", h_len);
+  GSV_REQUIRE(h_len <= kRsMaxFilter, "postprocess_groups_rate: h_len = %d, the kernel takes filters up to %d taps", h_len, kRsMaxFilter);
+  const long long win = rs_window(kRsTile, up, down, h_len);
+  GSV_REQUIRE(win <= kRsLdsFloats, "postprocess_groups_rate: %d -> %d with %d taps needs an input window of %lld samples per tile, "
+              "the kernel holds %d", down, up, h_len, win, kRsLdsFloats);
+  GSV_REQUIRE(n_groups == 0 || (group_n && group_gap && group_off), "postprocess_groups_rate: null group table");
+  long long in_groups = 0;
+  for (int g = 0; g < n_groups; ++g) {
+    GSV_REQUIRE(group_n[g] >= 0 && group_gap[g] >= 0, "postprocess_groups_rate: group %d has %d sentences, gap %d", g, group_n[g], group_gap[g]);
+    in_groups += group_n[g];
+  }
+  GSV_REQUIRE(in_groups == n, "postprocess_groups_rate: the groups hold %lld sentences, n is %d", in_groups, n);
+  if (n == 0) {
+    for (int g = 0; g <= n_groups && group_off; ++g) group_off[g] = 0;
+    return GSV_OK;
+  }
+  GSV_REQUIRE(frags && lens && out && table && workspace && h, "postprocess_groups_rate: null pointer");
+  GroupSent* sent = (GroupSent*)table;
+  RateGroup* groups = (RateGroup*)(sent + n);
+  GroupTile* tiles = (GroupTile*)(groups + n_groups);
+  long long off = 0, n_peak = 0, n_tiles = 0;
+  int i = 0;
+  for (int g = 0; g < n_groups; ++g) {
+    group_off[g] = off;
+    const int sent0 = i;
+    long long at = 0;                                                    // position in the group's stream
+    for (int k = 0; k < group_n[g]; ++k, ++i) {
+      GSV_REQUIRE(lens[i] >= 0 && (lens[i] == 0 || frags[i]), "postprocess_groups_rate: sentence %d is null", i);
+      sent[i] = GroupSent{frags[i], at, lens[i], group_gap[g], 0u, 0};
+      for (long long t = 0; t * kGroupTile < lens[i]; ++t) tiles[n_peak++] = GroupTile{i, (int)(t * kGroupTile)};
+      at += (long long)lens[i] + group_gap[g];
+    }
+    const long long m = (at * up + down - 1) / down;
+    GSV_REQUIRE(at <= 0x7fffffffLL && m <= 0x7fffffffLL, "postprocess_groups_rate: group %d has %lld samples, %lld outputs", g, at, m);
+    GSV_REQUIRE(n_tiles <= 0x7fffffffLL, "postprocess_groups_rate: %lld tiles are too many for one launch", n_tiles);
+    groups[g] = RateGroup{off, at, sent0, group_n[g], (int)m, (int)n_tiles};
+    n_tiles += (m + kRsTile - 1) / kRsTile;
+    off += m;
+  }
+  group_off[n_groups] = off;
+  GSV_REQUIRE(n_peak <= 0x7fffffffLL && n_tiles <= 0x7fffffffLL, "postprocess_groups_rate: %lld tiles are too many for one launch",
+              n_peak > n_tiles ? n_peak : n_tiles);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t bytes = (size_t)n * sizeof(GroupSent) + (size_t)n_groups * sizeof(RateGroup) + (size_t)n_peak * sizeof(GroupTile);
+  GSV_HIP(hipMemcpyAsync(workspace, table, bytes, hipMemcpyHostToDevice, s));
+  GroupSent* dsent = (GroupSent*)workspace;
+  const RateGroup* dgroups = (const RateGroup*)(dsent + n);
+  const GroupTile* dtiles = (const GroupTile*)(dgroups + n_groups);
+  if (n_peak) {
+    if (dtype == GSV_F16) GSV_LAUNCH((post_groups_peak_kernel<_Float16>), dim3((unsigned)n_peak), dim3(256), 0, s, dsent, dtiles);
+    else GSV_LAUNCH((post_groups_peak_kernel<float>), dim3((unsigned)n_peak), dim3(256), 0, s, dsent, dtiles);
+  }
+  if (n_tiles == 0) return GSV_OK;
+  const int win_cap = (int)win, h_at = win_cap > kRsTile ? win_cap : kRsTile;
+  const bool hlds = (long long)h_at + h_len <= kRsLdsFloats;
+  const size_t lds = sizeof(float) * (size_t)(h_at + (hlds ? h_len : 0));
+  if (dtype == GSV_F16)
+    return rate_launch_fmt<_Float16>(out_fmt, hlds, (unsigned)n_tiles, lds, s, (const GroupSent*)dsent, dgroups, n_groups, h, h_len, up, down,
+                                     out, win_cap);
+  return rate_launch_fmt<float>(out_fmt, hlds, (unsigned)n_tiles, lds, s, (const GroupSent*)dsent, dgroups, n_groups, h, h_len, up, down, out,
+                                win_cap);
 }

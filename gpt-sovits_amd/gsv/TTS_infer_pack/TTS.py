@@ -936,12 +936,18 @@ class TTS:
 
     def audio_postprocess(self, audio: List[List[torch.Tensor]], sr: int, batch_index_list: Optional[list] = None,
                           speed_factor: float = 1.0, split_bucket: bool = True, fragment_interval: float = 0.3,
-                          super_sampling: bool = False) -> Tuple[int, np.ndarray]:
+                          super_sampling: bool = False, sample_rate: Optional[int] = None,
+                          encoding: Optional[str] = None) -> Tuple[int, np.ndarray]:
         """TTS.py:1377-1429: per fragment divide by its peak if the peak exceeds 1, append
         int(sr*interval) zeros, restore order, concatenate, scale by 32768 and truncate to int16.
 
         super_sampling (TTS.py:1407-1417): the same concatenation as fp32 (gsv_postprocess_f32), AP_BWE to 48 kHz, then the
-        peak rule and int16 step of gsv_postprocess on that one fragment without a gap; returns 48000."""
+        peak rule and int16 step of gsv_postprocess on that one fragment without a gap; returns 48000.
+
+        sample_rate / encoding (None: the launches above, unchanged): the same normalised concatenation
+        resampled to `sample_rate` and written as int16 ("pcm_s16", saturating) or as G.711 bytes ("mulaw", "alaw") by one
+        gsv_postprocess_groups_rate call -- the sentences in recovered order are one group; with super_sampling the 48 kHz
+        AP_BWE result is the one sentence of a group without a gap -- and one copy; returns (sample_rate, int16 or uint8)."""
         import ctypes as C
         from .. import _lib
         dev = torch.device(self.configs.device)
@@ -966,22 +972,71 @@ class TTS:
                            "gsv_postprocess_f32")
                 hr = self.sr_model.forward_device(wav, sr)
                 sr = self.sr_model.config["hr_sampling_rate"]
+                if sample_rate is not None or encoding is not None:
+                    return self._postprocess_rate([([hr.view(-1)], 0)], sr, sample_rate, encoding)[:2]
                 pcm = torch.empty(int(hr.shape[0]), dtype=torch.int16, device=dev)
                 one_p, one_n = (C.c_void_p * 1)(hr.data_ptr()), (C.c_int * 1)(int(hr.shape[0]))
                 _lib.check(_lib.lib().gsv_postprocess(one_p, one_n, 1, _lib.GSV_F32, 0, pcm.data_ptr(), C.c_void_p(st.cuda_stream)),
                            "gsv_postprocess")
                 return sr, self._to_host(pcm)
+            if sample_rate is not None or encoding is not None:
+                return self._postprocess_rate([(flat, gap)], sr, sample_rate, encoding)[:2]
             pcm = torch.empty(sum(lens) + gap * len(lens), dtype=torch.int16, device=dev)
             _lib.check(_lib.lib().gsv_postprocess(ptrs, arr, len(flat), code, gap, pcm.data_ptr(), C.c_void_p(st.cuda_stream)),
                        "gsv_postprocess")
         return sr, self._to_host(pcm)
 
-    def postprocess_fragments(self, groups: Sequence[Tuple[Sequence[torch.Tensor], float]]) -> List[np.ndarray]:
+    def _postprocess_rate(self, groups: Sequence[Tuple[Sequence[torch.Tensor], int]], sr: int, sample_rate: Optional[int],
+                          encoding: Optional[str]) -> Tuple[int, np.ndarray, List[int]]:
+        """One gsv_postprocess_groups_rate call (csrc/sola.hip) and one device-to-host copy: groups[g] =
+        (its sentences, 1-D device tensors of one dtype, fp16 or fp32; its gap in samples at `sr`) -> (the output rate, all
+        groups packed, int16 or uint8; the n_groups + 1 offsets of the groups in it).  sample_rate None is `sr` (the identity
+        filter), encoding None is "pcm_s16".  The table and the workspace are the pipeline's, as in postprocess_fragments."""
+        import ctypes as C
+        from .. import _lib, audio_io
+        dev = torch.device(self.configs.device)
+        sr_out = int(sr) if sample_rate is None else int(sample_rate)
+        fmt = audio_io.ENCODINGS["pcm_s16" if encoding is None else encoding]
+        if not audio_io.output_rate_supported(sr, sr_out):
+            raise ValueError(f"sample_rate {sr_out}: the resampling kernel does not take {sr} -> {sr_out}")
+        flat = [f for frags, _ in groups for f in frags]
+        counts, gaps = [len(frags) for frags, _ in groups], [int(g) for _, g in groups]
+        n, code = len(flat), _lib.dtype_code(flat[0].dtype if flat else self.precision)
+        lens = (C.c_int * max(n, 1))(*[int(f.shape[0]) for f in flat])
+        ptrs = (C.c_void_p * max(n, 1))(*[f.data_ptr() for f in flat])
+        group_n, group_gap = (C.c_int * len(groups))(*counts), (C.c_int * len(groups))(*gaps)
+        off = (C.c_longlong * (len(groups) + 1))()
+        l = _lib.lib()
+        need = int(l.gsv_postprocess_groups_rate_workspace(lens, n, len(groups)))
+        if need < 0:
+            raise RuntimeError("gsv_postprocess_groups_rate_workspace: bad lengths")
+        with torch.cuda.device(dev):
+            ws = getattr(self, "_post_groups_ws", None)
+            if ws is None or ws[0].numel() < need:
+                size = max(1 << 16, 2 * need)
+                ws = self._post_groups_ws = (torch.empty(size, dtype=torch.uint8).pin_memory(),
+                                             torch.empty(size, dtype=torch.uint8, device=dev))
+            hd, up, down = audio_io.output_filter_device(sr, sr_out, dev)
+            total = sum(audio_io.resampled_len(sum(int(f.shape[0]) for f in frags) + len(frags) * g, sr, sr_out)
+                        for (frags, _), g in zip(groups, gaps))
+            out = torch.empty(max(total, 1), dtype=torch.int16 if fmt == _lib.GSV_OUT_S16 else torch.uint8, device=dev)
+            st = torch.cuda.current_stream(dev)
+            _lib.check(l.gsv_postprocess_groups_rate(ptrs, lens, n, code, group_n, group_gap, len(groups), out.data_ptr(), off,
+                                                     ws[0].data_ptr(), ws[1].data_ptr(), hd.data_ptr(), int(hd.numel()), up, down,
+                                                     fmt, C.c_void_p(st.cuda_stream)), "gsv_postprocess_groups_rate")
+            host = self._to_host(out)                                   # waits for the stream: `flat` and the table are done with
+        assert int(off[len(groups)]) == total
+        return sr_out, host[:total], [int(v) for v in off]
+
+    def postprocess_fragments(self, groups: Sequence[Tuple[Sequence[torch.Tensor], float]], sample_rate: Optional[int] = None,
+                              encoding: Optional[str] = None) -> List[np.ndarray]:
         """audio_postprocess([frags], sr, None, speed, False, fragment_interval) of several fragments in ONE launch pair and
         ONE device-to-host copy (`gsv_postprocess_groups`, csrc/sola.hip): groups[g] = (the sentences of one fragment, its
         fragment_interval) -> the int16 audio of each, what audio_postprocess returns for it alone (super_sampling is not
         handled here: AP-BWE runs per fragment).  The table and the workspace are kept on the pipeline and grow on demand;
-        the call waits for its copy, so the next call may rewrite them."""
+        the call waits for its copy, so the next call may rewrite them.
+        sample_rate / encoding (None: the launches above, unchanged): every fragment at that rate and in that encoding, as
+        audio_postprocess gives it with the same keywords, from ONE gsv_postprocess_groups_rate call; int16 or uint8."""
         import ctypes as C
         from .. import _lib
         dev = torch.device(self.configs.device)
@@ -989,6 +1044,11 @@ class TTS:
             raise RuntimeError("postprocess_fragments is a HIP kernel (gsv_postprocess_groups); there is no CPU path")
         if not groups:
             return []
+        if sample_rate is not None or encoding is not None:
+            rated = [([f.to(dev, self.precision).contiguous().view(-1) for f in frags], int(self.configs.sampling_rate * interval))
+                     for frags, interval in groups]
+            _, host, off = self._postprocess_rate(rated, self._output_sr(), sample_rate, encoding)
+            return [host[off[g]:off[g + 1]].copy() for g in range(len(groups))]
         flat = [f.to(dev, self.precision).contiguous().view(-1) for frags, _ in groups for f in frags]
         gaps = [int(self.configs.sampling_rate * interval) for _, interval in groups]
         counts = [len(frags) for frags, _ in groups]
@@ -1547,7 +1607,9 @@ class TTS:
         "lora_voice" (a name given to add_lora_voice) is carried only when the request names one: absent or None is the base
         model, and the options of such a request are the ones they were (read it with o.get("lora_voice")).  "best_of"
         (candidates per sentence) likewise only when the request names one other than 1, as given, with
-        its "best_of_score" callable if it brings one: _resolve_options checks both."""
+        its "best_of_score" callable if it brings one: _resolve_options checks both.  "sample_rate" (int, Hz) and "encoding"
+        ("pcm_s16", "mulaw", "alaw") are checked and carried only when the request gives them: a rate
+        that is no positive int and an unknown encoding raise ValueError."""
         o = dict(top_k=req.get("top_k", 5), top_p=req.get("top_p", 1), temperature=req.get("temperature", 1),
                  batch_size=req.get("batch_size", 1), batch_threshold=req.get("batch_threshold", 0.75),
                  speed_factor=req.get("speed_factor", 1.0), split_bucket=req.get("split_bucket", True),
@@ -1566,14 +1628,32 @@ class TTS:
             o["best_of"] = n
             if req.get("best_of_score") is not None:
                 o["best_of_score"] = req["best_of_score"]
+        if req.get("sample_rate") is not None:
+            rate = req["sample_rate"]
+            if type(rate) is not int or rate <= 0:
+                raise ValueError(f"sample_rate {rate!r}: a positive int, in Hz")
+            o["sample_rate"] = rate
+        if req.get("encoding") is not None:
+            from ..audio_io import ENCODINGS
+            if req["encoding"] not in ENCODINGS:
+                raise ValueError(f"encoding {req['encoding']!r}: one of {', '.join(sorted(ENCODINGS))}")
+            o["encoding"] = req["encoding"]
         return o
+
+    @staticmethod
+    def _format_kw(o: dict) -> dict:
+        """the output-format keywords of audio_postprocess for resolved options: only the ones the request kept"""
+        return {k: o[k] for k in ("sample_rate", "encoding") if k in o}
 
     def _resolve_options(self, req: dict) -> dict:
         """_request_options(req) under the rules of the loaded model, what run() and run_batch work from: fragments, another
         speed and v3 / v4 parallel runs are never bucketed (reference TTS.py:1048-1062), and AP_BWE super-sampling applies to
         the v3 vocoder output only -- v1 / v2 / v2Pro / v4 ignore the key (TTS.py:1040, 1328, 1349).  A "lora_voice" that was
         not added raises ValueError here, before any GPU work, and so does a "best_of" that is no int in 1..16 or that comes
-        with parallel_infer=False (check_best_of; the prompt-free case is refused as soon as the voice is known)."""
+        with parallel_infer=False (check_best_of; the prompt-free case is refused as soon as the voice is known).  A
+        "sample_rate" equal to the rate the request leaves at anyway (the model's, 48 kHz under super_sampling) and the
+        encoding "pcm_s16" are dropped: such a request takes the default launches.  A rate the resampling kernel does not take
+        from the model's raises ValueError here.  _output_sr() is asked only when the request names a rate."""
         o = self._request_options(req)
         check_best_of(o)
         if "lora_voice" in o:
@@ -1581,6 +1661,19 @@ class TTS:
         if o["return_fragment"] or o["speed_factor"] != 1.0 or (self.configs.use_vocoder and o["parallel_infer"]):
             o["split_bucket"] = False
         o["super_sampling"] = o["super_sampling"] and self.configs.use_vocoder and self.configs.version == "v3"
+        if o.get("encoding") == "pcm_s16":
+            del o["encoding"]
+        if "sample_rate" in o:
+            from ..audio_io import output_rate_supported
+            sr = self._output_sr()
+            if o["super_sampling"]:
+                self.init_sr_model()
+                sr = self.sr_model.config["hr_sampling_rate"]
+            if o["sample_rate"] == sr:
+                del o["sample_rate"]
+            elif not output_rate_supported(sr, o["sample_rate"]):
+                raise ValueError(f"sample_rate {o['sample_rate']}: the resampling kernel does not take {sr} -> {o['sample_rate']} "
+                                 "(its filter or its input window per tile is too large)")
         return o
 
     def plan_batch(self, plans: List[dict], mixed_sampling: bool = False, mixed_limits: bool = False) -> List[List[dict]]:
@@ -2072,7 +2165,7 @@ class TTS:
                                                              voice_refer, have=pl["frags"][bi])
             self._wait_stream()
             return self.audio_postprocess(pl["frags"], sr, pl["index"], o["speed_factor"], o["split_bucket"],
-                                          o["fragment_interval"], o["super_sampling"])
+                                          o["fragment_interval"], o["super_sampling"], **self._format_kw(o))
 
     def _output_sr(self) -> int:
         """the rate of the waveform stage: the SoVITS model's, v3 / v4 the vocoder's (which must be loaded)"""
@@ -2225,7 +2318,7 @@ class TTS:
                 t_45 += t5 - t4
                 if o["return_fragment"]:
                     yield self.audio_postprocess([frags], sr, None, o["speed_factor"], False, o["fragment_interval"],
-                                                 o["super_sampling"])
+                                                 o["super_sampling"], **self._format_kw(o))
                 else:
                     audio.append(frags)
                 if self.stop_flag:
@@ -2238,7 +2331,7 @@ class TTS:
                     return
                 t6 = time.perf_counter()
                 result = self.audio_postprocess(audio, sr, batch_index_list, o["speed_factor"], o["split_bucket"],
-                                                o["fragment_interval"], o["super_sampling"])
+                                                o["fragment_interval"], o["super_sampling"], **self._format_kw(o))
                 self.last_postprocess_s = time.perf_counter() - t6
                 yield result
         except Exception as e:

@@ -9,6 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libgsv_hip.so")
 
 GSV_F32, GSV_F16 = 0, 1
+GSV_OUT_S16, GSV_OUT_MULAW, GSV_OUT_ALAW, GSV_OUT_F32 = 0, 1, 2, 3   # out_fmt of gsv_postprocess_groups_rate
 
 
 class T2SConfig(C.Structure):
@@ -188,6 +189,10 @@ _SIGS = {
     "gsv_postprocess_groups": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int),
                                          C.POINTER(C.c_int), C.c_int, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
+    "gsv_postprocess_groups_rate_workspace": (C.c_longlong, [C.POINTER(C.c_int), C.c_int, C.c_int]),
+    "gsv_postprocess_groups_rate": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int),
+                                              C.POINTER(C.c_int), C.c_int, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "gsv_bwe_create": (C.c_int, [C.POINTER(BweConfig), C.c_int, C.POINTER(C.c_void_p)]),
     "gsv_bwe_destroy": (None, [C.c_void_p]),
     "gsv_bwe_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),

@@ -134,3 +134,67 @@ def device_resample_supported(sr_in: int, sr_out: int) -> bool:
     """whether gsv_op_resample_poly_seg takes this pair (include/gsv.h: its filter and its input window per tile fit the kernel)"""
     h, up, down = resample_filter(sr_in, sr_out)
     return len(h) <= RS_MAX_FILTER and ((RS_TILE - 1) * down + len(h) - 1) // up + 2 <= RS_LDS_FLOATS
+
+
+# ---- the output format of a request (gsv_postprocess_groups_rate, DESIGN.md section 4u) ------------------------------------------
+ENCODINGS = {"pcm_s16": 0, "mulaw": 1, "alaw": 2}   # include/gsv.h: GSV_OUT_S16, GSV_OUT_MULAW, GSV_OUT_ALAW
+
+
+def output_rate_supported(sr_in: int, sr_out: int) -> bool:
+    """whether gsv_postprocess_groups_rate takes a model at sr_in to sr_out: the same rate (the identity filter), or a pair whose
+    filter and input window per tile fit the kernel, the limits of gsv_op_resample_poly_seg"""
+    if int(sr_in) <= 0 or int(sr_out) <= 0:
+        return False
+    return int(sr_in) == int(sr_out) or device_resample_supported(sr_in, sr_out)
+
+
+def output_filter(sr_in: int, sr_out: int) -> Tuple[np.ndarray, int, int]:
+    """-> (h float32 [L], up, down) of gsv_postprocess_groups_rate: resample_filter, or {1.0}, 1, 1 at the same rate"""
+    if int(sr_in) == int(sr_out):
+        return np.ones(1, dtype=np.float32), 1, 1
+    return resample_filter(sr_in, sr_out)
+
+
+def output_filter_device(sr_in: int, sr_out: int, dev):
+    """output_filter with the filter on `dev`, cached per rate pair and device"""
+    import torch
+    h, up, down = output_filter(sr_in, sr_out)
+    key = (int(sr_in), int(sr_out), str(dev))
+    if key not in _filters_dev:
+        _filters_dev[key] = torch.from_numpy(h).to(dev)
+    return _filters_dev[key], up, down
+
+
+def convert_pcm(pcm: np.ndarray, sr_in: int, sr_out: int, encoding: Optional[str] = None, device="cuda:0") -> np.ndarray:
+    """int16 audio at sr_in -> the same audio at sr_out as int16 ("pcm_s16", None) or G.711 bytes ("mulaw", "alaw"), through
+    one gsv_postprocess_groups_rate call on pcm / 32768 (exact in fp32, peak <= 1: nothing is normalised)."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    if encoding is not None and encoding not in ENCODINGS:
+        raise ValueError(f"encoding {encoding!r}: one of {', '.join(sorted(ENCODINGS))}")
+    if not output_rate_supported(sr_in, sr_out):
+        raise ValueError(f"sample_rate {sr_out}: the resampling kernel does not take {sr_in} -> {sr_out}")
+    fmt = ENCODINGS[encoding or "pcm_s16"]
+    dev = torch.device(device)
+    n = int(pcm.shape[0])
+    if n == 0:
+        return np.zeros(0, dtype=np.int16 if fmt == 0 else np.uint8)
+    with torch.cuda.device(dev):
+        _lib.init(dev.index if dev.index is not None else torch.cuda.current_device())
+        x = torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.int16)).to(dev).to(torch.float32) / 32768.0
+        hd, up, down = output_filter_device(sr_in, sr_out, dev)
+        lens, ptrs, one, gap = (C.c_int * 1)(n), (C.c_void_p * 1)(x.data_ptr()), (C.c_int * 1)(1), (C.c_int * 1)(0)
+        off = (C.c_longlong * 2)()
+        l = _lib.lib()
+        need = int(l.gsv_postprocess_groups_rate_workspace(lens, 1, 1))
+        table = torch.empty(need, dtype=torch.uint8).pin_memory()
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+        out = torch.empty(resampled_len(n, sr_in, sr_out), dtype=torch.int16 if fmt == 0 else torch.uint8, device=dev)
+        st = torch.cuda.current_stream(dev)
+        _lib.check(l.gsv_postprocess_groups_rate(ptrs, lens, 1, _lib.GSV_F32, one, gap, 1, out.data_ptr(), off, table.data_ptr(),
+                                                 work.data_ptr(), hd.data_ptr(), int(hd.numel()), up, down, fmt,
+                                                 C.c_void_p(st.cuda_stream)), "gsv_postprocess_groups_rate")
+        return out.cpu().numpy()                       # waits for the stream: the table is done with

@@ -160,7 +160,7 @@ class _SymbolAny:
 
 def synthesize(GPT_model_path, SoVITS_model_path, ref_audio_path, ref_text_path, ref_language, target_text_path,
                target_language, output_path, bert_path=None, cnhubert_base_path=None, gpu_number="0", is_half=True,
-               frontend=None):
+               frontend=None, sample_rate=None):
     if frontend is None:
         raise ValueError("pass `frontend` (an object, or a --frontend string for make_frontend): the reference's G2P "
                          "packages are third-party and not part of this build (see the module docstring)")
@@ -190,6 +190,9 @@ def synthesize(GPT_model_path, SoVITS_model_path, ref_audio_path, ref_text_path,
                               max_sec=s1["config"]["data"]["max_sec"]))
     if result:
         sr, audio = result[-1]
+        if sample_rate is not None and int(sample_rate) != sr:       # --sample_rate: resampled on the device
+            from .audio_io import convert_pcm
+            audio, sr = convert_pcm(audio, sr, int(sample_rate), device=device), int(sample_rate)
         os.makedirs(output_path, exist_ok=True)
         out = os.path.join(output_path, "output.wav")
         with wave.open(out, "wb") as w:            # 16-bit PCM, what soundfile.write produces for int16 (inference_cli.py:95-96)
@@ -218,10 +221,14 @@ def main(argv=None):
     p.add_argument("--frontend", default=os.environ.get("GSV_FRONTEND", "symbols"),
                    help="text front-end: 'symbols' (text files hold phoneme symbols), 'cmudict:<file>' (English dictionary G2P) "
                         "or 'pkg.module:factory' (default: $GSV_FRONTEND or 'symbols')")
+    p.add_argument("--sample_rate", type=int, default=None,
+                   help="sample rate of output.wav in Hz (an addition to the reference's flags; default: the model's, 32000)")
     a = p.parse_args(argv)
+    if a.sample_rate is not None and a.sample_rate <= 0:
+        p.error("--sample_rate must be positive")
     synthesize(a.gpt_model, a.sovits_model, a.ref_audio, a.ref_text, a.ref_language, a.target_text, a.target_language,
                a.output_path, a.bert_path, a.cnhubert_base_path, a.gpu_number, str(a.is_half).lower() in ("true", "1"),
-               frontend=a.frontend)
+               frontend=a.frontend, sample_rate=a.sample_rate)
 
 
 if __name__ == "__main__":

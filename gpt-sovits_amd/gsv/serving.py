@@ -849,7 +849,9 @@ class Scheduler:
         """the fragments that are due -- folds of streaming requests whose audio exists (a fold no shared stage took goes
         through _synthesize_batch here, as in _finish_request), per request in fold order -- are what run() yields for them,
         audio_postprocess([frags], ...), all through ONE postprocess_fragments call (super_sampling fragments:
-        audio_postprocess each, AP-BWE runs per fragment).  A request of `ends`, whose last fragment is among them, gets the
+        audio_postprocess each, AP-BWE runs per fragment).  Fragments whose requests name an output format ("sample_rate",
+        "encoding") are grouped by it: one postprocess_fragments call, that is one gsv_postprocess_groups_rate launch pair, per
+        format, the default format as before.  A request of `ends`, whose last fragment is among them, gets the
         list of all of them as its result.  -> the fragments emitted"""
         tts = self.tts
         got: Dict[Tuple[int, int], Any] = {}
@@ -868,21 +870,28 @@ class Scheduler:
                 if o["super_sampling"]:
                     tts._wait_stream()
                     got[(t, b)] = tts.audio_postprocess([pl["frags"][b]], tts._output_sr(), None, o["speed_factor"], False,
-                                                        o["fragment_interval"], True)
+                                                        o["fragment_interval"], True, **tts._format_kw(o))
                 else:
                     batch.append((t, b))
             except Exception as e:                                      # noqa: BLE001 -- the request's own result
                 self._fail([t], e)
-        batch = [(t, b) for t, b in batch if t in self._requests]
-        try:
-            if batch:
-                tts._wait_stream()
-                sr = tts._output_sr()
-                audios = tts.postprocess_fragments([(self._requests[t]["frags"][b], self._requests[t]["opts"]["fragment_interval"])
-                                                    for t, b in batch])
-                got.update({f: (sr, a) for f, a in zip(batch, audios)})
-        except Exception as e:                                          # noqa: BLE001 -- the requests of this launch
-            self._fail(sorted({t for t, _ in batch}), e)
+        classes: Dict[Tuple[Optional[int], Optional[str]], List[Tuple[int, int]]] = {}
+        for t, b in batch:
+            if t in self._requests:
+                o = self._requests[t]["opts"]
+                classes.setdefault((o.get("sample_rate"), o.get("encoding")), []).append((t, b))
+        for (rate, enc), batch in classes.items():
+            batch = [(t, b) for t, b in batch if t in self._requests]   # a class before this one may have failed its requests
+            try:
+                if batch:
+                    tts._wait_stream()
+                    sr = tts._output_sr()
+                    kw = {k: v for k, v in (("sample_rate", rate), ("encoding", enc)) if v is not None}
+                    audios = tts.postprocess_fragments([(self._requests[t]["frags"][b], self._requests[t]["opts"]["fragment_interval"])
+                                                        for t, b in batch], **kw)
+                    got.update({f: (sr if rate is None else rate, a) for f, a in zip(batch, audios)})
+            except Exception as e:                                      # noqa: BLE001 -- the requests of this launch
+                self._fail(sorted({t for t, _ in batch}), e)
         emitted = [f for f in due if f[0] in self._requests]
         for t, b in emitted:
             pl = self._requests[t]

@@ -161,6 +161,16 @@ def place_pieces(pieces, batches: List[List[int]], n_segments: int, dev: torch.d
     return result.numpy()
 
 
+def refuse_output_format(segments: Optional[List[dict]]) -> None:
+    """A sharded run gathers int16 fragments by `last_fragment_lengths`, which are counted at the model's own rate: the request
+    keys "sample_rate" and "encoding"  are refused here instead of being dropped on the way."""
+    for s in segments or []:
+        for k in ("sample_rate", "encoding"):
+            if s.get(k) is not None:
+                raise ValueError(f"a sharded run does not take {k!r}: its gather works on int16 fragments at the model's rate "
+                                 "(convert the gathered audio, or run unsharded)")
+
+
 class ShardedSynthesizer:
     """`synth(segments) -> (int16 1-D numpy array or device tensor, per-fragment sample counts in the order of `segments`)`
     is the local engine call (the TTS wrapper in production, a stub in the gloo tests)."""
@@ -261,6 +271,7 @@ class ShardedSynthesizer:
         text); on the other ranks yields nothing but must be iterated to the end.
         A failure anywhere (rank 0's own batch included) is raised on rank 0 AFTER every outstanding batch of the other
         ranks has been received, so that no rank is left waiting in a send."""
+        refuse_output_format(segments)                     # rank 0 holds them, before any collective
         self._job += 1
         job = self._job
         self.last_synth_s = 0.0
@@ -348,6 +359,7 @@ class ShardedSynthesizer:
         Every rank synthesises the batches it claims and keeps the int16 result on its GPU; when its queue is empty it sends
         ONE record to rank 0 over the device group (RCCL point to point over xGMI: sizes, then fragment table, then samples),
         i.e. the gather happens when no decode engine is running on the sender and rank 0 has finished its own work."""
+        refuse_output_format(segments)
         if batch_size is None:
             n = len(segments) if self.rank == 0 else 0
             if self.world > 1:

@@ -19,7 +19,8 @@ import numpy as np
 
 
 def pack_raw(io_buffer: BytesIO, data: np.ndarray, rate: int) -> BytesIO:
-    """api_v2.py:182-184: the samples' bytes as they are (int16 little endian from the path)."""
+    """api_v2.py:182-184: the samples' bytes as they are (int16 little endian from the path; one byte per sample, uint8, for
+    a request with a G.711 "encoding")."""
     io_buffer.write(data.tobytes())
     return io_buffer
 
@@ -44,7 +45,10 @@ def pack_wav(io_buffer: BytesIO, data: np.ndarray, rate: int) -> BytesIO:
 
 
 def pack_audio(io_buffer: BytesIO, data: np.ndarray, rate: int, media_type: str) -> BytesIO:
-    """api_v2.py:223-233: dispatch on media type, anything unknown is raw; the buffer is rewound."""
+    """api_v2.py:223-233: dispatch on media type, anything unknown is raw; the buffer is rewound.  G.711 bytes (uint8: a
+    request with "encoding" mulaw / alaw) leave as raw only: the containers here hold PCM."""
+    if data.dtype == np.uint8 and media_type in ("wav", "aac", "ogg"):
+        raise ValueError(G711_NEEDS_RAW % media_type)
     if media_type == "ogg":
         raise NotImplementedError("media_type 'ogg' needs libsndfile (the `soundfile` package, api_v2.py:176-179), which is not "
                                   "installed; request 'wav', 'raw' or 'aac'")
@@ -56,6 +60,9 @@ def pack_audio(io_buffer: BytesIO, data: np.ndarray, rate: int, media_type: str)
         io_buffer = pack_raw(io_buffer, data, rate)
     io_buffer.seek(0)
     return io_buffer
+
+
+G711_NEEDS_RAW = "media_type '%s' holds PCM: a request with encoding 'mulaw' or 'alaw' needs media_type 'raw'"
 
 
 def pack_aac(io_buffer: BytesIO, data: np.ndarray, rate: int) -> BytesIO:
@@ -99,6 +106,8 @@ def tts_handle(tts_pipeline, req: dict, server=None):
     return_fragment request that is not streamed, hand back the list of fragments at the end."""
     streaming_mode = req.get("streaming_mode", False)
     media_type = req.get("media_type", "wav")
+    if req.get("encoding") in ("mulaw", "alaw") and media_type in ("wav", "aac", "ogg"):     # before any stage runs
+        return 400, "application/json", {"message": "tts failed", "Exception": G711_NEEDS_RAW % media_type}
     if streaming_mode or req.get("return_fragment", False):
         req = dict(req, return_fragment=True)
     try:
@@ -140,7 +149,7 @@ def create_app(tts_pipeline, server=None):
 
     async def tts_get(request):
         q = dict(request.query_params)
-        for k in ("top_k", "batch_size", "seed", "sample_steps"):
+        for k in ("top_k", "batch_size", "seed", "sample_steps", "sample_rate"):
             if k in q:
                 q[k] = int(q[k])
         for k in ("top_p", "temperature", "batch_threshold", "speed_factor", "fragment_interval", "repetition_penalty",

@@ -517,6 +517,33 @@ int gsv_postprocess_f32(const void* const* frags, const int* lens, int n, int dt
 long long gsv_postprocess_groups_workspace(const int* lens, int n);
 int gsv_postprocess_groups(const void* const* frags, const int* lens, int n, int dtype, const int* group_n, const int* group_gap,
                            int n_groups, int16_t* out, long long* group_off, void* table, void* workspace, gsv_stream_t stream);
+/* gsv_postprocess_groups at another sample rate and in another encoding.  Per group g with sentences
+ * x_0 .. x_{k-1} and gap G:
+ *   stream    X_g = concat_i [norm(x_i), G zeros], N_g = sum(len_i + G) samples: what gsv_postprocess_f32 writes for that group
+ *             alone (the peak rule, with the division in the fragments' dtype), never materialised;
+ *   resample  Y_g[i] = sum_j h[i * down + half - j * up] * X_g[j],  j in [0, N_g) with the filter index in [0, h_len),
+ *             h_len = 2 * half + 1, i in [0, m_g), m_g = ceil(N_g * up / down): the arithmetic of gsv_op_resample_poly_seg (one fp32
+ *             accumulator per output, fmaf over its taps in ascending j), zeros beyond the group's ends, so an output's bits
+ *             depend on its own group's samples alone;
+ *   format    GSV_OUT_S16: y * 32768 in fp32, clamped to [-32768, 32767] and truncated toward zero (a resampled signal overshoots
+ *             its input's peak, so this path saturates instead of wrapping); GSV_OUT_MULAW / GSV_OUT_ALAW: ITU-T G.711 of that
+ *             int16, one byte per sample (the bytes of Python's audioop.lin2ulaw / lin2alaw at width 2); GSV_OUT_F32: y.
+ * h [dev] fp32: the filter, as gsv.audio_io.resample_filter designs it; up = down = 1 with h = {1.0f} applies an encoding at the
+ * model's own rate.  out [dev]: one packed buffer of int16, bytes or floats; group g starts at output sample group_off[g]
+ * ([host], n_groups + 1 entries, written by the call; the last one is the capacity out needs).  A group without sentences writes
+ * nothing; outputs whose taps touch a NaN are unspecified.  table [host] and workspace [dev]:
+ * gsv_postprocess_groups_rate_workspace(lens, n, n_groups) bytes each (-1: a negative length or count); filled, uploaded and kept
+ * as for gsv_postprocess_groups, nothing is allocated.  Two launches: the peaks (the kernel of gsv_postprocess_groups), then one
+ * workgroup per 1024 consecutive outputs of a group.  Refused with a message: an even h_len, one above 65535, and a pair whose
+ * input window per 1024 outputs, (1023 * down + h_len - 1) / up + 2 samples, exceeds 16384. */
+#define GSV_OUT_S16 0
+#define GSV_OUT_MULAW 1
+#define GSV_OUT_ALAW 2
+#define GSV_OUT_F32 3
+long long gsv_postprocess_groups_rate_workspace(const int* lens, int n, int n_groups);
+int gsv_postprocess_groups_rate(const void* const* frags, const int* lens, int n, int dtype, const int* group_n, const int* group_gap,
+                                int n_groups, void* out, long long* group_off, void* table, void* workspace, const float* h,
+                                int h_len, int up, int down, int out_fmt, gsv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * AP-BWE audio super-resolution (tools/audio_sr.py::AP_BWE.__call__): torchaudio resample to hr_sampling_rate

@@ -18,6 +18,7 @@ from __future__ import annotations
 import collections
 import contextlib
 import math
+import numbers
 import os
 import random
 import time
@@ -319,6 +320,9 @@ class TTS:
         self.text_preprocessor = TextPreprocessor(bert_fn=None, device="cpu")      # reference TTS.py:431-433
         self.vocoder_configs: dict = {"sr": None, "T_ref": None, "T_chunk": None, "upsample_rate": None, "overlapped_len": None}
         self._lora_voices: Dict[str, dict] = {}      # add_lora_voice: name -> {"slot", "engine", "state"}
+        # "loudness": [{"lufs", "gain_db", "gain", "limited"} per span] per fragment delivered with it by the last run() /
+        # run_batch(), or by the last audio_postprocess / postprocess_fragments call made directly (a server: its last call)
+        self.last_loudness: list = []
         self.last_candidates: list = []              # "best_of": the choices of the last run / run_batch call, [request][batch][sentence]
 
     # ---- weights (reference TTS.py:484-603) ------------------------------------------------
@@ -937,7 +941,8 @@ class TTS:
     def audio_postprocess(self, audio: List[List[torch.Tensor]], sr: int, batch_index_list: Optional[list] = None,
                           speed_factor: float = 1.0, split_bucket: bool = True, fragment_interval: float = 0.3,
                           super_sampling: bool = False, sample_rate: Optional[int] = None,
-                          encoding: Optional[str] = None) -> Tuple[int, np.ndarray]:
+                          encoding: Optional[str] = None, loudness: Optional[float] = None, loudness_scope: str = "fragment",
+                          loudness_peak: float = 0.0) -> Tuple[int, np.ndarray]:
         """TTS.py:1377-1429: per fragment divide by its peak if the peak exceeds 1, append
         int(sr*interval) zeros, restore order, concatenate, scale by 32768 and truncate to int16.
 
@@ -947,13 +952,23 @@ class TTS:
         sample_rate / encoding (None: the launches above, unchanged): the same normalised concatenation
         resampled to `sample_rate` and written as int16 ("pcm_s16", saturating) or as G.711 bytes ("mulaw", "alaw") by one
         gsv_postprocess_groups_rate call -- the sentences in recovered order are one group; with super_sampling the 48 kHz
-        AP_BWE result is the one sentence of a group without a gap -- and one copy; returns (sample_rate, int16 or uint8)."""
+        AP_BWE result is the one sentence of a group without a gap -- and one copy; returns (sample_rate, int16 or uint8).
+
+        loudness (None: everything above, unchanged): a target in LUFS.  The fragment (scope "fragment":
+        the whole normalised concatenation, gaps included) or each of its sentences (scope "sentence") is metered after ITU-R
+        BS.1770 on the device and multiplied by one gain towards the target, which loudness_peak (dBFS <= 0) caps at the
+        peak.  Such a call always leaves through gsv_postprocess_groups_loud, with the identity filter when it names no other
+        rate, so its int16 saturates instead of wrapping.  With super_sampling the 48 kHz AP_BWE result is the one sentence
+        that is metered, at 48 kHz.  self.last_loudness becomes this call's reports, [[one record per span]]; it is
+        replaced, never extended, so a server that calls this per request holds the last call's only (run() and run_batch()
+        gather the reports of their own calls)."""
         import ctypes as C
         from .. import _lib
         dev = torch.device(self.configs.device)
         if dev.type != "cuda":
             raise RuntimeError("audio_postprocess is a HIP kernel (gsv_postprocess); there is no CPU path")
         gap = int(self.configs.sampling_rate * fragment_interval)
+        loud = None if loudness is None else [(loudness, loudness_scope, loudness_peak)]
         flat = self.recovery_order(audio, batch_index_list) if split_bucket else [f for b in audio for f in b]
         flat = [f.to(dev, self.precision).contiguous().view(-1) for f in flat]
         lens = [int(f.shape[0]) for f in flat]
@@ -972,26 +987,36 @@ class TTS:
                            "gsv_postprocess_f32")
                 hr = self.sr_model.forward_device(wav, sr)
                 sr = self.sr_model.config["hr_sampling_rate"]
-                if sample_rate is not None or encoding is not None:
-                    return self._postprocess_rate([([hr.view(-1)], 0)], sr, sample_rate, encoding)[:2]
+                if sample_rate is not None or encoding is not None or loudness is not None:
+                    res = self._postprocess_rate([([hr.view(-1)], 0)], sr, sample_rate, encoding, loud)
+                    self.last_loudness = res[3]
+                    return res[:2]
                 pcm = torch.empty(int(hr.shape[0]), dtype=torch.int16, device=dev)
                 one_p, one_n = (C.c_void_p * 1)(hr.data_ptr()), (C.c_int * 1)(int(hr.shape[0]))
                 _lib.check(_lib.lib().gsv_postprocess(one_p, one_n, 1, _lib.GSV_F32, 0, pcm.data_ptr(), C.c_void_p(st.cuda_stream)),
                            "gsv_postprocess")
                 return sr, self._to_host(pcm)
-            if sample_rate is not None or encoding is not None:
-                return self._postprocess_rate([(flat, gap)], sr, sample_rate, encoding)[:2]
+            if sample_rate is not None or encoding is not None or loudness is not None:
+                res = self._postprocess_rate([(flat, gap)], sr, sample_rate, encoding, loud)
+                self.last_loudness = res[3]
+                return res[:2]
             pcm = torch.empty(sum(lens) + gap * len(lens), dtype=torch.int16, device=dev)
             _lib.check(_lib.lib().gsv_postprocess(ptrs, arr, len(flat), code, gap, pcm.data_ptr(), C.c_void_p(st.cuda_stream)),
                        "gsv_postprocess")
         return sr, self._to_host(pcm)
 
     def _postprocess_rate(self, groups: Sequence[Tuple[Sequence[torch.Tensor], int]], sr: int, sample_rate: Optional[int],
-                          encoding: Optional[str]) -> Tuple[int, np.ndarray, List[int]]:
+                          encoding: Optional[str], loudness: Optional[Sequence[Optional[tuple]]] = None
+                          ) -> Tuple[int, np.ndarray, List[int], list]:
         """One gsv_postprocess_groups_rate call (csrc/sola.hip) and one device-to-host copy: groups[g] =
         (its sentences, 1-D device tensors of one dtype, fp16 or fp32; its gap in samples at `sr`) -> (the output rate, all
         groups packed, int16 or uint8; the n_groups + 1 offsets of the groups in it).  sample_rate None is `sr` (the identity
-        filter), encoding None is "pcm_s16".  The table and the workspace are the pipeline's, as in postprocess_fragments."""
+        filter), encoding None is "pcm_s16".  The table and the workspace are the pipeline's, as in postprocess_fragments.
+        loudness (None: that call exactly): per group None or (target LUFS, scope, peak dBFS).  A group with settings is one
+        span with its gaps ("fragment") or one span per sentence ("sentence"), and the call is gsv_postprocess_groups_loud
+        with `sr` as the metered rate; a group without settings has no span and keeps gain 1.  The
+        report is copied to the host on the same stream in front of the audio and read after the one wait the audio needs.
+        The fourth result lists, per group with settings, [{"lufs", "gain_db", "limited"} per span] (empty without `loudness`)."""
         import ctypes as C
         from .. import _lib, audio_io
         dev = torch.device(self.configs.device)
@@ -1007,36 +1032,80 @@ class TTS:
         group_n, group_gap = (C.c_int * len(groups))(*counts), (C.c_int * len(groups))(*gaps)
         off = (C.c_longlong * (len(groups) + 1))()
         l = _lib.lib()
-        need = int(l.gsv_postprocess_groups_rate_workspace(lens, n, len(groups)))
+        spans, owner, first = [], [], 0                                 # owner[k]: the group of span k
+        for g, (cnt, cfg) in enumerate(zip(counts, loudness if loudness is not None else [None] * len(groups))):
+            if cfg is not None and cnt:
+                target, scope, peak = cfg
+                if scope not in audio_io.LOUDNESS_SCOPES:
+                    raise ValueError(f"loudness_scope {scope!r}: one of {', '.join(audio_io.LOUDNESS_SCOPES)}")
+                for f, c in ([(first, cnt)] if scope == "fragment" else [(first + i, 1) for i in range(cnt)]):
+                    spans.append(_lib.LoudSpan(f, c, int(scope == "fragment"), float(target), float(peak)))
+                    owner.append(g)
+            first += cnt
+        if spans:
+            span_arr = (_lib.LoudSpan * len(spans))(*spans)
+            need = int(l.gsv_postprocess_groups_loud_workspace(lens, n, group_n, group_gap, len(groups), int(sr), len(spans)))
+        else:
+            need = int(l.gsv_postprocess_groups_rate_workspace(lens, n, len(groups)))
         if need < 0:
-            raise RuntimeError("gsv_postprocess_groups_rate_workspace: bad lengths")
+            raise RuntimeError(f"gsv_postprocess_groups_loud_workspace: bad lengths, counts or rate {int(sr)}" if spans else
+                               "gsv_postprocess_groups_rate_workspace: bad lengths")
         with torch.cuda.device(dev):
             ws = getattr(self, "_post_groups_ws", None)
             if ws is None or ws[0].numel() < need:
                 size = max(1 << 16, 2 * need)
                 ws = self._post_groups_ws = (torch.empty(size, dtype=torch.uint8).pin_memory(),
                                              torch.empty(size, dtype=torch.uint8, device=dev))
+            rs = getattr(self, "_post_loud_reports", None)               # the reports: kept like the workspace, grown on demand
+            if spans and (rs is None or rs[0].numel() < 16 * len(spans)):
+                size = max(1 << 12, 32 * len(spans))
+                rs = self._post_loud_reports = (torch.empty(size, dtype=torch.uint8).pin_memory(),
+                                                torch.empty(size, dtype=torch.uint8, device=dev))
             hd, up, down = audio_io.output_filter_device(sr, sr_out, dev)
             total = sum(audio_io.resampled_len(sum(int(f.shape[0]) for f in frags) + len(frags) * g, sr, sr_out)
                         for (frags, _), g in zip(groups, gaps))
             out = torch.empty(max(total, 1), dtype=torch.int16 if fmt == _lib.GSV_OUT_S16 else torch.uint8, device=dev)
             st = torch.cuda.current_stream(dev)
-            _lib.check(l.gsv_postprocess_groups_rate(ptrs, lens, n, code, group_n, group_gap, len(groups), out.data_ptr(), off,
-                                                     ws[0].data_ptr(), ws[1].data_ptr(), hd.data_ptr(), int(hd.numel()), up, down,
-                                                     fmt, C.c_void_p(st.cuda_stream)), "gsv_postprocess_groups_rate")
+            rep_host = None
+            if spans:
+                rep_host, rep_dev = rs[0][:16 * len(spans)], rs[1][:16 * len(spans)]
+                _lib.check(l.gsv_postprocess_groups_loud(ptrs, lens, n, code, group_n, group_gap, len(groups), out.data_ptr(), off,
+                                                         ws[0].data_ptr(), ws[1].data_ptr(), hd.data_ptr(), int(hd.numel()), up, down,
+                                                         fmt, int(sr), span_arr, len(spans), rep_dev.data_ptr(),
+                                                         C.c_void_p(st.cuda_stream)), "gsv_postprocess_groups_loud")
+                rep_host.copy_(rep_dev, non_blocking=True)              # in front of the audio: the wait below covers both
+            else:
+                _lib.check(l.gsv_postprocess_groups_rate(ptrs, lens, n, code, group_n, group_gap, len(groups), out.data_ptr(), off,
+                                                         ws[0].data_ptr(), ws[1].data_ptr(), hd.data_ptr(), int(hd.numel()), up, down,
+                                                         fmt, C.c_void_p(st.cuda_stream)), "gsv_postprocess_groups_rate")
             host = self._to_host(out)                                   # waits for the stream: `flat` and the table are done with
         assert int(off[len(groups)]) == total
-        return sr_out, host[:total], [int(v) for v in off]
+        reports: list = []
+        if loudness is not None:
+            per_group: Dict[int, list] = {g: [] for g, cfg in enumerate(loudness) if cfg is not None}
+            if rep_host is not None:
+                for g, r in zip(owner, rep_host.numpy().view(_lib.LOUD_REPORT_DTYPE)):
+                    gain = float(r["gain"])
+                    per_group[g].append({"lufs": float(r["lufs"]), "gain_db": 20.0 * math.log10(gain) if gain > 0 else -math.inf,
+                                         "gain": gain, "limited": bool(int(r["flags"]) & _lib.LOUD_LIMITED)})
+            reports = [per_group[g] for g in sorted(per_group)]
+        return sr_out, host[:total], [int(v) for v in off], reports
 
     def postprocess_fragments(self, groups: Sequence[Tuple[Sequence[torch.Tensor], float]], sample_rate: Optional[int] = None,
-                              encoding: Optional[str] = None) -> List[np.ndarray]:
+                              encoding: Optional[str] = None, loudness: Optional[Sequence[Optional[tuple]]] = None
+                              ) -> List[np.ndarray]:
         """audio_postprocess([frags], sr, None, speed, False, fragment_interval) of several fragments in ONE launch pair and
         ONE device-to-host copy (`gsv_postprocess_groups`, csrc/sola.hip): groups[g] = (the sentences of one fragment, its
         fragment_interval) -> the int16 audio of each, what audio_postprocess returns for it alone (super_sampling is not
         handled here: AP-BWE runs per fragment).  The table and the workspace are kept on the pipeline and grow on demand;
         the call waits for its copy, so the next call may rewrite them.
         sample_rate / encoding (None: the launches above, unchanged): every fragment at that rate and in that encoding, as
-        audio_postprocess gives it with the same keywords, from ONE gsv_postprocess_groups_rate call; int16 or uint8."""
+        audio_postprocess gives it with the same keywords, from ONE gsv_postprocess_groups_rate call; int16 or uint8.
+        loudness (None, or all None: as above): per fragment None or (target LUFS, scope, peak dBFS), the loudness keywords of
+        audio_postprocess.  Fragments with and without settings, and with different ones, share the one call, which is then
+        gsv_postprocess_groups_loud: its int16 saturates, also for the fragments without settings in it (+1.0 gives 32767
+        where the launches above wrap to -32768).  self.last_loudness becomes the reports of the fragments with settings, in
+        order."""
         import ctypes as C
         from .. import _lib
         dev = torch.device(self.configs.device)
@@ -1044,10 +1113,14 @@ class TTS:
             raise RuntimeError("postprocess_fragments is a HIP kernel (gsv_postprocess_groups); there is no CPU path")
         if not groups:
             return []
-        if sample_rate is not None or encoding is not None:
+        if loudness is not None and all(c is None for c in loudness):
+            loudness = None
+        if sample_rate is not None or encoding is not None or loudness is not None:
             rated = [([f.to(dev, self.precision).contiguous().view(-1) for f in frags], int(self.configs.sampling_rate * interval))
                      for frags, interval in groups]
-            _, host, off = self._postprocess_rate(rated, self._output_sr(), sample_rate, encoding)
+            _, host, off, reports = self._postprocess_rate(rated, self._output_sr(), sample_rate, encoding, loudness)
+            if loudness is not None:
+                self.last_loudness = reports
             return [host[off[g]:off[g + 1]].copy() for g in range(len(groups))]
         flat = [f.to(dev, self.precision).contiguous().view(-1) for frags, _ in groups for f in frags]
         gaps = [int(self.configs.sampling_rate * interval) for _, interval in groups]
@@ -1609,7 +1682,10 @@ class TTS:
         (candidates per sentence) likewise only when the request names one other than 1, as given, with
         its "best_of_score" callable if it brings one: _resolve_options checks both.  "sample_rate" (int, Hz) and "encoding"
         ("pcm_s16", "mulaw", "alaw") are checked and carried only when the request gives them: a rate
-        that is no positive int and an unknown encoding raise ValueError."""
+        that is no positive int and an unknown encoding raise ValueError.  "loudness" (float, LUFS in -70 .. 0; DESIGN.md
+        section 4v) brings "loudness_scope" ("fragment", the default, or "sentence") and "loudness_peak" (dBFS <= 0, default 0.0)
+        with it; all three are carried only when the request gives "loudness", as floats (any real number, numpy's included,
+        but no bool), and the other two without it, wrong types and values out of range raise ValueError."""
         o = dict(top_k=req.get("top_k", 5), top_p=req.get("top_p", 1), temperature=req.get("temperature", 1),
                  batch_size=req.get("batch_size", 1), batch_threshold=req.get("batch_threshold", 0.75),
                  speed_factor=req.get("speed_factor", 1.0), split_bucket=req.get("split_bucket", True),
@@ -1638,12 +1714,25 @@ class TTS:
             if req["encoding"] not in ENCODINGS:
                 raise ValueError(f"encoding {req['encoding']!r}: one of {', '.join(sorted(ENCODINGS))}")
             o["encoding"] = req["encoding"]
+        if req.get("loudness") is not None:
+            from ..audio_io import LOUDNESS_SCOPES
+            target, scope, peak = req["loudness"], req.get("loudness_scope", "fragment"), req.get("loudness_peak", 0.0)
+            real = lambda v: isinstance(v, numbers.Real) and not isinstance(v, (bool, np.bool_))     # noqa: E731
+            if not real(target) or not -70.0 <= target <= 0.0:
+                raise ValueError(f"loudness {target!r}: a target in LUFS, -70 <= v <= 0")
+            if scope not in LOUDNESS_SCOPES:
+                raise ValueError(f"loudness_scope {scope!r}: one of {', '.join(LOUDNESS_SCOPES)}")
+            if not real(peak) or not peak <= 0.0:
+                raise ValueError(f"loudness_peak {peak!r}: a ceiling in dBFS, at most 0")
+            o["loudness"], o["loudness_scope"], o["loudness_peak"] = float(target), scope, float(peak)
+        elif req.get("loudness_scope") is not None or req.get("loudness_peak") is not None:
+            raise ValueError("loudness_scope / loudness_peak without \"loudness\": name the target in LUFS")
         return o
 
     @staticmethod
     def _format_kw(o: dict) -> dict:
         """the output-format keywords of audio_postprocess for resolved options: only the ones the request kept"""
-        return {k: o[k] for k in ("sample_rate", "encoding") if k in o}
+        return {k: o[k] for k in ("sample_rate", "encoding", "loudness", "loudness_scope", "loudness_peak") if k in o}
 
     def _resolve_options(self, req: dict) -> dict:
         """_request_options(req) under the rules of the loaded model, what run() and run_batch work from: fragments, another
@@ -2242,13 +2331,20 @@ class TTS:
         self._ar_stage(plans, mixed_sampling=mixed_sampling, **({"continuous_ar": True} if continuous_ar else {}),
                        **({"mixed_limits": True} if mixed_limits else {}))
         self.last_candidates = [pl.get("candidates", []) for pl in plans]
+        self.last_loudness = []
         sr = self._output_sr()
         if shared_sovits and not self.configs.use_vocoder:
             self._shared_sovits_stage(plans, shared_speed=shared_speed)
         if shared_cfm and self.configs.use_vocoder:
             # the keyword goes along only when it is set: a stage that predates it (a subclass, a stub) keeps working without it
             self._shared_cfm_stage(plans, shared_vocoder=shared_vocoder, **({"continuous_cfm": True} if continuous_cfm else {}))
-        return [self._finish_request(pl, sr) for pl in plans]
+        results, reports = [], []
+        for pl in plans:                                 # the reports of the requests with "loudness", in request order
+            self.last_loudness = []
+            results.append(self._finish_request(pl, sr))
+            reports += self.last_loudness
+        self.last_loudness = reports
+        return results
 
     def serve(self, **scheduler_kw):
         """Requests as they arrive instead of a closed list: a started `gsv.serving.Server` over a `Scheduler` of this
@@ -2278,6 +2374,7 @@ class TTS:
             prompt_data = None if pc["phones"] is None else {"phones": pc["phones"], "bert_features": pc["bert_features"]}
             check_best_of(o, prompt_data is None)
             self.last_candidates = [[]] if "best_of" in o else []
+            self.last_loudness, loud_reports = [], []
             t1 = time.perf_counter()
             # token ids stay on the host here: the engines pack a whole batch and move it with ONE copy
             # (the reference's per-item .to(device), TTS.py:899-912, is ~75 tiny transfers per batch of 32)
@@ -2317,8 +2414,12 @@ class TTS:
                 t5 = time.perf_counter()
                 t_45 += t5 - t4
                 if o["return_fragment"]:
-                    yield self.audio_postprocess([frags], sr, None, o["speed_factor"], False, o["fragment_interval"],
-                                                 o["super_sampling"], **self._format_kw(o))
+                    frag = self.audio_postprocess([frags], sr, None, o["speed_factor"], False, o["fragment_interval"],
+                                                  o["super_sampling"], **self._format_kw(o))
+                    if "loudness" in o:                                 # one report list per fragment, gathered over the run
+                        loud_reports += self.last_loudness
+                        self.last_loudness = loud_reports
+                    yield frag
                 else:
                     audio.append(frags)
                 if self.stop_flag:

@@ -32,6 +32,15 @@ class RowLimits(C.Structure):
     _fields_ = [("eos_mask_steps", C.c_int), ("early_stop_num", C.c_int), ("max_steps", C.c_int), ("reserved", C.c_int)]
 
 
+class LoudSpan(C.Structure):
+    """gsv_loud_span: sentences [first, first + count) of one group, metered together; target NaN = meter only"""
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("gaps", C.c_int32), ("target", C.c_float), ("peak_db", C.c_float)]
+
+
+LOUD_LIMITED, LOUD_NAN, LOUD_SILENT = 1, 2, 4   # gsv_loud_report.flags
+LOUD_REPORT_DTYPE = [("lufs", "<f8"), ("gain", "<f4"), ("flags", "<u4")]   # numpy view of gsv_loud_report [n_spans]
+
+
 class VitsConfig(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("inter_channels", "hidden_channels", "filter_channels", "n_heads", "n_layers",
                                         "kernel_size", "gin_channels", "n_symbols", "ssl_dim", "n_bins",
@@ -193,6 +202,15 @@ _SIGS = {
     "gsv_postprocess_groups_rate": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int),
                                               C.POINTER(C.c_int), C.c_int, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "gsv_postprocess_groups_loud_workspace": (C.c_longlong, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                             C.c_int, C.c_int, C.c_int]),
+    "gsv_postprocess_groups_loud": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int),
+                                              C.POINTER(C.c_int), C.c_int, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              C.POINTER(LoudSpan), C.c_int, C.c_void_p, C.c_void_p]),
+    "gsv_op_loudness": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                  C.c_int, C.c_int, C.POINTER(LoudSpan), C.c_int, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsv_bwe_create": (C.c_int, [C.POINTER(BweConfig), C.c_int, C.POINTER(C.c_void_p)]),
     "gsv_bwe_destroy": (None, [C.c_void_p]),
     "gsv_bwe_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),

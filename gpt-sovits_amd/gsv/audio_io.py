@@ -8,6 +8,7 @@ everything downstream of the waveform is pinned.
 """
 from __future__ import annotations
 
+import math
 import wave
 from math import gcd
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -165,36 +166,118 @@ def output_filter_device(sr_in: int, sr_out: int, dev):
     return _filters_dev[key], up, down
 
 
-def convert_pcm(pcm: np.ndarray, sr_in: int, sr_out: int, encoding: Optional[str] = None, device="cuda:0") -> np.ndarray:
+def convert_pcm(pcm: np.ndarray, sr_in: int, sr_out: int, encoding: Optional[str] = None, device="cuda:0",
+                loudness: Optional[float] = None, loudness_peak: float = 0.0) -> np.ndarray:
     """int16 audio at sr_in -> the same audio at sr_out as int16 ("pcm_s16", None) or G.711 bytes ("mulaw", "alaw"), through
-    one gsv_postprocess_groups_rate call on pcm / 32768 (exact in fp32, peak <= 1: nothing is normalised)."""
+    one gsv_postprocess_groups_rate call on pcm / 32768 (exact in fp32, peak <= 1: nothing is normalised).  loudness (LUFS,
+    -70 .. 0): the audio is one span of gsv_postprocess_groups_loud, metered at sr_in and scaled towards the target under the
+    ceiling loudness_peak (dBFS <= 0).  The level is then that of the quantised audio: a caller that
+    still has the float sentences uses postprocess_sentences."""
+    x = np.ascontiguousarray(pcm, dtype=np.int16).astype(np.float32) / np.float32(32768.0)
+    return postprocess_sentences([x], 0, sr_in, sr_out, encoding, device, loudness, "fragment", loudness_peak)[0]
+
+
+def postprocess_sentences(sentences: Sequence[np.ndarray], gap: int, sr_in: int, sr_out: Optional[int] = None,
+                          encoding: Optional[str] = None, device="cuda:0", loudness: Optional[float] = None,
+                          loudness_scope: str = "fragment", loudness_peak: float = 0.0) -> Tuple[np.ndarray, list]:
+    """The post-processing of one fragment outside a TTS pipeline (inference_cli): float sentences at sr_in, each followed by
+    `gap` zeros, through one gsv_postprocess_groups_rate / _loud call -> (int16 or G.711 bytes at sr_out, the loudness reports
+    [(lufs, linear gain, limited) per span]).  The peak rule, the saturating int16 and the loudness keywords are those of
+    TTS.audio_postprocess: the gain multiplies the float samples, per fragment or per sentence."""
     import ctypes as C
 
     import torch
 
     from . import _lib
+    sr_out = int(sr_in) if sr_out is None else int(sr_out)
     if encoding is not None and encoding not in ENCODINGS:
         raise ValueError(f"encoding {encoding!r}: one of {', '.join(sorted(ENCODINGS))}")
     if not output_rate_supported(sr_in, sr_out):
         raise ValueError(f"sample_rate {sr_out}: the resampling kernel does not take {sr_in} -> {sr_out}")
+    if loudness is not None and loudness_scope not in LOUDNESS_SCOPES:
+        raise ValueError(f"loudness_scope {loudness_scope!r}: one of {', '.join(LOUDNESS_SCOPES)}")
     fmt = ENCODINGS[encoding or "pcm_s16"]
     dev = torch.device(device)
-    n = int(pcm.shape[0])
-    if n == 0:
-        return np.zeros(0, dtype=np.int16 if fmt == 0 else np.uint8)
+    k = len(sentences)
+    total = sum(int(x.shape[0]) + int(gap) for x in sentences)
+    if total == 0:
+        return np.zeros(0, dtype=np.int16 if fmt == 0 else np.uint8), []
     with torch.cuda.device(dev):
         _lib.init(dev.index if dev.index is not None else torch.cuda.current_device())
-        x = torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.int16)).to(dev).to(torch.float32) / 32768.0
+        xs = [torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev) for x in sentences]
         hd, up, down = output_filter_device(sr_in, sr_out, dev)
-        lens, ptrs, one, gap = (C.c_int * 1)(n), (C.c_void_p * 1)(x.data_ptr()), (C.c_int * 1)(1), (C.c_int * 1)(0)
+        lens, ptrs = (C.c_int * k)(*[int(x.numel()) for x in xs]), (C.c_void_p * k)(*[x.data_ptr() for x in xs])
+        count, gaps = (C.c_int * 1)(k), (C.c_int * 1)(int(gap))
         off = (C.c_longlong * 2)()
         l = _lib.lib()
-        need = int(l.gsv_postprocess_groups_rate_workspace(lens, 1, 1))
+        spans = []
+        if loudness is not None:
+            frag = loudness_scope == "fragment"
+            spans = [_lib.LoudSpan(f, c, int(frag), float(loudness), float(loudness_peak))
+                     for f, c in ([(0, k)] if frag else [(i, 1) for i in range(k)])]
+            span_arr = (_lib.LoudSpan * len(spans))(*spans)
+            report = torch.empty(16 * len(spans), dtype=torch.uint8, device=dev)
+            need = int(l.gsv_postprocess_groups_loud_workspace(lens, k, count, gaps, 1, int(sr_in), len(spans)))
+        else:
+            need = int(l.gsv_postprocess_groups_rate_workspace(lens, k, 1))
+        if need < 0:
+            raise ValueError(f"postprocess_sentences: {total} samples at {sr_in} Hz are not taken")
         table = torch.empty(need, dtype=torch.uint8).pin_memory()
         work = torch.empty(need, dtype=torch.uint8, device=dev)
-        out = torch.empty(resampled_len(n, sr_in, sr_out), dtype=torch.int16 if fmt == 0 else torch.uint8, device=dev)
+        out = torch.empty(resampled_len(total, sr_in, sr_out), dtype=torch.int16 if fmt == 0 else torch.uint8, device=dev)
         st = torch.cuda.current_stream(dev)
-        _lib.check(l.gsv_postprocess_groups_rate(ptrs, lens, 1, _lib.GSV_F32, one, gap, 1, out.data_ptr(), off, table.data_ptr(),
-                                                 work.data_ptr(), hd.data_ptr(), int(hd.numel()), up, down, fmt,
-                                                 C.c_void_p(st.cuda_stream)), "gsv_postprocess_groups_rate")
-        return out.cpu().numpy()                       # waits for the stream: the table is done with
+        if spans:
+            _lib.check(l.gsv_postprocess_groups_loud(ptrs, lens, k, _lib.GSV_F32, count, gaps, 1, out.data_ptr(), off, table.data_ptr(),
+                                                     work.data_ptr(), hd.data_ptr(), int(hd.numel()), up, down, fmt, int(sr_in), span_arr,
+                                                     len(spans), report.data_ptr(), C.c_void_p(st.cuda_stream)),
+                       "gsv_postprocess_groups_loud")
+        else:
+            _lib.check(l.gsv_postprocess_groups_rate(ptrs, lens, k, _lib.GSV_F32, count, gaps, 1, out.data_ptr(), off, table.data_ptr(),
+                                                     work.data_ptr(), hd.data_ptr(), int(hd.numel()), up, down, fmt,
+                                                     C.c_void_p(st.cuda_stream)), "gsv_postprocess_groups_rate")
+        host = out.cpu().numpy()                       # waits for the stream: the table is done with
+        reports = []
+        if spans:
+            reports = [(float(r["lufs"]), float(r["gain"]), bool(int(r["flags"]) & _lib.LOUD_LIMITED))
+                       for r in report.cpu().numpy().view(_lib.LOUD_REPORT_DTYPE)]
+        return host, reports
+
+
+# ---- loudness normalisation (gsv_postprocess_groups_loud, DESIGN.md section 4v) ---------------------------------------------------
+LOUDNESS_SCOPES = ("fragment", "sentence")
+_k_weighting: Dict[int, dict] = {}
+
+
+def k_weighting(rate: int) -> dict:
+    """The ITU-R BS.1770 K-weighting for a stream at `rate`, re-derived from the analogue prototype as libebur128 and pyloudnorm
+    do, in fp64 and cached per rate: "shelf" and "highpass" = (b [3], a [3]); "A" [4, 4], "B" [4], "C" [4], "D": the cascade as
+    one recurrence s' = A s + B x, y = C s + D x (both biquads in transposed direct form II, the arithmetic of the device
+    meter); "A16", "A1024", "A4096": the powers of A behind a lane's chunk, a wave and a tile of that meter; "sub_block" =
+    round(0.1 rate) samples.  The library derives the same numbers from the rate it is given (csrc/sola.hip, loud_constants)."""
+    rate = int(rate)
+    if rate <= 0:
+        raise ValueError(f"rate {rate}: a sample rate is positive")
+    if rate not in _k_weighting:
+        f0, G, Q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+        K = math.tan(math.pi * f0 / rate)
+        Vh = 10.0 ** (G / 20.0)
+        Vb = Vh ** 0.4996667741545416
+        a0 = 1.0 + K / Q + K * K
+        sb = np.array([(Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0])
+        sa = np.array([1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0])
+        f0, Q = 38.13547087602444, 0.5003270373238773
+        K = math.tan(math.pi * f0 / rate)
+        d = 1.0 + K / Q + K * K
+        hb = np.array([1.0, -2.0, 1.0])
+        ha = np.array([1.0, 2.0 * (K * K - 1.0) / d, (1.0 - K / Q + K * K) / d])
+        # y1 = sb0 x + s0; s0' = sb1 x - sa1 y1 + s1; s1' = sb2 x - sa2 y1; y = hb0 y1 + s2; s2' = hb1 y1 - ha1 y + s3; s3' = hb2 y1 - ha2 y
+        A = np.array([[-sa[1], 1.0, 0.0, 0.0],
+                      [-sa[2], 0.0, 0.0, 0.0],
+                      [hb[1] - ha[1] * hb[0], 0.0, -ha[1], 1.0],
+                      [hb[2] - ha[2] * hb[0], 0.0, -ha[2], 0.0]])
+        B = np.array([sb[1] - sa[1] * sb[0], sb[2] - sa[2] * sb[0], (hb[1] - ha[1] * hb[0]) * sb[0], (hb[2] - ha[2] * hb[0]) * sb[0]])
+        Cm = np.array([hb[0], 0.0, 1.0, 0.0])
+        _k_weighting[rate] = {"shelf": (sb, sa), "highpass": (hb, ha), "A": A, "B": B, "C": Cm, "D": hb[0] * sb[0],
+                              "A16": np.linalg.matrix_power(A, 16), "A1024": np.linalg.matrix_power(A, 1024),
+                              "A4096": np.linalg.matrix_power(A, 4096), "sub_block": int(round(0.1 * rate))}
+    return _k_weighting[rate]

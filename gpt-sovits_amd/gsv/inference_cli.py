@@ -22,7 +22,7 @@ from __future__ import annotations
 import argparse
 import os
 import wave
-from typing import Iterator, Tuple
+from typing import Iterator, Optional, Tuple
 
 import numpy as np
 import torch
@@ -35,8 +35,13 @@ from .TTS_infer_pack.TTS import load_sovits_new
 def get_tts_wav(t2s: Text2SemanticDecoder, vits: SynthesizerTrn, prompt_semantic: torch.Tensor, refer_spec,
                 prompt_segment: dict, segments, top_k: int = 20, top_p: float = 1.0, temperature: float = 1.0,
                 speed: float = 1.0, hz: int = 50, max_sec: int = 54, pause_second: float = 0.3,
-                sampling_rate: int = 32000, seed: int = 0) -> Iterator[Tuple[int, np.ndarray]]:
-    """reference inference_webui.py:751-1001 restated for pre-tokenised input; yields (32000, int16)."""
+                sampling_rate: int = 32000, seed: int = 0, loudness: Optional[float] = None, loudness_scope: str = "fragment",
+                loudness_peak: float = 0.0, sample_rate: Optional[int] = None) -> Iterator[Tuple[int, np.ndarray]]:
+    """reference inference_webui.py:751-1001 restated for pre-tokenised input; yields (32000, int16).
+    loudness (LUFS) and sample_rate are additions: with `loudness` the float sentences and their pauses
+    go through audio_io.postprocess_sentences instead of the host conversion -- metered and scaled on the device per fragment
+    or per sentence, resampled to `sample_rate` when given, int16 as trunc(x * 32768) saturating -- and (rate, int16) is
+    yielded."""
     dev = t2s.device
     zero = np.zeros(int(sampling_rate * pause_second), dtype=np.float32)
     audio = []
@@ -63,6 +68,13 @@ def get_tts_wav(t2s: Text2SemanticDecoder, vits: SynthesizerTrn, prompt_semantic
         audio.append(wav)
         audio.append(zero)
     if not audio:
+        return
+    if loudness is not None:
+        from .audio_io import postprocess_sentences
+        rate = sampling_rate if sample_rate is None else int(sample_rate)
+        pcm, _ = postprocess_sentences(audio[0::2], zero.shape[0], sampling_rate, rate, None, dev, loudness, loudness_scope,
+                                       loudness_peak)
+        yield rate, pcm
         return
     yield sampling_rate, (np.concatenate(audio, 0) * 32767).astype(np.int16)
 
@@ -160,7 +172,7 @@ class _SymbolAny:
 
 def synthesize(GPT_model_path, SoVITS_model_path, ref_audio_path, ref_text_path, ref_language, target_text_path,
                target_language, output_path, bert_path=None, cnhubert_base_path=None, gpu_number="0", is_half=True,
-               frontend=None, sample_rate=None):
+               frontend=None, sample_rate=None, loudness=None, loudness_scope="fragment", loudness_peak=0.0):
     if frontend is None:
         raise ValueError("pass `frontend` (an object, or a --frontend string for make_frontend): the reference's G2P "
                          "packages are third-party and not part of this build (see the module docstring)")
@@ -187,11 +199,12 @@ def synthesize(GPT_model_path, SoVITS_model_path, ref_audio_path, ref_text_path,
     prompt_seg = frontend.text_to_segments(ref_text, ref_language)[0]
     segments = frontend.text_to_segments(target_text, target_language)
     result = list(get_tts_wav(t2s, vits, prompt_semantic, refer_spec, prompt_seg, segments,
-                              max_sec=s1["config"]["data"]["max_sec"]))
+                              max_sec=s1["config"]["data"]["max_sec"], loudness=loudness, loudness_scope=loudness_scope,
+                              loudness_peak=loudness_peak, sample_rate=sample_rate if loudness is not None else None))
     if result:
         sr, audio = result[-1]
         if sample_rate is not None and int(sample_rate) != sr:       # --sample_rate: resampled on the device
-            from .audio_io import convert_pcm
+            from .audio_io import convert_pcm                        # (with --loudness get_tts_wav has done both: sr is the rate)
             audio, sr = convert_pcm(audio, sr, int(sample_rate), device=device), int(sample_rate)
         os.makedirs(output_path, exist_ok=True)
         out = os.path.join(output_path, "output.wav")
@@ -223,12 +236,22 @@ def main(argv=None):
                         "or 'pkg.module:factory' (default: $GSV_FRONTEND or 'symbols')")
     p.add_argument("--sample_rate", type=int, default=None,
                    help="sample rate of output.wav in Hz (an addition to the reference's flags; default: the model's, 32000)")
+    p.add_argument("--loudness", type=float, default=None,
+                   help="normalise output.wav to this programme loudness in LUFS (ITU-R BS.1770, -70 .. 0; default: off)")
+    p.add_argument("--loudness_scope", default="fragment", choices=["fragment", "sentence"],
+                   help="what is metered together and gets one gain: the whole output with its pauses, or each sentence")
+    p.add_argument("--loudness_peak", type=float, default=0.0, help="ceiling of the normalised peak in dBFS (<= 0, default 0)")
     a = p.parse_args(argv)
     if a.sample_rate is not None and a.sample_rate <= 0:
         p.error("--sample_rate must be positive")
+    if a.loudness is not None and not -70.0 <= a.loudness <= 0.0:
+        p.error("--loudness is a target in LUFS, -70 .. 0")
+    if a.loudness_peak > 0.0:
+        p.error("--loudness_peak is a ceiling in dBFS, at most 0")
     synthesize(a.gpt_model, a.sovits_model, a.ref_audio, a.ref_text, a.ref_language, a.target_text, a.target_language,
                a.output_path, a.bert_path, a.cnhubert_base_path, a.gpu_number, str(a.is_half).lower() in ("true", "1"),
-               frontend=a.frontend, sample_rate=a.sample_rate)
+               frontend=a.frontend, sample_rate=a.sample_rate, loudness=a.loudness, loudness_scope=a.loudness_scope,
+               loudness_peak=a.loudness_peak)
 
 
 if __name__ == "__main__":

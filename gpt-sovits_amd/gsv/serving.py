@@ -887,6 +887,11 @@ class Scheduler:
                     tts._wait_stream()
                     sr = tts._output_sr()
                     kw = {k: v for k, v in (("sample_rate", rate), ("encoding", enc)) if v is not None}
+                    # "loudness" is per fragment inside the one call of its format
+                    loud = [None if "loudness" not in o else (o["loudness"], o["loudness_scope"], o["loudness_peak"])
+                            for o in (self._requests[t]["opts"] for t, _ in batch)]
+                    if any(c is not None for c in loud):
+                        kw["loudness"] = loud
                     audios = tts.postprocess_fragments([(self._requests[t]["frags"][b], self._requests[t]["opts"]["fragment_interval"])
                                                         for t, b in batch], **kw)
                     got.update({f: (sr if rate is None else rate, a) for f, a in zip(batch, audios)})

@@ -163,12 +163,17 @@ def place_pieces(pieces, batches: List[List[int]], n_segments: int, dev: torch.d
 
 def refuse_output_format(segments: Optional[List[dict]]) -> None:
     """A sharded run gathers int16 fragments by `last_fragment_lengths`, which are counted at the model's own rate: the request
-    keys "sample_rate" and "encoding"  are refused here instead of being dropped on the way."""
+    keys "sample_rate" and "encoding"  are refused here instead of being dropped on the way.  So are
+    "loudness", "loudness_scope" and "loudness_peak" (section 4v): each rank would meter and scale its own piece."""
     for s in segments or []:
         for k in ("sample_rate", "encoding"):
             if s.get(k) is not None:
                 raise ValueError(f"a sharded run does not take {k!r}: its gather works on int16 fragments at the model's rate "
                                  "(convert the gathered audio, or run unsharded)")
+        for k in ("loudness", "loudness_scope", "loudness_peak"):
+            if s.get(k) is not None:
+                raise ValueError(f"a sharded run does not take {k!r}: every rank would normalise its own piece of the audio "
+                                 "(normalise the gathered audio, or run unsharded)")
 
 
 class ShardedSynthesizer:

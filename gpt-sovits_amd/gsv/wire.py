@@ -153,7 +153,7 @@ def create_app(tts_pipeline, server=None):
             if k in q:
                 q[k] = int(q[k])
         for k in ("top_p", "temperature", "batch_threshold", "speed_factor", "fragment_interval", "repetition_penalty",
-                  "inference_cfg_rate"):
+                  "inference_cfg_rate", "loudness", "loudness_peak"):
             if k in q:
                 q[k] = float(q[k])
         for k in ("split_bucket", "streaming_mode", "parallel_infer", "super_sampling"):

@@ -544,6 +544,56 @@ long long gsv_postprocess_groups_rate_workspace(const int* lens, int n, int n_gr
 int gsv_postprocess_groups_rate(const void* const* frags, const int* lens, int n, int dtype, const int* group_n, const int* group_gap,
                                 int n_groups, void* out, long long* group_off, void* table, void* workspace, const float* h,
                                 int h_len, int up, int down, int out_fmt, gsv_stream_t stream);
+/* gsv_postprocess_groups_rate with loudness normalisation after ITU-R BS.1770, measured and applied on
+ * the device.  A span is a run of consecutive sentences of one group that is metered on its own and gets one gain:
+ *   samples   gaps = 1: concat_i [norm(x_i), G zeros] over its sentences (the whole X_g when it names all of a group);
+ *             gaps = 0: concat_i norm(x_i); N samples at the model's rate `rate`, never materialised;
+ *   weighting the two BS.1770 biquads re-derived for `rate` from the analogue prototype (shelf f0 = 1681.974450955533 Hz,
+ *             G = 3.999843853973347 dB, Q = 0.7071752369554196; high-pass f0 = 38.13547087602444 Hz, Q = 0.5003270373238773, as
+ *             libebur128 and pyloudnorm do), zero state at the span's start, fp64;
+ *   blocks    s = round(0.1 * rate); e_j = sum of y^2 over sub-block j < J = floor(N / s); z_b = (e_b + .. + e_{b+3}) / (4 s),
+ *             b <= J - 4; the trailing partial sub-block is ignored.  J < 4 and N > 0: the single block z_0 = sum of all y^2 / N;
+ *   gating    l(z) = -0.691 + 10 log10 z; blocks with l > -70, then those of them with l > l(their mean) - 10; L = l(mean of
+ *             those), -inf when none is left;
+ *   gain      1 when target is NaN (meter only), L = -inf or a sentence of the span holds a NaN; else 10^((target - L) / 20),
+ *             lowered to c / P with GSV_LOUD_LIMITED set when it would lift the span's peak P = max_i min(peak_i, 1) above
+ *             c = 10^(peak_db / 20); fp64, rounded to fp32 once.
+ * The gain multiplies the fp32 sample of the stream in front of the filter taps; resampling and formats are those of
+ * gsv_postprocess_groups_rate.  Sentences in no span keep gain 1.  spans [host]: sorted by `first`, not overlapping, none across
+ * two groups, -70 <= target <= 0 or NaN, peak_db <= 0, rate > 0: anything else is refused with a message before any launch, and
+ * so is a rate whose sub-block s is not longer than 2048 samples (a 4096-sample tile of the meter touches at most three).
+ * report [dev]: one record per span.  With n_spans = 0 the call is gsv_postprocess_groups_rate, launch for launch.  Otherwise
+ * six launches whatever n, n_groups and n_spans: peaks, tile end states, carries, sub-block energies, gates, write.  No floating-
+ * point atomics and no workgroup waits for another: a span's report and output bytes are bit-identical whatever else the call
+ * holds.  table [host] and workspace [dev]: gsv_postprocess_groups_loud_workspace(...) bytes each (-1: a bad length, count or
+ * rate); nothing is allocated and the host is not synchronised. */
+typedef struct gsv_loud_span {
+  int32_t first, count; /* sentences [first, first + count) of the call, all of one group */
+  int32_t gaps;         /* 1: each sentence is followed by its group's gap; 0: the sentences alone */
+  float target;         /* LUFS; NaN: meter only */
+  float peak_db;        /* ceiling of the span's peak after the gain, dBFS <= 0 */
+} gsv_loud_span;
+typedef struct gsv_loud_report {
+  double lufs; /* L; -inf when no block passes the gates; unspecified with GSV_LOUD_NAN */
+  float gain;  /* the linear gain that was (gsv_op_loudness: would be) applied */
+  uint32_t flags;
+} gsv_loud_report;
+#define GSV_LOUD_LIMITED 1u /* the ceiling lowered the gain */
+#define GSV_LOUD_NAN 2u     /* a sentence of the span holds a NaN: gain 1 */
+#define GSV_LOUD_SILENT 4u  /* L = -inf: gain 1 */
+long long gsv_postprocess_groups_loud_workspace(const int* lens, int n, const int* group_n, const int* group_gap, int n_groups,
+                                                int rate, int n_spans);
+int gsv_postprocess_groups_loud(const void* const* frags, const int* lens, int n, int dtype, const int* group_n, const int* group_gap,
+                                int n_groups, void* out, long long* group_off, void* table, void* workspace, const float* h,
+                                int h_len, int up, int down, int out_fmt, int rate, const gsv_loud_span* spans, int n_spans,
+                                gsv_loud_report* report, gsv_stream_t stream);
+/* test / debug: the meter of gsv_postprocess_groups_loud alone (its first five launches).  energies [dev] fp64: span k's
+ * sub-block energies e_j at energy_off[k] .. energy_off[k + 1] ([host], n_spans + 1 entries, written by the call):
+ * ceil(N_k / s) values, the last one the trailing partial sub-block where s does not divide N_k.  energies holds at most
+ * sum over the groups of N_g / s, plus n_spans, values.  table, workspace: as above. */
+int gsv_op_loudness(const void* const* frags, const int* lens, int n, int dtype, const int* group_n, const int* group_gap,
+                    int n_groups, int rate, const gsv_loud_span* spans, int n_spans, double* energies, long long* energy_off,
+                    gsv_loud_report* report, void* table, void* workspace, gsv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * AP-BWE audio super-resolution (tools/audio_sr.py::AP_BWE.__call__): torchaudio resample to hr_sampling_rate

@@ -17,6 +17,11 @@
 // entry point (GSV_WITH_T); every launch is written once (GSV_LAUNCH).
 #include "engine.h"
 
+#include <algorithm>
+#include <utility>
+
+#include "align.h"
+
 namespace gsv {
 
 // ---------------------------------------------------------------------------------------
@@ -267,6 +272,12 @@ struct gsv_vits : gsveng::Ctx {
   gsveng::SegUpload seg;                        // maps and noise keys of the last segmented decode
   hipStream_t ref_stream = nullptr;             // stream of the last set_refer (store_voice copies on it, then records ev[3])
   gsveng::GenTap dbg_last;                      // input of the last generator stage (intact after a decode) for the debug hook
+  // gsv_vits_set_align: the table pending for the next decode (consumed by it), and where its results go
+  std::vector<gsv_align_seg_span_t> align_req;
+  int32_t* align_ends = nullptr;
+  float* align_score = nullptr;
+  gsveng::SegUpload align_up;                   // host image of the device span table (maps: 6 ints per span)
+  int lastF0 = 0, lastL = 0;                    // rows of m_q / m_kv of the last enc_p (debug hook)
   // last decode bookkeeping
   int lastF = 0;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -412,6 +423,64 @@ static int conv_voice(gsv_vits* h, hipStream_t s, const Conv& c, const void* x, 
   return GSV_OK;
 }
 
+// The pending alignment table (gsv_vits_set_align) in the rows of this pass: span r of segment g covers frames
+// f0[g] + 2 code0 .. + 2 n_codes of m_q and phones l0[g] + phone0 .. + n_phones of m_kv (the layout's gap rows included in f0 / l0),
+// and writes ends[sum of the n_phones in front of it ..].  Checked before anything is launched; the table is consumed either way.
+static int align_prepare(gsv_vits* h, int Tc, int L, const SegRun* sr, std::vector<gsv_align_seg_span_t>* req) {
+  req->swap(h->align_req);
+  h->align_req.clear();
+  const int n = (int)req->size();
+  if (!n) return GSV_OK;
+  const int nseg = sr ? sr->lay->n : 1;
+  GSV_RC(seg_upload_begin(&h->align_up));   // the previous table's upload is done before its host image is rewritten
+  std::vector<int>& img = h->align_up.maps;
+  img.assign((size_t)n * 6, 0);
+  std::vector<std::pair<long long, int>> order(n);
+  int out0 = 0;
+  for (int r = 0; r < n; ++r) {
+    const gsv_align_seg_span_t& a = (*req)[r];
+    GSV_REQUIRE(a.segment >= 0 && a.segment < nseg, "vits align: span %d names segment %d of %d", r, a.segment, nseg);
+    const int g = a.segment;
+    const int codes = sr ? sr->lay->nf[g] / 2 : Tc;
+    const int phones = !sr ? L : (g + 1 < nseg ? sr->lay->l0[g + 1] - sr->lay->G : sr->lay->L) - sr->lay->l0[g];
+    GSV_REQUIRE(a.code0 >= 0 && a.n_codes >= 0 && a.code0 <= codes && a.n_codes <= codes - a.code0,
+                "vits align: span %d covers codes [%d, +%d) of a segment of %d", r, a.code0, a.n_codes, codes);
+    GSV_REQUIRE(a.phone0 >= 0 && a.n_phones >= 0 && a.phone0 <= phones && a.n_phones <= phones - a.phone0,
+                "vits align: span %d covers phones [%d, +%d) of a segment of %d", r, a.phone0, a.n_phones, phones);
+    int* d = &img[(size_t)r * 6];
+    d[0] = (sr ? sr->lay->f0[g] : 0) + 2 * a.code0; d[1] = 2 * a.n_codes;
+    d[2] = (sr ? sr->lay->l0[g] : 0) + a.phone0;   d[3] = a.n_phones;
+    d[4] = out0;
+    out0 += a.n_phones;
+    order[r] = {(long long)d[2], r};
+  }
+  std::sort(order.begin(), order.end());
+  long long end = -1;   // the furthest end of the non-empty spans so far, and the span that reaches it
+  int last = -1;
+  for (int i = 0; i < n; ++i) {
+    const int b = order[i].second, l0 = img[(size_t)b * 6 + 2], nl = img[(size_t)b * 6 + 3];
+    if (nl == 0) continue;             // an empty span holds no phoneme
+    GSV_REQUIRE(l0 >= end, "vits align: spans %d and %d overlap in phonemes", last, b);
+    end = (long long)l0 + nl;
+    last = b;
+  }
+  return GSV_OK;
+}
+
+// the two alignment launches on m_q [F0][MH] / m_kv [L][2 MH] (keys = the first MH columns), read in place
+static int align_run(gsv_vits* h, hipStream_t s, int n, const void* q, const void* kv, int MH) {
+  const gsv_align_span_t* img = reinterpret_cast<const gsv_align_span_t*>(h->align_up.maps.data());
+  const long long bytes = gsv_op_align_workspace(n, img, nullptr);
+  GSV_REQUIRE(bytes > 0, "vits align: bad span table");
+  void *tab, *ws;
+  GSV_RC(need(h, "align_tab", (size_t)n * sizeof(gsv_align_span_t), &tab));
+  GSV_RC(need(h, "align_ws", (size_t)bytes, &ws));
+  GSV_HIP(hipMemcpyAsync(tab, img, (size_t)n * sizeof(gsv_align_span_t), hipMemcpyHostToDevice, s));
+  GSV_HIP(hipEventRecord(h->align_up.ev, s));
+  GSV_RC(launch_align_logp(h->dtype, q, MH, kv, 2 * MH, 4, MH / 4, 1.f / sqrtf((float)(MH / 4)), (const gsv_align_span_t*)tab, n, ws, bytes, s));
+  return launch_align_path((const gsv_align_span_t*)tab, n, ws, bytes, h->align_ends, h->align_score, s);
+}
+
 // quantizer.decode + nearest x2 (H8) and TextEncoder.forward up to (and including) the speed interpolation (H10, reference
 // module/models.py:199-231): returns the hidden sequence y [F][hidden] (what `enc_p` returns as its first value)
 // sr != null: segmented, Tc / L / speed are ignored for the padded totals of sr->lay (in) and sr->post (out)
@@ -424,6 +493,9 @@ int run_enc_p(gsv_vits* h, hipStream_t s, const int32_t* codes, int Tc, const in
   if (sr) L = sr->lay->L;
   const int F0 = sr ? sr->lay->F : 2 * Tc;
   const int F = sr ? sr->post->F : speed == 1.0 ? F0 : (int)((double)F0 / speed) + 1;   // frames after the speed interpolation
+  std::vector<gsv_align_seg_span_t> align;
+  GSV_RC(align_prepare(h, Tc, L, sr, &align));
+  h->lastF0 = F0; h->lastL = L;
   // ---- H8: codebook gather + nearest x2
   void *q768, *y, *tx;
   GSV_RC(need(h, "q768", (size_t)F0 * SSL * es, &q768));
@@ -453,6 +525,7 @@ int run_enc_p(gsv_vits* h, hipStream_t s, const int32_t* codes, int Tc, const in
     GSV_RC(conv(h, s, h->mkv, t512, MH, L, kv512, L, o));
     GSV_RC(attention(h, s, q512, MH, 0, kv512, 2 * MH, 0, MH, F0, L, 4, MH / 4, 1.f / sqrtf((float)(MH / 4)), nullptr, nullptr, o512, MH,
                      sr ? sr->kr_x : nullptr));
+    if (!align.empty()) GSV_RC(align_run(h, s, (int)align.size(), q512, kv512, MH));
     ConvOpt om; om.res = s512; om.ldr = MH;
     GSV_RC(conv_voice(h, s, h->mo, o512, F0, x512, om, h->mo_bias_eff, sr, 0, seg_f));
     GSV_RC(conv(h, s, h->c_post, x512, MH, F0, y, F0, o));
@@ -1028,6 +1101,17 @@ int gsv_vits_decode_encp(gsv_vits_t* h, const int32_t* codes, int Tc, const int3
   return GSV_WITH_T(h, decode_encp<T>(h, (hipStream_t)stream, codes, Tc, phones, L, speed, fea));
 }
 
+int gsv_vits_set_align(gsv_vits_t* h, const gsv_align_seg_span_t* spans, int n, int32_t* ends, float* score) {
+  GSV_REQUIRE(h && h->finalized, "vits_set_align: handle not finalized");
+  h->align_req.clear();
+  if (!spans || n == 0) return GSV_OK;
+  GSV_REQUIRE(n > 0 && n <= ALIGN_MAX_SPANS && ends && score, "vits_set_align: %d spans, or no place for the results", n);
+  h->align_req.assign(spans, spans + n);
+  h->align_ends = ends;
+  h->align_score = score;
+  return GSV_OK;
+}
+
 int gsv_vits_last_timing(gsv_vits_t* h, float* total_ms, float* generator_ms) {
   GSV_REQUIRE(h && h->finalized && h->lastF > 0, "vits_last_timing: no decode yet");
   GSV_HIP(hipEventSynchronize(h->ev[2]));
@@ -1057,6 +1141,13 @@ int gsv_vits_debug_tensor(gsv_vits_t* h, const char* name, float* out, int64_t c
     *numel = c.gin_channels;
     return GSV_OK;
   }
+  if (n == "m_q" || n == "m_kv") {   // the MRTE attention's operands of the last enc_p: [512][F0] / [1024][L]
+    const int rows = n == "m_q" ? h->lastF0 : h->lastL, C = n == "m_q" ? 512 : 1024;
+    GSV_REQUIRE(rows > 0, "vits_debug_tensor: no decode yet");
+    GSV_REQUIRE(cap >= (int64_t)rows * C, "vits_debug_tensor: buffer too small");
+    *numel = (int64_t)rows * C;
+    return GSV_WITH_T(h, debug_cl_to_cf<T>(s, h->bufs[n].p, rows, C, out));
+  }
   GSV_REQUIRE(F > 0, "vits_debug_tensor: no decode yet");
   if (n == "gen_last_in") {        // input of the last generator stage, [C][T] (segmented decode: its gap rows are 0)
     const GenTap& tap = h->dbg_last;
@@ -1073,7 +1164,7 @@ int gsv_vits_debug_tensor(gsv_vits_t* h, const char* name, float* out, int64_t c
     return GSV_OK;
   }
   if (n == "z") return GSV_WITH_T(h, debug_cl_to_cf<T>(s, h->bufs["z_keep"].p, F, IC, out));
-  set_error("vits_debug_tensor: unknown tensor '%s' (ge, m_p, logs_p, z, gen_last_in)", name);
+  set_error("vits_debug_tensor: unknown tensor '%s' (ge, m_p, logs_p, z, gen_last_in, m_q, m_kv)", name);
   return GSV_ERR_ARG;
 }
 

@@ -33,6 +33,7 @@ from ..AR.models.t2s_model import Text2SemanticDecoder
 from .._lib import CFM_SESSION_MAX_ROWS
 from ..module.models import CFM, SynthesizerTrn, SynthesizerTrnV3, cfg_guided
 from ..process_ckpt import load_sovits_new  # noqa: F401  (reference process_ckpt.py:129-138; re-exported)
+from ..timestamps import build_marks
 
 
 spec_min, spec_max = -12, 2          # reference TTS.py:55-56
@@ -323,6 +324,9 @@ class TTS:
         # "loudness": [{"lufs", "gain_db", "gain", "limited"} per span] per fragment delivered with it by the last run() /
         # run_batch(), or by the last audio_postprocess / postprocess_fragments call made directly (a server: its last call)
         self.last_loudness: list = []
+        # speech marks of the last call (replaced, never extended): after run() the marks of the request, one record per sentence
+        # ([] without "timestamps"; with return_fragment the last fragment's); after run_batch() one such list per request
+        self.last_timestamps: list = []
         self.last_candidates: list = []              # "best_of": the choices of the last run / run_batch call, [request][batch][sentence]
 
     # ---- weights (reference TTS.py:484-603) ------------------------------------------------
@@ -893,7 +897,7 @@ class TTS:
             return zero_cache[k]
 
         for index_list in batch_index_list:
-            phones_list, phones_len, all_phones, all_len, all_bert, texts = [], [], [], [], [], []
+            phones_list, phones_len, all_phones, all_len, all_bert, texts, w2p = [], [], [], [], [], [], []
             max_len = 0
             for idx in index_list:
                 it = data[idx]
@@ -922,10 +926,12 @@ class TTS:
                 all_len.append(ap.shape[-1])
                 all_bert.append(ab)
                 texts.append(it["norm_text"])
+                w2p.append(it.get("word2ph"))
             batches.append({
                 "phones": phones_list, "phones_len": torch.LongTensor(phones_len).to(device),
                 "all_phones": all_phones, "all_phones_len": torch.LongTensor(all_len).to(device),
                 "all_bert_features": all_bert, "norm_text": texts, "max_len": max_len,
+                **({"word2ph": w2p} if any(w is not None for w in w2p) else {}),     # zh: phonemes per character (section 4w)
             })
         return batches, batch_index_list
 
@@ -1191,7 +1197,8 @@ class TTS:
     @torch.no_grad()
     def using_vocoder_synthesis(self, semantic_tokens: torch.Tensor, phones: torch.Tensor, speed: float = 1.0,
                                 sample_steps: int = 32, seed: int = 0, noise_fn: Optional[Callable] = None,
-                                inference_cfg_rate: float = 0, lora_voice: Optional[str] = None) -> torch.Tensor:
+                                inference_cfg_rate: float = 0, lora_voice: Optional[str] = None,
+                                align_out: Optional[list] = None) -> torch.Tensor:
         """TTS.py:1431-1494: one fragment; the mel is generated chunk by chunk, each chunk prompted with the tail of the
         previous one.  `noise_fn(call_index, shape)` (tests) pins the randn draw of each cfm.inference call.
         `inference_cfg_rate` is CFM.inference_guided's (the reference passes 0 here: CFM.inference).  `lora_voice`: a name
@@ -1200,7 +1207,10 @@ class TTS:
         lora_kw = {} if slot is None else dict(adapters=[slot])
         spec, fea_ref, ge, mel2, T_min = self._prompt_features(lora_voice)
         chunk_len = self.vocoder_configs["T_chunk"] - T_min
-        fea_todo, ge = enc_model.decode_encp(semantic_tokens, phones, spec, ge, speed)
+        # align_out (a list): the sentence's phoneme alignment (frames, ends, score) is appended to it
+        fea_todo, ge = enc_model.decode_encp(semantic_tokens, phones, spec, ge, speed, **({} if align_out is None else {"align": True}))
+        if align_out is not None:
+            align_out.append((2 * int(semantic_tokens.shape[-1]),) + enc_model.last_alignment[0])
         outs, pos, call = [], 0, 0
         while True:
             chunk = fea_todo[:, :, pos:pos + chunk_len]
@@ -1222,13 +1232,14 @@ class TTS:
     def using_vocoder_synthesis_batched_infer(self, idx_list: List[int], semantic_tokens_list: List[torch.Tensor],
                                               batch_phones: List[torch.Tensor], speed: float = 1.0, sample_steps: int = 32,
                                               seed: int = 0, noise_fn: Optional[Callable] = None,
-                                              inference_cfg_rate: float = 0, lora_voice: Optional[str] = None) -> List[torch.Tensor]:
+                                              inference_cfg_rate: float = 0, lora_voice: Optional[str] = None,
+                                              align_out: Optional[list] = None) -> List[torch.Tensor]:
         """TTS.py:1496-1609: all fragments of a batch concatenated, cut into overlapping chunks that go through ONE
         batched cfm.inference, vocoded as one sequence, re-joined with SOLA and split back per fragment.  `lora_voice` as in
         using_vocoder_synthesis: every row of the pass takes its adapter."""
         slot = None if lora_voice is None else self._lora_voice(lora_voice)[1]
         prompt = self._prompt_features(lora_voice)
-        fea, lens, pad_len = self._fold_chunks(prompt, idx_list, semantic_tokens_list, batch_phones, speed, lora_voice)
+        fea, lens, pad_len = self._fold_chunks(prompt, idx_list, semantic_tokens_list, batch_phones, speed, lora_voice, align_out)
         mel2 = prompt[3]
         nz = noise_fn(0, (fea.shape[0], 100, fea.shape[1])) if noise_fn else None
         lora_kw = {} if slot is None else dict(adapters=[slot] * int(fea.shape[0]))
@@ -1251,7 +1262,7 @@ class TTS:
 
     def _fold_chunks(self, prompt: tuple, idx_list: List[int], semantic_tokens_list: List[torch.Tensor],
                      batch_phones: List[torch.Tensor], speed: float,
-                     lora_voice: Optional[str] = None) -> Tuple[torch.Tensor, List[int], int]:
+                     lora_voice: Optional[str] = None, align_out: Optional[list] = None) -> Tuple[torch.Tensor, List[int], int]:
         """the CFM input rows of one fold with the voice of `prompt` (= _prompt_features(lora_voice)): [chunks, T_chunk, 512],
         every row the voice's fea_ref followed by one chunk; the sentences' frame counts; the padding of the last chunk"""
         enc_model = self.vits_model if lora_voice is None else self._lora_voice(lora_voice)[0]
@@ -1260,7 +1271,10 @@ class TTS:
         chunk_len, ov = vc["T_chunk"] - T_min, vc["overlapped_len"]
         feats, lens = [], []
         for i, idx in enumerate(idx_list):
-            f, _ = enc_model.decode_encp(semantic_tokens_list[i][-idx:].view(1, 1, -1), batch_phones[i].view(1, -1), spec, ge, speed)
+            f, _ = enc_model.decode_encp(semantic_tokens_list[i][-idx:].view(1, 1, -1), batch_phones[i].view(1, -1), spec, ge, speed,
+                                         **({} if align_out is None else {"align": True}))
+            if align_out is not None:          # as in using_vocoder_synthesis
+                align_out.append((2 * int(idx),) + enc_model.last_alignment[0])
             feats.append(f)
             lens.append(int(f.shape[2]))
         padded = F.pad(torch.cat(feats, 2), (ov, 0))
@@ -1458,13 +1472,17 @@ class TTS:
 
     def _synthesize_batch(self, item: dict, pred: List[torch.Tensor], pred_list: List[torch.Tensor], idx_list: List[int],
                           bi: int, actual_seed: int, opts: dict, voice_refer: Tuple[List[torch.Tensor], dict],
-                          have: Optional[List[Optional[torch.Tensor]]] = None) -> List[torch.Tensor]:
+                          have: Optional[List[Optional[torch.Tensor]]] = None,
+                          align_out: Optional[list] = None) -> List[torch.Tensor]:
         """run()'s post-AR stage of one to_batch batch `bi` (reference TTS.py:1259-1299): the fragments of its sentences from
         the generated tokens (`pred`, `idx_list` = _kept_tokens(`pred_list`, ...)), with the voice of self.prompt_cache
         (v3/v4) / `voice_refer` = _voice_refer(voice) (v1/v2/v2Pro), speed_factor, parallel_infer, sample_steps and
         inference_cfg_rate (v3/v4 only) of the resolved `opts`, and the seed actual_seed + bi.  `have` (v1/v2/v2Pro at
-        speed_factor != 1 only): the sentences a shared pass already decoded, None where it left one out."""
+        speed_factor != 1 only): the sentences a shared pass already decoded, None where it left one out.  `align_out` (a list;
+        "timestamps": "phone"): one (frames, ends, score) per sentence is appended, the phoneme alignment
+        the SoVITS engine computes in the same pass; the audio does not depend on it."""
         speed_factor, seed_b = opts["speed_factor"], actual_seed + bi
+        al_kw = {} if align_out is None else {"align_out": align_out}
         refer, sv_kw = voice_refer
         frags: List[torch.Tensor] = []
         if self.configs.use_vocoder:                                    # TTS.py:1283-1299
@@ -1473,11 +1491,11 @@ class TTS:
             if opts.get("lora_voice") is not None:
                 cfm_kw["lora_voice"] = opts["lora_voice"]
             if opts["parallel_infer"]:
-                frags = self.using_vocoder_synthesis_batched_infer(idx_list, pred_list, dev_ph, seed=seed_b, **cfm_kw)
+                frags = self.using_vocoder_synthesis_batched_infer(idx_list, pred_list, dev_ph, seed=seed_b, **cfm_kw, **al_kw)
             else:
                 for k, idx in enumerate(idx_list):
                     frags.append(self.using_vocoder_synthesis(pred_list[k][-idx:].view(1, 1, -1), dev_ph[k].view(1, -1),
-                                                              seed=actual_seed + bi * 4096 + k, **cfm_kw))
+                                                              seed=actual_seed + bi * 4096 + k, **cfm_kw, **al_kw))
         elif speed_factor == 1.0:
             # one decode over the batch folded into the time axis (TTS.py:1259-1282)
             cut = [int(p.shape[0]) * 2 * math.prod(self.vits_model.upsample_rates) for p in pred]
@@ -1485,17 +1503,32 @@ class TTS:
             if keep:
                 all_pred = torch.cat([pred[k] for k in keep]).view(1, 1, -1)
                 all_ph = torch.cat([item["phones"][k] for k in keep]).view(1, -1)
-                wav = self.vits_model.decode(all_pred, all_ph, refer, speed=speed_factor, seed=seed_b, **sv_kw)[0, 0]
+                spans, c0, p0 = [], 0, 0       # the fold's sentences back to back: one alignment span each
+                for k in keep:
+                    spans.append((c0, int(pred[k].shape[0]), p0, int(item["phones"][k].shape[0])))
+                    c0, p0 = c0 + spans[-1][1], p0 + spans[-1][3]
+                wav = self.vits_model.decode(all_pred, all_ph, refer, speed=speed_factor, seed=seed_b, **sv_kw,
+                                             **({} if align_out is None else {"align": spans}))[0, 0]
             else:
                 wav = torch.zeros(0, dtype=self.precision, device=self.configs.device)
+            if align_out is not None:
+                got = iter(self.vits_model.last_alignment if keep else [])
+                for k, p in enumerate(pred):   # a sentence without tokens: no frames, every phoneme empty
+                    align_out.append((2 * int(p.shape[0]),) + (next(got) if k in keep else
+                                                               (np.zeros(int(item["phones"][k].shape[0]), np.int32), float("-inf"))))
             frags = list(torch.split(wav, cut))        # decode gives exactly 2 * up samples per token at speed 1
         else:
             for k, p in enumerate(pred):
                 if have is not None and have[k] is not None:
                     frags.append(have[k])
+                    if align_out is not None:
+                        align_out.append(None)          # the shared pass that decoded it holds its alignment
                     continue
                 frags.append(self.vits_model.decode(p.view(1, 1, -1), item["phones"][k].view(1, -1), refer,
-                                                    speed=speed_factor, seed=seed_b, **sv_kw)[0, 0])
+                                                    speed=speed_factor, seed=seed_b, **sv_kw,
+                                                    **({} if align_out is None else {"align": True}))[0, 0])
+                if align_out is not None:
+                    align_out.append((2 * int(p.shape[0]),) + self.vits_model.last_alignment[0])
         return frags
 
     # ---- several voices in one AR decode -----------------------------------------------------------
@@ -1727,6 +1760,11 @@ class TTS:
             o["loudness"], o["loudness_scope"], o["loudness_peak"] = float(target), scope, float(peak)
         elif req.get("loudness_scope") is not None or req.get("loudness_peak") is not None:
             raise ValueError("loudness_scope / loudness_peak without \"loudness\": name the target in LUFS")
+        ts = req.get("timestamps")                # speech marks: carried only when the request asks
+        if ts is not None and ts is not False:
+            if ts not in ("sentence", "phone"):
+                raise ValueError(f"timestamps {ts!r}: False, \"sentence\" or \"phone\"")
+            o["timestamps"] = ts
         return o
 
     @staticmethod
@@ -1962,7 +2000,7 @@ class TTS:
         return passes
 
     # ---- run_batch's stages: a plan is one request's dict, and a stage reads what the earlier ones wrote on it
-    def _plan_request(self, req: dict, fragments: bool = False) -> dict:
+    def _plan_request(self, req: dict, fragments: bool = False, timestamps: bool = False) -> dict:
         """Stage 1, per request, what run() does before its AR loop.  Reads the request and seeds the host generators (after
         the voice is resolved).  Writes the plan: `opts`, `voice`, `actual_seed`, `data` / `index` (to_batch), `no_prompt`,
         `P` (prompt tokens) and `frags`, one slot per to_batch batch for its sentences' waveforms, filled by later stages.
@@ -1970,6 +2008,8 @@ class TTS:
         o = self._resolve_options(req)
         if o["return_fragment"] and not fragments:
             raise ValueError("run_batch returns whole utterances: return_fragment=True is not supported")
+        if "timestamps" in o and not timestamps:      # timestamps=True: run_batch, which returns the marks
+            raise ValueError("this caller returns (sr, audio): it does not pass timestamps=True, so it cannot return the marks")
         voice = self._request_voice(req)
         actual_seed = set_seed(o["seed"])
         segments = self._segments(req)
@@ -1982,7 +2022,8 @@ class TTS:
             segments, prompt_data=prompt_data, batch_size=o["batch_size"], threshold=o["batch_threshold"],
             split_bucket=o["split_bucket"], device=torch.device("cpu"), precision=self.precision)
         return dict(voice=voice, opts=o, actual_seed=actual_seed, data=data, index=index, no_prompt=no_prompt,
-                    P=0 if no_prompt else int(voice["prompt_semantic"].numel()), frags=[None] * len(data))
+                    P=0 if no_prompt else int(voice["prompt_semantic"].numel()), frags=[None] * len(data),
+                    **({"align": [[None] * len(item["phones"]) for item in data]} if o.get("timestamps") == "phone" else {}))
 
     @staticmethod
     def plan_sessions(launches: List[List[dict]]) -> List[Tuple[bool, List[dict]]]:
@@ -2088,11 +2129,16 @@ class TTS:
         launches = self.plan_sovits_rows(plans) if shared_speed else [[(r, bi, -1) for r, bi in launch]
                                                                       for launch in self.plan_sovits(plans)]
         for launch in launches:
-            codes, phones, voices, seeds, speeds, cuts = [], [], [], [], [], []
+            codes, phones, voices, seeds, speeds, cuts, align = [], [], [], [], [], [], []
             for r, bi, k in launch:
                 pl = plans[r]
                 pred = pl["kept"][bi][0]
                 keep = [k] if k >= 0 else [j for j, p_ in enumerate(pred) if p_.shape[0] > 0]
+                spans, c0, p0 = [], 0, 0        # "timestamps": "phone": one alignment span per sentence of the segment
+                for j in keep if "align" in pl else []:
+                    spans.append((c0, int(pred[j].shape[0]), p0, int(pl["data"][bi]["phones"][j].shape[0]), j))
+                    c0, p0 = c0 + spans[-1][1], p0 + spans[-1][3]
+                align.append(spans)
                 codes.append(torch.cat([pred[j] for j in keep]).view(1, 1, -1))
                 phones.append(torch.cat([pl["data"][bi]["phones"][j] for j in keep]).view(1, -1))
                 vk = self._voice_key(pl["voice"])
@@ -2104,7 +2150,13 @@ class TTS:
                 speeds.append(pl["opts"]["speed_factor"] if k >= 0 else 1.0)
                 cuts.append([int(p_.shape[0]) * 2 * up for p_ in pred])
             speed_kw = {} if all(v == 1.0 for v in speeds) else dict(speeds=speeds)
-            wavs = self.vits_model.decode_segments(codes, phones, voices, seeds, **speed_kw)
+            marked = any(align)
+            wavs = self.vits_model.decode_segments(codes, phones, voices, seeds, **speed_kw,
+                                                   **({"align": [[sp[:4] for sp in a] for a in align]} if marked else {}))
+            got = iter(self.vits_model.last_alignment if marked else [])
+            for (r, bi, k), a in zip(launch, align):
+                for c0, nc, p0, nph, j in a:
+                    plans[r]["align"][bi][j] = (2 * nc,) + next(got)
             for (r, bi, k), wav, cut in zip(launch, wavs, cuts):
                 if k < 0:
                     plans[r]["frags"][bi] = list(torch.split(wav[0, 0], cut))
@@ -2201,9 +2253,13 @@ class TTS:
                     idx_list = pl["kept"][bi][1]
                     if sum(int(i) for i in idx_list) <= 0:
                         continue
+                    al = [] if "align" in pl else None       # "timestamps": "phone": decode_encp aligns each sentence (4w)
                     fold_in[(r, bi)] = self._fold_chunks(prompt, idx_list, pl["preds"][bi],
                                                          [ph.to(self.configs.device) for ph in item["phones"]],
-                                                         pl["opts"]["speed_factor"], *([] if lora is None else [lora]))
+                                                         pl["opts"]["speed_factor"], *([] if lora is None else [lora]),
+                                                         **({} if al is None else {"align_out": al}))
+                    if al is not None:
+                        pl["align"][bi] = al
                     pl["cfm_folds"][bi] = sum(fold_in[(r, bi)][1])
         return prompts, fold_in, voice_of
 
@@ -2249,12 +2305,45 @@ class TTS:
             voice_refer = self._voice_refer(voice)
             for bi, item in enumerate(pl["data"]):
                 if pl["frags"][bi] is None or any(f is None for f in pl["frags"][bi]):
-                    pred, idx_list = pl["kept"][bi]
-                    pl["frags"][bi] = self._synthesize_batch(item, pred, pl["preds"][bi], idx_list, bi, pl["actual_seed"], o,
-                                                             voice_refer, have=pl["frags"][bi])
+                    self._synthesize_fold(pl, bi, voice_refer)
             self._wait_stream()
-            return self.audio_postprocess(pl["frags"], sr, pl["index"], o["speed_factor"], o["split_bucket"],
-                                          o["fragment_interval"], o["super_sampling"], **self._format_kw(o))
+            result = self.audio_postprocess(pl["frags"], sr, pl["index"], o["speed_factor"], o["split_bucket"],
+                                            o["fragment_interval"], o["super_sampling"], **self._format_kw(o))
+            if "timestamps" not in o:
+                return result
+            # speech marks, as run() builds them
+            sents = [s for bi in range(len(pl["data"])) for s in self._fold_sentences(pl, bi)]
+            order = sorted(range(len(sents)), key=lambda i: sents[i]["index"]) if o["split_bucket"] else None
+            marks = build_marks(sents, sr, int(self.configs.sampling_rate * o["fragment_interval"]), order=order)
+            return result + (marks,)
+
+    @staticmethod
+    def _fold_sentences(pl: dict, bi: int) -> List[dict]:
+        """build_marks' input for the sentences of fold `bi` of a planned request whose waveforms exist (`frags[bi]`): index,
+        text, samples and, with "timestamps": "phone", the alignment its waveform pass left in `align[bi]`"""
+        item, sents = pl["data"][bi], []
+        for k, f in enumerate(pl["frags"][bi]):
+            s = dict(index=pl["index"][bi][k], text=item["norm_text"][k], n_samples=int(f.shape[0]))
+            if "align" in pl:
+                a = pl["align"][bi][k]
+                if a is None:               # a sentence without tokens inside a shared fold: no frames, every phoneme empty
+                    a = (0, np.zeros(int(item["phones"][k].shape[0]), np.int32), float("-inf"))
+                s.update(phones=item["phones"][k].tolist(), nf=a[0], ends=a[1], score=a[2])
+            w2p = pl["data"][bi].get("word2ph")
+            if w2p is not None and w2p[k] is not None:
+                s["word2ph"] = w2p[k]
+            sents.append(s)
+        return sents
+
+    def _synthesize_fold(self, pl: dict, bi: int, voice_refer) -> None:
+        """`frags[bi]` of a planned request through _synthesize_batch where a shared stage left the fold or some of its sentences
+        out, with the alignment of what it decodes merged into `align[bi]` (the shared pass holds the rest)"""
+        pred, idx_list = pl["kept"][bi]
+        al = [] if "align" in pl else None
+        pl["frags"][bi] = self._synthesize_batch(pl["data"][bi], pred, pl["preds"][bi], idx_list, bi, pl["actual_seed"], pl["opts"],
+                                                 voice_refer, have=pl["frags"][bi], **({} if al is None else {"align_out": al}))
+        if al is not None:
+            pl["align"][bi] = [a if a is not None else b for a, b in zip(al, pl["align"][bi])]
 
     def _output_sr(self) -> int:
         """the rate of the waveform stage: the SoVITS model's, v3 / v4 the vocoder's (which must be loaded)"""
@@ -2327,7 +2416,9 @@ class TTS:
             requests = self._with_shared_segments(requests)
         if shared_hubert or shared_sv:
             requests = self._with_shared_voices(requests, shared_sv=shared_sv, device_frontend=device_frontend)
-        plans = [self._plan_request(req) for req in requests]
+        # the keyword goes along only with a request that brings the key: a stage that predates it (a subclass, a stub) keeps working
+        plans = [self._plan_request(req, **({} if req.get("timestamps") in (None, False) else {"timestamps": True}))
+                 for req in requests]
         self._ar_stage(plans, mixed_sampling=mixed_sampling, **({"continuous_ar": True} if continuous_ar else {}),
                        **({"mixed_limits": True} if mixed_limits else {}))
         self.last_candidates = [pl.get("candidates", []) for pl in plans]
@@ -2344,6 +2435,7 @@ class TTS:
             results.append(self._finish_request(pl, sr))
             reports += self.last_loudness
         self.last_loudness = reports
+        self.last_timestamps = [res[2] if isinstance(res, tuple) and len(res) == 3 else [] for res in results]      # per request, [] without the key
         return results
 
     def serve(self, **scheduler_kw):
@@ -2375,6 +2467,9 @@ class TTS:
             check_best_of(o, prompt_data is None)
             self.last_candidates = [[]] if "best_of" in o else []
             self.last_loudness, loud_reports = [], []
+            ts, sents, ts_offset = o.get("timestamps"), [], 0.0          # speech marks
+            self.last_timestamps = []
+            ts_gap = int(self.configs.sampling_rate * o["fragment_interval"])      # audio_postprocess's
             t1 = time.perf_counter()
             # token ids stay on the host here: the engines pack a whole batch and move it with ONE copy
             # (the reference's per-item .to(device), TTS.py:899-912, is ~75 tiny transfers per batch of 32)
@@ -2409,7 +2504,15 @@ class TTS:
                 t_34 += t4 - t3
                 pred, idx_list = self._kept_tokens(pred_list, idx_list, no_prompt)
                 self.last_generated_tokens += int(sum(idx_list))
-                frags = self._synthesize_batch(item, pred, pred_list, idx_list, bi, actual_seed, o, voice_refer)
+                al = [] if ts == "phone" else None
+                frags = self._synthesize_batch(item, pred, pred_list, idx_list, bi, actual_seed, o, voice_refer,
+                                               **({} if al is None else {"align_out": al}))
+                if ts:
+                    fold = [dict(index=batch_index_list[bi][k], text=item["norm_text"][k], n_samples=int(f.shape[0]),
+                                 **({} if al is None else dict(phones=item["phones"][k].tolist(), nf=al[k][0], ends=al[k][1],
+                                                               score=al[k][2])),
+                                 **({} if item.get("word2ph") is None or item["word2ph"][k] is None
+                                    else {"word2ph": item["word2ph"][k]})) for k, f in enumerate(frags)]
                 self._wait_stream()
                 t5 = time.perf_counter()
                 t_45 += t5 - t4
@@ -2419,9 +2522,16 @@ class TTS:
                     if "loudness" in o:                                 # one report list per fragment, gathered over the run
                         loud_reports += self.last_loudness
                         self.last_loudness = loud_reports
+                    if ts:        # times relative to the fragment, and where the fragment starts in the request's stream
+                        marks = [dict(m, offset=ts_offset) for m in build_marks(fold, sr, ts_gap)]
+                        ts_offset += sum(s["n_samples"] + ts_gap for s in fold) / sr
+                        self.last_timestamps = marks
+                        frag = frag + (marks,)
                     yield frag
                 else:
                     audio.append(frags)
+                    if ts:
+                        sents += fold
                 if self.stop_flag:
                     yield silence()
                     return
@@ -2434,6 +2544,10 @@ class TTS:
                 result = self.audio_postprocess(audio, sr, batch_index_list, o["speed_factor"], o["split_bucket"],
                                                 o["fragment_interval"], o["super_sampling"], **self._format_kw(o))
                 self.last_postprocess_s = time.perf_counter() - t6
+                if ts:            # output order: submission order when the buckets are put back, else batch order
+                    order = sorted(range(len(sents)), key=lambda i: sents[i]["index"]) if o["split_bucket"] else None
+                    self.last_timestamps = build_marks(sents, sr, ts_gap, order=order)
+                    result = result + (self.last_timestamps,)
                 yield result
         except Exception as e:
             traceback.print_exc()

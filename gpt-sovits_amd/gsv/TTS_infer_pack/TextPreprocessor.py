@@ -95,6 +95,15 @@ def script_segmenter(text: str, default_lang: Optional[str] = None) -> List[Dict
     return out
 
 
+def sentence_word2ph(runs, phones, norm_text):
+    """phonemes per character of a whole sentence from the word2ph of its runs: their concatenation when every run has one (zh)
+    and it covers the sentence's text and phones, else None"""
+    if not runs or any(w is None for w in runs):
+        return None
+    w2p = [int(v) for w in runs for v in w]
+    return w2p if len(w2p) == len(norm_text) and sum(w2p) == len(phones) else None
+
+
 class TextPreprocessor:
     def __init__(self, bert_fn: Optional[Callable[[str], torch.Tensor]] = None, device="cpu",
                  lang_segmenter: Callable[[str, Optional[str]], List[Dict[str, str]]] = script_segmenter):
@@ -113,6 +122,9 @@ class TextPreprocessor:
             if phones is None or norm_text == "":
                 continue
             result.append({"phones": phones, "bert_features": bert_features, "norm_text": norm_text})
+            w2p, self.last_word2ph = getattr(self, "last_word2ph", None), None
+            if w2p is not None:                     # zh: phonemes per character, for the "units" of speech marks
+                result[-1]["word2ph"] = w2p
         return result
 
     # ---- the same for many requests, with the zh BERT features of all of them computed in one call
@@ -154,6 +166,9 @@ class TextPreprocessor:
                         else:
                             berts.append(torch.zeros((1024, n_ph), dtype=torch.float32, device=self.device))
                     segs.append({"phones": phones, "bert_features": torch.cat(berts, dim=1), "norm_text": norm_text})
+                    w2p = sentence_word2ph([r[2] for r in runs], phones, norm_text)
+                    if w2p is not None:
+                        segs[-1]["word2ph"] = w2p
                 result.append(segs)
             return result
 
@@ -204,6 +219,7 @@ class TextPreprocessor:
         return list(bounded(terminated(speakable(pieces))))
 
     def segment_and_extract_feature_for_text(self, text: str, language: str, version: str = "v1"):
+        self.last_word2ph = None
         return self.get_phones_and_bert(text, language, version)
 
     # ---- reference :122-190
@@ -235,13 +251,16 @@ class TextPreprocessor:
             phones: List[int] = []
             berts: List[torch.Tensor] = []
             norm_text = ""
+            w2p: List[Optional[list]] = []
             for lang, piece in self._runs(text, language):
                 ph, word2ph, norm = self.clean_text_inf(piece, lang, version)
                 berts.append(self.get_bert_inf(ph, word2ph, norm, lang))
                 phones += ph
                 norm_text += norm
+                w2p.append(word2ph)
             if not final and len(phones) < 6:                       # too short to synthesise: once more behind a leading stop
                 return self.get_phones_and_bert("." + text, language, version, final=True)
+            self.last_word2ph = sentence_word2ph(w2p, phones, norm_text)      # beside the reference's three return values
             return phones, torch.cat(berts, dim=1), norm_text
 
     # ---- reference :191-204

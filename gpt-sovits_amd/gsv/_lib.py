@@ -37,6 +37,18 @@ class LoudSpan(C.Structure):
     _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("gaps", C.c_int32), ("target", C.c_float), ("peak_db", C.c_float)]
 
 
+class AlignSpan(C.Structure):
+    """gsv_align_span_t: frame rows [f0, f0 + nf) x phoneme rows [l0, l0 + nl) of one alignment; ends go to ends[out0:out0 + nl]"""
+    _fields_ = [(n, C.c_int32) for n in ("f0", "nf", "l0", "nl", "out0", "reserved")]
+
+
+class AlignSegSpan(C.Structure):
+    """gsv_align_seg_span_t: codes [code0, code0 + n_codes) and phones [phone0, phone0 + n_phones) of one segment of a decode"""
+    _fields_ = [(n, C.c_int32) for n in ("segment", "code0", "n_codes", "phone0", "n_phones")]
+
+
+ALIGN_SPAN_DTYPE = [(n, "<i4") for n in ("f0", "nf", "l0", "nl", "out0", "reserved")]   # numpy view of a span table
+
 LOUD_LIMITED, LOUD_NAN, LOUD_SILENT = 1, 2, 4   # gsv_loud_report.flags
 LOUD_REPORT_DTYPE = [("lufs", "<f8"), ("gain", "<f4"), ("flags", "<u4")]   # numpy view of gsv_loud_report [n_spans]
 
@@ -138,6 +150,7 @@ _SIGS = {
     "gsv_vits_extract_latent": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "gsv_vits_debug_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
                                         C.c_void_p]),
+    "gsv_vits_set_align": (C.c_int, [C.c_void_p, C.POINTER(AlignSegSpan), C.c_int, C.c_void_p, C.c_void_p]),
     "gsv_vits_last_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "gsv_vits_store_voice": (C.c_int, [C.c_void_p, C.c_int]),
     "gsv_vits_decode_segments": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int),
@@ -275,6 +288,12 @@ _SIGS = {
     "gsv_op_sample_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(RowSampling),
                                      C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsv_op_token_logprob": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsv_op_align_workspace": (C.c_longlong, [C.c_int, C.POINTER(AlignSpan), C.POINTER(C.c_int64)]),
+    "gsv_op_align_logp": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                    C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "gsv_op_align_path": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsv_op_align": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                               C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTS = tuple(_SIGS)   # every symbol include/gsv.h declares

@@ -36,13 +36,16 @@ def get_tts_wav(t2s: Text2SemanticDecoder, vits: SynthesizerTrn, prompt_semantic
                 prompt_segment: dict, segments, top_k: int = 20, top_p: float = 1.0, temperature: float = 1.0,
                 speed: float = 1.0, hz: int = 50, max_sec: int = 54, pause_second: float = 0.3,
                 sampling_rate: int = 32000, seed: int = 0, loudness: Optional[float] = None, loudness_scope: str = "fragment",
-                loudness_peak: float = 0.0, sample_rate: Optional[int] = None) -> Iterator[Tuple[int, np.ndarray]]:
+                loudness_peak: float = 0.0, sample_rate: Optional[int] = None,
+                timestamps: Optional[list] = None) -> Iterator[Tuple[int, np.ndarray]]:
     """reference inference_webui.py:751-1001 restated for pre-tokenised input; yields (32000, int16).
     loudness (LUFS) and sample_rate are additions: with `loudness` the float sentences and their pauses
     go through audio_io.postprocess_sentences instead of the host conversion -- metered and scaled on the device per fragment
     or per sentence, resampled to `sample_rate` when given, int16 as trunc(x * 32768) saturating -- and (rate, int16) is
-    yielded."""
+    yielded.  timestamps (a list): the speech marks of the output, one record per sentence with its
+    phonemes, are appended to it -- each decode then also aligns its phonemes; the audio does not depend on it."""
     dev = t2s.device
+    sents = []
     zero = np.zeros(int(sampling_rate * pause_second), dtype=np.float32)
     audio = []
     for si, seg in enumerate(segments):
@@ -60,8 +63,13 @@ def get_tts_wav(t2s: Text2SemanticDecoder, vits: SynthesizerTrn, prompt_semantic
         pred = pred[:, -idx:].unsqueeze(0) if idx > 0 else pred[:, :0].unsqueeze(0)
         if pred.shape[-1] == 0:
             continue
-        wav = vits.decode(pred, torch.LongTensor(seg["phones"]).unsqueeze(0), refer_spec, speed=speed,
-                          seed=seed + si)[0, 0].float().cpu().numpy()
+        wav = vits.decode(pred, torch.LongTensor(seg["phones"]).unsqueeze(0), refer_spec, speed=speed, seed=seed + si,
+                          **({} if timestamps is None else {"align": True}))[0, 0].float().cpu().numpy()
+        if timestamps is not None:
+            ends, score = vits.last_alignment[0]
+            sents.append(dict(index=si, text=seg.get("norm_text"), n_samples=int(wav.shape[0]), phones=list(seg["phones"]),
+                              nf=2 * int(pred.shape[-1]), ends=ends, score=score,
+                              **({"word2ph": seg["word2ph"]} if seg.get("word2ph") is not None else {})))
         peak = np.abs(wav).max()
         if peak > 1:
             wav = wav / peak
@@ -69,6 +77,9 @@ def get_tts_wav(t2s: Text2SemanticDecoder, vits: SynthesizerTrn, prompt_semantic
         audio.append(zero)
     if not audio:
         return
+    if timestamps is not None:
+        from .timestamps import build_marks
+        timestamps += build_marks(sents, sampling_rate, zero.shape[0])
     if loudness is not None:
         from .audio_io import postprocess_sentences
         rate = sampling_rate if sample_rate is None else int(sample_rate)
@@ -172,7 +183,8 @@ class _SymbolAny:
 
 def synthesize(GPT_model_path, SoVITS_model_path, ref_audio_path, ref_text_path, ref_language, target_text_path,
                target_language, output_path, bert_path=None, cnhubert_base_path=None, gpu_number="0", is_half=True,
-               frontend=None, sample_rate=None, loudness=None, loudness_scope="fragment", loudness_peak=0.0):
+               frontend=None, sample_rate=None, loudness=None, loudness_scope="fragment", loudness_peak=0.0,
+               timestamps_path=None):
     if frontend is None:
         raise ValueError("pass `frontend` (an object, or a --frontend string for make_frontend): the reference's G2P "
                          "packages are third-party and not part of this build (see the module docstring)")
@@ -198,9 +210,11 @@ def synthesize(GPT_model_path, SoVITS_model_path, ref_audio_path, ref_text_path,
     prompt_semantic, refer_spec = frontend.reference(ref_audio_path, vits)
     prompt_seg = frontend.text_to_segments(ref_text, ref_language)[0]
     segments = frontend.text_to_segments(target_text, target_language)
+    marks = None if timestamps_path is None else []
     result = list(get_tts_wav(t2s, vits, prompt_semantic, refer_spec, prompt_seg, segments,
                               max_sec=s1["config"]["data"]["max_sec"], loudness=loudness, loudness_scope=loudness_scope,
-                              loudness_peak=loudness_peak, sample_rate=sample_rate if loudness is not None else None))
+                              loudness_peak=loudness_peak, sample_rate=sample_rate if loudness is not None else None,
+                              **({} if marks is None else {"timestamps": marks})))
     if result:
         sr, audio = result[-1]
         if sample_rate is not None and int(sample_rate) != sr:       # --sample_rate: resampled on the device
@@ -214,6 +228,12 @@ def synthesize(GPT_model_path, SoVITS_model_path, ref_audio_path, ref_text_path,
             w.setframerate(sr)
             w.writeframes(audio.tobytes())
         print(f"Audio saved to {out}")
+        if marks is not None:                      # --timestamps PATH: the speech marks of output.wav as JSON (seconds)
+            import json
+            from .timestamps import to_json
+            with open(timestamps_path, "w", encoding="utf-8") as f:
+                json.dump(to_json(marks), f, ensure_ascii=False)
+            print(f"Timestamps saved to {timestamps_path}")
 
 
 def main(argv=None):
@@ -240,6 +260,8 @@ def main(argv=None):
                    help="normalise output.wav to this programme loudness in LUFS (ITU-R BS.1770, -70 .. 0; default: off)")
     p.add_argument("--loudness_scope", default="fragment", choices=["fragment", "sentence"],
                    help="what is metered together and gets one gain: the whole output with its pauses, or each sentence")
+    p.add_argument("--timestamps", default=None, metavar="PATH",
+                   help="write the speech marks of output.wav (sentence and phoneme times in seconds, with a confidence) as JSON")
     p.add_argument("--loudness_peak", type=float, default=0.0, help="ceiling of the normalised peak in dBFS (<= 0, default 0)")
     a = p.parse_args(argv)
     if a.sample_rate is not None and a.sample_rate <= 0:
@@ -251,7 +273,7 @@ def main(argv=None):
     synthesize(a.gpt_model, a.sovits_model, a.ref_audio, a.ref_text, a.ref_language, a.target_text, a.target_language,
                a.output_path, a.bert_path, a.cnhubert_base_path, a.gpu_number, str(a.is_half).lower() in ("true", "1"),
                frontend=a.frontend, sample_rate=a.sample_rate, loudness=a.loudness, loudness_scope=a.loudness_scope,
-               loudness_peak=a.loudness_peak)
+               loudness_peak=a.loudness_peak, **({} if a.timestamps is None else {"timestamps_path": a.timestamps}))
 
 
 if __name__ == "__main__":

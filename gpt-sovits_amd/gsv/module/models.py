@@ -139,10 +139,12 @@ class SynthesizerTrn:
 
     @torch.no_grad()
     def decode(self, codes: torch.Tensor, text: torch.Tensor, refer, noise_scale: float = 0.5, speed: float = 1,
-               sv_emb=None, noise: Optional[torch.Tensor] = None, seed: int = 0) -> torch.Tensor:
+               sv_emb=None, noise: Optional[torch.Tensor] = None, seed: int = 0, align=None) -> torch.Tensor:
         """reference models.py:961-1005: codes [1,1,T] int64, text [1,L] int64, refer = tensor or list of
         [1, bins, Tr] spectrograms -> waveform [1, 1, 2T*prod(upsample_rates)].
-        `noise` (optional, [inter, 2T]) injects the randn_like draw of models.py:1000 for parity tests."""
+        `noise` (optional, [inter, 2T]) injects the randn_like draw of models.py:1000 for parity tests.
+        `align` (optional): True = one span over the whole sequence, or spans (code0, n_codes, phone0, n_phones); the phoneme
+        alignment of each goes to `self.last_alignment` (see `_align_begin`).  The waveform does not depend on it."""
         if not self._loaded:
             raise RuntimeError("load_state_dict() first")
         if codes.numel() == 0 or text.numel() == 0:
@@ -161,12 +163,50 @@ class SynthesizerTrn:
             wav = torch.empty(frames * up, dtype=torch.float32, device=self.device)
             # after every conversion above: they are enqueued on torch's current stream, the engine reads on its own
             self.stream.wait_stream(torch.cuda.current_stream(self.device))
-            _lib.check(_lib.lib().gsv_vits_decode(self._h, cd.data_ptr(), T, tx.data_ptr(), L,
-                                                  nz.data_ptr() if nz is not None else None, float(noise_scale),
-                                                  float(speed), int(seed) & 0xFFFFFFFFFFFFFFFF, wav.data_ptr(),
-                                                  C.c_void_p(self.stream.cuda_stream)), "gsv_vits_decode")
-            self.stream.synchronize()
+            pend = self._align_begin([(0,) + tuple(a) for a in ([(0, T, 0, L)] if align is True else align)]) if align else None
+            if align is not None and not align:      # asked for, with no span: no stale result of an earlier call
+                self.last_alignment = []
+            try:
+                _lib.check(_lib.lib().gsv_vits_decode(self._h, cd.data_ptr(), T, tx.data_ptr(), L,
+                                                      nz.data_ptr() if nz is not None else None, float(noise_scale),
+                                                      float(speed), int(seed) & 0xFFFFFFFFFFFFFFFF, wav.data_ptr(),
+                                                      C.c_void_p(self.stream.cuda_stream)), "gsv_vits_decode")
+            finally:
+                self._align_end(pend)
         return wav.to(self.dtype).view(1, 1, -1)
+
+    last_alignment = None   # [(ends np.int32 [n_phones], score float), ...] of the last call that took `align`, in span order
+
+    def _align_begin(self, spans):
+        """Make `spans` [(segment, code0, n_codes, phone0, n_phones), ...] pending for the next engine decode
+        (gsv_vits_set_align): span r covers frames 2 code0 .. 2 (code0 + n_codes) of its segment's 50-per-second pre-speed axis
+        and the given phones, in the segment's own indices."""
+        n = len(spans)
+        tab = (_lib.AlignSegSpan * n)(*[_lib.AlignSegSpan(*[int(v) for v in sp]) for sp in spans])
+        counts = [int(sp[4]) for sp in spans]
+        ends = torch.zeros(max(sum(counts), 1), dtype=torch.int32, device=self.device)
+        score = torch.zeros(n, dtype=torch.float32, device=self.device)
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))     # the two fills above
+        _lib.check(_lib.lib().gsv_vits_set_align(self._h, tab, n, ends.data_ptr(), score.data_ptr()), "gsv_vits_set_align")
+        return counts, ends, score
+
+    def _align_end(self, pend):
+        """after the engine call: wait for its stream (as every decode does), drop a table the call did not reach, and with a
+        table fetch the ends and scores that travelled with the audio into `last_alignment`"""
+        try:
+            self.stream.synchronize()
+        finally:
+            if pend is not None:
+                _lib.lib().gsv_vits_set_align(self._h, None, 0, None, None)
+        if pend is None:
+            return
+        counts, ends, score = pend
+        e, sc = ends.cpu().numpy(), score.cpu().numpy()
+        out, o = [], 0
+        for c, v in zip(counts, sc):
+            out.append((e[o:o + c].copy(), float(v)))
+            o += c
+        self.last_alignment = out
 
     def segment_gap(self) -> int:
         """Zero frames decode_segments lays between neighbouring segments (gsv_vits_segment_gap): n segments of T_s codes
@@ -176,7 +216,7 @@ class SynthesizerTrn:
     @torch.no_grad()
     def decode_segments(self, codes_list, text_list, voices, seeds, noise_scale: float = 0.5,
                         noise: Optional[Sequence[torch.Tensor]] = None,
-                        speeds: Optional[Sequence[float]] = None) -> List[torch.Tensor]:
+                        speeds: Optional[Sequence[float]] = None, align=None) -> List[torch.Tensor]:
         """Segmented decode: segment s = (codes_list[s] [1,1,T_s], text_list[s] [1,L_s], voices[s], seeds[s]) in one
         pass of enc_p, flow and generator (gsv_vits_decode_segments).  A voice is (refer, sv_emb) as taken by `decode`
         (sv_emb None except for v2Pro / v2ProPlus); distinct voices are stored into slots once per call.  `noise`
@@ -184,7 +224,9 @@ class SynthesizerTrn:
         segment, what `decode(codes_list[s], text_list[s], *voices[s], noise_scale, seed=seeds[s])` returns.
         `speeds` (optional, one finite positive value per segment; gsv_vits_decode_segments_speed): segment s is decoded at
         `speed=speeds[s]`, so it has F_s = 2T_s frames at speed 1 and int(2T_s / speeds[s]) + 1 otherwise; its noise is
-        [inter, F_s] and its waveform [1, 1, F_s * prod(upsample_rates)]."""
+        [inter, F_s] and its waveform [1, 1, F_s * prod(upsample_rates)].
+        `align` (optional): one list per segment of spans (code0, n_codes, phone0, n_phones) (True = the whole segment, None /
+        empty = none); `self.last_alignment` receives them in segment, then span order.  The waveforms do not depend on it."""
         if not self._loaded:
             raise RuntimeError("load_state_dict() first")
         n = len(codes_list)
@@ -230,16 +272,27 @@ class SynthesizerTrn:
             sd = (C.c_uint64 * n)(*[int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds])
             self.stream.wait_stream(torch.cuda.current_stream(self.device))
             nzp = nz.data_ptr() if nz is not None else None
-            if speeds is None:
-                _lib.check(_lib.lib().gsv_vits_decode_segments(self._h, n, cd.data_ptr(), cl, tx.data_ptr(), pl, vs, sd, nzp,
-                                                               float(noise_scale), wav.data_ptr(),
-                                                               C.c_void_p(self.stream.cuda_stream)), "gsv_vits_decode_segments")
-            else:
-                _lib.check(_lib.lib().gsv_vits_decode_segments_speed(self._h, n, cd.data_ptr(), cl, tx.data_ptr(), pl, vs, sd,
-                                                                     (C.c_double * n)(*speeds), nzp, float(noise_scale),
-                                                                     wav.data_ptr(), C.c_void_p(self.stream.cuda_stream)),
-                           "gsv_vits_decode_segments_speed")
-            self.stream.synchronize()
+            pend = None
+            if align is not None:
+                if len(align) != n:
+                    raise ValueError("decode_segments: one list of alignment spans per segment")
+                spans = [(g,) + tuple(a) for g, al in enumerate(align)
+                         for a in ([(0, T[g], 0, L[g])] if al is True else (al or []))]
+                pend = self._align_begin(spans) if spans else None
+                if not spans:
+                    self.last_alignment = []
+            try:
+                if speeds is None:
+                    _lib.check(_lib.lib().gsv_vits_decode_segments(self._h, n, cd.data_ptr(), cl, tx.data_ptr(), pl, vs, sd, nzp,
+                                                                   float(noise_scale), wav.data_ptr(),
+                                                                   C.c_void_p(self.stream.cuda_stream)), "gsv_vits_decode_segments")
+                else:
+                    _lib.check(_lib.lib().gsv_vits_decode_segments_speed(self._h, n, cd.data_ptr(), cl, tx.data_ptr(), pl, vs, sd,
+                                                                         (C.c_double * n)(*speeds), nzp, float(noise_scale),
+                                                                         wav.data_ptr(), C.c_void_p(self.stream.cuda_stream)),
+                               "gsv_vits_decode_segments_speed")
+            finally:
+                self._align_end(pend)
         out = wav.to(self.dtype)
         return [p.view(1, 1, -1) for p in torch.split(out, [f * up for f in Fs])]
 
@@ -331,7 +384,7 @@ class SynthesizerTrnV3(SynthesizerTrn):
         raise NotImplementedError("v3/v4 models synthesise through decode_encp + cfm.inference + a vocoder (TTS.py:1431-1494)")
 
     @torch.no_grad()
-    def decode_encp(self, codes: torch.Tensor, text: torch.Tensor, refer, ge=None, speed: float = 1):
+    def decode_encp(self, codes: torch.Tensor, text: torch.Tensor, refer, ge=None, speed: float = 1, align=None):
         """reference models.py:1243-1267: codes [1,1,T], text [1,L], refer [1,bins,Tr] -> (fea [1,512,F], ge).
         `ge` is the handle of the reference audio whose style vector is resident in the engine: pass the value a
         previous call returned (with the same `refer`) to skip recomputing it, exactly like the reference."""
@@ -351,9 +404,15 @@ class SynthesizerTrnV3(SynthesizerTrn):
             tx = text.reshape(-1).to(self.device, torch.int32).contiguous()
             fea = torch.empty(512, F_, dtype=torch.float32, device=self.device)
             self.stream.wait_stream(torch.cuda.current_stream(self.device))
-            _lib.check(l.gsv_vits_decode_encp(self._h, cd.data_ptr(), T, tx.data_ptr(), L, float(speed), fea.data_ptr(),
-                                              C.c_void_p(self.stream.cuda_stream)), "gsv_vits_decode_encp")
-            self.stream.synchronize()
+            # `align`: as in `decode`; the features do not depend on it
+            pend = self._align_begin([(0,) + tuple(a) for a in ([(0, T, 0, L)] if align is True else align)]) if align else None
+            if align is not None and not align:      # asked for, with no span: no stale result of an earlier call
+                self.last_alignment = []
+            try:
+                _lib.check(l.gsv_vits_decode_encp(self._h, cd.data_ptr(), T, tx.data_ptr(), L, float(speed), fea.data_ptr(),
+                                                  C.c_void_p(self.stream.cuda_stream)), "gsv_vits_decode_encp")
+            finally:
+                self._align_end(pend)
         return fea.to(self.dtype).unsqueeze(0), self._ref_key
 
 

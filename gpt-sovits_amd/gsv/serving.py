@@ -711,7 +711,8 @@ class Scheduler:
         plans = {}
         for t, req in self._resolve(taken, out):
             try:
-                plans[t] = (req, self.tts._plan_request(req, **({"fragments": True} if req.get("return_fragment") else {})))
+                plans[t] = (req, self.tts._plan_request(req, **({"fragments": True} if req.get("return_fragment") else {}),
+                                                        **({} if req.get("timestamps") in (None, False) else {"timestamps": True})))
             except Exception as e:                                      # noqa: BLE001 -- the request's own result
                 out.append((t, e))
         for t, (req, pl) in sorted(plans.items()):                      # arrival order
@@ -864,9 +865,7 @@ class Scheduler:
             try:
                 if pl["frags"][b] is None or any(f is None for f in pl["frags"][b]):
                     with tts._with_prompt_cache(dict(pl["voice"])) as voice:
-                        pred, idx_list = pl["kept"][b]
-                        pl["frags"][b] = tts._synthesize_batch(pl["data"][b], pred, pl["preds"][b], idx_list, b, pl["actual_seed"], o,
-                                                               tts._voice_refer(voice), have=pl["frags"][b])
+                        tts._synthesize_fold(pl, b, tts._voice_refer(voice))
                 if o["super_sampling"]:
                     tts._wait_stream()
                     got[(t, b)] = tts.audio_postprocess([pl["frags"][b]], tts._output_sr(), None, o["speed_factor"], False,
@@ -900,6 +899,13 @@ class Scheduler:
         emitted = [f for f in due if f[0] in self._requests]
         for t, b in emitted:
             pl = self._requests[t]
+            if "timestamps" in pl["opts"]:      # speech marks of the fragment, as run() yields them: times
+                from .timestamps import build_marks       # relative to the fragment, "offset" = its start in the request's stream
+                sents, sr = tts._fold_sentences(pl, b), tts._output_sr()
+                gap = int(tts.configs.sampling_rate * pl["opts"]["fragment_interval"])
+                off = pl.get("ts_offset", 0)
+                got[(t, b)] = tuple(got[(t, b)]) + ([dict(m, offset=off / sr) for m in build_marks(sents, sr, gap)],)
+                pl["ts_offset"] = off + sum(s["n_samples"] + gap for s in sents)
             pl["stream"].append(got[(t, b)])
             pl["frags"][b] = []                                         # the waveforms are delivered: the device memory goes
             self._frags.append((t, b, got[(t, b)]))
@@ -1200,7 +1206,11 @@ class Server:
                 for kind, request, fut in cmds:
                     if kind == "submit":
                         if fut.set_running_or_notify_cancel():
-                            self._futures[sched.submit(request)] = fut
+                            try:
+                                self._futures[sched.submit(request)] = fut
+                            except Exception as e:           # noqa: BLE001 -- refused at the door: its own result, nobody else's
+                                fut.fragments.put(e)
+                                fut.set_exception(e)
                     else:
                         for ticket, f in list(self._futures.items()):
                             if f is fut:

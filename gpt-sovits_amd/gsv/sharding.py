@@ -174,6 +174,9 @@ def refuse_output_format(segments: Optional[List[dict]]) -> None:
             if s.get(k) is not None:
                 raise ValueError(f"a sharded run does not take {k!r}: every rank would normalise its own piece of the audio "
                                  "(normalise the gathered audio, or run unsharded)")
+        if s.get("timestamps") not in (None, False):
+            raise ValueError("a sharded run does not take 'timestamps': its gather carries int16 fragments only, no speech "
+                             "marks (run unsharded)")
 
 
 class ShardedSynthesizer:

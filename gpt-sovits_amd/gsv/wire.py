@@ -96,6 +96,12 @@ def streaming_generator(tts_generator, media_type: str):
         yield pack_audio(BytesIO(), chunk, sr, media_type).getvalue()
 
 
+def parse_timestamps(v):
+    """the query-string form of the request key "timestamps": "", "0", "false", "none" are False, anything else is the mode as
+    given ("sentence", "phone"; another word is refused by the pipeline)"""
+    return False if str(v).strip().lower() in ("", "0", "false", "none") else str(v).strip().lower()
+
+
 def tts_handle(tts_pipeline, req: dict, server=None):
     """api_v2.py:300-373 without the web framework: -> (status code, media type, payload); payload is bytes, an iterator of
     bytes (streaming_mode) or, on failure, the reference's error dict.
@@ -108,6 +114,10 @@ def tts_handle(tts_pipeline, req: dict, server=None):
     media_type = req.get("media_type", "wav")
     if req.get("encoding") in ("mulaw", "alaw") and media_type in ("wav", "aac", "ogg"):     # before any stage runs
         return 400, "application/json", {"message": "tts failed", "Exception": G711_NEEDS_RAW % media_type}
+    marked = req.get("timestamps") not in (None, False)
+    if marked and (streaming_mode or req.get("return_fragment", False)):                             # before any stage runs
+        return 400, "application/json", {"message": "tts failed", "Exception": "\"timestamps\" comes with the whole utterance in one "
+                                         "JSON answer: not with streaming_mode / return_fragment (DESIGN.md section 4w)"}
     if streaming_mode or req.get("return_fragment", False):
         req = dict(req, return_fragment=True)
     try:
@@ -120,6 +130,13 @@ def tts_handle(tts_pipeline, req: dict, server=None):
             gen = tts_pipeline.run(req)
         if streaming_mode:
             return 200, f"audio/{media_type}", streaming_generator(gen, media_type)
+        if marked:      # speech marks: one JSON answer, the packed media as base64 beside them
+            import base64
+            from .timestamps import to_json
+            sr, audio, marks = next(gen)
+            packed = pack_audio(BytesIO(), audio, sr, media_type).getvalue()
+            return 200, "application/json", {"audio": base64.b64encode(packed).decode("ascii"), "media_type": media_type,
+                                             "sample_rate": int(sr), "timestamps": to_json(marks)}
         sr, audio = next(gen)
         return 200, f"audio/{media_type}", pack_audio(BytesIO(), audio, sr, media_type).getvalue()
     except Exception as e:                                              # noqa: BLE001 -- the reference answers 400 with the message
@@ -159,6 +176,8 @@ def create_app(tts_pipeline, server=None):
         for k in ("split_bucket", "streaming_mode", "parallel_infer", "super_sampling"):
             if k in q:
                 q[k] = str(q[k]).lower() in ("1", "true")
+        if "timestamps" in q:
+            q["timestamps"] = parse_timestamps(q["timestamps"])
         return await respond(q)
 
     async def tts_post(request):

@@ -280,6 +280,21 @@ int gsv_vits_extract_latent(gsv_vits_t* h, const float* ssl, int T50, int32_t* c
  * into out [dev] fp32 in channels-first [C][T] order; returns element count via *numel. */
 int gsv_vits_debug_tensor(gsv_vits_t* h, const char* name, float* out, int64_t cap, int64_t* numel,
                           gsv_stream_t stream);
+/* the same for the MRTE attention's operands of the last enc_p: "m_q" [512][2T] and "m_kv" [1024][L] (keys = channels 0..511);
+ * after a segmented decode, the padded rows of its layout. */
+/* Phoneme alignment (csrc/align.hip, gsv_op_align below): spans [host] [n], each a run of codes and a run of phones of one
+ * segment in the segment's own packed indices (segment = 0 for gsv_vits_decode / _decode_encp); its frames are
+ * 2 * code0 .. 2 * (code0 + n_codes) of the 50-per-second pre-speed axis.  The table is pending for the NEXT gsv_vits_decode /
+ * gsv_vits_decode_segments[_speed] / gsv_vits_decode_encp on the handle and consumed by it: that call issues the two alignment
+ * launches on its stream right after the MRTE attention, on the attention's own q and k, and writes ends [dev] int32
+ * [sum n_phones] (span r's phonemes after those of the spans in front of it; frames counted from the span's first frame) and
+ * score [dev] fp32 [n].  A span outside its segment, or two spans that share a phoneme, make that call fail with GSV_ERR_ARG
+ * before it launches anything.  NULL spans or n = 0 clears a pending table.  Without a pending table a decode issues exactly
+ * the launches it issued before, and a pending table changes no value the decode computes. */
+typedef struct gsv_align_seg_span {
+  int32_t segment, code0, n_codes, phone0, n_phones;
+} gsv_align_seg_span_t;
+int gsv_vits_set_align(gsv_vits_t* h, const gsv_align_seg_span_t* spans, int n, int32_t* ends, float* score);
 /* v3 / v4 (H14, SynthesizerTrnV3.decode_encp, module/models.py:1243-1267): codes / phones as in gsv_vits_decode ->
  * fea [dev] fp32 [512][F] (channels-first, what the reference returns; ge comes from gsv_vits_set_refer).
  * F = gsv_vits_encp_frames(h, T, speed) = floor(frames_after_speed * (1.875 | 2)); returns -1 on bad arguments. */
@@ -869,6 +884,38 @@ int gsv_op_sample_rows(const float* logits, int B, int vocab, int vocab_eff, con
  * out [dev] fp32 [B] = log softmax(logits[b][:vocab_eff])[tokens[b]], -inf for a token outside [0, vocab_eff) */
 int gsv_op_token_logprob(const float* logits, int B, int vocab, int vocab_eff, const int32_t* tokens, float* out,
                          gsv_stream_t stream);
+
+/* Monotonic alignment of a text-to-frame attention (csrc/align.hip).  A call carries n spans; span i is the rectangle of frame
+ * rows [f0, f0 + nf) of q [.][ldq] and phoneme rows [l0, l0 + nl) of k [.][ldk], both [dev] in `dtype`, `heads` heads of
+ * `head_dim` columns each from column 0.  spans [dev] [n]; spans are independent: a span's outputs do not depend on what else
+ * the call holds.
+ *   gsv_op_align_logp: lp[t][j] = logf(max(1e-30, mean_h softmax_j(scale * <q_h[t], k_h[j]>))), fp32, the softmax over the
+ *     span's own nl phonemes, written [nf][nl] at the span's place in the workspace.
+ *   gsv_op_align_path: VITS' maximum_path over lp, V in fp64: V[0][0] = lp[0][0], V[t][j] = lp[t][j] + max(V[t-1][j],
+ *     V[t-1][j-1]), j <= t; the backtrack from (nf - 1, nl - 1) steps to j - 1 iff j > 0 && (j == t || V[t-1][j] < V[t-1][j-1])
+ *     (a tie stays).  ends [dev] int32: ends[out0 + j] = the exclusive end frame of phoneme j inside the span (its start is the
+ *     previous end, every phoneme gets >= 1 frame); score [dev] fp32 [n]: (float)(V[nf-1][nl-1] / nf).  A span with nf < nl or
+ *     nl > 1024 is not searched: ends[out0 + j] = ((j + 1) * nf) / nl and score = -inf; nf <= 0 or nl <= 0 writes no ends and
+ *     score = -inf.
+ *   gsv_op_align: both launches.
+ * Workspace [dev], 16-byte aligned: gsv_op_align_workspace(n, spans [host], offsets) returns its size in bytes (negative: bad
+ * table) and, when offsets is not NULL, the byte offset of each span's lp (offsets [host] [n]); a searched span takes
+ * nf * nl floats rounded up to 16 bytes, plus its decision bits when they exceed 32 KB, an unsearched one nothing.  A span whose
+ * region would pass workspace_bytes takes the fallback.  Nothing is allocated and nothing waits for the device. */
+typedef struct gsv_align_span {
+  int32_t f0, nf; /* frame rows of q */
+  int32_t l0, nl; /* phoneme rows of k */
+  int32_t out0;   /* first element of `ends` the span writes */
+  int32_t reserved;
+} gsv_align_span_t;
+long long gsv_op_align_workspace(int n_spans, const gsv_align_span_t* spans, int64_t* offsets);
+int gsv_op_align_logp(const void* q, int ldq, const void* k, int ldk, int dtype, int heads, int head_dim, float scale,
+                      const gsv_align_span_t* spans, int n_spans, void* workspace, long long workspace_bytes, gsv_stream_t stream);
+int gsv_op_align_path(const gsv_align_span_t* spans, int n_spans, void* workspace, long long workspace_bytes, int32_t* ends,
+                      float* score, gsv_stream_t stream);
+int gsv_op_align(const void* q, int ldq, const void* k, int ldk, int dtype, int heads, int head_dim, float scale,
+                 const gsv_align_span_t* spans, int n_spans, void* workspace, long long workspace_bytes, int32_t* ends, float* score,
+                 gsv_stream_t stream);
 
 #ifdef __cplusplus
 }
